@@ -2,7 +2,7 @@
 """bench.py -- measures BASELINE.json's metric (distinct k-mers counted / sec,
 whole job) for the `meryl count` hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--dump-outputs DIR] [--full]
 
 A "step" is one full pass of the hot path (per-file histogram -> pack+scatter ->
 per-file radix grouping passes on the top bits -> LDS hash-count of every sub-bucket
@@ -16,7 +16,10 @@ that grows with N); the 64*N top-bit buckets are cut into contiguous per-rank ra
 and k-mers are routed to their owner in point-to-point waves over RCCL/xGMI while
 the owner counts the buckets that have arrived.
 
-Prints ONE JSON line (rank 0), at every N:
+Prints ONE JSON line (rank 0), at every N.  A plain run sets up, warms up, times the K steps and prints the headline
+(`value`, `ms_per_step`, `config`, the stage times of the timed steps).  With --dump-outputs DIR it first writes what the last
+timed step computed (the session's result: a fixed, seeded sample of the distinct k-mers and their counts, the block starts, the
+totals) as DIR/<name>.npy in float64, one GPU only.  --full adds every object below to the same line:
   roofline      the kernel family with the largest WALL-CLOCK share of the step (computed from the stage clocks, not asserted: the
                 first grouping pass on the judged workload) priced on its algorithmic bytes and its own launch durations (HIP
                 events on the stream it is launched on); the other families -- second pass, sub-bucket count, partition,
@@ -512,6 +515,49 @@ def roofline_object(prof_acc, ms_per_step, steps, reads, single, where):
     return out
 
 
+DUMP_SAMPLE = 1 << 20               # positions of the distinct k-mers written by --dump-outputs (8 MB per array in float64)
+DUMP_BLOCK_SAMPLE = 1 << 21         # block starts beyond this are sampled too: every dump stays under 64 MB
+DUMP_SEED = 7
+
+
+def dump_sample_index(n, m, seed=DUMP_SEED):
+    """Ascending positions of an n-long output to dump: all of them when n <= m, else a fixed, seeded sample of at most m."""
+    import numpy as np
+    if n <= m:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(seed).integers(0, n, size=m, dtype=np.int64))
+
+
+def dump_outputs(path, sess):
+    """--dump-outputs: the session's result after the last timed step, what a caller of the path receives -- the distinct
+    k-mers ascending and their counts (mgc_copy_result_device), the block starts of the database layout (mgc_copy_result) and
+    the totals (mgc_get_result_info) -- as float64 .npy files.  keys / counts hold the positions in sample_index.npy; every
+    value is an integer below 2^53 (k = 21: 42-bit k-mers), so float64 holds it exactly."""
+    import ctypes
+    import numpy as np
+    import torch
+    from meryl_amd import capi
+    assert 2 * K <= 53, "k-mers beyond 53 bits do not fit a float64 exactly"
+    os.makedirs(path, exist_ok=True)
+    info = sess.info()
+    out = {"totals": np.array([info.n_instances, info.n_distinct]), "file_instances": np.array(list(info.file_instances))}
+    idx = dump_sample_index(info.n_distinct, DUMP_SAMPLE)
+    keys, cnts = sess.result_device()
+    at = torch.from_numpy(idx).to(keys.device)
+    out["sample_index"] = idx
+    out["keys"] = keys[at].cpu().numpy()
+    out["counts"] = (cnts[at].to(torch.int64) & 0xFFFFFFFF).cpu().numpy()
+    del keys, cnts, at
+    bstart = np.zeros(info.n_prefix + 1, dtype=np.uint64)
+    capi.check(capi.lib().mgc_copy_result(sess._h, None, None, None, bstart.ctypes.data_as(ctypes.c_void_p)), "mgc_copy_result", sess._h)
+    if bstart.size > DUMP_BLOCK_SAMPLE:
+        out["block_start_index"] = dump_sample_index(bstart.size, DUMP_BLOCK_SAMPLE)
+        bstart = bstart[out["block_start_index"]]
+    out["block_start"] = bstart
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -524,7 +570,14 @@ def main():
     ap.add_argument("--no-check", action="store_true", help="skip the untimed result check")
     ap.add_argument("--no-db", action="store_true", help="skip the untimed database write (N > 1: and the node-count comparison)")
     ap.add_argument("--cpu-sample", action="store_true", help="CPU leg over the bounded sample (three thread counts) instead of the whole workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's result as DIR/<name>.npy (float64; one GPU only)")
+    ap.add_argument("--full", action="store_true", help="also run the untimed legs: roofline, check, db_write, e2e, e2e_compressed, cpu_baseline "
+                                                        "(the --no-* options leave some of them out)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus > 1 or os.environ.get("MGC_BENCH_FORCE_SHARDED", "0") == "1"):
+        ap.error("--dump-outputs writes the result of the one-GPU session: not with --gpus > 1 or MGC_BENCH_FORCE_SHARDED=1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -643,6 +696,8 @@ def main():
     if single:
         sess = count.Session(cfg, dev_index)
         sess.push_bases_device(bases)
+        # on in plain runs too: every earlier line timed the step with the session's per-launch events, and ms_per_step
+        # stays comparable with them
         sess.set_profiling(True)
 
         def step(timed):
@@ -708,8 +763,10 @@ def main():
         step(True)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sess)
     stage_s = None
-    if dist is not None:
+    if dist is not None and args.full:
         os.environ["MGC_SHARD_PROFILE"] = "1"
         stage_db = {}
         step(False, profile=True)        # collective: every rank runs it; rank 0's pass timings feed the roofline object
@@ -764,7 +821,7 @@ def main():
         return ok
 
     # ---- check (collective at N > 1) ----
-    if not args.no_check and leg_ok_all("check", 10 if world == 1 else 30):
+    if args.full and not args.no_check and leg_ok_all("check", 10 if world == 1 else 30):
         t_leg = time.perf_counter()
         try:
             if single:
@@ -787,7 +844,7 @@ def main():
     result.pop("uniq", None); result.pop("cnts", None)
 
     # ---- the database (untimed) ----
-    if not args.no_db and leg_ok_all("db_write", 10 if world == 1 else 60):
+    if args.full and not args.no_db and leg_ok_all("db_write", 10 if world == 1 else 60):
         t_leg = time.perf_counter()
         import shutil
         try:
@@ -894,10 +951,10 @@ def main():
             line["stage_ms_per_step"] = {"partition": npf["partition_s"] * 1e3, "exchange+owner count": npf["exchange_count_s"] * 1e3,
                                          "files": npf["close_s"] * 1e3, "stitch": npf["merge_parts_s"] * 1e3}
         rf = roofline_object(prof_acc, ms_per_step, args.steps, reads, single,
-                             "over the timed steps" if single else "rank 0's owner-side count in one extra untimed step")
+                             "over the timed steps" if single else "rank 0's owner-side count in one extra untimed step") if args.full else None
         if rf:
             line["roofline"] = rf
-        elif node_fallback:
+        elif node_fallback and args.full:
             # mgc_count_node owns its sessions: the kernels' launch durations are measured in ONE session counting rank 0's
             # reads on the same device (the same kernels on the same per-GPU workload)
             try:
@@ -940,7 +997,7 @@ def main():
     count.release_cached_sessions()
     torch.cuda.empty_cache()
     if rank == 0:
-        if not args.no_e2e and bases is not None and leg_ok("e2e", 45 if world == 1 else 60 + 20 * world):
+        if args.full and not args.no_e2e and bases is not None and leg_ok("e2e", 45 if world == 1 else 60 + 20 * world):
             t_leg = time.perf_counter()
             try:
                 line["e2e"] = e2e_run(bases, min(reads, bases.numel() // (READ_LEN + 1)), threads, gpus=1 if one_device else world)
@@ -952,7 +1009,7 @@ def main():
                 line["e2e"] = {"error": str(e)[:300]}
             legs_s["e2e"] = time.perf_counter() - t_leg
         # ... and compressed inputs (one gzip stream; BGZF): a tenth of the reads -- the single stream inflates at a few hundred MB/s
-        if not args.no_e2e and bases is not None and world == 1 and leg_ok("e2e_compressed", 60):
+        if args.full and not args.no_e2e and bases is not None and world == 1 and leg_ok("e2e_compressed", 60):
             t_leg = time.perf_counter()
             try:
                 zreads = max(1000, min(reads, bases.numel() // (READ_LEN + 1)) // 10)
@@ -962,19 +1019,20 @@ def main():
             legs_s["e2e_compressed"] = time.perf_counter() - t_leg
         # the CPU leg: rank 0 at N = 1 only (the harness's rule); the whole workload at the best thread count when the budget
         # allows its ~150-170 s, else the bounded sample
-        if not args.no_cpu_baseline and bases is not None and world == 1:
+        if args.full and not args.no_cpu_baseline and bases is not None and world == 1:
             sample = min(args.cpu_sample_reads, reads, bases.numel() // (READ_LEN + 1))
             whole = (not args.cpu_sample) and leg_ok("cpu_baseline.whole_workload", 175.0 * reads / DEFAULT_READS)
             if whole or leg_ok("cpu_baseline.sample", 100.0 * sample / 14_000_000):
                 t_leg = time.perf_counter()
                 line["cpu_baseline"] = cpu_baseline(sample, os.cpu_count() or 1, bases, whole=whole)
                 legs_s["cpu_baseline"] = time.perf_counter() - t_leg
-        elif not args.no_cpu_baseline and world > 1:
+        elif args.full and not args.no_cpu_baseline and world > 1:
             skipped["cpu_baseline"] = "reported at N = 1 only"
         legs_s["total"] = time.perf_counter() - t_begin
         line["legs_s"] = {k: round(v, 3) for k, v in legs_s.items()}
-        line["legs_skipped"] = skipped
-        line["legs_budget_s"] = budget_s
+        if args.full:
+            line["legs_skipped"] = skipped
+            line["legs_budget_s"] = budget_s
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)
         print(json.dumps(line), flush=True)

@@ -4,7 +4,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/${TAG:-ab}; mkdir -p $O
-ARGS=${BENCH_ARGS:---steps 8 --warmup 2 --no-cpu-baseline --no-e2e --no-db --no-check}
+ARGS=${BENCH_ARGS:---full --steps 8 --warmup 2 --no-cpu-baseline --no-e2e --no-db --no-check}
 IFS=';' read -ra VARS <<< "${AB}"
 for r in $(seq 1 ${ROUNDS:-3}); do
   for v in "${VARS[@]}"; do

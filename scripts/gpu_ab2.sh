@@ -5,7 +5,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 ROOT=$PWD
 O=$ROOT/gpurun_out/${TAG:-ab2}; mkdir -p $O
-ARGS=${BENCH_ARGS:---steps 8 --warmup 2 --no-cpu-baseline --no-e2e --no-db --no-check}
+ARGS=${BENCH_ARGS:---full --steps 8 --warmup 2 --no-cpu-baseline --no-e2e --no-db --no-check}
 for r in $(seq 1 ${ROUNDS:-3}); do
   for vv in ${OTHER:-head} new ${NEW_VARIANTS:-}; do     # NEW_VARIANTS="name:ENV=1,ENV2=2 ..." run the working tree under that environment
     v=${vv%%:*}; envs=""; [ "$vv" != "$v" ] && envs=${vv#*:}

@@ -8,7 +8,7 @@ OUT=gpurun_out/${TAG}_final
 mkdir -p $OUT
 export TMPDIR=/tmp
 echo "== default bench (the driver's command)"
-timeout 1500 python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err
+timeout 1500 python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err
 echo "bench exit $?"; cut -c1-2500 $OUT/bench_full.json; tail -3 $OUT/bench_full.err
 echo "== rocprofv3 kernel stats of the same workload"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o full -- python bench.py --no-cpu-baseline --no-e2e --no-check --no-db > $OUT/prof_bench.json 2> $OUT/prof_bench.err

@@ -11,7 +11,7 @@ hipcc --offload-arch=gfx950 -O3 -o /tmp/calib scripts/ubench/calib.hip 2> $OUT/c
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/calib_$c -o c -- /tmp/calib > $OUT/calib_$c.log 2>&1
   echo "calib $c exit $?"
-  timeout 900 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/bench_$c -o b -- python bench.py --reads ${READS:-66666667} --steps 1 --warmup 0 --no-cpu-baseline > $OUT/bench_$c.json 2> $OUT/bench_$c.err
+  timeout 900 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/bench_$c -o b -- python bench.py --full --reads ${READS:-66666667} --steps 1 --warmup 0 --no-cpu-baseline > $OUT/bench_$c.json 2> $OUT/bench_$c.err
   echo "bench $c exit $?"
 done
 python - <<'PY'

@@ -2,7 +2,7 @@
 # One gpurun call, parameterised (replaces the per-experiment scripts of round 2):
 #   TAG=r03a TESTS="tests/test_gpu_parity.py -k bitmap" BENCH="default:;nobitmap:MGC_FINISH_BITMAP=0" bash scripts/gpu_run.sh
 #   TESTS   pytest arguments (empty: no tests), TESTS_K its -k expression;  BENCH  ';'-separated  name:ENV=VAL,ENV=VAL  bench.py variants
-#   BENCH_ARGS  bench.py flags of the variants (default: --steps 5 --warmup 1 --no-cpu-baseline --no-e2e)
+#   BENCH_ARGS  bench.py flags of the variants (default: --full --steps 5 --warmup 1 --no-cpu-baseline --no-e2e)
 #   PROF=1  rocprofv3 --kernel-trace --stats of the default bench;  EXTRA  a shell command run at the end
 # Everything is wrapped in `timeout` so a wedged kernel cannot hold the box.  Output: gpurun_out/$TAG/
 set -u
@@ -18,7 +18,7 @@ if [ -n "${TESTS:-}" ]; then
   echo "pytest exit $?" | tee -a $OUT/pytest.log
   tail -${TEST_TAIL:-15} $OUT/pytest.log
 fi
-BENCH_ARGS=${BENCH_ARGS:---steps 5 --warmup 1 --no-cpu-baseline --no-e2e}
+BENCH_ARGS=${BENCH_ARGS:---full --steps 5 --warmup 1 --no-cpu-baseline --no-e2e}
 IFS=';' read -ra VARS <<< "${BENCH:-}"
 for v in "${VARS[@]}"; do
   [ -z "$v" ] && continue
@@ -41,7 +41,7 @@ PY
 done
 if [ "${PROF:-0}" = "1" ]; then
   echo "== rocprofv3 kernel stats"
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o full -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --no-check > $OUT/prof_bench.json 2> $OUT/prof_bench.err
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o full -- python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --no-check > $OUT/prof_bench.json 2> $OUT/prof_bench.err
   echo "rocprof exit $?"
   cp $(find $OUT/prof -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv 2>/dev/null; head -14 $OUT/kernel_stats.csv | cut -c1-200
   rm -rf $OUT/prof

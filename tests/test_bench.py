@@ -23,7 +23,7 @@ def _run(args, env_extra=None, timeout=900):
 
 
 def test_bench_single_gpu_line_is_complete(native_lib):
-    d = _run(["--reads", "2000000", "--steps", "2", "--warmup", "1", "--cpu-sample-reads", "200000"])
+    d = _run(["--full", "--reads", "2000000", "--steps", "2", "--warmup", "1", "--cpu-sample-reads", "200000"])
     assert d["n_gpus"] == 1 and d["unit"] == "distinct k-mers/s" and d["value"] > 0 and d["higher_is_better"] is True
     assert d["check"]["ok"] is True
     rf = d["roofline"]
@@ -51,7 +51,7 @@ def test_bench_single_gpu_line_is_complete(native_lib):
 
 def test_bench_budget_guard_skips_legs_and_says_so(native_lib):
     # a budget the untimed tail cannot meet: the timed steps and the roofline still come, the legs are named as skipped
-    d = _run(["--reads", "2000000", "--steps", "2", "--warmup", "1"], {"MGC_BENCH_BUDGET_S": "1"})
+    d = _run(["--full", "--reads", "2000000", "--steps", "2", "--warmup", "1"], {"MGC_BENCH_BUDGET_S": "1"})
     assert d["value"] > 0 and 0 < d["roofline"]["frac"] < 1
     for leg in ("check", "db_write", "e2e", "cpu_baseline.whole_workload", "cpu_baseline.sample"):
         assert leg in d["legs_skipped"] and "budget" in d["legs_skipped"][leg]
@@ -61,7 +61,7 @@ def test_bench_budget_guard_skips_legs_and_says_so(native_lib):
 def test_bench_two_ranks_line_is_complete(native_lib):
     import torch
     one = torch.cuda.device_count() < 2
-    d = _run(["--gpus", "2", "--reads", "1500000", "--steps", "2", "--warmup", "1", "--cpu-sample-reads", "200000"],
+    d = _run(["--full", "--gpus", "2", "--reads", "1500000", "--steps", "2", "--warmup", "1", "--cpu-sample-reads", "200000"],
              {"MGC_BENCH_ONE_DEVICE": "1"} if one else None)
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["scaling"] == "weak"
     assert d["check"]["ok"] is True
@@ -74,3 +74,39 @@ def test_bench_two_ranks_line_is_complete(native_lib):
         assert d["check"]["keys_ascending_across_rank_boundaries"] is True
         assert 0 < d["roofline"]["frac"] < 1 and "stage_ms_one_profiled_step" in d
     assert 0 < d["roofline"]["frac"] < 1 and d["e2e"]["wall_s"] > 0       # (the one-process fallback measures it in a single session)
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(native_lib, oracle_lib, tmp_path):
+    """Without --full the line holds the headline of the timed steps and no untimed leg; --dump-outputs writes the last timed
+    step's result in float64, identical from run to run and equal to the CPU oracle's count of the same seeded reads."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    reads = 20000
+    runs = []
+    for i in range(2):
+        out = tmp_path / ("run%d" % i)
+        d = _run(["--reads", str(reads), "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["n_gpus"] == 1
+        assert d["metric"] == "distinct k-mers counted/sec (whole node)" and d["unit"] == "distinct k-mers/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "u64"
+        assert not {"roofline", "check", "db_write", "e2e", "e2e_compressed", "cpu_baseline", "legs_skipped"} & set(d)
+        paths = sorted(out.glob("*.npy"))
+        files = {p.stem: np.load(p) for p in paths}
+        assert set(files) == {"keys", "counts", "sample_index", "block_start", "file_instances", "totals"}
+        assert all(a.dtype == np.float64 for a in files.values())
+        assert sum(p.stat().st_size for p in paths) <= 64 << 20
+        runs.append((d, files))
+    (d, f), (_, g) = runs
+    assert all(np.array_equal(f[n], g[n]) for n in f)
+    bases = oracle_lib.synth_reads(b.SEED, b.GENOME_LEN, 0, reads, b.READ_LEN, 5000, 100)
+    _, lo, cn, ni = oracle_lib.count_brute(bases.tobytes(), b.K)
+    assert f["totals"].tolist() == [ni, len(lo)] == [d["config"]["n_instances"], d["config"]["n_distinct"]]
+    assert f["file_instances"].sum() == ni
+    idx = f["sample_index"].astype(np.int64)
+    assert np.array_equal(idx, b.dump_sample_index(len(lo), b.DUMP_SAMPLE))
+    assert np.array_equal(f["keys"], lo[idx].astype(np.float64)) and np.array_equal(f["counts"], cn[idx].astype(np.float64))
+    prefixes = np.arange(f["block_start"].size, dtype=np.uint64) << np.uint64(2 * b.K - d["config"]["w_prefix"])
+    assert np.array_equal(f["block_start"], np.searchsorted(lo, prefixes).astype(np.float64))

@@ -89,3 +89,13 @@ def test_roofline_object_arithmetic():
     acc3 = dict(acc, by_pass=[{"ms": 0.0, "launches": 0, "keys": 0, "bytes": 0}] * 2, finish=None)
     r3 = b.roofline_object(acc3, ms_per_step, steps, 66666667, False, "over the timed steps")
     assert r3["launches"] == 384 and 0 < r3["frac"] < 1 and "measured" in r3
+
+
+def test_dump_sample_index_is_fixed_ascending_and_bounded():
+    """--dump-outputs samples a large output at fixed, seeded positions, so that two builds dump the same positions."""
+    import numpy as np
+    b = _bench()
+    assert np.array_equal(b.dump_sample_index(5, 8), np.arange(5))
+    a = b.dump_sample_index(10 ** 9, 1000)
+    assert np.array_equal(a, b.dump_sample_index(10 ** 9, 1000))
+    assert 0 < a.size <= 1000 and (np.diff(a) > 0).all() and a[0] >= 0 and a[-1] < 10 ** 9
