@@ -13,7 +13,8 @@
  * one index read and a binary search over the handful of k-mers that share the top bits: exact, no hashing, no extra
  * copy of the keys, 12 (20) B per k-mer + 8 B per index entry.  Queries come in batches that are already on the device:
  * explicit k-mers (mgc_lookup_values) or a base stream whose every window is looked up (mgc_lookup_stream,
- * mgc_lookup_existence -- the reference's -existence report).
+ * mgc_lookup_existence -- the reference's -existence report; mgc_lookup_positions / mgc_lookup_report -- its -bed, -bed-runs,
+ * -wig-count and -wig-depth reports, src/meryl-lookup/dump.C).
  */
 #ifndef MERYL_LOOKUP_H
 #define MERYL_LOOKUP_H
@@ -69,6 +70,47 @@ int mgc_lookup_stream(const mgc_lookup *t, const uint8_t *d_bases, uint64_t n_ba
  * them are in the table (d_found[s]).  d_seq_start has n_seq + 1 device entries. */
 int mgc_lookup_existence(const mgc_lookup *t, const uint8_t *d_bases, uint64_t n_bases, const uint64_t *d_seq_start,
                          uint64_t n_seq, uint64_t *d_total, uint64_t *d_found, void *stream);
+
+/* ---- position reports over several tables (src/meryl-lookup/dump.C) ------------------------------------------------------
+ * Windows are the reference's kmerIterator windows (k consecutive ACGT bases, either case; any other byte breaks them), f the
+ * forward k-mer of a window and r its reverse complement.  Every table must have the same k; at most 32 tables. */
+#define MGC_LOOKUP_MAX_TABLES 32
+
+#define MGC_LOOKUP_PRESENCE 0   /* bit t: table t holds f or r                                      (dump.C:109-135) */
+#define MGC_LOOKUP_COUNT    1   /* sum over the tables of value(f) + value(r), value(f) alone when f == r, in uint32 (it
+                                   wraps mod 2^32)                                                   (dump.C:139-164) */
+#define MGC_LOOKUP_DEPTH    2   /* at every BASE: the windows covering it that table 0 -- only table 0, as the code does; the
+                                   help text says "any database" -- holds (f or r)                   (dump.C:175-244) */
+
+/* Replaces processSequence (dump.C:89-245) for a whole base stream: d_out[i] (n_bases entries, device) is the `what` of the
+ * window starting at base i (PRESENCE, COUNT; 0 where no window starts) or of base i (DEPTH). */
+int mgc_lookup_positions(const mgc_lookup *const *tables, uint32_t n_tables, int what, const uint8_t *d_bases, uint64_t n_bases,
+                         uint32_t *d_out, void *stream);
+
+#define MGC_REPORT_BED       0  /* -bed      (dump.C:251-298): name \t p \t p+k [\t label] \n, p ascending, then table  */
+#define MGC_REPORT_BED_RUNS  1  /* -bed-runs (dump.C:302-364): name \t bgn \t E+k [\t label] \n per maximal run of a table's
+                                   flags, E = the first position AFTER the run (so the end is one past the last window's end:
+                                   the help text's example, meryl-lookup-help.C:68-69, shows one less); E ascending, then table */
+#define MGC_REPORT_WIG_COUNT 2  /* -wig-count (dump.C:368-405): variableStep chrom=name \n for every sequence, then
+                                   p+1 \t count \n where the COUNT is not 0                          */
+#define MGC_REPORT_WIG_DEPTH 3  /* -wig-depth: the same with the DEPTH                                */
+
+/* Receives the report's text in order; nonzero stops the report (mgc_lookup_report returns MGC_ESTATE). */
+typedef int (*mgc_lookup_write_cb)(const void *data, uint64_t n, void *user);
+
+/* Replaces dumpExistence / outputSequence (dump.C:409-441) with its outputBED / outputBEDruns / outputWIG: the exact text of
+ * `mode` for the n_seq sequences of the device base stream d_bases -- sequence s is bases [seq_start[s], seq_start[s+1]) with
+ * positions counted from 0 at seq_start[s]; seq_start (host, n_seq + 1 entries) starts at 0, never decreases and ends at
+ * n_bases, and every non-empty sequence ends with a byte that is not ACGT (the stream meryl-lookup builds: '.' after each).
+ * names[s] is the sequence's identifier; labels[t] (n_labels of them, may be 0) is appended to table t's -bed lines.  Labels
+ * are "present" when at least one is non-empty (meryl-lookup.C:27-31): without them only "found in any table" is kept
+ * (dump.C:127-131).  The WIG modes take no labels.  The text goes to write_cb as consecutive pieces of at most chunk_bytes;
+ * it is formatted on the device over ranges of positions, each piece copied back through pinned memory while the next one is
+ * formatted.  Device memory: O(n_bases) plus two staging buffers of chunk_bytes.  MGC_EINVAL: tables of different k, more
+ * than 32 tables, chunk_bytes shorter than the longest line the report can hold, a stream that breaks the rules above. */
+int mgc_lookup_report(const mgc_lookup *const *tables, uint32_t n_tables, int mode, const char *const *labels, uint32_t n_labels,
+                      const uint8_t *d_bases, uint64_t n_bases, const uint64_t *seq_start, const char *const *names, uint64_t n_seq,
+                      uint64_t chunk_bytes, mgc_lookup_write_cb write_cb, void *user);
 
 #ifdef __cplusplus
 }

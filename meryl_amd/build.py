@@ -92,7 +92,7 @@ LOOKUP_CLI = os.path.join(HERE, "bin", "meryl-lookup")
 
 
 def build_lookup_cli(force=False, verbose=False):
-    """`meryl-lookup -existence` (meryl_amd/bin/meryl-lookup): links the library and the system HIP runtime."""
+    """`meryl-lookup` (meryl_amd/bin/meryl-lookup: -existence and the position reports): links the library and the system HIP runtime."""
     src = os.path.join(CSRC, "meryl_lookup_main.cpp")
     if (not force and os.path.exists(LOOKUP_CLI) and os.path.getmtime(LOOKUP_CLI) >= os.path.getmtime(src)
             and os.path.getmtime(LOOKUP_CLI) >= os.path.getmtime(LIB)):

@@ -37,7 +37,7 @@ SYMBOLS = (
     "mgc_runs_open", "mgc_runs_add", "mgc_runs_write", "mgc_runs_get_profile", "mgc_runs_error", "mgc_runs_close", "mgc_get_runs_profile", "mgc_db_merge", "mgc_db_filter", "mgc_count_node", "mgc_count_node_batched", "mgc_count_node_staged", "mgc_node_plan",
     # include/meryl_lookup.h
     "mgc_lookup_load", "mgc_lookup_estimate", "mgc_lookup_from_device", "mgc_lookup_free", "mgc_lookup_get_info", "mgc_lookup_error",
-    "mgc_lookup_values", "mgc_lookup_stream", "mgc_lookup_existence",
+    "mgc_lookup_values", "mgc_lookup_stream", "mgc_lookup_existence", "mgc_lookup_positions", "mgc_lookup_report",
     # include/meryl_seq.h
     "msr_open", "msr_read_text", "msr_close", "msr_last_error", "msr_load_bases", "msr_load_stream", "msr_format", "msr_is_compressed", "msr_guess_number_of_kmers",
 )
@@ -201,6 +201,8 @@ class BlockHeader(ctypes.Structure):
 BLOCK_CB2 = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
                              ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                              ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64)
+# mgc_lookup_write_cb (include/meryl_lookup.h): (data, n, user) -> 0 to go on
+LOOKUP_WRITE_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
 BLOCK_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                             ctypes.POINTER(ctypes.c_uint32))
@@ -380,6 +382,9 @@ def lib():
     sig("mgc_lookup_values", i32, vp, vp, u64, vp, vp)
     sig("mgc_lookup_stream", i32, vp, vp, u64, vp, vp)
     sig("mgc_lookup_existence", i32, vp, vp, u64, vp, u64, vp, vp, vp)
+    sig("mgc_lookup_positions", i32, P(vp), u32, i32, vp, u64, vp, vp)
+    sig("mgc_lookup_report", i32, P(vp), u32, i32, P(ctypes.c_char_p), u32, vp, u64, P(u64), P(ctypes.c_char_p), u64, u64,
+        LOOKUP_WRITE_CB, vp)
     sig("msr_open", vp, ctypes.c_char_p)
     sig("msr_close", None, vp)
     sig("msr_read_text", ctypes.c_int64, vp, vp, u64)

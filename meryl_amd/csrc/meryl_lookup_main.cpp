@@ -1,12 +1,17 @@
-// meryl_lookup_main.cpp -- `meryl-lookup -existence`: for every sequence of a FASTA/FASTQ file, the number of k-mers it
-// holds and how many of them occur in a meryl database.
+// meryl_lookup_main.cpp -- `meryl-lookup`: the k-mers of the sequences of a FASTA/FASTQ file looked up in meryl databases.
 //
-// Keeps the reference tool's surface for that mode (src/meryl-lookup/meryl-lookup.C:150-200 options, existence.C:48-132):
+// Keeps the reference tool's surface (src/meryl-lookup/meryl-lookup.C:150-368 options and their checks) for these modes:
 //   meryl-lookup -existence -sequence <in.fa[.gz]> -mers <db.meryl> [<db2.meryl> ...] [-min v] [-max v] [-output out.tsv]
-// output per sequence:  name <TAB> kmersInSequence { <TAB> kmersInDB <TAB> kmersFound } per database   (existence.C:96-113)
-// The database is loaded into the device-resident exact lookup table (include/meryl_lookup.h = merylExactLookup); the
-// sequences go to the device as one base stream with '.' between them.  The other modes of the reference tool (-dump,
-// -include, -exclude, -bed, -wig) are not part of this build.
+//     per sequence:  name <TAB> kmersInSequence { <TAB> kmersInDB <TAB> kmersFound } per database   (existence.C:48-132)
+//   meryl-lookup -bed | -bed-runs -sequence <in.fa> -mers <db.meryl> [...] [-labels <l1> ...] [-min v] [-max v] [-output out.bed]
+//     one line per k-mer (per run of k-mers) found, per database when labels are given           (dump.C:251-364)
+//   meryl-lookup -wig-count | -wig-depth -sequence <in.fa> -mers <db.meryl> [...] [-min v] [-max v] [-output out.wig]
+//     per base: the summed value of the k-mer starting there / the depth of found k-mers of the FIRST database over it
+//                                                                                                  (dump.C:139-244, 368-405)
+// Every database is loaded into the device-resident exact lookup table (include/meryl_lookup.h = merylExactLookup); the
+// sequences go to the device as one base stream with '.' after each.  The position reports are formatted on the device
+// (mgc_lookup_report) and written as they come; -output is optional (stdout) and must not name a compressed file.  The
+// other modes of the reference tool (-dump, -include, -exclude) are not part of this build.
 #include "../../include/meryl_gpu_count.h"
 #include "../../include/meryl_lookup.h"
 #include "../../include/meryl_seq.h"
@@ -65,31 +70,75 @@ void parse_text(const std::string &text, Seqs &out) {
   }
   out.start.push_back(out.bases.size());
 }
+
+enum Op { OP_NONE, OP_EXISTENCE, OP_BED, OP_BED_RUNS, OP_WIG_COUNT, OP_WIG_DEPTH };
+
+const char *op_name(Op op) {                                  // toString(lookupOp), meryl-lookup.H:38-50 (-bed-runs is opBED)
+  switch (op) {
+    case OP_EXISTENCE: return "-existence";
+    case OP_BED: case OP_BED_RUNS: return "-bed";
+    case OP_WIG_COUNT: return "-wig-count";
+    case OP_WIG_DEPTH: return "-wig-depth";
+    default: return "(not supplied)";
+  }
+}
+
+bool compressed_name(const std::string &n) {
+  for (const char *suf : {".gz", ".bz2", ".xz", ".zst"})
+    if (n.size() > strlen(suf) && n.compare(n.size() - strlen(suf), std::string::npos, suf) == 0) return true;
+  return false;
+}
+
+int write_piece(const void *data, uint64_t n, void *user) {
+  return fwrite(data, 1, (size_t)n, static_cast<FILE *>(user)) == (size_t)n ? 0 : 1;
+}
 }  // namespace
 
 int main(int argc, char **argv) {
-  std::string seq_name, out_name;
-  std::vector<std::string> dbs;
+  std::string seq_name, seq_name2, out_name, out_name2;
+  std::vector<std::string> dbs, labels;
   uint64_t vmin = 0, vmax = UINT64_MAX;
-  bool existence = false, estimate = false;
+  Op op = OP_NONE;
+  bool estimate = false;
   double max_memory_gb = 0.0;                                 // -memory: 0 = whatever the device has
   for (int a = 1; a < argc; a++) {
     const std::string w = argv[a];
-    if (w == "-existence") existence = true;
-    else if (w == "-sequence" && a + 1 < argc) seq_name = argv[++a];
-    else if (w == "-output" && a + 1 < argc) out_name = argv[++a];
+    if (w == "-existence") op = OP_EXISTENCE;
+    else if (w == "-bed") op = OP_BED;
+    else if (w == "-bed-runs") op = OP_BED_RUNS;
+    else if (w == "-wig-count") op = OP_WIG_COUNT;
+    else if (w == "-wig-depth") op = OP_WIG_DEPTH;
+    else if (w == "-sequence" && a + 1 < argc) {              // meryl-lookup.C:160-164: an optional second input
+      seq_name = argv[++a];
+      if (a + 1 < argc && argv[a + 1][0] != '-') seq_name2 = argv[++a];
+    } else if (w == "-output" && a + 1 < argc) {              // :174-178
+      out_name = argv[++a];
+      if (a + 1 < argc && argv[a + 1][0] != '-') out_name2 = argv[++a];
+    }
     else if (w == "-min" && a + 1 < argc) vmin = strtoull(argv[++a], nullptr, 10);
     else if (w == "-max" && a + 1 < argc) vmax = strtoull(argv[++a], nullptr, 10);
     else if (w == "-threads" && a + 1 < argc) ++a;
     else if (w == "-memory" && a + 1 < argc) max_memory_gb = strtod(argv[++a], nullptr);
     else if (w == "-estimate") estimate = true;
     else if (w == "-mers") { while (a + 1 < argc && argv[a + 1][0] != '-') dbs.push_back(argv[++a]); }
-    else if (w == "-dump" || w == "-include" || w == "-exclude" || w == "-bed" || w == "-bed-runs" || w == "-wig-count" || w == "-wig-depth")
-      die("ERROR: mode '%s' is not part of this build (-existence only).", w.c_str());
+    else if (w == "-labels") { while (a + 1 < argc && argv[a + 1][0] != '-') labels.push_back(argv[++a]); }
+    else if (w == "-dump" || w == "-include" || w == "-exclude")
+      die("ERROR: mode '%s' is not part of this build (-existence, -bed, -bed-runs, -wig-count, -wig-depth only).", w.c_str());
     else die("ERROR: unknown option '%s'.", w.c_str());
   }
-  if (!existence || (seq_name.empty() && !estimate) || dbs.empty()) {
-    fprintf(stderr, "usage: %s -existence -sequence <in.fa|fq[.gz]> -mers <db.meryl> [...] [-min v] [-max v] [-memory GB] [-estimate] [-output out.tsv]\n", argv[0]);
+  // lookupGlobal::checkInvalid (meryl-lookup.C:306-368), before any database or device is touched
+  if (op == OP_NONE && !estimate) die("No report-type (-bed, -wig-count, -wig-depth, -existence, -include, -exclude) supplied.");
+  if (op != OP_NONE) {
+    if (!seq_name2.empty()) die("Only one input sequence (-sequence) supported for %s.", op_name(op));
+    if (!out_name2.empty()) die("Only one output file (-output) supported for %s.", op_name(op));
+    if (op != OP_BED && op != OP_BED_RUNS && !labels.empty()) die("Labels (-labels) not supported for %s.", op_name(op));
+    if (op != OP_EXISTENCE && compressed_name(out_name))
+      die("ERROR: output '%s' names a compressed file; this build writes position reports uncompressed only.", out_name.c_str());
+    if (dbs.size() > MGC_LOOKUP_MAX_TABLES && op != OP_EXISTENCE) die("ERROR: at most 32 databases (-mers) for %s.", op_name(op));
+  }
+  if (op == OP_NONE || (seq_name.empty() && !estimate) || dbs.empty()) {
+    fprintf(stderr, "usage: %s -existence | -bed | -bed-runs | -wig-count | -wig-depth -sequence <in.fa|fq[.gz]> -mers <db.meryl> [...] "
+                    "[-labels l ...] [-min v] [-max v] [-memory GB] [-estimate] [-output out]\n", argv[0]);
     return 1;
   }
 
@@ -127,10 +176,39 @@ int main(int argc, char **argv) {
   parse_text(text, sq);
   std::string().swap(text);
   const uint64_t n_seq = sq.names.size();
+  auto hip = [](hipError_t e, const char *what) { if (e != hipSuccess) { fprintf(stderr, "ERROR: %s: %s\n", what, hipGetErrorString(e)); exit(1); } };
+
+  if (op != OP_EXISTENCE) {                                   // dumpExistence (dump.C:430-441): every table at once, one report
+    FILE *out = out_name.empty() ? stdout : fopen(out_name.c_str(), "w");
+    if (!out) die("ERROR: cannot write '%s'.", out_name.c_str());
+    std::vector<mgc_lookup *> tables;
+    for (const std::string &d : dbs) {
+      fprintf(stderr, "\nLoading kmers from '%s' into lookup table.\n", d.c_str());              // meryl-lookup.C:89
+      mgc_lookup *t = mgc_lookup_load(d.c_str(), vmin, vmax, -1, 0);
+      if (!t) die("ERROR: %s", mgc_lookup_error());
+      tables.push_back(t);
+    }
+    uint8_t *d_bases = nullptr;
+    hip(hipMalloc(reinterpret_cast<void **>(&d_bases), sq.bases.size() + 1), "hipMalloc");
+    hip(hipMemcpy(d_bases, sq.bases.data(), sq.bases.size(), hipMemcpyHostToDevice), "upload");
+    std::vector<const char *> names, labs;
+    for (const std::string &n : sq.names) names.push_back(n.c_str());
+    for (const std::string &l : labels) labs.push_back(l.c_str());
+    uint64_t chunk = 64ull << 20;                             // bytes per piece of text (MGC_LOOKUP_CHUNK overrides)
+    if (getenv("MGC_LOOKUP_CHUNK")) chunk = strtoull(getenv("MGC_LOOKUP_CHUNK"), nullptr, 10);
+    const int mode = op == OP_BED ? MGC_REPORT_BED : op == OP_BED_RUNS ? MGC_REPORT_BED_RUNS
+                   : op == OP_WIG_COUNT ? MGC_REPORT_WIG_COUNT : MGC_REPORT_WIG_DEPTH;
+    if (mgc_lookup_report(tables.data(), (uint32_t)tables.size(), mode, labs.data(), (uint32_t)labs.size(), d_bases, sq.bases.size(),
+                          sq.start.data(), names.data(), n_seq, chunk, write_piece, out) != MGC_OK)
+      die("ERROR: %s", mgc_lookup_error());
+    if (fflush(out) != 0 || (out != stdout && fclose(out) != 0)) die("ERROR: cannot write '%s'.", out_name.c_str());
+    for (mgc_lookup *t : tables) mgc_lookup_free(t);
+    (void)hipFree(d_bases);
+    return 0;
+  }
 
   uint8_t *d_bases = nullptr;
   uint64_t *d_start = nullptr, *d_total = nullptr, *d_found = nullptr;
-  auto hip = [](hipError_t e, const char *what) { if (e != hipSuccess) { fprintf(stderr, "ERROR: %s: %s\n", what, hipGetErrorString(e)); exit(1); } };
   hip(hipMalloc(reinterpret_cast<void **>(&d_bases), sq.bases.size() + 1), "hipMalloc");
   hip(hipMalloc(reinterpret_cast<void **>(&d_start), 8 * (n_seq + 1)), "hipMalloc");
   hip(hipMalloc(reinterpret_cast<void **>(&d_total), 8 * (n_seq + 1)), "hipMalloc");

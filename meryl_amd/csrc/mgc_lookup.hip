@@ -64,11 +64,10 @@ __device__ __forceinline__ int lk_code(u32 c) {
 constexpr int LK_RUN = 16;                          // window starts per thread
 
 // Every window start of [i0, i0 + LK_RUN): the rolling forward / reverse-complement pair of the reference's kmerIterator
-// (call sites src/meryl-lookup/existence.C:69-77), restarted at i0 -- windows that start at or after i0 depend on no
-// earlier base.  visit(start, value_or_0, is_kmer)
+// (call sites src/meryl-lookup/existence.C:69-77, dump.C:98-112), restarted at i0 -- windows that start at or after i0 depend on
+// no earlier base.  visit(start, fmer, rmer, fmer == rmer)
 template <typename K, typename F>
-__device__ __forceinline__ void lk_walk(const K *__restrict__ keys, const u32 *__restrict__ vals, const u64 *__restrict__ index,
-                                        u32 shift, const uint8_t *__restrict__ bases, u64 n_bases, u32 k, u64 i0, F visit) {
+__device__ __forceinline__ void lk_roll(const uint8_t *__restrict__ bases, u64 n_bases, u32 k, u64 i0, F visit) {
   typedef typename LkOps<K>::W W;
   const W one = 1;
   const W mask = (2 * k >= sizeof(W) * 8) ? ~(W)0 : ((one << (2 * k)) - 1);
@@ -84,10 +83,19 @@ __device__ __forceinline__ void lk_walk(const K *__restrict__ keys, const u32 *_
     if (load < k) continue;
     const u64 s = j + 1 - k;                        // >= i0 because load restarted at i0
     if (s >= i0 + LK_RUN) break;
-    u32 v = lk_find<K>(keys, vals, index, shift, LkOps<K>::key(f));
-    if (v == 0 && f != r) v = lk_find<K>(keys, vals, index, shift, LkOps<K>::key(r));   // value(fmer) > 0 || value(rmer) > 0
-    visit(s, v);
+    visit(s, LkOps<K>::key(f), LkOps<K>::key(r), f == r);
   }
+}
+
+// visit(start, value_or_0) of every window start of [i0, i0 + LK_RUN) in one table
+template <typename K, typename F>
+__device__ __forceinline__ void lk_walk(const K *__restrict__ keys, const u32 *__restrict__ vals, const u64 *__restrict__ index,
+                                        u32 shift, const uint8_t *__restrict__ bases, u64 n_bases, u32 k, u64 i0, F visit) {
+  lk_roll<K>(bases, n_bases, k, i0, [&](u64 s, K f, K r, bool pal) {
+    u32 v = lk_find<K>(keys, vals, index, shift, f);
+    if (v == 0 && !pal) v = lk_find<K>(keys, vals, index, shift, r);   // value(fmer) > 0 || value(rmer) > 0
+    visit(s, v);
+  });
 }
 
 template <typename K>
@@ -153,6 +161,264 @@ void filter_emit_kernel(const K *__restrict__ keys, const u32 *__restrict__ vals
     const u64 i = base + q;
     if (i < n) { const u64 v = vals[i]; if (v >= vmin && v <= vmax) { out_k[o] = keys[i]; out_v[o] = (u32)v; o++; } }
   }
+}
+
+
+// ================================================================================================
+//  Position reports of meryl-lookup: -bed, -bed-runs, -wig-count, -wig-depth (src/meryl-lookup/dump.C)
+// ================================================================================================
+// The tables of one pass travel in the kernel-argument segment: a device-resident array of descriptors written at launch,
+// read with uniform loads, no allocation or upload per call.  At most 32 tables (one presence bit each).
+constexpr u32 LK_MAX_TABLES = 32;
+struct LkTable { const void *keys; const u32 *vals; const u64 *index; u64 n_index; u32 shift, reserved; };
+struct LkSet { LkTable t[LK_MAX_TABLES]; u32 n, k; };
+
+// dump.C:109-135 (presence: bit t = table t holds fmer or rmer), :146-164 (count: value(f) + value(r), value(f) alone for a
+// palindrome, summed over the tables in uint32 -- it wraps), :222-233 (depth: presence in table 0 only)
+template <typename K, int WHAT>
+__device__ __forceinline__ u32 lk_probe(const LkSet &set, K f, K r, bool pal) {
+  u32 acc = 0;
+  const u32 nt = WHAT == MGC_LOOKUP_DEPTH ? 1u : set.n;
+  for (u32 t = 0; t < nt; t++) {
+    const LkTable &d = set.t[t];
+    const K *keys = reinterpret_cast<const K *>(d.keys);
+    const u32 fv = lk_find<K>(keys, d.vals, d.index, d.shift, f, d.n_index);
+    if (WHAT == MGC_LOOKUP_COUNT) {
+      acc += fv;
+      if (!pal) acc += lk_find<K>(keys, d.vals, d.index, d.shift, r, d.n_index);
+    } else {
+      const bool hit = fv != 0 || (!pal && lk_find<K>(keys, d.vals, d.index, d.shift, r, d.n_index) != 0);
+      acc |= (u32)hit << t;
+    }
+  }
+  return acc;
+}
+
+template <typename K, int WHAT>
+__global__ __launch_bounds__(256)
+void lookup_positions_kernel(const LkSet set, const uint8_t *__restrict__ bases, u64 n_bases, u32 *__restrict__ out) {
+  const u64 i0 = ((u64)blockIdx.x * blockDim.x + threadIdx.x) * LK_RUN;
+  if (i0 >= n_bases) return;
+  for (int q = 0; q < LK_RUN; q++) if (i0 + q < n_bases) out[i0 + q] = 0;
+  lk_roll<K>(bases, n_bases, set.k, i0, [&](u64 s, K f, K r, bool pal) { out[s] = lk_probe<K, WHAT>(set, f, r, pal); });
+}
+
+// depth[i] = number of table-0 windows starting in i-k+1 .. i (dump.C:222-241 builds it as +1 / -1 at each found window's
+// begin / end and a prefix sum).  One workgroup = 4096 bases: waves 0-3 flag the windows starting in the tile, four lanes of
+// wave 4 the (k-1 <= 63)-window halo before it, into LDS; then every base sums its k flags (sliding over its 16 bases).  Windows
+// never cross a non-ACGT byte, so a sequence boundary needs no special case.
+constexpr int LK_DEPTH_TILE = 256 * LK_RUN;
+constexpr int LK_HALO = 64;
+template <typename K>
+__global__ __launch_bounds__(320)
+void lookup_depth_kernel(const LkSet set, const uint8_t *__restrict__ bases, u64 n_bases, u32 *__restrict__ out) {
+  __shared__ uint8_t s_hit[LK_HALO + LK_DEPTH_TILE];
+  const u64 b0 = (u64)blockIdx.x * LK_DEPTH_TILE;
+  const u32 tid = threadIdx.x;
+  const bool main = tid < 256;
+  const u32 h = tid - 256;                                    // halo lane (wave 4)
+  const bool halo = !main && h < (u32)(LK_HALO / LK_RUN);
+  const u32 slot = main ? LK_HALO + tid * LK_RUN : h * LK_RUN;
+  if (main || halo) {
+    for (int q = 0; q < LK_RUN; q++) s_hit[slot + q] = 0;
+    const u64 i0 = main ? b0 + (u64)tid * LK_RUN : b0 - LK_HALO + (u64)h * LK_RUN;
+    if ((main || b0 >= (u64)LK_HALO) && i0 < n_bases)
+      lk_roll<K>(bases, n_bases, set.k, i0, [&](u64 s, K f, K r, bool pal) {
+        s_hit[slot + (u32)(s - i0)] = (uint8_t)lk_probe<K, MGC_LOOKUP_DEPTH>(set, f, r, pal);
+      });
+  }
+  __syncthreads();
+  if (!main) return;
+  const u64 i_first = b0 + (u64)tid * LK_RUN;
+  if (i_first >= n_bases) return;
+  const u32 k = set.k;                                        // 1..64: slot - (k - 1) >= 0
+  u32 d = 0;
+  for (u32 j = 0; j < k; j++) d += s_hit[slot - j];
+  for (int q = 0; q < LK_RUN; q++) {
+    if (i_first + q >= n_bases) break;
+    if (q) d += (u32)s_hit[slot + q] - (u32)s_hit[slot + q - k];
+    out[i_first + q] = d;
+  }
+}
+
+// ---- text (dump.C:251-298 outputBED, :302-364 outputBEDruns, :368-405 outputWIG) ----------------------------------------
+// Without labels only one flag is kept, "found in any table" (dump.C:127-131).
+__device__ __forceinline__ u32 rp_eff(u32 m, u32 any_only) { return any_only ? (u32)(m != 0) : m; }
+// tables whose run of flags ends just before p: p is the run's E, the first position after it (dump.C:329-350).  The base
+// before a sequence's first one is its predecessor's trailing breaker, whose flags are 0.
+__device__ __forceinline__ u32 rp_fall(const u32 *__restrict__ val, u64 p, u32 any_only) {
+  const u32 prev = p ? rp_eff(val[p - 1], any_only) : 0u;
+  return prev & ~rp_eff(val[p], any_only);
+}
+__device__ __forceinline__ u32 rp_edge(const u32 *__restrict__ val, u64 p, u32 t, u32 any_only) {
+  const u32 cur = (rp_eff(val[p], any_only) >> t) & 1u;
+  const u32 prev = p ? (rp_eff(val[p - 1], any_only) >> t) & 1u : 0u;
+  return cur ^ prev;
+}
+
+__global__ __launch_bounds__(256)
+void runs_lines_kernel(const u32 *__restrict__ val, u64 n, u32 any_only, u64 *__restrict__ lines) {
+  const u64 stride = (u64)gridDim.x * blockDim.x;
+  for (u64 p = (u64)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) lines[p] = (u64)__popc(rp_fall(val, p, any_only));
+}
+// rising and falling edges of table t's flags, compacted in order (count per tile, scan, emit): they alternate, so the j-th
+// run of the table is [edges[2j], edges[2j+1]) -- no thread walks a run
+__global__ __launch_bounds__(256)
+void runs_edge_count_kernel(const u32 *__restrict__ val, u64 n, u32 t, u32 any_only, u64 *__restrict__ tile_cnt) {
+  __shared__ u32 s_tmp[256 / 64 + 1];
+  const u64 base = (u64)blockIdx.x * FL_TILE + (u64)threadIdx.x * 8;
+  u32 c = 0;
+  for (int q = 0; q < 8; q++) { const u64 i = base + q; if (i < n) c += rp_edge(val, i, t, any_only); }
+  u32 tot;
+  (void)block_excl_scan<256, u32>(c, s_tmp, &tot);
+  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
+}
+__global__ __launch_bounds__(256)
+void runs_edge_emit_kernel(const u32 *__restrict__ val, u64 n, u32 t, u32 any_only, const u64 *__restrict__ tile_base,
+                           u64 *__restrict__ edges) {
+  __shared__ u32 s_tmp[256 / 64 + 1];
+  const u64 base = (u64)blockIdx.x * FL_TILE + (u64)threadIdx.x * 8;
+  u32 c = 0;
+  for (int q = 0; q < 8; q++) { const u64 i = base + q; if (i < n) c += rp_edge(val, i, t, any_only); }
+  u32 tot;
+  u64 o = tile_base[blockIdx.x] + block_excl_scan<256, u32>(c, s_tmp, &tot);
+  for (int q = 0; q < 8; q++) { const u64 i = base + q; if (i < n && rp_edge(val, i, t, any_only)) edges[o++] = i; }
+}
+// run j of table t -> its line: lines[E] (exclusive scan of the lines per position) + the tables before t that also end at E
+__global__ __launch_bounds__(256)
+void runs_pair_kernel(const u64 *__restrict__ edges, u64 n_runs, const u32 *__restrict__ val, u64 n, const u64 *__restrict__ lines,
+                      u32 t, u32 any_only, u64 *__restrict__ run_bgn) {
+  const u64 stride = (u64)gridDim.x * blockDim.x;
+  for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < n_runs; j += stride) {
+    const u64 e = edges[2 * j + 1];
+    if (e >= n) continue;                                     // cannot happen: every sequence ends with a breaker
+    const u32 below = rp_fall(val, e, any_only) & ((1u << t) - 1u);
+    run_bgn[lines[e] + __popc(below)] = edges[2 * j];
+  }
+}
+
+struct RpCtx {
+  const u32 *val;                    // per position: presence mask / count / depth
+  const u64 *seq_start;              // n_seq + 1: seq_start[0] = 0, seq_start[n_seq] = n_bases
+  u64 n_seq;
+  const char *names; const u64 *name_off;
+  const char *labels; const u64 *label_off;
+  const u64 *lines, *run_bgn;        // -bed-runs: first line of each position, begin of each line
+  u32 n_labels, k, mode, any_only;
+};
+
+__device__ __forceinline__ u32 rp_dec_len(u64 x) {
+  u32 l = 1;
+  for (u64 p = 10; l < 20 && x >= p; p *= 10) l++;
+  return l;
+}
+struct RpCount {                     // bytes only
+  u64 o = 0;
+  __device__ void put(char) { o++; }
+  __device__ void put_str(const char *, u64 n) { o += n; }
+  __device__ void put_dec(u64 x) { o += rp_dec_len(x); }
+};
+struct RpWrite {                     // the bytes [lo, hi) of the range's text land in buf[0, hi - lo)
+  char *buf;
+  u64 o, lo, hi;
+  __device__ void at(u64 i, char c) { if (i >= lo && i < hi) buf[i - lo] = c; }
+  __device__ void put(char c) { at(o++, c); }
+  __device__ void put_str(const char *s, u64 n) { for (u64 i = 0; i < n; i++) at(o + i, s[i]); o += n; }
+  __device__ void put_dec(u64 x) {   // toDec()
+    const u32 l = rp_dec_len(x);
+    if (x >> 32) { for (u32 j = l; j-- > 0;) { at(o + j, (char)('0' + x % 10)); x /= 10; } }
+    else { u32 y = (u32)x; for (u32 j = l; j-- > 0;) { at(o + j, (char)('0' + y % 10u)); y /= 10u; } }
+    o += l;
+  }
+};
+
+// last sequence starting at or before p: the non-empty one that holds it
+__device__ __forceinline__ u64 rp_seq(const u64 *__restrict__ ss, u64 n_seq, u64 p) {
+  u64 lo = 0, hi = n_seq;
+  while (hi - lo > 1) { const u64 mid = lo + ((hi - lo) >> 1); if (ss[mid] <= p) lo = mid; else hi = mid; }
+  return lo;
+}
+
+// all lines of position p (sequence s)
+template <typename O>
+__device__ void rp_emit(const RpCtx &c, u64 p, u64 s, O &out) {
+  const u64 ss = c.seq_start[s], loc = p - ss;
+  if (c.mode == MGC_REPORT_WIG_COUNT || c.mode == MGC_REPORT_WIG_DEPTH) {
+    if (loc == 0) {                                           // dump.C:377, for this sequence and the empty ones just before it
+      u64 a = 0, b = s;
+      while (a < b) { const u64 mid = a + ((b - a) >> 1); if (c.seq_start[mid] < p) a = mid + 1; else b = mid; }
+      for (u64 q = a; q <= s; q++) {
+        out.put_str("variableStep chrom=", 19);
+        out.put_str(c.names + c.name_off[q], c.name_off[q + 1] - c.name_off[q]);
+        out.put('\n');
+      }
+    }
+    const u32 v = c.val[p];                                   // dump.C:387-401: zero prints nothing
+    if (v) { out.put_dec(loc + 1); out.put('\t'); out.put_dec(v); out.put('\n'); }
+    return;
+  }
+  const bool runs = c.mode == MGC_REPORT_BED_RUNS;
+  u32 m = runs ? rp_fall(c.val, p, c.any_only) : rp_eff(c.val[p], c.any_only);
+  if (!m) return;
+  const char *nm = c.names + c.name_off[s];
+  const u64 nl = c.name_off[s + 1] - c.name_off[s];
+  u64 li = runs ? c.lines[p] : 0;
+  while (m) {                                                 // table order (dump.C:275, :330)
+    const u32 t = __ffs(m) - 1;
+    m &= m - 1;
+    out.put_str(nm, nl);
+    out.put('\t');
+    out.put_dec(runs ? c.run_bgn[li++] - ss : loc);
+    out.put('\t');
+    out.put_dec(loc + c.k);                                   // -bed: p + k; -bed-runs: E + k (dump.C:350)
+    if (t < c.n_labels) { out.put('\t'); out.put_str(c.labels + c.label_off[t], c.label_off[t + 1] - c.label_off[t]); }
+    out.put('\n');
+  }
+}
+
+// bytes of every position of [a, b) -> len[p - a]
+__global__ __launch_bounds__(256)
+void report_len_kernel(const RpCtx c, u64 a, u64 b, u64 *__restrict__ len) {
+  const u64 i0 = a + ((u64)blockIdx.x * blockDim.x + threadIdx.x) * LK_RUN;
+  if (i0 >= b) return;
+  u64 s = rp_seq(c.seq_start, c.n_seq, i0);
+  for (int q = 0; q < LK_RUN; q++) {
+    const u64 p = i0 + q;
+    if (p >= b) break;
+    while (c.seq_start[s + 1] <= p) s++;
+    RpCount o;
+    rp_emit(c, p, s, o);
+    len[p - a] = o.o;
+  }
+}
+
+// the bytes [lo, hi) of the text of positions [a, b): off = exclusive scan of len, off[b - a] = the range's total
+__global__ __launch_bounds__(256)
+void report_format_kernel(const RpCtx c, u64 a, u64 b, const u64 *__restrict__ off, u64 lo, u64 hi, char *__restrict__ buf) {
+  u64 x = 0, y = b - a;                                       // the position whose text holds byte lo: last off <= lo
+  while (y - x > 1) { const u64 mid = x + ((y - x) >> 1); if (off[mid] <= lo) x = mid; else y = mid; }
+  const u64 stride = (u64)gridDim.x * blockDim.x * LK_RUN;
+  for (u64 i0 = a + x + ((u64)blockIdx.x * blockDim.x + threadIdx.x) * LK_RUN; i0 < b && off[i0 - a] < hi; i0 += stride) {
+    u64 s = rp_seq(c.seq_start, c.n_seq, i0);
+    for (int q = 0; q < LK_RUN; q++) {
+      const u64 p = i0 + q;
+      if (p >= b) break;
+      const u64 o0 = off[p - a];
+      if (o0 >= hi) break;
+      if (off[p - a + 1] <= lo) continue;
+      while (c.seq_start[s + 1] <= p) s++;
+      RpWrite w{buf, o0, lo, hi};
+      rp_emit(c, p, s, w);
+    }
+  }
+}
+
+// every non-empty sequence must end with a byte that is not ACGT, so that no window crosses into the next one
+__global__ __launch_bounds__(256)
+void report_check_kernel(const uint8_t *__restrict__ bases, const u64 *__restrict__ ss, u64 n_seq, u32 *__restrict__ bad) {
+  const u64 stride = (u64)gridDim.x * blockDim.x;
+  for (u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x; s < n_seq; s += stride)
+    if (ss[s + 1] > ss[s] && lk_code(bases[ss[s + 1] - 1]) >= 0) *bad = 1u;
 }
 
 }  // namespace mgc
@@ -487,4 +753,255 @@ extern "C" int mgc_lookup_existence(const mgc_lookup *t, const uint8_t *d_bases,
                        reinterpret_cast<const mgc::u64 *>(t->d_index), t->shift, d_bases, (mgc::u64)n_bases, t->k,
                        reinterpret_cast<const mgc::u64 *>(d_seq_start), (mgc::u64)n_seq, reinterpret_cast<mgc::u64 *>(d_total), reinterpret_cast<mgc::u64 *>(d_found));
   return lk_rc(hipGetLastError(), "lookup_existence");
+}
+
+// ---- position reports (src/meryl-lookup/dump.C) ------------------------------------------------------------------------------
+namespace {
+int lk_set(const mgc_lookup *const *tables, uint32_t n_tables, mgc::LkSet &set, const char *who) {
+  if (!tables || n_tables == 0 || n_tables > mgc::LK_MAX_TABLES) {
+    lk_err(std::string(who) + ": between 1 and " + std::to_string(mgc::LK_MAX_TABLES) + " tables");
+    return MGC_EINVAL;
+  }
+  memset(&set, 0, sizeof(set));
+  for (uint32_t t = 0; t < n_tables; t++) {
+    const mgc_lookup *L = tables[t];
+    if (!L) { lk_err(std::string(who) + ": no table"); return MGC_EINVAL; }
+    if (L->k != tables[0]->k) { lk_err(std::string(who) + ": the tables have different k-mer sizes"); return MGC_EINVAL; }
+    set.t[t].keys = L->d_keys; set.t[t].vals = L->d_vals; set.t[t].index = reinterpret_cast<const mgc::u64 *>(L->d_index);
+    set.t[t].n_index = 1ull << L->index_bits; set.t[t].shift = L->shift;
+  }
+  set.n = n_tables; set.k = tables[0]->k;
+  return MGC_OK;
+}
+
+hipError_t lk_launch_positions(const mgc::LkSet &set, bool wide, int what, const uint8_t *d_bases, uint64_t n_bases, uint32_t *d_out,
+                               hipStream_t st) {
+  if (n_bases == 0) return hipSuccess;
+  if (what == MGC_LOOKUP_DEPTH) {
+    const uint32_t g = (uint32_t)((n_bases + mgc::LK_DEPTH_TILE - 1) / mgc::LK_DEPTH_TILE);
+    if (wide) hipLaunchKernelGGL(mgc::lookup_depth_kernel<mgc::K128>, dim3(g), dim3(320), 0, st, set, d_bases, (mgc::u64)n_bases, d_out);
+    else      hipLaunchKernelGGL(mgc::lookup_depth_kernel<mgc::u64>, dim3(g), dim3(320), 0, st, set, d_bases, (mgc::u64)n_bases, d_out);
+    return hipGetLastError();
+  }
+  const uint32_t g = lk_grid((n_bases + mgc::LK_RUN - 1) / mgc::LK_RUN);
+  if (what == MGC_LOOKUP_COUNT) {
+    if (wide) hipLaunchKernelGGL((mgc::lookup_positions_kernel<mgc::K128, MGC_LOOKUP_COUNT>), dim3(g), dim3(256), 0, st, set, d_bases, (mgc::u64)n_bases, d_out);
+    else      hipLaunchKernelGGL((mgc::lookup_positions_kernel<mgc::u64, MGC_LOOKUP_COUNT>), dim3(g), dim3(256), 0, st, set, d_bases, (mgc::u64)n_bases, d_out);
+  } else {
+    if (wide) hipLaunchKernelGGL((mgc::lookup_positions_kernel<mgc::K128, MGC_LOOKUP_PRESENCE>), dim3(g), dim3(256), 0, st, set, d_bases, (mgc::u64)n_bases, d_out);
+    else      hipLaunchKernelGGL((mgc::lookup_positions_kernel<mgc::u64, MGC_LOOKUP_PRESENCE>), dim3(g), dim3(256), 0, st, set, d_bases, (mgc::u64)n_bases, d_out);
+  }
+  return hipGetLastError();
+}
+}  // namespace
+
+extern "C" int mgc_lookup_positions(const mgc_lookup *const *tables, uint32_t n_tables, int what, const uint8_t *d_bases, uint64_t n_bases,
+                                    uint32_t *d_out, void *stream) {
+  mgc::LkSet set;
+  const int rc = lk_set(tables, n_tables, set, "mgc_lookup_positions");
+  if (rc != MGC_OK) return rc;
+  if (what < MGC_LOOKUP_PRESENCE || what > MGC_LOOKUP_DEPTH) { lk_err("mgc_lookup_positions: unknown 'what'"); return MGC_EINVAL; }
+  if (n_bases && (!d_bases || !d_out)) { lk_err("mgc_lookup_positions: no bases or no output"); return MGC_EINVAL; }
+  return lk_rc(lk_launch_positions(set, tables[0]->kw == 2, what, d_bases, n_bases, d_out, (hipStream_t)stream), "lookup_positions");
+}
+
+namespace {
+// device and pinned buffers of one report, released on every way out
+struct RpBuffers {
+  std::vector<void *> dev, pinned;
+  hipStream_t cs = nullptr, xs = nullptr;
+  hipEvent_t ev_fmt[2] = {nullptr, nullptr}, ev_cp[2] = {nullptr, nullptr};
+  hipError_t alloc(void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes ? bytes : 8); if (e == hipSuccess) dev.push_back(*p); return e; }
+  hipError_t host(void **p, size_t bytes) { hipError_t e = hipHostMalloc(p, bytes ? bytes : 8, hipHostMallocDefault); if (e == hipSuccess) pinned.push_back(*p); return e; }
+  ~RpBuffers() {
+    if (cs) (void)hipStreamSynchronize(cs);
+    if (xs) (void)hipStreamSynchronize(xs);
+    for (void *p : dev) (void)hipFree(p);
+    for (void *p : pinned) (void)hipHostFree(p);
+    for (int i = 0; i < 2; i++) { if (ev_fmt[i]) (void)hipEventDestroy(ev_fmt[i]); if (ev_cp[i]) (void)hipEventDestroy(ev_cp[i]); }
+    if (cs) (void)hipStreamDestroy(cs);
+    if (xs) (void)hipStreamDestroy(xs);
+  }
+};
+}  // namespace
+
+#define RP_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return lk_rc(e__, #expr); } while (0)
+
+extern "C" int mgc_lookup_report(const mgc_lookup *const *tables, uint32_t n_tables, int mode, const char *const *labels, uint32_t n_labels,
+                                 const uint8_t *d_bases, uint64_t n_bases, const uint64_t *seq_start, const char *const *names, uint64_t n_seq,
+                                 uint64_t chunk_bytes, mgc_lookup_write_cb write_cb, void *user) {
+  mgc::LkSet set;
+  int rc = lk_set(tables, n_tables, set, "mgc_lookup_report");
+  if (rc != MGC_OK) return rc;
+  const bool wig = mode == MGC_REPORT_WIG_COUNT || mode == MGC_REPORT_WIG_DEPTH;
+  if (mode < MGC_REPORT_BED || mode > MGC_REPORT_WIG_DEPTH) { lk_err("mgc_lookup_report: unknown mode"); return MGC_EINVAL; }
+  if (!write_cb || !seq_start || (n_seq && !names) || (n_labels && !labels) || (n_bases && !d_bases)) {
+    lk_err("mgc_lookup_report: bad arguments");
+    return MGC_EINVAL;
+  }
+  if (wig && n_labels) { lk_err("mgc_lookup_report: labels are not supported for the WIG reports"); return MGC_EINVAL; }
+  if (seq_start[0] != 0 || seq_start[n_seq] != n_bases) { lk_err("mgc_lookup_report: seq_start must run from 0 to n_bases"); return MGC_EINVAL; }
+  // names and labels: one blob + offsets each; the longest line decides the smallest piece
+  std::string name_blob, label_blob;
+  std::vector<uint64_t> name_off(n_seq + 1, 0), label_off((size_t)n_labels + 1, 0);
+  uint64_t max_name = 0, max_label = 0;
+  for (uint64_t s = 0; s < n_seq; s++) {
+    if (seq_start[s + 1] < seq_start[s]) { lk_err("mgc_lookup_report: seq_start decreases"); return MGC_EINVAL; }
+    if (!names[s]) { lk_err("mgc_lookup_report: a sequence without a name"); return MGC_EINVAL; }
+    const size_t l = strlen(names[s]);
+    name_blob.append(names[s], l);
+    name_off[s + 1] = name_blob.size();
+    max_name = std::max<uint64_t>(max_name, l);
+  }
+  bool labels_present = false;                                                    // meryl-lookup.C:27-31
+  for (uint32_t t = 0; t < n_labels; t++) {
+    const size_t l = labels[t] ? strlen(labels[t]) : 0;
+    if (l) label_blob.append(labels[t], l);
+    label_off[t + 1] = label_blob.size();
+    max_label = std::max<uint64_t>(max_label, l);
+    labels_present = labels_present || l > 0;
+  }
+  const uint64_t longest = wig ? std::max<uint64_t>(19 + max_name + 1, 20 + 1 + 10 + 1)
+                               : max_name + 1 + 20 + 1 + 20 + (n_labels ? 1 + max_label : 0) + 1;
+  if (chunk_bytes < longest) {
+    lk_err("mgc_lookup_report: chunk_bytes " + std::to_string(chunk_bytes) + " is shorter than the longest line (" + std::to_string(longest) + " bytes)");
+    return MGC_EINVAL;
+  }
+  RP_HIP(hipSetDevice(tables[0]->device));
+  RpBuffers B;
+  RP_HIP(hipStreamCreate(&B.cs));
+  RP_HIP(hipStreamCreate(&B.xs));
+  for (int i = 0; i < 2; i++) { RP_HIP(hipEventCreateWithFlags(&B.ev_fmt[i], hipEventDisableTiming)); RP_HIP(hipEventCreateWithFlags(&B.ev_cp[i], hipEventDisableTiming)); }
+  hipStream_t cs = B.cs;
+
+  // ranges of positions: a range's byte offsets are one scan; its text leaves in pieces of chunk_bytes
+  const uint64_t R = std::max<uint64_t>(4096, std::min<uint64_t>(1ull << 24, chunk_bytes / 4));
+  const uint64_t R_eff = std::max<uint64_t>(1, std::min<uint64_t>(R, n_bases));
+  mgc::u64 *d_ss = nullptr, *d_noff = nullptr, *d_loff = nullptr, *d_off = nullptr, *d_scr = nullptr, *d_lines = nullptr, *d_bgn = nullptr;
+  char *d_names = nullptr, *d_labels = nullptr, *d_stage[2] = {nullptr, nullptr}, *h_stage[2] = {nullptr, nullptr};
+  uint32_t *d_val = nullptr, *d_bad = nullptr;
+  RP_HIP(B.alloc(reinterpret_cast<void **>(&d_ss), 8 * (n_seq + 1)));
+  RP_HIP(B.alloc(reinterpret_cast<void **>(&d_noff), 8 * (n_seq + 1)));
+  RP_HIP(B.alloc(reinterpret_cast<void **>(&d_loff), 8 * ((uint64_t)n_labels + 1)));
+  RP_HIP(B.alloc(reinterpret_cast<void **>(&d_names), name_blob.size()));
+  RP_HIP(B.alloc(reinterpret_cast<void **>(&d_labels), label_blob.size()));
+  RP_HIP(B.alloc(reinterpret_cast<void **>(&d_val), 4 * n_bases));
+  RP_HIP(B.alloc(reinterpret_cast<void **>(&d_bad), 8));
+  const size_t scr_elems = mgc::scan_scratch_elems(R_eff + 1) + 8;
+  RP_HIP(B.alloc(reinterpret_cast<void **>(&d_off), 8 * (R_eff + 1 + 8)));
+  RP_HIP(B.alloc(reinterpret_cast<void **>(&d_scr), 8 * scr_elems));
+  for (int i = 0; i < 2; i++) {
+    RP_HIP(B.alloc(reinterpret_cast<void **>(&d_stage[i]), chunk_bytes));
+    RP_HIP(B.host(reinterpret_cast<void **>(&h_stage[i]), chunk_bytes));
+  }
+  RP_HIP(hipMemcpyAsync(d_ss, seq_start, 8 * (n_seq + 1), hipMemcpyHostToDevice, cs));
+  RP_HIP(hipMemcpyAsync(d_noff, name_off.data(), 8 * (n_seq + 1), hipMemcpyHostToDevice, cs));
+  RP_HIP(hipMemcpyAsync(d_loff, label_off.data(), 8 * ((uint64_t)n_labels + 1), hipMemcpyHostToDevice, cs));
+  if (!name_blob.empty()) RP_HIP(hipMemcpyAsync(d_names, name_blob.data(), name_blob.size(), hipMemcpyHostToDevice, cs));
+  if (!label_blob.empty()) RP_HIP(hipMemcpyAsync(d_labels, label_blob.data(), label_blob.size(), hipMemcpyHostToDevice, cs));
+  RP_HIP(hipMemsetAsync(d_bad, 0, 8, cs));
+  if (n_seq) {
+    hipLaunchKernelGGL(mgc::report_check_kernel, dim3(lk_grid(std::min<uint64_t>(n_seq, 1u << 20))), dim3(256), 0, cs, d_bases, d_ss, (mgc::u64)n_seq, d_bad);
+    RP_HIP(hipGetLastError());
+  }
+  uint32_t h_bad = 0;
+  RP_HIP(hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, cs));
+  RP_HIP(hipStreamSynchronize(cs));                       // (the pageable uploads above are done too)
+  if (h_bad) { lk_err("mgc_lookup_report: a non-empty sequence does not end with a non-ACGT byte"); return MGC_EINVAL; }
+
+  // per position: presence mask, count or depth
+  const int what = mode == MGC_REPORT_WIG_COUNT ? MGC_LOOKUP_COUNT : mode == MGC_REPORT_WIG_DEPTH ? MGC_LOOKUP_DEPTH : MGC_LOOKUP_PRESENCE;
+  RP_HIP(lk_launch_positions(set, tables[0]->kw == 2, what, d_bases, n_bases, d_val, cs));
+  const uint32_t any_only = labels_present ? 0u : 1u;
+
+  // -bed-runs: the line of every run, and its begin
+  if (mode == MGC_REPORT_BED_RUNS && n_bases) {
+    RP_HIP(B.alloc(reinterpret_cast<void **>(&d_lines), 8 * (n_bases + 1)));
+    const size_t lscr = mgc::scan_scratch_elems(n_bases + 1) + 8;
+    const uint64_t tiles = (n_bases + mgc::FL_TILE - 1) / mgc::FL_TILE;
+    const size_t escr = mgc::scan_scratch_elems(tiles + 1) + 8;
+    mgc::u64 *d_s2 = nullptr, *d_tiles = nullptr, *d_edges = nullptr;
+    RP_HIP(B.alloc(reinterpret_cast<void **>(&d_s2), 8 * std::max(lscr, escr)));
+    RP_HIP(B.alloc(reinterpret_cast<void **>(&d_tiles), 8 * (tiles + 1 + 8)));
+    hipLaunchKernelGGL(mgc::runs_lines_kernel, dim3(lk_grid(std::min<uint64_t>(n_bases, 1u << 24))), dim3(256), 0, cs, d_val, (mgc::u64)n_bases, any_only, d_lines);
+    RP_HIP(hipGetLastError());
+    RP_HIP(mgc::scan_u64_exclusive(d_lines, n_bases, d_s2, d_tiles + tiles + 1, cs));
+    uint64_t n_lines = 0;
+    RP_HIP(hipMemcpyAsync(&n_lines, d_tiles + tiles + 1, 8, hipMemcpyDeviceToHost, cs));
+    RP_HIP(hipStreamSynchronize(cs));
+    RP_HIP(B.alloc(reinterpret_cast<void **>(&d_bgn), 8 * n_lines));
+    const uint32_t n_flag = any_only ? 1u : n_tables;
+    for (uint32_t t = 0; t < n_flag && n_lines; t++) {
+      hipLaunchKernelGGL(mgc::runs_edge_count_kernel, dim3((uint32_t)tiles), dim3(256), 0, cs, d_val, (mgc::u64)n_bases, t, any_only, d_tiles);
+      RP_HIP(hipGetLastError());
+      RP_HIP(mgc::scan_u64_exclusive(d_tiles, tiles, d_s2, d_tiles + tiles + 1, cs));
+      uint64_t n_edges = 0;
+      RP_HIP(hipMemcpyAsync(&n_edges, d_tiles + tiles + 1, 8, hipMemcpyDeviceToHost, cs));
+      RP_HIP(hipStreamSynchronize(cs));
+      if (!n_edges) continue;
+      if (n_edges > 2 * n_lines) { lk_err("mgc_lookup_report: a run of flags does not end inside the stream"); return MGC_EINVAL; }
+      if (!d_edges) RP_HIP(B.alloc(reinterpret_cast<void **>(&d_edges), 8 * 2 * n_lines));   // every run is a line: enough for any table
+      hipLaunchKernelGGL(mgc::runs_edge_emit_kernel, dim3((uint32_t)tiles), dim3(256), 0, cs, d_val, (mgc::u64)n_bases, t, any_only, d_tiles, d_edges);
+      RP_HIP(hipGetLastError());
+      hipLaunchKernelGGL(mgc::runs_pair_kernel, dim3(lk_grid(std::min<uint64_t>(n_edges / 2, 1u << 24))), dim3(256), 0, cs, d_edges, (mgc::u64)(n_edges / 2),
+                         d_val, (mgc::u64)n_bases, d_lines, t, any_only, d_bgn);
+      RP_HIP(hipGetLastError());
+    }
+  }
+
+  mgc::RpCtx ctx;
+  ctx.val = d_val; ctx.seq_start = d_ss; ctx.n_seq = n_seq; ctx.names = d_names; ctx.name_off = d_noff;
+  ctx.labels = d_labels; ctx.label_off = d_loff; ctx.lines = d_lines; ctx.run_bgn = d_bgn;
+  ctx.n_labels = n_labels; ctx.k = set.k; ctx.mode = (uint32_t)mode; ctx.any_only = any_only;
+
+  // pieces: piece j is formatted into d_stage[j & 1] on cs, copied to h_stage[j & 1] on xs, and handed to the callback while
+  // piece j + 1 is formatted
+  uint64_t piece = 0, pending_bytes = 0;
+  bool pending = false;
+  auto deliver = [&](int slot) -> int {
+    hipError_t e = hipEventSynchronize(B.ev_cp[slot]);
+    if (e != hipSuccess) return lk_rc(e, "report copy");
+    const int r = write_cb(h_stage[slot], pending_bytes, user);
+    if (r != 0) { lk_err("mgc_lookup_report: the write callback returned " + std::to_string(r)); return MGC_ESTATE; }
+    return MGC_OK;
+  };
+  for (uint64_t a = 0; a < n_bases; a += R_eff) {
+    const uint64_t b = std::min<uint64_t>(n_bases, a + R_eff), np = b - a;
+    RP_HIP(hipMemsetAsync(d_off + np, 0, 8, cs));
+    hipLaunchKernelGGL(mgc::report_len_kernel, dim3(lk_grid((np + mgc::LK_RUN - 1) / mgc::LK_RUN)), dim3(256), 0, cs, ctx, (mgc::u64)a, (mgc::u64)b, d_off);
+    RP_HIP(hipGetLastError());
+    RP_HIP(mgc::scan_u64_exclusive(d_off, np + 1, d_scr, d_off + np + 1, cs));
+    uint64_t total = 0;
+    RP_HIP(hipMemcpyAsync(&total, d_off + np, 8, hipMemcpyDeviceToHost, cs));
+    RP_HIP(hipStreamSynchronize(cs));
+    const uint32_t g = lk_grid(std::min<uint64_t>((np + mgc::LK_RUN - 1) / mgc::LK_RUN, 256u * 1024u));
+    for (uint64_t lo = 0; lo < total; lo += chunk_bytes, piece++) {
+      const uint64_t hi = std::min<uint64_t>(total, lo + chunk_bytes);
+      const int slot = (int)(piece & 1);
+      if (piece >= 2) RP_HIP(hipStreamWaitEvent(cs, B.ev_cp[slot], 0));        // piece - 2 has left d_stage[slot]
+      hipLaunchKernelGGL(mgc::report_format_kernel, dim3(g), dim3(256), 0, cs, ctx, (mgc::u64)a, (mgc::u64)b, d_off, (mgc::u64)lo, (mgc::u64)hi, d_stage[slot]);
+      RP_HIP(hipGetLastError());
+      RP_HIP(hipEventRecord(B.ev_fmt[slot], cs));
+      RP_HIP(hipStreamWaitEvent(B.xs, B.ev_fmt[slot], 0));
+      RP_HIP(hipMemcpyAsync(h_stage[slot], d_stage[slot], hi - lo, hipMemcpyDeviceToHost, B.xs));
+      RP_HIP(hipEventRecord(B.ev_cp[slot], B.xs));
+      if (pending && (rc = deliver(slot ^ 1)) != MGC_OK) return rc;
+      pending = true;
+      pending_bytes = hi - lo;
+    }
+  }
+  if (pending && (rc = deliver((int)((piece - 1) & 1))) != MGC_OK) return rc;
+  // WIG headers of the empty sequences at the very end of the stream (the device writes the others before their successor)
+  if (wig) {
+    std::string tail;
+    for (uint64_t s = 0; s < n_seq; s++)
+      if (seq_start[s] == n_bases) tail += "variableStep chrom=" + std::string(names[s]) + "\n";
+    for (uint64_t o = 0; o < tail.size(); o += chunk_bytes) {
+      const uint64_t m = std::min<uint64_t>(chunk_bytes, tail.size() - o);
+      memcpy(h_stage[0], tail.data() + o, m);
+      const int r = write_cb(h_stage[0], m, user);
+      if (r != 0) { lk_err("mgc_lookup_report: the write callback returned " + std::to_string(r)); return MGC_ESTATE; }
+    }
+  }
+  return MGC_OK;
 }

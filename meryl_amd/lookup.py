@@ -72,3 +72,54 @@ class Lookup:
         capi.check(capi.lib().mgc_lookup_existence(self._h, _ptr(bases), bases.numel(), _ptr(ss), n, _ptr(tot), _ptr(fnd), _stream()),
                    "mgc_lookup_existence")
         return tot[:n].cpu().numpy().view(np.uint64), fnd[:n].cpu().numpy().view(np.uint64)
+
+
+WHAT = {"presence": 0, "count": 1, "depth": 2}
+MODES = {"bed": 0, "bed-runs": 1, "wig-count": 2, "wig-depth": 3}
+
+
+def _tables(tables):
+    hs = [t._h for t in tables]
+    return (ctypes.c_void_p * max(len(hs), 1))(*hs), len(hs)
+
+
+def positions(tables, what, bases):
+    """mgc_lookup_positions (src/meryl-lookup/dump.C:89-245) over the Lookups `tables`: what = "presence" (bit t: table t holds
+    the window's fmer or rmer), "count" (sum of value(f) + value(r) over the tables, uint32) or "depth" (windows of table 0
+    covering each base).  bases: uint8 cuda tensor -> int32[n_bases] (read as uint32)."""
+    arr, n = _tables(tables)
+    out = torch.empty(bases.numel(), dtype=torch.int32, device=bases.device)
+    _check(capi.lib().mgc_lookup_positions(arr, n, WHAT.get(what, what), _ptr(bases), bases.numel(), _ptr(out), _stream()),
+           "mgc_lookup_positions")
+    return out
+
+
+def _check(rc, what):
+    if rc != capi.MGC_OK:
+        raise capi.MgcError(rc, what, capi.lib().mgc_lookup_error().decode("utf-8", "replace"))
+
+
+def report(tables, mode, names, bases, seq_start, labels=None, chunk_bytes=64 << 20, pieces=None):
+    """mgc_lookup_report: the text of meryl-lookup -bed / -bed-runs / -wig-count / -wig-depth (mode: one of MODES) as bytes.
+    bases: uint8 cuda tensor holding the sequences one after the other, each non-empty one ending with a non-ACGT byte;
+    seq_start: n_seq + 1 offsets from 0 to bases.numel(); names: the n_seq identifiers; labels: one per table (-labels).
+    pieces: a list that receives the callback's pieces as they come (at most chunk_bytes each)."""
+    arr, n = _tables(tables)
+    ss = np.ascontiguousarray(np.asarray(seq_start, dtype=np.uint64))
+    names_b = [s.encode() if isinstance(s, str) else bytes(s) for s in names]
+    labels_b = [s.encode() if isinstance(s, str) else bytes(s) for s in (labels or [])]
+    c_names = (ctypes.c_char_p * max(len(names_b), 1))(*names_b)
+    c_labels = (ctypes.c_char_p * max(len(labels_b), 1))(*labels_b)
+    if pieces is None:
+        pieces = []
+
+    def _write(data, nbytes, _user):
+        pieces.append(ctypes.string_at(data, nbytes))
+        return 0
+
+    cb = capi.LOOKUP_WRITE_CB(_write)
+    torch.cuda.current_stream(bases.device).synchronize()
+    _check(capi.lib().mgc_lookup_report(arr, n, MODES.get(mode, mode), c_labels, len(labels_b), _ptr(bases), bases.numel(),
+                                        ss.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), c_names, len(names_b), chunk_bytes,
+                                        cb, None), "mgc_lookup_report")
+    return b"".join(pieces)
