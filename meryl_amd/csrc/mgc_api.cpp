@@ -15,7 +15,6 @@
 #include <cerrno>
 #include <chrono>
 #include <condition_variable>
-#include <deque>
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -427,14 +426,10 @@ extern "C" mgc_session *mgc_open(const mgc_count_config *cfg, int device) {
   return s;
 }
 
-static void join_prepare(mgc_session *s) {
-  if (s->prep_active) { s->prep_thread.join(); s->prep_active = false; }
-}
-
 extern "C" void mgc_close(mgc_session *s) {
   if (!s) return;
   if (s->worker_active) { s->worker.join(); s->worker_active = false; }
-  join_prepare(s);
+  s->join_prepare();
   (void)hipSetDevice(s->device);
   if (s->st_in) (void)hipStreamSynchronize(s->st_in);
   s->free_result();
@@ -1169,932 +1164,6 @@ extern "C" int mgc_get_profile(const mgc_session *s, mgc_profile *p) {
   return MGC_OK;
 }
 
-namespace {
-struct DevBuf {                                   // frees on scope exit
-  void *p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 256); }
-  template <typename T> T *as() { return reinterpret_cast<T *>(p); }
-  void *release() { void *q = p; p = nullptr; return q; }
-};
-
-struct StageTimer {
-  bool on;
-  hipStream_t st;
-  hipEvent_t ev[MGC_NUM_STAGES][2];
-  bool used[MGC_NUM_STAGES];
-  StageTimer(bool enable, hipStream_t s) : on(enable), st(s) {
-    for (int i = 0; i < MGC_NUM_STAGES; i++) {
-      used[i] = false;
-      if (on) { (void)hipEventCreate(&ev[i][0]); (void)hipEventCreate(&ev[i][1]); }
-    }
-  }
-  ~StageTimer() {
-    if (on) for (int i = 0; i < MGC_NUM_STAGES; i++) { (void)hipEventDestroy(ev[i][0]); (void)hipEventDestroy(ev[i][1]); }
-  }
-  void begin(int i) { if (on) { (void)hipEventRecord(ev[i][0], st); used[i] = true; } }
-  void end(int i)   { if (on) (void)hipEventRecord(ev[i][1], st); }
-};
-}  // namespace
-
-// One pass over bases that are resident in HBM (s->d_bases / s->n_bases): results stay in HBM.
-// ext_keys/ext_counts: k-mers already extracted and grouped by file by the caller (the owner side of a sharded
-// count): extraction and partition are skipped, the caller's buffer is processed in place.
-static int count_device(mgc_session *s, void *ext_keys = nullptr, const uint64_t *ext_counts = nullptr,
-                        uint32_t ext_bucket_bits = MGC_NUM_FILES_BITS) {
-  join_prepare(s);
-  s->free_result();
-  HIP_TRY(s, hipSetDevice(s->device));
-  hipStream_t st = s->stream;
-  const mgc_count_config &c = s->cfg;
-  const mgc::Switches &sw = s->sw;
-  const uint32_t k = c.k;
-  // buckets = the 64 files, or (sharded owner side) finer top-bit ranges of the k-mer: 2^bucket_bits of them
-  // The session's own partition uses the files while a file stays within what two grouping digits cover
-  // (1152 << 18 = 302 M k-mers); larger inputs are partitioned one or more bits finer -- the 64 files are ranges
-  // of buckets either way.
-  uint32_t bucket_bits = ext_keys ? ext_bucket_bits : (uint32_t)MGC_NUM_FILES_BITS;
-  if (!ext_keys) {
-    // `compress`: two dense-rank digits cover 3^10 sub-buckets (below), i.e. buckets of up to 68 M k-mers, and the digits
-    // are whole bases, so the buckets get finer two bits at a time
-    // (`compress` buckets are uneven -- a canonical k-mer starts with A or C twice as often as with G or T, and 36 of the 64 / 108 of the
-    // 256 bucket prefixes repeat no base -- so the largest bucket of a 10 Gbp input at 256 buckets holds ~100 M k-mers: above the 68 M of the
-    // index-claimed tables.  Round 6: such a bucket keeps its two dense-rank digits and is counted by the distinct-sized kernel,
-    // sub-buckets of up to 2304 k-mers on average, instead of falling back to the stable sort: hpc_stream[] below.)
-    auto per_bucket = [&](uint32_t) -> uint64_t {
-      if (sw.bucket_bases) return sw.bucket_bases;            // tests force finer buckets on small inputs
-      return c.homopoly_compress ? 60000000ull : 180000000ull;
-    };
-    const uint32_t step = c.homopoly_compress ? 2u : 1u;
-    while (bucket_bits + step <= MGC_MAX_BUCKET_BITS && bucket_bits + step <= 2 * c.k && (s->n_bases >> bucket_bits) > per_bucket(bucket_bits)) bucket_bits += step;
-  }
-  const uint32_t nb = 1u << bucket_bits;
-  const uint32_t kw = s->key_words;
-  const size_t   kbytes = sizeof(uint64_t) * kw;
-  memset(&s->prof, 0, sizeof(s->prof));
-
-  // ---- `compress`: homopolymer-compress the base stream on the device (merylInput.C:261-268) ----
-  const uint8_t *d_bases = s->d_bases;
-  uint64_t n_bases = s->n_bases;
-  if (c.homopoly_compress && n_bases && !ext_keys) {
-    HIP_TRY(s, s->ensure(mgc_session::B_HPC, n_bases));
-    HIP_TRY(s, s->ensure(mgc_session::B_HPC_WS, mgc::hpc_workspace_bytes(n_bases)));
-    uint8_t *d_hpc = reinterpret_cast<uint8_t *>(s->buf[mgc_session::B_HPC].p);
-    void *hws = s->buf[mgc_session::B_HPC_WS].p;
-    HIP_TRY(s, mgc::launch_homopoly_compress(d_bases, n_bases, d_hpc, hws, st));
-    uint64_t n_out = 0;
-    HIP_TRY(s, hipMemcpyAsync(&n_out, hws, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(s, hipStreamSynchronize(st));
-    d_bases = d_hpc;
-    n_bases = n_out;
-  }
-
-  hipEvent_t ev_all[2];
-  if (s->profiling) { (void)hipEventCreate(&ev_all[0]); (void)hipEventCreate(&ev_all[1]); (void)hipEventRecord(ev_all[0], st); }
-  StageTimer tm(s->profiling, st);
-
-  // ---- pass 1: per-file histogram ----
-  HIP_TRY(s, s->ensure(mgc_session::B_PART_WS, mgc::kp_workspace_bytes(bucket_bits)));
-  HIP_TRY(s, s->ensure(mgc_session::B_META, sizeof(uint64_t) * nb * 3));        // counts, starts, per-file K96 flags
-  void *part_ws = s->buf[mgc_session::B_PART_WS].p;
-  uint64_t *d_counts64 = reinterpret_cast<uint64_t *>(s->buf[mgc_session::B_META].p), *d_starts = d_counts64 + nb;
-  std::vector<uint64_t> h_counts_v(nb), h_starts_v(nb + 1);
-  uint64_t *h_counts = h_counts_v.data(), *h_starts = h_starts_v.data();
-  // The narrowed grouping passes (k <= ~25, below) group a file by its TOP digit first when that digit's histogram is at
-  // hand: the file histogram then counts fifteen top bits instead of six (one kernel, same read of the bases) and the
-  // 8 B/k-mer digit-histogram read of every file goes away.
-  const uint64_t *d_fine = nullptr;
-  const uint64_t *d_fine_hpc = nullptr;                              // `compress`: the dense-rank form of that histogram
-  if (!ext_keys) {
-    tm.begin(MGC_STAGE_HISTOGRAM);
-    // (two digits cover at most 18 bits: beyond 2k - 6 = 41 nothing narrows -- the files' WHOLE keys then take the same
-    // high-digit-first passes, mgc::launch_group_wide, 16-byte keys included; MGC_WIDE_MSD=0: low digit first off a histogram
-    // read of the keys, as `compress` always does: its digits are dense ranks)
-    const bool wide_msd_on = sw.wide_msd && !c.homopoly_compress;
-    if (n_bases >= (1u << 22) && ((kw == 1 && 2 * k - bucket_bits <= 41) || wide_msd_on) && mgc::kmer_histogram_fine_ok(k, bucket_bits, s->sfx_mask, sw)) {
-      HIP_TRY(s, s->ensure(mgc_session::B_FINE, sizeof(uint64_t) << 15));
-      uint64_t *fine = reinterpret_cast<uint64_t *>(s->buf[mgc_session::B_FINE].p);
-      HIP_TRY(s, mgc::launch_kmer_histogram_fine(d_bases, n_bases, k, c.mode, d_counts64, fine, part_ws, st, sw.const_k));
-      d_fine = fine;
-    } else if (c.homopoly_compress && n_bases >= (1u << 22) && (2 * k - bucket_bits) % 2 == 0 && 2 * k - bucket_bits >= 20 &&
-               sw.hpc_digits && mgc::kmer_histogram_hpc_ok(k, bucket_bits, s->sfx_mask, sw)) {
-      // `compress`: k-mers per (bucket, dense-rank digit below it) -- the buckets' high digit goes first as well (MGC_HPC_MSD=0: off)
-      HIP_TRY(s, s->ensure(mgc_session::B_FINE, sizeof(uint64_t) * std::max<size_t>((size_t)1 << 15, mgc::kmer_histogram_hpc_entries(bucket_bits))));
-      uint64_t *fine = reinterpret_cast<uint64_t *>(s->buf[mgc_session::B_FINE].p);
-      HIP_TRY(s, mgc::launch_kmer_histogram_hpc(d_bases, n_bases, k, c.mode, bucket_bits, d_counts64, fine, part_ws, st, sw.const_k));
-      d_fine_hpc = fine;
-    } else
-    HIP_TRY(s, mgc::launch_kmer_histogram(d_bases, n_bases, k, c.mode, bucket_bits, d_counts64, part_ws, st, s->sfx_mask, s->sfx_test));
-    tm.end(MGC_STAGE_HISTOGRAM);
-    s->prof.stage_launches[MGC_STAGE_HISTOGRAM] = 1;
-    HIP_TRY(s, hipMemcpyAsync(h_counts, d_counts64, sizeof(uint64_t) * nb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(s, hipStreamSynchronize(st));
-  } else {
-    memcpy(h_counts, ext_counts, sizeof(uint64_t) * nb);
-    // the owner side of a sharded count: the senders' fifteen-bit histograms, summed over the ranks (mgc_count_buckets_into), give
-    // every bucket's first grouping digit -- 15 - bucket_bits bits of it -- so that nobody reads the keys for a histogram here either
-    uint64_t n_ext = 0;
-    for (uint32_t b = 0; b < nb; b++) n_ext += h_counts[b];
-    const bool wide_msd_on = sw.wide_msd && !c.homopoly_compress;
-    if (s->ext_fine && sw.fine_hist && bucket_bits <= 8 && n_ext >= (1u << 22) && s->sfx_mask == 0 && !c.homopoly_compress &&
-        2 * k >= 15 + 2 && ((kw == 1 && 2 * k - bucket_bits <= 41) || wide_msd_on))
-      d_fine = s->ext_fine;
-  }
-  const uint32_t fine_bits = 15u - bucket_bits;              // bits of a bucket's first digit the fifteen-bit histogram knows (9 for the 64 files)
-  uint64_t N = 0, max_bucket = 0;
-  memset(s->file_instances, 0, sizeof(s->file_instances));
-  for (uint32_t b = 0; b < nb; b++) {
-    h_starts[b] = N;
-    N += h_counts[b];
-    max_bucket = std::max(max_bucket, h_counts[b]);
-    s->file_instances[b >> (bucket_bits - MGC_NUM_FILES_BITS)] += h_counts[b];
-  }
-  h_starts[nb] = N;
-  s->n_instances = N;
-
-  // ---- pass 2: pack + scatter into per-file regions ----
-  // Two ways from file-grouped k-mers to the (k-mer, count) stream:
-  //   finish (default): LSB-sort only the top t bits of every file globally, then sort the low bits of
-  //                     every sub-bucket in LDS with the run-length count fused in (mgc_finish.hip);
-  //   full   (MGC_FINISH=0, and the fallback for files with an oversized sub-bucket): LSB-sort all 2k-6
-  //                     bits globally, then the separate run-length kernels.
-  const bool use_finish = sw.finish;
-  mgc::SortPlan plan;
-  mgc::make_sort_plan(0, 2 * k - bucket_bits, &plan);
-  const bool odd = !use_finish && (plan.num_passes & 1u) != 0;
-  if (!ext_keys) HIP_TRY(s, s->ensure(mgc_session::B_X, kbytes * N));
-  HIP_TRY(s, s->ensure(mgc_session::B_Y, kbytes * (odd ? N : max_bucket)));
-  unsigned char *X = ext_keys ? reinterpret_cast<unsigned char *>(ext_keys) : reinterpret_cast<unsigned char *>(s->buf[mgc_session::B_X].p);
-  unsigned char *Y = reinterpret_cast<unsigned char *>(s->buf[mgc_session::B_Y].p);
-  // The partition is launched once the plan of the files is known (below): when every file takes the narrowed passes its
-  // k-mers leave as 5 bytes (u32 + u8 per file) instead of 8 -- the file's first grouping pass puts them together again.
-  bool partition_done = false;
-  std::vector<uint64_t> h_k96flags(nb, 0);                   // (lives until the partition's copy has been issued and the stream synchronised)
-  auto run_partition = [&](bool soa, bool k96 = false) -> int {
-    if (ext_keys || partition_done) return MGC_OK;
-    partition_done = true;
-    HIP_TRY(s, hipMemcpyAsync(d_starts, h_starts, sizeof(uint64_t) * nb, hipMemcpyHostToDevice, st));
-    uint64_t *d_k96flags = d_starts + nb;
-    if (k96) HIP_TRY(s, hipMemcpyAsync(d_k96flags, h_k96flags.data(), sizeof(uint64_t) * nb, hipMemcpyHostToDevice, st));
-    tm.begin(MGC_STAGE_PARTITION);
-    HIP_TRY(s, mgc::launch_kmer_partition(d_bases, n_bases, k, c.mode, bucket_bits, d_starts, (void *)X, part_ws, st,
-                                          s->sfx_mask, s->sfx_test, k96 ? d_k96flags : (soa ? d_counts64 : nullptr), sw.const_k));
-    tm.end(MGC_STAGE_PARTITION);
-    s->prof.hist_bytes = n_bases;
-    s->prof.partition_bytes = n_bases;
-    for (uint32_t b = 0; b < nb; b++) s->prof.partition_bytes += h_counts[b] * (soa ? 5u : ((k96 && h_k96flags[b]) ? 12u : (uint64_t)kbytes));
-    s->prof.stage_launches[MGC_STAGE_PARTITION] = 2;
-    return MGC_OK;
-  };
-  uint32_t soa_hi_mask = 0;                                  // nonzero: the files lie in the 5-byte layout
-  std::vector<char> file_k96(nb, 0), k96_passes(nb, 0);      // files that lie as 12-byte K96 records (k = 33..51; below); ... and whose passes moved them
-
-  // ---- per-file LSB radix sort of the low 2k-6 bits ----
-  const size_t sort_ws_bytes = mgc::sort_workspace_bytes(max_bucket) + 256;
-  HIP_TRY(s, s->ensure(mgc_session::B_SORT_WS, sort_ws_bytes));
-  void *sort_ws = s->buf[mgc_session::B_SORT_WS].p;
-  // device flags: [0] look-back timeout, [1] scratch answer of the hash probe, [2] overflow of a streamed sub-bucket
-  uint32_t *d_err = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(sort_ws) + sort_ws_bytes - 256);
-  HIP_TRY(s, hipMemsetAsync(d_err, 0, 32, st));
-
-  const uint32_t rem_bits = 2 * k - bucket_bits;
-  const uint32_t ev_per_file = 2 * 16;                     // room for 16 passes per file
-  std::vector<hipEvent_t> pass_ev;
-  std::vector<uint32_t> file_passes(nb, 0);
-  std::vector<char> narrowed(nb, 0);                       // files whose grouping passes ran on 32-bit words
-  if (s->profiling) {
-    pass_ev.resize((size_t)nb * ev_per_file);
-    for (auto &e : pass_ev) (void)hipEventCreate(&e);
-  }
-  uint32_t sort_launch_groups = 0;
-  uint64_t nd = 0;
-
-  if (!use_finish) {
-    { const int prc = run_partition(false); if (prc != MGC_OK) return prc; }
-    tm.begin(MGC_STAGE_SORT);
-    for (uint32_t b = 0; b < nb; b++) {
-      if (h_counts[b] == 0) continue;
-      void *src = X + kbytes * h_starts[b];
-      void *alt = odd ? (void *)(Y + kbytes * h_starts[b]) : (void *)Y;
-      int in_alt = 0;
-      hipEvent_t *pe = s->profiling ? &pass_ev[(size_t)b * ev_per_file] : nullptr;
-      HIP_TRY(s, mgc::launch_radix_sort(src, alt, h_counts[b], kw, plan, sort_ws, sort_ws_bytes - 256, d_err, &in_alt, st, pe));
-      file_passes[b] = plan.num_passes;
-      sort_launch_groups++;
-      (void)in_alt;   // odd pass count: every file ends in Y at the same offsets; even: back in X
-    }
-    tm.end(MGC_STAGE_SORT);
-    void *d_sorted = odd ? (void *)Y : (void *)X;
-
-    // ---- run-length count ----
-    HIP_TRY(s, s->ensure(mgc_session::B_RLE_WS, mgc::rle_workspace_bytes(N)));
-    void *rle_ws = s->buf[mgc_session::B_RLE_WS].p;
-    tm.begin(MGC_STAGE_RLE);
-    HIP_TRY(s, mgc::launch_rle_count(d_sorted, N, kw, rle_ws, st));
-    HIP_TRY(s, mgc::rle_read_total(rle_ws, &nd, st));
-    s->n_distinct = nd;
-    HIP_TRY(s, s->ensure(mgc_session::B_UNIQUE, kbytes * nd));
-    HIP_TRY(s, s->ensure(mgc_session::B_COUNTS, sizeof(uint32_t) * nd));
-    s->d_unique = s->buf[mgc_session::B_UNIQUE].p;
-    s->d_counts = reinterpret_cast<uint32_t *>(s->buf[mgc_session::B_COUNTS].p);
-    HIP_TRY(s, mgc::launch_rle_emit(d_sorted, N, kw, rle_ws, s->d_unique, s->d_counts, st));
-    tm.end(MGC_STAGE_RLE);
-    s->prof.stage_launches[MGC_STAGE_RLE] = 3;
-  } else {
-    // ---- plan: per file, t top bits so that a sub-bucket holds ~target k-mers ----
-    const uint64_t target = mgc::finish_target_for(kw, sw), cap = mgc::finish_capacity_for(kw);
-    std::vector<uint32_t> top_bits(nb);
-    std::vector<char> hpc_digits(nb, 0);
-    std::vector<uint64_t> gbase(nb + 1), sbase(nb + 1);
-    gbase[0] = sbase[0] = 0;
-    // fstream[b] (round 6): the file takes the DISTINCT-sized count (hash_count_stream_kernel: up to 4094 keys per sub-bucket streamed
-    // through a table that holds ~1280 distinct suffixes) and with it one grouping bit fewer -- sub-buckets of 1152..2304 k-mers on
-    // average instead of 576..1152, so that a file of up to 302 M k-mers groups by an eight-bit first digit (256-byte runs out of
-    // the 16384-key tiles instead of 128-byte ones).  Narrowed files whose suffix fits the packed entry (8..20 bits).
-    std::vector<char> fstream(nb, 0);
-    std::vector<uint32_t> top_str(nb, 0);                              // the candidate: grouping bits under that plan (0: none)
-    const bool stream_on = sw.hash_stream != 0 && kw == 1 && !c.homopoly_compress;
-    const uint64_t starget = mgc::finish_stream_target(sw);
-    // `compress`: the grouping digits are dense ranks of five homopolymer-free bases (make_hpc_group_plan): 10 key bits
-    // hold 243 patterns, 20 bits 59049.  Needs the remaining bits to be whole bases (the 64 files, or an even number of
-    // bucket bits) and the bucket to fit 59049 sub-buckets; otherwise the generic bit digits below (MGC_HPC_DIGITS=0: always).
-    const bool hpc_ok = sw.hpc_digits && c.homopoly_compress && (rem_bits % 2 == 0) && bucket_bits >= 2;
-    // hpc_stream[b] (round 6): a two-digit `compress` bucket whose sub-buckets average more than the index-claimed tables take counts
-    // its whole 8-byte k-mers with the distinct-sized kernel (64-bit entries): everything the high-digit-first passes of such a
-    // bucket need is known here (the dense-rank histogram is at hand, the suffix has 32..52 bits), so the plan is final at once
-    const bool hpc_stream_ok = hpc_ok && sw.hash_stream != 0 && sw.hash_stream != 2 && kw == 1 && d_fine_hpc && nb <= 256 && sw.wide_msd &&
-                               rem_bits >= 20 + 32 && mgc::finish_stream_ok(kw, rem_bits - 20, false);
-    std::vector<char> hpc_stream(nb, 0), hpc_cand(nb, 0);
-    // hpc_mixed[b]: a candidate bucket of a size at which 3^9 sub-buckets (dense-rank high digit + the plain eight bits of four bases:
-    // make_hpc_mixed_plan) average what the distinct-sized count likes (0.3 .. 1 of its target: 700 .. 2304 k-mers) -- 3^10 of them hold a few hundred k-mers
-    // each at 5 Gbp and the count kernel's per-sub-bucket steps dominate.  Taken where the probe says coverage is high.
-    std::vector<char> hpc_mixed(nb, 0);
-    const bool hpc_mixed_ok = hpc_stream_ok && rem_bits >= 18 + 32 && mgc::finish_stream_ok(kw, rem_bits - 18, false) && mgc::finish_can_stream(kw, rem_bits - 18);
-    for (uint32_t b = 0; b < nb; b++) {
-      uint32_t t = 0;
-      if (hpc_ok && h_counts[b] > target) {                            // sub-buckets average `target` k-mers or fewer
-        if (h_counts[b] <= 243ull * target && rem_bits >= 10) t = 10;
-        else if (h_counts[b] <= 59049ull * target && rem_bits >= 20) t = 20;
-        else if (hpc_stream_ok && h_counts[b] <= 59049ull * starget && h_counts[b] < (1ull << 30)) { t = 20; hpc_stream[b] = 1; }
-        if (t == 20 && sw.hash_stream == 1 && hpc_stream_ok && h_counts[b] < (1ull << 30)) hpc_stream[b] = 1;   // (tests, A/B: every two-digit bucket)
-        if (t) hpc_digits[b] = 1;                                      // else (tiny k, gigantic bucket): generic path
-      }
-      if (!hpc_digits[b]) {
-        while (t < rem_bits && t < 26 && (h_counts[b] >> t) > target) t++;
-        // tests reach the large-input plans (two nine-bit digits, 18-bit suffixes at k = 21) on small inputs
-        if (sw.min_top) { const uint32_t m = sw.min_top; if (h_counts[b] && t < m) t = m < rem_bits ? m : rem_bits; }
-        if (stream_on && h_counts[b]) {
-          uint32_t ts = 0;
-          while (ts < rem_bits && ts < 26 && (h_counts[b] >> ts) > starget) ts++;
-          if (sw.min_top) { const uint32_t m = sw.min_top; if (ts < m) ts = m < rem_bits ? m : rem_bits; }
-          top_str[b] = ts;                                             // (clamped and validated once the file's kind of passes is known: below)
-        }
-      }
-      if (c.homopoly_compress && t && !hpc_digits[b]) {
-        // homopolymer-compressed sequence never repeats a base: every 2-bit group after the first takes 3 of its 4
-        // values, so only (3/4)^(t/2) of the 2^t top-bit patterns occur and the occupied sub-buckets are that much
-        // larger than planned: log2(4/3)/2 = 0.2075 of every key bit carries no information
-        const double scale = 1.0 / (1.0 - 0.2075);
-        const uint32_t tc = (uint32_t)((double)t * scale + 0.5);
-        t = tc < rem_bits ? (tc < 26 ? tc : 26) : rem_bits;
-      }
-      top_bits[b] = t;
-    }
-
-    // ---- A. global LSB passes on the top bits only ----
-    // the finish only needs the file grouped by its top bits
-    std::vector<mgc::SortPlan> fplan(nb);
-    // narrow[b]: the file's k-mers travel as 32-bit words from the first grouping pass on (mgc::launch_group_narrow)
-    std::vector<char> narrow(nb, 0);
-    // wide_msd[b]: the file's whole keys take the high-digit-first passes (mgc::launch_group_wide)
-    std::vector<char> wide_msd(nb, 0);
-    std::vector<uint32_t> tr_a(nb, 0), tr_b(nb, 0);        // ... and in which order its sub-buckets lie (mgc::tr_index)
-    const size_t hdr_bytes = mgc::sort_header_bytes();
-    // msd_ok[b]: the histogram of the bucket's HIGH digit is at hand (the fifteen-bit histogram holds fine_bits bits below the bucket:
-    // a plan whose high digit is wider gives bits to the low one; a low digit that would pass nine bits keeps the low digit first)
-    std::vector<char> msd_ok(nb, 1);
-    auto fit_split = [&](uint32_t b) {
-      mgc::SortPlan &fp = fplan[b];
-      if (!d_fine || fp.num_passes != 2 || fp.hpc || fp.pass_bits[1] <= fine_bits) return;
-      const uint32_t t = fp.pass_bits[0] + fp.pass_bits[1];
-      if (t - fine_bits > 9) { msd_ok[b] = 0; return; }
-      fp.pass_bits[1] = fine_bits; fp.pass_bits[0] = t - fine_bits;
-      fp.pass_shift[1] = fp.pass_shift[0] + fp.pass_bits[0];
-    };
-    for (uint32_t b = 0; b < nb; b++) {
-      if (h_counts[b] == 0 || top_bits[b] == 0) continue;
-      if (hpc_digits[b]) {
-        mgc::make_hpc_group_plan(rem_bits - top_bits[b], top_bits[b] / 10, &fplan[b]);
-        // (sub-bucket numbers made of dense ranks are no key bits: the kernels that put a k-mer's top bits back from its sub-bucket
-        // number -- 32-bit suffixes -- stay with the low digit first)
-        wide_msd[b] = d_fine_hpc && nb <= 256 && top_bits[b] == 20 && (kw == 2 || rem_bits - top_bits[b] >= 32) &&
-                      mgc::finish_can_stream(kw, rem_bits - top_bits[b]) && mgc::sort_plan_wide_msd(fplan[b], h_counts[b], sw.wide_msd);
-        // (above the index-claimed tables' reach: the distinct-sized count whatever the coverage; below: a candidate the probe file decides on)
-        if (hpc_stream[b] && wide_msd[b]) { fstream[b] = 1; s->prof.stream_files++; }
-        else if (hpc_stream_ok && wide_msd[b] && top_bits[b] == 20 && h_counts[b] < (1ull << 30)) hpc_cand[b] = 1;
-        if ((hpc_cand[b] || (fstream[b] && sw.hash_stream == 1)) && hpc_mixed_ok && h_counts[b] >= 19683ull * (starget * 3 / 10) &&
-            h_counts[b] <= 19683ull * starget) {
-          mgc::SortPlan mp;
-          mgc::make_hpc_mixed_plan(rem_bits - 18, &mp);
-          hpc_mixed[b] = mgc::sort_plan_wide_msd(mp, h_counts[b], sw.wide_msd) ? 1 : 0;
-          if (hpc_mixed[b] && sw.hash_stream == 1) {                   // (tests, A/B: no probe)
-            top_bits[b] = 18; fplan[b] = mp; s->prof.hpc_mixed_files++;
-            if (!fstream[b]) { fstream[b] = 1; s->prof.stream_files++; }
-            hpc_mixed[b] = 0; hpc_cand[b] = 0;
-          }
-        }
-        continue;
-      }
-      mgc::make_sort_plan(rem_bits - top_bits[b], rem_bits, &fplan[b]);
-      if (fplan[b].mode == 0) fplan[b].mode = 3;
-      fit_split(b);
-      const uint32_t low = rem_bits - top_bits[b];
-      narrow[b] = low < 32 && mgc::finish_can_stream(kw, low) && mgc::sort_plan_narrows(fplan[b], h_counts[b], kw, sw.narrow);
-      // (only the hash-count kernels translate the sub-bucket numbers of whole keys)
-      wide_msd[b] = !narrow[b] && d_fine && nb <= 256 && msd_ok[b] && mgc::finish_can_stream(kw, low) &&
-                    mgc::sort_plan_wide_msd(fplan[b], h_counts[b], sw.wide_msd);
-      if (top_str[b]) {
-        // the coarser plan stays a candidate if the file narrows under BOTH plans, its suffix then has to fit the packed 32-bit entry
-        // (20 bits) -- or if its whole 8-byte k-mers take the high-digit-first passes under both (k = 24..32: 64-bit entries, 52 bits)
-        uint32_t ts = top_str[b];
-        const uint32_t t = top_bits[b], max_low = narrow[b] ? 20u : 52u;
-        if (rem_bits - ts > max_low) ts = rem_bits - max_low;
-        // (a plan that does not coarsen the file keeps the kernels it has -- unless MGC_HASH_STREAM=1 asks for the new one)
-        bool ok = ts >= 1 && ts <= t && ts <= 18 && (ts < t || sw.hash_stream == 1) && (narrow[b] || (wide_msd[b] && kw == 1 && sw.hash_stream != 2)) &&
-                  h_counts[b] < (1ull << 32) && mgc::finish_stream_ok(kw, rem_bits - ts, narrow[b] != 0) && mgc::finish_can_stream(kw, rem_bits - ts);
-        if (ok) {
-          mgc::SortPlan sp;
-          mgc::make_sort_plan(rem_bits - ts, rem_bits, &sp);
-          if (sp.mode == 0) sp.mode = 3;
-          if (narrow[b]) ok = mgc::sort_plan_narrows(sp, h_counts[b], kw, sw.narrow);
-          else {
-            // (whole keys need the high digit's histogram at hand under the coarser plan as well: fit_split's test)
-            const bool split_ok = !(d_fine && sp.num_passes == 2 && sp.pass_bits[1] > fine_bits && ts - fine_bits > 9);
-            ok = split_ok && mgc::sort_plan_wide_msd(sp, h_counts[b], sw.wide_msd);
-          }
-        }
-        top_str[b] = ok ? ts : 0;
-      }
-    }
-    // a file's sub-bucket tables are laid out for the FINER of its two plans (2^top_bits slots); ngf(b) of them are in use
-    for (uint32_t b = 0; b < nb; b++) {
-      const uint64_t ng = h_counts[b] ? ((uint64_t)1 << top_bits[b]) : 0;
-      gbase[b + 1] = gbase[b] + ng;
-      sbase[b + 1] = sbase[b] + (ng ? ng + 1 : 0);
-    }
-    auto ngf = [&](uint32_t b) -> uint64_t { return h_counts[b] ? ((uint64_t)1 << top_bits[b]) : 0; };
-    auto take_mixed_plan = [&](uint32_t b) {
-      top_bits[b] = 18;
-      mgc::make_hpc_mixed_plan(rem_bits - 18, &fplan[b]);
-      s->prof.hpc_mixed_files++;
-    };
-    auto take_stream_plan = [&](uint32_t b) {                // the candidate becomes the file's plan (narrow[] / wide_msd[] stay as they are)
-      fstream[b] = 1; top_bits[b] = top_str[b];
-      mgc::make_sort_plan(rem_bits - top_bits[b], rem_bits, &fplan[b]);
-      if (fplan[b].mode == 0) fplan[b].mode = 3;
-      msd_ok[b] = 1;
-      fit_split(b);
-      s->prof.stream_files++;
-    };
-    // Which plan?  The distinct-sized count pays off when a sub-bucket's distinct suffixes are few against its keys (measured at
-    // 10 Gbp, profiles/r06_coverage_ab.txt: D / N = 0.14 -> -3.6 ms, 0.24 -> -1.5, 0.45 -> +3, 0.72 -> +50: above its table the retry
-    // launch counts the sub-bucket a second time), and D / N is not known before something has been counted: ONE file -- the PROBE
-    // file, the smallest one that is still a fair sample -- goes through its passes and its count first, on the finer plan; its
-    // distinct / instances ratio (one 8-byte copy) decides for the others.  MGC_HASH_STREAM=1: every candidate, no probe; 0: none.
-    int probe = -1;
-    {
-      bool any_cand = false;
-      for (uint32_t b = 0; b < nb; b++) any_cand = any_cand || top_str[b] != 0 || hpc_cand[b] != 0;
-      if (any_cand && sw.hash_stream == 1) { for (uint32_t b = 0; b < nb; b++) if (top_str[b]) take_stream_plan(b); }
-      else if (any_cand) {
-        uint64_t best = ~0ull;
-        for (uint32_t b = 0; b < nb; b++)
-          if (h_counts[b] >= max_bucket / 16 && h_counts[b] >= 4096 && h_counts[b] < best) { best = h_counts[b]; probe = (int)b; }
-      }
-    }
-    const uint64_t ng_total = gbase[nb];
-    HIP_TRY(s, s->ensure(mgc_session::B_SUBSTART, sizeof(uint64_t) * (sbase[nb] + 1)));
-    HIP_TRY(s, s->ensure(mgc_session::B_GROUPS, sizeof(uint64_t) * (ng_total + 2 + 3 * (uint64_t)nb)));
-    HIP_TRY(s, s->ensure(mgc_session::B_LARGE, sizeof(uint32_t) * (ng_total + 1)));
-    HIP_TRY(s, s->ensure(mgc_session::B_NONEMPTY, sizeof(uint32_t) * (ng_total + 1) + sizeof(uint64_t) * 2 * ((uint64_t)nb + 1)));
-    HIP_TRY(s, s->ensure(mgc_session::B_GSCAN, mgc::finish_scan_scratch_bytes(ng_total + 1)));
-    HIP_TRY(s, s->ensure(mgc_session::B_RLE_WS, mgc::rle_workspace_bytes(max_bucket)));
-    uint64_t *d_substart = reinterpret_cast<uint64_t *>(s->buf[mgc_session::B_SUBSTART].p);
-    uint64_t *d_group    = reinterpret_cast<uint64_t *>(s->buf[mgc_session::B_GROUPS].p);   // [ng_total+1], then the files' statistics
-    // per file, three words side by side (one small copy brings a file's back): [0] its largest sub-bucket, [1] how many are
-    // above the persistent kernels' capacity, [2] how many are not empty
-    uint64_t *d_stats    = d_group + ng_total + 1;
-    auto d_maxsub  = [&](uint32_t b) { return d_stats + 3 * (size_t)b; };
-    auto d_nlarge  = [&](uint32_t b) { return d_stats + 3 * (size_t)b + 1; };
-    auto d_nzcount = [&](uint32_t b) { return d_stats + 3 * (size_t)b + 2; };
-    uint32_t *d_large    = reinterpret_cast<uint32_t *>(s->buf[mgc_session::B_LARGE].p);
-    uint64_t *d_retrycnt = reinterpret_cast<uint64_t *>(s->buf[mgc_session::B_NONEMPTY].p) + nb + 1;  // [nb] retry lists of the count kernels
-    uint32_t *d_nz       = reinterpret_cast<uint32_t *>(d_retrycnt + nb + 1);                         // [ng_total] (a dense file's part: its retry list)
-    HIP_TRY(s, hipMemsetAsync(s->buf[mgc_session::B_NONEMPTY].p, 0, sizeof(uint64_t) * 2 * ((size_t)nb + 1), st));
-    HIP_TRY(s, hipMemsetAsync(d_group, 0, sizeof(uint64_t) * (ng_total + 1 + 3 * (size_t)nb), st));   // empty sub-buckets stay 0
-    void     *rle_ws     = s->buf[mgc_session::B_RLE_WS].p;
-    {
-      // 5-byte layout: 8-byte keys with 33..40 bits below the file (k = 20..23), every non-empty file on the narrowed passes with
-      // the high digit first off the fifteen-bit histogram (the instrumented instantiation reads whole keys).  MGC_SOA5=0: whole keys.
-      bool soa = sw.soa5 && !ext_keys && kw == 1 && nb == 64 && d_fine && rem_bits > 32 && rem_bits <= 40 && s->sfx_mask == 0;
-      for (uint32_t b = 0; b < nb && soa; b++) if (h_counts[b] && !(narrow[b] && top_bits[b])) soa = false;
-      if (soa) soa_hi_mask = (1u << (rem_bits - 32)) - 1u;
-      // K96 records (round 5): 16-byte keys with at most 96 bits below the file (k = 33..51), every non-empty file on the whole-key
-      // high-digit-first passes: 12 of the 16 bytes leave the partition, go through both passes and into the count kernel
-      // (mgc_common.hpp K96; the region of a file stays 16 bytes per k-mer, so a file can be widened back in place).  MGC_K96=0: whole keys.
-      bool k96 = sw.k96 && !ext_keys && kw == 2 && nb == 64 && d_fine && rem_bits <= 96 && s->sfx_mask == 0 && !c.homopoly_compress;
-      bool any96 = false;                                             // per file: the ones on the two-digit whole-key passes (a small file keeps 16-byte keys)
-      for (uint32_t b = 0; b < nb && k96; b++) if (h_counts[b] && wide_msd[b] && top_bits[b]) { file_k96[b] = 1; h_k96flags[b] = 1; any96 = true; s->prof.k96_files++; }
-      const int prc = run_partition(soa, k96 && any96);
-      if (prc != MGC_OK) return prc;
-    }
-    // Where the counts of a file's distinct k-mers wait for the packing step (one uint32 per k-mer instance position).  A NARROWED
-    // file keeps 4-byte words in the front half of its 8-byte region from the first grouping pass on: the back half is free and
-    // takes the counts -- no buffer of its own (35 GB of the 123 GB arena at 10 Gbp; a large first hipMalloc is the slowest thing
-    // a freshly started process does, profiles/r03m_e2e_io.txt).  The other files share B_CNT_TMP; a narrowed file that has to be
-    // widened back later (a sub-bucket nothing can stream) gets a buffer of its own then.
-    std::vector<uint32_t *> cnt_ptr(nb, nullptr);
-    std::deque<DevBuf> cnt_extra;                           // (a deque: DevBuf owns its pointer and must not be relocated)
-    {
-      uint64_t wide_total = 0;
-      for (uint32_t b = 0; b < nb; b++) if (!narrow[b]) wide_total += h_counts[b];
-      HIP_TRY(s, s->ensure(mgc_session::B_CNT_TMP, sizeof(uint32_t) * wide_total));
-      uint32_t *wide = reinterpret_cast<uint32_t *>(s->buf[mgc_session::B_CNT_TMP].p);
-      uint64_t at = 0;
-      for (uint32_t b = 0; b < nb; b++) {
-        if (narrow[b]) cnt_ptr[b] = reinterpret_cast<uint32_t *>(X + kbytes * h_starts[b]) + h_counts[b];
-        else { cnt_ptr[b] = wide + at; at += h_counts[b]; }
-      }
-    }
-    tm.begin(MGC_STAGE_SORT);
-    // high digit first: the headers of all narrowed files in one launch, their look-back granules zeroed in one memset
-    std::vector<size_t> nws_off(nb + 1, 0);
-    unsigned char *d_nws = nullptr, *d_nhdrs = nullptr;
-    // (with a probe file: its header first, the others' once their plan is known)
-    auto prepare_headers = [&](int only, int skip) -> int {
-      unsigned char bits_a[256] = {0}, on[256] = {0};
-      bool any = false;
-      for (uint32_t b = 0; b < nb; b++) {
-        if ((!narrow[b] && !wide_msd[b]) || !msd_ok[b] || (only >= 0 && (int)b != only) || (int)b == skip) continue;
-        on[b] = 1; bits_a[b] = (unsigned char)fplan[b].pass_bits[1]; any = true;
-      }
-      if (any) HIP_TRY(s, mgc::launch_narrow_prepare(d_fine, nb, bits_a, on, d_nhdrs, st));
-      return MGC_OK;
-    };
-    if (d_fine && nb <= 256) {
-      bool any = false;
-      for (uint32_t b = 0; b < nb; b++) {
-        nws_off[b + 1] = nws_off[b];
-        if ((!narrow[b] && !wide_msd[b]) || !msd_ok[b]) continue;
-        any = true;
-        nws_off[b + 1] += ((narrow[b] ? mgc::narrow_scratch_bytes(h_counts[b]) : mgc::wide_scratch_bytes(h_counts[b], kw)) + 255) / 256 * 256;
-      }
-      if (any) {
-        HIP_TRY(s, s->ensure(mgc_session::B_SORT_HDRS, hdr_bytes * nb));
-        HIP_TRY(s, s->ensure(mgc_session::B_NARROW_WS, nws_off[nb]));
-        d_nhdrs = reinterpret_cast<unsigned char *>(s->buf[mgc_session::B_SORT_HDRS].p);
-        d_nws = reinterpret_cast<unsigned char *>(s->buf[mgc_session::B_NARROW_WS].p);
-        { const int prc = prepare_headers(probe >= 0 ? probe : -1, -1); if (prc != MGC_OK) return prc; }
-        HIP_TRY(s, hipMemsetAsync(d_nws, 0, nws_off[nb], st));
-      }
-    }
-    if (d_fine_hpc && nb <= 256) {
-      uint64_t on[4] = {0, 0, 0, 0};
-      bool any = false;
-      for (uint32_t b = 0; b < nb; b++) {
-        nws_off[b + 1] = nws_off[b];
-        if (!wide_msd[b]) continue;
-        on[b >> 6] |= 1ull << (b & 63u); any = true;
-        nws_off[b + 1] += (mgc::wide_scratch_bytes(h_counts[b], kw) + 255) / 256 * 256;
-      }
-      if (any) {
-        HIP_TRY(s, s->ensure(mgc_session::B_SORT_HDRS, hdr_bytes * nb));
-        HIP_TRY(s, s->ensure(mgc_session::B_NARROW_WS, nws_off[nb]));
-        d_nhdrs = reinterpret_cast<unsigned char *>(s->buf[mgc_session::B_SORT_HDRS].p);
-        d_nws = reinterpret_cast<unsigned char *>(s->buf[mgc_session::B_NARROW_WS].p);
-        HIP_TRY(s, mgc::launch_hpc_prepare(d_fine_hpc, bucket_bits, on, d_nhdrs, st));
-        HIP_TRY(s, hipMemsetAsync(d_nws, 0, nws_off[nb], st));
-      }
-    }
-    // Stage after stage: the passes of all files go to the session stream back to back, one synchronisation brings the files'
-    // statistics back, then the count kernels run.  (A pipelined form -- a file's count kernel on another stream as soon as its
-    // statistics are back, beside the passes of the files after it -- was built in round 4, measured slower and removed in round 5:
-    // profiles/r04y_pipe_ab.txt, DESIGN_HISTORY.md.)
-    if (s->h_stats_cap < 3 * (size_t)nb) {
-      if (s->h_stats) { (void)hipHostFree(s->h_stats); s->h_stats = nullptr; s->h_stats_cap = 0; }
-      HIP_TRY(s, hipHostMalloc(reinterpret_cast<void **>(&s->h_stats), sizeof(uint64_t) * 3 * (size_t)nb, hipHostMallocDefault));
-      s->h_stats_cap = 3 * (size_t)nb;
-    }
-    unsigned char *huge_alt = Y;
-
-    // ---- A + B/C of one file: its grouping passes, then its sub-bucket boundaries and its largest sub-bucket ----
-    auto group_file = [&](uint32_t b) -> int {
-      if (h_counts[b] == 0) return MGC_OK;
-      const mgc::SortPlan &fp = fplan[b];
-      void *src = X + kbytes * h_starts[b];
-      int in_alt = 0;
-      hipEvent_t *pe = s->profiling ? &pass_ev[(size_t)b * ev_per_file] : nullptr;
-      if (top_bits[b] == 0) {
-        // (a file of one sub-bucket: nothing to group)
-      } else if (narrow[b]) {                                // X (8 B) -> Y (4 B) -> front of X (4 B); boundaries included
-        const bool msd = d_nhdrs && d_nws && msd_ok[b];
-        HIP_TRY(s, mgc::launch_group_narrow(src, (void *)Y, h_counts[b], fp, sort_ws, sort_ws_bytes - 256, d_err, d_substart + sbase[b], st, pe,
-                                            msd ? (void *)(d_nhdrs + hdr_bytes * b) : nullptr, msd ? (void *)(d_nws + nws_off[b]) : nullptr,
-                                            &tr_a[b], &tr_b[b], soa_hi_mask, sw.group_dbg, sw.group_pipe, sw.pass_stagger));
-        file_passes[b] = 2;
-        narrowed[b] = 1;
-        sort_launch_groups++;
-      } else if (wide_msd[b] && d_nhdrs) {                   // X -> Y -> X, whole keys; boundaries included
-        HIP_TRY(s, mgc::launch_group_wide(src, (void *)Y, h_counts[b], kw, fp, d_err, d_substart + sbase[b], st, pe,
-                                          (void *)(d_nhdrs + hdr_bytes * b), (void *)(d_nws + nws_off[b]), &tr_a[b], &tr_b[b], file_k96[b] != 0));
-        file_passes[b] = 2;
-        k96_passes[b] = file_k96[b];
-        sort_launch_groups++;
-        s->prof.wide_msd_files++;
-      } else {
-        wide_msd[b] = 0;
-        HIP_TRY(s, mgc::launch_radix_sort(src, (void *)Y, h_counts[b], kw, fp, sort_ws, sort_ws_bytes - 256, d_err, &in_alt, st, pe));
-        if (in_alt) HIP_TRY(s, hipMemcpyAsync(src, Y, kbytes * h_counts[b], hipMemcpyDeviceToDevice, st));
-        file_passes[b] = fp.num_passes;
-        sort_launch_groups++;
-      }
-      return MGC_OK;
-    };
-    auto stats_file = [&](uint32_t b) -> int {
-      if (h_counts[b] == 0) return MGC_OK;
-      if (narrow[b] || wide_msd[b])
-        HIP_TRY(s, mgc::launch_subbucket_max(d_substart + sbase[b], kw, rem_bits - top_bits[b], top_bits[b], d_maxsub(b),
-                                             d_large + gbase[b], d_nlarge(b), d_nz + gbase[b], d_nzcount(b), st,
-                                             fstream[b] ? mgc::finish_stream_capacity() : 0));
-      else
-        HIP_TRY(s, mgc::launch_subbucket_bounds(X + kbytes * h_starts[b], h_counts[b], kw, rem_bits - top_bits[b], top_bits[b],
-                                                d_substart + sbase[b], d_maxsub(b), d_large + gbase[b], d_nlarge(b),
-                                                d_nz + gbase[b], d_nzcount(b), st));
-      return MGC_OK;
-    };
-    std::vector<uint64_t> h_maxsub(nb, 0), h_nlarge(nb, 0), h_nzcount(nb, 0);
-    uint32_t grouped = 0;                                    // files [0, grouped) have their passes on the session stream
-    auto group_upto = [&](uint32_t end) -> int {
-      for (; grouped < end && grouped < nb; grouped++) {
-        if ((int)grouped != probe) { const int rc = group_file(grouped); if (rc != MGC_OK) return rc; }   // (the probe file went first)
-        if (grouped + 1 == nb) {
-          tm.end(MGC_STAGE_SORT);
-          tm.begin(MGC_STAGE_RLE);
-          // the small statistics kernels of all files back to back: they run beside each other
-          for (uint32_t b = 0; b < nb; b++) { if ((int)b == probe) continue; const int rc2 = stats_file(b); if (rc2 != MGC_OK) return rc2; }
-          HIP_TRY(s, hipMemcpyAsync(s->h_stats, d_stats, sizeof(uint64_t) * 3 * (size_t)nb, hipMemcpyDeviceToHost, st));
-        }
-      }
-      return MGC_OK;
-    };
-
-    // ---- D. finish every file: LDS sort + count, or the full-sort fallback ----
-    // The streaming kernel of a file's oversized sub-buckets goes to a second stream: it touches other sub-buckets than
-    // the persistent kernel, and one gigantic sub-bucket occupies ONE workgroup for hundreds of microseconds -- beside
-    // the persistent kernels of this and the next files that tail costs nothing.
-    const bool fork_huge = s->stream2 != nullptr;
-    hipStream_t st_huge = fork_huge ? s->stream2 : st;
-    // The persistent kernels of odd files go to the second stream too, so that the tail of one file's launch overlaps the
-    // head of the next: finish stage 58.5 -> 54.2 ms per 10 Gbp.  All streaming kernels stay on stream2: they share one
-    // second buffer.
-    const bool alt_files = fork_huge;
-    bool forked = false, need_join = false;          // forked: stream2 is ordered after everything st holds that it must see
-    // Round 6: the streaming kernels of different files on up to FOUR streams, each with a second buffer of its own.  One gigantic
-    // sub-bucket (a repeat family's k-mers: 266 K keys at 30x of a 10 % repeat genome) occupies ONE workgroup for ~600 us; with every
-    // file's streaming launch queued on one stream those tails added up to 39 ms of a 57 ms count stage (profiles/r06y: BASELINE config 3's
-    // read shape at 10 Gbp) while the device had room for all of them at once.  MGC_HUGE_STREAMS=1: one stream (round 5).
-    constexpr int NH = 1 + mgc_session::HUGE_EXTRA;
-    hipStream_t hstream[NH];
-    unsigned char *halt[NH];
-    void *hws[NH] = {nullptr, nullptr, nullptr, nullptr};     // the sliced count of gigantic sub-buckets: one plan workspace per stream (launch_finish_file)
-    const size_t hws_bytes = mgc::finish_huge_workspace_bytes(max_bucket);
-    int n_huge_streams = 1, huge_next = 0;
-    hstream[0] = st_huge; halt[0] = Y;
-    auto huge_sync_all = [&]() -> int {               // (the host waits for every streaming kernel: Y and its siblings are free)
-      for (int i = 0; i < n_huge_streams; i++) HIP_TRY(s, hipStreamSynchronize(hstream[i]));
-      return MGC_OK;
-    };
-    auto huge_join_all = [&]() -> int {               // (st is ordered behind every streaming kernel)
-      for (int i = 0; i < n_huge_streams; i++) {
-        HIP_TRY(s, hipEventRecord(s->ev_join, hstream[i]));
-        HIP_TRY(s, hipStreamWaitEvent(st, s->ev_join, 0));
-      }
-      return MGC_OK;
-    };
-    // (The streams are created on first need, behind all the others: HIP maps streams onto a few hardware queues in creation order, and
-    // three more of them created at mgc_open put the two count streams on ONE queue -- their kernels no longer ran side by side, the
-    // judged count stage went 25.4 -> 28.8 ms, profiles/r06_ab_runs.txt r06z.  Needed only where several files hold a GIGANTIC sub-bucket:
-    // the many slightly oversized ones of an ordinary file -- 615 of up to 1946 keys in a dense file of the judged workload -- are short.)
-    auto huge_setup = [&]() -> int {                  // once the files' statistics are back
-      uint32_t files_gigantic = 0;
-      for (uint32_t b = 0; b < nb; b++) if (h_counts[b] && s->h_stats[3 * (size_t)b + 1] != 0 && s->h_stats[3 * (size_t)b] > 16384) files_gigantic++;
-      if (files_gigantic && sw.huge_slices) {
-        HIP_TRY(s, s->ensure(mgc_session::B_HWS0, hws_bytes));
-        hws[0] = s->buf[mgc_session::B_HWS0].p;
-      }
-      const int want = (int)std::min<uint64_t>((uint64_t)sw.huge_streams, (uint64_t)NH);
-      if (!fork_huge || want <= 1 || files_gigantic < 2) return MGC_OK;
-      for (int i = 1; i < want; i++) {
-        if (!s->stream_h[i - 1] && hipStreamCreateWithFlags(&s->stream_h[i - 1], hipStreamNonBlocking) != hipSuccess) { s->stream_h[i - 1] = nullptr; (void)hipGetLastError(); }
-        if (!s->stream_h[i - 1]) break;
-        const int id = mgc_session::B_Y2 + (i - 1);
-        HIP_TRY(s, s->ensure(id, kbytes * max_bucket));
-        hstream[i] = s->stream_h[i - 1];
-        halt[i] = reinterpret_cast<unsigned char *>(s->buf[id].p);
-        if (sw.huge_slices) { HIP_TRY(s, s->ensure(mgc_session::B_HWS0 + i, hws_bytes)); hws[i] = s->buf[mgc_session::B_HWS0 + i].p; }
-        n_huge_streams = i + 1;
-      }
-      return MGC_OK;
-    };
-    // tests run the dense-grid instantiations of the count kernels on small inputs (whose 2^t grids are mostly empty)
-    const bool finish_nolist = sw.nolist;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> fin_ev;       // profiling: around every file's count-kernel launch
-    uint64_t fin_keys = 0, fin_in_bytes = 0;
-    bool fin_narrow = false;
-    std::vector<uint64_t> h_fallback_distinct(nb);
-    std::vector<char> fallback(nb);
-    auto finish_file = [&](uint32_t b) -> int {
-      fallback[b] = false;
-      if (h_counts[b] == 0) return MGC_OK;
-      const uint32_t low = rem_bits - top_bits[b];
-      void *seg = X + kbytes * h_starts[b];
-      // sub-buckets above the persistent kernels' capacity (a k-mer repeated thousands of times, a dense corner of the key
-      // space) are streamed through a large hash table, in several suffix ranges if their distinct k-mers do not fit at once.
-      // Only a gigantic one is asked about first (one pass must do), before anything touches the file
-      bool stream = mgc::finish_can_stream(kw, low) && h_nlarge[b] > 0;
-      if (stream && h_maxsub[b] > sw.stream_max && kw == 2) {
-        stream = false;                                 // no probe for 16-byte keys: a sub-bucket that large takes the sort
-      } else if (stream && h_maxsub[b] > sw.stream_max) {
-        uint32_t h_fail[3] = {0, 0, 0};                 // [0] answer, [2] most distinct suffixes met (diagnostics)
-        HIP_TRY(s, hipMemsetAsync(d_err + 4, 0, 12, st));
-        HIP_TRY(s, mgc::launch_finish_probe(seg, kw, d_substart + sbase[b], low, h_nlarge[b], d_large + gbase[b], d_err + 4, st, sw.stream_max, narrow[b] != 0));
-        HIP_TRY(s, hipMemcpyAsync(h_fail, d_err + 4, 12, hipMemcpyDeviceToHost, st));
-        HIP_TRY(s, hipStreamSynchronize(st));
-        stream = (h_fail[0] == 0);
-        if (sw.finish_trace)
-          fprintf(stderr, "[finish] bucket %u: largest sub-bucket %llu > %llu, up to %u distinct in one: %s\n", b,
-                  (unsigned long long)h_maxsub[b], (unsigned long long)sw.stream_max, h_fail[2],
-                  stream ? "streamed through the hash tables" : "too many distinct: stable-sort fallback");
-      } else if (sw.finish_trace && h_maxsub[b] > cap) {
-        fprintf(stderr, "[finish] bucket %u: largest sub-bucket %llu > %llu: %s\n", b, (unsigned long long)h_maxsub[b],
-                (unsigned long long)cap, stream ? "streamed through the hash tables" : "stable-sort fallback");
-      }
-      if (file_k96[b] && h_nlarge[b] > 0 && !stream) {
-        // K96 records with an oversized sub-bucket that nothing streams: the LDS sort / the stable-sort fallback want whole 16-byte
-        // k-mers -- the file is widened in its own (16 bytes per k-mer) region, through Y, and goes on as a launch_group_wide file
-        if (need_join) { const int jr = huge_sync_all(); if (jr != MGC_OK) return jr; }   // Y is the streaming kernels' second buffer
-        forked = false;
-        const unsigned __int128 fb = (unsigned __int128)b << rem_bits;
-        HIP_TRY(s, mgc::launch_widen_k96(seg, h_counts[b], (uint64_t)fb, (uint64_t)(fb >> 64), (void *)Y, st));
-        HIP_TRY(s, hipMemcpyAsync(seg, Y, kbytes * h_counts[b], hipMemcpyDeviceToDevice, st));
-        file_k96[b] = 0;
-        s->prof.k96_widened_files++;
-      }
-      bool unordered = false;
-      if (narrow[b] && h_nlarge[b] > 0 && !stream) {
-        // an oversized sub-bucket that cannot be streamed: the LDS sort / the stable-sort fallback want whole k-mers back
-        if (need_join) { const int jr = huge_sync_all(); if (jr != MGC_OK) return jr; }   // Y is the streaming kernels' second buffer
-        forked = false;
-        HIP_TRY(s, mgc::launch_widen_groups(seg, d_substart + sbase[b], ngf(b), (uint64_t)b << rem_bits, low, (void *)Y, st,
-                                            tr_a[b], tr_b[b]));
-        HIP_TRY(s, hipMemcpyAsync(seg, Y, kbytes * h_counts[b], hipMemcpyDeviceToDevice, st));
-        narrow[b] = 0;
-        unordered = tr_a[b] != 0;      // grouped, but not in key order: only the stable sort of all bits can take it from here
-        // (the coarser plan's oversized list was cut at ITS capacity: the whole-key kernels would miss the sub-buckets in between)
-        if (fstream[b]) { fstream[b] = 0; unordered = true; }
-        cnt_extra.emplace_back();      // the back half of its region holds k-mers again: counts of its own
-        HIP_TRY(s, cnt_extra.back().alloc(sizeof(uint32_t) * h_counts[b]));
-        cnt_ptr[b] = cnt_extra.back().as<uint32_t>();
-      }
-      // whole keys in (low digit : high digit) order whose oversized sub-buckets nothing streams: the stable sort of all bits
-      if (wide_msd[b] && h_nlarge[b] > 0 && !stream) unordered = true;
-      if ((h_maxsub[b] <= cap || stream) && !unordered) {
-        hipStream_t fst;
-        {
-          const bool on_second = alt_files && (b & 1u);
-          if ((stream || on_second) && fork_huge && !forked) {   // everything the forked kernels read is complete at this point of st
-            HIP_TRY(s, hipEventRecord(s->ev_fork, st));
-            for (int i = 0; i < n_huge_streams; i++) HIP_TRY(s, hipStreamWaitEvent(hstream[i], s->ev_fork, 0));
-            forked = need_join = true;
-          }
-          fst = on_second ? s->stream2 : st;
-        }
-        const int hsel = (stream && h_nlarge[b] > 0 && n_huge_streams > 1) ? (huge_next++ % n_huge_streams) : 0;
-        if (s->profiling) {
-          fin_ev.emplace_back(); (void)hipEventCreate(&fin_ev.back().first); (void)hipEventCreate(&fin_ev.back().second);
-          (void)hipEventRecord(fin_ev.back().first, fst);
-          fin_keys += h_counts[b];
-          fin_in_bytes += h_counts[b] * (narrow[b] ? 4u : (file_k96[b] ? 12u : (uint64_t)kbytes));
-          fin_narrow = fin_narrow || narrow[b];
-        }
-        HIP_TRY(s, mgc::launch_finish_file(seg, kw, d_substart + sbase[b], ngf(b), low, h_nlarge[b],
-                                           d_large + gbase[b], cnt_ptr[b], d_group + gbase[b], stream, (void *)halt[hsel], hstream[hsel],
-                                           // the list pays off only when a good part of the 2^t grid is empty
-                                           (4 * h_nzcount[b] < 3 * ngf(b) && !finish_nolist) ? d_nz + gbase[b] : nullptr,
-                                           d_nzcount(b), fst, narrow[b] != 0, tr_a[b], tr_b[b], h_maxsub[b], h_counts[b],
-                                           // (the distinct-sized count's retry list: behind the file's oversized list -- a sub-bucket is on one of them at most)
-                                           fstream[b] ? d_large + gbase[b] + h_nlarge[b] : d_nz + gbase[b], d_retrycnt + b, file_k96[b] != 0,
-                                           sw.hash_multi, sw.hash_dbg, fstream[b] ? mgc::finish_stream_capacity() : 0, hws[hsel], hws_bytes, max_bucket, d_err));
-        if (s->profiling) (void)hipEventRecord(fin_ev.back().second, fst);
-      } else {
-        // a sub-bucket does not fit in LDS (heavily repeated k-mers): finish this file the long way
-        fallback[b] = true;
-        if (need_join) { const int jr = huge_sync_all(); if (jr != MGC_OK) return jr; }   // the sort below uses Y, the streaming kernels' second buffer
-        forked = false;                                            // ... and the next streaming kernel must wait for that sort
-        if (low || unordered) {
-          // LSD order: the low bits cannot be sorted after the top bits, so the whole key is redone
-          mgc::SortPlan lp;
-          mgc::make_sort_plan(0, rem_bits, &lp);
-          int in_alt = 0;
-          HIP_TRY(s, mgc::launch_radix_sort(seg, (void *)Y, h_counts[b], kw, lp, sort_ws, sort_ws_bytes - 256, d_err, &in_alt, st, nullptr));
-          if (in_alt) HIP_TRY(s, hipMemcpyAsync(seg, Y, kbytes * h_counts[b], hipMemcpyDeviceToDevice, st));
-        }
-        HIP_TRY(s, mgc::launch_rle_count(seg, h_counts[b], kw, rle_ws, st));
-        HIP_TRY(s, mgc::rle_read_total(rle_ws, &h_fallback_distinct[b], st));
-        HIP_TRY(s, hipMemsetAsync(d_group + gbase[b], 0, sizeof(uint64_t) * (gbase[b + 1] - gbase[b]), st));
-        HIP_TRY(s, hipMemcpyAsync(d_group + gbase[b], &h_fallback_distinct[b], sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(s, hipStreamSynchronize(st));
-      }
-      return MGC_OK;
-    };
-
-    if (probe >= 0) {
-      // the probe file: passes, statistics, count -- then its distinct / instances ratio chooses the others' plan
-      const uint32_t pb = (uint32_t)probe;
-      { const int rc = group_file(pb); if (rc != MGC_OK) return rc; }
-      { const int rc = stats_file(pb); if (rc != MGC_OK) return rc; }
-      HIP_TRY(s, hipMemcpyAsync(s->h_stats + 3 * (size_t)pb, d_stats + 3 * (size_t)pb, sizeof(uint64_t) * 3, hipMemcpyDeviceToHost, st));
-      HIP_TRY(s, hipStreamSynchronize(st));
-      h_maxsub[pb] = s->h_stats[3 * (size_t)pb]; h_nlarge[pb] = s->h_stats[3 * (size_t)pb + 1]; h_nzcount[pb] = s->h_stats[3 * (size_t)pb + 2];
-      { const int rc = finish_file(pb); if (rc != MGC_OK) return rc; }
-      if (need_join) { const int jr = huge_join_all(); if (jr != MGC_OK) return jr; }
-      forked = false;                                        // (the second stream has to be ordered behind the other files' passes again)
-      uint64_t h_pd = 0;
-      HIP_TRY(s, mgc::launch_sum_u64(d_group + gbase[pb], gbase[pb + 1] - gbase[pb], d_group + ng_total, st));
-      HIP_TRY(s, hipMemcpyAsync(&h_pd, d_group + ng_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-      HIP_TRY(s, hipStreamSynchronize(st));
-      const double ratio = (double)h_pd / (double)h_counts[pb];
-      s->prof.probe_ratio = ratio;
-      if (sw.finish_trace) fprintf(stderr, "[finish] probe file %u: %llu distinct of %llu k-mers (%.3f): the other files take the %s plan\n", pb,
-                                   (unsigned long long)h_pd, (unsigned long long)h_counts[pb], ratio, ratio <= 0.30 ? "distinct-sized" : "finer");
-      if (ratio <= 0.30) for (uint32_t b = 0; b < nb; b++) {
-        if (b != pb && top_str[b]) take_stream_plan(b);
-        else if (b != pb && hpc_cand[b] && !fstream[b]) {      // (`compress`: the other count kernel, on 3^9 sub-buckets where the bucket's size asks for them)
-          fstream[b] = 1; s->prof.stream_files++;
-          if (hpc_mixed[b]) take_mixed_plan(b);
-        }
-      }
-      if (d_fine && nb <= 256 && d_nhdrs) { const int prc = prepare_headers(-1, probe); if (prc != MGC_OK) return prc; }
-    }
-    bool stats_back = false;
-    for (uint32_t b = 0; b < nb; b++) {
-      { const int rc = group_upto(nb); if (rc != MGC_OK) return rc; }
-      if (!stats_back) {
-        HIP_TRY(s, hipStreamSynchronize(st)); stats_back = true;
-        const int hrc = huge_setup(); if (hrc != MGC_OK) return hrc;
-      }
-      if ((int)b == probe) continue;
-      h_maxsub[b] = s->h_stats[3 * (size_t)b]; h_nlarge[b] = s->h_stats[3 * (size_t)b + 1]; h_nzcount[b] = s->h_stats[3 * (size_t)b + 2];
-      const int rc = finish_file(b);
-      if (rc != MGC_OK) return rc;
-    }
-
-    if (need_join) { const int jr = huge_join_all(); if (jr != MGC_OK) return jr; }
-    if (sw.finish_trace && hws[0]) {                          // what the LAST sliced file on every streaming stream did (diagnostics)
-      HIP_TRY(s, hipStreamSynchronize(st));
-      for (int i = 0; i < n_huge_streams; i++) {
-        if (!hws[i]) continue;
-        std::vector<uint32_t> w(hws_bytes / 4);
-        HIP_TRY(s, hipMemcpy(w.data(), hws[i], hws_bytes / 4 * 4, hipMemcpyDeviceToHost));
-        const uint32_t max_gig = (uint32_t)(max_bucket / 65536 + 2);
-        uint32_t dense = 0;
-        for (uint32_t q = 0; q < w[0] && q < max_gig; q++) dense += w[64 + 2 * (size_t)max_gig + q] ? 1u : 0u;
-        fprintf(stderr, "[finish] sliced count, stream %d: the last file had %u sub-buckets cut into %u slices; %u of them dense (counted by ranges)\n", i, w[0], w[1], dense);
-      }
-    }
-
-    // the sub-buckets hash_count_stream_kernel could not hold (more distinct suffixes than its table: low coverage, D ~ N): their
-    // numbers are on the device -- one small copy brings the counts back, the files that have any get the retry launch
-    {
-      bool any_stream = false;
-      for (uint32_t b = 0; b < nb; b++) any_stream = any_stream || (fstream[b] && !fallback[b] && h_counts[b]);
-      if (any_stream) {
-        std::vector<uint64_t> h_retry(nb, 0);
-        HIP_TRY(s, hipMemcpyAsync(h_retry.data(), d_retrycnt, sizeof(uint64_t) * nb, hipMemcpyDeviceToHost, st));
-        HIP_TRY(s, hipStreamSynchronize(st));
-        for (uint32_t b = 0; b < nb; b++) {
-          if (!fstream[b] || fallback[b] || h_retry[b] == 0) continue;
-          s->prof.stream_retries += h_retry[b];
-          HIP_TRY(s, mgc::launch_finish_retry(X + kbytes * h_starts[b], d_substart + sbase[b], ngf(b), rem_bits - top_bits[b],
-                                              cnt_ptr[b], d_group + gbase[b], tr_a[b], tr_b[b], d_large + gbase[b] + h_nlarge[b], d_retrycnt + b,
-                                              h_retry[b], mgc::finish_stream_capacity(), st, narrow[b] != 0, (void *)huge_alt));
-        }
-      }
-    }
-
-    // ---- E/F. offsets of every sub-bucket in the packed result ----
-    hipEvent_t ev_pack[2] = {nullptr, nullptr};
-    if (s->profiling) { (void)hipEventCreate(&ev_pack[0]); (void)hipEventCreate(&ev_pack[1]); (void)hipEventRecord(ev_pack[0], st); }
-    HIP_TRY(s, mgc::launch_finish_scan(d_group, ng_total, s->buf[mgc_session::B_GSCAN].p, st));
-    HIP_TRY(s, hipMemcpyAsync(&nd, d_group + ng_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(s, hipStreamSynchronize(st));
-    if (ng_total == 0) nd = 0;
-    s->n_distinct = nd;
-    if (s->ext_out_keys && s->ext_out_counts && nd <= s->ext_out_cap) {
-      // (mgc_count_buckets_into: the packing kernels write the caller's pre-sized result -- no copy out of the arena afterwards)
-      s->d_unique = s->ext_out_keys;
-      s->d_counts = s->ext_out_counts;
-    } else {
-      HIP_TRY(s, s->ensure(mgc_session::B_UNIQUE, kbytes * nd));
-      HIP_TRY(s, s->ensure(mgc_session::B_COUNTS, sizeof(uint32_t) * nd));
-      s->d_unique = s->buf[mgc_session::B_UNIQUE].p;
-      s->d_counts = reinterpret_cast<uint32_t *>(s->buf[mgc_session::B_COUNTS].p);
-    }
-
-    // ---- G/H. pack ----
-    for (uint32_t b = 0; b < nb; b++) {
-      if (h_counts[b] == 0) continue;
-      void *seg = X + kbytes * h_starts[b];
-      // a sparse sub-bucket grid (`compress`: 59049 of 2^20): only the non-empty ones are visited
-      const uint32_t *nzl = (4 * h_nzcount[b] < 3 * ngf(b) && !finish_nolist) ? d_nz + gbase[b] : nullptr;
-      if (narrow[b]) {
-        HIP_TRY(s, mgc::launch_compact_groups_narrow(seg, cnt_ptr[b], d_substart + sbase[b], d_group + gbase[b],
-                                                     ngf(b), (uint64_t)b << rem_bits, rem_bits - top_bits[b],
-                                                     s->d_unique, s->d_counts, st, tr_a[b], tr_b[b], nzl, h_nzcount[b]));
-      } else if (!fallback[b] && file_k96[b]) {
-        const unsigned __int128 fb = (unsigned __int128)b << rem_bits;
-        HIP_TRY(s, mgc::launch_compact_groups_k96(seg, cnt_ptr[b], d_substart + sbase[b], d_group + gbase[b], ngf(b),
-                                                  (uint64_t)fb, (uint64_t)(fb >> 64), s->d_unique, s->d_counts, st, tr_a[b], tr_b[b], nzl, h_nzcount[b]));
-      } else if (!fallback[b]) {
-        HIP_TRY(s, mgc::launch_compact_groups(seg, kw, cnt_ptr[b], d_substart + sbase[b], d_group + gbase[b],
-                                              ngf(b), s->d_unique, s->d_counts, st, tr_a[b], tr_b[b], nzl, h_nzcount[b]));
-      } else {
-        HIP_TRY(s, mgc::launch_rle_count(seg, h_counts[b], kw, rle_ws, st));
-        HIP_TRY(s, mgc::launch_rle_emit(seg, h_counts[b], kw, rle_ws, s->d_unique, s->d_counts, st, d_group + gbase[b]));
-      }
-    }
-    if (s->profiling) (void)hipEventRecord(ev_pack[1], st);
-    tm.end(MGC_STAGE_RLE);
-    s->prof.stage_launches[MGC_STAGE_RLE] = 4 * nb;
-    if (s->profiling) {
-      HIP_TRY(s, hipStreamSynchronize(st));
-      { float pms = 0; if (hipEventElapsedTime(&pms, ev_pack[0], ev_pack[1]) == hipSuccess) s->prof.pack_ms = pms; }
-      (void)hipEventDestroy(ev_pack[0]); (void)hipEventDestroy(ev_pack[1]);
-      for (auto &pe : fin_ev) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, pe.first, pe.second) == hipSuccess) { s->prof.finish_ms += ms; s->prof.finish_launches++; }
-        (void)hipEventDestroy(pe.first); (void)hipEventDestroy(pe.second);
-      }
-      s->prof.finish_keys = fin_keys;
-      s->prof.finish_bytes = fin_in_bytes + nd * (fin_narrow ? 8u : (uint64_t)kbytes + 4u);
-    }
-  }
-
-  // ---- block offsets ----
-  HIP_TRY(s, s->ensure(mgc_session::B_BLOCKS, sizeof(uint64_t) * (c.n_prefix + 1)));
-  s->d_block_start = reinterpret_cast<uint64_t *>(s->buf[mgc_session::B_BLOCKS].p);
-  tm.begin(MGC_STAGE_BLOCKS);
-  HIP_TRY(s, mgc::launch_block_offsets(s->d_unique, nd, kw, c.w_data, c.n_prefix, s->d_block_start, st));
-  tm.end(MGC_STAGE_BLOCKS);
-  s->prof.stage_launches[MGC_STAGE_BLOCKS] = 1;
-
-  uint32_t h_err[3] = {0, 0, 0};
-  HIP_TRY(s, hipMemcpyAsync(h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost, st));
-  if (s->profiling) (void)hipEventRecord(ev_all[1], st);
-  HIP_TRY(s, hipStreamSynchronize(st));
-  if (h_err[0]) { set_err(&s->err, "radix sort look-back timed out"); return MGC_ETIMEOUT; }
-
-  if (s->profiling) {
-    float ms = 0;
-    for (int i = 0; i < MGC_NUM_STAGES; i++)
-      if (tm.used[i] && hipEventElapsedTime(&ms, tm.ev[i][0], tm.ev[i][1]) == hipSuccess) s->prof.stage_ms[i] = ms;
-    if (hipEventElapsedTime(&ms, ev_all[0], ev_all[1]) == hipSuccess) s->prof.total_ms = ms;
-    s->prof.stage_launches[MGC_STAGE_SORT] = sort_launch_groups * (plan.num_passes + 2);
-    for (uint32_t b = 0; b < nb; b++) {
-      if (h_counts[b] == 0) continue;
-      for (uint32_t p = 0; p < file_passes[b]; p++) {
-        hipEvent_t *pe = &pass_ev[(size_t)b * ev_per_file + 2 * p];
-        if (hipEventElapsedTime(&ms, pe[0], pe[1]) == hipSuccess) {
-          s->prof.sort_pass_ms_total += ms;
-          s->prof.sort_pass_launches++;
-          s->prof.sort_pass_keys += h_counts[b];
-          const int pi = p ? 1 : 0;
-          s->prof.pass_ms[pi] += ms;
-          s->prof.pass_launches[pi]++;
-          s->prof.pass_keys[pi] += h_counts[b];
-          s->prof.pass_bytes[pi] += h_counts[b] * ((size_t)b < narrowed.size() && narrowed[b] ? (p ? 8u : (soa_hi_mask ? 9u : 12u)) : (k96_passes[b] ? 24u : 2u * kbytes));
-        }
-      }
-    }
-    for (auto &e : pass_ev) (void)hipEventDestroy(e);
-    (void)hipEventDestroy(ev_all[0]); (void)hipEventDestroy(ev_all[1]);
-    // (an elapsed-time query on an event pair a small file never recorded fails, harmlessly -- but the runtime keeps the error for
-    // the thread's next hipGetLastError(): the CLI's -V on a batched count failed in the run store's first launch that way)
-    (void)hipGetLastError();
-  }
-  return MGC_OK;                                             // the caller marks the session counted (a batch is not the result yet)
-}
-
 static int copy_device_result(mgc_session *s, uint64_t *keys_lo, uint64_t *keys_hi, uint32_t *counts, uint64_t *block_start) {
   const uint64_t nd = s->n_distinct;
   if (nd && (keys_lo || keys_hi)) {
@@ -2141,7 +1210,7 @@ static int park_batch_result(mgc_session *s) {
 static int count_staged_batch(mgc_session *s, int which, uint64_t n) {
   s->d_bases = stage_ptr(s, which);
   s->n_bases = n;
-  int rc = count_device(s);
+  int rc = mgc::count_device(s);
   if (rc != MGC_OK) return rc;
   s->total_bases += n;
   s->total_instances += s->n_instances;
@@ -2198,7 +1267,7 @@ static int finalize_from_runs(mgc_session *s) {
 extern "C" int mgc_count(mgc_session *s) {
   if (!s) return MGC_EINVAL;
   if (s->borrowed) {                                         // the caller's device buffer: every call counts it again
-    const int rc = count_device(s);
+    const int rc = mgc::count_device(s);
     if (rc == MGC_OK) s->counted = true;
     return rc;
   }
@@ -2214,7 +1283,7 @@ extern "C" int mgc_count(mgc_session *s) {
   if (!s->have_r) {                                          // everything fits in one pass
     s->d_bases = stage_ptr(s, s->fill);
     s->n_bases = s->fill_len;
-    rc = count_device(s);
+    rc = mgc::count_device(s);
     s->prof.n_batches = 1;
   } else {
     if (s->fill_len) rc = count_staged_batch(s, s->fill, s->fill_len);
@@ -2248,19 +1317,25 @@ extern "C" int mgc_staged_bases(mgc_session *s, const uint8_t **d_bases, uint64_
   return MGC_OK;
 }
 
-extern "C" int mgc_count_buckets(mgc_session *s, void *d_keys, uint32_t bucket_bits, const uint64_t *bucket_counts) {
-  if (!s || !bucket_counts || bucket_bits < MGC_NUM_FILES_BITS || bucket_bits > MGC_MAX_BUCKET_BITS || bucket_bits > 2 * s->cfg.k)
+static int count_buckets(mgc_session *s, const mgc::CountInput &in) {
+  if (!s || !in.counts || in.bucket_bits < MGC_NUM_FILES_BITS || in.bucket_bits > MGC_MAX_BUCKET_BITS || in.bucket_bits > 2 * s->cfg.k)
     return MGC_EINVAL;
   uint64_t n = 0;
-  for (uint32_t b = 0; b < (1u << bucket_bits); b++) n += bucket_counts[b];
-  if (n && !d_keys) return MGC_EINVAL;
+  for (uint32_t b = 0; b < (1u << in.bucket_bits); b++) n += in.counts[b];
+  if (n && !in.keys) return MGC_EINVAL;
   if (s->input_seen || s->borrowed) {
     set_err(&s->err, "mgc_count_buckets: the session already holds pushed bases");
     return MGC_ESTATE;
   }
-  const int rc = count_device(s, d_keys, bucket_counts, bucket_bits);
+  const int rc = mgc::count_device(s, in);
   if (rc == MGC_OK) s->counted = true;
   return rc;
+}
+
+extern "C" int mgc_count_buckets(mgc_session *s, void *d_keys, uint32_t bucket_bits, const uint64_t *bucket_counts) {
+  mgc::CountInput in;
+  in.keys = d_keys; in.counts = bucket_counts; in.bucket_bits = bucket_bits;
+  return count_buckets(s, in);
 }
 
 // ... with the packed result written straight to the caller's buffers when it fits (capacity in k-mers): the waves of a sharded
@@ -2270,11 +1345,10 @@ extern "C" int mgc_count_buckets_into(mgc_session *s, void *d_keys, uint32_t buc
                                       void *d_out_keys, uint32_t *d_out_counts, uint64_t capacity, uint64_t *n_distinct,
                                       const uint64_t *d_fine_hist) {
   if (!s || !n_distinct || (capacity && (!d_out_keys || !d_out_counts))) return MGC_EINVAL;
-  s->ext_out_keys = d_out_keys; s->ext_out_counts = d_out_counts; s->ext_out_cap = capacity;
-  s->ext_fine = d_fine_hist;
-  const int rc = mgc_count_buckets(s, d_keys, bucket_bits, bucket_counts);
-  s->ext_out_keys = nullptr; s->ext_out_counts = nullptr; s->ext_out_cap = 0;
-  s->ext_fine = nullptr;
+  mgc::CountInput in;
+  in.keys = d_keys; in.counts = bucket_counts; in.bucket_bits = bucket_bits; in.fine = d_fine_hist;
+  in.out_keys = d_out_keys; in.out_counts = d_out_counts; in.out_cap = capacity;
+  const int rc = count_buckets(s, in);
   if (rc == MGC_OK) *n_distinct = s->n_distinct;
   return rc;
 }

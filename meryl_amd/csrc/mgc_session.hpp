@@ -1,5 +1,5 @@
 // mgc_session.hpp -- the session object behind include/meryl_gpu_count.h and the helpers its translation units
-// (mgc_api.cpp: input + counting; mgc_stream.cpp: delivery of the result, database streaming) share.  Internal.
+// (mgc_api.cpp: input + batches; mgc_count.cpp: counting; mgc_stream.cpp: delivery of the result, database streaming) share.  Internal.
 #pragma once
 
 #include "../../include/meryl_gpu_count.h"
@@ -68,9 +68,6 @@ struct mgc_session {
   bool      counted = false;
   uint64_t  n_instances = 0, n_distinct = 0;
   uint64_t  file_instances[MGC_NUM_FILES];
-  // owner side of a sharded count (mgc_count_buckets_into): where the packed result goes when it fits -- the caller's buffers
-  void     *ext_out_keys = nullptr; uint32_t *ext_out_counts = nullptr; uint64_t ext_out_cap = 0;
-  const uint64_t *ext_fine = nullptr;     // ... and the senders' summed fifteen-bit histogram (the first grouping digit of every bucket)
   void     *d_unique = nullptr;           // uint64[D] (k <= 32) or {lo,hi}[D] (k > 32)
   uint32_t *d_counts = nullptr;
   uint64_t *d_block_start = nullptr;
@@ -180,6 +177,7 @@ struct mgc_session {
   // mgc_prepare: the count's largest buffers allocated by a helper thread while the input is still being read
   std::thread prep_thread;
   bool        prep_active = false;
+  void join_prepare() { if (prep_active) { prep_thread.join(); prep_active = false; } }
 
   // profiling
   bool        profiling = false;
@@ -190,4 +188,21 @@ struct mgc_session {
     counted = false;
   }
 };
+
+namespace mgc {
+// The owner side of a sharded count (mgc_count_buckets[_into]): k-mers already extracted and grouped by bucket by the caller --
+// extraction and partition are skipped, the caller's buffer is processed in place.  Default: the session's own input.
+struct CountInput {
+  void           *keys = nullptr;
+  const uint64_t *counts = nullptr;                 // [1 << bucket_bits]
+  uint32_t        bucket_bits = MGC_NUM_FILES_BITS;
+  const uint64_t *fine = nullptr;                   // the senders' summed fifteen-bit histogram (the first grouping digit of every bucket)
+  void           *out_keys = nullptr;               // where the packed result goes when it fits (out_cap k-mers): the caller's buffers
+  uint32_t       *out_counts = nullptr;
+  uint64_t        out_cap = 0;
+};
+// One count over the bases resident in HBM (s->d_bases / s->n_bases) or over in.keys: the result stays in the session's arena
+// (mgc_count.cpp).  The caller marks the session counted.
+int count_device(mgc_session *s, const CountInput &in = CountInput());
+}  // namespace mgc
 
