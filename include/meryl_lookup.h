@@ -112,6 +112,43 @@ int mgc_lookup_report(const mgc_lookup *const *tables, uint32_t n_tables, int mo
                       const uint8_t *d_bases, uint64_t n_bases, const uint64_t *seq_start, const char *const *names, uint64_t n_seq,
                       uint64_t chunk_bytes, mgc_lookup_write_cb write_cb, void *user);
 
+/* ---- read filtering: meryl-lookup -include / -exclude (src/meryl-lookup/include-exclude.C) --------------------------------------
+ * Records are taken in order, record i of the first input together with record i of the second when there is one (:44-58).
+ * found = the windows of the first sequence with value(fmer) > 0 || value(rmer) > 0 (:64-78) plus those of the second (:92-93);
+ * with skip_first = 23 (-10x) the windows of the FIRST input that begin before base 23 are not counted (:71).  The pair is
+ * written when found > 0 (INCLUDE) or found == 0 (EXCLUDE) (:124-125), each sequence to its own output, as
+ *   >ident nKmers=found \n bases \n                       when the record has no qualities
+ *   @ident nKmers=found \n bases \n + \n qualities \n     otherwise                                         (:107-108)
+ * ident is the header up to the first blank or tab; the bases are the sequence lines joined (multi-line FASTA; \r, \n, blanks
+ * and tabs dropped, every other byte kept); FASTQ is four lines per record -- anything else is MGC_EFORMAT. */
+#define MGC_FILTER_INCLUDE 0
+#define MGC_FILTER_EXCLUDE 1
+typedef struct mgc_filter_result {
+  uint64_t n_records, n_kept;      /* records (pairs) processed / written */
+  uint64_t consumed[2];            /* bytes of each input's piece that belonged to those records */
+  uint64_t out_bytes[2];           /* text written per output -- or needed, when an output buffer was too small */
+  uint32_t format[2];              /* MGC_TEXT_FASTA / MGC_TEXT_FASTQ (meryl_gpu_count.h) per input, from its first byte; 0: empty */
+} mgc_filter_result;
+
+/* One step, device in, device out.  d_text[i] / n_text[i]: a piece of raw FASTA/FASTQ text of input i (n_inputs 1 or 2) that
+ * begins at a record start.  final: the pieces end their inputs -- a last record without a line end is complete, and two inputs
+ * with different numbers of records are MGC_EINVAL (the message names both counts).  Not final: the last record of a piece
+ * is complete only when another record start follows it; with two inputs min(records_1, records_2) records of each are
+ * processed, and res->consumed tells where the caller's next pieces begin.  The kept text goes to d_out[i] (out_cap[i] bytes).
+ * When an output is too small NOTHING is written, res->out_bytes holds the sizes needed and the call returns MGC_EINVAL
+ * (its "capacity" meaning); d_out may be NULL to ask for the sizes.  The text is never copied to the host. */
+int mgc_lookup_filter_text(const mgc_lookup *t, int mode, uint32_t skip_first, uint32_t n_inputs, const uint8_t *const d_text[2],
+                           const uint64_t n_text[2], int final, uint8_t *const d_out[2], const uint64_t out_cap[2],
+                           mgc_filter_result *res, void *stream);
+
+/* Whole files (path2, out2 NULL: one input): both are read through msr_read_text (plain, gzip, BGZF, "-") into pinned
+ * buffers in pieces of about batch_bytes (0: 64 MiB), what a step did not consume is carried into the next piece, a piece
+ * grows when one record is longer than it, and the kept text is handed to the callbacks in order.  Inputs with different
+ * numbers of records: MGC_EINVAL naming both counts, after the common records have been written. */
+int mgc_lookup_filter_files(const mgc_lookup *t, int mode, uint32_t skip_first, const char *path1, const char *path2,
+                            uint64_t batch_bytes, mgc_lookup_write_cb out1, void *user1, mgc_lookup_write_cb out2, void *user2,
+                            mgc_filter_result *totals);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,7 +37,7 @@ SYMBOLS = (
     "mgc_runs_open", "mgc_runs_add", "mgc_runs_write", "mgc_runs_get_profile", "mgc_runs_error", "mgc_runs_close", "mgc_get_runs_profile", "mgc_db_merge", "mgc_db_filter", "mgc_count_node", "mgc_count_node_batched", "mgc_count_node_staged", "mgc_node_plan",
     # include/meryl_lookup.h
     "mgc_lookup_load", "mgc_lookup_estimate", "mgc_lookup_from_device", "mgc_lookup_free", "mgc_lookup_get_info", "mgc_lookup_error",
-    "mgc_lookup_values", "mgc_lookup_stream", "mgc_lookup_existence", "mgc_lookup_positions", "mgc_lookup_report",
+    "mgc_lookup_values", "mgc_lookup_stream", "mgc_lookup_existence", "mgc_lookup_positions", "mgc_lookup_report", "mgc_lookup_filter_text", "mgc_lookup_filter_files",
     # include/meryl_seq.h
     "msr_open", "msr_read_text", "msr_close", "msr_last_error", "msr_load_bases", "msr_load_stream", "msr_format", "msr_is_compressed", "msr_guess_number_of_kmers",
 )
@@ -186,6 +186,16 @@ class RunsProfile(ctypes.Structure):
 class LookupInfo(ctypes.Structure):
     _fields_ = [("k", ctypes.c_uint32), ("key_words", ctypes.c_uint32), ("index_bits", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
                 ("n_kmers", ctypes.c_uint64), ("n_kmers_in_db", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64)]
+
+
+class FilterResult(ctypes.Structure):
+    """mgc_filter_result (include/meryl_lookup.h)"""
+    _fields_ = [("n_records", ctypes.c_uint64), ("n_kept", ctypes.c_uint64), ("consumed", ctypes.c_uint64 * 2),
+                ("out_bytes", ctypes.c_uint64 * 2), ("format", ctypes.c_uint32 * 2)]
+
+    def as_dict(self):
+        return {"n_records": self.n_records, "n_kept": self.n_kept, "consumed": list(self.consumed),
+                "out_bytes": list(self.out_bytes), "format": list(self.format)}
 
 
 class IndexEntry(ctypes.Structure):
@@ -385,6 +395,9 @@ def lib():
     sig("mgc_lookup_positions", i32, P(vp), u32, i32, vp, u64, vp, vp)
     sig("mgc_lookup_report", i32, P(vp), u32, i32, P(ctypes.c_char_p), u32, vp, u64, P(u64), P(ctypes.c_char_p), u64, u64,
         LOOKUP_WRITE_CB, vp)
+    sig("mgc_lookup_filter_text", i32, vp, i32, u32, u32, P(vp), P(u64), i32, P(vp), P(u64), P(FilterResult), vp)
+    sig("mgc_lookup_filter_files", i32, vp, i32, u32, ctypes.c_char_p, ctypes.c_char_p, u64, LOOKUP_WRITE_CB, vp, LOOKUP_WRITE_CB, vp,
+        P(FilterResult))
     sig("msr_open", vp, ctypes.c_char_p)
     sig("msr_close", None, vp)
     sig("msr_read_text", ctypes.c_int64, vp, vp, u64)

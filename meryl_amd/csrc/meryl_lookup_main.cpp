@@ -10,8 +10,12 @@
 //                                                                                                  (dump.C:139-244, 368-405)
 // Every database is loaded into the device-resident exact lookup table (include/meryl_lookup.h = merylExactLookup); the
 // sequences go to the device as one base stream with '.' after each.  The position reports are formatted on the device
-// (mgc_lookup_report) and written as they come; -output is optional (stdout) and must not name a compressed file.  The
-// other modes of the reference tool (-dump, -include, -exclude) are not part of this build.
+// (mgc_lookup_report) and written as they come; -output is optional (stdout) and must not name a compressed file.
+//   meryl-lookup -include | -exclude [-10x] -sequence <R1.fq[.gz]> [<R2.fq[.gz]>] -mers <db.meryl> [-min v] [-max v] -output <o1> [<o2>]
+//     the reads (read pairs) with at least one / without any k-mer of the database, "ident nKmers=<found>" as the header;
+//     -10x leaves the first 23 bases of the first input out                                          (include-exclude.C)
+//     streamed in pieces through mgc_lookup_filter_files: records are found, looked up and written as text on the device.
+// -dump (no option of the reference tool) is not part of this build.
 #include "../../include/meryl_gpu_count.h"
 #include "../../include/meryl_lookup.h"
 #include "../../include/meryl_seq.h"
@@ -71,7 +75,7 @@ void parse_text(const std::string &text, Seqs &out) {
   out.start.push_back(out.bases.size());
 }
 
-enum Op { OP_NONE, OP_EXISTENCE, OP_BED, OP_BED_RUNS, OP_WIG_COUNT, OP_WIG_DEPTH };
+enum Op { OP_NONE, OP_EXISTENCE, OP_BED, OP_BED_RUNS, OP_WIG_COUNT, OP_WIG_DEPTH, OP_INCLUDE, OP_EXCLUDE };
 
 const char *op_name(Op op) {                                  // toString(lookupOp), meryl-lookup.H:38-50 (-bed-runs is opBED)
   switch (op) {
@@ -79,6 +83,8 @@ const char *op_name(Op op) {                                  // toString(lookup
     case OP_BED: case OP_BED_RUNS: return "-bed";
     case OP_WIG_COUNT: return "-wig-count";
     case OP_WIG_DEPTH: return "-wig-depth";
+    case OP_INCLUDE: return "-include";
+    case OP_EXCLUDE: return "-exclude";
     default: return "(not supplied)";
   }
 }
@@ -99,7 +105,7 @@ int main(int argc, char **argv) {
   std::vector<std::string> dbs, labels;
   uint64_t vmin = 0, vmax = UINT64_MAX;
   Op op = OP_NONE;
-  bool estimate = false;
+  bool estimate = false, is10x = false;
   double max_memory_gb = 0.0;                                 // -memory: 0 = whatever the device has
   for (int a = 1; a < argc; a++) {
     const std::string w = argv[a];
@@ -108,6 +114,9 @@ int main(int argc, char **argv) {
     else if (w == "-bed-runs") op = OP_BED_RUNS;
     else if (w == "-wig-count") op = OP_WIG_COUNT;
     else if (w == "-wig-depth") op = OP_WIG_DEPTH;
+    else if (w == "-include") op = OP_INCLUDE;
+    else if (w == "-exclude") op = OP_EXCLUDE;
+    else if (w == "-10x") is10x = true;
     else if (w == "-sequence" && a + 1 < argc) {              // meryl-lookup.C:160-164: an optional second input
       seq_name = argv[++a];
       if (a + 1 < argc && argv[a + 1][0] != '-') seq_name2 = argv[++a];
@@ -122,13 +131,22 @@ int main(int argc, char **argv) {
     else if (w == "-estimate") estimate = true;
     else if (w == "-mers") { while (a + 1 < argc && argv[a + 1][0] != '-') dbs.push_back(argv[++a]); }
     else if (w == "-labels") { while (a + 1 < argc && argv[a + 1][0] != '-') labels.push_back(argv[++a]); }
-    else if (w == "-dump" || w == "-include" || w == "-exclude")
-      die("ERROR: mode '%s' is not part of this build (-existence, -bed, -bed-runs, -wig-count, -wig-depth only).", w.c_str());
+    else if (w == "-dump")
+      die("ERROR: mode '%s' is not part of this build (-existence, -bed, -bed-runs, -wig-count, -wig-depth, -include, -exclude only).", w.c_str());
     else die("ERROR: unknown option '%s'.", w.c_str());
   }
   // lookupGlobal::checkInvalid (meryl-lookup.C:306-368), before any database or device is touched
   if (op == OP_NONE && !estimate) die("No report-type (-bed, -wig-count, -wig-depth, -existence, -include, -exclude) supplied.");
-  if (op != OP_NONE) {
+  const bool filtering = op == OP_INCLUDE || op == OP_EXCLUDE;
+  if (filtering) {                                            // :328-330, :346-358, :362-367
+    if (!seq_name.empty() && out_name.empty()) die("No output file (-output) supplied.");
+    if (!seq_name2.empty() && out_name2.empty()) die("No second output file (-output) supplied for second input (-input) file.");
+    if (seq_name2.empty() && !out_name2.empty()) die("No second input file (-input) supplied for second output (-output) file.");
+    if (dbs.size() > 1) die("Only one meryl database (-mers) supported for %s.", op_name(op));
+    if (!labels.empty()) die("Labels (-labels) not supported for %s.", op_name(op));
+    for (const std::string *o : {&out_name, &out_name2})
+      if (compressed_name(*o)) die("ERROR: output '%s' names a compressed file; this build writes position reports uncompressed only.", o->c_str());
+  } else if (op != OP_NONE) {
     if (!seq_name2.empty()) die("Only one input sequence (-sequence) supported for %s.", op_name(op));
     if (!out_name2.empty()) die("Only one output file (-output) supported for %s.", op_name(op));
     if (op != OP_BED && op != OP_BED_RUNS && !labels.empty()) die("Labels (-labels) not supported for %s.", op_name(op));
@@ -138,7 +156,9 @@ int main(int argc, char **argv) {
   }
   if (op == OP_NONE || (seq_name.empty() && !estimate) || dbs.empty()) {
     fprintf(stderr, "usage: %s -existence | -bed | -bed-runs | -wig-count | -wig-depth -sequence <in.fa|fq[.gz]> -mers <db.meryl> [...] "
-                    "[-labels l ...] [-min v] [-max v] [-memory GB] [-estimate] [-output out]\n", argv[0]);
+                    "[-labels l ...] [-min v] [-max v] [-memory GB] [-estimate] [-output out]\n"
+                    "       %s -include | -exclude [-10x] -sequence <in1> [<in2>] -mers <db.meryl> [-min v] [-max v] -output <out1> [<out2>]\n",
+            argv[0], argv[0]);
     return 1;
   }
 
@@ -159,6 +179,32 @@ int main(int argc, char **argv) {
     if (required_gb > max_memory_gb) { fprintf(stderr, "\nNot enough memory to load databases.  Increase -memory.\n"); return 1; }
   }
   if (estimate) { fprintf(stderr, "\nStopping after memory estimated reported; -estimate option enabled.\n"); return 0; }
+
+  if (filtering) {                                            // filter(), include-exclude.C:137-154
+    FILE *outs[2] = {nullptr, nullptr};
+    const std::string *onames[2] = {&out_name, &out_name2};
+    const uint32_t n_in = seq_name2.empty() ? 1u : 2u;
+    for (uint32_t i = 0; i < n_in; i++)
+      if (!(outs[i] = fopen(onames[i]->c_str(), "w"))) die("ERROR: cannot write '%s'.", onames[i]->c_str());
+    fprintf(stderr, "\nLoading kmers from '%s' into lookup table.\n", dbs[0].c_str());
+    mgc_lookup *t = mgc_lookup_load(dbs[0].c_str(), vmin, vmax, -1, 0);
+    if (!t) die("ERROR: %s", mgc_lookup_error());
+    if (is10x)
+      fprintf(stderr, "\nRunning in 10x mode. The first 23 bp of every sequence in %s will be ignored while looking up.\n", seq_name.c_str());
+    uint64_t batch = 0;                                       // bytes per piece of input (MGC_LOOKUP_BATCH overrides the default)
+    if (getenv("MGC_LOOKUP_BATCH")) batch = strtoull(getenv("MGC_LOOKUP_BATCH"), nullptr, 10);
+    mgc_filter_result tot;
+    const int rc = mgc_lookup_filter_files(t, op == OP_INCLUDE ? MGC_FILTER_INCLUDE : MGC_FILTER_EXCLUDE, is10x ? 23u : 0u, seq_name.c_str(),
+                                           n_in == 2 ? seq_name2.c_str() : nullptr, batch, write_piece, outs[0],
+                                           n_in == 2 ? write_piece : nullptr, outs[1], &tot);
+    for (uint32_t i = 0; i < n_in; i++)
+      if (fclose(outs[i]) != 0) die("ERROR: cannot write '%s'.", onames[i]->c_str());
+    if (rc != MGC_OK) die("ERROR: %s", mgc_lookup_error());
+    // the reference passes the two numbers the other way round (include-exclude.C:153); here the sentence is true
+    fprintf(stderr, "\nIncluding %" PRIu64 " reads (or read pairs) out of %" PRIu64 ".\n", tot.n_kept, tot.n_records);
+    mgc_lookup_free(t);
+    return 0;
+  }
 
   msr_reader *r = msr_open(seq_name.c_str());
   if (!r) die("ERROR: %s", msr_last_error());

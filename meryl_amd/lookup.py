@@ -123,3 +123,70 @@ def report(tables, mode, names, bases, seq_start, labels=None, chunk_bytes=64 <<
                                         ss.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), c_names, len(names_b), chunk_bytes,
                                         cb, None), "mgc_lookup_report")
     return b"".join(pieces)
+
+
+FILTER_MODES = {"include": 0, "exclude": 1}
+
+
+def filter_text(table, mode, texts, skip_first=0, final=True, outs=None):
+    """mgc_lookup_filter_text: one step of meryl-lookup -include / -exclude (src/meryl-lookup/include-exclude.C) over raw
+    FASTA/FASTQ text.  texts: one or two uint8 cuda tensors, each beginning at a record start; mode: "include" / "exclude";
+    skip_first: 23 for -10x.  Returns (list of the kept text per input as bytes, capi.FilterResult).  outs: the output
+    tensors to use as they are; without them they are sized here and grown once when the library asks for more.  A failed
+    call raises capi.MgcError with the result (the sizes needed, when an output was too small) as its `result`."""
+    n = len(texts)
+    res = capi.FilterResult()
+    c_text = (ctypes.c_void_p * 2)(*[_ptr(t).value for t in texts])
+    c_n = (ctypes.c_uint64 * 2)(*[t.numel() for t in texts])
+    dev = texts[0].device
+    given = outs is not None
+    if not given:
+        outs = [torch.empty(t.numel() + t.numel() // 4 + 4096, dtype=torch.uint8, device=dev) for t in texts]
+    for attempt in range(2):
+        c_out = (ctypes.c_void_p * 2)(*[_ptr(o).value for o in outs])
+        c_cap = (ctypes.c_uint64 * 2)(*[o.numel() for o in outs])
+        rc = capi.lib().mgc_lookup_filter_text(table._h, FILTER_MODES.get(mode, mode), skip_first, n, c_text, c_n, 1 if final else 0,
+                                               c_out, c_cap, ctypes.byref(res), _stream())
+        short = rc == capi.MGC_EINVAL and any(res.out_bytes[i] > outs[i].numel() for i in range(n))
+        if rc == capi.MGC_OK or given or not short or attempt:
+            break
+        outs = [torch.empty(max(int(res.out_bytes[i]), 1), dtype=torch.uint8, device=dev) for i in range(n)]
+    if rc != capi.MGC_OK:
+        err = capi.MgcError(rc, "mgc_lookup_filter_text", capi.lib().mgc_lookup_error().decode("utf-8", "replace"))
+        err.result = res
+        raise err
+    torch.cuda.current_stream(dev).synchronize()
+    return [bytes(outs[i][:int(res.out_bytes[i])].cpu().numpy().tobytes()) for i in range(n)], res
+
+
+def filter_files(table, mode, paths, outputs, skip_first=0, batch_bytes=0, pieces=None):
+    """mgc_lookup_filter_files: the same over whole files (plain, gzip, BGZF), one or two of them.  outputs: per input a
+    path or a binary file object that receives the kept text.  pieces: a list that receives (input, bytes) as the callbacks
+    are called.  Returns capi.FilterResult with the totals."""
+    files = [open(o, "wb") if isinstance(o, (str, bytes)) or hasattr(o, "__fspath__") else o for o in outputs]
+    res = capi.FilterResult()
+
+    def _writer(i):
+        def _write(data, nbytes, _user):
+            b = ctypes.string_at(data, nbytes)
+            if pieces is not None:
+                pieces.append((i, b))
+            files[i].write(b)
+            return 0
+        return capi.LOOKUP_WRITE_CB(_write)
+
+    cbs = [_writer(i) for i in range(len(paths))]
+    null_cb = ctypes.cast(None, capi.LOOKUP_WRITE_CB)
+    try:
+        rc = capi.lib().mgc_lookup_filter_files(table._h, FILTER_MODES.get(mode, mode), skip_first, str(paths[0]).encode(),
+                                                str(paths[1]).encode() if len(paths) > 1 else None, batch_bytes, cbs[0], None,
+                                                cbs[1] if len(paths) > 1 else null_cb, None, ctypes.byref(res))
+    finally:
+        for f, o in zip(files, outputs):
+            if f is not o:
+                f.close()
+    if rc != capi.MGC_OK:
+        err = capi.MgcError(rc, "mgc_lookup_filter_files", capi.lib().mgc_lookup_error().decode("utf-8", "replace"))
+        err.result = res
+        raise err
+    return res
