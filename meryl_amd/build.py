@@ -14,12 +14,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmeryl_gpu_count.so")
 SOURCES = ["mgc_kmer.hip", "mgc_sort.hip", "mgc_scan.hip", "mgc_finish.hip", "mgc_misc.hip", "mgc_parse.hip",
-           "mgc_encode.hip", "mgc_decode.hip", "mgc_merge.hip", "mgc_lookup.hip", "mgc_filter.hip",
-           "mgc_api.cpp", "mgc_count.cpp", "mgc_stream.cpp", "mgc_runs.cpp", "mgc_node.cpp", "meryl_db.cpp", "meryl_seq.cpp"]
-HEADERS = ["mgc_device.h", "mgc_common.hpp", "mdb_layout.h", "mgc_session.hpp", "mgc_runs.hpp", "mgc_lookup_dev.hpp",
+           "mgc_encode.hip", "mgc_decode.hip", "mgc_merge.hip", "mgc_lookup.hip", "mgc_filter.hip", "mgc_import.hip",
+           "mgc_api.cpp", "mgc_import.cpp", "mgc_count.cpp", "mgc_stream.cpp", "mgc_runs.cpp", "mgc_node.cpp", "meryl_db.cpp", "meryl_seq.cpp"]
+HEADERS = ["mgc_device.h", "mgc_common.hpp", "mdb_layout.h", "mgc_session.hpp", "mgc_runs.hpp", "mgc_lookup_dev.hpp", "mgc_import_dev.hpp",
            os.path.join("..", "..", "include", "meryl_gpu_count.h"),
            os.path.join("..", "..", "include", "meryl_db.h"), os.path.join("..", "..", "include", "meryl_seq.h"),
-           os.path.join("..", "..", "include", "meryl_lookup.h")]
+           os.path.join("..", "..", "include", "meryl_lookup.h"), os.path.join("..", "..", "include", "meryl_import.h")]
 OBJDIR = os.path.join(HERE, "build")
 # -no-hip-rt: the library carries no DT_NEEDED on a particular libamdhip64; it binds to the
 # HIP runtime already in the process (torch's bundled one under Python -- two HIP/HSA runtimes
@@ -109,12 +109,34 @@ def build_lookup_cli(force=False, verbose=False):
     return LOOKUP_CLI
 
 
+IMPORT_CLI = os.path.join(HERE, "bin", "meryl-import")
+
+
+def build_import_cli(force=False, verbose=False):
+    """`meryl-import` (meryl_amd/bin/meryl-import: `kmer value` text -> database): links the library and the system HIP runtime."""
+    src = os.path.join(CSRC, "meryl_import_main.cpp")
+    if (not force and os.path.exists(IMPORT_CLI) and os.path.getmtime(IMPORT_CLI) >= os.path.getmtime(src)
+            and os.path.getmtime(IMPORT_CLI) >= os.path.getmtime(LIB)):
+        return IMPORT_CLI
+    os.makedirs(os.path.dirname(IMPORT_CLI), exist_ok=True)
+    rocm_lib = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
+    tmp = "%s.tmp%d" % (IMPORT_CLI, os.getpid())
+    cmd = [hipcc(), "-O2", "-std=c++17", "-pthread", src, "-o", tmp, "-L" + HERE, "-lmeryl_gpu_count",
+           "-Wl,-rpath,$ORIGIN/..", "-L" + rocm_lib, "-lamdhip64", "-Wl,-rpath," + rocm_lib, "-lz"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    os.replace(tmp, IMPORT_CLI)
+    return IMPORT_CLI
+
+
 def build(force=False, verbose=False):
     """Compile every HIP/C++ source for gfx950 (one object per source, rebuilt only when the source or a
     header changed, in parallel) and link libmeryl_gpu_count.so (and the CLI).  Returns the library path."""
     if not force and not _stale():
         build_cli(False, verbose)
         build_lookup_cli(False, verbose)
+        build_import_cli(False, verbose)
         return LIB
     os.makedirs(OBJDIR, exist_ok=True)
     todo = _stale_objects(force)
@@ -141,6 +163,7 @@ def build(force=False, verbose=False):
     os.replace(tmp, LIB)
     build_cli(True, verbose)
     build_lookup_cli(True, verbose)
+    build_import_cli(True, verbose)
     return LIB
 
 

@@ -1,4 +1,4 @@
-"""ctypes binding of include/meryl_gpu_count.h.
+"""ctypes binding of include/meryl_gpu_count.h (and meryl_db.h, meryl_lookup.h, meryl_seq.h, meryl_import.h).
 
 Loads meryl_amd/libmeryl_gpu_count.so and fails loudly when it is missing or
 an expected symbol is absent -- there is no Python/CPU fallback for any compute
@@ -39,6 +39,10 @@ SYMBOLS = (
     "mgc_lookup_load", "mgc_lookup_estimate", "mgc_lookup_from_device", "mgc_lookup_free", "mgc_lookup_get_info", "mgc_lookup_error",
     "mgc_lookup_values", "mgc_lookup_stream", "mgc_lookup_existence", "mgc_lookup_positions", "mgc_lookup_report", "mgc_lookup_filter_text", "mgc_lookup_filter_files",
     # include/meryl_seq.h
+    # include/meryl_import.h
+    "mgc_dev_import_parse_state_bytes", "mgc_dev_import_parse_workspace_bytes", "mgc_dev_import_parse_begin", "mgc_dev_import_parse_count",
+    "mgc_dev_import_parse", "mgc_dev_sort_pairs_workspace_bytes", "mgc_dev_sort_pairs", "mgc_dev_reduce_pairs_workspace_bytes",
+    "mgc_dev_reduce_pairs_count", "mgc_dev_reduce_pairs_emit", "mgc_import_file", "mgc_import_text", "mgc_import_error",
     "msr_open", "msr_read_text", "msr_close", "msr_last_error", "msr_load_bases", "msr_load_stream", "msr_format", "msr_is_compressed", "msr_guess_number_of_kmers",
 )
 
@@ -196,6 +200,25 @@ class FilterResult(ctypes.Structure):
     def as_dict(self):
         return {"n_records": self.n_records, "n_kept": self.n_kept, "consumed": list(self.consumed),
                 "out_bytes": list(self.out_bytes), "format": list(self.format)}
+
+
+class ImportParseResult(ctypes.Structure):
+    """mgc_import_parse_result (include/meryl_import.h)"""
+    _fields_ = [("n_lines", ctypes.c_uint64), ("n_records", ctypes.c_uint64), ("bad_line", ctypes.c_uint64),
+                ("bad_kind", ctypes.c_uint32), ("persistent_value", ctypes.c_uint32)]
+
+
+class ImportInfo(ctypes.Structure):
+    """mgc_import_info (include/meryl_import.h)"""
+    _fields_ = [("n_lines", ctypes.c_uint64), ("n_records", ctypes.c_uint64), ("n_distinct", ctypes.c_uint64),
+                ("n_batches", ctypes.c_uint64), ("text_bytes", ctypes.c_uint64), ("bad_line", ctypes.c_uint64),
+                ("bad_kind", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("upload_ms", ctypes.c_double), ("parse_ms", ctypes.c_double), ("sort_ms", ctypes.c_double),
+                ("reduce_ms", ctypes.c_double), ("read_s", ctypes.c_double), ("write_s", ctypes.c_double),
+                ("total_s", ctypes.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
 class IndexEntry(ctypes.Structure):
@@ -398,6 +421,19 @@ def lib():
     sig("mgc_lookup_filter_text", i32, vp, i32, u32, u32, P(vp), P(u64), i32, P(vp), P(u64), P(FilterResult), vp)
     sig("mgc_lookup_filter_files", i32, vp, i32, u32, ctypes.c_char_p, ctypes.c_char_p, u64, LOOKUP_WRITE_CB, vp, LOOKUP_WRITE_CB, vp,
         P(FilterResult))
+    sig("mgc_dev_import_parse_state_bytes", sz)
+    sig("mgc_dev_import_parse_workspace_bytes", sz, u64)
+    sig("mgc_dev_import_parse_begin", i32, vp, vp)
+    sig("mgc_dev_import_parse_count", i32, vp, u64, u32, vp, vp, sz, P(ImportParseResult), vp)
+    sig("mgc_dev_import_parse", i32, vp, u64, u32, i32, vp, vp, sz, vp, vp, vp)
+    sig("mgc_dev_sort_pairs_workspace_bytes", sz, u64)
+    sig("mgc_dev_sort_pairs", i32, vp, vp, vp, vp, u64, u32, u32, u32, vp, sz, P(i32), vp)
+    sig("mgc_dev_reduce_pairs_workspace_bytes", sz, u64)
+    sig("mgc_dev_reduce_pairs_count", i32, vp, vp, u64, u32, vp, sz, P(u64), vp)
+    sig("mgc_dev_reduce_pairs_emit", i32, vp, vp, u64, u32, vp, sz, vp, vp, vp)
+    sig("mgc_import_file", i32, ctypes.c_char_p, u32, i32, ctypes.c_char_p, i32, i32, P(ImportInfo))
+    sig("mgc_import_text", i32, ctypes.c_char_p, u64, u32, i32, ctypes.c_char_p, i32, i32, P(ImportInfo))
+    sig("mgc_import_error", ctypes.c_char_p)
     sig("msr_open", vp, ctypes.c_char_p)
     sig("msr_close", None, vp)
     sig("msr_read_text", ctypes.c_int64, vp, vp, u64)

@@ -1,0 +1,425 @@
+// mgc_import.cpp -- C-ABI layer of include/meryl_import.h: the bare device steps and the text -> database driver.
+//
+// Reference side: main() of src/meryl-import/meryl-import.C:137-256 -- read a line, push (suffix, value) into one of 1024
+// merylCountArrays, then countKmers + dumpCountedKmers per prefix into a wPrefix = 10 database.  Here the text goes to the
+// device in batches cut at a line end; every batch is parsed, sorted and reduced there (mgc_import.hip); one batch is handed
+// straight to the database stream, several are parked as runs and merged once (include/meryl_db.h).  Nothing is created at
+// the output path before the whole input has been accepted.
+#include "../../include/meryl_import.h"
+#include "../../include/meryl_db.h"
+#include "mgc_import_dev.hpp"
+#include "mgc_runs.hpp"
+
+#include <algorithm>
+#include <chrono>
+#include <condition_variable>
+#include <cstdlib>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+#include <zlib.h>
+
+using mgc::set_err;
+
+namespace {
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+int hip_rc(hipError_t e, const char *what) {
+  if (e == hipSuccess) return MGC_OK;
+  set_err(nullptr, "%s: %s", what, hipGetErrorString(e));
+  return (e == hipErrorOutOfMemory) ? MGC_ENOMEM : MGC_EHIP;
+}
+bool k_ok(uint32_t k) {
+  if (k >= MGC_IMPORT_MIN_K && k <= MGC_IMPORT_MAX_K) return true;
+  set_err(nullptr, "meryl-import: k=%u out of range (%d..%d: a 10-bit prefix must leave a suffix)", k, MGC_IMPORT_MIN_K, MGC_IMPORT_MAX_K);
+  return false;
+}
+const char *bad_text(uint32_t kind) {
+  switch (kind) {
+    case MGC_IMPORT_BAD_BASE:  return "the k-mer holds a byte that is not one of ACGTacgt";
+    case MGC_IMPORT_BAD_SHORT: return "the k-mer is shorter than k";
+    case MGC_IMPORT_BAD_VALUE: return "the value is not a decimal number of at most 4294967295";
+    case MGC_IMPORT_BAD_HASH:  return "the number after '#' is not a decimal number of at most 4294967295";
+  }
+  return "malformed";
+}
+}  // namespace
+
+// ================================================================================================
+//  device steps
+// ================================================================================================
+extern "C" const char *mgc_import_error(void) { return mgc::thread_last_error().c_str(); }
+
+extern "C" size_t mgc_dev_import_parse_state_bytes(void) { return sizeof(mgc::ImportState); }
+extern "C" size_t mgc_dev_import_parse_workspace_bytes(uint64_t n_text) { return mgc::import_parse_workspace_bytes(n_text); }
+
+extern "C" int mgc_dev_import_parse_begin(void *d_state, void *stream) {
+  if (!d_state) return MGC_EINVAL;
+  return hip_rc(mgc::launch_import_begin(reinterpret_cast<mgc::ImportState *>(d_state), (hipStream_t)stream), "import_parse_begin");
+}
+
+extern "C" int mgc_dev_import_parse_count(const uint8_t *d_text, uint64_t n_text, uint32_t k, void *d_state, void *d_ws,
+                                          size_t ws_bytes, mgc_import_parse_result *res, void *stream) {
+  if (!k_ok(k)) return MGC_EINVAL;
+  if (!d_state || !d_ws || !res || (n_text && !d_text) || n_text > 0xFFFFFFFFull || ws_bytes < mgc::import_parse_workspace_bytes(n_text)) {
+    set_err(nullptr, "mgc_dev_import_parse_count: bad arguments (a chunk holds fewer than 2^32 bytes)");
+    return MGC_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  mgc::ImportState *ds = reinterpret_cast<mgc::ImportState *>(d_state);
+  hipError_t e = mgc::launch_import_parse_count(d_text, n_text, k, ds, d_ws, st);
+  if (e != hipSuccess) return hip_rc(e, "import_parse_count");
+  mgc::ImportState h;
+  e = hipMemcpyAsync(&h, ds, sizeof(h), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return hip_rc(e, "import_parse_count sync");
+  res->n_lines = h.chunk_lines;
+  res->n_records = h.chunk_records;
+  res->bad_line = h.first_bad == ~0ull ? 0 : h.first_bad >> 3;
+  res->bad_kind = h.first_bad == ~0ull ? 0u : (uint32_t)(h.first_bad & 7);
+  res->persistent_value = h.chunk_has ? h.chunk_val : h.persistent;
+  return MGC_OK;
+}
+
+extern "C" int mgc_dev_import_parse(const uint8_t *d_text, uint64_t n_text, uint32_t k, int mode, void *d_state, void *d_ws,
+                                    size_t ws_bytes, void *d_keys, uint32_t *d_values, void *stream) {
+  if (!k_ok(k)) return MGC_EINVAL;
+  if (mode < 0 || mode > 2 || !d_state || !d_ws || (n_text && !d_text) || n_text > 0xFFFFFFFFull ||
+      ws_bytes < mgc::import_parse_workspace_bytes(n_text)) {
+    set_err(nullptr, "mgc_dev_import_parse: bad arguments");
+    return MGC_EINVAL;
+  }
+  return hip_rc(mgc::launch_import_parse_emit(d_text, n_text, k, mode, reinterpret_cast<mgc::ImportState *>(d_state), d_ws, d_keys,
+                                              d_values, (hipStream_t)stream), "import_parse");
+}
+
+extern "C" size_t mgc_dev_sort_pairs_workspace_bytes(uint64_t n) { return mgc::sort_pairs_workspace_bytes(n); }
+
+extern "C" int mgc_dev_sort_pairs(void *d_keys, uint32_t *d_values, void *d_alt_keys, uint32_t *d_alt_values, uint64_t n,
+                                  uint32_t key_words, uint32_t begin_bit, uint32_t end_bit, void *d_ws, size_t ws_bytes,
+                                  int *result_in_alt, void *stream) {
+  if (!result_in_alt || begin_bit > end_bit || (key_words != 1 && key_words != 2) || end_bit > 64 * key_words) return MGC_EINVAL;
+  *result_in_alt = 0;
+  if (n == 0 || begin_bit == end_bit) return MGC_OK;
+  if (!d_keys || !d_values || !d_alt_keys || !d_alt_values || !d_ws || ws_bytes < mgc::sort_pairs_workspace_bytes(n)) return MGC_EINVAL;
+  return hip_rc(mgc::launch_sort_pairs(d_keys, d_values, d_alt_keys, d_alt_values, n, key_words, begin_bit, end_bit, d_ws, result_in_alt,
+                                       (hipStream_t)stream), "sort_pairs");
+}
+
+extern "C" size_t mgc_dev_reduce_pairs_workspace_bytes(uint64_t n) { return mgc::reduce_pairs_workspace_bytes(n); }
+
+extern "C" int mgc_dev_reduce_pairs_count(const void *d_keys, const uint32_t *d_values, uint64_t n, uint32_t key_words, void *d_ws,
+                                          size_t ws_bytes, uint64_t *n_distinct, void *stream) {
+  if (!n_distinct || !d_ws || ws_bytes < mgc::reduce_pairs_workspace_bytes(n) || (n && (!d_keys || !d_values)) ||
+      (key_words != 1 && key_words != 2)) return MGC_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = mgc::launch_reduce_pairs_count(d_keys, d_values, n, key_words, d_ws, st);
+  if (e != hipSuccess) return hip_rc(e, "reduce_pairs_count");
+  e = hipMemcpyAsync(n_distinct, d_ws, sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return hip_rc(e, "reduce_pairs_count sync");
+}
+
+extern "C" int mgc_dev_reduce_pairs_emit(const void *d_keys, const uint32_t *d_values, uint64_t n, uint32_t key_words, void *d_ws,
+                                         size_t ws_bytes, void *d_out_keys, uint32_t *d_out_values, void *stream) {
+  if (!d_ws || ws_bytes < mgc::reduce_pairs_workspace_bytes(n) || (n && (!d_keys || !d_values || !d_out_keys || !d_out_values)) ||
+      (key_words != 1 && key_words != 2)) return MGC_EINVAL;
+  return hip_rc(mgc::launch_reduce_pairs_emit(d_keys, d_values, n, key_words, d_ws, d_out_keys, d_out_values, (hipStream_t)stream),
+                "reduce_pairs_emit");
+}
+
+// ================================================================================================
+//  text -> database
+// ================================================================================================
+namespace {
+
+struct Source {                                            // bytes, 0 at the end, < 0 on a read error
+  virtual int64_t read(char *dst, size_t cap) = 0;
+  virtual ~Source() {}
+};
+struct MemSource : Source {
+  const char *p; uint64_t n, at = 0;
+  MemSource(const char *p_, uint64_t n_) : p(p_), n(n_) {}
+  int64_t read(char *dst, size_t cap) override {
+    const size_t m = (size_t)std::min<uint64_t>(cap, n - at);
+    if (m) memcpy(dst, p + at, m);
+    at += m;
+    return (int64_t)m;
+  }
+};
+struct GzSource : Source {                                 // plain files pass through zlib unchanged
+  gzFile gz = nullptr;
+  ~GzSource() override { if (gz) gzclose(gz); }
+  int64_t read(char *dst, size_t cap) override {
+    size_t got = 0;
+    while (got < cap) {
+      const unsigned want = (unsigned)std::min<size_t>(cap - got, 1u << 30);
+      const int r = gzread(gz, dst + got, want);
+      if (r < 0) return -1;
+      if (r == 0) break;
+      got += (size_t)r;
+    }
+    return (int64_t)got;
+  }
+};
+
+// Two pinned buffers filled by a reader thread: a batch is everything up to the last '\n' that fits; what follows it is
+// carried into the next batch; a line longer than the buffer grows it.
+struct Reader {
+  struct Slot { char *p = nullptr; size_t cap = 0, n = 0; bool last = false, full = false; };
+  Slot slot[2];
+  Source *src = nullptr;
+  std::mutex mu;
+  std::condition_variable cv;
+  std::thread th;
+  bool stop = false, failed = false;
+  double read_s = 0;
+  int device = 0;
+
+  ~Reader() {
+    { std::lock_guard<std::mutex> g(mu); stop = true; }
+    cv.notify_all();
+    if (th.joinable()) th.join();
+    for (Slot &s : slot) if (s.p) (void)hipHostFree(s.p);
+  }
+  bool grow(Slot &s, size_t cap, size_t keep) {
+    void *q = nullptr;
+    if (hipHostMalloc(&q, cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (keep) memcpy(q, s.p, keep);
+    if (s.p) (void)hipHostFree(s.p);
+    s.p = reinterpret_cast<char *>(q); s.cap = cap;
+    return true;
+  }
+  bool start(Source *s, size_t batch, int dev) {
+    src = s; device = dev;
+    for (Slot &sl : slot) if (!grow(sl, batch, 0)) return false;
+    th = std::thread([this] { main(); });
+    return true;
+  }
+  void main() {
+    (void)hipSetDevice(device);
+    std::vector<char> tail;
+    bool eof = false;
+    for (int i = 0; !eof; i ^= 1) {
+      Slot &s = slot[i];
+      {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return stop || !s.full; });
+        if (stop) return;
+      }
+      const double t0 = now_s();
+      size_t have = tail.size();
+      bool bad = false;
+      if (have > s.cap && !grow(s, 2 * have, 0)) bad = true;
+      if (!bad && have) memcpy(s.p, tail.data(), have);
+      tail.clear();
+      size_t cut = 0;
+      while (!bad) {
+        const int64_t r = src->read(s.p + have, s.cap - have);
+        if (r < 0) { bad = true; break; }
+        have += (size_t)r;
+        if (have < s.cap) { eof = true; cut = have; break; }
+        size_t j = have;
+        while (j > 0 && s.p[j - 1] != '\n') j--;
+        if (j > 0) { cut = j; break; }
+        if (s.cap >= (0xFFFFFFFFull >> 1) || !grow(s, 2 * s.cap, have)) bad = true;      // one line longer than the batch
+      }
+      read_s += now_s() - t0;
+      std::lock_guard<std::mutex> g(mu);
+      if (bad) { failed = true; s.n = 0; s.last = true; s.full = true; cv.notify_all(); return; }
+      if (cut < have) tail.assign(s.p + cut, s.p + have);
+      s.n = cut; s.last = eof; s.full = true;
+      cv.notify_all();
+    }
+  }
+  Slot *wait(int i) {
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [&] { return slot[i].full; });
+    return &slot[i];
+  }
+  void release(int i) {
+    { std::lock_guard<std::mutex> g(mu); slot[i].full = false; }
+    cv.notify_all();
+  }
+};
+
+struct Importer {
+  typedef mgc_runs::DBuf DBuf;
+  uint32_t k, kw;
+  int mode, device, host_threads;
+  hipStream_t st = nullptr;
+  hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  DBuf d_text, d_state, d_pws, d_k[2], d_v[2], d_sws, d_rws;
+  mgc_runs *runs = nullptr;
+  mgc_import_info info;
+
+  ~Importer() {
+    (void)hipSetDevice(device);
+    if (runs) mgc_runs_close(runs);
+    for (DBuf *b : {&d_text, &d_state, &d_pws, &d_k[0], &d_k[1], &d_v[0], &d_v[1], &d_sws, &d_rws}) b->release();
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    if (st) (void)hipStreamDestroy(st);
+  }
+
+#define IM_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) {                                        \
+    set_err(nullptr, "%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e__));                      \
+    return (e__ == hipErrorOutOfMemory) ? MGC_ENOMEM : MGC_EHIP; } } while (0)
+
+  // one batch of whole lines -> *out_k / *out_v: nd ascending distinct k-mers and their summed values (device memory of this object)
+  int batch(const char *h_text, size_t n, Reader *rd, int slot, const void **out_k, const uint32_t **out_v, uint64_t *nd) {
+    *out_k = nullptr; *out_v = nullptr; *nd = 0;
+    IM_TRY(d_text.ensure(n + 64));
+    IM_TRY(d_pws.ensure(mgc::import_parse_workspace_bytes(n)));
+    IM_TRY(hipEventRecord(ev[0], st));
+    IM_TRY(hipMemcpyAsync(d_text.p, h_text, n, hipMemcpyHostToDevice, st));
+    IM_TRY(hipEventRecord(ev[1], st));
+    mgc::ImportState *ds = d_state.as<mgc::ImportState>();
+    IM_TRY(mgc::launch_import_parse_count(d_text.as<uint8_t>(), n, k, ds, d_pws.p, st));
+    IM_TRY(hipEventRecord(ev[2], st));
+    mgc::ImportState h;
+    IM_TRY(hipMemcpyAsync(&h, ds, sizeof(h), hipMemcpyDeviceToHost, st));
+    IM_TRY(hipStreamSynchronize(st));
+    rd->release(slot);                                      // the text has left the pinned buffer
+    info.n_lines += h.chunk_lines;
+    if (h.first_bad != ~0ull) {
+      info.bad_line = h.first_bad >> 3; info.bad_kind = (uint32_t)(h.first_bad & 7);
+      set_err(nullptr, "meryl-import: line %llu: %s", (unsigned long long)info.bad_line, bad_text(info.bad_kind));
+      return MGC_EFORMAT;
+    }
+    info.n_records += h.chunk_records;
+    const uint64_t nr = h.chunk_records;
+    const size_t kb = sizeof(uint64_t) * kw;
+    for (int i = 0; i < 2; i++) { IM_TRY(d_k[i].ensure(kb * nr)); IM_TRY(d_v[i].ensure(sizeof(uint32_t) * nr)); }
+    IM_TRY(d_sws.ensure(mgc::sort_pairs_workspace_bytes(nr)));
+    IM_TRY(d_rws.ensure(mgc::reduce_pairs_workspace_bytes(nr)));
+    IM_TRY(hipEventRecord(ev[3], st));
+    IM_TRY(mgc::launch_import_parse_emit(d_text.as<uint8_t>(), n, k, mode, ds, d_pws.p, d_k[0].p, d_v[0].as<uint32_t>(), st));
+    IM_TRY(hipEventRecord(ev[4], st));
+    int in_alt = 0;
+    IM_TRY(mgc::launch_sort_pairs(d_k[0].p, d_v[0].as<uint32_t>(), d_k[1].p, d_v[1].as<uint32_t>(), nr, kw, 0, 2 * k, d_sws.p, &in_alt, st));
+    IM_TRY(hipEventRecord(ev[5], st));
+    const int s = in_alt ? 1 : 0, o = s ^ 1;
+    IM_TRY(mgc::launch_reduce_pairs_count(d_k[s].p, d_v[s].as<uint32_t>(), nr, kw, d_rws.p, st));
+    IM_TRY(mgc::launch_reduce_pairs_emit(d_k[s].p, d_v[s].as<uint32_t>(), nr, kw, d_rws.p, d_k[o].p, d_v[o].as<uint32_t>(), st));   // (synchronises for the count)
+    IM_TRY(hipMemcpyAsync(nd, d_rws.p, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    IM_TRY(hipEventRecord(ev[6], st));
+    IM_TRY(hipEventSynchronize(ev[6]));
+    float ms[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 6; i++) IM_TRY(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    info.upload_ms += ms[0]; info.parse_ms += ms[1] + ms[3]; info.sort_ms += ms[4]; info.reduce_ms += ms[5];
+    *out_k = d_k[o].p; *out_v = d_v[o].as<uint32_t>();
+    return MGC_OK;
+  }
+
+  int run(Source *src, const char *output) {
+    const double t_begin = now_s();
+    memset(&info, 0, sizeof(info));
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_err(nullptr, "meryl-import: no HIP device"); return MGC_EHIP; }
+    if (device < 0) (void)hipGetDevice(&device);
+    IM_TRY(hipSetDevice(device));
+    IM_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    for (hipEvent_t &e : ev) IM_TRY(hipEventCreate(&e));
+    size_t free_b = 0, total_b = 0;
+    IM_TRY(hipMemGetInfo(&free_b, &total_b));
+    // per byte of text: the text itself, two (key, value) buffer pairs (a record takes at least k + 1 bytes) and the runs.
+    // At most 256 MiB: the reader fills the next batch while this one is uploaded and worked on, and pinning the two
+    // buffers is paid before the first byte moves (one 1 GiB batch took twice the wall clock of seven 128 MiB ones)
+    uint64_t batch_bytes = std::min<uint64_t>(std::max<uint64_t>(free_b / 12, 1u << 20), 256ull << 20);
+    if (const char *e = getenv("MGC_IMPORT_BATCH")) { if (*e) batch_bytes = strtoull(e, nullptr, 10); }
+    batch_bytes = std::min<uint64_t>(std::max<uint64_t>(batch_bytes, 64), 1ull << 31);
+    IM_TRY(d_state.ensure(sizeof(mgc::ImportState)));
+    IM_TRY(mgc::launch_import_begin(d_state.as<mgc::ImportState>(), st));
+
+    Reader rd;
+    if (!rd.start(src, (size_t)batch_bytes, device)) { set_err(nullptr, "meryl-import: no pinned memory for batches of %llu bytes", (unsigned long long)batch_bytes); return MGC_ENOMEM; }
+
+    int rc = MGC_OK;
+    const void *bk = nullptr; const uint32_t *bv = nullptr; uint64_t bn = 0;
+    bool single = false;
+    for (int i = 0;; i ^= 1) {
+      Reader::Slot *s = rd.wait(i);
+      if (rd.failed) { set_err(nullptr, "meryl-import: reading the input failed"); return MGC_EINVAL; }
+      const bool last = s->last;
+      const size_t n = s->n;
+      info.text_bytes += n;
+      if (n == 0) { rd.release(i); if (last) break; continue; }
+      info.n_batches++;
+      rc = batch(s->p, n, &rd, i, &bk, &bv, &bn);
+      if (rc != MGC_OK) return rc;
+      if (last && info.n_batches == 1) { single = true; break; }
+      if (!runs) {
+        runs = mgc_runs_open(k, MGC_IMPORT_W_PREFIX, device, free_b / 3, 0);
+        if (!runs) { set_err(nullptr, "meryl-import: %s", mgc_runs_error(nullptr)); return MGC_EHIP; }
+      }
+      rc = mgc_runs_add(runs, bk, bv, bn, st);
+      if (rc != MGC_OK) { set_err(nullptr, "meryl-import: %s", mgc_runs_error(runs)); return rc; }
+      if (last) break;
+    }
+    info.read_s = rd.read_s;
+
+    // the whole input is accepted: only now does anything appear at the output path
+    const double t_write = now_s();
+    mgc_db_stream *d = mgc_db_stream_open(output, k, MGC_IMPORT_W_PREFIX, 0, 0, 0, 1, host_threads, device);
+    if (!d) { set_err(nullptr, "meryl-import: %s", mgc_db_stream_error(nullptr)); return MGC_EINVAL; }
+    std::string msg;
+    const uint64_t n_prefix = 1ull << MGC_IMPORT_W_PREFIX;
+    if (runs) {
+      for (DBuf *b : {&d_text, &d_k[0], &d_k[1], &d_v[0], &d_v[1], &d_sws}) b->release();     // room for the merge
+      rc = mgc_runs_write(runs, d, 0, n_prefix);
+      if (rc != MGC_OK) msg = mgc_runs_error(runs);
+      mgc_runs_profile rp;
+      if (rc == MGC_OK && mgc_runs_get_profile(runs, &rp) == MGC_OK) info.n_distinct = rp.n_merged;
+    } else {
+      rc = mgc_db_stream_write(d, single ? bk : nullptr, single ? bv : nullptr, single ? bn : 0, 0, n_prefix);
+      if (rc != MGC_OK) msg = mgc_db_stream_error(d);
+      info.n_distinct = single ? bn : 0;
+    }
+    const int rc2 = mgc_db_stream_close(d, nullptr);
+    if (rc == MGC_OK && rc2 != MGC_OK) { rc = rc2; msg = mgc_db_stream_error(nullptr); }
+    if (rc != MGC_OK) set_err(nullptr, "meryl-import: %s", msg.c_str());
+    info.write_s = now_s() - t_write;
+    info.total_s = now_s() - t_begin;
+    return rc;
+  }
+#undef IM_TRY
+};
+
+int import_from(Source *src, uint32_t k, int mode, const char *output, int device, int host_threads, mgc_import_info *info) {
+  Importer im;
+  im.k = k; im.kw = k > 32 ? 2u : 1u; im.mode = mode; im.device = device; im.host_threads = host_threads;
+  memset(&im.info, 0, sizeof(im.info));
+  const int rc = im.run(src, output);
+  if (info) *info = im.info;
+  return rc;
+}
+
+bool import_args_ok(uint32_t k, int mode, const char *output) {
+  if (!k_ok(k)) return false;
+  if (mode < 0 || mode > 2 || !output || !*output) { set_err(nullptr, "meryl-import: bad mode or no output path"); return false; }
+  return true;
+}
+}  // namespace
+
+extern "C" int mgc_import_file(const char *path, uint32_t k, int mode, const char *output, int device, int host_threads,
+                               mgc_import_info *info) {
+  if (info) memset(info, 0, sizeof(*info));
+  if (!path || !*path) { set_err(nullptr, "meryl-import: no input path"); return MGC_EINVAL; }
+  if (!import_args_ok(k, mode, output)) return MGC_EINVAL;
+  GzSource src;
+  const std::string p(path);
+  src.gz = (p == "-") ? gzdopen(0, "rb") : gzopen(path, "rb");
+  if (!src.gz) { set_err(nullptr, "meryl-import: cannot open '%s'", path); return MGC_EINVAL; }
+  (void)gzbuffer(src.gz, 1u << 20);
+  return import_from(&src, k, mode, output, device, host_threads, info);
+}
+
+extern "C" int mgc_import_text(const char *text, uint64_t n_text, uint32_t k, int mode, const char *output, int device,
+                               int host_threads, mgc_import_info *info) {
+  if (info) memset(info, 0, sizeof(*info));
+  if (!text && n_text) { set_err(nullptr, "meryl-import: NULL text"); return MGC_EINVAL; }
+  if (!import_args_ok(k, mode, output)) return MGC_EINVAL;
+  MemSource src(text, n_text);
+  return import_from(&src, k, mode, output, device, host_threads, info);
+}

@@ -1,0 +1,563 @@
+// mgc_import.hip -- `kmer value` text -> sorted distinct (k-mer, summed value) pairs, on the device (gfx950).
+//
+// What it replaces in the reference (paths relative to the reference root):
+//   import_parse_*   the line loop of src/meryl-import/meryl-import.C:177-219: readLine + splitToWords, `#<value>` lines
+//                    setting the persistent value (:175, :188-191), addR of every base of the first word (:196-197: a word
+//                    longer than k keeps its LAST k bases), reverseComplement and the canonical / forward / reverse pick
+//                    (:199-211), the optional second word as the value (:193-194)
+//   pair_*           the std::sort of (suffix, value) records in countSingleKmersWithValues, src/meryl/merylCountArray.C:387
+//   reduce_*         its summing loop over equal suffixes, :393-408 (uint32 sums wrap, :403)
+//
+// Two things are sequential in the text: the output slot of a record (records before it) and the persistent value (the
+// last `#` line before it).  Both are one scan with the operator of PAgg below: tiles of 4096 bytes summarise themselves,
+// one workgroup composes the summaries, a second pass over the text writes.  The same shape -- per-tile aggregate, one
+// composing workgroup, emit -- sums the values of equal keys: the aggregate carries "sum of the segment still open at the
+// end", so a key repeated over any number of tiles and workgroups is summed across them (RAgg).
+// No kernel here waits for another workgroup of its launch; every index is checked against n before it is used.
+#include "mgc_common.hpp"
+#include "mgc_import_dev.hpp"
+#include "../../include/meryl_import.h"
+
+namespace mgc {
+
+// Exclusive scan of one aggregate per thread with A::combine (associative, not commutative), through LDS.
+// s: BLOCK entries.  Every thread of the block must call it.
+template <int BLOCK, typename A>
+__device__ __forceinline__ A block_scan_excl(A v, A *s, A *total) {
+  const u32 t = threadIdx.x;
+  __syncthreads();                        // s may still be read from a previous call
+  s[t] = v;
+  __syncthreads();
+  for (u32 d = 1; d < (u32)BLOCK; d <<= 1) {
+    A x = s[t];
+    if (t >= d) x = A::combine(s[t - d], x);
+    __syncthreads();
+    s[t] = x;
+    __syncthreads();
+  }
+  *total = s[BLOCK - 1];
+  return t ? s[t - 1] : A::identity();
+}
+
+// One workgroup turns T per-tile aggregates into their exclusive scan, in place; the total goes to *total.
+constexpr int CP_BLOCK = 1024;
+template <typename A>
+__global__ __launch_bounds__(CP_BLOCK)
+void compose_tiles_kernel(A *__restrict__ tiles, u64 T, A *__restrict__ total) {
+  __shared__ A s[CP_BLOCK];
+  const u64 per = (T + CP_BLOCK - 1) / CP_BLOCK;
+  const u64 a = (u64)threadIdx.x * per < T ? (u64)threadIdx.x * per : T;
+  const u64 b = a + per < T ? a + per : T;
+  A agg = A::identity();
+  for (u64 i = a; i < b; i++) agg = A::combine(agg, tiles[i]);
+  A tot;
+  A run = block_scan_excl<CP_BLOCK, A>(agg, s, &tot);
+  for (u64 i = a; i < b; i++) {
+    const A x = tiles[i];
+    tiles[i] = run;
+    run = A::combine(run, x);
+  }
+  if (threadIdx.x == 0) *total = tot;
+}
+
+// ============================================================================
+//  Text parser
+// ============================================================================
+constexpr int PR_BLOCK = 256;
+constexpr int PR_BYTES = 16;                       // text bytes per thread
+constexpr int PR_TILE  = PR_BLOCK * PR_BYTES;      // 4096
+
+// records / lines that start in a range, and the number of the last `#` line in it
+struct PAgg {
+  u32 rec, lines, has, val;
+  static __device__ __forceinline__ PAgg identity() { PAgg a; a.rec = a.lines = a.has = a.val = 0; return a; }
+  static __device__ __forceinline__ PAgg combine(PAgg a, PAgg b) {
+    PAgg r; r.rec = a.rec + b.rec; r.lines = a.lines + b.lines; r.has = a.has | b.has; r.val = b.has ? b.val : a.val; return r;
+  }
+};
+
+enum { LN_BLANK = 0, LN_HASH = 1, LN_RECORD = 2, LN_BAD = 3 };
+struct Line { u32 kind, bad, value, has_value; u64 lo, hi; };
+
+__device__ __forceinline__ bool pr_is_space(u32 c) { return c == ' ' || c == '\t' || c == '\r'; }
+
+// a decimal word at t[j...]: ends at white space, '\n' or n.  false: no digit, a byte that is not a digit, or above 2^32 - 1
+__device__ __forceinline__ bool pr_number(const uint8_t *__restrict__ t, u64 n, u64 &j, u32 *out) {
+  u64 v = 0;
+  u32 nd = 0;
+  bool ok = true;
+  while (j < n) {
+    const u32 c = t[j];
+    if (c == '\n' || pr_is_space(c)) break;
+    if (c < '0' || c > '9') ok = false;
+    else { v = v * 10ull + (u64)(c - '0'); if (v > 0xFFFFFFFFull) { ok = false; v = 0; } nd++; }
+    j++;
+  }
+  *out = (u32)v;
+  return ok && nd > 0;
+}
+
+// first byte of the line's first word (n: none)
+__device__ __forceinline__ u64 pr_first_word(const uint8_t *__restrict__ t, u64 n, u64 p) {
+  while (p < n && pr_is_space(t[p])) p++;
+  return (p < n && t[p] != '\n') ? p : n;
+}
+
+// the line that starts at byte p.  KT: u64 (k <= 32) or u128
+template <typename KT>
+__device__ Line parse_line(const uint8_t *__restrict__ t, u64 n, u64 p, u32 k, int mode, bool want_key) {
+  Line L;
+  L.kind = LN_BLANK; L.bad = 0; L.value = 0; L.has_value = 0; L.lo = L.hi = 0;
+  u64 j = pr_first_word(t, n, p);
+  if (j >= n) return L;
+  if (t[j] == '#') {                                                     // meryl-import.C:188-191
+    j++;
+    if (pr_number(t, n, j, &L.value)) L.kind = LN_HASH;
+    else { L.kind = LN_BAD; L.bad = MGC_IMPORT_BAD_HASH; }
+    return L;
+  }
+  const KT mask = (2 * k == 8 * sizeof(KT)) ? ~(KT)0 : (((KT)1 << (2 * k)) - 1);
+  KT f = 0;
+  u32 len = 0;
+  bool bases_ok = true;
+  while (j < n) {
+    const u32 c = t[j];
+    if (c == '\n' || pr_is_space(c)) break;
+    const u32 up = c & 0xDFu;
+    if (up != 'A' && up != 'C' && up != 'G' && up != 'T') bases_ok = false;
+    f = ((f << 2) | (KT)((c >> 1) & 3u)) & mask;                         // A0 C1 T2 G3, either case (mgc_kmer.hip)
+    if (len < 0xFFFFFFFFu) len++;
+    j++;
+  }
+  if (!bases_ok) { L.kind = LN_BAD; L.bad = MGC_IMPORT_BAD_BASE; return L; }
+  if (len < k)   { L.kind = LN_BAD; L.bad = MGC_IMPORT_BAD_SHORT; return L; }
+  while (j < n && pr_is_space(t[j])) j++;
+  if (j < n && t[j] != '\n') {                                           // :193-194; words after it are ignored
+    if (!pr_number(t, n, j, &L.value)) { L.kind = LN_BAD; L.bad = MGC_IMPORT_BAD_VALUE; return L; }
+    L.has_value = 1;
+  }
+  L.kind = LN_RECORD;
+  if (want_key) {
+    KT key = f;
+    if (mode != MGC_MODE_FORWARD) {
+      KT r = 0, x = f;
+      for (u32 i = 0; i < k; i++) { r = (r << 2) | ((x & 3) ^ 2); x >>= 2; }   // base i -> base k-1-i, complemented
+      key = (mode == MGC_MODE_REVERSE) ? r : (f < r ? f : r);
+    }
+    L.lo = (u64)key;
+    if (sizeof(KT) > 8) L.hi = (u64)((u128)key >> 64);
+  }
+  return L;
+}
+
+// bit q: a line starts at byte p0 + q (a line starts at byte 0 and after every '\n')
+__device__ __forceinline__ u32 pr_line_starts(const uint8_t *__restrict__ t, u64 n, u64 p0, bool aligned) {
+  if (p0 >= n) return 0;
+  const uint4 w = load16(t, p0, n, aligned);             // bytes at and beyond n read as '.'
+  const u32 ww[4] = {w.x, w.y, w.z, w.w};
+  u32 prev = p0 ? (u32)t[p0 - 1] : (u32)'\n';
+  u32 starts = 0;
+#pragma unroll
+  for (int q = 0; q < PR_BYTES; q++) {
+    if (p0 + q < n && prev == '\n') starts |= 1u << q;
+    prev = (ww[q >> 2] >> (8 * (q & 3))) & 0xFFu;
+  }
+  return starts;
+}
+
+// Pass 1: every line validated, the tile's aggregate written; the first refused line of the chunk by its byte offset.
+template <typename KT>
+__global__ __launch_bounds__(PR_BLOCK)
+void import_parse_count_kernel(const uint8_t *__restrict__ t, u64 n, u32 k, ImportState *__restrict__ state, PAgg *__restrict__ tiles) {
+  __shared__ PAgg s[PR_BLOCK];
+  const bool aligned = (reinterpret_cast<uintptr_t>(t) & 15u) == 0;
+  const u64 p0 = (u64)blockIdx.x * PR_TILE + (u64)threadIdx.x * PR_BYTES;
+  u32 starts = pr_line_starts(t, n, p0, aligned);
+  PAgg agg = PAgg::identity();
+  u64 bad = ~0ull;
+  while (starts) {
+    const u32 q = (u32)__builtin_ctz(starts);
+    starts &= starts - 1;
+    const Line L = parse_line<KT>(t, n, p0 + q, k, MGC_MODE_FORWARD, false);
+    agg.lines++;
+    if (L.kind == LN_RECORD) agg.rec++;
+    else if (L.kind == LN_HASH) { agg.has = 1; agg.val = L.value; }
+    else if (L.kind == LN_BAD && bad == ~0ull) bad = ((p0 + q) << 3) | (u64)L.bad;
+  }
+  if (bad != ~0ull) atomicMin(reinterpret_cast<unsigned long long *>(&state->chunk_bad), (unsigned long long)bad);   // refused input only
+  PAgg tot;
+  (void)block_scan_excl<PR_BLOCK, PAgg>(agg, s, &tot);
+  if (threadIdx.x == 0) tiles[blockIdx.x] = tot;
+}
+
+// after the composing step: the chunk's totals into the state; a refused line's byte offset -> its line number
+__global__ __launch_bounds__(PR_BLOCK)
+void import_parse_total_kernel(const uint8_t *__restrict__ t, u64 n, ImportState *__restrict__ state, const PAgg *__restrict__ tiles,
+                               const PAgg *__restrict__ total) {
+  __shared__ u32 s_cnt;
+  if (threadIdx.x == 0) s_cnt = 0;
+  __syncthreads();
+  const u64 bad = state->chunk_bad;
+  if (bad != ~0ull) {
+    const u64 pos = bad >> 3, tile0 = (pos / PR_TILE) * PR_TILE;
+    u32 c = 0;
+    for (u64 q = tile0 + threadIdx.x; q < pos && q < n; q += PR_BLOCK) c += (q == 0 || t[q - 1] == '\n') ? 1u : 0u;
+    if (c) atomicAdd(&s_cnt, c);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    state->chunk_lines = total->lines;
+    state->chunk_records = total->rec;
+    state->chunk_has = total->has;
+    state->chunk_val = total->val;
+    if (bad != ~0ull && state->first_bad == ~0ull) {
+      const u64 line = state->lines_seen + (u64)tiles[(bad >> 3) / PR_TILE].lines + (u64)s_cnt + 1ull;
+      state->first_bad = (line << 3) | (bad & 7ull);
+    }
+  }
+}
+
+// Pass 2: the records of the chunk in input order.
+template <typename KT>
+__global__ __launch_bounds__(PR_BLOCK)
+void import_parse_emit_kernel(const uint8_t *__restrict__ t, u64 n, u32 k, int mode, const ImportState *__restrict__ state,
+                              const PAgg *__restrict__ tiles, u64 n_records, void *__restrict__ keys, u32 *__restrict__ vals) {
+  __shared__ PAgg s[PR_BLOCK];
+  const bool aligned = (reinterpret_cast<uintptr_t>(t) & 15u) == 0;
+  const u64 p0 = (u64)blockIdx.x * PR_TILE + (u64)threadIdx.x * PR_BYTES;
+  const u32 starts0 = pr_line_starts(t, n, p0, aligned);
+  // what this thread's lines are: only a `#` line is read beyond its first byte
+  PAgg agg = PAgg::identity();
+  u32 recs = 0;                                                           // bit q: the line at p0 + q is a record
+  for (u32 starts = starts0; starts;) {
+    const u32 q = (u32)__builtin_ctz(starts);
+    starts &= starts - 1;
+    u64 j = pr_first_word(t, n, p0 + q);
+    if (j >= n) continue;
+    if (t[j] == '#') { j++; u32 v = 0; if (pr_number(t, n, j, &v)) { agg.has = 1; agg.val = v; } }
+    else { agg.rec++; recs |= 1u << q; }
+  }
+  PAgg tot;
+  const PAgg before = PAgg::combine(tiles[blockIdx.x], block_scan_excl<PR_BLOCK, PAgg>(agg, s, &tot));
+  u64 slot = (u64)before.rec;
+  u32 persistent = before.has ? before.val : state->persistent;
+  for (u32 starts = starts0; starts;) {
+    const u32 q = (u32)__builtin_ctz(starts);
+    starts &= starts - 1;
+    if (recs & (1u << q)) {
+      const Line L = parse_line<KT>(t, n, p0 + q, k, mode, true);
+      if (slot < n_records) {                                             // (always, for text the count pass accepted)
+        if (sizeof(KT) > 8) { K128 kk; kk.lo = L.lo; kk.hi = L.hi; reinterpret_cast<K128 *>(keys)[slot] = kk; }
+        else reinterpret_cast<u64 *>(keys)[slot] = L.lo;
+        vals[slot] = L.has_value ? L.value : persistent;
+      }
+      slot++;
+    } else {
+      u64 j = pr_first_word(t, n, p0 + q);
+      if (j < n && t[j] == '#') { j++; u32 v = 0; if (pr_number(t, n, j, &v)) persistent = v; }
+    }
+  }
+}
+
+__global__ void import_begin_kernel(ImportState *state) {
+  state->lines_seen = 0; state->records_seen = 0; state->first_bad = ~0ull; state->persistent = 1; state->pad0 = 0;
+  state->chunk_lines = 0; state->chunk_records = 0; state->chunk_has = 0; state->chunk_val = 0; state->chunk_bad = ~0ull;
+}
+__global__ void import_chunk_reset_kernel(ImportState *state) {
+  state->chunk_lines = 0; state->chunk_records = 0; state->chunk_has = 0; state->chunk_val = 0; state->chunk_bad = ~0ull;
+}
+__global__ void import_commit_kernel(ImportState *state) {
+  state->lines_seen += state->chunk_lines;
+  state->records_seen += state->chunk_records;
+  if (state->chunk_has) state->persistent = state->chunk_val;
+  state->chunk_lines = 0; state->chunk_records = 0; state->chunk_has = 0; state->chunk_val = 0; state->chunk_bad = ~0ull;
+}
+
+static inline uint64_t parse_tiles(uint64_t n) { return (n + PR_TILE - 1) / PR_TILE; }
+// workspace: [0, 64): the total; then one PAgg per tile
+size_t import_parse_workspace_bytes(uint64_t n_text) { return 64 + sizeof(PAgg) * (size_t)(parse_tiles(n_text) + 1); }
+
+hipError_t launch_import_begin(ImportState *d_state, hipStream_t st) {
+  hipLaunchKernelGGL(import_begin_kernel, dim3(1), dim3(1), 0, st, d_state);
+  return hipGetLastError();
+}
+
+hipError_t launch_import_parse_count(const uint8_t *d_text, uint64_t n, uint32_t k, ImportState *d_state, void *d_ws, hipStream_t st) {
+  hipLaunchKernelGGL(import_chunk_reset_kernel, dim3(1), dim3(1), 0, st, d_state);
+  MGC_CHECK(hipGetLastError());
+  const uint64_t T = parse_tiles(n);
+  if (T == 0) return hipSuccess;
+  PAgg *total = reinterpret_cast<PAgg *>(d_ws);
+  PAgg *tiles = reinterpret_cast<PAgg *>(reinterpret_cast<unsigned char *>(d_ws) + 64);
+  if (k > 32) hipLaunchKernelGGL(import_parse_count_kernel<u128>, dim3((uint32_t)T), dim3(PR_BLOCK), 0, st, d_text, (u64)n, k, d_state, tiles);
+  else        hipLaunchKernelGGL(import_parse_count_kernel<u64>, dim3((uint32_t)T), dim3(PR_BLOCK), 0, st, d_text, (u64)n, k, d_state, tiles);
+  MGC_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(compose_tiles_kernel<PAgg>, dim3(1), dim3(CP_BLOCK), 0, st, tiles, (u64)T, total);
+  MGC_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(import_parse_total_kernel, dim3(1), dim3(PR_BLOCK), 0, st, d_text, (u64)n, d_state, (const PAgg *)tiles, (const PAgg *)total);
+  return hipGetLastError();
+}
+
+hipError_t launch_import_parse_emit(const uint8_t *d_text, uint64_t n, uint32_t k, int mode, ImportState *d_state, void *d_ws,
+                                    void *d_keys, uint32_t *d_values, hipStream_t st) {
+  const uint64_t T = parse_tiles(n);
+  if (T) {
+    const PAgg *tiles = reinterpret_cast<const PAgg *>(reinterpret_cast<const unsigned char *>(d_ws) + 64);
+    // the number of records the count pass found bounds every store (the host allocated that many)
+    uint64_t n_records = 0;
+    MGC_CHECK(hipMemcpyAsync(&n_records, &d_state->chunk_records, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    MGC_CHECK(hipStreamSynchronize(st));
+    if (n_records) {
+      if (k > 32) hipLaunchKernelGGL(import_parse_emit_kernel<u128>, dim3((uint32_t)T), dim3(PR_BLOCK), 0, st, d_text, (u64)n, k, mode,
+                                     (const ImportState *)d_state, tiles, (u64)n_records, d_keys, d_values);
+      else        hipLaunchKernelGGL(import_parse_emit_kernel<u64>, dim3((uint32_t)T), dim3(PR_BLOCK), 0, st, d_text, (u64)n, k, mode,
+                                     (const ImportState *)d_state, tiles, (u64)n_records, d_keys, d_values);
+      MGC_CHECK(hipGetLastError());
+    }
+  }
+  hipLaunchKernelGGL(import_commit_kernel, dim3(1), dim3(1), 0, st, d_state);
+  return hipGetLastError();
+}
+
+// ============================================================================
+//  Pair sort: stable, low digit first, 8 bits per pass.
+//  Per pass: digit counts per (digit, tile) -> exclusive scan over the whole table -> scatter, every pair ranked inside its
+//  tile by 64-lane ballots (per-wave counters in LDS, no atomics on them: a wave's leaders hold distinct digits).
+//  Traffic per pass: keys read twice, values once, both written once: 2 x (8|16) + 4 + (8|16) + 4 bytes per pair.
+// ============================================================================
+constexpr int SP_BLOCK = 256;
+constexpr int SP_WAVES = SP_BLOCK / 64;
+constexpr int SP_BITS  = 8;
+constexpr int SP_BINS  = 1 << SP_BITS;
+template <typename K> struct SpItems;
+template <> struct SpItems<u64>  { static constexpr int N = 16; };
+template <> struct SpItems<K128> { static constexpr int N = 8; };
+
+template <typename K>
+__global__ __launch_bounds__(SP_BLOCK)
+void pair_hist_kernel(const K *__restrict__ keys, u64 n, u32 shift, u32 mask, u64 *__restrict__ table, u32 nblk) {
+  constexpr int ITEMS = SpItems<K>::N;
+  __shared__ u32 s_h[SP_BINS];
+  s_h[threadIdx.x] = 0;
+  __syncthreads();
+  const u64 tile0 = (u64)blockIdx.x * (SP_BLOCK * ITEMS);
+#pragma unroll
+  for (int it = 0; it < ITEMS; it++) {
+    const u64 pos = tile0 + (u64)it * SP_BLOCK + threadIdx.x;
+    if (pos < n) atomicAdd(&s_h[KeyOps<K>::digit(keys[pos], shift, mask)], 1u);
+  }
+  __syncthreads();
+  table[(u64)threadIdx.x * nblk + blockIdx.x] = s_h[threadIdx.x];
+}
+
+template <typename K>
+__global__ __launch_bounds__(SP_BLOCK)
+void pair_scatter_kernel(const K *__restrict__ kin, const u32 *__restrict__ vin, K *__restrict__ kout, u32 *__restrict__ vout, u64 n,
+                         u32 shift, u32 mask, const u64 *__restrict__ table /*scanned*/, u32 nblk) {
+  constexpr int ITEMS = SpItems<K>::N;
+  __shared__ u32 s_cnt[SP_WAVES][SP_BINS];
+  __shared__ u64 s_base[SP_BINS];
+  const u32 lane = lane_id(), w = wave_id();
+#pragma unroll
+  for (int i = 0; i < SP_WAVES; i++) s_cnt[i][threadIdx.x] = 0;
+  __syncthreads();
+  const u64 wave0 = (u64)blockIdx.x * (SP_BLOCK * ITEMS) + (u64)w * (64 * ITEMS);
+  const u64 lt = (1ull << lane) - 1ull;
+  K   key[ITEMS];
+  u32 val[ITEMS], dig[ITEMS], rk[ITEMS];
+#pragma unroll
+  for (int it = 0; it < ITEMS; it++) {
+    const u64 pos = wave0 + (u64)it * 64 + lane;
+    const bool valid = pos < n;
+    key[it] = KeyOps<K>::zero(); val[it] = 0;
+    if (valid) { key[it] = kin[pos]; val[it] = vin[pos]; }
+    const u32 d = valid ? KeyOps<K>::digit(key[it], shift, mask) : 0u;
+    u64 peers = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < SP_BITS; b++) {
+      const bool bit = (d >> b) & 1u;
+      const u64 bal = __ballot(bit);
+      peers &= bit ? bal : ~bal;
+    }
+    const u32 leader = peers ? (u32)__builtin_ctzll(peers) : 0u;
+    u32 pre = 0;
+    if (valid && lane == leader) { pre = s_cnt[w][d]; s_cnt[w][d] = pre + (u32)__popcll(peers); }
+    __builtin_amdgcn_wave_barrier();
+    pre = __shfl(pre, (int)leader);
+    dig[it] = d;
+    rk[it] = pre + (u32)__popcll(peers & lt);
+  }
+  __syncthreads();
+  {
+    const u32 d = threadIdx.x;
+    u32 run = 0;
+#pragma unroll
+    for (int i = 0; i < SP_WAVES; i++) { const u32 c = s_cnt[i][d]; s_cnt[i][d] = run; run += c; }
+    s_base[d] = table[(u64)d * nblk + blockIdx.x];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < ITEMS; it++) {
+    const u64 pos = wave0 + (u64)it * 64 + lane;
+    if (pos < n) {
+      const u64 dst = s_base[dig[it]] + (u64)s_cnt[w][dig[it]] + (u64)rk[it];
+      if (dst < n) { kout[dst] = key[it]; vout[dst] = val[it]; }         // (always: the table counts exactly these pairs)
+    }
+  }
+}
+
+static inline uint64_t sp_tiles(uint64_t n, uint32_t key_words) {
+  const uint64_t tile = (uint64_t)SP_BLOCK * (key_words == 2 ? SpItems<K128>::N : SpItems<u64>::N);
+  return (n + tile - 1) / tile;
+}
+size_t sort_pairs_workspace_bytes(uint64_t n) {
+  const uint64_t e = (uint64_t)SP_BINS * sp_tiles(n, 2);                 // (the smaller tile: enough for either key width)
+  return (size_t)(e + scan_scratch_elems(e) + 8) * sizeof(u64);
+}
+
+template <typename K>
+static hipError_t sort_pairs_t(K *keys, u32 *vals, K *akeys, u32 *avals, uint64_t n, uint32_t begin_bit, uint32_t end_bit, void *d_ws,
+                               int *result_in_alt, hipStream_t st) {
+  const uint32_t nblk = (uint32_t)sp_tiles(n, KeyOps<K>::WORDS);
+  const uint64_t e = (uint64_t)SP_BINS * nblk;
+  u64 *table = reinterpret_cast<u64 *>(d_ws), *scratch = table + e;
+  int in_alt = 0;
+  for (uint32_t shift = begin_bit; shift < end_bit; shift += SP_BITS) {
+    const uint32_t bits = end_bit - shift < (uint32_t)SP_BITS ? end_bit - shift : (uint32_t)SP_BITS;
+    const uint32_t mask = (1u << bits) - 1u;
+    K *src = in_alt ? akeys : keys, *dst = in_alt ? keys : akeys;
+    u32 *vsrc = in_alt ? avals : vals, *vdst = in_alt ? vals : avals;
+    hipLaunchKernelGGL(pair_hist_kernel<K>, dim3(nblk), dim3(SP_BLOCK), 0, st, (const K *)src, (u64)n, shift, mask, table, nblk);
+    MGC_CHECK(hipGetLastError());
+    MGC_CHECK(scan_u64_exclusive(table, e, scratch, nullptr, st));
+    hipLaunchKernelGGL(pair_scatter_kernel<K>, dim3(nblk), dim3(SP_BLOCK), 0, st, (const K *)src, (const u32 *)vsrc, dst, vdst, (u64)n,
+                       shift, mask, (const u64 *)table, nblk);
+    MGC_CHECK(hipGetLastError());
+    in_alt ^= 1;
+  }
+  *result_in_alt = in_alt;
+  return hipSuccess;
+}
+
+hipError_t launch_sort_pairs(void *d_keys, uint32_t *d_vals, void *d_alt_keys, uint32_t *d_alt_vals, uint64_t n, uint32_t key_words,
+                             uint32_t begin_bit, uint32_t end_bit, void *d_ws, int *result_in_alt, hipStream_t st) {
+  *result_in_alt = 0;
+  if (n == 0 || begin_bit >= end_bit) return hipSuccess;
+  if (n > (1ull << 40)) return hipErrorInvalidValue;                     // (the tile count is a 32-bit grid dimension)
+  if (key_words == 2)
+    return sort_pairs_t<K128>(reinterpret_cast<K128 *>(d_keys), d_vals, reinterpret_cast<K128 *>(d_alt_keys), d_alt_vals, n, begin_bit,
+                              end_bit, d_ws, result_in_alt, st);
+  return sort_pairs_t<u64>(reinterpret_cast<u64 *>(d_keys), d_vals, reinterpret_cast<u64 *>(d_alt_keys), d_alt_vals, n, begin_bit, end_bit,
+                           d_ws, result_in_alt, st);
+}
+
+// ============================================================================
+//  Reduce by key over sorted pairs
+// ============================================================================
+constexpr int RD_BLOCK = 256;
+constexpr int RD_ITEMS = 8;
+constexpr int RD_TILE  = RD_BLOCK * RD_ITEMS;
+
+// segment heads of a range, and the (wrapped) sum of the values from its last head to its end -- of ALL its values when it
+// holds no head: the part of a segment that is still open where the range ends
+struct RAgg {
+  u64 heads; u32 has, sum;
+  static __device__ __forceinline__ RAgg identity() { RAgg a; a.heads = 0; a.has = 0; a.sum = 0; return a; }
+  static __device__ __forceinline__ RAgg combine(RAgg a, RAgg b) {
+    RAgg r; r.heads = a.heads + b.heads; r.has = a.has | b.has; r.sum = b.has ? b.sum : a.sum + b.sum; return r;
+  }
+};
+
+template <typename K, bool EMIT>
+__global__ __launch_bounds__(RD_BLOCK)
+void reduce_pairs_kernel(const K *__restrict__ keys, const u32 *__restrict__ vals, u64 n, RAgg *__restrict__ tiles /*EMIT: scanned*/,
+                         u64 n_out, K *__restrict__ out_keys, u32 *__restrict__ out_vals) {
+  __shared__ RAgg s[RD_BLOCK];
+  const u64 i0 = (u64)blockIdx.x * RD_TILE + (u64)threadIdx.x * RD_ITEMS;
+  K   kreg[RD_ITEMS];
+  u32 vreg[RD_ITEMS];
+  u32 head = 0;                                          // bit q: element i0 + q starts a segment
+  K prev = KeyOps<K>::zero();
+  if (i0 > 0 && i0 < n) prev = keys[i0 - 1];
+  RAgg agg = RAgg::identity();
+#pragma unroll
+  for (int q = 0; q < RD_ITEMS; q++) {
+    const u64 i = i0 + q;
+    kreg[q] = KeyOps<K>::zero(); vreg[q] = 0;
+    if (i < n) {
+      kreg[q] = keys[i]; vreg[q] = vals[i];
+      const bool h = (i == 0) || KeyOps<K>::ne(prev, kreg[q]);
+      if (h) { head |= 1u << q; agg.heads++; agg.has = 1; agg.sum = 0; }
+      agg.sum += vreg[q];
+      prev = kreg[q];
+    }
+  }
+  RAgg tot;
+  const RAgg excl = block_scan_excl<RD_BLOCK, RAgg>(agg, s, &tot);
+  if (!EMIT) {
+    if (threadIdx.x == 0) tiles[blockIdx.x] = tot;
+    return;
+  }
+  const RAgg before = RAgg::combine(tiles[blockIdx.x], excl);
+  u64 hc = before.heads;
+  u32 run = before.sum;
+  K next = KeyOps<K>::zero();
+  if (i0 + RD_ITEMS < n) next = keys[i0 + RD_ITEMS];
+#pragma unroll
+  for (int q = 0; q < RD_ITEMS; q++) {
+    const u64 i = i0 + q;
+    if (i < n) {
+      if (head & (1u << q)) { hc++; run = 0; }
+      run += vreg[q];
+      const K nx = (q + 1 < RD_ITEMS) ? kreg[(q + 1 < RD_ITEMS) ? q + 1 : q] : next;
+      const bool last = (i + 1 == n) || KeyOps<K>::ne(kreg[q], nx);      // the segment ends here: its sum is complete
+      if (last && hc >= 1 && hc - 1 < n_out) { out_keys[hc - 1] = kreg[q]; out_vals[hc - 1] = run; }
+    }
+  }
+}
+
+__global__ void reduce_total_kernel(const RAgg *total, u64 *out) { *out = total->heads; }
+
+static inline uint64_t rd_tiles(uint64_t n) { return (n + RD_TILE - 1) / RD_TILE; }
+// workspace: [0] distinct keys (u64), [64, 128): the composed total, then one RAgg per tile
+size_t reduce_pairs_workspace_bytes(uint64_t n) { return 128 + sizeof(RAgg) * (size_t)(rd_tiles(n) + 1); }
+
+hipError_t launch_reduce_pairs_count(const void *d_keys, const uint32_t *d_vals, uint64_t n, uint32_t key_words, void *d_ws, hipStream_t st) {
+  const uint64_t T = rd_tiles(n);
+  if (T == 0) return hipMemsetAsync(d_ws, 0, 8, st);
+  if (T > 0xFFFFFFFFull) return hipErrorInvalidValue;
+  RAgg *total = reinterpret_cast<RAgg *>(reinterpret_cast<unsigned char *>(d_ws) + 64);
+  RAgg *tiles = reinterpret_cast<RAgg *>(reinterpret_cast<unsigned char *>(d_ws) + 128);
+  if (key_words == 2)
+    hipLaunchKernelGGL((reduce_pairs_kernel<K128, false>), dim3((uint32_t)T), dim3(RD_BLOCK), 0, st, reinterpret_cast<const K128 *>(d_keys),
+                       d_vals, (u64)n, tiles, (u64)0, (K128 *)nullptr, (u32 *)nullptr);
+  else
+    hipLaunchKernelGGL((reduce_pairs_kernel<u64, false>), dim3((uint32_t)T), dim3(RD_BLOCK), 0, st, reinterpret_cast<const u64 *>(d_keys),
+                       d_vals, (u64)n, tiles, (u64)0, (u64 *)nullptr, (u32 *)nullptr);
+  MGC_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(compose_tiles_kernel<RAgg>, dim3(1), dim3(CP_BLOCK), 0, st, tiles, (u64)T, total);
+  MGC_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(reduce_total_kernel, dim3(1), dim3(1), 0, st, (const RAgg *)total, reinterpret_cast<u64 *>(d_ws));
+  return hipGetLastError();
+}
+
+hipError_t launch_reduce_pairs_emit(const void *d_keys, const uint32_t *d_vals, uint64_t n, uint32_t key_words, void *d_ws,
+                                    void *d_out_keys, uint32_t *d_out_vals, hipStream_t st) {
+  const uint64_t T = rd_tiles(n);
+  if (T == 0) return hipSuccess;
+  if (T > 0xFFFFFFFFull) return hipErrorInvalidValue;
+  // the count pass's total bounds every store (the caller allocated that many)
+  uint64_t n_out = 0;
+  MGC_CHECK(hipMemcpyAsync(&n_out, d_ws, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  MGC_CHECK(hipStreamSynchronize(st));
+  RAgg *tiles = reinterpret_cast<RAgg *>(reinterpret_cast<unsigned char *>(d_ws) + 128);
+  if (key_words == 2)
+    hipLaunchKernelGGL((reduce_pairs_kernel<K128, true>), dim3((uint32_t)T), dim3(RD_BLOCK), 0, st, reinterpret_cast<const K128 *>(d_keys),
+                       d_vals, (u64)n, tiles, (u64)n_out, reinterpret_cast<K128 *>(d_out_keys), d_out_vals);
+  else
+    hipLaunchKernelGGL((reduce_pairs_kernel<u64, true>), dim3((uint32_t)T), dim3(RD_BLOCK), 0, st, reinterpret_cast<const u64 *>(d_keys),
+                       d_vals, (u64)n, tiles, (u64)n_out, reinterpret_cast<u64 *>(d_out_keys), d_out_vals);
+  return hipGetLastError();
+}
+
+}  // namespace mgc
