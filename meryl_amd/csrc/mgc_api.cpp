@@ -34,6 +34,29 @@ std::string &thread_last_error() {
   thread_local std::string e;
   return e;
 }
+
+// Every MGC_* switch of the count path, from the environment (mgc_device.h: once per session / per bare-operator call)
+Switches read_switches() {
+  Switches sw;
+  auto off = [](const char *n) { const char *e = getenv(n); return e && e[0] == '0'; };
+  auto on1 = [](const char *n) { const char *e = getenv(n); return e && e[0] == '1'; };
+  auto num = [](const char *n, uint64_t d) { const char *e = getenv(n); return (e && *e) ? strtoull(e, nullptr, 10) : d; };
+  sw.fine_hist = !off("MGC_FINE_HIST"); sw.hpc_msd = !off("MGC_HPC_MSD"); sw.hpc_digits = !off("MGC_HPC_DIGITS");
+  sw.const_k = !off("MGC_KMER_CONST_K"); sw.narrow = !off("MGC_NARROW"); sw.wide_msd = !off("MGC_WIDE_MSD");
+  sw.group_pipe = !off("MGC_GROUP_PIPE"); sw.soa5 = !off("MGC_SOA5"); sw.k96 = !off("MGC_K96"); sw.finish = !off("MGC_FINISH");
+  sw.nolist = on1("MGC_FINISH_NOLIST");
+  sw.finish_trace = getenv("MGC_FINISH_TRACE") != nullptr; sw.group_dbg = getenv("MGC_GROUP_DBG") != nullptr; sw.hash_dbg = getenv("MGC_HASH_DBG") != nullptr;
+  { const char *e = getenv("MGC_HASH_MULTI"); sw.hash_multi = (e && *e) ? atoi(e) : -1; }
+  { const char *e = getenv("MGC_HASH_STREAM"); sw.hash_stream = (e && *e) ? atoi(e) : -1; }
+  sw.min_top = (uint32_t)num("MGC_FINISH_MIN_TOP", 0);
+  sw.finish_target = num("MGC_FINISH_TARGET", 0);
+  sw.stream_max = num("MGC_STREAM_MAX", (uint64_t)1 << 22);
+  sw.bucket_bases = num("MGC_BUCKET_BASES", 0);
+  sw.huge_streams = (uint32_t)num("MGC_HUGE_STREAMS", 4);
+  sw.huge_slices = !off("MGC_HUGE_SLICES");
+  sw.pass_stagger = (uint32_t)num("MGC_PASS_STAGGER", 0);
+  return sw;
+}
 }  // namespace mgc
 using mgc::set_err;
 

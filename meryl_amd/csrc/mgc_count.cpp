@@ -132,7 +132,7 @@ struct CountPlan {
     // is known here (the dense-rank histogram is at hand, the suffix has 32..52 bits), so the plan is final at once
     hpc_stream_ok = hpc_ok && sw.hash_stream != 0 && sw.hash_stream != 2 && kw == 1 && fine_hpc && nb <= 256 && sw.wide_msd &&
                     rem_bits >= 20 + 32 && mgc::finish_stream_ok(kw, rem_bits - 20, false);
-    hpc_mixed_ok = hpc_stream_ok && rem_bits >= 18 + 32 && mgc::finish_stream_ok(kw, rem_bits - 18, false) && mgc::finish_can_stream(kw, rem_bits - 18);
+    hpc_mixed_ok = hpc_stream_ok && rem_bits >= 18 + 32 && mgc::finish_stream_ok(kw, rem_bits - 18, false) && mgc::finish_uses_hash(kw, rem_bits - 18);
   }
 
   // t top bits so that a sub-bucket holds ~target k-mers; the distinct-sized count's candidate (top_str)
@@ -177,7 +177,7 @@ struct CountPlan {
     // (sub-bucket numbers made of dense ranks are no key bits: the kernels that put a k-mer's top bits back from its sub-bucket
     // number -- 32-bit suffixes -- stay with the low digit first)
     const bool wide = fine_hpc && nb <= 256 && x.top == 20 && (kw == 2 || rem_bits - x.top >= 32) &&
-                      mgc::finish_can_stream(kw, rem_bits - x.top) && mgc::sort_plan_wide_msd(x.sp, x.size, sw.wide_msd);
+                      mgc::finish_uses_hash(kw, rem_bits - x.top) && mgc::sort_plan_wide_msd(x.sp, x.size, sw.wide_msd);
     x.kind = wide ? Group::WIDE : Group::SORT;
     // (above the index-claimed tables' reach: the distinct-sized count whatever the coverage; below: a candidate the probe file decides on)
     if (x.hpc_stream && wide) { x.stream = true; prof.stream_files++; }
@@ -199,9 +199,9 @@ struct CountPlan {
     x.sp = group_plan(rem_bits - x.top);
     fit_split(x);
     const uint32_t low = rem_bits - x.top;
-    if (low < 32 && mgc::finish_can_stream(kw, low) && mgc::sort_plan_narrows(x.sp, x.size, kw, sw.narrow)) x.kind = Group::NARROW;
+    if (low < 32 && mgc::finish_uses_hash(kw, low) && mgc::sort_plan_narrows(x.sp, x.size, kw, sw.narrow)) x.kind = Group::NARROW;
     // (only the hash-count kernels translate the sub-bucket numbers of whole keys)
-    else if (fine && nb <= 256 && x.msd_ok && mgc::finish_can_stream(kw, low) && mgc::sort_plan_wide_msd(x.sp, x.size, sw.wide_msd)) x.kind = Group::WIDE;
+    else if (fine && nb <= 256 && x.msd_ok && mgc::finish_uses_hash(kw, low) && mgc::sort_plan_wide_msd(x.sp, x.size, sw.wide_msd)) x.kind = Group::WIDE;
     else x.kind = Group::SORT;
     if (!x.top_str) return;
     // the coarser plan stays a candidate if the file narrows under BOTH plans, its suffix then has to fit the packed 32-bit entry
@@ -212,7 +212,7 @@ struct CountPlan {
     if (rem_bits - ts > max_low) ts = rem_bits - max_low;
     // (a plan that does not coarsen the file keeps the kernels it has -- unless MGC_HASH_STREAM=1 asks for the new one)
     bool ok = ts >= 1 && ts <= t && ts <= 18 && (ts < t || sw.hash_stream == 1) && (narrow || (x.kind == Group::WIDE && kw == 1 && sw.hash_stream != 2)) &&
-              x.size < (1ull << 32) && mgc::finish_stream_ok(kw, rem_bits - ts, narrow) && mgc::finish_can_stream(kw, rem_bits - ts);
+              x.size < (1ull << 32) && mgc::finish_stream_ok(kw, rem_bits - ts, narrow) && mgc::finish_uses_hash(kw, rem_bits - ts);
     if (ok) {
       const mgc::SortPlan sp = group_plan(rem_bits - ts);
       if (narrow) ok = mgc::sort_plan_narrows(sp, x.size, kw, sw.narrow);
@@ -362,6 +362,7 @@ struct Count {
   bool msd_file(const FilePlan &x) const {
     return d_fine_hpc ? x.kind == Group::WIDE : (x.kind == Group::NARROW || x.kind == Group::WIDE) && x.msd_ok;
   }
+  mgc::FinishFile finish_desc(uint32_t b, bool stream, hipStream_t fst, int hsel) const;
   void take_stats(uint32_t b) {
     const uint64_t *h = s->h_stats + 3 * (size_t)b;
     plan.files[b].maxsub = h[0]; plan.files[b].nlarge = h[1]; plan.files[b].nzcount = h[2];
@@ -752,14 +753,13 @@ int Count::finish_file(uint32_t b) {
 // first (one pass must do), before anything touches the file.
 int Count::oversized_streams(uint32_t b, bool *stream) {
   const FilePlan &x = plan.files[b];
-  *stream = mgc::finish_can_stream(kw, low(x)) && x.nlarge > 0;
+  *stream = mgc::finish_uses_hash(kw, low(x)) && x.nlarge > 0;
   if (*stream && x.maxsub > sw.stream_max && kw == 2) {
     *stream = false;                                     // no probe for 16-byte keys: a sub-bucket that large takes the sort
   } else if (*stream && x.maxsub > sw.stream_max) {
     uint32_t h_fail[3] = {0, 0, 0};                      // [0] answer, [2] most distinct suffixes met (diagnostics)
     HIP_TRY(s, hipMemsetAsync(d_err + 4, 0, 12, st));
-    HIP_TRY(s, mgc::launch_finish_probe(seg(b), kw, d_substart + x.sbase, low(x), x.nlarge, d_large + x.gbase, d_err + 4, st, sw.stream_max,
-                                        x.kind == Group::NARROW));
+    HIP_TRY(s, mgc::launch_finish_probe(finish_desc(b, true, st, 0), sw.stream_max, d_err + 4));
     HIP_TRY(s, hipMemcpyAsync(h_fail, d_err + 4, 12, hipMemcpyDeviceToHost, st));
     HIP_TRY(s, hipStreamSynchronize(st));
     *stream = (h_fail[0] == 0);
@@ -808,6 +808,27 @@ int Count::widen_back(uint32_t b, bool *unordered) {
 // the next files that tail costs nothing.  The persistent kernels of odd files go to the second stream too, so that the tail of one
 // file's launch overlaps the head of the next: finish stage 58.5 -> 54.2 ms per 10 Gbp.  All streaming kernels stay on stream2: they
 // share one second buffer.
+// What the count-stage launchers are told about file b (mgc_device.h, FinishFile).  stream: its oversized list goes through the streaming
+// kernels, on streaming stream hsel with that stream's second buffer and workspace; fst: where its persistent kernels go.
+mgc::FinishFile Count::finish_desc(uint32_t b, bool stream, hipStream_t fst, int hsel) const {
+  const FilePlan &x = plan.files[b];
+  mgc::FinishFile f;
+  f.keys = seg(b); f.alt = halt[hsel];
+  f.layout = x.kind == Group::NARROW ? mgc::FinishKeys::NARROW32 : x.k96 ? mgc::FinishKeys::K96 : kw == 2 ? mgc::FinishKeys::WHOLE16 : mgc::FinishKeys::WHOLE8;
+  f.starts = d_substart + x.sbase; f.ng = x.ngf(); f.low_bits = low(x); f.tr_a = x.tr_a; f.tr_b = x.tr_b;
+  f.n_keys = x.size; f.max_sub = x.maxsub;
+  f.cnt_tmp = x.cnt; f.group_distinct = d_group + x.gbase;
+  f.large_list = d_large + x.gbase; f.n_large = x.nlarge; f.stream = stream;
+  f.nonempty_list = nz_list(x); f.nonempty_count = d_stats + 3 * (size_t)b + 2;
+  // (the distinct-sized count's retry list: behind the file's oversized list -- a sub-bucket is on one of them at most)
+  f.retry_list = x.stream ? d_large + x.gbase + x.nlarge : d_nz + x.gbase; f.retry_count = d_retrycnt + b;
+  f.stream_cap = x.stream ? mgc::finish_stream_capacity() : 0;
+  f.huge_ws = hws[hsel]; f.huge_ws_bytes = hws_bytes; f.huge_ws_keys = plan.max_bucket; f.d_error = d_err;
+  f.st = fst; f.st_huge = hstream[hsel];
+  f.hash_multi = sw.hash_multi; f.hash_dbg = sw.hash_dbg;
+  return f;
+}
+
 int Count::count_file(uint32_t b, bool stream) {
   const FilePlan &x = plan.files[b];
   const bool on_second = fork_huge && (b & 1u);
@@ -826,12 +847,7 @@ int Count::count_file(uint32_t b, bool stream) {
     fin_in_bytes += x.size * (narrow ? 4u : (x.k96 ? 12u : (uint64_t)kbytes));
     fin_narrow = fin_narrow || narrow;
   }
-  HIP_TRY(s, mgc::launch_finish_file(seg(b), kw, d_substart + x.sbase, x.ngf(), low(x), x.nlarge, d_large + x.gbase, x.cnt, d_group + x.gbase,
-                                     stream, (void *)halt[hsel], hstream[hsel], nz_list(x), d_stats + 3 * (size_t)b + 2, fst, narrow,
-                                     x.tr_a, x.tr_b, x.maxsub, x.size,
-                                     // (the distinct-sized count's retry list: behind the file's oversized list -- a sub-bucket is on one of them at most)
-                                     x.stream ? d_large + x.gbase + x.nlarge : d_nz + x.gbase, d_retrycnt + b, x.k96,
-                                     sw.hash_multi, sw.hash_dbg, x.stream ? mgc::finish_stream_capacity() : 0, hws[hsel], hws_bytes, plan.max_bucket, d_err));
+  HIP_TRY(s, mgc::launch_finish_file(finish_desc(b, stream, fst, hsel)));
   if (s->profiling) (void)hipEventRecord(fin_ev.back().second, fst);
   return MGC_OK;
 }
@@ -862,12 +878,9 @@ int Count::trace_slices() {                              // what the LAST sliced
   HIP_TRY(s, hipStreamSynchronize(st));
   for (int i = 0; i < n_huge_streams; i++) {
     if (!hws[i]) continue;
-    std::vector<uint32_t> w(hws_bytes / 4);
-    HIP_TRY(s, hipMemcpy(w.data(), hws[i], hws_bytes / 4 * 4, hipMemcpyDeviceToHost));
-    const uint32_t max_gig = (uint32_t)(plan.max_bucket / 65536 + 2);
-    uint32_t dense = 0;
-    for (uint32_t q = 0; q < w[0] && q < max_gig; q++) dense += w[64 + 2 * (size_t)max_gig + q] ? 1u : 0u;
-    fprintf(stderr, "[finish] sliced count, stream %d: the last file had %u sub-buckets cut into %u slices; %u of them dense (counted by ranges)\n", i, w[0], w[1], dense);
+    mgc::HugeTrace t;
+    HIP_TRY(s, mgc::finish_huge_trace(hws[i], plan.max_bucket, &t));
+    fprintf(stderr, "[finish] sliced count, stream %d: the last file had %u sub-buckets cut into %u slices; %u of them dense (counted by ranges)\n", i, t.cut, t.slices, t.dense);
   }
   return MGC_OK;
 }
@@ -885,9 +898,7 @@ int Count::retry() {
     const FilePlan &x = plan.files[b];
     if (!x.stream || x.fallback || h_retry[b] == 0) continue;
     prof.stream_retries += h_retry[b];
-    HIP_TRY(s, mgc::launch_finish_retry(seg(b), d_substart + x.sbase, x.ngf(), low(x), x.cnt, d_group + x.gbase, x.tr_a, x.tr_b,
-                                        d_large + x.gbase + x.nlarge, d_retrycnt + b, h_retry[b], mgc::finish_stream_capacity(), st,
-                                        x.kind == Group::NARROW, (void *)Y));
+    HIP_TRY(s, mgc::launch_finish_retry(finish_desc(b, true, st, 0), h_retry[b]));
   }
   return MGC_OK;
 }

@@ -1,5 +1,6 @@
-// mgc_device.h -- internal launch interface between the C-ABI layer
-// (mgc_api.cpp) and the gfx950 kernels (mgc_kmer / mgc_sort / mgc_scan / mgc_finish / mgc_misc / mgc_parse .hip).  Not installed.
+// mgc_device.h -- internal launch interface between the host layer (mgc_api / mgc_count / mgc_stream / mgc_runs / mgc_node .cpp)
+// and the gfx950 kernels (mgc_kmer / mgc_sort / mgc_scan / mgc_finish / mgc_misc / mgc_parse / mgc_encode / mgc_decode / mgc_merge
+// .hip; mgc_lookup / mgc_filter / mgc_import .hip have headers of their own).  Not installed.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -41,7 +42,7 @@ struct Switches {
   uint32_t huge_streams = 4;    // MGC_HUGE_STREAMS: streams the streaming kernels of oversized sub-buckets are spread over (1..4)
   uint64_t bucket_bases = 0;    // MGC_BUCKET_BASES: bases per partition bucket above which the partition gets finer (0: default)
 };
-Switches read_switches();
+Switches read_switches();        // (mgc_api.cpp)
 
 
 
@@ -182,36 +183,56 @@ hipError_t launch_subbucket_max(const uint64_t *d_starts, uint32_t key_words, ui
                                 uint32_t *d_large_list, uint64_t *d_large_count, uint32_t *d_nonempty_list, uint64_t *d_nonempty_count,
                                 hipStream_t st, uint64_t small_cap = 0 /*0: the capacity of the kernels (key_words, low) selects*/);
                                 // the list half of launch_subbucket_bounds (boundaries already known)
-// sub-buckets above finish_capacity_for(): can they be streamed through the hash-count tables (distinct suffixes fit)?
-bool       finish_can_stream(uint32_t key_words, uint32_t low_bits);
-hipError_t launch_finish_probe(const void *d_keys, uint32_t key_words, const uint64_t *d_starts, uint32_t low_bits,
-                               uint64_t n_large, const uint32_t *d_large_list, uint32_t *d_file_fail /*set to 1: no*/, hipStream_t st,
-                               uint64_t stream_max /*Switches::stream_max*/, bool narrow = false /*d_keys: uint32 narrowed keys*/);
-hipError_t launch_finish_file(void *d_keys, uint32_t key_words, const uint64_t *d_starts, uint64_t ng, uint32_t low_bits,
-                              uint64_t n_large, const uint32_t *d_large_list, uint32_t *d_cnt_tmp, uint64_t *d_group_distinct,
-                              bool stream /*large list -> streaming hash-count*/, void *d_alt /*room for the file's keys*/,
-                              hipStream_t st_huge /*where that kernel is launched (st, or a stream forked from it)*/,
-                              const uint32_t *d_nonempty_list, const uint64_t *d_nonempty_count /*the hash kernels visit only these;
-                              d_group_distinct must be zero for the others*/, hipStream_t st,
-                              bool narrow = false /*d_keys/d_alt: uint32 narrowed keys; the distinct SUFFIXES go back in place*/,
-                              uint32_t tr_a = 0, uint32_t tr_b = 0 /*launch_group_narrow's / launch_group_wide's (whole keys: hash paths only)*/,
-                              uint64_t max_sub = 0 /*the file's largest sub-bucket, if known: small files take smaller tables*/,
-                              uint64_t n_keys = 0 /*keys of the file, if known: the narrowed hash-count takes several sub-buckets per iteration by their average*/,
-                              uint32_t *d_retry_list = nullptr /*[ng] + a zeroed counter: with both, dense narrowed files take hash_count_multi_kernel*/,
-                              uint64_t *d_retry_count = nullptr,
-                              bool k96 = false /*d_keys: 12-byte K96 records (key_words 2; oversized sub-buckets only with `stream`)*/,
-                              int hash_multi = -1 /*Switches::hash_multi*/, bool hash_dbg = false /*Switches::hash_dbg*/,
-                              uint64_t stream_cap = 0 /*nonzero (narrowed dense files, finish_stream_ok): hash_count_stream_kernel counts the
-                              sub-buckets of up to that many keys; the ones with too many distinct suffixes go on d_retry_list*/,
-                              void *d_huge_ws = nullptr, size_t huge_ws_bytes = 0, uint64_t huge_ws_keys = 0, uint32_t *d_error = nullptr /*(d_error: the count's look-back / chain time-out flag) finish_huge_workspace_bytes(huge_ws_keys >= n_keys), one per stream the streaming
-                              kernels run on: with it (8-byte and narrowed keys) a GIGANTIC sub-bucket -- above 65536 keys -- is counted in slices by
-                              many workgroups instead of one*/);
-size_t     finish_huge_workspace_bytes(uint64_t n_keys);
+// which files the hash-count kernels take (the others: the LDS sort); their sub-buckets above finish_capacity_for() can be streamed
+// through the hash-count tables (the distinct suffixes fit)
+bool       finish_uses_hash(uint32_t key_words, uint32_t low_bits);
+// what a file's keys are when its sub-buckets are counted
+enum class FinishKeys : uint32_t {
+  WHOLE8,                       // whole 8-byte k-mers
+  NARROW32,                     // uint32 narrowed keys (launch_group_narrow); the distinct SUFFIXES go back in place
+  K96,                          // 12-byte K96 records (k = 33..51); oversized sub-buckets only with `stream`
+  WHOLE16,                      // whole 16-byte k-mers
+};
+// One file's count launch: what launch_finish_probe / launch_finish_file / launch_finish_retry share.
+struct FinishFile {
+  void *keys = nullptr;                       // the file's segment; distinct keys are written in place
+  void *alt = nullptr;                        // room for the file's keys (the streaming kernels' second buffer)
+  FinishKeys layout = FinishKeys::WHOLE8;
+  const uint64_t *starts = nullptr;           // [ng + 1] sub-bucket boundaries
+  uint64_t ng = 0;
+  uint32_t low_bits = 0;                      // bits below the sub-bucket (the suffix)
+  uint32_t tr_a = 0, tr_b = 0;                // launch_group_narrow's / launch_group_wide's (whole keys: hash paths only)
+  uint64_t n_keys = 0;                        // keys of the file, if known: the narrowed hash-count takes several sub-buckets per iteration by their average
+  uint64_t max_sub = 0;                       // the file's largest sub-bucket, if known: small files take smaller tables
+  uint32_t *cnt_tmp = nullptr;
+  uint64_t *group_distinct = nullptr;
+  const uint32_t *large_list = nullptr;       // the oversized list: sub-buckets above the small-kernel capacity
+  uint64_t n_large = 0;
+  bool stream = false;                        // large list -> streaming hash-count (otherwise the LDS sort's 8192-key instantiation)
+  const uint32_t *nonempty_list = nullptr;    // the hash kernels visit only these; group_distinct must be zero for the others
+  const uint64_t *nonempty_count = nullptr;
+  uint32_t *retry_list = nullptr;             // [ng] + a zeroed counter: with both, dense narrowed files take hash_count_multi_kernel
+  uint64_t *retry_count = nullptr;
+  uint64_t stream_cap = 0;                    // nonzero (dense files, finish_stream_ok): hash_count_stream_kernel counts the sub-buckets of up
+                                              // to that many keys; the ones with too many distinct suffixes go on retry_list
+  // finish_huge_workspace_bytes(huge_ws_keys >= n_keys), one per stream the streaming kernels run on: with it a GIGANTIC sub-bucket --
+  // above 65536 keys -- is counted in slices by many workgroups instead of one
+  void *huge_ws = nullptr; size_t huge_ws_bytes = 0; uint64_t huge_ws_keys = 0;
+  uint32_t *d_error = nullptr;                // the count's look-back / chain time-out flag
+  hipStream_t st = nullptr;                   // where the persistent kernels are launched
+  hipStream_t st_huge = nullptr;              // where the streaming kernel of the oversized list is launched (st, or a stream forked from it)
+  int  hash_multi = -1;                       // Switches::hash_multi
+  bool hash_dbg = false;                      // Switches::hash_dbg
+};
+// would every listed sub-bucket above stream_max keys fit the streaming tables?  *d_file_fail is set to 1 if not
+hipError_t launch_finish_probe(const FinishFile &f, uint64_t stream_max /*Switches::stream_max*/, uint32_t *d_file_fail);
+hipError_t launch_finish_file(const FinishFile &f);
 // the sub-buckets hash_count_stream_kernel put on the retry list (their number is on the device: the caller brings it back first)
-hipError_t launch_finish_retry(void *d_keys32, const uint64_t *d_starts, uint64_t ng, uint32_t low_bits, uint32_t *d_cnt_tmp,
-                               uint64_t *d_group_distinct, uint32_t tr_a, uint32_t tr_b, const uint32_t *d_retry_list,
-                               const uint64_t *d_retry_count, uint64_t n_retry, uint64_t stream_cap, hipStream_t st,
-                               bool narrow = true /*false: d_keys32 holds whole 8-byte k-mers*/, void *d_alt = nullptr /*whole k-mers: room for the file's keys*/);
+hipError_t launch_finish_retry(const FinishFile &f, uint64_t n_retry);
+size_t     finish_huge_workspace_bytes(uint64_t n_keys);
+// what the last sliced count left in a workspace (diagnostics): sub-buckets cut, their slices, the cut ones counted by ranges
+struct HugeTrace { uint32_t cut, slices, dense; };
+hipError_t finish_huge_trace(const void *d_ws, uint64_t ws_keys, HugeTrace *out);
 size_t     finish_scan_scratch_bytes(uint64_t ng_total);
 hipError_t launch_finish_scan(uint64_t *d_group /*[ng_total+1]*/, uint64_t ng_total, void *d_scratch, hipStream_t st);
 hipError_t launch_compact_groups(const void *d_keys, uint32_t key_words, const uint32_t *d_cnt_tmp, const uint64_t *d_starts,

@@ -21,6 +21,10 @@
 // the datum is the flag).  Wave = 64 everywhere.
 #include "mgc_common.hpp"
 
+#include <algorithm>
+#include <type_traits>
+#include <vector>
+
 namespace mgc {
 
 // ============================================================================
@@ -2428,6 +2432,12 @@ constexpr u64 FIN_CAP_SMALL = 256 * 16, FIN_CAP_LARGE = 1024 * 8;   // LDS: 46 K
 // longest chain among 64 lanes made an insert round 4x as long (scripts/gpu_huge.sh)
 constexpr int HUGE_CAP32 = 4096, HUGE_SLOTS32 = 8192;            // 32-bit suffixes: 96 KiB of LDS
 constexpr int HUGE_CAP64 = 2048, HUGE_SLOTS64 = 4096;            // 64-bit suffixes: 72 KiB
+constexpr int HUGE_CAP128 = 2048, HUGE_SLOTS128 = 4096;          // 16-byte keys / K96 records: 72 KiB (suffixes up to 64 bits), 120 KiB (wider)
+// ... their dynamic LDS (hash_count_huge_body / hash_count128_huge_body carve it up)
+constexpr size_t HUGE_LDS32 = (size_t)(4 + 4) * HUGE_SLOTS32 + (size_t)(4 + 4) * HUGE_CAP32 + 16 * 4;
+constexpr size_t HUGE_LDS64 = (size_t)(8 + 4) * HUGE_SLOTS64 + (size_t)(8 + 4) * HUGE_CAP64 + 16 * 8;
+constexpr size_t HUGE_LDS128 = (size_t)(8 + 4) * HUGE_SLOTS128 + (size_t)8 * (HUGE_CAP128 + 16) + (size_t)4 * HUGE_CAP128;
+constexpr size_t HUGE_LDS128_WIDE = (size_t)(8 + 8 + 4) * HUGE_SLOTS128 + (size_t)(8 + 8) * (HUGE_CAP128 + 16) + (size_t)4 * HUGE_CAP128;
 constexpr u64 FIN_CAP_HASH  = 1536;                               // hash-count kernel: 2048 slots, 26 KiB of LDS, 6 workgroups per CU
 // hash_count_stream_kernel: sub-buckets of up to 4094 keys (a 12-bit count, all ones excluded) in chunks of <= 1536; 2048-entry table
 // and room for 1280 distinct suffixes (17.6 KiB of LDS, eight workgroups per CU); the retry instantiation: 8192 entries, 58 KiB
@@ -2441,8 +2451,9 @@ constexpr int FIN_STREAM64_DCAP = 1024;
 constexpr u64 FIN_CAP_HASH128 = 1536;
 
 // which files the hash-count kernels take: 8-byte keys with suffixes of up to 58 bits (the packed 32-bit table below 32, the
-// index-claimed table of hash_countw_kernel above), 16-byte keys with suffixes of up to 122 bits
-static bool finish_uses_hash(uint32_t key_words, uint32_t low_bits) {
+// index-claimed table of hash_countw_kernel above), 16-byte keys with suffixes of up to 122 bits.  Their sub-buckets above
+// finish_capacity_for() can be streamed through the hash-count tables (the distinct suffixes fit)
+bool finish_uses_hash(uint32_t key_words, uint32_t low_bits) {
   if (key_words == 2) return low_bits <= 122;
   return key_words == 1 && low_bits <= 58;
 }
@@ -2477,11 +2488,25 @@ hipError_t launch_subbucket_max(const uint64_t *d_starts, uint32_t key_words, ui
   return hipGetLastError();
 }
 
+// ---- what the count-stage launchers below share ----
+static uint32_t finish_key_words(FinishKeys layout) { return (layout == FinishKeys::K96 || layout == FinishKeys::WHOLE16) ? 2u : 1u; }
+static const u64 *fin_starts(const FinishFile &f) { return reinterpret_cast<const u64 *>(f.starts); }
+static u64 *fin_distinct(const FinishFile &f) { return reinterpret_cast<u64 *>(f.group_distinct); }
+static uint32_t fin_grid(uint64_t items, uint32_t max_wgs) { return items < max_wgs ? (uint32_t)items : max_wgs; }
+
+// run-time booleans as template arguments: with_bools(fn, a, b) calls fn(std::bool_constant<a>(), std::bool_constant<b>()).  EVERY
+// combination is instantiated: a kernel family that exists for a part of them only takes explicit template arguments instead.
+template <typename F> static hipError_t with_bools(F &&fn) { return fn(); }
+template <typename F, typename... B> static hipError_t with_bools(F &&fn, bool b, B... rest) {
+  return b ? with_bools([&](auto... c) { return fn(std::true_type(), c...); }, rest...)
+           : with_bools([&](auto... c) { return fn(std::false_type(), c...); }, rest...);
+}
+
+// the LDS sort + fused count of `n` workgroups' sub-buckets: every sub-bucket of the grid (list == nullptr) or the listed ones, those
+// of (min_size, max_size] keys
 template <typename K, int BLOCK, int KPT>
-static hipError_t finish_launch(void *d_keys, const uint64_t *d_starts, uint64_t ng, uint32_t low_bits, uint64_t min_size,
-                                uint64_t max_size, uint32_t *d_cnt_tmp, uint64_t *d_group_distinct, hipStream_t st,
-                                const uint32_t *d_list = nullptr) {
-  if (ng == 0) return hipSuccess;
+static hipError_t launch_lds_sort(const FinishFile &f, uint64_t n, uint64_t min_size, uint64_t max_size, const uint32_t *list = nullptr) {
+  if (n == 0) return hipSuccess;
   using SM = FinishSmem<K, BLOCK, KPT>;
   static bool attr_done = false;
   if (!attr_done) {
@@ -2489,14 +2514,11 @@ static hipError_t finish_launch(void *d_keys, const uint64_t *d_starts, uint64_t
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)SM::BYTES);
     attr_done = true;
   }
-  hipLaunchKernelGGL((lds_sort_count_kernel<K, BLOCK, KPT>), dim3((uint32_t)ng), dim3(BLOCK), SM::BYTES, st,
-                     reinterpret_cast<K *>(d_keys), reinterpret_cast<const u64 *>(d_starts), low_bits, (u64)min_size,
-                     (u64)max_size, d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), d_list);
+  hipLaunchKernelGGL((lds_sort_count_kernel<K, BLOCK, KPT>), dim3((uint32_t)n), dim3(BLOCK), SM::BYTES, f.st,
+                     reinterpret_cast<K *>(f.keys), fin_starts(f), f.low_bits, (u64)min_size, (u64)max_size, f.cnt_tmp, fin_distinct(f), list);
   return hipGetLastError();
 }
 
-// Sorts + counts every sub-bucket of one file segment; sub-buckets larger than FIN_CAP_SMALL use the
-// large-capacity instantiation (launched only if the file has any: max_sub tells).
 // MGC_HASH_DBG=1: per-phase cycle sums of the first 64 workgroups of the hash-count kernel, printed for a few launches
 static u64 *hash_dbg_buffer(bool on) {
   static u64 *buf = nullptr;
@@ -2523,11 +2545,95 @@ static void hash_dbg_report(hipStream_t st, uint64_t ng, bool multi = false) {
   reports++;
 }
 
+// ---- the persistent count kernels: one launcher per family (the template arguments a family exists for are the ones spelled out
+// or dispatched here -- nothing else is instantiated) ----
+
+// hash_countw_kernel (index-claimed tables: K96 records, whole 16-byte keys, whole 8-byte keys with suffixes of 32 bits and more).
+// small: a file whose LARGEST sub-bucket holds at most 768 k-mers (`compress`: 59049 sub-buckets per bucket, a few hundred k-mers each)
+// takes three keys per thread instead of six -- fewer idle unrolled slots, half the LDS, more workgroups per CU
+template <typename KT, bool WIDE>
+static hipError_t launch_countw(const FinishFile &f, bool small) {
+  const uint32_t grid = fin_grid(f.ng, 256u * (small ? 12u : (sizeof(KT) == 8 ? 10u : 8u)));
+  return with_bools([&](auto SMALL, auto LIST) {
+    constexpr int CAP = decltype(SMALL)::value ? 768 : (int)FIN_CAP_HASH128, SLOTS = decltype(SMALL)::value ? 1024 : 2048;
+    hipLaunchKernelGGL((hash_countw_kernel<KT, 256, CAP, SLOTS, WIDE, decltype(LIST)::value>), dim3(grid), dim3(256), 0, f.st,
+                       reinterpret_cast<KT *>(f.keys), fin_starts(f), (u64)f.ng, (u64)CAP, f.low_bits, f.cnt_tmp, fin_distinct(f),
+                       f.nonempty_list, reinterpret_cast<const u64 *>(f.nonempty_count), f.tr_a, f.tr_b);
+    return hipGetLastError();
+  }, small, f.nonempty_list != nullptr);
+}
+static_assert(FIN_CAP_HASH128 == FIN_CAP_HASH, "launch_countw: 8-byte and 16-byte keys share the 1536-key instantiation's capacity");
+
+// hash_count_kernel (packed 32-bit table: suffixes below 32 bits; NARROW: u32 narrowed keys): the sub-buckets of `list` (nullptr: the
+// whole grid).  dbg: the instrumented instantiation (MGC_HASH_DBG) and its report
+template <bool NARROW>
+static hipError_t launch_hash_count(const FinishFile &f, uint32_t max_wgs, const uint32_t *list, const uint64_t *list_count, u64 *dbg) {
+  MGC_CHECK(with_bools([&](auto DBG, auto LIST) {
+    hipLaunchKernelGGL((hash_count_kernel<256, (int)FIN_CAP_HASH, 2048, decltype(DBG)::value, decltype(LIST)::value, NARROW>),
+                       dim3(fin_grid(f.ng, max_wgs)), dim3(256), 0, f.st, reinterpret_cast<u64 *>(f.keys), fin_starts(f), (u64)f.ng,
+                       (u64)FIN_CAP_HASH, f.low_bits, f.cnt_tmp, fin_distinct(f), list, reinterpret_cast<const u64 *>(list_count), dbg,
+                       f.tr_a, f.tr_b);
+    return hipGetLastError();
+  }, dbg != nullptr, list != nullptr));
+  if (dbg) hash_dbg_report(f.st, f.ng);
+  return hipSuccess;
+}
+
+// hash_count_multi_kernel: R physically consecutive sub-buckets per iteration with packed key|count entries; ranges above the table go
+// on the retry list.  The instrumented instantiation exists for R = 2 only.
+template <int R, bool DBG>
+static hipError_t launch_multi(const FinishFile &f, u64 *dbg) {
+  const uint64_t nsuper = (f.ng + (uint64_t)R - 1) / (uint64_t)R;
+  hipLaunchKernelGGL((hash_count_multi_kernel<256, (int)FIN_CAP_HASH, 2048, R, DBG>), dim3(fin_grid(nsuper, 256u * 16u)), dim3(256), 0, f.st,
+                     reinterpret_cast<u32 *>(f.keys), fin_starts(f), (u64)f.ng, (u64)FIN_CAP_HASH, f.low_bits, f.cnt_tmp, fin_distinct(f), dbg,
+                     f.tr_a, f.tr_b, f.retry_list, reinterpret_cast<u64 *>(f.retry_count));
+  MGC_CHECK(hipGetLastError());
+  if (DBG) hash_dbg_report(f.st, f.ng, true);
+  return hipSuccess;
+}
+
+// hash_count_stream_kernel (the distinct-sized count): one sub-bucket of up to stream_cap keys per iteration, streamed through a
+// SLOTS-entry table in chunks; a sub-bucket with more than DCAP distinct suffixes lands on `overflow` (the retry list).  The
+// instrumented instantiation exists for u32 keys without a list only.
+template <typename KT, int SLOTS, int DCAP, bool LIST, bool DBG>
+static hipError_t launch_stream(const FinishFile &f, uint64_t items, uint32_t max_wgs, const uint32_t *list, const uint64_t *list_count,
+                                u32 *overflow, uint64_t *overflow_count, u64 *dbg = nullptr) {
+  hipLaunchKernelGGL((hash_count_stream_kernel<KT, 256, FIN_STREAM_KPC, SLOTS, DCAP, LIST, DBG>), dim3(fin_grid(items, max_wgs)), dim3(256), 0,
+                     f.st, reinterpret_cast<KT *>(f.keys), fin_starts(f), (u64)f.ng, (u64)f.stream_cap, f.low_bits, f.cnt_tmp, fin_distinct(f),
+                     dbg, f.tr_a, f.tr_b, list, reinterpret_cast<const u64 *>(list_count), overflow, reinterpret_cast<u64 *>(overflow_count));
+  MGC_CHECK(hipGetLastError());
+  if (DBG) hash_dbg_report(f.st, f.ng, true);
+  return hipSuccess;
+}
+
 // ---- the streaming count of a file's oversized sub-buckets: the plain launch, or -- the file holds a gigantic one and the caller
 // brought a workspace -- plan + slices + merge, the range-parallel form for the dense ones, the single-workgroup form for the rest ----
 size_t finish_huge_workspace_bytes(uint64_t n_keys) {
   const uint64_t max_gig = n_keys / HUGE_SLICE_MIN + 2, max_slices = n_keys / HUGE_SLICE + max_gig + 2;
   return 256 + sizeof(u32) * (4 * max_gig + 3 * max_slices) + 8 + sizeof(u64) * max_gig * HUGE_RANGES * 3;
+}
+// the plan's arrays inside a workspace of finish_huge_workspace_bytes(ws_keys) (laid out for ws_keys keys, the largest file of the
+// count: the same layout for every file)
+static HugeSliced huge_layout(void *ws, u64 ws_keys, u32 *d_error) {
+  HugeSliced hs;
+  hs.max_gig = (u32)(ws_keys / HUGE_SLICE_MIN + 2);
+  hs.max_slices = (u32)(ws_keys / HUGE_SLICE + hs.max_gig + 2);
+  u32 *w = reinterpret_cast<u32 *>(ws);
+  hs.counters = w;
+  hs.gig_g = w + 64; hs.gig_pairs = hs.gig_g + hs.max_gig; hs.gig_fail = hs.gig_pairs + hs.max_gig; hs.gig_dist = hs.gig_fail + hs.max_gig;
+  hs.slice_g = hs.gig_dist + hs.max_gig; hs.slice_j = hs.slice_g + hs.max_slices; hs.slice_q = hs.slice_j + hs.max_slices;
+  hs.chain = reinterpret_cast<u64 *>((reinterpret_cast<uintptr_t>(hs.slice_q + hs.max_slices) + 7) & ~(uintptr_t)7);
+  hs.split = hs.chain + (size_t)hs.max_gig * HUGE_RANGES;
+  hs.error = d_error;
+  return hs;
+}
+hipError_t finish_huge_trace(const void *d_ws, uint64_t ws_keys, HugeTrace *out) {
+  std::vector<u32> w(finish_huge_workspace_bytes(ws_keys) / 4);
+  MGC_CHECK(hipMemcpy(w.data(), d_ws, w.size() * 4, hipMemcpyDeviceToHost));
+  const HugeSliced hs = huge_layout(w.data(), ws_keys, nullptr);
+  *out = HugeTrace{hs.counters[0], hs.counters[1], 0};
+  for (u32 q = 0; q < out->cut && q < hs.max_gig; q++) out->dense += hs.gig_fail[q] ? 1u : 0u;
+  return hipSuccess;
 }
 // MODE 3 left a dense sub-bucket's k-mers in alt[] (its other ranges were still reading the keys): home, now that all of them are done
 template <typename KT>
@@ -2539,427 +2645,248 @@ void huge_copy_back_kernel(KT *__restrict__ keys, const KT *__restrict__ alt, co
   const u32 d = hs.gig_dist[q];
   for (u32 i = threadIdx.x; i < d; i += 1024) keys[a + i] = alt[a + i];
 }
-template <typename S, int CAP, int SLOTS, typename KT>
-static hipError_t launch_huge(KT *keys, const u64 *starts, const u32 *list, u64 n_large, u64 ng, u64 huge_min, u32 low_bits, u32 *cnt_tmp,
-                              u64 *group_distinct, KT *alt, u32 tr_a, u32 tr_b, size_t smem, hipStream_t st, u64 max_sub, u64 n_keys,
-                              void *ws, size_t ws_bytes, u64 ws_keys, u32 *d_error) {
+
+// A streaming family: its key type, its four MODE instantiations, their dynamic LDS, and where the MODE 0 pass over what the plan
+// did not cut goes in the sliced form (REST_LAST).
+// 8-byte keys and narrowed words (KT = u32); S: the table's suffix type
+template <typename S, typename KT>
+struct Huge8 {
+  using Key = KT;
+  static constexpr int CAP = sizeof(S) == 4 ? HUGE_CAP32 : HUGE_CAP64, SLOTS = sizeof(S) == 4 ? HUGE_SLOTS32 : HUGE_SLOTS64;
+  static constexpr size_t LDS = sizeof(S) == 4 ? HUGE_LDS32 : HUGE_LDS64;
+  static constexpr bool REST_LAST = false;               // after the slices, before their merge (MODE 2)
+  template <int MODE> static auto kernel() { return &hash_count_huge_kernel<S, 1024, CAP, SLOTS, KT, MODE>; }
+};
+// 16-byte keys / K96 records (a pair = two records: the suffix, the count); WIDE: suffixes above 64 bits
+template <bool WIDE, typename KT>
+struct Huge16 {
+  using Key = KT;
+  static constexpr size_t LDS = WIDE ? HUGE_LDS128_WIDE : HUGE_LDS128;
+  static constexpr bool REST_LAST = true;                // after the dense sub-buckets' ranges (MODE 3)
+  template <int MODE> static auto kernel() { return &hash_count128_huge_kernel<1024, HUGE_CAP128, HUGE_SLOTS128, WIDE, KT, MODE>; }
+};
+
+// one MODE of family T over `grid` workgroups; list entries at or below huge_min are somebody else's
+template <typename T, int MODE>
+static hipError_t launch_huge_mode(const FinishFile &f, const uint32_t *list, uint32_t grid, u64 huge_min, u64 huge_max, const HugeSliced &hs,
+                                   hipStream_t st) {
+  using KT = typename T::Key;
+  const auto kernel = T::template kernel<MODE>();
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hash_count_huge_kernel<S, 1024, CAP, SLOTS, KT, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hash_count_huge_kernel<S, 1024, CAP, SLOTS, KT, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hash_count_huge_kernel<S, 1024, CAP, SLOTS, KT, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hash_count_huge_kernel<S, 1024, CAP, SLOTS, KT, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::LDS);
     attr = true;
   }
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(1024), T::LDS, st, reinterpret_cast<KT *>(f.keys), fin_starts(f), list, (u64)f.ng,
+                     huge_min, f.low_bits, f.cnt_tmp, fin_distinct(f), reinterpret_cast<KT *>(f.alt), f.tr_a, f.tr_b, huge_max, hs);
+  return hipGetLastError();
+}
+
+// the file's oversized list through family T, on f.st_huge
+template <typename T>
+static hipError_t launch_huge(const FinishFile &f, u64 huge_min) {
+  using KT = typename T::Key;
+  const u64 n_large = f.n_large, n_keys = f.n_keys;
+  hipStream_t st = f.st_huge;
   if (n_large == 0) return hipSuccess;
-  // (the workspace is laid out for ws_keys keys, the largest file of the count: the same layout for every file)
-  const bool sliced = ws && d_error && max_sub > (u64)HUGE_SLICE_MIN && n_keys && n_keys <= ws_keys && ws_bytes >= finish_huge_workspace_bytes(ws_keys);
-  if (!sliced) {
-    hipLaunchKernelGGL((hash_count_huge_kernel<S, 1024, CAP, SLOTS, KT, 0>), dim3((uint32_t)n_large), dim3(1024), smem, st, keys, starts, list, ng, huge_min,
-                       low_bits, cnt_tmp, group_distinct, alt, tr_a, tr_b, (u64)0, HugeSliced());
-    return hipGetLastError();
-  }
-  HugeSliced hs;
-  hs.max_gig = (u32)(ws_keys / HUGE_SLICE_MIN + 2);
-  hs.max_slices = (u32)(ws_keys / HUGE_SLICE + hs.max_gig + 2);
-  u32 *w = reinterpret_cast<u32 *>(ws);
-  hs.counters = w;
-  hs.gig_g = w + 64; hs.gig_pairs = hs.gig_g + hs.max_gig; hs.gig_fail = hs.gig_pairs + hs.max_gig; hs.gig_dist = hs.gig_fail + hs.max_gig;
-  hs.slice_g = hs.gig_dist + hs.max_gig; hs.slice_j = hs.slice_g + hs.max_slices; hs.slice_q = hs.slice_j + hs.max_slices;
-  hs.chain = reinterpret_cast<u64 *>((reinterpret_cast<uintptr_t>(hs.slice_q + hs.max_slices) + 7) & ~(uintptr_t)7);
-  hs.split = hs.chain + (size_t)hs.max_gig * HUGE_RANGES;
-  hs.error = d_error;
-  MGC_CHECK(hipMemsetAsync(ws, 0, finish_huge_workspace_bytes(ws_keys), st));
-  hipLaunchKernelGGL(huge_plan_kernel, dim3((uint32_t)((n_large + 255) / 256)), dim3(256), 0, st, starts, list, n_large, (u64)HUGE_SLICE_MIN, hs, 0u);
+  const bool sliced = f.huge_ws && f.d_error && f.max_sub > (u64)HUGE_SLICE_MIN && n_keys && n_keys <= f.huge_ws_keys &&
+                      f.huge_ws_bytes >= finish_huge_workspace_bytes(f.huge_ws_keys);
+  if (!sliced) return launch_huge_mode<T, 0>(f, f.large_list, (uint32_t)n_large, huge_min, 0, HugeSliced(), st);
+  const HugeSliced hs = huge_layout(f.huge_ws, f.huge_ws_keys, f.d_error);
+  MGC_CHECK(hipMemsetAsync(f.huge_ws, 0, finish_huge_workspace_bytes(f.huge_ws_keys), st));
+  hipLaunchKernelGGL(huge_plan_kernel, dim3((uint32_t)((n_large + 255) / 256)), dim3(256), 0, st, fin_starts(f), f.large_list, n_large, (u64)HUGE_SLICE_MIN, hs, 0u);
   MGC_CHECK(hipGetLastError());
   const uint32_t sgrid = (uint32_t)std::min<u64>(512, std::min<u64>((u64)hs.max_slices, n_keys / HUGE_SLICE + n_keys / HUGE_SLICE_MIN + 4));   // (by ticket)
   const uint32_t ggrid = (uint32_t)std::min<u64>(std::min<u64>(n_large, (u64)hs.max_gig), n_keys / HUGE_SLICE_MIN + 1);
   // the slices first: they are the long pole
-  hipLaunchKernelGGL((hash_count_huge_kernel<S, 1024, CAP, SLOTS, KT, 1>), dim3(sgrid), dim3(1024), smem, st, keys, starts, list, ng, huge_min,
-                     low_bits, cnt_tmp, group_distinct, alt, tr_a, tr_b, (u64)0, hs);
-  MGC_CHECK(hipGetLastError());
-  hipLaunchKernelGGL((hash_count_huge_kernel<S, 1024, CAP, SLOTS, KT, 0>), dim3((uint32_t)n_large), dim3(1024), smem, st, keys, starts, list, ng, huge_min,
-                     low_bits, cnt_tmp, group_distinct, alt, tr_a, tr_b, (u64)HUGE_SLICE_MIN, hs);
-  MGC_CHECK(hipGetLastError());
-  hipLaunchKernelGGL((hash_count_huge_kernel<S, 1024, CAP, SLOTS, KT, 2>), dim3(ggrid), dim3(1024), smem, st, keys, starts, list, ng, huge_min,
-                     low_bits, cnt_tmp, group_distinct, alt, tr_a, tr_b, (u64)0, hs);
-  MGC_CHECK(hipGetLastError());
+  MGC_CHECK((launch_huge_mode<T, 1>(f, f.large_list, sgrid, huge_min, 0, hs, st)));
+  if (!T::REST_LAST) MGC_CHECK((launch_huge_mode<T, 0>(f, f.large_list, (uint32_t)n_large, huge_min, HUGE_SLICE_MIN, hs, st)));
+  MGC_CHECK((launch_huge_mode<T, 2>(f, f.large_list, ggrid, huge_min, 0, hs, st)));
   // ... and the dense ones (their slices' pairs did not fit): quantiles of a sample, HUGE_RANGES workgroups each, by ticket; then their k-mers home from alt[]
-  hipLaunchKernelGGL(huge_split_kernel<KT>, dim3(ggrid), dim3(1024), 0, st, (const KT *)keys, starts, low_bits, hs);
+  hipLaunchKernelGGL(huge_split_kernel<KT>, dim3(ggrid), dim3(1024), 0, st, reinterpret_cast<const KT *>(f.keys), fin_starts(f), f.low_bits, hs);
   MGC_CHECK(hipGetLastError());
-  hipLaunchKernelGGL((hash_count_huge_kernel<S, 1024, CAP, SLOTS, KT, 3>), dim3(256), dim3(1024), smem, st, keys, starts, list, ng, huge_min,
-                     low_bits, cnt_tmp, group_distinct, alt, tr_a, tr_b, (u64)0, hs);
-  MGC_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(huge_copy_back_kernel<KT>, dim3(ggrid), dim3(1024), 0, st, keys, (const KT *)alt, starts, hs);
+  MGC_CHECK((launch_huge_mode<T, 3>(f, f.large_list, 256u, huge_min, 0, hs, st)));
+  if (T::REST_LAST) MGC_CHECK((launch_huge_mode<T, 0>(f, f.large_list, (uint32_t)n_large, huge_min, HUGE_SLICE_MIN, hs, st)));
+  hipLaunchKernelGGL(huge_copy_back_kernel<KT>, dim3(ggrid), dim3(1024), 0, st, reinterpret_cast<KT *>(f.keys), reinterpret_cast<const KT *>(f.alt), fin_starts(f), hs);
   return hipGetLastError();
 }
 
-// the same for 16-byte keys / K96 records (a pair = two records: the suffix, the count)
-template <bool WIDE, typename KT>
-static hipError_t launch_huge128(KT *keys, const u64 *starts, const u32 *list, u64 n_large, u64 ng, u64 huge_min, u32 low_bits, u32 *cnt_tmp,
-                                 u64 *group_distinct, KT *alt, u32 tr_a, u32 tr_b, hipStream_t st, u64 max_sub, u64 n_keys,
-                                 void *ws, size_t ws_bytes, u64 ws_keys, u32 *d_error) {
-  constexpr int HS = 4096, HC = 2048;
-  constexpr size_t smem = WIDE ? (size_t)(8 + 8 + 4) * HS + (size_t)(8 + 8) * (HC + 16) + (size_t)4 * HC
-                               : (size_t)(8 + 4) * HS + (size_t)8 * (HC + 16) + (size_t)4 * HC;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hash_count128_huge_kernel<1024, HC, HS, WIDE, KT, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hash_count128_huge_kernel<1024, HC, HS, WIDE, KT, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hash_count128_huge_kernel<1024, HC, HS, WIDE, KT, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hash_count128_huge_kernel<1024, HC, HS, WIDE, KT, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr = true;
-  }
-  if (n_large == 0) return hipSuccess;
-  const bool sliced = ws && d_error && max_sub > (u64)HUGE_SLICE_MIN && n_keys && n_keys <= ws_keys && ws_bytes >= finish_huge_workspace_bytes(ws_keys);
-  if (!sliced) {
-    hipLaunchKernelGGL((hash_count128_huge_kernel<1024, HC, HS, WIDE, KT, 0>), dim3((uint32_t)n_large), dim3(1024), smem, st, keys, starts, list, ng, huge_min,
-                       low_bits, cnt_tmp, group_distinct, alt, tr_a, tr_b, (u64)0, HugeSliced());
-    return hipGetLastError();
-  }
-  HugeSliced hs;
-  hs.max_gig = (u32)(ws_keys / HUGE_SLICE_MIN + 2);
-  hs.max_slices = (u32)(ws_keys / HUGE_SLICE + hs.max_gig + 2);
-  u32 *w = reinterpret_cast<u32 *>(ws);
-  hs.counters = w;
-  hs.gig_g = w + 64; hs.gig_pairs = hs.gig_g + hs.max_gig; hs.gig_fail = hs.gig_pairs + hs.max_gig; hs.gig_dist = hs.gig_fail + hs.max_gig;
-  hs.slice_g = hs.gig_dist + hs.max_gig; hs.slice_j = hs.slice_g + hs.max_slices; hs.slice_q = hs.slice_j + hs.max_slices;
-  hs.chain = reinterpret_cast<u64 *>((reinterpret_cast<uintptr_t>(hs.slice_q + hs.max_slices) + 7) & ~(uintptr_t)7);
-  hs.split = hs.chain + (size_t)hs.max_gig * HUGE_RANGES;
-  hs.error = d_error;
-  MGC_CHECK(hipMemsetAsync(ws, 0, finish_huge_workspace_bytes(ws_keys), st));
-  hipLaunchKernelGGL(huge_plan_kernel, dim3((uint32_t)((n_large + 255) / 256)), dim3(256), 0, st, starts, list, n_large, (u64)HUGE_SLICE_MIN, hs, 0u);
-  MGC_CHECK(hipGetLastError());
-  const uint32_t sgrid = (uint32_t)std::min<u64>(512, std::min<u64>((u64)hs.max_slices, n_keys / HUGE_SLICE + n_keys / HUGE_SLICE_MIN + 4));   // (by ticket)
-  hipLaunchKernelGGL((hash_count128_huge_kernel<1024, HC, HS, WIDE, KT, 1>), dim3(sgrid), dim3(1024), smem, st, keys, starts, list, ng, huge_min,
-                     low_bits, cnt_tmp, group_distinct, alt, tr_a, tr_b, (u64)0, hs);
-  MGC_CHECK(hipGetLastError());
-  const uint32_t ggrid = (uint32_t)std::min<u64>(std::min<u64>(n_large, (u64)hs.max_gig), n_keys / HUGE_SLICE_MIN + 1);
-  hipLaunchKernelGGL((hash_count128_huge_kernel<1024, HC, HS, WIDE, KT, 2>), dim3(ggrid), dim3(1024), smem, st, keys, starts, list, ng, huge_min,
-                     low_bits, cnt_tmp, group_distinct, alt, tr_a, tr_b, (u64)0, hs);
-  MGC_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(huge_split_kernel<KT>, dim3(ggrid), dim3(1024), 0, st, (const KT *)keys, starts, low_bits, hs);
-  MGC_CHECK(hipGetLastError());
-  hipLaunchKernelGGL((hash_count128_huge_kernel<1024, HC, HS, WIDE, KT, 3>), dim3(256), dim3(1024), smem, st, keys, starts, list, ng, huge_min,
-                     low_bits, cnt_tmp, group_distinct, alt, tr_a, tr_b, (u64)0, hs);
-  MGC_CHECK(hipGetLastError());
-  hipLaunchKernelGGL((hash_count128_huge_kernel<1024, HC, HS, WIDE, KT, 0>), dim3((uint32_t)n_large), dim3(1024), smem, st, keys, starts, list, ng, huge_min,
-                     low_bits, cnt_tmp, group_distinct, alt, tr_a, tr_b, (u64)HUGE_SLICE_MIN, hs);
-  MGC_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(huge_copy_back_kernel<KT>, dim3(ggrid), dim3(1024), 0, st, keys, (const KT *)alt, starts, hs);
+template <typename S, int CAP, int SLOTS, typename KT>
+static hipError_t launch_probe(const FinishFile &f, uint64_t stream_max, uint32_t *d_file_fail) {
+  hipLaunchKernelGGL((hash_probe_kernel<S, 1024, CAP, SLOTS, KT>), dim3((uint32_t)f.n_large), dim3(1024), 0, f.st,
+                     reinterpret_cast<const KT *>(f.keys), fin_starts(f), f.large_list, (u64)stream_max, f.low_bits, d_file_fail);
   return hipGetLastError();
 }
-
-bool finish_can_stream(uint32_t key_words, uint32_t low_bits) {
-  return finish_uses_hash(key_words, low_bits);
+hipError_t launch_finish_probe(const FinishFile &f, uint64_t stream_max, uint32_t *d_file_fail) {
+  if (f.n_large == 0 || finish_key_words(f.layout) != 1) return hipSuccess;
+  if (f.layout == FinishKeys::NARROW32) {
+    if (f.low_bits >= 32) return hipErrorInvalidValue;
+    return launch_probe<u32, HUGE_CAP32, HUGE_SLOTS32, u32>(f, stream_max, d_file_fail);
+  }
+  if (f.low_bits < 32) return launch_probe<u32, HUGE_CAP32, HUGE_SLOTS32, u64>(f, stream_max, d_file_fail);
+  return launch_probe<u64, HUGE_CAP64, HUGE_SLOTS64, u64>(f, stream_max, d_file_fail);
 }
 
-hipError_t launch_finish_probe(const void *d_keys, uint32_t key_words, const uint64_t *d_starts, uint32_t low_bits,
-                               uint64_t n_large, const uint32_t *d_large_list, uint32_t *d_file_fail, hipStream_t st, uint64_t stream_max, bool narrow) {
-  if (n_large == 0 || key_words != 1) return hipSuccess;
-  if (narrow) {
-    if (low_bits >= 32) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((hash_probe_kernel<u32, 1024, HUGE_CAP32, HUGE_SLOTS32, u32>), dim3((uint32_t)n_large), dim3(1024), 0, st,
-                       reinterpret_cast<const u32 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), d_large_list,
-                       (u64)stream_max, low_bits, d_file_fail);
-    return hipGetLastError();
-  }
-  if (low_bits < 32)
-    hipLaunchKernelGGL((hash_probe_kernel<u32, 1024, HUGE_CAP32, HUGE_SLOTS32>), dim3((uint32_t)n_large), dim3(1024), 0, st,
-                       reinterpret_cast<const u64 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), d_large_list,
-                       (u64)stream_max, low_bits, d_file_fail);
-  else
-    hipLaunchKernelGGL((hash_probe_kernel<u64, 1024, HUGE_CAP64, HUGE_SLOTS64>), dim3((uint32_t)n_large), dim3(1024), 0, st,
-                       reinterpret_cast<const u64 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), d_large_list,
-                       (u64)stream_max, low_bits, d_file_fail);
-  return hipGetLastError();
-}
+// ---- launch_finish_file: the preconditions, the path, the launches ----
 
-// stream: the sub-buckets on the large list go through hash_count_huge_kernel (d_alt: room for the file's keys); otherwise
-// through the LDS sort, and the file holds none above its capacity (the caller checked the largest sub-bucket)
-hipError_t launch_finish_file(void *d_keys, uint32_t key_words, const uint64_t *d_starts, uint64_t ng, uint32_t low_bits,
-                              uint64_t n_large, const uint32_t *d_large_list, uint32_t *d_cnt_tmp, uint64_t *d_group_distinct,
-                              bool stream, void *d_alt, hipStream_t st_huge, const uint32_t *d_nz, const uint64_t *d_nz_count,
-                              hipStream_t st, bool narrow, uint32_t tr_a, uint32_t tr_b, uint64_t max_sub, uint64_t n_keys,
-                              uint32_t *d_retry_list, uint64_t *d_retry_count, bool k96, int hash_multi, bool hash_dbg,
-                              uint64_t stream_cap, void *d_huge_ws, size_t huge_ws_bytes, uint64_t huge_ws_keys, uint32_t *d_error) {
-  const u64 *nzc = reinterpret_cast<const u64 *>(d_nz_count);
-  if (stream_cap && !(d_retry_list && d_retry_count && finish_stream_ok(key_words, low_bits, narrow) && !k96 && n_keys < (1ull << 32) &&
-                      stream_cap <= FIN_CAP_STREAM && (n_large == 0 || stream)))
-    return hipErrorInvalidValue;
-  if (k96) {
-    // 12-byte K96 records: the persistent hash-count, and the streaming count of oversized sub-buckets (a file whose oversized
-    // sub-buckets nothing streams is widened to 16-byte keys by the caller first)
-    if (key_words != 2 || narrow || (n_large && !stream) || !finish_uses_hash(key_words, low_bits)) return hipErrorInvalidValue;
-    const bool small96 = max_sub && max_sub <= 768 && n_large == 0;
-    const u64 msize = small96 ? (u64)768 : FIN_CAP_HASH128;
-    const bool lst = d_nz != nullptr, wide = low_bits > 64;
-    const uint32_t gmax = 256u * (small96 ? 12u : 8u), g96 = ng < gmax ? (uint32_t)ng : gmax;
-#define MGC_W96_LAUNCH(CAP_, SLOTS_, WIDE_, LIST_)                                                                                       \
-    hipLaunchKernelGGL((hash_countw_kernel<K96, 256, CAP_, SLOTS_, WIDE_, LIST_>), dim3(g96), dim3(256), 0, st,                          \
-                       reinterpret_cast<K96 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), (u64)ng, msize, low_bits,               \
-                       d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), d_nz, nzc, tr_a, tr_b)
-    if (small96) {
-      if (wide) { if (lst) MGC_W96_LAUNCH(768, 1024, true, true);  else MGC_W96_LAUNCH(768, 1024, true, false); }
-      else      { if (lst) MGC_W96_LAUNCH(768, 1024, false, true); else MGC_W96_LAUNCH(768, 1024, false, false); }
-    } else {
-      if (wide) { if (lst) MGC_W96_LAUNCH(1536, 2048, true, true);  else MGC_W96_LAUNCH(1536, 2048, true, false); }
-      else      { if (lst) MGC_W96_LAUNCH(1536, 2048, false, true); else MGC_W96_LAUNCH(1536, 2048, false, false); }
-    }
-#undef MGC_W96_LAUNCH
-    MGC_CHECK(hipGetLastError());
-    if (n_large) {
-      if (wide)
-        MGC_CHECK((launch_huge128<true, K96>(reinterpret_cast<K96 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), d_large_list, (u64)n_large, (u64)ng,
-                   FIN_CAP_HASH128, low_bits, d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), reinterpret_cast<K96 *>(d_alt), tr_a, tr_b, st_huge,
-                   (u64)max_sub, (u64)n_keys, d_huge_ws, huge_ws_bytes, (u64)huge_ws_keys, d_error)));
-      else
-        MGC_CHECK((launch_huge128<false, K96>(reinterpret_cast<K96 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), d_large_list, (u64)n_large, (u64)ng,
-                   FIN_CAP_HASH128, low_bits, d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), reinterpret_cast<K96 *>(d_alt), tr_a, tr_b, st_huge,
-                   (u64)max_sub, (u64)n_keys, d_huge_ws, huge_ws_bytes, (u64)huge_ws_keys, d_error)));
-    }
-    return hipSuccess;
-  }
-  const bool use_list = d_nz != nullptr;
-  if (narrow) {
-    // narrowed keys (u32): the 32-bit hash-count kernels and the streaming kernel have u32-storage instantiations; anything
-    // else wants whole k-mers -- the caller widens the file first (launch_widen_groups)
-    if (key_words != 1 || low_bits >= 32 || (n_large && !stream)) return hipErrorInvalidValue;
-    const uint32_t hgrid = ng < 256u * 14u ? (uint32_t)ng : 256u * 14u;
-#define MGC_NARROW_LAUNCH(DBG_, LIST_, DBGBUF_)                                                                                          \
-    hipLaunchKernelGGL((hash_count_kernel<256, (int)FIN_CAP_HASH, 2048, DBG_, LIST_, true>), dim3(hgrid), dim3(256), 0, st,              \
-                       reinterpret_cast<u64 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), (u64)ng, (u64)FIN_CAP_HASH, low_bits, \
-                       d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), d_nz, nzc, DBGBUF_, tr_a, tr_b)
-    // R physically consecutive sub-buckets per iteration with packed key|count entries (hash_count_multi_kernel): dense grids
-    // whose tagged suffix fits 20 bits.  R from the file's average sub-bucket (MGC_HASH_MULTI=0: the one-at-a-time kernel;
-    // 1/2/4: that R whatever the average -- tests).  Measured at 10 Gbp (profiles/r05a: MGC_HASH_MULTI=2 on every file): R = 2
-    // on files whose sub-buckets average more than 690 k-mers sends most ranges to the retry list (they exceed the 1536-key
-    // table): 68 ms of count stage against 29 -- R = 1 there is the table's size, not the heuristic's choice.
-    const int multi_env = hash_multi;
-    int multi_r = 0;
-    if (multi_env != 0 && !d_nz && ng >= 4 && d_retry_list && d_retry_count) {
-      const uint64_t avg = n_keys ? n_keys / ng : FIN_CAP_HASH;
-      multi_r = multi_env > 0 ? multi_env : (avg <= 340 ? 4 : (avg <= 690 ? 2 : 1));
-      const uint32_t tagb = multi_r == 1 ? 0u : (multi_r == 2 ? 1u : 2u);
-      if (multi_env < 0 && multi_r > 1 && low_bits + tagb > 20) multi_r = (multi_r == 4 && low_bits + 1 <= 20) ? 2 : 1;   // fewer tag bits
-      const uint32_t tagb2 = multi_r == 1 ? 0u : (multi_r == 2 ? 1u : 2u);
-      if (multi_r > 4 || multi_r == 3 || low_bits + tagb2 < 8 || low_bits + tagb2 > 20) multi_r = 0;
-    }
-    u64 *dbgb = hash_dbg_buffer(hash_dbg);                           // MGC_HASH_DBG=1: the instrumented instantiations (per-phase cycle stamps)
-    if (stream_cap) {
-      // the distinct-sized count: one sub-bucket of up to stream_cap keys per iteration, streamed through a 2048-entry table
-      // in chunks; sub-buckets with more distinct suffixes than it holds land on the retry list (launch_finish_retry)
-      const uint64_t gmax = 256ull * 16ull;
-      const dim3 sgrid((uint32_t)(ng < gmax ? ng : gmax));
-      if (use_list)
-        hipLaunchKernelGGL((hash_count_stream_kernel<u32, 256, FIN_STREAM_KPC, FIN_STREAM_SLOTS, FIN_STREAM_DCAP, true, false>), sgrid, dim3(256), 0, st,
-                           reinterpret_cast<u32 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), (u64)ng, (u64)stream_cap, low_bits,
-                           d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), (u64 *)nullptr, tr_a, tr_b, d_nz, nzc,
-                           d_retry_list, reinterpret_cast<u64 *>(d_retry_count));
-      else if (dbgb)
-        hipLaunchKernelGGL((hash_count_stream_kernel<u32, 256, FIN_STREAM_KPC, FIN_STREAM_SLOTS, FIN_STREAM_DCAP, false, true>), sgrid, dim3(256), 0, st,
-                           reinterpret_cast<u32 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), (u64)ng, (u64)stream_cap, low_bits,
-                           d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), dbgb, tr_a, tr_b, (const u32 *)nullptr, (const u64 *)nullptr,
-                           d_retry_list, reinterpret_cast<u64 *>(d_retry_count));
-      else
-        hipLaunchKernelGGL((hash_count_stream_kernel<u32, 256, FIN_STREAM_KPC, FIN_STREAM_SLOTS, FIN_STREAM_DCAP, false, false>), sgrid, dim3(256), 0, st,
-                           reinterpret_cast<u32 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), (u64)ng, (u64)stream_cap, low_bits,
-                           d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), (u64 *)nullptr, tr_a, tr_b, (const u32 *)nullptr,
-                           (const u64 *)nullptr, d_retry_list, reinterpret_cast<u64 *>(d_retry_count));
-      MGC_CHECK(hipGetLastError());
-      if (dbgb && !use_list) hash_dbg_report(st, ng, true);
-    }
-    else if (multi_r) {
-      const uint64_t nsuper = (ng + (uint64_t)multi_r - 1) / (uint64_t)multi_r;
-#define MGC_MULTI_LAUNCH(R_, DBG_)                                                                                                       \
-      do { const uint64_t gmax = 256ull * 16ull;                                                                                        \
-           hipLaunchKernelGGL((hash_count_multi_kernel<256, (int)FIN_CAP_HASH, 2048, R_, DBG_>), dim3((uint32_t)(nsuper < gmax ? nsuper : gmax)), \
-                       dim3(256), 0, st, reinterpret_cast<u32 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), (u64)ng,              \
-                       (u64)FIN_CAP_HASH, low_bits, d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), dbgb, tr_a, tr_b,             \
-                       d_retry_list, reinterpret_cast<u64 *>(d_retry_count)); } while (0)
-      if (dbgb && multi_r == 2) MGC_MULTI_LAUNCH(2, true);
-      else if (multi_r == 1)    MGC_MULTI_LAUNCH(1, false);
-      else if (multi_r == 2)    MGC_MULTI_LAUNCH(2, false);
-      else                      MGC_MULTI_LAUNCH(4, false);
-#undef MGC_MULTI_LAUNCH
-      MGC_CHECK(hipGetLastError());
-      if (dbgb && multi_r == 2) hash_dbg_report(st, ng, true);
-      // the sub-buckets of ranges above the table (retry list, usually short): one at a time.  (R = 1: a range is one sub-bucket,
-      // the list stays empty -- no launch: queued behind the other stream's persistent kernel an empty one still lasted 170 us)
-      if (multi_r > 1) { const uint32_t rgrid = ng < 256u * 7u ? (uint32_t)ng : 256u * 7u;
-        hipLaunchKernelGGL((hash_count_kernel<256, (int)FIN_CAP_HASH, 2048, false, true, true>), dim3(rgrid), dim3(256), 0, st,
-                           reinterpret_cast<u64 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), (u64)ng, (u64)FIN_CAP_HASH, low_bits,
-                           d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), d_retry_list, reinterpret_cast<const u64 *>(d_retry_count),
-                           (u64 *)nullptr, tr_a, tr_b);
-        MGC_CHECK(hipGetLastError()); }
-    }
-    else if (dbgb) {
-      if (use_list) MGC_NARROW_LAUNCH(true, true, dbgb); else MGC_NARROW_LAUNCH(true, false, dbgb);
-      MGC_CHECK(hipGetLastError());
-      hash_dbg_report(st, ng);
-    }
-    else if (use_list) MGC_NARROW_LAUNCH(false, true, (u64 *)nullptr);
-    else               MGC_NARROW_LAUNCH(false, false, (u64 *)nullptr);
-#undef MGC_NARROW_LAUNCH
-    MGC_CHECK(hipGetLastError());
-    if (n_large) {
-      constexpr size_t B32 = (size_t)(4 + 4) * HUGE_SLOTS32 + (size_t)(4 + 4) * HUGE_CAP32 + 16 * 4;
-      MGC_CHECK((launch_huge<u32, HUGE_CAP32, HUGE_SLOTS32, u32>(reinterpret_cast<u32 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), d_large_list, (u64)n_large,
-                 (u64)ng, (u64)(stream_cap ? stream_cap : FIN_CAP_HASH), low_bits, d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct),
-                 reinterpret_cast<u32 *>(d_alt), tr_a, tr_b, B32, st_huge, (u64)max_sub, (u64)n_keys, d_huge_ws, huge_ws_bytes, (u64)huge_ws_keys, d_error)));
-    }
-    return hipSuccess;
-  }
+// every oversized sub-bucket has somewhere to go
+static bool fin_large_ok(const FinishFile &f) { return f.n_large == 0 || f.stream; }
+
+static bool finish_file_valid(const FinishFile &f) {
+  const uint32_t kw = finish_key_words(f.layout);
+  const bool narrow = f.layout == FinishKeys::NARROW32, k96 = f.layout == FinishKeys::K96;
+  if (f.stream_cap && !(f.retry_list && f.retry_count && finish_stream_ok(kw, f.low_bits, narrow) && !k96 && f.n_keys < (1ull << 32) &&
+                        f.stream_cap <= FIN_CAP_STREAM && fin_large_ok(f)))
+    return false;
+  // 12-byte K96 records: the persistent hash-count, and the streaming count of oversized sub-buckets (a file whose oversized
+  // sub-buckets nothing streams is widened to 16-byte keys by the caller first)
+  if (k96) return fin_large_ok(f) && finish_uses_hash(kw, f.low_bits);
+  // narrowed keys (u32): the 32-bit hash-count kernels and the streaming kernel have u32-storage instantiations; anything
+  // else wants whole k-mers -- the caller widens the file first (launch_widen_groups)
+  if (narrow) return f.low_bits < 32 && fin_large_ok(f);
   // whole keys in (low digit : high digit) order (launch_group_wide): only the hash-count kernels translate the sub-bucket numbers
-  if (tr_a && !(finish_uses_hash(key_words, low_bits) && (n_large == 0 || stream))) return hipErrorInvalidValue;
-  // a file whose LARGEST sub-bucket holds at most 768 k-mers (`compress`: 59049 sub-buckets per bucket, a few hundred k-mers each):
-  // three keys per thread instead of six -- fewer idle unrolled slots, half the LDS, more workgroups per CU
-  const bool small = max_sub && max_sub <= 768 && n_large == 0;
-  if (key_words == 2 && finish_uses_hash(key_words, low_bits)) {
-    const u64 msize = small ? (u64)768 : FIN_CAP_HASH128;
-#define MGC_W128_LAUNCH(CAP_, SLOTS_, WIDE_, LIST_, GRID_)                                                                               \
-    hipLaunchKernelGGL((hash_countw_kernel<K128, 256, CAP_, SLOTS_, WIDE_, LIST_>), dim3(GRID_), dim3(256), 0, st,                       \
-                       reinterpret_cast<K128 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), (u64)ng, msize, low_bits,              \
-                       d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), d_nz, nzc, tr_a, tr_b)
-    const uint32_t g128_max = 256u * (small ? 12u : 8u);
-    const uint32_t g128 = ng < g128_max ? (uint32_t)ng : g128_max;
-    const bool wide128 = low_bits > 64;
-    if (small) {
-      if (wide128) { if (use_list) MGC_W128_LAUNCH(768, 1024, true, true, g128);  else MGC_W128_LAUNCH(768, 1024, true, false, g128); }
-      else         { if (use_list) MGC_W128_LAUNCH(768, 1024, false, true, g128); else MGC_W128_LAUNCH(768, 1024, false, false, g128); }
-    } else {
-      if (wide128) { if (use_list) MGC_W128_LAUNCH(1536, 2048, true, true, g128);  else MGC_W128_LAUNCH(1536, 2048, true, false, g128); }
-      else         { if (use_list) MGC_W128_LAUNCH(1536, 2048, false, true, g128); else MGC_W128_LAUNCH(1536, 2048, false, false, g128); }
+  return !f.tr_a || (finish_uses_hash(kw, f.low_bits) && fin_large_ok(f));
+}
+
+// sub-buckets per iteration of hash_count_multi_kernel (0: the one-at-a-time kernel): dense grids whose tagged suffix fits 20 bits.
+// R from the file's average sub-bucket (MGC_HASH_MULTI=0: the one-at-a-time kernel; 1/2/4: that R whatever the average -- tests).
+// Measured at 10 Gbp (profiles/r05a: MGC_HASH_MULTI=2 on every file): R = 2 on files whose sub-buckets average more than 690 k-mers
+// sends most ranges to the retry list (they exceed the 1536-key table): 68 ms of count stage against 29 -- R = 1 there is the
+// table's size, not the heuristic's choice.
+static int finish_multi_r(const FinishFile &f) {
+  const int multi_env = f.hash_multi;
+  const uint32_t low_bits = f.low_bits;
+  if (multi_env == 0 || f.nonempty_list || f.ng < 4 || !f.retry_list || !f.retry_count) return 0;
+  const uint64_t avg = f.n_keys ? f.n_keys / f.ng : FIN_CAP_HASH;
+  int multi_r = multi_env > 0 ? multi_env : (avg <= 340 ? 4 : (avg <= 690 ? 2 : 1));
+  const uint32_t tagb = multi_r == 1 ? 0u : (multi_r == 2 ? 1u : 2u);
+  if (multi_env < 0 && multi_r > 1 && low_bits + tagb > 20) multi_r = (multi_r == 4 && low_bits + 1 <= 20) ? 2 : 1;   // fewer tag bits
+  const uint32_t tagb2 = multi_r == 1 ? 0u : (multi_r == 2 ? 1u : 2u);
+  if (multi_r > 4 || multi_r == 3 || low_bits + tagb2 < 8 || low_bits + tagb2 > 20) multi_r = 0;
+  return multi_r;
+}
+
+// which kernel counts the sub-buckets up to the small capacity
+enum class FinishPath {
+  K96_HASH,                                              // K96 records: hash_countw_kernel
+  NARROW_STREAM, NARROW_MULTI1, NARROW_MULTI2, NARROW_MULTI4, NARROW_HASH,   // narrowed keys: hash_count_stream / _multi<R> / hash_count kernels
+  K128_HASH, K128_SORT,                                  // whole 16-byte keys: hash_countw_kernel; the LDS sort (suffixes above 122 bits)
+  U64_STREAM, U64_CLAIMED, U64_PACKED, U64_SORT          // whole 8-byte keys: hash_count_stream; hash_countw (suffixes of 32 bits and more);
+};                                                       // hash_count; the LDS sort (suffixes above 58 bits)
+static FinishPath finish_path(const FinishFile &f) {
+  const bool hash = finish_uses_hash(finish_key_words(f.layout), f.low_bits);
+  switch (f.layout) {
+  case FinishKeys::K96:      return FinishPath::K96_HASH;
+  case FinishKeys::WHOLE16:  return hash ? FinishPath::K128_HASH : FinishPath::K128_SORT;
+  case FinishKeys::NARROW32:
+    if (f.stream_cap) return FinishPath::NARROW_STREAM;
+    switch (finish_multi_r(f)) {
+    case 1:  return FinishPath::NARROW_MULTI1;
+    case 2:  return FinishPath::NARROW_MULTI2;
+    case 4:  return FinishPath::NARROW_MULTI4;
+    default: return FinishPath::NARROW_HASH;
     }
-#undef MGC_W128_LAUNCH
-    MGC_CHECK(hipGetLastError());
-    if (stream && n_large) {
-      if (low_bits > 64)
-        MGC_CHECK((launch_huge128<true, K128>(reinterpret_cast<K128 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), d_large_list, (u64)n_large, (u64)ng,
-                   FIN_CAP_HASH128, low_bits, d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), reinterpret_cast<K128 *>(d_alt), tr_a, tr_b, st_huge,
-                   (u64)max_sub, (u64)n_keys, d_huge_ws, huge_ws_bytes, (u64)huge_ws_keys, d_error)));
-      else
-        MGC_CHECK((launch_huge128<false, K128>(reinterpret_cast<K128 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), d_large_list, (u64)n_large, (u64)ng,
-                   FIN_CAP_HASH128, low_bits, d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), reinterpret_cast<K128 *>(d_alt), tr_a, tr_b, st_huge,
-                   (u64)max_sub, (u64)n_keys, d_huge_ws, huge_ws_bytes, (u64)huge_ws_keys, d_error)));
-    } else {
-      MGC_CHECK((finish_launch<K128, 1024, 8>(d_keys, d_starts, n_large, low_bits, FIN_CAP_HASH128, 8192, d_cnt_tmp, d_group_distinct, st, d_large_list)));
-    }
-    return hipSuccess;
+  case FinishKeys::WHOLE8:   break;
   }
-  if (key_words == 2) {
-    // 16-byte keys: 256x8 (2048) and 1024x8 (8192) keep LDS at 32 / 128 KiB
-    MGC_CHECK((finish_launch<K128, 256, 8>(d_keys, d_starts, ng, low_bits, 0, 2048, d_cnt_tmp, d_group_distinct, st)));
-    MGC_CHECK((finish_launch<K128, 1024, 8>(d_keys, d_starts, n_large, low_bits, 2048, 8192, d_cnt_tmp, d_group_distinct, st, d_large_list)));
-    return hipSuccess;
+  if (!hash) return FinishPath::U64_SORT;
+  if (f.stream_cap) return FinishPath::U64_STREAM;
+  return f.low_bits >= 32 ? FinishPath::U64_CLAIMED : FinishPath::U64_PACKED;
+}
+
+// the sub-buckets on the oversized list: streamed through a large table, one 1024-thread workgroup each (f.stream, hash paths), or LDS
+// radix passes in the 8192-key instantiation -- the file then holds none above its capacity (the caller checked the largest sub-bucket)
+static hipError_t launch_oversized(const FinishFile &f) {
+  const uint32_t kw = finish_key_words(f.layout);
+  if (f.n_large == 0) return hipSuccess;
+  if (!(f.stream && finish_uses_hash(kw, f.low_bits))) {
+    const uint64_t small_cap = finish_small_capacity(kw, f.low_bits), cap = finish_capacity_for(kw);
+    return kw == 2 ? launch_lds_sort<K128, 1024, 8>(f, f.n_large, small_cap, cap, f.large_list)
+                   : launch_lds_sort<u64, 1024, 8>(f, f.n_large, small_cap, cap, f.large_list);
   }
-  if (finish_uses_hash(key_words, low_bits)) {
-    // <= FIN_CAP_HASH keys: hash-count; larger sub-buckets: streamed, or LDS radix passes in the 8192-key instantiation
-    if (stream_cap) {
-      // the distinct-sized count on whole 8-byte k-mers (k = 24..32, `compress`): 64-bit entries suffix << 12 | count, the bits above the
-      // suffix put back on the way out; sub-buckets with more distinct suffixes than the table holds land on the retry list
-      const uint64_t gmax = 256ull * 10ull;
-      const dim3 sgrid((uint32_t)(ng < gmax ? ng : gmax));
-      if (use_list)
-        hipLaunchKernelGGL((hash_count_stream_kernel<u64, 256, FIN_STREAM_KPC, FIN_STREAM_SLOTS, FIN_STREAM64_DCAP, true, false>), sgrid, dim3(256), 0, st,
-                           reinterpret_cast<u64 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), (u64)ng, (u64)stream_cap, low_bits,
-                           d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), (u64 *)nullptr, tr_a, tr_b, d_nz, nzc,
-                           d_retry_list, reinterpret_cast<u64 *>(d_retry_count));
-      else
-        hipLaunchKernelGGL((hash_count_stream_kernel<u64, 256, FIN_STREAM_KPC, FIN_STREAM_SLOTS, FIN_STREAM64_DCAP, false, false>), sgrid, dim3(256), 0, st,
-                           reinterpret_cast<u64 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), (u64)ng, (u64)stream_cap, low_bits,
-                           d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), (u64 *)nullptr, tr_a, tr_b, (const u32 *)nullptr,
-                           (const u64 *)nullptr, d_retry_list, reinterpret_cast<u64 *>(d_retry_count));
-    } else if (low_bits >= 32) {
-#define MGC_W64_LAUNCH(CAP_, SLOTS_, LIST_, GRID_, MS_)                                                                                  \
-      hipLaunchKernelGGL((hash_countw_kernel<u64, 256, CAP_, SLOTS_, false, LIST_>), dim3(GRID_), dim3(256), 0, st, reinterpret_cast<u64 *>(d_keys), \
-                         reinterpret_cast<const u64 *>(d_starts), (u64)ng, (u64)(MS_), low_bits, d_cnt_tmp,                             \
-                         reinterpret_cast<u64 *>(d_group_distinct), d_nz, nzc, tr_a, tr_b)
-      if (small) {
-        const uint32_t sgrid = ng < 256u * 12u ? (uint32_t)ng : 256u * 12u;
-        if (use_list) MGC_W64_LAUNCH(768, 1024, true, sgrid, 768); else MGC_W64_LAUNCH(768, 1024, false, sgrid, 768);
-      } else {
-        const uint32_t mgrid = ng < 256u * 10u ? (uint32_t)ng : 256u * 10u;
-        if (use_list) MGC_W64_LAUNCH((int)FIN_CAP_HASH, 2048, true, mgrid, FIN_CAP_HASH); else MGC_W64_LAUNCH((int)FIN_CAP_HASH, 2048, false, mgrid, FIN_CAP_HASH);
-      }
-#undef MGC_W64_LAUNCH
-    } else {
-      const uint32_t hgrid = ng < 256u * 14u ? (uint32_t)ng : 256u * 14u;
-      u64 *dbgb = hash_dbg_buffer(hash_dbg);
-#define MGC_HASH_LAUNCH(DBG_, LIST_)                                                                                                     \
-      hipLaunchKernelGGL((hash_count_kernel<256, (int)FIN_CAP_HASH, 2048, DBG_, LIST_, false>), dim3(hgrid), dim3(256), 0, st,           \
-                         reinterpret_cast<u64 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), (u64)ng, (u64)FIN_CAP_HASH, low_bits, \
-                         d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), d_nz, nzc, dbgb, tr_a, tr_b)
-      if (dbgb)          { if (use_list) MGC_HASH_LAUNCH(true, true); else MGC_HASH_LAUNCH(true, false); }
-      else if (use_list) MGC_HASH_LAUNCH(false, true);
-      else               MGC_HASH_LAUNCH(false, false);
-#undef MGC_HASH_LAUNCH
-      MGC_CHECK(hipGetLastError());
-      if (dbgb) hash_dbg_report(st, ng);
-    }
-    MGC_CHECK(hipGetLastError());
-    if (stream && n_large) {
-      // sub-buckets above the small tables: one 1024-thread workgroup each, keys streamed through a large table
-      constexpr size_t B32 = (size_t)(4 + 4) * HUGE_SLOTS32 + (size_t)(4 + 4) * HUGE_CAP32 + 16 * 4;
-      constexpr size_t B64 = (size_t)(8 + 4) * HUGE_SLOTS64 + (size_t)(8 + 4) * HUGE_CAP64 + 16 * 8;
-      if (low_bits < 32)
-        MGC_CHECK((launch_huge<u32, HUGE_CAP32, HUGE_SLOTS32, u64>(reinterpret_cast<u64 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), d_large_list, (u64)n_large,
-                   (u64)ng, (u64)(stream_cap ? stream_cap : FIN_CAP_HASH), low_bits, d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct),
-                   reinterpret_cast<u64 *>(d_alt), tr_a, tr_b, B32, st_huge, (u64)max_sub, (u64)n_keys, d_huge_ws, huge_ws_bytes, (u64)huge_ws_keys, d_error)));
-      else
-        MGC_CHECK((launch_huge<u64, HUGE_CAP64, HUGE_SLOTS64, u64>(reinterpret_cast<u64 *>(d_keys), reinterpret_cast<const u64 *>(d_starts), d_large_list, (u64)n_large,
-                   (u64)ng, (u64)(stream_cap ? stream_cap : FIN_CAP_HASH), low_bits, d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct),
-                   reinterpret_cast<u64 *>(d_alt), tr_a, tr_b, B64, st_huge, (u64)max_sub, (u64)n_keys, d_huge_ws, huge_ws_bytes, (u64)huge_ws_keys, d_error)));
-    } else {
-      MGC_CHECK((finish_launch<u64, 1024, 8>(d_keys, d_starts, n_large, low_bits, FIN_CAP_HASH, FIN_CAP_LARGE, d_cnt_tmp,
-                                             d_group_distinct, st, d_large_list)));
-    }
-    return hipSuccess;
+  const u64 min8 = f.stream_cap ? f.stream_cap : FIN_CAP_HASH;
+  const bool wide = f.low_bits > 64;
+  switch (f.layout) {
+  case FinishKeys::K96:      return wide ? launch_huge<Huge16<true, K96>>(f, FIN_CAP_HASH128) : launch_huge<Huge16<false, K96>>(f, FIN_CAP_HASH128);
+  case FinishKeys::WHOLE16:  return wide ? launch_huge<Huge16<true, K128>>(f, FIN_CAP_HASH128) : launch_huge<Huge16<false, K128>>(f, FIN_CAP_HASH128);
+  case FinishKeys::NARROW32: return launch_huge<Huge8<u32, u32>>(f, min8);
+  case FinishKeys::WHOLE8:   break;
   }
-  MGC_CHECK((finish_launch<u64, 256, 16>(d_keys, d_starts, ng, low_bits, 0, FIN_CAP_SMALL, d_cnt_tmp, d_group_distinct, st)));
-  MGC_CHECK((finish_launch<u64, 1024, 8>(d_keys, d_starts, n_large, low_bits, FIN_CAP_SMALL, FIN_CAP_LARGE, d_cnt_tmp,
-                                         d_group_distinct, st, d_large_list)));
-  return hipSuccess;
+  return f.low_bits < 32 ? launch_huge<Huge8<u32, u64>>(f, min8) : launch_huge<Huge8<u64, u64>>(f, min8);
+}
+
+// Counts every sub-bucket of one file: the sub-buckets up to the small capacity by the path's kernel, the oversized list after it.
+hipError_t launch_finish_file(const FinishFile &f) {
+  if (!finish_file_valid(f)) return hipErrorInvalidValue;
+  const bool small = f.max_sub && f.max_sub <= 768 && f.n_large == 0, wide = f.low_bits > 64, list = f.nonempty_list != nullptr;
+  const FinishPath path = finish_path(f);
+  switch (path) {
+  case FinishPath::K96_HASH:
+    MGC_CHECK((wide ? launch_countw<K96, true>(f, small) : launch_countw<K96, false>(f, small)));
+    break;
+  case FinishPath::K128_HASH:
+    MGC_CHECK((wide ? launch_countw<K128, true>(f, small) : launch_countw<K128, false>(f, small)));
+    break;
+  case FinishPath::K128_SORT:      // 16-byte keys: 256x8 (2048) and 1024x8 (8192) keep LDS at 32 / 128 KiB
+    MGC_CHECK((launch_lds_sort<K128, 256, 8>(f, f.ng, 0, 2048)));
+    break;
+  case FinishPath::NARROW_STREAM: {
+    u64 *dbg = hash_dbg_buffer(f.hash_dbg);                // MGC_HASH_DBG=1: the instrumented instantiations (per-phase cycle stamps)
+    if (list)     MGC_CHECK((launch_stream<u32, FIN_STREAM_SLOTS, FIN_STREAM_DCAP, true, false>(f, f.ng, 256u * 16u, f.nonempty_list, f.nonempty_count, f.retry_list, f.retry_count)));
+    else if (dbg) MGC_CHECK((launch_stream<u32, FIN_STREAM_SLOTS, FIN_STREAM_DCAP, false, true>(f, f.ng, 256u * 16u, nullptr, nullptr, f.retry_list, f.retry_count, dbg)));
+    else          MGC_CHECK((launch_stream<u32, FIN_STREAM_SLOTS, FIN_STREAM_DCAP, false, false>(f, f.ng, 256u * 16u, nullptr, nullptr, f.retry_list, f.retry_count)));
+    break;
+  }
+  case FinishPath::NARROW_MULTI1:
+    // (R = 1: a range is one sub-bucket, the retry list stays empty -- no launch for it: queued behind the other stream's persistent
+    // kernel an empty one still lasted 170 us)
+    MGC_CHECK((launch_multi<1, false>(f, hash_dbg_buffer(f.hash_dbg))));
+    break;
+  case FinishPath::NARROW_MULTI2:
+  case FinishPath::NARROW_MULTI4: {
+    u64 *dbg = hash_dbg_buffer(f.hash_dbg);
+    if (path == FinishPath::NARROW_MULTI4) MGC_CHECK((launch_multi<4, false>(f, dbg)));
+    else if (dbg)                            MGC_CHECK((launch_multi<2, true>(f, dbg)));
+    else                                     MGC_CHECK((launch_multi<2, false>(f, dbg)));
+    // the sub-buckets of ranges above the table (retry list, usually short): one at a time
+    MGC_CHECK(launch_hash_count<true>(f, 256u * 7u, f.retry_list, f.retry_count, nullptr));
+    break;
+  }
+  case FinishPath::NARROW_HASH:
+    MGC_CHECK(launch_hash_count<true>(f, 256u * 14u, f.nonempty_list, f.nonempty_count, hash_dbg_buffer(f.hash_dbg)));
+    break;
+  case FinishPath::U64_STREAM:
+    // the distinct-sized count on whole 8-byte k-mers (k = 24..32, `compress`): 64-bit entries suffix << 12 | count, the bits above the
+    // suffix put back on the way out (MGC_HASH_DBG: no instrumented instantiation)
+    if (list) MGC_CHECK((launch_stream<u64, FIN_STREAM_SLOTS, FIN_STREAM64_DCAP, true, false>(f, f.ng, 256u * 10u, f.nonempty_list, f.nonempty_count, f.retry_list, f.retry_count)));
+    else      MGC_CHECK((launch_stream<u64, FIN_STREAM_SLOTS, FIN_STREAM64_DCAP, false, false>(f, f.ng, 256u * 10u, nullptr, nullptr, f.retry_list, f.retry_count)));
+    break;
+  case FinishPath::U64_CLAIMED:
+    MGC_CHECK((launch_countw<u64, false>(f, small)));
+    break;
+  case FinishPath::U64_PACKED:
+    MGC_CHECK(launch_hash_count<false>(f, 256u * 14u, f.nonempty_list, f.nonempty_count, hash_dbg_buffer(f.hash_dbg)));
+    break;
+  case FinishPath::U64_SORT:
+    MGC_CHECK((launch_lds_sort<u64, 256, 16>(f, f.ng, 0, FIN_CAP_SMALL)));
+    break;
+  }
+  return launch_oversized(f);
 }
 
 // the retry list of hash_count_stream_kernel: the same kernel with a table no sub-bucket of up to FIN_CAP_STREAM keys can overflow
-hipError_t launch_finish_retry(void *d_keys32, const uint64_t *d_starts, uint64_t ng, uint32_t low_bits, uint32_t *d_cnt_tmp,
-                               uint64_t *d_group_distinct, uint32_t tr_a, uint32_t tr_b, const uint32_t *d_retry_list,
-                               const uint64_t *d_retry_count, uint64_t n_retry, uint64_t stream_cap, hipStream_t st, bool narrow, void *d_alt) {
+hipError_t launch_finish_retry(const FinishFile &f, uint64_t n_retry) {
+  const bool narrow = f.layout == FinishKeys::NARROW32;
   if (n_retry == 0) return hipSuccess;
-  if (!finish_stream_ok(1, low_bits, narrow) || stream_cap == 0 || stream_cap > FIN_CAP_STREAM) return hipErrorInvalidValue;
+  if (!finish_stream_ok(1, f.low_bits, narrow) || f.stream_cap == 0 || f.stream_cap > FIN_CAP_STREAM) return hipErrorInvalidValue;
   if (!narrow) {
     // whole 8-byte k-mers: a table for 4094 distinct 64-bit entries does not fit a workgroup's static LDS -- the sub-buckets on the
     // list go through the streaming kernel of the oversized ones, one workgroup each (huge_min = 0: every listed sub-bucket)
-    if (!d_alt) return hipErrorInvalidValue;
-    constexpr size_t B32 = (size_t)(4 + 4) * HUGE_SLOTS32 + (size_t)(4 + 4) * HUGE_CAP32 + 16 * 4;
-    constexpr size_t B64 = (size_t)(8 + 4) * HUGE_SLOTS64 + (size_t)(8 + 4) * HUGE_CAP64 + 16 * 8;
-    static bool rattr = false;
-    if (!rattr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hash_count_huge_kernel<u32, 1024, HUGE_CAP32, HUGE_SLOTS32>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)B32);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hash_count_huge_kernel<u64, 1024, HUGE_CAP64, HUGE_SLOTS64>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)B64);
-      rattr = true;
-    }
-    if (low_bits < 32)
-      hipLaunchKernelGGL((hash_count_huge_kernel<u32, 1024, HUGE_CAP32, HUGE_SLOTS32>), dim3((uint32_t)n_retry), dim3(1024), B32, st,
-                         reinterpret_cast<u64 *>(d_keys32), reinterpret_cast<const u64 *>(d_starts), d_retry_list, (u64)ng, (u64)0, low_bits,
-                         d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), reinterpret_cast<u64 *>(d_alt), tr_a, tr_b);
-    else
-      hipLaunchKernelGGL((hash_count_huge_kernel<u64, 1024, HUGE_CAP64, HUGE_SLOTS64>), dim3((uint32_t)n_retry), dim3(1024), B64, st,
-                         reinterpret_cast<u64 *>(d_keys32), reinterpret_cast<const u64 *>(d_starts), d_retry_list, (u64)ng, (u64)0, low_bits,
-                         d_cnt_tmp, reinterpret_cast<u64 *>(d_group_distinct), reinterpret_cast<u64 *>(d_alt), tr_a, tr_b);
-    return hipGetLastError();
+    if (!f.alt) return hipErrorInvalidValue;
+    return f.low_bits < 32 ? launch_huge_mode<Huge8<u32, u64>, 0>(f, f.retry_list, (uint32_t)n_retry, 0, 0, HugeSliced(), f.st)
+                           : launch_huge_mode<Huge8<u64, u64>, 0>(f, f.retry_list, (uint32_t)n_retry, 0, 0, HugeSliced(), f.st);
   }
   static_assert(FIN_STREAM_RETRY_DCAP >= (int)FIN_CAP_STREAM, "the retry table holds every suffix of a sub-bucket");
-  const uint64_t gmax = 256ull * 2ull;
-  hipLaunchKernelGGL((hash_count_stream_kernel<u32, 256, FIN_STREAM_KPC, FIN_STREAM_RETRY_SLOTS, FIN_STREAM_RETRY_DCAP, true, false>),
-                     dim3((uint32_t)(n_retry < gmax ? n_retry : gmax)), dim3(256), 0, st, reinterpret_cast<u32 *>(d_keys32),
-                     reinterpret_cast<const u64 *>(d_starts), (u64)ng, (u64)stream_cap, low_bits, d_cnt_tmp,
-                     reinterpret_cast<u64 *>(d_group_distinct), (u64 *)nullptr, tr_a, tr_b, d_retry_list,
-                     reinterpret_cast<const u64 *>(d_retry_count), (u32 *)nullptr, (u64 *)nullptr);
-  return hipGetLastError();
+  return launch_stream<u32, FIN_STREAM_RETRY_SLOTS, FIN_STREAM_RETRY_DCAP, true, false>(f, n_retry, 256u * 2u, f.retry_list, f.retry_count, nullptr, nullptr);
 }
 
 bool     finish_stream_ok(uint32_t key_words, uint32_t low_bits, bool narrow) { return key_words == 1 && low_bits >= 8 && low_bits <= (narrow ? 20u : 52u); }
@@ -3092,30 +3019,6 @@ hipError_t launch_block_offsets(const void *d_unique, uint64_t n_distinct, uint3
   return hipGetLastError();
 }
 
-
-
-// Every MGC_* switch of the count path, from the environment (mgc_device.h: once per session / per bare-operator call)
-Switches read_switches() {
-  Switches sw;
-  auto off = [](const char *n) { const char *e = getenv(n); return e && e[0] == '0'; };
-  auto on1 = [](const char *n) { const char *e = getenv(n); return e && e[0] == '1'; };
-  auto num = [](const char *n, uint64_t d) { const char *e = getenv(n); return (e && *e) ? strtoull(e, nullptr, 10) : d; };
-  sw.fine_hist = !off("MGC_FINE_HIST"); sw.hpc_msd = !off("MGC_HPC_MSD"); sw.hpc_digits = !off("MGC_HPC_DIGITS");
-  sw.const_k = !off("MGC_KMER_CONST_K"); sw.narrow = !off("MGC_NARROW"); sw.wide_msd = !off("MGC_WIDE_MSD");
-  sw.group_pipe = !off("MGC_GROUP_PIPE"); sw.soa5 = !off("MGC_SOA5"); sw.k96 = !off("MGC_K96"); sw.finish = !off("MGC_FINISH");
-  sw.nolist = on1("MGC_FINISH_NOLIST");
-  sw.finish_trace = getenv("MGC_FINISH_TRACE") != nullptr; sw.group_dbg = getenv("MGC_GROUP_DBG") != nullptr; sw.hash_dbg = getenv("MGC_HASH_DBG") != nullptr;
-  { const char *e = getenv("MGC_HASH_MULTI"); sw.hash_multi = (e && *e) ? atoi(e) : -1; }
-  { const char *e = getenv("MGC_HASH_STREAM"); sw.hash_stream = (e && *e) ? atoi(e) : -1; }
-  sw.min_top = (uint32_t)num("MGC_FINISH_MIN_TOP", 0);
-  sw.finish_target = num("MGC_FINISH_TARGET", 0);
-  sw.stream_max = num("MGC_STREAM_MAX", (uint64_t)1 << 22);
-  sw.bucket_bases = num("MGC_BUCKET_BASES", 0);
-  sw.huge_streams = (uint32_t)num("MGC_HUGE_STREAMS", 4);
-  sw.huge_slices = !off("MGC_HUGE_SLICES");
-  sw.pass_stagger = (uint32_t)num("MGC_PASS_STAGGER", 0);
-  return sw;
-}
 
 hipError_t warm_finish() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&store_u64_kernel)); }
 
