@@ -14,12 +14,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmeryl_gpu_count.so")
 SOURCES = ["mgc_kmer.hip", "mgc_sort.hip", "mgc_scan.hip", "mgc_finish.hip", "mgc_misc.hip", "mgc_parse.hip",
-           "mgc_encode.hip", "mgc_decode.hip", "mgc_merge.hip", "mgc_lookup.hip", "mgc_filter.hip", "mgc_import.hip",
-           "mgc_api.cpp", "mgc_import.cpp", "mgc_count.cpp", "mgc_stream.cpp", "mgc_runs.cpp", "mgc_node.cpp", "meryl_db.cpp", "meryl_seq.cpp"]
-HEADERS = ["mgc_device.h", "mgc_common.hpp", "mdb_layout.h", "mgc_session.hpp", "mgc_runs.hpp", "mgc_lookup_dev.hpp", "mgc_import_dev.hpp",
+           "mgc_encode.hip", "mgc_decode.hip", "mgc_merge.hip", "mgc_lookup.hip", "mgc_filter.hip", "mgc_import.hip", "mgc_analyze.hip",
+           "mgc_api.cpp", "mgc_import.cpp", "mgc_analyze.cpp", "mgc_count.cpp", "mgc_stream.cpp", "mgc_runs.cpp", "mgc_node.cpp", "meryl_db.cpp", "meryl_seq.cpp"]
+HEADERS = ["mgc_device.h", "mgc_common.hpp", "mdb_layout.h", "mgc_session.hpp", "mgc_runs.hpp", "mgc_lookup_dev.hpp", "mgc_import_dev.hpp", "mgc_analyze_dev.hpp",
            os.path.join("..", "..", "include", "meryl_gpu_count.h"),
            os.path.join("..", "..", "include", "meryl_db.h"), os.path.join("..", "..", "include", "meryl_seq.h"),
-           os.path.join("..", "..", "include", "meryl_lookup.h"), os.path.join("..", "..", "include", "meryl_import.h")]
+           os.path.join("..", "..", "include", "meryl_lookup.h"), os.path.join("..", "..", "include", "meryl_import.h"),
+           os.path.join("..", "..", "include", "meryl_analyze.h")]
 OBJDIR = os.path.join(HERE, "build")
 # -no-hip-rt: the library carries no DT_NEEDED on a particular libamdhip64; it binds to the
 # HIP runtime already in the process (torch's bundled one under Python -- two HIP/HSA runtimes
@@ -130,6 +131,27 @@ def build_import_cli(force=False, verbose=False):
     return IMPORT_CLI
 
 
+ANALYZE_CLI = os.path.join(HERE, "bin", "meryl-analyze")
+
+
+def build_analyze_cli(force=False, verbose=False):
+    """`meryl-analyze` (meryl_amd/bin/meryl-analyze: -gc / -ga / -gt histograms of a database): links the library and the system HIP runtime."""
+    src = os.path.join(CSRC, "meryl_analyze_main.cpp")
+    if (not force and os.path.exists(ANALYZE_CLI) and os.path.getmtime(ANALYZE_CLI) >= os.path.getmtime(src)
+            and os.path.getmtime(ANALYZE_CLI) >= os.path.getmtime(LIB)):
+        return ANALYZE_CLI
+    os.makedirs(os.path.dirname(ANALYZE_CLI), exist_ok=True)
+    rocm_lib = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
+    tmp = "%s.tmp%d" % (ANALYZE_CLI, os.getpid())
+    cmd = [hipcc(), "-O2", "-std=c++17", "-pthread", src, "-o", tmp, "-L" + HERE, "-lmeryl_gpu_count",
+           "-Wl,-rpath,$ORIGIN/..", "-L" + rocm_lib, "-lamdhip64", "-Wl,-rpath," + rocm_lib, "-lz"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    os.replace(tmp, ANALYZE_CLI)
+    return ANALYZE_CLI
+
+
 def build(force=False, verbose=False):
     """Compile every HIP/C++ source for gfx950 (one object per source, rebuilt only when the source or a
     header changed, in parallel) and link libmeryl_gpu_count.so (and the CLI).  Returns the library path."""
@@ -137,6 +159,7 @@ def build(force=False, verbose=False):
         build_cli(False, verbose)
         build_lookup_cli(False, verbose)
         build_import_cli(False, verbose)
+        build_analyze_cli(False, verbose)
         return LIB
     os.makedirs(OBJDIR, exist_ok=True)
     todo = _stale_objects(force)
@@ -164,6 +187,7 @@ def build(force=False, verbose=False):
     build_cli(True, verbose)
     build_lookup_cli(True, verbose)
     build_import_cli(True, verbose)
+    build_analyze_cli(True, verbose)
     return LIB
 
 

@@ -1,4 +1,4 @@
-"""ctypes binding of include/meryl_gpu_count.h (and meryl_db.h, meryl_lookup.h, meryl_seq.h, meryl_import.h).
+"""ctypes binding of include/meryl_gpu_count.h (and meryl_db.h, meryl_lookup.h, meryl_seq.h, meryl_import.h, meryl_analyze.h).
 
 Loads meryl_amd/libmeryl_gpu_count.so and fails loudly when it is missing or
 an expected symbol is absent -- there is no Python/CPU fallback for any compute
@@ -43,6 +43,9 @@ SYMBOLS = (
     "mgc_dev_import_parse_state_bytes", "mgc_dev_import_parse_workspace_bytes", "mgc_dev_import_parse_begin", "mgc_dev_import_parse_count",
     "mgc_dev_import_parse", "mgc_dev_sort_pairs_workspace_bytes", "mgc_dev_sort_pairs", "mgc_dev_reduce_pairs_workspace_bytes",
     "mgc_dev_reduce_pairs_count", "mgc_dev_reduce_pairs_emit", "mgc_import_file", "mgc_import_text", "mgc_import_error",
+    # include/meryl_analyze.h
+    "mgc_dev_analyze_scores", "mgc_analyze_open", "mgc_analyze_close", "mgc_analyze_add_device", "mgc_analyze_add_database",
+    "mgc_analyze_result_rows", "mgc_analyze_result", "mgc_analyze_write", "mgc_analyze_get_info", "mgc_analyze_error",
     "msr_open", "msr_read_text", "msr_close", "msr_last_error", "msr_load_bases", "msr_load_stream", "msr_format", "msr_is_compressed", "msr_guess_number_of_kmers",
 )
 
@@ -219,6 +222,16 @@ class ImportInfo(ctypes.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
+class AnalyzeInfo(ctypes.Structure):
+    """mgc_analyze_info (include/meryl_analyze.h)"""
+    _fields_ = [("n_kmers", ctypes.c_uint64), ("n_files", ctypes.c_uint64), ("n_overflow_kmers", ctypes.c_uint64),
+                ("n_overflow_retries", ctypes.c_uint64), ("decode_ms", ctypes.c_double), ("hist_ms", ctypes.c_double),
+                ("overflow_ms", ctypes.c_double), ("read_s", ctypes.c_double), ("total_s", ctypes.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class IndexEntry(ctypes.Structure):
@@ -434,6 +447,16 @@ def lib():
     sig("mgc_import_file", i32, ctypes.c_char_p, u32, i32, ctypes.c_char_p, i32, i32, P(ImportInfo))
     sig("mgc_import_text", i32, ctypes.c_char_p, u64, u32, i32, ctypes.c_char_p, i32, i32, P(ImportInfo))
     sig("mgc_import_error", ctypes.c_char_p)
+    sig("mgc_dev_analyze_scores", i32, vp, u64, u32, i32, vp, vp, vp)
+    sig("mgc_analyze_open", i32, u32, i32, i32, P(vp))
+    sig("mgc_analyze_close", None, vp)
+    sig("mgc_analyze_add_device", i32, vp, vp, vp, u64, vp)
+    sig("mgc_analyze_add_database", i32, vp, ctypes.c_char_p, i32)
+    sig("mgc_analyze_result_rows", i32, vp, i32, P(u64))
+    sig("mgc_analyze_result", i32, vp, i32, vp, vp, vp)
+    sig("mgc_analyze_write", i32, vp, ctypes.c_char_p)
+    sig("mgc_analyze_get_info", i32, vp, P(AnalyzeInfo))
+    sig("mgc_analyze_error", ctypes.c_char_p)
     sig("msr_open", vp, ctypes.c_char_p)
     sig("msr_close", None, vp)
     sig("msr_read_text", ctypes.c_int64, vp, vp, u64)
