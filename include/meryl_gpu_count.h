@@ -409,7 +409,7 @@ typedef struct mgc_profile {
   double   total_ms;
   double   merge_ms;               /* out-of-core: device merges of batch results into the running result (all batches) */
   uint32_t n_batches;              /* batches the input was counted in (1 = single pass) */
-  uint32_t reserved;
+  uint32_t narrow_digit_widths;    /* bit b set: a narrowed file's first grouping pass took a digit of b bits (8: the 256-counter kernel, 9: the 512-counter one) */
   /* the same pass launches split by position: [0] a file's first pass, [1] its later passes -- with their ALGORITHMIC
    * bytes (key bytes read + written; narrowed files: 8 + 4 in the first pass, 4 + 4 in the second) */
   double   pass_ms[2];

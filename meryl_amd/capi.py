@@ -96,7 +96,7 @@ class Profile(ctypes.Structure):
         ("total_ms", ctypes.c_double),
         ("merge_ms", ctypes.c_double),
         ("n_batches", ctypes.c_uint32),
-        ("reserved", ctypes.c_uint32),
+        ("narrow_digit_widths", ctypes.c_uint32),
         ("pass_ms", ctypes.c_double * 2),
         ("pass_bytes", ctypes.c_uint64 * 2),
         ("pass_keys", ctypes.c_uint64 * 2),

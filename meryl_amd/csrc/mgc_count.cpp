@@ -1047,6 +1047,7 @@ void Count::collect_profile() {
       prof.pass_ms[pi] += ms;
       prof.pass_launches[pi]++;
       prof.pass_keys[pi] += x.size;
+      if (x.narrowed && !p) prof.narrow_digit_widths |= 1u << (x.tr_a ? x.tr_a : x.sp.pass_bits[0]);
       prof.pass_bytes[pi] += x.size * (x.narrowed ? (p ? 8u : (soa_hi_mask ? 9u : 12u)) : (x.k96_passes ? 24u : 2u * kbytes));
     }
   }

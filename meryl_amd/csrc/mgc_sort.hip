@@ -22,6 +22,7 @@
 #include "mgc_common.hpp"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace mgc {
 
@@ -374,10 +375,11 @@ void radix_scatter_kernel(const K *__restrict__ in, K *__restrict__ out, u64 n, 
 // at the d_lo region boundaries of pass 1's output (region table below), every region's last tile
 // being partial.  Persistent workgroups, ticket one tile ahead, next tile's keys fetched behind the
 // look-back and the write-out, as in radix_scatter_pipe_kernel.
-template <typename K, int RB, int BLOCK, int KPT>
+// XB: bytes per key of the exchange buffer -- sizeof(K) for whole keys; a NARROWING pass exchanges what it writes (group_xb below)
+template <typename K, int RB, int BLOCK, int KPT, int XB = (int)sizeof(K)>
 struct GroupSmem {
   static constexpr int R = 1 << RB, NW = BLOCK / 64, TILE = BLOCK * KPT;
-  static constexpr size_t OFF_HIST  = (size_t)TILE * sizeof(K);       // u32[R]
+  static constexpr size_t OFF_HIST  = ((size_t)TILE * XB + 15) / 16 * 16;   // u32[R]
   static constexpr size_t OFF_GBASE = OFF_HIST + (size_t)R * 4;       // u64[R]
   static constexpr size_t OFF_DBASE = OFF_GBASE + (size_t)R * 8;      // u32[R]
   static constexpr size_t OFF_CNT   = OFF_DBASE + (size_t)R * 4;      // u32[R]
@@ -409,6 +411,11 @@ void group_regions_kernel(const u64 *__restrict__ gbase_prev, u64 n, u32 tile, u
 // the finish move half the bytes.
 template <typename K, bool NARROW> struct GroupOut { typedef K type; };
 template <> struct GroupOut<u64, true> { typedef u32 type; };
+// A narrowing pass exchanges what it writes: a key goes through LDS as its 32-bit narrowed word plus its digit of this pass -- u32[TILE]
+// words, then the digits, one byte each for digits of up to eight bits (5 bytes per key; the judged plan), 16 bits each for nine-bit
+// digits (6 bytes per key) -- instead of the whole 8-byte key, of which 36 bits are live at k = 21.  Every plan that narrows has room
+// for that (the word is what leaves the kernel anyway), so no narrowing instantiation keeps the whole-key exchange.
+template <typename K, int RB, bool NARROW> constexpr int group_xb() { return NARROW ? (RB <= 8 ? 5 : 6) : (int)sizeof(K); }
 
 // HIST2: the pass also takes the histogram of ANOTHER digit (the next pass's) of the keys it reads -- 512 LDS counters per
 // workgroup, flushed with global atomics at the end -- so that nobody has to read the keys for it.
@@ -431,7 +438,7 @@ struct GroupExtra { u32 digit_bits /* NARROW */; u32 shift2, mask2; u64 *ghist2 
 // 4096 ranks of the twelve bits a digit is taken from lie in 8 KiB of LDS behind the tile, a digit is one 16-bit LDS read.
 template <typename K, int RB, int BLOCK, int KPT, bool DBG, bool NARROW = false, bool HIST2 = false, bool SOA = false, int PIPE = 0 /* 1: the next fetch before the write-out; 2: after it */,
           int HPCD = 0 /* 1: both digits are dense ranks; 2: only this pass's (the other digit, HIST2's, is a plain bit field) */>
-__global__ __launch_bounds__(BLOCK, (GroupSmem<K, RB, BLOCK, KPT>::MIN_WAVES_PER_SIMD))
+__global__ __launch_bounds__(BLOCK, (GroupSmem<K, RB, BLOCK, KPT, group_xb<K, RB, NARROW>()>::MIN_WAVES_PER_SIMD))
 void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::type *__restrict__ out, u64 n, u32 shift, u32 dmask,
                         const u64 *__restrict__ gbase, u64 *__restrict__ status, u32 *__restrict__ ticket,
                         u32 *__restrict__ error_flag, u64 num_tiles_plain,
@@ -441,13 +448,18 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
   const u32 digit_bits = ex.digit_bits;
   __shared__ u32 s_h2[HIST2 ? RS_MAX_RADIX : 1];
   if (HIST2) { for (u32 i = threadIdx.x; i < (u32)RS_MAX_RADIX; i += BLOCK) s_h2[i] = 0; }
-  using SM = GroupSmem<K, RB, BLOCK, KPT>;
+  using SM = GroupSmem<K, RB, BLOCK, KPT, group_xb<K, RB, NARROW>()>;
   using KO = KeyOps<K>;
   constexpr int R = SM::R, TILE = SM::TILE, G = R / 2;
+  static_assert(!NARROW || !HPCD, "dense-rank digits keep whole keys");
   constexpr int WALK = (sizeof(K) == 4 || PIPE) ? 8 : 16;      // 32 words per thread leave registers for eight granules in flight, not sixteen (no spills)
   static_assert(BLOCK >= RS_MAX_RADIX && G % 64 == 0 && TILE <= 65536, "one thread per region/digit; 16-bit ranks");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   K   *s_keys  = reinterpret_cast<K *>(smem);
+  // NARROW: the exchange buffer holds the narrowed words and, behind them, the digits of this pass
+  using DT = typename std::conditional<(RB <= 8), uint8_t, unsigned short>::type;
+  u32 *s_words = reinterpret_cast<u32 *>(smem);
+  DT  *s_dig   = reinterpret_cast<DT *>(smem + (NARROW ? (size_t)TILE * 4 : 0));
   u32 *s_hist  = reinterpret_cast<u32 *>(smem + SM::OFF_HIST);
   u64 *s_gbase = reinterpret_cast<u64 *>(smem + SM::OFF_GBASE);
   u32 *s_dbase = reinterpret_cast<u32 *>(smem + SM::OFF_DBASE);
@@ -506,6 +518,34 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
     return w * (u32)(64 * KPT) + ((u32)(j / VEC) * 64u + lane) * (u32)VEC + (u32)(j % VEC);
   };
   K keys[KPT];
+  // NARROW: once put together a key lives as word + digit -- narrowed ONCE; ranking, exchange and write-out take the stored digit -- the
+  // digits DPR to a register: 24 keys per thread are 24 + 6 registers at eight-bit digits, not 48 (keys[] then only holds what a
+  // fetch that is not PIPE's has brought in, until the ranking narrows it)
+  constexpr int DPR = (RB <= 8) ? 4 : 2, DBITS = 32 / DPR;
+  static_assert(!NARROW || KPT % DPR == 0, "whole registers of digits");
+  u32 wd[NARROW ? KPT : 1], dgp[NARROW ? KPT / DPR : 1];
+  if constexpr (NARROW) {
+#pragma unroll
+    for (int j = 0; j < KPT; j++) wd[j] = 0u;
+#pragma unroll
+    for (int j = 0; j < KPT / DPR; j++) dgp[j] = 0u;
+  }
+  // (32-bit operations on the key's halves -- one v_alignbit_b32 per field -- instead of 64-bit shifts on register pairs; the shift
+  // amounts are the same in all lanes.  sort_plan_narrows: shift <= 32, so the bits below the digit come from the low half alone.)
+  auto bits_from = [&](u32 hi, u32 lo, u32 at) __attribute__((always_inline)) -> u32 {      // bits at .. at + 31 of hi:lo
+    return at < 32u ? __builtin_amdgcn_alignbit(hi, lo, at) : (at < 64u ? hi >> (at - 32u) : 0u);
+  };
+  const u32 low_mask = shift < 32u ? (1u << shift) - 1u : 0xFFFFFFFFu;
+  auto narrow_to = [&](int j, u32 hi, u32 lo) __attribute__((always_inline)) {
+    const u32 up = bits_from(hi, lo, shift + digit_bits);
+    wd[j] = (shift < 32u ? up << shift : 0u) | (lo & low_mask);
+    const u32 d = bits_from(hi, lo, shift) & dmask;
+    if (j % DPR) dgp[j / DPR] |= d << (DBITS * (j % DPR));
+    else         dgp[j / DPR]  = d;
+  };
+  auto dig_of = [&](int j) __attribute__((always_inline)) -> u32 { return (dgp[j / DPR] >> (DBITS * (j % DPR))) & ((1u << DBITS) - 1u); };
+  // HIST2 of a narrowing pass counts the other digit from the WORDS: below this pass's digit it sits where it sat in the key
+  const u32 shift2w = (ex.shift2 >= shift + digit_bits) ? ex.shift2 - digit_bits : ex.shift2;
   auto fetch = [&](u64 kb, u32 nv) __attribute__((always_inline)) {
     if constexpr (SOA) {
       struct __attribute__((aligned(4))) LVec { u32 v[4]; };
@@ -596,7 +636,10 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
 #pragma unroll
       for (int g = 0; g < KPT / 4; g++)
 #pragma unroll
-        for (int c = 0; c < 4; c++) keys[g * 4 + c] = (K)((u64)raw[g * 5 + c] | ((u64)((raw[g * 5 + 4] >> (8 * c)) & hm) << 32));
+        for (int c = 0; c < 4; c++) {
+          if constexpr (NARROW) narrow_to(g * 4 + c, (raw[g * 5 + 4] >> (8 * c)) & hm, raw[g * 5 + c]);
+          else                  keys[g * 4 + c] = (K)((u64)raw[g * 5 + c] | ((u64)((raw[g * 5 + 4] >> (8 * c)) & hm) << 32));
+        }
     } else if constexpr (PIPE) {
 #pragma unroll
       for (int j = 0; j < KPT; j++) keys[j] = (K)raw[j];
@@ -668,7 +711,8 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
     for (int j = 0; j < KPT; j++) {
       u32 r = 0, d = 0;
       if (idx_of(j) < nv) {
-        d = dig(keys[j]);
+        if constexpr (NARROW) { if constexpr (!PIPE) narrow_to(j, (u32)((u64)keys[j] >> 32), (u32)(u64)keys[j]); d = dig_of(j); }
+        else d = dig(keys[j]);
         r = atomicAdd(&s_hist[d], 1u);
       }
       if (j & 1) ranks[j / 2] |= r << 16;
@@ -683,6 +727,14 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
     const u32 excl = block_excl_scan<BLOCK, u32>(count, s_tmp, &tile_total);
     if (tid < (u32)R) { s_cnt[tid] = count; s_dbase[tid] = excl; }
     __syncthreads();                                      // (C)
+    if constexpr (NARROW) {
+      // the exchange takes its digits, its counter addresses and its in-tile tests afresh: kept from the ranking they are a vector
+      // register (the address) and a scalar pair (the test) per key, held across the scan -- with 20 and 24 keys per thread that spills
+      asm volatile("" : "+v"(tid));
+      lane = tid & 63u; w = tid >> 6;
+#pragma unroll
+      for (int j = 0; j < KPT / DPR; j++) asm volatile("" : "+v"(dgp[j]));
+    }
 
     u64 *mine = status + tile * (u64)G + tid;
     u32 c0 = 0, c1 = 0;
@@ -696,9 +748,11 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
       if (idx_of(j) < nv) {
         u32 d;
         if constexpr (HPCD) d = (j & 1) ? (dgs[j / 2] >> 16) : (dgs[j / 2] & 0xFFFFu);
+        else if constexpr (NARROW) d = dig_of(j);
         else d = dig(keys[j]);
         const u32 r = (j & 1) ? (ranks[j / 2] >> 16) : (ranks[j / 2] & 0xFFFFu);
-        s_keys[s_dbase[d] + r] = keys[j];
+        if constexpr (NARROW) { const u32 pos = s_dbase[d] + r; s_words[pos] = wd[j]; s_dig[pos] = (DT)d; }
+        else s_keys[s_dbase[d] + r] = keys[j];
       }
     }
     u64 nkb = 0; u32 nnv = 0;
@@ -751,7 +805,10 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
       // the waves that do not walk would only wait now: they count the other digit of the tile's keys (in LDS, in digit
       // order since the exchange) -- LDS work in the shadow of the look-back
       if constexpr (HIST2) {
-        for (u32 i = tid - (u32)G; i < nv; i += (u32)(BLOCK - G)) atomicAdd(&s_h2[dig2(s_keys[i])], 1u);
+        for (u32 i = tid - (u32)G; i < nv; i += (u32)(BLOCK - G)) {
+          if constexpr (NARROW) atomicAdd(&s_h2[(s_words[i] >> shift2w) & ex.mask2], 1u);
+          else                  atomicAdd(&s_h2[dig2(s_keys[i])], 1u);
+        }
       }
       if (tid == (u32)BLOCK - 1u) s_tmp[34] = tk_pre;
     } else {
@@ -774,10 +831,12 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
     for (int j = 0; j < KPT; j++) {
       const u32 i = (u32)j * BLOCK + tid;
       if (i < nv) {
-        const K   key = s_keys[i];
-        const u32 d   = dig(key);
-        if constexpr (NARROW) out[s_gbase[d] + (u64)i] = (u32)(((key >> (shift + digit_bits)) << shift) | (key & ((1ull << shift) - 1ull)));
-        else                  out[s_gbase[d] + (u64)i] = key;
+        if constexpr (NARROW) out[s_gbase[s_dig[i]] + (u64)i] = s_words[i];
+        else {
+          const K   key = s_keys[i];
+          const u32 d   = dig(key);
+          out[s_gbase[d] + (u64)i] = key;
+        }
       }
     }
     PK_STAMP(4);
@@ -1048,9 +1107,18 @@ void narrow_mid_kernel(SortHeader *__restrict__ hdr, u64 n, u32 tile, u64 *__res
 }
 
 // per-file scratch of the batched form: [status of pass A][status of pass B][region table]
-constexpr uint64_t NARROW_TILE0 = 16384, NARROW_TILE1 = 24576;   // keys per tile of the first / second pass (launch_group_narrow)
-constexpr uint32_t NARROW_TILE0_CYCLES = 31000;                 // a first-pass tile's time (MGC_GROUP_DBG): the staggered groups share it
+// Keys per tile of the first / second pass (launch_group_narrow).  The first pass exchanges 5 or 6 bytes per key (group_xb), so the LDS
+// has room for 24576 keys; the register file has it only where the next tile waits in the form it has in memory (PIPE: 30 registers
+// for 24 keys of the 5-byte layout) -- the forms that fetch whole 8-byte keys inside the look-back (MGC_GROUP_PIPE=0, MGC_SOA5=0, the
+// owner side of a sharded count) hold 48 registers of them beside the words and spill at 20 and at 24 keys per thread: they keep 16.
+#ifndef MGC_NARROW_KPT0
+#define MGC_NARROW_KPT0 24                                       // keys per thread of the pipelined first pass (A/B builds: 16, 20)
+#endif
+constexpr uint64_t NARROW_TILE0 = 16384, NARROW_TILE0P = 1024ull * MGC_NARROW_KPT0, NARROW_TILE1 = 24576;
+// a pipelined first-pass tile's time, which the staggered groups share: 31000 cycles measured at 16384 keys (MGC_GROUP_DBG), scaled
+constexpr uint32_t NARROW_TILE0_CYCLES = 31000u * MGC_NARROW_KPT0 / 16u;
 size_t narrow_scratch_bytes(uint64_t n) {
+  static_assert(NARROW_TILE0 <= NARROW_TILE0P, "rows for the smaller of the first pass's tiles");
   const uint64_t tiles0 = (n + NARROW_TILE0 - 1) / NARROW_TILE0, tiles1_max = (n + NARROW_TILE1 - 1) / NARROW_TILE1 + RS_MAX_RADIX + 1;
   return (size_t)(tiles0 + tiles1_max) * (RS_MAX_RADIX / 2) * sizeof(u64) + (size_t)(RS_MAX_RADIX + 2) * 16 + 512;
 }
@@ -1083,11 +1151,15 @@ hipError_t launch_group_narrow(void *d_keys, void *d_alt, uint64_t n, const Sort
                                uint32_t *d_error, uint64_t *d_sub_starts, hipStream_t st, hipEvent_t *pass_events,
                                void *d_prepared, void *d_scratch, uint32_t *tr_a, uint32_t *tr_b, uint32_t soa_hi_mask, bool group_dbg, bool pipe, uint32_t stagger) {
   if (!sort_plan_narrows(plan, n, 1) || ws_bytes < sort_workspace_bytes(n)) return hipErrorInvalidValue;
-  constexpr int RB = 9, BLOCK = 1024, KPT0 = 16, KPT1 = 24, R = 1 << RB;
-  using GS0 = GroupSmem<u64, RB, BLOCK, KPT0>;
+  constexpr int RB = 9, BLOCK = 1024, KPT0 = 16, KPT0P = MGC_NARROW_KPT0, KPT1 = 24, R = 1 << RB;
+  using GS0  = GroupSmem<u64, RB, BLOCK, KPT0, group_xb<u64, RB, true>()>;
+  using GS0P = GroupSmem<u64, RB, BLOCK, KPT0P, group_xb<u64, RB, true>()>;  // (words + 16-bit digits: 144 + 10 KiB at 24576 keys)
+  static_assert(GS0P::BYTES + RS_MAX_RADIX * 4 <= 160 * 1024 && GS0P::WG_PER_CU == 1 && GS0::WG_PER_CU == 1, "the first pass's tile and its low-digit counters fit the LDS");
   using GS1 = GroupSmem<u32, RB, BLOCK, KPT1>;
-  constexpr uint64_t TILE0 = (uint64_t)BLOCK * KPT0, TILE1 = (uint64_t)BLOCK * KPT1;
-  static_assert(TILE0 == NARROW_TILE0 && TILE1 == NARROW_TILE1, "narrow_scratch_bytes");
+  constexpr uint64_t TILE1 = (uint64_t)BLOCK * KPT1;
+  static_assert((uint64_t)BLOCK * KPT0 == NARROW_TILE0 && (uint64_t)BLOCK * KPT0P == NARROW_TILE0P && TILE1 == NARROW_TILE1, "narrow_scratch_bytes");
+  const bool msd = d_prepared != nullptr && d_scratch != nullptr;
+  const uint64_t TILE0 = (msd && soa_hi_mask && pipe) ? NARROW_TILE0P : NARROW_TILE0;   // (the pipelined forms, instrumented or not)
   static bool attr_done = false;
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, RB, BLOCK, KPT0, false, true, false>),
@@ -1098,7 +1170,6 @@ hipError_t launch_group_narrow(void *d_keys, void *d_alt, uint64_t n, const Sort
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS1::BYTES);
     attr_done = true;
   }
-  const bool msd = d_prepared != nullptr && d_scratch != nullptr;
   const uint64_t tile1 = TILE1;    // (28 words per thread -- 28672-word tiles, the most the register file takes -- measured equal: r06_ab_runs.txt)
   const uint64_t tiles0 = (n + TILE0 - 1) / TILE0, tiles1_max = (n + tile1 - 1) / tile1 + RS_MAX_RADIX + 1;
   SortHeader *hdr;
@@ -1152,14 +1223,14 @@ hipError_t launch_group_narrow(void *d_keys, void *d_alt, uint64_t n, const Sort
   if (dbg && dbg_buf && soa_hi_mask) {                     // the shipped first pass, instrumented: 5-byte layout, the fetch a whole tile ahead (or not)
     static bool dsattr = false;
     if (!dsattr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, RB, BLOCK, KPT0, true, true, true, true, 2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS0::BYTES);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, RB, BLOCK, KPT0P, true, true, true, true, 2>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS0P::BYTES);
       (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, RB, BLOCK, KPT0, true, true, true, true, 0>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS0::BYTES);
       dsattr = true;
     }
     if (pipe)
-      hipLaunchKernelGGL((radix_group_kernel<u64, RB, BLOCK, KPT0, true, true, true, true, 2>), grid0, dim3(BLOCK), GS0::BYTES, st,
+      hipLaunchKernelGGL((radix_group_kernel<u64, RB, BLOCK, KPT0P, true, true, true, true, 2>), grid0, dim3(BLOCK), GS0P::BYTES, st,
                          reinterpret_cast<const u64 *>(d_keys), reinterpret_cast<u32 *>(d_alt), (u64)n, shA, (1u << bA) - 1u,
                          &hdr->gbase[0][0], status_a, &hdr->ticket[0], d_error, (u64)tiles0, (const u64 *)nullptr, (const u32 *)nullptr,
                          ex_first, dbg_buf);
@@ -1183,27 +1254,27 @@ hipError_t launch_group_narrow(void *d_keys, void *d_alt, uint64_t n, const Sort
     }
     static bool spattr = false;
     if (pipe && !spattr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, RB, BLOCK, KPT0, false, true, true, true, 2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS0::BYTES);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, RB, BLOCK, KPT0P, false, true, true, true, 2>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS0P::BYTES);
       spattr = true;
     }
     if (pipe && bA <= 8u) {
       // an eight-bit first digit (the plan of the judged files): 256 counters, 128 walkers and look-back rows of 128 granules instead of
       // 512 / 256 / 256 -- half the status traffic, two more waves for the low digit's count
-      using GS08 = GroupSmem<u64, 8, BLOCK, KPT0>;
+      using GS08 = GroupSmem<u64, 8, BLOCK, KPT0P, group_xb<u64, 8, true>()>;
       static bool r8attr = false;
       if (!r8attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, 8, BLOCK, KPT0, false, true, true, true, 2>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, 8, BLOCK, KPT0P, false, true, true, true, 2>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS08::BYTES);
         r8attr = true;
       }
-      hipLaunchKernelGGL((radix_group_kernel<u64, 8, BLOCK, KPT0, false, true, true, true, 2>), grid0, dim3(BLOCK), GS08::BYTES, st,
+      hipLaunchKernelGGL((radix_group_kernel<u64, 8, BLOCK, KPT0P, false, true, true, true, 2>), grid0, dim3(BLOCK), GS08::BYTES, st,
                          reinterpret_cast<const u64 *>(d_keys), reinterpret_cast<u32 *>(d_alt), (u64)n, shA, (1u << bA) - 1u,
                          &hdr->gbase[0][0], status_a, &hdr->ticket[0], d_error, (u64)tiles0, (const u64 *)nullptr, (const u32 *)nullptr,
                          ex_first, (u64 *)nullptr);
     }
     else if (pipe)
-      hipLaunchKernelGGL((radix_group_kernel<u64, RB, BLOCK, KPT0, false, true, true, true, 2>), grid0, dim3(BLOCK), GS0::BYTES, st,
+      hipLaunchKernelGGL((radix_group_kernel<u64, RB, BLOCK, KPT0P, false, true, true, true, 2>), grid0, dim3(BLOCK), GS0P::BYTES, st,
                          reinterpret_cast<const u64 *>(d_keys), reinterpret_cast<u32 *>(d_alt), (u64)n, shA, (1u << bA) - 1u,
                          &hdr->gbase[0][0], status_a, &hdr->ticket[0], d_error, (u64)tiles0, (const u64 *)nullptr, (const u32 *)nullptr,
                          ex_first, (u64 *)nullptr);
