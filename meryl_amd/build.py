@@ -15,8 +15,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmeryl_gpu_count.so")
 SOURCES = ["mgc_kmer.hip", "mgc_sort.hip", "mgc_scan.hip", "mgc_finish.hip", "mgc_misc.hip", "mgc_parse.hip",
            "mgc_encode.hip", "mgc_decode.hip", "mgc_merge.hip", "mgc_lookup.hip", "mgc_filter.hip", "mgc_import.hip", "mgc_analyze.hip",
-           "mgc_api.cpp", "mgc_import.cpp", "mgc_analyze.cpp", "mgc_count.cpp", "mgc_stream.cpp", "mgc_runs.cpp", "mgc_node.cpp", "meryl_db.cpp", "meryl_seq.cpp"]
-HEADERS = ["mgc_device.h", "mgc_common.hpp", "mdb_layout.h", "mgc_session.hpp", "mgc_runs.hpp", "mgc_lookup_dev.hpp", "mgc_import_dev.hpp", "mgc_analyze_dev.hpp",
+           "mgc_api.cpp", "mgc_textfile.cpp", "mgc_import.cpp", "mgc_analyze.cpp", "mgc_count.cpp", "mgc_stream.cpp", "mgc_runs.cpp", "mgc_node.cpp", "meryl_db.cpp", "meryl_seq.cpp"]
+HEADERS = ["mgc_device.h", "mgc_common.hpp", "mdb_layout.h", "mgc_session.hpp", "mgc_clock.hpp", "mgc_chunk_ring.hpp", "mgc_bgzf.hpp", "mgc_runs.hpp", "mgc_lookup_dev.hpp", "mgc_import_dev.hpp", "mgc_analyze_dev.hpp",
            os.path.join("..", "..", "include", "meryl_gpu_count.h"),
            os.path.join("..", "..", "include", "meryl_db.h"), os.path.join("..", "..", "include", "meryl_seq.h"),
            os.path.join("..", "..", "include", "meryl_lookup.h"), os.path.join("..", "..", "include", "meryl_import.h"),
@@ -69,87 +69,47 @@ def _stale():
 
 
 CLI = os.path.join(HERE, "bin", "meryl")
-
-
-def build_cli(force=False, verbose=False):
-    """The `meryl` front end (meryl_amd/bin/meryl): links the library and the system HIP runtime."""
-    src = os.path.join(CSRC, "meryl_main.cpp")
-    if (not force and os.path.exists(CLI) and os.path.getmtime(CLI) >= os.path.getmtime(src)
-            and os.path.getmtime(CLI) >= os.path.getmtime(LIB)):
-        return CLI
-    os.makedirs(os.path.dirname(CLI), exist_ok=True)
-    rocm_lib = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
-    tmp = "%s.tmp%d" % (CLI, os.getpid())             # several ranks may build at once: private file, atomic rename
-    cmd = [hipcc(), "-O2", "-std=c++17", "-pthread", src, "-o", tmp, "-L" + HERE, "-lmeryl_gpu_count",
-           "-Wl,-rpath,$ORIGIN/..", "-L" + rocm_lib, "-lamdhip64", "-Wl,-rpath," + rocm_lib, "-lz"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
-    os.replace(tmp, CLI)
-    return CLI
-
-
 LOOKUP_CLI = os.path.join(HERE, "bin", "meryl-lookup")
-
-
-def build_lookup_cli(force=False, verbose=False):
-    """`meryl-lookup` (meryl_amd/bin/meryl-lookup: -existence and the position reports): links the library and the system HIP runtime."""
-    src = os.path.join(CSRC, "meryl_lookup_main.cpp")
-    if (not force and os.path.exists(LOOKUP_CLI) and os.path.getmtime(LOOKUP_CLI) >= os.path.getmtime(src)
-            and os.path.getmtime(LOOKUP_CLI) >= os.path.getmtime(LIB)):
-        return LOOKUP_CLI
-    os.makedirs(os.path.dirname(LOOKUP_CLI), exist_ok=True)
-    rocm_lib = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
-    tmp = "%s.tmp%d" % (LOOKUP_CLI, os.getpid())
-    cmd = [hipcc(), "-O2", "-std=c++17", "-pthread", src, "-o", tmp, "-L" + HERE, "-lmeryl_gpu_count",
-           "-Wl,-rpath,$ORIGIN/..", "-L" + rocm_lib, "-lamdhip64", "-Wl,-rpath," + rocm_lib, "-lz"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
-    os.replace(tmp, LOOKUP_CLI)
-    return LOOKUP_CLI
-
-
 IMPORT_CLI = os.path.join(HERE, "bin", "meryl-import")
-
-
-def build_import_cli(force=False, verbose=False):
-    """`meryl-import` (meryl_amd/bin/meryl-import: `kmer value` text -> database): links the library and the system HIP runtime."""
-    src = os.path.join(CSRC, "meryl_import_main.cpp")
-    if (not force and os.path.exists(IMPORT_CLI) and os.path.getmtime(IMPORT_CLI) >= os.path.getmtime(src)
-            and os.path.getmtime(IMPORT_CLI) >= os.path.getmtime(LIB)):
-        return IMPORT_CLI
-    os.makedirs(os.path.dirname(IMPORT_CLI), exist_ok=True)
-    rocm_lib = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
-    tmp = "%s.tmp%d" % (IMPORT_CLI, os.getpid())
-    cmd = [hipcc(), "-O2", "-std=c++17", "-pthread", src, "-o", tmp, "-L" + HERE, "-lmeryl_gpu_count",
-           "-Wl,-rpath,$ORIGIN/..", "-L" + rocm_lib, "-lamdhip64", "-Wl,-rpath," + rocm_lib, "-lz"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
-    os.replace(tmp, IMPORT_CLI)
-    return IMPORT_CLI
-
-
 ANALYZE_CLI = os.path.join(HERE, "bin", "meryl-analyze")
 
 
-def build_analyze_cli(force=False, verbose=False):
-    """`meryl-analyze` (meryl_amd/bin/meryl-analyze: -gc / -ga / -gt histograms of a database): links the library and the system HIP runtime."""
-    src = os.path.join(CSRC, "meryl_analyze_main.cpp")
-    if (not force and os.path.exists(ANALYZE_CLI) and os.path.getmtime(ANALYZE_CLI) >= os.path.getmtime(src)
-            and os.path.getmtime(ANALYZE_CLI) >= os.path.getmtime(LIB)):
-        return ANALYZE_CLI
-    os.makedirs(os.path.dirname(ANALYZE_CLI), exist_ok=True)
+def _build_front_end(source, out, force, verbose):
+    """One front end (meryl_amd/bin/*): links the library and the system HIP runtime."""
+    src = os.path.join(CSRC, source)
+    if (not force and os.path.exists(out) and os.path.getmtime(out) >= os.path.getmtime(src)
+            and os.path.getmtime(out) >= os.path.getmtime(LIB)):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
     rocm_lib = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
-    tmp = "%s.tmp%d" % (ANALYZE_CLI, os.getpid())
+    tmp = "%s.tmp%d" % (out, os.getpid())             # several ranks may build at once: private file, atomic rename
     cmd = [hipcc(), "-O2", "-std=c++17", "-pthread", src, "-o", tmp, "-L" + HERE, "-lmeryl_gpu_count",
            "-Wl,-rpath,$ORIGIN/..", "-L" + rocm_lib, "-lamdhip64", "-Wl,-rpath," + rocm_lib, "-lz"]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.check_call(cmd)
-    os.replace(tmp, ANALYZE_CLI)
-    return ANALYZE_CLI
+    os.replace(tmp, out)
+    return out
+
+
+def build_cli(force=False, verbose=False):
+    """The `meryl` front end (meryl_amd/bin/meryl)."""
+    return _build_front_end("meryl_main.cpp", CLI, force, verbose)
+
+
+def build_lookup_cli(force=False, verbose=False):
+    """`meryl-lookup` (meryl_amd/bin/meryl-lookup: -existence and the position reports)."""
+    return _build_front_end("meryl_lookup_main.cpp", LOOKUP_CLI, force, verbose)
+
+
+def build_import_cli(force=False, verbose=False):
+    """`meryl-import` (meryl_amd/bin/meryl-import: `kmer value` text -> database)."""
+    return _build_front_end("meryl_import_main.cpp", IMPORT_CLI, force, verbose)
+
+
+def build_analyze_cli(force=False, verbose=False):
+    """`meryl-analyze` (meryl_amd/bin/meryl-analyze: -gc / -ga / -gt histograms of a database)."""
+    return _build_front_end("meryl_analyze_main.cpp", ANALYZE_CLI, force, verbose)
 
 
 def build(force=False, verbose=False):

@@ -24,6 +24,7 @@
 // its vendored htslib inside the absent submodule (src/main.mk:92-140), whose
 // call sites are not in the tree, so which records it keeps is unpinned here.
 #include "../../include/meryl_seq.h"
+#include "mgc_bgzf.hpp"
 
 #include <cerrno>
 #include <cstdio>
@@ -47,23 +48,9 @@ bool ends_with(const std::string &s, const char *suf) {
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// BGZF: gzip members of at most 64 KiB with the compressed size in a 'BC' extra subfield (SAMv1 4.1)
+// BGZF: gzip members of at most 64 KiB with the compressed size in an extra subfield (SAMv1 4.1; mgc_bgzf.hpp)
 // ---------------------------------------------------------------------------
 namespace {
-// total size of the block starting at p (n >= 18 bytes available), 0 if it is not a BGZF block
-size_t bgzf_block_size(const unsigned char *p, size_t n) {
-  if (n < 18 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return 0;
-  const size_t xlen = (size_t)p[10] | ((size_t)p[11] << 8);
-  if (n < 12 + xlen) return 0;
-  for (size_t o = 12; o + 4 <= 12 + xlen;) {
-    const size_t slen = (size_t)p[o + 2] | ((size_t)p[o + 3] << 8);
-    if (p[o] == 'B' && p[o + 1] == 'C' && slen == 2 && o + 6 <= 12 + xlen)
-      return ((size_t)p[o + 4] | ((size_t)p[o + 5] << 8)) + 1;
-    o += 4 + slen;
-  }
-  return 0;
-}
-
 struct BgzfSource {
   FILE *f = nullptr;
   std::vector<unsigned char> raw;          // compressed bytes not yet decoded
@@ -74,7 +61,7 @@ struct BgzfSource {
   unsigned threads = 1;
   std::string err;
 
-  struct Block { size_t src, csize, hdr, isize, dst; };
+  struct Block { mgc::BgzfBlock b; size_t dst; };            // b.off: its place in `raw`
 
   bool fill_raw(size_t want) {             // make at least `want` bytes available at raw_pos (if the file has them)
     if (raw.size() - raw_pos >= want || raw_eof) return raw.size() - raw_pos >= want;
@@ -101,17 +88,19 @@ struct BgzfSource {
         if (raw.size() != raw_pos) { err = "truncated BGZF block header"; return false; }
         break;
       }
-      const size_t bs = bgzf_block_size(raw.data() + raw_pos, raw.size() - raw_pos);
-      if (bs == 0) { err = "not a BGZF block (plain gzip data inside a BGZF file?)"; return false; }
-      if (!fill_raw(bs)) { err = "truncated BGZF block"; return false; }
-      const unsigned char *p = raw.data() + raw_pos;
-      const size_t xlen = (size_t)p[10] | ((size_t)p[11] << 8), hdr = 12 + xlen;
-      if (bs < hdr + 8) { err = "corrupt BGZF block"; return false; }
-      const size_t isize = (size_t)p[bs - 4] | ((size_t)p[bs - 3] << 8) | ((size_t)p[bs - 2] << 16) | ((size_t)p[bs - 1] << 24);
-      if (isize > 65536) { err = "corrupt BGZF block (ISIZE)"; return false; }
-      blocks.push_back({raw_pos, bs, hdr, isize, total});
-      total += isize;
-      raw_pos += bs;
+      mgc::BgzfBlock b{0, 0, 0, 0};
+      mgc::BgzfParse r = mgc::bgzf_parse_block(raw.data() + raw_pos, raw.size() - raw_pos, &b);
+      if (r == mgc::BGZF_NOT_BLOCK) { err = "not a BGZF block (plain gzip data inside a BGZF file?)"; return false; }
+      if (r == mgc::BGZF_TRUNCATED) {
+        if (!fill_raw(b.csize)) { err = "truncated BGZF block"; return false; }
+        r = mgc::bgzf_parse_block(raw.data() + raw_pos, raw.size() - raw_pos, &b);
+      }
+      if (r == mgc::BGZF_SHORT) { err = "corrupt BGZF block"; return false; }
+      if (r == mgc::BGZF_BAD_ISIZE) { err = "corrupt BGZF block (ISIZE)"; return false; }
+      b.off = raw_pos;                               // (after fill_raw, which may have moved `raw`)
+      blocks.push_back({b, total});
+      total += b.isize;
+      raw_pos += b.csize;
       // fill_raw may move `raw`: the blocks of one batch must stay inside one buffer generation
       if (raw.size() - raw_pos < 65536 + 18 && !raw_eof) break;
     }
@@ -123,18 +112,7 @@ struct BgzfSource {
       memset(&z, 0, sizeof(z));
       if (inflateInit2(&z, -15) != Z_OK) { bad[t] = 1; return; }
       for (size_t i = t; i < blocks.size(); i += threads) {
-        const Block &b = blocks[i];
-        const unsigned char *p = raw.data() + b.src;
-        if (b.isize == 0) continue;                  // the EOF marker (and any other empty block): nothing to produce
-        inflateReset(&z);
-        z.next_in = const_cast<unsigned char *>(p + b.hdr);
-        z.avail_in = (unsigned)(b.csize - b.hdr - 8);
-        z.next_out = out.data() + b.dst;
-        z.avail_out = (unsigned)b.isize;
-        const int rc = inflate(&z, Z_FINISH);
-        const uint32_t want_crc = (uint32_t)p[b.csize - 8] | ((uint32_t)p[b.csize - 7] << 8) | ((uint32_t)p[b.csize - 6] << 16) |
-                                  ((uint32_t)p[b.csize - 5] << 24);
-        if (rc != Z_STREAM_END || z.avail_out != 0 || (uint32_t)crc32(0L, out.data() + b.dst, (unsigned)b.isize) != want_crc) bad[t] = 1;
+        if (!mgc::bgzf_inflate_block(z, raw.data() + blocks[i].b.off, blocks[i].b, out.data() + blocks[i].dst)) bad[t] = 1;
       }
       inflateEnd(&z);
     };
@@ -322,7 +300,8 @@ extern "C" msr_reader *msr_open(const char *name) {
     const size_t got = fread(head, 1, sizeof(head), f);
     const char *off = getenv("MERYL_BGZF_THREADS");
     const unsigned want = off ? (unsigned)atoi(off) : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-    if (bgzf_block_size(head, got) != 0 && want >= 1) {
+    mgc::BgzfBlock first;
+    if (mgc::bgzf_parse_block(head, got, &first) != mgc::BGZF_NOT_BLOCK && want >= 1) {
       rewind(f);
       r->bgzf = new BgzfSource();
       r->bgzf->f = f;

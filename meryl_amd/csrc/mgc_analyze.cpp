@@ -26,7 +26,7 @@
 using mgc::set_err;
 
 namespace {
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+using mgc::now_s;
 
 bool type_ok(int type) { return type == MGC_ANALYZE_GC || type == MGC_ANALYZE_GA || type == MGC_ANALYZE_GT; }
 bool k_ok(uint32_t k) {

@@ -11,23 +11,12 @@
 #include "mgc_runs.hpp"
 
 #include <algorithm>
-#include <atomic>
-#include <cerrno>
-#include <chrono>
-#include <condition_variable>
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
-#include <zlib.h>
 
 namespace mgc {
 std::string &thread_last_error() {
@@ -557,13 +546,11 @@ static int resolve_length(mgc_session *s, HostParseState *out = nullptr) {
   return MGC_OK;
 }
 
-static double io_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 static int join_worker(mgc_session *s) {
   if (s->worker_active) {
-    const double t0 = io_now();
+    const double t0 = mgc::now_s();
     s->worker.join();
-    s->tr_join += io_now() - t0;
+    s->tr_join += mgc::now_s() - t0;
     s->worker_active = false;
     if (s->worker_rc != MGC_OK) return s->worker_rc;
   }
@@ -656,15 +643,15 @@ extern "C" int mgc_push_bases(mgc_session *s, const char *bases, size_t len, int
     size_t left = part ? (end_of_sequence ? 1 : 0) : len;
     while (left) {
       const size_t take = std::min(left, mgc_session::PIN_CHUNK - s->pin_len);
-      const double t0 = io_now();
+      const double t0 = mgc::now_s();
       memcpy(s->pin[s->pin_cur] + s->pin_len, src, take);
-      const double t1 = io_now();
+      const double t1 = mgc::now_s();
       s->tr_memcpy += t1 - t0;
       s->pin_len += take; src += take; left -= take;
       if (s->pin_len == mgc_session::PIN_CHUNK) { rc = flush_pinned(s); if (rc != MGC_OK) return rc; }
-      const double t2 = io_now();
+      const double t2 = mgc::now_s();
       s->tr_flush += t2 - t1;
-      if (s->fill_len + s->pin_len >= s->batch_limit) { rc = cut_batch(s); if (rc != MGC_OK) return rc; s->tr_cut += io_now() - t2; }
+      if (s->fill_len + s->pin_len >= s->batch_limit) { rc = cut_batch(s); if (rc != MGC_OK) return rc; s->tr_cut += mgc::now_s() - t2; }
     }
   }
   return MGC_OK;
@@ -714,7 +701,7 @@ extern "C" int mgc_begin_text(mgc_session *s, int format) {
 }
 
 // one piece (<= TEXT_CHUNK bytes, in pinned memory) -> device input buffer b -> parse kernels; returns once they are queued
-static int text_submit(mgc_session *s, const char *pinned_src, size_t piece) {
+int mgc::text_submit(mgc_session *s, const char *pinned_src, size_t piece) {
   const uint32_t b = s->text_next & 1u;
   if (s->text_ev_used[b]) HIP_TRY(s, hipEventSynchronize(s->text_ev[b]));       // device buffer b (and its previous source) are free again
   HIP_TRY(s, s->ensure_preserve(stage_id(s->fill), s->fill_len + piece + 4096, s->fill_len, s->st_in));
@@ -744,7 +731,7 @@ extern "C" int mgc_push_text(mgc_session *s, const char *text, size_t len) {
     const uint32_t b = s->text_next & 1u;
     if (s->text_ev_used[b]) HIP_TRY(s, hipEventSynchronize(s->text_ev[b]));     // pinned + device buffer b are free again
     memcpy(s->text_pinned[b], text, piece);
-    const int rc = text_submit(s, s->text_pinned[b], piece);
+    const int rc = mgc::text_submit(s, s->text_pinned[b], piece);
     if (rc != MGC_OK) return rc;
     text += piece;
     len -= piece;
@@ -752,391 +739,18 @@ extern "C" int mgc_push_text(mgc_session *s, const char *text, size_t len) {
   return MGC_OK;
 }
 
-// A whole uncompressed FASTA/FASTQ file: `reader_threads` threads pread() 32 MiB chunks straight into a ring of pinned
-// buffers (no intermediate copy), the calling thread uploads and parses them in file order.  A 20 GB FASTQ on tmpfs is
-// otherwise bound by ONE thread's read()+memcpy (measured 11 GB/s, 1.8 s of a 3 s file -> database run).
-// format of a FASTA / FASTQ file from its first byte that is not white space; 0: neither
-static int sniff_text_format(int fd, char *first) {
-  char head[4096];
-  const ssize_t got = pread(fd, head, sizeof(head), 0);
-  char c = '>';
-  for (ssize_t i = 0; i < got; i++) if (head[i] != '\n' && head[i] != '\r' && head[i] != ' ' && head[i] != '\t') { c = head[i]; break; }
-  if (first) *first = c;
-  return c == '@' ? MGC_TEXT_FASTQ : (c == '>' ? MGC_TEXT_FASTA : 0);
-}
-
-// First record start at or after `offset` of a FASTA / FASTQ file -- where a reader that takes the file from the middle
-// may begin (the ranks of a node count read disjoint byte windows of the input, each through its own device's link).
-// FASTA: a line that starts with '>'.  FASTQ (four-line records): a line that starts with '@' whose next-but-one line starts
-// with '+' -- a quality line may start with '@', but then the line two below it is a sequence line, never '+'.
-extern "C" int mgc_text_record_start(const char *path, int format, uint64_t offset, uint64_t *start) {
-  if (!path || !start) return MGC_EINVAL;
-  const int fd = open(path, O_RDONLY);
-  if (fd < 0) { set_err(nullptr, "mgc_text_record_start: cannot open '%s': %s", path, strerror(errno)); return MGC_EINVAL; }
-  struct stat st;
-  if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { close(fd); set_err(nullptr, "mgc_text_record_start: '%s' is not a regular file", path); return MGC_EINVAL; }
-  const uint64_t size = (uint64_t)st.st_size;
-  if (format == 0) format = sniff_text_format(fd, nullptr);
-  if (format != MGC_TEXT_FASTA && format != MGC_TEXT_FASTQ) { close(fd); set_err(nullptr, "'%s' is neither FASTA nor FASTQ", path); return MGC_EFORMAT; }
-  if (offset == 0 || offset >= size) { close(fd); *start = offset >= size ? size : 0; return MGC_OK; }
-  // line starts from offset - 1 on: the byte before a line start is '\n'
-  std::vector<char> buf(1u << 20);
-  uint64_t pos = offset - 1;                               // file position of buf[0]
-  std::vector<uint64_t> ls;                                // line starts found so far (file offsets), with their first byte
-  std::vector<char> lc;
-  uint64_t answer = size;
-  bool found = false;
-  while (!found && pos < size) {
-    const ssize_t got = pread(fd, buf.data(), buf.size(), (off_t)pos);
-    if (got <= 0) break;
-    for (ssize_t i = 0; i < got && !found; i++) {
-      if (buf[i] != '\n') continue;
-      const uint64_t line = pos + (uint64_t)i + 1;
-      if (line >= size) break;
-      char c;
-      if (i + 1 < got) c = buf[i + 1];
-      else if (pread(fd, &c, 1, (off_t)line) != 1) break;
-      if (format == MGC_TEXT_FASTA) { if (c == '>') { answer = line; found = true; } continue; }
-      ls.push_back(line); lc.push_back(c);
-      const size_t m = ls.size();
-      if (m >= 3 && lc[m - 3] == '@' && lc[m - 1] == '+') { answer = ls[m - 3]; found = true; }
-    }
-    pos += (uint64_t)got;
-  }
-  close(fd);
-  *start = found ? answer : size;
-  return MGC_OK;
-}
-
-static int push_text_file_range(mgc_session *s, const char *path, int format, int reader_threads, uint64_t range_begin, uint64_t range_end);
-
-extern "C" int mgc_push_text_file(mgc_session *s, const char *path, int format, int reader_threads) {
-  return push_text_file_range(s, path, format, reader_threads, 0, ~0ull);
-}
-
-extern "C" int mgc_push_text_file_range(mgc_session *s, const char *path, int format, int reader_threads, uint64_t begin, uint64_t end) {
-  return push_text_file_range(s, path, format, reader_threads, begin, end);
-}
-
-// bytes [range_begin, range_end) of the file (range_begin at a record start; range_end = the next reader's start, or past the end)
-static int push_text_file_range(mgc_session *s, const char *path, int format, int reader_threads, uint64_t range_begin, uint64_t range_end) {
-  if (!s || !path) return MGC_EINVAL;
-  const int fd = open(path, O_RDONLY);
-  if (fd < 0) { set_err(&s->err, "mgc_push_text_file: cannot open '%s': %s", path, strerror(errno)); return MGC_EINVAL; }
-  struct stat st;
-  if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { close(fd); set_err(&s->err, "mgc_push_text_file: '%s' is not a regular file", path); return MGC_EINVAL; }
-  if (format == 0) {                                        // sniff: first byte that is not white space
-    char c = 0;
-    format = sniff_text_format(fd, &c);
-    if (!format) { close(fd); set_err(&s->err, "'%s' is neither FASTA nor FASTQ (record starts with '%c')", path, c); return MGC_EFORMAT; }
-  }
-  const uint64_t file_size = (uint64_t)st.st_size;
-  if (range_end > file_size) range_end = file_size;
-  if (range_begin > range_end) range_begin = range_end;
-  const uint64_t base = range_begin;                        // every file offset below is relative to the window
-  const uint64_t size = range_end - range_begin;
-  int rc = mgc_begin_text(s, format);
-  if (rc != MGC_OK) { close(fd); return rc; }
-
-  // Readers and ring: measured on the 2 x 64-core box (scripts/e2e_cli.py, 20.5 GB FASTQ on tmpfs): 6 readers / 8 slots keep
-  // the uploader waiting 1.7 s, 16 readers / 24 slots 0.01 s (the loop then runs at the 0.5 s of upload + parse).  The pinned
-  // slots are allocated by the readers themselves, in parallel, on first use, and stay with the session for the next file.
-  constexpr int RMAX = mgc_session::TEXT_RING_MAX;
-  if (reader_threads <= 0) reader_threads = 16;
-  reader_threads = std::max(1, std::min(reader_threads, RMAX - 8));
-  int R = reader_threads + 8;                               // up to R-2 chunks of read-ahead
-  const size_t CH = mgc_session::TEXT_CHUNK;
-  const uint64_t nchunks = (size + CH - 1) / CH;
-  reader_threads = (int)std::min<uint64_t>((uint64_t)std::max(1, std::min(reader_threads, R - 2)), nchunks ? nchunks : 1);
-  char **ring = s->text_ring;
-  std::atomic<bool> alloc_failed(false);
-  std::mutex mu;
-  std::condition_variable cv;
-  uint64_t free_gen[RMAX], ready_chunk[RMAX];               // slot i may be filled with chunk c iff free_gen[i] == c / R
-  size_t   ready_len[RMAX];
-  std::vector<double> t_pread(64, 0.0), t_slotwait(64, 0.0);
-  std::atomic<int> reader_ids(0);
-  for (int i = 0; i < R; i++) { free_gen[i] = 0; ready_chunk[i] = ~0ull; ready_len[i] = 0; }
-  std::atomic<uint64_t> next_chunk(0);
-  bool abort_all = false, read_failed = false;
-  auto reader = [&]() {
-    const int me = reader_ids.fetch_add(1) & 63;
-    auto rnow = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    for (;;) {
-      const uint64_t c = next_chunk.fetch_add(1);
-      if (c >= nchunks) return;
-      const int slot = (int)(c % R);
-      const double w0 = rnow();
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return abort_all || free_gen[slot] == c / R; });
-        if (abort_all) return;
-      }
-      if (!ring[slot]) {                                    // first use of this slot (exactly one reader gets here per slot)
-        (void)hipSetDevice(s->device);
-        if (hipHostMalloc(reinterpret_cast<void **>(&ring[slot]), CH, hipHostMallocDefault) != hipSuccess) {
-          ring[slot] = nullptr;
-          alloc_failed.store(true);
-          std::lock_guard<std::mutex> g(mu);
-          read_failed = true; abort_all = true;
-          cv.notify_all();
-          return;
-        }
-      }
-      const double w1 = rnow();
-      t_slotwait[me] += w1 - w0;
-      const uint64_t off = c * CH;
-      const size_t want = (size_t)std::min<uint64_t>(CH, size - off);
-      size_t have = 0;
-      bool ok = true;
-      while (have < want) {
-        const ssize_t r = pread(fd, ring[slot] + have, want - have, (off_t)(base + off + have));
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) { ok = false; break; }                  // an error, or the file shrank under us
-        have += (size_t)r;
-      }
-      t_pread[me] += rnow() - w1;
-      std::lock_guard<std::mutex> g(mu);
-      if (!ok) { read_failed = true; abort_all = true; }
-      ready_chunk[slot] = c; ready_len[slot] = have;
-      cv.notify_all();
-    }
-  };
-  std::vector<std::thread> readers;
-  for (int t = 0; t < reader_threads; t++) readers.emplace_back(reader);
-  const bool trace = getenv("MGC_IO_TRACE") != nullptr;
-  double t_wait = 0, t_submit = 0;
-  auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  for (uint64_t c = 0; c < nchunks && rc == MGC_OK; c++) {
-    const int slot = (int)(c % R);
-    size_t len = 0;
-    const double t0 = now();
-    {
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return abort_all || ready_chunk[slot] == c; });
-      if (abort_all) break;
-      len = ready_len[slot];
-    }
-    const double t1 = now();
-    t_wait += t1 - t0;
-    // text_submit first waits for the parse of chunk c-2 (same device buffer): after that the pinned slot of chunk c-2
-    // has been read by its upload and goes back to the readers
-    rc = text_submit(s, ring[slot], len);
-    t_submit += now() - t1;
-    if (c >= 2) {
-      std::lock_guard<std::mutex> g(mu);
-      free_gen[(c - 2) % R]++;
-      cv.notify_all();
-    }
-  }
-  { std::lock_guard<std::mutex> g(mu); if (rc != MGC_OK) abort_all = true; cv.notify_all(); }
-  // the last uploads still read from the ring
+// the last two text uploads still read from their pinned sources: wait for them
+void mgc::text_drain(mgc_session *s) {
   for (int b = 0; b < 2; b++) if (s->text_ev_used[b]) (void)hipEventSynchronize(s->text_ev[b]);
-  { std::lock_guard<std::mutex> g(mu); abort_all = abort_all || true; cv.notify_all(); }
-  for (auto &t : readers) t.join();
-  close(fd);
-  if (alloc_failed.load()) { set_err(&s->err, "mgc_push_text_file: pinned buffers: out of memory"); (void)mgc_end_text(s); return MGC_ENOMEM; }
-  if (trace) {
-    double sp = 0, sw = 0;
-    for (int i = 0; i < 64; i++) { sp += t_pread[i]; sw += t_slotwait[i]; }
-    fprintf(stderr, "[io] text file %.2f GB in %llu chunks, %d readers, ring %d: waiting for readers %.3f s, upload+parse submit (incl. waits "
-                    "for the device) %.3f s; readers: %.3f s in pread (%.1f GB/s each), %.3f s waiting for a free slot\n",
-            size / 1e9, (unsigned long long)nchunks, reader_threads, R, t_wait, t_submit, sp, sp > 0 ? size / 1e9 / sp : 0.0, sw);
-  }
-  if (read_failed) { set_err(&s->err, "mgc_push_text_file: reading '%s' failed: %s", path, strerror(errno)); rc = MGC_EINVAL; }
-  const int rc_end = mgc_end_text(s);                       // closes the file in every case (rolls it back on MGC_EFORMAT)
-  return rc != MGC_OK ? rc : rc_end;
 }
 
-// ---- a BGZF file (bgzip'd FASTA / FASTQ: independent gzip members of <= 64 KiB of text, their compressed size in a 'BC' extra field,
-// SAMv1 4.1) inflated by `threads` threads STRAIGHT into the pinned upload ring (round 6) ----
-// Through the generic reader (meryl_seq.cpp: BgzfSource -> msr_read_text -> mgc_push_text) the text of a batch of blocks was copied twice
-// by the calling thread (out of the inflater's batch, into the pinned buffer) behind batches of 32 MiB whose threads were spawned per
-// batch: 4 GB/s of text with 32 threads (profiles/r06w: bench.py e2e_compressed).  Here the file is mapped, its blocks are indexed in one
-// walk over the headers, chunks of <= TEXT_CHUNK of text are handed to persistent worker threads that inflate block after block into the
-// chunk's ring slot, and the calling thread uploads and parses the chunks in order (push_text_file_range's ring).
-namespace {
-struct BgzfBlock { uint64_t off; uint32_t csize, hdr, isize; };
-// size of the BGZF block at p (n >= 18 bytes there), its header length; 0: not a BGZF block
-static size_t bgzf_block_at(const unsigned char *p, size_t n, uint32_t *hdr) {
-  if (n < 18 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return 0;
-  const size_t xlen = (size_t)p[10] | ((size_t)p[11] << 8);
-  if (12 + xlen > n) return 0;
-  size_t o = 12;
-  while (o + 4 <= 12 + xlen) {
-    const size_t slen = (size_t)p[o + 2] | ((size_t)p[o + 3] << 8);
-    if (p[o] == 'B' && p[o + 1] == 'C' && slen == 2 && o + 6 <= 12 + xlen) { *hdr = (uint32_t)(12 + xlen); return ((size_t)p[o + 4] | ((size_t)p[o + 5] << 8)) + 1; }
-    o += 4 + slen;
-  }
-  return 0;
-}
-}  // namespace
-
-extern "C" int mgc_is_bgzf_file(const char *path) {
-  if (!path) return 0;
-  const int fd = open(path, O_RDONLY);
-  if (fd < 0) return 0;
-  unsigned char head[64];
-  const ssize_t got = pread(fd, head, sizeof(head), 0);
-  close(fd);
-  uint32_t hdr = 0;
-  return (got >= 18 && bgzf_block_at(head, (size_t)got, &hdr) != 0) ? 1 : 0;
-}
-
-extern "C" int mgc_push_text_bgzf_file(mgc_session *s, const char *path, int format, int threads) {
-  if (!s || !path) return MGC_EINVAL;
-  const int fd = open(path, O_RDONLY);
-  if (fd < 0) { set_err(&s->err, "mgc_push_text_bgzf_file: cannot open '%s': %s", path, strerror(errno)); return MGC_EINVAL; }
-  struct stat st;
-  if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < 28) { close(fd); set_err(&s->err, "mgc_push_text_bgzf_file: '%s' is not a regular BGZF file", path); return MGC_EINVAL; }
-  const size_t fsize = (size_t)st.st_size;
-  const unsigned char *map = reinterpret_cast<const unsigned char *>(mmap(nullptr, fsize, PROT_READ, MAP_SHARED, fd, 0));
-  if (map == MAP_FAILED) { close(fd); set_err(&s->err, "mgc_push_text_bgzf_file: mmap of '%s' failed: %s", path, strerror(errno)); return MGC_EINVAL; }
-  auto unmap = [&]() { munmap(const_cast<unsigned char *>(map), fsize); close(fd); };
-  // ---- index: one walk over the block headers; chunks of whole blocks, <= TEXT_CHUNK of text each ----
-  const size_t CH = mgc_session::TEXT_CHUNK;
-  std::vector<BgzfBlock> blocks;
-  struct Chunk { size_t first, last; size_t text; };
-  std::vector<Chunk> chunks;
-  {
-    size_t off = 0, text = 0, first = 0;
-    while (off < fsize) {
-      uint32_t hdr = 0;
-      const size_t bs = bgzf_block_at(map + off, fsize - off, &hdr);
-      if (bs == 0 || off + bs > fsize || bs < (size_t)hdr + 8) { unmap(); set_err(&s->err, "'%s': not a BGZF block at offset %zu (plain gzip data, or a truncated file)", path, off); return MGC_EFORMAT; }
-      const unsigned char *e = map + off + bs;
-      const uint32_t isize = (uint32_t)e[-4] | ((uint32_t)e[-3] << 8) | ((uint32_t)e[-2] << 16) | ((uint32_t)e[-1] << 24);
-      if (isize > 65536) { unmap(); set_err(&s->err, "'%s': corrupt BGZF block at offset %zu (ISIZE %u)", path, off, isize); return MGC_EFORMAT; }
-      if (text + isize > CH) { chunks.push_back({first, blocks.size(), text}); first = blocks.size(); text = 0; }
-      blocks.push_back({(uint64_t)off, (uint32_t)bs, hdr, isize});
-      text += isize;
-      off += bs;
-    }
-    if (blocks.size() > first) chunks.push_back({first, blocks.size(), text});
-  }
-  auto inflate_block = [&](z_stream &z, const BgzfBlock &b, unsigned char *dst) -> bool {
-    if (b.isize == 0) return true;                             // the end-of-file marker (and any other empty block)
-    const unsigned char *p = map + b.off;
-    if (inflateReset(&z) != Z_OK) return false;
-    z.next_in = const_cast<unsigned char *>(p + b.hdr);
-    z.avail_in = b.csize - b.hdr - 8;
-    z.next_out = dst;
-    z.avail_out = b.isize;
-    const int zr = inflate(&z, Z_FINISH);
-    const uint32_t want = (uint32_t)p[b.csize - 8] | ((uint32_t)p[b.csize - 7] << 8) | ((uint32_t)p[b.csize - 6] << 16) | ((uint32_t)p[b.csize - 5] << 24);
-    return zr == Z_STREAM_END && z.avail_out == 0 && (uint32_t)crc32(0L, dst, b.isize) == want;
-  };
-  if (format == 0) {                                            // sniff: the first byte of text that is not white space
-    char c = 0;
-    z_stream z; memset(&z, 0, sizeof(z));
-    std::vector<unsigned char> tmp(65536);
-    if (inflateInit2(&z, -15) != Z_OK) { unmap(); set_err(&s->err, "zlib: inflateInit2 failed"); return MGC_ENOMEM; }
-    for (size_t i = 0; i < blocks.size() && !c; i++) {
-      if (!inflate_block(z, blocks[i], tmp.data())) { inflateEnd(&z); unmap(); set_err(&s->err, "'%s': BGZF block %zu failed to inflate (corrupt file)", path, i); return MGC_EFORMAT; }
-      for (uint32_t j = 0; j < blocks[i].isize; j++) if (tmp[j] != '\n' && tmp[j] != '\r' && tmp[j] != ' ' && tmp[j] != '\t') { c = (char)tmp[j]; break; }
-    }
-    inflateEnd(&z);
-    format = c == '@' ? MGC_TEXT_FASTQ : (c == '>' ? MGC_TEXT_FASTA : 0);
-    if (!format) { unmap(); set_err(&s->err, "'%s' is neither FASTA nor FASTQ (record starts with '%c')", path, c ? c : '?'); return MGC_EFORMAT; }
-  }
-  int rc = mgc_begin_text(s, format);
-  if (rc != MGC_OK) { unmap(); return rc; }
-
-  constexpr int RMAX = mgc_session::TEXT_RING_MAX;
-  if (threads <= 0) threads = 16;
-  threads = std::max(1, std::min(threads, RMAX - 8));
-  const int R = threads + 8;
-  const uint64_t nchunks = chunks.size();
-  threads = (int)std::min<uint64_t>((uint64_t)std::max(1, std::min(threads, R - 2)), nchunks ? nchunks : 1);
-  char **ring = s->text_ring;
-  std::mutex mu;
-  std::condition_variable cv;
-  uint64_t free_gen[RMAX], ready_chunk[RMAX];                 // slot i may be filled with chunk c iff free_gen[i] == c / R
-  for (int i = 0; i < R; i++) { free_gen[i] = 0; ready_chunk[i] = ~0ull; }
-  std::atomic<uint64_t> next_chunk(0);
-  bool abort_all = false, failed = false, alloc_failed = false;
-  std::atomic<uint64_t> bad_block(~0ull);
-  auto worker = [&]() {
-    z_stream z; memset(&z, 0, sizeof(z));
-    if (inflateInit2(&z, -15) != Z_OK) { std::lock_guard<std::mutex> g(mu); failed = abort_all = true; cv.notify_all(); return; }
-    for (;;) {
-      const uint64_t c = next_chunk.fetch_add(1);
-      if (c >= nchunks) break;
-      const int slot = (int)(c % R);
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return abort_all || free_gen[slot] == c / R; });
-        if (abort_all) break;
-      }
-      if (!ring[slot]) {                                      // first use of this slot (exactly one worker gets here per slot)
-        (void)hipSetDevice(s->device);
-        if (hipHostMalloc(reinterpret_cast<void **>(&ring[slot]), CH, hipHostMallocDefault) != hipSuccess) {
-          ring[slot] = nullptr;
-          std::lock_guard<std::mutex> g(mu);
-          alloc_failed = failed = abort_all = true;
-          cv.notify_all();
-          break;
-        }
-      }
-      bool ok = true;
-      size_t at = 0;
-      for (size_t i = chunks[c].first; i < chunks[c].last && ok; i++) {
-        ok = inflate_block(z, blocks[i], reinterpret_cast<unsigned char *>(ring[slot]) + at);
-        if (!ok) bad_block.store(i);
-        at += blocks[i].isize;
-      }
-      std::lock_guard<std::mutex> g(mu);
-      if (!ok) { failed = abort_all = true; }
-      ready_chunk[slot] = c;
-      cv.notify_all();
-    }
-    inflateEnd(&z);
-  };
-  std::vector<std::thread> pool;
-  for (int t = 0; t < threads; t++) pool.emplace_back(worker);
-  const bool trace = getenv("MGC_IO_TRACE") != nullptr;
-  auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_wait = 0, t_submit = 0;
-  uint64_t text_total = 0;
-  for (uint64_t c = 0; c < nchunks && rc == MGC_OK; c++) {
-    const int slot = (int)(c % R);
-    const double t0 = now();
-    {
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return abort_all || ready_chunk[slot] == c; });
-      if (abort_all) break;
-    }
-    const double t1 = now();
-    t_wait += t1 - t0;
-    if (chunks[c].text) rc = text_submit(s, ring[slot], chunks[c].text);       // (a chunk of empty blocks: the end-of-file marker)
-    text_total += chunks[c].text;
-    t_submit += now() - t1;
-    if (c >= 2) { std::lock_guard<std::mutex> g(mu); free_gen[(c - 2) % R]++; cv.notify_all(); }
-  }
-  { std::lock_guard<std::mutex> g(mu); if (rc != MGC_OK) abort_all = true; cv.notify_all(); }
-  for (int b = 0; b < 2; b++) if (s->text_ev_used[b]) (void)hipEventSynchronize(s->text_ev[b]);   // the last uploads still read from the ring
-  { std::lock_guard<std::mutex> g(mu); abort_all = true; cv.notify_all(); }
-  for (auto &t : pool) t.join();
-  unmap();
-  if (trace)
-    fprintf(stderr, "[io] BGZF file %.2f GB -> %.2f GB of text in %llu chunks (%zu blocks), %d inflaters, ring %d: waiting for the inflaters %.3f s, "
-                    "upload+parse submit (incl. waits for the device) %.3f s\n", fsize / 1e9, text_total / 1e9, (unsigned long long)nchunks, blocks.size(),
-            threads, R, t_wait, t_submit);
-  if (alloc_failed) { set_err(&s->err, "mgc_push_text_bgzf_file: pinned buffers: out of memory"); (void)mgc_end_text(s); return MGC_ENOMEM; }
-  if (failed) {
-    // what the file has put into the stream is taken back (as for a file that stops being strict FASTQ), unless part of it already went
-    // into a counted batch
-    const unsigned long long bb = (unsigned long long)bad_block.load();
-    s->text_open = false;
-    if (s->text_cut_in_file) { set_err(&s->err, "'%s': BGZF block %llu failed to inflate after part of the file was counted (input larger than one batch)", path, bb); return MGC_EINVAL; }
-    HIP_TRY(s, mgc::launch_text_file_op(s->buf[mgc_session::B_TEXT_STATE].p, stage_ptr(s, s->fill), 2, s->st_in));
-    const int rrc = resolve_length(s);
-    if (rrc != MGC_OK) return rrc;
-    set_err(&s->err, "'%s': BGZF block %llu failed to inflate (corrupt file)", path, bb);
-    return MGC_EFORMAT;
-  }
-  const int rc_end = mgc_end_text(s);                        // closes the file in every case (rolls it back on MGC_EFORMAT)
-  return rc != MGC_OK ? rc : rc_end;
+// Closes the open file and takes what it has put into the stream back out.  MGC_EINVAL, and the stream as it is, when part
+// of the file went into a batch that is already counted: that cannot be taken back.
+int mgc::text_rollback(mgc_session *s) {
+  s->text_open = false;
+  if (s->text_cut_in_file) return MGC_EINVAL;
+  HIP_TRY(s, mgc::launch_text_file_op(s->buf[mgc_session::B_TEXT_STATE].p, stage_ptr(s, s->fill), 2, s->st_in));
+  return resolve_length(s);
 }
 
 extern "C" int mgc_end_text(mgc_session *s) {
@@ -1150,14 +764,10 @@ extern "C" int mgc_end_text(mgc_session *s) {
   int rc = resolve_length(s, &h);
   if (rc != MGC_OK) return rc;
   if (h.error) {
-    if (s->text_cut_in_file) {
-      // part of this file went into a batch that is already counted: it cannot be taken back
+    rc = mgc::text_rollback(s);
+    if (rc == MGC_EINVAL)
       set_err(&s->err, "the file stops being strict four-line FASTQ after part of it was counted (input larger than one batch): "
                        "convert it, or feed it through mgc_push_bases from the start");
-      return MGC_EINVAL;
-    }
-    HIP_TRY(s, mgc::launch_text_file_op(s->buf[mgc_session::B_TEXT_STATE].p, stage_ptr(s, s->fill), 2, s->st_in));
-    rc = resolve_length(s);
     if (rc != MGC_OK) return rc;
     set_err(&s->err, "the file is not strict four-line FASTQ: feed it through mgc_push_bases (meryl_seq.h reader)");
     return MGC_EFORMAT;

@@ -23,7 +23,7 @@
 using mgc::set_err;
 
 namespace {
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+using mgc::now_s;
 
 int hip_rc(hipError_t e, const char *what) {
   if (e == hipSuccess) return MGC_OK;

@@ -30,7 +30,7 @@ using mgc::set_err;
 
 namespace {
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+using mgc::now_s;
 
 struct Barrier {
   std::mutex m; std::condition_variable cv; uint32_t n = 1, waiting = 0; uint64_t gen = 0;

@@ -15,7 +15,7 @@
 using mgc::set_err;
 
 namespace {
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+using mgc::now_s;
 uint64_t env_u64(const char *name, uint64_t dflt) {
   const char *e = getenv(name);
   return (e && *e) ? strtoull(e, nullptr, 10) : dflt;

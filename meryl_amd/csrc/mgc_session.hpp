@@ -1,11 +1,11 @@
 // mgc_session.hpp -- the session object behind include/meryl_gpu_count.h and the helpers its translation units
-// (mgc_api.cpp: input + batches; mgc_count.cpp: counting; mgc_stream.cpp: delivery of the result, database streaming) share.  Internal.
+// (mgc_api.cpp: input + batches; mgc_textfile.cpp: whole-file readers; mgc_count.cpp: counting; mgc_stream.cpp: delivery of the result, database streaming) share.  Internal.
 #pragma once
 
 #include "../../include/meryl_gpu_count.h"
+#include "mgc_clock.hpp"
 #include "mgc_device.h"
 
-#include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -86,11 +86,11 @@ struct mgc_session {
     Buf &b = buf[which];
     if (bytes < 256) bytes = 256;
     if (b.cap >= bytes) return hipSuccess;
-    const auto t0 = std::chrono::steady_clock::now();
+    const double t0 = mgc::now_s();
     if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
     hipError_t e = hipMalloc(&b.p, bytes);
     if (e == hipSuccess) b.cap = bytes;
-    tr_alloc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    tr_alloc += mgc::now_s() - t0;
     tr_alloc_bytes += bytes;
     return e;
   }
@@ -103,8 +103,7 @@ struct mgc_session {
   hipError_t ensure_preserve(int which, size_t bytes, size_t keep, hipStream_t on) {
     Buf &b = buf[which];
     if (b.cap >= bytes) return hipSuccess;
-    struct Tm { double *acc; double t0; static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-                Tm(double *a) : acc(a), t0(now()) {} ~Tm() { *acc += now() - t0; } } tm_(&tr_grow);
+    struct Tm { double *acc; double t0; Tm(double *a) : acc(a), t0(mgc::now_s()) {} ~Tm() { *acc += mgc::now_s() - t0; } } tm_(&tr_grow);
     size_t want = b.cap * 4;
     const size_t full = batch_limit ? (size_t)batch_limit + 4 * PIN_CHUNK : 0;       // what a whole batch needs
     if (full && want > full && full >= bytes) want = full;
@@ -145,7 +144,7 @@ struct mgc_session {
   bool        text_ev_used[2] = {false, false};
   uint32_t    text_next = 0;
   static constexpr int TEXT_RING_MAX = 64;
-  char       *text_ring[TEXT_RING_MAX] = {nullptr};      // mgc_push_text_file's pinned read-ahead slots (allocated on first use)
+  char       *text_ring[TEXT_RING_MAX] = {nullptr};      // the whole-file readers' pinned slots (mgc_textfile.cpp; allocated on first use)
   // host-pushed bases: two pinned chunks, the upload of one overlaps the filling of the other
   char       *pin[2] = {nullptr, nullptr};
   size_t      pin_len = 0;
@@ -204,5 +203,13 @@ struct CountInput {
 // One count over the bases resident in HBM (s->d_bases / s->n_bases) or over in.keys: the result stays in the session's arena
 // (mgc_count.cpp).  The caller marks the session counted.
 int count_device(mgc_session *s, const CountInput &in = CountInput());
+
+// What the whole-file readers (mgc_textfile.cpp) use of the open text file besides mgc_begin_text / mgc_end_text (mgc_api.cpp):
+// one piece (<= TEXT_CHUNK bytes, in pinned memory) -> device input buffer -> parse kernels; returns once they are queued
+int text_submit(mgc_session *s, const char *pinned_src, size_t piece);
+// waits until the last two pieces submitted have been read from their pinned sources
+void text_drain(mgc_session *s);
+// closes the open file and takes it back out of the stream; MGC_EINVAL when part of it was already counted
+int text_rollback(mgc_session *s);
 }  // namespace mgc
 

@@ -24,7 +24,7 @@ using mgc::set_err;
 
 namespace {
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+using mgc::now_s;
 
 struct DBuf {                                             // grow-only device buffer
   void *p = nullptr; size_t cap = 0;

@@ -1,0 +1,249 @@
+// mgc_textfile.cpp -- whole FASTA / FASTQ files into a session's base stream (include/meryl_gpu_count.h): plain files read
+// with pread, BGZF files inflated, by several threads STRAIGHT into a ring of pinned buffers (mgc_chunk_ring.hpp) that the
+// calling thread uploads and parses in file order.  The session is reached through mgc_begin_text / mgc_end_text and
+// text_submit / text_drain / text_rollback (mgc_session.hpp) only.
+#include "../../include/meryl_gpu_count.h"
+#include "mgc_bgzf.hpp"
+#include "mgc_chunk_ring.hpp"
+#include "mgc_session.hpp"
+
+#include <algorithm>
+#include <cerrno>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+#include <vector>
+
+using mgc::set_err;
+
+namespace {
+// `path` opened for reading if it is a regular file (a `kind`) of at least min_size bytes, or -1 and why not in *err
+int open_regular(std::string *err, const char *who, const char *path, const char *kind, off_t min_size, uint64_t *size) {
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) { set_err(err, "%s: cannot open '%s': %s", who, path, strerror(errno)); return -1; }
+  struct stat st;
+  if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < min_size) { close(fd); set_err(err, "%s: '%s' is not a %s", who, path, kind); return -1; }
+  *size = (uint64_t)st.st_size;
+  return fd;
+}
+
+// the first byte of text that is not white space; 0: none
+char first_text_byte(const unsigned char *p, size_t n) {
+  for (size_t i = 0; i < n; i++) if (p[i] != '\n' && p[i] != '\r' && p[i] != ' ' && p[i] != '\t') return (char)p[i];
+  return 0;
+}
+int format_of(char c) { return c == '@' ? MGC_TEXT_FASTQ : (c == '>' ? MGC_TEXT_FASTA : 0); }
+
+// format of a FASTA / FASTQ file from its first byte that is not white space; 0: neither
+int sniff_text_format(int fd, char *first) {
+  unsigned char head[4096];
+  const ssize_t got = pread(fd, head, sizeof(head), 0);
+  char c = first_text_byte(head, got > 0 ? (size_t)got : 0);
+  if (!c) c = '>';
+  if (first) *first = c;
+  return format_of(c);
+}
+
+// The ring of a session: its pinned slots are allocated by the producers themselves, in parallel, on first use, and stay
+// with the session for the next file (mgc_close frees them).  lag 2: see run_chunk_ring.
+template <class Fill, class Consume>
+mgc::ChunkRingResult run_session_ring(mgc_session *s, uint64_t n_chunks, const mgc::ChunkRingGeometry &g, Fill fill, Consume consume) {
+  auto alloc = [s]() -> char * {
+    char *p = nullptr;
+    (void)hipSetDevice(s->device);
+    return hipHostMalloc(reinterpret_cast<void **>(&p), mgc_session::TEXT_CHUNK, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+  };
+  return mgc::run_chunk_ring(n_chunks, s->text_ring, g.slots, g.threads, 2, alloc, fill, consume);
+}
+}  // namespace
+
+// First record start at or after `offset` of a FASTA / FASTQ file -- where a reader that takes the file from the middle
+// may begin (the ranks of a node count read disjoint byte windows of the input, each through its own device's link).
+// FASTA: a line that starts with '>'.  FASTQ (four-line records): a line that starts with '@' whose next-but-one line starts
+// with '+' -- a quality line may start with '@', but then the line two below it is a sequence line, never '+'.
+extern "C" int mgc_text_record_start(const char *path, int format, uint64_t offset, uint64_t *start) {
+  if (!path || !start) return MGC_EINVAL;
+  uint64_t size = 0;
+  const int fd = open_regular(nullptr, "mgc_text_record_start", path, "regular file", 0, &size);
+  if (fd < 0) return MGC_EINVAL;
+  if (format == 0) format = sniff_text_format(fd, nullptr);
+  if (format != MGC_TEXT_FASTA && format != MGC_TEXT_FASTQ) { close(fd); set_err(nullptr, "'%s' is neither FASTA nor FASTQ", path); return MGC_EFORMAT; }
+  if (offset == 0 || offset >= size) { close(fd); *start = offset >= size ? size : 0; return MGC_OK; }
+  // line starts from offset - 1 on: the byte before a line start is '\n'
+  std::vector<char> buf(1u << 20);
+  uint64_t pos = offset - 1;                               // file position of buf[0]
+  std::vector<uint64_t> ls;                                // line starts found so far (file offsets), with their first byte
+  std::vector<char> lc;
+  uint64_t answer = size;
+  bool found = false;
+  while (!found && pos < size) {
+    const ssize_t got = pread(fd, buf.data(), buf.size(), (off_t)pos);
+    if (got <= 0) break;
+    for (ssize_t i = 0; i < got && !found; i++) {
+      if (buf[i] != '\n') continue;
+      const uint64_t line = pos + (uint64_t)i + 1;
+      if (line >= size) break;
+      char c;
+      if (i + 1 < got) c = buf[i + 1];
+      else if (pread(fd, &c, 1, (off_t)line) != 1) break;
+      if (format == MGC_TEXT_FASTA) { if (c == '>') { answer = line; found = true; } continue; }
+      ls.push_back(line); lc.push_back(c);
+      const size_t m = ls.size();
+      if (m >= 3 && lc[m - 3] == '@' && lc[m - 1] == '+') { answer = ls[m - 3]; found = true; }
+    }
+    pos += (uint64_t)got;
+  }
+  close(fd);
+  *start = found ? answer : size;
+  return MGC_OK;
+}
+
+// A whole uncompressed FASTA/FASTQ file: `reader_threads` threads pread() 32 MiB chunks straight into the ring of pinned
+// buffers (no intermediate copy), the calling thread uploads and parses them in file order.  A 20 GB FASTQ on tmpfs is
+// otherwise bound by ONE thread's read()+memcpy (measured 11 GB/s, 1.8 s of a 3 s file -> database run).
+extern "C" int mgc_push_text_file(mgc_session *s, const char *path, int format, int reader_threads) {
+  return mgc_push_text_file_range(s, path, format, reader_threads, 0, ~0ull);
+}
+
+// bytes [range_begin, range_end) of the file (range_begin at a record start; range_end = the next reader's start, or past the end)
+extern "C" int mgc_push_text_file_range(mgc_session *s, const char *path, int format, int reader_threads, uint64_t range_begin, uint64_t range_end) {
+  if (!s || !path) return MGC_EINVAL;
+  uint64_t file_size = 0;
+  const int fd = open_regular(&s->err, "mgc_push_text_file", path, "regular file", 0, &file_size);
+  if (fd < 0) return MGC_EINVAL;
+  if (format == 0) {
+    char c = 0;
+    format = sniff_text_format(fd, &c);
+    if (!format) { close(fd); set_err(&s->err, "'%s' is neither FASTA nor FASTQ (record starts with '%c')", path, c); return MGC_EFORMAT; }
+  }
+  if (range_end > file_size) range_end = file_size;
+  if (range_begin > range_end) range_begin = range_end;
+  const uint64_t size = range_end - range_begin;            // every chunk offset below is relative to the window
+  int rc = mgc_begin_text(s, format);
+  if (rc != MGC_OK) { close(fd); return rc; }
+
+  const size_t CH = mgc_session::TEXT_CHUNK;
+  const uint64_t nchunks = (size + CH - 1) / CH;
+  const mgc::ChunkRingGeometry g = mgc::chunk_ring_geometry(reader_threads, nchunks, mgc_session::TEXT_RING_MAX);
+  auto fill = [&](int, uint64_t c, char *dst, int *err_no) -> int64_t {
+    const uint64_t off = c * CH;
+    const size_t want = (size_t)std::min<uint64_t>(CH, size - off);
+    size_t have = 0;
+    while (have < want) {
+      const ssize_t r = pread(fd, dst + have, want - have, (off_t)(range_begin + off + have));
+      if (r < 0 && errno == EINTR) continue;
+      if (r <= 0) { *err_no = r < 0 ? errno : 0; return -1; }          // an error, or the file shrank under us
+      have += (size_t)r;
+    }
+    return (int64_t)have;
+  };
+  const mgc::ChunkRingResult res = run_session_ring(s, nchunks, g, fill, [&](uint64_t, const char *p, size_t len) { return mgc::text_submit(s, p, len); });
+  mgc::text_drain(s);                                       // the last uploads still read from the ring
+  close(fd);
+  if (res.end == mgc::ChunkRingResult::ALLOC_FAILED) { set_err(&s->err, "mgc_push_text_file: pinned buffers: out of memory"); (void)mgc_end_text(s); return MGC_ENOMEM; }
+  if (getenv("MGC_IO_TRACE"))
+    fprintf(stderr, "[io] text file %.2f GB in %llu chunks, %d readers, ring %d: waiting for readers %.3f s, upload+parse submit (incl. waits "
+                    "for the device) %.3f s; readers: %.3f s in pread (%.1f GB/s each), %.3f s waiting for a free slot\n",
+            size / 1e9, (unsigned long long)nchunks, g.threads, g.slots, res.t_wait, res.t_consume, res.t_fill,
+            res.t_fill > 0 ? size / 1e9 / res.t_fill : 0.0, res.t_slot_wait);
+  if (res.end == mgc::ChunkRingResult::CONSUMER_STOPPED) rc = res.detail;
+  if (res.end == mgc::ChunkRingResult::FILL_FAILED) {
+    set_err(&s->err, "mgc_push_text_file: reading '%s' failed: %s", path, res.detail ? strerror(res.detail) : "the file shrank");
+    rc = MGC_EINVAL;
+  }
+  const int rc_end = mgc_end_text(s);                       // closes the file in every case (rolls it back on MGC_EFORMAT)
+  return rc != MGC_OK ? rc : rc_end;
+}
+
+// ---- a BGZF file (bgzip'd FASTA / FASTQ; mgc_bgzf.hpp) inflated by `threads` threads STRAIGHT into the pinned upload ring (round 6) ----
+// Through the generic reader (meryl_seq.cpp: BgzfSource -> msr_read_text -> mgc_push_text) the text of a batch of blocks was copied twice
+// by the calling thread (out of the inflater's batch, into the pinned buffer) behind batches of 32 MiB whose threads were spawned per
+// batch: 4 GB/s of text with 32 threads (profiles/r06w: bench.py e2e_compressed).  Here the file is mapped, its blocks are indexed in one
+// walk over the headers, chunks of <= TEXT_CHUNK of text are handed to persistent worker threads that inflate block after block into the
+// chunk's ring slot, and the calling thread uploads and parses the chunks in order.
+extern "C" int mgc_is_bgzf_file(const char *path) {
+  if (!path) return 0;
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return 0;
+  unsigned char head[64];
+  const ssize_t got = pread(fd, head, sizeof(head), 0);
+  close(fd);
+  mgc::BgzfBlock b;
+  return (got >= 18 && mgc::bgzf_parse_block(head, (size_t)got, &b) != mgc::BGZF_NOT_BLOCK) ? 1 : 0;
+}
+
+extern "C" int mgc_push_text_bgzf_file(mgc_session *s, const char *path, int format, int threads) {
+  if (!s || !path) return MGC_EINVAL;
+  uint64_t fsize = 0;
+  const int fd = open_regular(&s->err, "mgc_push_text_bgzf_file", path, "regular BGZF file", 28, &fsize);
+  if (fd < 0) return MGC_EINVAL;
+  const unsigned char *map = reinterpret_cast<const unsigned char *>(mmap(nullptr, fsize, PROT_READ, MAP_SHARED, fd, 0));
+  if (map == MAP_FAILED) { close(fd); set_err(&s->err, "mgc_push_text_bgzf_file: mmap of '%s' failed: %s", path, strerror(errno)); return MGC_EINVAL; }
+  std::vector<z_stream> zs;                                     // one inflater per worker thread, n_z of them set up
+  int n_z = 0;
+  auto release = [&]() { for (int t = 0; t < n_z; t++) inflateEnd(&zs[t]); munmap(const_cast<unsigned char *>(map), fsize); close(fd); };
+  const mgc::BgzfPlan plan = mgc::bgzf_plan_chunks(map, fsize, mgc_session::TEXT_CHUNK);
+  const std::vector<mgc::BgzfBlock> &blocks = plan.blocks;
+  if (plan.bad != mgc::BGZF_BLOCK) {
+    release();
+    if (plan.bad == mgc::BGZF_BAD_ISIZE) set_err(&s->err, "'%s': corrupt BGZF block at offset %zu (ISIZE %u)", path, (size_t)plan.bad_off, plan.bad_isize);
+    else set_err(&s->err, "'%s': not a BGZF block at offset %zu (plain gzip data, or a truncated file)", path, (size_t)plan.bad_off);
+    return MGC_EFORMAT;
+  }
+  const uint64_t nchunks = plan.chunks.size();
+  const mgc::ChunkRingGeometry g = mgc::chunk_ring_geometry(threads, nchunks, mgc_session::TEXT_RING_MAX);
+  zs.resize(g.threads);
+  while (n_z < g.threads && inflateInit2(&zs[n_z], -15) == Z_OK) n_z++;
+  if (n_z < g.threads) { release(); set_err(&s->err, "zlib: inflateInit2 failed"); return MGC_ENOMEM; }
+  if (format == 0) {                                            // sniff: the first byte of text that is not white space
+    char c = 0;
+    std::vector<unsigned char> tmp(65536);
+    for (size_t i = 0; i < blocks.size() && !c; i++) {
+      if (!mgc::bgzf_inflate_block(zs[0], map + blocks[i].off, blocks[i], tmp.data())) { release(); set_err(&s->err, "'%s': BGZF block %zu failed to inflate (corrupt file)", path, i); return MGC_EFORMAT; }
+      c = first_text_byte(tmp.data(), blocks[i].isize);
+    }
+    format = format_of(c);
+    if (!format) { release(); set_err(&s->err, "'%s' is neither FASTA nor FASTQ (record starts with '%c')", path, c ? c : '?'); return MGC_EFORMAT; }
+  }
+  int rc = mgc_begin_text(s, format);
+  if (rc != MGC_OK) { release(); return rc; }
+
+  auto fill = [&](int t, uint64_t c, char *dst, int *bad_block) -> int64_t {
+    size_t at = 0;
+    for (size_t i = plan.chunks[c].first; i < plan.chunks[c].last; i++) {
+      if (!mgc::bgzf_inflate_block(zs[t], map + blocks[i].off, blocks[i], reinterpret_cast<unsigned char *>(dst) + at)) { *bad_block = (int)i; return -1; }
+      at += blocks[i].isize;
+    }
+    return (int64_t)at;
+  };
+  uint64_t text_total = 0;
+  auto consume = [&](uint64_t, const char *p, size_t len) {
+    text_total += len;
+    return len ? mgc::text_submit(s, p, len) : MGC_OK;          // (a chunk of empty blocks: the end-of-file marker)
+  };
+  const mgc::ChunkRingResult res = run_session_ring(s, nchunks, g, fill, consume);
+  mgc::text_drain(s);                                           // the last uploads still read from the ring
+  release();
+  if (getenv("MGC_IO_TRACE"))
+    fprintf(stderr, "[io] BGZF file %.2f GB -> %.2f GB of text in %llu chunks (%zu blocks), %d inflaters, ring %d: waiting for the inflaters %.3f s, "
+                    "upload+parse submit (incl. waits for the device) %.3f s\n", fsize / 1e9, text_total / 1e9, (unsigned long long)nchunks, blocks.size(),
+            g.threads, g.slots, res.t_wait, res.t_consume);
+  if (res.end == mgc::ChunkRingResult::ALLOC_FAILED) { set_err(&s->err, "mgc_push_text_bgzf_file: pinned buffers: out of memory"); (void)mgc_end_text(s); return MGC_ENOMEM; }
+  if (res.end == mgc::ChunkRingResult::FILL_FAILED) {
+    // what the file has put into the stream is taken back (as for a file that stops being strict FASTQ), unless part of it already went
+    // into a counted batch
+    const unsigned long long bb = (unsigned long long)res.detail;
+    rc = mgc::text_rollback(s);
+    if (rc == MGC_EINVAL) set_err(&s->err, "'%s': BGZF block %llu failed to inflate after part of the file was counted (input larger than one batch)", path, bb);
+    if (rc != MGC_OK) return rc;
+    set_err(&s->err, "'%s': BGZF block %llu failed to inflate (corrupt file)", path, bb);
+    return MGC_EFORMAT;
+  }
+  if (res.end == mgc::ChunkRingResult::CONSUMER_STOPPED) rc = res.detail;
+  const int rc_end = mgc_end_text(s);                           // closes the file in every case (rolls it back on MGC_EFORMAT)
+  return rc != MGC_OK ? rc : rc_end;
+}

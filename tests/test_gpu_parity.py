@@ -1080,8 +1080,9 @@ def test_device_text_parse_large_mixed_and_refusal(ops, oracle_lib, torch_cuda):
 
 
 def test_push_text_file_reader_ring(ops, oracle_lib, torch_cuda, tmp_path):
-    """mgc_push_text_file: a FASTQ file of ~10 upload chunks read by several threads into the pinned ring (chunks reused,
-    last chunk partial), a one-chunk FASTA, an empty file and a refused file, against the bases pushed directly."""
+    """mgc_push_text_file: a FASTQ file of ~10 upload chunks read by several threads into the pinned ring (last chunk partial;
+    no slot is used twice here: slot reuse is tests/test_input_host.py::test_ring_cases), a one-chunk FASTA, an empty file and a
+    refused file, against the bases pushed directly."""
     from meryl_amd import capi
     import ctypes
     k = 21
