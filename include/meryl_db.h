@@ -232,6 +232,36 @@ int mgc_db_merge(const char *const *inputs, uint32_t n_inputs, int op, const cha
  * increase ... modulo by it; src/meryl/merylOp-nextMer.C:490-557): k-mers whose new value is 0 are not written. */
 int mgc_db_filter(const char *input, int value_op, uint64_t constant, const char *output, int device, int host_threads);
 
+/* A whole tree of merge and value operations over databases, evaluated file slice by file slice with every intermediate
+ * result kept in HBM -- what the reference does when operations are nested on one command line (the inputs of a
+ * merylOperation are other operations, src/meryl/merylOp-nextMer.C:418-683; only operations given `output` write,
+ * :227).  nodes[]: a leaf names its database in `path`; an inner node holds a MGC_MERGE_* (merge) or MGC_VALUE_* + constant
+ * (value) operation over children[first_child .. first_child + n_children), and writes a database to `path` unless it is
+ * NULL -- the slice goes on to the parent either way.  Per file slice 0..63: every leaf's slice is loaded once, the nodes
+ * are evaluated bottom-up (a merge of 3..MGC_MERGE_MANY_MAX inputs in one pass pair, mgc_dev_merge_many_*; more inputs, or
+ * every merge under MGC_MERGE_MANY=0 in the environment, by the left fold of mgc_db_merge), and the root's slice is handed to
+ * `cb` (may be NULL) as host arrays, from the calling thread, files ascending.  An output has the prefix size of its
+ * leftmost leaf, no labels, and the files a staged run through mgc_db_merge / mgc_db_filter writes for that node, byte for
+ * byte.  Checked before any device call and before any output directory exists (MGC_EINVAL, text: mgc_db_stream_error(NULL)):
+ * indices in range, every node reached at most once, a leaf without children, a value node with exactly one, a merge node
+ * with at least one; every leaf opens, holds the same k and neither labels nor a multiset; no output named twice or also
+ * a leaf. */
+#define MGC_NODE_DATABASE 0
+#define MGC_NODE_MERGE    1
+#define MGC_NODE_VALUE    2
+typedef struct mgc_eval_node {
+  int32_t     kind;                /* MGC_NODE_* */
+  int32_t     op;                  /* MGC_MERGE_* / MGC_VALUE_* (ignored for a leaf) */
+  uint64_t    constant;            /* value operations */
+  const char *path;                /* leaf: the database; inner node: its output, or NULL */
+  uint32_t    first_child, n_children;   /* range of children[] */
+} mgc_eval_node;
+/* hi_or_null: NULL for k <= 32; values: uint32 per k-mer; the arrays are valid during the call only */
+typedef void (*mgc_eval_slice_cb)(void *ctx, uint32_t file, const uint64_t *lo, const uint64_t *hi_or_null,
+                                  const uint32_t *values, uint64_t n);
+int mgc_db_eval(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children, uint32_t root,
+                mgc_eval_slice_cb cb, void *ctx, int device, int host_threads);
+
 /* ONE count spread over the GPUs of a node, from one process (meryl_amd/csrc/mgc_node.cpp): rank r's reads are the
  * n_bases[r] bytes at d_bases[r] on device devices[r] (the base stream mgc_push_bases takes; with cfg->homopoly_compress
  * every rank's stream must hold whole sequences).  Every rank extracts the k-mers of its reads, the k-mers travel over

@@ -201,6 +201,24 @@ int mgc_dev_merge_count_values(const void *d_keys_a, const uint32_t *d_counts_a,
                                const uint32_t *d_counts_b, uint64_t nb, uint32_t key_words, int op, void *d_workspace,
                                size_t workspace_bytes, uint64_t *n_out, void *stream);
 
+/* Merge of 2..MGC_MERGE_MANY_MAX streams at once -- the reference's k-way step itself (merylOperation::nextMer,
+ * src/meryl/merylOp-nextMer.C:478-523: the smallest k-mer over the inputs and _actLen / _actCount[] / _actIndex[], the inputs
+ * that hold it in input order; :559-612 with findMin/Max/SumCount and subtractCount :23-62 combine them).  Every
+ * MGC_MERGE_* operation, MGC_MERGE_UNION included.  d_keys / d_values / n: HOST arrays of n_inputs device pointers and
+ * lengths (distinct ascending keys each, a length below 2^32).  The result equals the left fold of the two-input merge over
+ * the same inputs element by element (a sum that wraps to 0 is kept).  Two steps like the two-input merge; the count step
+ * takes the values, since MGC_MERGE_SUBTRACT needs them.  n_inputs outside 2..32 or an operation outside 0..10: MGC_EINVAL.
+ * mgc_dev_merge_many_tile: the merged positions one workgroup handles (tile borders fall on whole groups of equal k-mers, at
+ * most n_inputs - 1 positions earlier). */
+#define MGC_MERGE_MANY_MAX 32
+uint32_t mgc_dev_merge_many_tile(uint32_t key_words);
+size_t mgc_dev_merge_many_workspace_bytes(const uint64_t *n, uint32_t n_inputs, uint32_t key_words);
+int mgc_dev_merge_many_count(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *n, uint32_t n_inputs,
+                             uint32_t key_words, int op, void *d_workspace, size_t workspace_bytes, uint64_t *n_out, void *stream);
+int mgc_dev_merge_many_emit(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *n, uint32_t n_inputs,
+                            uint32_t key_words, int op, void *d_workspace, size_t workspace_bytes, void *d_keys_out,
+                            uint32_t *d_values_out, void *stream);
+
 /* One (k-mer, value) stream through a single-input operation of src/meryl/merylOp-nextMer.C:490-557: the value filters
  * (the value passes or the k-mer is dropped) and the arithmetic operations (with the reference's overflow / underflow /
  * divide-by-zero results; a k-mer whose new value is 0 is dropped, :470-474).  Two steps like the merge. */

@@ -25,6 +25,7 @@ SYMBOLS = (
     "mgc_get_result_info", "mgc_get_result_device", "mgc_copy_result", "mgc_finish", "mgc_finish_labelled",
     "mgc_set_profiling", "mgc_get_profile", "mgc_dev_synth_reads", "mgc_dev_synth_reads_ex", "mgc_version",
     "mgc_dev_merge_workspace_bytes", "mgc_dev_merge_count", "mgc_dev_merge_count_values", "mgc_dev_merge_emit",
+    "mgc_dev_merge_many_tile", "mgc_dev_merge_many_workspace_bytes", "mgc_dev_merge_many_count", "mgc_dev_merge_many_emit",
     "mgc_dev_select_workspace_bytes", "mgc_dev_select_count", "mgc_dev_select_emit",
     "mgc_dev_homopoly_workspace_bytes", "mgc_dev_homopoly_compress", "mgc_set_batch_bases", "mgc_prepare", "mgc_set_result_budget", "mgc_result_out_of_core",
     # include/meryl_db.h
@@ -34,7 +35,7 @@ SYMBOLS = (
     "mdb_reader_file_index", "mdb_reader_block_header", "mdb_reader_read_block_raw", "mdb_reader_raw_file", "mdb_reader_close",
     "mdb_free", "mgc_write_database", "mgc_write_database_profiled",
     "mgc_db_stream_open", "mgc_db_stream_write", "mgc_db_stream_sync", "mgc_db_stream_close", "mgc_db_stream_error", "mgc_db_stream_queued", "mgc_db_stream_done", "mgc_db_stream_wait_buffers",
-    "mgc_runs_open", "mgc_runs_add", "mgc_runs_write", "mgc_runs_get_profile", "mgc_runs_error", "mgc_runs_close", "mgc_get_runs_profile", "mgc_db_merge", "mgc_db_filter", "mgc_count_node", "mgc_count_node_batched", "mgc_count_node_staged", "mgc_node_plan",
+    "mgc_runs_open", "mgc_runs_add", "mgc_runs_write", "mgc_runs_get_profile", "mgc_runs_error", "mgc_runs_close", "mgc_get_runs_profile", "mgc_db_merge", "mgc_db_filter", "mgc_db_eval", "mgc_count_node", "mgc_count_node_batched", "mgc_count_node_staged", "mgc_node_plan",
     # include/meryl_lookup.h
     "mgc_lookup_load", "mgc_lookup_estimate", "mgc_lookup_from_device", "mgc_lookup_free", "mgc_lookup_get_info", "mgc_lookup_error",
     "mgc_lookup_values", "mgc_lookup_stream", "mgc_lookup_existence", "mgc_lookup_positions", "mgc_lookup_report", "mgc_lookup_filter_text", "mgc_lookup_filter_files",
@@ -72,6 +73,23 @@ class CountConfig(ctypes.Structure):
         ("reserved0", ctypes.c_uint32),
         ("label_constant", ctypes.c_uint64),
     ]
+
+
+class EvalNode(ctypes.Structure):
+    """mgc_eval_node (include/meryl_db.h)"""
+    _fields_ = [
+        ("kind", ctypes.c_int32),
+        ("op", ctypes.c_int32),
+        ("constant", ctypes.c_uint64),
+        ("path", ctypes.c_char_p),
+        ("first_child", ctypes.c_uint32),
+        ("n_children", ctypes.c_uint32),
+    ]
+
+
+NODE_DATABASE, NODE_MERGE, NODE_VALUE = 0, 1, 2
+EVAL_SLICE_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                 ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64)
 
 
 class ResultInfo(ctypes.Structure):
@@ -335,6 +353,10 @@ def lib():
     sig("mgc_dev_merge_count", i32, vp, u64, vp, u64, u32, i32, vp, sz, P(u64), vp)
     sig("mgc_dev_merge_emit", i32, vp, vp, u64, vp, vp, u64, u32, i32, vp, sz, vp, vp, vp)
     sig("mgc_dev_merge_count_values", i32, vp, vp, u64, vp, vp, u64, u32, i32, vp, sz, P(u64), vp)
+    sig("mgc_dev_merge_many_tile", u32, u32)
+    sig("mgc_dev_merge_many_workspace_bytes", sz, P(u64), u32, u32)
+    sig("mgc_dev_merge_many_count", i32, P(vp), P(vp), P(u64), u32, u32, i32, vp, sz, P(u64), vp)
+    sig("mgc_dev_merge_many_emit", i32, P(vp), P(vp), P(u64), u32, u32, i32, vp, sz, vp, vp, vp)
     sig("mgc_dev_select_workspace_bytes", sz, u64)
     sig("mgc_dev_select_count", i32, vp, vp, u64, u32, i32, u64, vp, sz, P(u64), vp)
     sig("mgc_dev_select_emit", i32, vp, vp, u64, u32, i32, u64, vp, sz, vp, vp, vp)
@@ -414,6 +436,7 @@ def lib():
     sig("mgc_db_stream_close", i32, vp, P(DbWriteProfile))
     sig("mgc_db_stream_error", ctypes.c_char_p, vp)
     sig("mgc_db_merge", i32, P(ctypes.c_char_p), u32, i32, ctypes.c_char_p, i32, i32)
+    sig("mgc_db_eval", i32, P(EvalNode), u32, P(u32), u32, u32, EVAL_SLICE_CB, vp, i32, i32)
     sig("mgc_count_node", i32, P(CountConfig), u32, P(ctypes.c_int), P(vp), P(u64), ctypes.c_char_p, i32, P(NodeProfile))
     sig("mgc_count_node_batched", i32, P(CountConfig), u32, P(ctypes.c_int), P(vp), P(u64), u64, ctypes.c_char_p, i32, P(NodeProfile))
     sig("mgc_staged_bases", i32, vp, P(vp), P(u64))

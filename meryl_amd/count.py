@@ -220,6 +220,35 @@ def dev_merge(keys_a, counts_a, keys_b, counts_b, op="union-sum"):
     return out_k, out_c
 
 
+MERGE_MANY_OPS = dict(MERGE_OPS, union=10)
+
+
+def dev_merge_many(keys_list, counts_list, op="union-sum"):
+    """2..32 (k-mer, value) streams with distinct ascending keys (int64[N] / int64[N, 2] cuda tensors, int32 values) -> the
+    reference's k-way merge of them, every input read once per pass (mgc_dev_merge_many_*).  op: a MERGE_OPS word, "union",
+    or the operation's number."""
+    L = capi.lib()
+    m = len(keys_list)
+    kw = 2 if keys_list[0].dim() == 2 else 1
+    dev = keys_list[0].device
+    kp = (ctypes.c_void_p * m)(*[_ptr(k) if k.shape[0] else None for k in keys_list])
+    cp = (ctypes.c_void_p * m)(*[_ptr(c) if c.shape[0] else None for c in counts_list])
+    ns = (ctypes.c_uint64 * m)(*[int(k.shape[0]) for k in keys_list])
+    code = op if isinstance(op, int) else MERGE_MANY_OPS[op]
+    ws_bytes = max(int(L.mgc_dev_merge_many_workspace_bytes(ns, m, kw)), 256)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    n = ctypes.c_uint64(0)
+    capi.check(L.mgc_dev_merge_many_count(kp, cp, ns, m, kw, code, _ptr(ws), ws_bytes, ctypes.byref(n), _stream_ptr()),
+               "mgc_dev_merge_many_count")
+    out_k = _u64(n.value * kw, dev)
+    if kw == 2:
+        out_k = out_k.view(n.value, 2)
+    out_c = torch.empty(n.value, dtype=torch.int32, device=dev)
+    capi.check(L.mgc_dev_merge_many_emit(kp, cp, ns, m, kw, code, _ptr(ws), ws_bytes, _ptr(out_k), _ptr(out_c), _stream_ptr()),
+               "mgc_dev_merge_many_emit")
+    return out_k, out_c
+
+
 def dev_block_offsets(unique, w_data, n_prefix):
     out = _u64(n_prefix + 1, unique.device)
     kw = 2 if unique.dim() == 2 else 1

@@ -10,7 +10,9 @@
 // databases it writes.  Beyond the count path: `histogram`, `dumpFile`, the set operations over
 // databases (union[-min|-max|-sum], intersect[-min|-max|-sum], subtract, difference, symmetric-difference;
 // merylOp-nextMer.C:559-613) and the single-input value filters / arithmetic (less-than ... modulo; :490-557), all merged on
-// the device.  What stays refused: statistics, compare, ploidy, Canu sequence stores (segment=); CRAM only when no `samtools` is on the PATH.
+// the device.  Set and value operations nest as in the reference: a whole tree of them over databases and finished counts
+// runs as one evaluation with the intermediate results kept on the device (mgc_db_eval), `output` is optional on every
+// one of them, and `print [operation]` prints the tree's result (quick-start.rst:327-333).  What stays refused: statistics, compare, ploidy, Canu sequence stores (segment=); CRAM only when no `samtools` is on the PATH.
 #include "../../include/meryl_db.h"
 #include "../../include/meryl_gpu_count.h"
 #include "../../include/meryl_seq.h"
@@ -102,16 +104,19 @@ void usage(const char *prog) {
   fprintf(stderr,
           "usage: %s [k=<K>] [memory=<GB>] [threads=<T>] [gpus=<N>] [n=<kmers>] [compress] [-l <label-bits>] [-C] [-Q] [-V]\n"
           "          count|count-forward|count-reverse [label=#<n>] <reads.fa|fq[.gz]|sam|bam> ... output <database.meryl>\n"
-          "       %s print <database.meryl>\n"
+          "       %s print <database.meryl | [operation]>\n"
           "       %s dumpIndex <database.meryl>\n"
           "       %s dumpFile <database.meryl>/0x######\n"
-          "       %s union[-min|-max|-sum]|intersect[-min|-max|-sum]|subtract|difference|symmetric-difference <db | [operation]> ... output <db>\n"
-          "       %s less-than|greater-than|at-least|at-most|equal-to|not-equal-to <N | distinct=<f> | word-frequency=<f>> <db | [operation]> output <db>\n"
-          "       %s increase|decrease|multiply|divide|divide-round|modulo <N> <db | [operation]> output <db>\n"
+          "       %s union[-min|-max|-sum]|intersect[-min|-max|-sum]|subtract|difference|symmetric-difference <db | [operation]> ... [output <db>]\n"
+          "       %s less-than|greater-than|at-least|at-most|equal-to|not-equal-to <N | distinct=<f> | word-frequency=<f>> <db | [operation]> [output <db>]\n"
+          "       %s increase|decrease|multiply|divide|divide-round|modulo <N> <db | [operation]> [output <db>]\n"
           "\n"
           "  MI355X-native implementation of the `count` path of marbl/meryl.  Words are processed left to\n"
           "  right; options apply to the operations that follow.  A leading '[' and trailing ']' group the\n"
-          "  words of one operation; an operation inside another one's brackets is its input.  Other meryl operations are\n"
+          "  words of one operation; an operation inside another one's brackets is its input.  A tree of set and value\n"
+          "  operations is evaluated in one pass with its intermediate results on the device: only operations given\n"
+          "  'output' write a database, and 'print [operation]' prints the result of the tree (distinct= and\n"
+          "  word-frequency= need a database, or an input operation that writes one).  Other meryl operations are\n"
           "  not part of this build.\n",
           prog, prog, prog, prog, prog, prog, prog);
 }
@@ -487,35 +492,38 @@ int run_count(const Globals &g, const Operation &op) {
   return 0;
 }
 
-int run_print(const Operation &op) {
+// one slice as `print` writes it: k-mer <TAB> value (merylOp-nextMer.C:673-676; meryl2 adds the label in binary,
+// src/meryl2/merylOp-nextMer.C:36-43); hi / lb may be null
+void print_kmers(uint32_t k, uint32_t label_size, const uint64_t *lo, const uint64_t *hi, const uint32_t *cn, const uint64_t *lb, uint64_t n) {
   static const char acgt[4] = { 'A', 'C', 'T', 'G' };
-  for (const std::string &dbn : op.db_inputs) {
-    mdb_reader *r = mdb_reader_open(dbn.c_str());
-    if (!r) die("ERROR: %s", mdb_last_error());
-    mdb_info info;
-    mdb_reader_info(r, &info);
-    std::vector<char> kstr(info.k + 1, 0);
-    for (uint32_t ff = 0; ff < MGC_NUM_FILES; ff++) {            // ascending == `threads=1 print` order (quick-start.rst:74-77)
-      uint64_t *lo = nullptr, *hi = nullptr, *lb = nullptr, n = 0;
-      uint32_t *cn = nullptr;
-      if (mdb_reader_read_file_ex(r, ff, &lo, &hi, &cn, &lb, &n) != MGC_OK) die("ERROR: %s", mdb_last_error());
-      char lbits[72];
-      for (uint64_t i = 0; i < n; i++) {
-        const unsigned __int128 m = ((unsigned __int128)hi[i] << 64) | lo[i];
-        for (uint32_t b = 0; b < info.k; b++) kstr[b] = acgt[(unsigned)(m >> (2 * (info.k - 1 - b))) & 3];
-        if (info.label_size == 0) {
-          fprintf(stdout, "%s\t%u\n", kstr.data(), cn[i]);                                             // merylOp-nextMer.C:673-676
-        } else {                                                                                       // meryl2: + the label in binary
-          for (uint32_t b = 0; b < info.label_size; b++) lbits[b] = ((lb[i] >> (info.label_size - 1 - b)) & 1) ? '1' : '0';
-          lbits[info.label_size] = 0;                                                                  // (src/meryl2/merylOp-nextMer.C:36-43)
-          fprintf(stdout, "%s\t%u\t%s\n", kstr.data(), cn[i], lbits);
-        }
-      }
-      mdb_free(lo); mdb_free(hi); mdb_free(cn); mdb_free(lb);
+  std::vector<char> kstr(k + 1, 0);
+  char lbits[72];
+  for (uint64_t i = 0; i < n; i++) {
+    const unsigned __int128 m = ((unsigned __int128)(hi ? hi[i] : 0) << 64) | lo[i];
+    for (uint32_t b = 0; b < k; b++) kstr[b] = acgt[(unsigned)(m >> (2 * (k - 1 - b))) & 3];
+    if (label_size == 0 || !lb) {
+      fprintf(stdout, "%s\t%u\n", kstr.data(), cn[i]);
+    } else {
+      for (uint32_t b = 0; b < label_size; b++) lbits[b] = ((lb[i] >> (label_size - 1 - b)) & 1) ? '1' : '0';
+      lbits[label_size] = 0;
+      fprintf(stdout, "%s\t%u\t%s\n", kstr.data(), cn[i], lbits);
     }
-    mdb_reader_close(r);
   }
-  return 0;
+}
+
+void print_database(const std::string &dbn) {
+  mdb_reader *r = mdb_reader_open(dbn.c_str());
+  if (!r) die("ERROR: %s", mdb_last_error());
+  mdb_info info;
+  mdb_reader_info(r, &info);
+  for (uint32_t ff = 0; ff < MGC_NUM_FILES; ff++) {            // ascending == `threads=1 print` order (quick-start.rst:74-77)
+    uint64_t *lo = nullptr, *hi = nullptr, *lb = nullptr, n = 0;
+    uint32_t *cn = nullptr;
+    if (mdb_reader_read_file_ex(r, ff, &lo, &hi, &cn, &lb, &n) != MGC_OK) die("ERROR: %s", mdb_last_error());
+    print_kmers(info.k, info.label_size, lo, hi, cn, lb, n);
+    mdb_free(lo); mdb_free(hi); mdb_free(cn); mdb_free(lb);
+  }
+  mdb_reader_close(r);
 }
 
 // `meryl histogram <db>`: value <TAB> number of distinct k-mers with that value, ascending -- the histogram the count
@@ -603,54 +611,116 @@ int run_dump_index(const Operation &op) {
   return 0;
 }
 
-// `union-sum a.meryl b.meryl [count ... output c.meryl] output u.meryl` and the five related operations
-// (merylOp-nextMer.C:560-612): the inputs -- databases named on the command line, and the outputs of child operations,
-// which ran first (meryl.C:211-227 turns a finished count into a pass-through over its new database) -- are merged on
-// the device, file slice by file slice (mgc_db_merge).
-int run_merge(const Globals &g, const std::vector<Operation> &ops, const Operation &op) {
-  if (op.output.empty()) die("ERROR: operation '%s' needs an 'output <database>' in this build.", op.word.c_str());
-  std::vector<std::string> inputs;
-  for (const InputRef &in : op.inputs) inputs.push_back(in.child >= 0 ? ops[in.child].output : in.path);
-  if (inputs.empty()) die("ERROR: operation '%s' has no inputs.", op.word.c_str());
-  for (const std::string &n : inputs) if (!dir_has_index(n)) die("ERROR: input '%s' is not a meryl database.", n.c_str());
-  std::vector<const char *> names;
-  for (const std::string &n : inputs) names.push_back(n.c_str());
-  if (g.verbosity > 0) {
-    fprintf(stderr, "\nPROCESSING %s of %zu database%s into '%s'.\n", op.word.c_str(), inputs.size(), inputs.size() == 1 ? "" : "s", op.output.c_str());
-    for (const std::string &n : inputs) fprintf(stderr, "  %15s: %s\n", "database", n.c_str());
+// `union-sum a.meryl [greater-than 1 b.meryl] [count ... output c.meryl] output u.meryl`: a tree of the set operations
+// (merylOp-nextMer.C:559-612) and the single-input value operations (:490-557) runs as ONE evaluation (mgc_db_eval): the
+// slices of its leaves -- databases named on the command line, and the outputs of counts, which ran first (meryl.C:211-227
+// turns a finished count into a pass-through over its new database) -- are loaded once per file, every operation's result
+// stays on the device, and only operations given `output` write, as in the reference (:227).  `print` of such a tree
+// receives the root's slices, files ascending.
+bool is_tree_op(const Operation &op) { return op.kind == OP_MERGE || op.kind == OP_VALUE; }
+
+struct EvalTree {
+  std::vector<mgc_eval_node>         nodes;
+  std::vector<std::vector<uint32_t>> kids;
+  std::string                        first_leaf;
+};
+
+// distinct=<f> / word-frequency=<f> turn into a threshold from the input's stored histogram (initializeThreshold, :65-118)
+uint64_t threshold_from_histogram(const Operation &op, const std::string &in) {
+  uint64_t c = op.constant;
+  mdb_reader *r = mdb_reader_open(in.c_str());
+  if (!r) die("ERROR: %s", mdb_last_error());
+  mdb_info info;
+  mdb_reader_info(r, &info);
+  std::vector<uint64_t> hv(info.hist_len), ho(info.hist_len);
+  if (info.hist_len) mdb_reader_histogram(r, hv.data(), ho.data());
+  mdb_reader_close(r);
+  if (op.frac_distinct >= 0) {                                             // :104-114
+    const uint64_t target = (uint64_t)(op.frac_distinct * (double)info.num_distinct);
+    uint64_t n = 0;
+    for (uint64_t i = 0; i < info.hist_len; i++) { n += ho[i]; if (n >= target) { c = hv[i]; break; } }
   }
-  if (mgc_db_merge(names.data(), (uint32_t)names.size(), op.merge_op, op.output.c_str(), -1, (int)g.threads) != MGC_OK)
-    die("ERROR: %s", mgc_db_stream_error(nullptr));
-  return 0;
+  if (op.word_freq >= 0) c = (uint64_t)(op.word_freq * (double)info.num_total);   // :116-118
+  return c;
 }
 
-// `less-than 5 a.meryl output b.meryl`, `divide 2 [count ...] output h.meryl`: the single-input operations
-// (merylOp-nextMer.C:490-557).  distinct=<f> / word-frequency=<f> turn into a threshold from the input's stored histogram
-// (initializeThreshold, :65-118).
-int run_value(const Globals &g, const std::vector<Operation> &ops, const Operation &op) {
-  if (op.output.empty()) die("ERROR: operation '%s' needs an 'output <database>' in this build.", op.word.c_str());
-  if (op.inputs.size() != 1) die("ERROR: operation '%s' takes exactly one input.", op.word.c_str());
-  const std::string in = op.inputs[0].child >= 0 ? ops[op.inputs[0].child].output : op.inputs[0].path;
-  if (!dir_has_index(in)) die("ERROR: input '%s' is not a meryl database.", in.c_str());
-  uint64_t c = op.constant;
-  if (op.frac_distinct >= 0 || op.word_freq >= 0) {
-    mdb_reader *r = mdb_reader_open(in.c_str());
-    if (!r) die("ERROR: %s", mdb_last_error());
-    mdb_info info;
-    mdb_reader_info(r, &info);
-    std::vector<uint64_t> hv(info.hist_len), ho(info.hist_len);
-    if (info.hist_len) mdb_reader_histogram(r, hv.data(), ho.data());
-    mdb_reader_close(r);
-    if (op.frac_distinct >= 0) {                                             // :104-114
-      const uint64_t target = (uint64_t)(op.frac_distinct * (double)info.num_distinct);
-      uint64_t n = 0;
-      for (uint64_t i = 0; i < info.hist_len; i++) { n += ho[i]; if (n >= target) { c = hv[i]; break; } }
+int run_tree(const Globals &g, const std::vector<Operation> &ops, int root, bool print);
+
+uint32_t add_tree_node(const Globals &g, const std::vector<Operation> &ops, int i, EvalTree &t) {
+  const Operation &op = ops[i];
+  const bool by_histogram = op.kind == OP_VALUE && (op.frac_distinct >= 0 || op.word_freq >= 0);
+  if (op.kind == OP_MERGE && op.inputs.empty()) die("ERROR: operation '%s' has no inputs.", op.word.c_str());
+  if (op.kind == OP_VALUE && op.inputs.size() != 1) die("ERROR: operation '%s' takes exactly one input.", op.word.c_str());
+  std::vector<uint32_t> kids;
+  std::string leaf;
+  for (const InputRef &in : op.inputs) {
+    if (in.child >= 0 && is_tree_op(ops[in.child]) && !by_histogram) { kids.push_back(add_tree_node(g, ops, in.child, t)); continue; }
+    if (in.child >= 0 && is_tree_op(ops[in.child])) {
+      // a threshold from statistics needs a database (merylOp-nextMer.C:85-96); an input operation that writes one runs first
+      if (ops[in.child].output.empty()) die("ERROR: input '%s' to operation most-frequent is not a meryl database.", ops[in.child].word.c_str());
+      run_tree(g, ops, in.child, false);
     }
-    if (op.word_freq >= 0) c = (uint64_t)(op.word_freq * (double)info.num_total);   // :116-118
+    leaf = in.child >= 0 ? ops[in.child].output : in.path;
+    if (!dir_has_index(leaf)) die("ERROR: input '%s' is not a meryl database.", leaf.c_str());
+    if (t.first_leaf.empty()) t.first_leaf = leaf;
+    mgc_eval_node nd;
+    memset(&nd, 0, sizeof(nd));
+    nd.kind = MGC_NODE_DATABASE;
+    nd.path = in.child >= 0 ? ops[in.child].output.c_str() : in.path.c_str();
+    t.nodes.push_back(nd);
+    t.kids.emplace_back();
+    kids.push_back((uint32_t)t.nodes.size() - 1);
   }
-  if (c == ~0ull) die("ERROR: operation '%s' needs a number (threshold / constant).", op.word.c_str());
-  if (g.verbosity > 0) fprintf(stderr, "\nPROCESSING %s %" PRIu64 " of '%s' into '%s'.\n", op.word.c_str(), c, in.c_str(), op.output.c_str());
-  if (mgc_db_filter(in.c_str(), op.value_op, c, op.output.c_str(), -1, (int)g.threads) != MGC_OK) die("ERROR: %s", mgc_db_stream_error(nullptr));
+  mgc_eval_node nd;
+  memset(&nd, 0, sizeof(nd));
+  nd.path = op.output.empty() ? nullptr : op.output.c_str();
+  if (op.kind == OP_MERGE) {
+    nd.kind = MGC_NODE_MERGE;
+    nd.op = op.merge_op;
+    if (g.verbosity > 0)
+      fprintf(stderr, "\nPROCESSING %s of %zu input%s%s%s%s.\n", op.word.c_str(), kids.size(), kids.size() == 1 ? "" : "s",
+              op.output.empty() ? "" : " into '", op.output.c_str(), op.output.empty() ? "" : "'");
+  } else {
+    nd.kind = MGC_NODE_VALUE;
+    nd.op = op.value_op;
+    nd.constant = by_histogram ? threshold_from_histogram(op, leaf) : op.constant;
+    if (nd.constant == ~0ull) die("ERROR: operation '%s' needs a number (threshold / constant).", op.word.c_str());
+    if (g.verbosity > 0)
+      fprintf(stderr, "\nPROCESSING %s %" PRIu64 "%s%s%s.\n", op.word.c_str(), (uint64_t)nd.constant,
+              op.output.empty() ? "" : " into '", op.output.c_str(), op.output.empty() ? "" : "'");
+  }
+  t.nodes.push_back(nd);
+  t.kids.push_back(kids);
+  return (uint32_t)t.nodes.size() - 1;
+}
+
+struct PrintCtx { uint32_t k; };
+void print_slice(void *ctx, uint32_t, const uint64_t *lo, const uint64_t *hi, const uint32_t *values, uint64_t n) {
+  print_kmers(static_cast<PrintCtx *>(ctx)->k, 0, lo, hi, values, nullptr, n);
+}
+
+// the operation tree under ops[root] (paths point into `ops`, which outlives the call)
+int run_tree(const Globals &g, const std::vector<Operation> &ops, int root, bool print) {
+  EvalTree t;
+  const uint32_t r = add_tree_node(g, ops, root, t);
+  std::vector<uint32_t> children;
+  for (size_t v = 0; v < t.nodes.size(); v++) {
+    t.nodes[v].first_child = (uint32_t)children.size();
+    t.nodes[v].n_children = (uint32_t)t.kids[v].size();
+    children.insert(children.end(), t.kids[v].begin(), t.kids[v].end());
+  }
+  PrintCtx pc{0};
+  if (print) {                                                 // (every leaf holds the same k: mgc_db_eval checks)
+    mdb_reader *rd = mdb_reader_open(t.first_leaf.c_str());
+    if (!rd) die("ERROR: %s", mdb_last_error());
+    mdb_info info;
+    mdb_reader_info(rd, &info);
+    mdb_reader_close(rd);
+    pc.k = info.k;
+  }
+  if (mgc_db_eval(t.nodes.data(), (uint32_t)t.nodes.size(), children.data(), (uint32_t)children.size(), r, print ? print_slice : nullptr, &pc,
+                  -1, (int)g.threads) != MGC_OK)
+    die("ERROR: %s", mgc_db_stream_error(nullptr));
   return 0;
 }
 
@@ -834,18 +904,24 @@ int main(int argc, char **argv) {
     if (g.verbosity > 0) fprintf(stderr, "\nCleaning up.\n\nBye.\n");
     return rc;
   }
-  // the other operations bottom-up: children were appended after their parents, so reverse list order runs a child
-  // before the operation that reads its output
-  for (size_t i = ops.size(); i-- > 0;)
-    if (ops[i].kind == OP_MERGE) rc |= run_merge(g, ops, ops[i]);
-    else if (ops[i].kind == OP_VALUE) rc |= run_value(g, ops, ops[i]);
+  for (const Operation &op : ops)                                              // before anything runs
+    if (op.kind == OP_DUMPINDEX || op.kind == OP_HISTOGRAM || op.kind == OP_DUMPFILE)
+      for (const InputRef &in : op.inputs)
+        if (in.child >= 0 && ops[in.child].output.empty()) die("ERROR: '%s' reads a database: its input operation needs an 'output <database>'.", op.word.c_str());
+  // the trees of set and value operations, one evaluation each; the tree under a `print` is evaluated by the print
+  for (size_t i = ops.size(); i-- > 0;) {
+    if (!is_tree_op(ops[i]) || (ops[i].parent >= 0 && (is_tree_op(ops[ops[i].parent]) || ops[ops[i].parent].kind == OP_PRINT))) continue;
+    rc |= run_tree(g, ops, (int)i, false);
+  }
   for (Operation &op : ops) {
     if (op.kind != OP_PRINT && op.kind != OP_DUMPINDEX && op.kind != OP_HISTOGRAM && op.kind != OP_DUMPFILE) continue;
-    for (const InputRef &in : op.inputs) {
-      if (in.child >= 0 && ops[in.child].output.empty()) die("ERROR: the input operation of '%s' needs an output in this build.", op.word.c_str());
-      op.db_inputs.push_back(in.child >= 0 ? ops[in.child].output : in.path);
+    if (op.kind == OP_PRINT) {
+      for (const InputRef &in : op.inputs)
+        if (in.child >= 0 && is_tree_op(ops[in.child])) rc |= run_tree(g, ops, in.child, true);
+        else print_database(in.child >= 0 ? ops[in.child].output : in.path);
+      continue;
     }
-    if (op.kind == OP_PRINT)     rc |= run_print(op);
+    for (const InputRef &in : op.inputs) op.db_inputs.push_back(in.child >= 0 ? ops[in.child].output : in.path);
     if (op.kind == OP_DUMPINDEX) rc |= run_dump_index(op);
     if (op.kind == OP_HISTOGRAM) rc |= run_histogram(op);
     if (op.kind == OP_DUMPFILE)  rc |= run_dump_file(op);

@@ -314,6 +314,40 @@ extern "C" int mgc_dev_merge_emit(const void *dA, const uint32_t *cA, uint64_t n
                 "merge_emit");
 }
 
+extern "C" uint32_t mgc_dev_merge_many_tile(uint32_t key_words) { return mgc::merge_many_tile(key_words); }
+
+static bool merge_many_args_ok(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *n, uint32_t n_inputs,
+                               uint32_t key_words, int op) {
+  if (!d_keys || !d_values || !n || n_inputs < 2 || n_inputs > MGC_MERGE_MANY_MAX || (key_words != 1 && key_words != 2) ||
+      op < MGC_MERGE_UNION_SUM || op > MGC_MERGE_UNION) return false;
+  for (uint32_t i = 0; i < n_inputs; i++)
+    if ((n[i] && (!d_keys[i] || !d_values[i])) || (n[i] >> 32)) return false;
+  return true;
+}
+
+extern "C" size_t mgc_dev_merge_many_workspace_bytes(const uint64_t *n, uint32_t n_inputs, uint32_t key_words) {
+  if (!n || n_inputs > MGC_MERGE_MANY_MAX) return 0;
+  return mgc::merge_many_workspace_bytes(n, n_inputs, key_words);
+}
+
+extern "C" int mgc_dev_merge_many_count(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *n, uint32_t n_inputs,
+                                        uint32_t key_words, int op, void *d_ws, size_t ws_bytes, uint64_t *n_out, void *stream) {
+  if (!n_out || !d_ws || !merge_many_args_ok(d_keys, d_values, n, n_inputs, key_words, op) ||
+      ws_bytes < mgc::merge_many_workspace_bytes(n, n_inputs, key_words)) return MGC_EINVAL;
+  hipError_t e = mgc::launch_merge_many_count(d_keys, d_values, n, n_inputs, key_words, op, d_ws, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_rc(e, "merge_many_count");
+  return hip_rc(mgc::merge_read_total(d_ws, n_out, (hipStream_t)stream), "merge_many_count sync");
+}
+
+extern "C" int mgc_dev_merge_many_emit(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *n, uint32_t n_inputs,
+                                       uint32_t key_words, int op, void *d_ws, size_t ws_bytes, void *d_keys_out, uint32_t *d_values_out,
+                                       void *stream) {
+  if (!d_ws || !merge_many_args_ok(d_keys, d_values, n, n_inputs, key_words, op) ||
+      ws_bytes < mgc::merge_many_workspace_bytes(n, n_inputs, key_words)) return MGC_EINVAL;
+  return hip_rc(mgc::launch_merge_many_emit(d_keys, d_values, n, n_inputs, key_words, op, d_ws, d_keys_out, d_values_out,
+                                            (hipStream_t)stream), "merge_many_emit");
+}
+
 extern "C" size_t mgc_dev_homopoly_workspace_bytes(uint64_t n) { return mgc::hpc_workspace_bytes(n); }
 
 extern "C" int mgc_dev_homopoly_compress(const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t *n_out, void *d_ws,

@@ -1,5 +1,5 @@
 // mgc_common.hpp -- shared by the gfx950 kernel translation units (mgc_kmer, mgc_sort, mgc_finish, mgc_scan, mgc_misc, mgc_encode,
-// mgc_decode, mgc_merge, mgc_import .hip; mgc_lookup / mgc_filter .hip through mgc_lookup_dev.hpp; mgc_parse.hip is self-contained).
+// mgc_decode, mgc_merge, mgc_merge_many, mgc_import .hip; mgc_lookup / mgc_filter .hip through mgc_lookup_dev.hpp; mgc_parse.hip is self-contained).
 // Not installed.
 #pragma once
 #include "mgc_device.h"

@@ -285,6 +285,15 @@ hipError_t launch_merge_count(const void *dA, uint64_t na, const void *dB, uint6
 hipError_t merge_read_total(const void *d_ws, uint64_t *n_out, hipStream_t st);       // synchronises the stream
 hipError_t launch_merge_emit(const void *dA, const uint32_t *cA, uint64_t na, const void *dB, const uint32_t *cB, uint64_t nb,
                              uint32_t key_words, int op, void *d_ws, void *d_out_keys, uint32_t *d_out_counts, hipStream_t st);
+// ---- merge of 2..32 sorted distinct (k-mer, value) streams in one pass pair (mgc_merge_many.hip) ----------------
+// op as above, and 10 union (the value is the number of inputs holding the k-mer); keys / vals / n: host arrays of device
+// pointers and lengths; equal to the left fold of the two-input merge over the same inputs, element by element
+uint32_t   merge_many_tile(uint32_t key_words);
+size_t     merge_many_workspace_bytes(const uint64_t *n, uint32_t n_inputs, uint32_t key_words);
+hipError_t launch_merge_many_count(const void *const *keys, const uint32_t *const *vals, const uint64_t *n, uint32_t n_inputs,
+                                   uint32_t key_words, int op, void *d_ws, hipStream_t st);
+hipError_t launch_merge_many_emit(const void *const *keys, const uint32_t *const *vals, const uint64_t *n, uint32_t n_inputs,
+                                  uint32_t key_words, int op, void *d_ws, void *d_out_keys, uint32_t *d_out_vals, hipStream_t st);
 // one stream through a value transform (fop 0..5 filters against `constant`: less-than, greater-than, at-least, at-most, equal-to,
 // not-equal-to; 6..11 arithmetic: increase, decrease, multiply, divide, divide-round, modulo; 12: keep where d_flags[i] == 1),
 // k-mers whose new value is 0 dropped; two passes like the merge (count -> merge_read_total -> emit)

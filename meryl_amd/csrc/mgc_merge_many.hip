@@ -1,0 +1,264 @@
+// mgc_merge_many.hip -- up to 32 sorted (k-mer, value) streams -> one, in one count pass and one emit pass (gfx950).
+//
+// What it replaces in the reference (paths relative to the reference root): the k-way streaming merge of
+// merylOperation::nextMer (src/meryl/merylOp-nextMer.C:418-683): the smallest k-mer over the inputs and the inputs that hold
+// it, _actLen / _actCount[] / _actIndex[] in input order (:478-523), combined by the operation (:559-612 with
+// findMin/Max/SumCount and subtractCount, :23-62).  mgc_merge.hip does this for two inputs per launch and more inputs fold
+// from the left; here every input is read once per pass.
+//
+// The merged-with-duplicates order is (key, input index).
+//   1. partition (one wave per tile border): border t is the largest key x with #{elements < x} <= t*TILE, found by bisecting
+//      the key space; lane i keeps input i's lower bound and narrows its own range with the key interval, the wave sums the
+//      lanes.  At most N elements are equal to x, so a tile holds fewer than TILE + N elements, and since every input is cut
+//      at the same key a group of equal keys never straddles a border.
+//   2. tile kernel (count and emit): the N runs of a tile are staged in LDS side by side with a tag (input << 16 | index in
+//      the run), then merged pairwise in ceil(log2 N) rounds between two LDS images: every element finds its place by one
+//      binary search in its partner run (left run first on ties, so equal keys end up in input order).  The first element
+//      of each group of equal keys walks the group, combines the values (read from global memory through the tag) and
+//      decides whether the k-mer is written; block scan of the heads, tile bases from scan_u64_exclusive.
+// LDS: 2 images x CAP x (key + 4 B tag) + a 32-entry table per input property: 48 KiB for 8-byte keys (CAP 2048), 40 KiB for
+// 16-byte keys (CAP 1024) whatever N is -- three workgroups per CU.  Per element and pass: (8|16) + 4 B read from HBM (the
+// values only where the pass needs them), and in LDS one write to stage, then per round one read, one write and
+// log2(run length) probes: about sum_{r < log2 N} log2(CAP * 2^r / N) key probes, 21 for N = 3 and 40 for N = 32 at CAP 2048.
+// No global atomics.
+#include "mgc_common.hpp"
+
+namespace mgc {
+
+constexpr int MM_BLOCK = 256;
+constexpr int MM_MAX   = 32;                       // MGC_MERGE_MANY_MAX
+template <typename K> struct MMGeom;
+template <> struct MMGeom<u64>  { static constexpr int ITEMS = 8; typedef u64  Int; };
+template <> struct MMGeom<K128> { static constexpr int ITEMS = 4; typedef u128 Int; };
+// a tile holds the elements between two borders: at most TILE + N - 1 <= CAP
+template <typename K> constexpr int mm_cap()  { return MM_BLOCK * MMGeom<K>::ITEMS; }
+template <typename K> constexpr int mm_tile() { return mm_cap<K>() - MM_MAX; }
+
+__device__ __forceinline__ u64  mm_int(u64 k)  { return k; }
+__device__ __forceinline__ u128 mm_int(K128 k) { return KeyOps<K128>::v(k); }
+
+// the inputs travel in the kernel-argument segment (like the tables of the position reports)
+struct MergeManyDesc {
+  const void *keys[MM_MAX];
+  const u32  *vals[MM_MAX];
+  u64         n[MM_MAX];
+  u32         count;
+};
+
+// splits[b * 32 + i] = number of elements of input i before border b (b in [0, tiles])
+template <typename K>
+__global__ __launch_bounds__(MM_BLOCK)
+void merge_many_partition_kernel(MergeManyDesc d, u64 total, u64 tiles, u64 *__restrict__ splits) {
+  typedef typename MMGeom<K>::Int KI;
+  const u64 b = (u64)blockIdx.x * (MM_BLOCK / 64) + wave_id();
+  if (b > tiles) return;                                     // (wave-uniform)
+  const u32 lane = lane_id();
+  const K *A = nullptr;
+  u64 n = 0;
+#pragma unroll
+  for (int i = 0; i < MM_MAX; i++)
+    if (lane == (u32)i && (u32)i < d.count) { A = reinterpret_cast<const K *>(d.keys[i]); n = d.n[i]; }
+  const u64 r = b * (u64)mm_tile<K>();
+  u64 L = 0, H = n;                                          // elements < lo, elements <= hi
+  if (r >= total) L = n;
+  else if (b > 0) {
+    KI lo = 0, hi = ~(KI)0;
+    while (lo < hi) {                                        // (wave-uniform: lo and hi are)
+      const KI span = hi - lo, mid = lo + (span >> 1) + (span & 1);
+      u64 l = L, h = H;
+      while (l < h) {
+        const u64 m = l + ((h - l) >> 1);
+        if (mm_int(A[m]) < mid) l = m + 1; else h = m;
+      }
+      u64 sum = l;
+#pragma unroll
+      for (int s = 32; s > 0; s >>= 1) sum += __shfl_xor(sum, s);
+      if (sum <= r) { lo = mid; L = l; } else { hi = mid - 1; H = l; }
+    }
+  }
+  if (lane < MM_MAX) splits[b * MM_MAX + lane] = L;
+}
+
+template <typename K, bool EMIT>
+__global__ __launch_bounds__(MM_BLOCK)
+void merge_many_kernel(MergeManyDesc d, int op, const u64 *__restrict__ splits, u64 *__restrict__ tile_cnt /*EMIT: exclusive bases*/,
+                       K *__restrict__ outK, u32 *__restrict__ outC) {
+  constexpr int CAP = mm_cap<K>(), ITEMS = MMGeom<K>::ITEMS;
+  __shared__ K         s_key[2][CAP];
+  __shared__ u32       s_tag[2][CAP];
+  __shared__ const K  *s_kp[MM_MAX];                         // input i's first element of this tile
+  __shared__ const u32 *s_vp[MM_MAX];
+  __shared__ u32       s_off[MM_MAX + 1];                    // where run i begins in the staged image; [i >= N] = nt
+  __shared__ u32       s_tmp[MM_BLOCK / 64 + 1];
+  const u32 N = d.count;
+  if (threadIdx.x < 64) {
+    const u32 i = threadIdx.x;
+    u64 beg = 0, end = 0;
+    if (i < N) { beg = splits[(u64)blockIdx.x * MM_MAX + i]; end = splits[((u64)blockIdx.x + 1) * MM_MAX + i]; }
+    const u32 len = (u32)(end - beg);
+    u32 x = len;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) { const u32 y = __shfl_up(x, s); if ((int)i >= s) x += y; }
+    if (i <= MM_MAX) s_off[i] = x - len;
+#pragma unroll
+    for (int j = 0; j < MM_MAX; j++)
+      if (i == (u32)j) { s_kp[j] = reinterpret_cast<const K *>(d.keys[j]) + beg; s_vp[j] = d.vals[j] + beg; }
+  }
+  __syncthreads();
+  const u32 nt = s_off[MM_MAX];
+  if (nt > (u32)CAP) {                                       // cannot happen (fewer than TILE + N elements between two borders)
+    if (!EMIT && threadIdx.x == 0) tile_cnt[blockIdx.x] = 0;
+    return;
+  }
+  // stage: element j of the image belongs to the last run that begins at or before j
+  for (u32 j = threadIdx.x; j < nt; j += MM_BLOCK) {
+    u32 run = 0;
+#pragma unroll
+    for (int s = MM_MAX / 2; s > 0; s >>= 1) if (s_off[run + s] <= j) run += s;
+    const u32 local = j - s_off[run];
+    s_key[0][j] = s_kp[run][local];
+    s_tag[0][j] = (run << 16) | local;
+  }
+  __syncthreads();
+  // pairwise rounds: at width w the runs are groups of w inputs; group m merges with group m ^ 1
+  int cur = 0;
+  for (u32 w = 1; w < N; w <<= 1) {
+    const K *sk = s_key[cur];
+    for (u32 j = threadIdx.x; j < nt; j += MM_BLOCK) {
+      const K   key = sk[j];
+      const u32 tag = s_tag[cur][j];
+      const u32 m = (tag >> 16) / w;
+      const u32 a0 = s_off[(m & ~1u) * w], a1 = s_off[(m | 1u) * w], b1 = s_off[((m | 1u) + 1) * w];
+      u32 dest;
+      if (!(m & 1u)) {                                       // left run: the right run's elements below the key come first
+        u32 l = a1, h = b1;
+        while (l < h) { const u32 mid = (l + h) >> 1; if (KeyOps<K>::lt(sk[mid], key)) l = mid + 1; else h = mid; }
+        dest = j + (l - a1);
+      } else {                                               // right run: the left run's elements up to the key come first
+        u32 l = a0, h = a1;
+        while (l < h) { const u32 mid = (l + h) >> 1; if (!KeyOps<K>::lt(key, sk[mid])) l = mid + 1; else h = mid; }
+        dest = a0 + (j - a1) + (l - a0);
+      }
+      s_key[cur ^ 1][dest] = key;
+      s_tag[cur ^ 1][dest] = tag;
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  const K   *sk = s_key[cur];
+  const u32 *sg = s_tag[cur];
+  const bool need_v = EMIT || op == 7;
+  const u32 l0 = threadIdx.x * ITEMS;
+  u32 heads = 0, head_mask = 0, vreg[ITEMS];
+#pragma unroll
+  for (int q = 0; q < ITEMS; q++) {
+    vreg[q] = 0;
+    const u32 p = l0 + q;
+    if (p >= nt) continue;
+    const K key = sk[p];
+    if (p > 0 && !KeyOps<K>::ne(sk[p - 1], key)) continue;   // not the first of its group
+    // the group, in input order: _actLen = cnt, _actIndex[0] = first, _actCount[] = the values
+    const u32 first = sg[p] >> 16;
+    u32 cnt = 0, v = 0;
+    bool alive = true;                                       // subtract: the running difference stayed positive
+    for (u32 g = p; g < nt && !KeyOps<K>::ne(sk[g], key); g++) {
+      u32 c = 0;
+      if (need_v) { const u32 tag = sg[g]; c = s_vp[tag >> 16][tag & 0xFFFFu]; }
+      if (cnt == 0) v = c;
+      else if (op == 7) { if (v > c) v -= c; else alive = false; }
+      else if (op == 0 || op == 3) v += c;                   // the sum wraps mod 2^32 like kmvalu arithmetic
+      else if (op == 1 || op == 4) v = c < v ? c : v;
+      else if (op == 2 || op == 5) v = c > v ? c : v;
+      cnt++;
+    }
+    bool keep;
+    if (op <= 2 || op == 10) keep = true;
+    else if (op <= 6) keep = cnt == N;
+    else if (op == 7) keep = first == 0 && alive;
+    else if (op == 8) keep = first == 0 && cnt == 1;
+    else keep = cnt == 1;
+    if (keep) { head_mask |= 1u << q; heads++; vreg[q] = (op == 10) ? cnt : v; }
+  }
+  u32 tot;
+  const u32 base = block_excl_scan<MM_BLOCK, u32>(heads, s_tmp, &tot);
+  if (!EMIT) {
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
+    return;
+  }
+  u64 o = tile_cnt[blockIdx.x] + base;
+#pragma unroll
+  for (int q = 0; q < ITEMS; q++)
+    if (head_mask & (1u << q)) { outK[o] = sk[l0 + q]; outC[o] = vreg[q]; o++; }
+}
+
+uint32_t merge_many_tile(uint32_t key_words) { return key_words == 2 ? (uint32_t)mm_tile<K128>() : (uint32_t)mm_tile<u64>(); }
+
+static inline uint64_t mm_total(const uint64_t *n, uint32_t n_inputs) {
+  uint64_t t = 0;
+  for (uint32_t i = 0; i < n_inputs; i++) t += n[i];
+  return t;
+}
+static inline uint64_t mm_tiles(uint64_t total, uint32_t key_words) {
+  const uint64_t T = merge_many_tile(key_words);
+  return (total + T - 1) / T;
+}
+// workspace: [0] total (u64), [8..] tile counts (u64 x (tiles + 1)), scan scratch, the borders (u64 x 32 x (tiles + 1))
+static inline size_t mm_splits_at(uint64_t t) { return (size_t)(8 + t + 1 + scan_scratch_elems(t + 1)); }
+
+size_t merge_many_workspace_bytes(const uint64_t *n, uint32_t n_inputs, uint32_t key_words) {
+  const uint64_t t = mm_tiles(mm_total(n, n_inputs), key_words);
+  return (mm_splits_at(t) + (size_t)(t + 1) * MM_MAX) * sizeof(u64) + 256;
+}
+
+static bool mm_desc(MergeManyDesc *d, const void *const *keys, const uint32_t *const *vals, const uint64_t *n, uint32_t n_inputs, int op) {
+  if (n_inputs < 2 || n_inputs > (uint32_t)MM_MAX || op < 0 || op > 10) return false;
+  memset(d, 0, sizeof(*d));
+  d->count = n_inputs;
+  for (uint32_t i = 0; i < n_inputs; i++) {
+    if (n[i] && (!keys[i] || !vals[i])) return false;
+    if (n[i] >> 32) return false;                            // a run's index inside a tile and the tile sizes are 32-bit; inputs are file slices
+    d->keys[i] = keys[i]; d->vals[i] = vals[i]; d->n[i] = n[i];
+  }
+  return true;
+}
+
+// pass 1: cuts the inputs into tiles and leaves the output length at ws[0] (merge_read_total reads it)
+hipError_t launch_merge_many_count(const void *const *keys, const uint32_t *const *vals, const uint64_t *n, uint32_t n_inputs,
+                                   uint32_t key_words, int op, void *d_ws, hipStream_t st) {
+  MergeManyDesc d;
+  if (!mm_desc(&d, keys, vals, n, n_inputs, op)) return hipErrorInvalidValue;
+  u64 *ws = reinterpret_cast<u64 *>(d_ws);
+  const uint64_t total = mm_total(n, n_inputs), t = mm_tiles(total, key_words);
+  if (t == 0) return hipMemsetAsync(ws, 0, 8, st);
+  u64 *tiles = ws + 8, *scratch = tiles + t + 1, *splits = ws + mm_splits_at(t);
+  const uint32_t pgrid = (uint32_t)((t + 1 + MM_BLOCK / 64 - 1) / (MM_BLOCK / 64));
+  if (key_words == 2) {
+    hipLaunchKernelGGL((merge_many_partition_kernel<K128>), dim3(pgrid), dim3(MM_BLOCK), 0, st, d, (u64)total, (u64)t, splits);
+    hipLaunchKernelGGL((merge_many_kernel<K128, false>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, op, splits, tiles, (K128 *)nullptr, (u32 *)nullptr);
+  } else {
+    hipLaunchKernelGGL((merge_many_partition_kernel<u64>), dim3(pgrid), dim3(MM_BLOCK), 0, st, d, (u64)total, (u64)t, splits);
+    hipLaunchKernelGGL((merge_many_kernel<u64, false>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, op, splits, tiles, (u64 *)nullptr, (u32 *)nullptr);
+  }
+  MGC_CHECK(hipGetLastError());
+  return scan_u64_exclusive(tiles, t, scratch, ws, st);
+}
+
+// pass 2 (same inputs, the workspace pass 1 left): writes the merged stream
+hipError_t launch_merge_many_emit(const void *const *keys, const uint32_t *const *vals, const uint64_t *n, uint32_t n_inputs,
+                                  uint32_t key_words, int op, void *d_ws, void *d_out_keys, uint32_t *d_out_vals, hipStream_t st) {
+  MergeManyDesc d;
+  if (!mm_desc(&d, keys, vals, n, n_inputs, op)) return hipErrorInvalidValue;
+  u64 *ws = reinterpret_cast<u64 *>(d_ws);
+  const uint64_t t = mm_tiles(mm_total(n, n_inputs), key_words);
+  if (t == 0) return hipSuccess;
+  u64 *tiles = ws + 8, *splits = ws + mm_splits_at(t);
+  if (key_words == 2)
+    hipLaunchKernelGGL((merge_many_kernel<K128, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, op, splits, tiles,
+                       reinterpret_cast<K128 *>(d_out_keys), d_out_vals);
+  else
+    hipLaunchKernelGGL((merge_many_kernel<u64, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, op, splits, tiles,
+                       reinterpret_cast<u64 *>(d_out_keys), d_out_vals);
+  return hipGetLastError();
+}
+
+}  // namespace mgc

@@ -790,6 +790,82 @@ bool open_merge_inputs(const char *const *inputs, uint32_t n_inputs, std::vector
   }
   return true;
 }
+
+// one (k-mer, value) stream in HBM
+struct SliceRef { const void *k = nullptr; const uint32_t *c = nullptr; uint64_t n = 0; };
+
+// buffers of the left fold (grow-only, reused from slice to slice)
+struct FoldBufs {
+  DBuf acc_k[2], acc_c[2], mem_k[2], mem_c[2], ones, ws;
+  void release() {
+    for (int t = 0; t < 2; t++) { acc_k[t].release(); acc_c[t].release(); mem_k[t].release(); mem_c[t].release(); }
+    ones.release();
+    ws.release();
+  }
+};
+
+// The inputs of one slice folded from the left with the two-input merge (mgc_merge.hip) -- mgc_db_merge, and the merge nodes
+// of mgc_db_eval that do not go through merge_many.
+//   union (value = how many inputs hold the k-mer, :559-561) = union-sum over values of one;
+//   symmetric-difference over more than two inputs (in exactly ONE input, :609-612) = the union-sum of the values
+//   filtered by "union-sum of ones == 1" (written to sel_k / sel_c, which must not hold the value fold's result);
+//   everything else folds from the left with its own two-input step.
+// *out: the result (an input's or one of the buffers' memory), valid once this returns (the stream is synchronised).
+hipError_t fold_slices(const std::vector<SliceRef> &in, int op, uint32_t kw, FoldBufs &fb, DBuf &sel_k, DBuf &sel_c, hipStream_t st,
+                       SliceRef *out, const char **what) {
+  const uint32_t n_inputs = (uint32_t)in.size();
+  const bool by_membership = (op == MGC_MERGE_SYMMETRIC_DIFFERENCE && n_inputs > 2);
+  const int fold_op = (op == MGC_MERGE_UNION || by_membership) ? MGC_MERGE_UNION_SUM : op;
+  // fold: values (and, for the membership forms, ones) through the same sequence of two-input steps
+  auto fold = [&](bool use_ones, DBuf (&ak)[2], DBuf (&ac)[2], SliceRef *res) -> hipError_t {
+    uint64_t most = 0;
+    for (uint32_t i = 0; i < n_inputs; i++) most = std::max(most, in[i].n);
+    if (use_ones) {
+      hipError_t e = fb.ones.ensure(4 * most);
+      if (e == hipSuccess) e = mgc::launch_fill_u32(fb.ones.as<uint32_t>(), most, 1u, st);
+      if (e != hipSuccess) { *what = "ones"; return e; }
+    }
+    auto cof = [&](uint32_t i) -> const uint32_t * { return use_ones ? fb.ones.as<uint32_t>() : in[i].c; };
+    SliceRef cur{in[0].k, cof(0), in[0].n};
+    for (uint32_t i = 1; i < n_inputs; i++) {
+      const int t = (int)(i & 1u);
+      uint64_t n_new = 0;
+      hipError_t e = fb.ws.ensure(mgc::merge_workspace_bytes(cur.n, in[i].n));
+      if (e == hipSuccess) e = mgc::launch_merge_count(cur.k, cur.n, in[i].k, in[i].n, kw, fold_op, fb.ws.p, st, cur.c, cof(i));
+      if (e == hipSuccess) e = mgc::merge_read_total(fb.ws.p, &n_new, st);
+      if (e == hipSuccess) e = ak[t].ensure(8 * (size_t)kw * n_new);
+      if (e == hipSuccess) e = ac[t].ensure(4 * n_new);
+      if (e == hipSuccess) e = mgc::launch_merge_emit(cur.k, cur.c, cur.n, in[i].k, cof(i), in[i].n, kw, fold_op, fb.ws.p, ak[t].p, ac[t].as<uint32_t>(), st);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);
+      if (e != hipSuccess) { *what = "merging a slice"; return e; }
+      cur = SliceRef{ak[t].p, ac[t].as<uint32_t>(), n_new};
+    }
+    *res = cur;
+    return hipSuccess;
+  };
+  SliceRef res;
+  hipError_t e = fold(op == MGC_MERGE_UNION, fb.acc_k, fb.acc_c, &res);
+  if (e != hipSuccess) return e;
+  if (by_membership) {
+    SliceRef mem;                                            // same k-mers as the value fold, values = inputs holding each
+    e = fold(true, fb.mem_k, fb.mem_c, &mem);
+    if (e != hipSuccess) return e;
+    uint64_t n_new = 0;
+    *what = "selecting the k-mers of exactly one input";
+    if (res.k == sel_k.p) { *what = "symmetric-difference buffers"; return hipErrorInvalidValue; }
+    e = fb.ws.ensure(mgc::select_workspace_bytes(res.n));
+    if (e == hipSuccess) e = mgc::launch_select_count(res.k, res.c, mem.c, res.n, kw, 12, 0, fb.ws.p, st);
+    if (e == hipSuccess) e = mgc::merge_read_total(fb.ws.p, &n_new, st);
+    if (e == hipSuccess) e = sel_k.ensure(8 * (size_t)kw * n_new);
+    if (e == hipSuccess) e = sel_c.ensure(4 * n_new);
+    if (e == hipSuccess) e = mgc::launch_select_emit(res.k, res.c, mem.c, res.n, kw, 12, 0, fb.ws.p, sel_k.p, sel_c.as<uint32_t>(), st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return e;
+    res = SliceRef{sel_k.p, sel_c.as<uint32_t>(), n_new};
+  }
+  *out = res;
+  return hipSuccess;
+}
 }  // namespace
 
 extern "C" int mgc_db_merge(const char *const *inputs, uint32_t n_inputs, int op, const char *output, int device, int host_threads) {
@@ -815,76 +891,29 @@ extern "C" int mgc_db_merge(const char *const *inputs, uint32_t n_inputs, int op
   {
     hipStream_t st = nullptr;
     std::vector<DBuf> in_k(n_inputs), in_c(n_inputs);
-    DBuf acc_k[2], acc_c[2], mem_k[2], mem_c[2], ones, ws;
+    FoldBufs fb;
     std::vector<uint64_t> hn;
+    std::vector<SliceRef> in(n_inputs);
     const uint64_t blocks_per_file = 1ull << (w_prefix - MGC_NUM_FILES_BITS);
-    // union (value = how many inputs hold the k-mer, :559-561) = union-sum over values of one;
-    // symmetric-difference over more than two inputs (in exactly ONE input, :609-612) = the union-sum of the values
-    // filtered by "union-sum of ones == 1"; everything else folds from the left with its own two-input step
-    const bool by_membership = (op == MGC_MERGE_SYMMETRIC_DIFFERENCE && n_inputs > 2);
-    const int fold_op = (op == MGC_MERGE_UNION || by_membership) ? MGC_MERGE_UNION_SUM : op;
     const bool host_decode = decode_on_host();
     MG_TRY(hipSetDevice(device));
     MG_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     for (uint32_t ff = 0; ff < MGC_NUM_FILES && rc == MGC_OK; ff++) {
       rc = load_slices(rd, ff, kw, in_k, in_c, hn, st, &msg, host_decode);
       if (rc != MGC_OK) { msg = "mgc_db_merge: " + msg; break; }
-      // fold: values (and, for the membership forms, ones) through the same sequence of two-input steps
-      auto fold = [&](bool use_ones, DBuf (&ak)[2], DBuf (&ac)[2], const void **out_k, const uint32_t **out_c, uint64_t *out_n) -> bool {
-        uint64_t most = 0;
-        for (uint32_t i = 0; i < n_inputs; i++) most = std::max(most, hn[i]);
-        if (use_ones) {
-          hipError_t e = ones.ensure(4 * most);
-          if (e == hipSuccess) e = mgc::launch_fill_u32(ones.as<uint32_t>(), most, 1u, st);
-          if (e != hipSuccess) { hip_fail(e, "ones"); return false; }
-        }
-        auto cof = [&](uint32_t i) -> const uint32_t * { return use_ones ? ones.as<uint32_t>() : in_c[i].as<uint32_t>(); };
-        const void *cur_k = in_k[0].p;
-        const uint32_t *cur_c = cof(0);
-        uint64_t cur_n = hn[0];
-        for (uint32_t i = 1; i < n_inputs; i++) {
-          const int t = (int)(i & 1u);
-          uint64_t n_new = 0;
-          hipError_t e = ws.ensure(mgc::merge_workspace_bytes(cur_n, hn[i]));
-          if (e == hipSuccess) e = mgc::launch_merge_count(cur_k, cur_n, in_k[i].p, hn[i], kw, fold_op, ws.p, st, cur_c, cof(i));
-          if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
-          if (e == hipSuccess) e = ak[t].ensure(8 * (size_t)kw * n_new);
-          if (e == hipSuccess) e = ac[t].ensure(4 * n_new);
-          if (e == hipSuccess) e = mgc::launch_merge_emit(cur_k, cur_c, cur_n, in_k[i].p, cof(i), hn[i], kw, fold_op, ws.p, ak[t].p, ac[t].as<uint32_t>(), st);
-          if (e == hipSuccess) e = hipStreamSynchronize(st);
-          if (e != hipSuccess) { hip_fail(e, "merging a slice"); return false; }
-          cur_k = ak[t].p; cur_c = ac[t].as<uint32_t>(); cur_n = n_new;
-        }
-        *out_k = cur_k; *out_c = cur_c; *out_n = cur_n;
-        return true;
-      };
-      const void *res_k = nullptr; const uint32_t *res_c = nullptr; uint64_t res_n = 0;
-      if (!fold(op == MGC_MERGE_UNION, acc_k, acc_c, &res_k, &res_c, &res_n)) break;
-      if (by_membership) {
-        const void *mk = nullptr; const uint32_t *mc = nullptr; uint64_t mn = 0;
-        if (!fold(true, mem_k, mem_c, &mk, &mc, &mn)) break;          // same k-mers as the value fold, values = inputs holding each
-        uint64_t n_new = 0;
-        DBuf &ok = in_k[0], &oc = in_c[0];                             // the first input's buffers are free by now
-        MG_TRY(ws.ensure(mgc::select_workspace_bytes(res_n)));
-        MG_TRY(mgc::launch_select_count(res_k, res_c, mc, res_n, kw, 12, 0, ws.p, st));
-        MG_TRY(mgc::merge_read_total(ws.p, &n_new, st));
-        if (res_k == ok.p) { hip_fail(hipErrorInvalidValue, "symmetric-difference buffers"); break; }
-        MG_TRY(ok.ensure(8 * (size_t)kw * n_new));
-        MG_TRY(oc.ensure(4 * n_new));
-        MG_TRY(mgc::launch_select_emit(res_k, res_c, mc, res_n, kw, 12, 0, ws.p, ok.p, oc.as<uint32_t>(), st));
-        MG_TRY(hipStreamSynchronize(st));
-        res_k = ok.p; res_c = oc.as<uint32_t>(); res_n = n_new;
-      }
-      rc = mgc_db_stream_write(d, res_k, res_c, res_n, (uint64_t)ff * blocks_per_file, ((uint64_t)ff + 1) * blocks_per_file);
+      for (uint32_t i = 0; i < n_inputs; i++) in[i] = SliceRef{in_k[i].p, in_c[i].as<uint32_t>(), hn[i]};
+      SliceRef res;
+      const char *what = "";
+      const hipError_t fe = fold_slices(in, op, kw, fb, in_k[0], in_c[0] /*the first input's buffers are free by then*/, st, &res, &what);
+      if (fe != hipSuccess) { hip_fail(fe, what); break; }
+      rc = mgc_db_stream_write(d, res.k, res.c, res.n, (uint64_t)ff * blocks_per_file, ((uint64_t)ff + 1) * blocks_per_file);
       if (rc == MGC_OK) rc = mgc_db_stream_sync(d);         // the buffers are reused for the next slice
       if (rc != MGC_OK) msg = std::string("mgc_db_merge: ") + mgc_db_stream_error(d);
     }
   done:
     for (auto &b : in_k) b.release();
     for (auto &b : in_c) b.release();
-    for (int t = 0; t < 2; t++) { acc_k[t].release(); acc_c[t].release(); mem_k[t].release(); mem_c[t].release(); }
-    ones.release();
-    ws.release();
+    fb.release();
     if (st) (void)hipStreamDestroy(st);
   }
 #undef MG_TRY
@@ -938,6 +967,223 @@ extern "C" int mgc_db_filter(const char *input, int value_op, uint64_t constant,
   mdb_reader_close(rd[0]);
   const int rc2 = mgc_db_stream_close(d, nullptr);
   if (rc == MGC_OK && rc2 != MGC_OK) { rc = rc2; msg = mgc_db_stream_error(nullptr); }
+  if (rc != MGC_OK) set_err(nullptr, "%s", msg.c_str());
+  return rc;
+}
+
+// ================================================================================================
+//  a tree of merge and value operations per file slice (include/meryl_db.h, mgc_db_eval)
+// ================================================================================================
+// The reference nests operations on the command line and streams k-mers through the whole tree, writing only where
+// `output` is given (src/meryl/merylOp-nextMer.C:418-683, :227).  Here the slices of all leaves are loaded once per file,
+// every inner node's result stays in HBM in the node's own buffers, and only outputs and the root's callback leave it.
+namespace {
+// a merge node takes merge_many (one count pass, one emit pass over all inputs) from this many inputs on; below it the
+// two-input merge path kernel.  NOT MEASURED yet: 3 is what the bytes moved suggest; scripts/setops_bench.py leg (a) decides
+// (the smallest N at which merge_many is not slower than the fold on both input mixes).
+constexpr uint32_t MERGE_MANY_MIN_INPUTS = 3;
+
+bool merge_many_enabled() { const char *e = getenv("MGC_MERGE_MANY"); return !(e && e[0] == '0'); }
+
+struct EvalNode {
+  DBuf k, c;                       // an inner node's result
+  FoldBufs *fold = nullptr;        // merge nodes that fold
+  SliceRef res;
+  mgc_db_stream *out = nullptr;
+  uint32_t leaf = 0;               // leaf: its reader; inner node: its leftmost leaf's
+};
+
+std::string plain_path(const char *p) {
+  std::string s(p);
+  while (s.size() > 1 && s.back() == '/') s.pop_back();
+  return s;
+}
+}  // namespace
+
+extern "C" int mgc_db_eval(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children, uint32_t root,
+                           mgc_eval_slice_cb cb, void *ctx, int device, int host_threads) {
+  auto bad = [&](const std::string &m) { set_err(nullptr, "mgc_db_eval: %s", m.c_str()); return MGC_EINVAL; };
+  if (!nodes || n_nodes == 0 || root >= n_nodes || (n_children && !children)) return bad("bad arguments");
+  // ---- the tree: every node reached at most once, from the root (post-order = evaluation order)
+  std::vector<uint32_t> order, leaves;
+  {
+    std::vector<uint8_t> seen(n_nodes, 0);
+    struct Frame { uint32_t node, next; };
+    std::vector<Frame> stack;
+    seen[root] = 1;
+    stack.push_back({root, 0});
+    while (!stack.empty()) {
+      Frame &f = stack.back();
+      const mgc_eval_node &nd = nodes[f.node];
+      if (f.next == 0) {
+        const std::string id = "node " + std::to_string(f.node);
+        if (nd.kind < MGC_NODE_DATABASE || nd.kind > MGC_NODE_VALUE) return bad(id + ": unknown kind");
+        if ((uint64_t)nd.first_child + nd.n_children > n_children) return bad(id + ": its children are out of range");
+        if (nd.kind == MGC_NODE_DATABASE && nd.n_children != 0) return bad(id + ": a database has no inputs");
+        if (nd.kind == MGC_NODE_DATABASE && !nd.path) return bad(id + ": a database needs a path");
+        if (nd.kind == MGC_NODE_VALUE && nd.n_children != 1) return bad(id + ": a value operation has exactly one input");
+        if (nd.kind == MGC_NODE_VALUE && (nd.op < MGC_VALUE_LESS_THAN || nd.op > MGC_VALUE_MODULO)) return bad(id + ": unknown value operation");
+        if (nd.kind == MGC_NODE_MERGE && nd.n_children == 0) return bad(id + ": a merge operation needs an input");
+        if (nd.kind == MGC_NODE_MERGE && (nd.op < MGC_MERGE_UNION_SUM || nd.op > MGC_MERGE_UNION)) return bad(id + ": unknown merge operation");
+      }
+      if (f.next < nd.n_children) {
+        const uint32_t ch = children[nd.first_child + f.next++];
+        if (ch >= n_nodes) return bad("node " + std::to_string(f.node) + ": input " + std::to_string(ch) + " is out of range");
+        if (seen[ch]) return bad("node " + std::to_string(ch) + " is reached twice (an input of two operations, or a cycle)");
+        seen[ch] = 1;
+        stack.push_back({ch, 0});                            // (f is dead from here)
+        continue;
+      }
+      if (nd.kind == MGC_NODE_DATABASE) leaves.push_back(f.node);
+      order.push_back(f.node);
+      stack.pop_back();
+    }
+  }
+  // ---- outputs: named once, and not an input
+  {
+    std::map<std::string, uint32_t> names;
+    for (uint32_t v : leaves) names.emplace(plain_path(nodes[v].path), v);
+    for (uint32_t v : order) {
+      if (nodes[v].kind == MGC_NODE_DATABASE || !nodes[v].path) continue;
+      const auto ins = names.emplace(plain_path(nodes[v].path), v);
+      if (!ins.second)
+        return bad(std::string("output '") + nodes[v].path + "' of node " + std::to_string(v) +
+                   (nodes[ins.first->second].kind == MGC_NODE_DATABASE ? " is also an input" : " is also the output of node " + std::to_string(ins.first->second)));
+    }
+  }
+  // ---- leaves: open, one k, no labels, no multisets (leaves[] is in left-to-right order)
+  std::vector<mdb_reader *> rd;
+  mdb_info first;
+  {
+    std::vector<const char *> paths;
+    for (uint32_t v : leaves) paths.push_back(nodes[v].path);
+    if (!open_merge_inputs(paths.data(), (uint32_t)paths.size(), rd, &first, "mgc_db_eval")) return MGC_EINVAL;
+  }
+  auto close_readers = [&]() { for (mdb_reader *r : rd) if (r) mdb_reader_close(r); };
+  const uint32_t k = first.k, kw = k > 32 ? 2u : 1u, n_leaves = (uint32_t)leaves.size();
+  std::vector<EvalNode> ev(n_nodes);
+  for (uint32_t i = 0; i < n_leaves; i++) ev[leaves[i]].leaf = i;
+  for (uint32_t v : order)
+    if (nodes[v].kind != MGC_NODE_DATABASE) ev[v].leaf = ev[children[nodes[v].first_child]].leaf;
+  auto w_prefix_of = [&](uint32_t v) { mdb_info inf; mdb_reader_info(rd[ev[v].leaf], &inf); return inf.prefix_size; };
+
+  // ---- device work from here
+  const bool use_many = merge_many_enabled();
+  const bool host_decode = decode_on_host();
+  if (device < 0) (void)hipGetDevice(&device);
+  int rc = MGC_OK;
+  std::string msg;
+  auto hip_fail = [&](hipError_t e, const char *what) {
+    if (e == hipSuccess) return false;
+    rc = (e == hipErrorOutOfMemory) ? MGC_ENOMEM : MGC_EHIP;
+    msg = std::string("mgc_db_eval: ") + what + ": " + hipGetErrorString(e);
+    return true;
+  };
+  for (uint32_t v : order) {
+    if (nodes[v].kind == MGC_NODE_DATABASE || !nodes[v].path) continue;
+    ev[v].out = mgc_db_stream_open(nodes[v].path, k, w_prefix_of(v), 0, 0, 0, 1, host_threads, device);
+    if (!ev[v].out) { rc = MGC_EINVAL; msg = mgc_db_stream_error(nullptr); break; }
+  }
+  hipStream_t st = nullptr;
+  std::vector<DBuf> in_k(n_leaves), in_c(n_leaves);
+  DBuf ws;
+  std::vector<uint64_t> hn, h_keys, h_lo, h_hi;
+  std::vector<uint32_t> h_vals;
+  if (rc == MGC_OK && !hip_fail(hipSetDevice(device), "hipSetDevice")) (void)hip_fail(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate");
+
+  // one inner node of one slice: its inputs' results -> its own
+  auto eval_node = [&](uint32_t v) -> bool {
+    const mgc_eval_node &nd = nodes[v];
+    EvalNode &me = ev[v];
+    std::vector<SliceRef> in(nd.n_children);
+    for (uint32_t i = 0; i < nd.n_children; i++) in[i] = ev[children[nd.first_child + i]].res;
+    uint64_t n_new = 0;
+    hipError_t e;
+    if (nd.kind == MGC_NODE_VALUE) {
+      e = ws.ensure(mgc::select_workspace_bytes(in[0].n));
+      if (e == hipSuccess) e = mgc::launch_select_count(in[0].k, in[0].c, nullptr, in[0].n, kw, nd.op, nd.constant, ws.p, st);
+      if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
+      if (e == hipSuccess) e = me.k.ensure(8 * (size_t)kw * n_new);
+      if (e == hipSuccess) e = me.c.ensure(4 * n_new);
+      if (e == hipSuccess) e = mgc::launch_select_emit(in[0].k, in[0].c, nullptr, in[0].n, kw, nd.op, nd.constant, ws.p, me.k.p, me.c.as<uint32_t>(), st);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);
+      if (hip_fail(e, "a value operation")) return false;
+      me.res = SliceRef{me.k.p, me.c.as<uint32_t>(), n_new};
+      return true;
+    }
+    if (use_many && nd.n_children >= MERGE_MANY_MIN_INPUTS && nd.n_children <= MGC_MERGE_MANY_MAX) {
+      const void *kp[MGC_MERGE_MANY_MAX];
+      const uint32_t *cp[MGC_MERGE_MANY_MAX];
+      uint64_t nn[MGC_MERGE_MANY_MAX];
+      for (uint32_t i = 0; i < nd.n_children; i++) { kp[i] = in[i].k; cp[i] = in[i].c; nn[i] = in[i].n; }
+      e = ws.ensure(mgc::merge_many_workspace_bytes(nn, nd.n_children, kw));
+      if (e == hipSuccess) e = mgc::launch_merge_many_count(kp, cp, nn, nd.n_children, kw, nd.op, ws.p, st);
+      if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
+      if (e == hipSuccess) e = me.k.ensure(8 * (size_t)kw * n_new);
+      if (e == hipSuccess) e = me.c.ensure(4 * n_new);
+      if (e == hipSuccess) e = mgc::launch_merge_many_emit(kp, cp, nn, nd.n_children, kw, nd.op, ws.p, me.k.p, me.c.as<uint32_t>(), st);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);
+      if (hip_fail(e, "merging a slice")) return false;
+      me.res = SliceRef{me.k.p, me.c.as<uint32_t>(), n_new};
+      return true;
+    }
+    if (!me.fold) me.fold = new FoldBufs;
+    const char *what = "";
+    e = fold_slices(in, nd.op, kw, *me.fold, me.k, me.c, st, &me.res, &what);
+    return !hip_fail(e, what);
+  };
+
+  for (uint32_t ff = 0; ff < MGC_NUM_FILES && rc == MGC_OK; ff++) {
+    rc = load_slices(rd, ff, kw, in_k, in_c, hn, st, &msg, host_decode);
+    if (rc != MGC_OK) { msg = "mgc_db_eval: " + msg; break; }
+    for (uint32_t v : order) {
+      EvalNode &me = ev[v];
+      if (nodes[v].kind == MGC_NODE_DATABASE) me.res = SliceRef{in_k[me.leaf].p, in_c[me.leaf].as<uint32_t>(), hn[me.leaf]};
+      else if (!eval_node(v)) break;
+      if (me.out) {
+        const uint64_t blocks_per_file = 1ull << (w_prefix_of(v) - MGC_NUM_FILES_BITS);
+        rc = mgc_db_stream_write(me.out, me.res.k, me.res.c, me.res.n, (uint64_t)ff * blocks_per_file, ((uint64_t)ff + 1) * blocks_per_file);
+        if (rc != MGC_OK) { msg = std::string("mgc_db_eval: ") + mgc_db_stream_error(me.out); break; }
+      }
+    }
+    if (rc != MGC_OK) break;
+    if (cb) {
+      const SliceRef &r = ev[root].res;
+      h_keys.resize((size_t)kw * r.n);
+      h_vals.resize(r.n);
+      hipError_t e = hipSuccess;
+      if (r.n) {
+        e = hipMemcpyAsync(h_keys.data(), r.k, 8 * (size_t)kw * r.n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_vals.data(), r.c, 4 * r.n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+      }
+      if (hip_fail(e, "copying the root's slice")) break;
+      if (kw == 1) cb(ctx, ff, h_keys.data(), nullptr, h_vals.data(), r.n);
+      else {
+        h_lo.resize(r.n); h_hi.resize(r.n);
+        for (uint64_t j = 0; j < r.n; j++) { h_lo[j] = h_keys[2 * j]; h_hi[j] = h_keys[2 * j + 1]; }
+        cb(ctx, ff, h_lo.data(), h_hi.data(), h_vals.data(), r.n);
+      }
+    }
+    for (uint32_t v : order) {                               // the buffers are reused for the next slice
+      if (!ev[v].out) continue;
+      const int rs = mgc_db_stream_sync(ev[v].out);
+      if (rs != MGC_OK && rc == MGC_OK) { rc = rs; msg = std::string("mgc_db_eval: ") + mgc_db_stream_error(ev[v].out); }
+    }
+  }
+  // an output whose node failed mid-slice may still be encoding from buffers about to go
+  if (rc != MGC_OK) for (uint32_t v : order) if (ev[v].out) (void)mgc_db_stream_sync(ev[v].out);
+  for (auto &b : in_k) b.release();
+  for (auto &b : in_c) b.release();
+  ws.release();
+  for (EvalNode &e : ev) { e.k.release(); e.c.release(); if (e.fold) { e.fold->release(); delete e.fold; } }
+  if (st) (void)hipStreamDestroy(st);
+  close_readers();
+  for (uint32_t v : order) {
+    if (!ev[v].out) continue;
+    const int rc2 = mgc_db_stream_close(ev[v].out, nullptr);
+    if (rc == MGC_OK && rc2 != MGC_OK) { rc = rc2; msg = mgc_db_stream_error(nullptr); }
+  }
   if (rc != MGC_OK) set_err(nullptr, "%s", msg.c_str());
   return rc;
 }

@@ -121,3 +121,75 @@ class Reader:
         if self._h:
             capi.lib().mdb_reader_close(self._h)
             self._h = None
+
+
+MERGE_WORDS = {"union-sum": 0, "union-min": 1, "union-max": 2, "intersect-sum": 3, "intersect-min": 4, "intersect-max": 5,
+               "intersect": 6, "subtract": 7, "difference": 8, "symmetric-difference": 9, "union": 10}
+VALUE_WORDS = {"less-than": 0, "greater-than": 1, "at-least": 2, "at-most": 3, "equal-to": 4, "not-equal-to": 5,
+               "increase": 6, "decrease": 7, "multiply": 8, "divide": 9, "divide-round": 10, "modulo": 11}
+
+
+def build_tree(tree):
+    """A tree of operations -> (EvalNode array, children array, root index) for mgc_db_eval.  `tree` is a database path, or
+    (word, *children) for the merge operations, or (word, constant, child) for the value operations; a dict {"output": path}
+    as the last element names the database the node writes."""
+    nodes, kids = [], []
+
+    def add(t):
+        if isinstance(t, (str, bytes)):
+            nodes.append((capi.NODE_DATABASE, 0, 0, t if isinstance(t, bytes) else t.encode(), 0, 0))
+            return len(nodes) - 1
+        t = tuple(t)
+        out = None
+        if t and isinstance(t[-1], dict):
+            opts = dict(t[-1])
+            out = opts.pop("output", None)
+            if opts:
+                raise ValueError("unknown options %r" % sorted(opts))
+            t = t[:-1]
+        if not t or not isinstance(t[0], str):
+            raise ValueError("an operation is (word, ...): %r" % (t,))
+        word = t[0]
+        if word in VALUE_WORDS:
+            if len(t) != 3:
+                raise ValueError("'%s' takes a constant and one input" % word)
+            kind, op, constant, args = capi.NODE_VALUE, VALUE_WORDS[word], int(t[1]), t[2:]
+        elif word in MERGE_WORDS:
+            kind, op, constant, args = capi.NODE_MERGE, MERGE_WORDS[word], 0, t[1:]
+        else:
+            raise ValueError("unknown operation '%s'" % word)
+        ch = [add(a) for a in args]
+        first = len(kids)
+        kids.extend(ch)
+        nodes.append((kind, op, constant, None if out is None else (out if isinstance(out, bytes) else out.encode()), first, len(ch)))
+        return len(nodes) - 1
+
+    root = add(tree)
+    arr = (capi.EvalNode * len(nodes))()
+    for e, (kind, op, constant, path, first, n) in zip(arr, nodes):
+        e.kind, e.op, e.constant, e.path, e.first_child, e.n_children = kind, op, constant, path, first, n
+    return arr, (ctypes.c_uint32 * max(len(kids), 1))(*kids), len(kids), root
+
+
+def evaluate(tree, on_slice=None, device=-1, host_threads=8):
+    """A whole tree of merge / value operations over databases in ONE pass over the 64 file slices, intermediate results
+    kept in HBM (mgc_db_eval).  Nodes given {"output": path} write a database; on_slice(file, lo, hi_or_None, values)
+    receives the root's slices (numpy copies), files ascending."""
+    arr, kids, n_kids, root = build_tree(tree)
+    failure = []
+
+    def trampoline(ctx, ff, lo, hi, vals, n):
+        try:
+            def take(p, dtype):
+                return np.ctypeslib.as_array(p, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype=dtype)
+            on_slice(ff, take(lo, np.uint64), take(hi, np.uint64) if hi else None, take(vals, np.uint32))
+        except BaseException as e:                               # not through the C frames
+            failure.append(e)
+
+    cb = capi.EVAL_SLICE_CB(trampoline) if on_slice is not None else ctypes.cast(None, capi.EVAL_SLICE_CB)
+    rc = capi.lib().mgc_db_eval(arr, len(arr), kids, n_kids, root, cb, None, device, host_threads)
+    if failure:
+        raise failure[0]
+    if rc != 0:
+        msg = capi.lib().mgc_db_stream_error(None)
+        raise capi.MgcError(rc, "mgc_db_eval", msg.decode("utf-8", "replace") if msg else "")

@@ -4,7 +4,7 @@ Usage: python scripts/kres.py PATTERN"""
 import re, subprocess, sys, os
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = ""
-for name in ("mgc_kmer.hip", "mgc_sort.hip", "mgc_scan.hip", "mgc_finish.hip", "mgc_misc.hip", "mgc_parse.hip"):
+for name in ("mgc_kmer.hip", "mgc_sort.hip", "mgc_scan.hip", "mgc_finish.hip", "mgc_misc.hip", "mgc_parse.hip", "mgc_merge.hip", "mgc_merge_many.hip"):
     src = os.path.join(root, "meryl_amd", "csrc", name)
     out += subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "-Rpass-analysis=kernel-resource-usage",
                            "-o", "/tmp/kres.o", src], capture_output=True, text=True).stderr
