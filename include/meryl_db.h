@@ -163,6 +163,11 @@ mgc_db_stream *mgc_db_stream_open(const char *path, uint32_t k, uint32_t w_prefi
                                   uint32_t part, uint32_t n_parts, int host_threads, int device);
 int  mgc_db_stream_write(mgc_db_stream *d, const void *d_keys, const uint32_t *d_counts, uint64_t n,
                          uint64_t prefix_begin, uint64_t prefix_end);
+/* The same with one label per k-mer (d_labels: n device uint64; NULL = the stream's constant label, i.e. exactly
+ * mgc_db_stream_write): the low label_size bits (mgc_db_stream_open) of every label are stored, as
+ * mdb_writer_add_block_labelled stores them. */
+int  mgc_db_stream_write_labelled(mgc_db_stream *d, const void *d_keys, const uint32_t *d_counts, const uint64_t *d_labels,
+                                  uint64_t n, uint64_t prefix_begin, uint64_t prefix_end);
 int  mgc_db_stream_sync(mgc_db_stream *d);
 /* Waits for everything queued, closes the writer (a part: its side file; the plain writer: indexes + master index)
  * and frees the stream.  prof may be NULL. */
@@ -261,6 +266,34 @@ typedef void (*mgc_eval_slice_cb)(void *ctx, uint32_t file, const uint64_t *lo, 
                                   const uint32_t *values, uint64_t n);
 int mgc_db_eval(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children, uint32_t root,
                 mgc_eval_slice_cb cb, void *ctx, int device, int host_threads);
+
+/* The same over databases that may store LABELS (meryl2's `-l <bits>`): every node also names how the label of a written
+ * k-mer comes from the labels of the inputs that hold it -- label_op = MGC_LABEL_* (include/meryl_gpu_count.h, from
+ * merylOpCompute::findOutputLabel, src/meryl2/merylOpCompute.C:286-395) and label_constant, taken as given
+ * (mgc_label_default_constant names the reference's default).  Leaves are decoded with their labels (zeros where a
+ * database stores none), labels travel between nodes as full 64-bit values, and an output stores their low `label_size`
+ * bits; label_size = 0 means the largest label_size among the leaves.  When that is 0 too the outputs are byte-identical
+ * to mgc_db_eval's.  `cb` also receives the root's labels (uncut).
+ * Everything mgc_db_eval checks is checked here in the same way, before any device call and before any output directory
+ * exists (a multiset leaf is still refused; a labelled leaf is what this entry point is for), and also: an unknown label
+ * operation; MGC_LABEL_INVERT on a node with two or more inputs; a merge node with more than MGC_MERGE_MANY_MAX inputs --
+ * the left fold that mgc_db_eval falls back on cannot express DIFFERENCE, MIN or LIGHTEST over all inputs at once.  Every
+ * merge node goes through mgc_dev_merge_many_* here (a one-input merge included); MGC_MERGE_MANY=0 in the environment has
+ * no effect on this entry point. */
+typedef struct mgc_eval_node_labelled {
+  int32_t     kind;                /* MGC_NODE_* */
+  int32_t     op;                  /* MGC_MERGE_* / MGC_VALUE_* (ignored for a leaf) */
+  uint64_t    constant;            /* value operations */
+  const char *path;                /* leaf: the database; inner node: its output, or NULL */
+  uint32_t    first_child, n_children;   /* range of children[] */
+  int32_t     label_op;            /* MGC_LABEL_* (ignored for a leaf) */
+  int32_t     reserved;
+  uint64_t    label_constant;
+} mgc_eval_node_labelled;
+typedef void (*mgc_eval_slice_labelled_cb)(void *ctx, uint32_t file, const uint64_t *lo, const uint64_t *hi_or_null,
+                                           const uint32_t *values, const uint64_t *labels, uint64_t n);
+int mgc_db_eval_labelled(const mgc_eval_node_labelled *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
+                         uint32_t root, uint32_t label_size, mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads);
 
 /* ONE count spread over the GPUs of a node, from one process (meryl_amd/csrc/mgc_node.cpp): rank r's reads are the
  * n_bases[r] bytes at d_bases[r] on device devices[r] (the base stream mgc_push_bases takes; with cfg->homopoly_compress

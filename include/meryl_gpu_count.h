@@ -240,6 +240,71 @@ int mgc_dev_select_count(const void *d_keys, const uint32_t *d_values, uint64_t 
 int mgc_dev_select_emit(const void *d_keys, const uint32_t *d_values, uint64_t n, uint32_t key_words, int value_op, uint64_t constant,
                         void *d_workspace, size_t workspace_bytes, void *d_keys_out, uint32_t *d_values_out, void *stream);
 
+/* ---- labels through the merge and value operations (meryl2) ----------------------------------------------------------
+ * A k-mer may carry a label of up to 64 bits beside its value (kmlabl).  When an operation writes a k-mer it computes the
+ * label from the labels L[j] and values V[j] of its ACTIVE inputs (the inputs that hold the k-mer, in input order: _acta[],
+ * _actLen) and the operation's label constant c -- merylOpCompute::findOutputLabel, src/meryl2/merylOpCompute.C:286-395.
+ * Labels never decide which k-mers are written.  Between operations a label is a full 64-bit value; it is cut to the
+ * database's label_size bits only where it is stored or printed.
+ *   SET         c                                                                             (:295-297)
+ *   FIRST       L[0]: the first ACTIVE input, which need not be input 0                        (:304-307)
+ *   MIN         (l, v) = (c, 2^32-1); for each j: V[j] < v (strict) takes (L[j], V[j]); l      (:309-320; an input whose
+ *               value is 2^32-1 never wins, as there)
+ *   MAX         numeric maximum of c and every L[j]                                            (:322-326)
+ *   AND OR XOR  c combined with every L[j]                                                     (:329-345)
+ *   DIFFERENCE  L[0] & ~c & ~L[1] & ...                                                        (:347-352)
+ *   LIGHTEST    starts with c; L[j] replaces it when its popcount is strictly smaller          (:354-359)
+ *   HEAVIEST    the same with strictly larger                                                  (:361-366)
+ *   INVERT      ~L[0]; one active input only: value operations and one-input merges           (:368-371)
+ *   SELECTED    the label of the input whose VALUE the operation selected: under *-min the first active input with the
+ *               smallest value, under *-max the first with the largest, FIRST under every other operation.  The
+ *               reference's own labelSelected is a placeholder that takes _acta[0] under a `#warning wrong` (:299-302);
+ *               this follows its stated meaning instead.
+ *   DEFAULT     what the operation's alias sets (src/meryl2/merylCommandBuilder-processText.C:384-499): union, union-sum
+ *               -> OR; intersect, intersect-sum -> AND; union-min/-max, intersect-min/-max -> SELECTED; subtract ->
+ *               DIFFERENCE; difference, symmetric-difference and every value operation -> FIRST.
+ * The reference's shift-* and rotate-* label words are not offered: its code for them shifts the wrong way and its rotate
+ * is a shift (`#warning wrong`, :373-393).
+ * The constant is always taken as given; mgc_label_default_constant(op) is the one the reference uses when the command
+ * names none (merylCommandBuilder-isAssign.C:124-156): all ones for AND, XOR and LIGHTEST, 0 otherwise. */
+#define MGC_LABEL_DEFAULT     0
+#define MGC_LABEL_SET         1
+#define MGC_LABEL_FIRST       2
+#define MGC_LABEL_MIN         3
+#define MGC_LABEL_MAX         4
+#define MGC_LABEL_AND         5
+#define MGC_LABEL_OR          6
+#define MGC_LABEL_XOR         7
+#define MGC_LABEL_DIFFERENCE  8
+#define MGC_LABEL_LIGHTEST    9
+#define MGC_LABEL_HEAVIEST   10
+#define MGC_LABEL_INVERT     11
+#define MGC_LABEL_SELECTED   12
+uint64_t mgc_label_default_constant(int label_op);
+/* Step 2 of the merges above with labels: d_labels[i] (HOST array of device pointers) holds input i's labels, NULL = all 0
+ * (an unlabelled input costs no buffer); d_labels_out receives one label per written k-mer.  The count step is
+ * mgc_dev_merge_many_count over the same inputs, whose workspace this takes (labels do not change what is written).
+ * n_inputs = 1 is accepted here (the count step refuses it): every k-mer of the one input is written, so the output has
+ * n[0] entries, and this call runs the count pass itself.  MGC_LABEL_INVERT with two or more inputs, an unknown label
+ * operation: MGC_EINVAL. */
+int mgc_dev_merge_many_emit_labelled(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *const *d_labels,
+                                     const uint64_t *n, uint32_t n_inputs, uint32_t key_words, int op, int label_op,
+                                     uint64_t label_constant, void *d_workspace, size_t workspace_bytes, void *d_keys_out,
+                                     uint32_t *d_values_out, uint64_t *d_labels_out, void *stream);
+/* Step 2 of the value operations with labels: the label operation over the one active input (d_labels NULL = all 0);
+ * the count step is mgc_dev_select_count. */
+int mgc_dev_select_emit_labelled(const void *d_keys, const uint32_t *d_values, const uint64_t *d_labels, uint64_t n,
+                                 uint32_t key_words, int value_op, uint64_t constant, int label_op, uint64_t label_constant,
+                                 void *d_workspace, size_t workspace_bytes, void *d_keys_out, uint32_t *d_values_out,
+                                 uint64_t *d_labels_out, void *stream);
+/* Database blocks decoded on the device (mgc_decode.hip): d_file = the bytes of one data file followed by 16 bytes of slack,
+ * d_blocks = the mdb_raw_block array of include/meryl_db.h (mdb_reader_raw_file gives both, validated against the file
+ * size), suffix_size / label_size as the database's mdb_info has them.  d_keys / d_values / d_labels receive the k-mers of
+ * block b from index blocks[b].out_offset on; d_labels may be NULL (labels skipped) and is filled with zeros when
+ * label_size is 0, as the host reader does.  MGC_EINVAL with a message when a block is corrupt. */
+int mgc_dev_decode_blocks(const void *d_file, const void *d_blocks, uint64_t n_blocks, uint32_t suffix_size, uint32_t label_size,
+                          uint32_t key_words, void *d_keys, uint32_t *d_values, uint64_t *d_labels, void *stream);
+
 /* Homopolymer compression of a base stream (the `compress` word: merylInput.C:
  * 237-240,261-268 calls homopolyCompress() on every chunk loadBases returns,
  * carrying the last byte across chunks of a sequence).  Drops every byte equal,

@@ -249,6 +249,100 @@ def dev_merge_many(keys_list, counts_list, op="union-sum"):
     return out_k, out_c
 
 
+def _label_code(label_op):
+    return label_op if isinstance(label_op, int) else capi.LABEL_OPS[label_op]
+
+
+def dev_merge_many_labelled(keys_list, counts_list, labels_list, op="union-sum", label_op="default", label_constant=None):
+    """dev_merge_many with labels: labels_list[i] is input i's labels (int64[N] cuda tensor, the 64 label bits) or None for an
+    input without labels (all zeros); label_op: a capi.LABEL_OPS word or number; label_constant None: the reference's default
+    for the word (mgc_label_default_constant).  One input is accepted.  -> (keys, values, labels)"""
+    L = capi.lib()
+    m = len(keys_list)
+    kw = 2 if keys_list[0].dim() == 2 else 1
+    dev = keys_list[0].device
+    kp = (ctypes.c_void_p * m)(*[_ptr(k) if k.shape[0] else None for k in keys_list])
+    cp = (ctypes.c_void_p * m)(*[_ptr(c) if c.shape[0] else None for c in counts_list])
+    lp = (ctypes.c_void_p * m)(*[_ptr(l) if l is not None and l.shape[0] else None for l in labels_list])
+    ns = (ctypes.c_uint64 * m)(*[int(k.shape[0]) for k in keys_list])
+    code = op if isinstance(op, int) else MERGE_MANY_OPS[op]
+    lcode = _label_code(label_op)
+    lc = int(L.mgc_label_default_constant(lcode)) if label_constant is None else int(label_constant) & 0xFFFFFFFFFFFFFFFF
+    ws_bytes = max(int(L.mgc_dev_merge_many_workspace_bytes(ns, m, kw)), 256)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    if m == 1:
+        n_out = int(ns[0])                                    # every k-mer of one input is written; the emit runs the count pass
+    else:
+        n = ctypes.c_uint64(0)
+        capi.check(L.mgc_dev_merge_many_count(kp, cp, ns, m, kw, code, _ptr(ws), ws_bytes, ctypes.byref(n), _stream_ptr()),
+                   "mgc_dev_merge_many_count")
+        n_out = n.value
+    out_k = _u64(n_out * kw, dev)
+    if kw == 2:
+        out_k = out_k.view(n_out, 2)
+    out_c = torch.empty(n_out, dtype=torch.int32, device=dev)
+    out_l = _u64(n_out, dev)
+    capi.check(L.mgc_dev_merge_many_emit_labelled(kp, cp, lp, ns, m, kw, code, lcode, lc, _ptr(ws), ws_bytes, _ptr(out_k), _ptr(out_c),
+                                                  _ptr(out_l), _stream_ptr()), "mgc_dev_merge_many_emit_labelled")
+    return out_k, out_c, out_l
+
+
+def dev_select_labelled(keys, counts, labels, value_op, constant, label_op="default", label_constant=None):
+    """One (k-mer, value, label) stream through a value operation (value_op: number, MGC_VALUE_*): the k-mers whose new value is
+    not 0, their new values and their labels through label_op.  labels None: all zeros.  -> (keys, values, labels)"""
+    L = capi.lib()
+    kw = 2 if keys.dim() == 2 else 1
+    n_in = keys.shape[0]
+    dev = keys.device
+    lcode = _label_code(label_op)
+    lc = int(L.mgc_label_default_constant(lcode)) if label_constant is None else int(label_constant) & 0xFFFFFFFFFFFFFFFF
+    ws_bytes = max(int(L.mgc_dev_select_workspace_bytes(n_in)), 256)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    n = ctypes.c_uint64(0)
+    capi.check(L.mgc_dev_select_count(_ptr(keys), _ptr(counts), n_in, kw, value_op, int(constant), _ptr(ws), ws_bytes, ctypes.byref(n),
+                                      _stream_ptr()), "mgc_dev_select_count")
+    out_k = _u64(n.value * kw, dev)
+    if kw == 2:
+        out_k = out_k.view(n.value, 2)
+    out_c = torch.empty(n.value, dtype=torch.int32, device=dev)
+    out_l = _u64(n.value, dev)
+    capi.check(L.mgc_dev_select_emit_labelled(_ptr(keys), _ptr(counts), _ptr(labels) if labels is not None and n_in else None, n_in, kw,
+                                              value_op, int(constant), lcode, lc, _ptr(ws), ws_bytes, _ptr(out_k), _ptr(out_c), _ptr(out_l),
+                                              _stream_ptr()), "mgc_dev_select_emit_labelled")
+    return out_k, out_c, out_l
+
+
+def dev_decode_file(reader, ff, device=None):
+    """Data file ff of a meryl_amd.db.Reader decoded on the device (mgc_dev_decode_blocks): the file's bytes are uploaded as
+    they are.  -> (keys int64[n] / int64[n, 2], values int32[n], labels int64[n]) cuda tensors; labels are zeros when the
+    database stores none."""
+    L = capi.lib()
+    by, bl = ctypes.c_void_p(), ctypes.c_void_p()
+    sz, nb, nk = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = L.mdb_reader_raw_file(reader._h, ff, ctypes.byref(by), ctypes.byref(sz), ctypes.byref(bl), ctypes.byref(nb), ctypes.byref(nk))
+    if rc != 0:
+        raise capi.MgcError(rc, "mdb_reader_raw_file", (L.mdb_last_error() or b"").decode("utf-8", "replace"))
+    try:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        kw = 2 if reader.info.k > 32 else 1
+        raw_block_bytes = 48                                  # sizeof(mdb_raw_block): six uint64
+        d_file = torch.from_numpy(np.ctypeslib.as_array(ctypes.cast(by, ctypes.POINTER(ctypes.c_uint8)), shape=(sz.value + 16,)).copy()).to(dev)
+        n_desc = max(nb.value * raw_block_bytes, 1)
+        d_blocks = torch.from_numpy(np.ctypeslib.as_array(ctypes.cast(bl, ctypes.POINTER(ctypes.c_uint8)), shape=(n_desc,)).copy()
+                                    if nb.value else np.zeros(1, np.uint8)).to(dev)
+    finally:
+        L.mdb_free(by)
+        L.mdb_free(bl)
+    keys = _u64(nk.value * kw, dev)
+    if kw == 2:
+        keys = keys.view(nk.value, 2)
+    vals = torch.empty(nk.value, dtype=torch.int32, device=dev)
+    labs = _u64(nk.value, dev)
+    capi.check(L.mgc_dev_decode_blocks(_ptr(d_file), _ptr(d_blocks), nb.value, reader.info.suffix_size, reader.info.label_size, kw,
+                                       _ptr(keys), _ptr(vals), _ptr(labs), _stream_ptr()), "mgc_dev_decode_blocks")
+    return keys, vals, labs
+
+
 def dev_block_offsets(unique, w_data, n_prefix):
     out = _u64(n_prefix + 1, unique.device)
     kw = 2 if unique.dim() == 2 else 1
@@ -479,14 +573,20 @@ class DbStream:
             msg = capi.lib().mgc_db_stream_error(self._h if self._h else None)
             raise capi.MgcError(rc, what, msg.decode("utf-8", "replace") if msg else "")
 
-    def write(self, keys, counts, prefix_begin, prefix_end):
+    def write(self, keys, counts, prefix_begin, prefix_end, labels=None):
         """Queues the blocks of prefixes [prefix_begin, prefix_end): `keys` (int64[n] / int64[n, 2] cuda tensor, ascending)
-        hold exactly the distinct k-mers of that range, `counts` (int32[n]) their counts.  Asynchronous: the tensors are
-        kept alive here until sync()/close()."""
+        hold exactly the distinct k-mers of that range, `counts` (int32[n]) their counts, `labels` (int64[n], optional) one
+        label per k-mer instead of the stream's constant one.  Asynchronous: the tensors are kept alive here until
+        sync()/close()."""
         torch.cuda.current_stream(keys.device).synchronize()       # the stream's own HIP streams read them
-        self._check(capi.lib().mgc_db_stream_write(self._h, _ptr(keys), _ptr(counts), keys.shape[0], int(prefix_begin),
-                                                   int(prefix_end)), "mgc_db_stream_write")
-        self._keep.append((int(capi.lib().mgc_db_stream_queued(self._h)), keys, counts))
+        if labels is None:
+            self._check(capi.lib().mgc_db_stream_write(self._h, _ptr(keys), _ptr(counts), keys.shape[0], int(prefix_begin),
+                                                       int(prefix_end)), "mgc_db_stream_write")
+        else:
+            self._check(capi.lib().mgc_db_stream_write_labelled(self._h, _ptr(keys), _ptr(counts), _ptr(labels) if keys.shape[0] else None,
+                                                                keys.shape[0], int(prefix_begin), int(prefix_end)),
+                        "mgc_db_stream_write_labelled")
+        self._keep.append((int(capi.lib().mgc_db_stream_queued(self._h)), keys, counts, labels))
 
     def release_done(self):
         """drops the tensors of the ranges that have been encoded and copied out (no waiting)"""

@@ -12,7 +12,11 @@
 // merylOp-nextMer.C:559-613) and the single-input value filters / arithmetic (less-than ... modulo; :490-557), all merged on
 // the device.  Set and value operations nest as in the reference: a whole tree of them over databases and finished counts
 // runs as one evaluation with the intermediate results kept on the device (mgc_db_eval), `output` is optional on every
-// one of them, and `print [operation]` prints the tree's result (quick-start.rst:327-333).  What stays refused: statistics, compare, ploidy, Canu sequence stores (segment=); CRAM only when no `samtools` is on the PATH.
+// one of them, and `print [operation]` prints the tree's result (quick-start.rst:327-333).  Labels (meryl2): `label=<word>`,
+// `label=<word>#<const>` or `label=#<const>` after a set or value operation names how the label of a written k-mer comes from
+// its inputs' labels (merylCommandBuilder-isAssign.C:124-156, merylOpCompute.C:286-395); a tree is evaluated with labels
+// (mgc_db_eval_labelled) when `-l` was given, one of its operations carries such a word or one of its leaves stores labels,
+// and as before otherwise.  What stays refused: statistics, compare, ploidy, Canu sequence stores (segment=); CRAM only when no `samtools` is on the PATH.
 #include "../../include/meryl_db.h"
 #include "../../include/meryl_gpu_count.h"
 #include "../../include/meryl_seq.h"
@@ -24,6 +28,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <filesystem>
 #include <string>
 #include <sys/stat.h>
 #include <thread>
@@ -81,6 +86,9 @@ struct Operation {
   uint64_t                 exp_num_kmers = 0;   // n=
   std::string              count_suffix;        // count-suffix=
   uint64_t                 label = 0;           // label=#<n> (meryl2: the constant label of a count, merylCommandBuilder-isAssign.C:124)
+  bool                     has_label_op = false;   // label=<word>[#<const>] on a set or value operation (:124-156)
+  int                      label_op = MGC_LABEL_DEFAULT;
+  uint64_t                 label_constant = 0;
 };
 
 struct Globals {
@@ -92,6 +100,7 @@ struct Globals {
   bool     compress = false;       // sticky
   uint32_t gpus = 1;               // gpus=<N> (this build only): ranks of ONE count spread over the node's devices
   uint32_t label_size = 0;         // -l <bits> (meryl2: kmerTiny::setLabelSize, merylGlobals.C:75-77)
+  bool     label_size_given = false;
   bool     fast_exit = false;      // set when ONE count is all the command does (and MERYL_FAST_EXIT is not 0): see run_count
   Globals() {
     const long pages = sysconf(_SC_PHYS_PAGES), psz = sysconf(_SC_PAGE_SIZE);
@@ -107,7 +116,7 @@ void usage(const char *prog) {
           "       %s print <database.meryl | [operation]>\n"
           "       %s dumpIndex <database.meryl>\n"
           "       %s dumpFile <database.meryl>/0x######\n"
-          "       %s union[-min|-max|-sum]|intersect[-min|-max|-sum]|subtract|difference|symmetric-difference <db | [operation]> ... [output <db>]\n"
+          "       %s union[-min|-max|-sum]|intersect[-min|-max|-sum]|subtract|difference|symmetric-difference [label=<word>[#<n>]] <db | [operation]> ... [output <db>]\n"
           "       %s less-than|greater-than|at-least|at-most|equal-to|not-equal-to <N | distinct=<f> | word-frequency=<f>> <db | [operation]> [output <db>]\n"
           "       %s increase|decrease|multiply|divide|divide-round|modulo <N> <db | [operation]> [output <db>]\n"
           "\n"
@@ -116,7 +125,10 @@ void usage(const char *prog) {
           "  words of one operation; an operation inside another one's brackets is its input.  A tree of set and value\n"
           "  operations is evaluated in one pass with its intermediate results on the device: only operations given\n"
           "  'output' write a database, and 'print [operation]' prints the result of the tree (distinct= and\n"
-          "  word-frequency= need a database, or an input operation that writes one).  Other meryl operations are\n"
+          "  word-frequency= need a database, or an input operation that writes one).  label=<word> on a set or value\n"
+          "  operation (first selected min max and or xor difference lightest heaviest invert, with #<n> a constant;\n"
+          "  label=#<n> sets it) combines the labels of its inputs; a count inside such a tree may omit 'output'.\n"
+          "  Other meryl operations are\n"
           "  not part of this build.\n",
           prog, prog, prog, prog, prog, prog, prog);
 }
@@ -620,10 +632,32 @@ int run_dump_index(const Operation &op) {
 bool is_tree_op(const Operation &op) { return op.kind == OP_MERGE || op.kind == OP_VALUE; }
 
 struct EvalTree {
-  std::vector<mgc_eval_node>         nodes;
-  std::vector<std::vector<uint32_t>> kids;
-  std::string                        first_leaf;
+  std::vector<mgc_eval_node_labelled> nodes;              // (the label fields are used by a labelled evaluation only)
+  std::vector<std::vector<uint32_t>>  kids;
+  std::string                         first_leaf;
+  bool                                label_words = false;    // an operation of the tree carries label=
+  uint32_t                            leaf_label_size = 0;    // the largest label size among the leaves
 };
+
+// label=<word> | <word>#<const> | #<const> on a set or value operation (merylCommandBuilder-isAssign.C:124-156); without a
+// constant the word's identity (:142-156, mgc_label_default_constant)
+void parse_label_assign(const std::string &w, const std::string &val, Operation &op) {
+  static const struct { const char *word; int code; } words[] = {
+    {"first", MGC_LABEL_FIRST}, {"selected", MGC_LABEL_SELECTED}, {"min", MGC_LABEL_MIN}, {"max", MGC_LABEL_MAX}, {"and", MGC_LABEL_AND},
+    {"or", MGC_LABEL_OR}, {"xor", MGC_LABEL_XOR}, {"difference", MGC_LABEL_DIFFERENCE}, {"lightest", MGC_LABEL_LIGHTEST},
+    {"heaviest", MGC_LABEL_HEAVIEST}, {"invert", MGC_LABEL_INVERT}};
+  const size_t hash = val.find('#');
+  const std::string word = val.substr(0, hash);
+  int code = -1;
+  if (word.empty() && hash != std::string::npos) code = MGC_LABEL_SET;
+  for (const auto &e : words) if (word == e.word) code = e.code;
+  if (word == "shift-left" || word == "shift-right" || word == "rotate-left" || word == "rotate-right")
+    die("ERROR: '%s': the shift and rotate label words are not part of this build (the reference's shift the wrong way and its rotate is a shift).", w.c_str());
+  if (code < 0) die("ERROR: Unknown assign:label=<parameter> in '%s'.", w.c_str());                    // :160-163
+  op.has_label_op = true;
+  op.label_op = code;
+  op.label_constant = (hash != std::string::npos) ? strtoull(val.c_str() + hash + 1, nullptr, 0) : mgc_label_default_constant(code);
+}
 
 // distinct=<f> / word-frequency=<f> turn into a threshold from the input's stored histogram (initializeThreshold, :65-118)
 uint64_t threshold_from_histogram(const Operation &op, const std::string &in) {
@@ -663,7 +697,15 @@ uint32_t add_tree_node(const Globals &g, const std::vector<Operation> &ops, int 
     leaf = in.child >= 0 ? ops[in.child].output : in.path;
     if (!dir_has_index(leaf)) die("ERROR: input '%s' is not a meryl database.", leaf.c_str());
     if (t.first_leaf.empty()) t.first_leaf = leaf;
-    mgc_eval_node nd;
+    {
+      mdb_reader *rd = mdb_reader_open(leaf.c_str());
+      if (!rd) die("ERROR: %s", mdb_last_error());
+      mdb_info info;
+      mdb_reader_info(rd, &info);
+      mdb_reader_close(rd);
+      t.leaf_label_size = std::max(t.leaf_label_size, info.label_size);
+    }
+    mgc_eval_node_labelled nd;
     memset(&nd, 0, sizeof(nd));
     nd.kind = MGC_NODE_DATABASE;
     nd.path = in.child >= 0 ? ops[in.child].output.c_str() : in.path.c_str();
@@ -671,9 +713,12 @@ uint32_t add_tree_node(const Globals &g, const std::vector<Operation> &ops, int 
     t.kids.emplace_back();
     kids.push_back((uint32_t)t.nodes.size() - 1);
   }
-  mgc_eval_node nd;
+  mgc_eval_node_labelled nd;
   memset(&nd, 0, sizeof(nd));
   nd.path = op.output.empty() ? nullptr : op.output.c_str();
+  nd.label_op = op.label_op;
+  nd.label_constant = op.label_constant;
+  t.label_words = t.label_words || op.has_label_op;
   if (op.kind == OP_MERGE) {
     nd.kind = MGC_NODE_MERGE;
     nd.op = op.merge_op;
@@ -694,9 +739,13 @@ uint32_t add_tree_node(const Globals &g, const std::vector<Operation> &ops, int 
   return (uint32_t)t.nodes.size() - 1;
 }
 
-struct PrintCtx { uint32_t k; };
+struct PrintCtx { uint32_t k, label_size; };
 void print_slice(void *ctx, uint32_t, const uint64_t *lo, const uint64_t *hi, const uint32_t *values, uint64_t n) {
   print_kmers(static_cast<PrintCtx *>(ctx)->k, 0, lo, hi, values, nullptr, n);
+}
+void print_slice_labelled(void *ctx, uint32_t, const uint64_t *lo, const uint64_t *hi, const uint32_t *values, const uint64_t *labels, uint64_t n) {
+  const PrintCtx *pc = static_cast<PrintCtx *>(ctx);
+  print_kmers(pc->k, pc->label_size, lo, hi, values, labels, n);
 }
 
 // the operation tree under ops[root] (paths point into `ops`, which outlives the call)
@@ -709,7 +758,7 @@ int run_tree(const Globals &g, const std::vector<Operation> &ops, int root, bool
     t.nodes[v].n_children = (uint32_t)t.kids[v].size();
     children.insert(children.end(), t.kids[v].begin(), t.kids[v].end());
   }
-  PrintCtx pc{0};
+  PrintCtx pc{0, 0};
   if (print) {                                                 // (every leaf holds the same k: mgc_db_eval checks)
     mdb_reader *rd = mdb_reader_open(t.first_leaf.c_str());
     if (!rd) die("ERROR: %s", mdb_last_error());
@@ -718,10 +767,38 @@ int run_tree(const Globals &g, const std::vector<Operation> &ops, int root, bool
     mdb_reader_close(rd);
     pc.k = info.k;
   }
-  if (mgc_db_eval(t.nodes.data(), (uint32_t)t.nodes.size(), children.data(), (uint32_t)children.size(), r, print ? print_slice : nullptr, &pc,
+  // with labels only when something asks for them: -l, a label= word, or a leaf that stores labels; the outputs (and the
+  // label column `print` adds) take -l bits, or the largest label size among the leaves
+  if (g.label_size_given || t.label_words || t.leaf_label_size) {
+    pc.label_size = g.label_size_given && g.label_size ? g.label_size : t.leaf_label_size;
+    if (mgc_db_eval_labelled(t.nodes.data(), (uint32_t)t.nodes.size(), children.data(), (uint32_t)children.size(), r,
+                             g.label_size_given ? g.label_size : 0, print ? print_slice_labelled : nullptr, &pc, -1, (int)g.threads) != MGC_OK)
+      die("ERROR: %s", mgc_db_stream_error(nullptr));
+    return 0;
+  }
+  std::vector<mgc_eval_node> plain(t.nodes.size());
+  for (size_t v = 0; v < t.nodes.size(); v++) {
+    plain[v].kind = t.nodes[v].kind; plain[v].op = t.nodes[v].op; plain[v].constant = t.nodes[v].constant; plain[v].path = t.nodes[v].path;
+    plain[v].first_child = t.nodes[v].first_child; plain[v].n_children = t.nodes[v].n_children;
+  }
+  if (mgc_db_eval(plain.data(), (uint32_t)plain.size(), children.data(), (uint32_t)children.size(), r, print ? print_slice : nullptr, &pc,
                   -1, (int)g.threads) != MGC_OK)
     die("ERROR: %s", mgc_db_stream_error(nullptr));
   return 0;
+}
+
+// temporary databases (counts inside a tree that name no output): one directory each under $TMPDIR, removed at exit
+std::vector<std::string> g_temp_dirs;
+void remove_temp_dirs() {
+  for (const std::string &d : g_temp_dirs) { std::error_code ec; std::filesystem::remove_all(d, ec); }
+}
+std::string temp_database() {
+  const char *base = getenv("TMPDIR");
+  std::string tmpl = std::string(base && base[0] ? base : "/tmp") + "/meryl-count-XXXXXX";
+  if (!mkdtemp(&tmpl[0])) die("ERROR: cannot create a temporary directory '%s' for a count without 'output'.", tmpl.c_str());
+  if (g_temp_dirs.empty()) atexit(remove_temp_dirs);
+  g_temp_dirs.push_back(tmpl);
+  return tmpl + "/count.meryl";
 }
 
 }  // namespace
@@ -797,6 +874,10 @@ int main(int argc, char **argv) {
         if (a + 1 >= argc) die("ERROR: -l needs the label size in bits.");
         g.label_size = (uint32_t)strtoul(argv[++a], nullptr, 10);
         if (g.label_size > 64) die("ERROR: label size of more than 64 bits.");
+        g.label_size_given = true;
+      }
+      else if (key == "label" && eq != std::string::npos && top() >= 0 && is_tree_op(ops[top()])) {
+        parse_label_assign(w, val, ops[top()]);                              // how the operation combines its inputs' labels
       }
       else if (key == "label" && eq != std::string::npos) {                  // label=#<n>: the count's constant label
         if (!is_counting(top())) die("ERROR: option '%s' needs a counting operation before it.", w.c_str());
@@ -894,6 +975,13 @@ int main(int argc, char **argv) {
     const char *fe = getenv("MERYL_FAST_EXIT");
     g.fast_exit = n_ops == 1 && n_counts == 1 && !g.only_config && g.gpus <= 1 && !(fe && fe[0] == '0');
   }
+  // a count that is the input of a set or value operation may omit `output` (`union-sum label=or [count label=#1 a.fa]
+  // [count label=#2 b.fa]`): its database is a temporary one, removed when the command ends
+  if (!g.only_config)
+    for (Operation &op : ops)
+      if (op.kind >= OP_COUNT && op.kind <= OP_COUNT_REVERSE && op.output.empty() && op.parent >= 0 && is_tree_op(ops[op.parent]) &&
+          !op.seq_inputs.empty() && g.k != 0)
+        op.output = temp_database();
   for (const Operation &op : ops) {                                           // counting ops first, in list order (meryl.C:211-227)
     if (op.kind >= OP_COUNT && op.kind <= OP_COUNT_REVERSE) {
       if (op.seq_inputs.empty() && !g.only_config) die("ERROR: count operation has no sequence inputs.");

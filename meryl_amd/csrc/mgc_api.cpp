@@ -317,8 +317,8 @@ extern "C" int mgc_dev_merge_emit(const void *dA, const uint32_t *cA, uint64_t n
 extern "C" uint32_t mgc_dev_merge_many_tile(uint32_t key_words) { return mgc::merge_many_tile(key_words); }
 
 static bool merge_many_args_ok(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *n, uint32_t n_inputs,
-                               uint32_t key_words, int op) {
-  if (!d_keys || !d_values || !n || n_inputs < 2 || n_inputs > MGC_MERGE_MANY_MAX || (key_words != 1 && key_words != 2) ||
+                               uint32_t key_words, int op, uint32_t min_inputs = 2) {
+  if (!d_keys || !d_values || !n || n_inputs < min_inputs || n_inputs > MGC_MERGE_MANY_MAX || (key_words != 1 && key_words != 2) ||
       op < MGC_MERGE_UNION_SUM || op > MGC_MERGE_UNION) return false;
   for (uint32_t i = 0; i < n_inputs; i++)
     if ((n[i] && (!d_keys[i] || !d_values[i])) || (n[i] >> 32)) return false;
@@ -346,6 +346,62 @@ extern "C" int mgc_dev_merge_many_emit(const void *const *d_keys, const uint32_t
       ws_bytes < mgc::merge_many_workspace_bytes(n, n_inputs, key_words)) return MGC_EINVAL;
   return hip_rc(mgc::launch_merge_many_emit(d_keys, d_values, n, n_inputs, key_words, op, d_ws, d_keys_out, d_values_out,
                                             (hipStream_t)stream), "merge_many_emit");
+}
+
+// ---- labels (include/meryl_gpu_count.h: MGC_LABEL_*) --------------------------------------------------------------------------
+extern "C" uint64_t mgc_label_default_constant(int label_op) {      // src/meryl2/merylCommandBuilder-isAssign.C:124-156
+  return (label_op == MGC_LABEL_AND || label_op == MGC_LABEL_XOR || label_op == MGC_LABEL_LIGHTEST) ? ~0ull : 0ull;
+}
+
+extern "C" int mgc_dev_merge_many_emit_labelled(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *const *d_labels,
+                                                const uint64_t *n, uint32_t n_inputs, uint32_t key_words, int op, int label_op,
+                                                uint64_t label_constant, void *d_ws, size_t ws_bytes, void *d_keys_out,
+                                                uint32_t *d_values_out, uint64_t *d_labels_out, void *stream) {
+  const bool ok = merge_many_args_ok(d_keys, d_values, n, n_inputs, key_words, op, 1);
+  const int lop = mgc::label_kernel_op(true, op, label_op);
+  if (!d_ws || !ok || ws_bytes < mgc::merge_many_workspace_bytes(n, n_inputs, key_words)) return MGC_EINVAL;
+  if (lop < 0) { set_err(nullptr, "mgc_dev_merge_many_emit_labelled: unknown label operation %d", label_op); return MGC_EINVAL; }
+  if (lop == MGC_LABEL_INVERT && n_inputs > 1) {
+    set_err(nullptr, "mgc_dev_merge_many_emit_labelled: label=invert takes one input (merylOpCompute.C:368-371)");
+    return MGC_EINVAL;
+  }
+  if (n_inputs == 1) {                                               // the count step refuses one input: its pass runs here
+    hipError_t e = mgc::launch_merge_many_count(d_keys, d_values, n, 1, key_words, op, d_ws, (hipStream_t)stream, true);
+    if (e != hipSuccess) return hip_rc(e, "merge_many_count (one input)");
+  }
+  return hip_rc(mgc::launch_merge_many_emit_labelled(d_keys, d_values, d_labels, n, n_inputs, key_words, op, lop, label_constant, d_ws,
+                                                     d_keys_out, d_values_out, d_labels_out, (hipStream_t)stream), "merge_many_emit_labelled");
+}
+
+extern "C" int mgc_dev_select_emit_labelled(const void *d_keys, const uint32_t *d_values, const uint64_t *d_labels, uint64_t n,
+                                            uint32_t key_words, int value_op, uint64_t constant, int label_op, uint64_t label_constant,
+                                            void *d_ws, size_t ws_bytes, void *d_keys_out, uint32_t *d_values_out, uint64_t *d_labels_out,
+                                            void *stream) {
+  if (!d_ws || ws_bytes < mgc::select_workspace_bytes(n) || (n && (!d_keys || !d_values)) ||
+      (key_words != 1 && key_words != 2) || value_op < 0 || value_op > MGC_VALUE_MODULO) return MGC_EINVAL;
+  const int lop = mgc::label_kernel_op(false, value_op, label_op);
+  if (lop < 0) { set_err(nullptr, "mgc_dev_select_emit_labelled: unknown label operation %d", label_op); return MGC_EINVAL; }
+  return hip_rc(mgc::launch_select_emit_labelled(d_keys, d_values, d_labels, n, key_words, value_op, constant, lop, label_constant, d_ws,
+                                                 d_keys_out, d_values_out, d_labels_out, (hipStream_t)stream), "select_emit_labelled");
+}
+
+extern "C" int mgc_dev_decode_blocks(const void *d_file, const void *d_blocks, uint64_t n_blocks, uint32_t suffix_size, uint32_t label_size,
+                                     uint32_t key_words, void *d_keys, uint32_t *d_values, uint64_t *d_labels, void *stream) {
+  if ((key_words != 1 && key_words != 2) || label_size > 64 || suffix_size > 64 * key_words ||
+      (n_blocks && (!d_file || !d_blocks || !d_keys || !d_values))) return MGC_EINVAL;
+  if (n_blocks == 0) return MGC_OK;
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t *d_err = nullptr, h_err = 0;
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_err), 256);
+  if (e != hipSuccess) return hip_rc(e, "decode_blocks");
+  e = hipMemsetAsync(d_err, 0, 4, st);
+  if (e == hipSuccess) e = mgc::launch_decode_blocks(d_file, d_blocks, n_blocks, suffix_size, label_size, key_words, d_keys, d_values, d_err, st, d_labels);
+  if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(d_err);
+  if (e != hipSuccess) return hip_rc(e, "decode_blocks");
+  if (h_err) { set_err(nullptr, "mgc_dev_decode_blocks: corrupt block (device decoder, code %u)", h_err); return MGC_EINVAL; }
+  return MGC_OK;
 }
 
 extern "C" size_t mgc_dev_homopoly_workspace_bytes(uint64_t n) { return mgc::hpc_workspace_bytes(n); }

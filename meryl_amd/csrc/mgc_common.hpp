@@ -3,6 +3,7 @@
 // Not installed.
 #pragma once
 #include "mgc_device.h"
+#include "mgc_label.hpp"
 
 #include <cstdio>
 #include <cstdlib>

@@ -36,10 +36,13 @@ struct BitWin {                                        // MSB-first cursor over 
   __device__ __forceinline__ u64 pos() const { return (wi << 6) + off; }
 };
 
-template <typename K>
+// LABELS: also the block's label section (A10: n labels of label_size bits after the values) into labels[], zeros when the
+// database stores none -- what mdb_reader_read_file_ex gives
+template <typename K, bool LABELS = false>
 __global__ __launch_bounds__(128)
 void decode_blocks_kernel(const unsigned char *__restrict__ file, const mdb_raw_block *__restrict__ blocks, u64 n_blocks, u32 ss,
-                          u32 label_size, K *__restrict__ keys, u32 *__restrict__ counts, u32 *__restrict__ err) {
+                          u32 label_size, K *__restrict__ keys, u32 *__restrict__ counts, u32 *__restrict__ err,
+                          u64 *__restrict__ labels = nullptr) {
   const u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= n_blocks) return;
   const mdb_raw_block d = blocks[b];
@@ -83,17 +86,34 @@ void decode_blocks_kernel(const unsigned char *__restrict__ file, const mdb_raw_
   }
   if (bw.pos() + n * (u64)(mdb::VALUE_BITS + label_size) > nbits) { atomicExch(err, 3u); return; }
   for (u64 i = 0; i < n; i++) co[i] = (u32)bw.get(mdb::VALUE_BITS);
+  if constexpr (LABELS) {                                // (the check above covers the label section too)
+    u64 *lo = labels + d.out_offset;
+    if (label_size == 0 || label_size > 64) { for (u64 i = 0; i < n; i++) lo[i] = 0; }
+    else for (u64 i = 0; i < n; i++) lo[i] = bw.get(label_size);
+  }
 }
 
 hipError_t launch_decode_blocks(const void *d_file, const void *d_blocks, uint64_t n_blocks, uint32_t suffix_size, uint32_t label_size,
-                                uint32_t key_words, void *d_keys, uint32_t *d_counts, uint32_t *d_err, hipStream_t st) {
+                                uint32_t key_words, void *d_keys, uint32_t *d_counts, uint32_t *d_err, hipStream_t st, uint64_t *d_labels) {
   if (n_blocks == 0) return hipSuccess;
+  if (label_size > 64) return hipErrorInvalidValue;
   const dim3 grid((uint32_t)((n_blocks + 127) / 128));
+  if (d_labels) {
+    if (key_words == 2)
+      hipLaunchKernelGGL((decode_blocks_kernel<K128, true>), grid, dim3(128), 0, st, reinterpret_cast<const unsigned char *>(d_file),
+                         reinterpret_cast<const mdb_raw_block *>(d_blocks), (u64)n_blocks, suffix_size, label_size, reinterpret_cast<K128 *>(d_keys), d_counts, d_err,
+                         reinterpret_cast<u64 *>(d_labels));
+    else
+      hipLaunchKernelGGL((decode_blocks_kernel<u64, true>), grid, dim3(128), 0, st, reinterpret_cast<const unsigned char *>(d_file),
+                         reinterpret_cast<const mdb_raw_block *>(d_blocks), (u64)n_blocks, suffix_size, label_size, reinterpret_cast<u64 *>(d_keys), d_counts, d_err,
+                         reinterpret_cast<u64 *>(d_labels));
+    return hipGetLastError();
+  }
   if (key_words == 2)
-    hipLaunchKernelGGL(decode_blocks_kernel<K128>, grid, dim3(128), 0, st, reinterpret_cast<const unsigned char *>(d_file),
+    hipLaunchKernelGGL((decode_blocks_kernel<K128, false>), grid, dim3(128), 0, st, reinterpret_cast<const unsigned char *>(d_file),
                        reinterpret_cast<const mdb_raw_block *>(d_blocks), (u64)n_blocks, suffix_size, label_size, reinterpret_cast<K128 *>(d_keys), d_counts, d_err);
   else
-    hipLaunchKernelGGL(decode_blocks_kernel<u64>, grid, dim3(128), 0, st, reinterpret_cast<const unsigned char *>(d_file),
+    hipLaunchKernelGGL((decode_blocks_kernel<u64, false>), grid, dim3(128), 0, st, reinterpret_cast<const unsigned char *>(d_file),
                        reinterpret_cast<const mdb_raw_block *>(d_blocks), (u64)n_blocks, suffix_size, label_size, reinterpret_cast<u64 *>(d_keys), d_counts, d_err);
   return hipGetLastError();
 }

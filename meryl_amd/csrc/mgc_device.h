@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "mgc_label.hpp"
 
 namespace mgc {
 
@@ -265,7 +266,8 @@ hipError_t launch_encode_sizes(const void *d_keys, uint32_t key_words, const uin
 hipError_t launch_encode_chunk(const void *d_keys, const uint32_t *d_counts, uint32_t key_words, const uint64_t *d_bs,
                                const uint64_t *d_blk_pos, const uint64_t *d_blk_vbase, const uint32_t *d_blk_bb,
                                uint64_t b0, uint64_t b1, uint64_t n_kmers_chunk, uint64_t prefix_of_block0,
-                               uint32_t suffix_size, uint32_t label_size, uint64_t label, void *d_img, hipStream_t st);
+                               uint32_t suffix_size, uint32_t label_size, uint64_t label, void *d_img, hipStream_t st,
+                               const uint64_t *d_labels = nullptr /*per k-mer, beside d_counts; null: the constant `label`*/);
 uint32_t   value_hist_small_bins();
 hipError_t launch_value_hist(const uint32_t *d_counts, uint64_t n, uint64_t *d_hist, uint32_t *d_big_list, uint64_t big_cap,
                              uint64_t *d_big_n, hipStream_t st);
@@ -273,7 +275,8 @@ hipError_t launch_value_hist(const uint32_t *d_counts, uint64_t n, uint64_t *d_h
 // ---- database blocks decoded on the device (mgc_decode.hip): d_file = the data file's bytes (+ 16 bytes of slack),
 // d_blocks = mdb_raw_block[n_blocks] (include/meryl_db.h, mdb_reader_raw_file); one thread per block; *d_err != 0: a corrupt block
 hipError_t launch_decode_blocks(const void *d_file, const void *d_blocks, uint64_t n_blocks, uint32_t suffix_size, uint32_t label_size,
-                                uint32_t key_words, void *d_keys, uint32_t *d_counts, uint32_t *d_err, hipStream_t st);
+                                uint32_t key_words, void *d_keys, uint32_t *d_counts, uint32_t *d_err, hipStream_t st,
+                                uint64_t *d_labels = nullptr /*the labels beside d_counts (zeros when label_size is 0); null: skipped*/);
 
 // ---- merge of two sorted distinct (k-mer, value) streams (mgc_merge.hip) ----------------------------------------
 // op: 0 union-sum, 1 union-min, 2 union-max, 3 intersect-sum, 4 intersect-min, 5 intersect-max
@@ -291,9 +294,15 @@ hipError_t launch_merge_emit(const void *dA, const uint32_t *cA, uint64_t na, co
 uint32_t   merge_many_tile(uint32_t key_words);
 size_t     merge_many_workspace_bytes(const uint64_t *n, uint32_t n_inputs, uint32_t key_words);
 hipError_t launch_merge_many_count(const void *const *keys, const uint32_t *const *vals, const uint64_t *n, uint32_t n_inputs,
-                                   uint32_t key_words, int op, void *d_ws, hipStream_t st);
+                                   uint32_t key_words, int op, void *d_ws, hipStream_t st, bool allow_one = false);
 hipError_t launch_merge_many_emit(const void *const *keys, const uint32_t *const *vals, const uint64_t *n, uint32_t n_inputs,
                                   uint32_t key_words, int op, void *d_ws, void *d_out_keys, uint32_t *d_out_vals, hipStream_t st);
+// the same emit with labels (MergeManyDesc::labs; a null entry = all zeros): outL[o] = the label operation `lop` (a kernel code,
+// label_kernel_op, mgc_label.hpp) with constant `lc` over the labels and values of the inputs that hold k-mer o.  n_inputs may be 1 here,
+// and launch_merge_many_count takes one input when `allow_one` is set (the labelled evaluation's one-input merge nodes).
+hipError_t launch_merge_many_emit_labelled(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs,
+                                           const uint64_t *n, uint32_t n_inputs, uint32_t key_words, int op, int lop, uint64_t lc, void *d_ws,
+                                           void *d_out_keys, uint32_t *d_out_vals, uint64_t *d_out_labs, hipStream_t st);
 // one stream through a value transform (fop 0..5 filters against `constant`: less-than, greater-than, at-least, at-most, equal-to,
 // not-equal-to; 6..11 arithmetic: increase, decrease, multiply, divide, divide-round, modulo; 12: keep where d_flags[i] == 1),
 // k-mers whose new value is 0 dropped; two passes like the merge (count -> merge_read_total -> emit)
@@ -302,6 +311,10 @@ hipError_t launch_select_count(const void *d_keys, const uint32_t *d_vals, const
                                uint64_t constant, void *d_ws, hipStream_t st);
 hipError_t launch_select_emit(const void *d_keys, const uint32_t *d_vals, const uint32_t *d_flags, uint64_t n, uint32_t key_words, int fop,
                               uint64_t constant, void *d_ws, void *d_out_keys, uint32_t *d_out_vals, hipStream_t st);
+// the emit with labels: d_labs (null = all zeros) follow the kept k-mers, through label operation `lop` (kernel code) with one active input
+hipError_t launch_select_emit_labelled(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words, int fop,
+                                       uint64_t constant, int lop, uint64_t lc, void *d_ws, void *d_out_keys, uint32_t *d_out_vals,
+                                       uint64_t *d_out_labs, hipStream_t st);
 hipError_t launch_fill_u32(uint32_t *d, uint64_t n, uint32_t v, hipStream_t st);
 // *d_out <- 1 + index of the last '.' in bases[0, n), 0 if none
 hipError_t launch_last_breaker(const uint8_t *d_bases, uint64_t n, uint64_t *d_out, hipStream_t st);

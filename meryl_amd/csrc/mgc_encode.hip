@@ -151,11 +151,14 @@ template <> struct EncRun<K128>     { static constexpr int R = 8; };
 constexpr int ENC_BLOCK = 256;
 
 // One thread = R consecutive k-mers of the chunk [bs[b0], bs[b1]).
-template <typename K>
+// LABELS: segment 3 holds labels[i] per k-mer (mdb_writer_add_block_labelled with a labels array; only the low ls bits are
+// stored) instead of the one constant; they are read from global memory where they are written, not held in registers.
+template <typename K, bool LABELS = false>
 __global__ __launch_bounds__(ENC_BLOCK)
 void encode_kmers_kernel(const K *__restrict__ keys, const u32 *__restrict__ counts, const u64 *__restrict__ bs,
                          const u64 *__restrict__ blk_pos, const u64 *__restrict__ blk_vbase, const u32 *__restrict__ blk_bb,
-                         u64 b0, u64 b1, u32 ss, u32 ls, u64 label, unsigned char *__restrict__ img) {
+                         u64 b0, u64 b1, u32 ss, u32 ls, u64 label, unsigned char *__restrict__ img,
+                         const u64 *__restrict__ labels = nullptr) {
   constexpr int R = EncRun<K>::R;
   const u64 g_begin = bs[b0], g_end = bs[b1];
   const u64 i0 = g_begin + ((u64)blockIdx.x * ENC_BLOCK + threadIdx.x) * R;
@@ -214,8 +217,13 @@ void encode_kmers_kernel(const K *__restrict__ keys, const u32 *__restrict__ cou
     // segment 3: labels (A10)
     if (ls) {
       const u64 lbase = vbase + n * (u64)VALUE_BITS;
-      const u64 lv = (ls >= 64) ? label : (label & ((1ull << ls) - 1ull));
-      for (int q = q0; q < q1; q++) rw.put(lbase + (i0 + q - bstart) * (u64)ls, ls, lv);
+      if constexpr (LABELS) {
+        const u64 lmask = (ls >= 64) ? ~0ull : ((1ull << ls) - 1ull);
+        for (int q = q0; q < q1; q++) rw.put(lbase + (i0 + q - bstart) * (u64)ls, ls, labels[i0 + q] & lmask);
+      } else {
+        const u64 lv = (ls >= 64) ? label : (label & ((1ull << ls) - 1ull));
+        for (int q = q0; q < q1; q++) rw.put(lbase + (i0 + q - bstart) * (u64)ls, ls, lv);
+      }
       rw.end_segment();
     }
     i = jend;
@@ -277,7 +285,8 @@ hipError_t launch_encode_sizes(const void *d_keys, uint32_t key_words, const uin
 hipError_t launch_encode_chunk(const void *d_keys, const uint32_t *d_counts, uint32_t key_words, const uint64_t *d_bs,
                                const uint64_t *d_blk_pos, const uint64_t *d_blk_vbase, const uint32_t *d_blk_bb,
                                uint64_t b0, uint64_t b1, uint64_t n_kmers_chunk, uint64_t prefix_of_block0,
-                               uint32_t suffix_size, uint32_t label_size, uint64_t label, void *d_img, hipStream_t st) {
+                               uint32_t suffix_size, uint32_t label_size, uint64_t label, void *d_img, hipStream_t st,
+                               const uint64_t *d_labels) {
   if (b1 <= b0) return hipSuccess;
   unsigned char *img = reinterpret_cast<unsigned char *>(d_img);
   hipLaunchKernelGGL(encode_headers_kernel, dim3((uint32_t)((b1 - b0 + 255) / 256)), dim3(256), 0, st,
@@ -286,15 +295,32 @@ hipError_t launch_encode_chunk(const void *d_keys, const uint32_t *d_counts, uin
                      suffix_size, label_size, img);
   MGC_CHECK(hipGetLastError());
   if (n_kmers_chunk == 0) return hipSuccess;
+  if (d_labels && label_size) {
+    const u64 *labs = reinterpret_cast<const u64 *>(d_labels);
+    if (key_words == 2) {
+      const uint64_t per_wg = (uint64_t)ENC_BLOCK * EncRun<K128>::R;
+      hipLaunchKernelGGL((encode_kmers_kernel<K128, true>), dim3((uint32_t)((n_kmers_chunk + per_wg - 1) / per_wg)), dim3(ENC_BLOCK), 0, st,
+                         reinterpret_cast<const K128 *>(d_keys), d_counts, reinterpret_cast<const u64 *>(d_bs),
+                         reinterpret_cast<const u64 *>(d_blk_pos), reinterpret_cast<const u64 *>(d_blk_vbase), d_blk_bb,
+                         (u64)b0, (u64)b1, suffix_size, label_size, (u64)label, img, labs);
+    } else {
+      const uint64_t per_wg = (uint64_t)ENC_BLOCK * EncRun<u64>::R;
+      hipLaunchKernelGGL((encode_kmers_kernel<u64, true>), dim3((uint32_t)((n_kmers_chunk + per_wg - 1) / per_wg)), dim3(ENC_BLOCK), 0, st,
+                         reinterpret_cast<const u64 *>(d_keys), d_counts, reinterpret_cast<const u64 *>(d_bs),
+                         reinterpret_cast<const u64 *>(d_blk_pos), reinterpret_cast<const u64 *>(d_blk_vbase), d_blk_bb,
+                         (u64)b0, (u64)b1, suffix_size, label_size, (u64)label, img, labs);
+    }
+    return hipGetLastError();
+  }
   if (key_words == 2) {
     const uint64_t per_wg = (uint64_t)ENC_BLOCK * EncRun<K128>::R;
-    hipLaunchKernelGGL(encode_kmers_kernel<K128>, dim3((uint32_t)((n_kmers_chunk + per_wg - 1) / per_wg)), dim3(ENC_BLOCK), 0, st,
+    hipLaunchKernelGGL((encode_kmers_kernel<K128, false>), dim3((uint32_t)((n_kmers_chunk + per_wg - 1) / per_wg)), dim3(ENC_BLOCK), 0, st,
                        reinterpret_cast<const K128 *>(d_keys), d_counts, reinterpret_cast<const u64 *>(d_bs),
                        reinterpret_cast<const u64 *>(d_blk_pos), reinterpret_cast<const u64 *>(d_blk_vbase), d_blk_bb,
                        (u64)b0, (u64)b1, suffix_size, label_size, (u64)label, img);
   } else {
     const uint64_t per_wg = (uint64_t)ENC_BLOCK * EncRun<u64>::R;
-    hipLaunchKernelGGL(encode_kmers_kernel<u64>, dim3((uint32_t)((n_kmers_chunk + per_wg - 1) / per_wg)), dim3(ENC_BLOCK), 0, st,
+    hipLaunchKernelGGL((encode_kmers_kernel<u64, false>), dim3((uint32_t)((n_kmers_chunk + per_wg - 1) / per_wg)), dim3(ENC_BLOCK), 0, st,
                        reinterpret_cast<const u64 *>(d_keys), d_counts, reinterpret_cast<const u64 *>(d_bs),
                        reinterpret_cast<const u64 *>(d_blk_pos), reinterpret_cast<const u64 *>(d_blk_vbase), d_blk_bb,
                        (u64)b0, (u64)b1, suffix_size, label_size, (u64)label, img);

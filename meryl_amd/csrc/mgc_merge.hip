@@ -211,10 +211,14 @@ __device__ __forceinline__ u32 sel_value(int fop, u32 v, u64 c, u32 flag) {
 }
 
 constexpr int SL_BLOCK = 256, SL_ITEMS = 8, SL_TILE = SL_BLOCK * SL_ITEMS;
-template <typename K, bool EMIT>
+// LABELS (emit only): the label of each kept k-mer follows it, through the label operation `lop` (LabelAcc, mgc_label.hpp) over
+// its one active input -- the input's value, not the new one, is what MIN sees (_acta[0]._val, src/meryl2/merylOpCompute.C:309-320)
+template <typename K, bool EMIT, bool LABELS = false>
 __global__ __launch_bounds__(SL_BLOCK)
 void select_kernel(const K *__restrict__ keys, const u32 *__restrict__ vals, const u32 *__restrict__ flags, u64 n, int fop, u64 c,
-                   u64 *__restrict__ tile_cnt /*EMIT: exclusive bases*/, K *__restrict__ outK, u32 *__restrict__ outC) {
+                   u64 *__restrict__ tile_cnt /*EMIT: exclusive bases*/, K *__restrict__ outK, u32 *__restrict__ outC,
+                   const u64 *__restrict__ labs = nullptr /*null: all zeros*/, int lop = 0, u64 lc = 0, u64 *__restrict__ outL = nullptr) {
+  static_assert(EMIT || !LABELS, "labels do not change what is kept");
   __shared__ u32 s_tmp[SL_BLOCK / 64 + 1];
   const u64 base = (u64)blockIdx.x * SL_TILE + (u64)threadIdx.x * SL_ITEMS;
   u32 nv[SL_ITEMS], kept = 0;
@@ -230,7 +234,16 @@ void select_kernel(const K *__restrict__ keys, const u32 *__restrict__ vals, con
   u64 o = tile_cnt[blockIdx.x] + off;
 #pragma unroll
   for (int q = 0; q < SL_ITEMS; q++)
-    if (nv[q]) { outK[o] = keys[base + q]; outC[o] = nv[q]; o++; }
+    if (nv[q]) {
+      outK[o] = keys[base + q]; outC[o] = nv[q];
+      if constexpr (LABELS) {
+        LabelAcc la;
+        la.begin(lc);
+        la.step(lop, labs ? labs[base + q] : 0ull, vals[base + q]);
+        outL[o] = la.l;
+      }
+      o++;
+    }
 }
 
 __global__ void fill_u32_kernel(u32 *__restrict__ p, u64 n, u32 v) {
@@ -271,6 +284,23 @@ hipError_t launch_select_emit(const void *d_keys, const uint32_t *d_vals, const 
   else
     hipLaunchKernelGGL((select_kernel<u64, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, reinterpret_cast<const u64 *>(d_keys), d_vals, d_flags,
                        (u64)n, fop, (u64)constant, tiles, reinterpret_cast<u64 *>(d_out_keys), d_out_vals);
+  return hipGetLastError();
+}
+hipError_t launch_select_emit_labelled(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words, int fop,
+                                       uint64_t constant, int lop, uint64_t lc, void *d_ws, void *d_out_keys, uint32_t *d_out_vals,
+                                       uint64_t *d_out_labs, hipStream_t st) {
+  if (fop < 0 || fop > 11 || lop < LOP_SET || lop > LOP_SEL_MAX || lop == 12) return hipErrorInvalidValue;
+  const uint64_t t = select_tiles(n);
+  if (t == 0) return hipSuccess;
+  u64 *tiles = reinterpret_cast<u64 *>(d_ws) + 8;
+  if (key_words == 2)
+    hipLaunchKernelGGL((select_kernel<K128, true, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, reinterpret_cast<const K128 *>(d_keys), d_vals,
+                       (const u32 *)nullptr, (u64)n, fop, (u64)constant, tiles, reinterpret_cast<K128 *>(d_out_keys), d_out_vals,
+                       reinterpret_cast<const u64 *>(d_labs), lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs));
+  else
+    hipLaunchKernelGGL((select_kernel<u64, true, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, reinterpret_cast<const u64 *>(d_keys), d_vals,
+                       (const u32 *)nullptr, (u64)n, fop, (u64)constant, tiles, reinterpret_cast<u64 *>(d_out_keys), d_out_vals,
+                       reinterpret_cast<const u64 *>(d_labs), lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs));
   return hipGetLastError();
 }
 hipError_t launch_fill_u32(uint32_t *d, uint64_t n, uint32_t v, hipStream_t st) {

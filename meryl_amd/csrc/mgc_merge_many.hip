@@ -21,6 +21,12 @@
 // values only where the pass needs them), and in LDS one write to stage, then per round one read, one write and
 // log2(run length) probes: about sum_{r < log2 N} log2(CAP * 2^r / N) key probes, 21 for N = 3 and 40 for N = 32 at CAP 2048.
 // No global atomics.
+//
+// Labels (meryl2; merylOpCompute::findOutputLabel, src/meryl2/merylOpCompute.C:286-395): the LABELS instantiation of the emit
+// pass reaches an element's label through the same tag as its value -- 8 B more read per element, 8 B more written per kept
+// k-mer, never staged in LDS (only a 32-entry table of the inputs' label pointers joins the value pointers') -- and the head
+// thread folds them with LabelAcc (mgc_label.hpp) in input order.  Labels do not decide what is written: the count pass is
+// the unlabelled one.
 #include "mgc_common.hpp"
 
 namespace mgc {
@@ -42,6 +48,7 @@ struct MergeManyDesc {
   const void *keys[MM_MAX];
   const u32  *vals[MM_MAX];
   u64         n[MM_MAX];
+  const u64  *labs[MM_MAX];                       // LABELS: input i's labels, null = all zeros
   u32         count;
 };
 
@@ -79,15 +86,17 @@ void merge_many_partition_kernel(MergeManyDesc d, u64 total, u64 tiles, u64 *__r
   if (lane < MM_MAX) splits[b * MM_MAX + lane] = L;
 }
 
-template <typename K, bool EMIT>
+template <typename K, bool EMIT, bool LABELS = false>
 __global__ __launch_bounds__(MM_BLOCK)
 void merge_many_kernel(MergeManyDesc d, int op, const u64 *__restrict__ splits, u64 *__restrict__ tile_cnt /*EMIT: exclusive bases*/,
-                       K *__restrict__ outK, u32 *__restrict__ outC) {
+                       K *__restrict__ outK, u32 *__restrict__ outC, int lop = 0, u64 lc = 0, u64 *__restrict__ outL = nullptr) {
+  static_assert(EMIT || !LABELS, "labels do not change what is written: there is no labelled count pass");
   constexpr int CAP = mm_cap<K>(), ITEMS = MMGeom<K>::ITEMS;
   __shared__ K         s_key[2][CAP];
   __shared__ u32       s_tag[2][CAP];
   __shared__ const K  *s_kp[MM_MAX];                         // input i's first element of this tile
   __shared__ const u32 *s_vp[MM_MAX];
+  __shared__ const u64 *s_lp[LABELS ? MM_MAX : 1];           // LABELS: input i's first label of this tile, null = all zeros
   __shared__ u32       s_off[MM_MAX + 1];                    // where run i begins in the staged image; [i >= N] = nt
   __shared__ u32       s_tmp[MM_BLOCK / 64 + 1];
   const u32 N = d.count;
@@ -102,7 +111,10 @@ void merge_many_kernel(MergeManyDesc d, int op, const u64 *__restrict__ splits, 
     if (i <= MM_MAX) s_off[i] = x - len;
 #pragma unroll
     for (int j = 0; j < MM_MAX; j++)
-      if (i == (u32)j) { s_kp[j] = reinterpret_cast<const K *>(d.keys[j]) + beg; s_vp[j] = d.vals[j] + beg; }
+      if (i == (u32)j) {
+        s_kp[j] = reinterpret_cast<const K *>(d.keys[j]) + beg; s_vp[j] = d.vals[j] + beg;
+        if constexpr (LABELS) s_lp[j] = d.labs[j] ? d.labs[j] + beg : nullptr;
+      }
   }
   __syncthreads();
   const u32 nt = s_off[MM_MAX];
@@ -150,9 +162,11 @@ void merge_many_kernel(MergeManyDesc d, int op, const u64 *__restrict__ splits, 
   const bool need_v = EMIT || op == 7;
   const u32 l0 = threadIdx.x * ITEMS;
   u32 heads = 0, head_mask = 0, vreg[ITEMS];
+  u64 lreg[LABELS ? ITEMS : 1];
 #pragma unroll
   for (int q = 0; q < ITEMS; q++) {
     vreg[q] = 0;
+    if constexpr (LABELS) lreg[q] = 0;
     const u32 p = l0 + q;
     if (p >= nt) continue;
     const K key = sk[p];
@@ -161,9 +175,16 @@ void merge_many_kernel(MergeManyDesc d, int op, const u64 *__restrict__ splits, 
     const u32 first = sg[p] >> 16;
     u32 cnt = 0, v = 0;
     bool alive = true;                                       // subtract: the running difference stayed positive
+    LabelAcc la;
+    if constexpr (LABELS) la.begin(lc);
     for (u32 g = p; g < nt && !KeyOps<K>::ne(sk[g], key); g++) {
       u32 c = 0;
       if (need_v) { const u32 tag = sg[g]; c = s_vp[tag >> 16][tag & 0xFFFFu]; }
+      if constexpr (LABELS) {                                // _acta[ll]._lab / ._val in input order
+        const u32 tag = sg[g];
+        const u64 *lp = s_lp[tag >> 16];
+        la.step(lop, lp ? lp[tag & 0xFFFFu] : 0ull, c);
+      }
       if (cnt == 0) v = c;
       else if (op == 7) { if (v > c) v -= c; else alive = false; }
       else if (op == 0 || op == 3) v += c;                   // the sum wraps mod 2^32 like kmvalu arithmetic
@@ -177,7 +198,10 @@ void merge_many_kernel(MergeManyDesc d, int op, const u64 *__restrict__ splits, 
     else if (op == 7) keep = first == 0 && alive;
     else if (op == 8) keep = first == 0 && cnt == 1;
     else keep = cnt == 1;
-    if (keep) { head_mask |= 1u << q; heads++; vreg[q] = (op == 10) ? cnt : v; }
+    if (keep) {
+      head_mask |= 1u << q; heads++; vreg[q] = (op == 10) ? cnt : v;
+      if constexpr (LABELS) lreg[q] = la.l;
+    }
   }
   u32 tot;
   const u32 base = block_excl_scan<MM_BLOCK, u32>(heads, s_tmp, &tot);
@@ -188,7 +212,11 @@ void merge_many_kernel(MergeManyDesc d, int op, const u64 *__restrict__ splits, 
   u64 o = tile_cnt[blockIdx.x] + base;
 #pragma unroll
   for (int q = 0; q < ITEMS; q++)
-    if (head_mask & (1u << q)) { outK[o] = sk[l0 + q]; outC[o] = vreg[q]; o++; }
+    if (head_mask & (1u << q)) {
+      outK[o] = sk[l0 + q]; outC[o] = vreg[q];
+      if constexpr (LABELS) outL[o] = lreg[q];
+      o++;
+    }
 }
 
 uint32_t merge_many_tile(uint32_t key_words) { return key_words == 2 ? (uint32_t)mm_tile<K128>() : (uint32_t)mm_tile<u64>(); }
@@ -210,8 +238,9 @@ size_t merge_many_workspace_bytes(const uint64_t *n, uint32_t n_inputs, uint32_t
   return (mm_splits_at(t) + (size_t)(t + 1) * MM_MAX) * sizeof(u64) + 256;
 }
 
-static bool mm_desc(MergeManyDesc *d, const void *const *keys, const uint32_t *const *vals, const uint64_t *n, uint32_t n_inputs, int op) {
-  if (n_inputs < 2 || n_inputs > (uint32_t)MM_MAX || op < 0 || op > 10) return false;
+static bool mm_desc(MergeManyDesc *d, const void *const *keys, const uint32_t *const *vals, const uint64_t *n, uint32_t n_inputs, int op,
+                    uint32_t min_inputs = 2) {
+  if (n_inputs < min_inputs || n_inputs > (uint32_t)MM_MAX || op < 0 || op > 10) return false;
   memset(d, 0, sizeof(*d));
   d->count = n_inputs;
   for (uint32_t i = 0; i < n_inputs; i++) {
@@ -224,9 +253,9 @@ static bool mm_desc(MergeManyDesc *d, const void *const *keys, const uint32_t *c
 
 // pass 1: cuts the inputs into tiles and leaves the output length at ws[0] (merge_read_total reads it)
 hipError_t launch_merge_many_count(const void *const *keys, const uint32_t *const *vals, const uint64_t *n, uint32_t n_inputs,
-                                   uint32_t key_words, int op, void *d_ws, hipStream_t st) {
+                                   uint32_t key_words, int op, void *d_ws, hipStream_t st, bool allow_one) {
   MergeManyDesc d;
-  if (!mm_desc(&d, keys, vals, n, n_inputs, op)) return hipErrorInvalidValue;
+  if (!mm_desc(&d, keys, vals, n, n_inputs, op, allow_one ? 1 : 2)) return hipErrorInvalidValue;
   u64 *ws = reinterpret_cast<u64 *>(d_ws);
   const uint64_t total = mm_total(n, n_inputs), t = mm_tiles(total, key_words);
   if (t == 0) return hipMemsetAsync(ws, 0, 8, st);
@@ -258,6 +287,27 @@ hipError_t launch_merge_many_emit(const void *const *keys, const uint32_t *const
   else
     hipLaunchKernelGGL((merge_many_kernel<u64, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, op, splits, tiles,
                        reinterpret_cast<u64 *>(d_out_keys), d_out_vals);
+  return hipGetLastError();
+}
+
+// pass 2 with labels: the same, and d_out_labs[o] = label operation `lop` (kernel code) over the inputs that hold k-mer o
+hipError_t launch_merge_many_emit_labelled(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs,
+                                           const uint64_t *n, uint32_t n_inputs, uint32_t key_words, int op, int lop, uint64_t lc, void *d_ws,
+                                           void *d_out_keys, uint32_t *d_out_vals, uint64_t *d_out_labs, hipStream_t st) {
+  MergeManyDesc d;
+  if (!mm_desc(&d, keys, vals, n, n_inputs, op, 1) || lop < LOP_SET || lop > LOP_SEL_MAX || lop == 12 || (lop == LOP_INVERT && n_inputs > 1))
+    return hipErrorInvalidValue;
+  for (uint32_t i = 0; i < n_inputs; i++) d.labs[i] = labs ? reinterpret_cast<const u64 *>(labs[i]) : nullptr;
+  u64 *ws = reinterpret_cast<u64 *>(d_ws);
+  const uint64_t t = mm_tiles(mm_total(n, n_inputs), key_words);
+  if (t == 0) return hipSuccess;
+  u64 *tiles = ws + 8, *splits = ws + mm_splits_at(t);
+  if (key_words == 2)
+    hipLaunchKernelGGL((merge_many_kernel<K128, true, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, op, splits, tiles,
+                       reinterpret_cast<K128 *>(d_out_keys), d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs));
+  else
+    hipLaunchKernelGGL((merge_many_kernel<u64, true, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, op, splits, tiles,
+                       reinterpret_cast<u64 *>(d_out_keys), d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs));
   return hipGetLastError();
 }
 

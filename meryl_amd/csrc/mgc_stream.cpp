@@ -67,7 +67,7 @@ struct mgc_db_stream {
   DBuf d_bs, d_bytes, d_vbase, d_bb, d_pos, d_hist, d_big, d_img[2];
   char *pinned[NSLOT_MAX] = {nullptr};
 
-  struct Range { const void *keys; const uint32_t *counts; uint64_t n, pb, pe; };
+  struct Range { const void *keys; const uint32_t *counts; uint64_t n, pb, pe; const uint64_t *labels = nullptr; /*per k-mer; null: `label`*/ };
   struct Piece { uint32_t ff; int slot; uint64_t nbytes, file_offset; };
 
   std::mutex mu;
@@ -223,7 +223,7 @@ int mgc_db_stream::process(const Range &r) {
     DS_TRY(hipEventRecord(ev_a, st_enc));
     DS_TRY(mgc::launch_encode_chunk(r.keys, r.counts, kw, d_bs.as<uint64_t>(), d_pos.as<uint64_t>(), d_vbase.as<uint64_t>(),
                                     d_bb.as<uint32_t>(), c.b0, c.b1, h_bs[c.b1] - h_bs[c.b0], r.pb, ss, label_size, label,
-                                    img.p, st_enc));
+                                    img.p, st_enc, r.labels));
     DS_TRY(hipEventRecord(ev_enc[ci & 1], st_enc));
     return MGC_OK;
   };
@@ -376,6 +376,12 @@ extern "C" mgc_db_stream *mgc_db_stream_open(const char *path, uint32_t k, uint3
 
 extern "C" int mgc_db_stream_write(mgc_db_stream *d, const void *d_keys, const uint32_t *d_counts, uint64_t n,
                                    uint64_t prefix_begin, uint64_t prefix_end) {
+  return mgc_db_stream_write_labelled(d, d_keys, d_counts, nullptr, n, prefix_begin, prefix_end);
+}
+
+// per-k-mer labels (merylBlockWriter::addCountedBlock with a labels array, src/meryl2/merylCountArray.C:469-471)
+extern "C" int mgc_db_stream_write_labelled(mgc_db_stream *d, const void *d_keys, const uint32_t *d_counts, const uint64_t *d_labels,
+                                            uint64_t n, uint64_t prefix_begin, uint64_t prefix_end) {
   if (!d) return MGC_EINVAL;
   std::lock_guard<std::mutex> g(d->mu);
   if (d->status != MGC_OK) return d->status;
@@ -387,7 +393,7 @@ extern "C" int mgc_db_stream_write(mgc_db_stream *d, const void *d_keys, const u
   d->next_prefix = prefix_end;
   if (prefix_begin == prefix_end) return n ? MGC_EINVAL : MGC_OK;
   mgc_db_stream::Range r;
-  r.keys = d_keys; r.counts = d_counts; r.n = n; r.pb = prefix_begin; r.pe = prefix_end;
+  r.keys = d_keys; r.counts = d_counts; r.n = n; r.pb = prefix_begin; r.pe = prefix_end; r.labels = d_labels;
   d->jobs.push_back(r);
   d->jobs_queued++;
   d->cv.notify_all();
@@ -699,13 +705,16 @@ namespace {
 // threads (65-70 M k-mers/s each) and uploaded as arrays, as before.
 // MGC_DECODE_HOST=1 (tests): read ONCE per merge / filter operation, by its entry point
 bool decode_on_host() { const char *e = getenv("MGC_DECODE_HOST"); return e && e[0] == '1'; }
+// in_l (the labelled evaluation; null otherwise): the labels of the inputs that store some, beside the values -- from the device
+// decoder, or from mdb_reader_read_file_ex on the host path; an input without labels gets no buffer (its labels are zeros)
 int load_slices(std::vector<mdb_reader *> &rd, uint32_t ff, uint32_t kw, std::vector<DBuf> &in_k, std::vector<DBuf> &in_c,
-                std::vector<uint64_t> &hn, hipStream_t st, std::string *msg, bool host_decode) {
+                std::vector<uint64_t> &hn, hipStream_t st, std::string *msg, bool host_decode, std::vector<DBuf> *in_l = nullptr) {
   const uint32_t n_inputs = (uint32_t)rd.size();
   struct Raw { unsigned char *bytes = nullptr; uint64_t size = 0; mdb_raw_block *blocks = nullptr; uint64_t nb = 0; bool on_device = false; };
   std::vector<Raw> raw(n_inputs);
   std::vector<std::vector<uint64_t>> hk(n_inputs);
   std::vector<uint32_t *> hc(n_inputs, nullptr);
+  std::vector<uint64_t *> hl(n_inputs, nullptr);
   std::vector<int> rrc(n_inputs, MGC_OK);
   std::vector<std::string> rmsg(n_inputs);
   std::vector<mdb_info> infos(n_inputs);
@@ -721,7 +730,7 @@ int load_slices(std::vector<mdb_reader *> &rd, uint32_t ff, uint32_t kw, std::ve
           if (rc != MGC_EUNSUPPORTED) { rrc[i] = rc; rmsg[i] = mdb_last_error(); return; }
         }
         uint64_t *lo = nullptr, *hi = nullptr;
-        rrc[i] = mdb_reader_read_file_ex(rd[i], ff, &lo, &hi, &hc[i], nullptr, &hn[i]);
+        rrc[i] = mdb_reader_read_file_ex(rd[i], ff, &lo, &hi, &hc[i], (in_l && infos[i].label_size) ? &hl[i] : nullptr, &hn[i]);
         if (rrc[i] != MGC_OK) { rmsg[i] = mdb_last_error(); return; }
         hk[i].resize((size_t)kw * hn[i]);
         if (kw == 1) { if (hn[i]) memcpy(hk[i].data(), lo, 8 * hn[i]); }
@@ -740,6 +749,8 @@ int load_slices(std::vector<mdb_reader *> &rd, uint32_t ff, uint32_t kw, std::ve
   for (uint32_t i = 0; i < n_inputs && rc == MGC_OK && e == hipSuccess; i++) {
     e = in_k[i].ensure(8 * (size_t)kw * hn[i]);
     if (e == hipSuccess) e = in_c[i].ensure(4 * hn[i]);
+    const bool with_l = in_l && infos[i].label_size;
+    if (e == hipSuccess && with_l) e = (*in_l)[i].ensure(8 * hn[i]);
     if (e != hipSuccess || !hn[i]) continue;
     if (raw[i].on_device) {
       e = d_file.ensure(raw[i].size + 16);
@@ -748,24 +759,27 @@ int load_slices(std::vector<mdb_reader *> &rd, uint32_t ff, uint32_t kw, std::ve
       if (e == hipSuccess) e = hipMemcpyAsync(d_file.p, raw[i].bytes, raw[i].size + 16, hipMemcpyHostToDevice, st);
       if (e == hipSuccess) e = hipMemcpyAsync(d_blocks.p, raw[i].blocks, sizeof(mdb_raw_block) * raw[i].nb, hipMemcpyHostToDevice, st);
       if (e == hipSuccess) e = mgc::launch_decode_blocks(d_file.p, d_blocks.p, raw[i].nb, infos[i].suffix_size, infos[i].label_size, kw, in_k[i].p,
-                                                         in_c[i].as<uint32_t>(), d_err.as<uint32_t>(), st);
+                                                         in_c[i].as<uint32_t>(), d_err.as<uint32_t>(), st, with_l ? (*in_l)[i].as<uint64_t>() : nullptr);
       if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err.p, 4, hipMemcpyDeviceToHost, st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);                     // d_file is reused by the next input
       if (e == hipSuccess && h_err) { rc = MGC_EINVAL; *msg = "corrupt block in a database file (device decoder, code " + std::to_string(h_err) + ")"; }
     } else {
       e = hipMemcpyAsync(in_k[i].p, hk[i].data(), 8 * (size_t)kw * hn[i], hipMemcpyHostToDevice, st);
       if (e == hipSuccess) e = hipMemcpyAsync(in_c[i].p, hc[i], 4 * hn[i], hipMemcpyHostToDevice, st);
+      if (e == hipSuccess && with_l) e = hipMemcpyAsync((*in_l)[i].p, hl[i], 8 * hn[i], hipMemcpyHostToDevice, st);
     }
   }
   if (e == hipSuccess && rc == MGC_OK) e = hipStreamSynchronize(st);
-  for (uint32_t i = 0; i < n_inputs; i++) { mdb_free(hc[i]); mdb_free(raw[i].bytes); mdb_free(raw[i].blocks); }
+  for (uint32_t i = 0; i < n_inputs; i++) { mdb_free(hc[i]); mdb_free(hl[i]); mdb_free(raw[i].bytes); mdb_free(raw[i].blocks); }
   d_file.release(); d_blocks.release(); d_err.release();
   if (e != hipSuccess) { rc = (e == hipErrorOutOfMemory) ? MGC_ENOMEM : MGC_EHIP; *msg = std::string("uploading a slice: ") + hipGetErrorString(e); }
   return rc;
 }
 
 // inputs of one k, no labels, no multisets -> readers + the first one's info; false: message in the thread error
-bool open_merge_inputs(const char *const *inputs, uint32_t n_inputs, std::vector<mdb_reader *> &rd, mdb_info *first, const char *who) {
+// (max_label_size given -- the labelled evaluation: labels are allowed, and the largest label_size among the inputs is returned)
+bool open_merge_inputs(const char *const *inputs, uint32_t n_inputs, std::vector<mdb_reader *> &rd, mdb_info *first, const char *who,
+                       uint32_t *max_label_size = nullptr) {
   rd.assign(n_inputs, nullptr);
   auto close_all = [&]() { for (mdb_reader *r : rd) if (r) mdb_reader_close(r); };
   memset(first, 0, sizeof(*first));
@@ -776,11 +790,12 @@ bool open_merge_inputs(const char *const *inputs, uint32_t n_inputs, std::vector
     mdb_reader_info(rd[i], &inf);
     // the merge combines VALUES only: labels would be dropped and a multiset's repeated k-mers folded -- refuse rather than
     // write something that silently differs
-    if (inf.label_size != 0 || (inf.flags & 1u)) {
-      set_err(nullptr, "%s: '%s' %s: not supported here", who, inputs[i], inf.label_size ? "stores labels" : "is a multiset");
+    if ((inf.label_size != 0 && !max_label_size) || (inf.flags & 1u)) {
+      set_err(nullptr, "%s: '%s' %s: not supported here", who, inputs[i], (inf.label_size && !max_label_size) ? "stores labels" : "is a multiset");
       close_all();
       return false;
     }
+    if (max_label_size) *max_label_size = std::max(*max_label_size, inf.label_size);
     if (i == 0) *first = inf;
     else if (inf.k != first->k) {
       set_err(nullptr, "%s: '%s' holds %u-mers, '%s' %u-mers", who, inputs[i], inf.k, inputs[0], first->k);   // merylOp.C: kmer size mismatch
@@ -792,7 +807,7 @@ bool open_merge_inputs(const char *const *inputs, uint32_t n_inputs, std::vector
 }
 
 // one (k-mer, value) stream in HBM
-struct SliceRef { const void *k = nullptr; const uint32_t *c = nullptr; uint64_t n = 0; };
+struct SliceRef { const void *k = nullptr; const uint32_t *c = nullptr; uint64_t n = 0; const uint64_t *l = nullptr; /*labelled evaluation; null: zeros*/ };
 
 // buffers of the left fold (grow-only, reused from slice to slice)
 struct FoldBufs {
@@ -986,7 +1001,7 @@ constexpr uint32_t MERGE_MANY_MIN_INPUTS = 3;
 bool merge_many_enabled() { const char *e = getenv("MGC_MERGE_MANY"); return !(e && e[0] == '0'); }
 
 struct EvalNode {
-  DBuf k, c;                       // an inner node's result
+  DBuf k, c, l;                    // an inner node's result (l: labelled evaluation)
   FoldBufs *fold = nullptr;        // merge nodes that fold
   SliceRef res;
   mgc_db_stream *out = nullptr;
@@ -998,11 +1013,20 @@ std::string plain_path(const char *p) {
   while (s.size() > 1 && s.back() == '/') s.pop_back();
   return s;
 }
-}  // namespace
 
-extern "C" int mgc_db_eval(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children, uint32_t root,
-                           mgc_eval_slice_cb cb, void *ctx, int device, int host_threads) {
-  auto bad = [&](const std::string &m) { set_err(nullptr, "mgc_db_eval: %s", m.c_str()); return MGC_EINVAL; };
+// what mgc_db_eval_labelled adds to a tree: per node the label operation (MGC_LABEL_*) and its constant, the label size of the
+// outputs (0: the largest among the leaves) and the callback that also takes labels
+struct LabelPlan {
+  const mgc_eval_node_labelled *nodes;
+  uint32_t label_size;
+  mgc_eval_slice_labelled_cb cb;
+};
+
+// mgc_db_eval (lp == nullptr) and mgc_db_eval_labelled: one walk, one validation, one slice loop
+int eval_impl(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children, uint32_t root,
+              mgc_eval_slice_cb cb, void *ctx, int device, int host_threads, const LabelPlan *lp) {
+  const char *who = lp ? "mgc_db_eval_labelled" : "mgc_db_eval";
+  auto bad = [&](const std::string &m) { set_err(nullptr, "%s: %s", who, m.c_str()); return MGC_EINVAL; };
   if (!nodes || n_nodes == 0 || root >= n_nodes || (n_children && !children)) return bad("bad arguments");
   // ---- the tree: every node reached at most once, from the root (post-order = evaluation order)
   std::vector<uint32_t> order, leaves;
@@ -1025,6 +1049,14 @@ extern "C" int mgc_db_eval(const mgc_eval_node *nodes, uint32_t n_nodes, const u
         if (nd.kind == MGC_NODE_VALUE && (nd.op < MGC_VALUE_LESS_THAN || nd.op > MGC_VALUE_MODULO)) return bad(id + ": unknown value operation");
         if (nd.kind == MGC_NODE_MERGE && nd.n_children == 0) return bad(id + ": a merge operation needs an input");
         if (nd.kind == MGC_NODE_MERGE && (nd.op < MGC_MERGE_UNION_SUM || nd.op > MGC_MERGE_UNION)) return bad(id + ": unknown merge operation");
+        if (lp && nd.kind != MGC_NODE_DATABASE) {
+          const int lop = lp->nodes[f.node].label_op;
+          if (mgc::label_kernel_op(nd.kind == MGC_NODE_MERGE, nd.op, lop) < 0) return bad(id + ": unknown label operation " + std::to_string(lop));
+          if (lop == MGC_LABEL_INVERT && nd.n_children > 1) return bad(id + ": label=invert takes one input, the node has " + std::to_string(nd.n_children));
+          // the left fold combines two streams at a time: DIFFERENCE, MIN or LIGHTEST over all inputs at once cannot be folded
+          if (nd.kind == MGC_NODE_MERGE && nd.n_children > MGC_MERGE_MANY_MAX)
+            return bad(id + ": a merge of " + std::to_string(nd.n_children) + " inputs; with labels at most " + std::to_string(MGC_MERGE_MANY_MAX));
+        }
       }
       if (f.next < nd.n_children) {
         const uint32_t ch = children[nd.first_child + f.next++];
@@ -1054,11 +1086,14 @@ extern "C" int mgc_db_eval(const mgc_eval_node *nodes, uint32_t n_nodes, const u
   // ---- leaves: open, one k, no labels, no multisets (leaves[] is in left-to-right order)
   std::vector<mdb_reader *> rd;
   mdb_info first;
+  uint32_t leaf_label_size = 0;
   {
     std::vector<const char *> paths;
     for (uint32_t v : leaves) paths.push_back(nodes[v].path);
-    if (!open_merge_inputs(paths.data(), (uint32_t)paths.size(), rd, &first, "mgc_db_eval")) return MGC_EINVAL;
+    if (!open_merge_inputs(paths.data(), (uint32_t)paths.size(), rd, &first, who, lp ? &leaf_label_size : nullptr)) return MGC_EINVAL;
   }
+  const uint32_t label_size = lp ? (lp->label_size ? lp->label_size : leaf_label_size) : 0;
+  if (label_size > 64) { for (mdb_reader *r : rd) if (r) mdb_reader_close(r); return bad("a label has at most 64 bits"); }
   auto close_readers = [&]() { for (mdb_reader *r : rd) if (r) mdb_reader_close(r); };
   const uint32_t k = first.k, kw = k > 32 ? 2u : 1u, n_leaves = (uint32_t)leaves.size();
   std::vector<EvalNode> ev(n_nodes);
@@ -1073,21 +1108,22 @@ extern "C" int mgc_db_eval(const mgc_eval_node *nodes, uint32_t n_nodes, const u
   if (device < 0) (void)hipGetDevice(&device);
   int rc = MGC_OK;
   std::string msg;
+  const std::string who_colon = std::string(who) + ": ";
   auto hip_fail = [&](hipError_t e, const char *what) {
     if (e == hipSuccess) return false;
     rc = (e == hipErrorOutOfMemory) ? MGC_ENOMEM : MGC_EHIP;
-    msg = std::string("mgc_db_eval: ") + what + ": " + hipGetErrorString(e);
+    msg = who_colon + what + ": " + hipGetErrorString(e);
     return true;
   };
   for (uint32_t v : order) {
     if (nodes[v].kind == MGC_NODE_DATABASE || !nodes[v].path) continue;
-    ev[v].out = mgc_db_stream_open(nodes[v].path, k, w_prefix_of(v), 0, 0, 0, 1, host_threads, device);
+    ev[v].out = mgc_db_stream_open(nodes[v].path, k, w_prefix_of(v), label_size, 0, 0, 1, host_threads, device);
     if (!ev[v].out) { rc = MGC_EINVAL; msg = mgc_db_stream_error(nullptr); break; }
   }
   hipStream_t st = nullptr;
-  std::vector<DBuf> in_k(n_leaves), in_c(n_leaves);
+  std::vector<DBuf> in_k(n_leaves), in_c(n_leaves), in_l(lp ? n_leaves : 0);
   DBuf ws;
-  std::vector<uint64_t> hn, h_keys, h_lo, h_hi;
+  std::vector<uint64_t> hn, h_keys, h_lo, h_hi, h_labs;
   std::vector<uint32_t> h_vals;
   if (rc == MGC_OK && !hip_fail(hipSetDevice(device), "hipSetDevice")) (void)hip_fail(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate");
 
@@ -1099,6 +1135,40 @@ extern "C" int mgc_db_eval(const mgc_eval_node *nodes, uint32_t n_nodes, const u
     for (uint32_t i = 0; i < nd.n_children; i++) in[i] = ev[children[nd.first_child + i]].res;
     uint64_t n_new = 0;
     hipError_t e;
+    if (lp) {                                                // labels travel with the k-mers; every merge through merge_many
+      const int lop = mgc::label_kernel_op(nd.kind == MGC_NODE_MERGE, nd.op, lp->nodes[v].label_op);
+      const uint64_t lc = lp->nodes[v].label_constant;
+      if (nd.kind == MGC_NODE_VALUE) {
+        e = ws.ensure(mgc::select_workspace_bytes(in[0].n));
+        if (e == hipSuccess) e = mgc::launch_select_count(in[0].k, in[0].c, nullptr, in[0].n, kw, nd.op, nd.constant, ws.p, st);
+        if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
+        if (e == hipSuccess) e = me.k.ensure(8 * (size_t)kw * n_new);
+        if (e == hipSuccess) e = me.c.ensure(4 * n_new);
+        if (e == hipSuccess) e = me.l.ensure(8 * n_new);
+        if (e == hipSuccess) e = mgc::launch_select_emit_labelled(in[0].k, in[0].c, in[0].l, in[0].n, kw, nd.op, nd.constant, lop, lc, ws.p, me.k.p,
+                                                                  me.c.as<uint32_t>(), me.l.as<uint64_t>(), st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (hip_fail(e, "a value operation")) return false;
+      } else {
+        const void *kp[MGC_MERGE_MANY_MAX];
+        const uint32_t *cp[MGC_MERGE_MANY_MAX];
+        const uint64_t *lpp[MGC_MERGE_MANY_MAX];
+        uint64_t nn[MGC_MERGE_MANY_MAX];
+        for (uint32_t i = 0; i < nd.n_children; i++) { kp[i] = in[i].k; cp[i] = in[i].c; lpp[i] = in[i].l; nn[i] = in[i].n; }
+        e = ws.ensure(mgc::merge_many_workspace_bytes(nn, nd.n_children, kw));
+        if (e == hipSuccess) e = mgc::launch_merge_many_count(kp, cp, nn, nd.n_children, kw, nd.op, ws.p, st, true);
+        if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
+        if (e == hipSuccess) e = me.k.ensure(8 * (size_t)kw * n_new);
+        if (e == hipSuccess) e = me.c.ensure(4 * n_new);
+        if (e == hipSuccess) e = me.l.ensure(8 * n_new);
+        if (e == hipSuccess) e = mgc::launch_merge_many_emit_labelled(kp, cp, lpp, nn, nd.n_children, kw, nd.op, lop, lc, ws.p, me.k.p,
+                                                                      me.c.as<uint32_t>(), me.l.as<uint64_t>(), st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (hip_fail(e, "merging a slice")) return false;
+      }
+      me.res = SliceRef{me.k.p, me.c.as<uint32_t>(), n_new, me.l.as<uint64_t>()};
+      return true;
+    }
     if (nd.kind == MGC_NODE_VALUE) {
       e = ws.ensure(mgc::select_workspace_bytes(in[0].n));
       if (e == hipSuccess) e = mgc::launch_select_count(in[0].k, in[0].c, nullptr, in[0].n, kw, nd.op, nd.constant, ws.p, st);
@@ -1134,49 +1204,56 @@ extern "C" int mgc_db_eval(const mgc_eval_node *nodes, uint32_t n_nodes, const u
   };
 
   for (uint32_t ff = 0; ff < MGC_NUM_FILES && rc == MGC_OK; ff++) {
-    rc = load_slices(rd, ff, kw, in_k, in_c, hn, st, &msg, host_decode);
-    if (rc != MGC_OK) { msg = "mgc_db_eval: " + msg; break; }
+    rc = load_slices(rd, ff, kw, in_k, in_c, hn, st, &msg, host_decode, lp ? &in_l : nullptr);
+    if (rc != MGC_OK) { msg = who_colon + msg; break; }
     for (uint32_t v : order) {
       EvalNode &me = ev[v];
-      if (nodes[v].kind == MGC_NODE_DATABASE) me.res = SliceRef{in_k[me.leaf].p, in_c[me.leaf].as<uint32_t>(), hn[me.leaf]};
+      if (nodes[v].kind == MGC_NODE_DATABASE)
+        me.res = SliceRef{in_k[me.leaf].p, in_c[me.leaf].as<uint32_t>(), hn[me.leaf], (lp && in_l[me.leaf].p) ? in_l[me.leaf].as<uint64_t>() : nullptr};
       else if (!eval_node(v)) break;
       if (me.out) {
         const uint64_t blocks_per_file = 1ull << (w_prefix_of(v) - MGC_NUM_FILES_BITS);
-        rc = mgc_db_stream_write(me.out, me.res.k, me.res.c, me.res.n, (uint64_t)ff * blocks_per_file, ((uint64_t)ff + 1) * blocks_per_file);
-        if (rc != MGC_OK) { msg = std::string("mgc_db_eval: ") + mgc_db_stream_error(me.out); break; }
+        rc = mgc_db_stream_write_labelled(me.out, me.res.k, me.res.c, label_size ? me.res.l : nullptr, me.res.n, (uint64_t)ff * blocks_per_file,
+                                          ((uint64_t)ff + 1) * blocks_per_file);
+        if (rc != MGC_OK) { msg = who_colon + mgc_db_stream_error(me.out); break; }
       }
     }
     if (rc != MGC_OK) break;
-    if (cb) {
+    if (cb || (lp && lp->cb)) {
       const SliceRef &r = ev[root].res;
       h_keys.resize((size_t)kw * r.n);
       h_vals.resize(r.n);
+      if (lp) h_labs.assign(r.n, 0);
       hipError_t e = hipSuccess;
       if (r.n) {
         e = hipMemcpyAsync(h_keys.data(), r.k, 8 * (size_t)kw * r.n, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipMemcpyAsync(h_vals.data(), r.c, 4 * r.n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && lp && r.l) e = hipMemcpyAsync(h_labs.data(), r.l, 8 * r.n, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
       }
       if (hip_fail(e, "copying the root's slice")) break;
-      if (kw == 1) cb(ctx, ff, h_keys.data(), nullptr, h_vals.data(), r.n);
-      else {
+      const uint64_t *lo = h_keys.data(), *hi = nullptr;
+      if (kw == 2) {
         h_lo.resize(r.n); h_hi.resize(r.n);
         for (uint64_t j = 0; j < r.n; j++) { h_lo[j] = h_keys[2 * j]; h_hi[j] = h_keys[2 * j + 1]; }
-        cb(ctx, ff, h_lo.data(), h_hi.data(), h_vals.data(), r.n);
+        lo = h_lo.data(); hi = h_hi.data();
       }
+      if (lp) lp->cb(ctx, ff, lo, hi, h_vals.data(), h_labs.data(), r.n);
+      else cb(ctx, ff, lo, hi, h_vals.data(), r.n);
     }
     for (uint32_t v : order) {                               // the buffers are reused for the next slice
       if (!ev[v].out) continue;
       const int rs = mgc_db_stream_sync(ev[v].out);
-      if (rs != MGC_OK && rc == MGC_OK) { rc = rs; msg = std::string("mgc_db_eval: ") + mgc_db_stream_error(ev[v].out); }
+      if (rs != MGC_OK && rc == MGC_OK) { rc = rs; msg = who_colon + mgc_db_stream_error(ev[v].out); }
     }
   }
   // an output whose node failed mid-slice may still be encoding from buffers about to go
   if (rc != MGC_OK) for (uint32_t v : order) if (ev[v].out) (void)mgc_db_stream_sync(ev[v].out);
   for (auto &b : in_k) b.release();
   for (auto &b : in_c) b.release();
+  for (auto &b : in_l) b.release();
   ws.release();
-  for (EvalNode &e : ev) { e.k.release(); e.c.release(); if (e.fold) { e.fold->release(); delete e.fold; } }
+  for (EvalNode &e : ev) { e.k.release(); e.c.release(); e.l.release(); if (e.fold) { e.fold->release(); delete e.fold; } }
   if (st) (void)hipStreamDestroy(st);
   close_readers();
   for (uint32_t v : order) {
@@ -1186,4 +1263,25 @@ extern "C" int mgc_db_eval(const mgc_eval_node *nodes, uint32_t n_nodes, const u
   }
   if (rc != MGC_OK) set_err(nullptr, "%s", msg.c_str());
   return rc;
+}
+}  // namespace
+
+extern "C" int mgc_db_eval(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children, uint32_t root,
+                           mgc_eval_slice_cb cb, void *ctx, int device, int host_threads) {
+  return eval_impl(nodes, n_nodes, children, n_children, root, cb, ctx, device, host_threads, nullptr);
+}
+
+// the same tree with labels (include/meryl_db.h): the label operation of every node is merylOpCompute::findOutputLabel
+// (src/meryl2/merylOpCompute.C:286-395) over the inputs that hold the k-mer
+extern "C" int mgc_db_eval_labelled(const mgc_eval_node_labelled *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
+                                    uint32_t root, uint32_t label_size, mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads) {
+  if (!nodes || n_nodes == 0) { set_err(nullptr, "mgc_db_eval_labelled: bad arguments"); return MGC_EINVAL; }
+  if (label_size > 64) { set_err(nullptr, "mgc_db_eval_labelled: a label has at most 64 bits"); return MGC_EINVAL; }
+  std::vector<mgc_eval_node> base(n_nodes);
+  for (uint32_t i = 0; i < n_nodes; i++) {
+    base[i].kind = nodes[i].kind; base[i].op = nodes[i].op; base[i].constant = nodes[i].constant; base[i].path = nodes[i].path;
+    base[i].first_child = nodes[i].first_child; base[i].n_children = nodes[i].n_children;
+  }
+  LabelPlan lp{nodes, label_size, cb};
+  return eval_impl(base.data(), n_nodes, children, n_children, root, nullptr, ctx, device, host_threads, &lp);
 }

@@ -24,13 +24,18 @@ class Writer:
         if not self._h:
             raise _err("mdb_writer_open")
 
-    def add_block(self, prefix, suffix_lo, counts, suffix_hi=None, label=0):
+    def add_block(self, prefix, suffix_lo, counts, suffix_hi=None, label=0, labels=None):
+        """labels: one label per k-mer (their low label_size bits are stored); None: the constant `label` for all of them"""
         slo = np.ascontiguousarray(suffix_lo, dtype=np.uint64)
         cnt = np.ascontiguousarray(counts, dtype=np.uint32)
         shi = None if suffix_hi is None else np.ascontiguousarray(suffix_hi, dtype=np.uint64)
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.uint64)
+        if lab is not None and lab.size != slo.size:
+            raise ValueError("labels: %d entries for %d k-mers" % (lab.size, slo.size))
         rc = capi.lib().mdb_writer_add_block_labelled(self._h, int(prefix), slo.size, slo.ctypes.data if slo.size else None,
                                                       shi.ctypes.data if shi is not None and shi.size else None,
-                                                      cnt.ctypes.data if cnt.size else None, None, int(label))
+                                                      cnt.ctypes.data if cnt.size else None,
+                                                      lab.ctypes.data if lab is not None and lab.size else None, int(label))
         if rc != 0:
             raise _err("mdb_writer_add_block")
 
@@ -193,3 +198,71 @@ def evaluate(tree, on_slice=None, device=-1, host_threads=8):
     if rc != 0:
         msg = capi.lib().mgc_db_stream_error(None)
         raise capi.MgcError(rc, "mgc_db_eval", msg.decode("utf-8", "replace") if msg else "")
+
+
+def _label_option(label):
+    """the "label" option of a node -> (MGC_LABEL_* code, constant): "or", ("and", 0x0F), or a number for the word"""
+    if label is None:
+        return capi.LABEL_OPS["default"], 0
+    word, const = (label, None) if isinstance(label, (str, int)) else tuple(label)
+    if isinstance(word, str) and word not in capi.LABEL_OPS:
+        raise ValueError("unknown label operation '%s'" % word)
+    code = capi.LABEL_OPS[word] if isinstance(word, str) else int(word)
+    if const is None:
+        const = int(capi.lib().mgc_label_default_constant(code))
+    return code, int(const) & 0xFFFFFFFFFFFFFFFF
+
+
+def build_tree_labelled(tree):
+    """build_tree for mgc_db_eval_labelled: the same trees, and the options dict of a node also takes "label": a word of
+    capi.LABEL_OPS ("or"), or (word, constant) (("and", 0x0F)); without it the node's label operation is the default of its
+    operation.  -> (EvalNodeLabelled array, children array, number of children, root index)"""
+    labels = []
+
+    def strip(t):
+        if isinstance(t, (str, bytes)):
+            labels.append(None)
+            return t
+        t = tuple(t)
+        opts = {}
+        if t and isinstance(t[-1], dict):
+            opts = dict(t[-1])
+            t = t[:-1]
+        label = opts.pop("label", None)
+        head = 2 if t and t[0] in VALUE_WORDS else 1
+        kids = tuple(strip(a) for a in t[head:])               # children first: the order build_tree numbers the nodes in
+        labels.append(label)
+        return t[:head] + kids + ((opts,) if opts else ())
+
+    plain, kids, n_kids, root = build_tree(strip(tree))
+    assert len(labels) == len(plain)
+    arr = (capi.EvalNodeLabelled * len(plain))()
+    for e, b, label in zip(arr, plain, labels):
+        e.kind, e.op, e.constant, e.path, e.first_child, e.n_children = b.kind, b.op, b.constant, b.path, b.first_child, b.n_children
+        e.label_op, e.label_constant = _label_option(label) if b.kind != capi.NODE_DATABASE else (0, 0)
+    return arr, kids, n_kids, root
+
+
+def evaluate_labelled(tree, on_slice=None, label_size=0, device=-1, host_threads=8):
+    """evaluate() over databases that may store labels (mgc_db_eval_labelled): every node combines the labels of the inputs
+    that hold a k-mer with its "label" option (build_tree_labelled), outputs store label_size bits per k-mer (0: the largest
+    label size among the leaves), and on_slice(file, lo, hi_or_None, values, labels) also receives the root's labels as
+    full 64-bit values."""
+    arr, kids, n_kids, root = build_tree_labelled(tree)
+    failure = []
+
+    def trampoline(ctx, ff, lo, hi, vals, labs, n):
+        try:
+            def take(p, dtype):
+                return np.ctypeslib.as_array(p, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype=dtype)
+            on_slice(ff, take(lo, np.uint64), take(hi, np.uint64) if hi else None, take(vals, np.uint32), take(labs, np.uint64))
+        except BaseException as e:                               # not through the C frames
+            failure.append(e)
+
+    cb = capi.EVAL_SLICE_LABELLED_CB(trampoline) if on_slice is not None else ctypes.cast(None, capi.EVAL_SLICE_LABELLED_CB)
+    rc = capi.lib().mgc_db_eval_labelled(arr, len(arr), kids, n_kids, root, int(label_size), cb, None, device, host_threads)
+    if failure:
+        raise failure[0]
+    if rc != 0:
+        msg = capi.lib().mgc_db_stream_error(None)
+        raise capi.MgcError(rc, "mgc_db_eval_labelled", msg.decode("utf-8", "replace") if msg else "")

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Register / scratch / LDS use of the kernels whose mangled name contains PATTERN (developer tool).
-Usage: python scripts/kres.py PATTERN"""
+Usage: python scripts/kres.py PATTERN [FILE.hip ...]   (only the named sources of meryl_amd/csrc when given)"""
 import re, subprocess, sys, os
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = ""
-for name in ("mgc_kmer.hip", "mgc_sort.hip", "mgc_scan.hip", "mgc_finish.hip", "mgc_misc.hip", "mgc_parse.hip", "mgc_merge.hip", "mgc_merge_many.hip"):
+names = ("mgc_kmer.hip", "mgc_sort.hip", "mgc_scan.hip", "mgc_finish.hip", "mgc_misc.hip", "mgc_parse.hip", "mgc_merge.hip", "mgc_merge_many.hip", "mgc_decode.hip", "mgc_encode.hip")
+for name in (sys.argv[2:] or names):
     src = os.path.join(root, "meryl_amd", "csrc", name)
     out += subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "-Rpass-analysis=kernel-resource-usage",
                            "-o", "/tmp/kres.o", src], capture_output=True, text=True).stderr
@@ -17,6 +18,6 @@ for line in out.splitlines():
         cur = m.group(1)
         continue
     if cur and sys.argv[1] in cur:
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
+        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
         if m:
             print(cur[:70], m.group(1), m.group(2))

@@ -12,8 +12,13 @@
     staged with three intermediate databases (`--staged-meryl PATH`: the front end of another build, e.g. the parent
     commit's; default: this build's), wall clock per command, median of 3 after a warm-up.  `start`: a filter of a database
     of a handful of k-mers -- what a process pays before it touches data.
+  * labels (leg c): merge_many with labels (mgc_dev_merge_many_count + mgc_dev_merge_many_emit_labelled, label=or, every input
+    labelled) beside the unlabelled pair over the same keys and values, union-sum over the `shared50` mix, N = 2, 8 and 32,
+    8- and 16-byte keys.  `expected_ratio` is the ratio of the bytes the two move: per input element the count pass reads the
+    key and the emit pass the key and the value (4 B), per kept k-mer the emit writes key and value; labels add 8 B per element
+    read and 8 B per kept k-mer written.
 
-usage: python scripts/setops_bench.py [KEYS_M] [READS_M] [--dir DIR] [--legs a,b] [--staged-meryl PATH] >> profiles/setops_bench.jsonl"""
+usage: python scripts/setops_bench.py [KEYS_M] [READS_M] [--dir DIR] [--legs a,b,c] [--staged-meryl PATH] >> profiles/setops_bench.jsonl"""
 import json
 import os
 import shutil
@@ -139,6 +144,40 @@ def kernel_leg():
             torch.cuda.empty_cache()
 
 
+def labels_leg():
+    n = int(keys_m * 1_000_000)
+    g = torch.Generator(device=dev)
+    g.manual_seed(20261019)
+    for kw in (1, 2):
+        for n_inputs in (2, 8, 32):
+            ks, vs = make_inputs(n_inputs, n, "shared50", g)
+            if kw == 2:                                              # 16-byte keys (lo, hi): the same order with hi = 0
+                ks = [torch.stack([k, torch.zeros_like(k)], dim=1).contiguous() for k in ks]
+            ls = [torch.randint(0, 1 << 62, (k.shape[0],), generator=g, device=dev, dtype=torch.int64) for k in ks]
+            total = sum(int(k.shape[0]) for k in ks)
+            out = {}
+
+            def plain():
+                out["plain"] = count.dev_merge_many(ks, vs, "union-sum")
+
+            def labelled():
+                out["lab"] = count.dev_merge_many_labelled(ks, vs, ls, "union-sum", "or")
+            plain_ms, plain_samples = timed(plain)
+            lab_ms, lab_samples = timed(labelled)
+            same = torch.equal(out["plain"][0], out["lab"][0]) and torch.equal(out["plain"][1], out["lab"][1])
+            n_out = int(out["plain"][0].shape[0])
+            out.clear()
+            kb = 8 * kw
+            plain_bytes = total * kb + total * (kb + 4) + n_out * (kb + 4)
+            lab_bytes = plain_bytes + 8 * total + 8 * n_out
+            emit(what="labels", n_inputs=n_inputs, key_bytes=kb, mix="shared50", op="union-sum", label_op="or", keys_per_input=n, total=total,
+                 n_out=n_out, equal=bool(same), merge_many_ms=round(plain_ms, 3), labelled_ms=round(lab_ms, 3),
+                 labelled_over_plain=round(lab_ms / plain_ms, 3), expected_ratio=round(lab_bytes / plain_bytes, 3),
+                 samples_plain_ms=plain_samples, samples_labelled_ms=lab_samples)
+            del ks, vs, ls
+            torch.cuda.empty_cache()
+
+
 def wall(cmd, env=None):
     t0 = time.perf_counter()
     subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, env=env)
@@ -214,5 +253,7 @@ if "a" in legs:
     kernel_leg()
 if "b" in legs:
     cli_leg()
+if "c" in legs:
+    labels_leg()
 if own_dir:
     shutil.rmtree(work, ignore_errors=True)
