@@ -295,6 +295,33 @@ typedef void (*mgc_eval_slice_labelled_cb)(void *ctx, uint32_t file, const uint6
 int mgc_db_eval_labelled(const mgc_eval_node_labelled *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
                          uint32_t root, uint32_t label_size, mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads);
 
+/* The same with SELECTORS (meryl2; include/meryl_gpu_count.h: mgc_select_term, mgc_select_parse): a node may also name a program,
+ * terms[first_term .. first_term + n_terms) of one terms array, that is ANDed onto the node's own rule for what is written.
+ * A node with a program always goes through mgc_dev_merge_many_*_selected (a merge of one input included) or
+ * mgc_dev_select_*_selected; a node without one takes exactly the route it takes today -- mgc_db_eval's when labels do not
+ * travel (the left fold and MGC_MERGE_MANY=0 included), mgc_db_eval_labelled's when they do.  Labels travel when with_labels
+ * or label_size is non-zero, or when any node's program holds a LABEL term; otherwise leaves that store labels are refused
+ * as mgc_db_eval refuses them and `cb` receives zeros for labels.  With labels travelling and no program anywhere the outputs
+ * are mgc_db_eval_labelled's, byte for byte.
+ * Checked with everything the other two entry points check, before any device call and before any output directory exists
+ * (MGC_EINVAL with text): a program on a database node; a range outside terms[]; more than MGC_SELECT_MAX_TERMS terms; a
+ * merge node with a program and more than MGC_MERGE_MANY_MAX inputs; and per term what mgc_select_check refuses for the
+ * node's input count -- an index above it, a count above it, both sides the same source, a BASES term that names an input. */
+typedef struct mgc_eval_node_selected {
+  int32_t     kind;                /* MGC_NODE_* */
+  int32_t     op;                  /* MGC_MERGE_* / MGC_VALUE_* (ignored for a leaf) */
+  uint64_t    constant;            /* value operations */
+  const char *path;                /* leaf: the database; inner node: its output, or NULL */
+  uint32_t    first_child, n_children;   /* range of children[] */
+  int32_t     label_op;            /* MGC_LABEL_* (ignored for a leaf) */
+  int32_t     reserved;
+  uint64_t    label_constant;
+  uint32_t    first_term, n_terms; /* range of terms[]; n_terms = 0: no selector */
+} mgc_eval_node_selected;
+int mgc_db_eval_selected(const mgc_eval_node_selected *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
+                         uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
+                         mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads);
+
 /* ONE count spread over the GPUs of a node, from one process (meryl_amd/csrc/mgc_node.cpp): rank r's reads are the
  * n_bases[r] bytes at d_bases[r] on device devices[r] (the base stream mgc_push_bases takes; with cfg->homopoly_compress
  * every rank's stream must hold whole sequences).  Every rank extracts the k-mers of its reads, the k-mers travel over

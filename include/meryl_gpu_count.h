@@ -297,6 +297,94 @@ int mgc_dev_select_emit_labelled(const void *d_keys, const uint32_t *d_values, c
                                  uint32_t key_words, int value_op, uint64_t constant, int label_op, uint64_t label_constant,
                                  void *d_workspace, size_t workspace_bytes, void *d_keys_out, uint32_t *d_values_out,
                                  uint64_t *d_labels_out, void *stream);
+/* ---- selectors (meryl2) -------------------------------------------------------------------------------------------------
+ * After an operation has assigned the value and the label of a k-mer, a SELECTOR decides whether it is written: a sum of
+ * products of tests (src/meryl2/merylSelector.{H,C}, merylCommandBuilder-isSelect.C, merylOp-nextMer.C:58-192).  A program
+ * is an array of at most MGC_SELECT_MAX_TERMS terms; a term with ends_product set closes its product (the word `or`
+ * followed it); the k-mer is kept when every term of some product holds; an empty program keeps everything.  A selector
+ * only removes k-mers: the operation's own rule (in all inputs, value not zero, ...) still applies.
+ * A side of a VALUE or LABEL term: index -1 = the constant, 0 = the output k-mer (after the operation's value and label
+ * rules), n = input n (1-based, command-line order).  merylSelector::isTrue (merylSelector.C:72-156):
+ *   VALUE  32-bit compare (a constant is cut to 32 bits).  A referenced input that does not hold the k-mer makes the term
+ *          FALSE, also under `not` (the reference returns before it applies _t, :89,:95).
+ *   LABEL  the same over 64-bit labels (:101-118).
+ *   BASES  the number of the letters of base_mask in the k-mer (MGC_SEL_BASE_*; merylSelector.H:123-145 -- the letter is
+ *          XORed to A, the two bits of a base are squashed and the set bits counted, over the 2k bits that hold bases) against
+ *          a constant: one side has index 0, the other -1.
+ *   INPUT  bit (number of inputs holding the k-mer) of count_mask is set AND every input of required_mask (bit i = input
+ *          i + 1) holds it (:141-150).
+ * negate (`not`) inverts BASES and INPUT terms, and VALUE / LABEL terms except in the absent-input case. */
+#define MGC_SELECT_MAX_TERMS 16
+#define MGC_SEL_VALUE 1
+#define MGC_SEL_LABEL 2
+#define MGC_SEL_BASES 3
+#define MGC_SEL_INPUT 4
+#define MGC_REL_EQ  1            /* merylSelectorRelation, merylSelector.H */
+#define MGC_REL_NEQ 2
+#define MGC_REL_LEQ 3
+#define MGC_REL_GEQ 4
+#define MGC_REL_LT  5
+#define MGC_REL_GT  6
+#define MGC_SEL_BASE_A 1u        /* base_mask: bit = the 2-bit code of the letter (A 0, C 1, T 2, G 3) */
+#define MGC_SEL_BASE_C 2u
+#define MGC_SEL_BASE_T 4u
+#define MGC_SEL_BASE_G 8u
+typedef struct mgc_select_term {
+  uint8_t  quantity;             /* MGC_SEL_* */
+  uint8_t  relation;             /* MGC_REL_* (unused by INPUT) */
+  uint8_t  negate;
+  uint8_t  ends_product;
+  uint8_t  base_mask;            /* BASES */
+  uint8_t  reserved[3];
+  int32_t  lhs_index, rhs_index; /* -1 constant, 0 output k-mer, n input n */
+  uint64_t lhs_constant, rhs_constant;
+  uint64_t count_mask;           /* INPUT: bit c = "held by exactly c inputs" passes (c = 0..32) */
+  uint32_t required_mask;        /* INPUT: inputs that must hold the k-mer */
+  uint32_t reserved2;
+} mgc_select_term;               /* 48 bytes */
+/* THE parser of selector words (the CLI and Python both call it): words[0..n_words) are the words that follow a set or
+ * value operation of n_inputs inputs --
+ *   value:[lhs]REL rhs   label:[lhs]REL rhs     REL: == = eq != <> ne <= le >= ge < lt > gt; a side: @n, #c or an integer
+ *                                               (decimal, 0x.., 0b..); a missing lhs is the output k-mer (decodeSelector)
+ *   bases:<letters of acgt>:REL n
+ *   input:w[:w...]       separator : or , ; w: n  n-m  all  any  n-all  first  @n  @a-@b
+ *   not   and (ignored)   or
+ * `n-all` means "in at least n inputs", as the reference documents it (merylSelector.H:236, isSelect.C:377); its code
+ * (merylSelector.C:243-246) marks inputs n..N as required instead.  distinct= / word-frequency= / threshold= inside a selector
+ * are refused.  Writes at most cap terms and their number; MGC_EINVAL with text in mgc_last_error(NULL) for a word it cannot
+ * decode and for everything mgc_select_check refuses. */
+int mgc_select_parse(const char *const *words, uint32_t n_words, uint32_t n_inputs, mgc_select_term *terms, uint32_t cap,
+                     uint32_t *n_terms);
+/* What every entry point that takes a program checks before any launch (MGC_EINVAL, text in mgc_last_error(NULL)): more than
+ * MGC_SELECT_MAX_TERMS terms; an unknown quantity or relation; an index below -1 or above n_inputs; both sides of a term the
+ * same source; a BASES term that names an input, without letters, or without exactly one k-mer side; an INPUT term that
+ * allows a count above n_inputs or requires an input above it. */
+int mgc_select_check(const mgc_select_term *terms, uint32_t n_terms, uint32_t n_inputs);
+/* The two steps of mgc_dev_merge_many_* with a program ANDed onto the operation's rule.  n_inputs = 1 is accepted.  k: the
+ * k-mer size (BASES terms; 1..32 for key_words 1, 1..64 for 2).  d_labels (HOST array of device pointers, entries or the
+ * array itself may be NULL = all zeros) and label_op / label_constant (MGC_LABEL_*) feed LABEL terms and d_labels_out (NULL:
+ * no labels written).  The count step reads the values when a VALUE or LABEL term or the operation needs them and the labels
+ * when a LABEL term is present, and decides exactly what the emit step writes. */
+int mgc_dev_merge_many_count_selected(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *const *d_labels,
+                                      const uint64_t *n, uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int label_op,
+                                      uint64_t label_constant, const mgc_select_term *terms, uint32_t n_terms, void *d_workspace,
+                                      size_t workspace_bytes, uint64_t *n_out, void *stream);
+int mgc_dev_merge_many_emit_selected(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *const *d_labels,
+                                     const uint64_t *n, uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int label_op,
+                                     uint64_t label_constant, const mgc_select_term *terms, uint32_t n_terms, void *d_workspace,
+                                     size_t workspace_bytes, void *d_keys_out, uint32_t *d_values_out, uint64_t *d_labels_out,
+                                     void *stream);
+/* The same for the value operations: "output value" is the value after the operation, @1 the input's value, and INPUT terms
+ * see one active input. */
+int mgc_dev_select_count_selected(const void *d_keys, const uint32_t *d_values, const uint64_t *d_labels, uint64_t n, uint32_t key_words,
+                                  uint32_t k, int value_op, uint64_t constant, int label_op, uint64_t label_constant,
+                                  const mgc_select_term *terms, uint32_t n_terms, void *d_workspace, size_t workspace_bytes,
+                                  uint64_t *n_out, void *stream);
+int mgc_dev_select_emit_selected(const void *d_keys, const uint32_t *d_values, const uint64_t *d_labels, uint64_t n, uint32_t key_words,
+                                 uint32_t k, int value_op, uint64_t constant, int label_op, uint64_t label_constant,
+                                 const mgc_select_term *terms, uint32_t n_terms, void *d_workspace, size_t workspace_bytes,
+                                 void *d_keys_out, uint32_t *d_values_out, uint64_t *d_labels_out, void *stream);
+
 /* Database blocks decoded on the device (mgc_decode.hip): d_file = the bytes of one data file followed by 16 bytes of slack,
  * d_blocks = the mdb_raw_block array of include/meryl_db.h (mdb_reader_raw_file gives both, validated against the file
  * size), suffix_size / label_size as the database's mdb_info has them.  d_keys / d_values / d_labels receive the k-mers of

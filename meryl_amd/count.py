@@ -312,6 +312,79 @@ def dev_select_labelled(keys, counts, labels, value_op, constant, label_op="defa
     return out_k, out_c, out_l
 
 
+def _select_terms(terms):
+    """a list of capi.SelectTerm (meryl_amd.db.parse_selector makes them) -> (array, count)"""
+    terms = list(terms or [])
+    return (capi.SelectTerm * max(len(terms), 1))(*terms), len(terms)
+
+
+def dev_merge_many_selected(keys_list, counts_list, labels_list, k, op="union-sum", terms=None, label_op="default", label_constant=None,
+                            with_labels=True, count_only=False):
+    """dev_merge_many_labelled with a selector program ANDed onto the operation's rule (mgc_dev_merge_many_*_selected): terms is
+    a list of capi.SelectTerm, k the k-mer size (bases: terms).  labels_list may be None (all inputs without labels);
+    with_labels False: no labels are written.  One input is accepted.  -> (keys, values, labels or None, the count pass's total);
+    count_only: the count pass alone -> its total"""
+    L = capi.lib()
+    m = len(keys_list)
+    kw = 2 if keys_list[0].dim() == 2 else 1
+    dev = keys_list[0].device
+    labels_list = labels_list if labels_list is not None else [None] * m
+    kp = (ctypes.c_void_p * m)(*[_ptr(x) if x.shape[0] else None for x in keys_list])
+    cp = (ctypes.c_void_p * m)(*[_ptr(c) if c.shape[0] else None for c in counts_list])
+    lp = (ctypes.c_void_p * m)(*[_ptr(l) if l is not None and l.shape[0] else None for l in labels_list])
+    ns = (ctypes.c_uint64 * m)(*[int(x.shape[0]) for x in keys_list])
+    code = op if isinstance(op, int) else MERGE_MANY_OPS[op]
+    lcode = _label_code(label_op)
+    lc = int(L.mgc_label_default_constant(lcode)) if label_constant is None else int(label_constant) & 0xFFFFFFFFFFFFFFFF
+    tarr, nt = _select_terms(terms)
+    ws_bytes = max(int(L.mgc_dev_merge_many_workspace_bytes(ns, m, kw)), 256)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    n = ctypes.c_uint64(0)
+    capi.check(L.mgc_dev_merge_many_count_selected(kp, cp, lp, ns, m, kw, int(k), code, lcode, lc, tarr, nt, _ptr(ws), ws_bytes, ctypes.byref(n),
+                                                   _stream_ptr()), "mgc_dev_merge_many_count_selected")
+    if count_only:
+        return n.value
+    out_k = _u64(n.value * kw, dev)
+    if kw == 2:
+        out_k = out_k.view(n.value, 2)
+    out_c = torch.empty(n.value, dtype=torch.int32, device=dev)
+    out_l = _u64(n.value, dev) if with_labels else None
+    capi.check(L.mgc_dev_merge_many_emit_selected(kp, cp, lp, ns, m, kw, int(k), code, lcode, lc, tarr, nt, _ptr(ws), ws_bytes, _ptr(out_k),
+                                                  _ptr(out_c), _ptr(out_l) if with_labels else None, _stream_ptr()),
+               "mgc_dev_merge_many_emit_selected")
+    return out_k, out_c, out_l, n.value
+
+
+def dev_select_selected(keys, counts, labels, k, value_op, constant, terms=None, label_op="default", label_constant=None, with_labels=True,
+                        count_only=False):
+    """dev_select_labelled with a selector program (mgc_dev_select_*_selected): "output value" is the value after value_op, @1 the
+    input's value.  -> (keys, values, labels or None, the count pass's total); count_only: the count pass alone -> its total"""
+    L = capi.lib()
+    kw = 2 if keys.dim() == 2 else 1
+    n_in = keys.shape[0]
+    dev = keys.device
+    lcode = _label_code(label_op)
+    lc = int(L.mgc_label_default_constant(lcode)) if label_constant is None else int(label_constant) & 0xFFFFFFFFFFFFFFFF
+    tarr, nt = _select_terms(terms)
+    lptr = _ptr(labels) if labels is not None and n_in else None
+    ws_bytes = max(int(L.mgc_dev_select_workspace_bytes(n_in)), 256)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    n = ctypes.c_uint64(0)
+    capi.check(L.mgc_dev_select_count_selected(_ptr(keys), _ptr(counts), lptr, n_in, kw, int(k), value_op, int(constant), lcode, lc, tarr, nt,
+                                               _ptr(ws), ws_bytes, ctypes.byref(n), _stream_ptr()), "mgc_dev_select_count_selected")
+    if count_only:
+        return n.value
+    out_k = _u64(n.value * kw, dev)
+    if kw == 2:
+        out_k = out_k.view(n.value, 2)
+    out_c = torch.empty(n.value, dtype=torch.int32, device=dev)
+    out_l = _u64(n.value, dev) if with_labels else None
+    capi.check(L.mgc_dev_select_emit_selected(_ptr(keys), _ptr(counts), lptr, n_in, kw, int(k), value_op, int(constant), lcode, lc, tarr, nt,
+                                              _ptr(ws), ws_bytes, _ptr(out_k), _ptr(out_c), _ptr(out_l) if with_labels else None, _stream_ptr()),
+               "mgc_dev_select_emit_selected")
+    return out_k, out_c, out_l, n.value
+
+
 def dev_decode_file(reader, ff, device=None):
     """Data file ff of a meryl_amd.db.Reader decoded on the device (mgc_dev_decode_blocks): the file's bytes are uploaded as
     they are.  -> (keys int64[n] / int64[n, 2], values int32[n], labels int64[n]) cuda tensors; labels are zeros when the

@@ -16,7 +16,11 @@
 // `label=<word>#<const>` or `label=#<const>` after a set or value operation names how the label of a written k-mer comes from
 // its inputs' labels (merylCommandBuilder-isAssign.C:124-156, merylOpCompute.C:286-395); a tree is evaluated with labels
 // (mgc_db_eval_labelled) when `-l` was given, one of its operations carries such a word or one of its leaves stores labels,
-// and as before otherwise.  What stays refused: statistics, compare, ploidy, Canu sequence stores (segment=); CRAM only when no `samtools` is on the PATH.
+// and as before otherwise.  Selectors (meryl2): `value:`, `label:`, `bases:` and `input:` words with `not`, `and`, `or` after a set
+// or value operation (merylCommandBuilder-isSelect.C, merylSelector.C:72-156) are decoded by the library's parser
+// (mgc_select_parse) once the operation's inputs are known, and a tree that holds any is evaluated through
+// mgc_db_eval_selected; distinct= / word-frequency= / threshold= inside a selector stay on the value operations.
+// What stays refused: statistics, compare, ploidy, Canu sequence stores (segment=); CRAM only when no `samtools` is on the PATH.
 #include "../../include/meryl_db.h"
 #include "../../include/meryl_gpu_count.h"
 #include "../../include/meryl_seq.h"
@@ -89,6 +93,7 @@ struct Operation {
   bool                     has_label_op = false;   // label=<word>[#<const>] on a set or value operation (:124-156)
   int                      label_op = MGC_LABEL_DEFAULT;
   uint64_t                 label_constant = 0;
+  std::vector<std::string> select_words;        // value: label: bases: input: not and or, after a set or value operation (meryl2 selectors)
 };
 
 struct Globals {
@@ -116,8 +121,8 @@ void usage(const char *prog) {
           "       %s print <database.meryl | [operation]>\n"
           "       %s dumpIndex <database.meryl>\n"
           "       %s dumpFile <database.meryl>/0x######\n"
-          "       %s union[-min|-max|-sum]|intersect[-min|-max|-sum]|subtract|difference|symmetric-difference [label=<word>[#<n>]] <db | [operation]> ... [output <db>]\n"
-          "       %s less-than|greater-than|at-least|at-most|equal-to|not-equal-to <N | distinct=<f> | word-frequency=<f>> <db | [operation]> [output <db>]\n"
+          "       %s union[-min|-max|-sum]|intersect[-min|-max|-sum]|subtract|difference|symmetric-difference [label=<word>[#<n>]] [selector ...] <db | [operation]> ... [output <db>]\n"
+          "       %s less-than|greater-than|at-least|at-most|equal-to|not-equal-to <N | distinct=<f> | word-frequency=<f>> [selector ...] <db | [operation]> [output <db>]\n"
           "       %s increase|decrease|multiply|divide|divide-round|modulo <N> <db | [operation]> [output <db>]\n"
           "\n"
           "  MI355X-native implementation of the `count` path of marbl/meryl.  Words are processed left to\n"
@@ -128,6 +133,10 @@ void usage(const char *prog) {
           "  word-frequency= need a database, or an input operation that writes one).  label=<word> on a set or value\n"
           "  operation (first selected min max and or xor difference lightest heaviest invert, with #<n> a constant;\n"
           "  label=#<n> sets it) combines the labels of its inputs; a count inside such a tree may omit 'output'.\n"
+          "  A selector after a set or value operation keeps, of what the operation would write, the k-mers for which a\n"
+          "  sum of products of tests holds: value:[lhs]REL<rhs>, label:[lhs]REL<rhs> (a side: @<input>, #<n> or <n>; no lhs:\n"
+          "  the output k-mer; REL: == eq != <> ne <= le >= ge < lt > gt), bases:<acgt>:REL<n>, input:<n|n-m|n-all|all|any|\n"
+          "  first|@n|@a-@b>[:...], joined by 'and' (optional), 'or' and 'not' -- e.g. union input:3-all a b c d.\n"
           "  Other meryl operations are\n"
           "  not part of this build.\n",
           prog, prog, prog, prog, prog, prog, prog);
@@ -636,6 +645,8 @@ struct EvalTree {
   std::vector<std::vector<uint32_t>>  kids;
   std::string                         first_leaf;
   bool                                label_words = false;    // an operation of the tree carries label=
+  std::vector<mgc_select_term>        terms;                  // the selector programs of all nodes, one after the other
+  std::vector<std::pair<uint32_t, uint32_t>> term_range;      // per node: first term, number of terms
   uint32_t                            leaf_label_size = 0;    // the largest label size among the leaves
 };
 
@@ -710,6 +721,7 @@ uint32_t add_tree_node(const Globals &g, const std::vector<Operation> &ops, int 
     nd.kind = MGC_NODE_DATABASE;
     nd.path = in.child >= 0 ? ops[in.child].output.c_str() : in.path.c_str();
     t.nodes.push_back(nd);
+    t.term_range.emplace_back(0u, 0u);
     t.kids.emplace_back();
     kids.push_back((uint32_t)t.nodes.size() - 1);
   }
@@ -734,7 +746,18 @@ uint32_t add_tree_node(const Globals &g, const std::vector<Operation> &ops, int 
       fprintf(stderr, "\nPROCESSING %s %" PRIu64 "%s%s%s.\n", op.word.c_str(), (uint64_t)nd.constant,
               op.output.empty() ? "" : " into '", op.output.c_str(), op.output.empty() ? "" : "'");
   }
+  // the selector words are decoded once the number of inputs is known (`input:all`, `@n`), by the library's one parser
+  std::pair<uint32_t, uint32_t> range((uint32_t)t.terms.size(), 0u);
+  if (!op.select_words.empty()) {
+    std::vector<const char *> words;
+    for (const std::string &w : op.select_words) words.push_back(w.c_str());
+    mgc_select_term terms[MGC_SELECT_MAX_TERMS];
+    if (mgc_select_parse(words.data(), (uint32_t)words.size(), (uint32_t)kids.size(), terms, MGC_SELECT_MAX_TERMS, &range.second) != MGC_OK)
+      die("ERROR: %s", ("operation '" + op.word + "': " + mgc_last_error(nullptr)).c_str());
+    t.terms.insert(t.terms.end(), terms, terms + range.second);
+  }
   t.nodes.push_back(nd);
+  t.term_range.push_back(range);
   t.kids.push_back(kids);
   return (uint32_t)t.nodes.size() - 1;
 }
@@ -769,7 +792,24 @@ int run_tree(const Globals &g, const std::vector<Operation> &ops, int root, bool
   }
   // with labels only when something asks for them: -l, a label= word, or a leaf that stores labels; the outputs (and the
   // label column `print` adds) take -l bits, or the largest label size among the leaves
-  if (g.label_size_given || t.label_words || t.leaf_label_size) {
+  const bool with_labels = g.label_size_given || t.label_words || t.leaf_label_size;
+  if (!t.terms.empty()) {                                      // a selector somewhere: the same tree through mgc_db_eval_selected
+    std::vector<mgc_eval_node_selected> sel(t.nodes.size());
+    for (size_t v = 0; v < t.nodes.size(); v++) {
+      memset(&sel[v], 0, sizeof(sel[v]));
+      sel[v].kind = t.nodes[v].kind; sel[v].op = t.nodes[v].op; sel[v].constant = t.nodes[v].constant; sel[v].path = t.nodes[v].path;
+      sel[v].first_child = t.nodes[v].first_child; sel[v].n_children = t.nodes[v].n_children;
+      sel[v].label_op = t.nodes[v].label_op; sel[v].label_constant = t.nodes[v].label_constant;
+      sel[v].first_term = t.term_range[v].first; sel[v].n_terms = t.term_range[v].second;
+    }
+    if (with_labels) pc.label_size = g.label_size_given && g.label_size ? g.label_size : t.leaf_label_size;
+    if (mgc_db_eval_selected(sel.data(), (uint32_t)sel.size(), children.data(), (uint32_t)children.size(), r, t.terms.data(), (uint32_t)t.terms.size(),
+                             with_labels ? 1 : 0, g.label_size_given ? g.label_size : 0, print ? print_slice_labelled : nullptr, &pc, -1,
+                             (int)g.threads) != MGC_OK)
+      die("ERROR: %s", mgc_db_stream_error(nullptr));
+    return 0;
+  }
+  if (with_labels) {
     pc.label_size = g.label_size_given && g.label_size ? g.label_size : t.leaf_label_size;
     if (mgc_db_eval_labelled(t.nodes.data(), (uint32_t)t.nodes.size(), children.data(), (uint32_t)children.size(), r,
                              g.label_size_given ? g.label_size : 0, print ? print_slice_labelled : nullptr, &pc, -1, (int)g.threads) != MGC_OK)
@@ -848,6 +888,15 @@ int main(int argc, char **argv) {
         if (!ops[top()].output.empty()) die("ERROR: operation already has an output ('%s').", ops[top()].output.c_str());   // merylOp.C:256-257
         ops[top()].output = w;
         expect_output_name = false;
+      }
+      // meryl2 selectors: value: label: bases: input: and the connectives, after a set or value operation (isSelect.C)
+      else if (w.compare(0, 6, "value:") == 0 || w.compare(0, 6, "label:") == 0 || w.compare(0, 6, "bases:") == 0 || w.compare(0, 6, "input:") == 0) {
+        if (top() < 0 || !is_tree_op(ops[top()])) die("ERROR: selector '%s' needs a set or value operation before it.", w.c_str());
+        if (!ops[top()].inputs.empty()) die("ERROR: selector '%s' must come before the inputs of its operation.", w.c_str());
+        ops[top()].select_words.push_back(w);
+      }
+      else if ((w == "not" || w == "and" || w == "or") && top() >= 0 && is_tree_op(ops[top()]) && ops[top()].inputs.empty()) {
+        ops[top()].select_words.push_back(w);
       }
       // a bare number is the threshold / constant of the value operation on top ("greater-than 45", "divide 2"; :216-233)
       // (the reference takes an all-digits word as the number whenever the operation wants one, before it is ever looked at

@@ -9,6 +9,7 @@
 #include "mgc_device.h"
 #include "mgc_session.hpp"
 #include "mgc_runs.hpp"
+#include "mgc_selector.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -383,6 +384,89 @@ extern "C" int mgc_dev_select_emit_labelled(const void *d_keys, const uint32_t *
   if (lop < 0) { set_err(nullptr, "mgc_dev_select_emit_labelled: unknown label operation %d", label_op); return MGC_EINVAL; }
   return hip_rc(mgc::launch_select_emit_labelled(d_keys, d_values, d_labels, n, key_words, value_op, constant, lop, label_constant, d_ws,
                                                  d_keys_out, d_values_out, d_labels_out, (hipStream_t)stream), "select_emit_labelled");
+}
+
+// ---- selectors (include/meryl_gpu_count.h: mgc_select_term; the evaluator, the checks and the parser are mgc_selector.hpp) ------
+extern "C" int mgc_select_parse(const char *const *words, uint32_t n_words, uint32_t n_inputs, mgc_select_term *terms, uint32_t cap,
+                                uint32_t *n_terms) {
+  if ((n_words && !words) || !n_terms || (cap && !terms) || n_inputs == 0) { set_err(nullptr, "mgc_select_parse: bad arguments"); return MGC_EINVAL; }
+  const std::string m = mgc::select_parse(words, n_words, n_inputs, terms, cap, n_terms);
+  if (!m.empty()) { set_err(nullptr, "%s", m.c_str()); return MGC_EINVAL; }
+  return MGC_OK;
+}
+
+extern "C" int mgc_select_check(const mgc_select_term *terms, uint32_t n_terms, uint32_t n_inputs) {
+  const std::string m = mgc::select_check(terms, n_terms, n_inputs);
+  if (!m.empty()) { set_err(nullptr, "selector: %s", m.c_str()); return MGC_EINVAL; }
+  return MGC_OK;
+}
+
+// the arguments every *_selected entry point shares, checked before any launch; *lop: the kernel's label code
+static int selected_args(const char *who, bool is_merge, int op, uint32_t n_inputs, uint32_t key_words, uint32_t k, int label_op,
+                         const mgc_select_term *terms, uint32_t n_terms, int *lop) {
+  if (k < 1 || k > 32 * key_words) { set_err(nullptr, "%s: k = %u does not fit %u key word(s)", who, k, key_words); return MGC_EINVAL; }
+  *lop = mgc::label_kernel_op(is_merge, op, label_op);
+  if (*lop < 0) { set_err(nullptr, "%s: unknown label operation %d", who, label_op); return MGC_EINVAL; }
+  if (*lop == MGC_LABEL_INVERT && n_inputs > 1) { set_err(nullptr, "%s: label=invert takes one input (merylOpCompute.C:368-371)", who); return MGC_EINVAL; }
+  const std::string m = mgc::select_check(terms, n_terms, n_inputs);
+  if (!m.empty()) { set_err(nullptr, "%s: selector: %s", who, m.c_str()); return MGC_EINVAL; }
+  return MGC_OK;
+}
+
+extern "C" int mgc_dev_merge_many_count_selected(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *const *d_labels,
+                                                 const uint64_t *n, uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int label_op,
+                                                 uint64_t label_constant, const mgc_select_term *terms, uint32_t n_terms, void *d_ws,
+                                                 size_t ws_bytes, uint64_t *n_out, void *stream) {
+  if (!n_out || !d_ws || !merge_many_args_ok(d_keys, d_values, n, n_inputs, key_words, op, 1) ||
+      ws_bytes < mgc::merge_many_workspace_bytes(n, n_inputs, key_words)) return MGC_EINVAL;
+  int lop = 0;
+  const int rc = selected_args("mgc_dev_merge_many_count_selected", true, op, n_inputs, key_words, k, label_op, terms, n_terms, &lop);
+  if (rc != MGC_OK) return rc;
+  hipError_t e = mgc::launch_merge_many_count_selected(d_keys, d_values, d_labels, n, n_inputs, key_words, k, op, lop, label_constant, terms, n_terms,
+                                                       d_ws, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_rc(e, "merge_many_count_selected");
+  return hip_rc(mgc::merge_read_total(d_ws, n_out, (hipStream_t)stream), "merge_many_count_selected sync");
+}
+
+extern "C" int mgc_dev_merge_many_emit_selected(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *const *d_labels,
+                                                const uint64_t *n, uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int label_op,
+                                                uint64_t label_constant, const mgc_select_term *terms, uint32_t n_terms, void *d_ws,
+                                                size_t ws_bytes, void *d_keys_out, uint32_t *d_values_out, uint64_t *d_labels_out, void *stream) {
+  if (!d_ws || !merge_many_args_ok(d_keys, d_values, n, n_inputs, key_words, op, 1) ||
+      ws_bytes < mgc::merge_many_workspace_bytes(n, n_inputs, key_words)) return MGC_EINVAL;
+  int lop = 0;
+  const int rc = selected_args("mgc_dev_merge_many_emit_selected", true, op, n_inputs, key_words, k, label_op, terms, n_terms, &lop);
+  if (rc != MGC_OK) return rc;
+  return hip_rc(mgc::launch_merge_many_emit_selected(d_keys, d_values, d_labels, n, n_inputs, key_words, k, op, lop, label_constant, terms, n_terms,
+                                                     d_ws, d_keys_out, d_values_out, d_labels_out, (hipStream_t)stream), "merge_many_emit_selected");
+}
+
+extern "C" int mgc_dev_select_count_selected(const void *d_keys, const uint32_t *d_values, const uint64_t *d_labels, uint64_t n, uint32_t key_words,
+                                             uint32_t k, int value_op, uint64_t constant, int label_op, uint64_t label_constant,
+                                             const mgc_select_term *terms, uint32_t n_terms, void *d_ws, size_t ws_bytes, uint64_t *n_out,
+                                             void *stream) {
+  if (!n_out || !d_ws || ws_bytes < mgc::select_workspace_bytes(n) || (n && (!d_keys || !d_values)) || (key_words != 1 && key_words != 2) ||
+      value_op < 0 || value_op > MGC_VALUE_MODULO) return MGC_EINVAL;
+  int lop = 0;
+  const int rc = selected_args("mgc_dev_select_count_selected", false, value_op, 1, key_words, k, label_op, terms, n_terms, &lop);
+  if (rc != MGC_OK) return rc;
+  hipError_t e = mgc::launch_select_count_selected(d_keys, d_values, d_labels, n, key_words, k, value_op, constant, lop, label_constant, terms, n_terms,
+                                                   d_ws, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_rc(e, "select_count_selected");
+  return hip_rc(mgc::merge_read_total(d_ws, n_out, (hipStream_t)stream), "select_count_selected sync");
+}
+
+extern "C" int mgc_dev_select_emit_selected(const void *d_keys, const uint32_t *d_values, const uint64_t *d_labels, uint64_t n, uint32_t key_words,
+                                            uint32_t k, int value_op, uint64_t constant, int label_op, uint64_t label_constant,
+                                            const mgc_select_term *terms, uint32_t n_terms, void *d_ws, size_t ws_bytes, void *d_keys_out,
+                                            uint32_t *d_values_out, uint64_t *d_labels_out, void *stream) {
+  if (!d_ws || ws_bytes < mgc::select_workspace_bytes(n) || (n && (!d_keys || !d_values)) || (key_words != 1 && key_words != 2) ||
+      value_op < 0 || value_op > MGC_VALUE_MODULO) return MGC_EINVAL;
+  int lop = 0;
+  const int rc = selected_args("mgc_dev_select_emit_selected", false, value_op, 1, key_words, k, label_op, terms, n_terms, &lop);
+  if (rc != MGC_OK) return rc;
+  return hip_rc(mgc::launch_select_emit_selected(d_keys, d_values, d_labels, n, key_words, k, value_op, constant, lop, label_constant, terms, n_terms,
+                                                 d_ws, d_keys_out, d_values_out, d_labels_out, (hipStream_t)stream), "select_emit_selected");
 }
 
 extern "C" int mgc_dev_decode_blocks(const void *d_file, const void *d_blocks, uint64_t n_blocks, uint32_t suffix_size, uint32_t label_size,

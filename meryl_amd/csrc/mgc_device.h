@@ -7,6 +7,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "mgc_label.hpp"
+#include "../../include/meryl_gpu_count.h"
 
 namespace mgc {
 
@@ -315,6 +316,22 @@ hipError_t launch_select_emit(const void *d_keys, const uint32_t *d_vals, const 
 hipError_t launch_select_emit_labelled(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words, int fop,
                                        uint64_t constant, int lop, uint64_t lc, void *d_ws, void *d_out_keys, uint32_t *d_out_vals,
                                        uint64_t *d_out_labs, hipStream_t st);
+// ---- the merge and the value transform with a selector program (mgc_selector.hpp; include/meryl_gpu_count.h: mgc_select_term) ----
+// terms: checked by the caller (select_check); k: the k-mer size (BASES terms); lop: a kernel code; labs / its entries / d_out_labs may
+// be null.  The count pass decides exactly what the emit pass writes; one input is accepted.
+hipError_t launch_merge_many_count_selected(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
+                                            uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int lop, uint64_t lc,
+                                            const ::mgc_select_term *terms, uint32_t n_terms, void *d_ws, hipStream_t st);
+hipError_t launch_merge_many_emit_selected(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
+                                           uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int lop, uint64_t lc,
+                                           const ::mgc_select_term *terms, uint32_t n_terms, void *d_ws, void *d_out_keys, uint32_t *d_out_vals,
+                                           uint64_t *d_out_labs, hipStream_t st);
+hipError_t launch_select_count_selected(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words, uint32_t k,
+                                        int fop, uint64_t constant, int lop, uint64_t lc, const ::mgc_select_term *terms, uint32_t n_terms,
+                                        void *d_ws, hipStream_t st);
+hipError_t launch_select_emit_selected(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words, uint32_t k,
+                                       int fop, uint64_t constant, int lop, uint64_t lc, const ::mgc_select_term *terms, uint32_t n_terms,
+                                       void *d_ws, void *d_out_keys, uint32_t *d_out_vals, uint64_t *d_out_labs, hipStream_t st);
 hipError_t launch_fill_u32(uint32_t *d, uint64_t n, uint32_t v, hipStream_t st);
 // *d_out <- 1 + index of the last '.' in bases[0, n), 0 if none
 hipError_t launch_last_breaker(const uint8_t *d_bases, uint64_t n, uint64_t *d_out, hipStream_t st);

@@ -15,6 +15,7 @@
 // looks at the next B candidate, the B element at the previous A element; no cross-thread exchange is needed.  Two passes
 // (count heads per tile, scan, emit): HBM-bound, (8|16)+4 B read per input element per pass + the output.
 #include "mgc_common.hpp"
+#include "mgc_selector.hpp"
 
 namespace mgc {
 
@@ -213,19 +214,62 @@ __device__ __forceinline__ u32 sel_value(int fop, u32 v, u64 c, u32 flag) {
 constexpr int SL_BLOCK = 256, SL_ITEMS = 8, SL_TILE = SL_BLOCK * SL_ITEMS;
 // LABELS (emit only): the label of each kept k-mer follows it, through the label operation `lop` (LabelAcc, mgc_label.hpp) over
 // its one active input -- the input's value, not the new one, is what MIN sees (_acta[0]._val, src/meryl2/merylOpCompute.C:309-320)
-template <typename K, bool EMIT, bool LABELS = false>
+// what a selector term sees of one element (Src of mgc_selector.hpp): one active input, whose value is the one before `fop`
+struct SLSelectSrc {
+  u32 presence, out_value, in_value;
+  u64 out_label, in_label, lo, hi;
+  __device__ __forceinline__ u32 value(u32) const { return in_value; }
+  __device__ __forceinline__ u64 label(u32) const { return in_label; }
+};
+__device__ __forceinline__ u64 sl_key_lo(u64 k)  { return k; }
+__device__ __forceinline__ u64 sl_key_hi(u64)    { return 0; }
+__device__ __forceinline__ u64 sl_key_lo(K128 k) { return k.lo; }
+__device__ __forceinline__ u64 sl_key_hi(K128 k) { return k.hi; }
+
+// SELECT: a selector program is ANDed onto "the new value is not zero"; both passes then read what it needs (SELF_*) -- the keys
+// for BASES terms, the labels (LABELS) for LABEL terms -- and decide alike.
+template <typename K, bool EMIT, bool LABELS = false, bool SELECT = false>
 __global__ __launch_bounds__(SL_BLOCK)
-void select_kernel(const K *__restrict__ keys, const u32 *__restrict__ vals, const u32 *__restrict__ flags, u64 n, int fop, u64 c,
-                   u64 *__restrict__ tile_cnt /*EMIT: exclusive bases*/, K *__restrict__ outK, u32 *__restrict__ outC,
-                   const u64 *__restrict__ labs = nullptr /*null: all zeros*/, int lop = 0, u64 lc = 0, u64 *__restrict__ outL = nullptr) {
-  static_assert(EMIT || !LABELS, "labels do not change what is kept");
+void select_kernel(typename SelectWordsArg<SELECT>::type prog, const K *__restrict__ keys, const u32 *__restrict__ vals,
+                   const u32 *__restrict__ flags, u64 n, int fop, u64 c, u64 *__restrict__ tile_cnt /*EMIT: exclusive bases*/,
+                   K *__restrict__ outK, u32 *__restrict__ outC, const u64 *__restrict__ labs = nullptr /*null: all zeros*/, int lop = 0,
+                   u64 lc = 0, u64 *__restrict__ outL = nullptr) {
+  static_assert(EMIT || !LABELS || SELECT, "labels do not change what is kept unless a selector looks at them");
   __shared__ u32 s_tmp[SL_BLOCK / 64 + 1];
+  // the program is read from an LDS image (staged with constant indices: an argument indexed at run time would be copied to
+  // scratch by every lane)
+  constexpr int PW = SELECT ? (int)(sizeof(SelectProgram) / 8) : 1;
+  __shared__ u64 s_prog[PW];
+  const SelectProgram *pg = reinterpret_cast<const SelectProgram *>(s_prog);
+  if constexpr (SELECT) {
+    static_assert(sizeof(SelectProgram) / 8 <= SL_BLOCK, "one word of the program per thread");
+#pragma unroll
+    for (int j = 0; j < PW; j++)
+      if (threadIdx.x == (u32)j) s_prog[j] = prog.w[j];
+    __syncthreads();
+  }
   const u64 base = (u64)blockIdx.x * SL_TILE + (u64)threadIdx.x * SL_ITEMS;
   u32 nv[SL_ITEMS], kept = 0;
 #pragma unroll
   for (int q = 0; q < SL_ITEMS; q++) {
     nv[q] = 0;
     if (base + q < n) nv[q] = sel_value(fop, vals[base + q], c, flags ? flags[base + q] : 0u);
+    if constexpr (SELECT) {
+      if (nv[q]) {
+        SLSelectSrc src;
+        src.presence = 1u; src.out_value = nv[q]; src.in_value = vals[base + q];
+        src.out_label = 0; src.in_label = 0; src.lo = 0; src.hi = 0;
+        if constexpr (LABELS) {
+          LabelAcc la;
+          la.begin(lc);
+          src.in_label = labs ? labs[base + q] : 0ull;
+          la.step(lop, src.in_label, src.in_value);
+          src.out_label = la.l;
+        }
+        if (pg->flags & SELF_KEYS) { const K key = keys[base + q]; src.lo = sl_key_lo(key); src.hi = sl_key_hi(key); }
+        if (!select_keep(pg->t, pg->n, pg->k, src)) nv[q] = 0;
+      }
+    }
     kept += nv[q] ? 1u : 0u;
   }
   u32 tot;
@@ -240,7 +284,7 @@ void select_kernel(const K *__restrict__ keys, const u32 *__restrict__ vals, con
         LabelAcc la;
         la.begin(lc);
         la.step(lop, labs ? labs[base + q] : 0ull, vals[base + q]);
-        outL[o] = la.l;
+        if (!SELECT || outL) outL[o] = la.l;
       }
       o++;
     }
@@ -265,10 +309,10 @@ hipError_t launch_select_count(const void *d_keys, const uint32_t *d_vals, const
   if (t == 0) return hipMemsetAsync(ws, 0, 8, st);
   u64 *tiles = ws + 8, *scratch = tiles + t + 1;
   if (key_words == 2)
-    hipLaunchKernelGGL((select_kernel<K128, false>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, reinterpret_cast<const K128 *>(d_keys), d_vals, d_flags,
+    hipLaunchKernelGGL((select_kernel<K128, false>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, SelectNone{}, reinterpret_cast<const K128 *>(d_keys), d_vals, d_flags,
                        (u64)n, fop, (u64)constant, tiles, (K128 *)nullptr, (u32 *)nullptr);
   else
-    hipLaunchKernelGGL((select_kernel<u64, false>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, reinterpret_cast<const u64 *>(d_keys), d_vals, d_flags,
+    hipLaunchKernelGGL((select_kernel<u64, false>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, SelectNone{}, reinterpret_cast<const u64 *>(d_keys), d_vals, d_flags,
                        (u64)n, fop, (u64)constant, tiles, (u64 *)nullptr, (u32 *)nullptr);
   MGC_CHECK(hipGetLastError());
   return scan_u64_exclusive(tiles, t, scratch, ws, st);
@@ -279,10 +323,10 @@ hipError_t launch_select_emit(const void *d_keys, const uint32_t *d_vals, const 
   if (t == 0) return hipSuccess;
   u64 *tiles = reinterpret_cast<u64 *>(d_ws) + 8;
   if (key_words == 2)
-    hipLaunchKernelGGL((select_kernel<K128, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, reinterpret_cast<const K128 *>(d_keys), d_vals, d_flags,
+    hipLaunchKernelGGL((select_kernel<K128, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, SelectNone{}, reinterpret_cast<const K128 *>(d_keys), d_vals, d_flags,
                        (u64)n, fop, (u64)constant, tiles, reinterpret_cast<K128 *>(d_out_keys), d_out_vals);
   else
-    hipLaunchKernelGGL((select_kernel<u64, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, reinterpret_cast<const u64 *>(d_keys), d_vals, d_flags,
+    hipLaunchKernelGGL((select_kernel<u64, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, SelectNone{}, reinterpret_cast<const u64 *>(d_keys), d_vals, d_flags,
                        (u64)n, fop, (u64)constant, tiles, reinterpret_cast<u64 *>(d_out_keys), d_out_vals);
   return hipGetLastError();
 }
@@ -294,13 +338,64 @@ hipError_t launch_select_emit_labelled(const void *d_keys, const uint32_t *d_val
   if (t == 0) return hipSuccess;
   u64 *tiles = reinterpret_cast<u64 *>(d_ws) + 8;
   if (key_words == 2)
-    hipLaunchKernelGGL((select_kernel<K128, true, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, reinterpret_cast<const K128 *>(d_keys), d_vals,
+    hipLaunchKernelGGL((select_kernel<K128, true, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, SelectNone{}, reinterpret_cast<const K128 *>(d_keys), d_vals,
                        (const u32 *)nullptr, (u64)n, fop, (u64)constant, tiles, reinterpret_cast<K128 *>(d_out_keys), d_out_vals,
                        reinterpret_cast<const u64 *>(d_labs), lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs));
   else
-    hipLaunchKernelGGL((select_kernel<u64, true, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, reinterpret_cast<const u64 *>(d_keys), d_vals,
+    hipLaunchKernelGGL((select_kernel<u64, true, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, SelectNone{}, reinterpret_cast<const u64 *>(d_keys), d_vals,
                        (const u32 *)nullptr, (u64)n, fop, (u64)constant, tiles, reinterpret_cast<u64 *>(d_out_keys), d_out_vals,
                        reinterpret_cast<const u64 *>(d_labs), lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs));
+  return hipGetLastError();
+}
+// the two passes with a selector program (terms checked by the caller; lop: a kernel code; d_out_labs may be null)
+template <typename K, bool EMIT>
+static void sl_launch_selected(bool labels, const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, int fop, uint64_t constant,
+                               const SelectProgram &program, uint64_t t, u64 *tiles, void *outK, u32 *outC, int lop, u64 lc, u64 *outL, hipStream_t st) {
+  SelectWords pg;
+  memcpy(&pg, &program, sizeof(pg));
+  if (labels)
+    hipLaunchKernelGGL((select_kernel<K, EMIT, true, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, pg, reinterpret_cast<const K *>(d_keys), d_vals,
+                       (const u32 *)nullptr, (u64)n, fop, (u64)constant, tiles, reinterpret_cast<K *>(outK), outC,
+                       reinterpret_cast<const u64 *>(d_labs), lop, lc, outL);
+  else
+    hipLaunchKernelGGL((select_kernel<K, EMIT, false, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, pg, reinterpret_cast<const K *>(d_keys), d_vals,
+                       (const u32 *)nullptr, (u64)n, fop, (u64)constant, tiles, reinterpret_cast<K *>(outK), outC,
+                       reinterpret_cast<const u64 *>(d_labs), lop, lc, outL);
+}
+static bool sl_program(SelectProgram *pg, uint32_t k, int fop, int lop, const mgc_select_term *terms, uint32_t n_terms) {
+  if (fop < 0 || fop > 11 || lop < LOP_SET || lop > LOP_SEL_MAX || lop == 12 || n_terms > MGC_SELECT_MAX_TERMS || (n_terms && !terms) || k < 1 || k > 64)
+    return false;
+  memset(pg, 0, sizeof(*pg));
+  for (uint32_t i = 0; i < n_terms; i++) pg->t[i] = terms[i];
+  pg->n = n_terms; pg->flags = select_flags(terms, n_terms); pg->k = k;
+  return true;
+}
+hipError_t launch_select_count_selected(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words, uint32_t k,
+                                        int fop, uint64_t constant, int lop, uint64_t lc, const mgc_select_term *terms, uint32_t n_terms, void *d_ws,
+                                        hipStream_t st) {
+  SelectProgram pg;
+  if (!sl_program(&pg, k, fop, lop, terms, n_terms)) return hipErrorInvalidValue;
+  u64 *ws = reinterpret_cast<u64 *>(d_ws);
+  const uint64_t t = select_tiles(n);
+  if (t == 0) return hipMemsetAsync(ws, 0, 8, st);
+  u64 *tiles = ws + 8, *scratch = tiles + t + 1;
+  const bool labels = (pg.flags & SELF_LABELS) != 0;
+  if (key_words == 2) sl_launch_selected<K128, false>(labels, d_keys, d_vals, d_labs, n, fop, constant, pg, t, tiles, nullptr, nullptr, lop, (u64)lc, nullptr, st);
+  else sl_launch_selected<u64, false>(labels, d_keys, d_vals, d_labs, n, fop, constant, pg, t, tiles, nullptr, nullptr, lop, (u64)lc, nullptr, st);
+  MGC_CHECK(hipGetLastError());
+  return scan_u64_exclusive(tiles, t, scratch, ws, st);
+}
+hipError_t launch_select_emit_selected(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words, uint32_t k,
+                                       int fop, uint64_t constant, int lop, uint64_t lc, const mgc_select_term *terms, uint32_t n_terms, void *d_ws,
+                                       void *d_out_keys, uint32_t *d_out_vals, uint64_t *d_out_labs, hipStream_t st) {
+  SelectProgram pg;
+  if (!sl_program(&pg, k, fop, lop, terms, n_terms)) return hipErrorInvalidValue;
+  const uint64_t t = select_tiles(n);
+  if (t == 0) return hipSuccess;
+  u64 *tiles = reinterpret_cast<u64 *>(d_ws) + 8;
+  const bool labels = (pg.flags & SELF_LABELS) != 0 || d_out_labs != nullptr;
+  if (key_words == 2) sl_launch_selected<K128, true>(labels, d_keys, d_vals, d_labs, n, fop, constant, pg, t, tiles, d_out_keys, d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs), st);
+  else sl_launch_selected<u64, true>(labels, d_keys, d_vals, d_labs, n, fop, constant, pg, t, tiles, d_out_keys, d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs), st);
   return hipGetLastError();
 }
 hipError_t launch_fill_u32(uint32_t *d, uint64_t n, uint32_t v, hipStream_t st) {

@@ -27,7 +27,12 @@
 // k-mer, never staged in LDS (only a 32-entry table of the inputs' label pointers joins the value pointers') -- and the head
 // thread folds them with LabelAcc (mgc_label.hpp) in input order.  Labels do not decide what is written: the count pass is
 // the unlabelled one.
+//
+// Selectors (meryl2; merylSelector::isTrue, src/meryl2/merylSelector.C:72-156): the SELECT instantiations AND a program of
+// value: / label: / bases: / input: tests (mgc_selector.hpp) onto the operation's rule.  Then labels and values can decide what is
+// written, and the count pass reads what the program needs.
 #include "mgc_common.hpp"
+#include "mgc_selector.hpp"
 
 namespace mgc {
 
@@ -86,11 +91,37 @@ void merge_many_partition_kernel(MergeManyDesc d, u64 total, u64 tiles, u64 *__r
   if (lane < MM_MAX) splits[b * MM_MAX + lane] = L;
 }
 
-template <typename K, bool EMIT, bool LABELS = false>
+// what a selector term sees of one group of equal keys (Src of mgc_selector.hpp).  The group is stored in input order from
+// position p on, so input i's element is at p + popcount(presence below bit i): one LDS tag read and one global read.
+template <typename K> struct MMSelectSrc {
+  u32 presence, out_value;
+  u64 out_label, lo, hi;
+  const u32 *sg;                                             // the merged image's tags
+  u32 p;                                                     // where the group begins
+  const u32 *const *vp;
+  const u64 *const *lp;                                      // null: no LABEL term asks
+  __device__ __forceinline__ u32 tag(u32 i) const { return sg[p + __builtin_popcount(presence & ((1u << i) - 1u))]; }
+  __device__ __forceinline__ u32 value(u32 i) const { const u32 t = tag(i); return vp[t >> 16][t & 0xFFFFu]; }
+  __device__ __forceinline__ u64 label(u32 i) const {
+    if (!lp) return 0ull;
+    const u32 t = tag(i);
+    const u64 *q = lp[t >> 16];
+    return q ? q[t & 0xFFFFu] : 0ull;
+  }
+};
+__device__ __forceinline__ void mm_key_words(u64 k, u64 *lo, u64 *hi)  { *lo = k; *hi = 0; }
+__device__ __forceinline__ void mm_key_words(K128 k, u64 *lo, u64 *hi) { *lo = k.lo; *hi = k.hi; }
+
+// SELECT: a selector program (mgc_selector.hpp) is ANDed onto the operation's keep rule by the head thread of every group; it
+// travels in the kernel-argument segment beside the descriptor and every read of it is wave-uniform.  The count pass then reads
+// what the program needs (SELF_*): values for VALUE terms, labels -- the LABELS instantiation, LabelAcc included -- for LABEL
+// terms, so that it decides exactly what the emit pass decides.  Without SELECT the argument is an empty struct.
+template <typename K, bool EMIT, bool LABELS = false, bool SELECT = false>
 __global__ __launch_bounds__(MM_BLOCK)
-void merge_many_kernel(MergeManyDesc d, int op, const u64 *__restrict__ splits, u64 *__restrict__ tile_cnt /*EMIT: exclusive bases*/,
-                       K *__restrict__ outK, u32 *__restrict__ outC, int lop = 0, u64 lc = 0, u64 *__restrict__ outL = nullptr) {
-  static_assert(EMIT || !LABELS, "labels do not change what is written: there is no labelled count pass");
+void merge_many_kernel(MergeManyDesc d, typename SelectArg<SELECT>::type prog, int op, const u64 *__restrict__ splits,
+                       u64 *__restrict__ tile_cnt /*EMIT: exclusive bases*/, K *__restrict__ outK, u32 *__restrict__ outC, int lop = 0, u64 lc = 0,
+                       u64 *__restrict__ outL = nullptr) {
+  static_assert(EMIT || !LABELS || SELECT, "labels do not change what is written: without a selector there is no labelled count pass");
   constexpr int CAP = mm_cap<K>(), ITEMS = MMGeom<K>::ITEMS;
   __shared__ K         s_key[2][CAP];
   __shared__ u32       s_tag[2][CAP];
@@ -159,7 +190,8 @@ void merge_many_kernel(MergeManyDesc d, int op, const u64 *__restrict__ splits, 
   }
   const K   *sk = s_key[cur];
   const u32 *sg = s_tag[cur];
-  const bool need_v = EMIT || op == 7;
+  bool need_v = EMIT || op == 7;
+  if constexpr (SELECT) need_v = need_v || (prog.flags & SELF_VALUES);
   const u32 l0 = threadIdx.x * ITEMS;
   u32 heads = 0, head_mask = 0, vreg[ITEMS];
   u64 lreg[LABELS ? ITEMS : 1];
@@ -173,13 +205,14 @@ void merge_many_kernel(MergeManyDesc d, int op, const u64 *__restrict__ splits, 
     if (p > 0 && !KeyOps<K>::ne(sk[p - 1], key)) continue;   // not the first of its group
     // the group, in input order: _actLen = cnt, _actIndex[0] = first, _actCount[] = the values
     const u32 first = sg[p] >> 16;
-    u32 cnt = 0, v = 0;
+    u32 cnt = 0, v = 0, presence = 0;                        // SELECT: bit i = input i holds the k-mer
     bool alive = true;                                       // subtract: the running difference stayed positive
     LabelAcc la;
     if constexpr (LABELS) la.begin(lc);
     for (u32 g = p; g < nt && !KeyOps<K>::ne(sk[g], key); g++) {
       u32 c = 0;
       if (need_v) { const u32 tag = sg[g]; c = s_vp[tag >> 16][tag & 0xFFFFu]; }
+      if constexpr (SELECT) presence |= 1u << (sg[g] >> 16);
       if constexpr (LABELS) {                                // _acta[ll]._lab / ._val in input order
         const u32 tag = sg[g];
         const u64 *lp = s_lp[tag >> 16];
@@ -198,6 +231,16 @@ void merge_many_kernel(MergeManyDesc d, int op, const u64 *__restrict__ splits, 
     else if (op == 7) keep = first == 0 && alive;
     else if (op == 8) keep = first == 0 && cnt == 1;
     else keep = cnt == 1;
+    if constexpr (SELECT) {
+      if (keep) {
+        MMSelectSrc<K> src;
+        src.presence = presence; src.out_value = (op == 10) ? cnt : v; src.out_label = 0;
+        if constexpr (LABELS) src.out_label = la.l;
+        mm_key_words(key, &src.lo, &src.hi);
+        src.sg = sg; src.p = p; src.vp = s_vp; src.lp = LABELS ? s_lp : nullptr;
+        keep = select_keep(prog.t, prog.n, prog.k, src);
+      }
+    }
     if (keep) {
       head_mask |= 1u << q; heads++; vreg[q] = (op == 10) ? cnt : v;
       if constexpr (LABELS) lreg[q] = la.l;
@@ -214,7 +257,7 @@ void merge_many_kernel(MergeManyDesc d, int op, const u64 *__restrict__ splits, 
   for (int q = 0; q < ITEMS; q++)
     if (head_mask & (1u << q)) {
       outK[o] = sk[l0 + q]; outC[o] = vreg[q];
-      if constexpr (LABELS) outL[o] = lreg[q];
+      if constexpr (LABELS) { if (!SELECT || outL) outL[o] = lreg[q]; }
       o++;
     }
 }
@@ -263,10 +306,10 @@ hipError_t launch_merge_many_count(const void *const *keys, const uint32_t *cons
   const uint32_t pgrid = (uint32_t)((t + 1 + MM_BLOCK / 64 - 1) / (MM_BLOCK / 64));
   if (key_words == 2) {
     hipLaunchKernelGGL((merge_many_partition_kernel<K128>), dim3(pgrid), dim3(MM_BLOCK), 0, st, d, (u64)total, (u64)t, splits);
-    hipLaunchKernelGGL((merge_many_kernel<K128, false>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, op, splits, tiles, (K128 *)nullptr, (u32 *)nullptr);
+    hipLaunchKernelGGL((merge_many_kernel<K128, false>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, SelectNone{}, op, splits, tiles, (K128 *)nullptr, (u32 *)nullptr);
   } else {
     hipLaunchKernelGGL((merge_many_partition_kernel<u64>), dim3(pgrid), dim3(MM_BLOCK), 0, st, d, (u64)total, (u64)t, splits);
-    hipLaunchKernelGGL((merge_many_kernel<u64, false>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, op, splits, tiles, (u64 *)nullptr, (u32 *)nullptr);
+    hipLaunchKernelGGL((merge_many_kernel<u64, false>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, SelectNone{}, op, splits, tiles, (u64 *)nullptr, (u32 *)nullptr);
   }
   MGC_CHECK(hipGetLastError());
   return scan_u64_exclusive(tiles, t, scratch, ws, st);
@@ -282,10 +325,10 @@ hipError_t launch_merge_many_emit(const void *const *keys, const uint32_t *const
   if (t == 0) return hipSuccess;
   u64 *tiles = ws + 8, *splits = ws + mm_splits_at(t);
   if (key_words == 2)
-    hipLaunchKernelGGL((merge_many_kernel<K128, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, op, splits, tiles,
+    hipLaunchKernelGGL((merge_many_kernel<K128, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, SelectNone{}, op, splits, tiles,
                        reinterpret_cast<K128 *>(d_out_keys), d_out_vals);
   else
-    hipLaunchKernelGGL((merge_many_kernel<u64, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, op, splits, tiles,
+    hipLaunchKernelGGL((merge_many_kernel<u64, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, SelectNone{}, op, splits, tiles,
                        reinterpret_cast<u64 *>(d_out_keys), d_out_vals);
   return hipGetLastError();
 }
@@ -303,11 +346,77 @@ hipError_t launch_merge_many_emit_labelled(const void *const *keys, const uint32
   if (t == 0) return hipSuccess;
   u64 *tiles = ws + 8, *splits = ws + mm_splits_at(t);
   if (key_words == 2)
-    hipLaunchKernelGGL((merge_many_kernel<K128, true, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, op, splits, tiles,
+    hipLaunchKernelGGL((merge_many_kernel<K128, true, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, SelectNone{}, op, splits, tiles,
                        reinterpret_cast<K128 *>(d_out_keys), d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs));
   else
-    hipLaunchKernelGGL((merge_many_kernel<u64, true, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, op, splits, tiles,
+    hipLaunchKernelGGL((merge_many_kernel<u64, true, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, SelectNone{}, op, splits, tiles,
                        reinterpret_cast<u64 *>(d_out_keys), d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs));
+  return hipGetLastError();
+}
+
+// ---- with a selector program (SELECT) ------------------------------------------------------------------------------------------
+// terms: checked by the caller (select_check); lop: a kernel code.  The LABELS instantiations run where a LABEL term asks for
+// labels (both passes) or labels are written (emit).
+static bool mm_select_desc(MergeManyDesc *d, SelectProgram *pg, const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs,
+                           const uint64_t *n, uint32_t n_inputs, uint32_t k, int op, int lop, const mgc_select_term *terms, uint32_t n_terms) {
+  if (!mm_desc(d, keys, vals, n, n_inputs, op, 1) || n_terms > MGC_SELECT_MAX_TERMS || (n_terms && !terms) || k < 1 || k > 64) return false;
+  if (lop < LOP_SET || lop > LOP_SEL_MAX || lop == 12 || (lop == LOP_INVERT && n_inputs > 1)) return false;
+  for (uint32_t i = 0; i < n_inputs; i++) d->labs[i] = labs ? reinterpret_cast<const u64 *>(labs[i]) : nullptr;
+  memset(pg, 0, sizeof(*pg));
+  for (uint32_t i = 0; i < n_terms; i++) pg->t[i] = terms[i];
+  pg->n = n_terms; pg->flags = select_flags(terms, n_terms); pg->k = k;
+  return true;
+}
+
+template <typename K, bool EMIT>
+static void mm_launch_selected(bool labels, const MergeManyDesc &d, const SelectProgram &pg, int op, uint64_t t, const u64 *splits, u64 *tiles,
+                               void *outK, u32 *outC, int lop, u64 lc, u64 *outL, hipStream_t st) {
+  if (labels)
+    hipLaunchKernelGGL((merge_many_kernel<K, EMIT, true, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, pg, op, splits, tiles,
+                       reinterpret_cast<K *>(outK), outC, lop, lc, outL);
+  else
+    hipLaunchKernelGGL((merge_many_kernel<K, EMIT, false, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, pg, op, splits, tiles,
+                       reinterpret_cast<K *>(outK), outC, lop, lc, outL);
+}
+
+hipError_t launch_merge_many_count_selected(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
+                                            uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int lop, uint64_t lc,
+                                            const mgc_select_term *terms, uint32_t n_terms, void *d_ws, hipStream_t st) {
+  MergeManyDesc d;
+  SelectProgram pg;
+  if (!mm_select_desc(&d, &pg, keys, vals, labs, n, n_inputs, k, op, lop, terms, n_terms)) return hipErrorInvalidValue;
+  u64 *ws = reinterpret_cast<u64 *>(d_ws);
+  const uint64_t total = mm_total(n, n_inputs), t = mm_tiles(total, key_words);
+  if (t == 0) return hipMemsetAsync(ws, 0, 8, st);
+  u64 *tiles = ws + 8, *scratch = tiles + t + 1, *splits = ws + mm_splits_at(t);
+  const uint32_t pgrid = (uint32_t)((t + 1 + MM_BLOCK / 64 - 1) / (MM_BLOCK / 64));
+  const bool labels = (pg.flags & SELF_LABELS) != 0;
+  if (key_words == 2) {
+    hipLaunchKernelGGL((merge_many_partition_kernel<K128>), dim3(pgrid), dim3(MM_BLOCK), 0, st, d, (u64)total, (u64)t, splits);
+    mm_launch_selected<K128, false>(labels, d, pg, op, t, splits, tiles, nullptr, nullptr, lop, (u64)lc, nullptr, st);
+  } else {
+    hipLaunchKernelGGL((merge_many_partition_kernel<u64>), dim3(pgrid), dim3(MM_BLOCK), 0, st, d, (u64)total, (u64)t, splits);
+    mm_launch_selected<u64, false>(labels, d, pg, op, t, splits, tiles, nullptr, nullptr, lop, (u64)lc, nullptr, st);
+  }
+  MGC_CHECK(hipGetLastError());
+  return scan_u64_exclusive(tiles, t, scratch, ws, st);
+}
+
+// d_out_labs may be null: no labels are written (they are still computed where a LABEL term looks at the output label)
+hipError_t launch_merge_many_emit_selected(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
+                                           uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int lop, uint64_t lc,
+                                           const mgc_select_term *terms, uint32_t n_terms, void *d_ws, void *d_out_keys, uint32_t *d_out_vals,
+                                           uint64_t *d_out_labs, hipStream_t st) {
+  MergeManyDesc d;
+  SelectProgram pg;
+  if (!mm_select_desc(&d, &pg, keys, vals, labs, n, n_inputs, k, op, lop, terms, n_terms)) return hipErrorInvalidValue;
+  u64 *ws = reinterpret_cast<u64 *>(d_ws);
+  const uint64_t t = mm_tiles(mm_total(n, n_inputs), key_words);
+  if (t == 0) return hipSuccess;
+  u64 *tiles = ws + 8, *splits = ws + mm_splits_at(t);
+  const bool labels = (pg.flags & SELF_LABELS) != 0 || d_out_labs != nullptr;
+  if (key_words == 2) mm_launch_selected<K128, true>(labels, d, pg, op, t, splits, tiles, d_out_keys, d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs), st);
+  else mm_launch_selected<u64, true>(labels, d, pg, op, t, splits, tiles, d_out_keys, d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs), st);
   return hipGetLastError();
 }
 

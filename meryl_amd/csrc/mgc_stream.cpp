@@ -10,6 +10,7 @@
 #include "mdb_layout.h"
 #include "mgc_session.hpp"
 #include "mgc_runs.hpp"
+#include "mgc_selector.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1022,10 +1023,20 @@ struct LabelPlan {
   mgc_eval_slice_labelled_cb cb;
 };
 
-// mgc_db_eval (lp == nullptr) and mgc_db_eval_labelled: one walk, one validation, one slice loop
+// what mgc_db_eval_selected adds: per node a range of one terms array (a selector program, mgc_selector.hpp), and the callback
+// (the labelled one; labels are zeros when they do not travel)
+struct SelectPlan {
+  const mgc_eval_node_selected *nodes;
+  const mgc_select_term *terms;
+  uint32_t n_terms;
+  mgc_eval_slice_labelled_cb cb;
+};
+
+// mgc_db_eval (lp == nullptr), mgc_db_eval_labelled and mgc_db_eval_selected (sp; with or without lp): one walk, one validation,
+// one slice loop
 int eval_impl(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children, uint32_t root,
-              mgc_eval_slice_cb cb, void *ctx, int device, int host_threads, const LabelPlan *lp) {
-  const char *who = lp ? "mgc_db_eval_labelled" : "mgc_db_eval";
+              mgc_eval_slice_cb cb, void *ctx, int device, int host_threads, const LabelPlan *lp, const SelectPlan *sp = nullptr) {
+  const char *who = sp ? "mgc_db_eval_selected" : lp ? "mgc_db_eval_labelled" : "mgc_db_eval";
   auto bad = [&](const std::string &m) { set_err(nullptr, "%s: %s", who, m.c_str()); return MGC_EINVAL; };
   if (!nodes || n_nodes == 0 || root >= n_nodes || (n_children && !children)) return bad("bad arguments");
   // ---- the tree: every node reached at most once, from the root (post-order = evaluation order)
@@ -1056,6 +1067,15 @@ int eval_impl(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *chil
           // the left fold combines two streams at a time: DIFFERENCE, MIN or LIGHTEST over all inputs at once cannot be folded
           if (nd.kind == MGC_NODE_MERGE && nd.n_children > MGC_MERGE_MANY_MAX)
             return bad(id + ": a merge of " + std::to_string(nd.n_children) + " inputs; with labels at most " + std::to_string(MGC_MERGE_MANY_MAX));
+        }
+        if (sp && sp->nodes[f.node].n_terms) {
+          const mgc_eval_node_selected &sn = sp->nodes[f.node];
+          if (nd.kind == MGC_NODE_DATABASE) return bad(id + ": a database takes no selector");
+          if ((uint64_t)sn.first_term + sn.n_terms > sp->n_terms) return bad(id + ": its selector terms are out of range");
+          if (nd.n_children > MGC_MERGE_MANY_MAX)
+            return bad(id + ": a merge of " + std::to_string(nd.n_children) + " inputs; with a selector at most " + std::to_string(MGC_MERGE_MANY_MAX));
+          const std::string m = mgc::select_check(sp->terms + sn.first_term, sn.n_terms, nd.n_children);
+          if (!m.empty()) return bad(id + ": selector: " + m);
         }
       }
       if (f.next < nd.n_children) {
@@ -1135,6 +1155,42 @@ int eval_impl(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *chil
     for (uint32_t i = 0; i < nd.n_children; i++) in[i] = ev[children[nd.first_child + i]].res;
     uint64_t n_new = 0;
     hipError_t e;
+    if (sp && sp->nodes[v].n_terms) {                        // a node with a program: select_kernel, or merge_many whatever its input count
+      const mgc_select_term *terms = sp->terms + sp->nodes[v].first_term;
+      const uint32_t n_terms = sp->nodes[v].n_terms;
+      const int lop = mgc::label_kernel_op(nd.kind == MGC_NODE_MERGE, nd.op, lp ? lp->nodes[v].label_op : MGC_LABEL_DEFAULT);
+      const uint64_t lc = lp ? lp->nodes[v].label_constant : 0;
+      if (nd.kind == MGC_NODE_VALUE) {
+        e = ws.ensure(mgc::select_workspace_bytes(in[0].n));
+        if (e == hipSuccess) e = mgc::launch_select_count_selected(in[0].k, in[0].c, in[0].l, in[0].n, kw, k, nd.op, nd.constant, lop, lc, terms, n_terms, ws.p, st);
+        if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
+        if (e == hipSuccess) e = me.k.ensure(8 * (size_t)kw * n_new);
+        if (e == hipSuccess) e = me.c.ensure(4 * n_new);
+        if (e == hipSuccess && lp) e = me.l.ensure(8 * n_new);
+        if (e == hipSuccess) e = mgc::launch_select_emit_selected(in[0].k, in[0].c, in[0].l, in[0].n, kw, k, nd.op, nd.constant, lop, lc, terms, n_terms, ws.p,
+                                                                  me.k.p, me.c.as<uint32_t>(), lp ? me.l.as<uint64_t>() : nullptr, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (hip_fail(e, "a value operation with a selector")) return false;
+      } else {
+        const void *kp[MGC_MERGE_MANY_MAX];
+        const uint32_t *cp[MGC_MERGE_MANY_MAX];
+        const uint64_t *lpp[MGC_MERGE_MANY_MAX];
+        uint64_t nn[MGC_MERGE_MANY_MAX];
+        for (uint32_t i = 0; i < nd.n_children; i++) { kp[i] = in[i].k; cp[i] = in[i].c; lpp[i] = in[i].l; nn[i] = in[i].n; }
+        e = ws.ensure(mgc::merge_many_workspace_bytes(nn, nd.n_children, kw));
+        if (e == hipSuccess) e = mgc::launch_merge_many_count_selected(kp, cp, lpp, nn, nd.n_children, kw, k, nd.op, lop, lc, terms, n_terms, ws.p, st);
+        if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
+        if (e == hipSuccess) e = me.k.ensure(8 * (size_t)kw * n_new);
+        if (e == hipSuccess) e = me.c.ensure(4 * n_new);
+        if (e == hipSuccess && lp) e = me.l.ensure(8 * n_new);
+        if (e == hipSuccess) e = mgc::launch_merge_many_emit_selected(kp, cp, lpp, nn, nd.n_children, kw, k, nd.op, lop, lc, terms, n_terms, ws.p, me.k.p,
+                                                                      me.c.as<uint32_t>(), lp ? me.l.as<uint64_t>() : nullptr, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (hip_fail(e, "merging a slice with a selector")) return false;
+      }
+      me.res = SliceRef{me.k.p, me.c.as<uint32_t>(), n_new, lp ? me.l.as<uint64_t>() : nullptr};
+      return true;
+    }
     if (lp) {                                                // labels travel with the k-mers; every merge through merge_many
       const int lop = mgc::label_kernel_op(nd.kind == MGC_NODE_MERGE, nd.op, lp->nodes[v].label_op);
       const uint64_t lc = lp->nodes[v].label_constant;
@@ -1219,11 +1275,11 @@ int eval_impl(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *chil
       }
     }
     if (rc != MGC_OK) break;
-    if (cb || (lp && lp->cb)) {
+    if (cb || (lp && lp->cb) || (sp && sp->cb)) {
       const SliceRef &r = ev[root].res;
       h_keys.resize((size_t)kw * r.n);
       h_vals.resize(r.n);
-      if (lp) h_labs.assign(r.n, 0);
+      if (lp || sp) h_labs.assign(r.n, 0);
       hipError_t e = hipSuccess;
       if (r.n) {
         e = hipMemcpyAsync(h_keys.data(), r.k, 8 * (size_t)kw * r.n, hipMemcpyDeviceToHost, st);
@@ -1238,7 +1294,8 @@ int eval_impl(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *chil
         for (uint64_t j = 0; j < r.n; j++) { h_lo[j] = h_keys[2 * j]; h_hi[j] = h_keys[2 * j + 1]; }
         lo = h_lo.data(); hi = h_hi.data();
       }
-      if (lp) lp->cb(ctx, ff, lo, hi, h_vals.data(), h_labs.data(), r.n);
+      if (sp) sp->cb(ctx, ff, lo, hi, h_vals.data(), h_labs.data(), r.n);
+      else if (lp) lp->cb(ctx, ff, lo, hi, h_vals.data(), h_labs.data(), r.n);
       else cb(ctx, ff, lo, hi, h_vals.data(), r.n);
     }
     for (uint32_t v : order) {                               // the buffers are reused for the next slice
@@ -1284,4 +1341,28 @@ extern "C" int mgc_db_eval_labelled(const mgc_eval_node_labelled *nodes, uint32_
   }
   LabelPlan lp{nodes, label_size, cb};
   return eval_impl(base.data(), n_nodes, children, n_children, root, nullptr, ctx, device, host_threads, &lp);
+}
+
+// the same tree with selector programs (include/meryl_db.h): nodes without one take the route they take in mgc_db_eval (labels do
+// not travel) or mgc_db_eval_labelled (they do: with_labels, or a LABEL term anywhere in the tree)
+extern "C" int mgc_db_eval_selected(const mgc_eval_node_selected *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
+                                    uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
+                                    mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads) {
+  if (!nodes || n_nodes == 0 || (n_terms && !terms)) { set_err(nullptr, "mgc_db_eval_selected: bad arguments"); return MGC_EINVAL; }
+  if (label_size > 64) { set_err(nullptr, "mgc_db_eval_selected: a label has at most 64 bits"); return MGC_EINVAL; }
+  std::vector<mgc_eval_node> base(n_nodes);
+  std::vector<mgc_eval_node_labelled> lab(n_nodes);
+  bool labels = with_labels != 0 || label_size != 0;
+  for (uint32_t i = 0; i < n_nodes; i++) {
+    base[i].kind = nodes[i].kind; base[i].op = nodes[i].op; base[i].constant = nodes[i].constant; base[i].path = nodes[i].path;
+    base[i].first_child = nodes[i].first_child; base[i].n_children = nodes[i].n_children;
+    lab[i].kind = nodes[i].kind; lab[i].op = nodes[i].op; lab[i].constant = nodes[i].constant; lab[i].path = nodes[i].path;
+    lab[i].first_child = nodes[i].first_child; lab[i].n_children = nodes[i].n_children;
+    lab[i].label_op = nodes[i].label_op; lab[i].reserved = 0; lab[i].label_constant = nodes[i].label_constant;
+    if ((uint64_t)nodes[i].first_term + nodes[i].n_terms <= n_terms)
+      for (uint32_t j = 0; j < nodes[i].n_terms; j++) labels = labels || terms[nodes[i].first_term + j].quantity == MGC_SEL_LABEL;
+  }
+  LabelPlan lp{lab.data(), label_size, nullptr};
+  SelectPlan sp{nodes, terms, n_terms, cb};
+  return eval_impl(base.data(), n_nodes, children, n_children, root, nullptr, ctx, device, host_threads, labels ? &lp : nullptr, &sp);
 }

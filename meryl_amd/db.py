@@ -266,3 +266,79 @@ def evaluate_labelled(tree, on_slice=None, label_size=0, device=-1, host_threads
     if rc != 0:
         msg = capi.lib().mgc_db_stream_error(None)
         raise capi.MgcError(rc, "mgc_db_eval_labelled", msg.decode("utf-8", "replace") if msg else "")
+
+
+def parse_selector(words, n_inputs):
+    """selector words ("input:2-all", "not", "value:@2>@1", "or", ...) of a node of n_inputs inputs -> list of capi.SelectTerm,
+    through mgc_select_parse -- the one parser, which the command line uses too"""
+    words = [w.encode() if isinstance(w, str) else bytes(w) for w in words]
+    arr = (ctypes.c_char_p * max(len(words), 1))(*words)
+    terms = (capi.SelectTerm * capi.SELECT_MAX_TERMS)()
+    n = ctypes.c_uint32(0)
+    rc = capi.lib().mgc_select_parse(arr, len(words), int(n_inputs), terms, capi.SELECT_MAX_TERMS, ctypes.byref(n))
+    if rc != 0:
+        msg = capi.lib().mgc_last_error(None)
+        raise capi.MgcError(rc, "mgc_select_parse", msg.decode("utf-8", "replace") if msg else "")
+    return [terms[i] for i in range(n.value)]
+
+
+def build_tree_selected(tree):
+    """build_tree_labelled for mgc_db_eval_selected: the options dict of a node also takes "select": [words...], the selector
+    words of the command line, parsed for the node's input count.
+    -> (EvalNodeSelected array, children array, number of children, root index, SelectTerm array, number of terms)"""
+    selects = []
+
+    def strip(t):
+        if isinstance(t, (str, bytes)):
+            selects.append(None)
+            return t
+        t = tuple(t)
+        opts = {}
+        if t and isinstance(t[-1], dict):
+            opts = dict(t[-1])
+            t = t[:-1]
+        words = opts.pop("select", None)
+        head = 2 if t and t[0] in VALUE_WORDS else 1
+        kids = tuple(strip(a) for a in t[head:])
+        selects.append(None if words is None else ([words] if isinstance(words, str) else list(words)))
+        return t[:head] + kids + ((opts,) if opts else ())
+
+    lab, kids, n_kids, root = build_tree_labelled(strip(tree))
+    assert len(selects) == len(lab)
+    arr = (capi.EvalNodeSelected * len(lab))()
+    terms = []
+    for e, b, words in zip(arr, lab, selects):
+        e.kind, e.op, e.constant, e.path, e.first_child, e.n_children = b.kind, b.op, b.constant, b.path, b.first_child, b.n_children
+        e.label_op, e.label_constant = b.label_op, b.label_constant
+        e.first_term, e.n_terms = len(terms), 0
+        if words:
+            got = parse_selector(words, b.n_children)
+            e.n_terms = len(got)
+            terms.extend(got)
+    tarr = (capi.SelectTerm * max(len(terms), 1))(*terms)
+    return arr, kids, n_kids, root, tarr, len(terms)
+
+
+def evaluate_selected(tree, on_slice=None, with_labels=False, label_size=0, device=-1, host_threads=8):
+    """evaluate_labelled() for trees whose nodes may carry selectors (mgc_db_eval_selected).  Labels travel when with_labels
+    or label_size is set or a label: selector asks for them; otherwise the tree is evaluated as evaluate() does, and
+    on_slice(file, lo, hi_or_None, values, labels) receives zeros for labels."""
+    arr, kids, n_kids, root, terms, n_terms = build_tree_selected(tree)
+    failure = []
+
+    def trampoline(ctx, ff, lo, hi, vals, labs, n):
+        try:
+            def take(p, dtype):
+                return np.ctypeslib.as_array(p, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype=dtype)
+            on_slice(ff, take(lo, np.uint64), take(hi, np.uint64) if hi else None, take(vals, np.uint32), take(labs, np.uint64))
+        except BaseException as e:                               # not through the C frames
+            failure.append(e)
+
+    cb = capi.EVAL_SLICE_LABELLED_CB(trampoline) if on_slice is not None else ctypes.cast(None, capi.EVAL_SLICE_LABELLED_CB)
+    rc = capi.lib().mgc_db_eval_selected(arr, len(arr), kids, n_kids, root, terms, n_terms, int(bool(with_labels)), int(label_size), cb, None,
+                                         device, host_threads)
+    if failure:
+        raise failure[0]
+    if rc != 0:
+        msg = capi.lib().mgc_db_stream_error(None)
+        raise capi.MgcError(rc, "mgc_db_eval_selected", msg.decode("utf-8", "replace") if msg else "")

@@ -17,8 +17,13 @@
     8- and 16-byte keys.  `expected_ratio` is the ratio of the bytes the two move: per input element the count pass reads the
     key and the emit pass the key and the value (4 B), per kept k-mer the emit writes key and value; labels add 8 B per element
     read and 8 B per kept k-mer written.
+  * selectors (leg s): merge_many with a selector program (`input:2-all value:ge2`, mgc_dev_merge_many_*_selected, no labels)
+    beside the same union-sum without one (mgc_dev_merge_many_*) over the `shared50` mix, N = 3 and 8, 8-byte keys.  No ratio
+    is fixed in advance; the line holds the bytes each pair moves: the plain count pass reads the keys and the emit pass keys and
+    values and writes what is kept; with a VALUE term the selected count pass reads the values too (4 B more per element), and
+    the selected emit writes fewer k-mers.
 
-usage: python scripts/setops_bench.py [KEYS_M] [READS_M] [--dir DIR] [--legs a,b,c] [--staged-meryl PATH] >> profiles/setops_bench.jsonl"""
+usage: python scripts/setops_bench.py [KEYS_M] [READS_M] [--dir DIR] [--legs a,b,c,s] [--staged-meryl PATH] >> profiles/setops_bench.jsonl"""
 import json
 import os
 import shutil
@@ -30,7 +35,7 @@ import time
 
 sys.path.insert(0, '.')
 import torch  # noqa: E402
-from meryl_amd import build, capi, count  # noqa: E402
+from meryl_amd import build, capi, count, db  # noqa: E402
 
 
 def option(name, default=None):
@@ -178,6 +183,40 @@ def labels_leg():
             torch.cuda.empty_cache()
 
 
+def selectors_leg():
+    n = int(keys_m * 1_000_000)
+    g = torch.Generator(device=dev)
+    g.manual_seed(20261020)
+    words = ["input:2-all", "value:ge2"]
+    for n_inputs in (3, 8):
+        ks, vs = make_inputs(n_inputs, n, "shared50", g)
+        terms = db.parse_selector(words, n_inputs)
+        total = sum(int(k.shape[0]) for k in ks)
+        out = {}
+
+        def plain():
+            out["plain"] = count.dev_merge_many(ks, vs, "union-sum")
+
+        def selected():
+            out["sel"] = count.dev_merge_many_selected(ks, vs, None, 28, "union-sum", terms, with_labels=False)
+        plain_ms, plain_samples = timed(plain)
+        sel_ms, sel_samples = timed(selected)
+        n_plain, n_sel = int(out["plain"][0].shape[0]), int(out["sel"][0].shape[0])
+        pk, pc = out["plain"]
+        # what the program keeps, from the plain result: the shared k-mers (tag 32, held by every input; their sums are >= 2)
+        keep = (pk & 63) == 32
+        same = torch.equal(pk[keep], out["sel"][0]) and torch.equal(pc[keep], out["sel"][1])
+        out.clear()
+        plain_bytes = total * 8 + total * 12 + n_plain * 12
+        sel_bytes = total * 12 + total * 12 + n_sel * 12
+        emit(what="selectors", n_inputs=n_inputs, key_bytes=8, mix="shared50", op="union-sum", select=words, keys_per_input=n, total=total,
+             n_out_plain=n_plain, n_out_selected=n_sel, equal=bool(same), merge_many_ms=round(plain_ms, 3), selected_ms=round(sel_ms, 3),
+             selected_over_plain=round(sel_ms / plain_ms, 3), plain_bytes=plain_bytes, selected_bytes=sel_bytes,
+             bytes_ratio=round(sel_bytes / plain_bytes, 3), samples_plain_ms=plain_samples, samples_selected_ms=sel_samples)
+        del ks, vs
+        torch.cuda.empty_cache()
+
+
 def wall(cmd, env=None):
     t0 = time.perf_counter()
     subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, env=env)
@@ -255,5 +294,7 @@ if "b" in legs:
     cli_leg()
 if "c" in legs:
     labels_leg()
+if "s" in legs:
+    selectors_leg()
 if own_dir:
     shutil.rmtree(work, ignore_errors=True)
