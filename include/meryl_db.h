@@ -322,6 +322,36 @@ int mgc_db_eval_selected(const mgc_eval_node_selected *nodes, uint32_t n_nodes, 
                          uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
                          mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads);
 
+/* The same with VALUE ASSIGNMENT (meryl2's value=<word>[#c]; include/meryl_gpu_count.h: MGC_ASSIGN_*, mgc_value_assign_parse): a
+ * node may also name how the value of a written k-mer comes from the values of the inputs that hold it.  A node with an
+ * assignment keeps only the presence rule of its operation, writes no k-mer whose assigned value is 0, and shows the assigned
+ * value to its selector program; on a value FILTER node (MGC_VALUE_LESS_THAN .. MGC_VALUE_NOT_EQUAL_TO) the filter tests the
+ * assigned value.  MGC_LABEL_SELECTED on such a node follows the assignment (MIN, MAX, otherwise FIRST).  Such a node always goes
+ * through mgc_dev_merge_many_*_assigned (one input included); a node with MGC_ASSIGN_NONE takes exactly the route it takes in
+ * mgc_db_eval_selected, and a tree with no assignment anywhere gives that entry point's outputs byte for byte.  The stored
+ * histogram of an output describes the assigned values.  The other parameters are mgc_db_eval_selected's.
+ * Checked with everything mgc_db_eval_selected checks, before any device call and before any output directory exists
+ * (MGC_EINVAL with text): an unknown assign code; an assignment on a database node or on an arithmetic value node
+ * (MGC_VALUE_INCREASE .. MGC_VALUE_MODULO -- the operation word is one); a merge node with an assignment and more than
+ * MGC_MERGE_MANY_MAX inputs. */
+typedef struct mgc_eval_node_assigned {
+  int32_t     kind;                /* MGC_NODE_* */
+  int32_t     op;                  /* MGC_MERGE_* / MGC_VALUE_* (ignored for a leaf) */
+  uint64_t    constant;            /* value operations */
+  const char *path;                /* leaf: the database; inner node: its output, or NULL */
+  uint32_t    first_child, n_children;   /* range of children[] */
+  int32_t     label_op;            /* MGC_LABEL_* (ignored for a leaf) */
+  int32_t     reserved;
+  uint64_t    label_constant;
+  uint32_t    first_term, n_terms; /* range of terms[]; n_terms = 0: no selector */
+  int32_t     value_assign;        /* MGC_ASSIGN_*; MGC_ASSIGN_NONE: the operation's own value rule */
+  int32_t     reserved2;
+  uint64_t    value_constant;      /* cut to 32 bits; taken as given (mgc_value_default_constant names the reference's default) */
+} mgc_eval_node_assigned;
+int mgc_db_eval_assigned(const mgc_eval_node_assigned *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
+                         uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
+                         mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads);
+
 /* ONE count spread over the GPUs of a node, from one process (meryl_amd/csrc/mgc_node.cpp): rank r's reads are the
  * n_bases[r] bytes at d_bases[r] on device devices[r] (the base stream mgc_push_bases takes; with cfg->homopoly_compress
  * every rank's stream must hold whole sequences).  Every rank extracts the k-mers of its reads, the k-mers travel over

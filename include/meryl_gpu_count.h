@@ -385,6 +385,69 @@ int mgc_dev_select_emit_selected(const void *d_keys, const uint32_t *d_values, c
                                  const mgc_select_term *terms, uint32_t n_terms, void *d_workspace, size_t workspace_bytes,
                                  void *d_keys_out, uint32_t *d_values_out, uint64_t *d_labels_out, void *stream);
 
+/* ---- value assignment (meryl2) ---------------------------------------------------------------------------------------------
+ * value=<word>[#c] after a set or value-filter operation names how the VALUE of a written k-mer comes from the values V[j] of its
+ * ACTIVE inputs (the inputs that hold the k-mer, in input order) and the constant c, cut to 32 bits --
+ * merylOpCompute::findOutputValue, src/meryl2/merylOpCompute.C:136-282; all arithmetic is on 32-bit kmvalu.  With an assignment
+ * the operation supplies only the presence rule (merylCommandBuilder-processText.C:384-442): union* any input, intersect* all
+ * inputs, subtract the first input holds it, difference the first input and only it, symmetric-difference exactly one input.  A
+ * k-mer whose assigned value is 0 is not written (src/meryl2/merylOp-nextMer.C:119).  A selector's "output value" is the assigned
+ * value; labels still see the inputs' values.
+ *   NONE      the operation's own rule, exactly as without an assignment                      (valueNOP :142-143)
+ *   SET       c                                                                              (:145-147)
+ *   FIRST     V[0]: the first ACTIVE input                                                   (:154-157)
+ *   SELECTED  V[0].  The reference's valueSelected is a placeholder that takes _acta[0] under a `#warning wrong` (:149-152);
+ *             its stated meaning -- the value of the input the assignment selects -- is the first active input's here too, so
+ *             SELECTED and FIRST coincide.
+ *   MIN MAX   the smallest / largest of c and every V[j]                                     (:159-169)
+ *   ADD       c + V[0] + ..., SATURATING at 2^32-1 (:171-178) -- unlike MGC_MERGE_UNION_SUM, which keeps wrapping
+ *   SUB       V[0] - V[1] - ... - c; a step that would reach 0 or less gives 0               (:180-194)
+ *   MUL       c * V[0] * ..., saturating at 2^32-1 (:196-203).  A running value of 0 stays 0: the reference divides
+ *             kmvalumax by it (:199), which is undefined there.
+ *   DIV       V[0] / V[1] / ... / c, truncating; a zero divisor gives 0                      (:206-220)
+ *   DIVZ      per divisor d (V[1], ..., then c): d == 0 gives 0; running < d gives 1 (also when running is 0, as there);
+ *             otherwise round(running / (double)d), computed as (2 * running + d) / (2 * d) in 64-bit integers, which is the
+ *             same number for all 32-bit operands                                            (:227-245)
+ *   MOD       q = V[0], r = 0; per divisor d (V[1], ..., then c): d > 0: r += q mod d, q = q / d; d == 0: r += q, q = 0;
+ *             the value is r, accumulated mod 2^32                                           (:248-275)
+ *   COUNT     the number of active inputs                                                    (:278-280)
+ * mgc_value_default_constant(assign): the constant the reference uses when the command names none
+ * (merylCommandBuilder-isAssign.C:78-91): 2^32-1 for MIN, 1 for MUL, DIV and DIVZ, 0 otherwise.  The reference's float constants
+ * for mul / div are not offered. */
+#define MGC_ASSIGN_NONE      0
+#define MGC_ASSIGN_SET       1
+#define MGC_ASSIGN_FIRST     2
+#define MGC_ASSIGN_SELECTED  3
+#define MGC_ASSIGN_MIN       4
+#define MGC_ASSIGN_MAX       5
+#define MGC_ASSIGN_ADD       6
+#define MGC_ASSIGN_SUB       7
+#define MGC_ASSIGN_MUL       8
+#define MGC_ASSIGN_DIV       9
+#define MGC_ASSIGN_DIVZ     10
+#define MGC_ASSIGN_MOD      11
+#define MGC_ASSIGN_COUNT    12
+uint64_t mgc_value_default_constant(int assign);
+/* THE parser of what follows `value=` (the CLI and Python both call it): `word`, `word#c` or `#c` with the words first selected
+ * min max add sum sub dif mul div divzero mod rem count (isAssignValue, merylCommandBuilder-isAssign.C:44-103) and c an
+ * integer as the selector parser takes them (decimal, 0x.., 0b..).  Without #c the constant is the word's default.  MGC_EINVAL
+ * with text in mgc_last_error(NULL): an unknown word, a constant above 2^32-1 or that is no integer, and a constant on count,
+ * first or selected (the reference knows no `count#`, `first#` or `selected#`). */
+int mgc_value_assign_parse(const char *text, int *assign, uint64_t *constant);
+/* The two steps of mgc_dev_merge_many_*_selected with a value assignment: value_assign = MGC_ASSIGN_*, value_constant cut to 32
+ * bits.  n_inputs = 1 is accepted and the program may be empty.  The count step reads the values unless the rule is SET or COUNT
+ * (and no term asks), and decides exactly what the emit step writes.  MGC_LABEL_SELECTED follows the assignment (MIN, MAX,
+ * otherwise FIRST).  MGC_ASSIGN_NONE gives exactly the _selected result; an unknown code: MGC_EINVAL with text. */
+int mgc_dev_merge_many_count_assigned(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *const *d_labels,
+                                      const uint64_t *n, uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int value_assign,
+                                      uint64_t value_constant, int label_op, uint64_t label_constant, const mgc_select_term *terms,
+                                      uint32_t n_terms, void *d_workspace, size_t workspace_bytes, uint64_t *n_out, void *stream);
+int mgc_dev_merge_many_emit_assigned(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *const *d_labels,
+                                     const uint64_t *n, uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int value_assign,
+                                     uint64_t value_constant, int label_op, uint64_t label_constant, const mgc_select_term *terms,
+                                     uint32_t n_terms, void *d_workspace, size_t workspace_bytes, void *d_keys_out,
+                                     uint32_t *d_values_out, uint64_t *d_labels_out, void *stream);
+
 /* Database blocks decoded on the device (mgc_decode.hip): d_file = the bytes of one data file followed by 16 bytes of slack,
  * d_blocks = the mdb_raw_block array of include/meryl_db.h (mdb_reader_raw_file gives both, validated against the file
  * size), suffix_size / label_size as the database's mdb_info has them.  d_keys / d_values / d_labels receive the k-mers of

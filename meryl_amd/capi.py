@@ -30,6 +30,7 @@ SYMBOLS = (
     "mgc_label_default_constant", "mgc_dev_merge_many_emit_labelled", "mgc_dev_select_emit_labelled", "mgc_dev_decode_blocks",
     "mgc_select_parse", "mgc_select_check", "mgc_dev_merge_many_count_selected", "mgc_dev_merge_many_emit_selected",
     "mgc_dev_select_count_selected", "mgc_dev_select_emit_selected",
+    "mgc_value_default_constant", "mgc_value_assign_parse", "mgc_dev_merge_many_count_assigned", "mgc_dev_merge_many_emit_assigned",
     "mgc_dev_homopoly_workspace_bytes", "mgc_dev_homopoly_compress", "mgc_set_batch_bases", "mgc_prepare", "mgc_set_result_budget", "mgc_result_out_of_core",
     # include/meryl_db.h
     "mdb_writer_open", "mdb_writer_open_ex", "mdb_merge_parts", "mdb_writer_add_block", "mdb_writer_add_block_labelled",
@@ -37,7 +38,7 @@ SYMBOLS = (
     "mdb_reader_open", "mdb_reader_info", "mdb_reader_histogram", "mdb_reader_read_file", "mdb_reader_read_file_ex",
     "mdb_reader_file_index", "mdb_reader_block_header", "mdb_reader_read_block_raw", "mdb_reader_raw_file", "mdb_reader_close",
     "mdb_free", "mgc_write_database", "mgc_write_database_profiled",
-    "mgc_db_stream_open", "mgc_db_stream_write", "mgc_db_stream_write_labelled", "mgc_db_eval_labelled", "mgc_db_eval_selected", "mgc_db_stream_sync", "mgc_db_stream_close", "mgc_db_stream_error", "mgc_db_stream_queued", "mgc_db_stream_done", "mgc_db_stream_wait_buffers",
+    "mgc_db_stream_open", "mgc_db_stream_write", "mgc_db_stream_write_labelled", "mgc_db_eval_labelled", "mgc_db_eval_selected", "mgc_db_eval_assigned", "mgc_db_stream_sync", "mgc_db_stream_close", "mgc_db_stream_error", "mgc_db_stream_queued", "mgc_db_stream_done", "mgc_db_stream_wait_buffers",
     "mgc_runs_open", "mgc_runs_add", "mgc_runs_write", "mgc_runs_get_profile", "mgc_runs_error", "mgc_runs_close", "mgc_get_runs_profile", "mgc_db_merge", "mgc_db_filter", "mgc_db_eval", "mgc_count_node", "mgc_count_node_batched", "mgc_count_node_staged", "mgc_node_plan",
     # include/meryl_lookup.h
     "mgc_lookup_load", "mgc_lookup_estimate", "mgc_lookup_from_device", "mgc_lookup_free", "mgc_lookup_get_info", "mgc_lookup_error",
@@ -126,6 +127,18 @@ class EvalNodeSelected(ctypes.Structure):
     ]
 
 
+class EvalNodeAssigned(ctypes.Structure):
+    """mgc_eval_node_assigned (include/meryl_db.h): mgc_eval_node_selected plus the node's value assignment and constant"""
+    _fields_ = EvalNodeSelected._fields_ + [
+        ("value_assign", ctypes.c_int32),
+        ("reserved2", ctypes.c_int32),
+        ("value_constant", ctypes.c_uint64),
+    ]
+
+
+# MGC_ASSIGN_* (include/meryl_gpu_count.h): the words of value=<word>[#c]
+ASSIGN_OPS = {"none": 0, "set": 1, "first": 2, "selected": 3, "min": 4, "max": 5, "add": 6, "sum": 6, "sub": 7, "dif": 7, "mul": 8, "div": 9,
+              "divzero": 10, "mod": 11, "rem": 11, "count": 12}
 # MGC_SEL_* / MGC_REL_* / MGC_SELECT_MAX_TERMS (include/meryl_gpu_count.h)
 SEL_VALUE, SEL_LABEL, SEL_BASES, SEL_INPUT = 1, 2, 3, 4
 REL_EQ, REL_NEQ, REL_LEQ, REL_GEQ, REL_LT, REL_GT = 1, 2, 3, 4, 5, 6
@@ -415,6 +428,10 @@ def lib():
     sig("mgc_select_check", i32, P(SelectTerm), u32, u32)
     sig("mgc_dev_merge_many_count_selected", i32, P(vp), P(vp), P(vp), P(u64), u32, u32, u32, i32, i32, u64, P(SelectTerm), u32, vp, sz, P(u64), vp)
     sig("mgc_dev_merge_many_emit_selected", i32, P(vp), P(vp), P(vp), P(u64), u32, u32, u32, i32, i32, u64, P(SelectTerm), u32, vp, sz, vp, vp, vp, vp)
+    sig("mgc_value_default_constant", u64, i32)
+    sig("mgc_value_assign_parse", i32, ctypes.c_char_p, P(i32), P(u64))
+    sig("mgc_dev_merge_many_count_assigned", i32, P(vp), P(vp), P(vp), P(u64), u32, u32, u32, i32, i32, u64, i32, u64, P(SelectTerm), u32, vp, sz, P(u64), vp)
+    sig("mgc_dev_merge_many_emit_assigned", i32, P(vp), P(vp), P(vp), P(u64), u32, u32, u32, i32, i32, u64, i32, u64, P(SelectTerm), u32, vp, sz, vp, vp, vp, vp)
     sig("mgc_dev_select_count_selected", i32, vp, vp, vp, u64, u32, u32, i32, u64, i32, u64, P(SelectTerm), u32, vp, sz, P(u64), vp)
     sig("mgc_dev_select_emit_selected", i32, vp, vp, vp, u64, u32, u32, i32, u64, i32, u64, P(SelectTerm), u32, vp, sz, vp, vp, vp, vp)
     sig("mgc_dev_decode_blocks", i32, vp, vp, u64, u32, u32, u32, vp, vp, vp, vp)
@@ -498,6 +515,7 @@ def lib():
     sig("mgc_db_eval", i32, P(EvalNode), u32, P(u32), u32, u32, EVAL_SLICE_CB, vp, i32, i32)
     sig("mgc_db_eval_labelled", i32, P(EvalNodeLabelled), u32, P(u32), u32, u32, u32, EVAL_SLICE_LABELLED_CB, vp, i32, i32)
     sig("mgc_db_eval_selected", i32, P(EvalNodeSelected), u32, P(u32), u32, u32, P(SelectTerm), u32, i32, u32, EVAL_SLICE_LABELLED_CB, vp, i32, i32)
+    sig("mgc_db_eval_assigned", i32, P(EvalNodeAssigned), u32, P(u32), u32, u32, P(SelectTerm), u32, i32, u32, EVAL_SLICE_LABELLED_CB, vp, i32, i32)
     sig("mgc_count_node", i32, P(CountConfig), u32, P(ctypes.c_int), P(vp), P(u64), ctypes.c_char_p, i32, P(NodeProfile))
     sig("mgc_count_node_batched", i32, P(CountConfig), u32, P(ctypes.c_int), P(vp), P(u64), u64, ctypes.c_char_p, i32, P(NodeProfile))
     sig("mgc_staged_bases", i32, vp, P(vp), P(u64))

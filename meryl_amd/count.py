@@ -355,6 +355,46 @@ def dev_merge_many_selected(keys_list, counts_list, labels_list, k, op="union-su
     return out_k, out_c, out_l, n.value
 
 
+def dev_merge_many_assigned(keys_list, counts_list, labels_list, k, op, value=None, terms=None, label_op="default", label_constant=None,
+                            with_labels=True, count_only=False):
+    """dev_merge_many_selected with a value assignment (mgc_dev_merge_many_*_assigned): value is what follows value= on the command
+    line ("sub#3", "#1", "count"), (word, constant) with a word of capi.ASSIGN_OPS or an MGC_ASSIGN_* number, or None (the
+    operation's own rule: the selected result).  The operation gives the presence rule, k-mers whose assigned value is 0 are not
+    written, and the program sees the assigned value.  -> (keys, values, labels or None, the count pass's total); count_only: the
+    count pass alone -> its total"""
+    from . import db
+    L = capi.lib()
+    m = len(keys_list)
+    kw = 2 if keys_list[0].dim() == 2 else 1
+    dev = keys_list[0].device
+    labels_list = labels_list if labels_list is not None else [None] * m
+    kp = (ctypes.c_void_p * m)(*[_ptr(x) if x.shape[0] else None for x in keys_list])
+    cp = (ctypes.c_void_p * m)(*[_ptr(c) if c.shape[0] else None for c in counts_list])
+    lp = (ctypes.c_void_p * m)(*[_ptr(l) if l is not None and l.shape[0] else None for l in labels_list])
+    ns = (ctypes.c_uint64 * m)(*[int(x.shape[0]) for x in keys_list])
+    code = op if isinstance(op, int) else MERGE_MANY_OPS[op]
+    vcode, vc = db.value_assign_option(value)
+    lcode = _label_code(label_op)
+    lc = int(L.mgc_label_default_constant(lcode)) if label_constant is None else int(label_constant) & 0xFFFFFFFFFFFFFFFF
+    tarr, nt = _select_terms(terms)
+    ws_bytes = max(int(L.mgc_dev_merge_many_workspace_bytes(ns, m, kw)), 256)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    n = ctypes.c_uint64(0)
+    capi.check(L.mgc_dev_merge_many_count_assigned(kp, cp, lp, ns, m, kw, int(k), code, vcode, vc, lcode, lc, tarr, nt, _ptr(ws), ws_bytes,
+                                                   ctypes.byref(n), _stream_ptr()), "mgc_dev_merge_many_count_assigned")
+    if count_only:
+        return n.value
+    out_k = _u64(n.value * kw, dev)
+    if kw == 2:
+        out_k = out_k.view(n.value, 2)
+    out_c = torch.empty(n.value, dtype=torch.int32, device=dev)
+    out_l = _u64(n.value, dev) if with_labels else None
+    capi.check(L.mgc_dev_merge_many_emit_assigned(kp, cp, lp, ns, m, kw, int(k), code, vcode, vc, lcode, lc, tarr, nt, _ptr(ws), ws_bytes,
+                                                  _ptr(out_k), _ptr(out_c), _ptr(out_l) if with_labels else None, _stream_ptr()),
+               "mgc_dev_merge_many_emit_assigned")
+    return out_k, out_c, out_l, n.value
+
+
 def dev_select_selected(keys, counts, labels, k, value_op, constant, terms=None, label_op="default", label_constant=None, with_labels=True,
                         count_only=False):
     """dev_select_labelled with a selector program (mgc_dev_select_*_selected): "output value" is the value after value_op, @1 the

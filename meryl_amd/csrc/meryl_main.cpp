@@ -19,7 +19,12 @@
 // and as before otherwise.  Selectors (meryl2): `value:`, `label:`, `bases:` and `input:` words with `not`, `and`, `or` after a set
 // or value operation (merylCommandBuilder-isSelect.C, merylSelector.C:72-156) are decoded by the library's parser
 // (mgc_select_parse) once the operation's inputs are known, and a tree that holds any is evaluated through
-// mgc_db_eval_selected; distinct= / word-frequency= / threshold= inside a selector stay on the value operations.
+// mgc_db_eval_selected; distinct= / word-frequency= / threshold= inside a selector stay on the value operations.  Value assignment
+// (meryl2): `value=<word>`, `value=<word>#<const>` or `value=#<const>` after a set or value-filter operation names how the value of
+// a written k-mer comes from its inputs' values (merylCommandBuilder-isAssign.C:44-103, merylOpCompute.C:136-282): the operation
+// then gives the presence rule only, k-mers whose assigned value is 0 are not written, and selectors and the filter see the
+// assigned value.  The text is decoded by the library's parser (mgc_value_assign_parse) and a tree that holds any is evaluated
+// through mgc_db_eval_assigned; the arithmetic value operations and the counting operations refuse it.
 // What stays refused: statistics, compare, ploidy, Canu sequence stores (segment=); CRAM only when no `samtools` is on the PATH.
 #include "../../include/meryl_db.h"
 #include "../../include/meryl_gpu_count.h"
@@ -93,6 +98,9 @@ struct Operation {
   bool                     has_label_op = false;   // label=<word>[#<const>] on a set or value operation (:124-156)
   int                      label_op = MGC_LABEL_DEFAULT;
   uint64_t                 label_constant = 0;
+  bool                     has_value_assign = false;   // value=<word>[#<const>] on a set or value-filter operation (:44-103)
+  int                      value_assign = MGC_ASSIGN_NONE;
+  uint64_t                 value_constant = 0;
   std::vector<std::string> select_words;        // value: label: bases: input: not and or, after a set or value operation (meryl2 selectors)
 };
 
@@ -121,8 +129,8 @@ void usage(const char *prog) {
           "       %s print <database.meryl | [operation]>\n"
           "       %s dumpIndex <database.meryl>\n"
           "       %s dumpFile <database.meryl>/0x######\n"
-          "       %s union[-min|-max|-sum]|intersect[-min|-max|-sum]|subtract|difference|symmetric-difference [label=<word>[#<n>]] [selector ...] <db | [operation]> ... [output <db>]\n"
-          "       %s less-than|greater-than|at-least|at-most|equal-to|not-equal-to <N | distinct=<f> | word-frequency=<f>> [selector ...] <db | [operation]> [output <db>]\n"
+          "       %s union[-min|-max|-sum]|intersect[-min|-max|-sum]|subtract|difference|symmetric-difference [value=<word>[#<n>]] [label=<word>[#<n>]] [selector ...] <db | [operation]> ... [output <db>]\n"
+          "       %s less-than|greater-than|at-least|at-most|equal-to|not-equal-to <N | distinct=<f> | word-frequency=<f>> [value=<word>[#<n>]] [selector ...] <db | [operation]> [output <db>]\n"
           "       %s increase|decrease|multiply|divide|divide-round|modulo <N> <db | [operation]> [output <db>]\n"
           "\n"
           "  MI355X-native implementation of the `count` path of marbl/meryl.  Words are processed left to\n"
@@ -133,6 +141,10 @@ void usage(const char *prog) {
           "  word-frequency= need a database, or an input operation that writes one).  label=<word> on a set or value\n"
           "  operation (first selected min max and or xor difference lightest heaviest invert, with #<n> a constant;\n"
           "  label=#<n> sets it) combines the labels of its inputs; a count inside such a tree may omit 'output'.\n"
+          "  value=<word> on a set operation or a value filter (first selected min max add sum sub dif mul div divzero mod rem\n"
+          "  count, with #<n> a constant; value=#<n> sets it) computes the value of a written k-mer from the values of the\n"
+          "  inputs that hold it; the operation then only decides where a k-mer must be present, a k-mer whose value\n"
+          "  becomes 0 is dropped, and selectors and the filter see the new value -- e.g. intersect value=sub a b.\n"
           "  A selector after a set or value operation keeps, of what the operation would write, the k-mers for which a\n"
           "  sum of products of tests holds: value:[lhs]REL<rhs>, label:[lhs]REL<rhs> (a side: @<input>, #<n> or <n>; no lhs:\n"
           "  the output k-mer; REL: == eq != <> ne <= le >= ge < lt > gt), bases:<acgt>:REL<n>, input:<n|n-m|n-all|all|any|\n"
@@ -647,6 +659,8 @@ struct EvalTree {
   bool                                label_words = false;    // an operation of the tree carries label=
   std::vector<mgc_select_term>        terms;                  // the selector programs of all nodes, one after the other
   std::vector<std::pair<uint32_t, uint32_t>> term_range;      // per node: first term, number of terms
+  std::vector<std::pair<int, uint64_t>> assign;               // per node: MGC_ASSIGN_*, constant
+  bool                                value_words = false;    // an operation of the tree carries value=
   uint32_t                            leaf_label_size = 0;    // the largest label size among the leaves
 };
 
@@ -722,6 +736,7 @@ uint32_t add_tree_node(const Globals &g, const std::vector<Operation> &ops, int 
     nd.path = in.child >= 0 ? ops[in.child].output.c_str() : in.path.c_str();
     t.nodes.push_back(nd);
     t.term_range.emplace_back(0u, 0u);
+    t.assign.emplace_back(MGC_ASSIGN_NONE, 0ull);
     t.kids.emplace_back();
     kids.push_back((uint32_t)t.nodes.size() - 1);
   }
@@ -758,6 +773,8 @@ uint32_t add_tree_node(const Globals &g, const std::vector<Operation> &ops, int 
   }
   t.nodes.push_back(nd);
   t.term_range.push_back(range);
+  t.assign.emplace_back(op.value_assign, op.value_constant);
+  t.value_words = t.value_words || op.has_value_assign;
   t.kids.push_back(kids);
   return (uint32_t)t.nodes.size() - 1;
 }
@@ -793,6 +810,23 @@ int run_tree(const Globals &g, const std::vector<Operation> &ops, int root, bool
   // with labels only when something asks for them: -l, a label= word, or a leaf that stores labels; the outputs (and the
   // label column `print` adds) take -l bits, or the largest label size among the leaves
   const bool with_labels = g.label_size_given || t.label_words || t.leaf_label_size;
+  if (t.value_words) {                                         // a value= somewhere: the same tree through mgc_db_eval_assigned
+    std::vector<mgc_eval_node_assigned> asg(t.nodes.size());
+    for (size_t v = 0; v < t.nodes.size(); v++) {
+      memset(&asg[v], 0, sizeof(asg[v]));
+      asg[v].kind = t.nodes[v].kind; asg[v].op = t.nodes[v].op; asg[v].constant = t.nodes[v].constant; asg[v].path = t.nodes[v].path;
+      asg[v].first_child = t.nodes[v].first_child; asg[v].n_children = t.nodes[v].n_children;
+      asg[v].label_op = t.nodes[v].label_op; asg[v].label_constant = t.nodes[v].label_constant;
+      asg[v].first_term = t.term_range[v].first; asg[v].n_terms = t.term_range[v].second;
+      asg[v].value_assign = t.assign[v].first; asg[v].value_constant = t.assign[v].second;
+    }
+    if (with_labels) pc.label_size = g.label_size_given && g.label_size ? g.label_size : t.leaf_label_size;
+    if (mgc_db_eval_assigned(asg.data(), (uint32_t)asg.size(), children.data(), (uint32_t)children.size(), r, t.terms.data(), (uint32_t)t.terms.size(),
+                             with_labels ? 1 : 0, g.label_size_given ? g.label_size : 0, print ? print_slice_labelled : nullptr, &pc, -1,
+                             (int)g.threads) != MGC_OK)
+      die("ERROR: %s", mgc_db_stream_error(nullptr));
+    return 0;
+  }
   if (!t.terms.empty()) {                                      // a selector somewhere: the same tree through mgc_db_eval_selected
     std::vector<mgc_eval_node_selected> sel(t.nodes.size());
     for (size_t v = 0; v < t.nodes.size(); v++) {
@@ -924,6 +958,15 @@ int main(int argc, char **argv) {
         g.label_size = (uint32_t)strtoul(argv[++a], nullptr, 10);
         if (g.label_size > 64) die("ERROR: label size of more than 64 bits.");
         g.label_size_given = true;
+      }
+      else if (key == "value" && eq != std::string::npos) {                  // value=<word>[#<const>]: how the operation computes the value
+        if (is_counting(top())) die("ERROR: '%s': a counting operation takes no value assignment.", w.c_str());
+        if (top() < 0 || !is_tree_op(ops[top()])) die("ERROR: '%s' needs a set or value-filter operation before it.", w.c_str());
+        if (ops[top()].kind == OP_VALUE && ops[top()].value_op > MGC_VALUE_NOT_EQUAL_TO)
+          die("ERROR: %s", ("operation '" + ops[top()].word + "' takes no '" + w + "': the operation is a value assignment itself.").c_str());
+        if (mgc_value_assign_parse(val.c_str(), &ops[top()].value_assign, &ops[top()].value_constant) != MGC_OK)
+          die("ERROR: %s", mgc_last_error(nullptr));
+        ops[top()].has_value_assign = true;
       }
       else if (key == "label" && eq != std::string::npos && top() >= 0 && is_tree_op(ops[top()])) {
         parse_label_assign(w, val, ops[top()]);                              // how the operation combines its inputs' labels

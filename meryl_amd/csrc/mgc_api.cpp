@@ -10,6 +10,7 @@
 #include "mgc_session.hpp"
 #include "mgc_runs.hpp"
 #include "mgc_selector.hpp"
+#include "mgc_value.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -439,6 +440,57 @@ extern "C" int mgc_dev_merge_many_emit_selected(const void *const *d_keys, const
   if (rc != MGC_OK) return rc;
   return hip_rc(mgc::launch_merge_many_emit_selected(d_keys, d_values, d_labels, n, n_inputs, key_words, k, op, lop, label_constant, terms, n_terms,
                                                      d_ws, d_keys_out, d_values_out, d_labels_out, (hipStream_t)stream), "merge_many_emit_selected");
+}
+
+// ---- value assignment (include/meryl_gpu_count.h: MGC_ASSIGN_*; the rule and the parser are mgc_value.hpp) ----------------------
+extern "C" uint64_t mgc_value_default_constant(int assign) { return mgc::value_default_constant(assign); }
+
+extern "C" int mgc_value_assign_parse(const char *text, int *assign, uint64_t *constant) {
+  if (!text || !assign || !constant) { set_err(nullptr, "mgc_value_assign_parse: bad arguments"); return MGC_EINVAL; }
+  const std::string m = mgc::value_assign_parse(text, assign, constant);
+  if (!m.empty()) { set_err(nullptr, "%s", m.c_str()); return MGC_EINVAL; }
+  return MGC_OK;
+}
+
+// selected_args with an assignment: *vop the kernel's value code, *lop resolved by the assignment where it is SELECTED
+static int assigned_args(const char *who, int op, uint32_t n_inputs, uint32_t key_words, uint32_t k, int value_assign, int label_op,
+                         const mgc_select_term *terms, uint32_t n_terms, int *vop, int *lop) {
+  *vop = mgc::value_kernel_op(value_assign);
+  if (*vop < 0) { set_err(nullptr, "%s: unknown value assignment %d", who, value_assign); return MGC_EINVAL; }
+  const int rc = selected_args(who, true, op, n_inputs, key_words, k, label_op, terms, n_terms, lop);
+  if (rc != MGC_OK) return rc;
+  *lop = mgc::label_kernel_op_assigned(true, op, label_op, value_assign);
+  return MGC_OK;
+}
+
+extern "C" int mgc_dev_merge_many_count_assigned(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *const *d_labels,
+                                                 const uint64_t *n, uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int value_assign,
+                                                 uint64_t value_constant, int label_op, uint64_t label_constant, const mgc_select_term *terms,
+                                                 uint32_t n_terms, void *d_ws, size_t ws_bytes, uint64_t *n_out, void *stream) {
+  if (!n_out || !d_ws || !merge_many_args_ok(d_keys, d_values, n, n_inputs, key_words, op, 1) ||
+      ws_bytes < mgc::merge_many_workspace_bytes(n, n_inputs, key_words)) return MGC_EINVAL;
+  int vop = 0, lop = 0;
+  const int rc = assigned_args("mgc_dev_merge_many_count_assigned", op, n_inputs, key_words, k, value_assign, label_op, terms, n_terms, &vop, &lop);
+  if (rc != MGC_OK) return rc;
+  hipError_t e = mgc::launch_merge_many_count_assigned(d_keys, d_values, d_labels, n, n_inputs, key_words, k, op, vop, value_constant, -1, 0, lop,
+                                                       label_constant, terms, n_terms, d_ws, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_rc(e, "merge_many_count_assigned");
+  return hip_rc(mgc::merge_read_total(d_ws, n_out, (hipStream_t)stream), "merge_many_count_assigned sync");
+}
+
+extern "C" int mgc_dev_merge_many_emit_assigned(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *const *d_labels,
+                                                const uint64_t *n, uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int value_assign,
+                                                uint64_t value_constant, int label_op, uint64_t label_constant, const mgc_select_term *terms,
+                                                uint32_t n_terms, void *d_ws, size_t ws_bytes, void *d_keys_out, uint32_t *d_values_out,
+                                                uint64_t *d_labels_out, void *stream) {
+  if (!d_ws || !merge_many_args_ok(d_keys, d_values, n, n_inputs, key_words, op, 1) ||
+      ws_bytes < mgc::merge_many_workspace_bytes(n, n_inputs, key_words)) return MGC_EINVAL;
+  int vop = 0, lop = 0;
+  const int rc = assigned_args("mgc_dev_merge_many_emit_assigned", op, n_inputs, key_words, k, value_assign, label_op, terms, n_terms, &vop, &lop);
+  if (rc != MGC_OK) return rc;
+  return hip_rc(mgc::launch_merge_many_emit_assigned(d_keys, d_values, d_labels, n, n_inputs, key_words, k, op, vop, value_constant, -1, 0, lop,
+                                                     label_constant, terms, n_terms, d_ws, d_keys_out, d_values_out, d_labels_out,
+                                                     (hipStream_t)stream), "merge_many_emit_assigned");
 }
 
 extern "C" int mgc_dev_select_count_selected(const void *d_keys, const uint32_t *d_values, const uint64_t *d_labels, uint64_t n, uint32_t key_words,

@@ -326,6 +326,15 @@ hipError_t launch_merge_many_emit_selected(const void *const *keys, const uint32
                                            uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int lop, uint64_t lc,
                                            const ::mgc_select_term *terms, uint32_t n_terms, void *d_ws, void *d_out_keys, uint32_t *d_out_vals,
                                            uint64_t *d_out_labs, hipStream_t st);
+// the same with a value assignment (mgc_value.hpp): vop a kernel code (VOP_NONE: the selected launch, unless a filter is given), vc its
+// constant; fop / fc: the value filter of a filter node tested on the assigned value (fop < 0: none)
+hipError_t launch_merge_many_count_assigned(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
+                                            uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int vop, uint64_t vc, int fop, uint64_t fc,
+                                            int lop, uint64_t lc, const ::mgc_select_term *terms, uint32_t n_terms, void *d_ws, hipStream_t st);
+hipError_t launch_merge_many_emit_assigned(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
+                                           uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int vop, uint64_t vc, int fop, uint64_t fc,
+                                           int lop, uint64_t lc, const ::mgc_select_term *terms, uint32_t n_terms, void *d_ws, void *d_out_keys,
+                                           uint32_t *d_out_vals, uint64_t *d_out_labs, hipStream_t st);
 hipError_t launch_select_count_selected(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words, uint32_t k,
                                         int fop, uint64_t constant, int lop, uint64_t lc, const ::mgc_select_term *terms, uint32_t n_terms,
                                         void *d_ws, hipStream_t st);

@@ -31,8 +31,14 @@
 // Selectors (meryl2; merylSelector::isTrue, src/meryl2/merylSelector.C:72-156): the SELECT instantiations AND a program of
 // value: / label: / bases: / input: tests (mgc_selector.hpp) onto the operation's rule.  Then labels and values can decide what is
 // written, and the count pass reads what the program needs.
+//
+// Value assignment (meryl2; merylOpCompute::findOutputValue, src/meryl2/merylOpCompute.C:136-282): the ASSIGN instantiations
+// (always with SELECT) keep the operation's presence rule only and let the head thread fold the group's values with ValueAcc
+// (mgc_value.hpp) in place of the operation's value chain; a k-mer whose assigned value is 0 is not written, so the count pass
+// reads the values unless the rule is #c or count.  The program, the labels and a value filter see the assigned value.
 #include "mgc_common.hpp"
 #include "mgc_selector.hpp"
+#include "mgc_value.hpp"
 
 namespace mgc {
 
@@ -116,12 +122,20 @@ __device__ __forceinline__ void mm_key_words(K128 k, u64 *lo, u64 *hi) { *lo = k
 // travels in the kernel-argument segment beside the descriptor and every read of it is wave-uniform.  The count pass then reads
 // what the program needs (SELF_*): values for VALUE terms, labels -- the LABELS instantiation, LabelAcc included -- for LABEL
 // terms, so that it decides exactly what the emit pass decides.  Without SELECT the argument is an empty struct.
-template <typename K, bool EMIT, bool LABELS = false, bool SELECT = false>
+// ASSIGN: the value rule (a kernel code of mgc_value.hpp), its constant and the value filter of a filter node travel as one more
+// argument, wave-uniform like the program; without ASSIGN it is an empty struct and the kernel is the one it was.
+struct AssignRule { int vop; u32 vc; int fop; u32 reserved; u64 fc; };   // fop < 0: no filter; fc: the filter's threshold
+struct AssignNone {};
+template <bool ASSIGN> struct AssignArg { typedef AssignNone type; };
+template <> struct AssignArg<true> { typedef AssignRule type; };
+
+template <typename K, bool EMIT, bool LABELS = false, bool SELECT = false, bool ASSIGN = false>
 __global__ __launch_bounds__(MM_BLOCK)
 void merge_many_kernel(MergeManyDesc d, typename SelectArg<SELECT>::type prog, int op, const u64 *__restrict__ splits,
                        u64 *__restrict__ tile_cnt /*EMIT: exclusive bases*/, K *__restrict__ outK, u32 *__restrict__ outC, int lop = 0, u64 lc = 0,
-                       u64 *__restrict__ outL = nullptr) {
+                       u64 *__restrict__ outL = nullptr, typename AssignArg<ASSIGN>::type asg = {}) {
   static_assert(EMIT || !LABELS || SELECT, "labels do not change what is written: without a selector there is no labelled count pass");
+  static_assert(SELECT || !ASSIGN, "an assignment comes with a (possibly empty) program");
   constexpr int CAP = mm_cap<K>(), ITEMS = MMGeom<K>::ITEMS;
   __shared__ K         s_key[2][CAP];
   __shared__ u32       s_tag[2][CAP];
@@ -192,6 +206,7 @@ void merge_many_kernel(MergeManyDesc d, typename SelectArg<SELECT>::type prog, i
   const u32 *sg = s_tag[cur];
   bool need_v = EMIT || op == 7;
   if constexpr (SELECT) need_v = need_v || (prog.flags & SELF_VALUES);
+  if constexpr (ASSIGN) need_v = EMIT || value_needs_values(asg.vop) || (prog.flags & SELF_VALUES);
   const u32 l0 = threadIdx.x * ITEMS;
   u32 heads = 0, head_mask = 0, vreg[ITEMS];
   u64 lreg[LABELS ? ITEMS : 1];
@@ -209,6 +224,8 @@ void merge_many_kernel(MergeManyDesc d, typename SelectArg<SELECT>::type prog, i
     bool alive = true;                                       // subtract: the running difference stayed positive
     LabelAcc la;
     if constexpr (LABELS) la.begin(lc);
+    ValueAcc va;
+    if constexpr (ASSIGN) va.begin(asg.vc);
     for (u32 g = p; g < nt && !KeyOps<K>::ne(sk[g], key); g++) {
       u32 c = 0;
       if (need_v) { const u32 tag = sg[g]; c = s_vp[tag >> 16][tag & 0xFFFFu]; }
@@ -218,7 +235,8 @@ void merge_many_kernel(MergeManyDesc d, typename SelectArg<SELECT>::type prog, i
         const u64 *lp = s_lp[tag >> 16];
         la.step(lop, lp ? lp[tag & 0xFFFFu] : 0ull, c);
       }
-      if (cnt == 0) v = c;
+      if constexpr (ASSIGN) va.step(asg.vop, c);            // _acta[ii]._val in input order
+      else if (cnt == 0) v = c;
       else if (op == 7) { if (v > c) v -= c; else alive = false; }
       else if (op == 0 || op == 3) v += c;                   // the sum wraps mod 2^32 like kmvalu arithmetic
       else if (op == 1 || op == 4) v = c < v ? c : v;
@@ -231,10 +249,14 @@ void merge_many_kernel(MergeManyDesc d, typename SelectArg<SELECT>::type prog, i
     else if (op == 7) keep = first == 0 && alive;
     else if (op == 8) keep = first == 0 && cnt == 1;
     else keep = cnt == 1;
+    if constexpr (ASSIGN) {                                  // so far the presence rule alone (`alive` was never cleared); now the value
+      v = va.finish(asg.vop, asg.vc, cnt);
+      keep = keep && v != 0 && value_filter_keeps(asg.fop, v, asg.fc);
+    }
     if constexpr (SELECT) {
       if (keep) {
         MMSelectSrc<K> src;
-        src.presence = presence; src.out_value = (op == 10) ? cnt : v; src.out_label = 0;
+        src.presence = presence; src.out_value = (!ASSIGN && op == 10) ? cnt : v; src.out_label = 0;
         if constexpr (LABELS) src.out_label = la.l;
         mm_key_words(key, &src.lo, &src.hi);
         src.sg = sg; src.p = p; src.vp = s_vp; src.lp = LABELS ? s_lp : nullptr;
@@ -242,7 +264,7 @@ void merge_many_kernel(MergeManyDesc d, typename SelectArg<SELECT>::type prog, i
       }
     }
     if (keep) {
-      head_mask |= 1u << q; heads++; vreg[q] = (op == 10) ? cnt : v;
+      head_mask |= 1u << q; heads++; vreg[q] = (!ASSIGN && op == 10) ? cnt : v;
       if constexpr (LABELS) lreg[q] = la.l;
     }
   }
@@ -417,6 +439,75 @@ hipError_t launch_merge_many_emit_selected(const void *const *keys, const uint32
   const bool labels = (pg.flags & SELF_LABELS) != 0 || d_out_labs != nullptr;
   if (key_words == 2) mm_launch_selected<K128, true>(labels, d, pg, op, t, splits, tiles, d_out_keys, d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs), st);
   else mm_launch_selected<u64, true>(labels, d, pg, op, t, splits, tiles, d_out_keys, d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs), st);
+  return hipGetLastError();
+}
+
+// ---- with a value assignment (ASSIGN; always with SELECT) --------------------------------------------------------------------------
+// vop: a kernel code (value_kernel_op, mgc_value.hpp); VOP_NONE without a filter is the selected launch itself.  fop >= 0: the
+// value filter of a filter node (MGC_VALUE_LESS_THAN .. NOT_EQUAL_TO) with threshold fc, tested on the assigned value.
+static bool mm_assign_rule(AssignRule *r, int vop, uint64_t vc, int fop, uint64_t fc) {
+  if (vop < VOP_SET || vop > VOP_COUNT || vop == 3 || fop > 5) return false;
+  r->vop = vop; r->vc = (u32)vc; r->fop = fop < 0 ? -1 : fop; r->reserved = 0; r->fc = fc;
+  return true;
+}
+
+template <typename K, bool EMIT>
+static void mm_launch_assigned(bool labels, const MergeManyDesc &d, const SelectProgram &pg, const AssignRule &rule, int op, uint64_t t,
+                               const u64 *splits, u64 *tiles, void *outK, u32 *outC, int lop, u64 lc, u64 *outL, hipStream_t st) {
+  if (labels)
+    hipLaunchKernelGGL((merge_many_kernel<K, EMIT, true, true, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, pg, op, splits, tiles,
+                       reinterpret_cast<K *>(outK), outC, lop, lc, outL, rule);
+  else
+    hipLaunchKernelGGL((merge_many_kernel<K, EMIT, false, true, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, pg, op, splits, tiles,
+                       reinterpret_cast<K *>(outK), outC, lop, lc, outL, rule);
+}
+
+hipError_t launch_merge_many_count_assigned(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
+                                            uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int vop, uint64_t vc, int fop, uint64_t fc,
+                                            int lop, uint64_t lc, const mgc_select_term *terms, uint32_t n_terms, void *d_ws, hipStream_t st) {
+  if (vop == VOP_NONE && fop < 0)
+    return launch_merge_many_count_selected(keys, vals, labs, n, n_inputs, key_words, k, op, lop, lc, terms, n_terms, d_ws, st);
+  MergeManyDesc d;
+  SelectProgram pg;
+  AssignRule rule;
+  if (!mm_select_desc(&d, &pg, keys, vals, labs, n, n_inputs, k, op, lop, terms, n_terms) || !mm_assign_rule(&rule, vop, vc, fop, fc))
+    return hipErrorInvalidValue;
+  u64 *ws = reinterpret_cast<u64 *>(d_ws);
+  const uint64_t total = mm_total(n, n_inputs), t = mm_tiles(total, key_words);
+  if (t == 0) return hipMemsetAsync(ws, 0, 8, st);
+  u64 *tiles = ws + 8, *scratch = tiles + t + 1, *splits = ws + mm_splits_at(t);
+  const uint32_t pgrid = (uint32_t)((t + 1 + MM_BLOCK / 64 - 1) / (MM_BLOCK / 64));
+  const bool labels = (pg.flags & SELF_LABELS) != 0;
+  if (key_words == 2) {
+    hipLaunchKernelGGL((merge_many_partition_kernel<K128>), dim3(pgrid), dim3(MM_BLOCK), 0, st, d, (u64)total, (u64)t, splits);
+    mm_launch_assigned<K128, false>(labels, d, pg, rule, op, t, splits, tiles, nullptr, nullptr, lop, (u64)lc, nullptr, st);
+  } else {
+    hipLaunchKernelGGL((merge_many_partition_kernel<u64>), dim3(pgrid), dim3(MM_BLOCK), 0, st, d, (u64)total, (u64)t, splits);
+    mm_launch_assigned<u64, false>(labels, d, pg, rule, op, t, splits, tiles, nullptr, nullptr, lop, (u64)lc, nullptr, st);
+  }
+  MGC_CHECK(hipGetLastError());
+  return scan_u64_exclusive(tiles, t, scratch, ws, st);
+}
+
+hipError_t launch_merge_many_emit_assigned(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
+                                           uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int vop, uint64_t vc, int fop, uint64_t fc,
+                                           int lop, uint64_t lc, const mgc_select_term *terms, uint32_t n_terms, void *d_ws, void *d_out_keys,
+                                           uint32_t *d_out_vals, uint64_t *d_out_labs, hipStream_t st) {
+  if (vop == VOP_NONE && fop < 0)
+    return launch_merge_many_emit_selected(keys, vals, labs, n, n_inputs, key_words, k, op, lop, lc, terms, n_terms, d_ws, d_out_keys, d_out_vals,
+                                           d_out_labs, st);
+  MergeManyDesc d;
+  SelectProgram pg;
+  AssignRule rule;
+  if (!mm_select_desc(&d, &pg, keys, vals, labs, n, n_inputs, k, op, lop, terms, n_terms) || !mm_assign_rule(&rule, vop, vc, fop, fc))
+    return hipErrorInvalidValue;
+  u64 *ws = reinterpret_cast<u64 *>(d_ws);
+  const uint64_t t = mm_tiles(mm_total(n, n_inputs), key_words);
+  if (t == 0) return hipSuccess;
+  u64 *tiles = ws + 8, *splits = ws + mm_splits_at(t);
+  const bool labels = (pg.flags & SELF_LABELS) != 0 || d_out_labs != nullptr;
+  if (key_words == 2) mm_launch_assigned<K128, true>(labels, d, pg, rule, op, t, splits, tiles, d_out_keys, d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs), st);
+  else mm_launch_assigned<u64, true>(labels, d, pg, rule, op, t, splits, tiles, d_out_keys, d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs), st);
   return hipGetLastError();
 }
 

@@ -11,6 +11,7 @@
 #include "mgc_session.hpp"
 #include "mgc_runs.hpp"
 #include "mgc_selector.hpp"
+#include "mgc_value.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1032,11 +1033,18 @@ struct SelectPlan {
   mgc_eval_slice_labelled_cb cb;
 };
 
-// mgc_db_eval (lp == nullptr), mgc_db_eval_labelled and mgc_db_eval_selected (sp; with or without lp): one walk, one validation,
-// one slice loop
+// what mgc_db_eval_assigned adds: per node a value assignment (MGC_ASSIGN_*, mgc_value.hpp) and its constant
+struct AssignPlan {
+  std::vector<int32_t>  assign;
+  std::vector<uint64_t> constant;
+};
+
+// mgc_db_eval (lp == nullptr), mgc_db_eval_labelled, mgc_db_eval_selected (sp; with or without lp) and mgc_db_eval_assigned (ap, with
+// sp): one walk, one validation, one slice loop
 int eval_impl(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children, uint32_t root,
-              mgc_eval_slice_cb cb, void *ctx, int device, int host_threads, const LabelPlan *lp, const SelectPlan *sp = nullptr) {
-  const char *who = sp ? "mgc_db_eval_selected" : lp ? "mgc_db_eval_labelled" : "mgc_db_eval";
+              mgc_eval_slice_cb cb, void *ctx, int device, int host_threads, const LabelPlan *lp, const SelectPlan *sp = nullptr,
+              const AssignPlan *ap = nullptr) {
+  const char *who = ap ? "mgc_db_eval_assigned" : sp ? "mgc_db_eval_selected" : lp ? "mgc_db_eval_labelled" : "mgc_db_eval";
   auto bad = [&](const std::string &m) { set_err(nullptr, "%s: %s", who, m.c_str()); return MGC_EINVAL; };
   if (!nodes || n_nodes == 0 || root >= n_nodes || (n_children && !children)) return bad("bad arguments");
   // ---- the tree: every node reached at most once, from the root (post-order = evaluation order)
@@ -1076,6 +1084,15 @@ int eval_impl(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *chil
             return bad(id + ": a merge of " + std::to_string(nd.n_children) + " inputs; with a selector at most " + std::to_string(MGC_MERGE_MANY_MAX));
           const std::string m = mgc::select_check(sp->terms + sn.first_term, sn.n_terms, nd.n_children);
           if (!m.empty()) return bad(id + ": selector: " + m);
+        }
+        if (ap && ap->assign[f.node] != MGC_ASSIGN_NONE) {
+          const int a = ap->assign[f.node];
+          if (mgc::value_kernel_op(a) < 0) return bad(id + ": unknown value assignment " + std::to_string(a));
+          if (nd.kind == MGC_NODE_DATABASE) return bad(id + ": a database takes no value assignment");
+          if (nd.kind == MGC_NODE_VALUE && nd.op > MGC_VALUE_NOT_EQUAL_TO)
+            return bad(id + ": an arithmetic value operation takes no value assignment (the operation is one)");
+          if (nd.n_children > MGC_MERGE_MANY_MAX)
+            return bad(id + ": a merge of " + std::to_string(nd.n_children) + " inputs; with a value assignment at most " + std::to_string(MGC_MERGE_MANY_MAX));
         }
       }
       if (f.next < nd.n_children) {
@@ -1155,6 +1172,34 @@ int eval_impl(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *chil
     for (uint32_t i = 0; i < nd.n_children; i++) in[i] = ev[children[nd.first_child + i]].res;
     uint64_t n_new = 0;
     hipError_t e;
+    if (ap && ap->assign[v] != MGC_ASSIGN_NONE) {            // a node with a value assignment: merge_many whatever its kind and input count
+      const bool is_merge = nd.kind == MGC_NODE_MERGE;
+      const mgc_select_term *terms = sp ? sp->terms + sp->nodes[v].first_term : nullptr;
+      const uint32_t n_terms = sp ? sp->nodes[v].n_terms : 0;
+      const int lop = mgc::label_kernel_op_assigned(is_merge, nd.op, lp ? lp->nodes[v].label_op : MGC_LABEL_DEFAULT, ap->assign[v]);
+      const uint64_t lc = lp ? lp->nodes[v].label_constant : 0;
+      const int vop = mgc::value_kernel_op(ap->assign[v]);
+      // a value filter node: its one input under the presence rule of a union, the filter on the assigned value
+      const int mop = is_merge ? nd.op : MGC_MERGE_UNION, fop = is_merge ? -1 : nd.op;
+      const void *kp[MGC_MERGE_MANY_MAX];
+      const uint32_t *cp[MGC_MERGE_MANY_MAX];
+      const uint64_t *lpp[MGC_MERGE_MANY_MAX];
+      uint64_t nn[MGC_MERGE_MANY_MAX];
+      for (uint32_t i = 0; i < nd.n_children; i++) { kp[i] = in[i].k; cp[i] = in[i].c; lpp[i] = in[i].l; nn[i] = in[i].n; }
+      e = ws.ensure(mgc::merge_many_workspace_bytes(nn, nd.n_children, kw));
+      if (e == hipSuccess) e = mgc::launch_merge_many_count_assigned(kp, cp, lpp, nn, nd.n_children, kw, k, mop, vop, ap->constant[v], fop, nd.constant, lop, lc,
+                                                                     terms, n_terms, ws.p, st);
+      if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
+      if (e == hipSuccess) e = me.k.ensure(8 * (size_t)kw * n_new);
+      if (e == hipSuccess) e = me.c.ensure(4 * n_new);
+      if (e == hipSuccess && lp) e = me.l.ensure(8 * n_new);
+      if (e == hipSuccess) e = mgc::launch_merge_many_emit_assigned(kp, cp, lpp, nn, nd.n_children, kw, k, mop, vop, ap->constant[v], fop, nd.constant, lop, lc,
+                                                                    terms, n_terms, ws.p, me.k.p, me.c.as<uint32_t>(), lp ? me.l.as<uint64_t>() : nullptr, st);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);
+      if (hip_fail(e, "merging a slice with a value assignment")) return false;
+      me.res = SliceRef{me.k.p, me.c.as<uint32_t>(), n_new, lp ? me.l.as<uint64_t>() : nullptr};
+      return true;
+    }
     if (sp && sp->nodes[v].n_terms) {                        // a node with a program: select_kernel, or merge_many whatever its input count
       const mgc_select_term *terms = sp->terms + sp->nodes[v].first_term;
       const uint32_t n_terms = sp->nodes[v].n_terms;
@@ -1344,12 +1389,12 @@ extern "C" int mgc_db_eval_labelled(const mgc_eval_node_labelled *nodes, uint32_
 }
 
 // the same tree with selector programs (include/meryl_db.h): nodes without one take the route they take in mgc_db_eval (labels do
-// not travel) or mgc_db_eval_labelled (they do: with_labels, or a LABEL term anywhere in the tree)
-extern "C" int mgc_db_eval_selected(const mgc_eval_node_selected *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
-                                    uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
-                                    mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads) {
-  if (!nodes || n_nodes == 0 || (n_terms && !terms)) { set_err(nullptr, "mgc_db_eval_selected: bad arguments"); return MGC_EINVAL; }
-  if (label_size > 64) { set_err(nullptr, "mgc_db_eval_selected: a label has at most 64 bits"); return MGC_EINVAL; }
+// not travel) or mgc_db_eval_labelled (they do: with_labels, or a LABEL term anywhere in the tree); ap: mgc_db_eval_assigned
+static int eval_selected_impl(const char *who, const mgc_eval_node_selected *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
+                              uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
+                              mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads, const AssignPlan *ap) {
+  if (!nodes || n_nodes == 0 || (n_terms && !terms)) { set_err(nullptr, "%s: bad arguments", who); return MGC_EINVAL; }
+  if (label_size > 64) { set_err(nullptr, "%s: a label has at most 64 bits", who); return MGC_EINVAL; }
   std::vector<mgc_eval_node> base(n_nodes);
   std::vector<mgc_eval_node_labelled> lab(n_nodes);
   bool labels = with_labels != 0 || label_size != 0;
@@ -1364,5 +1409,32 @@ extern "C" int mgc_db_eval_selected(const mgc_eval_node_selected *nodes, uint32_
   }
   LabelPlan lp{lab.data(), label_size, nullptr};
   SelectPlan sp{nodes, terms, n_terms, cb};
-  return eval_impl(base.data(), n_nodes, children, n_children, root, nullptr, ctx, device, host_threads, labels ? &lp : nullptr, &sp);
+  return eval_impl(base.data(), n_nodes, children, n_children, root, nullptr, ctx, device, host_threads, labels ? &lp : nullptr, &sp, ap);
+}
+
+extern "C" int mgc_db_eval_selected(const mgc_eval_node_selected *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
+                                    uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
+                                    mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads) {
+  return eval_selected_impl("mgc_db_eval_selected", nodes, n_nodes, children, n_children, root, terms, n_terms, with_labels, label_size, cb, ctx,
+                            device, host_threads, nullptr);
+}
+
+// the same tree with value assignments (include/meryl_db.h): a node without one takes the route it takes in mgc_db_eval_selected
+extern "C" int mgc_db_eval_assigned(const mgc_eval_node_assigned *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
+                                    uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
+                                    mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads) {
+  if (!nodes || n_nodes == 0) { set_err(nullptr, "mgc_db_eval_assigned: bad arguments"); return MGC_EINVAL; }
+  std::vector<mgc_eval_node_selected> sel(n_nodes);
+  AssignPlan ap;
+  ap.assign.resize(n_nodes);
+  ap.constant.resize(n_nodes);
+  for (uint32_t i = 0; i < n_nodes; i++) {
+    sel[i].kind = nodes[i].kind; sel[i].op = nodes[i].op; sel[i].constant = nodes[i].constant; sel[i].path = nodes[i].path;
+    sel[i].first_child = nodes[i].first_child; sel[i].n_children = nodes[i].n_children;
+    sel[i].label_op = nodes[i].label_op; sel[i].reserved = 0; sel[i].label_constant = nodes[i].label_constant;
+    sel[i].first_term = nodes[i].first_term; sel[i].n_terms = nodes[i].n_terms;
+    ap.assign[i] = nodes[i].value_assign; ap.constant[i] = nodes[i].value_constant;
+  }
+  return eval_selected_impl("mgc_db_eval_assigned", sel.data(), n_nodes, children, n_children, root, terms, n_terms, with_labels, label_size, cb, ctx,
+                            device, host_threads, &ap);
 }

@@ -342,3 +342,86 @@ def evaluate_selected(tree, on_slice=None, with_labels=False, label_size=0, devi
     if rc != 0:
         msg = capi.lib().mgc_db_stream_error(None)
         raise capi.MgcError(rc, "mgc_db_eval_selected", msg.decode("utf-8", "replace") if msg else "")
+
+
+def parse_value_assign(text):
+    """what follows value= on the command line ("sub", "max#5", "#1") -> (MGC_ASSIGN_* code, constant), through
+    mgc_value_assign_parse -- the one parser, which the command line uses too"""
+    code, const = ctypes.c_int32(0), ctypes.c_uint64(0)
+    rc = capi.lib().mgc_value_assign_parse(text.encode() if isinstance(text, str) else bytes(text), ctypes.byref(code), ctypes.byref(const))
+    if rc != 0:
+        msg = capi.lib().mgc_last_error(None)
+        raise capi.MgcError(rc, "mgc_value_assign_parse", msg.decode("utf-8", "replace") if msg else "")
+    return code.value, const.value
+
+
+def value_assign_option(value):
+    """the "value" option of a node -> (MGC_ASSIGN_* code, constant): the command-line text ("sub#3"), (word, constant) with a word of
+    capi.ASSIGN_OPS or a number for the word (a constant of None: the word's default), or None (no assignment)"""
+    if value is None:
+        return capi.ASSIGN_OPS["none"], 0
+    if isinstance(value, (str, bytes)):
+        return parse_value_assign(value)
+    word, const = (value, None) if isinstance(value, int) else tuple(value)
+    if isinstance(word, str) and word not in capi.ASSIGN_OPS:
+        raise ValueError("unknown value assignment '%s'" % word)
+    code = capi.ASSIGN_OPS[word] if isinstance(word, str) else int(word)
+    if const is None:
+        const = int(capi.lib().mgc_value_default_constant(code))
+    return code, int(const) & 0xFFFFFFFFFFFFFFFF
+
+
+def build_tree_assigned(tree):
+    """build_tree_selected for mgc_db_eval_assigned: the options dict of a node also takes "value": what follows value= on the
+    command line ("sub#3") or (word, constant) (value_assign_option).
+    -> (EvalNodeAssigned array, children array, number of children, root index, SelectTerm array, number of terms)"""
+    values = []
+
+    def strip(t):
+        if isinstance(t, (str, bytes)):
+            values.append(None)
+            return t
+        t = tuple(t)
+        opts = {}
+        if t and isinstance(t[-1], dict):
+            opts = dict(t[-1])
+            t = t[:-1]
+        value = opts.pop("value", None)
+        head = 2 if t and t[0] in VALUE_WORDS else 1
+        kids = tuple(strip(a) for a in t[head:])
+        values.append(value)
+        return t[:head] + kids + ((opts,) if opts else ())
+
+    sel, kids, n_kids, root, terms, n_terms = build_tree_selected(strip(tree))
+    assert len(values) == len(sel)
+    arr = (capi.EvalNodeAssigned * len(sel))()
+    for e, b, value in zip(arr, sel, values):
+        e.kind, e.op, e.constant, e.path, e.first_child, e.n_children = b.kind, b.op, b.constant, b.path, b.first_child, b.n_children
+        e.label_op, e.label_constant, e.first_term, e.n_terms = b.label_op, b.label_constant, b.first_term, b.n_terms
+        e.value_assign, e.value_constant = value_assign_option(value)
+    return arr, kids, n_kids, root, terms, n_terms
+
+
+def evaluate_assigned(tree, on_slice=None, with_labels=False, label_size=0, device=-1, host_threads=8):
+    """evaluate_selected() for trees whose nodes may carry value assignments (mgc_db_eval_assigned): a node with {"value": ...}
+    keeps the presence rule of its operation and computes the value of a written k-mer by the assignment; k-mers whose assigned
+    value is 0 are not written, and the node's selector and a value filter see the assigned value."""
+    arr, kids, n_kids, root, terms, n_terms = build_tree_assigned(tree)
+    failure = []
+
+    def trampoline(ctx, ff, lo, hi, vals, labs, n):
+        try:
+            def take(p, dtype):
+                return np.ctypeslib.as_array(p, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype=dtype)
+            on_slice(ff, take(lo, np.uint64), take(hi, np.uint64) if hi else None, take(vals, np.uint32), take(labs, np.uint64))
+        except BaseException as e:                               # not through the C frames
+            failure.append(e)
+
+    cb = capi.EVAL_SLICE_LABELLED_CB(trampoline) if on_slice is not None else ctypes.cast(None, capi.EVAL_SLICE_LABELLED_CB)
+    rc = capi.lib().mgc_db_eval_assigned(arr, len(arr), kids, n_kids, root, terms, n_terms, int(bool(with_labels)), int(label_size), cb, None,
+                                         device, host_threads)
+    if failure:
+        raise failure[0]
+    if rc != 0:
+        msg = capi.lib().mgc_db_stream_error(None)
+        raise capi.MgcError(rc, "mgc_db_eval_assigned", msg.decode("utf-8", "replace") if msg else "")

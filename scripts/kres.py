@@ -18,6 +18,6 @@ for line in out.splitlines():
         cur = m.group(1)
         continue
     if cur and sys.argv[1] in cur:
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
+        m = re.search(r"remark:\s+(TotalSGPRs|SGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
         if m:
             print(cur[:70], m.group(1), m.group(2))

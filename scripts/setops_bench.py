@@ -22,8 +22,12 @@
     is fixed in advance; the line holds the bytes each pair moves: the plain count pass reads the keys and the emit pass keys and
     values and writes what is kept; with a VALUE term the selected count pass reads the values too (4 B more per element), and
     the selected emit writes fewer k-mers.
+  * values (leg v): merge_many with a value assignment (mgc_dev_merge_many_*_assigned, no program, no labels) -- `value=sub` and
+    `value=divzero`, whose count passes read the values (a zero result is not written), under `union` presence -- beside the same
+    run's `union-sum` (the count pass reads keys only) and `subtract` (the existing case whose count pass reads the values) through
+    mgc_dev_merge_many_*, over the `shared50` mix, N = 3 and 32, 8-byte keys.  No threshold is fixed in advance.
 
-usage: python scripts/setops_bench.py [KEYS_M] [READS_M] [--dir DIR] [--legs a,b,c,s] [--staged-meryl PATH] >> profiles/setops_bench.jsonl"""
+usage: python scripts/setops_bench.py [KEYS_M] [READS_M] [--dir DIR] [--legs a,b,c,s,v] [--staged-meryl PATH] >> profiles/setops_bench.jsonl"""
 import json
 import os
 import shutil
@@ -217,6 +221,37 @@ def selectors_leg():
         torch.cuda.empty_cache()
 
 
+def values_leg():
+    n = int(keys_m * 1_000_000)
+    g = torch.Generator(device=dev)
+    g.manual_seed(20261021)
+    for n_inputs in (3, 32):
+        ks, vs = make_inputs(n_inputs, n, "shared50", g)
+        total = sum(int(k.shape[0]) for k in ks)
+        out, line = {}, {}
+        for name, fn in (("union-sum", lambda: count.dev_merge_many(ks, vs, "union-sum")),
+                         ("subtract", lambda: count.dev_merge_many(ks, vs, "subtract")),
+                         ("value=sub", lambda: count.dev_merge_many_assigned(ks, vs, None, 28, "union", "sub", with_labels=False)),
+                         ("value=divzero", lambda: count.dev_merge_many_assigned(ks, vs, None, 28, "union", "divzero", with_labels=False))):
+            def run():
+                out[name] = fn()
+            ms, samples = timed(run)
+            line[name] = dict(ms=round(ms, 3), n_out=int(out[name][0].shape[0]), samples_ms=samples)
+        # own k-mers keep their value under both rules; a shared k-mer stays under value=sub exactly where subtract keeps it
+        sk, sc = out["subtract"][:2]
+        ak, ac = out["value=sub"][:2]
+        shared = (ak & 63) == 32
+        same = torch.equal(ak[shared], sk[(sk & 63) == 32]) and torch.equal(ac[shared], sc[(sk & 63) == 32])
+        same = same and line["value=divzero"]["n_out"] == line["union-sum"]["n_out"]          # divzero of positive values is never 0
+        out.clear()
+        base, sub = line["union-sum"]["ms"], line["subtract"]["ms"]
+        emit(what="values", n_inputs=n_inputs, key_bytes=8, mix="shared50", presence="union", keys_per_input=n, total=total, equal=bool(same),
+             legs=line, sub_over_union_sum=round(line["value=sub"]["ms"] / base, 3), sub_over_subtract=round(line["value=sub"]["ms"] / sub, 3),
+             divzero_over_union_sum=round(line["value=divzero"]["ms"] / base, 3), divzero_over_subtract=round(line["value=divzero"]["ms"] / sub, 3))
+        del ks, vs
+        torch.cuda.empty_cache()
+
+
 def wall(cmd, env=None):
     t0 = time.perf_counter()
     subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, env=env)
@@ -294,6 +329,8 @@ if "b" in legs:
     cli_leg()
 if "c" in legs:
     labels_leg()
+if "v" in legs:
+    values_leg()
 if "s" in legs:
     selectors_leg()
 if own_dir:
