@@ -41,6 +41,7 @@
 #include <string>
 #include <sys/stat.h>
 #include <thread>
+#include <type_traits>
 #include <unistd.h>
 #include <chrono>
 #include <vector>
@@ -653,13 +654,11 @@ int run_dump_index(const Operation &op) {
 bool is_tree_op(const Operation &op) { return op.kind == OP_MERGE || op.kind == OP_VALUE; }
 
 struct EvalTree {
-  std::vector<mgc_eval_node_labelled> nodes;              // (the label fields are used by a labelled evaluation only)
+  std::vector<mgc_eval_node_assigned> nodes;              // the widest public node; run_tree narrows it for the entry point it calls
   std::vector<std::vector<uint32_t>>  kids;
   std::string                         first_leaf;
   bool                                label_words = false;    // an operation of the tree carries label=
   std::vector<mgc_select_term>        terms;                  // the selector programs of all nodes, one after the other
-  std::vector<std::pair<uint32_t, uint32_t>> term_range;      // per node: first term, number of terms
-  std::vector<std::pair<int, uint64_t>> assign;               // per node: MGC_ASSIGN_*, constant
   bool                                value_words = false;    // an operation of the tree carries value=
   uint32_t                            leaf_label_size = 0;    // the largest label size among the leaves
 };
@@ -730,17 +729,15 @@ uint32_t add_tree_node(const Globals &g, const std::vector<Operation> &ops, int 
       mdb_reader_close(rd);
       t.leaf_label_size = std::max(t.leaf_label_size, info.label_size);
     }
-    mgc_eval_node_labelled nd;
+    mgc_eval_node_assigned nd;
     memset(&nd, 0, sizeof(nd));
     nd.kind = MGC_NODE_DATABASE;
     nd.path = in.child >= 0 ? ops[in.child].output.c_str() : in.path.c_str();
     t.nodes.push_back(nd);
-    t.term_range.emplace_back(0u, 0u);
-    t.assign.emplace_back(MGC_ASSIGN_NONE, 0ull);
     t.kids.emplace_back();
     kids.push_back((uint32_t)t.nodes.size() - 1);
   }
-  mgc_eval_node_labelled nd;
+  mgc_eval_node_assigned nd;
   memset(&nd, 0, sizeof(nd));
   nd.path = op.output.empty() ? nullptr : op.output.c_str();
   nd.label_op = op.label_op;
@@ -762,18 +759,18 @@ uint32_t add_tree_node(const Globals &g, const std::vector<Operation> &ops, int 
               op.output.empty() ? "" : " into '", op.output.c_str(), op.output.empty() ? "" : "'");
   }
   // the selector words are decoded once the number of inputs is known (`input:all`, `@n`), by the library's one parser
-  std::pair<uint32_t, uint32_t> range((uint32_t)t.terms.size(), 0u);
+  nd.first_term = (uint32_t)t.terms.size();
   if (!op.select_words.empty()) {
     std::vector<const char *> words;
     for (const std::string &w : op.select_words) words.push_back(w.c_str());
     mgc_select_term terms[MGC_SELECT_MAX_TERMS];
-    if (mgc_select_parse(words.data(), (uint32_t)words.size(), (uint32_t)kids.size(), terms, MGC_SELECT_MAX_TERMS, &range.second) != MGC_OK)
+    if (mgc_select_parse(words.data(), (uint32_t)words.size(), (uint32_t)kids.size(), terms, MGC_SELECT_MAX_TERMS, &nd.n_terms) != MGC_OK)
       die("ERROR: %s", ("operation '" + op.word + "': " + mgc_last_error(nullptr)).c_str());
-    t.terms.insert(t.terms.end(), terms, terms + range.second);
+    t.terms.insert(t.terms.end(), terms, terms + nd.n_terms);
   }
+  nd.value_assign = op.value_assign;
+  nd.value_constant = op.value_constant;
   t.nodes.push_back(nd);
-  t.term_range.push_back(range);
-  t.assign.emplace_back(op.value_assign, op.value_constant);
   t.value_words = t.value_words || op.has_value_assign;
   t.kids.push_back(kids);
   return (uint32_t)t.nodes.size() - 1;
@@ -786,6 +783,21 @@ void print_slice(void *ctx, uint32_t, const uint64_t *lo, const uint64_t *hi, co
 void print_slice_labelled(void *ctx, uint32_t, const uint64_t *lo, const uint64_t *hi, const uint32_t *values, const uint64_t *labels, uint64_t n) {
   const PrintCtx *pc = static_cast<PrintCtx *>(ctx);
   print_kmers(pc->k, pc->label_size, lo, hi, values, labels, n);
+}
+
+// the nodes as a narrower public struct: the fields it names, copied
+template <typename T>
+std::vector<T> narrowed(const std::vector<mgc_eval_node_assigned> &nodes) {
+  std::vector<T> out(nodes.size());
+  for (size_t v = 0; v < nodes.size(); v++) {
+    const mgc_eval_node_assigned &s = nodes[v];
+    T &d = out[v];
+    memset(&d, 0, sizeof(d));
+    d.kind = s.kind; d.op = s.op; d.constant = s.constant; d.path = s.path; d.first_child = s.first_child; d.n_children = s.n_children;
+    if constexpr (!std::is_same<T, mgc_eval_node>::value) { d.label_op = s.label_op; d.label_constant = s.label_constant; }
+    if constexpr (std::is_same<T, mgc_eval_node_selected>::value) { d.first_term = s.first_term; d.n_terms = s.n_terms; }
+  }
+  return out;
 }
 
 // the operation tree under ops[root] (paths point into `ops`, which outlives the call)
@@ -810,54 +822,23 @@ int run_tree(const Globals &g, const std::vector<Operation> &ops, int root, bool
   // with labels only when something asks for them: -l, a label= word, or a leaf that stores labels; the outputs (and the
   // label column `print` adds) take -l bits, or the largest label size among the leaves
   const bool with_labels = g.label_size_given || t.label_words || t.leaf_label_size;
-  if (t.value_words) {                                         // a value= somewhere: the same tree through mgc_db_eval_assigned
-    std::vector<mgc_eval_node_assigned> asg(t.nodes.size());
-    for (size_t v = 0; v < t.nodes.size(); v++) {
-      memset(&asg[v], 0, sizeof(asg[v]));
-      asg[v].kind = t.nodes[v].kind; asg[v].op = t.nodes[v].op; asg[v].constant = t.nodes[v].constant; asg[v].path = t.nodes[v].path;
-      asg[v].first_child = t.nodes[v].first_child; asg[v].n_children = t.nodes[v].n_children;
-      asg[v].label_op = t.nodes[v].label_op; asg[v].label_constant = t.nodes[v].label_constant;
-      asg[v].first_term = t.term_range[v].first; asg[v].n_terms = t.term_range[v].second;
-      asg[v].value_assign = t.assign[v].first; asg[v].value_constant = t.assign[v].second;
-    }
-    if (with_labels) pc.label_size = g.label_size_given && g.label_size ? g.label_size : t.leaf_label_size;
-    if (mgc_db_eval_assigned(asg.data(), (uint32_t)asg.size(), children.data(), (uint32_t)children.size(), r, t.terms.data(), (uint32_t)t.terms.size(),
-                             with_labels ? 1 : 0, g.label_size_given ? g.label_size : 0, print ? print_slice_labelled : nullptr, &pc, -1,
-                             (int)g.threads) != MGC_OK)
-      die("ERROR: %s", mgc_db_stream_error(nullptr));
-    return 0;
-  }
-  if (!t.terms.empty()) {                                      // a selector somewhere: the same tree through mgc_db_eval_selected
-    std::vector<mgc_eval_node_selected> sel(t.nodes.size());
-    for (size_t v = 0; v < t.nodes.size(); v++) {
-      memset(&sel[v], 0, sizeof(sel[v]));
-      sel[v].kind = t.nodes[v].kind; sel[v].op = t.nodes[v].op; sel[v].constant = t.nodes[v].constant; sel[v].path = t.nodes[v].path;
-      sel[v].first_child = t.nodes[v].first_child; sel[v].n_children = t.nodes[v].n_children;
-      sel[v].label_op = t.nodes[v].label_op; sel[v].label_constant = t.nodes[v].label_constant;
-      sel[v].first_term = t.term_range[v].first; sel[v].n_terms = t.term_range[v].second;
-    }
-    if (with_labels) pc.label_size = g.label_size_given && g.label_size ? g.label_size : t.leaf_label_size;
-    if (mgc_db_eval_selected(sel.data(), (uint32_t)sel.size(), children.data(), (uint32_t)children.size(), r, t.terms.data(), (uint32_t)t.terms.size(),
-                             with_labels ? 1 : 0, g.label_size_given ? g.label_size : 0, print ? print_slice_labelled : nullptr, &pc, -1,
-                             (int)g.threads) != MGC_OK)
-      die("ERROR: %s", mgc_db_stream_error(nullptr));
-    return 0;
-  }
-  if (with_labels) {
-    pc.label_size = g.label_size_given && g.label_size ? g.label_size : t.leaf_label_size;
-    if (mgc_db_eval_labelled(t.nodes.data(), (uint32_t)t.nodes.size(), children.data(), (uint32_t)children.size(), r,
-                             g.label_size_given ? g.label_size : 0, print ? print_slice_labelled : nullptr, &pc, -1, (int)g.threads) != MGC_OK)
-      die("ERROR: %s", mgc_db_stream_error(nullptr));
-    return 0;
-  }
-  std::vector<mgc_eval_node> plain(t.nodes.size());
-  for (size_t v = 0; v < t.nodes.size(); v++) {
-    plain[v].kind = t.nodes[v].kind; plain[v].op = t.nodes[v].op; plain[v].constant = t.nodes[v].constant; plain[v].path = t.nodes[v].path;
-    plain[v].first_child = t.nodes[v].first_child; plain[v].n_children = t.nodes[v].n_children;
-  }
-  if (mgc_db_eval(plain.data(), (uint32_t)plain.size(), children.data(), (uint32_t)children.size(), r, print ? print_slice : nullptr, &pc,
-                  -1, (int)g.threads) != MGC_OK)
-    die("ERROR: %s", mgc_db_stream_error(nullptr));
+  const uint32_t n_nodes = (uint32_t)t.nodes.size(), n_children = (uint32_t)children.size(), n_terms = (uint32_t)t.terms.size();
+  const uint32_t label_size = g.label_size_given ? g.label_size : 0;
+  if (with_labels) pc.label_size = g.label_size_given && g.label_size ? g.label_size : t.leaf_label_size;
+  int rc;
+  if (t.value_words)                                           // a value= somewhere: the tree through mgc_db_eval_assigned
+    rc = mgc_db_eval_assigned(t.nodes.data(), n_nodes, children.data(), n_children, r, t.terms.data(), n_terms, with_labels ? 1 : 0, label_size,
+                              print ? print_slice_labelled : nullptr, &pc, -1, (int)g.threads);
+  else if (!t.terms.empty())                                   // a selector somewhere: the same tree through mgc_db_eval_selected
+    rc = mgc_db_eval_selected(narrowed<mgc_eval_node_selected>(t.nodes).data(), n_nodes, children.data(), n_children, r, t.terms.data(), n_terms,
+                              with_labels ? 1 : 0, label_size, print ? print_slice_labelled : nullptr, &pc, -1, (int)g.threads);
+  else if (with_labels)
+    rc = mgc_db_eval_labelled(narrowed<mgc_eval_node_labelled>(t.nodes).data(), n_nodes, children.data(), n_children, r, label_size,
+                              print ? print_slice_labelled : nullptr, &pc, -1, (int)g.threads);
+  else
+    rc = mgc_db_eval(narrowed<mgc_eval_node>(t.nodes).data(), n_nodes, children.data(), n_children, r, print ? print_slice : nullptr, &pc, -1,
+                     (int)g.threads);
+  if (rc != MGC_OK) die("ERROR: %s", mgc_db_stream_error(nullptr));
   return 0;
 }
 

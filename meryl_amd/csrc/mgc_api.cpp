@@ -294,7 +294,8 @@ extern "C" int mgc_dev_select_count(const void *d_keys, const uint32_t *d_values
                                     void *d_ws, size_t ws_bytes, uint64_t *n_out, void *stream) {
   if (!n_out || !d_ws || ws_bytes < mgc::select_workspace_bytes(n) || (n && (!d_keys || !d_values)) || (key_words != 1 && key_words != 2) ||
       value_op < 0 || value_op > MGC_VALUE_MODULO) return MGC_EINVAL;
-  hipError_t e = mgc::launch_select_count(d_keys, d_values, nullptr, n, key_words, value_op, constant, d_ws, (hipStream_t)stream);
+  hipError_t e = mgc::launch_select(false, mgc::SelectInput{d_keys, d_values, nullptr, nullptr, n, key_words}, value_op, constant, mgc::PassRule(), d_ws, nullptr, nullptr,
+                                    (hipStream_t)stream);
   if (e != hipSuccess) return hip_rc(e, "select_count");
   return hip_rc(mgc::merge_read_total(d_ws, n_out, (hipStream_t)stream), "select_count sync");
 }
@@ -303,8 +304,8 @@ extern "C" int mgc_dev_select_emit(const void *d_keys, const uint32_t *d_values,
                                    void *d_ws, size_t ws_bytes, void *d_keys_out, uint32_t *d_values_out, void *stream) {
   if (!d_ws || ws_bytes < mgc::select_workspace_bytes(n) || (n && (!d_keys || !d_values)) || (key_words != 1 && key_words != 2) ||
       value_op < 0 || value_op > MGC_VALUE_MODULO) return MGC_EINVAL;
-  return hip_rc(mgc::launch_select_emit(d_keys, d_values, nullptr, n, key_words, value_op, constant, d_ws, d_keys_out, d_values_out,
-                                        (hipStream_t)stream), "select_emit");
+  return hip_rc(mgc::launch_select(true, mgc::SelectInput{d_keys, d_values, nullptr, nullptr, n, key_words}, value_op, constant, mgc::PassRule(), d_ws, d_keys_out,
+                                   d_values_out, (hipStream_t)stream), "select_emit");
 }
 
 extern "C" int mgc_dev_merge_emit(const void *dA, const uint32_t *cA, uint64_t na, const void *dB, const uint32_t *cB, uint64_t nb,
@@ -336,7 +337,8 @@ extern "C" int mgc_dev_merge_many_count(const void *const *d_keys, const uint32_
                                         uint32_t key_words, int op, void *d_ws, size_t ws_bytes, uint64_t *n_out, void *stream) {
   if (!n_out || !d_ws || !merge_many_args_ok(d_keys, d_values, n, n_inputs, key_words, op) ||
       ws_bytes < mgc::merge_many_workspace_bytes(n, n_inputs, key_words)) return MGC_EINVAL;
-  hipError_t e = mgc::launch_merge_many_count(d_keys, d_values, n, n_inputs, key_words, op, d_ws, (hipStream_t)stream);
+  hipError_t e = mgc::launch_merge_many(false, mgc::MergeManyInputs{d_keys, d_values, nullptr, n, n_inputs, key_words}, op, mgc::PassRule(), d_ws, nullptr, nullptr,
+                                        (hipStream_t)stream);
   if (e != hipSuccess) return hip_rc(e, "merge_many_count");
   return hip_rc(mgc::merge_read_total(d_ws, n_out, (hipStream_t)stream), "merge_many_count sync");
 }
@@ -346,8 +348,8 @@ extern "C" int mgc_dev_merge_many_emit(const void *const *d_keys, const uint32_t
                                        void *stream) {
   if (!d_ws || !merge_many_args_ok(d_keys, d_values, n, n_inputs, key_words, op) ||
       ws_bytes < mgc::merge_many_workspace_bytes(n, n_inputs, key_words)) return MGC_EINVAL;
-  return hip_rc(mgc::launch_merge_many_emit(d_keys, d_values, n, n_inputs, key_words, op, d_ws, d_keys_out, d_values_out,
-                                            (hipStream_t)stream), "merge_many_emit");
+  return hip_rc(mgc::launch_merge_many(true, mgc::MergeManyInputs{d_keys, d_values, nullptr, n, n_inputs, key_words}, op, mgc::PassRule(), d_ws, d_keys_out,
+                                       d_values_out, (hipStream_t)stream), "merge_many_emit");
 }
 
 // ---- labels (include/meryl_gpu_count.h: MGC_LABEL_*) --------------------------------------------------------------------------
@@ -367,12 +369,14 @@ extern "C" int mgc_dev_merge_many_emit_labelled(const void *const *d_keys, const
     set_err(nullptr, "mgc_dev_merge_many_emit_labelled: label=invert takes one input (merylOpCompute.C:368-371)");
     return MGC_EINVAL;
   }
+  const mgc::MergeManyInputs in{d_keys, d_values, d_labels, n, n_inputs, key_words};
+  mgc::PassRule rule;
+  rule.lop = lop; rule.lc = label_constant; rule.out_labs = d_labels_out;
   if (n_inputs == 1) {                                               // the count step refuses one input: its pass runs here
-    hipError_t e = mgc::launch_merge_many_count(d_keys, d_values, n, 1, key_words, op, d_ws, (hipStream_t)stream, true);
+    hipError_t e = mgc::launch_merge_many(false, in, op, rule, d_ws, nullptr, nullptr, (hipStream_t)stream);
     if (e != hipSuccess) return hip_rc(e, "merge_many_count (one input)");
   }
-  return hip_rc(mgc::launch_merge_many_emit_labelled(d_keys, d_values, d_labels, n, n_inputs, key_words, op, lop, label_constant, d_ws,
-                                                     d_keys_out, d_values_out, d_labels_out, (hipStream_t)stream), "merge_many_emit_labelled");
+  return hip_rc(mgc::launch_merge_many(true, in, op, rule, d_ws, d_keys_out, d_values_out, (hipStream_t)stream), "merge_many_emit_labelled");
 }
 
 extern "C" int mgc_dev_select_emit_labelled(const void *d_keys, const uint32_t *d_values, const uint64_t *d_labels, uint64_t n,
@@ -383,8 +387,10 @@ extern "C" int mgc_dev_select_emit_labelled(const void *d_keys, const uint32_t *
       (key_words != 1 && key_words != 2) || value_op < 0 || value_op > MGC_VALUE_MODULO) return MGC_EINVAL;
   const int lop = mgc::label_kernel_op(false, value_op, label_op);
   if (lop < 0) { set_err(nullptr, "mgc_dev_select_emit_labelled: unknown label operation %d", label_op); return MGC_EINVAL; }
-  return hip_rc(mgc::launch_select_emit_labelled(d_keys, d_values, d_labels, n, key_words, value_op, constant, lop, label_constant, d_ws,
-                                                 d_keys_out, d_values_out, d_labels_out, (hipStream_t)stream), "select_emit_labelled");
+  mgc::PassRule rule;
+  rule.lop = lop; rule.lc = label_constant; rule.out_labs = d_labels_out;
+  return hip_rc(mgc::launch_select(true, mgc::SelectInput{d_keys, d_values, nullptr, d_labels, n, key_words}, value_op, constant, rule, d_ws, d_keys_out,
+                                   d_values_out, (hipStream_t)stream), "select_emit_labelled");
 }
 
 // ---- selectors (include/meryl_gpu_count.h: mgc_select_term; the evaluator, the checks and the parser are mgc_selector.hpp) ------
@@ -414,6 +420,15 @@ static int selected_args(const char *who, bool is_merge, int op, uint32_t n_inpu
   return MGC_OK;
 }
 
+// the rule of a *_selected / *_assigned launch: the label code, the program (possibly empty), the assignment's kernel code
+static mgc::PassRule selected_rule(int lop, uint64_t label_constant, const mgc_select_term *terms, uint32_t n_terms, uint32_t k, uint64_t *d_labels_out,
+                                   int vop = 0, uint64_t value_constant = 0) {
+  mgc::PassRule r;
+  r.lop = lop; r.lc = label_constant; r.select = true; r.terms = terms; r.n_terms = n_terms; r.k = k;
+  r.vop = vop; r.vc = value_constant; r.out_labs = d_labels_out;
+  return r;
+}
+
 extern "C" int mgc_dev_merge_many_count_selected(const void *const *d_keys, const uint32_t *const *d_values, const uint64_t *const *d_labels,
                                                  const uint64_t *n, uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int label_op,
                                                  uint64_t label_constant, const mgc_select_term *terms, uint32_t n_terms, void *d_ws,
@@ -423,8 +438,8 @@ extern "C" int mgc_dev_merge_many_count_selected(const void *const *d_keys, cons
   int lop = 0;
   const int rc = selected_args("mgc_dev_merge_many_count_selected", true, op, n_inputs, key_words, k, label_op, terms, n_terms, &lop);
   if (rc != MGC_OK) return rc;
-  hipError_t e = mgc::launch_merge_many_count_selected(d_keys, d_values, d_labels, n, n_inputs, key_words, k, op, lop, label_constant, terms, n_terms,
-                                                       d_ws, (hipStream_t)stream);
+  hipError_t e = mgc::launch_merge_many(false, mgc::MergeManyInputs{d_keys, d_values, d_labels, n, n_inputs, key_words}, op,
+                                        selected_rule(lop, label_constant, terms, n_terms, k, nullptr), d_ws, nullptr, nullptr, (hipStream_t)stream);
   if (e != hipSuccess) return hip_rc(e, "merge_many_count_selected");
   return hip_rc(mgc::merge_read_total(d_ws, n_out, (hipStream_t)stream), "merge_many_count_selected sync");
 }
@@ -438,8 +453,9 @@ extern "C" int mgc_dev_merge_many_emit_selected(const void *const *d_keys, const
   int lop = 0;
   const int rc = selected_args("mgc_dev_merge_many_emit_selected", true, op, n_inputs, key_words, k, label_op, terms, n_terms, &lop);
   if (rc != MGC_OK) return rc;
-  return hip_rc(mgc::launch_merge_many_emit_selected(d_keys, d_values, d_labels, n, n_inputs, key_words, k, op, lop, label_constant, terms, n_terms,
-                                                     d_ws, d_keys_out, d_values_out, d_labels_out, (hipStream_t)stream), "merge_many_emit_selected");
+  return hip_rc(mgc::launch_merge_many(true, mgc::MergeManyInputs{d_keys, d_values, d_labels, n, n_inputs, key_words}, op,
+                                       selected_rule(lop, label_constant, terms, n_terms, k, d_labels_out), d_ws, d_keys_out, d_values_out,
+                                       (hipStream_t)stream), "merge_many_emit_selected");
 }
 
 // ---- value assignment (include/meryl_gpu_count.h: MGC_ASSIGN_*; the rule and the parser are mgc_value.hpp) ----------------------
@@ -472,8 +488,9 @@ extern "C" int mgc_dev_merge_many_count_assigned(const void *const *d_keys, cons
   int vop = 0, lop = 0;
   const int rc = assigned_args("mgc_dev_merge_many_count_assigned", op, n_inputs, key_words, k, value_assign, label_op, terms, n_terms, &vop, &lop);
   if (rc != MGC_OK) return rc;
-  hipError_t e = mgc::launch_merge_many_count_assigned(d_keys, d_values, d_labels, n, n_inputs, key_words, k, op, vop, value_constant, -1, 0, lop,
-                                                       label_constant, terms, n_terms, d_ws, (hipStream_t)stream);
+  hipError_t e = mgc::launch_merge_many(false, mgc::MergeManyInputs{d_keys, d_values, d_labels, n, n_inputs, key_words}, op,
+                                        selected_rule(lop, label_constant, terms, n_terms, k, nullptr, vop, value_constant), d_ws, nullptr, nullptr,
+                                        (hipStream_t)stream);
   if (e != hipSuccess) return hip_rc(e, "merge_many_count_assigned");
   return hip_rc(mgc::merge_read_total(d_ws, n_out, (hipStream_t)stream), "merge_many_count_assigned sync");
 }
@@ -488,9 +505,9 @@ extern "C" int mgc_dev_merge_many_emit_assigned(const void *const *d_keys, const
   int vop = 0, lop = 0;
   const int rc = assigned_args("mgc_dev_merge_many_emit_assigned", op, n_inputs, key_words, k, value_assign, label_op, terms, n_terms, &vop, &lop);
   if (rc != MGC_OK) return rc;
-  return hip_rc(mgc::launch_merge_many_emit_assigned(d_keys, d_values, d_labels, n, n_inputs, key_words, k, op, vop, value_constant, -1, 0, lop,
-                                                     label_constant, terms, n_terms, d_ws, d_keys_out, d_values_out, d_labels_out,
-                                                     (hipStream_t)stream), "merge_many_emit_assigned");
+  return hip_rc(mgc::launch_merge_many(true, mgc::MergeManyInputs{d_keys, d_values, d_labels, n, n_inputs, key_words}, op,
+                                       selected_rule(lop, label_constant, terms, n_terms, k, d_labels_out, vop, value_constant), d_ws, d_keys_out,
+                                       d_values_out, (hipStream_t)stream), "merge_many_emit_assigned");
 }
 
 extern "C" int mgc_dev_select_count_selected(const void *d_keys, const uint32_t *d_values, const uint64_t *d_labels, uint64_t n, uint32_t key_words,
@@ -502,8 +519,8 @@ extern "C" int mgc_dev_select_count_selected(const void *d_keys, const uint32_t 
   int lop = 0;
   const int rc = selected_args("mgc_dev_select_count_selected", false, value_op, 1, key_words, k, label_op, terms, n_terms, &lop);
   if (rc != MGC_OK) return rc;
-  hipError_t e = mgc::launch_select_count_selected(d_keys, d_values, d_labels, n, key_words, k, value_op, constant, lop, label_constant, terms, n_terms,
-                                                   d_ws, (hipStream_t)stream);
+  hipError_t e = mgc::launch_select(false, mgc::SelectInput{d_keys, d_values, nullptr, d_labels, n, key_words}, value_op, constant,
+                                    selected_rule(lop, label_constant, terms, n_terms, k, nullptr), d_ws, nullptr, nullptr, (hipStream_t)stream);
   if (e != hipSuccess) return hip_rc(e, "select_count_selected");
   return hip_rc(mgc::merge_read_total(d_ws, n_out, (hipStream_t)stream), "select_count_selected sync");
 }
@@ -517,8 +534,9 @@ extern "C" int mgc_dev_select_emit_selected(const void *d_keys, const uint32_t *
   int lop = 0;
   const int rc = selected_args("mgc_dev_select_emit_selected", false, value_op, 1, key_words, k, label_op, terms, n_terms, &lop);
   if (rc != MGC_OK) return rc;
-  return hip_rc(mgc::launch_select_emit_selected(d_keys, d_values, d_labels, n, key_words, k, value_op, constant, lop, label_constant, terms, n_terms,
-                                                 d_ws, d_keys_out, d_values_out, d_labels_out, (hipStream_t)stream), "select_emit_selected");
+  return hip_rc(mgc::launch_select(true, mgc::SelectInput{d_keys, d_values, nullptr, d_labels, n, key_words}, value_op, constant,
+                                   selected_rule(lop, label_constant, terms, n_terms, k, d_labels_out), d_ws, d_keys_out, d_values_out,
+                                   (hipStream_t)stream), "select_emit_selected");
 }
 
 extern "C" int mgc_dev_decode_blocks(const void *d_file, const void *d_blocks, uint64_t n_blocks, uint32_t suffix_size, uint32_t label_size,

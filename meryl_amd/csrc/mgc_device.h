@@ -1,4 +1,4 @@
-// mgc_device.h -- internal launch interface between the host layer (mgc_api / mgc_count / mgc_stream / mgc_runs / mgc_node .cpp)
+// mgc_device.h -- internal launch interface between the host layer (mgc_api / mgc_count / mgc_stream / mgc_eval / mgc_runs / mgc_node .cpp)
 // and the gfx950 kernels (mgc_kmer / mgc_sort / mgc_scan / mgc_finish / mgc_misc / mgc_parse / mgc_encode / mgc_decode / mgc_merge
 // .hip; mgc_lookup / mgc_filter / mgc_import .hip have headers of their own).  Not installed.
 #pragma once
@@ -289,58 +289,37 @@ hipError_t launch_merge_count(const void *dA, uint64_t na, const void *dB, uint6
 hipError_t merge_read_total(const void *d_ws, uint64_t *n_out, hipStream_t st);       // synchronises the stream
 hipError_t launch_merge_emit(const void *dA, const uint32_t *cA, uint64_t na, const void *dB, const uint32_t *cB, uint64_t nb,
                              uint32_t key_words, int op, void *d_ws, void *d_out_keys, uint32_t *d_out_counts, hipStream_t st);
-// ---- merge of 2..32 sorted distinct (k-mer, value) streams in one pass pair (mgc_merge_many.hip) ----------------
-// op as above, and 10 union (the value is the number of inputs holding the k-mer); keys / vals / n: host arrays of device
-// pointers and lengths; equal to the left fold of the two-input merge over the same inputs, element by element
+// ---- one description of what a count / emit pass pair does beyond its operation (mgc_merge_many.hip, mgc_merge.hip) ----------
+// The same rule goes to both passes (out_labs may be set in between, once the output length is known); the launcher picks the
+// kernel instantiation from it (pass_inst, mgc_route.hpp) so that the count pass decides exactly what the emit pass writes.
+struct PassRule {
+  int       lop = 0;                       // label operation, a kernel code (label_kernel_op, mgc_label.hpp): read with a program or out_labs
+  uint64_t  lc = 0;                        //   and its constant
+  bool      select = false;                // a selector program (mgc_selector.hpp), possibly empty, is ANDed onto the operation's rule
+  const ::mgc_select_term *terms = nullptr;  // checked by the caller (select_check)
+  uint32_t  n_terms = 0, k = 0;            //   k: the k-mer size (BASES terms)
+  int       vop = 0;                       // merge_many: value assignment, a kernel code (value_kernel_op, mgc_value.hpp; 0: VOP_NONE, the
+  uint64_t  vc = 0;                        //   operation's own value); its constant.  An assignment implies `select`.
+  int       fop = -1;                      // merge_many, with an assignment: the value filter of a filter node tested on the assigned
+  uint64_t  fc = 0;                        //   value (fop < 0: none); its threshold
+  uint64_t *out_labs = nullptr;            // emit: where the labels of the written k-mers go (null: none are written)
+};
+// ---- merge of 1..32 sorted distinct (k-mer, value) streams in one pass pair (mgc_merge_many.hip) ----------------
+// op as above, and 10 union (the value is the number of inputs holding the k-mer); keys / vals / labs / n: host arrays of device
+// pointers and lengths (labs, or an entry of it, null: all zeros); without a rule equal to the left fold of the two-input merge over
+// the same inputs, element by element.  count (emit false) -> merge_read_total -> emit, like the two-input merge.
+struct MergeManyInputs { const void *const *keys; const uint32_t *const *vals; const uint64_t *const *labs; const uint64_t *n; uint32_t count, key_words; };
 uint32_t   merge_many_tile(uint32_t key_words);
 size_t     merge_many_workspace_bytes(const uint64_t *n, uint32_t n_inputs, uint32_t key_words);
-hipError_t launch_merge_many_count(const void *const *keys, const uint32_t *const *vals, const uint64_t *n, uint32_t n_inputs,
-                                   uint32_t key_words, int op, void *d_ws, hipStream_t st, bool allow_one = false);
-hipError_t launch_merge_many_emit(const void *const *keys, const uint32_t *const *vals, const uint64_t *n, uint32_t n_inputs,
-                                  uint32_t key_words, int op, void *d_ws, void *d_out_keys, uint32_t *d_out_vals, hipStream_t st);
-// the same emit with labels (MergeManyDesc::labs; a null entry = all zeros): outL[o] = the label operation `lop` (a kernel code,
-// label_kernel_op, mgc_label.hpp) with constant `lc` over the labels and values of the inputs that hold k-mer o.  n_inputs may be 1 here,
-// and launch_merge_many_count takes one input when `allow_one` is set (the labelled evaluation's one-input merge nodes).
-hipError_t launch_merge_many_emit_labelled(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs,
-                                           const uint64_t *n, uint32_t n_inputs, uint32_t key_words, int op, int lop, uint64_t lc, void *d_ws,
-                                           void *d_out_keys, uint32_t *d_out_vals, uint64_t *d_out_labs, hipStream_t st);
+hipError_t launch_merge_many(bool emit, const MergeManyInputs &in, int op, const PassRule &rule, void *d_ws, void *d_out_keys,
+                             uint32_t *d_out_vals, hipStream_t st);
 // one stream through a value transform (fop 0..5 filters against `constant`: less-than, greater-than, at-least, at-most, equal-to,
-// not-equal-to; 6..11 arithmetic: increase, decrease, multiply, divide, divide-round, modulo; 12: keep where d_flags[i] == 1),
-// k-mers whose new value is 0 dropped; two passes like the merge (count -> merge_read_total -> emit)
+// not-equal-to; 6..11 arithmetic: increase, decrease, multiply, divide, divide-round, modulo; 12: keep where flags[i] == 1, without
+// a program or labels only), k-mers whose new value is 0 dropped; the same two passes.  labs null: all zeros.
+struct SelectInput { const void *keys; const uint32_t *vals; const uint32_t *flags; const uint64_t *labs; uint64_t n; uint32_t key_words; };
 size_t     select_workspace_bytes(uint64_t n);
-hipError_t launch_select_count(const void *d_keys, const uint32_t *d_vals, const uint32_t *d_flags, uint64_t n, uint32_t key_words, int fop,
-                               uint64_t constant, void *d_ws, hipStream_t st);
-hipError_t launch_select_emit(const void *d_keys, const uint32_t *d_vals, const uint32_t *d_flags, uint64_t n, uint32_t key_words, int fop,
-                              uint64_t constant, void *d_ws, void *d_out_keys, uint32_t *d_out_vals, hipStream_t st);
-// the emit with labels: d_labs (null = all zeros) follow the kept k-mers, through label operation `lop` (kernel code) with one active input
-hipError_t launch_select_emit_labelled(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words, int fop,
-                                       uint64_t constant, int lop, uint64_t lc, void *d_ws, void *d_out_keys, uint32_t *d_out_vals,
-                                       uint64_t *d_out_labs, hipStream_t st);
-// ---- the merge and the value transform with a selector program (mgc_selector.hpp; include/meryl_gpu_count.h: mgc_select_term) ----
-// terms: checked by the caller (select_check); k: the k-mer size (BASES terms); lop: a kernel code; labs / its entries / d_out_labs may
-// be null.  The count pass decides exactly what the emit pass writes; one input is accepted.
-hipError_t launch_merge_many_count_selected(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
-                                            uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int lop, uint64_t lc,
-                                            const ::mgc_select_term *terms, uint32_t n_terms, void *d_ws, hipStream_t st);
-hipError_t launch_merge_many_emit_selected(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
-                                           uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int lop, uint64_t lc,
-                                           const ::mgc_select_term *terms, uint32_t n_terms, void *d_ws, void *d_out_keys, uint32_t *d_out_vals,
-                                           uint64_t *d_out_labs, hipStream_t st);
-// the same with a value assignment (mgc_value.hpp): vop a kernel code (VOP_NONE: the selected launch, unless a filter is given), vc its
-// constant; fop / fc: the value filter of a filter node tested on the assigned value (fop < 0: none)
-hipError_t launch_merge_many_count_assigned(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
-                                            uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int vop, uint64_t vc, int fop, uint64_t fc,
-                                            int lop, uint64_t lc, const ::mgc_select_term *terms, uint32_t n_terms, void *d_ws, hipStream_t st);
-hipError_t launch_merge_many_emit_assigned(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
-                                           uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int vop, uint64_t vc, int fop, uint64_t fc,
-                                           int lop, uint64_t lc, const ::mgc_select_term *terms, uint32_t n_terms, void *d_ws, void *d_out_keys,
-                                           uint32_t *d_out_vals, uint64_t *d_out_labs, hipStream_t st);
-hipError_t launch_select_count_selected(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words, uint32_t k,
-                                        int fop, uint64_t constant, int lop, uint64_t lc, const ::mgc_select_term *terms, uint32_t n_terms,
-                                        void *d_ws, hipStream_t st);
-hipError_t launch_select_emit_selected(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words, uint32_t k,
-                                       int fop, uint64_t constant, int lop, uint64_t lc, const ::mgc_select_term *terms, uint32_t n_terms,
-                                       void *d_ws, void *d_out_keys, uint32_t *d_out_vals, uint64_t *d_out_labs, hipStream_t st);
+hipError_t launch_select(bool emit, const SelectInput &in, int fop, uint64_t constant, const PassRule &rule, void *d_ws, void *d_out_keys,
+                         uint32_t *d_out_vals, hipStream_t st);
 hipError_t launch_fill_u32(uint32_t *d, uint64_t n, uint32_t v, hipStream_t st);
 // *d_out <- 1 + index of the last '.' in bases[0, n), 0 if none
 hipError_t launch_last_breaker(const uint8_t *d_bases, uint64_t n, uint64_t *d_out, hipStream_t st);

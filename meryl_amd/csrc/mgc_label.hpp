@@ -1,7 +1,7 @@
 // mgc_label.hpp -- the label of a written k-mer from the labels and values of the inputs that hold it: meryl2's
 // merylOpCompute::findOutputLabel (src/meryl2/merylOpCompute.C:286-395); the rules, with the line each comes from, are in
 // include/meryl_gpu_count.h (MGC_LABEL_*).  Shared by the kernels (mgc_merge_many.hip, mgc_merge.hip through mgc_common.hpp),
-// the host code that resolves an operation's label word (mgc_api.cpp, mgc_stream.cpp) and a stand-alone host program
+// the host code that resolves an operation's label word (mgc_api.cpp, mgc_eval.cpp) and a stand-alone host program
 // (tests/host/label_host.cpp): plain C++, no HIP header needed.
 #pragma once
 #include <cstdint>

@@ -15,6 +15,7 @@
 // looks at the next B candidate, the B element at the previous A element; no cross-thread exchange is needed.  Two passes
 // (count heads per tile, scan, emit): HBM-bound, (8|16)+4 B read per input element per pass + the output.
 #include "mgc_common.hpp"
+#include "mgc_route.hpp"
 #include "mgc_selector.hpp"
 
 namespace mgc {
@@ -300,103 +301,53 @@ size_t select_workspace_bytes(uint64_t n) {
   const uint64_t t = select_tiles(n);
   return (size_t)(8 + t + 1 + scan_scratch_elems(t + 1)) * sizeof(u64) + 256;
 }
-// pass 1: the number of k-mers kept lands at ws[0] (merge_read_total reads it)
-hipError_t launch_select_count(const void *d_keys, const uint32_t *d_vals, const uint32_t *d_flags, uint64_t n, uint32_t key_words, int fop,
-                               uint64_t constant, void *d_ws, hipStream_t st) {
-  if (fop < 0 || fop > 12 || (fop == 12 && n && !d_flags)) return hipErrorInvalidValue;
-  u64 *ws = reinterpret_cast<u64 *>(d_ws);
-  const uint64_t t = select_tiles(n);
-  if (t == 0) return hipMemsetAsync(ws, 0, 8, st);
-  u64 *tiles = ws + 8, *scratch = tiles + t + 1;
-  if (key_words == 2)
-    hipLaunchKernelGGL((select_kernel<K128, false>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, SelectNone{}, reinterpret_cast<const K128 *>(d_keys), d_vals, d_flags,
-                       (u64)n, fop, (u64)constant, tiles, (K128 *)nullptr, (u32 *)nullptr);
-  else
-    hipLaunchKernelGGL((select_kernel<u64, false>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, SelectNone{}, reinterpret_cast<const u64 *>(d_keys), d_vals, d_flags,
-                       (u64)n, fop, (u64)constant, tiles, (u64 *)nullptr, (u32 *)nullptr);
-  MGC_CHECK(hipGetLastError());
-  return scan_u64_exclusive(tiles, t, scratch, ws, st);
-}
-hipError_t launch_select_emit(const void *d_keys, const uint32_t *d_vals, const uint32_t *d_flags, uint64_t n, uint32_t key_words, int fop,
-                              uint64_t constant, void *d_ws, void *d_out_keys, uint32_t *d_out_vals, hipStream_t st) {
-  const uint64_t t = select_tiles(n);
-  if (t == 0) return hipSuccess;
-  u64 *tiles = reinterpret_cast<u64 *>(d_ws) + 8;
-  if (key_words == 2)
-    hipLaunchKernelGGL((select_kernel<K128, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, SelectNone{}, reinterpret_cast<const K128 *>(d_keys), d_vals, d_flags,
-                       (u64)n, fop, (u64)constant, tiles, reinterpret_cast<K128 *>(d_out_keys), d_out_vals);
-  else
-    hipLaunchKernelGGL((select_kernel<u64, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, SelectNone{}, reinterpret_cast<const u64 *>(d_keys), d_vals, d_flags,
-                       (u64)n, fop, (u64)constant, tiles, reinterpret_cast<u64 *>(d_out_keys), d_out_vals);
-  return hipGetLastError();
-}
-hipError_t launch_select_emit_labelled(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words, int fop,
-                                       uint64_t constant, int lop, uint64_t lc, void *d_ws, void *d_out_keys, uint32_t *d_out_vals,
-                                       uint64_t *d_out_labs, hipStream_t st) {
-  if (fop < 0 || fop > 11 || lop < LOP_SET || lop > LOP_SEL_MAX || lop == 12) return hipErrorInvalidValue;
-  const uint64_t t = select_tiles(n);
-  if (t == 0) return hipSuccess;
-  u64 *tiles = reinterpret_cast<u64 *>(d_ws) + 8;
-  if (key_words == 2)
-    hipLaunchKernelGGL((select_kernel<K128, true, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, SelectNone{}, reinterpret_cast<const K128 *>(d_keys), d_vals,
-                       (const u32 *)nullptr, (u64)n, fop, (u64)constant, tiles, reinterpret_cast<K128 *>(d_out_keys), d_out_vals,
-                       reinterpret_cast<const u64 *>(d_labs), lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs));
-  else
-    hipLaunchKernelGGL((select_kernel<u64, true, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, SelectNone{}, reinterpret_cast<const u64 *>(d_keys), d_vals,
-                       (const u32 *)nullptr, (u64)n, fop, (u64)constant, tiles, reinterpret_cast<u64 *>(d_out_keys), d_out_vals,
-                       reinterpret_cast<const u64 *>(d_labs), lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs));
-  return hipGetLastError();
-}
-// the two passes with a selector program (terms checked by the caller; lop: a kernel code; d_out_labs may be null)
+// the one place that names the instantiations: <K, false>, <K, true>, <K, true, true> and every <K, EMIT, LABELS, true>
 template <typename K, bool EMIT>
-static void sl_launch_selected(bool labels, const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, int fop, uint64_t constant,
-                               const SelectProgram &program, uint64_t t, u64 *tiles, void *outK, u32 *outC, int lop, u64 lc, u64 *outL, hipStream_t st) {
-  SelectWords pg;
-  memcpy(&pg, &program, sizeof(pg));
-  if (labels)
-    hipLaunchKernelGGL((select_kernel<K, EMIT, true, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, pg, reinterpret_cast<const K *>(d_keys), d_vals,
-                       (const u32 *)nullptr, (u64)n, fop, (u64)constant, tiles, reinterpret_cast<K *>(outK), outC,
-                       reinterpret_cast<const u64 *>(d_labs), lop, lc, outL);
-  else
-    hipLaunchKernelGGL((select_kernel<K, EMIT, false, true>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, pg, reinterpret_cast<const K *>(d_keys), d_vals,
-                       (const u32 *)nullptr, (u64)n, fop, (u64)constant, tiles, reinterpret_cast<K *>(outK), outC,
-                       reinterpret_cast<const u64 *>(d_labs), lop, lc, outL);
+static void sl_launch(PassInst pi, const SelectInput &in, const SelectProgram &program, int fop, uint64_t constant, uint64_t t, u64 *tiles, void *outK,
+                      u32 *outC, int lop, u64 lc, u64 *outL, hipStream_t st) {
+#define SL_GO(LABELS, SELECT, PROG)                                                                                                          \
+  hipLaunchKernelGGL((select_kernel<K, EMIT, LABELS, SELECT>), dim3((uint32_t)t), dim3(SL_BLOCK), 0, st, PROG, reinterpret_cast<const K *>(in.keys), \
+                     in.vals, in.flags, (u64)in.n, fop, (u64)constant, tiles, reinterpret_cast<K *>(outK), outC,                            \
+                     reinterpret_cast<const u64 *>(in.labs), lop, lc, outL)
+  if (pi.select) {
+    SelectWords pg;
+    memcpy(&pg, &program, sizeof(pg));
+    if (pi.labels) SL_GO(true, true, pg);
+    else SL_GO(false, true, pg);
+  } else if constexpr (EMIT) {
+    if (pi.labels) SL_GO(true, false, SelectNone{});
+    else SL_GO(false, false, SelectNone{});
+  } else {
+    SL_GO(false, false, SelectNone{});
+  }
+#undef SL_GO
 }
-static bool sl_program(SelectProgram *pg, uint32_t k, int fop, int lop, const mgc_select_term *terms, uint32_t n_terms) {
-  if (fop < 0 || fop > 11 || lop < LOP_SET || lop > LOP_SEL_MAX || lop == 12 || n_terms > MGC_SELECT_MAX_TERMS || (n_terms && !terms) || k < 1 || k > 64)
-    return false;
-  memset(pg, 0, sizeof(*pg));
-  for (uint32_t i = 0; i < n_terms; i++) pg->t[i] = terms[i];
-  pg->n = n_terms; pg->flags = select_flags(terms, n_terms); pg->k = k;
-  return true;
-}
-hipError_t launch_select_count_selected(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words, uint32_t k,
-                                        int fop, uint64_t constant, int lop, uint64_t lc, const mgc_select_term *terms, uint32_t n_terms, void *d_ws,
-                                        hipStream_t st) {
+
+// count (emit false): the number of k-mers kept lands at ws[0] (merge_read_total reads it); emit: the same input, operation and rule
+// over the workspace the count pass left.  in.flags (fop 12) belongs to the form without a program and without labels; the rule's
+// assignment and filter are merge_many's and are not read here.
+hipError_t launch_select(bool emit, const SelectInput &in, int fop, uint64_t constant, const PassRule &r, void *d_ws, void *d_out_keys,
+                         uint32_t *d_out_vals, hipStream_t st) {
   SelectProgram pg;
-  if (!sl_program(&pg, k, fop, lop, terms, n_terms)) return hipErrorInvalidValue;
+  u64 *outL = emit ? reinterpret_cast<u64 *>(r.out_labs) : nullptr;
+  const bool ruled = r.select || outL;
+  if (fop < 0 || fop > (ruled ? 11 : 12) || (fop == 12 && in.n && !in.flags) || (in.key_words != 1 && in.key_words != 2)) return hipErrorInvalidValue;
+  if (ruled && (r.lop < LOP_SET || r.lop > LOP_SEL_MAX || r.lop == 12)) return hipErrorInvalidValue;
+  if (!select_program(&pg, r.select ? r.terms : nullptr, r.select ? r.n_terms : 0, r.select ? r.k : 1)) return hipErrorInvalidValue;
+  const PassInst pi = pass_inst(emit, r.select, (pg.flags & SELF_LABELS) != 0, false, false, outL != nullptr);
   u64 *ws = reinterpret_cast<u64 *>(d_ws);
-  const uint64_t t = select_tiles(n);
-  if (t == 0) return hipMemsetAsync(ws, 0, 8, st);
+  const uint64_t t = select_tiles(in.n);
+  if (t == 0) return emit ? hipSuccess : hipMemsetAsync(ws, 0, 8, st);
   u64 *tiles = ws + 8, *scratch = tiles + t + 1;
-  const bool labels = (pg.flags & SELF_LABELS) != 0;
-  if (key_words == 2) sl_launch_selected<K128, false>(labels, d_keys, d_vals, d_labs, n, fop, constant, pg, t, tiles, nullptr, nullptr, lop, (u64)lc, nullptr, st);
-  else sl_launch_selected<u64, false>(labels, d_keys, d_vals, d_labs, n, fop, constant, pg, t, tiles, nullptr, nullptr, lop, (u64)lc, nullptr, st);
+  if (emit) {
+    if (in.key_words == 2) sl_launch<K128, true>(pi, in, pg, fop, constant, t, tiles, d_out_keys, d_out_vals, r.lop, (u64)r.lc, outL, st);
+    else sl_launch<u64, true>(pi, in, pg, fop, constant, t, tiles, d_out_keys, d_out_vals, r.lop, (u64)r.lc, outL, st);
+    return hipGetLastError();
+  }
+  if (in.key_words == 2) sl_launch<K128, false>(pi, in, pg, fop, constant, t, tiles, nullptr, nullptr, r.lop, (u64)r.lc, nullptr, st);
+  else sl_launch<u64, false>(pi, in, pg, fop, constant, t, tiles, nullptr, nullptr, r.lop, (u64)r.lc, nullptr, st);
   MGC_CHECK(hipGetLastError());
   return scan_u64_exclusive(tiles, t, scratch, ws, st);
-}
-hipError_t launch_select_emit_selected(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words, uint32_t k,
-                                       int fop, uint64_t constant, int lop, uint64_t lc, const mgc_select_term *terms, uint32_t n_terms, void *d_ws,
-                                       void *d_out_keys, uint32_t *d_out_vals, uint64_t *d_out_labs, hipStream_t st) {
-  SelectProgram pg;
-  if (!sl_program(&pg, k, fop, lop, terms, n_terms)) return hipErrorInvalidValue;
-  const uint64_t t = select_tiles(n);
-  if (t == 0) return hipSuccess;
-  u64 *tiles = reinterpret_cast<u64 *>(d_ws) + 8;
-  const bool labels = (pg.flags & SELF_LABELS) != 0 || d_out_labs != nullptr;
-  if (key_words == 2) sl_launch_selected<K128, true>(labels, d_keys, d_vals, d_labs, n, fop, constant, pg, t, tiles, d_out_keys, d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs), st);
-  else sl_launch_selected<u64, true>(labels, d_keys, d_vals, d_labs, n, fop, constant, pg, t, tiles, d_out_keys, d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs), st);
-  return hipGetLastError();
 }
 hipError_t launch_fill_u32(uint32_t *d, uint64_t n, uint32_t v, hipStream_t st) {
   if (n == 0) return hipSuccess;

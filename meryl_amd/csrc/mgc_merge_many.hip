@@ -37,6 +37,7 @@
 // (mgc_value.hpp) in place of the operation's value chain; a k-mer whose assigned value is 0 is not written, so the count pass
 // reads the values unless the rule is #c or count.  The program, the labels and a value filter see the assigned value.
 #include "mgc_common.hpp"
+#include "mgc_route.hpp"
 #include "mgc_selector.hpp"
 #include "mgc_value.hpp"
 
@@ -303,212 +304,83 @@ size_t merge_many_workspace_bytes(const uint64_t *n, uint32_t n_inputs, uint32_t
   return (mm_splits_at(t) + (size_t)(t + 1) * MM_MAX) * sizeof(u64) + 256;
 }
 
-static bool mm_desc(MergeManyDesc *d, const void *const *keys, const uint32_t *const *vals, const uint64_t *n, uint32_t n_inputs, int op,
-                    uint32_t min_inputs = 2) {
-  if (n_inputs < min_inputs || n_inputs > (uint32_t)MM_MAX || op < 0 || op > 10) return false;
+static bool mm_desc(MergeManyDesc *d, const MergeManyInputs &in, int op) {
+  if (!in.keys || !in.vals || !in.n || in.count < 1 || in.count > (uint32_t)MM_MAX || op < 0 || op > 10) return false;
   memset(d, 0, sizeof(*d));
-  d->count = n_inputs;
-  for (uint32_t i = 0; i < n_inputs; i++) {
-    if (n[i] && (!keys[i] || !vals[i])) return false;
-    if (n[i] >> 32) return false;                            // a run's index inside a tile and the tile sizes are 32-bit; inputs are file slices
-    d->keys[i] = keys[i]; d->vals[i] = vals[i]; d->n[i] = n[i];
+  d->count = in.count;
+  for (uint32_t i = 0; i < in.count; i++) {
+    if (in.n[i] && (!in.keys[i] || !in.vals[i])) return false;
+    if (in.n[i] >> 32) return false;                         // a run's index inside a tile and the tile sizes are 32-bit; inputs are file slices
+    d->keys[i] = in.keys[i]; d->vals[i] = in.vals[i]; d->n[i] = in.n[i];
+    d->labs[i] = in.labs ? reinterpret_cast<const u64 *>(in.labs[i]) : nullptr;
   }
   return true;
 }
 
-// pass 1: cuts the inputs into tiles and leaves the output length at ws[0] (merge_read_total reads it)
-hipError_t launch_merge_many_count(const void *const *keys, const uint32_t *const *vals, const uint64_t *n, uint32_t n_inputs,
-                                   uint32_t key_words, int op, void *d_ws, hipStream_t st, bool allow_one) {
-  MergeManyDesc d;
-  if (!mm_desc(&d, keys, vals, n, n_inputs, op, allow_one ? 1 : 2)) return hipErrorInvalidValue;
-  u64 *ws = reinterpret_cast<u64 *>(d_ws);
-  const uint64_t total = mm_total(n, n_inputs), t = mm_tiles(total, key_words);
-  if (t == 0) return hipMemsetAsync(ws, 0, 8, st);
-  u64 *tiles = ws + 8, *scratch = tiles + t + 1, *splits = ws + mm_splits_at(t);
-  const uint32_t pgrid = (uint32_t)((t + 1 + MM_BLOCK / 64 - 1) / (MM_BLOCK / 64));
-  if (key_words == 2) {
-    hipLaunchKernelGGL((merge_many_partition_kernel<K128>), dim3(pgrid), dim3(MM_BLOCK), 0, st, d, (u64)total, (u64)t, splits);
-    hipLaunchKernelGGL((merge_many_kernel<K128, false>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, SelectNone{}, op, splits, tiles, (K128 *)nullptr, (u32 *)nullptr);
-  } else {
-    hipLaunchKernelGGL((merge_many_partition_kernel<u64>), dim3(pgrid), dim3(MM_BLOCK), 0, st, d, (u64)total, (u64)t, splits);
-    hipLaunchKernelGGL((merge_many_kernel<u64, false>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, SelectNone{}, op, splits, tiles, (u64 *)nullptr, (u32 *)nullptr);
-  }
-  MGC_CHECK(hipGetLastError());
-  return scan_u64_exclusive(tiles, t, scratch, ws, st);
-}
-
-// pass 2 (same inputs, the workspace pass 1 left): writes the merged stream
-hipError_t launch_merge_many_emit(const void *const *keys, const uint32_t *const *vals, const uint64_t *n, uint32_t n_inputs,
-                                  uint32_t key_words, int op, void *d_ws, void *d_out_keys, uint32_t *d_out_vals, hipStream_t st) {
-  MergeManyDesc d;
-  if (!mm_desc(&d, keys, vals, n, n_inputs, op)) return hipErrorInvalidValue;
-  u64 *ws = reinterpret_cast<u64 *>(d_ws);
-  const uint64_t t = mm_tiles(mm_total(n, n_inputs), key_words);
-  if (t == 0) return hipSuccess;
-  u64 *tiles = ws + 8, *splits = ws + mm_splits_at(t);
-  if (key_words == 2)
-    hipLaunchKernelGGL((merge_many_kernel<K128, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, SelectNone{}, op, splits, tiles,
-                       reinterpret_cast<K128 *>(d_out_keys), d_out_vals);
-  else
-    hipLaunchKernelGGL((merge_many_kernel<u64, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, SelectNone{}, op, splits, tiles,
-                       reinterpret_cast<u64 *>(d_out_keys), d_out_vals);
-  return hipGetLastError();
-}
-
-// pass 2 with labels: the same, and d_out_labs[o] = label operation `lop` (kernel code) over the inputs that hold k-mer o
-hipError_t launch_merge_many_emit_labelled(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs,
-                                           const uint64_t *n, uint32_t n_inputs, uint32_t key_words, int op, int lop, uint64_t lc, void *d_ws,
-                                           void *d_out_keys, uint32_t *d_out_vals, uint64_t *d_out_labs, hipStream_t st) {
-  MergeManyDesc d;
-  if (!mm_desc(&d, keys, vals, n, n_inputs, op, 1) || lop < LOP_SET || lop > LOP_SEL_MAX || lop == 12 || (lop == LOP_INVERT && n_inputs > 1))
-    return hipErrorInvalidValue;
-  for (uint32_t i = 0; i < n_inputs; i++) d.labs[i] = labs ? reinterpret_cast<const u64 *>(labs[i]) : nullptr;
-  u64 *ws = reinterpret_cast<u64 *>(d_ws);
-  const uint64_t t = mm_tiles(mm_total(n, n_inputs), key_words);
-  if (t == 0) return hipSuccess;
-  u64 *tiles = ws + 8, *splits = ws + mm_splits_at(t);
-  if (key_words == 2)
-    hipLaunchKernelGGL((merge_many_kernel<K128, true, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, SelectNone{}, op, splits, tiles,
-                       reinterpret_cast<K128 *>(d_out_keys), d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs));
-  else
-    hipLaunchKernelGGL((merge_many_kernel<u64, true, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, SelectNone{}, op, splits, tiles,
-                       reinterpret_cast<u64 *>(d_out_keys), d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs));
-  return hipGetLastError();
-}
-
-// ---- with a selector program (SELECT) ------------------------------------------------------------------------------------------
-// terms: checked by the caller (select_check); lop: a kernel code.  The LABELS instantiations run where a LABEL term asks for
-// labels (both passes) or labels are written (emit).
-static bool mm_select_desc(MergeManyDesc *d, SelectProgram *pg, const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs,
-                           const uint64_t *n, uint32_t n_inputs, uint32_t k, int op, int lop, const mgc_select_term *terms, uint32_t n_terms) {
-  if (!mm_desc(d, keys, vals, n, n_inputs, op, 1) || n_terms > MGC_SELECT_MAX_TERMS || (n_terms && !terms) || k < 1 || k > 64) return false;
-  if (lop < LOP_SET || lop > LOP_SEL_MAX || lop == 12 || (lop == LOP_INVERT && n_inputs > 1)) return false;
-  for (uint32_t i = 0; i < n_inputs; i++) d->labs[i] = labs ? reinterpret_cast<const u64 *>(labs[i]) : nullptr;
-  memset(pg, 0, sizeof(*pg));
-  for (uint32_t i = 0; i < n_terms; i++) pg->t[i] = terms[i];
-  pg->n = n_terms; pg->flags = select_flags(terms, n_terms); pg->k = k;
-  return true;
-}
-
-template <typename K, bool EMIT>
-static void mm_launch_selected(bool labels, const MergeManyDesc &d, const SelectProgram &pg, int op, uint64_t t, const u64 *splits, u64 *tiles,
-                               void *outK, u32 *outC, int lop, u64 lc, u64 *outL, hipStream_t st) {
-  if (labels)
-    hipLaunchKernelGGL((merge_many_kernel<K, EMIT, true, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, pg, op, splits, tiles,
-                       reinterpret_cast<K *>(outK), outC, lop, lc, outL);
-  else
-    hipLaunchKernelGGL((merge_many_kernel<K, EMIT, false, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, pg, op, splits, tiles,
-                       reinterpret_cast<K *>(outK), outC, lop, lc, outL);
-}
-
-hipError_t launch_merge_many_count_selected(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
-                                            uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int lop, uint64_t lc,
-                                            const mgc_select_term *terms, uint32_t n_terms, void *d_ws, hipStream_t st) {
-  MergeManyDesc d;
-  SelectProgram pg;
-  if (!mm_select_desc(&d, &pg, keys, vals, labs, n, n_inputs, k, op, lop, terms, n_terms)) return hipErrorInvalidValue;
-  u64 *ws = reinterpret_cast<u64 *>(d_ws);
-  const uint64_t total = mm_total(n, n_inputs), t = mm_tiles(total, key_words);
-  if (t == 0) return hipMemsetAsync(ws, 0, 8, st);
-  u64 *tiles = ws + 8, *scratch = tiles + t + 1, *splits = ws + mm_splits_at(t);
-  const uint32_t pgrid = (uint32_t)((t + 1 + MM_BLOCK / 64 - 1) / (MM_BLOCK / 64));
-  const bool labels = (pg.flags & SELF_LABELS) != 0;
-  if (key_words == 2) {
-    hipLaunchKernelGGL((merge_many_partition_kernel<K128>), dim3(pgrid), dim3(MM_BLOCK), 0, st, d, (u64)total, (u64)t, splits);
-    mm_launch_selected<K128, false>(labels, d, pg, op, t, splits, tiles, nullptr, nullptr, lop, (u64)lc, nullptr, st);
-  } else {
-    hipLaunchKernelGGL((merge_many_partition_kernel<u64>), dim3(pgrid), dim3(MM_BLOCK), 0, st, d, (u64)total, (u64)t, splits);
-    mm_launch_selected<u64, false>(labels, d, pg, op, t, splits, tiles, nullptr, nullptr, lop, (u64)lc, nullptr, st);
-  }
-  MGC_CHECK(hipGetLastError());
-  return scan_u64_exclusive(tiles, t, scratch, ws, st);
-}
-
-// d_out_labs may be null: no labels are written (they are still computed where a LABEL term looks at the output label)
-hipError_t launch_merge_many_emit_selected(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
-                                           uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int lop, uint64_t lc,
-                                           const mgc_select_term *terms, uint32_t n_terms, void *d_ws, void *d_out_keys, uint32_t *d_out_vals,
-                                           uint64_t *d_out_labs, hipStream_t st) {
-  MergeManyDesc d;
-  SelectProgram pg;
-  if (!mm_select_desc(&d, &pg, keys, vals, labs, n, n_inputs, k, op, lop, terms, n_terms)) return hipErrorInvalidValue;
-  u64 *ws = reinterpret_cast<u64 *>(d_ws);
-  const uint64_t t = mm_tiles(mm_total(n, n_inputs), key_words);
-  if (t == 0) return hipSuccess;
-  u64 *tiles = ws + 8, *splits = ws + mm_splits_at(t);
-  const bool labels = (pg.flags & SELF_LABELS) != 0 || d_out_labs != nullptr;
-  if (key_words == 2) mm_launch_selected<K128, true>(labels, d, pg, op, t, splits, tiles, d_out_keys, d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs), st);
-  else mm_launch_selected<u64, true>(labels, d, pg, op, t, splits, tiles, d_out_keys, d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs), st);
-  return hipGetLastError();
-}
-
-// ---- with a value assignment (ASSIGN; always with SELECT) --------------------------------------------------------------------------
-// vop: a kernel code (value_kernel_op, mgc_value.hpp); VOP_NONE without a filter is the selected launch itself.  fop >= 0: the
-// value filter of a filter node (MGC_VALUE_LESS_THAN .. NOT_EQUAL_TO) with threshold fc, tested on the assigned value.
+// vop: a kernel code (value_kernel_op, mgc_value.hpp).  fop >= 0: the value filter of a filter node (MGC_VALUE_LESS_THAN ..
+// NOT_EQUAL_TO) with threshold fc, tested on the assigned value.
 static bool mm_assign_rule(AssignRule *r, int vop, uint64_t vc, int fop, uint64_t fc) {
   if (vop < VOP_SET || vop > VOP_COUNT || vop == 3 || fop > 5) return false;
   r->vop = vop; r->vc = (u32)vc; r->fop = fop < 0 ? -1 : fop; r->reserved = 0; r->fc = fc;
   return true;
 }
 
+// the one place that names the instantiations: <K, false>, <K, true>, <K, true, true>, and every <K, EMIT, LABELS, true[, true]>
 template <typename K, bool EMIT>
-static void mm_launch_assigned(bool labels, const MergeManyDesc &d, const SelectProgram &pg, const AssignRule &rule, int op, uint64_t t,
-                               const u64 *splits, u64 *tiles, void *outK, u32 *outC, int lop, u64 lc, u64 *outL, hipStream_t st) {
-  if (labels)
-    hipLaunchKernelGGL((merge_many_kernel<K, EMIT, true, true, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, pg, op, splits, tiles,
-                       reinterpret_cast<K *>(outK), outC, lop, lc, outL, rule);
-  else
-    hipLaunchKernelGGL((merge_many_kernel<K, EMIT, false, true, true>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, pg, op, splits, tiles,
-                       reinterpret_cast<K *>(outK), outC, lop, lc, outL, rule);
+static void mm_launch(PassInst pi, const MergeManyDesc &d, const SelectProgram &pg, const AssignRule &asg, int op, uint64_t t, const u64 *splits,
+                      u64 *tiles, void *outK, u32 *outC, int lop, u64 lc, u64 *outL, hipStream_t st) {
+#define MM_GO(LABELS, SELECT, ASSIGN, ...) \
+  hipLaunchKernelGGL((merge_many_kernel<K, EMIT, LABELS, SELECT, ASSIGN>), dim3((uint32_t)t), dim3(MM_BLOCK), 0, st, d, __VA_ARGS__)
+#define MM_ARGS op, splits, tiles, reinterpret_cast<K *>(outK), outC, lop, lc, outL
+  if (pi.assign) {
+    if (pi.labels) MM_GO(true, true, true, pg, MM_ARGS, asg);
+    else MM_GO(false, true, true, pg, MM_ARGS, asg);
+  } else if (pi.select) {
+    if (pi.labels) MM_GO(true, true, false, pg, MM_ARGS);
+    else MM_GO(false, true, false, pg, MM_ARGS);
+  } else if constexpr (EMIT) {
+    if (pi.labels) MM_GO(true, false, false, SelectNone{}, MM_ARGS);
+    else MM_GO(false, false, false, SelectNone{}, MM_ARGS);
+  } else {
+    MM_GO(false, false, false, SelectNone{}, MM_ARGS);
+  }
+#undef MM_ARGS
+#undef MM_GO
 }
 
-hipError_t launch_merge_many_count_assigned(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
-                                            uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int vop, uint64_t vc, int fop, uint64_t fc,
-                                            int lop, uint64_t lc, const mgc_select_term *terms, uint32_t n_terms, void *d_ws, hipStream_t st) {
-  if (vop == VOP_NONE && fop < 0)
-    return launch_merge_many_count_selected(keys, vals, labs, n, n_inputs, key_words, k, op, lop, lc, terms, n_terms, d_ws, st);
+// count (emit false): cuts the inputs into tiles and leaves the output length at ws[0] (merge_read_total reads it); emit: the same
+// inputs, operation and rule over the workspace the count pass left, writes the merged stream.  One to MM_MAX inputs.
+hipError_t launch_merge_many(bool emit, const MergeManyInputs &in, int op, const PassRule &r, void *d_ws, void *d_out_keys,
+                             uint32_t *d_out_vals, hipStream_t st) {
   MergeManyDesc d;
   SelectProgram pg;
-  AssignRule rule;
-  if (!mm_select_desc(&d, &pg, keys, vals, labs, n, n_inputs, k, op, lop, terms, n_terms) || !mm_assign_rule(&rule, vop, vc, fop, fc))
-    return hipErrorInvalidValue;
+  AssignRule asg = {};
+  const bool assignment = r.vop != VOP_NONE, filter = r.fop >= 0, select = r.select || assignment || filter;
+  u64 *outL = emit ? reinterpret_cast<u64 *>(r.out_labs) : nullptr;
+  if (!mm_desc(&d, in, op) || (in.key_words != 1 && in.key_words != 2)) return hipErrorInvalidValue;
+  if ((select || outL) && (r.lop < LOP_SET || r.lop > LOP_SEL_MAX || r.lop == 12 || (r.lop == LOP_INVERT && in.count > 1))) return hipErrorInvalidValue;
+  if (!select_program(&pg, select ? r.terms : nullptr, select ? r.n_terms : 0, select ? r.k : 1)) return hipErrorInvalidValue;
+  if ((assignment || filter) && !mm_assign_rule(&asg, r.vop, r.vc, r.fop, r.fc)) return hipErrorInvalidValue;
+  const PassInst pi = pass_inst(emit, select, (pg.flags & SELF_LABELS) != 0, assignment, filter, outL != nullptr);
   u64 *ws = reinterpret_cast<u64 *>(d_ws);
-  const uint64_t total = mm_total(n, n_inputs), t = mm_tiles(total, key_words);
-  if (t == 0) return hipMemsetAsync(ws, 0, 8, st);
+  const uint64_t total = mm_total(in.n, in.count), t = mm_tiles(total, in.key_words);
+  if (t == 0) return emit ? hipSuccess : hipMemsetAsync(ws, 0, 8, st);
   u64 *tiles = ws + 8, *scratch = tiles + t + 1, *splits = ws + mm_splits_at(t);
+  if (emit) {
+    if (in.key_words == 2) mm_launch<K128, true>(pi, d, pg, asg, op, t, splits, tiles, d_out_keys, d_out_vals, r.lop, (u64)r.lc, outL, st);
+    else mm_launch<u64, true>(pi, d, pg, asg, op, t, splits, tiles, d_out_keys, d_out_vals, r.lop, (u64)r.lc, outL, st);
+    return hipGetLastError();
+  }
   const uint32_t pgrid = (uint32_t)((t + 1 + MM_BLOCK / 64 - 1) / (MM_BLOCK / 64));
-  const bool labels = (pg.flags & SELF_LABELS) != 0;
-  if (key_words == 2) {
+  if (in.key_words == 2) {
     hipLaunchKernelGGL((merge_many_partition_kernel<K128>), dim3(pgrid), dim3(MM_BLOCK), 0, st, d, (u64)total, (u64)t, splits);
-    mm_launch_assigned<K128, false>(labels, d, pg, rule, op, t, splits, tiles, nullptr, nullptr, lop, (u64)lc, nullptr, st);
+    mm_launch<K128, false>(pi, d, pg, asg, op, t, splits, tiles, nullptr, nullptr, r.lop, (u64)r.lc, nullptr, st);
   } else {
     hipLaunchKernelGGL((merge_many_partition_kernel<u64>), dim3(pgrid), dim3(MM_BLOCK), 0, st, d, (u64)total, (u64)t, splits);
-    mm_launch_assigned<u64, false>(labels, d, pg, rule, op, t, splits, tiles, nullptr, nullptr, lop, (u64)lc, nullptr, st);
+    mm_launch<u64, false>(pi, d, pg, asg, op, t, splits, tiles, nullptr, nullptr, r.lop, (u64)r.lc, nullptr, st);
   }
   MGC_CHECK(hipGetLastError());
   return scan_u64_exclusive(tiles, t, scratch, ws, st);
-}
-
-hipError_t launch_merge_many_emit_assigned(const void *const *keys, const uint32_t *const *vals, const uint64_t *const *labs, const uint64_t *n,
-                                           uint32_t n_inputs, uint32_t key_words, uint32_t k, int op, int vop, uint64_t vc, int fop, uint64_t fc,
-                                           int lop, uint64_t lc, const mgc_select_term *terms, uint32_t n_terms, void *d_ws, void *d_out_keys,
-                                           uint32_t *d_out_vals, uint64_t *d_out_labs, hipStream_t st) {
-  if (vop == VOP_NONE && fop < 0)
-    return launch_merge_many_emit_selected(keys, vals, labs, n, n_inputs, key_words, k, op, lop, lc, terms, n_terms, d_ws, d_out_keys, d_out_vals,
-                                           d_out_labs, st);
-  MergeManyDesc d;
-  SelectProgram pg;
-  AssignRule rule;
-  if (!mm_select_desc(&d, &pg, keys, vals, labs, n, n_inputs, k, op, lop, terms, n_terms) || !mm_assign_rule(&rule, vop, vc, fop, fc))
-    return hipErrorInvalidValue;
-  u64 *ws = reinterpret_cast<u64 *>(d_ws);
-  const uint64_t t = mm_tiles(mm_total(n, n_inputs), key_words);
-  if (t == 0) return hipSuccess;
-  u64 *tiles = ws + 8, *splits = ws + mm_splits_at(t);
-  const bool labels = (pg.flags & SELF_LABELS) != 0 || d_out_labs != nullptr;
-  if (key_words == 2) mm_launch_assigned<K128, true>(labels, d, pg, rule, op, t, splits, tiles, d_out_keys, d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs), st);
-  else mm_launch_assigned<u64, true>(labels, d, pg, rule, op, t, splits, tiles, d_out_keys, d_out_vals, lop, (u64)lc, reinterpret_cast<u64 *>(d_out_labs), st);
-  return hipGetLastError();
 }
 
 }  // namespace mgc

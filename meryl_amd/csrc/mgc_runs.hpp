@@ -22,19 +22,7 @@ struct RunSink {
 }  // namespace mgc
 
 struct mgc_runs {
-  struct DBuf {                                             // grow-only device buffer
-    void *p = nullptr; size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-      if (bytes < 256) bytes = 256;
-      if (cap >= bytes) return hipSuccess;
-      if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-      hipError_t e = hipMalloc(&p, bytes);
-      if (e == hipSuccess) cap = bytes;
-      return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-  };
+  typedef mgc::DBuf DBuf;
   struct Run {
     uint64_t  n = 0;
     bool      on_host = false;

@@ -1,7 +1,7 @@
 // mgc_selector.hpp -- whether a k-mer an operation is about to write passes the operation's selector program: meryl2's
 // merylSelector::isTrue (src/meryl2/merylSelector.C:72-156) over a sum of products (merylOp-nextMer.C:58-192); the rules, with the
 // line each comes from, are in include/meryl_gpu_count.h (mgc_select_term).  Shared by the kernels (mgc_merge_many.hip,
-// mgc_merge.hip), the host code that checks and parses programs (mgc_api.cpp, mgc_stream.cpp) and a stand-alone host program
+// mgc_merge.hip), the host code that checks and parses programs (mgc_api.cpp, mgc_eval.cpp) and a stand-alone host program
 // (tests/host/select_host.cpp): plain C++, no HIP header needed.
 #pragma once
 #include "../../include/meryl_gpu_count.h"
@@ -149,6 +149,15 @@ inline uint32_t select_flags(const mgc_select_term *t, uint32_t n) {
     if (t[i].quantity == MGC_SEL_BASES) f |= SELF_KEYS;
   }
   return f;
+}
+
+// checked terms (select_check) -> the program a launch passes; false: more terms than a program holds, or a k no key holds
+inline bool select_program(SelectProgram *pg, const mgc_select_term *t, uint32_t n, uint32_t k) {
+  if (n > MGC_SELECT_MAX_TERMS || (n && !t) || k < 1 || k > 64) return false;
+  memset(pg, 0, sizeof(*pg));
+  for (uint32_t i = 0; i < n; i++) pg->t[i] = t[i];
+  pg->n = n; pg->flags = select_flags(t, n); pg->k = k;
+  return true;
 }
 
 // mgc_select_check: empty string = a program every kernel may take for a node of n_inputs inputs

@@ -10,8 +10,6 @@
 #include "mdb_layout.h"
 #include "mgc_session.hpp"
 #include "mgc_runs.hpp"
-#include "mgc_selector.hpp"
-#include "mgc_value.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -22,25 +20,12 @@
 #include <mutex>
 #include <thread>
 
+using mgc::DBuf;
 using mgc::set_err;
 
 namespace {
 
 using mgc::now_s;
-
-struct DBuf {                                             // grow-only device buffer
-  void *p = nullptr; size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes < 256) bytes = 256;
-    if (cap >= bytes) return hipSuccess;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
 
 constexpr size_t   SLOT_BYTES = 32u << 20;                // pinned copy buffers: NSLOT x SLOT_BYTES
 constexpr int      NSLOT_MAX  = 64;
@@ -690,751 +675,4 @@ extern "C" int mgc_finish(mgc_session *s, mgc_block_cb cb, void *ctx, int host_t
 
 extern "C" int mgc_finish_labelled(mgc_session *s, mgc_block_cb2 cb, void *ctx, int host_threads) {
   return finish_impl(s, nullptr, cb, ctx, host_threads);
-}
-
-// ================================================================================================
-//  union-sum & friends over whole databases
-// ================================================================================================
-// The reference streams the 64 file slices of its inputs through merylOperation::nextMer -- smallest k-mer over the
-// inputs, values of the inputs that hold it combined (src/meryl/merylOp-nextMer.C:418-683; one slice per thread,
-// src/meryl/meryl.C:250-263).  Here a slice is decoded by host threads (one per input), merged two inputs at a time on the
-// device (mgc_merge.hip), encoded on the device and written by the database stream -- the same merge that folds the
-// batches of an out-of-core count.
-namespace {
-// The slice (file ff) of every input in HBM: in_k[i] / in_c[i] / hn[i].  The data file's bytes are read by one host thread per
-// input, uploaded as they are and DECODED ON THE DEVICE (mgc_decode.hip: one thread per block) -- the host only does I/O and
-// checks the framing.  MGC_DECODE_HOST=1, or a file framed in a way only the host decoder follows: decoded by the host
-// threads (65-70 M k-mers/s each) and uploaded as arrays, as before.
-// MGC_DECODE_HOST=1 (tests): read ONCE per merge / filter operation, by its entry point
-bool decode_on_host() { const char *e = getenv("MGC_DECODE_HOST"); return e && e[0] == '1'; }
-// in_l (the labelled evaluation; null otherwise): the labels of the inputs that store some, beside the values -- from the device
-// decoder, or from mdb_reader_read_file_ex on the host path; an input without labels gets no buffer (its labels are zeros)
-int load_slices(std::vector<mdb_reader *> &rd, uint32_t ff, uint32_t kw, std::vector<DBuf> &in_k, std::vector<DBuf> &in_c,
-                std::vector<uint64_t> &hn, hipStream_t st, std::string *msg, bool host_decode, std::vector<DBuf> *in_l = nullptr) {
-  const uint32_t n_inputs = (uint32_t)rd.size();
-  struct Raw { unsigned char *bytes = nullptr; uint64_t size = 0; mdb_raw_block *blocks = nullptr; uint64_t nb = 0; bool on_device = false; };
-  std::vector<Raw> raw(n_inputs);
-  std::vector<std::vector<uint64_t>> hk(n_inputs);
-  std::vector<uint32_t *> hc(n_inputs, nullptr);
-  std::vector<uint64_t *> hl(n_inputs, nullptr);
-  std::vector<int> rrc(n_inputs, MGC_OK);
-  std::vector<std::string> rmsg(n_inputs);
-  std::vector<mdb_info> infos(n_inputs);
-  hn.assign(n_inputs, 0);
-  {
-    std::vector<std::thread> th;
-    for (uint32_t i = 0; i < n_inputs; i++)
-      th.emplace_back([&, i]() {
-        mdb_reader_info(rd[i], &infos[i]);
-        if (!host_decode) {
-          const int rc = mdb_reader_raw_file(rd[i], ff, &raw[i].bytes, &raw[i].size, &raw[i].blocks, &raw[i].nb, &hn[i]);
-          if (rc == MGC_OK) { raw[i].on_device = true; return; }
-          if (rc != MGC_EUNSUPPORTED) { rrc[i] = rc; rmsg[i] = mdb_last_error(); return; }
-        }
-        uint64_t *lo = nullptr, *hi = nullptr;
-        rrc[i] = mdb_reader_read_file_ex(rd[i], ff, &lo, &hi, &hc[i], (in_l && infos[i].label_size) ? &hl[i] : nullptr, &hn[i]);
-        if (rrc[i] != MGC_OK) { rmsg[i] = mdb_last_error(); return; }
-        hk[i].resize((size_t)kw * hn[i]);
-        if (kw == 1) { if (hn[i]) memcpy(hk[i].data(), lo, 8 * hn[i]); }
-        else for (uint64_t j = 0; j < hn[i]; j++) { hk[i][2 * j] = lo[j]; hk[i][2 * j + 1] = hi[j]; }
-        mdb_free(lo); mdb_free(hi);
-      });
-    for (auto &t : th) t.join();
-  }
-  int rc = MGC_OK;
-  for (uint32_t i = 0; i < n_inputs; i++)
-    if (rrc[i] != MGC_OK && rc == MGC_OK) { rc = rrc[i]; *msg = rmsg[i]; }
-  hipError_t e = hipSuccess;
-  DBuf d_file, d_blocks, d_err;
-  uint32_t h_err = 0;
-  if (rc == MGC_OK) e = d_err.ensure(256);
-  for (uint32_t i = 0; i < n_inputs && rc == MGC_OK && e == hipSuccess; i++) {
-    e = in_k[i].ensure(8 * (size_t)kw * hn[i]);
-    if (e == hipSuccess) e = in_c[i].ensure(4 * hn[i]);
-    const bool with_l = in_l && infos[i].label_size;
-    if (e == hipSuccess && with_l) e = (*in_l)[i].ensure(8 * hn[i]);
-    if (e != hipSuccess || !hn[i]) continue;
-    if (raw[i].on_device) {
-      e = d_file.ensure(raw[i].size + 16);
-      if (e == hipSuccess) e = d_blocks.ensure(sizeof(mdb_raw_block) * raw[i].nb);
-      if (e == hipSuccess) e = hipMemsetAsync(d_err.p, 0, 4, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(d_file.p, raw[i].bytes, raw[i].size + 16, hipMemcpyHostToDevice, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(d_blocks.p, raw[i].blocks, sizeof(mdb_raw_block) * raw[i].nb, hipMemcpyHostToDevice, st);
-      if (e == hipSuccess) e = mgc::launch_decode_blocks(d_file.p, d_blocks.p, raw[i].nb, infos[i].suffix_size, infos[i].label_size, kw, in_k[i].p,
-                                                         in_c[i].as<uint32_t>(), d_err.as<uint32_t>(), st, with_l ? (*in_l)[i].as<uint64_t>() : nullptr);
-      if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err.p, 4, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);                     // d_file is reused by the next input
-      if (e == hipSuccess && h_err) { rc = MGC_EINVAL; *msg = "corrupt block in a database file (device decoder, code " + std::to_string(h_err) + ")"; }
-    } else {
-      e = hipMemcpyAsync(in_k[i].p, hk[i].data(), 8 * (size_t)kw * hn[i], hipMemcpyHostToDevice, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(in_c[i].p, hc[i], 4 * hn[i], hipMemcpyHostToDevice, st);
-      if (e == hipSuccess && with_l) e = hipMemcpyAsync((*in_l)[i].p, hl[i], 8 * hn[i], hipMemcpyHostToDevice, st);
-    }
-  }
-  if (e == hipSuccess && rc == MGC_OK) e = hipStreamSynchronize(st);
-  for (uint32_t i = 0; i < n_inputs; i++) { mdb_free(hc[i]); mdb_free(hl[i]); mdb_free(raw[i].bytes); mdb_free(raw[i].blocks); }
-  d_file.release(); d_blocks.release(); d_err.release();
-  if (e != hipSuccess) { rc = (e == hipErrorOutOfMemory) ? MGC_ENOMEM : MGC_EHIP; *msg = std::string("uploading a slice: ") + hipGetErrorString(e); }
-  return rc;
-}
-
-// inputs of one k, no labels, no multisets -> readers + the first one's info; false: message in the thread error
-// (max_label_size given -- the labelled evaluation: labels are allowed, and the largest label_size among the inputs is returned)
-bool open_merge_inputs(const char *const *inputs, uint32_t n_inputs, std::vector<mdb_reader *> &rd, mdb_info *first, const char *who,
-                       uint32_t *max_label_size = nullptr) {
-  rd.assign(n_inputs, nullptr);
-  auto close_all = [&]() { for (mdb_reader *r : rd) if (r) mdb_reader_close(r); };
-  memset(first, 0, sizeof(*first));
-  for (uint32_t i = 0; i < n_inputs; i++) {
-    rd[i] = inputs[i] ? mdb_reader_open(inputs[i]) : nullptr;
-    if (!rd[i]) { set_err(nullptr, "%s: %s", who, mdb_last_error()); close_all(); return false; }
-    mdb_info inf;
-    mdb_reader_info(rd[i], &inf);
-    // the merge combines VALUES only: labels would be dropped and a multiset's repeated k-mers folded -- refuse rather than
-    // write something that silently differs
-    if ((inf.label_size != 0 && !max_label_size) || (inf.flags & 1u)) {
-      set_err(nullptr, "%s: '%s' %s: not supported here", who, inputs[i], (inf.label_size && !max_label_size) ? "stores labels" : "is a multiset");
-      close_all();
-      return false;
-    }
-    if (max_label_size) *max_label_size = std::max(*max_label_size, inf.label_size);
-    if (i == 0) *first = inf;
-    else if (inf.k != first->k) {
-      set_err(nullptr, "%s: '%s' holds %u-mers, '%s' %u-mers", who, inputs[i], inf.k, inputs[0], first->k);   // merylOp.C: kmer size mismatch
-      close_all();
-      return false;
-    }
-  }
-  return true;
-}
-
-// one (k-mer, value) stream in HBM
-struct SliceRef { const void *k = nullptr; const uint32_t *c = nullptr; uint64_t n = 0; const uint64_t *l = nullptr; /*labelled evaluation; null: zeros*/ };
-
-// buffers of the left fold (grow-only, reused from slice to slice)
-struct FoldBufs {
-  DBuf acc_k[2], acc_c[2], mem_k[2], mem_c[2], ones, ws;
-  void release() {
-    for (int t = 0; t < 2; t++) { acc_k[t].release(); acc_c[t].release(); mem_k[t].release(); mem_c[t].release(); }
-    ones.release();
-    ws.release();
-  }
-};
-
-// The inputs of one slice folded from the left with the two-input merge (mgc_merge.hip) -- mgc_db_merge, and the merge nodes
-// of mgc_db_eval that do not go through merge_many.
-//   union (value = how many inputs hold the k-mer, :559-561) = union-sum over values of one;
-//   symmetric-difference over more than two inputs (in exactly ONE input, :609-612) = the union-sum of the values
-//   filtered by "union-sum of ones == 1" (written to sel_k / sel_c, which must not hold the value fold's result);
-//   everything else folds from the left with its own two-input step.
-// *out: the result (an input's or one of the buffers' memory), valid once this returns (the stream is synchronised).
-hipError_t fold_slices(const std::vector<SliceRef> &in, int op, uint32_t kw, FoldBufs &fb, DBuf &sel_k, DBuf &sel_c, hipStream_t st,
-                       SliceRef *out, const char **what) {
-  const uint32_t n_inputs = (uint32_t)in.size();
-  const bool by_membership = (op == MGC_MERGE_SYMMETRIC_DIFFERENCE && n_inputs > 2);
-  const int fold_op = (op == MGC_MERGE_UNION || by_membership) ? MGC_MERGE_UNION_SUM : op;
-  // fold: values (and, for the membership forms, ones) through the same sequence of two-input steps
-  auto fold = [&](bool use_ones, DBuf (&ak)[2], DBuf (&ac)[2], SliceRef *res) -> hipError_t {
-    uint64_t most = 0;
-    for (uint32_t i = 0; i < n_inputs; i++) most = std::max(most, in[i].n);
-    if (use_ones) {
-      hipError_t e = fb.ones.ensure(4 * most);
-      if (e == hipSuccess) e = mgc::launch_fill_u32(fb.ones.as<uint32_t>(), most, 1u, st);
-      if (e != hipSuccess) { *what = "ones"; return e; }
-    }
-    auto cof = [&](uint32_t i) -> const uint32_t * { return use_ones ? fb.ones.as<uint32_t>() : in[i].c; };
-    SliceRef cur{in[0].k, cof(0), in[0].n};
-    for (uint32_t i = 1; i < n_inputs; i++) {
-      const int t = (int)(i & 1u);
-      uint64_t n_new = 0;
-      hipError_t e = fb.ws.ensure(mgc::merge_workspace_bytes(cur.n, in[i].n));
-      if (e == hipSuccess) e = mgc::launch_merge_count(cur.k, cur.n, in[i].k, in[i].n, kw, fold_op, fb.ws.p, st, cur.c, cof(i));
-      if (e == hipSuccess) e = mgc::merge_read_total(fb.ws.p, &n_new, st);
-      if (e == hipSuccess) e = ak[t].ensure(8 * (size_t)kw * n_new);
-      if (e == hipSuccess) e = ac[t].ensure(4 * n_new);
-      if (e == hipSuccess) e = mgc::launch_merge_emit(cur.k, cur.c, cur.n, in[i].k, cof(i), in[i].n, kw, fold_op, fb.ws.p, ak[t].p, ac[t].as<uint32_t>(), st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-      if (e != hipSuccess) { *what = "merging a slice"; return e; }
-      cur = SliceRef{ak[t].p, ac[t].as<uint32_t>(), n_new};
-    }
-    *res = cur;
-    return hipSuccess;
-  };
-  SliceRef res;
-  hipError_t e = fold(op == MGC_MERGE_UNION, fb.acc_k, fb.acc_c, &res);
-  if (e != hipSuccess) return e;
-  if (by_membership) {
-    SliceRef mem;                                            // same k-mers as the value fold, values = inputs holding each
-    e = fold(true, fb.mem_k, fb.mem_c, &mem);
-    if (e != hipSuccess) return e;
-    uint64_t n_new = 0;
-    *what = "selecting the k-mers of exactly one input";
-    if (res.k == sel_k.p) { *what = "symmetric-difference buffers"; return hipErrorInvalidValue; }
-    e = fb.ws.ensure(mgc::select_workspace_bytes(res.n));
-    if (e == hipSuccess) e = mgc::launch_select_count(res.k, res.c, mem.c, res.n, kw, 12, 0, fb.ws.p, st);
-    if (e == hipSuccess) e = mgc::merge_read_total(fb.ws.p, &n_new, st);
-    if (e == hipSuccess) e = sel_k.ensure(8 * (size_t)kw * n_new);
-    if (e == hipSuccess) e = sel_c.ensure(4 * n_new);
-    if (e == hipSuccess) e = mgc::launch_select_emit(res.k, res.c, mem.c, res.n, kw, 12, 0, fb.ws.p, sel_k.p, sel_c.as<uint32_t>(), st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return e;
-    res = SliceRef{sel_k.p, sel_c.as<uint32_t>(), n_new};
-  }
-  *out = res;
-  return hipSuccess;
-}
-}  // namespace
-
-extern "C" int mgc_db_merge(const char *const *inputs, uint32_t n_inputs, int op, const char *output, int device, int host_threads) {
-  if (!inputs || n_inputs == 0 || !output || op < MGC_MERGE_UNION_SUM || op > MGC_MERGE_UNION) {
-    set_err(nullptr, "mgc_db_merge: bad arguments");
-    return MGC_EINVAL;
-  }
-  std::vector<mdb_reader *> rd;
-  mdb_info first;
-  if (!open_merge_inputs(inputs, n_inputs, rd, &first, "mgc_db_merge")) return MGC_EINVAL;
-  auto close_all = [&]() { for (mdb_reader *r : rd) if (r) mdb_reader_close(r); };
-  const uint32_t k = first.k, w_prefix = first.prefix_size, kw = k > 32 ? 2u : 1u;
-  if (device < 0) (void)hipGetDevice(&device);
-  mgc_db_stream *d = mgc_db_stream_open(output, k, w_prefix, 0, 0, 0, 1, host_threads, device);
-  if (!d) { close_all(); return MGC_EINVAL; }
-  int rc = MGC_OK;
-  std::string msg;
-  auto hip_fail = [&](hipError_t e, const char *what) {
-    rc = (e == hipErrorOutOfMemory) ? MGC_ENOMEM : MGC_EHIP;
-    msg = std::string("mgc_db_merge: ") + what + ": " + hipGetErrorString(e);
-  };
-#define MG_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { hip_fail(e__, #expr); goto done; } } while (0)
-  {
-    hipStream_t st = nullptr;
-    std::vector<DBuf> in_k(n_inputs), in_c(n_inputs);
-    FoldBufs fb;
-    std::vector<uint64_t> hn;
-    std::vector<SliceRef> in(n_inputs);
-    const uint64_t blocks_per_file = 1ull << (w_prefix - MGC_NUM_FILES_BITS);
-    const bool host_decode = decode_on_host();
-    MG_TRY(hipSetDevice(device));
-    MG_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    for (uint32_t ff = 0; ff < MGC_NUM_FILES && rc == MGC_OK; ff++) {
-      rc = load_slices(rd, ff, kw, in_k, in_c, hn, st, &msg, host_decode);
-      if (rc != MGC_OK) { msg = "mgc_db_merge: " + msg; break; }
-      for (uint32_t i = 0; i < n_inputs; i++) in[i] = SliceRef{in_k[i].p, in_c[i].as<uint32_t>(), hn[i]};
-      SliceRef res;
-      const char *what = "";
-      const hipError_t fe = fold_slices(in, op, kw, fb, in_k[0], in_c[0] /*the first input's buffers are free by then*/, st, &res, &what);
-      if (fe != hipSuccess) { hip_fail(fe, what); break; }
-      rc = mgc_db_stream_write(d, res.k, res.c, res.n, (uint64_t)ff * blocks_per_file, ((uint64_t)ff + 1) * blocks_per_file);
-      if (rc == MGC_OK) rc = mgc_db_stream_sync(d);         // the buffers are reused for the next slice
-      if (rc != MGC_OK) msg = std::string("mgc_db_merge: ") + mgc_db_stream_error(d);
-    }
-  done:
-    for (auto &b : in_k) b.release();
-    for (auto &b : in_c) b.release();
-    fb.release();
-    if (st) (void)hipStreamDestroy(st);
-  }
-#undef MG_TRY
-  close_all();
-  const int rc2 = mgc_db_stream_close(d, nullptr);
-  if (rc == MGC_OK && rc2 != MGC_OK) { rc = rc2; msg = mgc_db_stream_error(nullptr); }
-  if (rc != MGC_OK) set_err(nullptr, "%s", msg.c_str());
-  return rc;
-}
-
-// The single-input operations over a whole database: less-than ... not-equal-to, increase ... modulo (MGC_VALUE_*).
-extern "C" int mgc_db_filter(const char *input, int value_op, uint64_t constant, const char *output, int device, int host_threads) {
-  if (!input || !output || value_op < MGC_VALUE_LESS_THAN || value_op > MGC_VALUE_MODULO) { set_err(nullptr, "mgc_db_filter: bad arguments"); return MGC_EINVAL; }
-  std::vector<mdb_reader *> rd;
-  mdb_info first;
-  const char *ins[1] = {input};
-  if (!open_merge_inputs(ins, 1, rd, &first, "mgc_db_filter")) return MGC_EINVAL;
-  const uint32_t k = first.k, w_prefix = first.prefix_size, kw = k > 32 ? 2u : 1u;
-  if (device < 0) (void)hipGetDevice(&device);
-  mgc_db_stream *d = mgc_db_stream_open(output, k, w_prefix, 0, 0, 0, 1, host_threads, device);
-  if (!d) { mdb_reader_close(rd[0]); return MGC_EINVAL; }
-  int rc = MGC_OK;
-  std::string msg;
-  hipStream_t st = nullptr;
-  std::vector<DBuf> in_k(1), in_c(1);
-  DBuf out_k, out_c, ws;
-  std::vector<uint64_t> hn;
-  const uint64_t blocks_per_file = 1ull << (w_prefix - MGC_NUM_FILES_BITS);
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-  const bool host_decode = decode_on_host();
-  for (uint32_t ff = 0; ff < MGC_NUM_FILES && rc == MGC_OK && e == hipSuccess; ff++) {
-    rc = load_slices(rd, ff, kw, in_k, in_c, hn, st, &msg, host_decode);
-    if (rc != MGC_OK) { msg = "mgc_db_filter: " + msg; break; }
-    uint64_t n_new = 0;
-    e = ws.ensure(mgc::select_workspace_bytes(hn[0]));
-    if (e == hipSuccess) e = mgc::launch_select_count(in_k[0].p, in_c[0].as<uint32_t>(), nullptr, hn[0], kw, value_op, constant, ws.p, st);
-    if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
-    if (e == hipSuccess) e = out_k.ensure(8 * (size_t)kw * n_new);
-    if (e == hipSuccess) e = out_c.ensure(4 * n_new);
-    if (e == hipSuccess) e = mgc::launch_select_emit(in_k[0].p, in_c[0].as<uint32_t>(), nullptr, hn[0], kw, value_op, constant, ws.p, out_k.p, out_c.as<uint32_t>(), st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) break;
-    rc = mgc_db_stream_write(d, out_k.p, out_c.as<uint32_t>(), n_new, (uint64_t)ff * blocks_per_file, ((uint64_t)ff + 1) * blocks_per_file);
-    if (rc == MGC_OK) rc = mgc_db_stream_sync(d);
-    if (rc != MGC_OK) msg = std::string("mgc_db_filter: ") + mgc_db_stream_error(d);
-  }
-  if (e != hipSuccess && rc == MGC_OK) { rc = (e == hipErrorOutOfMemory) ? MGC_ENOMEM : MGC_EHIP; msg = std::string("mgc_db_filter: ") + hipGetErrorString(e); }
-  in_k[0].release(); in_c[0].release(); out_k.release(); out_c.release(); ws.release();
-  if (st) (void)hipStreamDestroy(st);
-  mdb_reader_close(rd[0]);
-  const int rc2 = mgc_db_stream_close(d, nullptr);
-  if (rc == MGC_OK && rc2 != MGC_OK) { rc = rc2; msg = mgc_db_stream_error(nullptr); }
-  if (rc != MGC_OK) set_err(nullptr, "%s", msg.c_str());
-  return rc;
-}
-
-// ================================================================================================
-//  a tree of merge and value operations per file slice (include/meryl_db.h, mgc_db_eval)
-// ================================================================================================
-// The reference nests operations on the command line and streams k-mers through the whole tree, writing only where
-// `output` is given (src/meryl/merylOp-nextMer.C:418-683, :227).  Here the slices of all leaves are loaded once per file,
-// every inner node's result stays in HBM in the node's own buffers, and only outputs and the root's callback leave it.
-namespace {
-// a merge node takes merge_many (one count pass, one emit pass over all inputs) from this many inputs on; below it the
-// two-input merge path kernel.  NOT MEASURED yet: 3 is what the bytes moved suggest; scripts/setops_bench.py leg (a) decides
-// (the smallest N at which merge_many is not slower than the fold on both input mixes).
-constexpr uint32_t MERGE_MANY_MIN_INPUTS = 3;
-
-bool merge_many_enabled() { const char *e = getenv("MGC_MERGE_MANY"); return !(e && e[0] == '0'); }
-
-struct EvalNode {
-  DBuf k, c, l;                    // an inner node's result (l: labelled evaluation)
-  FoldBufs *fold = nullptr;        // merge nodes that fold
-  SliceRef res;
-  mgc_db_stream *out = nullptr;
-  uint32_t leaf = 0;               // leaf: its reader; inner node: its leftmost leaf's
-};
-
-std::string plain_path(const char *p) {
-  std::string s(p);
-  while (s.size() > 1 && s.back() == '/') s.pop_back();
-  return s;
-}
-
-// what mgc_db_eval_labelled adds to a tree: per node the label operation (MGC_LABEL_*) and its constant, the label size of the
-// outputs (0: the largest among the leaves) and the callback that also takes labels
-struct LabelPlan {
-  const mgc_eval_node_labelled *nodes;
-  uint32_t label_size;
-  mgc_eval_slice_labelled_cb cb;
-};
-
-// what mgc_db_eval_selected adds: per node a range of one terms array (a selector program, mgc_selector.hpp), and the callback
-// (the labelled one; labels are zeros when they do not travel)
-struct SelectPlan {
-  const mgc_eval_node_selected *nodes;
-  const mgc_select_term *terms;
-  uint32_t n_terms;
-  mgc_eval_slice_labelled_cb cb;
-};
-
-// what mgc_db_eval_assigned adds: per node a value assignment (MGC_ASSIGN_*, mgc_value.hpp) and its constant
-struct AssignPlan {
-  std::vector<int32_t>  assign;
-  std::vector<uint64_t> constant;
-};
-
-// mgc_db_eval (lp == nullptr), mgc_db_eval_labelled, mgc_db_eval_selected (sp; with or without lp) and mgc_db_eval_assigned (ap, with
-// sp): one walk, one validation, one slice loop
-int eval_impl(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children, uint32_t root,
-              mgc_eval_slice_cb cb, void *ctx, int device, int host_threads, const LabelPlan *lp, const SelectPlan *sp = nullptr,
-              const AssignPlan *ap = nullptr) {
-  const char *who = ap ? "mgc_db_eval_assigned" : sp ? "mgc_db_eval_selected" : lp ? "mgc_db_eval_labelled" : "mgc_db_eval";
-  auto bad = [&](const std::string &m) { set_err(nullptr, "%s: %s", who, m.c_str()); return MGC_EINVAL; };
-  if (!nodes || n_nodes == 0 || root >= n_nodes || (n_children && !children)) return bad("bad arguments");
-  // ---- the tree: every node reached at most once, from the root (post-order = evaluation order)
-  std::vector<uint32_t> order, leaves;
-  {
-    std::vector<uint8_t> seen(n_nodes, 0);
-    struct Frame { uint32_t node, next; };
-    std::vector<Frame> stack;
-    seen[root] = 1;
-    stack.push_back({root, 0});
-    while (!stack.empty()) {
-      Frame &f = stack.back();
-      const mgc_eval_node &nd = nodes[f.node];
-      if (f.next == 0) {
-        const std::string id = "node " + std::to_string(f.node);
-        if (nd.kind < MGC_NODE_DATABASE || nd.kind > MGC_NODE_VALUE) return bad(id + ": unknown kind");
-        if ((uint64_t)nd.first_child + nd.n_children > n_children) return bad(id + ": its children are out of range");
-        if (nd.kind == MGC_NODE_DATABASE && nd.n_children != 0) return bad(id + ": a database has no inputs");
-        if (nd.kind == MGC_NODE_DATABASE && !nd.path) return bad(id + ": a database needs a path");
-        if (nd.kind == MGC_NODE_VALUE && nd.n_children != 1) return bad(id + ": a value operation has exactly one input");
-        if (nd.kind == MGC_NODE_VALUE && (nd.op < MGC_VALUE_LESS_THAN || nd.op > MGC_VALUE_MODULO)) return bad(id + ": unknown value operation");
-        if (nd.kind == MGC_NODE_MERGE && nd.n_children == 0) return bad(id + ": a merge operation needs an input");
-        if (nd.kind == MGC_NODE_MERGE && (nd.op < MGC_MERGE_UNION_SUM || nd.op > MGC_MERGE_UNION)) return bad(id + ": unknown merge operation");
-        if (lp && nd.kind != MGC_NODE_DATABASE) {
-          const int lop = lp->nodes[f.node].label_op;
-          if (mgc::label_kernel_op(nd.kind == MGC_NODE_MERGE, nd.op, lop) < 0) return bad(id + ": unknown label operation " + std::to_string(lop));
-          if (lop == MGC_LABEL_INVERT && nd.n_children > 1) return bad(id + ": label=invert takes one input, the node has " + std::to_string(nd.n_children));
-          // the left fold combines two streams at a time: DIFFERENCE, MIN or LIGHTEST over all inputs at once cannot be folded
-          if (nd.kind == MGC_NODE_MERGE && nd.n_children > MGC_MERGE_MANY_MAX)
-            return bad(id + ": a merge of " + std::to_string(nd.n_children) + " inputs; with labels at most " + std::to_string(MGC_MERGE_MANY_MAX));
-        }
-        if (sp && sp->nodes[f.node].n_terms) {
-          const mgc_eval_node_selected &sn = sp->nodes[f.node];
-          if (nd.kind == MGC_NODE_DATABASE) return bad(id + ": a database takes no selector");
-          if ((uint64_t)sn.first_term + sn.n_terms > sp->n_terms) return bad(id + ": its selector terms are out of range");
-          if (nd.n_children > MGC_MERGE_MANY_MAX)
-            return bad(id + ": a merge of " + std::to_string(nd.n_children) + " inputs; with a selector at most " + std::to_string(MGC_MERGE_MANY_MAX));
-          const std::string m = mgc::select_check(sp->terms + sn.first_term, sn.n_terms, nd.n_children);
-          if (!m.empty()) return bad(id + ": selector: " + m);
-        }
-        if (ap && ap->assign[f.node] != MGC_ASSIGN_NONE) {
-          const int a = ap->assign[f.node];
-          if (mgc::value_kernel_op(a) < 0) return bad(id + ": unknown value assignment " + std::to_string(a));
-          if (nd.kind == MGC_NODE_DATABASE) return bad(id + ": a database takes no value assignment");
-          if (nd.kind == MGC_NODE_VALUE && nd.op > MGC_VALUE_NOT_EQUAL_TO)
-            return bad(id + ": an arithmetic value operation takes no value assignment (the operation is one)");
-          if (nd.n_children > MGC_MERGE_MANY_MAX)
-            return bad(id + ": a merge of " + std::to_string(nd.n_children) + " inputs; with a value assignment at most " + std::to_string(MGC_MERGE_MANY_MAX));
-        }
-      }
-      if (f.next < nd.n_children) {
-        const uint32_t ch = children[nd.first_child + f.next++];
-        if (ch >= n_nodes) return bad("node " + std::to_string(f.node) + ": input " + std::to_string(ch) + " is out of range");
-        if (seen[ch]) return bad("node " + std::to_string(ch) + " is reached twice (an input of two operations, or a cycle)");
-        seen[ch] = 1;
-        stack.push_back({ch, 0});                            // (f is dead from here)
-        continue;
-      }
-      if (nd.kind == MGC_NODE_DATABASE) leaves.push_back(f.node);
-      order.push_back(f.node);
-      stack.pop_back();
-    }
-  }
-  // ---- outputs: named once, and not an input
-  {
-    std::map<std::string, uint32_t> names;
-    for (uint32_t v : leaves) names.emplace(plain_path(nodes[v].path), v);
-    for (uint32_t v : order) {
-      if (nodes[v].kind == MGC_NODE_DATABASE || !nodes[v].path) continue;
-      const auto ins = names.emplace(plain_path(nodes[v].path), v);
-      if (!ins.second)
-        return bad(std::string("output '") + nodes[v].path + "' of node " + std::to_string(v) +
-                   (nodes[ins.first->second].kind == MGC_NODE_DATABASE ? " is also an input" : " is also the output of node " + std::to_string(ins.first->second)));
-    }
-  }
-  // ---- leaves: open, one k, no labels, no multisets (leaves[] is in left-to-right order)
-  std::vector<mdb_reader *> rd;
-  mdb_info first;
-  uint32_t leaf_label_size = 0;
-  {
-    std::vector<const char *> paths;
-    for (uint32_t v : leaves) paths.push_back(nodes[v].path);
-    if (!open_merge_inputs(paths.data(), (uint32_t)paths.size(), rd, &first, who, lp ? &leaf_label_size : nullptr)) return MGC_EINVAL;
-  }
-  const uint32_t label_size = lp ? (lp->label_size ? lp->label_size : leaf_label_size) : 0;
-  if (label_size > 64) { for (mdb_reader *r : rd) if (r) mdb_reader_close(r); return bad("a label has at most 64 bits"); }
-  auto close_readers = [&]() { for (mdb_reader *r : rd) if (r) mdb_reader_close(r); };
-  const uint32_t k = first.k, kw = k > 32 ? 2u : 1u, n_leaves = (uint32_t)leaves.size();
-  std::vector<EvalNode> ev(n_nodes);
-  for (uint32_t i = 0; i < n_leaves; i++) ev[leaves[i]].leaf = i;
-  for (uint32_t v : order)
-    if (nodes[v].kind != MGC_NODE_DATABASE) ev[v].leaf = ev[children[nodes[v].first_child]].leaf;
-  auto w_prefix_of = [&](uint32_t v) { mdb_info inf; mdb_reader_info(rd[ev[v].leaf], &inf); return inf.prefix_size; };
-
-  // ---- device work from here
-  const bool use_many = merge_many_enabled();
-  const bool host_decode = decode_on_host();
-  if (device < 0) (void)hipGetDevice(&device);
-  int rc = MGC_OK;
-  std::string msg;
-  const std::string who_colon = std::string(who) + ": ";
-  auto hip_fail = [&](hipError_t e, const char *what) {
-    if (e == hipSuccess) return false;
-    rc = (e == hipErrorOutOfMemory) ? MGC_ENOMEM : MGC_EHIP;
-    msg = who_colon + what + ": " + hipGetErrorString(e);
-    return true;
-  };
-  for (uint32_t v : order) {
-    if (nodes[v].kind == MGC_NODE_DATABASE || !nodes[v].path) continue;
-    ev[v].out = mgc_db_stream_open(nodes[v].path, k, w_prefix_of(v), label_size, 0, 0, 1, host_threads, device);
-    if (!ev[v].out) { rc = MGC_EINVAL; msg = mgc_db_stream_error(nullptr); break; }
-  }
-  hipStream_t st = nullptr;
-  std::vector<DBuf> in_k(n_leaves), in_c(n_leaves), in_l(lp ? n_leaves : 0);
-  DBuf ws;
-  std::vector<uint64_t> hn, h_keys, h_lo, h_hi, h_labs;
-  std::vector<uint32_t> h_vals;
-  if (rc == MGC_OK && !hip_fail(hipSetDevice(device), "hipSetDevice")) (void)hip_fail(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate");
-
-  // one inner node of one slice: its inputs' results -> its own
-  auto eval_node = [&](uint32_t v) -> bool {
-    const mgc_eval_node &nd = nodes[v];
-    EvalNode &me = ev[v];
-    std::vector<SliceRef> in(nd.n_children);
-    for (uint32_t i = 0; i < nd.n_children; i++) in[i] = ev[children[nd.first_child + i]].res;
-    uint64_t n_new = 0;
-    hipError_t e;
-    if (ap && ap->assign[v] != MGC_ASSIGN_NONE) {            // a node with a value assignment: merge_many whatever its kind and input count
-      const bool is_merge = nd.kind == MGC_NODE_MERGE;
-      const mgc_select_term *terms = sp ? sp->terms + sp->nodes[v].first_term : nullptr;
-      const uint32_t n_terms = sp ? sp->nodes[v].n_terms : 0;
-      const int lop = mgc::label_kernel_op_assigned(is_merge, nd.op, lp ? lp->nodes[v].label_op : MGC_LABEL_DEFAULT, ap->assign[v]);
-      const uint64_t lc = lp ? lp->nodes[v].label_constant : 0;
-      const int vop = mgc::value_kernel_op(ap->assign[v]);
-      // a value filter node: its one input under the presence rule of a union, the filter on the assigned value
-      const int mop = is_merge ? nd.op : MGC_MERGE_UNION, fop = is_merge ? -1 : nd.op;
-      const void *kp[MGC_MERGE_MANY_MAX];
-      const uint32_t *cp[MGC_MERGE_MANY_MAX];
-      const uint64_t *lpp[MGC_MERGE_MANY_MAX];
-      uint64_t nn[MGC_MERGE_MANY_MAX];
-      for (uint32_t i = 0; i < nd.n_children; i++) { kp[i] = in[i].k; cp[i] = in[i].c; lpp[i] = in[i].l; nn[i] = in[i].n; }
-      e = ws.ensure(mgc::merge_many_workspace_bytes(nn, nd.n_children, kw));
-      if (e == hipSuccess) e = mgc::launch_merge_many_count_assigned(kp, cp, lpp, nn, nd.n_children, kw, k, mop, vop, ap->constant[v], fop, nd.constant, lop, lc,
-                                                                     terms, n_terms, ws.p, st);
-      if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
-      if (e == hipSuccess) e = me.k.ensure(8 * (size_t)kw * n_new);
-      if (e == hipSuccess) e = me.c.ensure(4 * n_new);
-      if (e == hipSuccess && lp) e = me.l.ensure(8 * n_new);
-      if (e == hipSuccess) e = mgc::launch_merge_many_emit_assigned(kp, cp, lpp, nn, nd.n_children, kw, k, mop, vop, ap->constant[v], fop, nd.constant, lop, lc,
-                                                                    terms, n_terms, ws.p, me.k.p, me.c.as<uint32_t>(), lp ? me.l.as<uint64_t>() : nullptr, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-      if (hip_fail(e, "merging a slice with a value assignment")) return false;
-      me.res = SliceRef{me.k.p, me.c.as<uint32_t>(), n_new, lp ? me.l.as<uint64_t>() : nullptr};
-      return true;
-    }
-    if (sp && sp->nodes[v].n_terms) {                        // a node with a program: select_kernel, or merge_many whatever its input count
-      const mgc_select_term *terms = sp->terms + sp->nodes[v].first_term;
-      const uint32_t n_terms = sp->nodes[v].n_terms;
-      const int lop = mgc::label_kernel_op(nd.kind == MGC_NODE_MERGE, nd.op, lp ? lp->nodes[v].label_op : MGC_LABEL_DEFAULT);
-      const uint64_t lc = lp ? lp->nodes[v].label_constant : 0;
-      if (nd.kind == MGC_NODE_VALUE) {
-        e = ws.ensure(mgc::select_workspace_bytes(in[0].n));
-        if (e == hipSuccess) e = mgc::launch_select_count_selected(in[0].k, in[0].c, in[0].l, in[0].n, kw, k, nd.op, nd.constant, lop, lc, terms, n_terms, ws.p, st);
-        if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
-        if (e == hipSuccess) e = me.k.ensure(8 * (size_t)kw * n_new);
-        if (e == hipSuccess) e = me.c.ensure(4 * n_new);
-        if (e == hipSuccess && lp) e = me.l.ensure(8 * n_new);
-        if (e == hipSuccess) e = mgc::launch_select_emit_selected(in[0].k, in[0].c, in[0].l, in[0].n, kw, k, nd.op, nd.constant, lop, lc, terms, n_terms, ws.p,
-                                                                  me.k.p, me.c.as<uint32_t>(), lp ? me.l.as<uint64_t>() : nullptr, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (hip_fail(e, "a value operation with a selector")) return false;
-      } else {
-        const void *kp[MGC_MERGE_MANY_MAX];
-        const uint32_t *cp[MGC_MERGE_MANY_MAX];
-        const uint64_t *lpp[MGC_MERGE_MANY_MAX];
-        uint64_t nn[MGC_MERGE_MANY_MAX];
-        for (uint32_t i = 0; i < nd.n_children; i++) { kp[i] = in[i].k; cp[i] = in[i].c; lpp[i] = in[i].l; nn[i] = in[i].n; }
-        e = ws.ensure(mgc::merge_many_workspace_bytes(nn, nd.n_children, kw));
-        if (e == hipSuccess) e = mgc::launch_merge_many_count_selected(kp, cp, lpp, nn, nd.n_children, kw, k, nd.op, lop, lc, terms, n_terms, ws.p, st);
-        if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
-        if (e == hipSuccess) e = me.k.ensure(8 * (size_t)kw * n_new);
-        if (e == hipSuccess) e = me.c.ensure(4 * n_new);
-        if (e == hipSuccess && lp) e = me.l.ensure(8 * n_new);
-        if (e == hipSuccess) e = mgc::launch_merge_many_emit_selected(kp, cp, lpp, nn, nd.n_children, kw, k, nd.op, lop, lc, terms, n_terms, ws.p, me.k.p,
-                                                                      me.c.as<uint32_t>(), lp ? me.l.as<uint64_t>() : nullptr, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (hip_fail(e, "merging a slice with a selector")) return false;
-      }
-      me.res = SliceRef{me.k.p, me.c.as<uint32_t>(), n_new, lp ? me.l.as<uint64_t>() : nullptr};
-      return true;
-    }
-    if (lp) {                                                // labels travel with the k-mers; every merge through merge_many
-      const int lop = mgc::label_kernel_op(nd.kind == MGC_NODE_MERGE, nd.op, lp->nodes[v].label_op);
-      const uint64_t lc = lp->nodes[v].label_constant;
-      if (nd.kind == MGC_NODE_VALUE) {
-        e = ws.ensure(mgc::select_workspace_bytes(in[0].n));
-        if (e == hipSuccess) e = mgc::launch_select_count(in[0].k, in[0].c, nullptr, in[0].n, kw, nd.op, nd.constant, ws.p, st);
-        if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
-        if (e == hipSuccess) e = me.k.ensure(8 * (size_t)kw * n_new);
-        if (e == hipSuccess) e = me.c.ensure(4 * n_new);
-        if (e == hipSuccess) e = me.l.ensure(8 * n_new);
-        if (e == hipSuccess) e = mgc::launch_select_emit_labelled(in[0].k, in[0].c, in[0].l, in[0].n, kw, nd.op, nd.constant, lop, lc, ws.p, me.k.p,
-                                                                  me.c.as<uint32_t>(), me.l.as<uint64_t>(), st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (hip_fail(e, "a value operation")) return false;
-      } else {
-        const void *kp[MGC_MERGE_MANY_MAX];
-        const uint32_t *cp[MGC_MERGE_MANY_MAX];
-        const uint64_t *lpp[MGC_MERGE_MANY_MAX];
-        uint64_t nn[MGC_MERGE_MANY_MAX];
-        for (uint32_t i = 0; i < nd.n_children; i++) { kp[i] = in[i].k; cp[i] = in[i].c; lpp[i] = in[i].l; nn[i] = in[i].n; }
-        e = ws.ensure(mgc::merge_many_workspace_bytes(nn, nd.n_children, kw));
-        if (e == hipSuccess) e = mgc::launch_merge_many_count(kp, cp, nn, nd.n_children, kw, nd.op, ws.p, st, true);
-        if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
-        if (e == hipSuccess) e = me.k.ensure(8 * (size_t)kw * n_new);
-        if (e == hipSuccess) e = me.c.ensure(4 * n_new);
-        if (e == hipSuccess) e = me.l.ensure(8 * n_new);
-        if (e == hipSuccess) e = mgc::launch_merge_many_emit_labelled(kp, cp, lpp, nn, nd.n_children, kw, nd.op, lop, lc, ws.p, me.k.p,
-                                                                      me.c.as<uint32_t>(), me.l.as<uint64_t>(), st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (hip_fail(e, "merging a slice")) return false;
-      }
-      me.res = SliceRef{me.k.p, me.c.as<uint32_t>(), n_new, me.l.as<uint64_t>()};
-      return true;
-    }
-    if (nd.kind == MGC_NODE_VALUE) {
-      e = ws.ensure(mgc::select_workspace_bytes(in[0].n));
-      if (e == hipSuccess) e = mgc::launch_select_count(in[0].k, in[0].c, nullptr, in[0].n, kw, nd.op, nd.constant, ws.p, st);
-      if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
-      if (e == hipSuccess) e = me.k.ensure(8 * (size_t)kw * n_new);
-      if (e == hipSuccess) e = me.c.ensure(4 * n_new);
-      if (e == hipSuccess) e = mgc::launch_select_emit(in[0].k, in[0].c, nullptr, in[0].n, kw, nd.op, nd.constant, ws.p, me.k.p, me.c.as<uint32_t>(), st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-      if (hip_fail(e, "a value operation")) return false;
-      me.res = SliceRef{me.k.p, me.c.as<uint32_t>(), n_new};
-      return true;
-    }
-    if (use_many && nd.n_children >= MERGE_MANY_MIN_INPUTS && nd.n_children <= MGC_MERGE_MANY_MAX) {
-      const void *kp[MGC_MERGE_MANY_MAX];
-      const uint32_t *cp[MGC_MERGE_MANY_MAX];
-      uint64_t nn[MGC_MERGE_MANY_MAX];
-      for (uint32_t i = 0; i < nd.n_children; i++) { kp[i] = in[i].k; cp[i] = in[i].c; nn[i] = in[i].n; }
-      e = ws.ensure(mgc::merge_many_workspace_bytes(nn, nd.n_children, kw));
-      if (e == hipSuccess) e = mgc::launch_merge_many_count(kp, cp, nn, nd.n_children, kw, nd.op, ws.p, st);
-      if (e == hipSuccess) e = mgc::merge_read_total(ws.p, &n_new, st);
-      if (e == hipSuccess) e = me.k.ensure(8 * (size_t)kw * n_new);
-      if (e == hipSuccess) e = me.c.ensure(4 * n_new);
-      if (e == hipSuccess) e = mgc::launch_merge_many_emit(kp, cp, nn, nd.n_children, kw, nd.op, ws.p, me.k.p, me.c.as<uint32_t>(), st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-      if (hip_fail(e, "merging a slice")) return false;
-      me.res = SliceRef{me.k.p, me.c.as<uint32_t>(), n_new};
-      return true;
-    }
-    if (!me.fold) me.fold = new FoldBufs;
-    const char *what = "";
-    e = fold_slices(in, nd.op, kw, *me.fold, me.k, me.c, st, &me.res, &what);
-    return !hip_fail(e, what);
-  };
-
-  for (uint32_t ff = 0; ff < MGC_NUM_FILES && rc == MGC_OK; ff++) {
-    rc = load_slices(rd, ff, kw, in_k, in_c, hn, st, &msg, host_decode, lp ? &in_l : nullptr);
-    if (rc != MGC_OK) { msg = who_colon + msg; break; }
-    for (uint32_t v : order) {
-      EvalNode &me = ev[v];
-      if (nodes[v].kind == MGC_NODE_DATABASE)
-        me.res = SliceRef{in_k[me.leaf].p, in_c[me.leaf].as<uint32_t>(), hn[me.leaf], (lp && in_l[me.leaf].p) ? in_l[me.leaf].as<uint64_t>() : nullptr};
-      else if (!eval_node(v)) break;
-      if (me.out) {
-        const uint64_t blocks_per_file = 1ull << (w_prefix_of(v) - MGC_NUM_FILES_BITS);
-        rc = mgc_db_stream_write_labelled(me.out, me.res.k, me.res.c, label_size ? me.res.l : nullptr, me.res.n, (uint64_t)ff * blocks_per_file,
-                                          ((uint64_t)ff + 1) * blocks_per_file);
-        if (rc != MGC_OK) { msg = who_colon + mgc_db_stream_error(me.out); break; }
-      }
-    }
-    if (rc != MGC_OK) break;
-    if (cb || (lp && lp->cb) || (sp && sp->cb)) {
-      const SliceRef &r = ev[root].res;
-      h_keys.resize((size_t)kw * r.n);
-      h_vals.resize(r.n);
-      if (lp || sp) h_labs.assign(r.n, 0);
-      hipError_t e = hipSuccess;
-      if (r.n) {
-        e = hipMemcpyAsync(h_keys.data(), r.k, 8 * (size_t)kw * r.n, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_vals.data(), r.c, 4 * r.n, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && lp && r.l) e = hipMemcpyAsync(h_labs.data(), r.l, 8 * r.n, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-      }
-      if (hip_fail(e, "copying the root's slice")) break;
-      const uint64_t *lo = h_keys.data(), *hi = nullptr;
-      if (kw == 2) {
-        h_lo.resize(r.n); h_hi.resize(r.n);
-        for (uint64_t j = 0; j < r.n; j++) { h_lo[j] = h_keys[2 * j]; h_hi[j] = h_keys[2 * j + 1]; }
-        lo = h_lo.data(); hi = h_hi.data();
-      }
-      if (sp) sp->cb(ctx, ff, lo, hi, h_vals.data(), h_labs.data(), r.n);
-      else if (lp) lp->cb(ctx, ff, lo, hi, h_vals.data(), h_labs.data(), r.n);
-      else cb(ctx, ff, lo, hi, h_vals.data(), r.n);
-    }
-    for (uint32_t v : order) {                               // the buffers are reused for the next slice
-      if (!ev[v].out) continue;
-      const int rs = mgc_db_stream_sync(ev[v].out);
-      if (rs != MGC_OK && rc == MGC_OK) { rc = rs; msg = who_colon + mgc_db_stream_error(ev[v].out); }
-    }
-  }
-  // an output whose node failed mid-slice may still be encoding from buffers about to go
-  if (rc != MGC_OK) for (uint32_t v : order) if (ev[v].out) (void)mgc_db_stream_sync(ev[v].out);
-  for (auto &b : in_k) b.release();
-  for (auto &b : in_c) b.release();
-  for (auto &b : in_l) b.release();
-  ws.release();
-  for (EvalNode &e : ev) { e.k.release(); e.c.release(); e.l.release(); if (e.fold) { e.fold->release(); delete e.fold; } }
-  if (st) (void)hipStreamDestroy(st);
-  close_readers();
-  for (uint32_t v : order) {
-    if (!ev[v].out) continue;
-    const int rc2 = mgc_db_stream_close(ev[v].out, nullptr);
-    if (rc == MGC_OK && rc2 != MGC_OK) { rc = rc2; msg = mgc_db_stream_error(nullptr); }
-  }
-  if (rc != MGC_OK) set_err(nullptr, "%s", msg.c_str());
-  return rc;
-}
-}  // namespace
-
-extern "C" int mgc_db_eval(const mgc_eval_node *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children, uint32_t root,
-                           mgc_eval_slice_cb cb, void *ctx, int device, int host_threads) {
-  return eval_impl(nodes, n_nodes, children, n_children, root, cb, ctx, device, host_threads, nullptr);
-}
-
-// the same tree with labels (include/meryl_db.h): the label operation of every node is merylOpCompute::findOutputLabel
-// (src/meryl2/merylOpCompute.C:286-395) over the inputs that hold the k-mer
-extern "C" int mgc_db_eval_labelled(const mgc_eval_node_labelled *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
-                                    uint32_t root, uint32_t label_size, mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads) {
-  if (!nodes || n_nodes == 0) { set_err(nullptr, "mgc_db_eval_labelled: bad arguments"); return MGC_EINVAL; }
-  if (label_size > 64) { set_err(nullptr, "mgc_db_eval_labelled: a label has at most 64 bits"); return MGC_EINVAL; }
-  std::vector<mgc_eval_node> base(n_nodes);
-  for (uint32_t i = 0; i < n_nodes; i++) {
-    base[i].kind = nodes[i].kind; base[i].op = nodes[i].op; base[i].constant = nodes[i].constant; base[i].path = nodes[i].path;
-    base[i].first_child = nodes[i].first_child; base[i].n_children = nodes[i].n_children;
-  }
-  LabelPlan lp{nodes, label_size, cb};
-  return eval_impl(base.data(), n_nodes, children, n_children, root, nullptr, ctx, device, host_threads, &lp);
-}
-
-// the same tree with selector programs (include/meryl_db.h): nodes without one take the route they take in mgc_db_eval (labels do
-// not travel) or mgc_db_eval_labelled (they do: with_labels, or a LABEL term anywhere in the tree); ap: mgc_db_eval_assigned
-static int eval_selected_impl(const char *who, const mgc_eval_node_selected *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
-                              uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
-                              mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads, const AssignPlan *ap) {
-  if (!nodes || n_nodes == 0 || (n_terms && !terms)) { set_err(nullptr, "%s: bad arguments", who); return MGC_EINVAL; }
-  if (label_size > 64) { set_err(nullptr, "%s: a label has at most 64 bits", who); return MGC_EINVAL; }
-  std::vector<mgc_eval_node> base(n_nodes);
-  std::vector<mgc_eval_node_labelled> lab(n_nodes);
-  bool labels = with_labels != 0 || label_size != 0;
-  for (uint32_t i = 0; i < n_nodes; i++) {
-    base[i].kind = nodes[i].kind; base[i].op = nodes[i].op; base[i].constant = nodes[i].constant; base[i].path = nodes[i].path;
-    base[i].first_child = nodes[i].first_child; base[i].n_children = nodes[i].n_children;
-    lab[i].kind = nodes[i].kind; lab[i].op = nodes[i].op; lab[i].constant = nodes[i].constant; lab[i].path = nodes[i].path;
-    lab[i].first_child = nodes[i].first_child; lab[i].n_children = nodes[i].n_children;
-    lab[i].label_op = nodes[i].label_op; lab[i].reserved = 0; lab[i].label_constant = nodes[i].label_constant;
-    if ((uint64_t)nodes[i].first_term + nodes[i].n_terms <= n_terms)
-      for (uint32_t j = 0; j < nodes[i].n_terms; j++) labels = labels || terms[nodes[i].first_term + j].quantity == MGC_SEL_LABEL;
-  }
-  LabelPlan lp{lab.data(), label_size, nullptr};
-  SelectPlan sp{nodes, terms, n_terms, cb};
-  return eval_impl(base.data(), n_nodes, children, n_children, root, nullptr, ctx, device, host_threads, labels ? &lp : nullptr, &sp, ap);
-}
-
-extern "C" int mgc_db_eval_selected(const mgc_eval_node_selected *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
-                                    uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
-                                    mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads) {
-  return eval_selected_impl("mgc_db_eval_selected", nodes, n_nodes, children, n_children, root, terms, n_terms, with_labels, label_size, cb, ctx,
-                            device, host_threads, nullptr);
-}
-
-// the same tree with value assignments (include/meryl_db.h): a node without one takes the route it takes in mgc_db_eval_selected
-extern "C" int mgc_db_eval_assigned(const mgc_eval_node_assigned *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
-                                    uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
-                                    mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads) {
-  if (!nodes || n_nodes == 0) { set_err(nullptr, "mgc_db_eval_assigned: bad arguments"); return MGC_EINVAL; }
-  std::vector<mgc_eval_node_selected> sel(n_nodes);
-  AssignPlan ap;
-  ap.assign.resize(n_nodes);
-  ap.constant.resize(n_nodes);
-  for (uint32_t i = 0; i < n_nodes; i++) {
-    sel[i].kind = nodes[i].kind; sel[i].op = nodes[i].op; sel[i].constant = nodes[i].constant; sel[i].path = nodes[i].path;
-    sel[i].first_child = nodes[i].first_child; sel[i].n_children = nodes[i].n_children;
-    sel[i].label_op = nodes[i].label_op; sel[i].reserved = 0; sel[i].label_constant = nodes[i].label_constant;
-    sel[i].first_term = nodes[i].first_term; sel[i].n_terms = nodes[i].n_terms;
-    ap.assign[i] = nodes[i].value_assign; ap.constant[i] = nodes[i].value_constant;
-  }
-  return eval_selected_impl("mgc_db_eval_assigned", sel.data(), n_nodes, children, n_children, root, terms, n_terms, with_labels, label_size, cb, ctx,
-                            device, host_threads, &ap);
 }

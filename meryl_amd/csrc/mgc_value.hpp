@@ -2,7 +2,7 @@
 // merylOpCompute::findOutputValue (src/meryl2/merylOpCompute.C:136-282), named on the command line by value=<word>[#c]
 // (merylCommandBuilder::isAssignValue, src/meryl2/merylCommandBuilder-isAssign.C:44-103); the rules, with the line each comes
 // from, are in include/meryl_gpu_count.h (MGC_ASSIGN_*).  Shared by the kernels (mgc_merge_many.hip), the host code that parses
-// and checks an assignment (mgc_api.cpp, mgc_stream.cpp) and a stand-alone host program (tests/host/value_host.cpp): plain C++,
+// and checks an assignment (mgc_api.cpp, mgc_eval.cpp) and a stand-alone host program (tests/host/value_host.cpp): plain C++,
 // no HIP header needed.
 #pragma once
 #include "mgc_label.hpp"

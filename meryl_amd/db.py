@@ -134,72 +134,6 @@ VALUE_WORDS = {"less-than": 0, "greater-than": 1, "at-least": 2, "at-most": 3, "
                "increase": 6, "decrease": 7, "multiply": 8, "divide": 9, "divide-round": 10, "modulo": 11}
 
 
-def build_tree(tree):
-    """A tree of operations -> (EvalNode array, children array, root index) for mgc_db_eval.  `tree` is a database path, or
-    (word, *children) for the merge operations, or (word, constant, child) for the value operations; a dict {"output": path}
-    as the last element names the database the node writes."""
-    nodes, kids = [], []
-
-    def add(t):
-        if isinstance(t, (str, bytes)):
-            nodes.append((capi.NODE_DATABASE, 0, 0, t if isinstance(t, bytes) else t.encode(), 0, 0))
-            return len(nodes) - 1
-        t = tuple(t)
-        out = None
-        if t and isinstance(t[-1], dict):
-            opts = dict(t[-1])
-            out = opts.pop("output", None)
-            if opts:
-                raise ValueError("unknown options %r" % sorted(opts))
-            t = t[:-1]
-        if not t or not isinstance(t[0], str):
-            raise ValueError("an operation is (word, ...): %r" % (t,))
-        word = t[0]
-        if word in VALUE_WORDS:
-            if len(t) != 3:
-                raise ValueError("'%s' takes a constant and one input" % word)
-            kind, op, constant, args = capi.NODE_VALUE, VALUE_WORDS[word], int(t[1]), t[2:]
-        elif word in MERGE_WORDS:
-            kind, op, constant, args = capi.NODE_MERGE, MERGE_WORDS[word], 0, t[1:]
-        else:
-            raise ValueError("unknown operation '%s'" % word)
-        ch = [add(a) for a in args]
-        first = len(kids)
-        kids.extend(ch)
-        nodes.append((kind, op, constant, None if out is None else (out if isinstance(out, bytes) else out.encode()), first, len(ch)))
-        return len(nodes) - 1
-
-    root = add(tree)
-    arr = (capi.EvalNode * len(nodes))()
-    for e, (kind, op, constant, path, first, n) in zip(arr, nodes):
-        e.kind, e.op, e.constant, e.path, e.first_child, e.n_children = kind, op, constant, path, first, n
-    return arr, (ctypes.c_uint32 * max(len(kids), 1))(*kids), len(kids), root
-
-
-def evaluate(tree, on_slice=None, device=-1, host_threads=8):
-    """A whole tree of merge / value operations over databases in ONE pass over the 64 file slices, intermediate results
-    kept in HBM (mgc_db_eval).  Nodes given {"output": path} write a database; on_slice(file, lo, hi_or_None, values)
-    receives the root's slices (numpy copies), files ascending."""
-    arr, kids, n_kids, root = build_tree(tree)
-    failure = []
-
-    def trampoline(ctx, ff, lo, hi, vals, n):
-        try:
-            def take(p, dtype):
-                return np.ctypeslib.as_array(p, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype=dtype)
-            on_slice(ff, take(lo, np.uint64), take(hi, np.uint64) if hi else None, take(vals, np.uint32))
-        except BaseException as e:                               # not through the C frames
-            failure.append(e)
-
-    cb = capi.EVAL_SLICE_CB(trampoline) if on_slice is not None else ctypes.cast(None, capi.EVAL_SLICE_CB)
-    rc = capi.lib().mgc_db_eval(arr, len(arr), kids, n_kids, root, cb, None, device, host_threads)
-    if failure:
-        raise failure[0]
-    if rc != 0:
-        msg = capi.lib().mgc_db_stream_error(None)
-        raise capi.MgcError(rc, "mgc_db_eval", msg.decode("utf-8", "replace") if msg else "")
-
-
 def _label_option(label):
     """the "label" option of a node -> (MGC_LABEL_* code, constant): "or", ("and", 0x0F), or a number for the word"""
     if label is None:
@@ -211,61 +145,6 @@ def _label_option(label):
     if const is None:
         const = int(capi.lib().mgc_label_default_constant(code))
     return code, int(const) & 0xFFFFFFFFFFFFFFFF
-
-
-def build_tree_labelled(tree):
-    """build_tree for mgc_db_eval_labelled: the same trees, and the options dict of a node also takes "label": a word of
-    capi.LABEL_OPS ("or"), or (word, constant) (("and", 0x0F)); without it the node's label operation is the default of its
-    operation.  -> (EvalNodeLabelled array, children array, number of children, root index)"""
-    labels = []
-
-    def strip(t):
-        if isinstance(t, (str, bytes)):
-            labels.append(None)
-            return t
-        t = tuple(t)
-        opts = {}
-        if t and isinstance(t[-1], dict):
-            opts = dict(t[-1])
-            t = t[:-1]
-        label = opts.pop("label", None)
-        head = 2 if t and t[0] in VALUE_WORDS else 1
-        kids = tuple(strip(a) for a in t[head:])               # children first: the order build_tree numbers the nodes in
-        labels.append(label)
-        return t[:head] + kids + ((opts,) if opts else ())
-
-    plain, kids, n_kids, root = build_tree(strip(tree))
-    assert len(labels) == len(plain)
-    arr = (capi.EvalNodeLabelled * len(plain))()
-    for e, b, label in zip(arr, plain, labels):
-        e.kind, e.op, e.constant, e.path, e.first_child, e.n_children = b.kind, b.op, b.constant, b.path, b.first_child, b.n_children
-        e.label_op, e.label_constant = _label_option(label) if b.kind != capi.NODE_DATABASE else (0, 0)
-    return arr, kids, n_kids, root
-
-
-def evaluate_labelled(tree, on_slice=None, label_size=0, device=-1, host_threads=8):
-    """evaluate() over databases that may store labels (mgc_db_eval_labelled): every node combines the labels of the inputs
-    that hold a k-mer with its "label" option (build_tree_labelled), outputs store label_size bits per k-mer (0: the largest
-    label size among the leaves), and on_slice(file, lo, hi_or_None, values, labels) also receives the root's labels as
-    full 64-bit values."""
-    arr, kids, n_kids, root = build_tree_labelled(tree)
-    failure = []
-
-    def trampoline(ctx, ff, lo, hi, vals, labs, n):
-        try:
-            def take(p, dtype):
-                return np.ctypeslib.as_array(p, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype=dtype)
-            on_slice(ff, take(lo, np.uint64), take(hi, np.uint64) if hi else None, take(vals, np.uint32), take(labs, np.uint64))
-        except BaseException as e:                               # not through the C frames
-            failure.append(e)
-
-    cb = capi.EVAL_SLICE_LABELLED_CB(trampoline) if on_slice is not None else ctypes.cast(None, capi.EVAL_SLICE_LABELLED_CB)
-    rc = capi.lib().mgc_db_eval_labelled(arr, len(arr), kids, n_kids, root, int(label_size), cb, None, device, host_threads)
-    if failure:
-        raise failure[0]
-    if rc != 0:
-        msg = capi.lib().mgc_db_stream_error(None)
-        raise capi.MgcError(rc, "mgc_db_eval_labelled", msg.decode("utf-8", "replace") if msg else "")
 
 
 def parse_selector(words, n_inputs):
@@ -280,68 +159,6 @@ def parse_selector(words, n_inputs):
         msg = capi.lib().mgc_last_error(None)
         raise capi.MgcError(rc, "mgc_select_parse", msg.decode("utf-8", "replace") if msg else "")
     return [terms[i] for i in range(n.value)]
-
-
-def build_tree_selected(tree):
-    """build_tree_labelled for mgc_db_eval_selected: the options dict of a node also takes "select": [words...], the selector
-    words of the command line, parsed for the node's input count.
-    -> (EvalNodeSelected array, children array, number of children, root index, SelectTerm array, number of terms)"""
-    selects = []
-
-    def strip(t):
-        if isinstance(t, (str, bytes)):
-            selects.append(None)
-            return t
-        t = tuple(t)
-        opts = {}
-        if t and isinstance(t[-1], dict):
-            opts = dict(t[-1])
-            t = t[:-1]
-        words = opts.pop("select", None)
-        head = 2 if t and t[0] in VALUE_WORDS else 1
-        kids = tuple(strip(a) for a in t[head:])
-        selects.append(None if words is None else ([words] if isinstance(words, str) else list(words)))
-        return t[:head] + kids + ((opts,) if opts else ())
-
-    lab, kids, n_kids, root = build_tree_labelled(strip(tree))
-    assert len(selects) == len(lab)
-    arr = (capi.EvalNodeSelected * len(lab))()
-    terms = []
-    for e, b, words in zip(arr, lab, selects):
-        e.kind, e.op, e.constant, e.path, e.first_child, e.n_children = b.kind, b.op, b.constant, b.path, b.first_child, b.n_children
-        e.label_op, e.label_constant = b.label_op, b.label_constant
-        e.first_term, e.n_terms = len(terms), 0
-        if words:
-            got = parse_selector(words, b.n_children)
-            e.n_terms = len(got)
-            terms.extend(got)
-    tarr = (capi.SelectTerm * max(len(terms), 1))(*terms)
-    return arr, kids, n_kids, root, tarr, len(terms)
-
-
-def evaluate_selected(tree, on_slice=None, with_labels=False, label_size=0, device=-1, host_threads=8):
-    """evaluate_labelled() for trees whose nodes may carry selectors (mgc_db_eval_selected).  Labels travel when with_labels
-    or label_size is set or a label: selector asks for them; otherwise the tree is evaluated as evaluate() does, and
-    on_slice(file, lo, hi_or_None, values, labels) receives zeros for labels."""
-    arr, kids, n_kids, root, terms, n_terms = build_tree_selected(tree)
-    failure = []
-
-    def trampoline(ctx, ff, lo, hi, vals, labs, n):
-        try:
-            def take(p, dtype):
-                return np.ctypeslib.as_array(p, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype=dtype)
-            on_slice(ff, take(lo, np.uint64), take(hi, np.uint64) if hi else None, take(vals, np.uint32), take(labs, np.uint64))
-        except BaseException as e:                               # not through the C frames
-            failure.append(e)
-
-    cb = capi.EVAL_SLICE_LABELLED_CB(trampoline) if on_slice is not None else ctypes.cast(None, capi.EVAL_SLICE_LABELLED_CB)
-    rc = capi.lib().mgc_db_eval_selected(arr, len(arr), kids, n_kids, root, terms, n_terms, int(bool(with_labels)), int(label_size), cb, None,
-                                         device, host_threads)
-    if failure:
-        raise failure[0]
-    if rc != 0:
-        msg = capi.lib().mgc_db_stream_error(None)
-        raise capi.MgcError(rc, "mgc_db_eval_selected", msg.decode("utf-8", "replace") if msg else "")
 
 
 def parse_value_assign(text):
@@ -371,35 +188,153 @@ def value_assign_option(value):
     return code, int(const) & 0xFFFFFFFFFFFFFFFF
 
 
-def build_tree_assigned(tree):
-    """build_tree_selected for mgc_db_eval_assigned: the options dict of a node also takes "value": what follows value= on the
-    command line ("sub#3") or (word, constant) (value_assign_option).
-    -> (EvalNodeAssigned array, children array, number of children, root index, SelectTerm array, number of terms)"""
-    values = []
+def _walk(tree, allowed):
+    """The one tree walk: `tree` is a database path, or (word, *children) for the merge operations, or (word, constant, child) for
+    the value operations; a dict as the last element holds the node's options, of which only `allowed` are taken.
+    -> ([node record], [children], root index); a record is a dict of kind, op, constant, path, first, n and the raw options
+    label, select, value (None where not given); children come before their parent."""
+    nodes, kids = [], []
 
-    def strip(t):
+    def add(t):
         if isinstance(t, (str, bytes)):
-            values.append(None)
-            return t
+            nodes.append(dict(kind=capi.NODE_DATABASE, op=0, constant=0, path=t if isinstance(t, bytes) else t.encode(), first=0, n=0,
+                              label=None, select=None, value=None))
+            return len(nodes) - 1
         t = tuple(t)
         opts = {}
         if t and isinstance(t[-1], dict):
             opts = dict(t[-1])
             t = t[:-1]
-        value = opts.pop("value", None)
-        head = 2 if t and t[0] in VALUE_WORDS else 1
-        kids = tuple(strip(a) for a in t[head:])
-        values.append(value)
-        return t[:head] + kids + ((opts,) if opts else ())
+        unknown = sorted(set(opts) - set(allowed))
+        if unknown:
+            raise ValueError("unknown options %r" % unknown)
+        if not t or not isinstance(t[0], str):
+            raise ValueError("an operation is (word, ...): %r" % (t,))
+        word = t[0]
+        if word in VALUE_WORDS:
+            if len(t) != 3:
+                raise ValueError("'%s' takes a constant and one input" % word)
+            kind, op, constant, args = capi.NODE_VALUE, VALUE_WORDS[word], int(t[1]), t[2:]
+        elif word in MERGE_WORDS:
+            kind, op, constant, args = capi.NODE_MERGE, MERGE_WORDS[word], 0, t[1:]
+        else:
+            raise ValueError("unknown operation '%s'" % word)
+        ch = [add(a) for a in args]
+        out, words = opts.get("output"), opts.get("select")
+        nodes.append(dict(kind=kind, op=op, constant=constant, path=None if out is None else (out if isinstance(out, bytes) else out.encode()),
+                          first=len(kids), n=len(ch), label=opts.get("label"), value=opts.get("value"),
+                          select=None if words is None else ([words] if isinstance(words, str) else list(words))))
+        kids.extend(ch)
+        return len(nodes) - 1
 
-    sel, kids, n_kids, root, terms, n_terms = build_tree_selected(strip(tree))
-    assert len(values) == len(sel)
-    arr = (capi.EvalNodeAssigned * len(sel))()
-    for e, b, value in zip(arr, sel, values):
-        e.kind, e.op, e.constant, e.path, e.first_child, e.n_children = b.kind, b.op, b.constant, b.path, b.first_child, b.n_children
-        e.label_op, e.label_constant, e.first_term, e.n_terms = b.label_op, b.label_constant, b.first_term, b.n_terms
-        e.value_assign, e.value_constant = value_assign_option(value)
-    return arr, kids, n_kids, root, terms, n_terms
+    root = add(tree)
+    return nodes, kids, root
+
+
+def _fill(struct, tree, allowed):
+    """_walk -> an array of `struct` with the fields of the options in `allowed` set: label -> label_op / label_constant, select ->
+    first_term / n_terms (parsed for the node's input count), value -> value_assign / value_constant.
+    -> (array, children array, number of children, root index, SelectTerm array, number of terms)"""
+    nodes, kids, root = _walk(tree, allowed)
+    arr = (struct * len(nodes))()
+    for e, r in zip(arr, nodes):
+        e.kind, e.op, e.constant, e.path, e.first_child, e.n_children = r["kind"], r["op"], r["constant"], r["path"], r["first"], r["n"]
+    inner = [(e, r) for e, r in zip(arr, nodes) if r["kind"] != capi.NODE_DATABASE]
+    if "label" in allowed:
+        for e, r in inner:
+            e.label_op, e.label_constant = _label_option(r["label"])
+    terms = []
+    if "select" in allowed:
+        for e, r in zip(arr, nodes):
+            e.first_term, e.n_terms = len(terms), 0
+            if r["select"]:
+                got = parse_selector(r["select"], r["n"])
+                e.n_terms = len(got)
+                terms.extend(got)
+    if "value" in allowed:
+        for e, r in inner:
+            e.value_assign, e.value_constant = value_assign_option(r["value"])
+    return arr, (ctypes.c_uint32 * max(len(kids), 1))(*kids), len(kids), root, (capi.SelectTerm * max(len(terms), 1))(*terms), len(terms)
+
+
+def build_tree(tree):
+    """A tree of operations -> (EvalNode array, children array, number of children, root index) for mgc_db_eval.  `tree` is a
+    database path, or (word, *children) for the merge operations, or (word, constant, child) for the value operations; a dict
+    {"output": path} as the last element names the database the node writes."""
+    return _fill(capi.EvalNode, tree, ("output",))[:4]
+
+
+def build_tree_labelled(tree):
+    """build_tree for mgc_db_eval_labelled: the same trees, and the options dict of a node also takes "label": a word of
+    capi.LABEL_OPS ("or"), or (word, constant) (("and", 0x0F)); without it the node's label operation is the default of its
+    operation.  -> (EvalNodeLabelled array, children array, number of children, root index)"""
+    return _fill(capi.EvalNodeLabelled, tree, ("output", "label"))[:4]
+
+
+def build_tree_selected(tree):
+    """build_tree_labelled for mgc_db_eval_selected: the options dict of a node also takes "select": [words...], the selector
+    words of the command line, parsed for the node's input count.
+    -> (EvalNodeSelected array, children array, number of children, root index, SelectTerm array, number of terms)"""
+    return _fill(capi.EvalNodeSelected, tree, ("output", "label", "select"))
+
+
+def build_tree_assigned(tree):
+    """build_tree_selected for mgc_db_eval_assigned: the options dict of a node also takes "value": what follows value= on the
+    command line ("sub#3") or (word, constant) (value_assign_option).
+    -> (EvalNodeAssigned array, children array, number of children, root index, SelectTerm array, number of terms)"""
+    return _fill(capi.EvalNodeAssigned, tree, ("output", "label", "select", "value"))
+
+
+def _evaluate(name, call, on_slice, labelled=True):
+    """One evaluation through entry point `name`: call(cb) makes the native call with the slice callback; on_slice receives numpy
+    copies (file, lo, hi_or_None, values[, labels]); an exception it raises is relayed once the native call has returned."""
+    failure = []
+
+    def trampoline(ctx, ff, lo, hi, vals, *rest):
+        n = rest[-1]
+        try:
+            def take(p, dtype):
+                return np.ctypeslib.as_array(p, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype=dtype)
+            on_slice(ff, take(lo, np.uint64), take(hi, np.uint64) if hi else None, take(vals, np.uint32), *[take(p, np.uint64) for p in rest[:-1]])
+        except BaseException as e:                               # not through the C frames
+            failure.append(e)
+
+    cb_type = capi.EVAL_SLICE_LABELLED_CB if labelled else capi.EVAL_SLICE_CB
+    rc = call(cb_type(trampoline) if on_slice is not None else ctypes.cast(None, cb_type))
+    if failure:
+        raise failure[0]
+    if rc != 0:
+        msg = capi.lib().mgc_db_stream_error(None)
+        raise capi.MgcError(rc, name, msg.decode("utf-8", "replace") if msg else "")
+
+
+def evaluate(tree, on_slice=None, device=-1, host_threads=8):
+    """A whole tree of merge / value operations over databases in ONE pass over the 64 file slices, intermediate results
+    kept in HBM (mgc_db_eval).  Nodes given {"output": path} write a database; on_slice(file, lo, hi_or_None, values)
+    receives the root's slices (numpy copies), files ascending."""
+    arr, kids, n_kids, root = build_tree(tree)
+    _evaluate("mgc_db_eval", lambda cb: capi.lib().mgc_db_eval(arr, len(arr), kids, n_kids, root, cb, None, device, host_threads), on_slice,
+              labelled=False)
+
+
+def evaluate_labelled(tree, on_slice=None, label_size=0, device=-1, host_threads=8):
+    """evaluate() over databases that may store labels (mgc_db_eval_labelled): every node combines the labels of the inputs
+    that hold a k-mer with its "label" option (build_tree_labelled), outputs store label_size bits per k-mer (0: the largest
+    label size among the leaves), and on_slice(file, lo, hi_or_None, values, labels) also receives the root's labels as
+    full 64-bit values."""
+    arr, kids, n_kids, root = build_tree_labelled(tree)
+    _evaluate("mgc_db_eval_labelled",
+              lambda cb: capi.lib().mgc_db_eval_labelled(arr, len(arr), kids, n_kids, root, int(label_size), cb, None, device, host_threads), on_slice)
+
+
+def evaluate_selected(tree, on_slice=None, with_labels=False, label_size=0, device=-1, host_threads=8):
+    """evaluate_labelled() for trees whose nodes may carry selectors (mgc_db_eval_selected).  Labels travel when with_labels
+    or label_size is set or a label: selector asks for them; otherwise the tree is evaluated as evaluate() does, and
+    on_slice(file, lo, hi_or_None, values, labels) receives zeros for labels."""
+    arr, kids, n_kids, root, terms, n_terms = build_tree_selected(tree)
+    _evaluate("mgc_db_eval_selected",
+              lambda cb: capi.lib().mgc_db_eval_selected(arr, len(arr), kids, n_kids, root, terms, n_terms, int(bool(with_labels)), int(label_size), cb,
+                                                         None, device, host_threads), on_slice)
 
 
 def evaluate_assigned(tree, on_slice=None, with_labels=False, label_size=0, device=-1, host_threads=8):
@@ -407,21 +342,6 @@ def evaluate_assigned(tree, on_slice=None, with_labels=False, label_size=0, devi
     keeps the presence rule of its operation and computes the value of a written k-mer by the assignment; k-mers whose assigned
     value is 0 are not written, and the node's selector and a value filter see the assigned value."""
     arr, kids, n_kids, root, terms, n_terms = build_tree_assigned(tree)
-    failure = []
-
-    def trampoline(ctx, ff, lo, hi, vals, labs, n):
-        try:
-            def take(p, dtype):
-                return np.ctypeslib.as_array(p, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype=dtype)
-            on_slice(ff, take(lo, np.uint64), take(hi, np.uint64) if hi else None, take(vals, np.uint32), take(labs, np.uint64))
-        except BaseException as e:                               # not through the C frames
-            failure.append(e)
-
-    cb = capi.EVAL_SLICE_LABELLED_CB(trampoline) if on_slice is not None else ctypes.cast(None, capi.EVAL_SLICE_LABELLED_CB)
-    rc = capi.lib().mgc_db_eval_assigned(arr, len(arr), kids, n_kids, root, terms, n_terms, int(bool(with_labels)), int(label_size), cb, None,
-                                         device, host_threads)
-    if failure:
-        raise failure[0]
-    if rc != 0:
-        msg = capi.lib().mgc_db_stream_error(None)
-        raise capi.MgcError(rc, "mgc_db_eval_assigned", msg.decode("utf-8", "replace") if msg else "")
+    _evaluate("mgc_db_eval_assigned",
+              lambda cb: capi.lib().mgc_db_eval_assigned(arr, len(arr), kids, n_kids, root, terms, n_terms, int(bool(with_labels)), int(label_size), cb,
+                                                         None, device, host_threads), on_slice)
