@@ -352,6 +352,51 @@ int mgc_db_eval_assigned(const mgc_eval_node_assigned *nodes, uint32_t n_nodes, 
                          uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
                          mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads);
 
+/* ------------------------------------------------------------------------
+ * The value histogram of device-resident values (meryl_amd/csrc/mgc_value_hist.hip): value -> number of k-mers that carry it,
+ * what merylHistogram collects per compute thread and `output:histogram` / `output:statistics` report for any action of
+ * meryl2 (src/meryl2/merylOpTemplate.C:168-209,285-307).  An accumulator is opened, fed any number of arrays and read:
+ * values below a dense limit are counted in LDS bins and flushed into uint64 device bins; the others go onto a device list
+ * with room for every value of the call (no overflow, no second pass), which is sorted and run-length counted ON THE DEVICE --
+ * only (value, occurrences) pairs cross to the host, so the traffic follows the DISTINCT large values, never the k-mers.
+ * The result is exact for any uint32 values (0 and 2^32-1 included).
+ * mgc_value_hist_open never fails for want of a device: the device (-1: the current one) is first touched by the first
+ * non-empty add.  add: d_values is DEVICE memory, 4-byte aligned; `stream` is where the values were produced; the call
+ * returns once they are counted (the array may be reused).  get: ascending by value, arrays of mgc_value_hist_len entries.
+ * totals: unique = occurrences of value 1, distinct = sum of occurrences, total = sum(value * occurrences) in uint64 --
+ * the three numbers of the master index's histogram header; any of the three may be NULL.
+ * geometry: the dense limit and the values one workgroup takes per iteration (tests aim at both).
+ * One accumulator is used by one thread at a time.  An add that fails may have counted part of its values: the accumulator is
+ * unusable from then on -- every later add, len, get and totals returns MGC_ESTATE -- and can only be closed.
+ * Failure text: mgc_db_stream_error(NULL). */
+typedef struct mgc_value_hist mgc_value_hist;
+mgc_value_hist *mgc_value_hist_open(int device);
+int  mgc_value_hist_add(mgc_value_hist *h, const uint32_t *d_values, uint64_t n, void *stream);
+int  mgc_value_hist_len(mgc_value_hist *h, uint64_t *n_pairs);
+int  mgc_value_hist_get(mgc_value_hist *h, uint64_t *values, uint64_t *occurrences);
+int  mgc_value_hist_totals(mgc_value_hist *h, uint64_t *unique, uint64_t *distinct, uint64_t *total);
+void mgc_value_hist_close(mgc_value_hist *h);
+void mgc_value_hist_geometry(uint32_t *dense_limit, uint32_t *workgroup_values);
+
+/* mgc_db_eval_assigned with REPORTS: want_hist[v] != 0 asks for the value histogram of node v's result over all 64 slices --
+ * an inner node's, the root's, or a leaf's (from its decoded values; it equals the one its master index stores).  After every
+ * slice the flagged nodes' values are added to their accumulators on the device.  On success hists[v] is an accumulator to
+ * read and close (mgc_value_hist_*) for every flagged node and NULL for the others; on failure every entry is NULL.
+ * want_hist == NULL, or no node flagged: exactly mgc_db_eval_assigned -- the same routes, the same outputs byte for byte
+ * (hists, if given, is filled with NULLs).  Checked with everything mgc_db_eval_assigned checks, before any device call and
+ * before any output directory exists (MGC_EINVAL with text): a node flagged and hists NULL; want_hist set on a node the
+ * root does not reach. */
+int mgc_db_eval_reported(const mgc_eval_node_assigned *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
+                         uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
+                         mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads,
+                         const uint8_t *want_hist /*[n_nodes]*/, mgc_value_hist **hists /*[n_nodes], out*/);
+
+/* The `statistics` report of a histogram as text (src/meryl/merylOp-histogram.C:65-93): the four header lines, the column
+ * titles and one row per pair.  Host only.  Returns the length of the text (without the final NUL); up to buf_size - 1
+ * characters of it and a NUL are written to buf (buf may be NULL with buf_size 0: the length alone). */
+size_t mdb_format_statistics(uint32_t k, const uint64_t *values, const uint64_t *occurrences, uint64_t n_pairs,
+                             uint64_t num_unique, uint64_t num_distinct, uint64_t num_total, char *buf, size_t buf_size);
+
 /* ONE count spread over the GPUs of a node, from one process (meryl_amd/csrc/mgc_node.cpp): rank r's reads are the
  * n_bases[r] bytes at d_bases[r] on device devices[r] (the base stream mgc_push_bases takes; with cfg->homopoly_compress
  * every rank's stream must hold whole sequences).  Every rank extracts the k-mers of its reads, the k-mers travel over

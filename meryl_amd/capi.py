@@ -38,7 +38,9 @@ SYMBOLS = (
     "mdb_reader_open", "mdb_reader_info", "mdb_reader_histogram", "mdb_reader_read_file", "mdb_reader_read_file_ex",
     "mdb_reader_file_index", "mdb_reader_block_header", "mdb_reader_read_block_raw", "mdb_reader_raw_file", "mdb_reader_close",
     "mdb_free", "mgc_write_database", "mgc_write_database_profiled",
-    "mgc_db_stream_open", "mgc_db_stream_write", "mgc_db_stream_write_labelled", "mgc_db_eval_labelled", "mgc_db_eval_selected", "mgc_db_eval_assigned", "mgc_db_stream_sync", "mgc_db_stream_close", "mgc_db_stream_error", "mgc_db_stream_queued", "mgc_db_stream_done", "mgc_db_stream_wait_buffers",
+    "mgc_db_stream_open", "mgc_db_stream_write", "mgc_db_stream_write_labelled", "mgc_db_eval_labelled", "mgc_db_eval_selected", "mgc_db_eval_assigned", "mgc_db_eval_reported", "mgc_db_stream_sync", "mgc_db_stream_close", "mgc_db_stream_error", "mgc_db_stream_queued", "mgc_db_stream_done", "mgc_db_stream_wait_buffers",
+    "mgc_value_hist_open", "mgc_value_hist_add", "mgc_value_hist_len", "mgc_value_hist_get", "mgc_value_hist_totals", "mgc_value_hist_close",
+    "mgc_value_hist_geometry", "mdb_format_statistics", "mgc_dev_value_hist_listed_bins", "mgc_dev_value_hist_listed",
     "mgc_runs_open", "mgc_runs_add", "mgc_runs_write", "mgc_runs_get_profile", "mgc_runs_error", "mgc_runs_close", "mgc_get_runs_profile", "mgc_db_merge", "mgc_db_filter", "mgc_db_eval", "mgc_count_node", "mgc_count_node_batched", "mgc_count_node_staged", "mgc_node_plan",
     # include/meryl_lookup.h
     "mgc_lookup_load", "mgc_lookup_estimate", "mgc_lookup_from_device", "mgc_lookup_free", "mgc_lookup_get_info", "mgc_lookup_error",
@@ -516,6 +518,18 @@ def lib():
     sig("mgc_db_eval_labelled", i32, P(EvalNodeLabelled), u32, P(u32), u32, u32, u32, EVAL_SLICE_LABELLED_CB, vp, i32, i32)
     sig("mgc_db_eval_selected", i32, P(EvalNodeSelected), u32, P(u32), u32, u32, P(SelectTerm), u32, i32, u32, EVAL_SLICE_LABELLED_CB, vp, i32, i32)
     sig("mgc_db_eval_assigned", i32, P(EvalNodeAssigned), u32, P(u32), u32, u32, P(SelectTerm), u32, i32, u32, EVAL_SLICE_LABELLED_CB, vp, i32, i32)
+    sig("mgc_db_eval_reported", i32, P(EvalNodeAssigned), u32, P(u32), u32, u32, P(SelectTerm), u32, i32, u32, EVAL_SLICE_LABELLED_CB, vp, i32, i32,
+        P(ctypes.c_uint8), P(vp))
+    sig("mgc_value_hist_open", vp, i32)
+    sig("mgc_value_hist_add", i32, vp, vp, u64, vp)
+    sig("mgc_value_hist_len", i32, vp, P(u64))
+    sig("mgc_value_hist_get", i32, vp, vp, vp)
+    sig("mgc_value_hist_totals", i32, vp, P(u64), P(u64), P(u64))
+    sig("mgc_value_hist_close", None, vp)
+    sig("mgc_value_hist_geometry", None, P(u32), P(u32))
+    sig("mgc_dev_value_hist_listed_bins", u32)
+    sig("mgc_dev_value_hist_listed", i32, vp, u64, vp, vp, u64, vp, P(u64), P(u64))
+    sig("mdb_format_statistics", sz, u32, vp, vp, u64, u64, u64, u64, ctypes.c_char_p, sz)
     sig("mgc_count_node", i32, P(CountConfig), u32, P(ctypes.c_int), P(vp), P(u64), ctypes.c_char_p, i32, P(NodeProfile))
     sig("mgc_count_node_batched", i32, P(CountConfig), u32, P(ctypes.c_int), P(vp), P(u64), u64, ctypes.c_char_p, i32, P(NodeProfile))
     sig("mgc_staged_bases", i32, vp, P(vp), P(u64))

@@ -38,6 +38,7 @@
 #include "../../include/meryl_db.h"
 #include "../../include/meryl_gpu_count.h"
 #include "mdb_layout.h"
+#include "mdb_statistics.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -938,3 +939,16 @@ extern "C" int mdb_reader_read_file(mdb_reader *r, uint32_t ff, uint64_t **klo, 
 extern "C" void mdb_reader_close(mdb_reader *r) { delete r; }
 extern "C" void mdb_free(void *p) { free(p); }
 
+
+// the `statistics` report as text (mdb_statistics.hpp; src/meryl/merylOp-histogram.C:65-93)
+extern "C" size_t mdb_format_statistics(uint32_t k, const uint64_t *values, const uint64_t *occurrences, uint64_t n_pairs,
+                                        uint64_t num_unique, uint64_t num_distinct, uint64_t num_total, char *buf, size_t buf_size) {
+  if (n_pairs && (!values || !occurrences)) n_pairs = 0;
+  const std::string text = mdb::format_statistics(k, values, occurrences, n_pairs, num_unique, num_distinct, num_total);
+  if (buf && buf_size) {
+    const size_t n = std::min(text.size(), buf_size - 1);
+    memcpy(buf, text.data(), n);
+    buf[n] = 0;
+  }
+  return text.size();
+}

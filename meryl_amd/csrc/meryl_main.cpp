@@ -24,8 +24,12 @@
 // a written k-mer comes from its inputs' values (merylCommandBuilder-isAssign.C:44-103, merylOpCompute.C:136-282): the operation
 // then gives the presence rule only, k-mers whose assigned value is 0 are not written, and selectors and the filter see the
 // assigned value.  The text is decoded by the library's parser (mgc_value_assign_parse) and a tree that holds any is evaluated
-// through mgc_db_eval_assigned; the arithmetic value operations and the counting operations refuse it.
-// What stays refused: statistics, compare, ploidy, Canu sequence stores (segment=); CRAM only when no `samtools` is on the PATH.
+// through mgc_db_eval_assigned; the arithmetic value operations and the counting operations refuse it.  Reports: `histogram` and
+// `statistics` (src/meryl/merylOp-histogram.C:20-97) take a database -- the histogram its master index stores, host only -- or an
+// operation, whose tree is then evaluated once with the value histogram of its root collected on the device (mgc_db_eval_reported);
+// meryl2's `output:histogram[=file]` and `output:statistics[=file]` (merylCommandBuilder-processText.C:153-154,
+// merylOpTemplate.C:168-209,285-307) ask the same of any set or value operation of a tree, to a file or (no file, or `-`) stdout.
+// What stays refused: compare, ploidy, noise, printACGT, Canu sequence stores (segment=); CRAM only when no `samtools` is on the PATH.
 #include "../../include/meryl_db.h"
 #include "../../include/meryl_gpu_count.h"
 #include "../../include/meryl_seq.h"
@@ -76,7 +80,7 @@ bool has_compressed_suffix(const std::string &n) {
   return false;
 }
 
-enum OpKind { OP_NONE, OP_COUNT, OP_COUNT_FORWARD, OP_COUNT_REVERSE, OP_PRINT, OP_DUMPINDEX, OP_HISTOGRAM, OP_DUMPFILE, OP_MERGE, OP_VALUE };
+enum OpKind { OP_NONE, OP_COUNT, OP_COUNT_FORWARD, OP_COUNT_REVERSE, OP_PRINT, OP_DUMPINDEX, OP_HISTOGRAM, OP_STATISTICS, OP_DUMPFILE, OP_MERGE, OP_VALUE };
 
 struct InputRef { std::string path; int child = -1; };      // a database on the command line, or the output of a child operation
 
@@ -103,6 +107,8 @@ struct Operation {
   int                      value_assign = MGC_ASSIGN_NONE;
   uint64_t                 value_constant = 0;
   std::vector<std::string> select_words;        // value: label: bases: input: not and or, after a set or value operation (meryl2 selectors)
+  bool                     has_hist_out = false, has_stats_out = false;   // output:histogram[=file] / output:statistics[=file] (meryl2)
+  std::string              hist_out, stats_out;                            //   their files; "-": stdout
 };
 
 struct Globals {
@@ -128,6 +134,7 @@ void usage(const char *prog) {
           "usage: %s [k=<K>] [memory=<GB>] [threads=<T>] [gpus=<N>] [n=<kmers>] [compress] [-l <label-bits>] [-C] [-Q] [-V]\n"
           "          count|count-forward|count-reverse [label=#<n>] <reads.fa|fq[.gz]|sam|bam> ... output <database.meryl>\n"
           "       %s print <database.meryl | [operation]>\n"
+          "       %s histogram|statistics <database.meryl | [operation]>\n"
           "       %s dumpIndex <database.meryl>\n"
           "       %s dumpFile <database.meryl>/0x######\n"
           "       %s union[-min|-max|-sum]|intersect[-min|-max|-sum]|subtract|difference|symmetric-difference [value=<word>[#<n>]] [label=<word>[#<n>]] [selector ...] <db | [operation]> ... [output <db>]\n"
@@ -150,9 +157,14 @@ void usage(const char *prog) {
           "  sum of products of tests holds: value:[lhs]REL<rhs>, label:[lhs]REL<rhs> (a side: @<input>, #<n> or <n>; no lhs:\n"
           "  the output k-mer; REL: == eq != <> ne <= le >= ge < lt > gt), bases:<acgt>:REL<n>, input:<n|n-m|n-all|all|any|\n"
           "  first|@n|@a-@b>[:...], joined by 'and' (optional), 'or' and 'not' -- e.g. union input:3-all a b c d.\n"
-          "  Other meryl operations are\n"
+          "  histogram and statistics report how the values of a database, or of the result of an operation, are\n"
+          "  distributed (value <TAB> k-mers; the statistics table); of an operation the tree is evaluated once, the\n"
+          "  histogram is collected on the device and nothing is written unless an operation says 'output'.\n"
+          "  output:histogram[=file] and output:statistics[=file] on a set or value operation report that operation's\n"
+          "  result while the tree runs on (no file, or '-': stdout) -- e.g. print [union-sum output:histogram=u.hist a b].\n"
+          "  Other meryl operations (compare, ploidy, noise, printACGT) are\n"
           "  not part of this build.\n",
-          prog, prog, prog, prog, prog, prog, prog);
+          prog, prog, prog, prog, prog, prog, prog, prog);
 }
 
 [[noreturn]] void die(const char *fmt, const char *a = "") {
@@ -560,18 +572,54 @@ void print_database(const std::string &dbn) {
   mdb_reader_close(r);
 }
 
-// `meryl histogram <db>`: value <TAB> number of distinct k-mers with that value, ascending -- the histogram the count
-// path's writer stored in the master index (src/meryl/merylOp-histogram.C:20-44, quick-start.rst:144)
-int run_histogram(const Operation &op) {
-  if (op.db_inputs.size() != 1) die("ERROR: told to dump a histogram for more than one input!");
-  mdb_reader *r = mdb_reader_open(op.db_inputs[0].c_str());
+// ---- histogram / statistics (src/meryl/merylOp-histogram.C:20-97) ----
+struct Histogram { std::vector<uint64_t> values, occurrences; uint64_t unique = 0, distinct = 0, total = 0; };
+
+// the histogram the writer stored in a database's master index (quick-start.rst:144); *k: its k-mer size
+Histogram stored_histogram(const std::string &dbn, uint32_t *k) {
+  mdb_reader *r = mdb_reader_open(dbn.c_str());
   if (!r) die("ERROR: %s", mdb_last_error());
   mdb_info i;
   mdb_reader_info(r, &i);
-  std::vector<uint64_t> v(i.hist_len), o(i.hist_len);
-  if (i.hist_len && mdb_reader_histogram(r, v.data(), o.data()) != 0) die("ERROR: %s", mdb_last_error());
-  for (uint64_t ii = 0; ii < i.hist_len; ii++) fprintf(stdout, "%" PRIu64 "\t%" PRIu64 "\n", v[ii], o[ii]);
+  Histogram h;
+  h.values.resize(i.hist_len); h.occurrences.resize(i.hist_len);
+  if (i.hist_len && mdb_reader_histogram(r, h.values.data(), h.occurrences.data()) != 0) die("ERROR: %s", mdb_last_error());
+  h.unique = i.num_unique; h.distinct = i.num_distinct; h.total = i.num_total;
+  *k = i.k;
   mdb_reader_close(r);
+  return h;
+}
+
+// value <TAB> number of distinct k-mers with that value, ascending (:39-42)
+void write_histogram(FILE *f, const Histogram &h) {
+  for (size_t ii = 0; ii < h.values.size(); ii++) fprintf(f, "%" PRIu64 "\t%" PRIu64 "\n", h.values[ii], h.occurrences[ii]);
+}
+
+// the statistics table (:65-93; the text is the library's, mdb_format_statistics)
+void write_statistics(FILE *f, uint32_t k, const Histogram &h) {
+  const size_t len = mdb_format_statistics(k, h.values.data(), h.occurrences.data(), h.values.size(), h.unique, h.distinct, h.total, nullptr, 0);
+  std::vector<char> text(len + 1);
+  mdb_format_statistics(k, h.values.data(), h.occurrences.data(), h.values.size(), h.unique, h.distinct, h.total, text.data(), text.size());
+  fwrite(text.data(), 1, len, f);
+}
+
+// where a report goes: no name or "-" is stdout (merylOpTemplate.C:174-175)
+FILE *open_report(const std::string &name) {
+  if (name.empty() || name == "-") return stdout;
+  FILE *f = fopen(name.c_str(), "w");
+  if (!f) die("ERROR: cannot create the report file '%s'.", name.c_str());
+  return f;
+}
+void close_report(FILE *f, const std::string &name) {
+  if (f == stdout) { fflush(f); return; }
+  if (fclose(f) != 0) die("ERROR: writing the report file '%s' failed.", name.c_str());
+}
+
+// `meryl histogram <db>` / `meryl statistics <db>`: from the stored histogram, on the host
+int run_stored_report(OpKind verb, const std::string &dbn) {
+  uint32_t k = 0;
+  const Histogram h = stored_histogram(dbn, &k);
+  if (verb == OP_HISTOGRAM) write_histogram(stdout, h); else write_statistics(stdout, k, h);
   return 0;
 }
 
@@ -661,6 +709,7 @@ struct EvalTree {
   std::vector<mgc_select_term>        terms;                  // the selector programs of all nodes, one after the other
   bool                                value_words = false;    // an operation of the tree carries value=
   uint32_t                            leaf_label_size = 0;    // the largest label size among the leaves
+  std::vector<int>                    node_op;                // the operation (index into ops) behind every node; -1: a database
 };
 
 // label=<word> | <word>#<const> | #<const> on a set or value operation (merylCommandBuilder-isAssign.C:124-156); without a
@@ -702,7 +751,7 @@ uint64_t threshold_from_histogram(const Operation &op, const std::string &in) {
   return c;
 }
 
-int run_tree(const Globals &g, const std::vector<Operation> &ops, int root, bool print);
+int run_tree(const Globals &g, const std::vector<Operation> &ops, int root, bool print, OpKind verb = OP_NONE);
 
 uint32_t add_tree_node(const Globals &g, const std::vector<Operation> &ops, int i, EvalTree &t) {
   const Operation &op = ops[i];
@@ -735,6 +784,7 @@ uint32_t add_tree_node(const Globals &g, const std::vector<Operation> &ops, int 
     nd.path = in.child >= 0 ? ops[in.child].output.c_str() : in.path.c_str();
     t.nodes.push_back(nd);
     t.kids.emplace_back();
+    t.node_op.push_back(-1);
     kids.push_back((uint32_t)t.nodes.size() - 1);
   }
   mgc_eval_node_assigned nd;
@@ -773,6 +823,7 @@ uint32_t add_tree_node(const Globals &g, const std::vector<Operation> &ops, int 
   t.nodes.push_back(nd);
   t.value_words = t.value_words || op.has_value_assign;
   t.kids.push_back(kids);
+  t.node_op.push_back(i);
   return (uint32_t)t.nodes.size() - 1;
 }
 
@@ -800,8 +851,9 @@ std::vector<T> narrowed(const std::vector<mgc_eval_node_assigned> &nodes) {
   return out;
 }
 
-// the operation tree under ops[root] (paths point into `ops`, which outlives the call)
-int run_tree(const Globals &g, const std::vector<Operation> &ops, int root, bool print) {
+// the operation tree under ops[root] (paths point into `ops`, which outlives the call); verb: OP_HISTOGRAM / OP_STATISTICS when the
+// tree is the input of that verb, whose report of the root goes to stdout
+int run_tree(const Globals &g, const std::vector<Operation> &ops, int root, bool print, OpKind verb) {
   EvalTree t;
   const uint32_t r = add_tree_node(g, ops, root, t);
   std::vector<uint32_t> children;
@@ -810,8 +862,22 @@ int run_tree(const Globals &g, const std::vector<Operation> &ops, int root, bool
     t.nodes[v].n_children = (uint32_t)t.kids[v].size();
     children.insert(children.end(), t.kids[v].begin(), t.kids[v].end());
   }
+  // reports: the verb's on the root, output:histogram / output:statistics on any operation; their files exist before anything runs
+  struct Report { uint32_t node; bool stats; std::string name; FILE *f; };
+  std::vector<Report> reports;
+  std::vector<uint8_t> want(t.nodes.size(), 0);
+  for (uint32_t v = 0; v < t.nodes.size(); v++) {
+    if (t.node_op[v] < 0) continue;
+    const Operation &o = ops[t.node_op[v]];
+    if (o.has_hist_out) reports.push_back(Report{v, false, o.hist_out, nullptr});
+    if (o.has_stats_out) reports.push_back(Report{v, true, o.stats_out, nullptr});
+  }
+  if (verb != OP_NONE) reports.push_back(Report{r, verb == OP_STATISTICS, "-", nullptr});
+  // deliberately before the evaluation, like the reference, which opens them while it reads the command (merylOpTemplate.C:187-188,
+  // 207-208): a name that cannot be written stops the command before any work; an evaluation that fails leaves the file empty
+  for (Report &rp : reports) { want[rp.node] = 1; rp.f = open_report(rp.name); }
   PrintCtx pc{0, 0};
-  if (print) {                                                 // (every leaf holds the same k: mgc_db_eval checks)
+  if (print || !reports.empty()) {                                                 // (every leaf holds the same k: mgc_db_eval checks)
     mdb_reader *rd = mdb_reader_open(t.first_leaf.c_str());
     if (!rd) die("ERROR: %s", mdb_last_error());
     mdb_info info;
@@ -826,7 +892,11 @@ int run_tree(const Globals &g, const std::vector<Operation> &ops, int root, bool
   const uint32_t label_size = g.label_size_given ? g.label_size : 0;
   if (with_labels) pc.label_size = g.label_size_given && g.label_size ? g.label_size : t.leaf_label_size;
   int rc;
-  if (t.value_words)                                           // a value= somewhere: the tree through mgc_db_eval_assigned
+  std::vector<mgc_value_hist *> hists(t.nodes.size(), nullptr);
+  if (!reports.empty())                                        // a report somewhere: the widest entry point, which collects them
+    rc = mgc_db_eval_reported(t.nodes.data(), n_nodes, children.data(), n_children, r, t.terms.data(), n_terms, with_labels ? 1 : 0, label_size,
+                              print ? print_slice_labelled : nullptr, &pc, -1, (int)g.threads, want.data(), hists.data());
+  else if (t.value_words)                                      // a value= somewhere: the tree through mgc_db_eval_assigned
     rc = mgc_db_eval_assigned(t.nodes.data(), n_nodes, children.data(), n_children, r, t.terms.data(), n_terms, with_labels ? 1 : 0, label_size,
                               print ? print_slice_labelled : nullptr, &pc, -1, (int)g.threads);
   else if (!t.terms.empty())                                   // a selector somewhere: the same tree through mgc_db_eval_selected
@@ -839,6 +909,19 @@ int run_tree(const Globals &g, const std::vector<Operation> &ops, int root, bool
     rc = mgc_db_eval(narrowed<mgc_eval_node>(t.nodes).data(), n_nodes, children.data(), n_children, r, print ? print_slice : nullptr, &pc, -1,
                      (int)g.threads);
   if (rc != MGC_OK) die("ERROR: %s", mgc_db_stream_error(nullptr));
+  fflush(stdout);
+  for (Report &rp : reports) {                                 // merylOpTemplate::finishAction, :295-307
+    mgc_value_hist *hh = hists[rp.node];
+    Histogram h;
+    uint64_t len = 0;
+    if (mgc_value_hist_len(hh, &len) != MGC_OK) die("ERROR: %s", mgc_db_stream_error(nullptr));
+    h.values.resize(len); h.occurrences.resize(len);
+    if (mgc_value_hist_get(hh, h.values.data(), h.occurrences.data()) != MGC_OK || mgc_value_hist_totals(hh, &h.unique, &h.distinct, &h.total) != MGC_OK)
+      die("ERROR: %s", mgc_db_stream_error(nullptr));
+    if (rp.stats) write_statistics(rp.f, pc.k, h); else write_histogram(rp.f, h);
+    close_report(rp.f, rp.name);
+  }
+  for (mgc_value_hist *hh : hists) mgc_value_hist_close(hh);
   return 0;
 }
 
@@ -903,6 +986,24 @@ int main(int argc, char **argv) {
         if (!ops[top()].output.empty()) die("ERROR: operation already has an output ('%s').", ops[top()].output.c_str());   // merylOp.C:256-257
         ops[top()].output = w;
         expect_output_name = false;
+      }
+      // meryl2's per-operation reports: output:histogram[=file], output:statistics[=file] (processText.C:153-154; any prefix of the
+      // report's word that is not ambiguous, as the reference's {p} patterns take it)
+      else if (w.compare(0, 7, "output:") == 0) {
+        const size_t e2 = w.find('=');
+        const std::string what = w.substr(7, e2 == std::string::npos ? std::string::npos : e2 - 7);
+        const std::string file = (e2 == std::string::npos || e2 + 1 >= w.size()) ? "-" : w.substr(e2 + 1);
+        const bool histo = !what.empty() && std::string("histogram").compare(0, what.size(), what) == 0;
+        const bool stats = what.size() >= 2 && (std::string("statistics").compare(0, what.size(), what) == 0 || std::string("stats").compare(0, what.size(), what) == 0);
+        if (what == "s") die("ERROR: '%s' is ambiguous; use output:show or output:stats.", w.c_str());              // :355
+        if (!histo && !stats) die("ERROR: '%s': of the output: words only output:histogram[=file] and output:statistics[=file] are part of this build.", w.c_str());
+        if (top() < 0 || !is_tree_op(ops[top()])) die("ERROR: '%s' needs a set or value operation before it.", w.c_str());
+        Operation &o = ops[top()];
+        if (histo ? o.has_hist_out : o.has_stats_out)                       // merylOpTemplate.C:180-185,200-205
+          die("ERROR: %s", ("operation '" + o.word + "' already has '" + (histo ? "histogram" : "statistics") + "' output to file '" +
+                            (histo ? o.hist_out : o.stats_out) + "', can't add another output to file '" + file + "'.").c_str());
+        (histo ? o.has_hist_out : o.has_stats_out) = true;
+        (histo ? o.hist_out : o.stats_out) = file;
       }
       // meryl2 selectors: value: label: bases: input: and the connectives, after a set or value operation (isSelect.C)
       else if (w.compare(0, 6, "value:") == 0 || w.compare(0, 6, "label:") == 0 || w.compare(0, 6, "bases:") == 0 || w.compare(0, 6, "input:") == 0) {
@@ -984,11 +1085,11 @@ int main(int argc, char **argv) {
         ops[top()].inputs.push_back(in);                                     // <database>/0x######
       }
       // ---- operations, :346-439 ----
-      else if (w == "count" || w == "count-forward" || w == "count-reverse" || w == "print" || w == "dumpIndex" || w == "histogram" ||
+      else if (w == "count" || w == "count-forward" || w == "count-reverse" || w == "print" || w == "dumpIndex" || w == "histogram" || w == "statistics" ||
                w == "dumpFile" || merge_code >= 0 || value_code >= 0) {
         const OpKind kind = (w == "count") ? OP_COUNT : (w == "count-forward") ? OP_COUNT_FORWARD :
                             (w == "count-reverse") ? OP_COUNT_REVERSE : (w == "print") ? OP_PRINT :
-                            (w == "histogram") ? OP_HISTOGRAM : (w == "dumpFile") ? OP_DUMPFILE :
+                            (w == "histogram") ? OP_HISTOGRAM : (w == "statistics") ? OP_STATISTICS : (w == "dumpFile") ? OP_DUMPFILE :
                             (w == "dumpIndex") ? OP_DUMPINDEX : (merge_code >= 0) ? OP_MERGE : OP_VALUE;
         ensure_top();
         if (is_counting(top())) { stack.pop_back(); ensure_top(); }         // :391-407: a counting operation takes no operation as input
@@ -1009,14 +1110,14 @@ int main(int argc, char **argv) {
         ops[top()].value_op = value_code;
       }
       else if (w == "output")                { expect_output_name = true; }
-      else if (w == "statistics" || w == "printACGT" || w == "compare" || w == "noise" || w == "ploidy") {
-        die("ERROR: operation '%s' is not part of this build (count, the set operations and the value filters / arithmetic only).", w.c_str());
+      else if (w == "printACGT" || w == "compare" || w == "noise" || w == "ploidy") {
+        die("ERROR: operation '%s' is not part of this build (count, the set operations, the value filters / arithmetic, histogram and statistics only).", w.c_str());
       }
       // ---- inputs ----
       else if (dir_has_index(w)) {                                           // :159,506-514
         const int t = top();
-        if (t < 0 || (ops[t].kind != OP_PRINT && ops[t].kind != OP_DUMPINDEX && ops[t].kind != OP_HISTOGRAM && ops[t].kind != OP_MERGE && ops[t].kind != OP_VALUE))
-          die("ERROR: database input '%s' needs a print, histogram, dumpIndex, set or value operation before it.", w.c_str());
+        if (t < 0 || (ops[t].kind != OP_PRINT && ops[t].kind != OP_DUMPINDEX && ops[t].kind != OP_HISTOGRAM && ops[t].kind != OP_STATISTICS && ops[t].kind != OP_MERGE && ops[t].kind != OP_VALUE))
+          die("ERROR: database input '%s' needs a print, histogram, statistics, dumpIndex, set or value operation before it.", w.c_str());
         InputRef in; in.path = w;
         ops[t].inputs.push_back(in);
       }
@@ -1065,26 +1166,40 @@ int main(int argc, char **argv) {
     if (g.verbosity > 0) fprintf(stderr, "\nCleaning up.\n\nBye.\n");
     return rc;
   }
-  for (const Operation &op : ops)                                              // before anything runs
-    if (op.kind == OP_DUMPINDEX || op.kind == OP_HISTOGRAM || op.kind == OP_DUMPFILE)
-      for (const InputRef &in : op.inputs)
-        if (in.child >= 0 && ops[in.child].output.empty()) die("ERROR: '%s' reads a database: its input operation needs an 'output <database>'.", op.word.c_str());
-  // the trees of set and value operations, one evaluation each; the tree under a `print` is evaluated by the print
+  auto is_report = [](const Operation &op) { return op.kind == OP_HISTOGRAM || op.kind == OP_STATISTICS; };
+  for (const Operation &op : ops) {                                            // before anything runs
+    if (is_report(op) && op.inputs.empty()) {
+      fprintf(stderr, "ERROR: '%s' needs one input: a database, or an [operation] whose result it reports.\n\n", op.word.c_str());
+      usage(argv[0]);
+      return 1;
+    }
+    if (is_report(op) && op.inputs.size() > 1) die("ERROR: told to dump a histogram for more than one input!");   // merylOp-histogram.C:24-25
+    if (op.kind == OP_DUMPINDEX || is_report(op) || op.kind == OP_DUMPFILE)
+      for (const InputRef &in : op.inputs)                                     // (a report evaluates the tree that is its input itself)
+        if (in.child >= 0 && ops[in.child].output.empty() && !(is_report(op) && is_tree_op(ops[in.child]))) die("ERROR: '%s' reads a database: its input operation needs an 'output <database>'.", op.word.c_str());
+  }
+  // the trees of set and value operations, one evaluation each; the tree under a `print`, `histogram` or `statistics` is evaluated by
+  // that verb
   for (size_t i = ops.size(); i-- > 0;) {
-    if (!is_tree_op(ops[i]) || (ops[i].parent >= 0 && (is_tree_op(ops[ops[i].parent]) || ops[ops[i].parent].kind == OP_PRINT))) continue;
+    if (!is_tree_op(ops[i]) || (ops[i].parent >= 0 && (is_tree_op(ops[ops[i].parent]) || ops[ops[i].parent].kind == OP_PRINT || is_report(ops[ops[i].parent])))) continue;
     rc |= run_tree(g, ops, (int)i, false);
   }
   for (Operation &op : ops) {
-    if (op.kind != OP_PRINT && op.kind != OP_DUMPINDEX && op.kind != OP_HISTOGRAM && op.kind != OP_DUMPFILE) continue;
+    if (op.kind != OP_PRINT && op.kind != OP_DUMPINDEX && !is_report(op) && op.kind != OP_DUMPFILE) continue;
     if (op.kind == OP_PRINT) {
       for (const InputRef &in : op.inputs)
         if (in.child >= 0 && is_tree_op(ops[in.child])) rc |= run_tree(g, ops, in.child, true);
         else print_database(in.child >= 0 ? ops[in.child].output : in.path);
       continue;
     }
+    if (is_report(op)) {
+      for (const InputRef &in : op.inputs)
+        if (in.child >= 0 && is_tree_op(ops[in.child])) rc |= run_tree(g, ops, in.child, false, op.kind);
+        else rc |= run_stored_report(op.kind, in.child >= 0 ? ops[in.child].output : in.path);
+      continue;
+    }
     for (const InputRef &in : op.inputs) op.db_inputs.push_back(in.child >= 0 ? ops[in.child].output : in.path);
     if (op.kind == OP_DUMPINDEX) rc |= run_dump_index(op);
-    if (op.kind == OP_HISTOGRAM) rc |= run_histogram(op);
     if (op.kind == OP_DUMPFILE)  rc |= run_dump_file(op);
   }
   if (g.verbosity > 0) fprintf(stderr, "\nCleaning up.\n\nBye.\n");                                    // meryl.C:268,273

@@ -1,5 +1,5 @@
 // mgc_eval.cpp -- operations over whole databases (include/meryl_db.h): mgc_db_merge, mgc_db_filter, and the operation trees of
-// mgc_db_eval, mgc_db_eval_labelled, mgc_db_eval_selected and mgc_db_eval_assigned.  Inputs are decoded on the device, every
+// mgc_db_eval, mgc_db_eval_labelled, mgc_db_eval_selected, mgc_db_eval_assigned and mgc_db_eval_reported.  Inputs are decoded on the device, every
 // operation is a count / emit pass pair over slices in HBM, and outputs go through the database stream (mgc_stream.cpp).
 #include "../../include/meryl_db.h"
 #include "mdb_layout.h"
@@ -336,6 +336,7 @@ struct EvalNode {
   FoldBufs *fold = nullptr;        // merge nodes that fold
   SliceRef res;
   mgc_db_stream *out = nullptr;
+  mgc_value_hist *hist = nullptr;  // flagged nodes (mgc_db_eval_reported): the histogram of the result's values over all slices
   uint32_t leaf = 0;               // leaf: its reader; inner node: its leftmost leaf's
 };
 
@@ -345,7 +346,7 @@ std::string plain_path(const char *p) {
   return s;
 }
 
-// everything a node of any of the four public structs can carry; what a narrower struct does not name keeps its default
+// everything a node of any of the public structs can carry; what a narrower struct does not name keeps its default
 struct Node {
   int32_t     kind = 0, op = 0;
   uint64_t    constant = 0;
@@ -356,9 +357,10 @@ struct Node {
   uint32_t    first_term = 0, n_terms = 0;           // the node's program in Eval::terms
   int32_t     value_assign = MGC_ASSIGN_NONE;
   uint64_t    value_constant = 0;
+  bool        want_hist = false;                      // mgc_db_eval_reported: the value histogram of the node's result
 };
 
-// one evaluation, as any of the four entry points states it
+// one evaluation, as any of the five entry points states it
 struct Eval {
   const char *who;                                   // the entry point, for messages
   std::vector<Node> nodes;
@@ -369,6 +371,7 @@ struct Eval {
   mgc_eval_slice_cb cb = nullptr;                    // mgc_db_eval's callback form, or
   mgc_eval_slice_labelled_cb lcb = nullptr;          //   the one that also takes labels (zeros when they do not travel)
   void    *ctx = nullptr;
+  mgc_value_hist **hists = nullptr;                  // [n_nodes], out: the accumulators of the nodes with want_hist
 };
 
 template <typename T>
@@ -387,7 +390,7 @@ std::vector<Node> to_nodes(const T *src, uint32_t n) {
   return out;
 }
 
-// the four entry points: one walk, one validation, one slice loop
+// the five entry points: one walk, one validation, one slice loop
 int eval_impl(const Eval &E, int device, int host_threads) {
   const char *who = E.who;
   const std::vector<Node> &nodes = E.nodes;
@@ -397,6 +400,8 @@ int eval_impl(const Eval &E, int device, int host_threads) {
   if (n_nodes == 0 || (E.n_terms && !E.terms)) return bad("bad arguments");
   if (E.label_size > 64) return bad("a label has at most 64 bits");
   if (root >= n_nodes || (n_children && !children)) return bad("bad arguments");
+  for (uint32_t v = 0; v < n_nodes; v++)
+    if (nodes[v].want_hist && !E.hists) return bad("node " + std::to_string(v) + ": a histogram is wanted but there is nowhere to return it");
   // ---- the tree: every node reached at most once, from the root (post-order = evaluation order)
   std::vector<uint32_t> order, leaves;
   {
@@ -456,6 +461,8 @@ int eval_impl(const Eval &E, int device, int host_threads) {
       order.push_back(f.node);
       stack.pop_back();
     }
+    for (uint32_t v = 0; v < n_nodes; v++)
+      if (nodes[v].want_hist && !seen[v]) return bad("node " + std::to_string(v) + ": a histogram is wanted of a node the root does not reach");
   }
   // ---- outputs: named once, and not an input
   {
@@ -506,6 +513,8 @@ int eval_impl(const Eval &E, int device, int host_threads) {
     ev[v].out = mgc_db_stream_open(nodes[v].path, k, w_prefix_of(v), label_size, 0, 0, 1, host_threads, device);
     if (!ev[v].out) { rc = MGC_EINVAL; msg = mgc_db_stream_error(nullptr); break; }
   }
+  for (uint32_t v : order)
+    if (nodes[v].want_hist && rc == MGC_OK) ev[v].hist = mgc_value_hist_open(device);
   hipStream_t st = nullptr;
   std::vector<DBuf> in_k(n_leaves), in_c(n_leaves), in_l(labels ? n_leaves : 0);
   DBuf ws;
@@ -581,6 +590,10 @@ int eval_impl(const Eval &E, int device, int host_threads) {
                                           ((uint64_t)ff + 1) * blocks_per_file);
         if (rc != MGC_OK) { msg = who_colon + mgc_db_stream_error(me.out); break; }
       }
+      if (me.hist) {                                         // the result's values, counted where they lie
+        rc = mgc_value_hist_add(me.hist, me.res.c, me.res.n, st);
+        if (rc != MGC_OK) { msg = who_colon + mgc_db_stream_error(nullptr); break; }
+      }
     }
     if (rc != MGC_OK) break;
     if (E.cb || E.lcb) {
@@ -624,6 +637,11 @@ int eval_impl(const Eval &E, int device, int host_threads) {
     if (!ev[v].out) continue;
     const int rc2 = mgc_db_stream_close(ev[v].out, nullptr);
     if (rc == MGC_OK && rc2 != MGC_OK) { rc = rc2; msg = mgc_db_stream_error(nullptr); }
+  }
+  for (uint32_t v : order) {                                 // the accumulators go to the caller, or nowhere
+    if (!ev[v].hist) continue;
+    if (rc == MGC_OK) E.hists[v] = ev[v].hist;
+    else mgc_value_hist_close(ev[v].hist);
   }
   if (rc != MGC_OK) set_err(nullptr, "%s", msg.c_str());
   return rc;
@@ -682,4 +700,19 @@ extern "C" int mgc_db_eval_assigned(const mgc_eval_node_assigned *nodes, uint32_
                                     mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads) {
   return eval_with_programs("mgc_db_eval_assigned", nodes, n_nodes, children, n_children, root, terms, n_terms, with_labels, label_size, cb, ctx,
                             device, host_threads);
+}
+
+// the same tree with reports (include/meryl_db.h): the flagged nodes' values of every slice go through their value-histogram
+// accumulators (mgc_value_hist.hip); nothing else differs from mgc_db_eval_assigned
+extern "C" int mgc_db_eval_reported(const mgc_eval_node_assigned *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
+                                    uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
+                                    mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads, const uint8_t *want_hist,
+                                    mgc_value_hist **hists) {
+  Eval E{"mgc_db_eval_reported", to_nodes(nodes, n_nodes), children, n_children, root};
+  E.terms = terms; E.n_terms = n_terms; E.label_size = label_size; E.lcb = cb; E.ctx = ctx;
+  E.labels = labels_asked(E, with_labels);
+  E.hists = hists;
+  if (hists) for (size_t v = 0; v < E.nodes.size(); v++) hists[v] = nullptr;       // on failure no handle is returned
+  if (want_hist) for (size_t v = 0; v < E.nodes.size(); v++) E.nodes[v].want_hist = want_hist[v] != 0;
+  return eval_impl(E, device, host_threads);
 }

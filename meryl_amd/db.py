@@ -192,13 +192,21 @@ def _walk(tree, allowed):
     """The one tree walk: `tree` is a database path, or (word, *children) for the merge operations, or (word, constant, child) for
     the value operations; a dict as the last element holds the node's options, of which only `allowed` are taken.
     -> ([node record], [children], root index); a record is a dict of kind, op, constant, path, first, n and the raw options
-    label, select, value (None where not given); children come before their parent."""
+    label, select, value (None where not given) and histogram (a bool); children come before their parent.  A database is flagged
+    for a histogram as ({"database": path, "histogram": True})."""
     nodes, kids = [], []
 
     def add(t):
+        if isinstance(t, dict):                                     # a database with options: {"database": path, "histogram": True}
+            unknown = sorted(set(t) - {"database", "histogram"})
+            if unknown or "database" not in t or "histogram" not in allowed:
+                raise ValueError("a database with options is {'database': path, 'histogram': bool}: %r" % (t,))
+            i = add(t["database"])
+            nodes[i]["histogram"] = bool(t["histogram"]) if "histogram" in t else False
+            return i
         if isinstance(t, (str, bytes)):
             nodes.append(dict(kind=capi.NODE_DATABASE, op=0, constant=0, path=t if isinstance(t, bytes) else t.encode(), first=0, n=0,
-                              label=None, select=None, value=None))
+                              label=None, select=None, value=None, histogram=False))
             return len(nodes) - 1
         t = tuple(t)
         opts = {}
@@ -222,7 +230,7 @@ def _walk(tree, allowed):
         ch = [add(a) for a in args]
         out, words = opts.get("output"), opts.get("select")
         nodes.append(dict(kind=kind, op=op, constant=constant, path=None if out is None else (out if isinstance(out, bytes) else out.encode()),
-                          first=len(kids), n=len(ch), label=opts.get("label"), value=opts.get("value"),
+                          first=len(kids), n=len(ch), label=opts.get("label"), value=opts.get("value"), histogram=bool(opts.get("histogram")),
                           select=None if words is None else ([words] if isinstance(words, str) else list(words))))
         kids.extend(ch)
         return len(nodes) - 1
@@ -234,7 +242,7 @@ def _walk(tree, allowed):
 def _fill(struct, tree, allowed):
     """_walk -> an array of `struct` with the fields of the options in `allowed` set: label -> label_op / label_constant, select ->
     first_term / n_terms (parsed for the node's input count), value -> value_assign / value_constant.
-    -> (array, children array, number of children, root index, SelectTerm array, number of terms)"""
+    -> (array, children array, number of children, root index, SelectTerm array, number of terms, the node records of _walk)"""
     nodes, kids, root = _walk(tree, allowed)
     arr = (struct * len(nodes))()
     for e, r in zip(arr, nodes):
@@ -254,7 +262,7 @@ def _fill(struct, tree, allowed):
     if "value" in allowed:
         for e, r in inner:
             e.value_assign, e.value_constant = value_assign_option(r["value"])
-    return arr, (ctypes.c_uint32 * max(len(kids), 1))(*kids), len(kids), root, (capi.SelectTerm * max(len(terms), 1))(*terms), len(terms)
+    return arr, (ctypes.c_uint32 * max(len(kids), 1))(*kids), len(kids), root, (capi.SelectTerm * max(len(terms), 1))(*terms), len(terms), nodes
 
 
 def build_tree(tree):
@@ -275,14 +283,14 @@ def build_tree_selected(tree):
     """build_tree_labelled for mgc_db_eval_selected: the options dict of a node also takes "select": [words...], the selector
     words of the command line, parsed for the node's input count.
     -> (EvalNodeSelected array, children array, number of children, root index, SelectTerm array, number of terms)"""
-    return _fill(capi.EvalNodeSelected, tree, ("output", "label", "select"))
+    return _fill(capi.EvalNodeSelected, tree, ("output", "label", "select"))[:6]
 
 
 def build_tree_assigned(tree):
     """build_tree_selected for mgc_db_eval_assigned: the options dict of a node also takes "value": what follows value= on the
     command line ("sub#3") or (word, constant) (value_assign_option).
     -> (EvalNodeAssigned array, children array, number of children, root index, SelectTerm array, number of terms)"""
-    return _fill(capi.EvalNodeAssigned, tree, ("output", "label", "select", "value"))
+    return _fill(capi.EvalNodeAssigned, tree, ("output", "label", "select", "value"))[:6]
 
 
 def _evaluate(name, call, on_slice, labelled=True):
@@ -345,3 +353,106 @@ def evaluate_assigned(tree, on_slice=None, with_labels=False, label_size=0, devi
     _evaluate("mgc_db_eval_assigned",
               lambda cb: capi.lib().mgc_db_eval_assigned(arr, len(arr), kids, n_kids, root, terms, n_terms, int(bool(with_labels)), int(label_size), cb,
                                                          None, device, host_threads), on_slice)
+
+
+def build_tree_reported(tree):
+    """build_tree_assigned for mgc_db_eval_reported: the options dict of a node also takes "histogram": True -- the value histogram
+    of that node's result is collected; a database is flagged as {"database": path, "histogram": True}.
+    -> (EvalNodeAssigned array, children array, number of children, root index, SelectTerm array, number of terms, want array)"""
+    allowed = ("output", "label", "select", "value", "histogram")
+    filled = _fill(capi.EvalNodeAssigned, tree, allowed)
+    return filled[:6] + ((ctypes.c_uint8 * len(filled[6]))(*[1 if r["histogram"] else 0 for r in filled[6]]),)
+
+
+class ValueHistogram:
+    """The value-histogram accumulator (mgc_value_hist_*, include/meryl_db.h) over torch device tensors of uint32 values (any 4-byte
+    integer dtype: the bits are taken as uint32): add() any number of tensors, then get() / totals()."""
+
+    def __init__(self, device=-1, handle=None):
+        self._h = handle if handle is not None else capi.lib().mgc_value_hist_open(int(device))
+        if not self._h:
+            raise DbError("mgc_value_hist_open failed")
+
+    @staticmethod
+    def geometry():
+        """(dense limit D: values below it are counted in LDS bins; values one workgroup takes per iteration)"""
+        d, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        capi.lib().mgc_value_hist_geometry(ctypes.byref(d), ctypes.byref(w))
+        return d.value, w.value
+
+    def _check(self, rc, what):
+        if rc != 0:
+            msg = capi.lib().mgc_db_stream_error(None)
+            raise capi.MgcError(rc, what, msg.decode("utf-8", "replace") if msg else "")
+
+    def add(self, values):
+        """values: a contiguous torch tensor on the device, 4 bytes per element"""
+        import torch
+        if not values.is_cuda or not values.is_contiguous() or values.element_size() != 4:
+            raise ValueError("ValueHistogram.add takes a contiguous device tensor of 4-byte values")
+        n = values.numel()
+        stream = torch.cuda.current_stream(values.device).cuda_stream
+        self._check(capi.lib().mgc_value_hist_add(self._h, values.data_ptr() if n else None, n, stream), "mgc_value_hist_add")
+
+    def get(self):
+        """(values, occurrences) as uint64 numpy arrays, ascending by value"""
+        n = ctypes.c_uint64(0)
+        self._check(capi.lib().mgc_value_hist_len(self._h, ctypes.byref(n)), "mgc_value_hist_len")
+        v = np.zeros(n.value, dtype=np.uint64)
+        o = np.zeros(n.value, dtype=np.uint64)
+        self._check(capi.lib().mgc_value_hist_get(self._h, v.ctypes.data if n.value else None, o.ctypes.data if n.value else None), "mgc_value_hist_get")
+        return v, o
+
+    def totals(self):
+        """(unique, distinct, total): occurrences of value 1, sum of occurrences, sum(value * occurrences) in uint64"""
+        u, d, t = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(capi.lib().mgc_value_hist_totals(self._h, ctypes.byref(u), ctypes.byref(d), ctypes.byref(t)), "mgc_value_hist_totals")
+        return u.value, d.value, t.value
+
+    def close(self):
+        if self._h:
+            capi.lib().mgc_value_hist_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def format_statistics(k, values, occurrences, unique, distinct, total):
+    """the text of `meryl statistics` for a histogram (mdb_format_statistics)"""
+    v = np.ascontiguousarray(values, dtype=np.uint64)
+    o = np.ascontiguousarray(occurrences, dtype=np.uint64)
+    args = (int(k), v.ctypes.data if v.size else None, o.ctypes.data if o.size else None, v.size, int(unique), int(distinct), int(total))
+    n = capi.lib().mdb_format_statistics(*args, None, 0)
+    buf = ctypes.create_string_buffer(n + 1)
+    capi.lib().mdb_format_statistics(*args, buf, n + 1)
+    return buf.value.decode()
+
+
+def evaluate_reported(tree, on_slice=None, with_labels=False, label_size=0, device=-1, host_threads=8):
+    """evaluate_assigned() that also collects value histograms (mgc_db_eval_reported): every node given {"histogram": True} (a
+    database: {"database": path, "histogram": True}) has the values of its result counted on the device, slice by slice.
+    -> [(values, occurrences)] as uint64 numpy arrays ascending by value, for the flagged nodes in pre-order (a node before its
+    inputs, inputs left to right)."""
+    arr, kids, n_kids, root, terms, n_terms, want = build_tree_reported(tree)
+    hists = (ctypes.c_void_p * len(arr))()
+    _evaluate("mgc_db_eval_reported",
+              lambda cb: capi.lib().mgc_db_eval_reported(arr, len(arr), kids, n_kids, root, terms, n_terms, int(bool(with_labels)), int(label_size), cb,
+                                                         None, device, host_threads, want, hists), on_slice)
+    order = []
+
+    def pre(v):
+        order.append(v)
+        for i in range(arr[v].n_children):
+            pre(kids[arr[v].first_child + i])
+    pre(root)
+    out = []
+    for v in order:
+        if want[v]:
+            h = ValueHistogram(handle=hists[v])
+            out.append(h.get())
+            h.close()
+    return out
