@@ -677,8 +677,10 @@ typedef struct mgc_profile {
   /* what the rest of the count stage lasts (offsets of the sub-buckets in the packed result + the packing kernels of all files), on
    * the session stream behind the count kernels: stage_ms[MGC_STAGE_RLE] - pack_ms = the wall clock of the count kernels themselves */
   double   pack_ms;
-  uint64_t hist_bytes;             /* ALGORITHMIC bytes of the histogram kernel (the bases read) ... */
-  uint64_t partition_bytes;        /* ... and of the partition (the bases read + the k-mers written in the layout the files take: 5 / 8 / 12 / 16 B) */
+  uint64_t hist_bytes;             /* ALGORITHMIC bytes of the histogram kernel (the bases read + the packed base stream it stores, 6 bytes per
+                                    * 16 bases, where the count has one: not with MGC_PACKED_BASES=0) ... */
+  uint64_t partition_bytes;        /* ... and of the partition (the packed base stream read -- without one, the bases -- + the k-mers written in
+                                    * the layout the files take: 5 / 8 / 12 / 16 B) */
 } mgc_profile;
 int mgc_set_profiling(mgc_session *s, int enable);
 int mgc_get_profile(const mgc_session *s, mgc_profile *p);

@@ -321,6 +321,7 @@ struct Count {
   uint64_t *d_counts64 = nullptr, *d_starts = nullptr;
   std::vector<uint64_t> h_meta;                          // [nb] starts, [nb] K96 flags: copied to d_starts (lives until the count returns)
   const uint64_t *d_fine = nullptr, *d_fine_hpc = nullptr;
+  void *d_packed = nullptr;                              // the packed base stream (mgc_device.h, kp_packed_bytes); nullptr: the partition reads ASCII
   mgc::SortPlan full{};                                  // the stable sort of all bits below the bucket
   bool use_finish;
   unsigned char *X = nullptr, *Y = nullptr;
@@ -413,21 +414,38 @@ int Count::histogram() {
     // The narrowed grouping passes (k <= ~25) group a file by its TOP digit first when that digit's histogram is at hand: the file
     // histogram then counts fifteen top bits instead of six (one kernel, same read of the bases) and the 8 B/k-mer digit-histogram
     // read of every file goes away.
+    // The packed base stream (MGC_PACKED_BASES=0: off): the histogram kernel stores the 2-bit codes and invalid-base masks it has to
+    // make anyway, and the partition stages its tiles from them instead of decoding the ASCII bases a second time.  Only where the
+    // arena can grow by it beside what the count itself is budgeted at (2 + 14 bytes per key word and base, mgc_api.cpp: input_setup);
+    // a count that cannot have it runs as before.
+    if (sw.packed_bases && n_bases) {
+      const size_t pb = mgc::kp_packed_bytes(n_bases);
+      bool room = s->buf[S::B_PACKED].cap >= pb;
+      if (!room) {
+        size_t free_b = 0, total_b = 0;
+        room = hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
+               (double)free_b + (double)s->arena_bytes() >= (double)n_bases * (double)(2 + 14ull * kw) + (double)pb;
+      }
+      if (room) {
+        if (s->ensure(S::B_PACKED, pb) == hipSuccess) d_packed = s->buf[S::B_PACKED].p;
+        else (void)hipGetLastError();
+      }
+    }
     tm.begin(MGC_STAGE_HISTOGRAM);
     if (n_bases >= (1u << 22) && ((kw == 1 && 2 * k - bucket_bits <= 41) || wide_msd_on) && mgc::kmer_histogram_fine_ok(k, bucket_bits, s->sfx_mask, sw)) {
       HIP_TRY(s, s->ensure(S::B_FINE, sizeof(uint64_t) << 15));
       uint64_t *fine = reinterpret_cast<uint64_t *>(s->buf[S::B_FINE].p);
-      HIP_TRY(s, mgc::launch_kmer_histogram_fine(d_bases, n_bases, k, c.mode, d_counts64, fine, part_ws, st, sw.const_k));
+      HIP_TRY(s, mgc::launch_kmer_histogram_fine(d_bases, n_bases, k, c.mode, d_counts64, fine, part_ws, st, sw.const_k, 6, d_packed));
       d_fine = fine;
     } else if (c.homopoly_compress && n_bases >= (1u << 22) && (2 * k - bucket_bits) % 2 == 0 && 2 * k - bucket_bits >= 20 &&
                sw.hpc_digits && mgc::kmer_histogram_hpc_ok(k, bucket_bits, s->sfx_mask, sw)) {
       // `compress`: k-mers per (bucket, dense-rank digit below it) -- the buckets' high digit goes first as well (MGC_HPC_MSD=0: off)
       HIP_TRY(s, s->ensure(S::B_FINE, sizeof(uint64_t) * std::max<size_t>((size_t)1 << 15, mgc::kmer_histogram_hpc_entries(bucket_bits))));
       uint64_t *fine = reinterpret_cast<uint64_t *>(s->buf[S::B_FINE].p);
-      HIP_TRY(s, mgc::launch_kmer_histogram_hpc(d_bases, n_bases, k, c.mode, bucket_bits, d_counts64, fine, part_ws, st, sw.const_k));
+      HIP_TRY(s, mgc::launch_kmer_histogram_hpc(d_bases, n_bases, k, c.mode, bucket_bits, d_counts64, fine, part_ws, st, sw.const_k, d_packed));
       d_fine_hpc = fine;
     } else
-    HIP_TRY(s, mgc::launch_kmer_histogram(d_bases, n_bases, k, c.mode, bucket_bits, d_counts64, part_ws, st, s->sfx_mask, s->sfx_test));
+    HIP_TRY(s, mgc::launch_kmer_histogram(d_bases, n_bases, k, c.mode, bucket_bits, d_counts64, part_ws, st, s->sfx_mask, s->sfx_test, d_packed));
     tm.end(MGC_STAGE_HISTOGRAM);
     prof.stage_launches[MGC_STAGE_HISTOGRAM] = 1;
     HIP_TRY(s, hipMemcpyAsync(h_counts.data(), d_counts64, sizeof(uint64_t) * nb, hipMemcpyDeviceToHost, st));
@@ -491,10 +509,11 @@ int Count::partition(bool soa, bool k96) {
   if (k96) HIP_TRY(s, hipMemcpyAsync(d_k96flags, h_meta.data() + nb, sizeof(uint64_t) * nb, hipMemcpyHostToDevice, st));
   tm.begin(MGC_STAGE_PARTITION);
   HIP_TRY(s, mgc::launch_kmer_partition(d_bases, n_bases, k, c.mode, bucket_bits, d_starts, (void *)X, part_ws, st,
-                                        s->sfx_mask, s->sfx_test, k96 ? d_k96flags : (soa ? d_counts64 : nullptr), sw.const_k));
+                                        s->sfx_mask, s->sfx_test, k96 ? d_k96flags : (soa ? d_counts64 : nullptr), sw.const_k, d_packed));
   tm.end(MGC_STAGE_PARTITION);
-  prof.hist_bytes = n_bases;
-  prof.partition_bytes = n_bases;
+  const uint64_t packed_b = d_packed ? mgc::kp_packed_bytes(n_bases) : 0;    // stored by the histogram, read by the partition in place of the bases
+  prof.hist_bytes = n_bases + packed_b;
+  prof.partition_bytes = d_packed ? packed_b : n_bases;
   for (uint32_t b = 0; b < nb; b++) prof.partition_bytes += plan.files[b].size * (soa ? 5u : ((k96 && plan.files[b].k96) ? 12u : (uint64_t)kbytes));
   prof.stage_launches[MGC_STAGE_PARTITION] = 2;
   return MGC_OK;

@@ -20,6 +20,7 @@ struct Switches {
   bool hpc_msd = true;          // MGC_HPC_MSD=0: `compress`, low digit first everywhere
   bool hpc_digits = true;       // MGC_HPC_DIGITS=0: `compress` with plain bit digits
   bool const_k = true;          // MGC_KMER_CONST_K=0: the front-end kernels with run-time k only
+  bool packed_bases = true;     // MGC_PACKED_BASES=0: the partition decodes the ASCII bases again (no packed base stream)
   bool narrow = true;           // MGC_NARROW=0: no 32-bit words after the first grouping pass
   bool wide_msd = true;         // MGC_WIDE_MSD=0: whole keys low digit first off a histogram read
   bool soa5 = true;             // MGC_SOA5=0: no 5-byte layout (k = 20..23)
@@ -57,6 +58,10 @@ constexpr int      KP_MAX_BUCKETS = 1024;
 // Persistent grid size used by both passes (they must agree).
 uint32_t kp_grid_size(uint64_t n_bases, uint32_t bucket_bits);   // rows of the per-workgroup histogram (virtual workgroups)
 size_t   kp_workspace_bytes(uint32_t bucket_bits);
+// The packed base stream of a count (mgc_kmer.hip, PackedBases): d_packed[kp_packed_bytes(n_bases)], about 0.375 bytes per base.
+// A histogram launch that gets it stores the 2-bit codes and invalid-base masks of the whole input there, and the partition
+// launch of the SAME d_bases / n_bases that gets it reads them instead of the ASCII bases.  nullptr (the bare operators): ASCII.
+size_t   kp_packed_bytes(uint64_t n_bases);
 
 // sfx_mask / sfx_test: count-suffix= filter, a k-mer is kept iff (its low word & sfx_mask) == sfx_test (0, 0: keep all)
 // the same + the k-mers per (file, next nine bits) into d_fine_hist[2^15] (the first digit of the narrowed grouping passes)
@@ -66,22 +71,24 @@ bool       kmer_histogram_fine_ok(uint32_t k, uint32_t bucket_bits, uint64_t sfx
 bool       kmer_histogram_hpc_ok(uint32_t k, uint32_t bucket_bits, uint64_t sfx_mask, const Switches &sw);
 uint32_t   kmer_histogram_hpc_entries(uint32_t bucket_bits);
 hipError_t launch_kmer_histogram_hpc(const uint8_t *d_bases, uint64_t n_bases, uint32_t k, int mode, uint32_t bucket_bits,
-                                     uint64_t *d_bucket_counts, uint64_t *d_fine_hist, void *d_ws, hipStream_t st, bool const_k = true /*Switches::const_k*/);
+                                     uint64_t *d_bucket_counts, uint64_t *d_fine_hist, void *d_ws, hipStream_t st, bool const_k = true /*Switches::const_k*/,
+                                     void *d_packed = nullptr);
 hipError_t launch_kmer_histogram_fine(const uint8_t *d_bases, uint64_t n_bases, uint32_t k, int mode, uint64_t *d_bucket_counts,
                                       uint64_t *d_fine_hist, void *d_ws, hipStream_t st, bool const_k = true /*Switches::const_k*/,
                                       uint32_t bucket_bits = 6 /*6..8: d_bucket_counts[2^bucket_bits] and the per-workgroup rows the partition
-                                      takes its cursors from go by that many top bits (a sharded count's senders); d_fine_hist stays 2^15*/);
+                                      takes its cursors from go by that many top bits (a sharded count's senders); d_fine_hist stays 2^15*/,
+                                      void *d_packed = nullptr);
 bool       kmer_histogram_fine_bits_ok(uint32_t k, uint32_t bucket_bits);
 hipError_t launch_kmer_histogram(const uint8_t *d_bases, uint64_t n_bases, uint32_t k, int mode,
                                  uint32_t bucket_bits, uint64_t *d_bucket_counts, void *d_ws, hipStream_t st,
-                                 uint64_t sfx_mask = 0, uint64_t sfx_test = 0);
+                                 uint64_t sfx_mask = 0, uint64_t sfx_test = 0, void *d_packed = nullptr);
 // keys are uint64 for k <= 32, 16-byte little-endian {lo,hi} for k in 33..64 (key_words 1 / 2)
 hipError_t launch_kmer_partition(const uint8_t *d_bases, uint64_t n_bases, uint32_t k, int mode,
                                  uint32_t bucket_bits, const uint64_t *d_bucket_starts, void *d_keys,
                                  void *d_ws, hipStream_t st, uint64_t sfx_mask = 0, uint64_t sfx_test = 0,
                                  const uint64_t *d_soa_counts = nullptr /*64 buckets, 8-byte keys, <= 40 bits below the file: a file's region =
                                  u32[count] low words + u8[count] bits 32..39 (5 bytes per k-mer; launch_group_narrow(soa_hi_mask))*/,
-                                 bool const_k = true /*Switches::const_k*/);
+                                 bool const_k = true /*Switches::const_k*/, void *d_packed = nullptr);
 
 // ---- radix sort ------------------------------------------------------------
 struct SortPlan {

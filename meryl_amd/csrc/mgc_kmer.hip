@@ -20,6 +20,7 @@
 // {flag,epoch,value} granules with agent-scope relaxed atomics (no fences needed:
 // the datum is the flag).  Wave = 64 everywhere.
 #include "mgc_common.hpp"
+#include "mgc_bases.hpp"
 
 namespace mgc {
 
@@ -27,29 +28,16 @@ namespace mgc {
 //  k-mer extraction (k <= 32, keys are uint64)
 // ============================================================================
 
-// 4 ASCII bytes (byte 0 = first base) -> 8 bits of 2-bit codes, first base most
-// significant.  code = (ascii >> 1) & 3 gives A0 C1 T2 G3 for both cases.
-__device__ __forceinline__ u32 enc4(u32 w) {
-  return (((w >> 1) & 0x03030303u) * 0x40100401u) >> 24;
-}
-// exact per-byte zero detector: 0x80 in every byte of x that is zero
-__device__ __forceinline__ u32 zero_bytes(u32 x) {
-  return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
-}
-// 4 ASCII bytes -> 4-bit mask, bit 3 = byte 0 is NOT one of ACGTacgt
-__device__ __forceinline__ u32 inv4(u32 w) {
-  const u32 u = w & 0xDFDFDFDFu;                     // fold case
-  const u32 ok = zero_bytes(u ^ 0x41414141u) | zero_bytes(u ^ 0x43434343u) |
-                 zero_bytes(u ^ 0x47474747u) | zero_bytes(u ^ 0x54545454u);
-  const u32 g = ((~ok) & 0x80808080u) >> 7;
-  return ((g * 0x08040201u) >> 24) & 0xFu;
-}
+// 16 ASCII bytes -> 32 bits of 2-bit codes (A0 C1 T2 G3, first base most significant) + 16 invalid-base bits: mgc_bases.hpp
+__device__ __forceinline__ void encode16(uint4 v, u32 &codes, u32 &inval) { encode16(v.x, v.y, v.z, v.w, codes, inval); }
 
-
-__device__ __forceinline__ void encode16(uint4 v, u32 &codes, u32 &inval) {
-  codes = (enc4(v.x) << 24) | (enc4(v.y) << 16) | (enc4(v.z) << 8) | enc4(v.w);
-  inval = (inv4(v.x) << 12) | (inv4(v.y) << 8) | (inv4(v.z) << 4) | inv4(v.w);
-}
+// The PACKED BASE STREAM of a count: what encode16 makes of every 16 bases of the input, counted from base 0 of the stream
+// whatever the alignment of the pointer -- `codes` in a u32 array, `inval` in a u16 array, 6 bytes per 16 bases.  The histogram
+// kernel of a count has to decode the ASCII bases anyway and stores both words for the tiles it owns; the partition kernel then
+// stages a tile from them (260 + 260 words, no encode16: a ninth of its VALU instructions, and 3.75 GB read per 10 Gbp instead
+// of 10).  Four more words behind the last tile -- its halo, all invalid, as load16 pads the ASCII stream -- are stored by
+// the owner of that tile, so that the reader needs no bounds test.  codes == nullptr: the ASCII path.
+struct PackedBases { u32 *codes; unsigned short *inval; };
 
 // reverse complement of a right-aligned k-mer (complement = xor 2 per base)
 __device__ __forceinline__ u64 revcomp64(u64 f, u32 key_shift /* 64-2k */) {
@@ -61,18 +49,22 @@ __device__ __forceinline__ u64 revcomp64(u64 f, u32 key_shift /* 64-2k */) {
 constexpr int KP_WORDS = KP_TILE / 16 + 4;            // 16 bases per staged word + 64-base halo
 
 // Stage one tile of bases as 2-bit codes + invalid masks in LDS.
+// pk.codes != nullptr: the tile's words go to the packed stream as well (`last`: the stream's last tile, whose halo goes too).
 __device__ __forceinline__ void kp_stage_tile(const uint8_t *__restrict__ bases, u64 n, u64 tile0, bool aligned,
-                                              u32 *s_codes, u32 *s_inval) {
+                                              u32 *s_codes, u32 *s_inval, PackedBases pk, bool last) {
   const u32 t = threadIdx.x;
+  const u64 w0 = tile0 / 16;
   {
     u32 c, iv;
     encode16(load16(bases, tile0 + (u64)t * 16, n, aligned), c, iv);
     s_codes[t] = c; s_inval[t] = iv;
+    if (pk.codes) { pk.codes[w0 + t] = c; pk.inval[w0 + t] = (unsigned short)iv; }
   }
   if (t < 4) {
     u32 c, iv;
     encode16(load16(bases, tile0 + (u64)KP_TILE + (u64)t * 16, n, aligned), c, iv);
     s_codes[KP_BLOCK + t] = c; s_inval[KP_BLOCK + t] = iv;
+    if (pk.codes && last) { pk.codes[w0 + KP_BLOCK + t] = c; pk.inval[w0 + KP_BLOCK + t] = (unsigned short)iv; }
   }
 }
 
@@ -227,7 +219,8 @@ __device__ __forceinline__ void kp_tile_range(u64 num_tiles, u64 &t_begin, u64 &
 template <typename K>
 __global__ __launch_bounds__(KP_BLOCK)
 void kmer_hist_kernel(const uint8_t *__restrict__ bases, u64 n, u32 k, int mode, u32 bucket_bits,
-                      u64 num_tiles, u64 *__restrict__ block_hist, u64 *__restrict__ bucket_counts, u64 sfx_mask, u64 sfx_test) {
+                      u64 num_tiles, u64 *__restrict__ block_hist, u64 *__restrict__ bucket_counts, u64 sfx_mask, u64 sfx_test,
+                      PackedBases pk) {
   __shared__ u32 s_codes[KP_WORDS];
   __shared__ u32 s_inval[KP_WORDS];
   __shared__ u32 s_hist[KP_MAX_BUCKETS];
@@ -244,7 +237,7 @@ void kmer_hist_kernel(const uint8_t *__restrict__ bases, u64 n, u32 k, int mode,
   u32 my_count = 0;
 
   for (u64 tile = t_begin; tile < t_end; tile++) {
-    kp_stage_tile(bases, n, tile * KP_TILE, aligned, s_codes, s_inval);
+    kp_stage_tile(bases, n, tile * KP_TILE, aligned, s_codes, s_inval, pk, tile + 1 == num_tiles);
     __syncthreads();
     if (sizeof(K) == 8 && nb > 1 && 2 * k >= bucket_bits && sfx_mask == 0) {
       u32 bk[KP_ITEMS];
@@ -305,7 +298,8 @@ __global__ __launch_bounds__(KP_BLOCK * KH_NV)
 void kmer_hist_fine_kernel(const uint8_t *__restrict__ bases, u64 n, u32 k_arg, int mode_arg, u64 num_tiles, u32 vgrid,
                            u64 *__restrict__ block_hist, u64 *__restrict__ bucket_counts, u64 *__restrict__ fine_hist,
                            u32 fbits = 6 /* HB == 0: the buckets of the per-workgroup rows and of bucket_counts are the top fbits (6..8) bits */,
-                           u32 nvp = KH_NV /* virtual workgroups (rows) this workgroup takes, one after the other */) {
+                           u32 nvp = KH_NV /* virtual workgroups (rows) this workgroup takes, one after the other */,
+                           PackedBases pk = PackedBases{nullptr, nullptr} /* the count's packed base stream, stored here */) {
   const u32 k = KC ? (u32)KC : k_arg;
   const int mode = KC ? 0 : mode_arg;
   constexpr u32 TABLE = HB ? hpc_table_size(HB) : (1u << KH_FINE_BITS);
@@ -358,7 +352,12 @@ void kmer_hist_fine_kernel(const uint8_t *__restrict__ bases, u64 n, u32 k_arg, 
         u32 c, iv;
         encode16(cur, c, iv);
         s_codes[buf][v][t] = c; s_inval[buf][v][t] = iv;
-        if (t < 4) { encode16(halo, c, iv); s_codes[buf][v][KP_BLOCK + t] = c; s_inval[buf][v][KP_BLOCK + t] = iv; }
+        const u64 w0 = tile * (u64)KP_BLOCK;
+        if (pk.codes) { pk.codes[w0 + t] = c; pk.inval[w0 + t] = (unsigned short)iv; }
+        if (t < 4) {
+          encode16(halo, c, iv); s_codes[buf][v][KP_BLOCK + t] = c; s_inval[buf][v][KP_BLOCK + t] = iv;
+          if (pk.codes && tile + 1 == num_tiles) { pk.codes[w0 + KP_BLOCK + t] = c; pk.inval[w0 + KP_BLOCK + t] = (unsigned short)iv; }
+        }
       }
       __syncthreads();
       fetch(tile + KH_NV);                                           // in flight behind the counting below
@@ -485,12 +484,15 @@ __device__ __forceinline__ void kp_gstore8(u64 addr, uint8_t v)  { *reinterpret_
 __device__ __forceinline__ void kp_gstore64(u64 addr, u64 v)     { *reinterpret_cast<kp_gu64 *>(addr) = v; }
 __device__ __forceinline__ void kp_gstore96(u64 addr, u32 a, u32 b, u32 c) { kp_u32x3 v; v.x = a; v.y = b; v.z = c; *reinterpret_cast<kp_gu32x3 *>(addr) = v; }
 
-template <typename K, int MAXB, bool SOA = false, int KC = 0, int BB = 6>   // BB: the bucket bits of a constant-k form (6: the files; 8: `compress` at 5 Gbp and beyond)
+// PK: the tile's codes and invalid masks come from the count's packed base stream (PackedBases, written by the histogram kernel),
+// prefetched a tile ahead like the ASCII loads -- no load of `bases`, no encode16.
+template <typename K, int MAXB, bool SOA = false, int KC = 0, int BB = 6, bool PK = false>   // BB: the bucket bits of a constant-k form (6: the files; 8: `compress` at 5 Gbp and beyond)
 __global__ __launch_bounds__(KP_BLOCK, (sizeof(K) == 16) ? 2 : 4)   // 16-byte keys: the 64 KiB exchange tile allows two workgroups; 8-byte: four (five left 96 VGPRs: 20 spilled at constant k)
 void kmer_partition_kernel(const uint8_t *__restrict__ bases, u64 n, u32 k_arg, int mode_arg, u32 bucket_bits_arg,
                            u64 num_tiles, const u64 *__restrict__ block_base, K *__restrict__ out, u64 sfx_mask_arg, u64 sfx_test,
                            const u64 *__restrict__ soa_starts = nullptr, const u64 *__restrict__ soa_counts = nullptr,
-                           u32 vgrid = 0 /* rows of block_base = virtual workgroups (0: one per workgroup) */) {
+                           u32 vgrid = 0 /* rows of block_base = virtual workgroups (0: one per workgroup) */,
+                           PackedBases pk = PackedBases{nullptr, nullptr}) {
   const u32 k = KC ? (u32)KC : k_arg;
   const int mode = KC ? 0 : mode_arg;
   const u32 bucket_bits = KC ? (u32)BB : bucket_bits_arg;
@@ -542,13 +544,22 @@ void kmer_partition_kernel(const uint8_t *__restrict__ bases, u64 n, u32 k_arg, 
   uint4 nx = make_uint4(0, 0, 0, 0), nx_halo = make_uint4(0, 0, 0, 0);
   auto prefetch = [&](u64 tile) __attribute__((always_inline)) {
     if (tile >= t_end) return;
-    nx = load16(bases, tile * KP_TILE + (u64)tid * 16, n, aligned);
-    if (tid < 4) nx_halo = load16(bases, tile * KP_TILE + (u64)KP_TILE + (u64)tid * 16, n, aligned);
+    if constexpr (PK) {                                              // (.x: codes, .y: inval; the halo = the first words of the next tile, or the stream's four trailing ones)
+      const u64 w0 = tile * (u64)KP_BLOCK;
+      nx.x = pk.codes[w0 + tid]; nx.y = pk.inval[w0 + tid];
+      if (tid < 4) { nx_halo.x = pk.codes[w0 + KP_BLOCK + tid]; nx_halo.y = pk.inval[w0 + KP_BLOCK + tid]; }
+    } else {
+      nx = load16(bases, tile * KP_TILE + (u64)tid * 16, n, aligned);
+      if (tid < 4) nx_halo = load16(bases, tile * KP_TILE + (u64)KP_TILE + (u64)tid * 16, n, aligned);
+    }
   };
   prefetch(t_begin);
   for (u64 tile = t_begin; tile < t_end; tile++) {
     for (u32 b = tid; b < nb; b += KP_BLOCK) s_cnt[b] = 0;
-    {
+    if constexpr (PK) {
+      s_codes[tid] = nx.x; s_inval[tid] = nx.y;
+      if (tid < 4) { s_codes[KP_BLOCK + tid] = nx_halo.x; s_inval[KP_BLOCK + tid] = nx_halo.y; }
+    } else {
       u32 c, iv;
       encode16(nx, c, iv);
       s_codes[tid] = c; s_inval[tid] = iv;
@@ -675,9 +686,19 @@ size_t kp_workspace_bytes(uint32_t bucket_bits) {
   return (size_t)(bucket_bits > 8 ? KP_PHYS : KP_VGRID) * ((size_t)1 << bucket_bits) * sizeof(uint64_t);
 }
 
+// the packed base stream of n_bases bases in one buffer: u32 codes[words] followed by u16 inval[words], words = 256 per tile + 4
+static uint64_t kp_packed_words(uint64_t n_bases) { return (n_bases + KP_TILE - 1) / KP_TILE * (uint64_t)KP_BLOCK + 4; }
+size_t kp_packed_bytes(uint64_t n_bases) { return (size_t)(kp_packed_words(n_bases) * 6); }
+static PackedBases kp_packed(void *d_packed, uint64_t n_bases) {
+  if (!d_packed) return PackedBases{nullptr, nullptr};
+  u32 *codes = reinterpret_cast<u32 *>(d_packed);
+  return PackedBases{codes, reinterpret_cast<unsigned short *>(codes + kp_packed_words(n_bases))};
+}
+
 hipError_t launch_kmer_histogram(const uint8_t *d_bases, uint64_t n_bases, uint32_t k, int mode,
                                  uint32_t bucket_bits, uint64_t *d_bucket_counts, void *d_ws, hipStream_t st,
-                                 uint64_t sfx_mask, uint64_t sfx_test) {
+                                 uint64_t sfx_mask, uint64_t sfx_test, void *d_packed) {
+  const PackedBases pk = kp_packed(d_packed, n_bases);
   const uint32_t nb = 1u << bucket_bits;
   MGC_CHECK(hipMemsetAsync(d_bucket_counts, 0, sizeof(uint64_t) * nb, st));
   if (n_bases == 0) return hipSuccess;
@@ -686,11 +707,11 @@ hipError_t launch_kmer_histogram(const uint8_t *d_bases, uint64_t n_bases, uint3
   if (k <= 32)
     hipLaunchKernelGGL(kmer_hist_kernel<u64>, dim3(grid), dim3(KP_BLOCK), 0, st,
                        d_bases, (u64)n_bases, k, mode, bucket_bits, (u64)num_tiles,
-                       reinterpret_cast<u64 *>(d_ws), reinterpret_cast<u64 *>(d_bucket_counts), (u64)sfx_mask, (u64)sfx_test);
+                       reinterpret_cast<u64 *>(d_ws), reinterpret_cast<u64 *>(d_bucket_counts), (u64)sfx_mask, (u64)sfx_test, pk);
   else
     hipLaunchKernelGGL(kmer_hist_kernel<K128>, dim3(grid), dim3(KP_BLOCK), 0, st,
                        d_bases, (u64)n_bases, k, mode, bucket_bits, (u64)num_tiles,
-                       reinterpret_cast<u64 *>(d_ws), reinterpret_cast<u64 *>(d_bucket_counts), (u64)sfx_mask, (u64)sfx_test);
+                       reinterpret_cast<u64 *>(d_ws), reinterpret_cast<u64 *>(d_bucket_counts), (u64)sfx_mask, (u64)sfx_test, pk);
   return hipGetLastError();
 }
 
@@ -702,8 +723,10 @@ bool kmer_histogram_fine_bits_ok(uint32_t k, uint32_t bucket_bits) { return k <=
 
 // launch_kmer_histogram + d_fine_hist[2^15] (zeroed here): k-mers per (file, next nine bits)
 hipError_t launch_kmer_histogram_fine(const uint8_t *d_bases, uint64_t n_bases, uint32_t k, int mode, uint64_t *d_bucket_counts,
-                                      uint64_t *d_fine_hist, void *d_ws, hipStream_t st, bool const_k, uint32_t bucket_bits) {
+                                      uint64_t *d_fine_hist, void *d_ws, hipStream_t st, bool const_k, uint32_t bucket_bits,
+                                      void *d_packed) {
   if (bucket_bits < 6 || bucket_bits > 8) return hipErrorInvalidValue;
+  const PackedBases pk = kp_packed(d_packed, n_bases);
   MGC_CHECK(hipMemsetAsync(d_bucket_counts, 0, sizeof(uint64_t) << bucket_bits, st));
   MGC_CHECK(hipMemsetAsync(d_fine_hist, 0, sizeof(uint64_t) << KH_FINE_BITS, st));
   if (n_bases == 0) return hipSuccess;
@@ -725,7 +748,7 @@ hipError_t launch_kmer_histogram_fine(const uint8_t *d_bases, uint64_t n_bases, 
 #define MGC_KH_LAUNCH(KC_)                                                                                                             \
   hipLaunchKernelGGL((kmer_hist_fine_kernel<0, KC_>), dim3((vgrid + nvp - 1) / nvp), dim3(KP_BLOCK * KH_NV), sizeof(u32) << KH_FINE_BITS, st, \
                      d_bases, (u64)n_bases, k, mode, (u64)num_tiles, vgrid, reinterpret_cast<u64 *>(d_ws),                             \
-                     reinterpret_cast<u64 *>(d_bucket_counts), reinterpret_cast<u64 *>(d_fine_hist), bucket_bits, nvp)
+                     reinterpret_cast<u64 *>(d_bucket_counts), reinterpret_cast<u64 *>(d_fine_hist), bucket_bits, nvp, pk)
   const int kc = kmer_const_k(k, mode, const_k);
   if (kc == 21) MGC_KH_LAUNCH(21); else if (kc == 31) MGC_KH_LAUNCH(31); else if (kc == 51) MGC_KH_LAUNCH(51); else MGC_KH_LAUNCH(0);
 #undef MGC_KH_LAUNCH
@@ -740,8 +763,10 @@ bool kmer_histogram_hpc_ok(uint32_t k, uint32_t bucket_bits, uint64_t sfx_mask, 
 uint32_t kmer_histogram_hpc_entries(uint32_t bucket_bits) { return hpc_table_size((int)(bucket_bits / 2 + 5)); }
 
 hipError_t launch_kmer_histogram_hpc(const uint8_t *d_bases, uint64_t n_bases, uint32_t k, int mode, uint32_t bucket_bits,
-                                     uint64_t *d_bucket_counts, uint64_t *d_fine_hist, void *d_ws, hipStream_t st, bool const_k) {
+                                     uint64_t *d_bucket_counts, uint64_t *d_fine_hist, void *d_ws, hipStream_t st, bool const_k,
+                                     void *d_packed) {
   if (bucket_bits != 6 && bucket_bits != 8) return hipErrorInvalidValue;
+  const PackedBases pk = kp_packed(d_packed, n_bases);
   const uint32_t entries = kmer_histogram_hpc_entries(bucket_bits);
   MGC_CHECK(hipMemsetAsync(d_bucket_counts, 0, sizeof(uint64_t) << bucket_bits, st));
   MGC_CHECK(hipMemsetAsync(d_fine_hist, 0, sizeof(uint64_t) * entries, st));
@@ -765,25 +790,53 @@ hipError_t launch_kmer_histogram_hpc(const uint8_t *d_bases, uint64_t n_bases, u
   if (k31 && bucket_bits == 6)
     hipLaunchKernelGGL((kmer_hist_fine_kernel<8, 31>), dim3((vgrid + nvp - 1) / nvp), dim3(KP_BLOCK * KH_NV), sizeof(u32) * entries, st,
                        d_bases, (u64)n_bases, k, mode, (u64)num_tiles, vgrid, reinterpret_cast<u64 *>(d_ws),
-                       reinterpret_cast<u64 *>(d_bucket_counts), reinterpret_cast<u64 *>(d_fine_hist), 6u, nvp);
+                       reinterpret_cast<u64 *>(d_bucket_counts), reinterpret_cast<u64 *>(d_fine_hist), 6u, nvp, pk);
   else if (k31)
     hipLaunchKernelGGL((kmer_hist_fine_kernel<9, 31>), dim3((vgrid + nvp - 1) / nvp), dim3(KP_BLOCK * KH_NV), sizeof(u32) * entries, st,
                        d_bases, (u64)n_bases, k, mode, (u64)num_tiles, vgrid, reinterpret_cast<u64 *>(d_ws),
-                       reinterpret_cast<u64 *>(d_bucket_counts), reinterpret_cast<u64 *>(d_fine_hist), 6u, nvp);
+                       reinterpret_cast<u64 *>(d_bucket_counts), reinterpret_cast<u64 *>(d_fine_hist), 6u, nvp, pk);
   else if (bucket_bits == 6)
     hipLaunchKernelGGL(kmer_hist_fine_kernel<8>, dim3((vgrid + nvp - 1) / nvp), dim3(KP_BLOCK * KH_NV), sizeof(u32) * entries, st,
                        d_bases, (u64)n_bases, k, mode, (u64)num_tiles, vgrid, reinterpret_cast<u64 *>(d_ws),
-                       reinterpret_cast<u64 *>(d_bucket_counts), reinterpret_cast<u64 *>(d_fine_hist), 6u, nvp);
+                       reinterpret_cast<u64 *>(d_bucket_counts), reinterpret_cast<u64 *>(d_fine_hist), 6u, nvp, pk);
   else
     hipLaunchKernelGGL(kmer_hist_fine_kernel<9>, dim3((vgrid + nvp - 1) / nvp), dim3(KP_BLOCK * KH_NV), sizeof(u32) * entries, st,
                        d_bases, (u64)n_bases, k, mode, (u64)num_tiles, vgrid, reinterpret_cast<u64 *>(d_ws),
-                       reinterpret_cast<u64 *>(d_bucket_counts), reinterpret_cast<u64 *>(d_fine_hist), 6u, nvp);
+                       reinterpret_cast<u64 *>(d_bucket_counts), reinterpret_cast<u64 *>(d_fine_hist), 6u, nvp, pk);
   return hipGetLastError();
+}
+
+// One launch of kmer_partition_kernel<K, MAXB, SOA, KC, BB>: its PK form when the count has a packed base stream, the ASCII form
+// otherwise.  (16-byte keys: the 64 KiB exchange tile is above the default limit of dynamic LDS -- raised once per instantiation.)
+struct KpLaunch {
+  const uint8_t *d_bases; uint64_t n_bases; uint32_t k; int mode; uint32_t bucket_bits; uint64_t num_tiles;
+  void *d_ws, *d_keys; uint64_t sfx_mask, sfx_test; const u64 *soa_starts, *soa_counts; uint32_t rows, grid; hipStream_t st;
+  PackedBases pk;
+};
+template <typename K, int MAXB, bool SOA, int KC, int BB, bool PK>
+static void kp_launch_form(const KpLaunch &a) {
+  if constexpr (sizeof(K) == 16) {
+    static bool attr_done = false;
+    if (!attr_done) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kmer_partition_kernel<K, MAXB, SOA, KC, BB, PK>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(KP_TILE * sizeof(K)));
+      attr_done = true;
+    }
+  }
+  hipLaunchKernelGGL((kmer_partition_kernel<K, MAXB, SOA, KC, BB, PK>), dim3(a.grid), dim3(KP_BLOCK), KP_TILE * sizeof(K), a.st,
+                     a.d_bases, (u64)a.n_bases, a.k, a.mode, a.bucket_bits, (u64)a.num_tiles, reinterpret_cast<const u64 *>(a.d_ws),
+                     reinterpret_cast<K *>(a.d_keys), (u64)a.sfx_mask, (u64)a.sfx_test, a.soa_starts, a.soa_counts, a.rows, a.pk);
+}
+template <typename K, int MAXB, bool SOA, int KC, int BB = 6>
+static void kp_launch(const KpLaunch &a) {
+  if (a.pk.codes) kp_launch_form<K, MAXB, SOA, KC, BB, true>(a);
+  else            kp_launch_form<K, MAXB, SOA, KC, BB, false>(a);
 }
 
 hipError_t launch_kmer_partition(const uint8_t *d_bases, uint64_t n_bases, uint32_t k, int mode,
                                  uint32_t bucket_bits, const uint64_t *d_bucket_starts, void *d_keys,
-                                 void *d_ws, hipStream_t st, uint64_t sfx_mask, uint64_t sfx_test, const uint64_t *d_soa_counts, bool const_k) {
+                                 void *d_ws, hipStream_t st, uint64_t sfx_mask, uint64_t sfx_test, const uint64_t *d_soa_counts, bool const_k,
+                                 void *d_packed) {
   if (n_bases == 0) return hipSuccess;
   const uint32_t nb = 1u << bucket_bits;
   const uint64_t num_tiles = (n_bases + KP_TILE - 1) / KP_TILE;
@@ -792,67 +845,23 @@ hipError_t launch_kmer_partition(const uint8_t *d_bases, uint64_t n_bases, uint3
   hipLaunchKernelGGL(kmer_scan_kernel, dim3(nb), dim3(256), 0, st,
                      reinterpret_cast<u64 *>(d_ws), rows, nb, reinterpret_cast<const u64 *>(d_bucket_starts));
   MGC_CHECK(hipGetLastError());
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kmer_partition_kernel<K128, 64>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(KP_TILE * sizeof(K128)));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kmer_partition_kernel<K128, KP_MAX_BUCKETS>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(KP_TILE * sizeof(K128)));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kmer_partition_kernel<K128, 64, false, 51>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(KP_TILE * sizeof(K128)));
-    attr_done = true;
-  }
-#define MGC_KP_LAUNCH(K_, MAXB_)                                                                                   \
-  hipLaunchKernelGGL((kmer_partition_kernel<K_, MAXB_>), dim3(grid), dim3(KP_BLOCK), KP_TILE * sizeof(K_), st,      \
-                     d_bases, (u64)n_bases, k, mode, bucket_bits, (u64)num_tiles,                                  \
-                     reinterpret_cast<const u64 *>(d_ws), reinterpret_cast<K_ *>(d_keys), (u64)sfx_mask, (u64)sfx_test, (const u64 *)nullptr, (const u64 *)nullptr, rows)
-  if (d_soa_counts && k > 32) {                                       // K96 records (k = 33..51)
-    if (!(k <= 51 && nb == 64 && sfx_mask == 0)) return hipErrorInvalidValue;
-    static bool a96 = false;
-    if (!a96) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kmer_partition_kernel<K128, 64, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(KP_TILE * sizeof(K128)));
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kmer_partition_kernel<K128, 64, true, 51>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(KP_TILE * sizeof(K128)));
-      a96 = true;
-    }
-    if (kmer_const_k(k, mode, const_k) == 51)
-      hipLaunchKernelGGL((kmer_partition_kernel<K128, 64, true, 51>), dim3(grid), dim3(KP_BLOCK), KP_TILE * sizeof(K128), st, d_bases, (u64)n_bases, k, mode,
-                         bucket_bits, (u64)num_tiles, reinterpret_cast<const u64 *>(d_ws), reinterpret_cast<K128 *>(d_keys), (u64)0, (u64)0,
-                         reinterpret_cast<const u64 *>(d_bucket_starts), reinterpret_cast<const u64 *>(d_soa_counts), rows);
-    else
-      hipLaunchKernelGGL((kmer_partition_kernel<K128, 64, true>), dim3(grid), dim3(KP_BLOCK), KP_TILE * sizeof(K128), st, d_bases, (u64)n_bases, k, mode,
-                         bucket_bits, (u64)num_tiles, reinterpret_cast<const u64 *>(d_ws), reinterpret_cast<K128 *>(d_keys), (u64)0, (u64)0,
-                         reinterpret_cast<const u64 *>(d_bucket_starts), reinterpret_cast<const u64 *>(d_soa_counts), rows);
+  const KpLaunch a{d_bases, n_bases, k, mode, bucket_bits, num_tiles, d_ws, d_keys, sfx_mask, sfx_test, nullptr, nullptr, rows, grid, st,
+                   kp_packed(d_packed, n_bases)};
+  const int kck = (sfx_mask == 0) ? kmer_const_k(k, mode, const_k) : 0;
+  if (d_soa_counts) {
+    if (!(nb == 64 && sfx_mask == 0 && k <= 51)) return hipErrorInvalidValue;
+    KpLaunch s = a;
+    s.soa_starts = reinterpret_cast<const u64 *>(d_bucket_starts); s.soa_counts = reinterpret_cast<const u64 *>(d_soa_counts);
+    if (k > 32) { if (kck == 51) kp_launch<K128, 64, true, 51>(s); else kp_launch<K128, 64, true, 0>(s); }   // K96 records (k = 33..51)
+    else        { if (kck == 21) kp_launch<u64, 64, true, 21>(s);  else kp_launch<u64, 64, true, 0>(s); }    // 5-byte layout (kmer_partition_soa_ok)
     return hipGetLastError();
   }
-  if (d_soa_counts) {                                                 // 5-byte layout (kmer_partition_soa_ok)
-    if (!(k <= 32 && nb == 64 && sfx_mask == 0)) return hipErrorInvalidValue;
-    if (kmer_const_k(k, mode, const_k) == 21)
-      hipLaunchKernelGGL((kmer_partition_kernel<u64, 64, true, 21>), dim3(grid), dim3(KP_BLOCK), KP_TILE * sizeof(u64), st, d_bases, (u64)n_bases, k, mode,
-                         bucket_bits, (u64)num_tiles, reinterpret_cast<const u64 *>(d_ws), reinterpret_cast<u64 *>(d_keys), (u64)0, (u64)0,
-                         reinterpret_cast<const u64 *>(d_bucket_starts), reinterpret_cast<const u64 *>(d_soa_counts), rows);
-    else
-      hipLaunchKernelGGL((kmer_partition_kernel<u64, 64, true>), dim3(grid), dim3(KP_BLOCK), KP_TILE * sizeof(u64), st, d_bases, (u64)n_bases, k, mode,
-                         bucket_bits, (u64)num_tiles, reinterpret_cast<const u64 *>(d_ws), reinterpret_cast<u64 *>(d_keys), (u64)0, (u64)0,
-                         reinterpret_cast<const u64 *>(d_bucket_starts), reinterpret_cast<const u64 *>(d_soa_counts), rows);
-    return hipGetLastError();
-  }
-#define MGC_KPC_LAUNCH(K_, KC_)                                                                                    \
-  hipLaunchKernelGGL((kmer_partition_kernel<K_, 64, false, KC_>), dim3(grid), dim3(KP_BLOCK), KP_TILE * sizeof(K_), st, \
-                     d_bases, (u64)n_bases, k, mode, bucket_bits, (u64)num_tiles,                                  \
-                     reinterpret_cast<const u64 *>(d_ws), reinterpret_cast<K_ *>(d_keys), (u64)0, (u64)0, (const u64 *)nullptr, (const u64 *)nullptr, rows)
-  const int kc = (nb == 64 && sfx_mask == 0) ? kmer_const_k(k, mode, const_k) : 0;
-  if (nb == 256 && sfx_mask == 0 && kmer_const_k(k, mode, const_k) == 31)          // (k = 31 `compress` beyond ~4 Gbp: 256 buckets, 4 KiB of tables instead of 16)
-    hipLaunchKernelGGL((kmer_partition_kernel<u64, 256, false, 31, 8>), dim3(grid), dim3(KP_BLOCK), KP_TILE * sizeof(u64), st,
-                       d_bases, (u64)n_bases, k, mode, bucket_bits, (u64)num_tiles, reinterpret_cast<const u64 *>(d_ws), reinterpret_cast<u64 *>(d_keys), (u64)0, (u64)0, (const u64 *)nullptr, (const u64 *)nullptr, rows);
-  else if (kc == 21) MGC_KPC_LAUNCH(u64, 21);
-  else if (kc == 31) MGC_KPC_LAUNCH(u64, 31);
-  else if (kc == 51) MGC_KPC_LAUNCH(K128, 51);
-  else if (k <= 32) { if (nb <= 64) MGC_KP_LAUNCH(u64, 64); else MGC_KP_LAUNCH(u64, KP_MAX_BUCKETS); }
-  else              { if (nb <= 64) MGC_KP_LAUNCH(K128, 64); else MGC_KP_LAUNCH(K128, KP_MAX_BUCKETS); }
-#undef MGC_KPC_LAUNCH
-#undef MGC_KP_LAUNCH
+  if (nb == 256 && kck == 31) kp_launch<u64, 256, false, 31, 8>(a);   // (k = 31 `compress` beyond ~4 Gbp: 256 buckets, 4 KiB of tables instead of 16)
+  else if (nb == 64 && kck == 21) kp_launch<u64, 64, false, 21>(a);
+  else if (nb == 64 && kck == 31) kp_launch<u64, 64, false, 31>(a);
+  else if (nb == 64 && kck == 51) kp_launch<K128, 64, false, 51>(a);
+  else if (k <= 32) { if (nb <= 64) kp_launch<u64, 64, false, 0>(a);  else kp_launch<u64, KP_MAX_BUCKETS, false, 0>(a); }
+  else              { if (nb <= 64) kp_launch<K128, 64, false, 0>(a); else kp_launch<K128, KP_MAX_BUCKETS, false, 0>(a); }
   return hipGetLastError();
 }
 
