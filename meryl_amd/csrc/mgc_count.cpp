@@ -331,6 +331,7 @@ struct Count {
   static constexpr uint32_t ev_per_file = 2 * 16;        // room for 16 passes per file
   std::vector<hipEvent_t> pass_ev;
   uint32_t sort_launch_groups = 0;
+  int group_dbg_left = 2;                                // MGC_GROUP_DBG: instrumented files this count may still run (GroupFile::dbg)
 
   // the finish path
   int probe = -1;
@@ -620,22 +621,30 @@ int Count::group_file(uint32_t b) {
   if (x.size == 0) return MGC_OK;
   void *src = seg(b);
   hipEvent_t *pe = s->profiling ? &pass_ev[(size_t)b * ev_per_file] : nullptr;
+  const bool msd = d_nhdrs && d_nws && (x.kind == Group::WIDE || x.msd_ok);
+  mgc::GroupFile f;
+  f.keys = src; f.alt = (void *)Y; f.n = x.size; f.plan = &x.sp;
+  f.layout = x.k96 ? mgc::GroupKeys::K96 : (kw == 2 ? mgc::GroupKeys::K128 : (soa_hi_mask ? mgc::GroupKeys::SOA5 : mgc::GroupKeys::U64));
+  f.soa_hi_mask = soa_hi_mask;
+  f.d_error = d_err; f.d_sub_starts = d_substart + x.sbase; f.st = st; f.pass_events = pe;
+  f.prepared = msd ? (void *)(d_nhdrs + hdr_bytes * b) : nullptr; f.scratch = msd ? (void *)(d_nws + x.nws_off) : nullptr;
+  f.ws = sort_ws; f.ws_bytes = sort_ws_bytes - 256;
+  f.pipe = sw.group_pipe; f.stagger = sw.pass_stagger;
+  f.dbg = sw.group_dbg && msd && x.kind == Group::NARROW && group_dbg_left > 0;     // (developer output: the first two such files of a count)
   switch (x.kind) {
   case Group::NONE:                                        // (a file of one sub-bucket: nothing to group)
     return MGC_OK;
-  case Group::NARROW: {                                    // X (8 B) -> Y (4 B) -> front of X (4 B); boundaries included
-    const bool msd = d_nhdrs && d_nws && x.msd_ok;
-    HIP_TRY(s, mgc::launch_group_narrow(src, (void *)Y, x.size, x.sp, sort_ws, sort_ws_bytes - 256, d_err, d_substart + x.sbase, st, pe,
-                                        msd ? (void *)(d_nhdrs + hdr_bytes * b) : nullptr, msd ? (void *)(d_nws + x.nws_off) : nullptr,
-                                        &x.tr_a, &x.tr_b, soa_hi_mask, sw.group_dbg, sw.group_pipe, sw.pass_stagger));
+  case Group::NARROW:                                      // X (8 B) -> Y (4 B) -> front of X (4 B); boundaries included
+    HIP_TRY(s, mgc::launch_group_narrow(f));
+    if (f.dbg) group_dbg_left--;
+    x.tr_a = f.tr_a; x.tr_b = f.tr_b;
     x.passes = 2;
     x.narrowed = true;
     break;
-  }
   case Group::WIDE:                                        // X -> Y -> X, whole keys; boundaries included
     if (d_nhdrs) {
-      HIP_TRY(s, mgc::launch_group_wide(src, (void *)Y, x.size, kw, x.sp, d_err, d_substart + x.sbase, st, pe,
-                                        (void *)(d_nhdrs + hdr_bytes * b), (void *)(d_nws + x.nws_off), &x.tr_a, &x.tr_b, x.k96));
+      HIP_TRY(s, mgc::launch_group_wide(f));
+      x.tr_a = f.tr_a; x.tr_b = f.tr_b;
       x.passes = 2;
       x.k96_passes = x.k96;
       prof.wide_msd_files++;

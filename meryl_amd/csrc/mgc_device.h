@@ -87,7 +87,7 @@ hipError_t launch_kmer_partition(const uint8_t *d_bases, uint64_t n_bases, uint3
                                  uint32_t bucket_bits, const uint64_t *d_bucket_starts, void *d_keys,
                                  void *d_ws, hipStream_t st, uint64_t sfx_mask = 0, uint64_t sfx_test = 0,
                                  const uint64_t *d_soa_counts = nullptr /*64 buckets, 8-byte keys, <= 40 bits below the file: a file's region =
-                                 u32[count] low words + u8[count] bits 32..39 (5 bytes per k-mer; launch_group_narrow(soa_hi_mask))*/,
+                                 u32[count] low words + u8[count] bits 32..39 (5 bytes per k-mer; GroupKeys::SOA5)*/,
                                  bool const_k = true /*Switches::const_k*/, void *d_packed = nullptr);
 
 // ---- radix sort ------------------------------------------------------------
@@ -123,43 +123,59 @@ hipError_t launch_radix_sort(void *d_keys, void *d_alt, uint64_t n, uint32_t key
                              void *d_ws, size_t ws_bytes, uint32_t *d_error, int *result_in_alt,
                              hipStream_t st, hipEvent_t *pass_events /* 2 per pass or null */);
 size_t     sort_header_bytes();
-// Two grouping passes with NARROWED keys: uint64 keys whose bits above the first digit fit 32 bits leave the first pass as
-// uint32 words without that digit (its value is where the key lies), the second pass and the finish move half the bytes,
-// and the sub-bucket boundaries fall out of the second pass's look-back granules.  d_keys: uint64[n] in, uint32[n] out
-// (over its first half); d_alt: room for n uint32; d_sub_starts: 2^(pass_bits[0] + pass_bits[1]) + 1 entries.
-bool       sort_plan_narrows(const SortPlan &plan, uint64_t n, uint32_t key_words, bool on = true /*Switches::narrow*/);
+// ---- the two grouping passes of one file, boundaries included (mgc_sort.hip; which kernel a pass runs: mgc_group_route.hpp) ----
+enum class GroupKeys : uint32_t {
+  U64,                          // 8-byte keys
+  SOA5,                         // the 5-byte layout of launch_kmer_partition(d_soa_counts): u32[n] low words, then u8[n] bits 32..39 (narrowed files only)
+  K128,                         // 16-byte keys
+  K96,                          // 12-byte K96 records (launch_kmer_partition(d_soa_counts) at k = 33..51; whole-key files only)
+};
+// One file's grouping launch: what launch_group_narrow and launch_group_wide take.
+//
+// launch_group_narrow -- two grouping passes with NARROWED keys: uint64 keys whose bits above the first digit fit 32 bits leave the
+// first pass as uint32 words without that digit (its value is where the key lies), the second pass and the finish move half the
+// bytes, and the sub-bucket boundaries fall out of the second pass's look-back granules.  keys: uint64[n] (or the 5-byte layout)
+// in, uint32[n] out (over its first half); alt: room for n uint32; d_sub_starts: 2^(pass_bits[0] + pass_bits[1]) + 1 entries.
 // The high-digit-first form (files of a session with the fifteen-bit file histogram): launch_narrow_prepare fills one
-// header per file (nb <= 64, sort_header_bytes() apart) from d_fine; every file then gets its header and a scratch area of
-// narrow_scratch_bytes(n) that the caller has zeroed.  See mgc_sort.hip: nobody reads the
-// keys for a digit histogram, and the sub-buckets come out in the order tr_index(., *tr_a, *tr_b) describes.
-// d_prepared / d_scratch == nullptr: low digit first off one histogram read, scratch in d_ws, sub-buckets in key order.
+// header per file (nb <= 64, sort_header_bytes() apart) from d_fine; every file then gets its header (prepared) and a scratch area
+// of narrow_scratch_bytes(n) that the caller has zeroed.  See mgc_sort.hip: nobody reads the
+// keys for a digit histogram, and the sub-buckets come out in the order tr_index(., tr_a, tr_b) describes.
+// prepared / scratch == nullptr: low digit first off one histogram read, scratch in ws, sub-buckets in key order.
+//
+// launch_group_wide -- the same high-digit-first form for WHOLE keys (8-byte keys that leave more than 32 bits below their first
+// digit: k = 27..32 at the 10 Gbp scale; every 16-byte key): the high digit's histogram comes from the fifteen-bit file histogram
+// (launch_narrow_prepare), the first pass counts the low digit as it goes, the boundaries fall out of the second pass's
+// look-back granules -- neither the 8/16 B per k-mer digit-histogram read nor the boundary search over the grouped keys
+// happens.  keys: n keys in, the grouped keys out (same place); alt: room for n keys; scratch: wide_scratch_bytes(n,
+// key_words), zeroed by the caller; sub-buckets in tr_index(., tr_a, tr_b) order.
+// `compress`: the plan's digits are dense ranks (make_hpc_group_plan, two digits); the headers then come from
+// launch_hpc_prepare (the histogram of launch_kmer_histogram_hpc; `on`: one bit per bucket, nb <= 256)
+struct GroupFile {
+  void *keys = nullptr, *alt = nullptr;
+  uint64_t n = 0;
+  const SortPlan *plan = nullptr;
+  GroupKeys layout = GroupKeys::U64;
+  uint32_t soa_hi_mask = 0;                   // SOA5: the mask of the u8 array's payload bits (bits 32.. of the k-mer below the file)
+  uint32_t *d_error = nullptr;                // the count's look-back time-out flag
+  uint64_t *d_sub_starts = nullptr;           // out: the sub-bucket boundaries, in PHYSICAL order
+  hipStream_t st = nullptr;
+  hipEvent_t *pass_events = nullptr;          // 4 or null
+  void *prepared = nullptr, *scratch = nullptr;   // high digit first: this file's header and its look-back scratch
+  void *ws = nullptr; size_t ws_bytes = 0;    // narrowed files: the shared sort workspace (sort_workspace_bytes(n)), used low digit first
+  bool pipe = false;                          // Switches::group_pipe: the fetch a whole tile ahead (the 5-byte first pass)
+  uint32_t stagger = 0;                       // Switches::pass_stagger: the 5-byte first pass's workgroups start in that many groups, a tile's time shared between them
+  bool dbg = false;                           // narrowed files, high digit first: the instrumented instantiations, their cycle sums on stderr
+  uint32_t tr_a = 0, tr_b = 0;                // out: sub-bucket p holds the k-mers whose top bits are tr_index(p, tr_a, tr_b) (tr_a = 0: p itself)
+};
+bool       sort_plan_narrows(const SortPlan &plan, uint64_t n, uint32_t key_words, bool on = true /*Switches::narrow*/);
 size_t     narrow_scratch_bytes(uint64_t n);
 hipError_t launch_narrow_prepare(const uint64_t *d_fine, uint32_t nb, const unsigned char *bits_a, const unsigned char *on, void *d_hdrs,
                                  hipStream_t st);
-hipError_t launch_group_narrow(void *d_keys, void *d_alt, uint64_t n, const SortPlan &plan, void *d_ws, size_t ws_bytes,
-                               uint32_t *d_error, uint64_t *d_sub_starts, hipStream_t st, hipEvent_t *pass_events /* 4 or null */,
-                               void *d_prepared, void *d_scratch, uint32_t *tr_a, uint32_t *tr_b,
-                               uint32_t soa_hi_mask = 0 /*nonzero: d_keys is the 5-byte layout of launch_kmer_partition(d_soa_counts); the mask of
-                               the u8 array's payload bits (bits 32.. of the k-mer below the file)*/,
-                               bool group_dbg = false /*Switches::group_dbg*/,
-                               bool pipe = true /*Switches::group_pipe: the fetch a whole tile ahead (the 5-byte first pass, the second pass)*/,
-                               uint32_t stagger = 0 /*Switches::pass_stagger: the first pass's workgroups start in that many groups, a tile's time shared between them*/);
-
-// The same high-digit-first form for WHOLE keys (8-byte keys that leave more than 32 bits below their first digit: k = 27..32
-// at the 10 Gbp scale; every 16-byte key): the high digit's histogram comes from the fifteen-bit file histogram
-// (launch_narrow_prepare), the first pass counts the low digit as it goes, the boundaries fall out of the second pass's
-// look-back granules -- neither the 8/16 B per k-mer digit-histogram read nor the boundary search over the grouped keys
-// happens.  d_keys: n keys in, the grouped keys out (same place); d_alt: room for n keys; d_scratch: wide_scratch_bytes(n,
-// key_words), zeroed by the caller; sub-buckets in tr_index(., *tr_a, *tr_b) order.
-// `compress`: the plan's digits are dense ranks (make_hpc_group_plan, two digits); the headers then come from
-// launch_hpc_prepare (the histogram of launch_kmer_histogram_hpc; `on`: one bit per bucket, nb <= 256)
+hipError_t launch_group_narrow(GroupFile &f);
 bool       sort_plan_wide_msd(const SortPlan &plan, uint64_t n, bool on = true /*Switches::wide_msd*/);
 hipError_t launch_hpc_prepare(const uint64_t *d_fine_hpc, uint32_t bucket_bits, const uint64_t on[4], void *d_hdrs, hipStream_t st);
 size_t     wide_scratch_bytes(uint64_t n, uint32_t key_words);
-hipError_t launch_group_wide(void *d_keys, void *d_alt, uint64_t n, uint32_t key_words, const SortPlan &plan, uint32_t *d_error,
-                             uint64_t *d_sub_starts, hipStream_t st, hipEvent_t *pass_events /* 4 or null */, void *d_prepared,
-                             void *d_scratch, uint32_t *tr_a, uint32_t *tr_b,
-                             bool k96 = false /* d_keys / d_alt hold 12-byte K96 records (launch_kmer_partition(d_soa_counts) at k = 33..51) */);
+hipError_t launch_group_wide(GroupFile &f);
 
 // ---- run-length count ------------------------------------------------------
 size_t     rle_workspace_bytes(uint64_t n);

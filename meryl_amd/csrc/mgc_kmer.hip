@@ -721,38 +721,50 @@ bool kmer_histogram_fine_ok(uint32_t k, uint32_t bucket_bits, uint64_t sfx_mask,
 // (the bare operator of a sharded count's senders: buckets of 6..8 bits)
 bool kmer_histogram_fine_bits_ok(uint32_t k, uint32_t bucket_bits) { return k <= 64 && 2 * k >= (uint32_t)KH_FINE_BITS + 2 && bucket_bits >= 6 && bucket_bits <= 8; }
 
+// One launch of kmer_hist_fine_kernel<HB, KC>: the table (128 KiB; `compress`: 4 * 3^(HB-1) counters) is above the default limit of
+// dynamic LDS -- raised once per instantiation.
+struct KhLaunch {
+  const uint8_t *d_bases; uint64_t n_bases; uint32_t k; int mode; uint64_t num_tiles; uint32_t vgrid;
+  void *d_ws; uint64_t *d_bucket_counts, *d_fine_hist; uint32_t fbits, nvp; hipStream_t st; PackedBases pk;
+};
+template <int HB, int KC>
+static hipError_t kh_launch_form(const KhLaunch &a) {
+  constexpr size_t LDS = sizeof(u32) * (HB ? hpc_table_size(HB) : (1u << KH_FINE_BITS));
+  static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void *>(&kmer_hist_fine_kernel<HB, KC>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
+  (void)raised;
+  hipLaunchKernelGGL((kmer_hist_fine_kernel<HB, KC>), dim3((a.vgrid + a.nvp - 1) / a.nvp), dim3(KP_BLOCK * KH_NV), LDS, a.st,
+                     a.d_bases, (u64)a.n_bases, a.k, a.mode, (u64)a.num_tiles, a.vgrid, reinterpret_cast<u64 *>(a.d_ws),
+                     reinterpret_cast<u64 *>(a.d_bucket_counts), reinterpret_cast<u64 *>(a.d_fine_hist), a.fbits, a.nvp, a.pk);
+  return hipGetLastError();
+}
+// what both fine histograms do first: the counts zeroed, the rows (virtual workgroups) shared out (fbits 6: launch_kmer_histogram_fine sets its own)
+static hipError_t kh_prepare(const uint8_t *d_bases, uint64_t n_bases, uint32_t k, int mode, uint32_t bucket_bits, uint64_t *d_bucket_counts,
+                             uint64_t *d_fine_hist, size_t fine_entries, void *d_ws, hipStream_t st, void *d_packed, KhLaunch *a) {
+  MGC_CHECK(hipMemsetAsync(d_bucket_counts, 0, sizeof(uint64_t) << bucket_bits, st));
+  MGC_CHECK(hipMemsetAsync(d_fine_hist, 0, sizeof(uint64_t) * fine_entries, st));
+  const uint32_t vgrid = kp_grid_size(n_bases, bucket_bits);
+  const uint32_t nvp = std::max<uint32_t>((uint32_t)KH_NV, (vgrid + 511u) / 512u);     // <= 512 workgroups (each clears and flushes a 128 KiB table), nvp rows each
+  *a = KhLaunch{d_bases, n_bases, k, mode, (n_bases + KP_TILE - 1) / KP_TILE, vgrid, d_ws, d_bucket_counts, d_fine_hist, 6u, nvp, st,
+                kp_packed(d_packed, n_bases)};
+  return hipSuccess;
+}
+
 // launch_kmer_histogram + d_fine_hist[2^15] (zeroed here): k-mers per (file, next nine bits)
 hipError_t launch_kmer_histogram_fine(const uint8_t *d_bases, uint64_t n_bases, uint32_t k, int mode, uint64_t *d_bucket_counts,
                                       uint64_t *d_fine_hist, void *d_ws, hipStream_t st, bool const_k, uint32_t bucket_bits,
                                       void *d_packed) {
   if (bucket_bits < 6 || bucket_bits > 8) return hipErrorInvalidValue;
-  const PackedBases pk = kp_packed(d_packed, n_bases);
-  MGC_CHECK(hipMemsetAsync(d_bucket_counts, 0, sizeof(uint64_t) << bucket_bits, st));
-  MGC_CHECK(hipMemsetAsync(d_fine_hist, 0, sizeof(uint64_t) << KH_FINE_BITS, st));
+  KhLaunch a;
+  MGC_CHECK(kh_prepare(d_bases, n_bases, k, mode, bucket_bits, d_bucket_counts, d_fine_hist, (size_t)1 << KH_FINE_BITS, d_ws, st, d_packed, &a));
   if (n_bases == 0) return hipSuccess;
-  const uint64_t num_tiles = (n_bases + KP_TILE - 1) / KP_TILE;
-  const uint32_t vgrid = kp_grid_size(n_bases, bucket_bits);
-  const uint32_t nvp = std::max<uint32_t>((uint32_t)KH_NV, (vgrid + 511u) / 512u);     // <= 512 workgroups (each clears and flushes a 128 KiB table), nvp rows each
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kmer_hist_fine_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(sizeof(u32) << KH_FINE_BITS));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kmer_hist_fine_kernel<0, 21>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(sizeof(u32) << KH_FINE_BITS));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kmer_hist_fine_kernel<0, 31>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(sizeof(u32) << KH_FINE_BITS));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kmer_hist_fine_kernel<0, 51>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(sizeof(u32) << KH_FINE_BITS));
-    attr_done = true;
+  a.fbits = bucket_bits;
+  switch (kmer_const_k(k, mode, const_k)) {
+    case 21: return kh_launch_form<0, 21>(a);
+    case 31: return kh_launch_form<0, 31>(a);
+    case 51: return kh_launch_form<0, 51>(a);
+    default: return kh_launch_form<0, 0>(a);
   }
-#define MGC_KH_LAUNCH(KC_)                                                                                                             \
-  hipLaunchKernelGGL((kmer_hist_fine_kernel<0, KC_>), dim3((vgrid + nvp - 1) / nvp), dim3(KP_BLOCK * KH_NV), sizeof(u32) << KH_FINE_BITS, st, \
-                     d_bases, (u64)n_bases, k, mode, (u64)num_tiles, vgrid, reinterpret_cast<u64 *>(d_ws),                             \
-                     reinterpret_cast<u64 *>(d_bucket_counts), reinterpret_cast<u64 *>(d_fine_hist), bucket_bits, nvp, pk)
-  const int kc = kmer_const_k(k, mode, const_k);
-  if (kc == 21) MGC_KH_LAUNCH(21); else if (kc == 31) MGC_KH_LAUNCH(31); else if (kc == 51) MGC_KH_LAUNCH(51); else MGC_KH_LAUNCH(0);
-#undef MGC_KH_LAUNCH
-  return hipGetLastError();
 }
 
 // `compress`: the same kernel with the table indexed by dense ranks (kmer_hist_fine_kernel<HB>): bucket_bits 6 or 8,
@@ -766,44 +778,12 @@ hipError_t launch_kmer_histogram_hpc(const uint8_t *d_bases, uint64_t n_bases, u
                                      uint64_t *d_bucket_counts, uint64_t *d_fine_hist, void *d_ws, hipStream_t st, bool const_k,
                                      void *d_packed) {
   if (bucket_bits != 6 && bucket_bits != 8) return hipErrorInvalidValue;
-  const PackedBases pk = kp_packed(d_packed, n_bases);
-  const uint32_t entries = kmer_histogram_hpc_entries(bucket_bits);
-  MGC_CHECK(hipMemsetAsync(d_bucket_counts, 0, sizeof(uint64_t) << bucket_bits, st));
-  MGC_CHECK(hipMemsetAsync(d_fine_hist, 0, sizeof(uint64_t) * entries, st));
+  KhLaunch a;
+  MGC_CHECK(kh_prepare(d_bases, n_bases, k, mode, bucket_bits, d_bucket_counts, d_fine_hist, kmer_histogram_hpc_entries(bucket_bits), d_ws, st, d_packed, &a));
   if (n_bases == 0) return hipSuccess;
-  const uint64_t num_tiles = (n_bases + KP_TILE - 1) / KP_TILE;
-  const uint32_t vgrid = kp_grid_size(n_bases, bucket_bits);
-  const uint32_t nvp = std::max<uint32_t>((uint32_t)KH_NV, (vgrid + 511u) / 512u);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kmer_hist_fine_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(sizeof(u32) * hpc_table_size(8)));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kmer_hist_fine_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(sizeof(u32) * hpc_table_size(9)));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kmer_hist_fine_kernel<8, 31>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(sizeof(u32) * hpc_table_size(8)));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kmer_hist_fine_kernel<9, 31>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(sizeof(u32) * hpc_table_size(9)));
-    attr_done = true;
-  }
-  const bool k31 = kmer_const_k(k, mode, const_k) == 31;
-  if (k31 && bucket_bits == 6)
-    hipLaunchKernelGGL((kmer_hist_fine_kernel<8, 31>), dim3((vgrid + nvp - 1) / nvp), dim3(KP_BLOCK * KH_NV), sizeof(u32) * entries, st,
-                       d_bases, (u64)n_bases, k, mode, (u64)num_tiles, vgrid, reinterpret_cast<u64 *>(d_ws),
-                       reinterpret_cast<u64 *>(d_bucket_counts), reinterpret_cast<u64 *>(d_fine_hist), 6u, nvp, pk);
-  else if (k31)
-    hipLaunchKernelGGL((kmer_hist_fine_kernel<9, 31>), dim3((vgrid + nvp - 1) / nvp), dim3(KP_BLOCK * KH_NV), sizeof(u32) * entries, st,
-                       d_bases, (u64)n_bases, k, mode, (u64)num_tiles, vgrid, reinterpret_cast<u64 *>(d_ws),
-                       reinterpret_cast<u64 *>(d_bucket_counts), reinterpret_cast<u64 *>(d_fine_hist), 6u, nvp, pk);
-  else if (bucket_bits == 6)
-    hipLaunchKernelGGL(kmer_hist_fine_kernel<8>, dim3((vgrid + nvp - 1) / nvp), dim3(KP_BLOCK * KH_NV), sizeof(u32) * entries, st,
-                       d_bases, (u64)n_bases, k, mode, (u64)num_tiles, vgrid, reinterpret_cast<u64 *>(d_ws),
-                       reinterpret_cast<u64 *>(d_bucket_counts), reinterpret_cast<u64 *>(d_fine_hist), 6u, nvp, pk);
-  else
-    hipLaunchKernelGGL(kmer_hist_fine_kernel<9>, dim3((vgrid + nvp - 1) / nvp), dim3(KP_BLOCK * KH_NV), sizeof(u32) * entries, st,
-                       d_bases, (u64)n_bases, k, mode, (u64)num_tiles, vgrid, reinterpret_cast<u64 *>(d_ws),
-                       reinterpret_cast<u64 *>(d_bucket_counts), reinterpret_cast<u64 *>(d_fine_hist), 6u, nvp, pk);
-  return hipGetLastError();
+  const bool k31 = kmer_const_k(k, mode, const_k) == 31;   // (HB = bucket_bits / 2 + 5)
+  if (bucket_bits == 6) return k31 ? kh_launch_form<8, 31>(a) : kh_launch_form<8, 0>(a);
+  return k31 ? kh_launch_form<9, 31>(a) : kh_launch_form<9, 0>(a);
 }
 
 // One launch of kmer_partition_kernel<K, MAXB, SOA, KC, BB>: its PK form when the count has a packed base stream, the ASCII form

@@ -20,6 +20,7 @@
 // {flag,epoch,value} granules with agent-scope relaxed atomics (no fences needed:
 // the datum is the flag).  Wave = 64 everywhere.
 #include "mgc_common.hpp"
+#include "mgc_group_route.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -929,7 +930,7 @@ static int device_cu_count() {
   return cus;
 }
 
-// digit histograms + exclusive digit bases of a file's grouping passes into `hdr` (tickets zeroed)
+// digit histograms + exclusive digit bases of a file's passes into `hdr` (tickets zeroed)
 template <typename K>
 static hipError_t group_prepare(const K *src, uint64_t n, const SortPlan &plan, SortHeader *hdr, hipStream_t st) {
   MGC_CHECK(hipMemsetAsync(hdr, 0, sizeof(SortHeader), st));
@@ -946,6 +947,26 @@ static hipError_t group_prepare(const K *src, uint64_t n, const SortPlan &plan, 
   return hipGetLastError();
 }
 
+// ---- one launch of radix_group_kernel: what it takes (GroupPass), which instantiation (GroupInst, mgc_group_route.hpp) ----
+struct GroupPass {
+  const void *in; void *out;                 // K keys in; K keys out (a NARROW pass: u32 words)
+  u64 n; u32 shift, mask;
+  const u64 *gbase; u64 *status; u32 *ticket; u32 *d_error;
+  u64 tiles_plain;                           // tiles of n keys without region cuts
+  u64 *region_start; u32 *region_tiles;      // the regions a second pass's tiles are cut at; null on a first pass
+  GroupExtra ex;
+  u64 *dbg;                                  // DBG: where the cycle sums go
+  u64 tile_bound;                            // no tile index reaches this: the grid is min(tile_bound, resident workgroups)
+  hipStream_t st;
+};
+static hipError_t launch_group_pass(const GroupInst &inst, const GroupPass &p);   // (the table, below the tile constants)
+
+template <typename K> constexpr GroupKey group_key_of();
+template <> constexpr GroupKey group_key_of<u64>()  { return GROUP_U64; }
+template <> constexpr GroupKey group_key_of<u32>()  { return GROUP_U32; }
+template <> constexpr GroupKey group_key_of<K128>() { return GROUP_K128; }
+template <> constexpr GroupKey group_key_of<K96>()  { return GROUP_K96; }
+
 // LB 2: packed granules (n < 2^30); LB 3: wide granules
 template <typename K, int KPT, int LB>
 static hipError_t run_passes(void *d_keys, void *d_alt, uint64_t n, const SortPlan &plan, void *d_ws,
@@ -959,6 +980,8 @@ static hipError_t run_passes(void *d_keys, void *d_alt, uint64_t n, const SortPl
 
   K *src = reinterpret_cast<K *>(d_keys), *dst = reinterpret_cast<K *>(d_alt);
   int in_alt = 0;
+  u64 *status = reinterpret_cast<u64 *>(body);
+  MGC_CHECK(group_prepare<K>((const K *)src, n, plan, hdr, st));
 
   if (plan.mode != 3) {
     static bool attr_done = false;
@@ -967,20 +990,7 @@ static hipError_t run_passes(void *d_keys, void *d_alt, uint64_t n, const SortPl
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)SM::BYTES);
       attr_done = true;
     }
-    u64 *status = reinterpret_cast<u64 *>(body);
     const size_t status_bytes = (size_t)num_tiles * (LB == 3 ? R : R / 2) * sizeof(u64);
-    MGC_CHECK(hipMemsetAsync(hdr, 0, sizeof(SortHeader), st));
-    PassList pl;
-    pl.n = plan.num_passes;
-    for (uint32_t p = 0; p < plan.num_passes; p++) {
-      pl.shift[p] = plan.pass_shift[p];
-      pl.mask[p]  = plan_mask(plan, p);
-    }
-    launch_radix_hist<K>((const K *)src, (u64)n, pl, &hdr->ghist[0][0], st);
-    MGC_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(radix_digit_scan_kernel, dim3(plan.num_passes), dim3(RS_MAX_RADIX), 0, st,
-                       &hdr->ghist[0][0], &hdr->gbase[0][0]);
-    MGC_CHECK(hipGetLastError());
     for (uint32_t p = 0; p < plan.num_passes; p++) {
       MGC_CHECK(hipMemsetAsync(status, 0, status_bytes, st));
       if (pass_events) MGC_CHECK(hipEventRecord(pass_events[2 * p], st));
@@ -993,20 +1003,12 @@ static hipError_t run_passes(void *d_keys, void *d_alt, uint64_t n, const SortPl
     }
   } else {
     // ---- grouping passes (finish path): see radix_group_kernel ----
-    using GS = GroupSmem<K, RB, BLOCK, KPT>;
-    static bool gattr_done = false;
-    if (!gattr_done) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<K, RB, BLOCK, KPT, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS::BYTES);
-      gattr_done = true;
-    }
+    constexpr GroupInst inst = group_pick_sorted(group_key_of<K>());
+    static_assert(group_tile(inst) == (uint64_t)TILE, "the sort's tile");
     const uint64_t max_tiles = num_tiles + RS_MAX_RADIX + 1;          // region-aligned tiles: one partial tile per region
-    u64 *status = reinterpret_cast<u64 *>(body);
     const size_t status_bytes = (size_t)max_tiles * (R / 2) * sizeof(u64);
     u64 *region_start = reinterpret_cast<u64 *>(body + ((status_bytes + 255) / 256) * 256);
     u32 *region_tiles = reinterpret_cast<u32 *>(region_start + RS_MAX_RADIX + 1);
-    MGC_CHECK(group_prepare<K>((const K *)src, n, plan, hdr, st));
-    const uint64_t resident = (uint64_t)device_cu_count() * GS::WG_PER_CU;
     for (uint32_t p = 0; p < plan.num_passes; p++) {
       if (p == 1) {
         hipLaunchKernelGGL(group_regions_kernel, dim3(1), dim3(RS_MAX_RADIX), 0, st, &hdr->gbase[0][0], (u64)n, (u32)TILE,
@@ -1015,14 +1017,10 @@ static hipError_t run_passes(void *d_keys, void *d_alt, uint64_t n, const SortPl
       }
       MGC_CHECK(hipMemsetAsync(status, 0, status_bytes, st));
       if (pass_events) MGC_CHECK(hipEventRecord(pass_events[2 * p], st));
-      const uint64_t tiles_bound = (p == 0) ? num_tiles : max_tiles;
-      const uint32_t pgrid = (uint32_t)(tiles_bound < resident ? tiles_bound : resident);
-      const u64 *rs = (p == 0) ? nullptr : region_start;
-      const u32 *rt = (p == 0) ? nullptr : region_tiles;
-      hipLaunchKernelGGL((radix_group_kernel<K, RB, BLOCK, KPT, false>), dim3(pgrid), dim3(BLOCK), GS::BYTES, st,
-                         (const K *)src, dst, (u64)n, plan.pass_shift[p], plan_mask(plan, p),
-                         &hdr->gbase[p][0], status, &hdr->ticket[p], d_error, (u64)num_tiles, rs, rt, GroupExtra{0u, 0u, 0u, nullptr}, (u64 *)nullptr);
-      MGC_CHECK(hipGetLastError());
+      const GroupPass gp{src, dst, (u64)n, plan.pass_shift[p], plan_mask(plan, p), &hdr->gbase[p][0], status, &hdr->ticket[p], d_error,
+                         (u64)num_tiles, p ? region_start : nullptr, p ? region_tiles : nullptr, GroupExtra{0u, 0u, 0u, nullptr}, nullptr,
+                         (u64)(p ? max_tiles : num_tiles), st};
+      MGC_CHECK(launch_group_pass(inst, gp));
       if (pass_events) MGC_CHECK(hipEventRecord(pass_events[2 * p + 1], st));
       K *t = src; src = dst; dst = t; in_alt ^= 1;
     }
@@ -1138,210 +1136,170 @@ hipError_t launch_narrow_prepare(const uint64_t *d_fine, uint32_t nb, const unsi
   return hipGetLastError();
 }
 
-// d_keys: u64[n] in; u32[n] out over its first half (grouped by the plan's two digits, each key without the digit of the
-// FIRST pass, truncated to 32 bits).  d_alt: room for n u32.  d_sub_starts: 2^(b0+b1) + 1, in PHYSICAL order.
-// d_prepared == nullptr: the low digit first (LSD; one read of the keys for both digit histograms, scratch = d_ws); physical
-// order = key order.
-// d_prepared (this file's header from launch_narrow_prepare, i.e. the histogram of its HIGH digit taken from the fifteen-bit
-// file histogram) + d_scratch (narrow_scratch_bytes(n), its status part zeroed by the caller): the high digit goes first, the
-// low digit's histogram is taken by the first pass itself -- nobody reads the keys for a histogram -- and the physical order
-// is (low digit : high digit): sub-bucket p holds the k-mers whose top bits are
-// ((p & (2^*tr_a - 1)) << *tr_b) | (p >> *tr_a)  (*tr_a = 0: p itself).
-hipError_t launch_group_narrow(void *d_keys, void *d_alt, uint64_t n, const SortPlan &plan, void *d_ws, size_t ws_bytes,
-                               uint32_t *d_error, uint64_t *d_sub_starts, hipStream_t st, hipEvent_t *pass_events,
-                               void *d_prepared, void *d_scratch, uint32_t *tr_a, uint32_t *tr_b, uint32_t soa_hi_mask, bool group_dbg, bool pipe, uint32_t stagger) {
-  if (!sort_plan_narrows(plan, n, 1) || ws_bytes < sort_workspace_bytes(n)) return hipErrorInvalidValue;
-  constexpr int RB = 9, BLOCK = 1024, KPT0 = 16, KPT0P = MGC_NARROW_KPT0, KPT1 = 24, R = 1 << RB;
-  using GS0  = GroupSmem<u64, RB, BLOCK, KPT0, group_xb<u64, RB, true>()>;
-  using GS0P = GroupSmem<u64, RB, BLOCK, KPT0P, group_xb<u64, RB, true>()>;  // (words + 16-bit digits: 144 + 10 KiB at 24576 keys)
-  static_assert(GS0P::BYTES + RS_MAX_RADIX * 4 <= 160 * 1024 && GS0P::WG_PER_CU == 1 && GS0::WG_PER_CU == 1, "the first pass's tile and its low-digit counters fit the LDS");
-  using GS1 = GroupSmem<u32, RB, BLOCK, KPT1>;
-  constexpr uint64_t TILE1 = (uint64_t)BLOCK * KPT1;
-  static_assert((uint64_t)BLOCK * KPT0 == NARROW_TILE0 && (uint64_t)BLOCK * KPT0P == NARROW_TILE0P && TILE1 == NARROW_TILE1, "narrow_scratch_bytes");
-  const bool msd = d_prepared != nullptr && d_scratch != nullptr;
-  const uint64_t TILE0 = (msd && soa_hi_mask && pipe) ? NARROW_TILE0P : NARROW_TILE0;   // (the pipelined forms, instrumented or not)
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, RB, BLOCK, KPT0, false, true, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS0::BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, RB, BLOCK, KPT0, false, true, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS0::BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u32, RB, BLOCK, KPT1, false, false, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS1::BYTES);
-    attr_done = true;
-  }
-  const uint64_t tile1 = TILE1;    // (28 words per thread -- 28672-word tiles, the most the register file takes -- measured equal: r06_ab_runs.txt)
-  const uint64_t tiles0 = (n + TILE0 - 1) / TILE0, tiles1_max = (n + tile1 - 1) / tile1 + RS_MAX_RADIX + 1;
-  SortHeader *hdr;
-  u64 *status_a, *status_b, *region_start;
+// ---- the launcher and the table ----
+// One instantiation: the dynamic-LDS limit raised once (the tile, plus the rank table where HPCD), the persistent grid of its own
+// WG_PER_CU -- 1 for every row of the table, asserted below -- and the launch.
+template <typename K, int RB, int KPT, bool DBG, bool NARROW, bool HIST2, bool SOA, int PIPE, int HPCD>
+static hipError_t group_launch_form(const GroupPass &p) {
+  constexpr int BLOCK = GROUP_BLOCK;
+  using SM = GroupSmem<K, RB, BLOCK, KPT, group_xb<K, RB, NARROW>()>;
+  constexpr size_t LDS = SM::BYTES + (HPCD ? GROUP_RANK_TABLE_BYTES : 0);
+  static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<K, RB, BLOCK, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
+  (void)raised;
+  const u64 resident = (u64)device_cu_count() * SM::WG_PER_CU;
+  hipLaunchKernelGGL((radix_group_kernel<K, RB, BLOCK, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD>), dim3((uint32_t)std::min(p.tile_bound, resident)),
+                     dim3(BLOCK), LDS, p.st, reinterpret_cast<const K *>(p.in), reinterpret_cast<typename GroupOut<K, NARROW>::type *>(p.out),
+                     p.n, p.shift, p.mask, p.gbase, p.status, p.ticket, p.d_error, p.tiles_plain, (const u64 *)p.region_start,
+                     (const u32 *)p.region_tiles, p.ex, p.dbg);
+  return hipGetLastError();
+}
+
+// Every instantiation of radix_group_kernel the library holds: K, RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD (the rules that
+// pick among them: mgc_group_route.hpp; pinned by tests/test_group_route_host.py)
+#define MGC_GROUP_INSTS(X)                                                                                                     \
+  /* a narrowed file's first pass: low digit first; high digit first off whole keys / the 5-byte layout / that a tile ahead */ \
+  X(u64, 9, 16, false, true, false, false, 0, 0)                                                                               \
+  X(u64, 9, 16, false, true, true, false, 0, 0)                                                                                \
+  X(u64, 9, 16, false, true, true, true, 0, 0)                                                                                 \
+  X(u64, 9, MGC_NARROW_KPT0, false, true, true, true, 2, 0)                                                                    \
+  X(u64, 8, MGC_NARROW_KPT0, false, true, true, true, 2, 0)                                                                    \
+  X(u64, 9, 16, true, true, true, false, 0, 0)                                                                                 \
+  X(u64, 9, 16, true, true, true, true, 0, 0)                                                                                  \
+  X(u64, 9, MGC_NARROW_KPT0, true, true, true, true, 2, 0)                                                                     \
+  /* its second pass */                                                                                                        \
+  X(u32, 9, 24, false, false, false, false, 0, 0)                                                                              \
+  X(u32, 8, 24, false, false, false, false, 0, 0)                                                                              \
+  X(u32, 9, 24, true, false, false, false, 0, 0)                                                                               \
+  /* whole keys: first (HIST2) and second pass, nine- and eight-bit digits (the nine-bit second passes: launch_radix_sort too) */ \
+  X(u64, 9, 16, false, false, true, false, 0, 0)                                                                               \
+  X(u64, 9, 16, false, false, false, false, 0, 0)                                                                              \
+  X(u64, 8, 16, false, false, true, false, 0, 0)                                                                               \
+  X(u64, 8, 16, false, false, false, false, 0, 0)                                                                              \
+  X(K128, 9, 8, false, false, true, false, 0, 0)                                                                               \
+  X(K128, 9, 8, false, false, false, false, 0, 0)                                                                              \
+  X(K128, 8, 8, false, false, true, false, 0, 0)                                                                               \
+  X(K128, 8, 8, false, false, false, false, 0, 0)                                                                              \
+  X(K96, 9, 12, false, false, true, false, 0, 0)                                                                               \
+  X(K96, 9, 12, false, false, false, false, 0, 0)                                                                              \
+  X(K96, 8, 12, false, false, true, false, 0, 0)                                                                               \
+  X(K96, 8, 12, false, false, false, false, 0, 0)                                                                              \
+  /* `compress`: both digits dense ranks (first, second pass); only the high one (first pass) */                              \
+  X(u64, 9, 16, false, false, true, false, 0, 1)                                                                               \
+  X(u64, 9, 16, false, false, false, false, 0, 1)                                                                              \
+  X(u64, 9, 16, false, false, true, false, 0, 2)                                                                               \
+  X(K128, 9, 8, false, false, true, false, 0, 1)                                                                               \
+  X(K128, 9, 8, false, false, false, false, 0, 1)                                                                              \
+  X(K128, 9, 8, false, false, true, false, 0, 2)
+
+// every row: one workgroup per CU (so "the instantiation's own WG_PER_CU" is the grid every launch had), and the LDS bytes the
+// picking functions reckon with (the rank table only where it fits) are the kernel's
+#define MGC_GROUP_ROW_OK(K, RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD)                                                      \
+  static_assert(GroupSmem<K, RB, GROUP_BLOCK, KPT, group_xb<K, RB, NARROW>()>::WG_PER_CU == 1, "one workgroup per CU");        \
+  static_assert(GroupSmem<K, RB, GROUP_BLOCK, KPT, group_xb<K, RB, NARROW>()>::BYTES + (HPCD ? GROUP_RANK_TABLE_BYTES : 0) ==  \
+                group_lds_bytes(GroupInst{group_key_of<K>(), RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD}), "group_lds_bytes"); \
+  static_assert(group_lds_bytes(GroupInst{group_key_of<K>(), RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD}) + (HIST2 ? RS_MAX_RADIX * 4 : 0) <= GROUP_LDS_MAX, \
+                "the tile, the rank table and the other digit's counters fit the LDS");
+MGC_GROUP_INSTS(MGC_GROUP_ROW_OK)
+#undef MGC_GROUP_ROW_OK
+
+// an instantiation that is not in the table is an error, never a neighbouring kernel
+static hipError_t launch_group_pass(const GroupInst &inst, const GroupPass &p) {
+#define MGC_GROUP_ROW(K, RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD)                                                         \
+  if (inst == GroupInst{group_key_of<K>(), RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD})                                      \
+    return group_launch_form<K, RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD>(p);
+  MGC_GROUP_INSTS(MGC_GROUP_ROW)
+#undef MGC_GROUP_ROW
+  return hipErrorInvalidValue;
+}
+
+// What the two-pass forms share once the first pass is launched (p: the second pass): the second digit's bases and the region table
+// -- high digit first (msd): one kernel, off the histogram the first pass took; low digit first: the regions alone, and the shared
+// look-back rows cleared again -- then the second pass and the sub-bucket boundaries off its look-back granules.
+static hipError_t group_second_pass(const GroupInst &inst, const GroupPass &p, SortHeader *hdr, bool msd, u32 bits_first, u32 bits_second,
+                                    uint64_t *d_sub_starts, hipEvent_t *pass_events) {
+  if (pass_events) MGC_CHECK(hipEventRecord(pass_events[1], p.st));
   if (msd) {
-    hdr = reinterpret_cast<SortHeader *>(d_prepared);
-    status_a = reinterpret_cast<u64 *>(d_scratch);
-    status_b = status_a + (size_t)tiles0 * (R / 2);
-    region_start = status_b + (size_t)tiles1_max * (R / 2);
+    hipLaunchKernelGGL(narrow_mid_kernel, dim3(1), dim3(RS_MAX_RADIX), 0, p.st, hdr, p.n, (u32)group_tile(inst), p.region_start, p.region_tiles);
+    MGC_CHECK(hipGetLastError());
   } else {
-    hdr = reinterpret_cast<SortHeader *>(d_ws);
-    unsigned char *body = reinterpret_cast<unsigned char *>(d_ws) + ((sizeof(SortHeader) + 255) / 256) * 256;
-    status_a = status_b = reinterpret_cast<u64 *>(body);
-    const size_t status_bytes = (size_t)std::max(tiles0, tiles1_max) * (R / 2) * sizeof(u64);
-    region_start = reinterpret_cast<u64 *>(body + ((status_bytes + 255) / 256) * 256);
+    hipLaunchKernelGGL(group_regions_kernel, dim3(1), dim3(RS_MAX_RADIX), 0, p.st, &hdr->gbase[0][0], p.n, (u32)group_tile(inst), p.region_start, p.region_tiles);
+    MGC_CHECK(hipGetLastError());
+    MGC_CHECK(hipMemsetAsync(p.status, 0, (size_t)p.tile_bound * (RS_MAX_RADIX / 2) * sizeof(u64), p.st));
   }
-  u32 *region_tiles = reinterpret_cast<u32 *>(region_start + RS_MAX_RADIX + 1);
+  if (pass_events) MGC_CHECK(hipEventRecord(pass_events[2], p.st));
+  MGC_CHECK(launch_group_pass(inst, p));
+  if (pass_events) MGC_CHECK(hipEventRecord(pass_events[3], p.st));
+  const u64 ng = (u64)1 << (bits_first + bits_second);
+  hipLaunchKernelGGL(narrow_bounds_kernel, dim3((uint32_t)((ng + 1 + 255) / 256)), dim3(256), 0, p.st, p.status, p.region_tiles,
+                     p.gbase, p.n, bits_first, ng, reinterpret_cast<u64 *>(d_sub_starts), group_granules(inst));
+  return hipGetLastError();
+}
+
+// mgc_device.h, GroupFile.  Low digit first: one read of the keys for both digit histograms, scratch = f.ws, physical order = key
+// order.  High digit first: the histogram of the HIGH digit comes with the prepared header, the low digit's is taken by the first
+// pass itself -- nobody reads the keys for a histogram -- and the physical order is (low digit : high digit).
+hipError_t launch_group_narrow(GroupFile &f) {
+  static_assert(MGC_NARROW_KPT0 == GROUP_KPT_NARROW0P, "mgc_group_route.hpp");
+  static_assert((uint64_t)GROUP_BLOCK * GROUP_KPT_NARROW0 == NARROW_TILE0 && (uint64_t)GROUP_BLOCK * GROUP_KPT_NARROW0P == NARROW_TILE0P &&
+                (uint64_t)GROUP_BLOCK * GROUP_KPT_NARROW1 == NARROW_TILE1, "narrow_scratch_bytes");
+  const bool soa = f.layout == GroupKeys::SOA5, msd = f.prepared != nullptr && f.scratch != nullptr;
+  bool dbg = f.dbg && msd;
+  GroupInst i0, i1;
+  if ((f.layout != GroupKeys::U64 && !soa) || soa != (f.soa_hi_mask != 0) || !f.plan || !sort_plan_narrows(*f.plan, f.n, 1) ||
+      f.ws_bytes < sort_workspace_bytes(f.n))
+    return hipErrorInvalidValue;
+  const SortPlan &plan = *f.plan;
+  const uint64_t n = f.n;
   const u32 low = plan.pass_shift[0], b_lo = plan.pass_bits[0], b_hi = plan.pass_bits[1];
   // first pass: digit A at shA (bA bits), dropped from the keys; second pass: digit B -- after the drop it sits at `low`
   const u32 bA = msd ? b_hi : b_lo, bB = msd ? b_lo : b_hi, shA = msd ? low + b_lo : low;
-  *tr_a = msd ? bA : 0u; *tr_b = bB;
-  const uint64_t cus = (uint64_t)device_cu_count();
-
-  if (!msd) {
-    MGC_CHECK(group_prepare<u64>(reinterpret_cast<const u64 *>(d_keys), n, plan, hdr, st));   // rows 0 / 1 = low / high digit = A / B
-    MGC_CHECK(hipMemsetAsync(status_a, 0, (size_t)tiles0 * (R / 2) * sizeof(u64), st));
-  }
-  if (pass_events) MGC_CHECK(hipEventRecord(pass_events[0], st));
-  const dim3 grid0((uint32_t)std::min(tiles0, cus * GS0::WG_PER_CU));
-  // MGC_GROUP_DBG=1: per-phase cycle sums of the first 64 workgroups of both passes, printed for the first two files (developer
-  // instrumentation; the instrumented instantiations run instead of the plain ones for those files)
-  static int dbg_reports = 2;
+  if (!group_pick_narrow(msd, soa, f.pipe, dbg, bA, bB, &i0, &i1)) return hipErrorInvalidValue;   // the 5-byte layout: high digit first
+  // f.dbg: per-phase cycle sums of the first 64 workgroups of both passes, printed (developer instrumentation; the instrumented
+  // instantiations run instead of the plain ones)
   static u64 *dbg_buf = nullptr;
-  const bool dbg = group_dbg && msd && dbg_reports > 0;
-  if (dbg && !dbg_buf) {
-    static bool dattr = false;
-    if (!dattr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, RB, BLOCK, KPT0, true, true, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS0::BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u32, RB, BLOCK, KPT1, true, false, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS1::BYTES);
-      dattr = true;
-    }
-    if (hipMalloc(&dbg_buf, 2 * 64 * 8 * sizeof(u64)) != hipSuccess) dbg_buf = nullptr;
+  if (dbg && !dbg_buf && hipMalloc(&dbg_buf, 2 * 64 * 8 * sizeof(u64)) != hipSuccess) {
+    dbg_buf = nullptr; dbg = false;
+    group_pick_narrow(msd, soa, f.pipe, false, bA, bB, &i0, &i1);
   }
-  if (dbg && dbg_buf) MGC_CHECK(hipMemsetAsync(dbg_buf, 0, 2 * 64 * 8 * sizeof(u64), st));
-  if (soa_hi_mask && !msd) return hipErrorInvalidValue;   // the 5-byte layout: high digit first
-  GroupExtra ex_first{bA, low, (1u << bB) - 1u, &hdr->ghist[1][0], soa_hi_mask};
-  if (stagger > 1u && soa_hi_mask && pipe) { ex_first.stagger_groups = stagger; ex_first.stagger_cycles = NARROW_TILE0_CYCLES / stagger; }
-  const GroupExtra ex_second{0u, 0u, 0u, nullptr};
-  if (dbg && dbg_buf && soa_hi_mask) {                     // the shipped first pass, instrumented: 5-byte layout, the fetch a whole tile ahead (or not)
-    static bool dsattr = false;
-    if (!dsattr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, RB, BLOCK, KPT0P, true, true, true, true, 2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS0P::BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, RB, BLOCK, KPT0, true, true, true, true, 0>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS0::BYTES);
-      dsattr = true;
-    }
-    if (pipe)
-      hipLaunchKernelGGL((radix_group_kernel<u64, RB, BLOCK, KPT0P, true, true, true, true, 2>), grid0, dim3(BLOCK), GS0P::BYTES, st,
-                         reinterpret_cast<const u64 *>(d_keys), reinterpret_cast<u32 *>(d_alt), (u64)n, shA, (1u << bA) - 1u,
-                         &hdr->gbase[0][0], status_a, &hdr->ticket[0], d_error, (u64)tiles0, (const u64 *)nullptr, (const u32 *)nullptr,
-                         ex_first, dbg_buf);
-    else
-      hipLaunchKernelGGL((radix_group_kernel<u64, RB, BLOCK, KPT0, true, true, true, true, 0>), grid0, dim3(BLOCK), GS0::BYTES, st,
-                         reinterpret_cast<const u64 *>(d_keys), reinterpret_cast<u32 *>(d_alt), (u64)n, shA, (1u << bA) - 1u,
-                         &hdr->gbase[0][0], status_a, &hdr->ticket[0], d_error, (u64)tiles0, (const u64 *)nullptr, (const u32 *)nullptr,
-                         ex_first, dbg_buf);
-  }
-  else if (dbg && dbg_buf)
-    hipLaunchKernelGGL((radix_group_kernel<u64, RB, BLOCK, KPT0, true, true, true>), grid0, dim3(BLOCK), GS0::BYTES, st,
-                       reinterpret_cast<const u64 *>(d_keys), reinterpret_cast<u32 *>(d_alt), (u64)n, shA, (1u << bA) - 1u,
-                       &hdr->gbase[0][0], status_a, &hdr->ticket[0], d_error, (u64)tiles0, (const u64 *)nullptr, (const u32 *)nullptr,
-                       GroupExtra{bA, low, (1u << bB) - 1u, &hdr->ghist[1][0]}, dbg_buf);
-  else if (msd && soa_hi_mask) {
-    static bool sattr = false;
-    if (!sattr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, RB, BLOCK, KPT0, false, true, true, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS0::BYTES);
-      sattr = true;
-    }
-    static bool spattr = false;
-    if (pipe && !spattr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, RB, BLOCK, KPT0P, false, true, true, true, 2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS0P::BYTES);
-      spattr = true;
-    }
-    if (pipe && bA <= 8u) {
-      // an eight-bit first digit (the plan of the judged files): 256 counters, 128 walkers and look-back rows of 128 granules instead of
-      // 512 / 256 / 256 -- half the status traffic, two more waves for the low digit's count
-      using GS08 = GroupSmem<u64, 8, BLOCK, KPT0P, group_xb<u64, 8, true>()>;
-      static bool r8attr = false;
-      if (!r8attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u64, 8, BLOCK, KPT0P, false, true, true, true, 2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS08::BYTES);
-        r8attr = true;
-      }
-      hipLaunchKernelGGL((radix_group_kernel<u64, 8, BLOCK, KPT0P, false, true, true, true, 2>), grid0, dim3(BLOCK), GS08::BYTES, st,
-                         reinterpret_cast<const u64 *>(d_keys), reinterpret_cast<u32 *>(d_alt), (u64)n, shA, (1u << bA) - 1u,
-                         &hdr->gbase[0][0], status_a, &hdr->ticket[0], d_error, (u64)tiles0, (const u64 *)nullptr, (const u32 *)nullptr,
-                         ex_first, (u64 *)nullptr);
-    }
-    else if (pipe)
-      hipLaunchKernelGGL((radix_group_kernel<u64, RB, BLOCK, KPT0P, false, true, true, true, 2>), grid0, dim3(BLOCK), GS0P::BYTES, st,
-                         reinterpret_cast<const u64 *>(d_keys), reinterpret_cast<u32 *>(d_alt), (u64)n, shA, (1u << bA) - 1u,
-                         &hdr->gbase[0][0], status_a, &hdr->ticket[0], d_error, (u64)tiles0, (const u64 *)nullptr, (const u32 *)nullptr,
-                         ex_first, (u64 *)nullptr);
-    else
-    hipLaunchKernelGGL((radix_group_kernel<u64, RB, BLOCK, KPT0, false, true, true, true>), grid0, dim3(BLOCK), GS0::BYTES, st,
-                       reinterpret_cast<const u64 *>(d_keys), reinterpret_cast<u32 *>(d_alt), (u64)n, shA, (1u << bA) - 1u,
-                       &hdr->gbase[0][0], status_a, &hdr->ticket[0], d_error, (u64)tiles0, (const u64 *)nullptr, (const u32 *)nullptr,
-                       ex_first, (u64 *)nullptr);
-  }
-  else if (msd)
-    hipLaunchKernelGGL((radix_group_kernel<u64, RB, BLOCK, KPT0, false, true, true>), grid0, dim3(BLOCK), GS0::BYTES, st,
-                       reinterpret_cast<const u64 *>(d_keys), reinterpret_cast<u32 *>(d_alt), (u64)n, shA, (1u << bA) - 1u,
-                       &hdr->gbase[0][0], status_a, &hdr->ticket[0], d_error, (u64)tiles0, (const u64 *)nullptr, (const u32 *)nullptr,
-                       GroupExtra{bA, low, (1u << bB) - 1u, &hdr->ghist[1][0]}, (u64 *)nullptr);
-  else
-    hipLaunchKernelGGL((radix_group_kernel<u64, RB, BLOCK, KPT0, false, true, false>), grid0, dim3(BLOCK), GS0::BYTES, st,
-                       reinterpret_cast<const u64 *>(d_keys), reinterpret_cast<u32 *>(d_alt), (u64)n, shA, (1u << bA) - 1u,
-                       &hdr->gbase[0][0], status_a, &hdr->ticket[0], d_error, (u64)tiles0, (const u64 *)nullptr, (const u32 *)nullptr,
-                       GroupExtra{bA, 0u, 0u, nullptr}, (u64 *)nullptr);
-  MGC_CHECK(hipGetLastError());
-  if (pass_events) MGC_CHECK(hipEventRecord(pass_events[1], st));
-
+  const uint64_t tile0 = group_tile(i0), tile1 = group_tile(i1);    // (28 words per thread in the second pass -- the most the register file takes -- measured equal: r06_ab_runs.txt)
+  const uint64_t tiles0 = (n + tile0 - 1) / tile0, tiles1_max = (n + tile1 - 1) / tile1 + RS_MAX_RADIX + 1;
+  constexpr size_t ROW = RS_MAX_RADIX / 2;                           // granules of a status row, whatever the instantiation uses of it
+  SortHeader *hdr;
+  u64 *status_a, *status_b, *region_start;
   if (msd) {
-    hipLaunchKernelGGL(narrow_mid_kernel, dim3(1), dim3(RS_MAX_RADIX), 0, st, hdr, (u64)n, (u32)tile1, region_start, region_tiles);
-    MGC_CHECK(hipGetLastError());
+    hdr = reinterpret_cast<SortHeader *>(f.prepared);
+    status_a = reinterpret_cast<u64 *>(f.scratch);
+    status_b = status_a + (size_t)tiles0 * ROW;
+    region_start = status_b + (size_t)tiles1_max * ROW;
   } else {
-    hipLaunchKernelGGL(group_regions_kernel, dim3(1), dim3(RS_MAX_RADIX), 0, st, &hdr->gbase[0][0], (u64)n, (u32)TILE1, region_start, region_tiles);
-    MGC_CHECK(hipGetLastError());
-    MGC_CHECK(hipMemsetAsync(status_b, 0, (size_t)tiles1_max * (R / 2) * sizeof(u64), st));
+    hdr = reinterpret_cast<SortHeader *>(f.ws);
+    unsigned char *body = reinterpret_cast<unsigned char *>(f.ws) + ((sizeof(SortHeader) + 255) / 256) * 256;
+    status_a = status_b = reinterpret_cast<u64 *>(body);
+    const size_t status_bytes = (size_t)std::max(tiles0, tiles1_max) * ROW * sizeof(u64);
+    region_start = reinterpret_cast<u64 *>(body + ((status_bytes + 255) / 256) * 256);
   }
-  if (pass_events) MGC_CHECK(hipEventRecord(pass_events[2], st));
-  u32 granules1 = (u32)(R / 2);                             // granules per tile of the second pass's status rows (narrow_bounds_kernel)
-  if (dbg && dbg_buf)
-    hipLaunchKernelGGL((radix_group_kernel<u32, RB, BLOCK, KPT1, true, false, false>), dim3((uint32_t)std::min(tiles1_max, cus * GS1::WG_PER_CU)), dim3(BLOCK),
-                       GS1::BYTES, st, reinterpret_cast<const u32 *>(d_alt), reinterpret_cast<u32 *>(d_keys), (u64)n, low, (1u << bB) - 1u,
-                       &hdr->gbase[1][0], status_b, &hdr->ticket[1], d_error, (u64)((n + TILE1 - 1) / TILE1), region_start, region_tiles,
-                       ex_second, dbg_buf + 64 * 8);
-  else if (bB <= 8u) {                                      // an eight-bit digit: half the counters, walkers and granules (as in the first pass)
-    using GS18 = GroupSmem<u32, 8, BLOCK, KPT1>;
-    static bool r8attr1 = false;
-    if (!r8attr1) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<u32, 8, BLOCK, KPT1, false, false, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS18::BYTES);
-      r8attr1 = true;
-    }
-    granules1 = 128u;
-    hipLaunchKernelGGL((radix_group_kernel<u32, 8, BLOCK, KPT1, false, false, false>), dim3((uint32_t)std::min(tiles1_max, cus * GS18::WG_PER_CU)), dim3(BLOCK),
-                       GS18::BYTES, st, reinterpret_cast<const u32 *>(d_alt), reinterpret_cast<u32 *>(d_keys), (u64)n, low, (1u << bB) - 1u,
-                       &hdr->gbase[1][0], status_b, &hdr->ticket[1], d_error, (u64)((n + TILE1 - 1) / TILE1), region_start, region_tiles,
-                       ex_second, (u64 *)nullptr);
-  }
-  else
-  hipLaunchKernelGGL((radix_group_kernel<u32, RB, BLOCK, KPT1, false, false, false>), dim3((uint32_t)std::min(tiles1_max, cus * GS1::WG_PER_CU)), dim3(BLOCK),
-                     GS1::BYTES, st, reinterpret_cast<const u32 *>(d_alt), reinterpret_cast<u32 *>(d_keys), (u64)n, low, (1u << bB) - 1u,
-                     &hdr->gbase[1][0], status_b, &hdr->ticket[1], d_error, (u64)((n + TILE1 - 1) / TILE1), region_start, region_tiles,
-                     ex_second, (u64 *)nullptr);
-  MGC_CHECK(hipGetLastError());
-  if (pass_events) MGC_CHECK(hipEventRecord(pass_events[3], st));
+  u32 *region_tiles = reinterpret_cast<u32 *>(region_start + RS_MAX_RADIX + 1);
+  f.tr_a = msd ? bA : 0u; f.tr_b = bB;
 
-  const u64 ng = (u64)1 << (bA + bB);
-  hipLaunchKernelGGL(narrow_bounds_kernel, dim3((uint32_t)((ng + 1 + 255) / 256)), dim3(256), 0, st, status_b, region_tiles,
-                     &hdr->gbase[1][0], (u64)n, bA, ng, reinterpret_cast<u64 *>(d_sub_starts), granules1);
-  MGC_CHECK(hipGetLastError());
-  if (dbg && dbg_buf) {
-    dbg_reports--;
+  GroupExtra ex_first{bA, 0u, 0u, nullptr};
+  if (msd) ex_first = GroupExtra{bA, low, (1u << bB) - 1u, &hdr->ghist[1][0], f.soa_hi_mask};
+  if (f.stagger > 1u && soa && f.pipe) { ex_first.stagger_groups = f.stagger; ex_first.stagger_cycles = NARROW_TILE0_CYCLES / f.stagger; }
+  const GroupPass p0{f.keys, f.alt, (u64)n, shA, (1u << bA) - 1u, &hdr->gbase[0][0], status_a, &hdr->ticket[0], f.d_error, (u64)tiles0,
+                     nullptr, nullptr, ex_first, dbg ? dbg_buf : nullptr, (u64)tiles0, f.st};
+  const GroupPass p1{f.alt, f.keys, (u64)n, low, (1u << bB) - 1u, &hdr->gbase[1][0], status_b, &hdr->ticket[1], f.d_error, (u64)((n + tile1 - 1) / tile1),
+                     region_start, region_tiles, GroupExtra{0u, 0u, 0u, nullptr}, dbg ? dbg_buf + 64 * 8 : nullptr, (u64)tiles1_max, f.st};
+  if (!msd) {
+    MGC_CHECK(group_prepare<u64>(reinterpret_cast<const u64 *>(f.keys), n, plan, hdr, f.st));   // rows 0 / 1 = low / high digit = A / B
+    MGC_CHECK(hipMemsetAsync(status_a, 0, (size_t)tiles0 * ROW * sizeof(u64), f.st));
+  }
+  if (f.pass_events) MGC_CHECK(hipEventRecord(f.pass_events[0], f.st));
+  if (dbg) MGC_CHECK(hipMemsetAsync(dbg_buf, 0, 2 * 64 * 8 * sizeof(u64), f.st));
+  MGC_CHECK(launch_group_pass(i0, p0));
+  MGC_CHECK(group_second_pass(i1, p1, hdr, msd, bA, bB, f.d_sub_starts, f.pass_events));
+  if (dbg) {
     u64 h[2 * 64 * 8];
-    MGC_CHECK(hipStreamSynchronize(st));
+    MGC_CHECK(hipStreamSynchronize(f.st));
     MGC_CHECK(hipMemcpy(h, dbg_buf, sizeof(h), hipMemcpyDeviceToHost));
     for (int pass = 0; pass < 2; pass++) {
       double ps[8] = {0};
@@ -1349,7 +1307,7 @@ hipError_t launch_group_narrow(void *d_keys, void *d_alt, uint64_t n, const Sort
       const double it = ps[7] > 0 ? ps[7] : 1;
       fprintf(stderr, "[groupdbg] %s pass, %llu keys, %d-key tiles, tiles/wg=%.1f cycles/tile: ticket+zero=%.0f rank=%.0f scan+exchange=%.0f "
                       "lookback(+prefetch%s)=%.0f writeout=%.0f endsync=%.0f total=%.0f\n",
-              pass ? "second (u32 -> u32)" : (soa_hi_mask ? (pipe ? "first (5 B -> u32, fetch a tile ahead)" : "first (5 B -> u32)") : "first (u64 -> u32)"), (unsigned long long)n, pass ? (int)TILE1 : (int)TILE0, it / 64,
+              pass ? "second (u32 -> u32)" : (soa ? (f.pipe ? "first (5 B -> u32, fetch a tile ahead)" : "first (5 B -> u32)") : "first (u64 -> u32)"), (unsigned long long)n, pass ? (int)tile1 : (int)tile0, it / 64,
               ps[0] / it, ps[1] / it, ps[2] / it, pass ? "" : ", low-digit count", ps[3] / it, ps[4] / it, ps[5] / it,
               (ps[0] + ps[1] + ps[2] + ps[3] + ps[4] + ps[5]) / it);
     }
@@ -1395,7 +1353,7 @@ hipError_t launch_hpc_prepare(const uint64_t *d_fine_hpc, uint32_t bucket_bits, 
 }
 
 // (the look-back scratch is sized for the SMALLEST tile of any whole-key instantiation of a key width: K128 8192 keys, K96 12288 --
-// group_wide asserts that its tile is not smaller)
+// launch_group_wide asserts that its tiles are not smaller)
 static inline uint64_t wide_tile(uint32_t key_words) { return key_words == 2 ? 1024u * 8u : 1024u * 16u; }
 size_t wide_scratch_bytes(uint64_t n, uint32_t key_words) {
   const uint64_t tile = wide_tile(key_words);
@@ -1403,124 +1361,37 @@ size_t wide_scratch_bytes(uint64_t n, uint32_t key_words) {
   return (size_t)(tiles0 + tiles1_max) * (RS_MAX_RADIX / 2) * sizeof(u64) + (size_t)(RS_MAX_RADIX + 2) * 16 + 512;
 }
 
-// RB: 9, or 8 where both digits have at most eight bits (plain bit digits only): half the counters, walkers and look-back granules
-template <typename K, int KPT, int RB>
-static hipError_t group_wide_rb(void *d_keys, void *d_alt, uint64_t n, const SortPlan &plan, uint32_t *d_error, uint64_t *d_sub_starts,
-                                hipStream_t st, hipEvent_t *pass_events, void *d_prepared, void *d_scratch, uint32_t *tr_a, uint32_t *tr_b) {
-  constexpr int BLOCK = 1024, R = 1 << RB;
-  using GS = GroupSmem<K, RB, BLOCK, KPT>;
-  constexpr uint64_t TILE = (uint64_t)BLOCK * KPT;
-  static_assert(TILE >= (sizeof(K) >= 12 ? 1024u * 8u : 1024u * 16u), "wide_scratch_bytes sizes the granules for tiles of at least wide_tile() keys");
-  // `compress` (dense-rank digits): the instantiations with the rank table in LDS -- where 8 KiB are left behind the tile
-  constexpr bool HPC_TAB = RB == 9 && GS::BYTES + 8192 <= 160 * 1024;
-  if (RB != 9 && (plan.hpc || plan.pass_bits[0] > (u32)RB || plan.pass_bits[1] > (u32)RB)) return hipErrorInvalidValue;
-  const bool hpcd = HPC_TAB && plan.hpc && plan_mask(plan, 0) == HPC_DIGIT_MASK && plan_mask(plan, 1) == HPC_DIGIT_MASK;
-  // (make_hpc_mixed_plan: the high digit from the rank table, the low one a plain eight-bit field -- its pass is the eight-bit instantiation)
-  const bool mixed = HPC_TAB && plan.hpc == 2 && plan.pass_bits[0] <= 8u;
-  using GS8 = GroupSmem<K, 8, BLOCK, KPT>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<K, RB, BLOCK, KPT, false, false, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS::BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<K, RB, BLOCK, KPT, false, false, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS::BYTES);
-    if constexpr (HPC_TAB) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<K, RB, BLOCK, KPT, false, false, true, false, 0, 1>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS::BYTES + 8192);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<K, RB, BLOCK, KPT, false, false, false, false, 0, 1>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS::BYTES + 8192);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<K, RB, BLOCK, KPT, false, false, true, false, 0, 2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS::BYTES + 8192);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<K, 8, BLOCK, KPT, false, false, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS8::BYTES);
-    }
-    attr_done = true;
-  }
-  const uint64_t tiles0 = (n + TILE - 1) / TILE, tiles1_max = tiles0 + RS_MAX_RADIX + 1;
-  SortHeader *hdr = reinterpret_cast<SortHeader *>(d_prepared);
-  u64 *status_a = reinterpret_cast<u64 *>(d_scratch);
-  u64 *status_b = status_a + (size_t)tiles0 * (R / 2);
-  u64 *region_start = status_b + (size_t)tiles1_max * (R / 2);
-  u32 *region_tiles = reinterpret_cast<u32 *>(region_start + RS_MAX_RADIX + 1);
+hipError_t launch_group_wide(GroupFile &f) {
+  static_assert((uint64_t)GROUP_BLOCK * group_kpt_wide(GROUP_U64) >= 1024u * 16u && (uint64_t)GROUP_BLOCK * group_kpt_wide(GROUP_K128) >= 1024u * 8u &&
+                (uint64_t)GROUP_BLOCK * group_kpt_wide(GROUP_K96) >= 1024u * 8u, "wide_scratch_bytes sizes the granules for tiles of at least wide_tile() keys");
+  if (!f.plan || !sort_plan_wide_msd(*f.plan, f.n) || !f.prepared || !f.scratch ||
+      (f.layout != GroupKeys::U64 && f.layout != GroupKeys::K128 && f.layout != GroupKeys::K96))
+    return hipErrorInvalidValue;
+  const SortPlan &plan = *f.plan;
+  const uint64_t n = f.n;
   // the keys stay whole: digit A (high) at shA, digit B (low) at `low`, both where the plan put them
   // (`compress`: dense-rank digits in ten-bit fields -- the kernels take the digit with hpc_digit(), the sub-bucket numbers keep the fields)
   const u32 low = plan.pass_shift[0], bB = plan.pass_bits[0], bA = plan.pass_bits[1], shA = low + bB;
   const u32 maskA = plan_mask(plan, 1), maskB = plan_mask(plan, 0);
-  *tr_a = bA; *tr_b = bB;
-  const uint64_t resident = (uint64_t)device_cu_count() * GS::WG_PER_CU;
+  GroupInst i0, i1;
+  group_pick_wide(f.layout == GroupKeys::U64 ? GROUP_U64 : (f.layout == GroupKeys::K128 ? GROUP_K128 : GROUP_K96), plan.hpc, bB, bA, &i0, &i1);
+  const uint64_t tile = group_tile(i0);                      // (both passes: 12-byte K96 records take 12288-key tiles, 144 KiB of LDS)
+  const uint64_t tiles0 = (n + tile - 1) / tile, tiles1_max = tiles0 + RS_MAX_RADIX + 1;
+  const size_t row = group_granules(i0);                     // granules of a status row
+  SortHeader *hdr = reinterpret_cast<SortHeader *>(f.prepared);
+  u64 *status_a = reinterpret_cast<u64 *>(f.scratch);
+  u64 *status_b = status_a + (size_t)tiles0 * row;
+  u64 *region_start = status_b + (size_t)tiles1_max * row;
+  u32 *region_tiles = reinterpret_cast<u32 *>(region_start + RS_MAX_RADIX + 1);
+  f.tr_a = bA; f.tr_b = bB;
 
-  if (pass_events) MGC_CHECK(hipEventRecord(pass_events[0], st));
-  if constexpr (HPC_TAB) {
-    if (hpcd)
-      hipLaunchKernelGGL((radix_group_kernel<K, RB, BLOCK, KPT, false, false, true, false, 0, 1>), dim3((uint32_t)std::min(tiles0, resident)), dim3(BLOCK), GS::BYTES + 8192, st,
-                         reinterpret_cast<const K *>(d_keys), reinterpret_cast<K *>(d_alt), (u64)n, shA, maskA,
-                         &hdr->gbase[0][0], status_a, &hdr->ticket[0], d_error, (u64)tiles0, (const u64 *)nullptr, (const u32 *)nullptr,
-                         GroupExtra{0u, low, maskB, &hdr->ghist[1][0]}, (u64 *)nullptr);
-  }
-  if constexpr (HPC_TAB) {
-    if (mixed)
-      hipLaunchKernelGGL((radix_group_kernel<K, RB, BLOCK, KPT, false, false, true, false, 0, 2>), dim3((uint32_t)std::min(tiles0, resident)), dim3(BLOCK), GS::BYTES + 8192, st,
-                         reinterpret_cast<const K *>(d_keys), reinterpret_cast<K *>(d_alt), (u64)n, shA, maskA,
-                         &hdr->gbase[0][0], status_a, &hdr->ticket[0], d_error, (u64)tiles0, (const u64 *)nullptr, (const u32 *)nullptr,
-                         GroupExtra{0u, low, maskB, &hdr->ghist[1][0]}, (u64 *)nullptr);
-  }
-  if (!hpcd && !mixed)
-  hipLaunchKernelGGL((radix_group_kernel<K, RB, BLOCK, KPT, false, false, true>), dim3((uint32_t)std::min(tiles0, resident)), dim3(BLOCK), GS::BYTES, st,
-                     reinterpret_cast<const K *>(d_keys), reinterpret_cast<K *>(d_alt), (u64)n, shA, maskA,
-                     &hdr->gbase[0][0], status_a, &hdr->ticket[0], d_error, (u64)tiles0, (const u64 *)nullptr, (const u32 *)nullptr,
-                     GroupExtra{0u, low, maskB, &hdr->ghist[1][0]}, (u64 *)nullptr);
-  MGC_CHECK(hipGetLastError());
-  if (pass_events) MGC_CHECK(hipEventRecord(pass_events[1], st));
-  hipLaunchKernelGGL(narrow_mid_kernel, dim3(1), dim3(RS_MAX_RADIX), 0, st, hdr, (u64)n, (u32)TILE, region_start, region_tiles);
-  MGC_CHECK(hipGetLastError());
-  if (pass_events) MGC_CHECK(hipEventRecord(pass_events[2], st));
-  if constexpr (HPC_TAB) {
-    if (hpcd)
-      hipLaunchKernelGGL((radix_group_kernel<K, RB, BLOCK, KPT, false, false, false, false, 0, 1>), dim3((uint32_t)std::min(tiles1_max, resident)), dim3(BLOCK), GS::BYTES + 8192, st,
-                         reinterpret_cast<const K *>(d_alt), reinterpret_cast<K *>(d_keys), (u64)n, low, maskB,
-                         &hdr->gbase[1][0], status_b, &hdr->ticket[1], d_error, (u64)tiles0, region_start, region_tiles,
-                         GroupExtra{0u, 0u, 0u, nullptr}, (u64 *)nullptr);
-  }
-  u32 granules1 = (u32)(R / 2);
-  if constexpr (HPC_TAB) {
-    if (mixed) {
-      granules1 = 128u;
-      hipLaunchKernelGGL((radix_group_kernel<K, 8, BLOCK, KPT, false, false, false>), dim3((uint32_t)std::min(tiles1_max, resident)), dim3(BLOCK), GS8::BYTES, st,
-                         reinterpret_cast<const K *>(d_alt), reinterpret_cast<K *>(d_keys), (u64)n, low, maskB,
-                         &hdr->gbase[1][0], status_b, &hdr->ticket[1], d_error, (u64)tiles0, region_start, region_tiles,
-                         GroupExtra{0u, 0u, 0u, nullptr}, (u64 *)nullptr);
-    }
-  }
-  if (!hpcd && !mixed)
-  hipLaunchKernelGGL((radix_group_kernel<K, RB, BLOCK, KPT, false, false, false>), dim3((uint32_t)std::min(tiles1_max, resident)), dim3(BLOCK), GS::BYTES, st,
-                     reinterpret_cast<const K *>(d_alt), reinterpret_cast<K *>(d_keys), (u64)n, low, maskB,
-                     &hdr->gbase[1][0], status_b, &hdr->ticket[1], d_error, (u64)tiles0, region_start, region_tiles,
-                     GroupExtra{0u, 0u, 0u, nullptr}, (u64 *)nullptr);
-  MGC_CHECK(hipGetLastError());
-  if (pass_events) MGC_CHECK(hipEventRecord(pass_events[3], st));
-  const u64 ng = (u64)1 << (bA + bB);
-  hipLaunchKernelGGL(narrow_bounds_kernel, dim3((uint32_t)((ng + 1 + 255) / 256)), dim3(256), 0, st, status_b, region_tiles,
-                     &hdr->gbase[1][0], (u64)n, bA, ng, reinterpret_cast<u64 *>(d_sub_starts), granules1);
-  return hipGetLastError();
-}
-
-template <typename K, int KPT>
-static hipError_t group_wide(void *d_keys, void *d_alt, uint64_t n, const SortPlan &plan, uint32_t *d_error, uint64_t *d_sub_starts,
-                             hipStream_t st, hipEvent_t *pass_events, void *d_prepared, void *d_scratch, uint32_t *tr_a, uint32_t *tr_b) {
-  if (!plan.hpc && plan.pass_bits[0] <= 8u && plan.pass_bits[1] <= 8u)
-    return group_wide_rb<K, KPT, 8>(d_keys, d_alt, n, plan, d_error, d_sub_starts, st, pass_events, d_prepared, d_scratch, tr_a, tr_b);
-  return group_wide_rb<K, KPT, 9>(d_keys, d_alt, n, plan, d_error, d_sub_starts, st, pass_events, d_prepared, d_scratch, tr_a, tr_b);
-}
-
-hipError_t launch_group_wide(void *d_keys, void *d_alt, uint64_t n, uint32_t key_words, const SortPlan &plan, uint32_t *d_error,
-                             uint64_t *d_sub_starts, hipStream_t st, hipEvent_t *pass_events, void *d_prepared, void *d_scratch,
-                             uint32_t *tr_a, uint32_t *tr_b, bool k96) {
-  if (!sort_plan_wide_msd(plan, n) || !d_prepared || !d_scratch) return hipErrorInvalidValue;
-  // 12-byte K96 records (k = 33..51, the bits below the file): 12288-key tiles (144 KiB of LDS)
-  if (k96) return key_words == 2 ? group_wide<K96, 12>(d_keys, d_alt, n, plan, d_error, d_sub_starts, st, pass_events, d_prepared, d_scratch, tr_a, tr_b)
-                                 : hipErrorInvalidValue;
-  if (key_words == 2) return group_wide<K128, 8>(d_keys, d_alt, n, plan, d_error, d_sub_starts, st, pass_events, d_prepared, d_scratch, tr_a, tr_b);
-  return group_wide<u64, 16>(d_keys, d_alt, n, plan, d_error, d_sub_starts, st, pass_events, d_prepared, d_scratch, tr_a, tr_b);
+  const GroupPass p0{f.keys, f.alt, (u64)n, shA, maskA, &hdr->gbase[0][0], status_a, &hdr->ticket[0], f.d_error, (u64)tiles0,
+                     nullptr, nullptr, GroupExtra{0u, low, maskB, &hdr->ghist[1][0]}, nullptr, (u64)tiles0, f.st};
+  const GroupPass p1{f.alt, f.keys, (u64)n, low, maskB, &hdr->gbase[1][0], status_b, &hdr->ticket[1], f.d_error, (u64)tiles0,
+                     region_start, region_tiles, GroupExtra{0u, 0u, 0u, nullptr}, nullptr, (u64)tiles1_max, f.st};
+  if (f.pass_events) MGC_CHECK(hipEventRecord(f.pass_events[0], f.st));
+  MGC_CHECK(launch_group_pass(i0, p0));
+  return group_second_pass(i1, p1, hdr, true, bA, bB, f.d_sub_starts, f.pass_events);
 }
 
 size_t sort_header_bytes() { return ((sizeof(SortHeader) + 255) / 256) * 256; }

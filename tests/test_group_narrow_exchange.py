@@ -99,16 +99,33 @@ def test_digit_extremes(ops, oracle_lib, torch_cuda, monkeypatch, name, n, targe
 
 
 # both input layouts, both fetch forms, the staggered start and the low-digit-first order on one edge size: the forms that fetch
-# inside the look-back run on 16384-key tiles (196609 = 12 tiles + one key), the pipelined ones on 24576-key tiles (8 tiles + one key)
-@pytest.mark.parametrize("env", [{}, {"MGC_SOA5": "0"}, {"MGC_GROUP_PIPE": "0"}, {"MGC_PASS_STAGGER": "8"}, {"MGC_FINE_HIST": "0"},
-                                 {"MGC_SOA5": "0", "MGC_GROUP_PIPE": "0"}], ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()) or "default")
-@pytest.mark.parametrize("n,target", [(196609, 3), (270_001, 1)])
-def test_layouts_and_fetch_forms(ops, oracle_lib, torch_cuda, monkeypatch, n, target, env):
+# inside the look-back run on 16384-key tiles (196609 = 12 tiles + one key), the pipelined ones on 24576-key tiles (8 tiles + one key).
+# MGC_GROUP_DBG=1 (one size only): the instrumented instantiations of both passes -- the pipelined 5-byte first pass, the 5-byte one
+# that fetches inside the look-back, the whole-key one -- which report on stderr; a count instruments its first two files, whatever
+# ran before in the process.
+_FORMS = [{}, {"MGC_SOA5": "0"}, {"MGC_GROUP_PIPE": "0"}, {"MGC_PASS_STAGGER": "8"}, {"MGC_FINE_HIST": "0"}, {"MGC_SOA5": "0", "MGC_GROUP_PIPE": "0"}]
+_DBG_FORMS = [{"MGC_GROUP_DBG": "1"}, {"MGC_GROUP_DBG": "1", "MGC_GROUP_PIPE": "0"}, {"MGC_GROUP_DBG": "1", "MGC_SOA5": "0"}]
+
+
+def _form_cases():
+    cases = [(n, target, env) for n, target in ((196609, 3), (270_001, 1)) for env in _FORMS] + [(196609, 3, env) for env in _DBG_FORMS]
+    return [pytest.param(n, target, env, id="%d-%d-%s" % (n, target, ",".join("%s=%s" % kv for kv in env.items()) or "default"))
+            for n, target, env in cases]
+
+
+@pytest.mark.parametrize("n,target,env", _form_cases())
+def test_layouts_and_fetch_forms(ops, oracle_lib, torch_cuda, monkeypatch, capfd, n, target, env):
     monkeypatch.setenv("MGC_FINISH_TARGET", str(target))
     for name, value in env.items():
         monkeypatch.setenv(name, value)
     bases = _one_file_input(n, n)
     _count_and_check(ops, oracle_lib, torch_cuda, ("edge", n), bases, 21, FORWARD, want_n=n)
+    err = capfd.readouterr().err
+    if "MGC_GROUP_DBG" in env:                                      # the one file of the input, both passes
+        first = "first (u64 -> u32)" if "MGC_SOA5" in env else ("first (5 B -> u32)" if "MGC_GROUP_PIPE" in env else "first (5 B -> u32, fetch a tile ahead)")
+        assert "[groupdbg] %s pass, %d keys" % (first, n) in err and "[groupdbg] second (u32 -> u32) pass, %d keys" % n in err
+    else:
+        assert "[groupdbg]" not in err
 
 
 # canonical k-mers of ordinary reads.  k = 23: 40 bits below the file, the widest 5-byte key -- 32-bit words with no spare bit.
