@@ -163,4 +163,19 @@ size_t     scan_scratch_elems(uint64_t n);                 // scratch uint64 ent
 hipError_t scan_u64_exclusive(u64 *a, uint64_t n, u64 *scratch, u64 *d_total, hipStream_t st);
 hipError_t scan_u64_min_reverse(u64 *a, uint64_t n, u64 *scratch, u64 init, hipStream_t st);
 
+// ---- the host half of an order-preserving compaction (the device half: mgc_compact.hpp) ----
+// tiles[0, t): the count pass's totals, after compact_scan the emit pass's exclusive bases; *total: the number of kept items.
+// Contiguous form: the total at [0], the tiles at [8], the scratch after t + 1 of them.  The scratch is asked for t + 1 entries
+// although t are scanned: the two differ at t = 1 and at multiples of 4096 only, and callers pre-allocate from the byte counts
+// they were given, which therefore stay what they always were.
+struct CompactWs { u64 *total, *tiles, *scratch; uint64_t t; };
+inline size_t    compact_scratch_elems(uint64_t t) { return scan_scratch_elems(t + 1); }
+inline size_t    compact_ws_elems(uint64_t t) { return (size_t)(8 + t + 1) + compact_scratch_elems(t); }
+inline CompactWs compact_ws_at(void *ws, uint64_t t) { u64 *p = reinterpret_cast<u64 *>(ws); return {p, p + 8, p + 8 + t + 1, t}; }
+// after the count pass's launch: its launch error, then the scan of its totals
+inline hipError_t compact_scan(const CompactWs &w, hipStream_t st) {
+  MGC_CHECK(hipGetLastError());
+  return scan_u64_exclusive(w.tiles, w.t, w.scratch, w.total, st);
+}
+
 }  // namespace mgc

@@ -11,6 +11,7 @@
 //   emit   : keep = (found > 0) == include (:124-125); sizes -> scan -> a wave (a workgroup for long records) per kept record
 //            writes ">"/"@" ident " nKmers=" found, the bases on one line, ("+", qualities) (:107-108) with 16-byte stores
 #include "mgc_lookup_dev.hpp"
+#include "mgc_compact.hpp"
 #include "../../include/meryl_gpu_count.h"
 #include "../../include/meryl_seq.h"
 
@@ -45,26 +46,12 @@ __device__ __forceinline__ u64 fi_block_rec(const u64 *__restrict__ a, u64 cnt, 
 }
 
 // ---- line starts -------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256)
-void filter_nl_count_kernel(const uint8_t *__restrict__ text, u64 n, u64 *__restrict__ tile_cnt) {
-  __shared__ u32 s_tmp[256 / 64 + 1];
-  const u64 base = (u64)blockIdx.x * FI_TILE + (u64)threadIdx.x * 16;
-  u32 c = 0;
-  if (base < n) {
-    const uint4 v = fi_load(text, base, n);
-#pragma unroll
-    for (int q = 0; q < 16; q++) c += fi_byte(v, q) == '\n';
-  }
-  u32 tot;
-  (void)block_excl_scan<256, u32>(c, s_tmp, &tot);
-  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
-}
 // ls[0] = 0, ls[j] = the position after the j-th newline; an unterminated last line ends at the sentinel ls[nl + 1] = n + 1,
 // so that line j is always [ls[j], ls[j + 1] - 1)
+template <bool EMIT>
 __global__ __launch_bounds__(256)
-void filter_nl_emit_kernel(const uint8_t *__restrict__ text, u64 n, const u64 *__restrict__ tile_base, u64 nl, u32 open_tail,
-                           u64 *__restrict__ ls) {
-  __shared__ u32 s_tmp[256 / 64 + 1];
+void filter_nl_kernel(const uint8_t *__restrict__ text, u64 n, u64 *__restrict__ tiles /*EMIT: exclusive bases*/, u64 nl, u32 open_tail,
+                      u64 *__restrict__ ls) {
   const u64 base = (u64)blockIdx.x * FI_TILE + (u64)threadIdx.x * 16;
   u32 c = 0;
   uint4 v = make_uint4(0, 0, 0, 0);
@@ -73,8 +60,8 @@ void filter_nl_emit_kernel(const uint8_t *__restrict__ text, u64 n, const u64 *_
 #pragma unroll
     for (int q = 0; q < 16; q++) c += fi_byte(v, q) == '\n';
   }
-  u32 tot;
-  u64 o = tile_base[blockIdx.x] + block_excl_scan<256, u32>(c, s_tmp, &tot);
+  u64 o;
+  if (!compact_slot<256, EMIT>(c, tiles, &o)) return;
   if (blockIdx.x == 0 && threadIdx.x == 0) { ls[0] = 0; if (open_tail) ls[nl + 1] = n + 1; }
   if (c) {
 #pragma unroll
@@ -92,27 +79,17 @@ __global__ void filter_meta_kernel(const uint8_t *__restrict__ text, u64 n, u64 
 
 // ---- FASTA: the header lines, compacted in order -------------------------------------------------------------------------
 constexpr int FI_LTILE = 256 * 8;                   // lines per workgroup
+template <bool EMIT>
 __global__ __launch_bounds__(256)
-void filter_hdr_count_kernel(const uint8_t *__restrict__ text, const u64 *__restrict__ ls, u64 n_lines, u64 *__restrict__ tile_cnt) {
-  __shared__ u32 s_tmp[256 / 64 + 1];
+void filter_hdr_kernel(const uint8_t *__restrict__ text, const u64 *__restrict__ ls, u64 n_lines, u64 *__restrict__ tiles /*EMIT: exclusive bases*/,
+                       u64 n_rec, u64 *__restrict__ rl) {
   const u64 base = (u64)blockIdx.x * FI_LTILE + (u64)threadIdx.x * 8;
-  u32 c = 0;
-  for (int q = 0; q < 8; q++) { const u64 i = base + q; if (i < n_lines) c += text[ls[i]] == '>'; }
-  u32 tot;
-  (void)block_excl_scan<256, u32>(c, s_tmp, &tot);
-  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(256)
-void filter_hdr_emit_kernel(const uint8_t *__restrict__ text, const u64 *__restrict__ ls, u64 n_lines, const u64 *__restrict__ tile_base,
-                            u64 n_rec, u64 *__restrict__ rl) {
-  __shared__ u32 s_tmp[256 / 64 + 1];
-  const u64 base = (u64)blockIdx.x * FI_LTILE + (u64)threadIdx.x * 8;
-  u32 c = 0;
-  for (int q = 0; q < 8; q++) { const u64 i = base + q; if (i < n_lines) c += text[ls[i]] == '>'; }
-  u32 tot;
-  u64 o = tile_base[blockIdx.x] + block_excl_scan<256, u32>(c, s_tmp, &tot);
+  u32 hdr = 0;
+  for (int q = 0; q < 8; q++) { const u64 i = base + q; if (i < n_lines) hdr |= (u32)(text[ls[i]] == '>') << q; }
+  u64 o;
+  if (!compact_slot<256, EMIT>(__popc(hdr), tiles, &o)) return;
   if (blockIdx.x == 0 && threadIdx.x == 0) rl[n_rec] = n_lines;
-  for (int q = 0; q < 8; q++) { const u64 i = base + q; if (i < n_lines && text[ls[i]] == '>') rl[o++] = i; }
+  for (int q = 0; q < 8; q++) if ((hdr >> q) & 1u) rl[o++] = base + q;
 }
 
 // ---- spans of a record ------------------------------------------------------------------------------------------------
@@ -153,33 +130,11 @@ void filter_spans_kernel(const uint8_t *__restrict__ text, u64 n, const u64 *__r
 
 // ---- FASTA: the de-lined copy --------------------------------------------------------------------------------------------
 // kept: every byte outside the header lines that is not \r \n blank tab.  bb[r] = kept bytes before record r's header.
+// One record walk counts, one writes (it also leaves bb[r] where a header begins).
+template <bool EMIT>
 __global__ __launch_bounds__(256)
-void filter_flat_count_kernel(const uint8_t *__restrict__ text, u64 n, const u64 *__restrict__ hb, const u64 *__restrict__ he, u64 n_rec,
-                              u64 *__restrict__ tile_cnt) {
-  __shared__ u32 s_tmp[256 / 64 + 1];
-  __shared__ u64 s_rng[2];
-  const u64 tile_b = (u64)blockIdx.x * FI_TILE, base = tile_b + (u64)threadIdx.x * 16;
-  const u64 tile_e = tile_b + FI_TILE - 1 < n ? tile_b + FI_TILE - 1 : n - 1;
-  u64 r = fi_block_rec(hb, n_rec, tile_b, tile_e, base < n ? base : n - 1, s_rng);
-  u32 c = 0;
-  if (base < n) {
-    const uint4 v = fi_load(text, base, n);
-    u64 cur_he = he[r], nxt = r + 1 < n_rec ? hb[r + 1] : ~0ull;
-#pragma unroll
-    for (int q = 0; q < 16; q++) {
-      const u64 p = base + q;
-      if (p >= nxt) { r++; cur_he = he[r]; nxt = r + 1 < n_rec ? hb[r + 1] : ~0ull; }
-      c += (p < n && p >= cur_he && !fi_ws(fi_byte(v, q)));
-    }
-  }
-  u32 tot;
-  (void)block_excl_scan<256, u32>(c, s_tmp, &tot);
-  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(256)
-void filter_flat_emit_kernel(const uint8_t *__restrict__ text, u64 n, const u64 *__restrict__ hb, const u64 *__restrict__ he, u64 n_rec,
-                             const u64 *__restrict__ tile_base, uint8_t *__restrict__ flat, u64 *__restrict__ bb) {
-  __shared__ u32 s_tmp[256 / 64 + 1];
+void filter_flat_kernel(const uint8_t *__restrict__ text, u64 n, const u64 *__restrict__ hb, const u64 *__restrict__ he, u64 n_rec,
+                        u64 *__restrict__ tiles /*EMIT: exclusive bases*/, uint8_t *__restrict__ flat, u64 *__restrict__ bb) {
   __shared__ u64 s_rng[2];
   const u64 tile_b = (u64)blockIdx.x * FI_TILE, base = tile_b + (u64)threadIdx.x * 16;
   const u64 tile_e = tile_b + FI_TILE - 1 < n ? tile_b + FI_TILE - 1 : n - 1;
@@ -196,8 +151,8 @@ void filter_flat_emit_kernel(const uint8_t *__restrict__ text, u64 n, const u64 
       c += (p < n && p >= cur_he && !fi_ws(fi_byte(v, q)));
     }
   }
-  u32 tot;
-  u64 o = tile_base[blockIdx.x] + block_excl_scan<256, u32>(c, s_tmp, &tot);
+  u64 o;
+  if (!compact_slot<256, EMIT>(c, tiles, &o)) return;
   if (base < n) {
     u64 r = r0, cur_hb = hb[r], cur_he = he[r], nxt = r + 1 < n_rec ? hb[r + 1] : ~0ull;
 #pragma unroll
@@ -385,6 +340,14 @@ struct FiInput {
 };
 struct FiWork { FiInput in[2]; FiBuf found, misc; };
 
+// the compaction workspace of `tiles` tiles over an input's grow-only buffers; the total goes where the caller reads it
+hipError_t fi_compact_ws(FiInput &S, u64 tiles, u64 *d_total, mgc::CompactWs *w) {
+  MGC_CHECK(S.tiles.need(8 * (tiles + 2)));
+  MGC_CHECK(S.scr.need(8 * mgc::compact_scratch_elems(tiles)));
+  *w = {d_total, S.tiles.as<u64>(), S.scr.as<u64>(), tiles};
+  return hipSuccess;
+}
+
 uint32_t fi_grid(u64 items, u64 per_block) { const u64 g = (items + per_block - 1) / per_block; return (uint32_t)(g ? g : 1); }
 
 // lines and records of one piece
@@ -392,11 +355,10 @@ int fi_index(FiInput &S, const uint8_t *d_text, u64 n, bool final, u64 *d_misc, 
   S.n = n; S.n_lines = S.nr_all = S.nr = 0; S.fmt = 0;
   if (n == 0) return MGC_OK;
   const u64 tiles = (n + mgc::FI_TILE - 1) / mgc::FI_TILE;
-  FI_HIP(S.tiles.need(8 * (tiles + 2)));
-  FI_HIP(S.scr.need(8 * mgc::scan_scratch_elems(tiles + 1)));
-  hipLaunchKernelGGL(mgc::filter_nl_count_kernel, dim3((uint32_t)tiles), dim3(256), 0, st, d_text, n, S.tiles.as<u64>());
-  FI_HIP(hipGetLastError());
-  FI_HIP(mgc::scan_u64_exclusive(S.tiles.as<u64>(), tiles, S.scr.as<u64>(), d_misc + 0, st));
+  mgc::CompactWs w;
+  FI_HIP(fi_compact_ws(S, tiles, d_misc + 0, &w));
+  hipLaunchKernelGGL(mgc::filter_nl_kernel<false>, dim3((uint32_t)tiles), dim3(256), 0, st, d_text, n, w.tiles, (u64)0, 0u, (u64 *)nullptr);
+  FI_HIP(mgc::compact_scan(w, st));
   hipLaunchKernelGGL(mgc::filter_meta_kernel, dim3(1), dim3(1), 0, st, d_text, n, d_misc);
   FI_HIP(hipGetLastError());
   u64 m[4];
@@ -408,8 +370,7 @@ int fi_index(FiInput &S, const uint8_t *d_text, u64 n, bool final, u64 *d_misc, 
   if (!S.fmt) return fi_fail(MGC_EFORMAT, std::string("mgc_lookup_filter: a record starts with '") + (char)m[3] + "', neither '>' nor '@'");
   S.n_lines = nl + (open_tail ? 1 : 0);
   FI_HIP(S.ls.need(8 * (nl + 2)));
-  hipLaunchKernelGGL(mgc::filter_nl_emit_kernel, dim3((uint32_t)tiles), dim3(256), 0, st, d_text, n, S.tiles.as<u64>(), nl, open_tail ? 1u : 0u,
-                     S.ls.as<u64>());
+  hipLaunchKernelGGL(mgc::filter_nl_kernel<true>, dim3((uint32_t)tiles), dim3(256), 0, st, d_text, n, w.tiles, nl, open_tail ? 1u : 0u, S.ls.as<u64>());
   FI_HIP(hipGetLastError());
   if (S.fmt == MGC_TEXT_FASTQ) {
     if (final && S.n_lines % 4)
@@ -419,16 +380,15 @@ int fi_index(FiInput &S, const uint8_t *d_text, u64 n, bool final, u64 *d_misc, 
     return MGC_OK;
   }
   const u64 ltiles = (S.n_lines + mgc::FI_LTILE - 1) / mgc::FI_LTILE;
-  FI_HIP(S.tiles.need(8 * (ltiles + 2)));
-  FI_HIP(S.scr.need(8 * mgc::scan_scratch_elems(ltiles + 1)));
-  hipLaunchKernelGGL(mgc::filter_hdr_count_kernel, dim3((uint32_t)ltiles), dim3(256), 0, st, d_text, S.ls.as<u64>(), S.n_lines, S.tiles.as<u64>());
-  FI_HIP(hipGetLastError());
-  FI_HIP(mgc::scan_u64_exclusive(S.tiles.as<u64>(), ltiles, S.scr.as<u64>(), d_misc + 4, st));
+  FI_HIP(fi_compact_ws(S, ltiles, d_misc + 4, &w));
+  hipLaunchKernelGGL(mgc::filter_hdr_kernel<false>, dim3((uint32_t)ltiles), dim3(256), 0, st, d_text, S.ls.as<u64>(), S.n_lines, w.tiles, (u64)0,
+                     (u64 *)nullptr);
+  FI_HIP(mgc::compact_scan(w, st));
   FI_HIP(hipMemcpyAsync(&S.nr_all, d_misc + 4, 8, hipMemcpyDeviceToHost, st));
   FI_HIP(hipStreamSynchronize(st));
   FI_HIP(S.rl.need(8 * (S.nr_all + 1)));
-  hipLaunchKernelGGL(mgc::filter_hdr_emit_kernel, dim3((uint32_t)ltiles), dim3(256), 0, st, d_text, S.ls.as<u64>(), S.n_lines, S.tiles.as<u64>(),
-                     S.nr_all, S.rl.as<u64>());
+  hipLaunchKernelGGL(mgc::filter_hdr_kernel<true>, dim3((uint32_t)ltiles), dim3(256), 0, st, d_text, S.ls.as<u64>(), S.n_lines, w.tiles, S.nr_all,
+                     S.rl.as<u64>());
   FI_HIP(hipGetLastError());
   S.nr = final ? S.nr_all : S.nr_all - 1;                           // the last record is complete only when the input ends here
   return MGC_OK;
@@ -498,14 +458,13 @@ int fi_step(FiWork &W, const mgc_lookup *t, int mode, uint32_t skip_first, uint3
     const uint8_t *stream = d_text[i];
     if (fasta) {
       const u64 tiles = (n + mgc::FI_TILE - 1) / mgc::FI_TILE;
-      FI_HIP(S.tiles.need(8 * (tiles + 2)));
-      FI_HIP(S.scr.need(8 * mgc::scan_scratch_elems(tiles + 1)));
-      hipLaunchKernelGGL(mgc::filter_flat_count_kernel, dim3((uint32_t)tiles), dim3(256), 0, st, d_text[i], n, S.hb.as<u64>(), S.he.as<u64>(), nspan,
-                         S.tiles.as<u64>());
-      FI_HIP(hipGetLastError());
-      FI_HIP(mgc::scan_u64_exclusive(S.tiles.as<u64>(), tiles, S.scr.as<u64>(), S.bb.as<u64>() + nspan, st));
-      hipLaunchKernelGGL(mgc::filter_flat_emit_kernel, dim3((uint32_t)tiles), dim3(256), 0, st, d_text[i], n, S.hb.as<u64>(), S.he.as<u64>(), nspan,
-                         S.tiles.as<u64>(), S.flat.as<uint8_t>(), S.bb.as<u64>());
+      mgc::CompactWs w;                                               // the total is bb[nspan]: where the last record's bases end
+      FI_HIP(fi_compact_ws(S, tiles, S.bb.as<u64>() + nspan, &w));
+      hipLaunchKernelGGL(mgc::filter_flat_kernel<false>, dim3((uint32_t)tiles), dim3(256), 0, st, d_text[i], n, S.hb.as<u64>(), S.he.as<u64>(), nspan,
+                         w.tiles, (uint8_t *)nullptr, (u64 *)nullptr);
+      FI_HIP(mgc::compact_scan(w, st));
+      hipLaunchKernelGGL(mgc::filter_flat_kernel<true>, dim3((uint32_t)tiles), dim3(256), 0, st, d_text[i], n, S.hb.as<u64>(), S.he.as<u64>(), nspan,
+                         w.tiles, S.flat.as<uint8_t>(), S.bb.as<u64>());
       FI_HIP(hipGetLastError());
       stream = S.flat.as<uint8_t>();
     }

@@ -6,6 +6,7 @@
 // the top bits: index read -> binary search among the few k-mers sharing those bits.  Integer work bound by HBM/L2
 // latency, not bandwidth: queries are batched so that thousands of searches are in flight per CU.
 #include "mgc_lookup_dev.hpp"
+#include "mgc_compact.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -64,30 +65,18 @@ void lookup_existence_kernel(const K *__restrict__ keys, const u32 *__restrict__
 
 // ---- value filter (minValue <= v <= maxValue), order-preserving: count per tile, scan, emit ----------------------
 constexpr int FL_TILE = 256 * 8;
+// (the count pass reads no key: it is instantiated for u64 alone and launched without keys or outputs)
+template <typename K, bool EMIT>
 __global__ __launch_bounds__(256)
-void filter_count_kernel(const u32 *__restrict__ vals, u64 n, u64 vmin, u64 vmax, u64 *__restrict__ tile_cnt) {
-  __shared__ u32 s_tmp[256 / 64 + 1];
+void filter_kernel(const K *__restrict__ keys, const u32 *__restrict__ vals, u64 n, u64 vmin, u64 vmax,
+                   u64 *__restrict__ tiles /*EMIT: exclusive bases*/, K *__restrict__ out_k, u32 *__restrict__ out_v) {
   const u64 base = (u64)blockIdx.x * FL_TILE + (u64)threadIdx.x * 8;
-  u32 c = 0;
-  for (int q = 0; q < 8; q++) { const u64 i = base + q; if (i < n) { const u64 v = vals[i]; c += (v >= vmin && v <= vmax); } }
-  u32 tot;
-  (void)block_excl_scan<256, u32>(c, s_tmp, &tot);
-  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
-}
-template <typename K>
-__global__ __launch_bounds__(256)
-void filter_emit_kernel(const K *__restrict__ keys, const u32 *__restrict__ vals, u64 n, u64 vmin, u64 vmax,
-                        const u64 *__restrict__ tile_base, K *__restrict__ out_k, u32 *__restrict__ out_v) {
-  __shared__ u32 s_tmp[256 / 64 + 1];
-  const u64 base = (u64)blockIdx.x * FL_TILE + (u64)threadIdx.x * 8;
-  u32 c = 0;
-  for (int q = 0; q < 8; q++) { const u64 i = base + q; if (i < n) { const u64 v = vals[i]; c += (v >= vmin && v <= vmax); } }
-  u32 tot;
-  u64 o = tile_base[blockIdx.x] + block_excl_scan<256, u32>(c, s_tmp, &tot);
-  for (int q = 0; q < 8; q++) {
-    const u64 i = base + q;
-    if (i < n) { const u64 v = vals[i]; if (v >= vmin && v <= vmax) { out_k[o] = keys[i]; out_v[o] = (u32)v; o++; } }
-  }
+  u32 keep = 0;
+  for (int q = 0; q < 8; q++) { const u64 i = base + q; if (i < n) { const u64 v = vals[i]; keep |= (u32)(v >= vmin && v <= vmax) << q; } }
+  u64 o;
+  if (!compact_slot<256, EMIT>(__popc(keep), tiles, &o)) return;
+  for (int q = 0; q < 8; q++)
+    if ((keep >> q) & 1u) { out_k[o] = keys[base + q]; out_v[o] = vals[base + q]; o++; }
 }
 
 
@@ -184,26 +173,16 @@ void runs_lines_kernel(const u32 *__restrict__ val, u64 n, u32 any_only, u64 *__
 }
 // rising and falling edges of table t's flags, compacted in order (count per tile, scan, emit): they alternate, so the j-th
 // run of the table is [edges[2j], edges[2j+1]) -- no thread walks a run
+template <bool EMIT>
 __global__ __launch_bounds__(256)
-void runs_edge_count_kernel(const u32 *__restrict__ val, u64 n, u32 t, u32 any_only, u64 *__restrict__ tile_cnt) {
-  __shared__ u32 s_tmp[256 / 64 + 1];
+void runs_edge_kernel(const u32 *__restrict__ val, u64 n, u32 t, u32 any_only, u64 *__restrict__ tiles /*EMIT: exclusive bases*/,
+                      u64 *__restrict__ edges) {
   const u64 base = (u64)blockIdx.x * FL_TILE + (u64)threadIdx.x * 8;
-  u32 c = 0;
-  for (int q = 0; q < 8; q++) { const u64 i = base + q; if (i < n) c += rp_edge(val, i, t, any_only); }
-  u32 tot;
-  (void)block_excl_scan<256, u32>(c, s_tmp, &tot);
-  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(256)
-void runs_edge_emit_kernel(const u32 *__restrict__ val, u64 n, u32 t, u32 any_only, const u64 *__restrict__ tile_base,
-                           u64 *__restrict__ edges) {
-  __shared__ u32 s_tmp[256 / 64 + 1];
-  const u64 base = (u64)blockIdx.x * FL_TILE + (u64)threadIdx.x * 8;
-  u32 c = 0;
-  for (int q = 0; q < 8; q++) { const u64 i = base + q; if (i < n) c += rp_edge(val, i, t, any_only); }
-  u32 tot;
-  u64 o = tile_base[blockIdx.x] + block_excl_scan<256, u32>(c, s_tmp, &tot);
-  for (int q = 0; q < 8; q++) { const u64 i = base + q; if (i < n && rp_edge(val, i, t, any_only)) edges[o++] = i; }
+  u32 edge = 0;
+  for (int q = 0; q < 8; q++) { const u64 i = base + q; if (i < n) edge |= rp_edge(val, i, t, any_only) << q; }
+  u64 o;
+  if (!compact_slot<256, EMIT>(__popc(edge), tiles, &o)) return;
+  for (int q = 0; q < 8; q++) if ((edge >> q) & 1u) edges[o++] = base + q;
 }
 // run j of table t -> its line: lines[E] (exclusive scan of the lines per position) + the tables before t that also end at E
 __global__ __launch_bounds__(256)
@@ -430,33 +409,32 @@ extern "C" mgc_lookup *mgc_lookup_from_device(const void *d_keys, const uint32_t
     return lookup_finish(t);
   }
   const uint64_t tiles = (n + mgc::FL_TILE - 1) / mgc::FL_TILE;
-  uint64_t *d_tiles = nullptr, kept = 0;
+  void *d_ws = nullptr;
+  mgc::CompactWs w = {};
+  uint64_t kept = 0;
   if (tiles) {
-    const size_t elems = tiles + 1 + mgc::scan_scratch_elems(tiles + 1) + 8;
-    LK_TRY(hipMalloc(reinterpret_cast<void **>(&d_tiles), sizeof(uint64_t) * elems));
-    hipLaunchKernelGGL(mgc::filter_count_kernel, dim3((uint32_t)tiles), dim3(256), 0, nullptr, d_values, (mgc::u64)n, (mgc::u64)min_value,
-                       (mgc::u64)max_value, reinterpret_cast<mgc::u64 *>(d_tiles));
-    hipError_t e = mgc::scan_u64_exclusive(reinterpret_cast<mgc::u64 *>(d_tiles), tiles, reinterpret_cast<mgc::u64 *>(d_tiles) + tiles + 1 + 8,
-                                           reinterpret_cast<mgc::u64 *>(d_tiles) + tiles + 1, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(&kept, d_tiles + tiles + 1, sizeof(uint64_t), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { (void)hipFree(d_tiles); lk_err(std::string("value filter: ") + hipGetErrorString(e)); mgc_lookup_free(t); return nullptr; }
+    LK_TRY(hipMalloc(&d_ws, sizeof(uint64_t) * mgc::compact_ws_elems(tiles)));
+    w = mgc::compact_ws_at(d_ws, tiles);
+    hipLaunchKernelGGL((mgc::filter_kernel<mgc::u64, false>), dim3((uint32_t)tiles), dim3(256), 0, nullptr, (const mgc::u64 *)nullptr, d_values,
+                       (mgc::u64)n, (mgc::u64)min_value, (mgc::u64)max_value, w.tiles, (mgc::u64 *)nullptr, (uint32_t *)nullptr);
+    hipError_t e = mgc::compact_scan(w, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(&kept, w.total, sizeof(uint64_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { (void)hipFree(d_ws); lk_err(std::string("value filter: ") + hipGetErrorString(e)); mgc_lookup_free(t); return nullptr; }
   }
   t->n = kept;
   hipError_t e = hipMalloc(&t->d_keys, kbytes * (kept ? kept : 1));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&t->d_vals), sizeof(uint32_t) * (kept ? kept : 1));
   if (e == hipSuccess && tiles) {
     if (t->kw == 2)
-      hipLaunchKernelGGL((mgc::filter_emit_kernel<mgc::K128>), dim3((uint32_t)tiles), dim3(256), 0, nullptr, reinterpret_cast<const mgc::K128 *>(d_keys),
-                         d_values, (mgc::u64)n, (mgc::u64)min_value, (mgc::u64)max_value, reinterpret_cast<const mgc::u64 *>(d_tiles),
-                         reinterpret_cast<mgc::K128 *>(t->d_keys), t->d_vals);
+      hipLaunchKernelGGL((mgc::filter_kernel<mgc::K128, true>), dim3((uint32_t)tiles), dim3(256), 0, nullptr, reinterpret_cast<const mgc::K128 *>(d_keys),
+                         d_values, (mgc::u64)n, (mgc::u64)min_value, (mgc::u64)max_value, w.tiles, reinterpret_cast<mgc::K128 *>(t->d_keys), t->d_vals);
     else
-      hipLaunchKernelGGL((mgc::filter_emit_kernel<mgc::u64>), dim3((uint32_t)tiles), dim3(256), 0, nullptr, reinterpret_cast<const mgc::u64 *>(d_keys),
-                         d_values, (mgc::u64)n, (mgc::u64)min_value, (mgc::u64)max_value, reinterpret_cast<const mgc::u64 *>(d_tiles),
-                         reinterpret_cast<mgc::u64 *>(t->d_keys), t->d_vals);
+      hipLaunchKernelGGL((mgc::filter_kernel<mgc::u64, true>), dim3((uint32_t)tiles), dim3(256), 0, nullptr, reinterpret_cast<const mgc::u64 *>(d_keys),
+                         d_values, (mgc::u64)n, (mgc::u64)min_value, (mgc::u64)max_value, w.tiles, reinterpret_cast<mgc::u64 *>(t->d_keys), t->d_vals);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   }
-  if (d_tiles) (void)hipFree(d_tiles);
+  if (d_ws) (void)hipFree(d_ws);
   if (e != hipSuccess) { lk_err(std::string("value filter: ") + hipGetErrorString(e)); mgc_lookup_free(t); return nullptr; }
   return lookup_finish(t);
 }
@@ -826,31 +804,30 @@ extern "C" int mgc_lookup_report(const mgc_lookup *const *tables, uint32_t n_tab
   // -bed-runs: the line of every run, and its begin
   if (mode == MGC_REPORT_BED_RUNS && n_bases) {
     RP_HIP(B.alloc(reinterpret_cast<void **>(&d_lines), 8 * (n_bases + 1)));
-    const size_t lscr = mgc::scan_scratch_elems(n_bases + 1) + 8;
     const uint64_t tiles = (n_bases + mgc::FL_TILE - 1) / mgc::FL_TILE;
-    const size_t escr = mgc::scan_scratch_elems(tiles + 1) + 8;
-    mgc::u64 *d_s2 = nullptr, *d_tiles = nullptr, *d_edges = nullptr;
-    RP_HIP(B.alloc(reinterpret_cast<void **>(&d_s2), 8 * std::max(lscr, escr)));
-    RP_HIP(B.alloc(reinterpret_cast<void **>(&d_tiles), 8 * (tiles + 1 + 8)));
+    mgc::u64 *d_s2 = nullptr, *d_edges = nullptr;
+    void *d_ews = nullptr;
+    RP_HIP(B.alloc(reinterpret_cast<void **>(&d_s2), 8 * (mgc::scan_scratch_elems(n_bases + 1) + 8)));   // the scan of the lines per position
+    RP_HIP(B.alloc(&d_ews, 8 * mgc::compact_ws_elems(tiles)));                                           // the compaction of a table's edges
+    const mgc::CompactWs ew = mgc::compact_ws_at(d_ews, tiles);
     hipLaunchKernelGGL(mgc::runs_lines_kernel, dim3(lk_grid(std::min<uint64_t>(n_bases, 1u << 24))), dim3(256), 0, cs, d_val, (mgc::u64)n_bases, any_only, d_lines);
     RP_HIP(hipGetLastError());
-    RP_HIP(mgc::scan_u64_exclusive(d_lines, n_bases, d_s2, d_tiles + tiles + 1, cs));
+    RP_HIP(mgc::scan_u64_exclusive(d_lines, n_bases, d_s2, ew.total, cs));
     uint64_t n_lines = 0;
-    RP_HIP(hipMemcpyAsync(&n_lines, d_tiles + tiles + 1, 8, hipMemcpyDeviceToHost, cs));
+    RP_HIP(hipMemcpyAsync(&n_lines, ew.total, 8, hipMemcpyDeviceToHost, cs));
     RP_HIP(hipStreamSynchronize(cs));
     RP_HIP(B.alloc(reinterpret_cast<void **>(&d_bgn), 8 * n_lines));
     const uint32_t n_flag = any_only ? 1u : n_tables;
     for (uint32_t t = 0; t < n_flag && n_lines; t++) {
-      hipLaunchKernelGGL(mgc::runs_edge_count_kernel, dim3((uint32_t)tiles), dim3(256), 0, cs, d_val, (mgc::u64)n_bases, t, any_only, d_tiles);
-      RP_HIP(hipGetLastError());
-      RP_HIP(mgc::scan_u64_exclusive(d_tiles, tiles, d_s2, d_tiles + tiles + 1, cs));
+      hipLaunchKernelGGL(mgc::runs_edge_kernel<false>, dim3((uint32_t)tiles), dim3(256), 0, cs, d_val, (mgc::u64)n_bases, t, any_only, ew.tiles, (mgc::u64 *)nullptr);
+      RP_HIP(mgc::compact_scan(ew, cs));
       uint64_t n_edges = 0;
-      RP_HIP(hipMemcpyAsync(&n_edges, d_tiles + tiles + 1, 8, hipMemcpyDeviceToHost, cs));
+      RP_HIP(hipMemcpyAsync(&n_edges, ew.total, 8, hipMemcpyDeviceToHost, cs));
       RP_HIP(hipStreamSynchronize(cs));
       if (!n_edges) continue;
       if (n_edges > 2 * n_lines) { lk_err("mgc_lookup_report: a run of flags does not end inside the stream"); return MGC_EINVAL; }
       if (!d_edges) RP_HIP(B.alloc(reinterpret_cast<void **>(&d_edges), 8 * 2 * n_lines));   // every run is a line: enough for any table
-      hipLaunchKernelGGL(mgc::runs_edge_emit_kernel, dim3((uint32_t)tiles), dim3(256), 0, cs, d_val, (mgc::u64)n_bases, t, any_only, d_tiles, d_edges);
+      hipLaunchKernelGGL(mgc::runs_edge_kernel<true>, dim3((uint32_t)tiles), dim3(256), 0, cs, d_val, (mgc::u64)n_bases, t, any_only, ew.tiles, d_edges);
       RP_HIP(hipGetLastError());
       hipLaunchKernelGGL(mgc::runs_pair_kernel, dim3(lk_grid(std::min<uint64_t>(n_edges / 2, 1u << 24))), dim3(256), 0, cs, d_edges, (mgc::u64)(n_edges / 2),
                          d_val, (mgc::u64)n_bases, d_lines, t, any_only, d_bgn);

@@ -138,22 +138,19 @@ void merge_kernel(const K *__restrict__ A, const u32 *__restrict__ cA, u64 nA, c
   }
 }
 
-// workspace: [0] total (u64), [8..] tile counts (u64 x tiles), scan scratch
+// workspace: the contiguous CompactWs (mgc_common.hpp)
 static inline uint64_t merge_tiles(uint64_t na, uint64_t nb) { return (na + nb + MG_TILE - 1) / MG_TILE; }
 
-size_t merge_workspace_bytes(uint64_t na, uint64_t nb) {
-  const uint64_t t = merge_tiles(na, nb);
-  return (size_t)(8 + t + 1 + scan_scratch_elems(t + 1)) * sizeof(u64) + 256;
-}
+size_t merge_workspace_bytes(uint64_t na, uint64_t nb) { return compact_ws_elems(merge_tiles(na, nb)) * sizeof(u64) + 256; }
 
 // pass 1: leaves the output length at ws[0] (read it with merge_read_total after the stream is synchronised)
 hipError_t launch_merge_count(const void *dA, uint64_t na, const void *dB, uint64_t nb, uint32_t key_words, int op, void *d_ws,
                               hipStream_t st, const uint32_t *cA, const uint32_t *cB) {
   if (op < 0 || op >= MG_NUM_OPS || (op == 7 && ((na && !cA) || (nb && !cB)))) return hipErrorInvalidValue;
-  u64 *ws = reinterpret_cast<u64 *>(d_ws);
   const uint64_t t = merge_tiles(na, nb);
-  if (t == 0) return hipMemsetAsync(ws, 0, 8, st);
-  u64 *tiles = ws + 8, *scratch = tiles + t + 1;
+  if (t == 0) return hipMemsetAsync(d_ws, 0, 8, st);
+  const CompactWs w = compact_ws_at(d_ws, t);
+  u64 *tiles = w.tiles;
   if (key_words == 2)
     hipLaunchKernelGGL((merge_kernel<K128, false>), dim3((uint32_t)t), dim3(MG_BLOCK), 0, st, reinterpret_cast<const K128 *>(dA),
                        cA, (u64)na, reinterpret_cast<const K128 *>(dB), cB, (u64)nb, op, tiles,
@@ -162,8 +159,7 @@ hipError_t launch_merge_count(const void *dA, uint64_t na, const void *dB, uint6
     hipLaunchKernelGGL((merge_kernel<u64, false>), dim3((uint32_t)t), dim3(MG_BLOCK), 0, st, reinterpret_cast<const u64 *>(dA),
                        cA, (u64)na, reinterpret_cast<const u64 *>(dB), cB, (u64)nb, op, tiles,
                        (u64 *)nullptr, (u32 *)nullptr);
-  MGC_CHECK(hipGetLastError());
-  return scan_u64_exclusive(tiles, t, scratch, ws, st);
+  return compact_scan(w, st);
 }
 
 hipError_t merge_read_total(const void *d_ws, uint64_t *n_out, hipStream_t st) {
@@ -177,7 +173,7 @@ hipError_t launch_merge_emit(const void *dA, const uint32_t *cA, uint64_t na, co
                              uint32_t key_words, int op, void *d_ws, void *d_out_keys, uint32_t *d_out_counts, hipStream_t st) {
   const uint64_t t = merge_tiles(na, nb);
   if (t == 0) return hipSuccess;
-  u64 *tiles = reinterpret_cast<u64 *>(d_ws) + 8;
+  u64 *tiles = compact_ws_at(d_ws, t).tiles;
   if (key_words == 2)
     hipLaunchKernelGGL((merge_kernel<K128, true>), dim3((uint32_t)t), dim3(MG_BLOCK), 0, st, reinterpret_cast<const K128 *>(dA), cA,
                        (u64)na, reinterpret_cast<const K128 *>(dB), cB, (u64)nb, op, tiles, reinterpret_cast<K128 *>(d_out_keys),
@@ -297,10 +293,7 @@ __global__ void fill_u32_kernel(u32 *__restrict__ p, u64 n, u32 v) {
 }
 
 static inline uint64_t select_tiles(uint64_t n) { return (n + SL_TILE - 1) / SL_TILE; }
-size_t select_workspace_bytes(uint64_t n) {
-  const uint64_t t = select_tiles(n);
-  return (size_t)(8 + t + 1 + scan_scratch_elems(t + 1)) * sizeof(u64) + 256;
-}
+size_t select_workspace_bytes(uint64_t n) { return compact_ws_elems(select_tiles(n)) * sizeof(u64) + 256; }
 // the one place that names the instantiations: <K, false>, <K, true>, <K, true, true> and every <K, EMIT, LABELS, true>
 template <typename K, bool EMIT>
 static void sl_launch(PassInst pi, const SelectInput &in, const SelectProgram &program, int fop, uint64_t constant, uint64_t t, u64 *tiles, void *outK,
@@ -335,10 +328,10 @@ hipError_t launch_select(bool emit, const SelectInput &in, int fop, uint64_t con
   if (ruled && (r.lop < LOP_SET || r.lop > LOP_SEL_MAX || r.lop == 12)) return hipErrorInvalidValue;
   if (!select_program(&pg, r.select ? r.terms : nullptr, r.select ? r.n_terms : 0, r.select ? r.k : 1)) return hipErrorInvalidValue;
   const PassInst pi = pass_inst(emit, r.select, (pg.flags & SELF_LABELS) != 0, false, false, outL != nullptr);
-  u64 *ws = reinterpret_cast<u64 *>(d_ws);
   const uint64_t t = select_tiles(in.n);
-  if (t == 0) return emit ? hipSuccess : hipMemsetAsync(ws, 0, 8, st);
-  u64 *tiles = ws + 8, *scratch = tiles + t + 1;
+  if (t == 0) return emit ? hipSuccess : hipMemsetAsync(d_ws, 0, 8, st);
+  const CompactWs w = compact_ws_at(d_ws, t);
+  u64 *tiles = w.tiles;
   if (emit) {
     if (in.key_words == 2) sl_launch<K128, true>(pi, in, pg, fop, constant, t, tiles, d_out_keys, d_out_vals, r.lop, (u64)r.lc, outL, st);
     else sl_launch<u64, true>(pi, in, pg, fop, constant, t, tiles, d_out_keys, d_out_vals, r.lop, (u64)r.lc, outL, st);
@@ -346,8 +339,7 @@ hipError_t launch_select(bool emit, const SelectInput &in, int fop, uint64_t con
   }
   if (in.key_words == 2) sl_launch<K128, false>(pi, in, pg, fop, constant, t, tiles, nullptr, nullptr, r.lop, (u64)r.lc, nullptr, st);
   else sl_launch<u64, false>(pi, in, pg, fop, constant, t, tiles, nullptr, nullptr, r.lop, (u64)r.lc, nullptr, st);
-  MGC_CHECK(hipGetLastError());
-  return scan_u64_exclusive(tiles, t, scratch, ws, st);
+  return compact_scan(w, st);
 }
 hipError_t launch_fill_u32(uint32_t *d, uint64_t n, uint32_t v, hipStream_t st) {
   if (n == 0) return hipSuccess;

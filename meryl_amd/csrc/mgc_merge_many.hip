@@ -296,8 +296,8 @@ static inline uint64_t mm_tiles(uint64_t total, uint32_t key_words) {
   const uint64_t T = merge_many_tile(key_words);
   return (total + T - 1) / T;
 }
-// workspace: [0] total (u64), [8..] tile counts (u64 x (tiles + 1)), scan scratch, the borders (u64 x 32 x (tiles + 1))
-static inline size_t mm_splits_at(uint64_t t) { return (size_t)(8 + t + 1 + scan_scratch_elems(t + 1)); }
+// workspace: the contiguous CompactWs (mgc_common.hpp), then the borders (u64 x 32 x (tiles + 1))
+static inline size_t mm_splits_at(uint64_t t) { return compact_ws_elems(t); }
 
 size_t merge_many_workspace_bytes(const uint64_t *n, uint32_t n_inputs, uint32_t key_words) {
   const uint64_t t = mm_tiles(mm_total(n, n_inputs), key_words);
@@ -365,7 +365,8 @@ hipError_t launch_merge_many(bool emit, const MergeManyInputs &in, int op, const
   u64 *ws = reinterpret_cast<u64 *>(d_ws);
   const uint64_t total = mm_total(in.n, in.count), t = mm_tiles(total, in.key_words);
   if (t == 0) return emit ? hipSuccess : hipMemsetAsync(ws, 0, 8, st);
-  u64 *tiles = ws + 8, *scratch = tiles + t + 1, *splits = ws + mm_splits_at(t);
+  const CompactWs w = compact_ws_at(d_ws, t);
+  u64 *tiles = w.tiles, *splits = ws + mm_splits_at(t);
   if (emit) {
     if (in.key_words == 2) mm_launch<K128, true>(pi, d, pg, asg, op, t, splits, tiles, d_out_keys, d_out_vals, r.lop, (u64)r.lc, outL, st);
     else mm_launch<u64, true>(pi, d, pg, asg, op, t, splits, tiles, d_out_keys, d_out_vals, r.lop, (u64)r.lc, outL, st);
@@ -379,8 +380,7 @@ hipError_t launch_merge_many(bool emit, const MergeManyInputs &in, int op, const
     hipLaunchKernelGGL((merge_many_partition_kernel<u64>), dim3(pgrid), dim3(MM_BLOCK), 0, st, d, (u64)total, (u64)t, splits);
     mm_launch<u64, false>(pi, d, pg, asg, op, t, splits, tiles, nullptr, nullptr, r.lop, (u64)r.lc, nullptr, st);
   }
-  MGC_CHECK(hipGetLastError());
-  return scan_u64_exclusive(tiles, t, scratch, ws, st);
+  return compact_scan(w, st);
 }
 
 }  // namespace mgc

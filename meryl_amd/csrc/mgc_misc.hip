@@ -19,7 +19,7 @@
 // contiguous runs, ranking uses 64-lane ballots, cross-workgroup prefixes use 8-byte
 // {flag,epoch,value} granules with agent-scope relaxed atomics (no fences needed:
 // the datum is the flag).  Wave = 64 everywhere.
-#include "mgc_common.hpp"
+#include "mgc_compact.hpp"
 
 namespace mgc {
 
@@ -47,38 +47,29 @@ __device__ __forceinline__ u32 hp_keep_mask(const uint8_t *__restrict__ in, u64 
   return keep;
 }
 
+// Both passes.  Round 5: the kept bytes of a tile are packed in LDS first and leave as aligned dwords (a head and a tail of up to
+// three single bytes around them) -- one byte store per kept base and lane, sixteen per thread, each spread over ~700 bytes of the
+// output, was 5.0 ms per 5 Gbp (profiles/r05l kernel stats of the `compress` leg); the packed form writes 256 contiguous bytes per
+// wave instruction.
+template <bool EMIT>
 __global__ __launch_bounds__(HP_BLOCK)
-void hpc_count_kernel(const uint8_t *__restrict__ in, u64 n, u64 *__restrict__ tile_cnt) {
-  __shared__ u32 s_tmp[HP_BLOCK / 64 + 1];
-  const bool aligned = ((reinterpret_cast<uintptr_t>(in) & 15) == 0);
-  uint4 v;
-  const u32 keep = hp_keep_mask(in, n, (u64)blockIdx.x * HP_TILE + (u64)threadIdx.x * 16, aligned, v);
-  u32 tot;
-  (void)block_excl_scan<HP_BLOCK, u32>(__popc(keep), s_tmp, &tot);
-  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
-}
-
-// Round 5: the kept bytes of a tile are packed in LDS first and leave as aligned dwords (a head and a tail of up to three single
-// bytes around them) -- one byte store per kept base and lane, sixteen per thread, each spread over ~700 bytes of the output, was
-// 5.0 ms per 5 Gbp (profiles/r05l kernel stats of the `compress` leg); the packed form writes 256 contiguous bytes per wave instruction.
-__global__ __launch_bounds__(HP_BLOCK)
-void hpc_emit_kernel(const uint8_t *__restrict__ in, u64 n, const u64 *__restrict__ tile_offs, uint8_t *__restrict__ out) {
-  __shared__ u32 s_tmp[HP_BLOCK / 64 + 1];
-  __shared__ __attribute__((aligned(16))) uint8_t s_out[HP_TILE + 16];
+void hpc_kernel(const uint8_t *__restrict__ in, u64 n, u64 *__restrict__ tiles /*EMIT: exclusive bases*/, uint8_t *__restrict__ out) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_out[HP_TILE + 16];      // (the count pass never touches it)
   const bool aligned = ((reinterpret_cast<uintptr_t>(in) & 15) == 0);
   const u32 tid = threadIdx.x;
   uint4 v;
   const u32 keep = hp_keep_mask(in, n, (u64)blockIdx.x * HP_TILE + (u64)tid * 16, aligned, v);
   u32 tot;
-  const u32 base = block_excl_scan<HP_BLOCK, u32>(__popc(keep), s_tmp, &tot);
+  u64 slot;
+  if (!compact_slot<HP_BLOCK, EMIT>(__popc(keep), tiles, &slot, &tot)) return;
+  const u64 g0 = tiles[blockIdx.x];                         // where the tile's kept bytes go
   const u32 w[4] = { v.x, v.y, v.z, v.w };
-  u32 o = base;
+  u32 o = (u32)(slot - g0);
 #pragma unroll
   for (int i = 0; i < 16; i++)
     if ((keep >> i) & 1u) s_out[o++] = (uint8_t)((w[i >> 2] >> (8 * (i & 3))) & 0xFFu);
   // (a funnel shift below may read the word that holds the last kept byte and garbage behind it: those bits are shifted out)
   __syncthreads();
-  const u64 g0 = tile_offs[blockIdx.x];                     // where the tile's kept bytes go
   uint8_t *dst = out + g0;
   const u32 mis = (u32)(reinterpret_cast<uintptr_t>(dst) & 3u);
   u32 head = mis ? 4u - mis : 0u;
@@ -95,21 +86,15 @@ void hpc_emit_kernel(const uint8_t *__restrict__ in, u64 n, const u64 *__restric
   if (tid < tot - tail0) dst[tail0 + tid] = s_out[tail0 + tid];
 }
 
-size_t hpc_workspace_bytes(uint64_t n) {
-  const uint64_t t = (n + HP_TILE - 1) / HP_TILE;
-  return (size_t)(8 + t + 1 + scan_scratch_elems(t + 1)) * sizeof(uint64_t);
-}
+size_t hpc_workspace_bytes(uint64_t n) { return compact_ws_elems((n + HP_TILE - 1) / HP_TILE) * sizeof(uint64_t); }
 
 // d_ws[0] receives the compressed length (device); the caller reads it back.
 hipError_t launch_homopoly_compress(const uint8_t *d_in, uint64_t n, uint8_t *d_out, void *d_ws, hipStream_t st) {
-  u64 *total = reinterpret_cast<u64 *>(d_ws);
-  if (n == 0) return hipMemsetAsync(total, 0, sizeof(u64), st);
-  const uint64_t t = (n + HP_TILE - 1) / HP_TILE;
-  u64 *tile_offs = total + 8, *scratch = tile_offs + t + 1;
-  hipLaunchKernelGGL(hpc_count_kernel, dim3((uint32_t)t), dim3(HP_BLOCK), 0, st, d_in, (u64)n, tile_offs);
-  MGC_CHECK(hipGetLastError());
-  MGC_CHECK(scan_u64_exclusive(tile_offs, t, scratch, total, st));
-  hipLaunchKernelGGL(hpc_emit_kernel, dim3((uint32_t)t), dim3(HP_BLOCK), 0, st, d_in, (u64)n, (const u64 *)tile_offs, d_out);
+  if (n == 0) return hipMemsetAsync(d_ws, 0, sizeof(u64), st);
+  const CompactWs w = compact_ws_at(d_ws, (n + HP_TILE - 1) / HP_TILE);
+  hipLaunchKernelGGL(hpc_kernel<false>, dim3((uint32_t)w.t), dim3(HP_BLOCK), 0, st, d_in, (u64)n, w.tiles, (uint8_t *)nullptr);
+  MGC_CHECK(compact_scan(w, st));
+  hipLaunchKernelGGL(hpc_kernel<true>, dim3((uint32_t)w.t), dim3(HP_BLOCK), 0, st, d_in, (u64)n, w.tiles, d_out);
   return hipGetLastError();
 }
 
