@@ -14,13 +14,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmeryl_gpu_count.so")
 SOURCES = ["mgc_kmer.hip", "mgc_sort.hip", "mgc_scan.hip", "mgc_finish.hip", "mgc_misc.hip", "mgc_parse.hip",
-           "mgc_encode.hip", "mgc_decode.hip", "mgc_merge.hip", "mgc_merge_many.hip", "mgc_lookup.hip", "mgc_filter.hip", "mgc_import.hip", "mgc_analyze.hip", "mgc_value_hist.hip",
-           "mgc_api.cpp", "mgc_textfile.cpp", "mgc_import.cpp", "mgc_analyze.cpp", "mgc_count.cpp", "mgc_stream.cpp", "mgc_eval.cpp", "mgc_runs.cpp", "mgc_node.cpp", "meryl_db.cpp", "meryl_seq.cpp"]
-HEADERS = ["mgc_device.h", "mgc_common.hpp", "mgc_compact.hpp", "mgc_bases.hpp", "mdb_layout.h", "mdb_statistics.hpp", "mgc_session.hpp", "mgc_clock.hpp", "mgc_chunk_ring.hpp", "mgc_bgzf.hpp", "mgc_runs.hpp", "mgc_lookup_dev.hpp", "mgc_import_dev.hpp", "mgc_analyze_dev.hpp", "mgc_label.hpp", "mgc_selector.hpp", "mgc_value.hpp", "mgc_route.hpp", "mgc_group_route.hpp",
+           "mgc_encode.hip", "mgc_decode.hip", "mgc_merge.hip", "mgc_merge_many.hip", "mgc_lookup.hip", "mgc_filter.hip", "mgc_import.hip", "mgc_analyze.hip", "mgc_value_hist.hip", "mgc_positions.hip",
+           "mgc_api.cpp", "mgc_textfile.cpp", "mgc_import.cpp", "mgc_analyze.cpp", "mgc_positions.cpp", "mgc_count.cpp", "mgc_stream.cpp", "mgc_eval.cpp", "mgc_runs.cpp", "mgc_node.cpp", "meryl_db.cpp", "meryl_seq.cpp"]
+HEADERS = ["mgc_device.h", "mgc_common.hpp", "mgc_compact.hpp", "mgc_bases.hpp", "mdb_layout.h", "mdb_statistics.hpp", "mgc_session.hpp", "mgc_clock.hpp", "mgc_chunk_ring.hpp", "mgc_bgzf.hpp", "mgc_runs.hpp", "mgc_lookup_dev.hpp", "mgc_import_dev.hpp", "mgc_analyze_dev.hpp", "mgc_positions_dev.hpp", "mgc_fastx.hpp", "mgc_label.hpp", "mgc_selector.hpp", "mgc_value.hpp", "mgc_route.hpp", "mgc_group_route.hpp",
            os.path.join("..", "..", "include", "meryl_gpu_count.h"),
            os.path.join("..", "..", "include", "meryl_db.h"), os.path.join("..", "..", "include", "meryl_seq.h"),
            os.path.join("..", "..", "include", "meryl_lookup.h"), os.path.join("..", "..", "include", "meryl_import.h"),
-           os.path.join("..", "..", "include", "meryl_analyze.h")]
+           os.path.join("..", "..", "include", "meryl_analyze.h"), os.path.join("..", "..", "include", "meryl_positions.h")]
 OBJDIR = os.path.join(HERE, "build")
 # -no-hip-rt: the library carries no DT_NEEDED on a particular libamdhip64; it binds to the
 # HIP runtime already in the process (torch's bundled one under Python -- two HIP/HSA runtimes
@@ -62,9 +62,13 @@ def _stale_objects(force=False):
 
 
 def _stale():
-    if not os.path.exists(LIB) or _stale_objects():
+    if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
+    if max([_header_mtime()] + [os.path.getmtime(os.path.join(CSRC, f)) for f in _sources()]) <= t:
+        return False                                      # newer than every source and header: current, with or without its objects
+    if _stale_objects():
+        return True
     return any(os.path.getmtime(_obj(f)) > t for f in _sources())
 
 
@@ -72,12 +76,14 @@ CLI = os.path.join(HERE, "bin", "meryl")
 LOOKUP_CLI = os.path.join(HERE, "bin", "meryl-lookup")
 IMPORT_CLI = os.path.join(HERE, "bin", "meryl-import")
 ANALYZE_CLI = os.path.join(HERE, "bin", "meryl-analyze")
+POSITION_LOOKUP_CLI = os.path.join(HERE, "bin", "position-lookup")
 
 
-def _build_front_end(source, out, force, verbose):
-    """One front end (meryl_amd/bin/*): links the library and the system HIP runtime."""
+def _build_front_end(source, out, force, verbose, headers=()):
+    """One front end (meryl_amd/bin/*): links the library and the system HIP runtime.  headers: what it includes from csrc/."""
     src = os.path.join(CSRC, source)
-    if (not force and os.path.exists(out) and os.path.getmtime(out) >= os.path.getmtime(src)
+    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in (source,) + tuple(headers))
+    if (not force and os.path.exists(out) and os.path.getmtime(out) >= newest
             and os.path.getmtime(out) >= os.path.getmtime(LIB)):
         return out
     os.makedirs(os.path.dirname(out), exist_ok=True)
@@ -99,7 +105,7 @@ def build_cli(force=False, verbose=False):
 
 def build_lookup_cli(force=False, verbose=False):
     """`meryl-lookup` (meryl_amd/bin/meryl-lookup: -existence and the position reports)."""
-    return _build_front_end("meryl_lookup_main.cpp", LOOKUP_CLI, force, verbose)
+    return _build_front_end("meryl_lookup_main.cpp", LOOKUP_CLI, force, verbose, ("mgc_fastx.hpp",))
 
 
 def build_import_cli(force=False, verbose=False):
@@ -112,6 +118,11 @@ def build_analyze_cli(force=False, verbose=False):
     return _build_front_end("meryl_analyze_main.cpp", ANALYZE_CLI, force, verbose)
 
 
+def build_position_lookup_cli(force=False, verbose=False):
+    """`position-lookup` (meryl_amd/bin/position-lookup: -hpq / -mpb / -qpb of query sequences against a reference)."""
+    return _build_front_end("position_lookup_main.cpp", POSITION_LOOKUP_CLI, force, verbose, ("mgc_fastx.hpp",))
+
+
 def build(force=False, verbose=False):
     """Compile every HIP/C++ source for gfx950 (one object per source, rebuilt only when the source or a
     header changed, in parallel) and link libmeryl_gpu_count.so (and the CLI).  Returns the library path."""
@@ -120,6 +131,7 @@ def build(force=False, verbose=False):
         build_lookup_cli(False, verbose)
         build_import_cli(False, verbose)
         build_analyze_cli(False, verbose)
+        build_position_lookup_cli(False, verbose)
         return LIB
     os.makedirs(OBJDIR, exist_ok=True)
     todo = _stale_objects(force)
@@ -148,6 +160,7 @@ def build(force=False, verbose=False):
     build_lookup_cli(True, verbose)
     build_import_cli(True, verbose)
     build_analyze_cli(True, verbose)
+    build_position_lookup_cli(True, verbose)
     return LIB
 
 

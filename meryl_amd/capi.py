@@ -1,4 +1,4 @@
-"""ctypes binding of include/meryl_gpu_count.h (and meryl_db.h, meryl_lookup.h, meryl_seq.h, meryl_import.h, meryl_analyze.h).
+"""ctypes binding of include/meryl_gpu_count.h (and meryl_db.h, meryl_lookup.h, meryl_positions.h, meryl_seq.h, meryl_import.h, meryl_analyze.h).
 
 Loads meryl_amd/libmeryl_gpu_count.so and fails loudly when it is missing or
 an expected symbol is absent -- there is no Python/CPU fallback for any compute
@@ -45,6 +45,9 @@ SYMBOLS = (
     # include/meryl_lookup.h
     "mgc_lookup_load", "mgc_lookup_estimate", "mgc_lookup_from_device", "mgc_lookup_free", "mgc_lookup_get_info", "mgc_lookup_error",
     "mgc_lookup_values", "mgc_lookup_stream", "mgc_lookup_existence", "mgc_lookup_positions", "mgc_lookup_report", "mgc_lookup_filter_text", "mgc_lookup_filter_files",
+    # include/meryl_positions.h
+    "mgc_posidx_build", "mgc_posidx_free", "mgc_posidx_get_info", "mgc_posidx_arrays", "mgc_posidx_find",
+    "mgc_paint_open", "mgc_paint_close", "mgc_paint_add", "mgc_paint_get",
     # include/meryl_seq.h
     # include/meryl_import.h
     "mgc_dev_import_parse_state_bytes", "mgc_dev_import_parse_workspace_bytes", "mgc_dev_import_parse_begin", "mgc_dev_import_parse_count",
@@ -274,6 +277,16 @@ class RunsProfile(ctypes.Structure):
 class LookupInfo(ctypes.Structure):
     _fields_ = [("k", ctypes.c_uint32), ("key_words", ctypes.c_uint32), ("index_bits", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
                 ("n_kmers", ctypes.c_uint64), ("n_kmers_in_db", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64)]
+
+
+class PosIndexInfo(ctypes.Structure):
+    """mgc_posidx_info (include/meryl_positions.h)"""
+    _fields_ = [("k", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("n_kmers", ctypes.c_uint64), ("n_ref_bases", ctypes.c_uint64),
+                ("n_placed", ctypes.c_uint64), ("n_slots_used", ctypes.c_uint64), ("longest_list", ctypes.c_uint64),
+                ("device_bytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
 class FilterResult(ctypes.Structure):
@@ -550,6 +563,15 @@ def lib():
     sig("mgc_lookup_filter_text", i32, vp, i32, u32, u32, P(vp), P(u64), i32, P(vp), P(u64), P(FilterResult), vp)
     sig("mgc_lookup_filter_files", i32, vp, i32, u32, ctypes.c_char_p, ctypes.c_char_p, u64, LOOKUP_WRITE_CB, vp, LOOKUP_WRITE_CB, vp,
         P(FilterResult))
+    sig("mgc_posidx_build", vp, vp, vp, u64, vp)
+    sig("mgc_posidx_free", None, vp)
+    sig("mgc_posidx_get_info", i32, vp, P(PosIndexInfo))
+    sig("mgc_posidx_arrays", i32, vp, P(vp), P(vp), P(vp))
+    sig("mgc_posidx_find", i32, vp, vp, u64, vp, vp, vp)
+    sig("mgc_paint_open", vp, vp, u32)
+    sig("mgc_paint_close", None, vp)
+    sig("mgc_paint_add", i32, vp, vp, u64, vp, u64, vp, vp, vp)
+    sig("mgc_paint_get", i32, vp, u32, vp, vp)
     sig("mgc_dev_import_parse_state_bytes", sz)
     sig("mgc_dev_import_parse_workspace_bytes", sz, u64)
     sig("mgc_dev_import_parse_begin", i32, vp, vp)

@@ -36,45 +36,11 @@ namespace {
   exit(1);
 }
 
-// names and bases of a FASTA/FASTQ text (multi-line FASTA, four-line FASTQ; the reference reads both through
-// dnaSeqFile::loadSequence, meryl-utility)
-struct Seqs { std::vector<std::string> names; std::vector<uint64_t> start; std::string bases; };
+}  // namespace
 
-void parse_text(const std::string &text, Seqs &out) {
-  size_t p = 0;
-  const size_t n = text.size();
-  auto line = [&](size_t &a, size_t &b) {                   // next line [a, b) without its terminator; false at the end
-    if (p >= n) return false;
-    a = p;
-    while (p < n && text[p] != '\n') p++;
-    b = p;
-    if (p < n) p++;
-    if (b > a && text[b - 1] == '\r') b--;
-    return true;
-  };
-  size_t a, b;
-  bool have = line(a, b);
-  while (have) {
-    if (b == a) { have = line(a, b); continue; }
-    const char c = text[a];
-    if (c != '>' && c != '@') die("ERROR: sequence file: a record starts with '%s', neither '>' nor '@'.", std::string(1, c).c_str());
-    size_t e = a + 1;
-    while (e < b && text[e] != ' ' && text[e] != '\t') e++;
-    out.names.push_back(text.substr(a + 1, e - a - 1));       // the identifier: first word of the header (dnaSeq::ident())
-    out.start.push_back(out.bases.size());
-    if (c == '>') {
-      while ((have = line(a, b)) && !(b > a && text[a] == '>')) out.bases.append(text, a, b - a);
-    } else {
-      if ((have = line(a, b))) out.bases.append(text, a, b - a);
-      if ((have = line(a, b))) {                              // '+' line
-        if ((have = line(a, b))) have = line(a, b);           // quality line, then the next record
-      }
-    }
-    out.bases.push_back('.');
-  }
-  out.start.push_back(out.bases.size());
-}
+#include "mgc_fastx.hpp"               // Seqs, parse_text, read_fastx_text (they call die)
 
+namespace {
 enum Op { OP_NONE, OP_EXISTENCE, OP_BED, OP_BED_RUNS, OP_WIG_COUNT, OP_WIG_DEPTH, OP_INCLUDE, OP_EXCLUDE };
 
 const char *op_name(Op op) {                                  // toString(lookupOp), meryl-lookup.H:38-50 (-bed-runs is opBED)
@@ -206,18 +172,8 @@ int main(int argc, char **argv) {
     return 0;
   }
 
-  msr_reader *r = msr_open(seq_name.c_str());
-  if (!r) die("ERROR: %s", msr_last_error());
-  if (msr_format(r) != MSR_FORMAT_FASTX) die("ERROR: '%s' is not FASTA/FASTQ text.", seq_name.c_str());
   std::string text;
-  std::vector<char> buf(16u << 20);
-  for (;;) {
-    const int64_t got = msr_read_text(r, buf.data(), buf.size());
-    if (got < 0) die("ERROR: %s", msr_last_error());
-    if (got == 0) break;
-    text.append(buf.data(), (size_t)got);
-  }
-  msr_close(r);
+  read_fastx_text(seq_name, text);
   Seqs sq;
   parse_text(text, sq);
   std::string().swap(text);

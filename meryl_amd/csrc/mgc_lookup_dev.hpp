@@ -47,6 +47,23 @@ __device__ __forceinline__ u32 lk_find(const K *__restrict__ keys, const u32 *__
   return (lo < end && !KeyOps<K>::ne(keys[lo], q)) ? vals[lo] : 0u;
 }
 
+// The same search for the position index (mgc_positions.hip): the k-mer's rank in the table -- merylExactLookup::index() --
+// or LK_NO_SLOT.  A sibling of lk_find and not its body: lk_find stays as it is compiled into the timed lookup kernels.
+constexpr u32 LK_NO_SLOT = 0xFFFFFFFFu;             // (tables of the position index hold at most 2^32 - 2 k-mers)
+template <typename K>
+__device__ __forceinline__ u32 lk_find_slot(const K *__restrict__ keys, const u64 *__restrict__ index, u32 shift, K q, u64 n_index) {
+  const u64 p = LkOps<K>::bucket(q, shift);
+  if (p >= n_index) return LK_NO_SLOT;
+  u64 lo = index[p];
+  const u64 end = index[p + 1];
+  u64 hi = end;
+  while (lo < hi) {
+    const u64 mid = lo + ((hi - lo) >> 1);
+    if (KeyOps<K>::lt(keys[mid], q)) lo = mid + 1; else hi = mid;
+  }
+  return (lo < end && !KeyOps<K>::ne(keys[lo], q)) ? (u32)lo : LK_NO_SLOT;
+}
+
 // 2-bit code of a base (A0 C1 T2 G3, reference.rst:525), -1 for anything else
 __device__ __forceinline__ int lk_code(u32 c) {
   const u32 l = c | 0x20u;
