@@ -458,6 +458,11 @@ int mgc_dev_merge_many_emit_assigned(const void *const *d_keys, const uint32_t *
                                      uint32_t n_terms, void *d_workspace, size_t workspace_bytes, void *d_keys_out,
                                      uint32_t *d_values_out, uint64_t *d_labels_out, void *stream);
 
+/* What the library's owning device buffers hold in this process right now: bytes and buffers (either may be NULL).  The
+ * session arena, the run store's parked runs and pinned memory are not counted.  For tests and leak hunts: it is exact and
+ * process-local, where hipMemGetInfo is device-wide.  Always MGC_OK. */
+int mgc_dev_buffers_live(uint64_t *bytes, uint64_t *buffers);
+
 /* Database blocks decoded on the device (mgc_decode.hip): d_file = the bytes of one data file followed by 16 bytes of slack,
  * d_blocks = the mdb_raw_block array of include/meryl_db.h (mdb_reader_raw_file gives both, validated against the file
  * size), suffix_size / label_size as the database's mdb_info has them.  d_keys / d_values / d_labels receive the k-mers of

@@ -27,7 +27,7 @@ SYMBOLS = (
     "mgc_dev_merge_workspace_bytes", "mgc_dev_merge_count", "mgc_dev_merge_count_values", "mgc_dev_merge_emit",
     "mgc_dev_merge_many_tile", "mgc_dev_merge_many_workspace_bytes", "mgc_dev_merge_many_count", "mgc_dev_merge_many_emit",
     "mgc_dev_select_workspace_bytes", "mgc_dev_select_count", "mgc_dev_select_emit",
-    "mgc_label_default_constant", "mgc_dev_merge_many_emit_labelled", "mgc_dev_select_emit_labelled", "mgc_dev_decode_blocks",
+    "mgc_label_default_constant", "mgc_dev_merge_many_emit_labelled", "mgc_dev_select_emit_labelled", "mgc_dev_decode_blocks", "mgc_dev_buffers_live",
     "mgc_select_parse", "mgc_select_check", "mgc_dev_merge_many_count_selected", "mgc_dev_merge_many_emit_selected",
     "mgc_dev_select_count_selected", "mgc_dev_select_emit_selected",
     "mgc_value_default_constant", "mgc_value_assign_parse", "mgc_dev_merge_many_count_assigned", "mgc_dev_merge_many_emit_assigned",
@@ -450,6 +450,7 @@ def lib():
     sig("mgc_dev_select_count_selected", i32, vp, vp, vp, u64, u32, u32, i32, u64, i32, u64, P(SelectTerm), u32, vp, sz, P(u64), vp)
     sig("mgc_dev_select_emit_selected", i32, vp, vp, vp, u64, u32, u32, i32, u64, i32, u64, P(SelectTerm), u32, vp, sz, vp, vp, vp, vp)
     sig("mgc_dev_decode_blocks", i32, vp, vp, u64, u32, u32, u32, vp, vp, vp, vp)
+    sig("mgc_dev_buffers_live", i32, P(u64), P(u64))
     sig("mgc_db_filter", i32, ctypes.c_char_p, i32, u64, ctypes.c_char_p, i32, i32)
     sig("mgc_dev_homopoly_workspace_bytes", sz, u64)
     sig("mgc_dev_homopoly_compress", i32, vp, u64, vp, P(u64), vp, sz, vp)

@@ -8,6 +8,7 @@
 #include "../../include/meryl_analyze.h"
 #include "../../include/meryl_db.h"
 #include "mgc_analyze_dev.hpp"
+#include "mgc_dbfile.hpp"
 #include "mgc_device.h"
 #include "mgc_runs.hpp"
 
@@ -47,23 +48,22 @@ struct Row { uint64_t key, n; };            // key = analyze_pack(histogram, sco
 }  // namespace
 
 struct mgc_analyze {
-  typedef mgc_runs::DBuf DBuf;
+  typedef mgc::DBuf DBuf;
   uint32_t k = 0, kw = 1, dense = MGC_ANALYZE_DENSE_VALUES, n_cus = 1;
   int type = 0, device = -1;
   bool ready = false;
   hipStream_t st_own = nullptr;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   DBuf d_dense, d_ctr, d_list[2], d_sws, d_rws, d_uniq, d_ucnt;       // the accumulator
-  DBuf d_file, d_blocks, d_keys, d_vals;                              // one database file
+  mgc::DbFileScratch file_scratch;                                    // one database file
+  DBuf d_keys, d_vals;
   std::vector<Row> ovf;                     // what went through the overflow list, ascending by key
   std::vector<Row> rows[3];                 // result cache per histogram
   bool rows_ok[3] = {false, false, false};
   mgc_analyze_info info;
 
-  ~mgc_analyze() {
-    if (!ready) return;
-    (void)hipSetDevice(device);
-    for (DBuf *b : {&d_dense, &d_ctr, &d_list[0], &d_list[1], &d_sws, &d_rws, &d_uniq, &d_ucnt, &d_file, &d_blocks, &d_keys, &d_vals}) b->release();
+  ~mgc_analyze() {                          // (the buffers go after this body, on the device it selects)
+    if (st_own) (void)hipSetDevice(device);               // (init got as far as the device)
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     if (st_own) (void)hipStreamDestroy(st_own);
   }
@@ -178,48 +178,29 @@ struct mgc_analyze {
   }
 
   // ---- the database loop ----------------------------------------------------------------------------------------
-  struct Slot {
-    unsigned char *bytes = nullptr; mdb_raw_block *blocks = nullptr;
-    uint64_t size = 0, nb = 0, n = 0;
-    std::vector<uint64_t> hk;               // host-decoded keys (kw words each) when the raw framing is not the device decoder's
-    uint32_t *hc = nullptr;
-    bool raw = false, done = false;
-    int rc = MGC_OK;
-    std::string msg;
-    void drop() { mdb_free(bytes); mdb_free(blocks); mdb_free(hc); bytes = nullptr; blocks = nullptr; hc = nullptr; hk.clear(); hk.shrink_to_fit(); }
-  };
+  struct Slot { mgc::DbFile f; bool done = false; };
 
   int one_file(Slot &s, const mdb_info &inf) {
-    if (s.n == 0) return MGC_OK;
+    const uint64_t n = s.f.n;
+    if (n == 0) return MGC_OK;
     hipStream_t st = st_own;
-    AN_TRY(d_keys.ensure(8 * (size_t)kw * s.n));
-    AN_TRY(d_vals.ensure(4 * s.n));
+    AN_TRY(d_keys.ensure(8 * (size_t)kw * n));
+    AN_TRY(d_vals.ensure(4 * n));
     AN_TRY(hipEventRecord(ev[3], st));
     uint32_t h_err = 0;
-    if (s.raw) {
-      uint32_t *d_err = reinterpret_cast<uint32_t *>(d_ctr.as<unsigned char>() + 128);
-      AN_TRY(d_file.ensure(s.size + 16));
-      AN_TRY(d_blocks.ensure(sizeof(mdb_raw_block) * s.nb));
-      AN_TRY(hipMemsetAsync(d_err, 0, 4, st));
-      AN_TRY(hipMemcpyAsync(d_file.p, s.bytes, s.size + 16, hipMemcpyHostToDevice, st));
-      AN_TRY(hipMemcpyAsync(d_blocks.p, s.blocks, sizeof(mdb_raw_block) * s.nb, hipMemcpyHostToDevice, st));
-      AN_TRY(mgc::launch_decode_blocks(d_file.p, d_blocks.p, s.nb, inf.suffix_size, inf.label_size, kw, d_keys.p, d_vals.as<uint32_t>(), d_err, st));
-      AN_TRY(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
-    } else {
-      AN_TRY(hipMemcpyAsync(d_keys.p, s.hk.data(), 8 * (size_t)kw * s.n, hipMemcpyHostToDevice, st));
-      AN_TRY(hipMemcpyAsync(d_vals.p, s.hc, 4 * s.n, hipMemcpyHostToDevice, st));
-    }
+    AN_TRY(mgc::dbfile_upload(s.f, inf, kw, file_scratch, d_keys.p, d_vals.as<uint32_t>(), nullptr, &h_err, st));
     AN_TRY(hipEventRecord(ev[4], st));
     AN_TRY(hipStreamSynchronize(st));                       // the host copies may go
-    if (h_err) { set_err(nullptr, "meryl-analyze: corrupt block in a database file (device decoder, code %u)", h_err); return MGC_EINVAL; }
+    std::string msg;
+    if (mgc::dbfile_decode_rc(h_err, &msg) != MGC_OK) { set_err(nullptr, "meryl-analyze: %s", msg.c_str()); return MGC_EINVAL; }
     float ms = 0;
     AN_TRY(hipEventElapsedTime(&ms, ev[3], ev[4])); info.decode_ms += ms;
-    s.drop();
-    return add(d_keys.p, d_vals.as<uint32_t>(), s.n, st);
+    s.f.drop();
+    return add(d_keys.p, d_vals.as<uint32_t>(), n, st);
   }
 
   int add_database(const char *path, const mdb_info &inf, int host_threads) {
-    const bool host_decode = getenv("MGC_DECODE_HOST") && getenv("MGC_DECODE_HOST")[0] == '1';      // (tests) read once per call
+    const bool host_decode = mgc::decode_on_host();         // (tests) read once per call
     const uint32_t nf = MGC_NUM_FILES;
     const int nth = std::max(1, std::min(host_threads <= 0 ? 4 : host_threads, 16));
     const uint32_t ahead = (uint32_t)nth + 1;               // files read but not yet consumed
@@ -241,22 +222,8 @@ struct mgc_analyze {
         }
         Slot &s = slot[ff];
         const double t0 = now_s();
-        if (!r) { s.rc = MGC_EINVAL; s.msg = mdb_last_error(); }
-        else {
-          int rc = host_decode ? MGC_EUNSUPPORTED : mdb_reader_raw_file(r, ff, &s.bytes, &s.size, &s.blocks, &s.nb, &s.n);
-          if (rc == MGC_OK) s.raw = true;
-          else if (rc == MGC_EUNSUPPORTED) {
-            uint64_t *lo = nullptr, *hi = nullptr;
-            rc = mdb_reader_read_file_ex(r, ff, &lo, &hi, &s.hc, nullptr, &s.n);
-            if (rc == MGC_OK) {
-              s.hk.resize((size_t)kw * s.n);
-              if (kw == 1) { if (s.n) memcpy(s.hk.data(), lo, 8 * s.n); }
-              else for (uint64_t j = 0; j < s.n; j++) { s.hk[2 * j] = lo[j]; s.hk[2 * j + 1] = hi[j]; }
-            }
-            mdb_free(lo); mdb_free(hi);
-          }
-          if (rc != MGC_OK) { s.rc = rc; s.msg = mdb_last_error(); }
-        }
+        if (!r) { s.f.rc = MGC_EINVAL; s.f.msg = mdb_last_error(); }
+        else mgc::dbfile_read(r, ff, kw, host_decode, false, &s.f);
         const double dt = now_s() - t0;
         { std::lock_guard<std::mutex> g(mu); s.done = true; read_s += dt; }
         cv.notify_all();
@@ -272,16 +239,15 @@ struct mgc_analyze {
         cv.wait(lk, [&] { return slot[ff].done; });
       }
       Slot &s = slot[ff];
-      if (s.rc != MGC_OK) { set_err(nullptr, "meryl-analyze: '%s': %s", path, s.msg.c_str()); rc = s.rc; }
+      if (s.f.rc != MGC_OK) { set_err(nullptr, "meryl-analyze: '%s': %s", path, s.f.msg.c_str()); rc = s.f.rc; }
       else { rc = one_file(s, inf); info.n_files++; }
-      s.drop();
+      s.f.drop();
       { std::lock_guard<std::mutex> g(mu); consumed = ff + 1; }
       cv.notify_all();
     }
     { std::lock_guard<std::mutex> g(mu); stop = true; }
     cv.notify_all();
     for (auto &t : pool) t.join();
-    for (Slot &s : slot) s.drop();
     info.read_s += read_s;
     return rc;
   }

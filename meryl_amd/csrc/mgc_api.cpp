@@ -571,20 +571,25 @@ extern "C" int mgc_dev_select_emit_selected(const void *d_keys, const uint32_t *
                                    (hipStream_t)stream), "select_emit_selected");
 }
 
+extern "C" int mgc_dev_buffers_live(uint64_t *bytes, uint64_t *buffers) {
+  if (bytes) *bytes = mgc::dbuf_live().bytes.load(std::memory_order_relaxed);
+  if (buffers) *buffers = mgc::dbuf_live().buffers.load(std::memory_order_relaxed);
+  return MGC_OK;
+}
+
 extern "C" int mgc_dev_decode_blocks(const void *d_file, const void *d_blocks, uint64_t n_blocks, uint32_t suffix_size, uint32_t label_size,
                                      uint32_t key_words, void *d_keys, uint32_t *d_values, uint64_t *d_labels, void *stream) {
   if ((key_words != 1 && key_words != 2) || label_size > 64 || suffix_size > 64 * key_words ||
       (n_blocks && (!d_file || !d_blocks || !d_keys || !d_values))) return MGC_EINVAL;
   if (n_blocks == 0) return MGC_OK;
   hipStream_t st = (hipStream_t)stream;
-  uint32_t *d_err = nullptr, h_err = 0;
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_err), 256);
-  if (e != hipSuccess) return hip_rc(e, "decode_blocks");
-  e = hipMemsetAsync(d_err, 0, 4, st);
-  if (e == hipSuccess) e = mgc::launch_decode_blocks(d_file, d_blocks, n_blocks, suffix_size, label_size, key_words, d_keys, d_values, d_err, st, d_labels);
-  if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st);
+  mgc::DBuf d_err;
+  uint32_t h_err = 0;
+  hipError_t e = d_err.ensure(256);
+  if (e == hipSuccess) e = hipMemsetAsync(d_err.p, 0, 4, st);
+  if (e == hipSuccess) e = mgc::launch_decode_blocks(d_file, d_blocks, n_blocks, suffix_size, label_size, key_words, d_keys, d_values, d_err.as<uint32_t>(), st, d_labels);
+  if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err.p, 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(d_err);
   if (e != hipSuccess) return hip_rc(e, "decode_blocks");
   if (h_err) { set_err(nullptr, "mgc_dev_decode_blocks: corrupt block (device decoder, code %u)", h_err); return MGC_EINVAL; }
   return MGC_OK;

@@ -4,19 +4,12 @@
 #include "mgc_session.hpp"
 
 #include <algorithm>
-#include <deque>
 #include <vector>
 
 #define TRY(expr) do { const int rc__ = (expr); if (rc__ != MGC_OK) return rc__; } while (0)
 
 namespace {
 using S = mgc_session;
-
-struct DevBuf {                                   // frees on scope exit
-  void *p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 256); }
-};
 
 struct StageTimer {
   bool on;
@@ -339,7 +332,7 @@ struct Count {
   uint32_t *d_large = nullptr, *d_nz = nullptr;
   const size_t hdr_bytes = mgc::sort_header_bytes();
   unsigned char *d_nws = nullptr, *d_nhdrs = nullptr;
-  std::deque<DevBuf> cnt_extra;                          // (a deque: DevBuf owns its pointer and must not be relocated)
+  std::vector<mgc::DBuf> cnt_extra;
   bool fork_huge = false, forked = false, need_join = false;   // forked: stream2 is ordered after everything st holds that it must see
   static constexpr int NH = 1 + S::HUGE_EXTRA;
   hipStream_t hstream[NH] = {};
@@ -826,7 +819,7 @@ int Count::widen_back(uint32_t b, bool *unordered) {
   // (the coarser plan's oversized list was cut at ITS capacity: the whole-key kernels would miss the sub-buckets in between)
   if (x.stream) { x.stream = false; *unordered = true; }
   cnt_extra.emplace_back();        // the back half of its region holds k-mers again: counts of its own
-  HIP_TRY(s, cnt_extra.back().alloc(sizeof(uint32_t) * x.size));
+  HIP_TRY(s, cnt_extra.back().ensure(sizeof(uint32_t) * x.size));
   x.cnt = reinterpret_cast<uint32_t *>(cnt_extra.back().p);
   return MGC_OK;
 }

@@ -1,4 +1,5 @@
-// mgc_device.h -- internal launch interface between the host layer (mgc_api / mgc_count / mgc_stream / mgc_eval / mgc_runs / mgc_node .cpp)
+// mgc_device.h -- internal launch interface between the host layer (mgc_api / mgc_count / mgc_stream / mgc_eval / mgc_dbfile / mgc_runs / mgc_node .cpp;
+// their owning device buffer is mgc_devbuf.hpp's)
 // and the gfx950 kernels (mgc_kmer / mgc_sort / mgc_scan / mgc_finish / mgc_misc / mgc_parse / mgc_encode / mgc_decode / mgc_merge
 // .hip; mgc_lookup / mgc_filter / mgc_import .hip have headers of their own).  Not installed.
 #pragma once

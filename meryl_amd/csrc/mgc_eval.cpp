@@ -3,6 +3,7 @@
 // operation is a count / emit pass pair over slices in HBM, and outputs go through the database stream (mgc_stream.cpp).
 #include "../../include/meryl_db.h"
 #include "mdb_layout.h"
+#include "mgc_dbfile.hpp"
 #include "mgc_session.hpp"
 #include "mgc_route.hpp"
 #include "mgc_selector.hpp"
@@ -10,10 +11,12 @@
 
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <thread>
 #include <type_traits>
 
 using mgc::DBuf;
+using mgc::decode_on_host;
 using mgc::set_err;
 
 // ================================================================================================
@@ -25,79 +28,43 @@ using mgc::set_err;
 // device (mgc_merge.hip), encoded on the device and written by the database stream -- the same merge that folds the
 // batches of an out-of-core count.
 namespace {
-// The slice (file ff) of every input in HBM: in_k[i] / in_c[i] / hn[i].  The data file's bytes are read by one host thread per
-// input, uploaded as they are and DECODED ON THE DEVICE (mgc_decode.hip: one thread per block) -- the host only does I/O and
-// checks the framing.  MGC_DECODE_HOST=1, or a file framed in a way only the host decoder follows: decoded by the host
-// threads (65-70 M k-mers/s each) and uploaded as arrays, as before.
-// MGC_DECODE_HOST=1 (tests): read ONCE per merge / filter operation, by its entry point
-bool decode_on_host() { const char *e = getenv("MGC_DECODE_HOST"); return e && e[0] == '1'; }
-// in_l (the labelled evaluation; null otherwise): the labels of the inputs that store some, beside the values -- from the device
-// decoder, or from mdb_reader_read_file_ex on the host path; an input without labels gets no buffer (its labels are zeros)
+// The slice (file ff) of every input in HBM: in_k[i] / in_c[i] / hn[i].  One host thread per input reads the data file (mgc_dbfile.hpp:
+// raw, or host-decoded where only the host decoder follows the framing or under MGC_DECODE_HOST=1, which every entry point reads once);
+// then the files are uploaded and decoded one after the other.
+// in_l (the labelled evaluation; null otherwise): the labels of the inputs that store some, beside the values; an input without
+// labels gets no buffer (its labels are zeros)
 int load_slices(std::vector<mdb_reader *> &rd, uint32_t ff, uint32_t kw, std::vector<DBuf> &in_k, std::vector<DBuf> &in_c,
                 std::vector<uint64_t> &hn, hipStream_t st, std::string *msg, bool host_decode, std::vector<DBuf> *in_l = nullptr) {
   const uint32_t n_inputs = (uint32_t)rd.size();
-  struct Raw { unsigned char *bytes = nullptr; uint64_t size = 0; mdb_raw_block *blocks = nullptr; uint64_t nb = 0; bool on_device = false; };
-  std::vector<Raw> raw(n_inputs);
-  std::vector<std::vector<uint64_t>> hk(n_inputs);
-  std::vector<uint32_t *> hc(n_inputs, nullptr);
-  std::vector<uint64_t *> hl(n_inputs, nullptr);
-  std::vector<int> rrc(n_inputs, MGC_OK);
-  std::vector<std::string> rmsg(n_inputs);
-  std::vector<mdb_info> infos(n_inputs);
-  hn.assign(n_inputs, 0);
+  std::vector<mgc::DbFile> file(n_inputs);
   {
     std::vector<std::thread> th;
     for (uint32_t i = 0; i < n_inputs; i++)
-      th.emplace_back([&, i]() {
-        mdb_reader_info(rd[i], &infos[i]);
-        if (!host_decode) {
-          const int rc = mdb_reader_raw_file(rd[i], ff, &raw[i].bytes, &raw[i].size, &raw[i].blocks, &raw[i].nb, &hn[i]);
-          if (rc == MGC_OK) { raw[i].on_device = true; return; }
-          if (rc != MGC_EUNSUPPORTED) { rrc[i] = rc; rmsg[i] = mdb_last_error(); return; }
-        }
-        uint64_t *lo = nullptr, *hi = nullptr;
-        rrc[i] = mdb_reader_read_file_ex(rd[i], ff, &lo, &hi, &hc[i], (in_l && infos[i].label_size) ? &hl[i] : nullptr, &hn[i]);
-        if (rrc[i] != MGC_OK) { rmsg[i] = mdb_last_error(); return; }
-        hk[i].resize((size_t)kw * hn[i]);
-        if (kw == 1) { if (hn[i]) memcpy(hk[i].data(), lo, 8 * hn[i]); }
-        else for (uint64_t j = 0; j < hn[i]; j++) { hk[i][2 * j] = lo[j]; hk[i][2 * j + 1] = hi[j]; }
-        mdb_free(lo); mdb_free(hi);
-      });
+      th.emplace_back([&, i]() { mgc::dbfile_read(rd[i], ff, kw, host_decode, in_l != nullptr, &file[i]); });
     for (auto &t : th) t.join();
   }
+  hn.assign(n_inputs, 0);
+  for (uint32_t i = 0; i < n_inputs; i++) {
+    hn[i] = file[i].n;
+    if (file[i].rc != MGC_OK) { *msg = file[i].msg; return file[i].rc; }
+  }
   int rc = MGC_OK;
-  for (uint32_t i = 0; i < n_inputs; i++)
-    if (rrc[i] != MGC_OK && rc == MGC_OK) { rc = rrc[i]; *msg = rmsg[i]; }
   hipError_t e = hipSuccess;
-  DBuf d_file, d_blocks, d_err;
-  uint32_t h_err = 0;
-  if (rc == MGC_OK) e = d_err.ensure(256);
+  mgc::DbFileScratch scratch;
   for (uint32_t i = 0; i < n_inputs && rc == MGC_OK && e == hipSuccess; i++) {
+    mdb_info inf;
+    mdb_reader_info(rd[i], &inf);
+    const bool with_l = in_l && inf.label_size;
     e = in_k[i].ensure(8 * (size_t)kw * hn[i]);
     if (e == hipSuccess) e = in_c[i].ensure(4 * hn[i]);
-    const bool with_l = in_l && infos[i].label_size;
     if (e == hipSuccess && with_l) e = (*in_l)[i].ensure(8 * hn[i]);
     if (e != hipSuccess || !hn[i]) continue;
-    if (raw[i].on_device) {
-      e = d_file.ensure(raw[i].size + 16);
-      if (e == hipSuccess) e = d_blocks.ensure(sizeof(mdb_raw_block) * raw[i].nb);
-      if (e == hipSuccess) e = hipMemsetAsync(d_err.p, 0, 4, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(d_file.p, raw[i].bytes, raw[i].size + 16, hipMemcpyHostToDevice, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(d_blocks.p, raw[i].blocks, sizeof(mdb_raw_block) * raw[i].nb, hipMemcpyHostToDevice, st);
-      if (e == hipSuccess) e = mgc::launch_decode_blocks(d_file.p, d_blocks.p, raw[i].nb, infos[i].suffix_size, infos[i].label_size, kw, in_k[i].p,
-                                                         in_c[i].as<uint32_t>(), d_err.as<uint32_t>(), st, with_l ? (*in_l)[i].as<uint64_t>() : nullptr);
-      if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err.p, 4, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);                     // d_file is reused by the next input
-      if (e == hipSuccess && h_err) { rc = MGC_EINVAL; *msg = "corrupt block in a database file (device decoder, code " + std::to_string(h_err) + ")"; }
-    } else {
-      e = hipMemcpyAsync(in_k[i].p, hk[i].data(), 8 * (size_t)kw * hn[i], hipMemcpyHostToDevice, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(in_c[i].p, hc[i], 4 * hn[i], hipMemcpyHostToDevice, st);
-      if (e == hipSuccess && with_l) e = hipMemcpyAsync((*in_l)[i].p, hl[i], 8 * hn[i], hipMemcpyHostToDevice, st);
-    }
+    uint32_t h_err = 0;
+    e = mgc::dbfile_upload(file[i], inf, kw, scratch, in_k[i].p, in_c[i].as<uint32_t>(), with_l ? (*in_l)[i].as<uint64_t>() : nullptr, &h_err, st);
+    if (e == hipSuccess && file[i].raw) e = hipStreamSynchronize(st);        // the scratch is reused by the next input
+    if (e == hipSuccess) rc = mgc::dbfile_decode_rc(h_err, msg);
   }
-  if (e == hipSuccess && rc == MGC_OK) e = hipStreamSynchronize(st);
-  for (uint32_t i = 0; i < n_inputs; i++) { mdb_free(hc[i]); mdb_free(hl[i]); mdb_free(raw[i].bytes); mdb_free(raw[i].blocks); }
-  d_file.release(); d_blocks.release(); d_err.release();
+  if (e == hipSuccess && rc == MGC_OK) e = hipStreamSynchronize(st);         // the host-decoded arrays go with `file`
   if (e != hipSuccess) { rc = (e == hipErrorOutOfMemory) ? MGC_ENOMEM : MGC_EHIP; *msg = std::string("uploading a slice: ") + hipGetErrorString(e); }
   return rc;
 }
@@ -138,11 +105,6 @@ struct SliceRef { const void *k = nullptr; const uint32_t *c = nullptr; uint64_t
 // buffers of the left fold (grow-only, reused from slice to slice)
 struct FoldBufs {
   DBuf acc_k[2], acc_c[2], mem_k[2], mem_c[2], ones, ws;
-  void release() {
-    for (int t = 0; t < 2; t++) { acc_k[t].release(); acc_c[t].release(); mem_k[t].release(); mem_c[t].release(); }
-    ones.release();
-    ws.release();
-  }
 };
 
 // One count / emit pass pair, whatever the kernels: workspace -> count -> read the output length -> size the outputs -> emit ->
@@ -244,7 +206,6 @@ extern "C" int mgc_db_merge(const char *const *inputs, uint32_t n_inputs, int op
     rc = (e == hipErrorOutOfMemory) ? MGC_ENOMEM : MGC_EHIP;
     msg = std::string("mgc_db_merge: ") + what + ": " + hipGetErrorString(e);
   };
-#define MG_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { hip_fail(e__, #expr); goto done; } } while (0)
   {
     hipStream_t st = nullptr;
     std::vector<DBuf> in_k(n_inputs), in_c(n_inputs);
@@ -253,8 +214,9 @@ extern "C" int mgc_db_merge(const char *const *inputs, uint32_t n_inputs, int op
     std::vector<SliceRef> in(n_inputs);
     const uint64_t blocks_per_file = 1ull << (w_prefix - MGC_NUM_FILES_BITS);
     const bool host_decode = decode_on_host();
-    MG_TRY(hipSetDevice(device));
-    MG_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) hip_fail(e, "hipSetDevice(device)");
+    else if ((e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking)) != hipSuccess) hip_fail(e, "hipStreamCreateWithFlags(&st, hipStreamNonBlocking)");
     for (uint32_t ff = 0; ff < MGC_NUM_FILES && rc == MGC_OK; ff++) {
       rc = load_slices(rd, ff, kw, in_k, in_c, hn, st, &msg, host_decode);
       if (rc != MGC_OK) { msg = "mgc_db_merge: " + msg; break; }
@@ -267,13 +229,8 @@ extern "C" int mgc_db_merge(const char *const *inputs, uint32_t n_inputs, int op
       if (rc == MGC_OK) rc = mgc_db_stream_sync(d);         // the buffers are reused for the next slice
       if (rc != MGC_OK) msg = std::string("mgc_db_merge: ") + mgc_db_stream_error(d);
     }
-  done:
-    for (auto &b : in_k) b.release();
-    for (auto &b : in_c) b.release();
-    fb.release();
     if (st) (void)hipStreamDestroy(st);
   }
-#undef MG_TRY
   close_all();
   const int rc2 = mgc_db_stream_close(d, nullptr);
   if (rc == MGC_OK && rc2 != MGC_OK) { rc = rc2; msg = mgc_db_stream_error(nullptr); }
@@ -313,7 +270,6 @@ extern "C" int mgc_db_filter(const char *input, int value_op, uint64_t constant,
     if (rc != MGC_OK) msg = std::string("mgc_db_filter: ") + mgc_db_stream_error(d);
   }
   if (e != hipSuccess && rc == MGC_OK) { rc = (e == hipErrorOutOfMemory) ? MGC_ENOMEM : MGC_EHIP; msg = std::string("mgc_db_filter: ") + hipGetErrorString(e); }
-  in_k[0].release(); in_c[0].release(); out_k.release(); out_c.release(); ws.release();
   if (st) (void)hipStreamDestroy(st);
   mdb_reader_close(rd[0]);
   const int rc2 = mgc_db_stream_close(d, nullptr);
@@ -333,7 +289,7 @@ bool merge_many_enabled() { const char *e = getenv("MGC_MERGE_MANY"); return !(e
 
 struct EvalNode {
   DBuf k, c, l;                    // an inner node's result (l: labelled evaluation)
-  FoldBufs *fold = nullptr;        // merge nodes that fold
+  std::unique_ptr<FoldBufs> fold;  // merge nodes that fold
   SliceRef res;
   mgc_db_stream *out = nullptr;
   mgc_value_hist *hist = nullptr;  // flagged nodes (mgc_db_eval_reported): the histogram of the result's values over all slices
@@ -531,7 +487,7 @@ int eval_impl(const Eval &E, int device, int host_threads) {
     const bool is_merge = nd.kind == MGC_NODE_MERGE;
     const mgc::Route route = mgc::eval_route(!is_merge, nd.n_children, labels, nd.n_terms != 0, nd.value_assign != MGC_ASSIGN_NONE, use_many);
     if (route == mgc::ROUTE_FOLD) {
-      if (!me.fold) me.fold = new FoldBufs;
+      if (!me.fold) me.fold.reset(new FoldBufs);
       const char *what = "";
       return !hip_fail(fold_slices(in, nd.op, kw, *me.fold, me.k, me.c, st, &me.res, &what), what);
     }
@@ -626,11 +582,6 @@ int eval_impl(const Eval &E, int device, int host_threads) {
   }
   // an output whose node failed mid-slice may still be encoding from buffers about to go
   if (rc != MGC_OK) for (uint32_t v : order) if (ev[v].out) (void)mgc_db_stream_sync(ev[v].out);
-  for (auto &b : in_k) b.release();
-  for (auto &b : in_c) b.release();
-  for (auto &b : in_l) b.release();
-  ws.release();
-  for (EvalNode &e : ev) { e.k.release(); e.c.release(); e.l.release(); if (e.fold) { e.fold->release(); delete e.fold; } }
   if (st) (void)hipStreamDestroy(st);
   close_readers();
   for (uint32_t v : order) {

@@ -310,40 +310,26 @@ void filter_gather_long_kernel(const FiSide s, const u64 *__restrict__ found, u6
 //  C ABI
 // ================================================================================================
 namespace {
+using mgc::DBuf;
 using mgc::u32;
 using mgc::u64;
 
 int fi_fail(int rc, const std::string &m) { mgc::lk_set_error(m); return rc; }
 #define FI_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return fi_fail(MGC_EHIP, std::string("mgc_lookup_filter: " #expr ": ") + hipGetErrorString(e__)); } while (0)
 
-// a device buffer that only grows (one workspace serves every piece of a file)
-struct FiBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  hipError_t need(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    const size_t c = bytes + bytes / 4 + 256;
-    const hipError_t e = hipMalloc(&p, c);
-    if (e == hipSuccess) cap = c;
-    return e;
-  }
-  template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-  ~FiBuf() { if (p) (void)hipFree(p); }
-};
-
 struct FiInput {
-  FiBuf tiles, scr, ls, rl, rec, hb, he, bb, be, flat, off;
+  DBuf tiles, scr, ls, rl, rec, hb, he, bb, be, flat, off;
   u64 n = 0, n_lines = 0, nr_all = 0, nr = 0;   // nr: complete records of this piece; nr_all: record starts (FASTA)
   int fmt = 0;
 };
-struct FiWork { FiInput in[2]; FiBuf found, misc; };
+struct FiWork { FiInput in[2]; DBuf found, misc; };
+// the filter's buffers grow with a quarter of headroom (one workspace serves every piece of a file)
+hipError_t fi_need(DBuf &b, size_t bytes) { return bytes <= b.cap ? hipSuccess : b.ensure(bytes + bytes / 4 + 256); }
 
 // the compaction workspace of `tiles` tiles over an input's grow-only buffers; the total goes where the caller reads it
 hipError_t fi_compact_ws(FiInput &S, u64 tiles, u64 *d_total, mgc::CompactWs *w) {
-  MGC_CHECK(S.tiles.need(8 * (tiles + 2)));
-  MGC_CHECK(S.scr.need(8 * mgc::compact_scratch_elems(tiles)));
+  MGC_CHECK(fi_need(S.tiles, 8 * (tiles + 2)));
+  MGC_CHECK(fi_need(S.scr, 8 * mgc::compact_scratch_elems(tiles)));
   *w = {d_total, S.tiles.as<u64>(), S.scr.as<u64>(), tiles};
   return hipSuccess;
 }
@@ -369,7 +355,7 @@ int fi_index(FiInput &S, const uint8_t *d_text, u64 n, bool final, u64 *d_misc, 
   S.fmt = (int)m[1];
   if (!S.fmt) return fi_fail(MGC_EFORMAT, std::string("mgc_lookup_filter: a record starts with '") + (char)m[3] + "', neither '>' nor '@'");
   S.n_lines = nl + (open_tail ? 1 : 0);
-  FI_HIP(S.ls.need(8 * (nl + 2)));
+  FI_HIP(fi_need(S.ls, 8 * (nl + 2)));
   hipLaunchKernelGGL(mgc::filter_nl_kernel<true>, dim3((uint32_t)tiles), dim3(256), 0, st, d_text, n, w.tiles, nl, open_tail ? 1u : 0u, S.ls.as<u64>());
   FI_HIP(hipGetLastError());
   if (S.fmt == MGC_TEXT_FASTQ) {
@@ -386,7 +372,7 @@ int fi_index(FiInput &S, const uint8_t *d_text, u64 n, bool final, u64 *d_misc, 
   FI_HIP(mgc::compact_scan(w, st));
   FI_HIP(hipMemcpyAsync(&S.nr_all, d_misc + 4, 8, hipMemcpyDeviceToHost, st));
   FI_HIP(hipStreamSynchronize(st));
-  FI_HIP(S.rl.need(8 * (S.nr_all + 1)));
+  FI_HIP(fi_need(S.rl, 8 * (S.nr_all + 1)));
   hipLaunchKernelGGL(mgc::filter_hdr_kernel<true>, dim3((uint32_t)ltiles), dim3(256), 0, st, d_text, S.ls.as<u64>(), S.n_lines, w.tiles, S.nr_all,
                      S.rl.as<u64>());
   FI_HIP(hipGetLastError());
@@ -414,7 +400,7 @@ int fi_step(FiWork &W, const mgc_lookup *t, int mode, uint32_t skip_first, uint3
             mgc_filter_result *res, uint64_t nr_piece[2], hipStream_t st) {
   memset(res, 0, sizeof(*res));
   FI_HIP(hipSetDevice(t->device));
-  FI_HIP(W.misc.need(8 * 16));
+  FI_HIP(fi_need(W.misc, 8 * 16));
   u64 *d_misc = W.misc.as<u64>();
   FI_HIP(hipMemsetAsync(d_misc, 0, 8 * 16, st));
   for (uint32_t i = 0; i < n_inputs; i++) {
@@ -436,9 +422,9 @@ int fi_step(FiWork &W, const mgc_lookup *t, int mode, uint32_t skip_first, uint3
   if (NR == 0) return MGC_OK;
 
   mgc::LkTable tab;
-  tab.keys = t->d_keys; tab.vals = t->d_vals; tab.index = reinterpret_cast<const u64 *>(t->d_index);
+  tab.keys = t->d_keys.p; tab.vals = t->d_vals.as<u32>(); tab.index = t->d_index.as<const u64>();
   tab.n_index = 1ull << t->index_bits; tab.shift = t->shift; tab.reserved = 0;
-  FI_HIP(W.found.need(8 * NR));
+  FI_HIP(fi_need(W.found, 8 * NR));
   u64 *d_found = W.found.as<u64>();
   FI_HIP(hipMemsetAsync(d_found, 0, 8 * NR, st));
   uint32_t *d_err = reinterpret_cast<uint32_t *>(d_misc + 9);
@@ -448,9 +434,9 @@ int fi_step(FiWork &W, const mgc_lookup *t, int mode, uint32_t skip_first, uint3
     FiInput &S = W.in[i];
     const bool fasta = S.fmt == MGC_TEXT_FASTA;
     const u64 n = S.n, nspan = fasta ? S.nr_all : NR;
-    FI_HIP(S.rec.need(sizeof(mgc::FiRec) * nspan));
-    if (fasta) { FI_HIP(S.hb.need(8 * nspan)); FI_HIP(S.he.need(8 * nspan)); FI_HIP(S.bb.need(8 * (nspan + 1))); FI_HIP(S.flat.need(n)); }
-    else       { FI_HIP(S.bb.need(8 * nspan)); FI_HIP(S.be.need(8 * nspan)); }
+    FI_HIP(fi_need(S.rec, sizeof(mgc::FiRec) * nspan));
+    if (fasta) { FI_HIP(fi_need(S.hb, 8 * nspan)); FI_HIP(fi_need(S.he, 8 * nspan)); FI_HIP(fi_need(S.bb, 8 * (nspan + 1))); FI_HIP(fi_need(S.flat, n)); }
+    else       { FI_HIP(fi_need(S.bb, 8 * nspan)); FI_HIP(fi_need(S.be, 8 * nspan)); }
     hipLaunchKernelGGL(mgc::filter_spans_kernel, dim3(fi_grid(nspan, 256)), dim3(256), 0, st, d_text[i], n, S.ls.as<u64>(),
                        fasta ? S.rl.as<u64>() : (const u64 *)nullptr, nspan, S.rec.as<mgc::FiRec>(), S.hb.as<u64>(), S.he.as<u64>(),
                        S.bb.as<u64>(), S.be.as<u64>(), d_err);
@@ -476,7 +462,7 @@ int fi_step(FiWork &W, const mgc_lookup *t, int mode, uint32_t skip_first, uint3
     else
       hipLaunchKernelGGL(mgc::filter_found_kernel<mgc::u64>, dim3(g), dim3(256), 0, st, tab, t->k, stream, n, S.bb.as<u64>(), d_be, NR, skip, d_found);
     FI_HIP(hipGetLastError());
-    FI_HIP(S.off.need(8 * (NR + 1)));
+    FI_HIP(fi_need(S.off, 8 * (NR + 1)));
     side[i].text = d_text[i]; side[i].stream = stream; side[i].rec = S.rec.as<mgc::FiRec>();
     side[i].bb = S.bb.as<u64>(); side[i].be = d_be; side[i].off = S.off.as<u64>(); side[i].out = d_out ? d_out[i] : nullptr;
   }
@@ -486,7 +472,7 @@ int fi_step(FiWork &W, const mgc_lookup *t, int mode, uint32_t skip_first, uint3
   u64 totals[2] = {0, 0}, kept_err[2] = {0, 0};
   for (uint32_t i = 0; i < n_inputs; i++) {
     FiInput &S = W.in[i];
-    FI_HIP(S.scr.need(8 * mgc::scan_scratch_elems(NR + 1)));
+    FI_HIP(fi_need(S.scr, 8 * mgc::scan_scratch_elems(NR + 1)));
     FI_HIP(mgc::scan_u64_exclusive(S.off.as<u64>(), NR, S.scr.as<u64>(), S.off.as<u64>() + NR, st));
     FI_HIP(hipMemcpyAsync(&totals[i], S.off.as<u64>() + NR, 8, hipMemcpyDeviceToHost, st));
   }
@@ -535,7 +521,7 @@ struct FiFile {
   char *h = nullptr;                  // pinned: what is left of the last piece, then what was read since
   uint64_t cap = 0, have = 0;
   bool eof = false;
-  FiBuf d_in, d_out;
+  DBuf d_in, d_out;
   char *h_out = nullptr;
   uint64_t h_out_cap = 0;
   ~FiFile() { if (r) msr_close(r); if (h) (void)hipHostFree(h); if (h_out) (void)hipHostFree(h_out); }
@@ -588,8 +574,8 @@ extern "C" int mgc_lookup_filter_files(const mgc_lookup *t, int mode, uint32_t s
       int rc = f.fill();
       if (rc != MGC_OK) return rc;
       if (f.have == 0) return MGC_OK;
-      FI_HIP(f.d_in.need(f.have));
-      FI_HIP(W.misc.need(8 * 16));
+      FI_HIP(fi_need(f.d_in, f.have));
+      FI_HIP(fi_need(W.misc, 8 * 16));
       FI_HIP(hipMemcpyAsync(f.d_in.p, f.h, f.have, hipMemcpyHostToDevice, st));
       if ((rc = fi_index(S, f.d_in.as<uint8_t>(), f.have, f.eof, W.misc.as<u64>(), st)) != MGC_OK) return rc;
       uint64_t pos = 0;
@@ -608,8 +594,8 @@ extern "C" int mgc_lookup_filter_files(const mgc_lookup *t, int mode, uint32_t s
     for (uint32_t i = 0; i < n_inputs; i++) {
       const int rc = F[i].fill();
       if (rc != MGC_OK) return rc;
-      FI_HIP(F[i].d_in.need(F[i].have));
-      FI_HIP(F[i].d_out.need(F[i].have + F[i].have / 4 + 4096));
+      FI_HIP(fi_need(F[i].d_in, F[i].have));
+      FI_HIP(fi_need(F[i].d_out, F[i].have + F[i].have / 4 + 4096));
       if (F[i].have) FI_HIP(hipMemcpyAsync(F[i].d_in.p, F[i].h, F[i].have, hipMemcpyHostToDevice, st));
       d_text[i] = F[i].d_in.as<uint8_t>(); n_text[i] = F[i].have; fin[i] = F[i].eof;
       d_out[i] = F[i].d_out.as<uint8_t>(); out_cap[i] = F[i].d_out.cap;
@@ -617,7 +603,7 @@ extern "C" int mgc_lookup_filter_files(const mgc_lookup *t, int mode, uint32_t s
     mgc_filter_result res;
     int rc = fi_step(W, t, mode, skip_first, n_inputs, d_text, n_text, fin, false, d_out, out_cap, &res, nr_piece, st);
     if (rc == MGC_EINVAL && (res.out_bytes[0] > out_cap[0] || res.out_bytes[1] > out_cap[1])) {   // a piece of many short records
-      for (uint32_t i = 0; i < n_inputs; i++) { FI_HIP(F[i].d_out.need(res.out_bytes[i])); d_out[i] = F[i].d_out.as<uint8_t>(); out_cap[i] = F[i].d_out.cap; }
+      for (uint32_t i = 0; i < n_inputs; i++) { FI_HIP(fi_need(F[i].d_out, res.out_bytes[i])); d_out[i] = F[i].d_out.as<uint8_t>(); out_cap[i] = F[i].d_out.cap; }
       rc = fi_step(W, t, mode, skip_first, n_inputs, d_text, n_text, fin, false, d_out, out_cap, &res, nr_piece, st);
     }
     if (rc != MGC_OK) return rc;

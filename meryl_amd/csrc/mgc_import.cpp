@@ -245,7 +245,7 @@ struct Reader {
 };
 
 struct Importer {
-  typedef mgc_runs::DBuf DBuf;
+  typedef mgc::DBuf DBuf;
   uint32_t k, kw;
   int mode, device, host_threads;
   hipStream_t st = nullptr;
@@ -257,7 +257,6 @@ struct Importer {
   ~Importer() {
     (void)hipSetDevice(device);
     if (runs) mgc_runs_close(runs);
-    for (DBuf *b : {&d_text, &d_state, &d_pws, &d_k[0], &d_k[1], &d_v[0], &d_v[1], &d_sws, &d_rws}) b->release();
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     if (st) (void)hipStreamDestroy(st);
   }

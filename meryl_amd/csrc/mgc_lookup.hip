@@ -7,6 +7,7 @@
 // latency, not bandwidth: queries are batched so that thousands of searches are in flight per CU.
 #include "mgc_lookup_dev.hpp"
 #include "mgc_compact.hpp"
+#include "mgc_dbfile.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -333,9 +334,6 @@ extern "C" const char *mgc_lookup_error(void) { return g_lk_error.c_str(); }
 extern "C" void mgc_lookup_free(mgc_lookup *t) {
   if (!t) return;
   (void)hipSetDevice(t->device);
-  if (t->d_keys) (void)hipFree(t->d_keys);
-  if (t->d_vals) (void)hipFree(t->d_vals);
-  if (t->d_index) (void)hipFree(t->d_index);
   delete t;
 }
 
@@ -379,12 +377,12 @@ static mgc_lookup *lookup_finish(mgc_lookup *t) {
   t->index_bits = bits;
   t->shift = 2 * t->k - bits;
   const uint64_t entries = (1ull << bits) + 1;
-  LK_TRY(hipMalloc(reinterpret_cast<void **>(&t->d_index), sizeof(uint64_t) * entries));
+  LK_TRY(t->d_index.ensure(sizeof(uint64_t) * entries));
   if (bits == 0) {                                          // a handful of k-mers: one bucket
     const uint64_t two[2] = {0, t->n};
-    LK_TRY(hipMemcpy(t->d_index, two, sizeof(two), hipMemcpyHostToDevice));
+    LK_TRY(hipMemcpy(t->d_index.p, two, sizeof(two), hipMemcpyHostToDevice));
   } else {
-    LK_TRY(mgc::launch_block_offsets(t->d_keys, t->n, t->kw, t->shift, 1ull << bits, t->d_index, nullptr));
+    LK_TRY(mgc::launch_block_offsets(t->d_keys.p, t->n, t->kw, t->shift, 1ull << bits, t->d_index.as<uint64_t>(), nullptr));
     LK_TRY(hipStreamSynchronize(nullptr));
   }
   return t;
@@ -400,41 +398,40 @@ extern "C" mgc_lookup *mgc_lookup_from_device(const void *d_keys, const uint32_t
   const size_t kbytes = sizeof(uint64_t) * t->kw;
   if (min_value <= 1 && max_value >= 0xFFFFFFFFull) {       // nothing to filter (stored values are >= 1)
     t->n = n;
-    LK_TRY(hipMalloc(&t->d_keys, kbytes * (n ? n : 1)));
-    LK_TRY(hipMalloc(reinterpret_cast<void **>(&t->d_vals), sizeof(uint32_t) * (n ? n : 1)));
+    LK_TRY(t->d_keys.ensure(kbytes * n));
+    LK_TRY(t->d_vals.ensure(sizeof(uint32_t) * n));
     if (n) {
-      LK_TRY(hipMemcpy(t->d_keys, d_keys, kbytes * n, hipMemcpyDeviceToDevice));
-      LK_TRY(hipMemcpy(t->d_vals, d_values, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice));
+      LK_TRY(hipMemcpy(t->d_keys.p, d_keys, kbytes * n, hipMemcpyDeviceToDevice));
+      LK_TRY(hipMemcpy(t->d_vals.p, d_values, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice));
     }
     return lookup_finish(t);
   }
   const uint64_t tiles = (n + mgc::FL_TILE - 1) / mgc::FL_TILE;
-  void *d_ws = nullptr;
+  mgc::DBuf d_ws;
   mgc::CompactWs w = {};
   uint64_t kept = 0;
   if (tiles) {
-    LK_TRY(hipMalloc(&d_ws, sizeof(uint64_t) * mgc::compact_ws_elems(tiles)));
-    w = mgc::compact_ws_at(d_ws, tiles);
+    LK_TRY(d_ws.ensure(sizeof(uint64_t) * mgc::compact_ws_elems(tiles)));
+    w = mgc::compact_ws_at(d_ws.p, tiles);
     hipLaunchKernelGGL((mgc::filter_kernel<mgc::u64, false>), dim3((uint32_t)tiles), dim3(256), 0, nullptr, (const mgc::u64 *)nullptr, d_values,
                        (mgc::u64)n, (mgc::u64)min_value, (mgc::u64)max_value, w.tiles, (mgc::u64 *)nullptr, (uint32_t *)nullptr);
     hipError_t e = mgc::compact_scan(w, nullptr);
     if (e == hipSuccess) e = hipMemcpy(&kept, w.total, sizeof(uint64_t), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { (void)hipFree(d_ws); lk_err(std::string("value filter: ") + hipGetErrorString(e)); mgc_lookup_free(t); return nullptr; }
+    if (e != hipSuccess) { lk_err(std::string("value filter: ") + hipGetErrorString(e)); mgc_lookup_free(t); return nullptr; }
   }
   t->n = kept;
-  hipError_t e = hipMalloc(&t->d_keys, kbytes * (kept ? kept : 1));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&t->d_vals), sizeof(uint32_t) * (kept ? kept : 1));
+  hipError_t e = t->d_keys.ensure(kbytes * kept);
+  if (e == hipSuccess) e = t->d_vals.ensure(sizeof(uint32_t) * kept);
   if (e == hipSuccess && tiles) {
     if (t->kw == 2)
       hipLaunchKernelGGL((mgc::filter_kernel<mgc::K128, true>), dim3((uint32_t)tiles), dim3(256), 0, nullptr, reinterpret_cast<const mgc::K128 *>(d_keys),
-                         d_values, (mgc::u64)n, (mgc::u64)min_value, (mgc::u64)max_value, w.tiles, reinterpret_cast<mgc::K128 *>(t->d_keys), t->d_vals);
+                         d_values, (mgc::u64)n, (mgc::u64)min_value, (mgc::u64)max_value, w.tiles, t->d_keys.as<mgc::K128>(), t->d_vals.as<uint32_t>());
     else
       hipLaunchKernelGGL((mgc::filter_kernel<mgc::u64, true>), dim3((uint32_t)tiles), dim3(256), 0, nullptr, reinterpret_cast<const mgc::u64 *>(d_keys),
-                         d_values, (mgc::u64)n, (mgc::u64)min_value, (mgc::u64)max_value, w.tiles, reinterpret_cast<mgc::u64 *>(t->d_keys), t->d_vals);
+                         d_values, (mgc::u64)n, (mgc::u64)min_value, (mgc::u64)max_value, w.tiles, t->d_keys.as<mgc::u64>(), t->d_vals.as<uint32_t>());
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   }
-  if (d_ws) (void)hipFree(d_ws);
   if (e != hipSuccess) { lk_err(std::string("value filter: ") + hipGetErrorString(e)); mgc_lookup_free(t); return nullptr; }
   return lookup_finish(t);
 }
@@ -449,131 +446,59 @@ extern "C" mgc_lookup *mgc_lookup_load(const char *db_path, uint64_t min_value, 
   const uint32_t kw = info.k > 32 ? 2u : 1u;
   if (host_threads <= 0) host_threads = (int)std::thread::hardware_concurrency();
   host_threads = std::max(1, std::min(host_threads, MGC_NUM_FILES));
-  // Device decode (mgc_decode.hip): host threads only READ the 64 data files and check their framing; the bytes go to HBM as
-  // they are and every block is decoded there (one thread per block), straight into the table's arrays; the value filter is
-  // the device compaction mgc_lookup_from_device uses.  MGC_DECODE_HOST=1, or a file only the host decoder follows: below.
-  const bool host_decode = getenv("MGC_DECODE_HOST") && getenv("MGC_DECODE_HOST")[0] == '1';      // once per table load (tests switch it between loads)
-  if (!host_decode) {
-    if (device < 0) (void)hipGetDevice(&device);
-    if (hipSetDevice(device) != hipSuccess) { lk_err("mgc_lookup_load: hipSetDevice failed"); return nullptr; }
-    struct Raw { unsigned char *bytes = nullptr; uint64_t size = 0, nb = 0, n = 0; mdb_raw_block *blocks = nullptr; int rc = MGC_OK; };
-    std::vector<Raw> raw(MGC_NUM_FILES);
-    std::atomic<uint32_t> nextf(0);
-    std::mutex mu2;
-    std::string msg2;
-    auto reader = [&]() {
-      mdb_reader *rr = mdb_reader_open(db_path);
-      if (!rr) { std::lock_guard<std::mutex> g(mu2); msg2 = mdb_last_error(); for (auto &x : raw) if (x.rc == MGC_OK && !x.bytes) x.rc = MGC_EINVAL; return; }
-      for (;;) {
-        const uint32_t ff = nextf.fetch_add(1);
-        if (ff >= MGC_NUM_FILES) break;
-        Raw &x = raw[ff];
-        x.rc = mdb_reader_raw_file(rr, ff, &x.bytes, &x.size, &x.blocks, &x.nb, &x.n);
-        if (x.rc != MGC_OK && x.rc != MGC_EUNSUPPORTED) { std::lock_guard<std::mutex> g(mu2); msg2 = mdb_last_error(); }
-      }
-      mdb_reader_close(rr);
-    };
-    {
-      std::vector<std::thread> pool;
-      for (int i = 1; i < host_threads; i++) pool.emplace_back(reader);
-      reader();
-      for (auto &th : pool) th.join();
-    }
-    bool all_ok = true, hard_fail = false;
-    uint64_t total = 0, max_size = 0, max_nb = 0;
-    for (const Raw &x : raw) { all_ok = all_ok && x.rc == MGC_OK; hard_fail = hard_fail || (x.rc != MGC_OK && x.rc != MGC_EUNSUPPORTED); total += x.n; max_size = std::max(max_size, x.size); max_nb = std::max(max_nb, x.nb); }
-    auto free_raw = [&]() { for (Raw &x : raw) { mdb_free(x.bytes); mdb_free(x.blocks); x.bytes = nullptr; x.blocks = nullptr; } };
-    if (hard_fail) { free_raw(); lk_err("mgc_lookup_load: " + msg2); return nullptr; }
-    if (all_ok) {
-      const size_t kbytes = sizeof(uint64_t) * kw;
-      void *dk = nullptr, *dfile = nullptr, *dblocks = nullptr;
-      uint32_t *dv = nullptr, *derr = nullptr, h_err = 0;
-      hipError_t e = hipMalloc(&dk, kbytes * (total ? total : 1));
-      if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&dv), sizeof(uint32_t) * (total ? total : 1));
-      if (e == hipSuccess) e = hipMalloc(&dfile, max_size + 16);
-      if (e == hipSuccess) e = hipMalloc(&dblocks, sizeof(mdb_raw_block) * (max_nb ? max_nb : 1));
-      if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&derr), 256);
-      if (e == hipSuccess) e = hipMemset(derr, 0, 4);
-      uint64_t o = 0;
-      for (uint32_t ff = 0; ff < MGC_NUM_FILES && e == hipSuccess; ff++) {
-        const Raw &x = raw[ff];
-        if (x.n) {
-          e = hipMemcpy(dfile, x.bytes, x.size + 16, hipMemcpyHostToDevice);
-          if (e == hipSuccess) e = hipMemcpy(dblocks, x.blocks, sizeof(mdb_raw_block) * x.nb, hipMemcpyHostToDevice);
-          if (e == hipSuccess) e = mgc::launch_decode_blocks(dfile, dblocks, x.nb, info.suffix_size, info.label_size, kw,
-                                                             reinterpret_cast<unsigned char *>(dk) + kbytes * o, dv + o, derr, nullptr);
-          if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        }
-        o += x.n;
-      }
-      if (e == hipSuccess) e = hipMemcpy(&h_err, derr, 4, hipMemcpyDeviceToHost);
-      free_raw();
-      if (dfile) (void)hipFree(dfile);
-      if (dblocks) (void)hipFree(dblocks);
-      if (derr) (void)hipFree(derr);
-      if (e != hipSuccess || h_err) {
-        if (dk) (void)hipFree(dk);
-        if (dv) (void)hipFree(dv);
-        lk_err(e != hipSuccess ? std::string("mgc_lookup_load: ") + hipGetErrorString(e) : std::string("mgc_lookup_load: corrupt block in '") + db_path + "' (device decoder)");
-        return nullptr;
-      }
-      mgc_lookup *t = mgc_lookup_from_device(dk, dv, total, info.k, min_value, max_value, device);
-      (void)hipFree(dk); (void)hipFree(dv);
-      return t;
-    }
-    free_raw();                                            // some file needs the host decoder: all of them take it
-  }
-  // the 64 files decoded by host threads (one reader each: the reader is not shared), value filter applied on the way
-  struct Part { std::vector<uint64_t> keys; std::vector<uint32_t> vals; uint64_t n_db = 0; };
-  std::vector<Part> parts(MGC_NUM_FILES);
-  std::atomic<uint32_t> next(0);
-  std::atomic<bool> failed(false);
-  std::string fail_msg;
+  // Host threads only READ the 64 data files (mgc_dbfile.hpp); every file then goes to HBM at its running offset in the unfiltered
+  // arrays -- its bytes as they are, decoded there (mgc_decode.hip), or as arrays where only the host decoder follows it -- and the
+  // value filter is the device compaction of mgc_lookup_from_device.
+  const bool host_decode = mgc::decode_on_host();           // once per table load (tests switch it between loads)
+  if (device < 0) (void)hipGetDevice(&device);
+  if (hipSetDevice(device) != hipSuccess) { lk_err("mgc_lookup_load: hipSetDevice failed"); return nullptr; }
+  std::vector<mgc::DbFile> file(MGC_NUM_FILES);
+  std::atomic<uint32_t> nextf(0);
   std::mutex mu;
-  auto worker = [&]() {
+  std::string open_msg;
+  auto reader = [&]() {
     mdb_reader *rr = mdb_reader_open(db_path);
-    if (!rr) { std::lock_guard<std::mutex> g(mu); failed = true; fail_msg = mdb_last_error(); return; }
+    if (!rr) { std::lock_guard<std::mutex> g(mu); open_msg = mdb_last_error(); return; }
     for (;;) {
-      const uint32_t ff = next.fetch_add(1);
-      if (ff >= MGC_NUM_FILES || failed.load()) break;
-      uint64_t *lo = nullptr, *hi = nullptr, n = 0;
-      uint32_t *cn = nullptr;
-      if (mdb_reader_read_file(rr, ff, &lo, &hi, &cn, &n) != MGC_OK) { std::lock_guard<std::mutex> g(mu); failed = true; fail_msg = mdb_last_error(); break; }
-      Part &p = parts[ff];
-      p.n_db = n;
-      p.keys.reserve((size_t)kw * n); p.vals.reserve(n);
-      for (uint64_t i = 0; i < n; i++) {
-        if (cn[i] < min_value || cn[i] > max_value) continue;
-        p.keys.push_back(lo[i]);
-        if (kw == 2) p.keys.push_back(hi[i]);
-        p.vals.push_back(cn[i]);
-      }
-      mdb_free(lo); mdb_free(hi); mdb_free(cn);
+      const uint32_t ff = nextf.fetch_add(1);
+      if (ff >= MGC_NUM_FILES) break;
+      mgc::dbfile_read(rr, ff, kw, host_decode, false, &file[ff]);
     }
     mdb_reader_close(rr);
   };
-  std::vector<std::thread> pool;
-  for (int i = 1; i < host_threads; i++) pool.emplace_back(worker);
-  worker();
-  for (auto &th : pool) th.join();
-  if (failed.load()) { lk_err("mgc_lookup_load: " + fail_msg); return nullptr; }
-  mgc_lookup *t = new mgc_lookup();
-  if (device < 0) (void)hipGetDevice(&device);
-  t->device = device; t->k = info.k; t->kw = kw;
-  for (const Part &p : parts) { t->n += p.vals.size(); t->n_db += p.n_db; }
-  LK_TRY(hipSetDevice(device));
-  const size_t kbytes = sizeof(uint64_t) * kw;
-  LK_TRY(hipMalloc(&t->d_keys, kbytes * (t->n ? t->n : 1)));
-  LK_TRY(hipMalloc(reinterpret_cast<void **>(&t->d_vals), sizeof(uint32_t) * (t->n ? t->n : 1)));
-  uint64_t o = 0;
-  for (const Part &p : parts) {
-    const uint64_t m = p.vals.size();
-    if (!m) continue;
-    LK_TRY(hipMemcpy(reinterpret_cast<unsigned char *>(t->d_keys) + kbytes * o, p.keys.data(), kbytes * m, hipMemcpyHostToDevice));
-    LK_TRY(hipMemcpy(t->d_vals + o, p.vals.data(), sizeof(uint32_t) * m, hipMemcpyHostToDevice));
-    o += m;
+  {
+    std::vector<std::thread> pool;
+    for (int i = 1; i < host_threads; i++) pool.emplace_back(reader);
+    reader();
+    for (auto &th : pool) th.join();
   }
-  return lookup_finish(t);
+  if (nextf.load() < MGC_NUM_FILES) { lk_err("mgc_lookup_load: " + open_msg); return nullptr; }     // no thread could open the database
+  uint64_t total = 0, max_size = 0, max_nb = 0;
+  for (const mgc::DbFile &f : file) {
+    if (f.rc != MGC_OK) { lk_err("mgc_lookup_load: " + f.msg); return nullptr; }
+    total += f.n; max_size = std::max(max_size, f.size); max_nb = std::max(max_nb, f.nb);
+  }
+  const size_t kbytes = sizeof(uint64_t) * kw;
+  mgc::DBuf dk, dv;
+  mgc::DbFileScratch scratch;
+  hipError_t e = dk.ensure(kbytes * total);
+  if (e == hipSuccess) e = dv.ensure(sizeof(uint32_t) * total);
+  if (e == hipSuccess) e = scratch.file.ensure(max_size + 16);          // all files are read: the scratch never grows between them
+  if (e == hipSuccess) e = scratch.blocks.ensure(sizeof(mdb_raw_block) * max_nb);
+  std::string msg;
+  uint64_t o = 0;
+  for (uint32_t ff = 0; ff < MGC_NUM_FILES && e == hipSuccess; ff++) {
+    mgc::DbFile &f = file[ff];
+    uint32_t h_err = 0;
+    e = mgc::dbfile_upload(f, info, kw, scratch, dk.as<unsigned char>() + kbytes * o, dv.as<uint32_t>() + o, nullptr, &h_err, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);                  // the scratch is the next file's
+    if (e == hipSuccess && mgc::dbfile_decode_rc(h_err, &msg) != MGC_OK) { lk_err("mgc_lookup_load: " + msg); return nullptr; }
+    o += f.n;
+  }
+  file.clear();                                             // the host copies and the scratch go before the filter allocates
+  scratch = mgc::DbFileScratch();
+  if (e != hipSuccess) { lk_err(std::string("mgc_lookup_load: ") + hipGetErrorString(e)); return nullptr; }
+  return mgc_lookup_from_device(dk.p, dv.as<uint32_t>(), total, info.k, min_value, max_value, device);
 }
 
 extern "C" int mgc_lookup_get_info(const mgc_lookup *t, mgc_lookup_info *info) {
@@ -599,11 +524,11 @@ extern "C" int mgc_lookup_values(const mgc_lookup *t, const void *d_kmers, uint6
   uint64_t g = (n + 255) / 256;
   if (g > 65536) g = 65536;
   if (t->kw == 2)
-    hipLaunchKernelGGL((mgc::lookup_values_kernel<mgc::K128>), dim3((uint32_t)g), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const mgc::K128 *>(t->d_keys),
-                       t->d_vals, reinterpret_cast<const mgc::u64 *>(t->d_index), t->shift, reinterpret_cast<const mgc::K128 *>(d_kmers), (mgc::u64)n, d_out, (mgc::u64)1 << t->index_bits);
+    hipLaunchKernelGGL((mgc::lookup_values_kernel<mgc::K128>), dim3((uint32_t)g), dim3(256), 0, (hipStream_t)stream, t->d_keys.as<const mgc::K128>(),
+                       t->d_vals.as<uint32_t>(), t->d_index.as<const mgc::u64>(), t->shift, reinterpret_cast<const mgc::K128 *>(d_kmers), (mgc::u64)n, d_out, (mgc::u64)1 << t->index_bits);
   else
-    hipLaunchKernelGGL((mgc::lookup_values_kernel<mgc::u64>), dim3((uint32_t)g), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const mgc::u64 *>(t->d_keys),
-                       t->d_vals, reinterpret_cast<const mgc::u64 *>(t->d_index), t->shift, reinterpret_cast<const mgc::u64 *>(d_kmers), (mgc::u64)n, d_out, (mgc::u64)1 << t->index_bits);
+    hipLaunchKernelGGL((mgc::lookup_values_kernel<mgc::u64>), dim3((uint32_t)g), dim3(256), 0, (hipStream_t)stream, t->d_keys.as<const mgc::u64>(),
+                       t->d_vals.as<uint32_t>(), t->d_index.as<const mgc::u64>(), t->shift, reinterpret_cast<const mgc::u64 *>(d_kmers), (mgc::u64)n, d_out, (mgc::u64)1 << t->index_bits);
   return lk_rc(hipGetLastError(), "lookup_values");
 }
 
@@ -612,11 +537,11 @@ extern "C" int mgc_lookup_stream(const mgc_lookup *t, const uint8_t *d_bases, ui
   if (n_bases == 0) return MGC_OK;
   const uint32_t g = lk_grid((n_bases + mgc::LK_RUN - 1) / mgc::LK_RUN);
   if (t->kw == 2)
-    hipLaunchKernelGGL((mgc::lookup_stream_kernel<mgc::K128>), dim3(g), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const mgc::K128 *>(t->d_keys),
-                       t->d_vals, reinterpret_cast<const mgc::u64 *>(t->d_index), t->shift, d_bases, (mgc::u64)n_bases, t->k, d_out);
+    hipLaunchKernelGGL((mgc::lookup_stream_kernel<mgc::K128>), dim3(g), dim3(256), 0, (hipStream_t)stream, t->d_keys.as<const mgc::K128>(),
+                       t->d_vals.as<uint32_t>(), t->d_index.as<const mgc::u64>(), t->shift, d_bases, (mgc::u64)n_bases, t->k, d_out);
   else
-    hipLaunchKernelGGL((mgc::lookup_stream_kernel<mgc::u64>), dim3(g), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const mgc::u64 *>(t->d_keys),
-                       t->d_vals, reinterpret_cast<const mgc::u64 *>(t->d_index), t->shift, d_bases, (mgc::u64)n_bases, t->k, d_out);
+    hipLaunchKernelGGL((mgc::lookup_stream_kernel<mgc::u64>), dim3(g), dim3(256), 0, (hipStream_t)stream, t->d_keys.as<const mgc::u64>(),
+                       t->d_vals.as<uint32_t>(), t->d_index.as<const mgc::u64>(), t->shift, d_bases, (mgc::u64)n_bases, t->k, d_out);
   return lk_rc(hipGetLastError(), "lookup_stream");
 }
 
@@ -632,12 +557,12 @@ extern "C" int mgc_lookup_existence(const mgc_lookup *t, const uint8_t *d_bases,
   if (n_bases == 0 || n_seq == 0) return MGC_OK;
   const uint32_t g = lk_grid((n_bases + mgc::LK_RUN - 1) / mgc::LK_RUN);
   if (t->kw == 2)
-    hipLaunchKernelGGL((mgc::lookup_existence_kernel<mgc::K128>), dim3(g), dim3(256), 0, st, reinterpret_cast<const mgc::K128 *>(t->d_keys), t->d_vals,
-                       reinterpret_cast<const mgc::u64 *>(t->d_index), t->shift, d_bases, (mgc::u64)n_bases, t->k,
+    hipLaunchKernelGGL((mgc::lookup_existence_kernel<mgc::K128>), dim3(g), dim3(256), 0, st, t->d_keys.as<const mgc::K128>(), t->d_vals.as<uint32_t>(),
+                       t->d_index.as<const mgc::u64>(), t->shift, d_bases, (mgc::u64)n_bases, t->k,
                        reinterpret_cast<const mgc::u64 *>(d_seq_start), (mgc::u64)n_seq, reinterpret_cast<mgc::u64 *>(d_total), reinterpret_cast<mgc::u64 *>(d_found));
   else
-    hipLaunchKernelGGL((mgc::lookup_existence_kernel<mgc::u64>), dim3(g), dim3(256), 0, st, reinterpret_cast<const mgc::u64 *>(t->d_keys), t->d_vals,
-                       reinterpret_cast<const mgc::u64 *>(t->d_index), t->shift, d_bases, (mgc::u64)n_bases, t->k,
+    hipLaunchKernelGGL((mgc::lookup_existence_kernel<mgc::u64>), dim3(g), dim3(256), 0, st, t->d_keys.as<const mgc::u64>(), t->d_vals.as<uint32_t>(),
+                       t->d_index.as<const mgc::u64>(), t->shift, d_bases, (mgc::u64)n_bases, t->k,
                        reinterpret_cast<const mgc::u64 *>(d_seq_start), (mgc::u64)n_seq, reinterpret_cast<mgc::u64 *>(d_total), reinterpret_cast<mgc::u64 *>(d_found));
   return lk_rc(hipGetLastError(), "lookup_existence");
 }
@@ -654,7 +579,7 @@ int lk_set(const mgc_lookup *const *tables, uint32_t n_tables, mgc::LkSet &set, 
     const mgc_lookup *L = tables[t];
     if (!L) { lk_err(std::string(who) + ": no table"); return MGC_EINVAL; }
     if (L->k != tables[0]->k) { lk_err(std::string(who) + ": the tables have different k-mer sizes"); return MGC_EINVAL; }
-    set.t[t].keys = L->d_keys; set.t[t].vals = L->d_vals; set.t[t].index = reinterpret_cast<const mgc::u64 *>(L->d_index);
+    set.t[t].keys = L->d_keys.p; set.t[t].vals = L->d_vals.as<uint32_t>(); set.t[t].index = L->d_index.as<const mgc::u64>();
     set.t[t].n_index = 1ull << L->index_bits; set.t[t].shift = L->shift;
   }
   set.n = n_tables; set.k = tables[0]->k;

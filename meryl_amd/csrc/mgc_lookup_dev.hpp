@@ -4,6 +4,7 @@
 #include "../../include/meryl_db.h"
 #include "../../include/meryl_lookup.h"
 #include "mgc_common.hpp"
+#include "mgc_devbuf.hpp"
 
 #include <string>
 
@@ -11,9 +12,7 @@ struct mgc_lookup {
   int      device = 0;
   uint32_t k = 0, kw = 1, index_bits = 0, shift = 0;
   uint64_t n = 0, n_db = 0;
-  void     *d_keys = nullptr;
-  uint32_t *d_vals = nullptr;
-  uint64_t *d_index = nullptr;
+  mgc::DBuf d_keys, d_vals, d_index;               // kw x uint64[n], uint32[n], uint64[2^index_bits + 1]
 };
 
 namespace mgc {

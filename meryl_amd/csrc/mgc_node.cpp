@@ -26,6 +26,7 @@
 #include <thread>
 #include <vector>
 
+using mgc::DBuf;
 using mgc::set_err;
 
 namespace {
@@ -109,29 +110,22 @@ std::vector<uint32_t> balanced_ranges(const std::vector<uint64_t> &total, uint32
 #define ND_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { nd.fail("rank %u: %s -> %s", r, #expr, hipGetErrorString(e__)); return; } } while (0)
 #define ND_MGC(expr, sess) do { int rc__ = (expr); if (rc__ != MGC_OK) { nd.fail("rank %u: %s -> %d %s", r, #expr, rc__, mgc_last_error(sess)); return; } } while (0)
 
-struct DevMem {                                 // frees what a phase allocated, whichever way the phase ends
-  std::vector<void *> p;
-  ~DevMem() { for (void *q : p) if (q) (void)hipFree(q); }
-  hipError_t alloc(void **out, size_t bytes) { hipError_t e = hipMalloc(out, std::max<size_t>(bytes, 256)); if (e == hipSuccess) p.push_back(*out); return e; }
-};
-
 // once per rank: `compress` (the rank's whole sequences), the bucket histogram of ALL its reads -- every rank needs the same
 // routing plan for every batch, so the plan comes from the whole input, not from the first batch
 void phase_prepare(Node &nd, uint32_t r, hipStream_t st) {
   Rank &me = nd.ranks[r];
   const uint32_t nbk = 1u << nd.bits;
-  DevMem tmp;
+  DBuf d_hws, d_ws, d_cnt;                      // what the phase allocates goes whichever way it ends
   if (nd.cfg.homopoly_compress && me.n_bases) {
-    void *ws = nullptr;
     const size_t wsb = mgc_dev_homopoly_workspace_bytes(me.n_bases);
-    ND_HIP(hipMalloc(&me.d_own, me.n_bases)); ND_HIP(tmp.alloc(&ws, wsb));
+    ND_HIP(hipMalloc(&me.d_own, me.n_bases)); ND_HIP(d_hws.ensure(wsb));
     uint64_t n_out = 0;
-    ND_MGC(mgc_dev_homopoly_compress(me.d_bases, me.n_bases, (uint8_t *)me.d_own, &n_out, ws, wsb, st), nullptr);
+    ND_MGC(mgc_dev_homopoly_compress(me.d_bases, me.n_bases, (uint8_t *)me.d_own, &n_out, d_hws.p, wsb, st), nullptr);
     me.d_bases = (const uint8_t *)me.d_own; me.n_bases = n_out;
   }
   const size_t wsb = mgc_dev_partition_workspace_bytes(nd.bits);
-  void *ws = nullptr, *d_counts = nullptr;
-  ND_HIP(tmp.alloc(&ws, wsb)); ND_HIP(tmp.alloc(&d_counts, sizeof(uint64_t) * nbk));
+  ND_HIP(d_ws.ensure(wsb)); ND_HIP(d_cnt.ensure(sizeof(uint64_t) * nbk));
+  void *ws = d_ws.p, *d_counts = d_cnt.p;
   ND_MGC(mgc_dev_kmer_histogram(me.d_bases, me.n_bases, nd.cfg.k, nd.cfg.mode, nd.bits, (uint64_t *)d_counts, ws, wsb, st), nullptr);
   me.total.assign(nbk, 0);
   ND_HIP(hipMemcpyAsync(me.total.data(), d_counts, sizeof(uint64_t) * nbk, hipMemcpyDeviceToHost, st));
@@ -154,13 +148,13 @@ void phase_partition(Node &nd, uint32_t r, uint32_t batch, hipStream_t st) {
   Rank &me = nd.ranks[r];
   const uint32_t nbk = 1u << nd.bits;
   const double t0 = now_s();
-  DevMem tmp;
+  DBuf d_ws, d_cnt;
   uint64_t a = 0, nb = 0;
   batch_range(nd, me, batch, &a, &nb);
   const uint8_t *bases = me.d_bases + a;
   const size_t wsb = mgc_dev_partition_workspace_bytes(nd.bits);
-  void *ws = nullptr, *d_counts = nullptr;
-  ND_HIP(tmp.alloc(&ws, wsb)); ND_HIP(tmp.alloc(&d_counts, sizeof(uint64_t) * nbk));
+  ND_HIP(d_ws.ensure(wsb)); ND_HIP(d_cnt.ensure(sizeof(uint64_t) * nbk));
+  void *ws = d_ws.p, *d_counts = d_cnt.p;
   ND_MGC(mgc_dev_kmer_histogram(bases, nb, nd.cfg.k, nd.cfg.mode, nd.bits, (uint64_t *)d_counts, ws, wsb, st), nullptr);
   me.counts.assign(nbk, 0);
   ND_HIP(hipMemcpyAsync(me.counts.data(), d_counts, sizeof(uint64_t) * nbk, hipMemcpyDeviceToHost, st));
@@ -204,9 +198,8 @@ void phase_count(Node &nd, uint32_t r, hipStream_t st_copy) {
     for (uint32_t s = 0; s < n; s++) tot[f - f0] += nd.ranks[s].counts[f];
     file_off[f - f0 + 1] = file_off[f - f0] + tot[f - f0];
   }
-  DevMem mem;
-  void *inbox = nullptr, *res_keys = nullptr, *res_counts = nullptr;
-  ND_HIP(mem.alloc(&inbox, file_off[f1 - f0] * kb));
+  DBuf d_inbox, d_res_keys, d_res_counts;
+  ND_HIP(d_inbox.ensure(file_off[f1 - f0] * kb));
   // one batch: the counted waves stay here until the writer is closed (a wave has at most as many distinct k-mers as k-mers,
   // so its result fits at its own offset; one allocation for all waves -- hipMalloc beside running kernels is slow).
   // Several batches: a wave's result is parked in the run store at once, so one wave's room is enough.
@@ -222,8 +215,9 @@ void phase_count(Node &nd, uint32_t r, hipStream_t st_copy) {
       res_entries = std::max(res_entries, file_off[hi - f0] - file_off[lo - f0]);
     }
   }
-  ND_HIP(mem.alloc(&res_keys, res_entries * kb));
-  ND_HIP(mem.alloc(&res_counts, res_entries * sizeof(uint32_t)));
+  ND_HIP(d_res_keys.ensure(res_entries * kb));
+  ND_HIP(d_res_counts.ensure(res_entries * sizeof(uint32_t)));
+  void *inbox = d_inbox.p, *res_keys = d_res_keys.p, *res_counts = d_res_counts.p;
   mgc_session *sess = me.sess;
   mgc_db_stream *ds = me.ds;
   const mgc_count_config &cfg = nd.cfg;

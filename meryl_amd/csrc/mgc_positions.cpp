@@ -7,27 +7,15 @@
 // payload, and one pass over the sorted pairs that adds every slot's hits and distinct queries (mgc_positions.hip).
 #include "../../include/meryl_gpu_count.h"
 #include "../../include/meryl_positions.h"
+#include "mgc_devbuf.hpp"
 #include "mgc_import_dev.hpp"
 #include "mgc_positions_dev.hpp"
 
 #include <string>
+#include <utility>
 
 namespace {
-struct DBuf {                                              // grow-only device buffer
-  void *p = nullptr; size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes < 256) bytes = 256;
-    if (cap >= bytes) return hipSuccess;
-    release();
-    const hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  void *take() { void *q = p; p = nullptr; cap = 0; return q; }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-  ~DBuf() { release(); }
-};
+using mgc::DBuf;
 
 int pos_fail(const char *who, const char *what) {
   mgc::lk_set_error(std::string(who) + ": " + what);
@@ -77,14 +65,13 @@ struct PairSort {
 struct mgc_posidx {
   mgc::PosTable t;
   uint64_t n_bases = 0, n_placed = 0, n_used = 0, longest = 0;
-  uint32_t *d_ref_slot = nullptr, *d_pos_data = nullptr;
-  uint64_t *d_pos_start = nullptr;
+  DBuf d_ref_slot, d_pos_start, d_pos_data;                  // uint32[n_bases], uint64[n + 1], uint32[n_placed]
 };
 
 struct mgc_paint {
   const mgc_posidx *idx = nullptr;
   uint32_t what = 0;
-  uint32_t *d_hits = nullptr, *d_queries = nullptr;         // per slot: H and Q
+  DBuf d_hits, d_queries;                                   // per slot: H and Q (uint32 each; unallocated when not opened)
   DBuf slot, scratch;
   PairSort pairs;
 };
@@ -92,9 +79,6 @@ struct mgc_paint {
 extern "C" void mgc_posidx_free(mgc_posidx *idx) {
   if (!idx) return;
   (void)hipSetDevice(idx->t.device);
-  if (idx->d_ref_slot) (void)hipFree(idx->d_ref_slot);
-  if (idx->d_pos_start) (void)hipFree(idx->d_pos_start);
-  if (idx->d_pos_data) (void)hipFree(idx->d_pos_data);
   delete idx;
 }
 
@@ -112,20 +96,23 @@ extern "C" mgc_posidx *mgc_posidx_build(const mgc_lookup *table, const uint8_t *
   DBuf scratch, stats;
   uint64_t h_stats[2] = {0, 0};
   hipError_t e = hipSetDevice(t.device);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&idx->d_ref_slot), sizeof(uint32_t) * (n_bases ? n_bases : 1));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&idx->d_pos_start), sizeof(uint64_t) * (t.n + 1));
-  if (e == hipSuccess) e = mgc::launch_pos_slots(t, d_ref_bases, n_bases, idx->d_ref_slot, nullptr, 0, nullptr, nullptr, nullptr, st);
-  if (e == hipSuccess) e = ps.run(idx->d_ref_slot, n_bases, nullptr, 0, t.n, st);
+  uint32_t *d_ref_slot = nullptr;
+  uint64_t *d_pos_start = nullptr;
+  if (e == hipSuccess) e = idx->d_ref_slot.ensure(sizeof(uint32_t) * n_bases);
+  if (e == hipSuccess) e = idx->d_pos_start.ensure(sizeof(uint64_t) * (t.n + 1));
+  if (e == hipSuccess) { d_ref_slot = idx->d_ref_slot.as<uint32_t>(); d_pos_start = idx->d_pos_start.as<uint64_t>(); }
+  if (e == hipSuccess) e = mgc::launch_pos_slots(t, d_ref_bases, n_bases, d_ref_slot, nullptr, 0, nullptr, nullptr, nullptr, st);
+  if (e == hipSuccess) e = ps.run(d_ref_slot, n_bases, nullptr, 0, t.n, st);
   if (e == hipSuccess) e = scratch.ensure(sizeof(uint64_t) * mgc::pos_starts_scratch_elems(t.n));
   if (e == hipSuccess) e = stats.ensure(sizeof(h_stats));
   if (e == hipSuccess) e = hipMemsetAsync(stats.p, 0, sizeof(h_stats), st);
-  if (e == hipSuccess) e = mgc::launch_pos_starts(ps.keys(), ps.n, t.n, idx->d_pos_start, scratch.as<uint64_t>(), st);
-  if (e == hipSuccess) e = mgc::launch_pos_list_stats(idx->d_pos_start, t.n, stats.as<uint64_t>(), st);
+  if (e == hipSuccess) e = mgc::launch_pos_starts(ps.keys(), ps.n, t.n, d_pos_start, scratch.as<uint64_t>(), st);
+  if (e == hipSuccess) e = mgc::launch_pos_list_stats(d_pos_start, t.n, stats.as<uint64_t>(), st);
   if (e == hipSuccess) e = hipMemcpyAsync(h_stats, stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) { pos_rc(e, who); mgc_posidx_free(idx); return nullptr; }
   idx->n_placed = ps.n; idx->n_used = h_stats[0]; idx->longest = h_stats[1];
-  if (ps.n) idx->d_pos_data = reinterpret_cast<uint32_t *>(ps.v[ps.in_alt].take());     // the sorted payloads ARE the lists
+  if (ps.n) idx->d_pos_data = std::move(ps.v[ps.in_alt]);   // the sorted payloads ARE the lists
   return idx;
 }
 
@@ -140,23 +127,21 @@ extern "C" int mgc_posidx_get_info(const mgc_posidx *idx, mgc_posidx_info *info)
 
 extern "C" int mgc_posidx_arrays(const mgc_posidx *idx, const uint32_t **d_ref_slot, const uint64_t **d_pos_start, const uint32_t **d_pos_data) {
   if (!idx) return pos_fail("mgc_posidx_arrays", "no index");
-  if (d_ref_slot) *d_ref_slot = idx->d_ref_slot;
-  if (d_pos_start) *d_pos_start = idx->d_pos_start;
-  if (d_pos_data) *d_pos_data = idx->d_pos_data;
+  if (d_ref_slot) *d_ref_slot = idx->d_ref_slot.as<uint32_t>();
+  if (d_pos_start) *d_pos_start = idx->d_pos_start.as<uint64_t>();
+  if (d_pos_data) *d_pos_data = idx->d_pos_data.as<uint32_t>();
   return MGC_OK;
 }
 
 extern "C" int mgc_posidx_find(const mgc_posidx *idx, const void *d_kmers, uint64_t n, uint64_t *d_begin, uint32_t *d_count, void *stream) {
   if (!idx) return pos_fail("mgc_posidx_find", "no index");
   if (n && (!d_kmers || !d_begin || !d_count)) return pos_fail("mgc_posidx_find", "no k-mers or no outputs");
-  return pos_rc(mgc::launch_pos_find(idx->t, d_kmers, n, idx->d_pos_start, d_begin, d_count, (hipStream_t)stream), "mgc_posidx_find");
+  return pos_rc(mgc::launch_pos_find(idx->t, d_kmers, n, idx->d_pos_start.as<uint64_t>(), d_begin, d_count, (hipStream_t)stream), "mgc_posidx_find");
 }
 
 extern "C" void mgc_paint_close(mgc_paint *p) {
   if (!p) return;
   (void)hipSetDevice(p->idx->t.device);
-  if (p->d_hits) (void)hipFree(p->d_hits);
-  if (p->d_queries) (void)hipFree(p->d_queries);
   delete p;
 }
 
@@ -171,10 +156,10 @@ extern "C" mgc_paint *mgc_paint_open(const mgc_posidx *idx, uint32_t what) {
   p->idx = idx; p->what = what;
   const size_t bytes = sizeof(uint32_t) * (idx->t.n ? idx->t.n : 1);
   hipError_t e = hipSetDevice(idx->t.device);
-  for (uint32_t **a : {&p->d_hits, &p->d_queries}) {
+  for (DBuf *a : {&p->d_hits, &p->d_queries}) {
     if (!(what & (a == &p->d_hits ? MGC_PAINT_MERS : MGC_PAINT_QUERIES))) continue;
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(a), bytes);
-    if (e == hipSuccess) e = hipMemset(*a, 0, bytes);
+    if (e == hipSuccess) e = a->ensure(bytes);
+    if (e == hipSuccess) e = hipMemset(a->p, 0, bytes);
   }
   if (e != hipSuccess) { pos_rc(e, who); mgc_paint_close(p); return nullptr; }
   return p;
@@ -206,14 +191,14 @@ extern "C" int mgc_paint_add(mgc_paint *p, const uint8_t *d_bases, uint64_t n_ba
   const bool paint = (p->what & (MGC_PAINT_MERS | MGC_PAINT_QUERIES)) != 0;
   if (paint) e = p->slot.ensure(sizeof(uint32_t) * n_bases);
   if (e == hipSuccess)
-    e = mgc::launch_pos_slots(idx->t, d_bases, n_bases, paint ? p->slot.as<uint32_t>() : nullptr, d_seq_start, n_seq, idx->d_pos_start,
+    e = mgc::launch_pos_slots(idx->t, d_bases, n_bases, paint ? p->slot.as<uint32_t>() : nullptr, d_seq_start, n_seq, idx->d_pos_start.as<uint64_t>(),
                               hits ? d_t_cov : nullptr, hits ? d_n_per : nullptr, st);
   if (e == hipSuccess && paint) {
     PairSort &ps = p->pairs;
     e = ps.run(p->slot.as<uint32_t>(), n_bases, d_seq_start, n_seq, idx->t.n, st);
     if (e == hipSuccess && ps.n) e = p->scratch.ensure(sizeof(uint64_t) * mgc::pos_sums_scratch_elems(ps.n));
     if (e == hipSuccess && ps.n)
-      e = mgc::launch_pos_slot_sums(ps.keys(), ps.vals(), ps.n, p->d_hits, p->d_queries, ps.other_keys(), p->scratch.as<uint64_t>(), st);
+      e = mgc::launch_pos_slot_sums(ps.keys(), ps.vals(), ps.n, p->d_hits.as<uint32_t>(), p->d_queries.as<uint32_t>(), ps.other_keys(), p->scratch.as<uint64_t>(), st);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);          // the batch's buffers are the next batch's
   return pos_rc(e, who);
@@ -225,6 +210,6 @@ extern "C" int mgc_paint_get(const mgc_paint *p, uint32_t which, uint32_t *d_out
   if (which != MGC_PAINT_MERS && which != MGC_PAINT_QUERIES) return pos_fail(who, "'which' is MGC_PAINT_MERS or MGC_PAINT_QUERIES");
   if (!(p->what & which)) return pos_fail(who, "this output was not opened");
   if (p->idx->n_bases && !d_out) return pos_fail(who, "no output");
-  return pos_rc(mgc::launch_pos_gather(p->idx->d_ref_slot, p->idx->n_bases, which == MGC_PAINT_MERS ? p->d_hits : p->d_queries, d_out,
+  return pos_rc(mgc::launch_pos_gather(p->idx->d_ref_slot.as<uint32_t>(), p->idx->n_bases, (which == MGC_PAINT_MERS ? p->d_hits : p->d_queries).as<uint32_t>(), d_out,
                                        (hipStream_t)stream), who);
 }

@@ -211,7 +211,7 @@ static inline uint32_t pos_grid(uint64_t n) { uint64_t g = (n + 255) / 256; if (
 
 PosTable pos_table_of(const mgc_lookup *t) {
   PosTable p;
-  p.keys = t->d_keys; p.index = t->d_index; p.n = t->n; p.n_index = 1ull << t->index_bits;
+  p.keys = t->d_keys.p; p.index = t->d_index.as<uint64_t>(); p.n = t->n; p.n_index = 1ull << t->index_bits;
   p.k = t->k; p.key_words = t->kw; p.shift = t->shift; p.device = t->device;
   return p;
 }

@@ -63,8 +63,6 @@ mgc_runs::~mgc_runs() {
   (void)hipSetDevice(device);
   drop_prealloc();
   for (Run &r : runs) free_run(r);
-  for (auto &b : buf) b.release();
-  d_slices.release();
   if (st_copy) (void)hipStreamDestroy(st_copy);
   if (st_up) (void)hipStreamDestroy(st_up);
   if (st_mg) (void)hipStreamDestroy(st_mg);

@@ -1,9 +1,12 @@
 // mgc_session.hpp -- the session object behind include/meryl_gpu_count.h and the helpers its translation units
-// (mgc_api.cpp: input + batches; mgc_textfile.cpp: whole-file readers; mgc_count.cpp: counting; mgc_stream.cpp: delivery of the result, database streaming; mgc_eval.cpp: operations over databases) share.  Internal.
+// (mgc_api.cpp: input + batches; mgc_textfile.cpp: whole-file readers; mgc_count.cpp: counting; mgc_stream.cpp: delivery of the result,
+// database streaming; mgc_eval.cpp: operations over databases) share.  The owning device buffer they use, mgc::DBuf, is mgc_devbuf.hpp's;
+// the session's arena below is a different thing (grow-only for the session's life, traced by MGC_IO_TRACE).  Internal.
 #pragma once
 
 #include "../../include/meryl_gpu_count.h"
 #include "mgc_clock.hpp"
+#include "mgc_devbuf.hpp"
 #include "mgc_device.h"
 
 #include <cstdarg>
@@ -33,20 +36,6 @@ inline void set_err(std::string *dst, const char *fmt, ...) {
   }
   thread_last_error() = buf;
 }
-
-struct DBuf {                                             // grow-only device buffer
-  void *p = nullptr; size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes < 256) bytes = 256;
-    if (cap >= bytes) return hipSuccess;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
 }  // namespace mgc
 
 #define HIP_TRY(s, expr)                                                                         \

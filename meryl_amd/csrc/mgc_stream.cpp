@@ -429,8 +429,6 @@ extern "C" int mgc_db_stream_close(mgc_db_stream *d, mgc_db_write_profile *prof)
   if (rc == MGC_OK && rc2 != MGC_OK) { rc = rc2; d->err = std::string("closing the database: ") + mdb_last_error(); }
   if (rc != MGC_OK) set_err(nullptr, "%s", d->err.c_str());
   (void)hipSetDevice(d->device);
-  d->d_bs.release(); d->d_bytes.release(); d->d_vbase.release(); d->d_bb.release(); d->d_pos.release();
-  d->d_hist.release(); d->d_big.release(); d->d_img[0].release(); d->d_img[1].release();
   for (int i = 0; i < NSLOT; i++) if (d->pinned[i]) (void)hipHostFree(d->pinned[i]);
   for (int i = 0; i < 2; i++) if (d->ev_enc[i]) (void)hipEventDestroy(d->ev_enc[i]);
   if (d->ev_a) (void)hipEventDestroy(d->ev_a);
@@ -616,25 +614,19 @@ int deliver_view(mgc_session *s, const ResultView &view, mgc_block_cb cb1, mgc_b
 // chunk's buffers are free again when put() returns.  Chunks ascend, so every file still sees its prefixes in order.
 struct CallbackSink : mgc::RunSink {
   mgc_session *s; mgc_block_cb cb1; mgc_block_cb2 cb2; void *ctx; int host_threads;
-  void *d_bs = nullptr; size_t bs_cap = 0;
+  DBuf d_bs;
   std::string msg;
   uint64_t n_delivered = 0;
   CallbackSink(mgc_session *s_, mgc_block_cb a, mgc_block_cb2 b, void *c, int t) : s(s_), cb1(a), cb2(b), ctx(c), host_threads(t) {}
-  ~CallbackSink() override { if (d_bs) (void)hipFree(d_bs); }
   int put(const void *k, const uint32_t *c, uint64_t n, uint64_t sa, uint64_t sb, uint32_t slice_bits, uint64_t *job) override {
     *job = 0;
     const uint32_t sh = s->cfg.w_prefix - slice_bits;
     const uint64_t pb = sa << sh, pe = sb << sh, nblk = pe - pb;
     const size_t need = sizeof(uint64_t) * (nblk + 1);
-    if (bs_cap < need) {
-      if (d_bs) (void)hipFree(d_bs);
-      d_bs = nullptr; bs_cap = 0;
-      if (hipMalloc(&d_bs, need) != hipSuccess) { msg = "mgc_finish: out of device memory for the block offsets of a chunk"; return MGC_ENOMEM; }
-      bs_cap = need;
-    }
+    if (d_bs.ensure(need) != hipSuccess) { msg = "mgc_finish: out of device memory for the block offsets of a chunk"; return MGC_ENOMEM; }
     std::vector<uint64_t> h_bs(nblk + 1);
-    hipError_t e = mgc::launch_block_offsets_range(k, n, s->key_words, s->cfg.w_data, pb, nblk, s->cfg.n_prefix, reinterpret_cast<uint64_t *>(d_bs), s->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_bs.data(), d_bs, need, hipMemcpyDeviceToHost, s->stream);
+    hipError_t e = mgc::launch_block_offsets_range(k, n, s->key_words, s->cfg.w_data, pb, nblk, s->cfg.n_prefix, d_bs.as<uint64_t>(), s->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_bs.data(), d_bs.p, need, hipMemcpyDeviceToHost, s->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     if (e != hipSuccess) { msg = std::string("mgc_finish: block offsets of a chunk: ") + hipGetErrorString(e); return MGC_EHIP; }
     if (h_bs[0] != 0 || h_bs[nblk] != n) { msg = "mgc_finish: a merged chunk holds k-mers outside its prefix range"; return MGC_EINVAL; }

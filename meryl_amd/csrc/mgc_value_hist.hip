@@ -149,11 +149,7 @@ struct mgc_value_hist {
   bool rows_ok = false;
   bool failed = false;                      // an add failed part of the way: the dense bins may hold values the list lost
 
-  ~mgc_value_hist() {
-    if (!ready) return;
-    (void)hipSetDevice(device);
-    for (DBuf *b : {&d_dense, &d_ctr, &d_list[0], &d_list[1], &d_sws, &d_rws, &d_uniq, &d_ucnt}) b->release();
-  }
+  ~mgc_value_hist() { if (d_dense.p) (void)hipSetDevice(device); }      // (the buffers go after this body, on that device)
 
 #define VH_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) {                                         \
     set_err(nullptr, "mgc_value_hist: %s -> %s", #expr, hipGetErrorString(e__));                                  \

@@ -6,18 +6,22 @@ A synthetic genome (GENOME_MBP Mbp, default 300, cut into 50 Mbp "chromosomes" w
 looked up in the counted table:
   * mgc_lookup_positions for presence / count / depth, in windows per second (HIP events, median of 5 after a warm-up);
   * mgc_lookup_existence on the same stream and table -- presence with one table costs the same lookups per window;
+  * Lookup.load of the counted table written to a database (min_value 2), in seconds (median of 3 after a warm-up);
   * mgc_lookup_report end to end for every mode into a sink callback, in GB of text per second.
 usage: python scripts/lookup_bench.py [GENOME_MBP] > profiles/lookup_bench.json   (one JSON object per line)"""
 import ctypes
 import json
+import os
+import shutil
 import statistics
 import sys
+import tempfile
 import time
 
 sys.path.insert(0, '.')
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from meryl_amd import capi, count, lookup  # noqa: E402
+from meryl_amd import capi, count, db, lookup  # noqa: E402
 
 K = 21
 genome_mbp = int(sys.argv[1]) if len(sys.argv) > 1 else 300
@@ -49,6 +53,8 @@ with count.Session(cfg, 0) as s:
     s.count()
     keys, cnts = s.result_device()
     table = lookup.Lookup.from_device(keys, cnts, K)
+    work = tempfile.mkdtemp(prefix="lookup_bench.")
+    db.write_database(s, os.path.join(work, "reads.meryl"))
 del reads, keys, cnts
 torch.cuda.empty_cache()
 
@@ -85,6 +91,18 @@ def emit(**kv):
 
 emit(what="setup", genome_bases=n, k=K, table_kmers=int(table.info.n_kmers), index_bits=int(table.info.index_bits),
      read_coverage=10, sequences=len(names))
+# the table loaded from its database: 64 data files read by host threads, decoded and value-filtered on the device
+load_s = []
+for rep in range(4):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    loaded = lookup.Lookup.load(os.path.join(work, "reads.meryl"), min_value=2)
+    load_s.append(time.perf_counter() - t0)
+    load_kmers = int(loaded.info.n_kmers)
+    loaded.close()
+shutil.rmtree(work)
+emit(what="load", min_value=2, seconds=round(statistics.median(load_s[1:]), 4), table_kmers=load_kmers,
+     kmers_in_db_per_s=round(int(table.info.n_kmers) / statistics.median(load_s[1:])), samples_s=[round(x, 4) for x in load_s[1:]])
 out = torch.empty(n, dtype=torch.int32, device=dev)
 arr = (ctypes.c_void_p * 1)(table._h)
 res = {}
