@@ -1045,6 +1045,7 @@ int Count::block_offsets() {
   if (s->profiling) (void)hipEventRecord(ev_all[1], st);
   HIP_TRY(s, hipStreamSynchronize(st));
   if (h_err[0]) { mgc::set_err(&s->err, "radix sort look-back timed out"); return MGC_ETIMEOUT; }
+  if (h_err[2]) { mgc::set_err(&s->err, "count stage: the retry table of the distinct-sized count filled up, a sub-bucket was not counted"); return MGC_EHIP; }
   return MGC_OK;
 }
 

@@ -931,25 +931,30 @@ void hash_count_multi_kernel(u32 *__restrict__ keys, const u64 *__restrict__ sta
 //   * a table entry is suffix << 12 | count (suffix <= 20 bits, a count <= 4094 so that EMPTY = all ones is no entry): the claiming
 //     CAS deposits count 1, a duplicate adds 1, entry order == suffix order;
 //   * the table holds SLOTS entries and the claim list DCAP of them -- capacity in DISTINCT suffixes.  A sub-bucket that claims more
-//     (low coverage: D ~ N), or whose probes run long because the table fills, raises s_ovf: nothing of it is written, its number
-//     goes on the retry list, and the LIST instantiation (SLOTS = 8192, DCAP >= max_size: cannot overflow) counts it afterwards;
+//     (low coverage: D ~ N), or one of whose keys probes more than PROBE_MAX steps (the table fills, or many suffixes share a home
+//     slot: the multiplicative hash does that to structured suffixes, multiples of Fibonacci numbers for one), raises s_ovf: nothing
+//     of it is written, its number goes on the retry list, and the RETRY instantiation (SLOTS = 8192, DCAP >= max_size) counts it
+//     afterwards.  That one has nowhere to send a sub-bucket, so it probes for as long as it takes: its table is at most half full
+//     (slots_for(n) >= 2n up to max_size <= 4094), a probe ends within one turn of it whatever the suffixes are, and the turn is
+//     the bound -- reached only if the table were full, which raises the count's error word error[2] (the count then ends with an
+//     error code instead of a result that lacks the sub-bucket);
 //   * the per-distinct phases are hash_count_multi_kernel's (256 bins by the top eight suffix bits, one-wave scan with the table
 //     cleared in its shadow, rank inside the bin) with up to TWO entries per thread in registers (D <= 512), staged through LDS above.
 // LIST: visit the sub-buckets visit[0 .. *visit_count) (a sparse grid's non-empty list; the retry list); otherwise all ng.
-// retry_list == nullptr: the retry launch itself.
-template <typename KT, int BLOCK, int KPC, int SLOTS, int DCAP, bool LIST, bool DBG>
+// RETRY: the retry launch itself (retry_list is not used).
+template <typename KT, int BLOCK, int KPC, int SLOTS, int DCAP, bool LIST, bool DBG, bool RETRY>
 __global__ __launch_bounds__(BLOCK, (sizeof(KT) == 8 ? (SLOTS <= 2048 ? 5 : 1) : (SLOTS <= 2048 ? 8 : 2)))
 void hash_count_stream_kernel(KT *__restrict__ keys, const u64 *__restrict__ starts, u64 ng, u64 max_size_, u32 low_bits,
                               u32 *__restrict__ cnt_tmp, u64 *__restrict__ group_distinct, u64 *__restrict__ dbg,
                               u32 tr_a, u32 tr_b, const u32 *__restrict__ visit, const u64 *__restrict__ visit_count,
-                              u32 *__restrict__ retry_list, u64 *__restrict__ retry_count) {
+                              u32 *__restrict__ retry_list, u64 *__restrict__ retry_count, u32 *__restrict__ error) {
   static_assert((SLOTS & (SLOTS - 1)) == 0 && SLOTS % (4 * BLOCK) == 0 && DCAP <= SLOTS && DCAP <= 65536 && BLOCK == 256, "table geometry");
   static_assert(sizeof(KT) == 4 || sizeof(KT) == 8, "32-bit words of a narrowed file, or whole 8-byte k-mers");
   constexpr bool W64 = sizeof(KT) == 8;                               // whole k-mers: 64-bit entries, the bits above the suffix put back on the way out
   constexpr u32 CNTB = 12u, CNT_MASK = (1u << CNTB) - 1u;
   constexpr KT EMPTY = (KT)~(KT)0;
   constexpr u32 CH = (u32)(BLOCK * KPC);
-  constexpr u32 PROBE_MAX = 64u;                                     // probe steps of one key beyond which the table counts as full
+  constexpr u32 PROBE_MAX = 64u;                                     // probe steps of one key beyond which the sub-bucket goes to the retry launch
   __shared__ __attribute__((aligned(16))) KT tk[SLOTS];             // suffix << 12 | count
   __shared__ __attribute__((aligned(16))) KT srt[DCAP];             // the distinct entries in bin order
   __shared__ unsigned short lst[DCAP];                              // slots of the claimed entries, in claim order
@@ -1043,6 +1048,7 @@ void hash_count_stream_kernel(KT *__restrict__ keys, const u64 *__restrict__ sta
     const bool last = !active || rest <= csz;
     const u32 slots = slots_for(n0);
     const u32 smask = slots - 1, sshift = 32 - (u32)__builtin_ctz(slots);
+    const u32 probe_max = RETRY ? slots : PROBE_MAX;               // (RETRY: one full turn of the table -- every slot has been looked at)
     // the chunk that was loaded a whole chunk ago is consumed into comp[]; only then the next one is issued (a wait for old
     // registers behind new loads would wait for the new loads: hash_count_multi_kernel)
     if constexpr (W64) { if (off == 0u) pre = kcur[0] & ~low_mask; }   // (every lane holds a key of the sub-bucket: lanes past the end re-read the last one)
@@ -1107,7 +1113,7 @@ void hash_count_stream_kernel(KT *__restrict__ keys, const u64 *__restrict__ sta
             if (w || dup) pending &= ~(1u << j);
           }
         }
-        if (++steps > PROBE_MAX) { s_ovf = 1u; pending = 0; }       // the table is (nearly) full: more distinct suffixes than it holds
+        if (++steps > probe_max) { s_ovf = 1u; pending = 0; }       // a long chain: the table fills, or the suffixes crowd a few home slots
       }
       {
         u64 wm[KPC];
@@ -1211,14 +1217,15 @@ void hash_count_stream_kernel(KT *__restrict__ keys, const u64 *__restrict__ sta
         par ^= 1u;                                     // (srt and this parity's bin table are next written three barriers on)
         HC_STAMP(4);
       } else {
-        // more distinct suffixes than the table or the list holds: nothing is written, the retry launch takes the sub-bucket
+        // more distinct suffixes than the list holds, or a probe chain above the bound: nothing is written, the retry launch takes
+        // the sub-bucket.  RETRY: a whole turn of the table found no room, which the launcher's sizes exclude -- the count's error word is raised
         __syncthreads();                               // (everybody has read s_ovf and s_nd)
         uint4 *tk4 = reinterpret_cast<uint4 *>(tk);
         for (u32 i = tid; i < (u32)SLOTS / E16; i += BLOCK) tk4[i] = make_uint4(ONES, ONES, ONES, ONES);
         if (tid == 0) {
           s_nd = 0; s_ovf = 0;
-          if (retry_list) retry_list[atomicAdd((unsigned long long *)retry_count, 1ull)] = g;
-          else            group_distinct[tr_index(g, tr_a, tr_b)] = 0; // (the retry launch: DCAP >= max_size, does not happen)
+          if constexpr (RETRY) { atomicExch(error + 2, 1u); group_distinct[tr_index(g, tr_a, tr_b)] = 0; }
+          else                 retry_list[atomicAdd((unsigned long long *)retry_count, 1ull)] = g;
         }
         cleared = (u32)SLOTS;
         __syncthreads();
@@ -2595,12 +2602,13 @@ static hipError_t launch_multi(const FinishFile &f, u64 *dbg) {
 // hash_count_stream_kernel (the distinct-sized count): one sub-bucket of up to stream_cap keys per iteration, streamed through a
 // SLOTS-entry table in chunks; a sub-bucket with more than DCAP distinct suffixes lands on `overflow` (the retry list).  The
 // instrumented instantiation exists for u32 keys without a list only.
-template <typename KT, int SLOTS, int DCAP, bool LIST, bool DBG>
+template <typename KT, int SLOTS, int DCAP, bool LIST, bool DBG, bool RETRY = false>
 static hipError_t launch_stream(const FinishFile &f, uint64_t items, uint32_t max_wgs, const uint32_t *list, const uint64_t *list_count,
                                 u32 *overflow, uint64_t *overflow_count, u64 *dbg = nullptr) {
-  hipLaunchKernelGGL((hash_count_stream_kernel<KT, 256, FIN_STREAM_KPC, SLOTS, DCAP, LIST, DBG>), dim3(fin_grid(items, max_wgs)), dim3(256), 0,
+  if (RETRY ? !f.d_error : !overflow) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((hash_count_stream_kernel<KT, 256, FIN_STREAM_KPC, SLOTS, DCAP, LIST, DBG, RETRY>), dim3(fin_grid(items, max_wgs)), dim3(256), 0,
                      f.st, reinterpret_cast<KT *>(f.keys), fin_starts(f), (u64)f.ng, (u64)f.stream_cap, f.low_bits, f.cnt_tmp, fin_distinct(f),
-                     dbg, f.tr_a, f.tr_b, list, reinterpret_cast<const u64 *>(list_count), overflow, reinterpret_cast<u64 *>(overflow_count));
+                     dbg, f.tr_a, f.tr_b, list, reinterpret_cast<const u64 *>(list_count), overflow, reinterpret_cast<u64 *>(overflow_count), f.d_error);
   MGC_CHECK(hipGetLastError());
   if (DBG) hash_dbg_report(f.st, f.ng, true);
   return hipSuccess;
@@ -2873,7 +2881,8 @@ hipError_t launch_finish_file(const FinishFile &f) {
   return launch_oversized(f);
 }
 
-// the retry list of hash_count_stream_kernel: the same kernel with a table no sub-bucket of up to FIN_CAP_STREAM keys can overflow
+// the retry list of hash_count_stream_kernel: the same kernel with a table no sub-bucket of up to FIN_CAP_STREAM keys can fill (at
+// most half full), probing without the first launch's step bound
 hipError_t launch_finish_retry(const FinishFile &f, uint64_t n_retry) {
   const bool narrow = f.layout == FinishKeys::NARROW32;
   if (n_retry == 0) return hipSuccess;
@@ -2886,7 +2895,8 @@ hipError_t launch_finish_retry(const FinishFile &f, uint64_t n_retry) {
                            : launch_huge_mode<Huge8<u64, u64>, 0>(f, f.retry_list, (uint32_t)n_retry, 0, 0, HugeSliced(), f.st);
   }
   static_assert(FIN_STREAM_RETRY_DCAP >= (int)FIN_CAP_STREAM, "the retry table holds every suffix of a sub-bucket");
-  return launch_stream<u32, FIN_STREAM_RETRY_SLOTS, FIN_STREAM_RETRY_DCAP, true, false>(f, n_retry, 256u * 2u, f.retry_list, f.retry_count, nullptr, nullptr);
+  static_assert(FIN_STREAM_RETRY_SLOTS >= 2 * (int)FIN_CAP_STREAM, "... and stays at most half full: every probe ends");
+  return launch_stream<u32, FIN_STREAM_RETRY_SLOTS, FIN_STREAM_RETRY_DCAP, true, false, true>(f, n_retry, 256u * 2u, f.retry_list, f.retry_count, nullptr, nullptr);
 }
 
 bool     finish_stream_ok(uint32_t key_words, uint32_t low_bits, bool narrow) { return key_words == 1 && low_bits >= 8 && low_bits <= (narrow ? 20u : 52u); }
