@@ -168,16 +168,6 @@ int mgc_dev_rle_count(const void *d_sorted, uint64_t n, uint32_t key_words, void
 int mgc_dev_rle_emit(const void *d_sorted, uint64_t n, uint32_t key_words, void *d_workspace,
                      size_t workspace_bytes, void *d_unique, uint32_t *d_counts, void *stream);
 
-/* For measurements only (scripts/setops_bench.py --legs h): the histogram pass of the database writer (mgc_db_stream, include/meryl_db.h)
- * on its own, a copy that must mirror mgc_db_stream::process -- its kernel, its
- * list of every value above mgc_dev_value_hist_listed_bins(), the list's copy to the host and its element-by-element insertion
- * into a std::map.  d_hist: bins + 1 device uint64; d_big: big_cap >= n device uint32.  *n_pairs: distinct values; *n_listed:
- * values that went through the list. */
-uint32_t mgc_dev_value_hist_listed_bins(void);
-int  mgc_dev_value_hist_listed(const uint32_t *d_values, uint64_t n, uint64_t *d_hist, uint32_t *d_big, uint64_t big_cap, void *stream,
-                               uint64_t *n_pairs, uint64_t *n_listed);
-
-
 /* d_block_start[p] = index of the first distinct key with (key >> w_data) >= p,
  * for p in [0, n_prefix]; block p of the database is
  * [d_block_start[p], d_block_start[p+1]) -- the (prefix, nKmers) of addBlock. */

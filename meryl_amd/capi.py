@@ -40,7 +40,7 @@ SYMBOLS = (
     "mdb_free", "mgc_write_database", "mgc_write_database_profiled",
     "mgc_db_stream_open", "mgc_db_stream_write", "mgc_db_stream_write_labelled", "mgc_db_eval_labelled", "mgc_db_eval_selected", "mgc_db_eval_assigned", "mgc_db_eval_reported", "mgc_db_stream_sync", "mgc_db_stream_close", "mgc_db_stream_error", "mgc_db_stream_queued", "mgc_db_stream_done", "mgc_db_stream_wait_buffers",
     "mgc_value_hist_open", "mgc_value_hist_add", "mgc_value_hist_len", "mgc_value_hist_get", "mgc_value_hist_totals", "mgc_value_hist_close",
-    "mgc_value_hist_geometry", "mdb_format_statistics", "mgc_dev_value_hist_listed_bins", "mgc_dev_value_hist_listed",
+    "mgc_value_hist_geometry", "mdb_format_statistics",
     "mgc_runs_open", "mgc_runs_add", "mgc_runs_write", "mgc_runs_get_profile", "mgc_runs_error", "mgc_runs_close", "mgc_get_runs_profile", "mgc_db_merge", "mgc_db_filter", "mgc_db_eval", "mgc_count_node", "mgc_count_node_batched", "mgc_count_node_staged", "mgc_node_plan",
     # include/meryl_lookup.h
     "mgc_lookup_load", "mgc_lookup_estimate", "mgc_lookup_from_device", "mgc_lookup_free", "mgc_lookup_get_info", "mgc_lookup_error",
@@ -541,8 +541,6 @@ def lib():
     sig("mgc_value_hist_totals", i32, vp, P(u64), P(u64), P(u64))
     sig("mgc_value_hist_close", None, vp)
     sig("mgc_value_hist_geometry", None, P(u32), P(u32))
-    sig("mgc_dev_value_hist_listed_bins", u32)
-    sig("mgc_dev_value_hist_listed", i32, vp, u64, vp, vp, u64, vp, P(u64), P(u64))
     sig("mdb_format_statistics", sz, u32, vp, vp, u64, u64, u64, u64, ctypes.c_char_p, sz)
     sig("mgc_count_node", i32, P(CountConfig), u32, P(ctypes.c_int), P(vp), P(u64), ctypes.c_char_p, i32, P(NodeProfile))
     sig("mgc_count_node_batched", i32, P(CountConfig), u32, P(ctypes.c_int), P(vp), P(u64), u64, ctypes.c_char_p, i32, P(NodeProfile))

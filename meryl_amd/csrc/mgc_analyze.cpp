@@ -4,12 +4,14 @@
 // inserts its value into a std::map per (histogram, score) (:171-223, :257-322, :359-424); printHist (:139-152) writes the
 // maps out.  Here a file's raw bytes are read by host threads, uploaded and decoded on the device (mgc_decode.hip) while
 // the next files are read; the decoded arrays go through the score + histogram kernel (mgc_analyze.hip); what its dense tier
-// does not take is sorted and run-length counted on the device and merged into a sorted host list.
+// does not take goes through the one list tier of mgc_hist_list.hpp: sorted and run-length counted on the device, merged into a
+// sorted host list.
 #include "../../include/meryl_analyze.h"
 #include "../../include/meryl_db.h"
 #include "mgc_analyze_dev.hpp"
 #include "mgc_dbfile.hpp"
 #include "mgc_device.h"
+#include "mgc_hist_list.hpp"
 #include "mgc_runs.hpp"
 
 #include <algorithm>
@@ -44,7 +46,7 @@ bool have_device() {
 }
 
 constexpr uint64_t CHUNK = 1ull << 26;      // entries per kernel pass: bounds the overflow list (three 8-byte entries per k-mer at worst)
-struct Row { uint64_t key, n; };            // key = analyze_pack(histogram, score, value)
+typedef mgc::HistPair Row;                  // key = analyze_pack(histogram, score, value)
 }  // namespace
 
 struct mgc_analyze {
@@ -54,10 +56,10 @@ struct mgc_analyze {
   bool ready = false;
   hipStream_t st_own = nullptr;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  DBuf d_dense, d_ctr, d_list[2], d_sws, d_rws, d_uniq, d_ucnt;       // the accumulator
+  DBuf d_dense;                                                       // the accumulator: the dense tier ...
+  mgc::ListTier ovf{"meryl-analyze"};                                 // ... and what went through the overflow list
   mgc::DbFileScratch file_scratch;                                    // one database file
   DBuf d_keys, d_vals;
-  std::vector<Row> ovf;                     // what went through the overflow list, ascending by key
   std::vector<Row> rows[3];                 // result cache per histogram
   bool rows_ok[3] = {false, false, false};
   mgc_analyze_info info;
@@ -85,80 +87,37 @@ struct mgc_analyze {
     AN_TRY(hipStreamCreateWithFlags(&st_own, hipStreamNonBlocking));
     for (hipEvent_t &e : ev) AN_TRY(hipEventCreate(&e));
     AN_TRY(d_dense.ensure(dense_bytes()));
-    AN_TRY(d_ctr.ensure(256));
     AN_TRY(hipMemset(d_dense.p, 0, dense_bytes()));
     ready = true;
     return MGC_OK;
   }
 
-  // sorted distinct (key, count) of one pass -> ovf
-  void merge_overflow(const std::vector<uint64_t> &keys, const std::vector<uint32_t> &cnt) {
-    std::vector<Row> out;
-    out.reserve(ovf.size() + keys.size());
-    size_t i = 0, j = 0;
-    while (i < ovf.size() || j < keys.size()) {
-      if (j == keys.size() || (i < ovf.size() && ovf[i].key < keys[j])) out.push_back(ovf[i++]);
-      else if (i == ovf.size() || keys[j] < ovf[i].key) { out.push_back(Row{keys[j], cnt[j]}); j++; }
-      else { out.push_back(Row{keys[j], ovf[i].n + cnt[j]}); i++; j++; }
-    }
-    ovf.swap(out);
-  }
-
   int add_chunk(const void *keys, const uint32_t *vals, uint64_t n, hipStream_t st) {
     const uint32_t nh = mgc::analyze_device_hists(type);
-    uint64_t *d_list_n = d_ctr.as<uint64_t>();
-    uint32_t *d_sort_err = reinterpret_cast<uint32_t *>(d_ctr.as<unsigned char>() + 64);
     // the list starts at an eighth of the worst case (all of it when the dense tier is off) and grows to what a pass asked for
     const uint64_t first_cap = dense ? std::max<uint64_t>(n * nh / 8, 1u << 16) : n * nh;
-    if (d_list[0].cap < first_cap * 8) AN_TRY(d_list[0].ensure(first_cap * 8));
-    uint64_t cap = d_list[0].cap / 8, need = 0;
-    AN_TRY(hipMemsetAsync(d_ctr.p, 0, 128, st));
+    AN_TRY(ovf.reserve(first_cap));
+    uint64_t cap = ovf.capacity(), need = 0;
+    AN_TRY(ovf.reset(st));
     AN_TRY(hipEventRecord(ev[0], st));
-    AN_TRY(mgc::launch_analyze_hist(keys, vals, n, k, type, dense, true, d_dense.as<uint64_t>(), d_list[0].as<uint64_t>(), cap, d_list_n, n_cus, st));
-    AN_TRY(hipMemcpyAsync(&need, d_list_n, 8, hipMemcpyDeviceToHost, st));
+    AN_TRY(mgc::launch_analyze_hist(keys, vals, n, k, type, dense, true, d_dense.as<uint64_t>(), ovf.list(), cap, ovf.list_n(), n_cus, st));
+    AN_TRY(hipMemcpyAsync(&need, ovf.list_n(), 8, hipMemcpyDeviceToHost, st));
     AN_TRY(hipStreamSynchronize(st));
     if (need > cap) {                                       // the dense tier has counted its share: only the list is redone
-      AN_TRY(d_list[0].ensure(need * 8));
-      cap = d_list[0].cap / 8;
-      AN_TRY(hipMemsetAsync(d_ctr.p, 0, 128, st));
-      AN_TRY(mgc::launch_analyze_hist(keys, vals, n, k, type, dense, false, d_dense.as<uint64_t>(), d_list[0].as<uint64_t>(), cap, d_list_n, n_cus, st));
+      AN_TRY(ovf.reserve(need));
+      cap = ovf.capacity();
+      AN_TRY(ovf.reset(st));
+      AN_TRY(mgc::launch_analyze_hist(keys, vals, n, k, type, dense, false, d_dense.as<uint64_t>(), ovf.list(), cap, ovf.list_n(), n_cus, st));
       uint64_t again = 0;
-      AN_TRY(hipMemcpyAsync(&again, d_list_n, 8, hipMemcpyDeviceToHost, st));
+      AN_TRY(hipMemcpyAsync(&again, ovf.list_n(), 8, hipMemcpyDeviceToHost, st));
       AN_TRY(hipStreamSynchronize(st));
       if (again != need) { set_err(nullptr, "meryl-analyze: the overflow list changed size between passes"); return MGC_EHIP; }
       info.n_overflow_retries++;
     }
     AN_TRY(hipEventRecord(ev[1], st));
     info.n_overflow_kmers += need / nh;
-    if (need) {
-      AN_TRY(d_list[1].ensure(need * 8));
-      AN_TRY(d_sws.ensure(mgc::sort_workspace_bytes(need)));
-      AN_TRY(d_rws.ensure(mgc::rle_workspace_bytes(need)));
-      mgc::SortPlan plan;
-      mgc::make_sort_plan(0, mgc::ANALYZE_KEY_BITS, &plan);
-      int in_alt = 0;
-      AN_TRY(mgc::launch_radix_sort(d_list[0].p, d_list[1].p, need, 1, plan, d_sws.p, d_sws.cap, d_sort_err, &in_alt, st, nullptr));
-      const void *sorted = d_list[in_alt ? 1 : 0].p;
-      AN_TRY(mgc::launch_rle_count(sorted, need, 1, d_rws.p, st));
-      uint64_t nd = 0;
-      AN_TRY(mgc::rle_read_total(d_rws.p, &nd, st));        // (synchronises)
-      uint32_t h_err = 0;
-      AN_TRY(hipMemcpyAsync(&h_err, d_sort_err, 4, hipMemcpyDeviceToHost, st));
-      AN_TRY(d_uniq.ensure(nd * 8));
-      AN_TRY(d_ucnt.ensure(nd * 4));
-      AN_TRY(mgc::launch_rle_emit(sorted, need, 1, d_rws.p, d_uniq.p, d_ucnt.as<uint32_t>(), st));
-      std::vector<uint64_t> hk(nd);
-      std::vector<uint32_t> hc(nd);
-      AN_TRY(hipMemcpyAsync(hk.data(), d_uniq.p, nd * 8, hipMemcpyDeviceToHost, st));
-      AN_TRY(hipMemcpyAsync(hc.data(), d_ucnt.p, nd * 4, hipMemcpyDeviceToHost, st));
-      AN_TRY(hipEventRecord(ev[2], st));
-      AN_TRY(hipStreamSynchronize(st));
-      if (h_err) { set_err(nullptr, "meryl-analyze: radix sort look-back timed out"); return MGC_ETIMEOUT; }
-      merge_overflow(hk, hc);
-    } else {
-      AN_TRY(hipEventRecord(ev[2], st));
-      AN_TRY(hipEventSynchronize(ev[2]));
-    }
+    const int rc = ovf.drain(need, mgc::ANALYZE_KEY_BITS, st, ev[2]);
+    if (rc != MGC_OK) return rc;
     float ms = 0;
     AN_TRY(hipEventElapsedTime(&ms, ev[0], ev[1])); info.hist_ms += ms;
     AN_TRY(hipEventElapsedTime(&ms, ev[1], ev[2])); info.overflow_ms += ms;
@@ -271,8 +230,8 @@ struct mgc_analyze {
           if (const uint64_t c = hd[(size_t)s * MGC_ANALYZE_DENSE_VALUES + v]) put(s, v, c);
     }
     const uint64_t lo = mgc::analyze_pack(h, 0, 0), hi = mgc::analyze_pack(h + 1, 0, 0);
-    auto it = std::lower_bound(ovf.begin(), ovf.end(), lo, [](const Row &a, uint64_t key) { return a.key < key; });
-    for (; it != ovf.end() && it->key < hi; ++it) put((uint32_t)(it->key >> 32) & 127u, (uint32_t)it->key, it->n);
+    auto it = std::lower_bound(ovf.acc.begin(), ovf.acc.end(), lo, [](const Row &a, uint64_t key) { return a.key < key; });
+    for (; it != ovf.acc.end() && it->key < hi; ++it) put((uint32_t)(it->key >> 32) & 127u, (uint32_t)it->key, it->n);
     // both tiers may hold the same (score, value) when the dense bound was switched between adds; rows are unique after this
     std::sort(out.begin(), out.end(), [](const Row &a, const Row &b) { return a.key < b.key; });
     size_t w = 0;

@@ -16,7 +16,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <thread>
 #include <vector>
@@ -259,37 +258,6 @@ extern "C" int mgc_dev_rle_emit(const void *d_sorted, uint64_t n, uint32_t key_w
   if (!d_ws || ws_bytes < mgc::rle_workspace_bytes(n) || (n && (!d_sorted || !d_unique || !d_counts)) ||
       (key_words != 1 && key_words != 2)) return MGC_EINVAL;
   return hip_rc(mgc::launch_rle_emit(d_sorted, n, key_words, d_ws, d_unique, d_counts, (hipStream_t)stream), "rle_emit");
-}
-
-// ---- for measurements (scripts/setops_bench.py --legs h): the histogram pass of the database writer on its own -- what
-// mgc_db_stream::process (mgc_stream.cpp, "value histogram (A9)") does per range with launch_value_hist (mgc_encode.hip): dense bins
-// below value_hist_small_bins(), one list entry per larger value, the list copied to the host and inserted into a std::map one
-// element at a time.  It MUST MIRROR that block of mgc_db_stream::process: whoever changes the writer's pass changes this with it.
-// The caller brings the device scratch: d_hist[bins + 1] uint64 and a list of big_cap uint32 (big_cap >= n: the writer's state once
-// its list has grown, so the writer's retry never happens here).
-extern "C" uint32_t mgc_dev_value_hist_listed_bins(void) { return mgc::value_hist_small_bins(); }
-
-extern "C" int mgc_dev_value_hist_listed(const uint32_t *d_values, uint64_t n, uint64_t *d_hist, uint32_t *d_big, uint64_t big_cap, void *stream,
-                                         uint64_t *n_pairs, uint64_t *n_listed) {
-  if ((n && !d_values) || !d_hist || !d_big || big_cap < n || !n_pairs || !n_listed) { set_err(nullptr, "mgc_dev_value_hist_listed: bad arguments"); return MGC_EINVAL; }
-  hipStream_t st = (hipStream_t)stream;
-  const uint32_t nsmall = mgc::value_hist_small_bins();
-  std::vector<uint64_t> h_hist(nsmall + 1);
-  std::map<uint64_t, uint64_t> acc;
-#define VL_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) {                                         \
-    set_err(nullptr, "mgc_dev_value_hist_listed: %s -> %s", #expr, hipGetErrorString(e__)); return MGC_EHIP; } } while (0)
-  VL_TRY(hipMemsetAsync(d_hist, 0, 8 * (nsmall + 1), st));
-  VL_TRY(mgc::launch_value_hist(d_values, n, d_hist, d_big, big_cap, d_hist + nsmall, st));
-  VL_TRY(hipMemcpyAsync(h_hist.data(), d_hist, 8 * (nsmall + 1), hipMemcpyDeviceToHost, st));
-  VL_TRY(hipStreamSynchronize(st));
-  std::vector<uint32_t> big(h_hist[nsmall]);
-  if (!big.empty()) VL_TRY(hipMemcpy(big.data(), d_big, 4 * big.size(), hipMemcpyDeviceToHost));
-#undef VL_TRY
-  for (uint32_t v = 0; v < nsmall; v++) if (h_hist[v]) acc[v] += h_hist[v];
-  for (uint32_t v : big) acc[v]++;
-  *n_pairs = acc.size();
-  *n_listed = big.size();
-  return MGC_OK;
 }
 
 extern "C" int mgc_dev_block_offsets(const void *d_unique, uint64_t n_distinct, uint32_t key_words, uint32_t w_data,
@@ -777,7 +745,7 @@ extern "C" int mgc_prepare(mgc_session *s, uint64_t expected_bases) {
     if (s->ensure(mgc_session::B_X, bytes) != hipSuccess) (void)hipGetLastError();           // the count will say so itself
     // ... and the code objects of the count and of the database encoder: loaded lazily at the first launch, i.e. inside a fresh
     // process's first count otherwise (0.36 s of count for a 0.12 s step, profiles/r04o)
-    (void)mgc::warm_kmer(); (void)mgc::warm_scan(); (void)mgc::warm_sort(); (void)mgc::warm_finish(); (void)mgc::warm_encode();
+    (void)mgc::warm_kmer(); (void)mgc::warm_scan(); (void)mgc::warm_sort(); (void)mgc::warm_finish(); (void)mgc::warm_encode(); (void)mgc::warm_value_hist();
     (void)hipGetLastError();
   });
   return MGC_OK;

@@ -293,9 +293,6 @@ hipError_t launch_encode_chunk(const void *d_keys, const uint32_t *d_counts, uin
                                uint64_t b0, uint64_t b1, uint64_t n_kmers_chunk, uint64_t prefix_of_block0,
                                uint32_t suffix_size, uint32_t label_size, uint64_t label, void *d_img, hipStream_t st,
                                const uint64_t *d_labels = nullptr /*per k-mer, beside d_counts; null: the constant `label`*/);
-uint32_t   value_hist_small_bins();
-hipError_t launch_value_hist(const uint32_t *d_counts, uint64_t n, uint64_t *d_hist, uint32_t *d_big_list, uint64_t big_cap,
-                             uint64_t *d_big_n, hipStream_t st);
 
 // ---- database blocks decoded on the device (mgc_decode.hip): d_file = the data file's bytes (+ 16 bytes of slack),
 // d_blocks = mdb_raw_block[n_blocks] (include/meryl_db.h, mdb_reader_raw_file); one thread per block; *d_err != 0: a corrupt block
@@ -370,5 +367,5 @@ hipError_t launch_synth_reads(uint64_t seed, uint64_t genome_len, uint64_t first
                               uint8_t *d_out, hipStream_t st);
 
 // code objects load lazily at the first launch of a kernel of their translation unit: these touch one kernel each
-hipError_t warm_kmer(); hipError_t warm_sort(); hipError_t warm_finish(); hipError_t warm_encode(); hipError_t warm_scan();
+hipError_t warm_kmer(); hipError_t warm_sort(); hipError_t warm_finish(); hipError_t warm_encode(); hipError_t warm_scan(); hipError_t warm_value_hist();
 }  // namespace mgc

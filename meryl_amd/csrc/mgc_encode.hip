@@ -230,28 +230,6 @@ void encode_kmers_kernel(const K *__restrict__ keys, const u32 *__restrict__ cou
   }
 }
 
-// ---- value histogram (the master index's, A9) ------------------------------------------------------
-constexpr u32 HIST_SMALL = 1024;
-__global__ __launch_bounds__(256)
-void value_hist_kernel(const u32 *__restrict__ counts, u64 n, u64 *__restrict__ hist /*[HIST_SMALL]*/,
-                       u32 *__restrict__ big_list, u64 big_cap, u64 *__restrict__ big_n) {
-  __shared__ u32 s_h[HIST_SMALL];
-  for (u32 i = threadIdx.x; i < HIST_SMALL; i += blockDim.x) s_h[i] = 0;
-  __syncthreads();
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const u32 v = counts[i];
-    if (v < HIST_SMALL) atomicAdd(&s_h[v], 1u);
-    else {
-      const u64 at = atomicAdd(reinterpret_cast<unsigned long long *>(big_n), 1ull);
-      if (at < big_cap) big_list[at] = v;
-    }
-  }
-  __syncthreads();
-  for (u32 i = threadIdx.x; i < HIST_SMALL; i += blockDim.x)
-    if (s_h[i]) atomicAdd(reinterpret_cast<unsigned long long *>(hist + i), (unsigned long long)s_h[i]);
-}
-
 // ---- launchers -----------------------------------------------------------------------------------
 hipError_t launch_block_offsets_range(const void *d_keys, uint64_t n, uint32_t key_words, uint32_t w_data, uint64_t prefix_begin,
                                       uint64_t n_blocks, uint64_t n_prefix_total, uint64_t *d_rel_start, hipStream_t st) {
@@ -328,21 +306,6 @@ hipError_t launch_encode_chunk(const void *d_keys, const uint32_t *d_counts, uin
   return hipGetLastError();
 }
 
-uint32_t value_hist_small_bins() { return HIST_SMALL; }
-
-// d_hist[HIST_SMALL] and *d_big_n are accumulated into (zero them first); values >= HIST_SMALL are appended to d_big_list
-// (entries beyond big_cap are counted but dropped: the caller re-runs with a larger list)
-hipError_t launch_value_hist(const uint32_t *d_counts, uint64_t n, uint64_t *d_hist, uint32_t *d_big_list, uint64_t big_cap,
-                             uint64_t *d_big_n, hipStream_t st) {
-  if (n == 0) return hipSuccess;
-  uint64_t wgs = (n + 256 * 16 - 1) / (256 * 16);
-  if (wgs > 2048) wgs = 2048;
-  hipLaunchKernelGGL(value_hist_kernel, dim3((uint32_t)wgs), dim3(256), 0, st, d_counts, (u64)n, reinterpret_cast<u64 *>(d_hist),
-                     d_big_list, (u64)big_cap, reinterpret_cast<u64 *>(d_big_n));
-  return hipGetLastError();
-}
-
-
-hipError_t warm_encode() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&value_hist_kernel)); }
+hipError_t warm_encode() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&encode_headers_kernel)); }
 
 }  // namespace mgc

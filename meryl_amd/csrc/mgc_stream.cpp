@@ -16,7 +16,6 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
-#include <map>
 #include <mutex>
 #include <thread>
 
@@ -51,7 +50,7 @@ struct mgc_db_stream {
 
   hipStream_t st_enc = nullptr, st_copy = nullptr;
   hipEvent_t  ev_enc[2] = {nullptr, nullptr}, ev_a = nullptr, ev_b = nullptr;
-  DBuf d_bs, d_bytes, d_vbase, d_bb, d_pos, d_hist, d_big, d_img[2];
+  DBuf d_bs, d_bytes, d_vbase, d_bb, d_pos, d_img[2];
   char *pinned[NSLOT_MAX] = {nullptr};
 
   struct Range { const void *keys; const uint32_t *counts; uint64_t n, pb, pe; const uint64_t *labels = nullptr; /*per k-mer; null: `label`*/ };
@@ -72,7 +71,10 @@ struct mgc_db_stream {
   std::string err;
   uint64_t next_prefix = 0;                               // ranges must ascend
 
-  std::map<uint64_t, uint64_t> hist_acc;
+  // the values of every range written (A9).  Not thread-safe: process(), on the copy thread, is the only one that adds, and close
+  // reads it after that thread has ended.  Its device memory comes with the first non-empty range.
+  mgc_value_hist *hist = nullptr;
+  ~mgc_db_stream() { mgc_value_hist_close(hist); }        // (an open that failed; close has closed it already)
   mgc_db_write_profile prof;
   double t_open = 0, t_first_copy = 0;
 
@@ -162,33 +164,16 @@ int mgc_db_stream::process(const Range &r) {
   DS_TRY(d_vbase.ensure(8 * nblk));
   DS_TRY(d_bb.ensure(4 * nblk));
   DS_TRY(d_pos.ensure(8 * nblk));
-  const uint32_t nsmall = mgc::value_hist_small_bins();
-  DS_TRY(d_hist.ensure(8 * (nsmall + 1)));
-  if (d_big.cap == 0) DS_TRY(d_big.ensure(4u << 20));
   DS_TRY(mgc::launch_block_offsets_range(r.keys, r.n, kw, w_data, r.pb, nblk, 1ull << w_prefix, d_bs.as<uint64_t>(), st_enc));
   DS_TRY(mgc::launch_encode_sizes(r.keys, kw, d_bs.as<uint64_t>(), nblk, ss, label_size, d_bytes.as<uint64_t>(),
                                   d_vbase.as<uint64_t>(), d_bb.as<uint32_t>(), st_enc));
-  std::vector<uint64_t> h_bs(nblk + 1), h_bytes(nblk), h_pos(nblk), h_hist(nsmall + 1);
+  std::vector<uint64_t> h_bs(nblk + 1), h_bytes(nblk), h_pos(nblk);
   DS_TRY(hipMemcpyAsync(h_bs.data(), d_bs.p, 8 * (nblk + 1), hipMemcpyDeviceToHost, st_enc));
   if (nblk) DS_TRY(hipMemcpyAsync(h_bytes.data(), d_bytes.p, 8 * nblk, hipMemcpyDeviceToHost, st_enc));
-  // value histogram (A9): small values in LDS bins, the rare large ones as a list
-  for (int attempt = 0; attempt < 2; attempt++) {
-    DS_TRY(hipMemsetAsync(d_hist.p, 0, 8 * (nsmall + 1), st_enc));
-    DS_TRY(mgc::launch_value_hist(r.counts, r.n, d_hist.as<uint64_t>(), d_big.as<uint32_t>(), d_big.cap / 4,
-                                  d_hist.as<uint64_t>() + nsmall, st_enc));
-    DS_TRY(hipMemcpyAsync(h_hist.data(), d_hist.p, 8 * (nsmall + 1), hipMemcpyDeviceToHost, st_enc));
-    DS_TRY(hipStreamSynchronize(st_enc));
-    if (h_hist[nsmall] <= d_big.cap / 4) break;
-    DS_TRY(d_big.ensure(4 * h_hist[nsmall]));            // the list overflowed: once more with room for all of it
-  }
+  // value histogram (A9): the accumulator's pass.  It leaves st_enc idle, which the copies above rely on (an empty range adds nothing)
+  if (const int rc = mgc_value_hist_add(hist, r.counts, r.n, st_enc)) { fail(rc, mgc::thread_last_error()); return status; }
+  if (r.n == 0) DS_TRY(hipStreamSynchronize(st_enc));
   if (h_bs[nblk] != r.n || h_bs[0] != 0) { fail(MGC_EINVAL, "mgc_db_stream_write: keys outside the prefix range (or not ascending)"); return status; }
-  {
-    std::vector<uint32_t> big(h_hist[nsmall]);
-    if (!big.empty()) DS_TRY(hipMemcpy(big.data(), d_big.p, 4 * big.size(), hipMemcpyDeviceToHost));
-    std::lock_guard<std::mutex> g(mu);
-    for (uint32_t v = 0; v < nsmall; v++) if (h_hist[v]) hist_acc[v] += h_hist[v];
-    for (uint32_t v : big) hist_acc[v]++;
-  }
 
   // chunks: runs of blocks whose dumped bytes fit one device image (a larger single block gets an image of its own)
   struct Chunk { uint64_t b0, b1, bytes; };
@@ -339,6 +324,7 @@ extern "C" mgc_db_stream *mgc_db_stream_open(const char *path, uint32_t k, uint3
   d->t_open = now_s();
   if (device < 0) (void)hipGetDevice(&device);
   d->device = device;
+  d->hist = mgc_value_hist_open(device);
   if (host_threads <= 0) host_threads = (int)std::thread::hardware_concurrency();
   d->n_threads = std::max(1, std::min(host_threads, MGC_NUM_FILES));
   d->w = mdb_writer_open_ex(path, k, w_prefix, label_size, part, n_parts);
@@ -421,10 +407,15 @@ extern "C" int mgc_db_stream_close(mgc_db_stream *d, mgc_db_write_profile *prof)
   for (auto &t : d->pool) t.join();
   int rc = d->status;
   if (rc == MGC_OK) {
-    std::vector<uint64_t> hv, ho;
-    for (auto &kv : d->hist_acc) { hv.push_back(kv.first); ho.push_back(kv.second); }
-    rc = mdb_writer_add_histogram(d->w, hv.data(), ho.data(), hv.size());
+    uint64_t n_pairs = 0;
+    rc = mgc_value_hist_len(d->hist, &n_pairs);
+    std::vector<uint64_t> hv(n_pairs), ho(n_pairs);
+    if (rc == MGC_OK) rc = mgc_value_hist_get(d->hist, hv.data(), ho.data());
+    if (rc != MGC_OK) d->err = mgc::thread_last_error();
+    else rc = mdb_writer_add_histogram(d->w, hv.data(), ho.data(), hv.size());
   }
+  mgc_value_hist_close(d->hist);                            // (on its device, before the stream it counted on goes)
+  d->hist = nullptr;
   const int rc2 = mdb_writer_close(d->w);
   if (rc == MGC_OK && rc2 != MGC_OK) { rc = rc2; d->err = std::string("closing the database: ") + mdb_last_error(); }
   if (rc != MGC_OK) set_err(nullptr, "%s", d->err.c_str());

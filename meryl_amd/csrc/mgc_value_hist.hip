@@ -14,13 +14,14 @@
 //   list tier    values of VH_DENSE and above are appended to a device list as uint64 by a wave-aggregated append: one returning
 //                global atomic per wave and iteration (up to 256 values), every lane writes at the leader's base plus its rank in
 //                the ballots.  The list has room for every value of the pass, so it cannot overflow and nothing is retried.
-// A non-empty list is sorted (launch_radix_sort over 32 bits) and run-length counted (launch_rle_count / launch_rle_emit) on the
-// device; only the (value, occurrences) pairs cross to the host, where they are merged into a sorted vector.  A pass takes at
-// most VH_CHUNK = 2^26 values, so the 32-bit run lengths of the rle kernels and the uint32 LDS bins cannot wrap.
+// A non-empty list is sorted over 32 bits and run-length counted on the device, and its (value, occurrences) pairs are merged into a
+// sorted host vector: the one list tier of mgc_hist_list.hpp.  A pass takes at most VH_CHUNK = 2^26 values, so the 32-bit run lengths
+// of the rle kernels and the uint32 LDS bins cannot wrap.
 //
 // kernel-resource-usage (scripts/kres.py value_hist_tiers mgc_value_hist.hip): in DESIGN.md §9, "Value histograms of tree results".
 #include "../../include/meryl_db.h"
 #include "mgc_device.h"
+#include "mgc_hist_list.hpp"
 #include "mgc_session.hpp"
 
 #include <algorithm>
@@ -131,9 +132,9 @@ hipError_t launch_value_hist_tiers(const u32 *d_values, u64 n, u64 *d_dense, u64
                      reinterpret_cast<unsigned long long *>(d_list_n));
   return hipGetLastError();
 }
-
-struct Pair { u64 value, n; };
 }  // namespace
+
+hipError_t warm_value_hist() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&value_hist_tiers_kernel)); }
 }  // namespace mgc
 
 using mgc::set_err;
@@ -143,9 +144,9 @@ struct mgc_value_hist {
   int device = -1;
   uint32_t n_cus = 1;
   bool ready = false;
-  DBuf d_dense, d_ctr, d_list[2], d_sws, d_rws, d_uniq, d_ucnt;
-  std::vector<mgc::Pair> big;               // the list tier, ascending by value
-  std::vector<mgc::Pair> rows;              // both tiers, ascending by value (cache)
+  DBuf d_dense;
+  mgc::ListTier list{"mgc_value_hist"};     // values of VH_DENSE and above
+  std::vector<mgc::HistPair> rows;          // both tiers, ascending by value (cache)
   bool rows_ok = false;
   bool failed = false;                      // an add failed part of the way: the dense bins may hold values the list lost
 
@@ -165,60 +166,20 @@ struct mgc_value_hist {
     VH_TRY(hipGetDeviceProperties(&prop, device));
     n_cus = (uint32_t)std::max(prop.multiProcessorCount, 1);
     VH_TRY(d_dense.ensure(8 * mgc::VH_DENSE));
-    VH_TRY(d_ctr.ensure(256));
     VH_TRY(hipMemsetAsync(d_dense.p, 0, 8 * mgc::VH_DENSE, st));      // (ordered before the first kernel, whatever kind of stream st is)
     ready = true;
     return MGC_OK;
   }
 
-  // sorted distinct (value, occurrences) of one pass -> big
-  void merge_pairs(const std::vector<uint64_t> &keys, const std::vector<uint32_t> &cnt) {
-    std::vector<mgc::Pair> out;
-    out.reserve(big.size() + keys.size());
-    size_t i = 0, j = 0;
-    while (i < big.size() || j < keys.size()) {
-      if (j == keys.size() || (i < big.size() && big[i].value < keys[j])) out.push_back(big[i++]);
-      else if (i == big.size() || keys[j] < big[i].value) { out.push_back(mgc::Pair{keys[j], cnt[j]}); j++; }
-      else { out.push_back(mgc::Pair{keys[j], big[i].n + cnt[j]}); i++; j++; }
-    }
-    big.swap(out);
-  }
-
   int add_chunk(const uint32_t *d_values, uint64_t n, hipStream_t st) {
-    uint64_t *d_list_n = d_ctr.as<uint64_t>();
-    uint32_t *d_sort_err = reinterpret_cast<uint32_t *>(d_ctr.as<unsigned char>() + 64);
-    VH_TRY(d_list[0].ensure(8 * n));
-    VH_TRY(hipMemsetAsync(d_ctr.p, 0, 128, st));
-    VH_TRY(mgc::launch_value_hist_tiers(d_values, n, d_dense.as<uint64_t>(), d_list[0].as<uint64_t>(), d_list_n, n_cus, st));
+    VH_TRY(list.reserve(n));
+    VH_TRY(list.reset(st));
+    VH_TRY(mgc::launch_value_hist_tiers(d_values, n, d_dense.as<uint64_t>(), list.list(), list.list_n(), n_cus, st));
     uint64_t need = 0;
-    VH_TRY(hipMemcpyAsync(&need, d_list_n, 8, hipMemcpyDeviceToHost, st));
+    VH_TRY(hipMemcpyAsync(&need, list.list_n(), 8, hipMemcpyDeviceToHost, st));
     VH_TRY(hipStreamSynchronize(st));
     if (need > n) { set_err(nullptr, "mgc_value_hist: the list holds more entries than the pass has values"); return MGC_EHIP; }
-    if (need == 0) return MGC_OK;
-    VH_TRY(d_list[1].ensure(8 * need));
-    VH_TRY(d_sws.ensure(mgc::sort_workspace_bytes(need)));
-    VH_TRY(d_rws.ensure(mgc::rle_workspace_bytes(need)));
-    mgc::SortPlan plan;
-    mgc::make_sort_plan(0, 32, &plan);
-    int in_alt = 0;
-    VH_TRY(mgc::launch_radix_sort(d_list[0].p, d_list[1].p, need, 1, plan, d_sws.p, d_sws.cap, d_sort_err, &in_alt, st, nullptr));
-    const void *sorted = d_list[in_alt ? 1 : 0].p;
-    VH_TRY(mgc::launch_rle_count(sorted, need, 1, d_rws.p, st));
-    uint64_t nd = 0;
-    VH_TRY(mgc::rle_read_total(d_rws.p, &nd, st));            // (synchronises)
-    uint32_t h_err = 0;
-    VH_TRY(hipMemcpyAsync(&h_err, d_sort_err, 4, hipMemcpyDeviceToHost, st));
-    VH_TRY(d_uniq.ensure(8 * nd));
-    VH_TRY(d_ucnt.ensure(4 * nd));
-    VH_TRY(mgc::launch_rle_emit(sorted, need, 1, d_rws.p, d_uniq.p, d_ucnt.as<uint32_t>(), st));
-    std::vector<uint64_t> hk(nd);
-    std::vector<uint32_t> hc(nd);
-    VH_TRY(hipMemcpyAsync(hk.data(), d_uniq.p, 8 * nd, hipMemcpyDeviceToHost, st));
-    VH_TRY(hipMemcpyAsync(hc.data(), d_ucnt.p, 4 * nd, hipMemcpyDeviceToHost, st));
-    VH_TRY(hipStreamSynchronize(st));
-    if (h_err) { set_err(nullptr, "mgc_value_hist: radix sort look-back timed out"); return MGC_ETIMEOUT; }
-    merge_pairs(hk, hc);
-    return MGC_OK;
+    return list.drain(need, 32, st);
   }
 
   int add(const uint32_t *d_values, uint64_t n, hipStream_t st) {
@@ -238,9 +199,9 @@ struct mgc_value_hist {
       VH_TRY(hipSetDevice(device));
       std::vector<uint64_t> hd(mgc::VH_DENSE);
       VH_TRY(hipMemcpy(hd.data(), d_dense.p, 8 * mgc::VH_DENSE, hipMemcpyDeviceToHost));
-      for (uint32_t v = 0; v < mgc::VH_DENSE; v++) if (hd[v]) rows.push_back(mgc::Pair{v, hd[v]});
+      for (uint32_t v = 0; v < mgc::VH_DENSE; v++) if (hd[v]) rows.push_back(mgc::HistPair{v, hd[v]});
     }
-    rows.insert(rows.end(), big.begin(), big.end());         // every list value is >= VH_DENSE: already ascending
+    rows.insert(rows.end(), list.acc.begin(), list.acc.end());         // every list value is >= VH_DENSE: already ascending
     rows_ok = true;
     return MGC_OK;
   }
@@ -284,7 +245,7 @@ extern "C" int mgc_value_hist_get(mgc_value_hist *h, uint64_t *values, uint64_t 
   const int rc = h->build();
   if (rc != MGC_OK) return rc;
   if (!h->rows.empty() && (!values || !occurrences)) { set_err(nullptr, "mgc_value_hist_get: NULL array"); return MGC_EINVAL; }
-  for (size_t i = 0; i < h->rows.size(); i++) { values[i] = h->rows[i].value; occurrences[i] = h->rows[i].n; }
+  for (size_t i = 0; i < h->rows.size(); i++) { values[i] = h->rows[i].key; occurrences[i] = h->rows[i].n; }
   return MGC_OK;
 }
 
@@ -293,7 +254,7 @@ extern "C" int mgc_value_hist_totals(mgc_value_hist *h, uint64_t *unique, uint64
   const int rc = h->build();
   if (rc != MGC_OK) return rc;
   uint64_t u = 0, d = 0, t = 0;
-  for (const mgc::Pair &p : h->rows) { if (p.value == 1) u = p.n; d += p.n; t += p.value * p.n; }
+  for (const mgc::HistPair &p : h->rows) { if (p.key == 1) u = p.n; d += p.n; t += p.key * p.n; }
   if (unique) *unique = u;
   if (distinct) *distinct = d;
   if (total) *total = t;

@@ -27,14 +27,11 @@
     run's `union-sum` (the count pass reads keys only) and `subtract` (the existing case whose count pass reads the values) through
     mgc_dev_merge_many_*, over the `shared50` mix, N = 3 and 32, 8-byte keys.  No threshold is fixed in advance.
   * histogram (leg h): the value histogram of HIST_M million uint32 values in one device buffer (--hist-m, default 64), four
-    distributions -- all ones; geometric (p = 0.4, typical of counts); uniform in [1, 1000]; uniform in [1, 2^31] -- three ways over
+    distributions -- all ones; geometric (p = 0.4, typical of counts); uniform in [1, 1000]; uniform in [1, 2^31] -- two ways over
     the same buffer: the accumulator's add (mgc_value_hist_add and mgc_value_hist_get on one accumulator, its buffers grown by the
-    warm-up as the evaluator's are after its first slice); the
-    database writer's pass (mgc_dev_value_hist_listed: its kernel, the list of values above its dense bins copied to the host and
-    inserted into a std::map one by one; the list sized for all values, as the writer's is once it has grown); a device copy of
-    the buffer, the floor.  The median of 5 after a warm-up; where one call takes seconds (the writer's pass over the fourth
-    distribution) the warm-up runs on the first million values and ONE call is timed -- `samples_ms` shows how many were.
-    `equal`: both ways give the same number of pairs and the accumulator's pairs equal torch.unique's.
+    warm-up as the evaluator's are after its first slice), which is also the database writer's pass; a device copy of the buffer, the
+    floor.  The median of 5 after a warm-up.  `equal`: the accumulator's pairs equal torch.unique's.  (Lines recorded with a `writer`
+    leg timed the pass the database writer had before it took the accumulator; that code is gone.)
 
 usage: python scripts/setops_bench.py [KEYS_M] [READS_M] [--dir DIR] [--legs a,b,c,s,v,h] [--hist-m HIST_M] [--staged-meryl PATH] >> profiles/setops_bench.jsonl"""
 import json
@@ -263,15 +260,10 @@ def values_leg():
 
 
 def histogram_leg():
-    import ctypes
     import numpy as np
-    L = capi.lib()
     n = int(hist_m * 1_000_000)
     g = torch.Generator(device=dev)
     g.manual_seed(20261019)
-    bins = int(L.mgc_dev_value_hist_listed_bins())
-    d_hist = torch.zeros(bins + 1, dtype=torch.int64, device=dev)
-    d_big = torch.empty(n, dtype=torch.int32, device=dev)
     copy_to = torch.empty(n, dtype=torch.int32, device=dev)
     dense, _ = db.ValueHistogram.geometry()
 
@@ -283,7 +275,6 @@ def histogram_leg():
              ("uniform-1-2^31", lambda: torch.randint(1, (1 << 31) + 1, (n,), generator=g, device=dev, dtype=torch.int64).to(torch.int32)))
     for name, make in dists:
         v = make().contiguous()
-        stream = torch.cuda.current_stream().cuda_stream
         got = {}
 
         fresh = db.ValueHistogram()                              # what is compared: one add into an empty accumulator
@@ -296,36 +287,17 @@ def histogram_leg():
             acc.add(t)
             got["pairs"] = acc.get()[0].size
 
-        def parent(t=v):
-            n_pairs, n_listed = ctypes.c_uint64(0), ctypes.c_uint64(0)
-            rc = L.mgc_dev_value_hist_listed(t.data_ptr(), t.numel(), d_hist.data_ptr(), d_big.data_ptr(), n, stream, ctypes.byref(n_pairs),
-                                             ctypes.byref(n_listed))
-            assert rc == 0, capi.lib().mgc_db_stream_error(None)
-            got["parent"] = (n_pairs.value, n_listed.value)
         line = {}
         ms, samples = timed(lambda: copy_to.copy_(v))
         line["copy"] = dict(ms=round(ms, 3), samples_ms=samples)
         ms, samples = timed(new_add)
         line["add"] = dict(ms=round(ms, 3), samples_ms=samples, pairs=int(got["pairs"]))
         acc.close()
-        listed = int((v.view(torch.int32).to(torch.int64) & 0xFFFFFFFF).ge(bins).sum())
-        if listed > (8 << 20):                                   # seconds per call on the host: warm up small, time once
-            parent(v[:1_000_000])
-            torch.cuda.synchronize()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            parent()
-            b.record()
-            b.synchronize()
-            ms, samples = a.elapsed_time(b), [round(a.elapsed_time(b), 3)]
-        else:
-            ms, samples = timed(parent)
-        line["writer"] = dict(ms=round(ms, 3), samples_ms=samples, pairs=got["parent"][0], listed=got["parent"][1])
         uv, uc = torch.unique(v.to(torch.int64) & 0xFFFFFFFF, return_counts=True)
-        same = got["parent"][0] == got["new"][0].size == int(uv.numel()) and np.array_equal(got["new"][0].astype(np.int64), uv.cpu().numpy()) \
+        same = got["new"][0].size == int(uv.numel()) and np.array_equal(got["new"][0].astype(np.int64), uv.cpu().numpy()) \
             and np.array_equal(got["new"][1].astype(np.int64), uc.cpu().numpy())
-        emit(what="histogram", distribution=name, values=n, dense_limit=dense, writer_bins=bins, above_dense_limit=int((uv >= dense).sum()),
-             equal=bool(same), legs=line, add_over_writer=round(line["add"]["ms"] / line["writer"]["ms"], 4),
+        emit(what="histogram", distribution=name, values=n, dense_limit=dense, above_dense_limit=int((uv >= dense).sum()),
+             equal=bool(same), legs=line,
              add_over_copy=round(line["add"]["ms"] / line["copy"]["ms"], 2), gbytes_per_s_add=round(4e-6 * n / line["add"]["ms"], 1))
         del v, uv, uc
         torch.cuda.empty_cache()

@@ -3,6 +3,7 @@ it produces must equal, file by file, what the host encoder (mdb_writer_add_bloc
 merylBlockWriter::addBlock, src/meryl/merylCountArray.C:472-475) writes from the same (k-mer, count) stream.  The
 host encoder itself is checked against an independent Python parser and the reference's documented block shape in
 tests/test_db.py; byte parity with a genuine meryl database stays unpinned."""
+import ctypes
 import os
 import subprocess
 
@@ -84,7 +85,7 @@ def _to_device(lo, hi, cn, k):
 def _counts(rng, n):
     cn = rng.integers(1, 60, n).astype(np.uint32)
     big = rng.random(n) < 0.01
-    cn[big] = rng.integers(1000, 5000, int(big.sum())).astype(np.uint32)          # around the histogram's 1024-bin split
+    cn[big] = rng.integers(1000, 5000, int(big.sum())).astype(np.uint32)          # on both sides of the histogram's 4096 LDS bins
     huge = rng.random(n) < 0.001
     cn[huge] = rng.integers(1 << 20, 0xFFFFFFFF, int(huge.sum()), dtype=np.uint64).astype(np.uint32)
     return cn
@@ -339,3 +340,105 @@ def test_count_node_batches_park_waves_and_merge_once(tmp_path, native_lib, orac
         assert (prof["n_host_runs"] > 0 and prof["host_run_bytes"] > 0) if budget == 1 else prof["n_host_runs"] == 0
     else:
         assert prof["n_batches"] == 1 and prof["n_host_runs"] == 0
+
+
+# ---- the value histogram the stream stores: the accumulator of mgc_value_hist.hip, one add per range ----------------------------------
+HIST_POOL = np.array([1, 2, 4095, 4096, 4097, 1 << 20, (1 << 20) + 7, 3_000_000_000, 0xFFFFFFFF], np.uint32)
+
+
+def _stored_histogram(path):
+    from meryl_amd import db
+    r = db.Reader(path)
+    v, o = r.histogram()
+    r.close()
+    return v, o
+
+
+def _assert_histogram_of(path, values):
+    want_v, want_o = np.unique(values, return_counts=True)
+    v, o = _stored_histogram(path)
+    assert np.array_equal(v, want_v.astype(np.uint64)) and np.array_equal(o, want_o.astype(np.uint64))
+
+
+def _live():
+    from meryl_amd import capi
+    b, n = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    assert capi.lib().mgc_dev_buffers_live(ctypes.byref(b), ctypes.byref(n)) == 0
+    return b.value, n.value
+
+
+@pytest.mark.parametrize("k", [16, 40])
+def test_stream_histogram_over_ranges(tmp_path, native_lib, k):
+    """Three ranges of about 5000 k-mers and one without any between two of them: the stored histogram is numpy's over all values --
+    values on both sides of the LDS bins, listed values that recur in several ranges, 2^32 - 1, and 300 distinct listed values in one
+    range.  k = 40: two key words."""
+    from meryl_amd import count
+    wp, cuts = 12, [0, 1300, 1500, 2800, 4096]
+    rng = np.random.default_rng(k)
+    lo, hi = _random_keys(rng, k, 16_000)
+    pref = _prefixes(lo, hi, k, wp)
+    keep = (pref < np.uint64(cuts[1])) | (pref >= np.uint64(cuts[2]))
+    lo, hi, pref = lo[keep], hi[keep], pref[keep]
+    cn = HIST_POOL[rng.integers(0, HIST_POOL.size, lo.size)]
+    edges = [int(np.searchsorted(pref, np.uint64(c))) for c in cuts[:-1]] + [lo.size]
+    assert edges[1] == edges[2] and min(edges[1] - edges[0], edges[3] - edges[2], edges[4] - edges[3]) > 4000
+    cn[edges[2]:edges[2] + 300] = 5000 + 3 * np.arange(300, dtype=np.uint32)
+    keys, cnts = _to_device(lo, hi, cn, k)
+    s = count.DbStream(str(tmp_path / "dev"), k, wp, host_threads=4)
+    for i in range(4):
+        s.write(keys[edges[i]:edges[i + 1]], cnts[edges[i]:edges[i + 1]], cuts[i], cuts[i + 1])
+    prof = s.close()
+    assert prof["n_kmers"] == lo.size
+    _assert_histogram_of(str(tmp_path / "dev"), cn)
+    _host_write(str(tmp_path / "host"), lo, hi, cn, k, wp)
+    _assert_same_dirs(str(tmp_path / "host"), str(tmp_path / "dev"))
+
+
+def test_stream_histogram_of_misaligned_values(tmp_path, native_lib):
+    """The value array of a range starts 4, 8 and 12 bytes past a 16-byte boundary: the accumulator's scalar head inside the writer."""
+    import torch
+    from meryl_amd import count
+    k, wp = 16, 12
+    rng = np.random.default_rng(7)
+    lo, hi = _random_keys(rng, k, 5000)
+    cn = HIST_POOL[rng.integers(0, HIST_POOL.size, lo.size)]
+    keys, cnts = _to_device(lo, hi, cn, k)
+    for off in (1, 2, 3):
+        room = torch.zeros(lo.size + 4, dtype=torch.int32, device="cuda")
+        shifted = room[off:off + lo.size]
+        shifted.copy_(cnts)
+        assert shifted.data_ptr() % 16 == 4 * off
+        out = str(tmp_path / ("dev%d" % off))
+        s = count.DbStream(out, k, wp, host_threads=2)
+        s.write(keys, shifted, 0, 1 << wp)
+        s.close()
+        _assert_histogram_of(out, cn)
+
+
+def test_stream_close_gives_the_device_memory_back(tmp_path, native_lib):
+    """mgc_dev_buffers_live after mgc_db_stream_close is what it was before the open -- after a good stream, and after one whose
+    second range came out of order (MGC_EINVAL) once the first had been counted."""
+    import torch
+    from meryl_amd import capi, count
+    k, wp = 16, 12
+    rng = np.random.default_rng(11)
+    lo, hi = _random_keys(rng, k, 5000)
+    cn = HIST_POOL[rng.integers(0, HIST_POOL.size, lo.size)]
+    keys, cnts = _to_device(lo, hi, cn, k)
+    half = int(np.searchsorted(_prefixes(lo, hi, k, wp), np.uint64(2048)))
+    torch.cuda.synchronize()
+    before = _live()
+    s = count.DbStream(str(tmp_path / "good"), k, wp, host_threads=2)
+    s.write(keys, cnts, 0, 1 << wp)
+    s.close()
+    assert _live() == before
+    s = count.DbStream(str(tmp_path / "bad"), k, wp, host_threads=2)
+    s.write(keys[half:], cnts[half:], 2048, 4096)
+    s.sync()
+    assert _live()[0] > before[0]
+    with pytest.raises(capi.MgcError) as e:
+        s.write(keys[:half], cnts[:half], 0, 2048)
+    assert e.value.rc == capi.MGC_EINVAL
+    with pytest.raises(capi.MgcError):
+        s.close()
+    assert _live() == before
