@@ -20,6 +20,7 @@
 // {flag,epoch,value} granules with agent-scope relaxed atomics (no fences needed:
 // the datum is the flag).  Wave = 64 everywhere.
 #include "mgc_common.hpp"
+#include "mgc_stream_geom.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -930,7 +931,12 @@ void hash_count_multi_kernel(u32 *__restrict__ keys, const u64 *__restrict__ sta
 //     consume-before-issue order as hash_count_multi_kernel -- and all chunks claim / add into ONE table, no barrier between them;
 //   * a table entry is suffix << 12 | count (suffix <= 20 bits, a count <= 4094 so that EMPTY = all ones is no entry): the claiming
 //     CAS deposits count 1, a duplicate adds 1, entry order == suffix order;
-//   * the table holds SLOTS entries and the claim list DCAP of them -- capacity in DISTINCT suffixes.  A sub-bucket that claims more
+//   * a row of BLOCK keys makes its first probes together; a key that meets another suffix there goes to its wave's LDS queue
+//     (STREAM_QCAP keys, drained when a row would not fit and at the sub-bucket's end) and is probed on from there, one key per
+//     lane of consecutive lanes -- the table is ~7 % full while it is filled, rounds of the whole wave for those keys cost as
+//     much as all first probes.  Full rows carry no lane predicate, and the table's size, mask, shift and the chunk sizes are
+//     taken once per sub-bucket (mgc_stream_geom.hpp), not per chunk;
+//   * the table holds SLOTS entries and srt DCAP of them -- capacity in DISTINCT suffixes.  A sub-bucket that holds more
 //     (low coverage: D ~ N), or one of whose keys probes more than PROBE_MAX steps (the table fills, or many suffixes share a home
 //     slot: the multiplicative hash does that to structured suffixes, multiples of Fibonacci numbers for one), raises s_ovf: nothing
 //     of it is written, its number goes on the retry list, and the RETRY instantiation (SLOTS = 8192, DCAP >= max_size) counts it
@@ -938,8 +944,11 @@ void hash_count_multi_kernel(u32 *__restrict__ keys, const u64 *__restrict__ sta
 //     (slots_for(n) >= 2n up to max_size <= 4094), a probe ends within one turn of it whatever the suffixes are, and the turn is
 //     the bound -- reached only if the table were full, which raises the count's error word error[2] (the count then ends with an
 //     error code instead of a result that lacks the sub-bucket);
-//   * the per-distinct phases are hash_count_multi_kernel's (256 bins by the top eight suffix bits, one-wave scan with the table
-//     cleared in its shadow, rank inside the bin) with up to TWO entries per thread in registers (D <= 512), staged through LDS above.
+//   * a claim counts its suffix into one of 256 bins by the top eight suffix bits (the bin total is D); where the distinct entries
+//     are is read off the table: one wave scans the bins, then a sweep over the table's `slots` entries as 16-byte vectors takes
+//     every non-empty entry's place in srt from its bin's cursor and puts EMPTY back behind it, and the rank inside the bin is
+//     hash_count_multi_kernel's.  One path for every D; no claim list, three workgroup barriers per sub-bucket.  (Counting the
+//     bins by a first sweep instead cost a barrier and eight LDS atomics per thread: profiles/count_insert_ab.txt.)
 // LIST: visit the sub-buckets visit[0 .. *visit_count) (a sparse grid's non-empty list; the retry list); otherwise all ng.
 // RETRY: the retry launch itself (retry_list is not used).
 template <typename KT, int BLOCK, int KPC, int SLOTS, int DCAP, bool LIST, bool DBG, bool RETRY>
@@ -957,10 +966,11 @@ void hash_count_stream_kernel(KT *__restrict__ keys, const u64 *__restrict__ sta
   constexpr u32 PROBE_MAX = 64u;                                     // probe steps of one key beyond which the sub-bucket goes to the retry launch
   __shared__ __attribute__((aligned(16))) KT tk[SLOTS];             // suffix << 12 | count
   __shared__ __attribute__((aligned(16))) KT srt[DCAP];             // the distinct entries in bin order
-  __shared__ unsigned short lst[DCAP];                              // slots of the claimed entries, in claim order
-  __shared__ __attribute__((aligned(16))) u32 s_bin[2][BLOCK + 4];  // bin counts -> starts; [BLOCK] = D
-  __shared__ u32 s_nd, s_ovf;
+  __shared__ __attribute__((aligned(16))) u32 s_bin[2][BLOCK + 4];  // bin counts [0, BLOCK) -> bin bounds [0, BLOCK]; [BLOCK + 1] = D
+  __shared__ KT s_q[(BLOCK / 64) * (int)STREAM_QCAP];               // per wave: the keys whose first probe met another suffix
+  __shared__ u32 s_ovf;
   const u32 tid = threadIdx.x, lane = tid & 63u;
+  const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
   const u32 G = gridDim.x;
   const KT  low_mask = (KT)((1ull << low_bits) - 1ull);
   const u32 bshift = low_bits - 8u;                                 // the launcher guarantees 8 <= low_bits <= 20 (whole k-mers: <= 52)
@@ -980,14 +990,9 @@ void hash_count_stream_kernel(KT *__restrict__ keys, const u64 *__restrict__ sta
   // LIST: the number of the sub-bucket at position P (one load, the same address in every lane)
   auto load_gnum = [&](u32 P) -> u32 { return (LIST && P < np) ? visit[P] : 0u; };
   // chunks of an n-key sub-bucket: 1..3 of them, evenly cut, whole rows of BLOCK keys (n <= max_size <= 4094 < 3 * CH); 0: not
-  // counted here (empty, or above max_size: the streaming launch's)
-  auto chunk_size = [&](u32 n) -> u32 {
-    if (n == 0u || n > max_size) return 0u;
-    u32 per = n;
-    if (n > 2u * CH) per = ((n + 2u) * 43691u) >> 17;              // ceil(n / 3)
-    else if (n > CH) per = (n + 1u) >> 1;
-    return (per + (u32)BLOCK - 1u) & ~((u32)BLOCK - 1u);
-  };
+  // counted here (empty, or above max_size: the streaming launch's).  This and the table size are taken ONCE per sub-bucket, when
+  // it becomes the next one (mgc_stream_geom.hpp: tests/host/stream_geom_host.cpp walks every n)
+  auto chunk_size = [&](u32 n) -> u32 { return stream_chunk_size(n, max_size, CH, (u32)BLOCK); };
   // (uniform guards, lanes past the end re-read the last key: no per-lane predicate, no 64-bit address per slot)
   auto load_chunk = [&](u32 a, u32 cnt, KT (&kr)[KPC]) {
     const KT *src = keys + a;
@@ -1001,12 +1006,6 @@ void hash_count_stream_kernel(KT *__restrict__ keys, const u64 *__restrict__ sta
       }
     }
   };
-  auto slots_for = [&](u32 n) -> u32 {                              // (2n: D is not known, the keys bound it)
-    if (2u * n <= 256u) return 256u;
-    const u32 s = 1u << (32 - __builtin_clz(2u * n - 1u));
-    return s < (u32)SLOTS ? s : (u32)SLOTS;
-  };
-
   u32 P = blockIdx.x;
   u32 a0, a1, g0, g1, n0, n1;                                       // the current sub-bucket, the next one
   KT  kcur[KPC], comp[KPC];
@@ -1020,23 +1019,64 @@ void hash_count_stream_kernel(KT *__restrict__ keys, const u64 *__restrict__ sta
   unpack_bounds(load_starts(P, g0), a0, n0);
   unpack_bounds(load_starts(P + G, g1), a1, n1);
   u32 csz = chunk_size(n0), off = 0;                                // the current chunk: keys [off, off + csz) of the current sub-bucket
+  u32 ncs = chunk_size(n1);                                         // ... and the chunk size of the next sub-bucket
+  // the current sub-bucket's table: slots (a power of two), its mask, the hash's shift, the probe bound (RETRY: one full turn of
+  // the table -- every slot has been looked at)
+  u32 slots = csz ? stream_slots_for(n0, (u32)SLOTS) : 256u, smask = slots - 1u, sshift = 32u - (u32)__builtin_ctz(slots), probe_max = RETRY ? slots : PROBE_MAX;
   load_chunk(a0, csz < n0 ? csz : n0, kcur);                        // (csz == 0: nothing)
   u32 bvec = load_starts(P + 2 * G, gb);
   u32 gv = load_gnum(P + 3 * G);
   u32 par = 0;
-  u32 cleared = (u32)SLOTS;                                         // tk[0, cleared) is EMPTY whenever an insert phase begins
+  // The WHOLE table is EMPTY whenever an insert phase begins: a sub-bucket dirties tk[0, slots) only, and the sweep that collects
+  // its entries puts EMPTY back behind every vector it reads (an overflowing sub-bucket clears all of it).
   // (EMPTY is all ones in either width: the table is cleared as 16-byte vectors of ones, `slots` counted in entries)
   constexpr u32 E16 = 16u / (u32)sizeof(KT);                        // entries per 16-byte vector
   constexpr u32 ONES = 0xFFFFFFFFu;
+  auto vec_entry = [](const uint4 &q, int i) -> KT {                // entry i of a 16-byte vector of the table
+    if constexpr (W64) return i == 0 ? (((KT)q.y << 32) | (KT)q.x) : (((KT)q.w << 32) | (KT)q.z);
+    else               return i == 0 ? q.x : (i == 1 ? q.y : (i == 2 ? q.z : q.w));
+  };
+  auto home_of = [](KT c, u32 sshift) -> u32 {                      // home slot of a suffix in a table of 2^(32 - sshift) entries
+    if constexpr (W64) return ((((u32)c) ^ ((u32)(c >> 32) * 0x85EBCA6Bu)) * 0x9E3779B1u) >> sshift;   // (suffixes of <= 52 bits: the high word holds <= 20)
+    else               return (c * 0x9E3779B1u) >> sshift;
+  };
+  // The wave's queued keys, one per lane of consecutive lanes, 64 at a time: each is probed on from the slot behind its home
+  // (recomputed: a multiply and a shift) until it claims an empty slot or meets its own suffix -- linear probing, bounded by
+  // probe_max steps as the first launch's chains always were (a long chain: the table fills, or the suffixes crowd a few home
+  // slots).  Wave-private: LDS operations of one wave execute in order, the fences keep the compiler to that order.
+  auto drain_queue = [&](u32 &qn, u32 smask, u32 sshift, u32 probe_max) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (u32 b = 0; b < qn; b += 64u) {
+      if (b + lane < qn) {
+        const KT c = s_q[stream_queue_index(wave, b, lane)];
+        u32 h = home_of(c, sshift), steps = 0;
+        bool pend = true;
+        do {
+          h = (h + 1) & smask;
+          const KT old = atomicCAS(&tk[h], EMPTY, (KT)((c << CNTB) | (KT)1));
+          const bool w = old == EMPTY, dup = !w && (old >> CNTB) == c;
+          if (dup) atomicAdd(reinterpret_cast<u32 *>(&tk[h]), 1u);
+          if (w)   atomicAdd(&s_bin[par][(u32)(c >> bshift)], 1u);
+          if (w || dup) pend = false;
+          if (++steps > probe_max) { s_ovf = 1u; pend = false; }
+        } while (pend);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    qn = 0;
+  };
   {
     uint4 *tk4 = reinterpret_cast<uint4 *>(tk);
     for (u32 i = tid; i < (u32)SLOTS / E16; i += BLOCK) tk4[i] = make_uint4(ONES, ONES, ONES, ONES);
     s_bin[0][tid] = 0; s_bin[1][tid] = 0;
-    if (tid == 0) { s_nd = 0; s_ovf = 0; }
+    if (tid == 0) s_ovf = 0;
   }
   __syncthreads();
 
   u64 ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0;
+  u32 qn = 0;                                                        // keys in this wave's queue (uniform)
 #define HC_STAMP(i) do { if (DBG) { const u64 t = __builtin_readcyclecounter(); ph[i] += t - t0; t0 = t; } } while (0)
   // ONE loop over chunks (one load site: the loads of the next chunk land in the registers the consumed one has left, whichever
   // sub-bucket it belongs to -- two load sites merged by copies would wait for the loads they had just issued)
@@ -1046,9 +1086,6 @@ void hash_count_stream_kernel(KT *__restrict__ keys, const u64 *__restrict__ sta
     const u32 rest = n0 - off;
     const u32 cnt = active ? (rest < csz ? rest : csz) : 0u;
     const bool last = !active || rest <= csz;
-    const u32 slots = slots_for(n0);
-    const u32 smask = slots - 1, sshift = 32 - (u32)__builtin_ctz(slots);
-    const u32 probe_max = RETRY ? slots : PROBE_MAX;               // (RETRY: one full turn of the table -- every slot has been looked at)
     // the chunk that was loaded a whole chunk ago is consumed into comp[]; only then the next one is issued (a wait for old
     // registers behind new loads would wait for the new loads: hash_count_multi_kernel)
     if constexpr (W64) { if (off == 0u) pre = kcur[0] & ~low_mask; }   // (every lane holds a key of the sub-bucket: lanes past the end re-read the last one)
@@ -1057,7 +1094,6 @@ void hash_count_stream_kernel(KT *__restrict__ keys, const u64 *__restrict__ sta
       comp[j] = kcur[j] & low_mask;
       asm volatile("" : "+v"(comp[j]) :: "memory");
     }
-    const u32 ncs = chunk_size(n1);
     u32 a2 = 0, n2 = 0, g2 = 0, g3 = 0;
     if (last) {                                                     // (uniform) everything the last round loaded is consumed here ...
       unpack_bounds(bvec, a2, n2);
@@ -1076,126 +1112,125 @@ void hash_count_stream_kernel(KT *__restrict__ keys, const u64 *__restrict__ sta
     }
     HC_STAMP(6);
     if (active) {
-      if (off == 0u && slots > cleared) {                           // (the sub-bucket the last clear had been sized for was not counted)
-        uint4 *tk4 = reinterpret_cast<uint4 *>(tk);
-        for (u32 i = tid; i < (u32)SLOTS / E16; i += BLOCK) tk4[i] = make_uint4(ONES, ONES, ONES, ONES);
-        __syncthreads();
-      }
       HC_STAMP(0);
-      u32 hh[KPC];
-      u32 won = 0, pending = 0;
       // (the first probes issued back to back and their answers looked at afterwards -- six independent atomics in flight per thread
       // -- was measured SLOWER: 0.595 against 0.566 ms per launch, profiles/r06_ab_runs.txt: the kernel is issue-bound, not latency-bound)
-#pragma unroll
-      for (int j = 0; j < KPC; j++) {
-        if constexpr (W64) hh[j] = ((((u32)comp[j]) ^ ((u32)(comp[j] >> 32) * 0x85EBCA6Bu)) * 0x9E3779B1u) >> sshift;   // (suffixes of <= 52 bits: the high word holds <= 20)
-        else               hh[j] = (comp[j] * 0x9E3779B1u) >> sshift;
-        if ((u32)j * BLOCK < cnt) {
-          const bool act = (u32)j * BLOCK + tid < cnt;
-          KT old = (KT)0;
-          if (act) old = atomicCAS(&tk[hh[j]], EMPTY, (KT)((comp[j] << CNTB) | (KT)1));
-          const bool w = act && old == EMPTY, dup = act && !w && (old >> CNTB) == comp[j];   // (EMPTY >> 12 IS the all-ones suffix)
-          if (dup) atomicAdd(reinterpret_cast<u32 *>(&tk[hh[j]]), 1u);                        // (the count: the low twelve bits of the entry's low word)
-          won |= w ? (1u << j) : 0u;
-          pending |= (act && !w && !dup) ? (1u << j) : 0u;
+      // one row's first probes.  PARTIAL: the chunk's last row, where `act` says which lanes hold a key; a full row -- (j + 1) *
+      // BLOCK <= cnt, uniform -- carries no lane predicate
+      auto first_probe = [&](auto PARTIAL, const KT c, const bool act) {
+        const u32 h = home_of(c, sshift);
+        KT old = (KT)0;
+        bool pend;
+        if constexpr (decltype(PARTIAL)::value) {
+          if (act) old = atomicCAS(&tk[h], EMPTY, (KT)((c << CNTB) | (KT)1));
+          const bool w = act && old == EMPTY, dup = act && !w && (old >> CNTB) == c;          // (EMPTY >> 12 IS the all-ones suffix)
+          if (dup) atomicAdd(reinterpret_cast<u32 *>(&tk[h]), 1u);                            // (the count: the low twelve bits of the entry's low word)
+          if (w)   atomicAdd(&s_bin[par][(u32)(c >> bshift)], 1u);                            // (a claim: one more distinct suffix in its bin)
+          pend = act && !w && !dup;
+        } else {
+          old = atomicCAS(&tk[h], EMPTY, (KT)((c << CNTB) | (KT)1));
+          const bool w = old == EMPTY, dup = !w && (old >> CNTB) == c;
+          if (dup) atomicAdd(reinterpret_cast<u32 *>(&tk[h]), 1u);
+          if (w)   atomicAdd(&s_bin[par][(u32)(c >> bshift)], 1u);
+          pend = !w && !dup;
         }
-      }
-      u32 steps = 0;
-      while (pending) {                                // linear probing, one step of every still-pending key per round
-#pragma unroll
-        for (int j = 0; j < KPC; j++) {
-          if ((pending >> j) & 1u) {
-            hh[j] = (hh[j] + 1) & smask;
-            const KT old = atomicCAS(&tk[hh[j]], EMPTY, (KT)((comp[j] << CNTB) | (KT)1));
-            const bool w = old == EMPTY, dup = !w && (old >> CNTB) == comp[j];
-            if (dup) atomicAdd(reinterpret_cast<u32 *>(&tk[hh[j]]), 1u);
-            if (w) won |= 1u << j;
-            if (w || dup) pending &= ~(1u << j);
-          }
+        // a key that met another suffix goes to the wave's queue: the few such keys of a row (the table is ~7 % full while it
+        // is filled) are probed on LATER, one per lane of consecutive lanes, instead of in rounds the whole wave walks for them
+        const u64 pm = __ballot(pend);
+        if (pm) {                                      // (uniform)
+          const u32 pc = (u32)__popcll(pm);
+          if (stream_queue_must_drain(qn, pc)) drain_queue(qn, smask, sshift, probe_max);
+          if (pend) s_q[stream_queue_index(wave, qn, __builtin_amdgcn_mbcnt_hi((u32)(pm >> 32), __builtin_amdgcn_mbcnt_lo((u32)pm, 0u)))] = c;
+          qn += pc;
         }
-        if (++steps > probe_max) { s_ovf = 1u; pending = 0; }       // a long chain: the table fills, or the suffixes crowd a few home slots
-      }
-      {
-        u64 wm[KPC];
-        u32 tot = 0;
+      };
+      const u32 full_rows = cnt / (u32)BLOCK;          // (uniform; cnt <= KPC * BLOCK)
 #pragma unroll
-        for (int j = 0; j < KPC; j++) { wm[j] = __ballot((won >> j) & 1u); tot += (u32)__popcll(wm[j]); }
-        u32 base = 0;
-        if (lane == 0) base = atomicAdd(&s_nd, tot);
-        base = (u32)__builtin_amdgcn_readfirstlane((int)base);
-        if (base + tot > (u32)DCAP) { if (lane == 0) s_ovf = 1u; }  // more distinct suffixes than the list holds
-        else {
+      for (int j = 0; j < KPC; j++)
+        if ((u32)j < full_rows) first_probe(std::false_type(), comp[j], true);
+      if (cnt & ((u32)BLOCK - 1u)) {                   // the one partial row, behind the full ones: ONE body for whichever row it is
+        KT c = comp[0];
 #pragma unroll
-          for (int j = 0; j < KPC; j++) {
-            if (wm[j]) {
-              if ((won >> j) & 1u)
-                lst[base + __builtin_amdgcn_mbcnt_hi((u32)(wm[j] >> 32), __builtin_amdgcn_mbcnt_lo((u32)wm[j], 0u))] = (unsigned short)hh[j];
-              base += (u32)__popcll(wm[j]);
-            }
-          }
-        }
+        for (int j = 1; j < KPC; j++) c = (full_rows == (u32)j) ? comp[j] : c;
+        first_probe(std::true_type(), c, full_rows * (u32)BLOCK + tid < cnt);
       }
+      if (last && qn) drain_queue(qn, smask, sshift, probe_max);   // (the queue outlives a chunk, not a sub-bucket: the barrier below ends its inserts)
       HC_STAMP(1);
     }
     if (!last) { off += csz; continue; }               // the sub-bucket's next chunk (no barrier: one table, atomics only)
 
     // ---- the sub-bucket's last chunk is in: its distinct suffixes, ascending, back in place ----
     const u32 a = a0, g = g0, n = n0;
-    const u32 nslots = slots_for(n1);                  // what the next insert phase needs cleared
-    if (active) __syncthreads();                       // every insert and every list append of the sub-bucket is done
+    const u32 nvec = slots / E16;                      // 16-byte vectors of the table this sub-bucket had
+    if (active) __syncthreads();                       // every insert of the sub-bucket is done
     a0 = a1; n0 = n1; g0 = g1; off = 0; csz = ncs;
-    a1 = a2; n1 = n2; g1 = g2;
+    a1 = a2; n1 = n2; g1 = g2; ncs = chunk_size(n2);
+    slots = csz ? stream_slots_for(n0, (u32)SLOTS) : 256u;   // (a sub-bucket that is not counted here has no table)
+    smask = slots - 1u; sshift = 32u - (u32)__builtin_ctz(slots); probe_max = RETRY ? slots : PROBE_MAX;
     if (active) {
-      const bool ovf = s_ovf != 0u;
-      const u32 D = s_nd;
+      // The claims have counted the distinct suffixes into 256 bins by their top eight bits; the bins scanned, WHERE the entries are
+      // is read off the table itself: every thread sweeps vectors tid, tid + BLOCK, .. of the sub-bucket's `slots` entries and
+      // takes each non-empty one's place from its bin's cursor.  Order inside a bin is whatever the atomics give: the rank below
+      // makes it ascending.  D is the bin total: "more than DCAP" is decided before anything is written.
+      uint4 *tk4 = reinterpret_cast<uint4 *>(tk);
+      bool ovf = s_ovf != 0u;
+      u32 D = 0;
       if (!ovf) {
-        // the distinct entries into 256 bins by their top eight bits: one returning LDS atomic each
-        const bool big = D > 2u * (u32)BLOCK;          // more than two per thread (low-coverage input): staged through LDS
-        KT  ent0 = 0, ent1 = 0;
-        u32 li0 = 0, li1 = 0;
-        if (!big) {
-          if (tid < D)              { ent0 = tk[lst[tid]];              li0 = atomicAdd(&s_bin[par][(u32)(ent0 >> (CNTB + bshift))], 1u); }
-          if (tid + (u32)BLOCK < D) { ent1 = tk[lst[tid + (u32)BLOCK]]; li1 = atomicAdd(&s_bin[par][(u32)(ent1 >> (CNTB + bshift))], 1u); }
-        } else {
-          for (u32 i = tid; i < D; i += BLOCK) {
-            const KT e = tk[lst[i]];
-            srt[i] = e;
-            lst[i] = (unsigned short)atomicAdd(&s_bin[par][(u32)(e >> (CNTB + bshift))], 1u);
-          }
-        }
-        __syncthreads();
         HC_STAMP(2);
-        if (tid < 64) {                                // one wave scans the 256 bin counts: four per lane
-          uint4 c = reinterpret_cast<uint4 *>(s_bin[par])[tid];
+        if (tid < 64) {                                // one wave scans the 256 bin counts, four per lane: bin b's bounds -> [b], [b + 1]
+          const uint4 c = reinterpret_cast<uint4 *>(s_bin[par])[tid];
           const u32 s4 = c.x + c.y + c.z + c.w;
           u32 x = s4;
 #pragma unroll
           for (int d = 1; d < 64; d <<= 1) { const u32 y = __shfl_up(x, d); if ((int)lane >= d) x += y; }
           const u32 e0 = x - s4;
-          reinterpret_cast<uint4 *>(s_bin[par])[tid] = make_uint4(e0, e0 + c.x, e0 + c.x + c.y, e0 + c.x + c.y + c.z);
-          if (tid == 63) s_bin[par][BLOCK] = x;
+          // (one entry up: [b + 1] is bin b's cursor, it ends at the bin's end, which is bin b + 1's start; [0] stays 0.  Lane t
+          // writes [4t + 4], which lane t + 1 has read as its c.x: one wave, the read is an earlier instruction)
+          u32 *S = s_bin[par] + 1u + 4u * tid;
+          S[0] = e0; S[1] = e0 + c.x; S[2] = e0 + c.x + c.y; S[3] = e0 + c.x + c.y + c.z;
+          if (tid == 0)  s_bin[par][0] = 0;
+          if (tid == 63) s_bin[par][BLOCK + 1] = x;
         } else {
-          // ... the other three clear what the NEXT insert phase uses (tk, lst and s_nd are dead by now; staged: the table takes
-          // the sorted entries first and is cleared at the end)
-          uint4 *tk4 = reinterpret_cast<uint4 *>(tk);
-          if (!big) for (u32 i = tid - 64; i < nslots / E16; i += BLOCK - 64) tk4[i] = make_uint4(ONES, ONES, ONES, ONES);
+          // ... the other three zero the bin counts of the NEXT sub-bucket
           for (u32 i = tid - 64; i < BLOCK; i += BLOCK - 64) s_bin[par ^ 1u][i] = 0;
-          if (tid == 64) s_nd = 0;
         }
-        cleared = nslots;
         __syncthreads();
-        if (!big) {
-          if (tid < D)              srt[s_bin[par][(u32)(ent0 >> (CNTB + bshift))] + li0] = ent0;
-          if (tid + (u32)BLOCK < D) srt[s_bin[par][(u32)(ent1 >> (CNTB + bshift))] + li1] = ent1;
-        } else {
-          for (u32 i = tid; i < D; i += BLOCK) { const KT e = srt[i]; tk[s_bin[par][(u32)(e >> (CNTB + bshift))] + lst[i]] = e; }
+        D = s_bin[par][BLOCK + 1];
+        ovf = D > (u32)DCAP;                           // more distinct suffixes than srt holds
+      }
+      if (!ovf) {
+        // (the table is dead behind this sweep: EMPTY goes back into every vector right after it is read, and the barrier below
+        // stands between that and the next sub-bucket's inserts)
+        // two vectors per trip: their cursor atomics are issued together and waited for once, not one LDS round trip per entry
+        const uint4 ones4 = make_uint4(ONES, ONES, ONES, ONES);
+        for (u32 v = tid; v < nvec; v += 2u * BLOCK) {
+          const bool two = v + (u32)BLOCK < nvec;
+          const uint4 q0 = tk4[v];
+          uint4 q1 = ones4;
+          if (two) q1 = tk4[v + (u32)BLOCK];
+          tk4[v] = ones4;
+          if (two) tk4[v + (u32)BLOCK] = ones4;
+          u32 pos0[E16], pos1[E16];
+#pragma unroll
+          for (int i = 0; i < (int)E16; i++) {
+            const KT e0 = vec_entry(q0, i), e1 = vec_entry(q1, i);
+            pos0[i] = 0; pos1[i] = 0;
+            if (e0 != EMPTY) pos0[i] = atomicAdd(&s_bin[par][1u + (u32)(e0 >> (CNTB + bshift))], 1u);
+            if (e1 != EMPTY) pos1[i] = atomicAdd(&s_bin[par][1u + (u32)(e1 >> (CNTB + bshift))], 1u);
+          }
+#pragma unroll
+          for (int i = 0; i < (int)E16; i++) {
+            const KT e0 = vec_entry(q0, i), e1 = vec_entry(q1, i);
+            if (e0 != EMPTY) srt[pos0[i]] = e0;
+            if (e1 != EMPTY) srt[pos1[i]] = e1;
+          }
         }
         __syncthreads();
         HC_STAMP(3);
 
         // rank inside the bin, then back in place: the distinct suffixes ascending from the sub-bucket's own start
         const u32 *sb = s_bin[par];
-        const KT *sorted = big ? tk : srt;
+        const KT *sorted = srt;
         KT *kout = keys + a;
         u32 *cout = cnt_tmp + a;
         for (u32 p = tid; p < D; p += BLOCK) {
@@ -1208,26 +1243,19 @@ void hash_count_stream_kernel(KT *__restrict__ keys, const u64 *__restrict__ sta
           cout[r] = (u32)e & CNT_MASK;
         }
         if (tid == 0) group_distinct[tr_index(g, tr_a, tr_b)] = D;
-        if (big) {                                     // the table held the sorted entries: cleared now, behind two more barriers
-          __syncthreads();
-          uint4 *tk4 = reinterpret_cast<uint4 *>(tk);
-          for (u32 i = tid; i < nslots / E16; i += BLOCK) tk4[i] = make_uint4(ONES, ONES, ONES, ONES);
-          __syncthreads();
-        }
         par ^= 1u;                                     // (srt and this parity's bin table are next written three barriers on)
         HC_STAMP(4);
       } else {
-        // more distinct suffixes than the list holds, or a probe chain above the bound: nothing is written, the retry launch takes
+        // more distinct suffixes than srt holds, or a probe chain above the bound: nothing is written, the retry launch takes
         // the sub-bucket.  RETRY: a whole turn of the table found no room, which the launcher's sizes exclude -- the count's error word is raised
-        __syncthreads();                               // (everybody has read s_ovf and s_nd)
-        uint4 *tk4 = reinterpret_cast<uint4 *>(tk);
+        __syncthreads();                               // (everybody has read s_ovf and D)
         for (u32 i = tid; i < (u32)SLOTS / E16; i += BLOCK) tk4[i] = make_uint4(ONES, ONES, ONES, ONES);
+        s_bin[0][tid] = 0; s_bin[1][tid] = 0;          // (whichever of the two the sweep had got to)
         if (tid == 0) {
-          s_nd = 0; s_ovf = 0;
+          s_ovf = 0;
           if constexpr (RETRY) { atomicExch(error + 2, 1u); group_distinct[tr_index(g, tr_a, tr_b)] = 0; }
           else                 retry_list[atomicAdd((unsigned long long *)retry_count, 1ull)] = g;
         }
-        cleared = (u32)SLOTS;
         __syncthreads();
       }
     } else if (n == 0u && tid == 0) {
@@ -2447,10 +2475,11 @@ constexpr size_t HUGE_LDS128 = (size_t)(8 + 4) * HUGE_SLOTS128 + (size_t)8 * (HU
 constexpr size_t HUGE_LDS128_WIDE = (size_t)(8 + 8 + 4) * HUGE_SLOTS128 + (size_t)(8 + 8) * (HUGE_CAP128 + 16) + (size_t)4 * HUGE_CAP128;
 constexpr u64 FIN_CAP_HASH  = 1536;                               // hash-count kernel: 2048 slots, 26 KiB of LDS, 6 workgroups per CU
 // hash_count_stream_kernel: sub-buckets of up to 4094 keys (a 12-bit count, all ones excluded) in chunks of <= 1536; 2048-entry table
-// and room for 1280 distinct suffixes (17.6 KiB of LDS, eight workgroups per CU); the retry instantiation: 8192 entries, 58 KiB
+// and room for 1280 distinct suffixes (17.0 KiB of LDS with the waves' pending-key queues, eight workgroups per CU); the retry
+// instantiation: 8192 entries, 52 KiB
 constexpr u64 FIN_CAP_STREAM = 4094;
 constexpr int FIN_STREAM_KPC = 6, FIN_STREAM_SLOTS = 2048, FIN_STREAM_DCAP = 1280, FIN_STREAM_RETRY_SLOTS = 8192, FIN_STREAM_RETRY_DCAP = 4096;
-// ... on whole 8-byte k-mers (64-bit entries): 2048 entries and room for 1024 distinct suffixes: 28.3 KiB, five workgroups per CU
+// ... on whole 8-byte k-mers (64-bit entries): 2048 entries and room for 1024 distinct suffixes: 30.0 KiB, five workgroups per CU
 constexpr int FIN_STREAM64_DCAP = 1024;
 
 // 16-byte keys: the same 1536-key tables (sub-buckets of up to 1152 k-mers); a file whose largest sub-bucket holds at most 768 takes
