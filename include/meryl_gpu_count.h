@@ -676,6 +676,9 @@ typedef struct mgc_profile {
                                     * 16 bases, where the count has one: not with MGC_PACKED_BASES=0) ... */
   uint64_t partition_bytes;        /* ... and of the partition (the packed base stream read -- without one, the bases -- + the k-mers written in
                                     * the layout the files take: 5 / 8 / 12 / 16 B) */
+  /* kernel launches of the first / the second grouping pass: pass_launches[] counts one per FILE and pass whether or not files shared a
+   * launch; a batched launch over m files (mgc_device.h, GroupBatch) adds m there and 1 here */
+  uint32_t pass_kernel_launches[2];
 } mgc_profile;
 int mgc_set_profiling(mgc_session *s, int enable);
 int mgc_get_profile(const mgc_session *s, mgc_profile *p);

@@ -199,6 +199,7 @@ class Profile(ctypes.Structure):
         ("pack_ms", ctypes.c_double),
         ("hist_bytes", ctypes.c_uint64),
         ("partition_bytes", ctypes.c_uint64),
+        ("pass_kernel_launches", ctypes.c_uint32 * 2),
     ]
 
 

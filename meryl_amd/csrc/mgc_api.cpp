@@ -46,6 +46,8 @@ Switches read_switches() {
   sw.huge_streams = (uint32_t)num("MGC_HUGE_STREAMS", 4);
   sw.huge_slices = !off("MGC_HUGE_SLICES");
   sw.pass_stagger = (uint32_t)num("MGC_PASS_STAGGER", 0);
+  sw.group_batch_bytes = num("MGC_GROUP_BATCH_BYTES", sw.group_batch_bytes);
+  sw.group_batch_files = (uint32_t)num("MGC_GROUP_BATCH_FILES", 0);
   return sw;
 }
 }  // namespace mgc

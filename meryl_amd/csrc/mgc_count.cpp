@@ -2,6 +2,8 @@
 // packed (k-mer, count) result in the session's arena.  CountPlan makes every host-side decision about the buckets ("files") and
 // calls nothing on the device; Count runs the stages in the order the device sees them.
 #include "mgc_session.hpp"
+#include "mgc_group_batch.hpp"
+#include "mgc_group_route.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -57,6 +59,7 @@ struct FilePlan {
   uint64_t maxsub = 0, nlarge = 0, nzcount = 0;   // its statistics: largest sub-bucket, oversized ones, non-empty ones
   bool fallback = false;              // finished by the stable sort of all bits and the run-length kernels
   uint32_t passes = 0; bool narrowed = false, k96_passes = false;   // (profile) grouping passes that ran, and on what
+  int batch_lead = -1;                // its passes ran in a batched launch: the batch's first file, which holds the launch's events (-1: launches of its own)
   uint64_t ngf() const { return size ? (uint64_t)1 << top : 0; }
 };
 
@@ -324,6 +327,8 @@ struct Count {
   static constexpr uint32_t ev_per_file = 2 * 16;        // room for 16 passes per file
   std::vector<hipEvent_t> pass_ev;
   uint32_t sort_launch_groups = 0;
+  size_t y_base_bytes = 0;                               // what Y holds without batched launches (one file's keys, or all of them)
+  std::vector<unsigned char> h_batch_tables;             // the batched launches' descriptor tables (copied from here: lives until the count returns)
   int group_dbg_left = 2;                                // MGC_GROUP_DBG: instrumented files this count may still run (GroupFile::dbg)
 
   // the finish path
@@ -369,6 +374,7 @@ struct Count {
   int count_full();                                      // MGC_FINISH=0
   int count_finish(); int finish_buffers(); int prepare_headers(); int narrow_prepare(int only, int skip);
   int probe_file(); int group_file(uint32_t b); int stats_file(uint32_t b); int group_all();
+  mgc::GroupFile group_desc(uint32_t b); bool batch_file(uint32_t b) const; int group_batches();
   int huge_setup(); int huge_sync_all(); int huge_join_all();
   int finish_file(uint32_t b); int oversized_streams(uint32_t b, bool *stream); int widen_back(uint32_t b, bool *unordered);
   int count_file(uint32_t b, bool stream); int fallback_file(uint32_t b, bool unordered);
@@ -477,7 +483,8 @@ int Count::buffers() {
   mgc::make_sort_plan(0, rem_bits, &full);
   const bool odd = !use_finish && (full.num_passes & 1u) != 0;
   if (!in.keys) HIP_TRY(s, s->ensure(S::B_X, kbytes * N));
-  HIP_TRY(s, s->ensure(S::B_Y, kbytes * (odd ? N : plan.max_bucket)));
+  y_base_bytes = kbytes * (odd ? N : plan.max_bucket);
+  HIP_TRY(s, s->ensure(S::B_Y, y_base_bytes));
   X = in.keys ? reinterpret_cast<unsigned char *>(in.keys) : reinterpret_cast<unsigned char *>(s->buf[S::B_X].p);
   Y = reinterpret_cast<unsigned char *>(s->buf[S::B_Y].p);
   sort_ws_bytes = mgc::sort_workspace_bytes(plan.max_bucket) + 256;
@@ -608,22 +615,30 @@ int Count::narrow_prepare(int only, int skip) {
   return MGC_OK;
 }
 
+// what the grouping launchers are told about file b (mgc_device.h, GroupFile)
+mgc::GroupFile Count::group_desc(uint32_t b) {
+  FilePlan &x = plan.files[b];
+  const bool msd = d_nhdrs && d_nws && (x.kind == Group::WIDE || x.msd_ok);
+  mgc::GroupFile f;
+  f.keys = seg(b); f.alt = (void *)Y; f.n = x.size; f.plan = &x.sp;
+  f.layout = x.k96 ? mgc::GroupKeys::K96 : (kw == 2 ? mgc::GroupKeys::K128 : (soa_hi_mask ? mgc::GroupKeys::SOA5 : mgc::GroupKeys::U64));
+  f.soa_hi_mask = soa_hi_mask;
+  f.d_error = d_err; f.d_sub_starts = d_substart + x.sbase; f.st = st;
+  f.pass_events = s->profiling ? &pass_ev[(size_t)b * ev_per_file] : nullptr;
+  f.prepared = msd ? (void *)(d_nhdrs + hdr_bytes * b) : nullptr; f.scratch = msd ? (void *)(d_nws + x.nws_off) : nullptr;
+  f.ws = sort_ws; f.ws_bytes = sort_ws_bytes - 256;
+  f.pipe = sw.group_pipe; f.stagger = sw.pass_stagger;
+  f.dbg = sw.group_dbg && msd && x.kind == Group::NARROW && group_dbg_left > 0;     // (developer output: the first two such files of a count)
+  return f;
+}
+
 // ---- A. grouping passes of one file: global passes on its top bits only (the finish only needs the file grouped by them) ----
 int Count::group_file(uint32_t b) {
   FilePlan &x = plan.files[b];
   if (x.size == 0) return MGC_OK;
   void *src = seg(b);
-  hipEvent_t *pe = s->profiling ? &pass_ev[(size_t)b * ev_per_file] : nullptr;
-  const bool msd = d_nhdrs && d_nws && (x.kind == Group::WIDE || x.msd_ok);
-  mgc::GroupFile f;
-  f.keys = src; f.alt = (void *)Y; f.n = x.size; f.plan = &x.sp;
-  f.layout = x.k96 ? mgc::GroupKeys::K96 : (kw == 2 ? mgc::GroupKeys::K128 : (soa_hi_mask ? mgc::GroupKeys::SOA5 : mgc::GroupKeys::U64));
-  f.soa_hi_mask = soa_hi_mask;
-  f.d_error = d_err; f.d_sub_starts = d_substart + x.sbase; f.st = st; f.pass_events = pe;
-  f.prepared = msd ? (void *)(d_nhdrs + hdr_bytes * b) : nullptr; f.scratch = msd ? (void *)(d_nws + x.nws_off) : nullptr;
-  f.ws = sort_ws; f.ws_bytes = sort_ws_bytes - 256;
-  f.pipe = sw.group_pipe; f.stagger = sw.pass_stagger;
-  f.dbg = sw.group_dbg && msd && x.kind == Group::NARROW && group_dbg_left > 0;     // (developer output: the first two such files of a count)
+  mgc::GroupFile f = group_desc(b);
+  hipEvent_t *pe = f.pass_events;
   switch (x.kind) {
   case Group::NONE:                                        // (a file of one sub-bucket: nothing to group)
     return MGC_OK;
@@ -700,8 +715,89 @@ int Count::probe_file() {
 // back, then the count kernels run.  (A pipelined form -- a file's count kernel on another stream as soon as its statistics are back,
 // beside the passes of the files after it -- was built in round 4, measured slower and removed in round 5: profiles/r04y_pipe_ab.txt,
 // DESIGN_HISTORY.md.)
+// The grouping passes themselves: the narrowed files of the judged form go through them in BATCHES -- one launch per pass over the
+// tiles of all files of a batch, so that the device does not drain and fill again 128 times per count (mgc_sort.hip, radix_group_body,
+// BATCH; which files share a launch and where their words lie in Y meanwhile: mgc_group_batch.hpp).  Every other file, and every
+// file that is alone in its batch, keeps the per-file launches.
+bool Count::batch_file(uint32_t b) const {
+  const FilePlan &x = plan.files[b];
+  return (int)b != probe && x.size && x.top && x.kind == Group::NARROW && x.msd_ok && d_nhdrs && d_nws && soa_hi_mask != 0 &&
+         mgc::group_batch_form(true, true, sw.group_pipe, sw.group_dbg, sw.pass_stagger);
+}
+
+int Count::group_batches() {
+  std::vector<mgc::BatchFile> bf(nb);
+  for (uint32_t b = 0; b < nb; b++) {
+    const FilePlan &x = plan.files[b];
+    // (shifts and digit widths are arguments of a launch: the key is the plan's digits, which also fix both instantiations)
+    bf[b] = mgc::BatchFile{x.size, x.sp.pass_shift[0] | (x.sp.pass_bits[0] << 8) | (x.sp.pass_bits[1] << 16), batch_file(b)};
+  }
+  const uint64_t tile_keys = (uint64_t)mgc::GROUP_BLOCK * mgc::GROUP_KPT_NARROW0P;
+  // Y has to hold the words of all files of a batch at once.  Where the arena cannot grow to the budget the budget is halved, down to
+  // single files (which fit the Y every count has).  Nothing uses Y at this point: the probe file's kernels have been joined.
+  uint64_t budget = sw.group_batch_bytes;
+  std::vector<mgc::Batch> batches;
+  for (;;) {
+    batches = mgc::group_plan_batches(bf, budget, sw.group_batch_files, tile_keys);
+    const size_t need = std::max<size_t>(y_base_bytes, (size_t)mgc::group_batches_y_bytes(batches));
+    if (s->buf[S::B_Y].cap >= need) break;
+    const hipError_t e = s->ensure(S::B_Y, need);
+    if (e == hipSuccess) break;
+    (void)hipGetLastError();
+    if (need <= y_base_bytes) HIP_TRY(s, e);
+    budget /= 2;
+  }
+  Y = reinterpret_cast<unsigned char *>(s->buf[S::B_Y].p);
+  halt[0] = Y;
+  if (sw.finish_trace) {
+    uint32_t ne = 0, shared = 0;
+    for (const mgc::BatchFile &f : bf) ne += f.eligible && f.n;
+    for (const mgc::Batch &bt : batches) if (bt.files.size() > 1) shared += (uint32_t)bt.files.size();
+    fprintf(stderr, "[finish] grouping passes: %u files take the batched form, %u of them share launches, %zu batches, %llu bytes of the pass buffer "
+                    "(budget %llu), 5-byte mask %x, headers %d\n", ne, shared, batches.size(),
+            (unsigned long long)mgc::group_batches_y_bytes(batches), (unsigned long long)budget, soa_hi_mask, d_nhdrs && d_nws ? 1 : 0);
+  }
+  size_t table_bytes = 0, nbatch = 0;
+  for (const mgc::Batch &bt : batches) if (bt.files.size() > 1) { table_bytes += mgc::group_batch_table_bytes((uint32_t)bt.files.size()); nbatch++; }
+  if (!nbatch) return MGC_OK;
+  // device: [16 bytes of control words per batch, zeroed][the tables]
+  const size_t ctl_bytes = (nbatch * 16 + 255) / 256 * 256;
+  HIP_TRY(s, s->ensure(S::B_GROUP_BATCH, ctl_bytes + table_bytes));
+  unsigned char *d_gb = reinterpret_cast<unsigned char *>(s->buf[S::B_GROUP_BATCH].p);
+  HIP_TRY(s, hipMemsetAsync(d_gb, 0, ctl_bytes, st));
+  h_batch_tables.assign(table_bytes, 0);
+  size_t at = 0, bi = 0;
+  std::vector<mgc::GroupFile> gf;
+  for (const mgc::Batch &bt : batches) {
+    if (bt.files.size() < 2) continue;
+    const uint32_t lead = bt.files[0].file;
+    gf.clear();
+    for (const mgc::BatchSlot &sl : bt.files) {
+      gf.push_back(group_desc(sl.file));
+      gf.back().alt = (void *)(Y + sl.y_off);
+      gf.back().pass_events = nullptr;
+    }
+    mgc::GroupBatch gb;
+    gb.files = gf.data(); gb.nfiles = (uint32_t)gf.size();
+    gb.d_table = d_gb + ctl_bytes + at; gb.h_table = h_batch_tables.data() + at;
+    gb.d_ctl = reinterpret_cast<uint32_t *>(d_gb + 16 * bi);
+    gb.d_error = d_err; gb.st = st;
+    gb.pass_events = s->profiling ? &pass_ev[(size_t)lead * ev_per_file] : nullptr;
+    HIP_TRY(s, mgc::launch_group_narrow_batch(gb));
+    for (size_t j = 0; j < gf.size(); j++) {
+      FilePlan &x = plan.files[bt.files[j].file];
+      x.tr_a = gf[j].tr_a; x.tr_b = gf[j].tr_b;
+      x.passes = 2; x.narrowed = true; x.batch_lead = (int)lead;
+      sort_launch_groups++;
+    }
+    at += mgc::group_batch_table_bytes(gb.nfiles); bi++;
+  }
+  return MGC_OK;
+}
+
 int Count::group_all() {
-  for (uint32_t b = 0; b < nb; b++) if ((int)b != probe) TRY(group_file(b));   // (the probe file went first)
+  TRY(group_batches());
+  for (uint32_t b = 0; b < nb; b++) if ((int)b != probe && plan.files[b].batch_lead < 0) TRY(group_file(b));   // (the probe file went first)
   tm.end(MGC_STAGE_SORT);
   tm.begin(MGC_STAGE_RLE);
   // the small statistics kernels of all files back to back: they run beside each other
@@ -1059,9 +1155,14 @@ void Count::collect_profile() {
   for (uint32_t b = 0; b < nb; b++) {
     const FilePlan &x = plan.files[b];
     if (x.size == 0) continue;
+    // (a file of a batched launch counts as a launch of its own here -- the fields keep their meaning of one per file and pass -- and
+    // the batch's first file carries the launch's duration; the kernel launches themselves: pass_kernel_launches)
+    const bool follower = x.batch_lead >= 0 && (uint32_t)x.batch_lead != b;
     for (uint32_t p = 0; p < x.passes; p++) {
       hipEvent_t *pe = &pass_ev[(size_t)b * ev_per_file + 2 * p];
-      if (hipEventElapsedTime(&ms, pe[0], pe[1]) != hipSuccess) continue;
+      ms = 0;
+      if (!follower && hipEventElapsedTime(&ms, pe[0], pe[1]) != hipSuccess) continue;
+      if (!follower) prof.pass_kernel_launches[p ? 1 : 0]++;
       prof.sort_pass_ms_total += ms;
       prof.sort_pass_launches++;
       prof.sort_pass_keys += x.size;

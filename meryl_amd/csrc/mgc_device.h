@@ -45,6 +45,11 @@ struct Switches {
   bool     huge_slices = true;  // MGC_HUGE_SLICES=0: a gigantic sub-bucket (above 65536 keys) is streamed by ONE workgroup (round 5)
   uint32_t huge_streams = 4;    // MGC_HUGE_STREAMS: streams the streaming kernels of oversized sub-buckets are spread over (1..4)
   uint64_t bucket_bases = 0;    // MGC_BUCKET_BASES: bases per partition bucket above which the partition gets finer (0: default)
+  uint64_t group_batch_bytes = (uint64_t)1 << 40;   // MGC_GROUP_BATCH_BYTES: bytes of the pass buffer Y the narrowed files of ONE batched grouping
+                                // launch may fill with their 4-byte words (mgc_group_batch.hpp; below two files' words: one launch per file and pass).
+                                // The default holds every file (35 GB at 10 Gbp; measured against 8 GiB and one file: profiles/group_batch_ab.txt);
+                                // where the arena cannot grow to it the count halves it, down to single files
+  uint32_t group_batch_files = 0;   // MGC_GROUP_BATCH_FILES: at most that many files per batched launch (0: as many as the budget holds; tests)
 };
 Switches read_switches();        // (mgc_api.cpp)
 
@@ -173,6 +178,22 @@ size_t     narrow_scratch_bytes(uint64_t n);
 hipError_t launch_narrow_prepare(const uint64_t *d_fine, uint32_t nb, const unsigned char *bits_a, const unsigned char *on, void *d_hdrs,
                                  hipStream_t st);
 hipError_t launch_group_narrow(GroupFile &f);
+// launch_group_narrow_batch -- the same two passes for SEVERAL narrowed files with ONE launch per pass (and one per helper step): the
+// tiles of all files in one ticket sequence, so that the tail of one file's tiles runs beside the head of the next file's.  Only the
+// judged form (mgc_group_route.hpp, group_batch_form: high digit first off the 5-byte layout, fetched a tile ahead) and only files
+// whose plans have the same digits; every file as launch_group_narrow takes it, each with an `alt` of its own (n uint32).
+// d_table / h_table: group_batch_table_bytes(nfiles) on the device and on the host -- the host copy has to live until the stream has
+// passed the launch; d_ctl: four zeroed 32-bit words on the device (the passes' tickets, the helper step's arrival counter).
+struct GroupBatch {
+  GroupFile *files = nullptr; uint32_t nfiles = 0;
+  void *d_table = nullptr, *h_table = nullptr;
+  uint32_t *d_ctl = nullptr;
+  uint32_t *d_error = nullptr;
+  hipStream_t st = nullptr;
+  hipEvent_t *pass_events = nullptr;          // 4 or null: around each pass's launch
+};
+size_t     group_batch_table_bytes(uint32_t nfiles);
+hipError_t launch_group_narrow_batch(GroupBatch &b);
 bool       sort_plan_wide_msd(const SortPlan &plan, uint64_t n, bool on = true /*Switches::wide_msd*/);
 hipError_t launch_hpc_prepare(const uint64_t *d_fine_hpc, uint32_t bucket_bits, const uint64_t on[4], void *d_hdrs, hipStream_t st);
 size_t     wide_scratch_bytes(uint64_t n, uint32_t key_words);

@@ -1,4 +1,4 @@
-// mgc_group_route.hpp -- which instantiation of radix_group_kernel<K, RB, 1024, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD> a grouping
+// mgc_group_route.hpp -- which instantiation of radix_group_kernel<K, RB, 1024, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD, BATCH> a grouping
 // pass runs (mgc_sort.hip: launch_group_narrow, launch_group_wide, the grouping mode of launch_radix_sort).  The launchers there
 // ask these functions and hand the answer to the one table that maps a GroupInst to its template instantiation.  Shared with a
 // stand-alone host program (tests/host/group_route_host.cpp) that pins the rules: plain C++, no HIP header needed.
@@ -13,10 +13,11 @@ enum GroupKey : uint32_t { GROUP_U64, GROUP_U32 /* narrowed words: second pass o
 // the template arguments of one instantiation (BLOCK is 1024 everywhere)
 struct GroupInst {
   GroupKey key; int rb, kpt; bool dbg, narrow, hist2, soa; int pipe, hpcd;
+  bool batch = false;                                       // one launch over the tiles of many files (radix_group_batch_kernel)
 };
 inline bool operator==(const GroupInst &a, const GroupInst &b) {
   return a.key == b.key && a.rb == b.rb && a.kpt == b.kpt && a.dbg == b.dbg && a.narrow == b.narrow && a.hist2 == b.hist2 &&
-         a.soa == b.soa && a.pipe == b.pipe && a.hpcd == b.hpcd;
+         a.soa == b.soa && a.pipe == b.pipe && a.hpcd == b.hpcd && a.batch == b.batch;
 }
 
 // keys per thread of the narrowed passes: the first pass (fetch inside the look-back), the pipelined 5-byte first pass (A/B builds
@@ -56,6 +57,16 @@ inline bool group_pick_narrow(bool msd, bool soa, bool pipe, bool dbg, uint32_t 
   const int rb_first = (ahead && !dbg && bits_first <= 8) ? 8 : 9, rb_second = (!dbg && bits_second <= 8) ? 8 : 9;
   *first  = GroupInst{GROUP_U64, rb_first, ahead ? GROUP_KPT_NARROW0P : GROUP_KPT_NARROW0, dbg, true, msd, soa, ahead ? 2 : 0, 0};
   *second = GroupInst{GROUP_U32, rb_second, GROUP_KPT_NARROW1, dbg, false, false, false, 0, 0};
+  return true;
+}
+
+// ---- many narrowed files in one launch per pass (mgc_group_batch.hpp plans the batches) ----
+// Only the judged form is batched: high digit first off the 5-byte layout, fetched a tile ahead, not instrumented, not staggered.
+// Every other form keeps its per-file launches.
+inline bool group_batch_form(bool msd, bool soa, bool pipe, bool dbg, uint32_t stagger) { return msd && soa && pipe && !dbg && stagger <= 1u; }
+inline bool group_pick_narrow_batch(uint32_t bits_first, uint32_t bits_second, GroupInst *first, GroupInst *second) {
+  if (!group_pick_narrow(true, true, true, false, bits_first, bits_second, first, second)) return false;
+  first->batch = second->batch = true;
   return true;
 }
 

@@ -82,7 +82,8 @@ struct mgc_session {
   enum { B_PART_WS, B_META, B_X, B_Y, B_SORT_WS, B_RLE_WS, B_UNIQUE, B_COUNTS, B_BLOCKS, B_HPC, B_HPC_WS,
          B_SUBSTART, B_GROUPS, B_GSCAN, B_CNT_TMP, B_LARGE, B_NONEMPTY, B_STAGE0, B_STAGE1, B_TEXT_IN0, B_TEXT_IN1, B_TEXT_WS,
          B_TEXT_STATE, B_RK, B_RC, B_R2K, B_R2C, B_MERGE_WS, B_SORT_HDRS, B_FINE, B_NARROW_WS, B_Y2, B_Y3, B_Y4, B_HWS0, B_HWS1, B_HWS2, B_HWS3,
-         B_PACKED /* the count's packed base stream: 2-bit codes + invalid-base masks, written by the histogram, read by the partition */, B_NUM };
+         B_PACKED /* the count's packed base stream: 2-bit codes + invalid-base masks, written by the histogram, read by the partition */,
+         B_GROUP_BATCH /* the batched grouping launches' control words and descriptor tables (mgc_count.cpp, group_batches) */, B_NUM };
   Buf buf[B_NUM];
   size_t arena_bytes() const { size_t t = 0; for (const auto &b : buf) t += b.cap; return t; }
   double tr_alloc = 0;                   // seconds inside hipMalloc / hipFree of the arena (MGC_IO_TRACE)

@@ -437,16 +437,46 @@ struct GroupExtra { u32 digit_bits /* NARROW */; u32 shift2, mask2; u64 *ghist2 
 // HPCD (round 6; `compress`): both digits are dense ranks (hpc_digit: ~30 VALU instructions, taken three times per key and pass plus once
 // for HIST2 -- the whole-key passes of `compress` were VALU-bound at 0.357 ms per 69 M keys against 0.266 ms for plain bit digits): the
 // 4096 ranks of the twelve bits a digit is taken from lie in 8 KiB of LDS behind the tile, a digit is one 16-bit LDS read.
+//
+// BATCH: ONE launch runs a pass over the tiles of MANY files (the arguments that belong to a file are unused: `n` is the number of files
+// and `region_start` points at their descriptors -- the argument list, and with it the code of every per-file instantiation, is the
+// one it was: profiles/group_batch_parity.txt).  The launch has one dense ticket sequence over
+// the tiles of all its files; a table of per-file descriptors in global memory (GroupBatchFile, bfiles[nbf + 1]) says where a file's
+// tiles start in that sequence, and everything that belongs to a file rather than to the launch -- its keys, its output, its digit
+// bases, its look-back rows, the other digit's histogram, a second pass's regions -- comes from the descriptor of the file a tile lies
+// in.  The shifts and digit widths are the launch's: only files with the same plan digits share a launch.  A workgroup's tickets only
+// grow, so the file of an announced tile is found by walking forward from the file of the tile announced before it.  Row numbers of
+// the look-back are tile numbers INSIDE the file: a file's first tile publishes its inclusive prefix at once and no walker reads a row
+// of another file.  HIST2: the counters are flushed to the file's histogram and cleared when a workgroup's current tile leaves a file.
+// PROGRESS (the argument of the per-file launch, unchanged): tickets are dense and only handed to workgroups that run; a tile waits
+// only for earlier tiles of its own file; those have smaller tickets, so they are held by running workgroups (or are done), and the
+// tile with the smallest ticket that is not done waits for nobody.  The spin is bounded as before (RS_SPIN_LIMIT, the error flag),
+// and nothing here spins on what another launch produces: a batch's second pass is a launch of its own behind the first in stream order.
+struct GroupBatchFile {
+  u64 tile0;                                 // the file's first tile in the launch's ticket sequence; entry [nbf]: the tiles of all files
+  u64 tiles;                                 // (second pass: its tile count, from which narrow_mid_batch_kernel makes tile0)
+  u64 n;
+  const void *in; void *out;
+  u64 *gbase, *status, *ghist2;
+  u64 *region_start; u32 *region_tiles;      // a second pass's regions (written by narrow_mid_batch_kernel)
+  u64 *sub_starts;                           // where narrow_bounds_batch_kernel leaves the sub-bucket boundaries
+};
+
 template <typename K, int RB, int BLOCK, int KPT, bool DBG, bool NARROW = false, bool HIST2 = false, bool SOA = false, int PIPE = 0 /* 1: the next fetch before the write-out; 2: after it */,
-          int HPCD = 0 /* 1: both digits are dense ranks; 2: only this pass's (the other digit, HIST2's, is a plain bit field) */>
+          int HPCD = 0 /* 1: both digits are dense ranks; 2: only this pass's (the other digit, HIST2's, is a plain bit field) */,
+          bool BATCH = false /* the tiles of many files: `n` files, their descriptors in place of region_start, every other per-file argument unused */>
 __global__ __launch_bounds__(BLOCK, (GroupSmem<K, RB, BLOCK, KPT, group_xb<K, RB, NARROW>()>::MIN_WAVES_PER_SIMD))
 void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::type *__restrict__ out, u64 n, u32 shift, u32 dmask,
                         const u64 *__restrict__ gbase, u64 *__restrict__ status, u32 *__restrict__ ticket,
                         u32 *__restrict__ error_flag, u64 num_tiles_plain,
-                        const u64 *__restrict__ region_start,   // [RS_MAX_RADIX + 1] or nullptr (plain tiles)
+                        const u64 *__restrict__ region_start,   // [RS_MAX_RADIX + 1] or nullptr (plain tiles); BATCH: GroupBatchFile[n + 1]
                         const u32 *__restrict__ region_tiles,   // [RS_MAX_RADIX + 1] exclusive; last = total tiles
                         GroupExtra ex, u64 *__restrict__ dbg) {
+  // BATCH: the files' descriptors and their number ([nbf] closes the tile sequence)
+  const GroupBatchFile *__restrict__ bfiles = BATCH ? reinterpret_cast<const GroupBatchFile *>(region_start) : nullptr;
+  const u32 nbf = BATCH ? (u32)n : 0u;
   const u32 digit_bits = ex.digit_bits;
+  static_assert(!BATCH || (!DBG && !HPCD), "the batched forms: the judged plan's two passes");
   __shared__ u32 s_h2[HIST2 ? RS_MAX_RADIX : 1];
   if (HIST2) { for (u32 i = threadIdx.x; i < (u32)RS_MAX_RADIX; i += BLOCK) s_h2[i] = 0; }
   using SM = GroupSmem<K, RB, BLOCK, KPT, group_xb<K, RB, NARROW>()>;
@@ -484,9 +514,21 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
   // this thread's slice of the region table stays in registers
   // (a narrowing pass is a first pass: plain tiles -- known at compile time, so that the region slice below costs it no registers: the
   // 5-byte pass spilled them and reloaded them at the top of every tile behind an s_waitcnt vmcnt(0), i.e. behind its own prefetch)
-  const bool regions = !NARROW && (region_tiles != nullptr);
+  const bool regions = !NARROW && (BATCH || region_tiles != nullptr);
   u64 rt_lo = 0, rt_hi = 0, rs = 0, re = 0, total_tiles = num_tiles_plain;
-  if (regions) {
+  // BATCH: the slice is that of file `af`, the file of the tile announced last; it is loaded again when an announced tile lies in
+  // another file (the same for all threads: tickets are the workgroup's)
+  u32 af = 0;
+  auto load_regions = [&](const u64 *rsp, const u32 *rtp) __attribute__((always_inline)) {
+    if (tid0 < (u32)RS_MAX_RADIX) {
+      rt_lo = rtp[tid0]; rt_hi = rtp[tid0 + 1];
+      rs = rsp[tid0];    re = rsp[tid0 + 1];
+    }
+  };
+  if constexpr (BATCH) {
+    total_tiles = bfiles[nbf].tile0;
+    if (regions) load_regions(bfiles[0].region_start, bfiles[0].region_tiles);
+  } else if (regions) {
     if (tid0 < (u32)RS_MAX_RADIX) {
       rt_lo = region_tiles[tid0]; rt_hi = region_tiles[tid0 + 1];
       rs = region_start[tid0];    re = region_start[tid0 + 1];
@@ -498,6 +540,26 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
   // i.e. behind its write-out stores, at the top of every tile: round 6, found in the ISA)
   auto announce = [&](u64 t, int slot) __attribute__((always_inline)) {   // key range of tile t -> s_info[2*slot..]
     if (t >= total_tiles) return;
+    if constexpr (BATCH) {
+      // the tile's file and its number inside the file go along in s_tmp[40 + 2 * slot ..] (the scans use s_tmp[0 .. 16], the tickets
+      // s_tmp[32 .. 34]); t < bfiles[nbf].tile0 ends the walk, files without tiles are walked over
+      const u32 tu = __builtin_amdgcn_readfirstlane((u32)t);
+      u32 f = af;
+      while ((u64)tu >= bfiles[f + 1].tile0) f++;
+      if (regions && f != af) load_regions(bfiles[f].region_start, bfiles[f].region_tiles);
+      af = f;
+      const u64 lt = (u64)tu - bfiles[f].tile0;
+      const bool mine = regions ? (rt_lo <= lt && lt < rt_hi) : (tid0 == 0);
+      const u64  kb   = regions ? rs + (lt - rt_lo) * (u64)TILE : lt * (u64)TILE;
+      const u64  endk = regions ? re : bfiles[f].n;
+      if (mine) {
+        s_info[2 * slot] = kb;
+        s_info[2 * slot + 1] = (endk - kb < (u64)TILE) ? endk - kb : (u64)TILE;
+        s_tmp[40 + 2 * slot] = f;
+        s_tmp[41 + 2 * slot] = (u32)lt;
+      }
+      return;
+    }
     const bool mine = regions ? (rt_lo <= t && t < rt_hi) : (tid0 == 0);   // exactly one thread (empty regions own no tile)
     const u64  kb   = regions ? rs + (t - rt_lo) * (u64)TILE : t * (u64)TILE;
     const u64  endk = regions ? re : n;
@@ -547,12 +609,18 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
   auto dig_of = [&](int j) __attribute__((always_inline)) -> u32 { return (dgp[j / DPR] >> (DBITS * (j % DPR))) & ((1u << DBITS) - 1u); };
   // HIST2 of a narrowing pass counts the other digit from the WORDS: below this pass's digit it sits where it sat in the key
   const u32 shift2w = (ex.shift2 >= shift + digit_bits) ? ex.shift2 - digit_bits : ex.shift2;
+  // the file the fetches read: the launch's; BATCH: that of the tile a fetch is issued for (fetch_from)
+  const K *in_f = in;
+  u64 n_f = n;
+  auto fetch_from = [&](u32 f) __attribute__((always_inline)) {
+    if constexpr (BATCH) { in_f = reinterpret_cast<const K *>(bfiles[f].in); n_f = bfiles[f].n; }
+  };
   auto fetch = [&](u64 kb, u32 nv) __attribute__((always_inline)) {
     if constexpr (SOA) {
       struct __attribute__((aligned(4))) LVec { u32 v[4]; };
       struct __attribute__((packed, aligned(1))) HWord { u32 v; };
-      const u32 *lo32 = reinterpret_cast<const u32 *>(in) + kb;
-      const uint8_t *hi8 = reinterpret_cast<const uint8_t *>(in) + 4ull * n + kb;
+      const u32 *lo32 = reinterpret_cast<const u32 *>(in_f) + kb;
+      const uint8_t *hi8 = reinterpret_cast<const uint8_t *>(in_f) + 4ull * n_f + kb;
       const u32 hm = ex.soa_hi_mask;
 #pragma unroll
       for (int g = 0; g < KPT / 4; g++) {
@@ -570,7 +638,7 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
       }
       return;
     }
-    const K *base = in + kb;
+    const K *base = in_f + kb;
 #pragma unroll
     for (int g = 0; g < KPT / VEC; g++) {
       const u32 first = idx_of(g * VEC);
@@ -595,8 +663,8 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
     if constexpr (PIPE && SOA) {
       struct __attribute__((aligned(4))) LVec { u32 v[4]; };
       struct __attribute__((packed, aligned(1))) HWord { u32 v; };
-      const u32 *lo32 = reinterpret_cast<const u32 *>(in) + kb;
-      const uint8_t *hi8 = reinterpret_cast<const uint8_t *>(in) + 4ull * n + kb;
+      const u32 *lo32 = reinterpret_cast<const u32 *>(in_f) + kb;
+      const uint8_t *hi8 = reinterpret_cast<const uint8_t *>(in_f) + 4ull * n_f + kb;
 #pragma unroll
       for (int g = 0; g < KPT / 4; g++) {
         const u32 first = idx_of(g * 4);
@@ -614,7 +682,7 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
         }
       }
     } else if constexpr (PIPE) {
-      const u32 *base = reinterpret_cast<const u32 *>(in) + kb;
+      const u32 *base = reinterpret_cast<const u32 *>(in_f) + kb;
       struct __attribute__((aligned(4))) WVec { u32 v[4]; };
       static_assert(!PIPE || SOA || KPT % 4 == 0, "four words per load");
 #pragma unroll
@@ -676,16 +744,21 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
   __syncthreads();
   u64 kb = 0; u32 nv = 0;
   u64 tile1 = 0, kb1 = 0; u32 nv1 = 0;                    // PIPE: the tile after the current one (its keys in flight / in raw[])
+  // BATCH: file and tile number inside it of the current tile, of tile1 and of `next` (the same in all lanes: scalar registers)
+  u32 fi = 0, lt = 0, fi1 = 0, lt1 = 0, nfi = 0, nlt = 0;
+  auto info_file = [&](int slot, u32 &f, u32 &l) __attribute__((always_inline)) {
+    if constexpr (BATCH) { f = __builtin_amdgcn_readfirstlane(s_tmp[40 + 2 * slot]); l = __builtin_amdgcn_readfirstlane(s_tmp[41 + 2 * slot]); }
+  };
   if constexpr (!PIPE) {
-    if (tile < total_tiles) { kb = s_info[0]; nv = (u32)s_info[1]; fetch(kb, nv); }
+    if (tile < total_tiles) { kb = s_info[0]; nv = (u32)s_info[1]; info_file(0, fi, lt); fetch_from(fi); fetch(kb, nv); }
   } else {
-    if (tile < total_tiles) { kb = s_info[0]; nv = (u32)s_info[1]; fetch_raw(kb, nv); assemble(); }
+    if (tile < total_tiles) { kb = s_info[0]; nv = (u32)s_info[1]; info_file(0, fi, lt); fetch_from(fi); fetch_raw(kb, nv); assemble(); }
     if (tid == 0) s_tmp[33] = stag ? (ex.stagger_groups + st_g) * st_w + st_r : atomicAdd(ticket, 1u);
     __syncthreads();
     tile1 = s_tmp[33];
     announce(tile1, 1);
     __syncthreads();
-    if (tile1 < total_tiles) { kb1 = s_info[2]; nv1 = (u32)s_info[3]; fetch_raw(kb1, nv1); }
+    if (tile1 < total_tiles) { kb1 = s_info[2]; nv1 = (u32)s_info[3]; info_file(1, fi1, lt1); fetch_from(fi1); fetch_raw(kb1, nv1); }
     __syncthreads();                                      // (s_tmp[33] and s_info[2..3] are written again at the top of the loop)
   }
   // the ticket of the tile after those (from now on taken in the shadow of the look-back, below)
@@ -699,6 +772,15 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
     asm volatile("" : "+v"(tid));                         // keeps the unrolled body's LDS addresses out of the loop preheader
     lane = tid & 63u; w = tid >> 6;
     const bool walker = tid < (u32)G;
+    // what belongs to the current tile's file (BATCH: from its descriptor; the row number of the look-back is the tile's number in the file)
+    typename GroupOut<K, NARROW>::type *out_c = out;
+    const u64 *gbase_c = gbase;
+    u64 *status_c = status;
+    u64 row = tile;
+    if constexpr (BATCH) {
+      out_c = reinterpret_cast<typename GroupOut<K, NARROW>::type *>(bfiles[fi].out);
+      gbase_c = bfiles[fi].gbase; status_c = bfiles[fi].status; row = lt;
+    }
     if (tid < (u32)R) s_hist[tid] = 0;
     __syncthreads();                                      // (A)
     const u64 next = s_tmp[34];
@@ -737,11 +819,11 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
       for (int j = 0; j < KPT / DPR; j++) asm volatile("" : "+v"(dgp[j]));
     }
 
-    u64 *mine = status + tile * (u64)G + tid;
+    u64 *mine = status_c + row * (u64)G + tid;
     u32 c0 = 0, c1 = 0;
     if (walker) {
       c0 = s_cnt[2 * tid]; c1 = s_cnt[2 * tid + 1];
-      const u32 fl = (tile == 0) ? 2u : 1u;
+      const u32 fl = (row == 0) ? 2u : 1u;
       status_store(mine, st_pack(fl, c0, fl, c1));
     }
 #pragma unroll
@@ -757,7 +839,7 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
       }
     }
     u64 nkb = 0; u32 nnv = 0;
-    if (next < total_tiles) { nkb = s_info[2]; nnv = (u32)s_info[3]; }
+    if (next < total_tiles) { nkb = s_info[2]; nnv = (u32)s_info[3]; info_file(1, nfi, nlt); fetch_from(nfi); }
     __syncthreads();                                      // (D) keys live in LDS only
     PK_STAMP(2);
 
@@ -766,14 +848,14 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
     // predecessors per round trip sees the frontier move ~2*WALK tiles per round trip.  (Measured: holding
     // the key fetch back, or issuing the status loads ahead of it, does not shorten the walk.)
     u32 p0 = 0, p1 = 0;
-    bool done = (tile == 0);
-    u64  wt = tile ? tile - 1 : 0;
+    bool done = (row == 0);
+    u64  wt = row ? row - 1 : 0;
     u32  spins = 0;
     u64  gv[WALK];
     auto issue = [&]() __attribute__((always_inline)) {
 #pragma unroll
       for (int i = 0; i < WALK; i++)
-        gv[i] = (wt >= (u64)i) ? status_load(status + (wt - i) * (u64)G + tid) : st_pack(2, 0, 2, 0);
+        gv[i] = (wt >= (u64)i) ? status_load(status_c + (wt - i) * (u64)G + tid) : st_pack(2, 0, 2, 0);
     };
     auto consume = [&]() __attribute__((always_inline)) {
       u32 used = 0;
@@ -814,9 +896,9 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
       if (tid == (u32)BLOCK - 1u) s_tmp[34] = tk_pre;
     } else {
       while (!done) { issue(); consume(); }
-      if (tile != 0) status_store(mine, st_pack(2, p0 + c0, 2, p1 + c1));
-      s_gbase[2 * tid]     = gbase[2 * tid]     + (u64)p0 - (u64)s_dbase[2 * tid];
-      s_gbase[2 * tid + 1] = gbase[2 * tid + 1] + (u64)p1 - (u64)s_dbase[2 * tid + 1];
+      if (row != 0) status_store(mine, st_pack(2, p0 + c0, 2, p1 + c1));
+      s_gbase[2 * tid]     = gbase_c[2 * tid]     + (u64)p0 - (u64)s_dbase[2 * tid];
+      s_gbase[2 * tid + 1] = gbase_c[2 * tid + 1] + (u64)p1 - (u64)s_dbase[2 * tid + 1];
       if constexpr (!PIPE) { if (next < total_tiles) fetch(nkb, nnv); }
     }
     __syncthreads();                                      // (E)
@@ -832,11 +914,11 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
     for (int j = 0; j < KPT; j++) {
       const u32 i = (u32)j * BLOCK + tid;
       if (i < nv) {
-        if constexpr (NARROW) out[s_gbase[s_dig[i]] + (u64)i] = s_words[i];
+        if constexpr (NARROW) out_c[s_gbase[s_dig[i]] + (u64)i] = s_words[i];
         else {
           const K   key = s_keys[i];
           const u32 d   = dig(key);
-          out[s_gbase[d] + (u64)i] = key;
+          out_c[s_gbase[d] + (u64)i] = key;
         }
       }
     }
@@ -844,18 +926,28 @@ void radix_group_kernel(const K *__restrict__ in, typename GroupOut<K, NARROW>::
     if constexpr (PIPE == 2) { if (next < total_tiles) fetch_raw(nkb, nnv); }
     __syncthreads();                                      // (F)
     PK_STAMP(5);
-    if constexpr (PIPE) { tile = tile1; kb = kb1; nv = nv1; tile1 = next; kb1 = nkb; nv1 = nnv; }
-    else                { tile = next; kb = nkb; nv = nnv; }
+    if constexpr (BATCH && HIST2) {
+      // the current tile is the workgroup's last of its file (or its last): the other digit's counts go to that file's histogram.
+      // Behind (F) every count of the tile is in; a thread clears the counters it has read, and the next counts come behind (A)..(D).
+      const bool leaves = PIPE ? (tile1 >= total_tiles || fi1 != fi) : (next >= total_tiles || nfi != fi);
+      if (leaves) {
+        u64 *gh = bfiles[fi].ghist2;
+        for (u32 i = tid0; i < (u32)RS_MAX_RADIX; i += BLOCK) { const u32 c = s_h2[i]; if (c) { atomicAdd(&gh[i], (u64)c); s_h2[i] = 0; } }
+      }
+    }
+    if constexpr (PIPE) { tile = tile1; kb = kb1; nv = nv1; tile1 = next; kb1 = nkb; nv1 = nnv; fi = fi1; lt = lt1; fi1 = nfi; lt1 = nlt; }
+    else                { tile = next; kb = nkb; nv = nnv; fi = nfi; lt = nlt; }
     if (DBG) ph[7]++;
   }
   if (DBG && tid0 == 0 && blockIdx.x < 64)
     for (int i = 0; i < 8; i++) dbg[blockIdx.x * 8 + i] = ph[i];
 #undef PK_STAMP
   (void)kb;
-  if constexpr (HIST2) {
+  if constexpr (HIST2 && !BATCH) {
     __syncthreads();
     for (u32 i = tid0; i < (u32)RS_MAX_RADIX; i += BLOCK) { const u32 c = s_h2[i]; if (c) atomicAdd(&ex.ghist2[i], (u64)c); }
   }
+  (void)fi; (void)lt; (void)fi1; (void)lt1; (void)nfi; (void)nlt; (void)af;
 }
 
 struct NarrowPrep { unsigned char bits_a[256]; unsigned char on[256]; };   // per bucket: bits of its first (high) digit, narrowed at all
@@ -958,6 +1050,9 @@ struct GroupPass {
   u64 *dbg;                                  // DBG: where the cycle sums go
   u64 tile_bound;                            // no tile index reaches this: the grid is min(tile_bound, resident workgroups)
   hipStream_t st;
+  // a batched instantiation (GroupInst::batch): the files' descriptors on the device and their number; shift, mask, ticket, d_error,
+  // ex, tile_bound and st are the launch's, everything else is in the descriptors
+  const GroupBatchFile *bfiles = nullptr; u32 nbf = 0;
 };
 static hipError_t launch_group_pass(const GroupInst &inst, const GroupPass &p);   // (the table, below the tile constants)
 
@@ -1104,6 +1199,66 @@ void narrow_mid_kernel(SortHeader *__restrict__ hdr, u64 n, u32 tile, u64 *__res
   if (r == 0) { region_start[RS_MAX_RADIX] = n; region_tiles[RS_MAX_RADIX] = tt; }
 }
 
+// The same for the files of a batch (mgc_device.h, GroupBatch): one workgroup per file -- p1 / p2: the descriptors of the first / second
+// pass's launch -- and the workgroup that finishes LAST turns the files' second-pass tile counts into their exclusive prefix
+// (GroupBatchFile::tile0 of p2; entry [nbf] the total): the number a batched second pass needs and only the device knows.
+__global__ __launch_bounds__(RS_MAX_RADIX)
+void narrow_mid_batch_kernel(const GroupBatchFile *__restrict__ p1, GroupBatchFile *__restrict__ p2, u32 nbf, u32 tile, u32 *__restrict__ arrived) {
+  __shared__ u64 s_tmp[RS_MAX_RADIX / 64 + 1];
+  __shared__ u32 s_tmp32[RS_MAX_RADIX / 64 + 1];
+  __shared__ u32 s_last;
+  const u32 r = threadIdx.x, f = blockIdx.x;
+  const u64 n = p2[f].n;
+  const u64 *ghist1 = p1[f].ghist2, *gbase0 = p1[f].gbase;
+  u64 *gbase1 = p2[f].gbase, *region_start = p2[f].region_start;
+  u32 *region_tiles = p2[f].region_tiles;
+  u64 total;
+  const u64 e = block_excl_scan<RS_MAX_RADIX, u64>(ghist1[r], s_tmp, &total);
+  gbase1[r] = e;
+  const u64 a = gbase0[r], b = (r + 1 < RS_MAX_RADIX) ? gbase0[r + 1] : n;
+  const u32 nt = (u32)((b - a + tile - 1) / tile);
+  u32 tt;
+  const u32 et = block_excl_scan<RS_MAX_RADIX, u32>(nt, s_tmp32, &tt);
+  region_start[r] = a;
+  region_tiles[r] = et;
+  if (r == 0) {
+    region_start[RS_MAX_RADIX] = n; region_tiles[RS_MAX_RADIX] = tt;
+    status_store(&p2[f].tiles, (u64)tt);
+    __threadfence();
+    s_last = (atomicAdd(arrived, 1u) == nbf - 1u) ? 1u : 0u;
+  }
+  __syncthreads();
+  if (s_last && r == 0) {
+    __threadfence();
+    u64 at = 0;
+    for (u32 i = 0; i < nbf; i++) { p2[i].tile0 = at; at += status_load(&p2[i].tiles); }
+    p2[nbf].tile0 = at;
+  }
+}
+
+// narrow_bounds_kernel for the files of a batch: the file in blockIdx.y, what is the file's from its second-pass descriptor
+__global__ void narrow_bounds_batch_kernel(const GroupBatchFile *__restrict__ p2, u32 b0, u64 ng, u32 granules) {
+  const GroupBatchFile &d = p2[blockIdx.y];
+  const u64 *status = d.status, *gbase1 = d.gbase;
+  const u32 *region_tiles = d.region_tiles;
+  u64 *starts = d.sub_starts;
+  const u64 n = d.n;
+  const u64 v = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v > ng) return;
+  if (v == ng) { starts[v] = n; return; }
+  u32 d1 = (u32)(v >> b0), d0 = (u32)v & ((1u << b0) - 1u);
+  if (d1 >= (u32)RS_MAX_RADIX) { starts[v] = n; return; }
+  if (d0 > (u32)RS_MAX_RADIX) d0 = RS_MAX_RADIX;
+  const u32 tiles_before = region_tiles[d0];
+  u64 before = 0;
+  if (tiles_before) {
+    if ((d1 >> 1) >= granules) { starts[v] = n; return; }   // (a digit the pass's instantiation does not have: nothing lies there)
+    const u64 g = status[(u64)(tiles_before - 1) * granules + (d1 >> 1)];
+    before = (u64)(((d1 & 1u) ? (u32)(g >> 32) : (u32)g) & 0x3FFFFFFFu);
+  }
+  starts[v] = gbase1[d1] + before;
+}
+
 // per-file scratch of the batched form: [status of pass A][status of pass B][region table]
 // Keys per tile of the first / second pass (launch_group_narrow).  The first pass exchanges 5 or 6 bytes per key (group_xb), so the LDS
 // has room for 24576 keys; the register file has it only where the next tile waits in the form it has in memory (PIPE: 30 registers
@@ -1139,62 +1294,70 @@ hipError_t launch_narrow_prepare(const uint64_t *d_fine, uint32_t nb, const unsi
 // ---- the launcher and the table ----
 // One instantiation: the dynamic-LDS limit raised once (the tile, plus the rank table where HPCD), the persistent grid of its own
 // WG_PER_CU -- 1 for every row of the table, asserted below -- and the launch.
-template <typename K, int RB, int KPT, bool DBG, bool NARROW, bool HIST2, bool SOA, int PIPE, int HPCD>
+template <typename K, int RB, int KPT, bool DBG, bool NARROW, bool HIST2, bool SOA, int PIPE, int HPCD, bool BATCH>
 static hipError_t group_launch_form(const GroupPass &p) {
   constexpr int BLOCK = GROUP_BLOCK;
   using SM = GroupSmem<K, RB, BLOCK, KPT, group_xb<K, RB, NARROW>()>;
   constexpr size_t LDS = SM::BYTES + (HPCD ? GROUP_RANK_TABLE_BYTES : 0);
-  static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<K, RB, BLOCK, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD>),
+  static_assert(!BATCH || (!DBG && !HPCD), "the batched forms");
+  if (BATCH && (!p.bfiles || !p.nbf)) return hipErrorInvalidValue;
+  static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void *>(&radix_group_kernel<K, RB, BLOCK, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD, BATCH>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
   (void)raised;
   const u64 resident = (u64)device_cu_count() * SM::WG_PER_CU;
-  hipLaunchKernelGGL((radix_group_kernel<K, RB, BLOCK, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD>), dim3((uint32_t)std::min(p.tile_bound, resident)),
+  // (a batched launch: the descriptors go where a per-file launch has its regions, their number where it has its keys' number)
+  hipLaunchKernelGGL((radix_group_kernel<K, RB, BLOCK, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD, BATCH>), dim3((uint32_t)std::min(p.tile_bound, resident)),
                      dim3(BLOCK), LDS, p.st, reinterpret_cast<const K *>(p.in), reinterpret_cast<typename GroupOut<K, NARROW>::type *>(p.out),
-                     p.n, p.shift, p.mask, p.gbase, p.status, p.ticket, p.d_error, p.tiles_plain, (const u64 *)p.region_start,
-                     (const u32 *)p.region_tiles, p.ex, p.dbg);
+                     BATCH ? (u64)p.nbf : p.n, p.shift, p.mask, p.gbase, p.status, p.ticket, p.d_error, p.tiles_plain,
+                     BATCH ? reinterpret_cast<const u64 *>(p.bfiles) : (const u64 *)p.region_start, (const u32 *)p.region_tiles, p.ex, p.dbg);
   return hipGetLastError();
 }
 
-// Every instantiation of radix_group_kernel the library holds: K, RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD (the rules that
+// Every instantiation of radix_group_kernel the library holds: K, RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD, BATCH (the rules that
 // pick among them: mgc_group_route.hpp; pinned by tests/test_group_route_host.py)
 #define MGC_GROUP_INSTS(X)                                                                                                     \
   /* a narrowed file's first pass: low digit first; high digit first off whole keys / the 5-byte layout / that a tile ahead */ \
-  X(u64, 9, 16, false, true, false, false, 0, 0)                                                                               \
-  X(u64, 9, 16, false, true, true, false, 0, 0)                                                                                \
-  X(u64, 9, 16, false, true, true, true, 0, 0)                                                                                 \
-  X(u64, 9, MGC_NARROW_KPT0, false, true, true, true, 2, 0)                                                                    \
-  X(u64, 8, MGC_NARROW_KPT0, false, true, true, true, 2, 0)                                                                    \
-  X(u64, 9, 16, true, true, true, false, 0, 0)                                                                                 \
-  X(u64, 9, 16, true, true, true, true, 0, 0)                                                                                  \
-  X(u64, 9, MGC_NARROW_KPT0, true, true, true, true, 2, 0)                                                                     \
+  X(u64, 9, 16, false, true, false, false, 0, 0, false)                                                                        \
+  X(u64, 9, 16, false, true, true, false, 0, 0, false)                                                                         \
+  X(u64, 9, 16, false, true, true, true, 0, 0, false)                                                                          \
+  X(u64, 9, MGC_NARROW_KPT0, false, true, true, true, 2, 0, false)                                                             \
+  X(u64, 8, MGC_NARROW_KPT0, false, true, true, true, 2, 0, false)                                                             \
+  X(u64, 9, 16, true, true, true, false, 0, 0, false)                                                                          \
+  X(u64, 9, 16, true, true, true, true, 0, 0, false)                                                                           \
+  X(u64, 9, MGC_NARROW_KPT0, true, true, true, true, 2, 0, false)                                                              \
+  /* the two pipelined 5-byte first passes and the two second passes over the files of a batch */                              \
+  X(u64, 9, MGC_NARROW_KPT0, false, true, true, true, 2, 0, true)                                                              \
+  X(u64, 8, MGC_NARROW_KPT0, false, true, true, true, 2, 0, true)                                                              \
+  X(u32, 9, 24, false, false, false, false, 0, 0, true)                                                                        \
+  X(u32, 8, 24, false, false, false, false, 0, 0, true)                                                                        \
   /* its second pass */                                                                                                        \
-  X(u32, 9, 24, false, false, false, false, 0, 0)                                                                              \
-  X(u32, 8, 24, false, false, false, false, 0, 0)                                                                              \
-  X(u32, 9, 24, true, false, false, false, 0, 0)                                                                               \
+  X(u32, 9, 24, false, false, false, false, 0, 0, false)                                                                       \
+  X(u32, 8, 24, false, false, false, false, 0, 0, false)                                                                       \
+  X(u32, 9, 24, true, false, false, false, 0, 0, false)                                                                        \
   /* whole keys: first (HIST2) and second pass, nine- and eight-bit digits (the nine-bit second passes: launch_radix_sort too) */ \
-  X(u64, 9, 16, false, false, true, false, 0, 0)                                                                               \
-  X(u64, 9, 16, false, false, false, false, 0, 0)                                                                              \
-  X(u64, 8, 16, false, false, true, false, 0, 0)                                                                               \
-  X(u64, 8, 16, false, false, false, false, 0, 0)                                                                              \
-  X(K128, 9, 8, false, false, true, false, 0, 0)                                                                               \
-  X(K128, 9, 8, false, false, false, false, 0, 0)                                                                              \
-  X(K128, 8, 8, false, false, true, false, 0, 0)                                                                               \
-  X(K128, 8, 8, false, false, false, false, 0, 0)                                                                              \
-  X(K96, 9, 12, false, false, true, false, 0, 0)                                                                               \
-  X(K96, 9, 12, false, false, false, false, 0, 0)                                                                              \
-  X(K96, 8, 12, false, false, true, false, 0, 0)                                                                               \
-  X(K96, 8, 12, false, false, false, false, 0, 0)                                                                              \
+  X(u64, 9, 16, false, false, true, false, 0, 0, false)                                                                        \
+  X(u64, 9, 16, false, false, false, false, 0, 0, false)                                                                       \
+  X(u64, 8, 16, false, false, true, false, 0, 0, false)                                                                        \
+  X(u64, 8, 16, false, false, false, false, 0, 0, false)                                                                       \
+  X(K128, 9, 8, false, false, true, false, 0, 0, false)                                                                        \
+  X(K128, 9, 8, false, false, false, false, 0, 0, false)                                                                       \
+  X(K128, 8, 8, false, false, true, false, 0, 0, false)                                                                        \
+  X(K128, 8, 8, false, false, false, false, 0, 0, false)                                                                       \
+  X(K96, 9, 12, false, false, true, false, 0, 0, false)                                                                        \
+  X(K96, 9, 12, false, false, false, false, 0, 0, false)                                                                       \
+  X(K96, 8, 12, false, false, true, false, 0, 0, false)                                                                        \
+  X(K96, 8, 12, false, false, false, false, 0, 0, false)                                                                       \
   /* `compress`: both digits dense ranks (first, second pass); only the high one (first pass) */                              \
-  X(u64, 9, 16, false, false, true, false, 0, 1)                                                                               \
-  X(u64, 9, 16, false, false, false, false, 0, 1)                                                                              \
-  X(u64, 9, 16, false, false, true, false, 0, 2)                                                                               \
-  X(K128, 9, 8, false, false, true, false, 0, 1)                                                                               \
-  X(K128, 9, 8, false, false, false, false, 0, 1)                                                                              \
-  X(K128, 9, 8, false, false, true, false, 0, 2)
+  X(u64, 9, 16, false, false, true, false, 0, 1, false)                                                                        \
+  X(u64, 9, 16, false, false, false, false, 0, 1, false)                                                                       \
+  X(u64, 9, 16, false, false, true, false, 0, 2, false)                                                                        \
+  X(K128, 9, 8, false, false, true, false, 0, 1, false)                                                                        \
+  X(K128, 9, 8, false, false, false, false, 0, 1, false)                                                                       \
+  X(K128, 9, 8, false, false, true, false, 0, 2, false)
 
 // every row: one workgroup per CU (so "the instantiation's own WG_PER_CU" is the grid every launch had), and the LDS bytes the
 // picking functions reckon with (the rank table only where it fits) are the kernel's
-#define MGC_GROUP_ROW_OK(K, RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD)                                                      \
+#define MGC_GROUP_ROW_OK(K, RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD, BATCH)                                                      \
   static_assert(GroupSmem<K, RB, GROUP_BLOCK, KPT, group_xb<K, RB, NARROW>()>::WG_PER_CU == 1, "one workgroup per CU");        \
   static_assert(GroupSmem<K, RB, GROUP_BLOCK, KPT, group_xb<K, RB, NARROW>()>::BYTES + (HPCD ? GROUP_RANK_TABLE_BYTES : 0) ==  \
                 group_lds_bytes(GroupInst{group_key_of<K>(), RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD}), "group_lds_bytes"); \
@@ -1205,9 +1368,9 @@ MGC_GROUP_INSTS(MGC_GROUP_ROW_OK)
 
 // an instantiation that is not in the table is an error, never a neighbouring kernel
 static hipError_t launch_group_pass(const GroupInst &inst, const GroupPass &p) {
-#define MGC_GROUP_ROW(K, RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD)                                                         \
-  if (inst == GroupInst{group_key_of<K>(), RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD})                                      \
-    return group_launch_form<K, RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD>(p);
+#define MGC_GROUP_ROW(K, RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD, BATCH)                                                         \
+  if (inst == GroupInst{group_key_of<K>(), RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD, BATCH})                               \
+    return group_launch_form<K, RB, KPT, DBG, NARROW, HIST2, SOA, PIPE, HPCD, BATCH>(p);
   MGC_GROUP_INSTS(MGC_GROUP_ROW)
 #undef MGC_GROUP_ROW
   return hipErrorInvalidValue;
@@ -1313,6 +1476,66 @@ hipError_t launch_group_narrow(GroupFile &f) {
     }
   }
   return hipSuccess;
+}
+
+// ---- the two passes of a BATCH of narrowed files: one launch per pass and helper step (mgc_device.h, GroupBatch) ----
+// Both descriptor tables ([nfiles + 1] entries each: first pass, second pass) are put together here and go to the device in one
+// copy; the second pass's tile numbers are filled in on the device (narrow_mid_batch_kernel).
+size_t group_batch_table_bytes(uint32_t nfiles) { return 2 * ((size_t)nfiles + 1) * sizeof(GroupBatchFile); }
+
+hipError_t launch_group_narrow_batch(GroupBatch &b) {
+  if (!b.files || !b.nfiles || !b.d_table || !b.h_table || !b.d_ctl || !b.files[0].plan) return hipErrorInvalidValue;
+  const SortPlan &plan = *b.files[0].plan;
+  const u32 low = plan.pass_shift[0], bB = plan.pass_bits[0], bA = plan.pass_bits[1], shA = low + bB;   // high digit (A) first
+  const u32 hi_mask = b.files[0].soa_hi_mask;
+  GroupInst i0, i1;
+  if (!group_pick_narrow_batch(bA, bB, &i0, &i1)) return hipErrorInvalidValue;
+  const uint64_t tile0 = group_tile(i0), tile1 = group_tile(i1);
+  constexpr size_t ROW = RS_MAX_RADIX / 2;
+  const size_t bytes = group_batch_table_bytes(b.nfiles);
+  GroupBatchFile *h1 = reinterpret_cast<GroupBatchFile *>(b.h_table), *h2 = h1 + b.nfiles + 1;
+  const GroupBatchFile *d1 = reinterpret_cast<const GroupBatchFile *>(b.d_table);
+  GroupBatchFile *d2 = reinterpret_cast<GroupBatchFile *>(b.d_table) + b.nfiles + 1;
+  memset(h1, 0, bytes);
+  uint64_t at = 0, bound1 = 0;
+  for (uint32_t i = 0; i < b.nfiles; i++) {
+    GroupFile &f = b.files[i];
+    if (f.layout != GroupKeys::SOA5 || !hi_mask || f.soa_hi_mask != hi_mask || !f.prepared || !f.scratch || !f.keys || !f.alt || !f.d_sub_starts ||
+        !group_batch_form(true, true, f.pipe, f.dbg, f.stagger) || !f.plan || !sort_plan_narrows(*f.plan, f.n, 1) ||
+        f.plan->pass_shift[0] != low || f.plan->pass_bits[0] != bB || f.plan->pass_bits[1] != bA)
+      return hipErrorInvalidValue;
+    const uint64_t tiles0 = (f.n + tile0 - 1) / tile0, tiles1_max = (f.n + tile1 - 1) / tile1 + RS_MAX_RADIX + 1;
+    SortHeader *hdr = reinterpret_cast<SortHeader *>(f.prepared);          // (the scratch is laid out as launch_group_narrow lays it out)
+    u64 *status_a = reinterpret_cast<u64 *>(f.scratch), *status_b = status_a + (size_t)tiles0 * ROW;
+    u64 *region_start = status_b + (size_t)tiles1_max * ROW;
+    u32 *region_tiles = reinterpret_cast<u32 *>(region_start + RS_MAX_RADIX + 1);
+    h1[i] = GroupBatchFile{(u64)at, (u64)tiles0, (u64)f.n, f.keys, f.alt, &hdr->gbase[0][0], status_a, &hdr->ghist[1][0], nullptr, nullptr, nullptr};
+    h2[i] = GroupBatchFile{0, 0, (u64)f.n, f.alt, f.keys, &hdr->gbase[1][0], status_b, nullptr, region_start, region_tiles,
+                           reinterpret_cast<u64 *>(f.d_sub_starts)};
+    at += tiles0; bound1 += tiles1_max;
+    f.tr_a = bA; f.tr_b = bB;
+  }
+  h1[b.nfiles].tile0 = at;
+  if (bound1 >= (1ull << 32)) return hipErrorInvalidValue;                 // tickets are 32-bit words
+  MGC_CHECK(hipMemcpyAsync(b.d_table, b.h_table, bytes, hipMemcpyHostToDevice, b.st));
+  if (b.pass_events) MGC_CHECK(hipEventRecord(b.pass_events[0], b.st));
+  GroupPass p0{nullptr, nullptr, 0, shA, (1u << bA) - 1u, nullptr, nullptr, b.d_ctl, b.d_error, (u64)at, nullptr, nullptr,
+               GroupExtra{bA, low, (1u << bB) - 1u, nullptr, hi_mask}, nullptr, (u64)at, b.st};
+  p0.bfiles = d1; p0.nbf = b.nfiles;
+  MGC_CHECK(launch_group_pass(i0, p0));
+  if (b.pass_events) MGC_CHECK(hipEventRecord(b.pass_events[1], b.st));
+  hipLaunchKernelGGL(narrow_mid_batch_kernel, dim3(b.nfiles), dim3(RS_MAX_RADIX), 0, b.st, d1, d2, (u32)b.nfiles, (u32)tile1, b.d_ctl + 2);
+  MGC_CHECK(hipGetLastError());
+  if (b.pass_events) MGC_CHECK(hipEventRecord(b.pass_events[2], b.st));
+  GroupPass p1{nullptr, nullptr, 0, low, (1u << bB) - 1u, nullptr, nullptr, b.d_ctl + 1, b.d_error, 0, nullptr, nullptr,
+               GroupExtra{0u, 0u, 0u, nullptr}, nullptr, (u64)bound1, b.st};
+  p1.bfiles = d2; p1.nbf = b.nfiles;
+  MGC_CHECK(launch_group_pass(i1, p1));
+  if (b.pass_events) MGC_CHECK(hipEventRecord(b.pass_events[3], b.st));
+  const u64 ng = (u64)1 << (bA + bB);
+  hipLaunchKernelGGL(narrow_bounds_batch_kernel, dim3((uint32_t)((ng + 1 + 255) / 256), b.nfiles), dim3(256), 0, b.st,
+                     (const GroupBatchFile *)d2, bA, ng, group_granules(i1));
+  return hipGetLastError();
 }
 
 // ---- the same two passes for WHOLE keys (mgc_device.h, launch_group_wide) ----
