@@ -20,6 +20,7 @@ HEADERS = ["mgc_device.h", "mgc_common.hpp", "mgc_compact.hpp", "mgc_bases.hpp",
            os.path.join("..", "..", "include", "meryl_gpu_count.h"),
            os.path.join("..", "..", "include", "meryl_db.h"), os.path.join("..", "..", "include", "meryl_seq.h"),
            os.path.join("..", "..", "include", "meryl_lookup.h"), os.path.join("..", "..", "include", "meryl_import.h"),
+           os.path.join("..", "..", "include", "meryl_import_labelled.h"),
            os.path.join("..", "..", "include", "meryl_analyze.h"), os.path.join("..", "..", "include", "meryl_positions.h")]
 OBJDIR = os.path.join(HERE, "build")
 # -no-hip-rt: the library carries no DT_NEEDED on a particular libamdhip64; it binds to the

@@ -1,4 +1,4 @@
-"""ctypes binding of include/meryl_gpu_count.h (and meryl_db.h, meryl_lookup.h, meryl_positions.h, meryl_seq.h, meryl_import.h, meryl_analyze.h).
+"""ctypes binding of include/meryl_gpu_count.h (and meryl_db.h, meryl_lookup.h, meryl_positions.h, meryl_seq.h, meryl_import.h, meryl_import_labelled.h, meryl_analyze.h).
 
 Loads meryl_amd/libmeryl_gpu_count.so and fails loudly when it is missing or
 an expected symbol is absent -- there is no Python/CPU fallback for any compute
@@ -53,6 +53,10 @@ SYMBOLS = (
     "mgc_dev_import_parse_state_bytes", "mgc_dev_import_parse_workspace_bytes", "mgc_dev_import_parse_begin", "mgc_dev_import_parse_count",
     "mgc_dev_import_parse", "mgc_dev_sort_pairs_workspace_bytes", "mgc_dev_sort_pairs", "mgc_dev_reduce_pairs_workspace_bytes",
     "mgc_dev_reduce_pairs_count", "mgc_dev_reduce_pairs_emit", "mgc_import_file", "mgc_import_text", "mgc_import_error",
+    # include/meryl_import_labelled.h
+    "mgc_dev_import2_parse_state_bytes", "mgc_dev_import2_parse_workspace_bytes", "mgc_dev_import2_parse_begin", "mgc_dev_import2_parse_count",
+    "mgc_dev_import2_parse", "mgc_dev_sort_triples_workspace_bytes", "mgc_dev_sort_triples", "mgc_dev_reduce_triples_workspace_bytes",
+    "mgc_dev_reduce_triples_count", "mgc_dev_reduce_triples_emit", "mgc_import_labelled_file", "mgc_import_labelled_text",
     # include/meryl_analyze.h
     "mgc_dev_analyze_scores", "mgc_analyze_open", "mgc_analyze_close", "mgc_analyze_add_device", "mgc_analyze_add_database",
     "mgc_analyze_result_rows", "mgc_analyze_result", "mgc_analyze_write", "mgc_analyze_get_info", "mgc_analyze_error",
@@ -585,6 +589,18 @@ def lib():
     sig("mgc_import_file", i32, ctypes.c_char_p, u32, i32, ctypes.c_char_p, i32, i32, P(ImportInfo))
     sig("mgc_import_text", i32, ctypes.c_char_p, u64, u32, i32, ctypes.c_char_p, i32, i32, P(ImportInfo))
     sig("mgc_import_error", ctypes.c_char_p)
+    sig("mgc_dev_import2_parse_state_bytes", sz)
+    sig("mgc_dev_import2_parse_workspace_bytes", sz, u64)
+    sig("mgc_dev_import2_parse_begin", i32, vp, vp)
+    sig("mgc_dev_import2_parse_count", i32, vp, u64, u32, u32, vp, vp, sz, P(ImportParseResult), P(u64), vp)
+    sig("mgc_dev_import2_parse", i32, vp, u64, u32, i32, u32, vp, vp, sz, vp, vp, vp, vp)
+    sig("mgc_dev_sort_triples_workspace_bytes", sz, u64)
+    sig("mgc_dev_sort_triples", i32, vp, vp, vp, vp, vp, vp, u64, u32, u32, u32, vp, sz, P(i32), vp)
+    sig("mgc_dev_reduce_triples_workspace_bytes", sz, u64)
+    sig("mgc_dev_reduce_triples_count", i32, vp, vp, vp, u64, u32, vp, sz, P(u64), vp)
+    sig("mgc_dev_reduce_triples_emit", i32, vp, vp, vp, u64, u32, u32, vp, sz, vp, vp, vp, vp)
+    sig("mgc_import_labelled_file", i32, ctypes.c_char_p, u32, i32, u32, ctypes.c_char_p, i32, i32, P(ImportInfo))
+    sig("mgc_import_labelled_text", i32, ctypes.c_char_p, u64, u32, i32, u32, ctypes.c_char_p, i32, i32, P(ImportInfo))
     sig("mgc_dev_analyze_scores", i32, vp, u64, u32, i32, vp, vp, vp)
     sig("mgc_analyze_open", i32, u32, i32, i32, P(vp))
     sig("mgc_analyze_close", None, vp)

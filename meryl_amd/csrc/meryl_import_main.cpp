@@ -6,7 +6,11 @@
 // parsed, sorted and summed on the device (include/meryl_import.h); nothing here touches the device before the command
 // line is accepted.  Where the reference's behaviour is undefined the input is refused with its line number (see the header).
 // -multiset is not part of this build.
-#include "../../include/meryl_import.h"
+//
+// -labelwidth <lw> (1..64) selects the meryl 2 tool (src/meryl2-import/meryl-import.C:62-67, :199-233: `kmer value label` lines,
+// `value=` / `label=` lines; include/meryl_import_labelled.h); absent or 0 the tool is the meryl 1 one.  -valuewidth is
+// accepted as 0 only: the writer's default value encoding is the only one this build has.
+#include "../../include/meryl_import_labelled.h"
 
 #include <cinttypes>
 #include <cstdio>
@@ -40,6 +44,12 @@ void usage(const char *prog, const std::vector<std::string> &err) {
   fprintf(stderr, "\n");
   fprintf(stderr, "  -maxvalue <value>     (accepted, a hint only)\n");
   fprintf(stderr, "\n");
+  fprintf(stderr, "  -labelwidth <lw>      Store an <lw>-bit label (%d..%d) with each kmer, and read the meryl 2 dialect:\n", MGC_IMPORT_MIN_LABEL_WIDTH, MGC_IMPORT_MAX_LABEL_WIDTH);
+  fprintf(stderr, "                        'kmer [value [label]]' lines; 'value=<n>' / 'label=<n>' lines set the persistent\n");
+  fprintf(stderr, "                        value / label ('#' lines are not read); numbers are 123, 123d, 7bh, 173o or\n");
+  fprintf(stderr, "                        1111011b; the labels of duplicate kmers add (modulo 2^lw).  0: no labels (default).\n");
+  fprintf(stderr, "  -valuewidth <vw>      Only 0 (the default value encoding) is part of this build.\n");
+  fprintf(stderr, "\n");
   fprintf(stderr, "  -forward              By default, the canonical kmer is loaded into the database.  These\n");
   fprintf(stderr, "  -reverse              options force either the forward or reverse-complement kmer to be\n");
   fprintf(stderr, "                        loaded instead.  These options are mutually exclusive.\n");
@@ -58,7 +68,7 @@ bool ends_with(const std::string &n, const char *suf) {
 
 int main(int argc, char **argv) {
   const char *input = nullptr, *output = nullptr;
-  uint32_t k = 0;
+  uint32_t k = 0, label_width = 0;
   bool have_k = false, multiset = false;
   int mode = MGC_MODE_CANONICAL, threads = 0;
   std::vector<std::string> err;
@@ -74,6 +84,19 @@ int main(int argc, char **argv) {
     else if (w == "-output") output = value();
     else if (w == "-k") { if (const char *v = value()) { k = (uint32_t)strtoul(v, nullptr, 10); have_k = true; } }
     else if (w == "-maxvalue" || w == "-memory") (void)value();
+    else if (w == "-labelwidth" || w == "-valuewidth") {
+      if (const char *v = value()) {
+        char *end = nullptr;
+        const unsigned long x = strtoul(v, &end, 10);
+        const bool number = *v >= '0' && *v <= '9' && end && *end == 0;
+        if (w == "-labelwidth") {
+          if (!number || x > MGC_IMPORT_MAX_LABEL_WIDTH) err.push_back("Label width (-labelwidth) '" + std::string(v) + "' is not a number in 0..64.\n");
+          else label_width = (uint32_t)x;
+        } else if (!number || x != 0) {
+          err.push_back("Value width (-valuewidth) '" + std::string(v) + "': only 0, the default value encoding, is part of this build.\n");
+        }
+      }
+    }
     else if (w == "-threads") { if (const char *v = value()) threads = atoi(v); }
     else if (w == "-multiset") multiset = true;
     else if (w == "-forward") mode = MGC_MODE_FORWARD;
@@ -101,12 +124,14 @@ int main(int argc, char **argv) {
   }
 
   mgc_import_info info;
-  const int rc = mgc_import_file(input, k, mode, output, -1, threads, &info);
+  const int rc = label_width ? mgc_import_labelled_file(input, k, mode, label_width, output, -1, threads, &info)
+                             : mgc_import_file(input, k, mode, output, -1, threads, &info);
   if (rc != MGC_OK) {
     fprintf(stderr, "ERROR: %s\n", mgc_import_error());
     return 1;
   }
-  fprintf(stderr, "Found %" PRIu64 " kmers in the input.\n", info.n_records);
+  if (label_width) fprintf(stderr, "Added %" PRIu64 " kmers; incorrectly added 0 kmers.\n", info.n_records);   // meryl2-import/meryl-import.C:280
+  else fprintf(stderr, "Found %" PRIu64 " kmers in the input.\n", info.n_records);
   fprintf(stderr, "\n");
   fprintf(stderr, "Bye.\n");
   return 0;

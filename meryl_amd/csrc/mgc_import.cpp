@@ -5,7 +5,11 @@
 // device in batches cut at a line end; every batch is parsed, sorted and reduced there (mgc_import.hip); one batch is handed
 // straight to the database stream, several are parked as runs and merged once (include/meryl_db.h).  Nothing is created at
 // the output path before the whole input has been accepted.
-#include "../../include/meryl_import.h"
+//
+// The meryl 2 dialect with labels (include/meryl_import_labelled.h, the second half of this file) shares the reader and the
+// argument checks; its driver keeps every batch's triples on the device and sorts and reduces once, since the run store
+// carries no labels.
+#include "../../include/meryl_import_labelled.h"
 #include "../../include/meryl_db.h"
 #include "mgc_import_dev.hpp"
 #include "mgc_runs.hpp"
@@ -30,10 +34,25 @@ int hip_rc(hipError_t e, const char *what) {
   set_err(nullptr, "%s: %s", what, hipGetErrorString(e));
   return (e == hipErrorOutOfMemory) ? MGC_ENOMEM : MGC_EHIP;
 }
-bool k_ok(uint32_t k) {
+bool k_ok(uint32_t k, int w_prefix = MGC_IMPORT_W_PREFIX) {
   if (k >= MGC_IMPORT_MIN_K && k <= MGC_IMPORT_MAX_K) return true;
-  set_err(nullptr, "meryl-import: k=%u out of range (%d..%d: a 10-bit prefix must leave a suffix)", k, MGC_IMPORT_MIN_K, MGC_IMPORT_MAX_K);
+  set_err(nullptr, "meryl-import: k=%u out of range (%d..%d: a %d-bit prefix must leave a suffix)", k, MGC_IMPORT_MIN_K, MGC_IMPORT_MAX_K, w_prefix);
   return false;
+}
+bool label_width_ok(uint32_t lw) {
+  if (lw >= MGC_IMPORT_MIN_LABEL_WIDTH && lw <= MGC_IMPORT_MAX_LABEL_WIDTH) return true;
+  set_err(nullptr, "meryl-import: label width %u out of range (%d..%d)", lw, MGC_IMPORT_MIN_LABEL_WIDTH, MGC_IMPORT_MAX_LABEL_WIDTH);
+  return false;
+}
+const char *bad_text2(uint32_t kind) {                      // the meryl 2 dialect
+  switch (kind) {
+    case MGC_IMPORT_BAD_BASE:   return "the k-mer holds a byte that is not one of ACGTacgt";
+    case MGC_IMPORT_BAD_SHORT:  return "the k-mer is shorter than k";
+    case MGC_IMPORT_BAD_VALUE:  return "the value is not a number (123, 123d, 7bh, 173o, 1111011b) of at most 4294967295";
+    case MGC_IMPORT_BAD_LABEL:  return "the label is not a number (123, 123d, 7bh, 173o, 1111011b) that fits the label width";
+    case MGC_IMPORT_BAD_ASSIGN: return "the number of a 'value=' / 'label=' line is missing, malformed or out of range";
+  }
+  return "malformed";
 }
 const char *bad_text(uint32_t kind) {
   switch (kind) {
@@ -421,4 +440,348 @@ extern "C" int mgc_import_text(const char *text, uint64_t n_text, uint32_t k, in
   if (!import_args_ok(k, mode, output)) return MGC_EINVAL;
   MemSource src(text, n_text);
   return import_from(&src, k, mode, output, device, host_threads, info);
+}
+
+// ================================================================================================
+//  the meryl 2 dialect with labels (include/meryl_import_labelled.h): device steps
+// ================================================================================================
+extern "C" size_t mgc_dev_import2_parse_state_bytes(void) { return sizeof(mgc::Import2State); }
+extern "C" size_t mgc_dev_import2_parse_workspace_bytes(uint64_t n_text) { return mgc::import2_parse_workspace_bytes(n_text); }
+
+extern "C" int mgc_dev_import2_parse_begin(void *d_state, void *stream) {
+  if (!d_state) return MGC_EINVAL;
+  return hip_rc(mgc::launch_import2_begin(reinterpret_cast<mgc::Import2State *>(d_state), (hipStream_t)stream), "import2_parse_begin");
+}
+
+extern "C" int mgc_dev_import2_parse_count(const uint8_t *d_text, uint64_t n_text, uint32_t k, uint32_t label_width, void *d_state,
+                                           void *d_ws, size_t ws_bytes, mgc_import_parse_result *res, uint64_t *persistent_label,
+                                           void *stream) {
+  if (!k_ok(k, MGC_IMPORT2_W_PREFIX) || !label_width_ok(label_width)) return MGC_EINVAL;
+  if (!d_state || !d_ws || !res || (n_text && !d_text) || n_text > 0xFFFFFFFFull || ws_bytes < mgc::import2_parse_workspace_bytes(n_text)) {
+    set_err(nullptr, "mgc_dev_import2_parse_count: bad arguments (a chunk holds fewer than 2^32 bytes)");
+    return MGC_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  mgc::Import2State *ds = reinterpret_cast<mgc::Import2State *>(d_state);
+  hipError_t e = hipSuccess;
+  if (n_text) e = mgc::launch_import2_parse_count(d_text, n_text, k, label_width, ds, d_ws, st);
+  if (e != hipSuccess) return hip_rc(e, "import2_parse_count");
+  mgc::Import2State h;
+  e = hipMemcpyAsync(&h, ds, sizeof(h), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return hip_rc(e, "import2_parse_count sync");
+  res->bad_line = h.first_bad == ~0ull ? 0 : h.first_bad >> 3;
+  res->bad_kind = h.first_bad == ~0ull ? 0u : (uint32_t)(h.first_bad & 7);
+  if (n_text == 0) {                                        // no launch: the state as it stands, an empty chunk
+    res->n_lines = 0; res->n_records = 0; res->persistent_value = h.persistent_value;
+    if (persistent_label) *persistent_label = h.persistent_label;
+    return MGC_OK;
+  }
+  res->n_lines = h.chunk_lines;
+  res->n_records = h.chunk_records;
+  res->persistent_value = h.chunk_vhas ? h.chunk_val : h.persistent_value;
+  if (persistent_label) *persistent_label = h.chunk_lhas ? h.chunk_lab : h.persistent_label;
+  return MGC_OK;
+}
+
+extern "C" int mgc_dev_import2_parse(const uint8_t *d_text, uint64_t n_text, uint32_t k, int mode, uint32_t label_width, void *d_state,
+                                     void *d_ws, size_t ws_bytes, void *d_keys, uint32_t *d_values, uint64_t *d_labels, void *stream) {
+  if (!k_ok(k, MGC_IMPORT2_W_PREFIX) || !label_width_ok(label_width)) return MGC_EINVAL;
+  if (mode < 0 || mode > 2 || !d_state || !d_ws || (n_text && !d_text) || n_text > 0xFFFFFFFFull ||
+      ws_bytes < mgc::import2_parse_workspace_bytes(n_text)) {
+    set_err(nullptr, "mgc_dev_import2_parse: bad arguments");
+    return MGC_EINVAL;
+  }
+  if (n_text == 0) return MGC_OK;                           // an empty chunk: nothing to write, nothing to move the state past
+  return hip_rc(mgc::launch_import2_parse_emit(d_text, n_text, k, mode, label_width, reinterpret_cast<mgc::Import2State *>(d_state), d_ws,
+                                               d_keys, d_values, d_labels, (hipStream_t)stream), "import2_parse");
+}
+
+extern "C" size_t mgc_dev_sort_triples_workspace_bytes(uint64_t n) { return mgc::sort_triples_workspace_bytes(n); }
+
+extern "C" int mgc_dev_sort_triples(void *d_keys, uint32_t *d_values, uint64_t *d_labels, void *d_alt_keys, uint32_t *d_alt_values,
+                                    uint64_t *d_alt_labels, uint64_t n, uint32_t key_words, uint32_t begin_bit, uint32_t end_bit,
+                                    void *d_ws, size_t ws_bytes, int *result_in_alt, void *stream) {
+  if (!result_in_alt || begin_bit > end_bit || (key_words != 1 && key_words != 2) || end_bit > 64 * key_words) {
+    set_err(nullptr, "mgc_dev_sort_triples: bad key words or bit range");
+    return MGC_EINVAL;
+  }
+  *result_in_alt = 0;
+  if (n == 0 || begin_bit == end_bit) return MGC_OK;
+  if (n > MGC_SORT_TRIPLES_MAX_N) {
+    set_err(nullptr, "mgc_dev_sort_triples: %llu triples, one sort takes at most %llu (32-bit record numbers)", (unsigned long long)n,
+            (unsigned long long)MGC_SORT_TRIPLES_MAX_N);
+    return MGC_EINVAL;
+  }
+  if (!d_keys || !d_values || !d_labels || !d_alt_keys || !d_alt_values || !d_alt_labels || !d_ws ||
+      ws_bytes < mgc::sort_triples_workspace_bytes(n)) {
+    set_err(nullptr, "mgc_dev_sort_triples: NULL buffer or workspace too small");
+    return MGC_EINVAL;
+  }
+  return hip_rc(mgc::launch_sort_triples(d_keys, d_values, d_labels, d_alt_keys, d_alt_values, d_alt_labels, n, key_words, begin_bit, end_bit,
+                                         d_ws, result_in_alt, (hipStream_t)stream), "sort_triples");
+}
+
+extern "C" size_t mgc_dev_reduce_triples_workspace_bytes(uint64_t n) { return mgc::reduce_triples_workspace_bytes(n); }
+
+extern "C" int mgc_dev_reduce_triples_count(const void *d_keys, const uint32_t *d_values, const uint64_t *d_labels, uint64_t n,
+                                            uint32_t key_words, void *d_ws, size_t ws_bytes, uint64_t *n_distinct, void *stream) {
+  if (!n_distinct || (key_words != 1 && key_words != 2)) { set_err(nullptr, "mgc_dev_reduce_triples_count: bad arguments"); return MGC_EINVAL; }
+  *n_distinct = 0;
+  if (n == 0) return MGC_OK;
+  if (!d_ws || ws_bytes < mgc::reduce_triples_workspace_bytes(n) || !d_keys || !d_values || !d_labels) {
+    set_err(nullptr, "mgc_dev_reduce_triples_count: NULL buffer or workspace too small");
+    return MGC_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = mgc::launch_reduce_triples_count(d_keys, d_values, d_labels, n, key_words, d_ws, st);
+  if (e != hipSuccess) return hip_rc(e, "reduce_triples_count");
+  e = hipMemcpyAsync(n_distinct, d_ws, sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return hip_rc(e, "reduce_triples_count sync");
+}
+
+extern "C" int mgc_dev_reduce_triples_emit(const void *d_keys, const uint32_t *d_values, const uint64_t *d_labels, uint64_t n,
+                                           uint32_t key_words, uint32_t label_width, void *d_ws, size_t ws_bytes, void *d_out_keys,
+                                           uint32_t *d_out_values, uint64_t *d_out_labels, void *stream) {
+  if (!label_width_ok(label_width)) return MGC_EINVAL;
+  if (key_words != 1 && key_words != 2) { set_err(nullptr, "mgc_dev_reduce_triples_emit: bad arguments"); return MGC_EINVAL; }
+  if (n == 0) return MGC_OK;
+  if (!d_ws || ws_bytes < mgc::reduce_triples_workspace_bytes(n) || !d_keys || !d_values || !d_labels || !d_out_keys || !d_out_values ||
+      !d_out_labels) {
+    set_err(nullptr, "mgc_dev_reduce_triples_emit: NULL buffer or workspace too small");
+    return MGC_EINVAL;
+  }
+  return hip_rc(mgc::launch_reduce_triples_emit(d_keys, d_values, d_labels, n, key_words, label_width, d_ws, d_out_keys, d_out_values,
+                                                d_out_labels, (hipStream_t)stream), "reduce_triples_emit");
+}
+
+// ================================================================================================
+//  the meryl 2 dialect with labels: text -> database
+// ================================================================================================
+namespace {
+
+struct LabelledImporter {
+  typedef mgc::DBuf DBuf;
+  uint32_t k, kw, label_width;
+  int mode, device, host_threads;
+  hipStream_t st = nullptr;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  DBuf d_text, d_state, d_pws, d_k[2], d_v[2], d_l[2], d_sws, d_rws;
+  uint64_t n_total = 0, cap = 0;                           // triples held in d_k[0] / d_v[0] / d_l[0], and how many fit
+  mgc_import_info info;
+
+  ~LabelledImporter() {
+    (void)hipSetDevice(device);
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    if (st) (void)hipStreamDestroy(st);
+  }
+
+#define IM_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) {                                        \
+    set_err(nullptr, "%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e__));                      \
+    return (e__ == hipErrorOutOfMemory) ? MGC_ENOMEM : MGC_EHIP; } } while (0)
+
+  size_t triple_bytes() const { return sizeof(uint64_t) * kw + sizeof(uint32_t) + sizeof(uint64_t); }
+
+  // `need` more bytes of device memory, or the refusal that names them
+  int room_for(uint64_t need, const char *what) {
+    size_t free_b = 0, total_b = 0;
+    IM_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (need <= free_b) return MGC_OK;
+    set_err(nullptr, "meryl-import: %llu triples do not fit the device: %s needs %llu bytes, %llu are free", (unsigned long long)n_total, what,
+            (unsigned long long)need, (unsigned long long)free_b);
+    return MGC_ENOMEM;
+  }
+
+  // room for `want` triples in the [0] arrays, what they hold kept
+  int reserve(uint64_t want) {
+    if (want <= cap) return MGC_OK;
+    const uint64_t ncap = std::max<uint64_t>(want, 2 * cap);
+    const int rc = room_for(ncap * triple_bytes() + 3 * 256, "appending a batch");
+    if (rc != MGC_OK) return rc;
+    DBuf nk, nv, nl;
+    const size_t kb = sizeof(uint64_t) * kw;
+    IM_TRY(nk.ensure(kb * ncap)); IM_TRY(nv.ensure(sizeof(uint32_t) * ncap)); IM_TRY(nl.ensure(sizeof(uint64_t) * ncap));
+    if (n_total) {
+      IM_TRY(hipMemcpyAsync(nk.p, d_k[0].p, kb * n_total, hipMemcpyDeviceToDevice, st));
+      IM_TRY(hipMemcpyAsync(nv.p, d_v[0].p, sizeof(uint32_t) * n_total, hipMemcpyDeviceToDevice, st));
+      IM_TRY(hipMemcpyAsync(nl.p, d_l[0].p, sizeof(uint64_t) * n_total, hipMemcpyDeviceToDevice, st));
+      IM_TRY(hipStreamSynchronize(st));
+    }
+    d_k[0] = std::move(nk); d_v[0] = std::move(nv); d_l[0] = std::move(nl);
+    cap = ncap;
+    return MGC_OK;
+  }
+
+  // one batch of whole lines: its triples appended in input order
+  int batch(const char *h_text, size_t n, Reader *rd, int slot) {
+    IM_TRY(d_text.ensure(n + 64));
+    IM_TRY(d_pws.ensure(mgc::import2_parse_workspace_bytes(n)));
+    IM_TRY(hipEventRecord(ev[0], st));
+    IM_TRY(hipMemcpyAsync(d_text.p, h_text, n, hipMemcpyHostToDevice, st));
+    IM_TRY(hipEventRecord(ev[1], st));
+    mgc::Import2State *ds = d_state.as<mgc::Import2State>();
+    IM_TRY(mgc::launch_import2_parse_count(d_text.as<uint8_t>(), n, k, label_width, ds, d_pws.p, st));
+    IM_TRY(hipEventRecord(ev[2], st));
+    mgc::Import2State h;
+    IM_TRY(hipMemcpyAsync(&h, ds, sizeof(h), hipMemcpyDeviceToHost, st));
+    IM_TRY(hipStreamSynchronize(st));
+    rd->release(slot);                                      // the text has left the pinned buffer
+    info.n_lines += h.chunk_lines;
+    if (h.first_bad != ~0ull) {
+      info.bad_line = h.first_bad >> 3; info.bad_kind = (uint32_t)(h.first_bad & 7);
+      set_err(nullptr, "meryl-import: line %llu: %s", (unsigned long long)info.bad_line, bad_text2(info.bad_kind));
+      return MGC_EFORMAT;
+    }
+    const uint64_t nr = h.chunk_records;
+    info.n_records += nr;
+    const int rc = reserve(n_total + nr);
+    if (rc != MGC_OK) return rc;
+    const size_t kb = sizeof(uint64_t) * kw;
+    IM_TRY(hipEventRecord(ev[3], st));
+    IM_TRY(mgc::launch_import2_parse_emit(d_text.as<uint8_t>(), n, k, mode, label_width, ds, d_pws.p,
+                                          reinterpret_cast<unsigned char *>(d_k[0].p) + kb * n_total, d_v[0].as<uint32_t>() + n_total,
+                                          d_l[0].as<uint64_t>() + n_total, st));
+    IM_TRY(hipEventRecord(ev[4], st));
+    IM_TRY(hipEventSynchronize(ev[4]));
+    float up = 0, p1 = 0, p2 = 0;
+    IM_TRY(hipEventElapsedTime(&up, ev[0], ev[1]));
+    IM_TRY(hipEventElapsedTime(&p1, ev[1], ev[2]));
+    IM_TRY(hipEventElapsedTime(&p2, ev[3], ev[4]));
+    info.upload_ms += up; info.parse_ms += p1 + p2;
+    n_total += nr;
+    return MGC_OK;
+  }
+
+  // all triples -> *nd ascending distinct k-mers with their sums, back in the [0] arrays
+  int sort_and_reduce(uint64_t *nd) {
+    *nd = 0;
+    if (n_total == 0) return MGC_OK;
+    if (n_total > MGC_SORT_TRIPLES_MAX_N) {
+      set_err(nullptr, "meryl-import: %llu records, one labelled import takes at most %llu (the triple sort carries 32-bit record numbers)",
+              (unsigned long long)n_total, (unsigned long long)MGC_SORT_TRIPLES_MAX_N);
+      return MGC_EUNSUPPORTED;
+    }
+    d_text.release(); d_pws.release();
+    const size_t kb = sizeof(uint64_t) * kw;
+    const size_t sws = mgc::sort_triples_workspace_bytes(n_total), rws = mgc::reduce_triples_workspace_bytes(n_total);
+    const int rc = room_for(n_total * triple_bytes() + sws + rws + 5 * 256, "the sort");
+    if (rc != MGC_OK) return rc;
+    IM_TRY(d_k[1].ensure(kb * n_total)); IM_TRY(d_v[1].ensure(sizeof(uint32_t) * n_total)); IM_TRY(d_l[1].ensure(sizeof(uint64_t) * n_total));
+    IM_TRY(d_sws.ensure(sws)); IM_TRY(d_rws.ensure(rws));
+    IM_TRY(hipEventRecord(ev[0], st));
+    int in_alt = 0;
+    IM_TRY(mgc::launch_sort_triples(d_k[0].p, d_v[0].as<uint32_t>(), d_l[0].as<uint64_t>(), d_k[1].p, d_v[1].as<uint32_t>(),
+                                    d_l[1].as<uint64_t>(), n_total, kw, 0, 2 * k, d_sws.p, &in_alt, st));
+    IM_TRY(hipEventRecord(ev[1], st));
+    const int s = in_alt ? 1 : 0, o = s ^ 1;
+    IM_TRY(mgc::launch_reduce_triples_count(d_k[s].p, d_v[s].as<uint32_t>(), d_l[s].as<uint64_t>(), n_total, kw, d_rws.p, st));
+    IM_TRY(mgc::launch_reduce_triples_emit(d_k[s].p, d_v[s].as<uint32_t>(), d_l[s].as<uint64_t>(), n_total, kw, label_width, d_rws.p,
+                                           d_k[o].p, d_v[o].as<uint32_t>(), d_l[o].as<uint64_t>(), st));   // (synchronises for the count)
+    IM_TRY(hipMemcpyAsync(nd, d_rws.p, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    IM_TRY(hipEventRecord(ev[2], st));
+    IM_TRY(hipEventSynchronize(ev[2]));
+    float sm = 0, rm = 0;
+    IM_TRY(hipEventElapsedTime(&sm, ev[0], ev[1]));
+    IM_TRY(hipEventElapsedTime(&rm, ev[1], ev[2]));
+    info.sort_ms += sm; info.reduce_ms += rm;
+    if (o != 0) { std::swap(d_k[0], d_k[1]); std::swap(d_v[0], d_v[1]); std::swap(d_l[0], d_l[1]); }
+    return MGC_OK;
+  }
+
+  int run(Source *src, const char *output) {
+    const double t_begin = now_s();
+    memset(&info, 0, sizeof(info));
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_err(nullptr, "meryl-import: no HIP device"); return MGC_EHIP; }
+    if (device < 0) (void)hipGetDevice(&device);
+    IM_TRY(hipSetDevice(device));
+    IM_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    for (hipEvent_t &e : ev) IM_TRY(hipEventCreate(&e));
+    size_t free_b = 0, total_b = 0;
+    IM_TRY(hipMemGetInfo(&free_b, &total_b));
+    // the batch size of the meryl 1 driver: the triples a batch of text leaves (at most one per k + 1 >= 7 bytes) stay on
+    // the device, the text does not
+    uint64_t batch_bytes = std::min<uint64_t>(std::max<uint64_t>(free_b / 12, 1u << 20), 256ull << 20);
+    if (const char *e = getenv("MGC_IMPORT_BATCH")) { if (*e) batch_bytes = strtoull(e, nullptr, 10); }
+    batch_bytes = std::min<uint64_t>(std::max<uint64_t>(batch_bytes, 64), 1ull << 31);
+    IM_TRY(d_state.ensure(sizeof(mgc::Import2State)));
+    IM_TRY(mgc::launch_import2_begin(d_state.as<mgc::Import2State>(), st));
+
+    Reader rd;
+    if (!rd.start(src, (size_t)batch_bytes, device)) { set_err(nullptr, "meryl-import: no pinned memory for batches of %llu bytes", (unsigned long long)batch_bytes); return MGC_ENOMEM; }
+    for (int i = 0;; i ^= 1) {
+      Reader::Slot *s = rd.wait(i);
+      if (rd.failed) { set_err(nullptr, "meryl-import: reading the input failed"); return MGC_EINVAL; }
+      const bool last = s->last;
+      const size_t n = s->n;
+      info.text_bytes += n;
+      if (n == 0) { rd.release(i); if (last) break; continue; }
+      info.n_batches++;
+      const int rc = batch(s->p, n, &rd, i);
+      if (rc != MGC_OK) return rc;
+      if (last) break;
+    }
+    info.read_s = rd.read_s;
+
+    uint64_t nd = 0;
+    int rc = sort_and_reduce(&nd);
+    if (rc != MGC_OK) return rc;
+
+    // the whole input is accepted and reduced: only now does anything appear at the output path
+    const double t_write = now_s();
+    mgc_db_stream *d = mgc_db_stream_open(output, k, MGC_IMPORT2_W_PREFIX, label_width, 0, 0, 1, host_threads, device);
+    if (!d) { set_err(nullptr, "meryl-import: %s", mgc_db_stream_error(nullptr)); return MGC_EINVAL; }
+    std::string msg;
+    rc = mgc_db_stream_write_labelled(d, nd ? d_k[0].p : nullptr, nd ? d_v[0].as<uint32_t>() : nullptr, nd ? d_l[0].as<uint64_t>() : nullptr,
+                                      nd, 0, 1ull << MGC_IMPORT2_W_PREFIX);
+    if (rc != MGC_OK) msg = mgc_db_stream_error(d);
+    const int rc2 = mgc_db_stream_close(d, nullptr);
+    if (rc == MGC_OK && rc2 != MGC_OK) { rc = rc2; msg = mgc_db_stream_error(nullptr); }
+    if (rc != MGC_OK) set_err(nullptr, "meryl-import: %s", msg.c_str());
+    info.n_distinct = nd;
+    info.write_s = now_s() - t_write;
+    info.total_s = now_s() - t_begin;
+    return rc;
+  }
+#undef IM_TRY
+};
+
+int import_labelled_from(Source *src, uint32_t k, int mode, uint32_t label_width, const char *output, int device, int host_threads,
+                         mgc_import_info *info) {
+  LabelledImporter im;
+  im.k = k; im.kw = k > 32 ? 2u : 1u; im.label_width = label_width; im.mode = mode; im.device = device; im.host_threads = host_threads;
+  memset(&im.info, 0, sizeof(im.info));
+  const int rc = im.run(src, output);
+  if (info) *info = im.info;
+  return rc;
+}
+
+bool import_labelled_args_ok(uint32_t k, int mode, uint32_t label_width, const char *output) {
+  if (!k_ok(k, MGC_IMPORT2_W_PREFIX) || !label_width_ok(label_width)) return false;
+  if (mode < 0 || mode > 2 || !output || !*output) { set_err(nullptr, "meryl-import: bad mode or no output path"); return false; }
+  return true;
+}
+}  // namespace
+
+extern "C" int mgc_import_labelled_file(const char *path, uint32_t k, int mode, uint32_t label_width, const char *output, int device,
+                                        int host_threads, mgc_import_info *info) {
+  if (info) memset(info, 0, sizeof(*info));
+  if (!path || !*path) { set_err(nullptr, "meryl-import: no input path"); return MGC_EINVAL; }
+  if (!import_labelled_args_ok(k, mode, label_width, output)) return MGC_EINVAL;
+  GzSource src;
+  const std::string p(path);
+  src.gz = (p == "-") ? gzdopen(0, "rb") : gzopen(path, "rb");
+  if (!src.gz) { set_err(nullptr, "meryl-import: cannot open '%s'", path); return MGC_EINVAL; }
+  (void)gzbuffer(src.gz, 1u << 20);
+  return import_labelled_from(&src, k, mode, label_width, output, device, host_threads, info);
+}
+
+extern "C" int mgc_import_labelled_text(const char *text, uint64_t n_text, uint32_t k, int mode, uint32_t label_width, const char *output,
+                                        int device, int host_threads, mgc_import_info *info) {
+  if (info) memset(info, 0, sizeof(*info));
+  if (!text && n_text) { set_err(nullptr, "meryl-import: NULL text"); return MGC_EINVAL; }
+  if (!import_labelled_args_ok(k, mode, label_width, output)) return MGC_EINVAL;
+  MemSource src(text, n_text);
+  return import_labelled_from(&src, k, mode, label_width, output, device, host_threads, info);
 }

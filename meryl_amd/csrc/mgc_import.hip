@@ -7,6 +7,8 @@
 //                    (:199-211), the optional second word as the value (:193-194)
 //   pair_*           the std::sort of (suffix, value) records in countSingleKmersWithValues, src/meryl/merylCountArray.C:387
 //   reduce_*         its summing loop over equal suffixes, :393-408 (uint32 sums wrap, :403)
+//   import2_* / triple_* / reduce_triples_*   the same three steps for the meryl 2 dialect with labels
+//                    (src/meryl2-import/meryl-import.C:199-264, src/meryl2/merylCountArray.C:381-400), at the end of the file
 //
 // Two things are sequential in the text: the output slot of a record (records before it) and the persistent value (the
 // last `#` line before it).  Both are one scan with the operator of PAgg below: tiles of 4096 bytes summarise themselves,
@@ -16,7 +18,7 @@
 // No kernel here waits for another workgroup of its launch; every index is checked against n before it is used.
 #include "mgc_common.hpp"
 #include "mgc_import_dev.hpp"
-#include "../../include/meryl_import.h"
+#include "../../include/meryl_import_labelled.h"
 
 namespace mgc {
 
@@ -103,6 +105,40 @@ __device__ __forceinline__ u64 pr_first_word(const uint8_t *__restrict__ t, u64 
   return (p < n && t[p] != '\n') ? p : n;
 }
 
+// the k-mer word at t[j...] (ends at white space, '\n' or n; j is left behind it): its last k bases packed into *f -- A0 C1 T2 G3,
+// either case (mgc_kmer.hip).  -> 0, or MGC_IMPORT_BAD_BASE / MGC_IMPORT_BAD_SHORT.  KT: u64 (k <= 32) or u128
+template <typename KT>
+__device__ __forceinline__ u32 pr_kmer_word(const uint8_t *__restrict__ t, u64 n, u64 &j, u32 k, KT *f_out) {
+  const KT mask = (2 * k == 8 * sizeof(KT)) ? ~(KT)0 : (((KT)1 << (2 * k)) - 1);
+  KT f = 0;
+  u32 len = 0;
+  bool bases_ok = true;
+  while (j < n) {
+    const u32 c = t[j];
+    if (c == '\n' || pr_is_space(c)) break;
+    const u32 up = c & 0xDFu;
+    if (up != 'A' && up != 'C' && up != 'G' && up != 'T') bases_ok = false;
+    f = ((f << 2) | (KT)((c >> 1) & 3u)) & mask;
+    if (len < 0xFFFFFFFFu) len++;
+    j++;
+  }
+  *f_out = f;
+  return !bases_ok ? (u32)MGC_IMPORT_BAD_BASE : len < k ? (u32)MGC_IMPORT_BAD_SHORT : 0u;
+}
+
+// min(forward, reverse complement) / forward / reverse complement of the k bases in f -> {lo, hi}
+template <typename KT>
+__device__ __forceinline__ void pr_pick(KT f, u32 k, int mode, u64 *lo, u64 *hi) {
+  KT key = f;
+  if (mode != MGC_MODE_FORWARD) {
+    KT r = 0, x = f;
+    for (u32 i = 0; i < k; i++) { r = (r << 2) | ((x & 3) ^ 2); x >>= 2; }   // base i -> base k-1-i, complemented
+    key = (mode == MGC_MODE_REVERSE) ? r : (f < r ? f : r);
+  }
+  *lo = (u64)key;
+  if (sizeof(KT) > 8) *hi = (u64)((u128)key >> 64);
+}
+
 // the line that starts at byte p.  KT: u64 (k <= 32) or u128
 template <typename KT>
 __device__ Line parse_line(const uint8_t *__restrict__ t, u64 n, u64 p, u32 k, int mode, bool want_key) {
@@ -116,37 +152,15 @@ __device__ Line parse_line(const uint8_t *__restrict__ t, u64 n, u64 p, u32 k, i
     else { L.kind = LN_BAD; L.bad = MGC_IMPORT_BAD_HASH; }
     return L;
   }
-  const KT mask = (2 * k == 8 * sizeof(KT)) ? ~(KT)0 : (((KT)1 << (2 * k)) - 1);
   KT f = 0;
-  u32 len = 0;
-  bool bases_ok = true;
-  while (j < n) {
-    const u32 c = t[j];
-    if (c == '\n' || pr_is_space(c)) break;
-    const u32 up = c & 0xDFu;
-    if (up != 'A' && up != 'C' && up != 'G' && up != 'T') bases_ok = false;
-    f = ((f << 2) | (KT)((c >> 1) & 3u)) & mask;                         // A0 C1 T2 G3, either case (mgc_kmer.hip)
-    if (len < 0xFFFFFFFFu) len++;
-    j++;
-  }
-  if (!bases_ok) { L.kind = LN_BAD; L.bad = MGC_IMPORT_BAD_BASE; return L; }
-  if (len < k)   { L.kind = LN_BAD; L.bad = MGC_IMPORT_BAD_SHORT; return L; }
+  if (const u32 bad = pr_kmer_word<KT>(t, n, j, k, &f)) { L.kind = LN_BAD; L.bad = bad; return L; }
   while (j < n && pr_is_space(t[j])) j++;
   if (j < n && t[j] != '\n') {                                           // :193-194; words after it are ignored
     if (!pr_number(t, n, j, &L.value)) { L.kind = LN_BAD; L.bad = MGC_IMPORT_BAD_VALUE; return L; }
     L.has_value = 1;
   }
   L.kind = LN_RECORD;
-  if (want_key) {
-    KT key = f;
-    if (mode != MGC_MODE_FORWARD) {
-      KT r = 0, x = f;
-      for (u32 i = 0; i < k; i++) { r = (r << 2) | ((x & 3) ^ 2); x >>= 2; }   // base i -> base k-1-i, complemented
-      key = (mode == MGC_MODE_REVERSE) ? r : (f < r ? f : r);
-    }
-    L.lo = (u64)key;
-    if (sizeof(KT) > 8) L.hi = (u64)((u128)key >> 64);
-  }
+  if (want_key) pr_pick<KT>(f, k, mode, &L.lo, &L.hi);
   return L;
 }
 
@@ -190,21 +204,26 @@ void import_parse_count_kernel(const uint8_t *__restrict__ t, u64 n, u32 k, Impo
   if (threadIdx.x == 0) tiles[blockIdx.x] = tot;
 }
 
+// lines that start in the tile of byte `pos` before it, summed over the block into *s_cnt (LDS); every thread must call it
+__device__ __forceinline__ void pr_lines_before(const uint8_t *__restrict__ t, u64 n, u64 pos, bool count, u32 *s_cnt) {
+  if (threadIdx.x == 0) *s_cnt = 0;
+  __syncthreads();
+  if (count) {
+    const u64 tile0 = (pos / PR_TILE) * PR_TILE;
+    u32 c = 0;
+    for (u64 q = tile0 + threadIdx.x; q < pos && q < n; q += PR_BLOCK) c += (q == 0 || t[q - 1] == '\n') ? 1u : 0u;
+    if (c) atomicAdd(s_cnt, c);
+  }
+  __syncthreads();
+}
+
 // after the composing step: the chunk's totals into the state; a refused line's byte offset -> its line number
 __global__ __launch_bounds__(PR_BLOCK)
 void import_parse_total_kernel(const uint8_t *__restrict__ t, u64 n, ImportState *__restrict__ state, const PAgg *__restrict__ tiles,
                                const PAgg *__restrict__ total) {
   __shared__ u32 s_cnt;
-  if (threadIdx.x == 0) s_cnt = 0;
-  __syncthreads();
   const u64 bad = state->chunk_bad;
-  if (bad != ~0ull) {
-    const u64 pos = bad >> 3, tile0 = (pos / PR_TILE) * PR_TILE;
-    u32 c = 0;
-    for (u64 q = tile0 + threadIdx.x; q < pos && q < n; q += PR_BLOCK) c += (q == 0 || t[q - 1] == '\n') ? 1u : 0u;
-    if (c) atomicAdd(&s_cnt, c);
-  }
-  __syncthreads();
+  pr_lines_before(t, n, bad >> 3, bad != ~0ull, &s_cnt);
   if (threadIdx.x == 0) {
     state->chunk_lines = total->lines;
     state->chunk_records = total->rec;
@@ -557,6 +576,427 @@ hipError_t launch_reduce_pairs_emit(const void *d_keys, const uint32_t *d_vals, 
   else
     hipLaunchKernelGGL((reduce_pairs_kernel<u64, true>), dim3((uint32_t)T), dim3(RD_BLOCK), 0, st, reinterpret_cast<const u64 *>(d_keys),
                        d_vals, (u64)n, tiles, (u64)n_out, reinterpret_cast<u64 *>(d_out_keys), d_out_vals);
+  return hipGetLastError();
+}
+
+// ============================================================================
+//  The meryl 2 dialect (include/meryl_import_labelled.h): `kmer [value [label]]` records, `value=<n>` and `label=<n>` lines
+//  (src/meryl2-import/meryl-import.C:199-233).  The same scan as above with two persistent words in the aggregate.
+// ============================================================================
+struct P2Agg {
+  u32 rec, lines, vhas, val, lhas, pad;
+  u64 lab;
+  static __device__ __forceinline__ P2Agg identity() { P2Agg a; a.rec = a.lines = a.vhas = a.val = a.lhas = a.pad = 0; a.lab = 0; return a; }
+  static __device__ __forceinline__ P2Agg combine(P2Agg a, P2Agg b) {
+    P2Agg r; r.rec = a.rec + b.rec; r.lines = a.lines + b.lines; r.pad = 0;
+    r.vhas = a.vhas | b.vhas; r.val = b.vhas ? b.val : a.val;
+    r.lhas = a.lhas | b.lhas; r.lab = b.lhas ? b.lab : a.lab;
+    return r;
+  }
+};
+
+enum { L2_BLANK = 0, L2_VALUE = 1, L2_LABEL = 2, L2_RECORD = 3, L2_BAD = 4 };
+struct Line2 { u32 kind, bad, value, has_value, has_label; u64 label, lo, hi; };
+
+__device__ __forceinline__ u64 pr_word_end(const uint8_t *__restrict__ t, u64 n, u64 j) {
+  while (j < n && t[j] != '\n' && !pr_is_space(t[j])) j++;
+  return j;
+}
+
+// decodeInteger over the word t[a, e): `123` / `123d`, `<hex>h` (digits in either case), `<octal>o`, `<binary>b`
+// (documentation/source/reference.rst:615-617); the word's last byte decides the base.  false: no digit, a digit the base
+// does not have, any other byte (SI suffixes, an upper-case suffix letter, a sign), or a number above `limit`
+__device__ __forceinline__ bool pr2_number(const uint8_t *__restrict__ t, u64 a, u64 e, u64 limit, u64 *out) {
+  *out = 0;
+  if (a >= e) return false;
+  const u32 last = t[e - 1];
+  u32 base = 10;
+  if (last == 'h') base = 16;
+  else if (last == 'o') base = 8;
+  else if (last == 'b') base = 2;
+  if (last == 'h' || last == 'o' || last == 'b' || last == 'd') e--;
+  if (a >= e) return false;
+  u64 v = 0;
+  for (u64 j = a; j < e; j++) {
+    const u32 c = t[j], lc = c | 0x20u;
+    u32 d;
+    if (c >= '0' && c <= '9') d = c - '0';
+    else if (lc >= 'a' && lc <= 'f') d = lc - 'a' + 10u;
+    else return false;
+    if (d >= base || (u64)d > limit || v > (limit - (u64)d) / (u64)base) return false;
+    v = v * (u64)base + (u64)d;
+  }
+  *out = v;
+  return true;
+}
+
+// 1: the word at j starts with `value=`, 2: with `label=` (strncmp(word, ..., 6), meryl-import.C:210, :215), 0: neither
+__device__ __forceinline__ u32 pr2_assign(const uint8_t *__restrict__ t, u64 n, u64 j) {
+  if (j + 6 > n || t[j + 5] != '=') return 0;
+  if (t[j] == 'v' && t[j + 1] == 'a' && t[j + 2] == 'l' && t[j + 3] == 'u' && t[j + 4] == 'e') return 1;
+  if (t[j] == 'l' && t[j + 1] == 'a' && t[j + 2] == 'b' && t[j + 3] == 'e' && t[j + 4] == 'l') return 2;
+  return 0;
+}
+
+// the number of a `value=` / `label=` line whose first word starts at j (which = pr2_assign)
+__device__ __forceinline__ bool pr2_assign_number(const uint8_t *__restrict__ t, u64 n, u64 j, u32 which, u64 lmask, u64 *out) {
+  return pr2_number(t, j + 6, pr_word_end(t, n, j), which == 1 ? 0xFFFFFFFFull : lmask, out);
+}
+
+// the line that starts at byte p.  lmask: the bits a label may hold
+template <typename KT>
+__device__ Line2 parse_line2(const uint8_t *__restrict__ t, u64 n, u64 p, u32 k, int mode, u64 lmask, bool want_key) {
+  Line2 L;
+  L.kind = L2_BLANK; L.bad = 0; L.value = 0; L.has_value = 0; L.has_label = 0; L.label = 0; L.lo = L.hi = 0;
+  u64 j = pr_first_word(t, n, p);
+  if (j >= n) return L;
+  if (const u32 which = pr2_assign(t, n, j)) {                           // :210-218; words after it are ignored
+    u64 v = 0;
+    if (!pr2_assign_number(t, n, j, which, lmask, &v)) { L.kind = L2_BAD; L.bad = MGC_IMPORT_BAD_ASSIGN; return L; }
+    if (which == 1) { L.kind = L2_VALUE; L.value = (u32)v; } else { L.kind = L2_LABEL; L.label = v; }
+    return L;
+  }
+  KT f = 0;                                                              // :222-223, as parse_line reads it
+  if (const u32 bad = pr_kmer_word<KT>(t, n, j, k, &f)) { L.kind = L2_BAD; L.bad = bad; return L; }
+  while (j < n && pr_is_space(t[j])) j++;
+  if (j < n && t[j] != '\n') {                                           // :225-226
+    const u64 e = pr_word_end(t, n, j);
+    u64 v = 0;
+    if (!pr2_number(t, j, e, 0xFFFFFFFFull, &v)) { L.kind = L2_BAD; L.bad = MGC_IMPORT_BAD_VALUE; return L; }
+    L.value = (u32)v; L.has_value = 1;
+    j = e;
+    while (j < n && pr_is_space(t[j])) j++;
+    if (j < n && t[j] != '\n') {                                         // :230-231; words after it are ignored
+      if (!pr2_number(t, j, pr_word_end(t, n, j), lmask, &L.label)) { L.kind = L2_BAD; L.bad = MGC_IMPORT_BAD_LABEL; return L; }
+      L.has_label = 1;
+    }
+  }
+  L.kind = L2_RECORD;
+  if (want_key) pr_pick<KT>(f, k, mode, &L.lo, &L.hi);                   // :235-246
+  return L;
+}
+
+template <typename KT>
+__global__ __launch_bounds__(PR_BLOCK)
+void import2_parse_count_kernel(const uint8_t *__restrict__ t, u64 n, u32 k, u64 lmask, Import2State *__restrict__ state,
+                                P2Agg *__restrict__ tiles) {
+  __shared__ P2Agg s[PR_BLOCK];
+  const bool aligned = (reinterpret_cast<uintptr_t>(t) & 15u) == 0;
+  const u64 p0 = (u64)blockIdx.x * PR_TILE + (u64)threadIdx.x * PR_BYTES;
+  u32 starts = pr_line_starts(t, n, p0, aligned);
+  P2Agg agg = P2Agg::identity();
+  u64 bad = ~0ull;
+  while (starts) {
+    const u32 q = (u32)__builtin_ctz(starts);
+    starts &= starts - 1;
+    const Line2 L = parse_line2<KT>(t, n, p0 + q, k, MGC_MODE_FORWARD, lmask, false);
+    agg.lines++;
+    if (L.kind == L2_RECORD) agg.rec++;
+    else if (L.kind == L2_VALUE) { agg.vhas = 1; agg.val = L.value; }
+    else if (L.kind == L2_LABEL) { agg.lhas = 1; agg.lab = L.label; }
+    else if (L.kind == L2_BAD && bad == ~0ull) bad = ((p0 + q) << 3) | (u64)L.bad;
+  }
+  if (bad != ~0ull) atomicMin(reinterpret_cast<unsigned long long *>(&state->chunk_bad), (unsigned long long)bad);   // refused input only
+  P2Agg tot;
+  (void)block_scan_excl<PR_BLOCK, P2Agg>(agg, s, &tot);
+  if (threadIdx.x == 0) tiles[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(PR_BLOCK)
+void import2_parse_total_kernel(const uint8_t *__restrict__ t, u64 n, Import2State *__restrict__ state, const P2Agg *__restrict__ tiles,
+                                const P2Agg *__restrict__ total) {
+  __shared__ u32 s_cnt;
+  const u64 bad = state->chunk_bad;
+  pr_lines_before(t, n, bad >> 3, bad != ~0ull, &s_cnt);
+  if (threadIdx.x == 0) {
+    state->chunk_lines = total->lines;
+    state->chunk_records = total->rec;
+    state->chunk_vhas = total->vhas; state->chunk_val = total->val;
+    state->chunk_lhas = total->lhas; state->chunk_lab = total->lab;
+    if (bad != ~0ull && state->first_bad == ~0ull) {
+      const u64 line = state->lines_seen + (u64)tiles[(bad >> 3) / PR_TILE].lines + (u64)s_cnt + 1ull;
+      state->first_bad = (line << 3) | (bad & 7ull);
+    }
+  }
+}
+
+template <typename KT>
+__global__ __launch_bounds__(PR_BLOCK)
+void import2_parse_emit_kernel(const uint8_t *__restrict__ t, u64 n, u32 k, int mode, u64 lmask, const Import2State *__restrict__ state,
+                               const P2Agg *__restrict__ tiles, u64 n_records, void *__restrict__ keys, u32 *__restrict__ vals,
+                               u64 *__restrict__ labs) {
+  __shared__ P2Agg s[PR_BLOCK];
+  const bool aligned = (reinterpret_cast<uintptr_t>(t) & 15u) == 0;
+  const u64 p0 = (u64)blockIdx.x * PR_TILE + (u64)threadIdx.x * PR_BYTES;
+  const u32 starts0 = pr_line_starts(t, n, p0, aligned);
+  // what this thread's lines are: only a `value=` / `label=` line is read beyond its first word's head
+  P2Agg agg = P2Agg::identity();
+  u32 recs = 0;                                                           // bit q: the line at p0 + q is a record
+  for (u32 starts = starts0; starts;) {
+    const u32 q = (u32)__builtin_ctz(starts);
+    starts &= starts - 1;
+    const u64 j = pr_first_word(t, n, p0 + q);
+    if (j >= n) continue;
+    if (const u32 which = pr2_assign(t, n, j)) {
+      u64 v = 0;
+      if (pr2_assign_number(t, n, j, which, lmask, &v)) {
+        if (which == 1) { agg.vhas = 1; agg.val = (u32)v; } else { agg.lhas = 1; agg.lab = v; }
+      }
+    } else { agg.rec++; recs |= 1u << q; }
+  }
+  P2Agg tot;
+  const P2Agg before = P2Agg::combine(tiles[blockIdx.x], block_scan_excl<PR_BLOCK, P2Agg>(agg, s, &tot));
+  u64 slot = (u64)before.rec;
+  u32 pval = before.vhas ? before.val : state->persistent_value;
+  u64 plab = before.lhas ? before.lab : state->persistent_label;
+  for (u32 starts = starts0; starts;) {
+    const u32 q = (u32)__builtin_ctz(starts);
+    starts &= starts - 1;
+    if (recs & (1u << q)) {
+      const Line2 L = parse_line2<KT>(t, n, p0 + q, k, mode, lmask, true);
+      if (slot < n_records) {                                             // (always, for text the count pass accepted)
+        if (sizeof(KT) > 8) { K128 kk; kk.lo = L.lo; kk.hi = L.hi; reinterpret_cast<K128 *>(keys)[slot] = kk; }
+        else reinterpret_cast<u64 *>(keys)[slot] = L.lo;
+        vals[slot] = L.has_value ? L.value : pval;                        // :225-233
+        labs[slot] = L.has_label ? L.label : plab;
+      }
+      slot++;
+    } else {
+      const u64 j = pr_first_word(t, n, p0 + q);
+      const u32 which = j < n ? pr2_assign(t, n, j) : 0u;
+      u64 v = 0;
+      if (which && pr2_assign_number(t, n, j, which, lmask, &v)) { if (which == 1) pval = (u32)v; else plab = v; }
+    }
+  }
+}
+
+__device__ __forceinline__ void import2_chunk_clear(Import2State *state) {
+  state->chunk_lines = 0; state->chunk_records = 0; state->chunk_lab = 0;
+  state->chunk_vhas = 0; state->chunk_val = 0; state->chunk_lhas = 0; state->pad1 = 0; state->chunk_bad = ~0ull;
+}
+__global__ void import2_begin_kernel(Import2State *state) {
+  state->lines_seen = 0; state->records_seen = 0; state->first_bad = ~0ull;
+  state->persistent_label = 0; state->persistent_value = 1; state->pad0 = 0;     // (the reference leaves both unset, :176-177)
+  import2_chunk_clear(state);
+}
+__global__ void import2_chunk_reset_kernel(Import2State *state) { import2_chunk_clear(state); }
+__global__ void import2_commit_kernel(Import2State *state) {
+  state->lines_seen += state->chunk_lines;
+  state->records_seen += state->chunk_records;
+  if (state->chunk_vhas) state->persistent_value = state->chunk_val;
+  if (state->chunk_lhas) state->persistent_label = state->chunk_lab;
+  import2_chunk_clear(state);
+}
+
+static inline u64 label_mask(uint32_t label_width) { return label_width >= 64 ? ~0ull : ((1ull << label_width) - 1ull); }
+
+// workspace: [0, 64): the total; then one P2Agg per tile
+size_t import2_parse_workspace_bytes(uint64_t n_text) { return 64 + sizeof(P2Agg) * (size_t)(parse_tiles(n_text) + 1); }
+
+hipError_t launch_import2_begin(Import2State *d_state, hipStream_t st) {
+  hipLaunchKernelGGL(import2_begin_kernel, dim3(1), dim3(1), 0, st, d_state);
+  return hipGetLastError();
+}
+
+hipError_t launch_import2_parse_count(const uint8_t *d_text, uint64_t n, uint32_t k, uint32_t label_width, Import2State *d_state, void *d_ws,
+                                      hipStream_t st) {
+  hipLaunchKernelGGL(import2_chunk_reset_kernel, dim3(1), dim3(1), 0, st, d_state);
+  MGC_CHECK(hipGetLastError());
+  const uint64_t T = parse_tiles(n);
+  if (T == 0) return hipSuccess;
+  P2Agg *total = reinterpret_cast<P2Agg *>(d_ws);
+  P2Agg *tiles = reinterpret_cast<P2Agg *>(reinterpret_cast<unsigned char *>(d_ws) + 64);
+  const u64 lmask = label_mask(label_width);
+  if (k > 32) hipLaunchKernelGGL(import2_parse_count_kernel<u128>, dim3((uint32_t)T), dim3(PR_BLOCK), 0, st, d_text, (u64)n, k, lmask, d_state, tiles);
+  else        hipLaunchKernelGGL(import2_parse_count_kernel<u64>, dim3((uint32_t)T), dim3(PR_BLOCK), 0, st, d_text, (u64)n, k, lmask, d_state, tiles);
+  MGC_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(compose_tiles_kernel<P2Agg>, dim3(1), dim3(CP_BLOCK), 0, st, tiles, (u64)T, total);
+  MGC_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(import2_parse_total_kernel, dim3(1), dim3(PR_BLOCK), 0, st, d_text, (u64)n, d_state, (const P2Agg *)tiles, (const P2Agg *)total);
+  return hipGetLastError();
+}
+
+hipError_t launch_import2_parse_emit(const uint8_t *d_text, uint64_t n, uint32_t k, int mode, uint32_t label_width, Import2State *d_state,
+                                     void *d_ws, void *d_keys, uint32_t *d_values, uint64_t *d_labels, hipStream_t st) {
+  const uint64_t T = parse_tiles(n);
+  if (T) {
+    const P2Agg *tiles = reinterpret_cast<const P2Agg *>(reinterpret_cast<const unsigned char *>(d_ws) + 64);
+    // the number of records the count pass found bounds every store (the host allocated that many)
+    uint64_t n_records = 0;
+    MGC_CHECK(hipMemcpyAsync(&n_records, &d_state->chunk_records, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    MGC_CHECK(hipStreamSynchronize(st));
+    if (n_records) {
+      const u64 lmask = label_mask(label_width);
+      if (k > 32) hipLaunchKernelGGL(import2_parse_emit_kernel<u128>, dim3((uint32_t)T), dim3(PR_BLOCK), 0, st, d_text, (u64)n, k, mode, lmask,
+                                     (const Import2State *)d_state, tiles, (u64)n_records, d_keys, d_values, (u64 *)d_labels);
+      else        hipLaunchKernelGGL(import2_parse_emit_kernel<u64>, dim3((uint32_t)T), dim3(PR_BLOCK), 0, st, d_text, (u64)n, k, mode, lmask,
+                                     (const Import2State *)d_state, tiles, (u64)n_records, d_keys, d_values, (u64 *)d_labels);
+      MGC_CHECK(hipGetLastError());
+    }
+  }
+  hipLaunchKernelGGL(import2_commit_kernel, dim3(1), dim3(1), 0, st, d_state);
+  return hipGetLastError();
+}
+
+// ============================================================================
+//  Triple sort: the pair sort over (key, record number), then one gather of values and labels.  Per pass that moves 4 bytes
+//  of payload per record instead of 12; the price is one pass of scattered 4- and 8-byte reads at the end.
+// ============================================================================
+constexpr int TG_BLOCK = 256;
+__global__ __launch_bounds__(TG_BLOCK)
+void triple_number_kernel(u32 *__restrict__ idx, u64 n) {
+  const u64 i = (u64)blockIdx.x * TG_BLOCK + threadIdx.x;
+  if (i < n) idx[i] = (u32)i;
+}
+__global__ __launch_bounds__(TG_BLOCK)
+void triple_gather_kernel(const u32 *__restrict__ idx, const u32 *__restrict__ vin, const u64 *__restrict__ lin, u32 *__restrict__ vout,
+                          u64 *__restrict__ lout, u64 n) {
+  const u64 i = (u64)blockIdx.x * TG_BLOCK + threadIdx.x;
+  if (i < n) {
+    const u64 j = idx[i];
+    if (j < n) { vout[i] = vin[j]; lout[i] = lin[j]; }                   // (always: idx is a permutation of 0 .. n-1)
+  }
+}
+
+static inline size_t tg_index_bytes(uint64_t n) { return (size_t)((n * sizeof(u32) + 255) & ~255ull); }
+static inline size_t tg_pair_bytes(uint64_t n) { return (sort_pairs_workspace_bytes(n) + 255) & ~(size_t)255; }
+// workspace: the pair sort's, then two arrays of record numbers
+size_t sort_triples_workspace_bytes(uint64_t n) { return tg_pair_bytes(n) + 2 * tg_index_bytes(n); }
+
+hipError_t launch_sort_triples(void *d_keys, uint32_t *d_vals, uint64_t *d_labs, void *d_alt_keys, uint32_t *d_alt_vals, uint64_t *d_alt_labs,
+                               uint64_t n, uint32_t key_words, uint32_t begin_bit, uint32_t end_bit, void *d_ws, int *result_in_alt,
+                               hipStream_t st) {
+  *result_in_alt = 0;
+  if (n == 0 || begin_bit >= end_bit) return hipSuccess;
+  if (n > MGC_SORT_TRIPLES_MAX_N) return hipErrorInvalidValue;           // (a record number is 32 bits; the C layer says so in words)
+  unsigned char *ws = reinterpret_cast<unsigned char *>(d_ws);
+  u32 *idx0 = reinterpret_cast<u32 *>(ws + tg_pair_bytes(n)), *idx1 = reinterpret_cast<u32 *>(ws + tg_pair_bytes(n) + tg_index_bytes(n));
+  const uint32_t grid = (uint32_t)((n + TG_BLOCK - 1) / TG_BLOCK);
+  hipLaunchKernelGGL(triple_number_kernel, dim3(grid), dim3(TG_BLOCK), 0, st, idx0, (u64)n);
+  MGC_CHECK(hipGetLastError());
+  int in_alt = 0;
+  MGC_CHECK(launch_sort_pairs(d_keys, idx0, d_alt_keys, idx1, n, key_words, begin_bit, end_bit, d_ws, &in_alt, st));
+  hipLaunchKernelGGL(triple_gather_kernel, dim3(grid), dim3(TG_BLOCK), 0, st, (const u32 *)(in_alt ? idx1 : idx0), (const u32 *)d_vals,
+                     (const u64 *)d_labs, d_alt_vals, (u64 *)d_alt_labs, (u64)n);
+  MGC_CHECK(hipGetLastError());
+  // values and labels are in the alternates now: the keys join them there
+  if (!in_alt) MGC_CHECK(hipMemcpyAsync(d_alt_keys, d_keys, (size_t)n * sizeof(u64) * key_words, hipMemcpyDeviceToDevice, st));
+  *result_in_alt = 1;
+  return hipSuccess;
+}
+
+// ============================================================================
+//  Reduce by key over sorted triples: RAgg with the label sum of the open segment beside its value sum
+//  (_labels[...] += getLabel(), src/meryl2/merylCountArray.C:400; the low label_width bits are what the writer stores)
+// ============================================================================
+struct R2Agg {
+  u64 heads, lsum; u32 has, sum;
+  static __device__ __forceinline__ R2Agg identity() { R2Agg a; a.heads = 0; a.lsum = 0; a.has = 0; a.sum = 0; return a; }
+  static __device__ __forceinline__ R2Agg combine(R2Agg a, R2Agg b) {
+    R2Agg r; r.heads = a.heads + b.heads; r.has = a.has | b.has;
+    r.sum = b.has ? b.sum : a.sum + b.sum; r.lsum = b.has ? b.lsum : a.lsum + b.lsum;
+    return r;
+  }
+};
+
+template <typename K, bool EMIT>
+__global__ __launch_bounds__(RD_BLOCK)
+void reduce_triples_kernel(const K *__restrict__ keys, const u32 *__restrict__ vals, const u64 *__restrict__ labs, u64 n,
+                           R2Agg *__restrict__ tiles /*EMIT: scanned*/, u64 n_out, u64 lmask, K *__restrict__ out_keys,
+                           u32 *__restrict__ out_vals, u64 *__restrict__ out_labs) {
+  __shared__ R2Agg s[RD_BLOCK];
+  const u64 i0 = (u64)blockIdx.x * RD_TILE + (u64)threadIdx.x * RD_ITEMS;
+  K   kreg[RD_ITEMS];
+  u32 vreg[RD_ITEMS];
+  u64 lreg[RD_ITEMS];
+  u32 head = 0;                                          // bit q: element i0 + q starts a segment
+  K prev = KeyOps<K>::zero();
+  if (i0 > 0 && i0 < n) prev = keys[i0 - 1];
+  R2Agg agg = R2Agg::identity();
+#pragma unroll
+  for (int q = 0; q < RD_ITEMS; q++) {
+    const u64 i = i0 + q;
+    kreg[q] = KeyOps<K>::zero(); vreg[q] = 0; lreg[q] = 0;
+    if (i < n) {
+      kreg[q] = keys[i]; vreg[q] = vals[i]; lreg[q] = labs[i];
+      const bool h = (i == 0) || KeyOps<K>::ne(prev, kreg[q]);
+      if (h) { head |= 1u << q; agg.heads++; agg.has = 1; agg.sum = 0; agg.lsum = 0; }
+      agg.sum += vreg[q];
+      agg.lsum += lreg[q];
+      prev = kreg[q];
+    }
+  }
+  R2Agg tot;
+  const R2Agg excl = block_scan_excl<RD_BLOCK, R2Agg>(agg, s, &tot);
+  if (!EMIT) {
+    if (threadIdx.x == 0) tiles[blockIdx.x] = tot;
+    return;
+  }
+  const R2Agg before = R2Agg::combine(tiles[blockIdx.x], excl);
+  u64 hc = before.heads;
+  u32 run = before.sum;
+  u64 lrun = before.lsum;
+  K next = KeyOps<K>::zero();
+  if (i0 + RD_ITEMS < n) next = keys[i0 + RD_ITEMS];
+#pragma unroll
+  for (int q = 0; q < RD_ITEMS; q++) {
+    const u64 i = i0 + q;
+    if (i < n) {
+      if (head & (1u << q)) { hc++; run = 0; lrun = 0; }
+      run += vreg[q];
+      lrun += lreg[q];
+      const K nx = (q + 1 < RD_ITEMS) ? kreg[(q + 1 < RD_ITEMS) ? q + 1 : q] : next;
+      const bool last = (i + 1 == n) || KeyOps<K>::ne(kreg[q], nx);      // the segment ends here: its sums are complete
+      if (last && hc >= 1 && hc - 1 < n_out) { out_keys[hc - 1] = kreg[q]; out_vals[hc - 1] = run; out_labs[hc - 1] = lrun & lmask; }
+    }
+  }
+}
+
+__global__ void reduce_triples_total_kernel(const R2Agg *total, u64 *out) { *out = total->heads; }
+
+// workspace: [0] distinct keys (u64), [64, 128): the composed total, then one R2Agg per tile
+size_t reduce_triples_workspace_bytes(uint64_t n) { return 128 + sizeof(R2Agg) * (size_t)(rd_tiles(n) + 1); }
+
+hipError_t launch_reduce_triples_count(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words,
+                                       void *d_ws, hipStream_t st) {
+  const uint64_t T = rd_tiles(n);
+  if (T == 0) return hipMemsetAsync(d_ws, 0, 8, st);
+  if (T > 0xFFFFFFFFull) return hipErrorInvalidValue;
+  R2Agg *total = reinterpret_cast<R2Agg *>(reinterpret_cast<unsigned char *>(d_ws) + 64);
+  R2Agg *tiles = reinterpret_cast<R2Agg *>(reinterpret_cast<unsigned char *>(d_ws) + 128);
+  if (key_words == 2)
+    hipLaunchKernelGGL((reduce_triples_kernel<K128, false>), dim3((uint32_t)T), dim3(RD_BLOCK), 0, st, reinterpret_cast<const K128 *>(d_keys),
+                       d_vals, (const u64 *)d_labs, (u64)n, tiles, (u64)0, (u64)0, (K128 *)nullptr, (u32 *)nullptr, (u64 *)nullptr);
+  else
+    hipLaunchKernelGGL((reduce_triples_kernel<u64, false>), dim3((uint32_t)T), dim3(RD_BLOCK), 0, st, reinterpret_cast<const u64 *>(d_keys),
+                       d_vals, (const u64 *)d_labs, (u64)n, tiles, (u64)0, (u64)0, (u64 *)nullptr, (u32 *)nullptr, (u64 *)nullptr);
+  MGC_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(compose_tiles_kernel<R2Agg>, dim3(1), dim3(CP_BLOCK), 0, st, tiles, (u64)T, total);
+  MGC_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(reduce_triples_total_kernel, dim3(1), dim3(1), 0, st, (const R2Agg *)total, reinterpret_cast<u64 *>(d_ws));
+  return hipGetLastError();
+}
+
+hipError_t launch_reduce_triples_emit(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words,
+                                      uint32_t label_width, void *d_ws, void *d_out_keys, uint32_t *d_out_vals, uint64_t *d_out_labs,
+                                      hipStream_t st) {
+  const uint64_t T = rd_tiles(n);
+  if (T == 0) return hipSuccess;
+  if (T > 0xFFFFFFFFull) return hipErrorInvalidValue;
+  // the count pass's total bounds every store (the caller allocated that many)
+  uint64_t n_out = 0;
+  MGC_CHECK(hipMemcpyAsync(&n_out, d_ws, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  MGC_CHECK(hipStreamSynchronize(st));
+  R2Agg *tiles = reinterpret_cast<R2Agg *>(reinterpret_cast<unsigned char *>(d_ws) + 128);
+  const u64 lmask = label_mask(label_width);
+  if (key_words == 2)
+    hipLaunchKernelGGL((reduce_triples_kernel<K128, true>), dim3((uint32_t)T), dim3(RD_BLOCK), 0, st, reinterpret_cast<const K128 *>(d_keys),
+                       d_vals, (const u64 *)d_labs, (u64)n, tiles, (u64)n_out, lmask, reinterpret_cast<K128 *>(d_out_keys), d_out_vals,
+                       (u64 *)d_out_labs);
+  else
+    hipLaunchKernelGGL((reduce_triples_kernel<u64, true>), dim3((uint32_t)T), dim3(RD_BLOCK), 0, st, reinterpret_cast<const u64 *>(d_keys),
+                       d_vals, (const u64 *)d_labs, (u64)n, tiles, (u64)n_out, lmask, reinterpret_cast<u64 *>(d_out_keys), d_out_vals,
+                       (u64 *)d_out_labs);
   return hipGetLastError();
 }
 

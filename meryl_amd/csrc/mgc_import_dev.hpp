@@ -36,4 +36,37 @@ hipError_t launch_reduce_pairs_count(const void *d_keys, const uint32_t *d_vals,
 hipError_t launch_reduce_pairs_emit(const void *d_keys, const uint32_t *d_vals, uint64_t n, uint32_t key_words, void *d_ws,
                                     void *d_out_keys, uint32_t *d_out_vals, hipStream_t st);
 
+// ---- the meryl 2 dialect (include/meryl_import_labelled.h): `kmer value label` text -> (k-mer, value, label) triples ------------
+struct Import2State {
+  uint64_t lines_seen, records_seen;       // chunks already committed
+  uint64_t first_bad;                      // (1-based line << 3) | MGC_IMPORT_BAD_*; ~0: none
+  uint64_t persistent_label;               // meryl2-import/meryl-import.C:177
+  uint32_t persistent_value, pad0;         // :176
+  uint64_t chunk_lines, chunk_records;     // the chunk the count pass saw last
+  uint64_t chunk_lab;                      // the number of its last `label=` line
+  uint32_t chunk_vhas, chunk_val;          // it holds a `value=` line / the number of its last one
+  uint32_t chunk_lhas, pad1;               // it holds a `label=` line
+  uint64_t chunk_bad;                      // (byte offset of the line << 3) | kind; ~0: none
+};
+size_t     import2_parse_workspace_bytes(uint64_t n_text);
+hipError_t launch_import2_begin(Import2State *d_state, hipStream_t st);
+hipError_t launch_import2_parse_count(const uint8_t *d_text, uint64_t n, uint32_t k, uint32_t label_width, Import2State *d_state, void *d_ws,
+                                      hipStream_t st);
+hipError_t launch_import2_parse_emit(const uint8_t *d_text, uint64_t n, uint32_t k, int mode, uint32_t label_width, Import2State *d_state,
+                                     void *d_ws, void *d_keys, uint32_t *d_values, uint64_t *d_labels, hipStream_t st);
+
+// ---- triples: the pair sort over (key, record number), then a gather; the result is always in the alternates -----------------
+size_t     sort_triples_workspace_bytes(uint64_t n);
+hipError_t launch_sort_triples(void *d_keys, uint32_t *d_vals, uint64_t *d_labs, void *d_alt_keys, uint32_t *d_alt_vals, uint64_t *d_alt_labs,
+                               uint64_t n, uint32_t key_words, uint32_t begin_bit, uint32_t end_bit, void *d_ws, int *result_in_alt,
+                               hipStream_t st);
+
+// ---- sorted triples -> distinct keys + wrapped uint32 value sums + label sums modulo 2^label_width -----------------------------
+size_t     reduce_triples_workspace_bytes(uint64_t n);
+hipError_t launch_reduce_triples_count(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words,
+                                       void *d_ws, hipStream_t st);
+hipError_t launch_reduce_triples_emit(const void *d_keys, const uint32_t *d_vals, const uint64_t *d_labs, uint64_t n, uint32_t key_words,
+                                      uint32_t label_width, void *d_ws, void *d_out_keys, uint32_t *d_out_vals, uint64_t *d_out_labs,
+                                      hipStream_t st);
+
 }  // namespace mgc

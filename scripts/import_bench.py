@@ -10,8 +10,13 @@
     database: wall clock, text GB/s, and per run the time the text took to arrive over the host link (upload_ms) next to the
     device stages (parse + sort + reduce) -- the design wants the second to hide behind the first.  Once with the default
     batch size and once with MGC_IMPORT_BATCH = BATCH_MB so that the run store and its merge are in the path; and once through the CLI.
+  * the labelled leg (include/meryl_import_labelled.h), over the same k-mers: triple_sort / reduce_triples -- mgc_dev_sort_triples
+    and mgc_dev_reduce_triples_* over the keys and values of pair_sort / reduce plus a uint64 label each, with the pair times
+    beside them; import_labelled -- the same printed text with a third column (an 8-bit label) through mgc_import_labelled_file,
+    and import_labelled_vs_pairs -- the device times of parse, sort and reduce, triples against pairs, from the default runs.
 
-usage: python scripts/import_bench.py [READS_M] [PAIRS_M] [--dir DIR] [--batch-mb N] >> profiles/import_bench.jsonl"""
+usage: python scripts/import_bench.py [READS_M] [PAIRS_M] [--dir DIR] [--batch-mb N] >> profiles/import_bench.jsonl
+       (profiles/import_bench_labelled.jsonl holds a run of this script beside one of the commit before the labelled leg)"""
 import ctypes
 import json
 import os
@@ -118,7 +123,38 @@ for kw, bits, n in ((1, 42, pairs), (2, 102, pairs // 2)):
 
     med_r, ms_r = timed(reduce_step)
     emit(what="reduce", key_bytes=8 * kw, n=n, distinct=nd.value, ms=round(med_r, 3), pairs_per_s=round(n / med_r * 1e3), samples_ms=ms_r)
-    del src, vals, keys, alt, v, av, ws_p, ws_k, ws_r
+    # the labelled leg: the same keys and values with a uint64 label each
+    labs = torch.randint(0, 1 << 62, (n,), generator=g, device=dev, dtype=torch.int64)
+    lb, alb = torch.empty_like(labs), torch.empty_like(labs)
+    ws_t = torch.empty(L_.mgc_dev_sort_triples_workspace_bytes(n), dtype=torch.uint8, device=dev)
+
+    def refill3():
+        refill()
+        lb.copy_(labs)
+
+    def sort3():
+        capi.check(L_.mgc_dev_sort_triples(ptr(keys), ptr(v), ptr(lb), ptr(alt), ptr(av), ptr(alb), n, kw, 0, bits, ptr(ws_t), ws_t.numel(),
+                                           ctypes.byref(ia), sp), "sort_triples")
+
+    med_t, ms_t = timed(sort3, refill3)
+    emit(what="triple_sort", key_bytes=8 * kw, bits=bits, n=n, triples_ms=round(med_t, 3), pairs_ms=round(med_p, 3), ratio=round(med_t / med_p, 3),
+         triples_per_s=round(n / med_t * 1e3), triples_samples_ms=ms_t)
+    refill3()
+    (keys if kw == 1 else keys[:, 0]).div_(3, rounding_mode="floor")
+    sort3()
+    sk, sv, sl = (alt, av, alb) if ia.value else (keys, v, lb)
+    ok, ov, ol = (keys, v, lb) if ia.value else (alt, av, alb)
+    ws_r3 = torch.empty(L_.mgc_dev_reduce_triples_workspace_bytes(n), dtype=torch.uint8, device=dev)
+
+    def reduce3():
+        capi.check(L_.mgc_dev_reduce_triples_count(ptr(sk), ptr(sv), ptr(sl), n, kw, ptr(ws_r3), ws_r3.numel(), ctypes.byref(nd), sp), "reduce3_count")
+        capi.check(L_.mgc_dev_reduce_triples_emit(ptr(sk), ptr(sv), ptr(sl), n, kw, 64, ptr(ws_r3), ws_r3.numel(), ptr(ok), ptr(ov), ptr(ol), sp),
+                   "reduce3_emit")
+
+    med_r3, ms_r3 = timed(reduce3)
+    emit(what="reduce_triples", key_bytes=8 * kw, n=n, distinct=nd.value, triples_ms=round(med_r3, 3), pairs_ms=round(med_r, 3),
+         ratio=round(med_r3 / med_r, 3), triples_per_s=round(n / med_r3 * 1e3), samples_ms=ms_r3)
+    del src, vals, keys, alt, v, av, ws_p, ws_k, ws_r, labs, lb, alb, ws_t, ws_r3
     torch.cuda.empty_cache()
 
 # ---- `meryl print` of a k = 21 count -> database ------------------------------------------------------------------------
@@ -139,7 +175,9 @@ text_bytes = os.path.getsize(txt)
 emit(what="import_input", k=K, kmers=n_distinct, text_bytes=text_bytes, bytes_per_record=round(text_bytes / max(1, n_distinct), 2), dir=work)
 
 
-def import_runs(tag, env_batch):
+def import_runs(tag, env_batch, path=None, label_width=0):
+    path = path or txt
+    n_bytes = os.path.getsize(path)
     if env_batch:
         os.environ["MGC_IMPORT_BATCH"] = str(env_batch)
     else:
@@ -149,22 +187,33 @@ def import_runs(tag, env_batch):
         out = os.path.join(work, "b.meryl")
         shutil.rmtree(out, ignore_errors=True)
         t0 = time.perf_counter()
-        info = kmer_import.import_file(txt, K, out, host_threads=16)
+        info = kmer_import.import_file(path, K, out, host_threads=16, **({"label_width": label_width} if label_width else {}))
         info["wall_s"] = time.perf_counter() - t0
         if rep:
             runs.append(info)
     med = sorted(runs, key=lambda r: r["wall_s"])[len(runs) // 2]
     device_ms = med["parse_ms"] + med["sort_ms"] + med["reduce_ms"]
-    emit(what="import", mode=tag, batches=med["n_batches"], records=med["n_records"], distinct=med["n_distinct"],
-         wall_s=round(med["wall_s"], 3), text_gb_per_s=round(text_bytes / med["wall_s"] / 1e9, 3),
-         upload_ms=round(med["upload_ms"], 3), upload_gb_per_s=round(text_bytes / max(med["upload_ms"], 1e-9) / 1e6, 2),
+    emit(what="import_labelled" if label_width else "import", mode=tag, batches=med["n_batches"], records=med["n_records"], distinct=med["n_distinct"],
+         wall_s=round(med["wall_s"], 3), text_gb_per_s=round(n_bytes / med["wall_s"] / 1e9, 3),
+         upload_ms=round(med["upload_ms"], 3), upload_gb_per_s=round(n_bytes / max(med["upload_ms"], 1e-9) / 1e6, 2),
          parse_ms=round(med["parse_ms"], 3), sort_ms=round(med["sort_ms"], 3), reduce_ms=round(med["reduce_ms"], 3),
          device_ms=round(device_ms, 3), device_over_upload=round(device_ms / max(med["upload_ms"], 1e-9), 3),
          read_s=round(med["read_s"], 3), write_s=round(med["write_s"], 3), samples_wall_s=[round(r["wall_s"], 3) for r in runs])
+    return med
 
 
-import_runs("default", 0)
+pairs_run = import_runs("default", 0)
 import_runs("batches", batch_mb << 20)
+# the labelled leg: the same lines with a third column, the line number modulo 256 as an 8-bit label
+txt3 = os.path.join(work, "a3.txt")
+with open(txt3, "wb") as f:
+    subprocess.run(["awk", '{print $0 "\t" (NR % 256)}', txt], check=True, stdout=f)
+triples_run = import_runs("default", 0, txt3, 8)
+import_runs("batches", batch_mb << 20, txt3, 8)
+emit(what="import_labelled_vs_pairs", k=K, records=triples_run["n_records"], label_width=8,
+     **{"%s_ms" % stage: {"triples": round(triples_run["%s_ms" % stage], 3), "pairs": round(pairs_run["%s_ms" % stage], 3),
+                          "ratio": round(triples_run["%s_ms" % stage] / max(pairs_run["%s_ms" % stage], 1e-9), 3)}
+        for stage in ("parse", "sort", "reduce")})
 os.environ.pop("MGC_IMPORT_BATCH", None)
 times = []
 for rep in range(3):
