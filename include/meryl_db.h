@@ -391,6 +391,25 @@ int mgc_db_eval_reported(const mgc_eval_node_assigned *nodes, uint32_t n_nodes, 
                          mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads,
                          const uint8_t *want_hist /*[n_nodes]*/, mgc_value_hist **hists /*[n_nodes], out*/);
 
+/* mgc_db_eval_reported with LISTS: want_list[v] != 0 asks for the text of node v's result -- the lines of include/meryl_list.h
+ * (printKmer, src/meryl2/merylOp-nextMer.C:24-50: what `output:list=<file>` and `output:show` write for any action,
+ * src/meryl2/merylCommandBuilder-processText.C:149-150,358-359, merylOpTemplate.C:76-163), with the label column when the
+ * evaluation's outputs carry labels (label_size, or the largest label size among the leaves, above 0).  After node v's slice is
+ * ready its k-mers are formatted on the device and list_cb(list_user, v, file, text, n_bytes) receives the text of slice `file` in
+ * pieces of whole lines (n_bytes > 0; valid during the call): from the calling thread, in evaluation order, files ascending,
+ * pieces in order; an empty slice makes no call.  A nonzero return stops the evaluation (MGC_ESTATE).  One pair of staging
+ * buffers serves all flagged nodes; a piece holds at most 16 MiB (MGC_LIST_CHUNK, bytes, overrides it for tests; never less than
+ * one line).  Leaves may be flagged -- a tree whose root is a leaf lists a database.
+ * want_list == NULL, or no node flagged: exactly mgc_db_eval_reported -- the same routes, the same outputs byte for byte.
+ * Checked with everything mgc_db_eval_reported checks, before any device call and before any output directory exists
+ * (MGC_EINVAL with text): a node flagged and list_cb NULL; want_list set on a node the root does not reach. */
+typedef int (*mgc_eval_list_cb)(void *user, uint32_t node, uint32_t file, const void *text, uint64_t n_bytes);
+int mgc_db_eval_listed(const mgc_eval_node_assigned *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
+                       uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
+                       mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads,
+                       const uint8_t *want_hist /*[n_nodes]*/, mgc_value_hist **hists /*[n_nodes], out*/,
+                       const uint8_t *want_list /*[n_nodes]*/, mgc_eval_list_cb list_cb, void *list_user);
+
 /* The `statistics` report of a histogram as text (src/meryl/merylOp-histogram.C:65-93): the four header lines, the column
  * titles and one row per pair.  Host only.  Returns the length of the text (without the final NUL); up to buf_size - 1
  * characters of it and a NUL are written to buf (buf may be NULL with buf_size 0: the length alone). */

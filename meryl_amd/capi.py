@@ -40,7 +40,10 @@ SYMBOLS = (
     "mdb_free", "mgc_write_database", "mgc_write_database_profiled",
     "mgc_db_stream_open", "mgc_db_stream_write", "mgc_db_stream_write_labelled", "mgc_db_eval_labelled", "mgc_db_eval_selected", "mgc_db_eval_assigned", "mgc_db_eval_reported", "mgc_db_stream_sync", "mgc_db_stream_close", "mgc_db_stream_error", "mgc_db_stream_queued", "mgc_db_stream_done", "mgc_db_stream_wait_buffers",
     "mgc_value_hist_open", "mgc_value_hist_add", "mgc_value_hist_len", "mgc_value_hist_get", "mgc_value_hist_totals", "mgc_value_hist_close",
-    "mgc_value_hist_geometry", "mdb_format_statistics",
+    "mgc_value_hist_geometry", "mdb_format_statistics", "mgc_db_eval_listed",
+    # include/meryl_list.h
+    "mgc_list_max_line", "mgc_list_tile_kmers", "mgc_list_slice_name", "mgc_list_kmers",
+    "mgc_dev_list_workspace_bytes", "mgc_dev_list_lengths", "mgc_dev_list_format",
     "mgc_runs_open", "mgc_runs_add", "mgc_runs_write", "mgc_runs_get_profile", "mgc_runs_error", "mgc_runs_close", "mgc_get_runs_profile", "mgc_db_merge", "mgc_db_filter", "mgc_db_eval", "mgc_count_node", "mgc_count_node_batched", "mgc_count_node_staged", "mgc_node_plan",
     # include/meryl_lookup.h
     "mgc_lookup_load", "mgc_lookup_estimate", "mgc_lookup_from_device", "mgc_lookup_free", "mgc_lookup_get_info", "mgc_lookup_error",
@@ -347,6 +350,8 @@ BLOCK_CB2 = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, cty
                              ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                              ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64)
 # mgc_lookup_write_cb (include/meryl_lookup.h): (data, n, user) -> 0 to go on
+LIST_WRITE_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
+EVAL_LIST_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64)
 LOOKUP_WRITE_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
 BLOCK_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
@@ -539,6 +544,15 @@ def lib():
     sig("mgc_db_eval_assigned", i32, P(EvalNodeAssigned), u32, P(u32), u32, u32, P(SelectTerm), u32, i32, u32, EVAL_SLICE_LABELLED_CB, vp, i32, i32)
     sig("mgc_db_eval_reported", i32, P(EvalNodeAssigned), u32, P(u32), u32, u32, P(SelectTerm), u32, i32, u32, EVAL_SLICE_LABELLED_CB, vp, i32, i32,
         P(ctypes.c_uint8), P(vp))
+    sig("mgc_db_eval_listed", i32, P(EvalNodeAssigned), u32, P(u32), u32, u32, P(SelectTerm), u32, i32, u32, EVAL_SLICE_LABELLED_CB, vp, i32, i32,
+        P(ctypes.c_uint8), P(vp), P(ctypes.c_uint8), EVAL_LIST_CB, vp)
+    sig("mgc_list_max_line", u32, u32, u32)
+    sig("mgc_list_tile_kmers", u32, u32, u32)
+    sig("mgc_list_slice_name", sz, ctypes.c_char_p, u32, ctypes.c_char_p, sz)
+    sig("mgc_list_kmers", i32, vp, vp, vp, u64, u32, u32, u64, LIST_WRITE_CB, vp, vp)
+    sig("mgc_dev_list_workspace_bytes", sz, u64, u32, u32)
+    sig("mgc_dev_list_lengths", i32, vp, u64, u32, u32, vp, sz, P(u64), vp)
+    sig("mgc_dev_list_format", i32, vp, vp, vp, u64, u32, u32, vp, sz, vp, vp)
     sig("mgc_value_hist_open", vp, i32)
     sig("mgc_value_hist_add", i32, vp, vp, u64, vp)
     sig("mgc_value_hist_len", i32, vp, P(u64))

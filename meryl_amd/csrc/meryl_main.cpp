@@ -29,9 +29,13 @@
 // operation, whose tree is then evaluated once with the value histogram of its root collected on the device (mgc_db_eval_reported);
 // meryl2's `output:histogram[=file]` and `output:statistics[=file]` (merylCommandBuilder-processText.C:153-154,
 // merylOpTemplate.C:168-209,285-307) ask the same of any set or value operation of a tree, to a file or (no file, or `-`) stdout.
-// What stays refused: compare, ploidy, noise, printACGT, Canu sequence stores (segment=); CRAM only when no `samtools` is on the PATH.
+// `print [operation]` of a tree without reports is the list of the tree's root (include/meryl_list.h): the lines are formatted on the
+// device while the tree runs (mgc_db_eval_listed) and only text crosses to the host; a tree that also collects reports keeps
+// mgc_db_eval_reported and its slice callback, and `print <db>` the host reader, which needs no device.
+// What stays refused: output:list= and output:show, compare, ploidy, noise, printACGT, Canu sequence stores (segment=); CRAM only when no `samtools` is on the PATH.
 #include "../../include/meryl_db.h"
 #include "../../include/meryl_gpu_count.h"
+#include "../../include/meryl_list.h"
 #include "../../include/meryl_seq.h"
 
 #include <hip/hip_runtime_api.h>
@@ -836,6 +840,9 @@ void print_slice_labelled(void *ctx, uint32_t, const uint64_t *lo, const uint64_
   print_kmers(pc->k, pc->label_size, lo, hi, values, labels, n);
 }
 
+// mgc_db_eval_listed's callback of `print [operation]`: a piece of the root's text, files ascending, pieces in order
+int print_text(void *, uint32_t, uint32_t, const void *text, uint64_t n) { return fwrite(text, 1, n, stdout) == n ? 0 : 1; }
+
 // the nodes as a narrower public struct: the fields it names, copied
 template <typename T>
 std::vector<T> narrowed(const std::vector<mgc_eval_node_assigned> &nodes) {
@@ -893,7 +900,16 @@ int run_tree(const Globals &g, const std::vector<Operation> &ops, int root, bool
   if (with_labels) pc.label_size = g.label_size_given && g.label_size ? g.label_size : t.leaf_label_size;
   int rc;
   std::vector<mgc_value_hist *> hists(t.nodes.size(), nullptr);
-  if (!reports.empty())                                        // a report somewhere: the widest entry point, which collects them
+  if (print && reports.empty()) {                              // the root's text, formatted on the device; no slice leaves it as arrays
+    std::vector<uint8_t> want_list(t.nodes.size(), 0);
+    want_list[r] = 1;
+    rc = mgc_db_eval_listed(t.nodes.data(), n_nodes, children.data(), n_children, r, t.terms.data(), n_terms, with_labels ? 1 : 0, label_size,
+                            nullptr, nullptr, -1, (int)g.threads, nullptr, nullptr, want_list.data(), print_text, nullptr);
+  }
+  // a report somewhere: the entry point that collects them -- also under `print`, whose lines then come from the slice callback as before:
+  // mgc_db_eval_listed could take want[] and hists[] as well, but what that form says when it fails without a device is pinned to name
+  // mgc_db_eval_reported (tests/test_value_hist_host.py)
+  else if (!reports.empty())
     rc = mgc_db_eval_reported(t.nodes.data(), n_nodes, children.data(), n_children, r, t.terms.data(), n_terms, with_labels ? 1 : 0, label_size,
                               print ? print_slice_labelled : nullptr, &pc, -1, (int)g.threads, want.data(), hists.data());
   else if (t.value_words)                                      // a value= somewhere: the tree through mgc_db_eval_assigned
@@ -1135,6 +1151,10 @@ int main(int argc, char **argv) {
     for (; closing > 0 && !stack.empty(); closing--) stack.pop_back();       // terminateOperation(), :86-93
   }
   if (expect_output_name) die("ERROR: 'output' needs a database name.");
+  // print writes text by the gigabyte: a pipe or a file takes it in 1 MiB writes instead of stdio's 4 KiB ones (nothing has been written to
+  // stdout yet); a terminal stays line buffered, and the other verbs keep stdio's buffer
+  if (!isatty(STDOUT_FILENO) && std::any_of(ops.begin(), ops.end(), [](const Operation &op) { return op.kind == OP_PRINT; }))
+    setvbuf(stdout, nullptr, _IOFBF, 1 << 20);
 
   if (g.verbosity > 0) {
     size_t n_trees = 0;

@@ -1,9 +1,11 @@
 // mgc_eval.cpp -- operations over whole databases (include/meryl_db.h): mgc_db_merge, mgc_db_filter, and the operation trees of
-// mgc_db_eval, mgc_db_eval_labelled, mgc_db_eval_selected, mgc_db_eval_assigned and mgc_db_eval_reported.  Inputs are decoded on the device, every
-// operation is a count / emit pass pair over slices in HBM, and outputs go through the database stream (mgc_stream.cpp).
+// mgc_db_eval, mgc_db_eval_labelled, mgc_db_eval_selected, mgc_db_eval_assigned, mgc_db_eval_reported and mgc_db_eval_listed.  Inputs are decoded on the device, every
+// operation is a count / emit pass pair over slices in HBM, and outputs go through the database stream (mgc_stream.cpp).  mgc_db_eval_listed
+// also hands the flagged nodes' results to the text lister (mgc_list.hip).
 #include "../../include/meryl_db.h"
 #include "mdb_layout.h"
 #include "mgc_dbfile.hpp"
+#include "mgc_list.hpp"
 #include "mgc_session.hpp"
 #include "mgc_route.hpp"
 #include "mgc_selector.hpp"
@@ -314,9 +316,10 @@ struct Node {
   int32_t     value_assign = MGC_ASSIGN_NONE;
   uint64_t    value_constant = 0;
   bool        want_hist = false;                      // mgc_db_eval_reported: the value histogram of the node's result
+  bool        want_list = false;                      // mgc_db_eval_listed: the text of the node's result
 };
 
-// one evaluation, as any of the five entry points states it
+// one evaluation, as any of the six entry points states it
 struct Eval {
   const char *who;                                   // the entry point, for messages
   std::vector<Node> nodes;
@@ -328,6 +331,8 @@ struct Eval {
   mgc_eval_slice_labelled_cb lcb = nullptr;          //   the one that also takes labels (zeros when they do not travel)
   void    *ctx = nullptr;
   mgc_value_hist **hists = nullptr;                  // [n_nodes], out: the accumulators of the nodes with want_hist
+  mgc_eval_list_cb list_cb = nullptr;                // receives the text of the nodes with want_list
+  void    *list_user = nullptr;
 };
 
 template <typename T>
@@ -346,7 +351,7 @@ std::vector<Node> to_nodes(const T *src, uint32_t n) {
   return out;
 }
 
-// the five entry points: one walk, one validation, one slice loop
+// the six entry points: one walk, one validation, one slice loop
 int eval_impl(const Eval &E, int device, int host_threads) {
   const char *who = E.who;
   const std::vector<Node> &nodes = E.nodes;
@@ -358,6 +363,8 @@ int eval_impl(const Eval &E, int device, int host_threads) {
   if (root >= n_nodes || (n_children && !children)) return bad("bad arguments");
   for (uint32_t v = 0; v < n_nodes; v++)
     if (nodes[v].want_hist && !E.hists) return bad("node " + std::to_string(v) + ": a histogram is wanted but there is nowhere to return it");
+  for (uint32_t v = 0; v < n_nodes; v++)
+    if (nodes[v].want_list && !E.list_cb) return bad("node " + std::to_string(v) + ": a list is wanted but there is no callback to receive it");
   // ---- the tree: every node reached at most once, from the root (post-order = evaluation order)
   std::vector<uint32_t> order, leaves;
   {
@@ -419,6 +426,8 @@ int eval_impl(const Eval &E, int device, int host_threads) {
     }
     for (uint32_t v = 0; v < n_nodes; v++)
       if (nodes[v].want_hist && !seen[v]) return bad("node " + std::to_string(v) + ": a histogram is wanted of a node the root does not reach");
+    for (uint32_t v = 0; v < n_nodes; v++)
+      if (nodes[v].want_list && !seen[v]) return bad("node " + std::to_string(v) + ": a list is wanted of a node the root does not reach");
   }
   // ---- outputs: named once, and not an input
   {
@@ -471,6 +480,12 @@ int eval_impl(const Eval &E, int device, int host_threads) {
   }
   for (uint32_t v : order)
     if (nodes[v].want_hist && rc == MGC_OK) ev[v].hist = mgc_value_hist_open(device);
+  // the lists: one pair of staging buffers for all flagged nodes; pieces of MGC_LIST_CHUNK bytes (tests), at least one line
+  struct ListTo { mgc_eval_list_cb cb; void *user; uint32_t node, file; };
+  std::unique_ptr<mgc::ListStage, void (*)(mgc::ListStage *)> list_stage(nullptr, mgc::list_stage_close);
+  uint64_t list_chunk = 16ull << 20;
+  if (const char *e = getenv("MGC_LIST_CHUNK")) { if (*e) list_chunk = strtoull(e, nullptr, 10); }
+  list_chunk = std::max<uint64_t>(list_chunk, mgc_list_max_line(k, label_size));
   hipStream_t st = nullptr;
   std::vector<DBuf> in_k(n_leaves), in_c(n_leaves), in_l(labels ? n_leaves : 0);
   DBuf ws;
@@ -550,6 +565,16 @@ int eval_impl(const Eval &E, int device, int host_threads) {
         rc = mgc_value_hist_add(me.hist, me.res.c, me.res.n, st);
         if (rc != MGC_OK) { msg = who_colon + mgc_db_stream_error(nullptr); break; }
       }
+      if (nodes[v].want_list) {                              // the result's text, formatted where it lies
+        if (!list_stage) list_stage.reset(mgc::list_stage_open());
+        ListTo to{E.list_cb, E.list_user, v, ff};
+        rc = mgc::list_kmers(list_stage.get(), me.res.k, me.res.c, label_size ? me.res.l : nullptr, me.res.n, k, label_size, list_chunk,
+                             [](const void *text, uint64_t n, void *u) {
+                               const ListTo *t = static_cast<const ListTo *>(u);
+                               return t->cb(t->user, t->node, t->file, text, n);
+                             }, &to, st, who);
+        if (rc != MGC_OK) { msg = mgc_db_stream_error(nullptr); break; }
+      }
     }
     if (rc != MGC_OK) break;
     if (E.cb || E.lcb) {
@@ -582,6 +607,7 @@ int eval_impl(const Eval &E, int device, int host_threads) {
   }
   // an output whose node failed mid-slice may still be encoding from buffers about to go
   if (rc != MGC_OK) for (uint32_t v : order) if (ev[v].out) (void)mgc_db_stream_sync(ev[v].out);
+  list_stage.reset();
   if (st) (void)hipStreamDestroy(st);
   close_readers();
   for (uint32_t v : order) {
@@ -665,5 +691,21 @@ extern "C" int mgc_db_eval_reported(const mgc_eval_node_assigned *nodes, uint32_
   E.hists = hists;
   if (hists) for (size_t v = 0; v < E.nodes.size(); v++) hists[v] = nullptr;       // on failure no handle is returned
   if (want_hist) for (size_t v = 0; v < E.nodes.size(); v++) E.nodes[v].want_hist = want_hist[v] != 0;
+  return eval_impl(E, device, host_threads);
+}
+
+// the same tree with lists (include/meryl_db.h, include/meryl_list.h): the flagged nodes' results of every slice go through the text
+// lister (mgc_list.hip) to the callback; nothing else differs from mgc_db_eval_reported
+extern "C" int mgc_db_eval_listed(const mgc_eval_node_assigned *nodes, uint32_t n_nodes, const uint32_t *children, uint32_t n_children,
+                                  uint32_t root, const mgc_select_term *terms, uint32_t n_terms, int with_labels, uint32_t label_size,
+                                  mgc_eval_slice_labelled_cb cb, void *ctx, int device, int host_threads, const uint8_t *want_hist,
+                                  mgc_value_hist **hists, const uint8_t *want_list, mgc_eval_list_cb list_cb, void *list_user) {
+  Eval E{"mgc_db_eval_listed", to_nodes(nodes, n_nodes), children, n_children, root};
+  E.terms = terms; E.n_terms = n_terms; E.label_size = label_size; E.lcb = cb; E.ctx = ctx;
+  E.labels = labels_asked(E, with_labels);
+  E.hists = hists; E.list_cb = list_cb; E.list_user = list_user;
+  if (hists) for (size_t v = 0; v < E.nodes.size(); v++) hists[v] = nullptr;       // on failure no handle is returned
+  if (want_hist) for (size_t v = 0; v < E.nodes.size(); v++) E.nodes[v].want_hist = want_hist[v] != 0;
+  if (want_list) for (size_t v = 0; v < E.nodes.size(); v++) E.nodes[v].want_list = want_list[v] != 0;
   return eval_impl(E, device, host_threads);
 }

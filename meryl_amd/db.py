@@ -192,21 +192,22 @@ def _walk(tree, allowed):
     """The one tree walk: `tree` is a database path, or (word, *children) for the merge operations, or (word, constant, child) for
     the value operations; a dict as the last element holds the node's options, of which only `allowed` are taken.
     -> ([node record], [children], root index); a record is a dict of kind, op, constant, path, first, n and the raw options
-    label, select, value (None where not given) and histogram (a bool); children come before their parent.  A database is flagged
-    for a histogram as ({"database": path, "histogram": True})."""
+    label, select, value (None where not given), histogram and list (bools); children come before their parent.  A database is
+    flagged for a histogram or a list as ({"database": path, "histogram": True, "list": True})."""
     nodes, kids = [], []
 
     def add(t):
         if isinstance(t, dict):                                     # a database with options: {"database": path, "histogram": True}
-            unknown = sorted(set(t) - {"database", "histogram"})
-            if unknown or "database" not in t or "histogram" not in allowed:
-                raise ValueError("a database with options is {'database': path, 'histogram': bool}: %r" % (t,))
+            flags = {"histogram", "list"} & set(allowed)             # what this entry point lets a database carry
+            if set(t) - {"database"} - flags or "database" not in t or not flags:
+                raise ValueError("a database with options is {'database': path, 'histogram': bool%s}: %r" % (", 'list': bool" if "list" in flags else "", t))
             i = add(t["database"])
-            nodes[i]["histogram"] = bool(t["histogram"]) if "histogram" in t else False
+            nodes[i]["histogram"] = bool(t.get("histogram"))
+            nodes[i]["list"] = bool(t.get("list"))
             return i
         if isinstance(t, (str, bytes)):
             nodes.append(dict(kind=capi.NODE_DATABASE, op=0, constant=0, path=t if isinstance(t, bytes) else t.encode(), first=0, n=0,
-                              label=None, select=None, value=None, histogram=False))
+                              label=None, select=None, value=None, histogram=False, list=False))
             return len(nodes) - 1
         t = tuple(t)
         opts = {}
@@ -230,7 +231,7 @@ def _walk(tree, allowed):
         ch = [add(a) for a in args]
         out, words = opts.get("output"), opts.get("select")
         nodes.append(dict(kind=kind, op=op, constant=constant, path=None if out is None else (out if isinstance(out, bytes) else out.encode()),
-                          first=len(kids), n=len(ch), label=opts.get("label"), value=opts.get("value"), histogram=bool(opts.get("histogram")),
+                          first=len(kids), n=len(ch), label=opts.get("label"), value=opts.get("value"), histogram=bool(opts.get("histogram")), list=bool(opts.get("list")),
                           select=None if words is None else ([words] if isinstance(words, str) else list(words))))
         kids.extend(ch)
         return len(nodes) - 1
@@ -442,6 +443,11 @@ def evaluate_reported(tree, on_slice=None, with_labels=False, label_size=0, devi
     _evaluate("mgc_db_eval_reported",
               lambda cb: capi.lib().mgc_db_eval_reported(arr, len(arr), kids, n_kids, root, terms, n_terms, int(bool(with_labels)), int(label_size), cb,
                                                          None, device, host_threads, want, hists), on_slice)
+    return _read_hists(arr, kids, root, want, hists)
+
+
+def _read_hists(arr, kids, root, want, hists):
+    """the accumulators an evaluation returned -> [(values, occurrences)] for the flagged nodes in pre-order; closes them"""
     order = []
 
     def pre(v):
@@ -456,3 +462,111 @@ def evaluate_reported(tree, on_slice=None, with_labels=False, label_size=0, devi
             out.append(h.get())
             h.close()
     return out
+
+
+def build_tree_listed(tree):
+    """build_tree_reported for mgc_db_eval_listed: the options dict of a node also takes "list": True -- the text of that node's
+    result is handed over; a database is flagged as {"database": path, "list": True}.
+    -> (..., want-histogram array, want-list array)"""
+    allowed = ("output", "label", "select", "value", "histogram", "list")
+    filled = _fill(capi.EvalNodeAssigned, tree, allowed)
+    flags = lambda key: (ctypes.c_uint8 * len(filled[6]))(*[1 if r[key] else 0 for r in filled[6]])      # noqa: E731
+    return filled[:6] + (flags("histogram"), flags("list"))
+
+
+def list_geometry(k, label_size=0):
+    """(the longest line in bytes, the k-mers of one tile of the list kernels) for (k, label_size)"""
+    return capi.lib().mgc_list_max_line(int(k), int(label_size)), capi.lib().mgc_list_tile_kmers(int(k), int(label_size))
+
+
+def list_slice_name(name, file):
+    """the list file of slice `file` for a name with '#' (mgc_list_slice_name); None for a name without"""
+    raw = name.encode() if isinstance(name, str) else bytes(name)
+    buf = ctypes.create_string_buffer(len(raw) + 80)
+    n = capi.lib().mgc_list_slice_name(raw, int(file), buf, len(buf))
+    return buf.raw[:n].decode() if n else None
+
+
+LIST_CHUNK = 16 << 20
+
+
+def format_kmers_device(keys, values, labels=None, *, k, label_size=0):
+    """format_kmers that leaves the text on the device: -> a uint8 CUDA tensor (mgc_dev_list_lengths + mgc_dev_list_format)"""
+    import torch
+    L, n = capi.lib(), values.numel()
+    stream = torch.cuda.current_stream(values.device).cuda_stream
+    ws = torch.empty(max(L.mgc_dev_list_workspace_bytes(n, int(k), int(label_size)), 8), dtype=torch.uint8, device=values.device)
+    total = ctypes.c_uint64(0)
+    rc = L.mgc_dev_list_lengths(values.data_ptr() if n else None, n, int(k), int(label_size), ws.data_ptr(), ws.numel(), ctypes.byref(total), stream)
+    text = torch.empty(total.value, dtype=torch.uint8, device=values.device)
+    if rc == 0 and n:
+        rc = L.mgc_dev_list_format(keys.data_ptr(), values.data_ptr(), labels.data_ptr() if labels is not None else None, n, int(k), int(label_size),
+                                   ws.data_ptr(), ws.numel(), text.data_ptr(), stream)
+    if rc != 0:
+        msg = L.mgc_db_stream_error(None)
+        raise capi.MgcError(rc, "mgc_dev_list_format", msg.decode("utf-8", "replace") if msg else "")
+    return text
+
+
+def format_kmers(keys, values, labels=None, *, k, label_size=0, chunk_bytes=LIST_CHUNK, on_piece=None):
+    """The text of device-resident k-mers (mgc_list_kmers): keys a contiguous CUDA tensor of 8-byte integers, one per k-mer for
+    k <= 32 and (lo, hi) pairs for k > 32; values 4-byte integers; labels 8-byte integers or None (zeros).  -> bytes: the lines
+    `k-mer <TAB> value [<TAB> label] <NL>`.  on_piece(bytes) sees every piece as it leaves the device (at most chunk_bytes each,
+    whole lines); a true return stops the listing (MgcError, MGC_ESTATE)."""
+    import torch
+    n = values.numel()
+    tensors = [("keys", keys, 8, n * (2 if k > 32 else 1)), ("values", values, 4, n)] + ([("labels", labels, 8, n)] if labels is not None else [])
+    for name, t, size, count in tensors:
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != size or t.numel() != count:
+            raise ValueError("format_kmers: %s must be a contiguous device tensor of %d %d-byte integers" % (name, count, size))
+    pieces, failure = [], []
+
+    def trampoline(text, nbytes, user):
+        try:
+            piece = ctypes.string_at(text, nbytes)
+            pieces.append(piece)
+            return 1 if on_piece is not None and on_piece(piece) else 0
+        except BaseException as e:                               # not through the C frames
+            failure.append(e)
+            return 1
+
+    stream = torch.cuda.current_stream(values.device).cuda_stream
+    with torch.cuda.device(values.device):
+        rc = capi.lib().mgc_list_kmers(keys.data_ptr() if n else None, values.data_ptr() if n else None,
+                                       labels.data_ptr() if labels is not None and n else None, n, int(k), int(label_size), int(chunk_bytes),
+                                       capi.LIST_WRITE_CB(trampoline), None, stream)
+    if failure:
+        raise failure[0]
+    if rc != 0:
+        msg = capi.lib().mgc_db_stream_error(None)
+        raise capi.MgcError(rc, "mgc_list_kmers", msg.decode("utf-8", "replace") if msg else "")
+    return b"".join(pieces)
+
+
+def evaluate_listed(tree, on_text, on_slice=None, with_labels=False, label_size=0, device=-1, host_threads=8):
+    """evaluate_reported() that also lists results as text (mgc_db_eval_listed): every node given {"list": True} (a database:
+    {"database": path, "list": True}) has the k-mers of its result formatted on the device, slice by slice, and
+    on_text(node_index, file, bytes) receives the text in pieces of whole lines -- node_index in the order of build_tree_listed
+    (children before their parent), files ascending.  -> the histograms of the flagged nodes, as evaluate_reported."""
+    arr, kids, n_kids, root, terms, n_terms, want, want_list = build_tree_listed(tree)
+    hists = (ctypes.c_void_p * len(arr))()
+    failure = []
+
+    def text_trampoline(user, node, ff, text, nbytes):
+        try:
+            on_text(node, ff, ctypes.string_at(text, nbytes))
+            return 0
+        except BaseException as e:                               # not through the C frames
+            failure.append(e)
+            return 1
+
+    list_cb = capi.EVAL_LIST_CB(text_trampoline) if on_text is not None else ctypes.cast(None, capi.EVAL_LIST_CB)
+    try:
+        _evaluate("mgc_db_eval_listed",
+                  lambda cb: capi.lib().mgc_db_eval_listed(arr, len(arr), kids, n_kids, root, terms, n_terms, int(bool(with_labels)), int(label_size), cb,
+                                                           None, device, host_threads, want, hists, want_list, list_cb, None), on_slice)
+    except capi.MgcError:
+        if failure:
+            raise failure[0]
+        raise
+    return _read_hists(arr, kids, root, want, hists)
