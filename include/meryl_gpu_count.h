@@ -548,6 +548,32 @@ int mgc_text_record_start(const char *path, int format, uint64_t offset, uint64_
 int mgc_push_text_bgzf_file(mgc_session *s, const char *path, int format, int threads);
 int mgc_is_bgzf_file(const char *path);
 
+/* BAM records instead of text: the INFLATED bytes of a BAM file (SAMv1 4.2: magic, header text, reference names, then records
+ * of block_size + 32 fixed bytes + read name + CIGAR + SEQ packed two bases per byte + qualities + aux), in pieces of any
+ * size.  The host only walks the records -- header fields and the 36 fixed bytes of every record, resumable across pieces --
+ * and checks every length the device will rely on; the bytes are uploaded as they are and a kernel expands the SEQ fields
+ * into the base stream through the nt16 alphabet "=ACMGRSVTWYHKDBN" (SAMv1 4.2), high nibble first: every record's SEQ as
+ * stored, no FLAG filtering, one '.' after every record (a record without SEQ gives just the '.'), as the host reader of
+ * include/meryl_seq.h does.  begin / push / end mirror the text triple and share its one "open file": while a BAM is open,
+ * mgc_push_bases, mgc_begin_text, mgc_count and mgc_staged_bases return MGC_ESTATE.  A damaged stream (bad magic, a negative
+ * l_text / n_ref / l_name / l_seq, block_size < 32, fields longer than the record; at mgc_end_bam: a stream that ends inside
+ * the header or a record) is MGC_EFORMAT from the call that sees it: the file is closed and taken back out of the stream,
+ * mgc_last_error names the fault and the stream offset.  BAM input is batched like pushed bases (a batch may be cut inside a
+ * file, at a '.'): damage found AFTER part of the file was counted is MGC_EINVAL -- nothing can be rolled back then. */
+int mgc_begin_bam(mgc_session *s);
+int mgc_push_bam(mgc_session *s, const void *bam_bytes, size_t len);   /* inflated BAM bytes, any chunking */
+int mgc_end_bam(mgc_session *s);
+/* One whole BGZF BAM file (what samtools, SMRT Link and dorado write): mapped, its blocks inflated (CRC checked) by `threads`
+ * threads (0 = default) straight into the pinned upload buffers, walked, uploaded and decoded in file order.  MGC_EFORMAT: not
+ * BGZF / a corrupt block / a damaged BAM stream (nothing of the file stays in the session unless part of it was already counted
+ * as a batch: MGC_EINVAL then); mgc_last_error names the file.  MGC_EINVAL: the file cannot be opened. */
+int mgc_push_bam_file(mgc_session *s, const char *path, int threads);
+/* The decode alone, device to device, for tests and benchmarks: piece_bytes (< 4 GiB) of inflated BAM at d_piece and n_segments
+ * segments of 16 bytes {uint32 src_off; uint32 n_bases | '.' follows << 31; uint64 out_off} that tile [0, out_bytes) in ascending
+ * order -> out_bytes at d_out (any alignment), on `stream`.  Offsets that point outside the piece read as 0, never outside. */
+int mgc_dev_bam_decode(const uint8_t *d_piece, uint64_t piece_bytes, const void *d_segments, uint64_t n_segments, uint64_t out_bytes,
+                       uint8_t *d_out, void *stream);
+
 /* Bases already resident in HBM (breakers included).  The buffer is borrowed
  * until mgc_count returns.  May be called once per session. */
 int mgc_push_bases_device(mgc_session *s, const uint8_t *d_bases, uint64_t n_bases);

@@ -504,6 +504,31 @@ class Session:
             capi.check(L.mgc_push_text(self._h, piece, len(piece)), "mgc_push_text", self._h)
         capi.check(L.mgc_end_text(self._h), "mgc_end_text", self._h)
 
+    def push_bam(self, data, pieces=None):
+        """One whole BAM file as its INFLATED bytes (magic, header, records): walked on the host, decoded on the device.
+        pieces: optional chunk size, as for push_text.  Raises MgcError(code MGC_EFORMAT) if the stream is damaged (its
+        output is rolled back, the file is closed)."""
+        b = bytes(data)
+        L = capi.lib()
+        capi.check(L.mgc_begin_bam(self._h), "mgc_begin_bam", self._h)
+        step = pieces or max(len(b), 1)
+        for i in range(0, len(b), step):
+            piece = b[i:i + step]
+            capi.check(L.mgc_push_bam(self._h, piece, len(piece)), "mgc_push_bam", self._h)
+        capi.check(L.mgc_end_bam(self._h), "mgc_end_bam", self._h)
+
+    def push_bam_file(self, path, threads=0):
+        """One whole BGZF BAM file, inflated by `threads` threads (0: default) into the upload ring, decoded on the device."""
+        capi.check(capi.lib().mgc_push_bam_file(self._h, os.fsencode(path), int(threads)), "mgc_push_bam_file", self._h)
+
+    def staged_bases(self):
+        """A copy of the base stream staged so far ('.' breakers included) as a uint8 cuda tensor (mgc_staged_bases)."""
+        p, n = ctypes.c_void_p(), ctypes.c_uint64(0)
+        capi.check(capi.lib().mgc_staged_bases(self._h, ctypes.byref(p), ctypes.byref(n)), "mgc_staged_bases", self._h)
+        # the view is complete when mgc_staged_bases returns (it synchronises the session's input stream)
+        from .poslookup import _copy_from_device
+        return _copy_from_device(p, int(n.value), torch.uint8, torch.device("cuda", torch.cuda.current_device()))
+
     def push_bases_device(self, t):
         # the session runs on its own HIP stream: whatever produced `t` on torch's
         # stream must be complete before mgc_count reads it

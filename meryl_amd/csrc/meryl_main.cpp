@@ -244,9 +244,12 @@ void print_configuration(const Globals &g, const Operation &op, uint64_t exp_num
 // one input of a count, or a byte window of it (a plain-text file read by one rank of a node count)
 struct InputPiece { std::string name; uint64_t begin, end; };
 
-// Input: the file's raw text goes to the device and is parsed there (mgc_push_text*); files the device parser refuses
-// (multi-line FASTQ ...), SAM/BAM and MERYL_HOST_PARSER=1 take the host state machine of meryl_seq.cpp.  Returns the
-// bytes / bases taken in (reported with -V -V).
+static bool is_regular_file(const std::string &name) { struct stat st; return stat(name.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
+
+// Input: the file's raw text goes to the device and is parsed there (mgc_push_text*); a BGZF BAM file goes there as its
+// inflated bytes and its SEQ fields are decoded there (mgc_push_bam_file); files the device routes refuse (multi-line
+// FASTQ, a damaged BAM ...), SAM, BAM in plain gzip or on stdin and MERYL_HOST_PARSER=1 take the host state machine of
+// meryl_seq.cpp.  Returns the bytes / bases taken in (reported with -V -V).
 int g_inflate_threads = 16;                                  // threads= of the command line: the BGZF inflaters (readers of plain text: at most 16)
 uint64_t load_inputs(mgc_session *s, const std::vector<InputPiece> &pieces, int reader_threads) {
   const uint64_t buf_max = 2 * 1024 * 1024;                                                            // merylOp-countThreads.C:413
@@ -274,7 +277,19 @@ uint64_t load_inputs(mgc_session *s, const std::vector<InputPiece> &pieces, int 
     if (host_parser && whole) { load_on_host(name); continue; }
     msr_reader *r = msr_open(name.c_str());
     if (!r) die("ERROR: %s", msr_last_error());
-    if (msr_format(r) != MSR_FORMAT_FASTX) { msr_close(r); load_on_host(name); continue; }   // SAM/BAM records are decoded on the host
+    if (msr_format(r) == MSR_FORMAT_BAM && name != "-" && whole && is_regular_file(name) && mgc_is_bgzf_file(name.c_str()) && !getenv("MERYL_BGZF_GENERIC")) {
+      // a BGZF BAM file: the library maps it, inflates its blocks with several threads straight into its pinned upload buffers, walks
+      // the records and decodes their SEQ fields on the device.  A file it refuses is read again on the host, which says what is wrong.
+      msr_close(r);
+      const char *bt = getenv("MERYL_BGZF_THREADS");
+      const int rc = mgc_push_bam_file(s, name.c_str(), bt ? atoi(bt) : std::max(reader_threads, g_inflate_threads));
+      if (rc == MGC_EFORMAT) load_on_host(name);
+      else if (rc != MGC_OK) die("ERROR: %s", mgc_last_error(s));
+      struct stat fst;
+      if (rc == MGC_OK && stat(name.c_str(), &fst) == 0) total_bases += (uint64_t)fst.st_size * 3;   // (a guess, as for bgzip'd text)
+      continue;
+    }
+    if (msr_format(r) != MSR_FORMAT_FASTX) { msr_close(r); load_on_host(name); continue; }   // SAM text, BAM in plain gzip or on stdin: decoded on the host
     if (name != "-" && !has_compressed_suffix(name)) {
       // plain text: the library reads the file itself, several threads straight into its pinned upload buffers
       msr_close(r);

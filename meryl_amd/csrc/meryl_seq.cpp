@@ -23,6 +23,10 @@
 // No record is filtered by its flags -- the reference reads these files through
 // its vendored htslib inside the absent submodule (src/main.mk:92-140), whose
 // call sites are not in the tree, so which records it keeps is unpinned here.
+// A BGZF BAM file given to the CLI no longer comes through here: its records are
+// walked by mgc_bam_walk.hpp and decoded on the device (mgc_push_bam_file), with
+// the same semantics; this reader keeps BAM in plain gzip or on stdin, SAM,
+// MERYL_HOST_PARSER=1, and the files that route refuses (it says what is wrong).
 #include "../../include/meryl_seq.h"
 #include "mgc_bgzf.hpp"
 

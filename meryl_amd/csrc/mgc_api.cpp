@@ -706,6 +706,7 @@ extern "C" void mgc_close(mgc_session *s) {
     if (s->up_ev[i]) (void)hipEventDestroy(s->up_ev[i]);
     if (s->pin[i]) (void)hipHostFree(s->pin[i]);
     if (s->pin_ev[i]) (void)hipEventDestroy(s->pin_ev[i]);
+    if (s->bam_seg_pinned[i]) (void)hipHostFree(s->bam_seg_pinned[i]);
   }
   for (char *&p : s->text_ring) if (p) { (void)hipHostFree(p); p = nullptr; }
   if (s->st_up) { (void)hipStreamSynchronize(s->st_up); (void)hipStreamDestroy(s->st_up); }
@@ -975,7 +976,7 @@ int mgc::text_submit(mgc_session *s, const char *pinned_src, size_t piece) {
 
 extern "C" int mgc_push_text(mgc_session *s, const char *text, size_t len) {
   if (!s || (!text && len)) return MGC_EINVAL;
-  if (!s->text_open) { set_err(&s->err, "mgc_push_text without mgc_begin_text"); return MGC_ESTATE; }
+  if (!s->text_open || s->text_format == mgc_session::TEXT_BAM) { set_err(&s->err, "mgc_push_text without mgc_begin_text"); return MGC_ESTATE; }
   HIP_TRY(s, hipSetDevice(s->device));
   while (len) {
     const size_t piece = len < mgc_session::TEXT_CHUNK ? len : mgc_session::TEXT_CHUNK;
@@ -1006,7 +1007,7 @@ int mgc::text_rollback(mgc_session *s) {
 
 extern "C" int mgc_end_text(mgc_session *s) {
   if (!s) return MGC_EINVAL;
-  if (!s->text_open) { set_err(&s->err, "mgc_end_text without mgc_begin_text"); return MGC_ESTATE; }
+  if (!s->text_open || s->text_format == mgc_session::TEXT_BAM) { set_err(&s->err, "mgc_end_text without mgc_begin_text"); return MGC_ESTATE; }
   HIP_TRY(s, hipSetDevice(s->device));
   s->text_open = false;
   HIP_TRY(s, s->ensure_preserve(stage_id(s->fill), s->fill_len + 4096, s->fill_len, s->st_in));
@@ -1024,6 +1025,116 @@ extern "C" int mgc_end_text(mgc_session *s) {
     return MGC_EFORMAT;
   }
   if (s->fill_len >= s->batch_limit) return cut_batch(s);
+  return MGC_OK;
+}
+
+// ---- BAM input, decoded on the device (include/meryl_gpu_count.h) ------------------------------
+// The open BAM file shares the text file's state (text_open, the cut inside a file, the rollback point in the device's parse
+// state); its lengths are exact on the host, so fill_len stays exact while it is open.
+extern "C" int mgc_begin_bam(mgc_session *s) {
+  if (!s) return MGC_EINVAL;
+  if (s->text_open) { set_err(&s->err, "mgc_begin_bam: the previous file was not ended"); return MGC_ESTATE; }
+  int rc = text_setup(s);
+  if (rc != MGC_OK) return rc;
+  rc = flush_pinned(s);                                     // host-pushed bases come first in the stream
+  if (rc != MGC_OK) return rc;
+  if (s->len_inexact) { rc = resolve_length(s); if (rc != MGC_OK) return rc; }
+  HIP_TRY(s, mgc::launch_text_file_op(s->buf[mgc_session::B_TEXT_STATE].p, stage_ptr(s, s->fill), 0, s->st_in));
+  s->bam_walker.reset();
+  s->tr_bam_walk = 0;
+  s->text_format = mgc_session::TEXT_BAM;
+  s->text_open = true;
+  s->text_cut_in_file = false;
+  s->input_seen = true;
+  return MGC_OK;
+}
+
+int mgc::bam_submit(mgc_session *s, const char *pinned_src, size_t piece) {
+  const double t0 = mgc::now_s();
+  s->bam_segs.clear();
+  uint64_t out_bytes = 0;
+  const bool ok = s->bam_walker.walk(reinterpret_cast<const unsigned char *>(pinned_src), piece, &s->bam_segs, &out_bytes);
+  s->tr_bam_walk += mgc::now_s() - t0;
+  if (!ok) return mgc::BAM_REFUSED;
+  const size_t nseg = s->bam_segs.size();
+  if (nseg == 0) {
+    // Header bytes, names, qualities, aux -- a piece that lies wholly inside a long record's tail: nothing for the device.  The
+    // whole-file reader's ring gives a slot back two pieces after its submit BECAUSE a submit waits for the piece two before it
+    // (mgc_chunk_ring.hpp); a piece that queues nothing would break that count, so it waits for both pieces in flight instead.
+    mgc::text_drain(s);
+    return MGC_OK;
+  }
+  const uint32_t b = s->text_next & 1u;
+  if (s->text_ev_used[b]) HIP_TRY(s, hipEventSynchronize(s->text_ev[b]));       // device buffers b (and their previous sources) are free again
+  HIP_TRY(s, s->ensure_preserve(stage_id(s->fill), s->fill_len + out_bytes + 4096, s->fill_len, s->st_in));
+  if (s->bam_seg_cap[b] < nseg) {                           // grow-only, with room to spare: records of one file are alike
+    if (s->bam_seg_pinned[b]) { (void)hipHostFree(s->bam_seg_pinned[b]); s->bam_seg_pinned[b] = nullptr; s->bam_seg_cap[b] = 0; }
+    const size_t want = nseg + nseg / 2 + 4096;
+    HIP_TRY(s, hipHostMalloc(reinterpret_cast<void **>(&s->bam_seg_pinned[b]), want * sizeof(mgc::BamSegment), hipHostMallocDefault));
+    s->bam_seg_cap[b] = want;
+  }
+  const int seg_buf = b ? mgc_session::B_BAM_SEG1 : mgc_session::B_BAM_SEG0;
+  HIP_TRY(s, s->ensure(seg_buf, s->bam_seg_cap[b] * sizeof(mgc::BamSegment)));
+  memcpy(s->bam_seg_pinned[b], s->bam_segs.data(), nseg * sizeof(mgc::BamSegment));
+  uint8_t *d_in = reinterpret_cast<uint8_t *>(s->buf[b ? mgc_session::B_TEXT_IN1 : mgc_session::B_TEXT_IN0].p);
+  HIP_TRY(s, hipMemcpyAsync(d_in, pinned_src, piece, hipMemcpyHostToDevice, s->st_up));
+  HIP_TRY(s, hipMemcpyAsync(s->buf[seg_buf].p, s->bam_seg_pinned[b], nseg * sizeof(mgc::BamSegment), hipMemcpyHostToDevice, s->st_up));
+  HIP_TRY(s, hipEventRecord(s->up_ev[b], s->st_up));
+  HIP_TRY(s, hipStreamWaitEvent(s->st_in, s->up_ev[b], 0));
+  HIP_TRY(s, mgc::launch_bam_decode(d_in, piece, s->buf[seg_buf].p, nseg, out_bytes, stage_ptr(s, s->fill) + s->fill_len, s->st_in));
+  s->fill_len += out_bytes;                                 // exact
+  HIP_TRY(s, mgc::launch_text_set_len(s->buf[mgc_session::B_TEXT_STATE].p, s->fill_len, 0, s->st_in));
+  HIP_TRY(s, hipEventRecord(s->text_ev[b], s->st_in));
+  s->text_ev_used[b] = true;
+  s->text_next++;
+  if (s->fill_len >= s->batch_limit) return cut_batch(s);
+  return MGC_OK;
+}
+
+int mgc::bam_refuse(mgc_session *s, const char *what) {
+  const std::string why = s->bam_walker.error();
+  const int rc = mgc::text_rollback(s);
+  if (rc == MGC_EINVAL) set_err(&s->err, "'%s': %s, after part of the file was counted (input larger than one batch)", what, why.c_str());
+  if (rc != MGC_OK) return rc;
+  set_err(&s->err, "'%s': %s", what, why.c_str());
+  return MGC_EFORMAT;
+}
+
+extern "C" int mgc_push_bam(mgc_session *s, const void *bam_bytes, size_t len) {
+  if (!s || (!bam_bytes && len)) return MGC_EINVAL;
+  if (!s->text_open || s->text_format != mgc_session::TEXT_BAM) { set_err(&s->err, "mgc_push_bam without mgc_begin_bam"); return MGC_ESTATE; }
+  HIP_TRY(s, hipSetDevice(s->device));
+  const char *src = static_cast<const char *>(bam_bytes);
+  while (len) {
+    const size_t piece = len < mgc_session::TEXT_CHUNK ? len : mgc_session::TEXT_CHUNK;
+    const uint32_t b = s->text_next & 1u;
+    if (s->text_ev_used[b]) HIP_TRY(s, hipEventSynchronize(s->text_ev[b]));     // pinned + device buffer b are free again
+    memcpy(s->text_pinned[b], src, piece);
+    const int rc = mgc::bam_submit(s, s->text_pinned[b], piece);
+    if (rc == mgc::BAM_REFUSED) return mgc::bam_refuse(s, "mgc_push_bam");
+    if (rc != MGC_OK) return rc;
+    src += piece;
+    len -= piece;
+  }
+  return MGC_OK;
+}
+
+int mgc::bam_end(mgc_session *s, const char *what) {
+  if (!s->text_open || s->text_format != mgc_session::TEXT_BAM) { set_err(&s->err, "mgc_end_bam without mgc_begin_bam"); return MGC_ESTATE; }
+  HIP_TRY(s, hipSetDevice(s->device));
+  if (!s->bam_walker.finish()) return mgc::bam_refuse(s, what);
+  s->text_open = false;
+  if (s->fill_len >= s->batch_limit) return cut_batch(s);
+  return MGC_OK;
+}
+
+extern "C" int mgc_end_bam(mgc_session *s) { return s ? mgc::bam_end(s, "mgc_end_bam") : MGC_EINVAL; }
+
+extern "C" int mgc_dev_bam_decode(const uint8_t *d_piece, uint64_t piece_bytes, const void *d_segments, uint64_t n_segments, uint64_t out_bytes,
+                                  uint8_t *d_out, void *stream) {
+  if ((!d_piece && piece_bytes) || (!d_segments && n_segments) || (!d_out && out_bytes)) return MGC_EINVAL;
+  if (piece_bytes > 0xffffffffull) { set_err(nullptr, "mgc_dev_bam_decode: a piece holds less than 4 GiB"); return MGC_EINVAL; }
+  HIP_TRY((mgc_session *)nullptr, mgc::launch_bam_decode(d_piece, piece_bytes, d_segments, n_segments, out_bytes, d_out, static_cast<hipStream_t>(stream)));
   return MGC_OK;
 }
 

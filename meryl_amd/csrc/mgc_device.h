@@ -376,6 +376,12 @@ size_t     text_parse_state_bytes();
 size_t     text_parse_workspace_bytes(uint64_t n);            // for one chunk of n text bytes
 // appends the bases of one text chunk to d_out at the running length kept in d_state
 hipError_t launch_text_parse(const uint8_t *d_text, uint64_t n, int fastq, void *d_state, void *d_ws, uint8_t *d_out, hipStream_t st);
+// ---- BAM records -> base stream (mgc_bam.hip) ----
+// One piece of an inflated BAM stream (piece_bytes at d_piece) and the segments the host walker made of it (n_segments of 16
+// bytes, mgc::BamSegment of mgc_bam_walk.hpp, tiling [0, out_total)): writes out_total bytes at d_out (any alignment) -- the SEQ
+// fields through the nt16 alphabet, '.' after the flagged segments.  The running length of the stream is the caller's business.
+hipError_t launch_bam_decode(const uint8_t *d_piece, uint64_t piece_bytes, const void *d_segments, uint64_t n_segments, uint64_t out_total,
+                             uint8_t *d_out, hipStream_t st);
 // what: 0 begin file, 1 end file (breaker), 2 roll the current file back, 3 reset
 hipError_t launch_text_file_op(void *d_state, uint8_t *d_out, int what, hipStream_t st);
 // the stream now holds new_len bytes (bases appended by a plain copy, or the tail kept after a batch was cut off);

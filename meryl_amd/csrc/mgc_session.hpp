@@ -5,6 +5,7 @@
 #pragma once
 
 #include "../../include/meryl_gpu_count.h"
+#include "mgc_bam_walk.hpp"
 #include "mgc_clock.hpp"
 #include "mgc_devbuf.hpp"
 #include "mgc_device.h"
@@ -83,7 +84,8 @@ struct mgc_session {
          B_SUBSTART, B_GROUPS, B_GSCAN, B_CNT_TMP, B_LARGE, B_NONEMPTY, B_STAGE0, B_STAGE1, B_TEXT_IN0, B_TEXT_IN1, B_TEXT_WS,
          B_TEXT_STATE, B_RK, B_RC, B_R2K, B_R2C, B_MERGE_WS, B_SORT_HDRS, B_FINE, B_NARROW_WS, B_Y2, B_Y3, B_Y4, B_HWS0, B_HWS1, B_HWS2, B_HWS3,
          B_PACKED /* the count's packed base stream: 2-bit codes + invalid-base masks, written by the histogram, read by the partition */,
-         B_GROUP_BATCH /* the batched grouping launches' control words and descriptor tables (mgc_count.cpp, group_batches) */, B_NUM };
+         B_GROUP_BATCH /* the batched grouping launches' control words and descriptor tables (mgc_count.cpp, group_batches) */,
+         B_BAM_SEG0, B_BAM_SEG1 /* the segment tables of the two BAM pieces in flight (mgc_bam_walk.hpp) */, B_NUM };
   Buf buf[B_NUM];
   size_t arena_bytes() const { size_t t = 0; for (const auto &b : buf) t += b.cap; return t; }
   double tr_alloc = 0;                   // seconds inside hipMalloc / hipFree of the arena (MGC_IO_TRACE)
@@ -151,6 +153,14 @@ struct mgc_session {
   uint32_t    text_next = 0;
   static constexpr int TEXT_RING_MAX = 64;
   char       *text_ring[TEXT_RING_MAX] = {nullptr};      // the whole-file readers' pinned slots (mgc_textfile.cpp; allocated on first use)
+  // BAM (mgc_begin_bam ...): the open file is a text file of format TEXT_BAM -- one "open file" state for both -- whose pieces are
+  // inflated BAM bytes: walked on the host, decoded on the device (mgc_bam.hip) from a segment table that travels with the piece
+  static constexpr int TEXT_BAM = 3;
+  mgc::BamWalker bam_walker;
+  std::vector<mgc::BamSegment> bam_segs;                 // of the piece being walked
+  mgc::BamSegment *bam_seg_pinned[2] = {nullptr, nullptr};   // pinned, grow-only, one per device input buffer
+  size_t      bam_seg_cap[2] = {0, 0};                   // segments
+  double      tr_bam_walk = 0;                           // seconds in the walker, this file (MGC_IO_TRACE)
   // host-pushed bases: two pinned chunks, the upload of one overlaps the filling of the other
   char       *pin[2] = {nullptr, nullptr};
   size_t      pin_len = 0;
@@ -217,5 +227,15 @@ int text_submit(mgc_session *s, const char *pinned_src, size_t piece);
 void text_drain(mgc_session *s);
 // closes the open file and takes it back out of the stream; MGC_EINVAL when part of it was already counted
 int text_rollback(mgc_session *s);
+// The open BAM file (mgc_begin_bam): one piece of its inflated bytes (<= TEXT_CHUNK, in pinned memory) walked on the host,
+// uploaded with its segment table and decoded into the stream; returns once that is queued.  BAM_REFUSED (> 0): the walker
+// refuses the stream (s->bam_walker.error()); nothing of the piece was queued, the file is still open (bam_refuse closes it).
+constexpr int BAM_REFUSED = 1;
+int bam_submit(mgc_session *s, const char *pinned_src, size_t piece);
+// closes the refused BAM file and rolls it back: MGC_EFORMAT with "'what': the walker's words" as the session's error, or
+// MGC_EINVAL when part of the file was already counted
+int bam_refuse(mgc_session *s, const char *what);
+// mgc_end_bam with the name the refusal of a stream that ends inside the header or a record is reported under
+int bam_end(mgc_session *s, const char *what);
 }  // namespace mgc
 

@@ -1,7 +1,8 @@
 // mgc_textfile.cpp -- whole FASTA / FASTQ files into a session's base stream (include/meryl_gpu_count.h): plain files read
 // with pread, BGZF files inflated, by several threads STRAIGHT into a ring of pinned buffers (mgc_chunk_ring.hpp) that the
-// calling thread uploads and parses in file order.  The session is reached through mgc_begin_text / mgc_end_text and
-// text_submit / text_drain / text_rollback (mgc_session.hpp) only.
+// calling thread uploads and parses in file order; BGZF BAM files likewise, walked and decoded instead of parsed.  The session
+// is reached through mgc_begin_text / mgc_end_text / mgc_begin_bam / mgc_end_bam and text_submit / bam_submit / text_drain /
+// text_rollback / bam_refuse (mgc_session.hpp) only.
 #include "../../include/meryl_gpu_count.h"
 #include "mgc_bgzf.hpp"
 #include "mgc_chunk_ring.hpp"
@@ -246,4 +247,73 @@ extern "C" int mgc_push_text_bgzf_file(mgc_session *s, const char *path, int for
   if (res.end == mgc::ChunkRingResult::CONSUMER_STOPPED) rc = res.detail;
   const int rc_end = mgc_end_text(s);                           // closes the file in every case (rolls it back on MGC_EFORMAT)
   return rc != MGC_OK ? rc : rc_end;
+}
+
+// ---- a BGZF BAM file: mgc_push_text_bgzf_file with the record walker (mgc_bam_walk.hpp) and the device decoder (mgc_bam.hip) in the
+// consumer.  The workers inflate the blocks of chunk after chunk into the ring (CRC checked); the calling thread takes the chunks in
+// file order, walks each one's records -- a few bytes per record -- and queues upload + decode.  What was one host thread expanding
+// every base (meryl_seq.cpp) is one host thread reading 36 bytes per record.
+extern "C" int mgc_push_bam_file(mgc_session *s, const char *path, int threads) {
+  if (!s || !path) return MGC_EINVAL;
+  uint64_t fsize = 0;
+  const int fd = open_regular(&s->err, "mgc_push_bam_file", path, "regular BGZF file", 28, &fsize);
+  if (fd < 0) return MGC_EINVAL;
+  const unsigned char *map = reinterpret_cast<const unsigned char *>(mmap(nullptr, fsize, PROT_READ, MAP_SHARED, fd, 0));
+  if (map == MAP_FAILED) { close(fd); set_err(&s->err, "mgc_push_bam_file: mmap of '%s' failed: %s", path, strerror(errno)); return MGC_EINVAL; }
+  std::vector<z_stream> zs;                                     // one inflater per worker thread, n_z of them set up
+  int n_z = 0;
+  auto release = [&]() { for (int t = 0; t < n_z; t++) inflateEnd(&zs[t]); munmap(const_cast<unsigned char *>(map), fsize); close(fd); };
+  const mgc::BgzfPlan plan = mgc::bgzf_plan_chunks(map, fsize, mgc_session::TEXT_CHUNK);
+  const std::vector<mgc::BgzfBlock> &blocks = plan.blocks;
+  if (plan.bad != mgc::BGZF_BLOCK) {
+    release();
+    if (plan.bad == mgc::BGZF_BAD_ISIZE) set_err(&s->err, "'%s': corrupt BGZF block at offset %zu (ISIZE %u)", path, (size_t)plan.bad_off, plan.bad_isize);
+    else set_err(&s->err, "'%s': not a BGZF block at offset %zu (plain gzip data, or a truncated file)", path, (size_t)plan.bad_off);
+    return MGC_EFORMAT;
+  }
+  const uint64_t nchunks = plan.chunks.size();
+  const mgc::ChunkRingGeometry g = mgc::chunk_ring_geometry(threads, nchunks, mgc_session::TEXT_RING_MAX);
+  zs.resize(g.threads);
+  while (n_z < g.threads && inflateInit2(&zs[n_z], -15) == Z_OK) n_z++;
+  if (n_z < g.threads) { release(); set_err(&s->err, "zlib: inflateInit2 failed"); return MGC_ENOMEM; }
+  int rc = mgc_begin_bam(s);
+  if (rc != MGC_OK) { release(); return rc; }
+
+  auto fill = [&](int t, uint64_t c, char *dst, int *bad_block) -> int64_t {
+    size_t at = 0;
+    for (size_t i = plan.chunks[c].first; i < plan.chunks[c].last; i++) {
+      if (!mgc::bgzf_inflate_block(zs[t], map + blocks[i].off, blocks[i], reinterpret_cast<unsigned char *>(dst) + at)) { *bad_block = (int)i; return -1; }
+      at += blocks[i].isize;
+    }
+    return (int64_t)at;
+  };
+  uint64_t bam_total = 0;
+  bool refused = false;
+  auto consume = [&](uint64_t, const char *p, size_t len) {
+    bam_total += len;
+    if (!len) return (int)MGC_OK;                               // (a chunk of empty blocks: the end-of-file marker)
+    const int r = mgc::bam_submit(s, p, len);
+    if (r == mgc::BAM_REFUSED) refused = true;
+    return r;
+  };
+  const mgc::ChunkRingResult res = run_session_ring(s, nchunks, g, fill, consume);
+  mgc::text_drain(s);                                           // the last uploads still read from the ring
+  release();
+  if (getenv("MGC_IO_TRACE"))
+    fprintf(stderr, "[io] BAM file %.2f GB -> %.2f GB of records in %llu chunks (%zu blocks), %d inflaters, ring %d: waiting for the inflaters %.3f s, "
+                    "walk %.3f s (%llu records), upload+decode submit (incl. the walk and waits for the device) %.3f s\n", fsize / 1e9, bam_total / 1e9,
+            (unsigned long long)nchunks, blocks.size(), g.threads, g.slots, res.t_wait, s->tr_bam_walk, (unsigned long long)s->bam_walker.records(), res.t_consume);
+  if (res.end == mgc::ChunkRingResult::ALLOC_FAILED) { set_err(&s->err, "mgc_push_bam_file: pinned buffers: out of memory"); (void)mgc::text_rollback(s); return MGC_ENOMEM; }
+  if (res.end == mgc::ChunkRingResult::FILL_FAILED) {
+    // what the file has put into the stream is taken back, unless part of it already went into a counted batch
+    const unsigned long long bb = (unsigned long long)res.detail;
+    rc = mgc::text_rollback(s);
+    if (rc == MGC_EINVAL) set_err(&s->err, "'%s': BGZF block %llu failed to inflate after part of the file was counted (input larger than one batch)", path, bb);
+    if (rc != MGC_OK) return rc;
+    set_err(&s->err, "'%s': BGZF block %llu failed to inflate (corrupt file)", path, bb);
+    return MGC_EFORMAT;
+  }
+  if (refused) return mgc::bam_refuse(s, path);
+  if (res.end == mgc::ChunkRingResult::CONSUMER_STOPPED) { (void)mgc::text_rollback(s); return res.detail; }
+  return mgc::bam_end(s, path);                                 // a stream that ends inside a record is refused here, by the file's name
 }
