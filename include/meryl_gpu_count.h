@@ -548,6 +548,38 @@ int mgc_text_record_start(const char *path, int format, uint64_t offset, uint64_
 int mgc_push_text_bgzf_file(mgc_session *s, const char *path, int format, int threads);
 int mgc_is_bgzf_file(const char *path);
 
+/* A whole FASTA / FASTQ file in PLAIN gzip (one deflate stream per member, any number of members; not BGZF), which has no index of
+ * independent blocks: `threads` workers (0: 16) start inflating at guessed deflate block boundaries, one per span of MGC_GZIP_SPAN
+ * compressed bytes (default 4 MiB), straight into the pinned upload ring, and write MARKERS where a back-reference reaches into the
+ * 32 KiB before their start.  The device, which receives the pieces in stream order, replaces the markers from the text it already
+ * holds and computes every member's CRC-32 over the resolved text; CRC32 and ISIZE are compared with the trailers.  A worker's output
+ * is taken only when the piece before it ended exactly at its start, so the text is exact whatever was guessed: a file of fixed blocks
+ * only, or one where every guess is wrong, inflates serially.  MGC_GZIP_TEXT_CAP: bytes of text per piece (default and most 32 MiB).
+ * Bytes after the last member that do not start a gzip member are ignored, as zlib's gzread ignores them.
+ * Return codes and rollback as mgc_push_text_bgzf_file: MGC_EFORMAT -- not gzip, a damaged or truncated stream, a CRC32 / ISIZE
+ * mismatch, neither FASTA nor strict FASTQ -- leaves nothing of the file in the session; MGC_EINVAL when part of the file was already
+ * counted as a batch, or when the file cannot be opened.  mgc_last_error names the file and the compressed offset.
+ * info (may be NULL): members read; chunks = spans + cuts; confirmed: spans whose worker's output was taken; discarded: spans whose
+ * worker started from a false candidate; text_bytes; symbol_bytes: 16-bit symbols uploaded beside the text; cuts: pieces that continue a
+ * worker's output because it did not fit one slot.  mgc_is_gzip_file: 1 when the file starts with a gzip member that is not BGZF. */
+typedef struct {
+  uint64_t members, chunks, confirmed, discarded;
+  uint64_t text_bytes, symbol_bytes, cuts;
+} mgc_gzip_info;
+int mgc_push_text_gzip_file(mgc_session *s, const char *path, int format, int threads, mgc_gzip_info *info);
+int mgc_is_gzip_file(const char *path);
+
+/* The device side of the above, on buffers of the caller's (any alignment; `stream`: a hipStream_t, NULL: the default stream).
+ * mgc_dev_gzip_resolve: d_text[i] = d_symbols[i] < 256 ? d_symbols[i] : d_window_in[d_symbols[i] - 0x8000] for i < n_symbols
+ * (<= text_bytes), in place; a symbol in 0x100..0x7FFF ORs 1 into *d_error, a marker below 32768 - window_valid ORs 2, both write 0.
+ * d_window_out (NULL: none; never d_window_in): the last 32 KiB of (d_window_in ++ d_text[0 .. text_bytes)), read after the patch.
+ * d_window_in may be NULL when window_valid is 0.  mgc_dev_crc32_pieces: d_crc[i] = CRC-32 of d_text[d_begin[i] .. + d_len[i]),
+ * d_len[i] <= 4096; zlib's crc32_combine joins them. */
+int mgc_dev_gzip_resolve(uint8_t *d_text, uint64_t text_bytes, const uint16_t *d_symbols, uint64_t n_symbols,
+                         const uint8_t *d_window_in, uint32_t window_valid, uint8_t *d_window_out, uint32_t *d_error, void *stream);
+int mgc_dev_crc32_pieces(const uint8_t *d_text, const uint64_t *d_begin, const uint32_t *d_len, uint64_t n_pieces, uint32_t *d_crc,
+                         void *stream);
+
 /* BAM records instead of text: the INFLATED bytes of a BAM file (SAMv1 4.2: magic, header text, reference names, then records
  * of block_size + 32 fixed bytes + read name + CIGAR + SEQ packed two bases per byte + qualities + aux), in pieces of any
  * size.  The host only walks the records -- header fields and the 36 fixed bytes of every record, resumable across pieces --

@@ -21,7 +21,7 @@ SYMBOLS = (
     "mgc_dev_partition_workspace_bytes", "mgc_dev_kmer_histogram", "mgc_dev_kmer_partition",
     "mgc_dev_sort_workspace_bytes", "mgc_dev_radix_sort", "mgc_dev_radix_group", "mgc_dev_kmer_histogram_fine",
     "mgc_dev_rle_workspace_bytes", "mgc_dev_rle_count", "mgc_dev_rle_emit", "mgc_dev_block_offsets",
-    "mgc_open", "mgc_close", "mgc_last_error", "mgc_push_bases", "mgc_push_bases_device", "mgc_staged_bases", "mgc_reserve_text", "mgc_begin_text", "mgc_push_text", "mgc_end_text", "mgc_push_text_file", "mgc_push_text_file_range", "mgc_text_record_start", "mgc_push_text_bgzf_file", "mgc_is_bgzf_file", "mgc_begin_bam", "mgc_push_bam", "mgc_end_bam", "mgc_push_bam_file", "mgc_dev_bam_decode", "mgc_count", "mgc_count_partitioned", "mgc_count_buckets", "mgc_count_buckets_into", "mgc_copy_result_device",
+    "mgc_open", "mgc_close", "mgc_last_error", "mgc_push_bases", "mgc_push_bases_device", "mgc_staged_bases", "mgc_reserve_text", "mgc_begin_text", "mgc_push_text", "mgc_end_text", "mgc_push_text_file", "mgc_push_text_file_range", "mgc_text_record_start", "mgc_push_text_bgzf_file", "mgc_is_bgzf_file", "mgc_begin_bam", "mgc_push_bam", "mgc_end_bam", "mgc_push_bam_file", "mgc_dev_bam_decode", "mgc_push_text_gzip_file", "mgc_is_gzip_file", "mgc_dev_gzip_resolve", "mgc_dev_crc32_pieces", "mgc_count", "mgc_count_partitioned", "mgc_count_buckets", "mgc_count_buckets_into", "mgc_copy_result_device",
     "mgc_get_result_info", "mgc_get_result_device", "mgc_copy_result", "mgc_finish", "mgc_finish_labelled",
     "mgc_set_profiling", "mgc_get_profile", "mgc_dev_synth_reads", "mgc_dev_synth_reads_ex", "mgc_version",
     "mgc_dev_merge_workspace_bytes", "mgc_dev_merge_count", "mgc_dev_merge_count_values", "mgc_dev_merge_emit",
@@ -282,6 +282,11 @@ class RunsProfile(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class GzipInfo(ctypes.Structure):
+    """mgc_gzip_info (include/meryl_gpu_count.h)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("members", "chunks", "confirmed", "discarded", "text_bytes", "symbol_bytes", "cuts")]
+
+
 class LookupInfo(ctypes.Structure):
     _fields_ = [("k", ctypes.c_uint32), ("key_words", ctypes.c_uint32), ("index_bits", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
                 ("n_kmers", ctypes.c_uint64), ("n_kmers_in_db", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64)]
@@ -498,6 +503,10 @@ def lib():
     sig("mgc_end_bam", i32, vp)
     sig("mgc_push_bam_file", i32, vp, ctypes.c_char_p, i32)
     sig("mgc_dev_bam_decode", i32, vp, u64, vp, u64, u64, vp, vp)
+    sig("mgc_push_text_gzip_file", i32, vp, ctypes.c_char_p, i32, i32, ctypes.POINTER(GzipInfo))
+    sig("mgc_is_gzip_file", i32, ctypes.c_char_p)
+    sig("mgc_dev_gzip_resolve", i32, vp, u64, vp, u64, vp, u32, vp, vp, vp)
+    sig("mgc_dev_crc32_pieces", i32, vp, vp, vp, u64, vp, vp)
     sig("mgc_text_record_start", i32, ctypes.c_char_p, i32, u64, P(u64))
     sig("mgc_count", i32, vp)
     sig("mgc_count_partitioned", i32, vp, vp, vp, vp)

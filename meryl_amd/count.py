@@ -521,6 +521,16 @@ class Session:
         """One whole BGZF BAM file, inflated by `threads` threads (0: default) into the upload ring, decoded on the device."""
         capi.check(capi.lib().mgc_push_bam_file(self._h, os.fsencode(path), int(threads)), "mgc_push_bam_file", self._h)
 
+    def push_text_gzip_file(self, path, threads=0):
+        """One whole FASTA / FASTQ file in plain gzip (not BGZF), inflated by `threads` threads (0: default) from guessed block
+        starts into the upload ring; the device resolves what they could not know and checks every member's CRC-32.  Returns
+        mgc_gzip_info as a dict.  Raises MgcError(code MGC_EFORMAT) for a file that is not gzip, is damaged or is not strict
+        FASTA / FASTQ (its output is rolled back)."""
+        info = capi.GzipInfo()
+        capi.check(capi.lib().mgc_push_text_gzip_file(self._h, os.fsencode(path), 0, int(threads), ctypes.byref(info)),
+                   "mgc_push_text_gzip_file", self._h)
+        return {n: int(getattr(info, n)) for n, _ in capi.GzipInfo._fields_}
+
     def staged_bases(self):
         """A copy of the base stream staged so far ('.' breakers included) as a uint8 cuda tensor (mgc_staged_bases)."""
         p, n = ctypes.c_void_p(), ctypes.c_uint64(0)

@@ -246,11 +246,13 @@ struct InputPiece { std::string name; uint64_t begin, end; };
 
 static bool is_regular_file(const std::string &name) { struct stat st; return stat(name.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
 
-// Input: the file's raw text goes to the device and is parsed there (mgc_push_text*); a BGZF BAM file goes there as its
+// Input: the file's raw text goes to the device and is parsed there (mgc_push_text*; a plain gzip file's is inflated by several threads
+// and resolved there, mgc_push_text_gzip_file); a BGZF BAM file goes there as its
 // inflated bytes and its SEQ fields are decoded there (mgc_push_bam_file); files the device routes refuse (multi-line
 // FASTQ, a damaged BAM ...), SAM, BAM in plain gzip or on stdin and MERYL_HOST_PARSER=1 take the host state machine of
 // meryl_seq.cpp.  Returns the bytes / bases taken in (reported with -V -V).
 int g_inflate_threads = 16;                                  // threads= of the command line: the BGZF inflaters (readers of plain text: at most 16)
+bool g_gzip_parallel = true;                                 // false under gpus=N: every rank reads its files with the host reader's one gzread thread
 uint64_t load_inputs(mgc_session *s, const std::vector<InputPiece> &pieces, int reader_threads) {
   const uint64_t buf_max = 2 * 1024 * 1024;                                                            // merylOp-countThreads.C:413
   std::vector<char> buf(buf_max);
@@ -309,6 +311,18 @@ uint64_t load_inputs(mgc_session *s, const std::vector<InputPiece> &pieces, int 
       msr_close(r);
       const char *bt = getenv("MERYL_BGZF_THREADS");
       const int rc = mgc_push_text_bgzf_file(s, name.c_str(), 0, bt ? atoi(bt) : std::max(reader_threads, g_inflate_threads));
+      if (rc == MGC_EFORMAT) load_on_host(name);
+      else if (rc != MGC_OK) die("ERROR: %s", mgc_last_error(s));
+      struct stat fst;
+      if (stat(name.c_str(), &fst) == 0) total_bases += (uint64_t)fst.st_size * 3;             // (text bytes, as the reference guesses them for .gz)
+      continue;
+    }
+    if (name != "-" && whole && g_gzip_parallel && is_regular_file(name) && mgc_is_gzip_file(name.c_str()) && !getenv("MERYL_GZIP_GENERIC")) {
+      // plain gzip: the library maps the file, several threads inflate it from guessed block starts straight into its pinned upload
+      // buffers, the device resolves what they could not know and checks the CRC (MERYL_GZIP_GENERIC=1: one gzread thread, below)
+      msr_close(r);
+      const char *gt = getenv("MERYL_GZIP_THREADS");
+      const int rc = mgc_push_text_gzip_file(s, name.c_str(), 0, gt ? atoi(gt) : std::max(reader_threads, g_inflate_threads), nullptr);
       if (rc == MGC_EFORMAT) load_on_host(name);
       else if (rc != MGC_OK) die("ERROR: %s", mgc_last_error(s));
       struct stat fst;
@@ -406,6 +420,7 @@ int run_count_node(const Globals &g, const Operation &op, const mgc_count_config
   }
   {
     std::vector<std::thread> th;
+    g_gzip_parallel = false;
     for (uint32_t r = 0; r < N; r++) th.emplace_back([&, r] { taken[r] = load_inputs(sess[r], share[r], readers); });
     for (auto &t : th) t.join();
   }

@@ -8,6 +8,7 @@
 #include "../../include/meryl_gpu_count.h"
 #include "mgc_device.h"
 #include "mgc_session.hpp"
+#include "mgc_gzip_par.hpp"
 #include "mgc_runs.hpp"
 #include "mgc_selector.hpp"
 #include "mgc_value.hpp"
@@ -707,6 +708,8 @@ extern "C" void mgc_close(mgc_session *s) {
     if (s->pin[i]) (void)hipHostFree(s->pin[i]);
     if (s->pin_ev[i]) (void)hipEventDestroy(s->pin_ev[i]);
     if (s->bam_seg_pinned[i]) (void)hipHostFree(s->bam_seg_pinned[i]);
+    if (s->gz_sym_pinned[i]) (void)hipHostFree(s->gz_sym_pinned[i]);
+    if (s->gz_tab_pinned[i]) (void)hipHostFree(s->gz_tab_pinned[i]);
   }
   for (char *&p : s->text_ring) if (p) { (void)hipHostFree(p); p = nullptr; }
   if (s->st_up) { (void)hipStreamSynchronize(s->st_up); (void)hipStreamDestroy(s->st_up); }
@@ -1135,6 +1138,215 @@ extern "C" int mgc_dev_bam_decode(const uint8_t *d_piece, uint64_t piece_bytes, 
   if ((!d_piece && piece_bytes) || (!d_segments && n_segments) || (!d_out && out_bytes)) return MGC_EINVAL;
   if (piece_bytes > 0xffffffffull) { set_err(nullptr, "mgc_dev_bam_decode: a piece holds less than 4 GiB"); return MGC_EINVAL; }
   HIP_TRY((mgc_session *)nullptr, mgc::launch_bam_decode(d_piece, piece_bytes, d_segments, n_segments, out_bytes, d_out, static_cast<hipStream_t>(stream)));
+  return MGC_OK;
+}
+
+// ---- gzip input, inflated by several host threads, resolved on the device (mgc_gzip_par.hpp, mgc_gzip.hip) ----------------------
+// The open gzip file IS an open text file (mgc_begin_text): its pieces go through the same device input buffers, upload stream and
+// parse kernels as text_submit's.  Before the parse kernels read a piece, its unresolved prefix is patched from the window the device
+// keeps of the text before it; the CRC-32 of the resolved text comes back two pieces later (or at gzip_finish) and is held against the
+// members' trailers then.
+static uint32_t *gz_error_word(mgc_session *s) { return reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(s->buf[mgc_session::B_GZ_WIN].p) + 2 * mgc::GZ_WINDOW); }
+
+int mgc::gzip_begin(mgc_session *s) {
+  HIP_TRY(s, s->ensure(mgc_session::B_GZ_WIN, 2 * mgc::GZ_WINDOW + 256));
+  HIP_TRY(s, hipMemsetAsync(s->buf[mgc_session::B_GZ_WIN].p, 0, 2 * mgc::GZ_WINDOW + 256, s->st_in));
+  s->gz_win = 0;
+  s->tr_gz_copy = s->tr_gz_collect = s->tr_gz_wait = 0;
+  s->gz_crc = 0; s->gz_member_len = 0; s->gz_members = 0;
+  s->gz_verdict.clear();
+  for (int b = 0; b < 2; b++) { s->gz_pending[b].clear(); s->gz_ends[b].clear(); }
+  return MGC_OK;
+}
+
+// crc32_combine(crc1, crc2, 4096) without zlib's work: zlib squares a 32 x 32 GF(2) matrix some fifteen times per call (tens of
+// microseconds in zlib 1.2), and a 32 MiB piece brings 8192 values.  Nearly every CRC piece is exactly 4096 bytes, so the operator
+// "append 4096 zero bytes" is built once -- the one-zero-bit operator squared fifteen times -- and applied in at most 32 steps.
+static uint32_t gf2_times(const uint32_t *mat, uint32_t vec) {
+  uint32_t sum = 0;
+  for (; vec; vec >>= 1, mat++) if (vec & 1u) sum ^= *mat;
+  return sum;
+}
+static uint32_t crc32_combine_4096(uint32_t crc1, uint32_t crc2) {
+  static const struct Op {
+    uint32_t m[32];
+    Op() {
+      uint32_t a[32], b[32];
+      a[0] = 0xedb88320u;                                    // one zero bit
+      for (int n = 1; n < 32; n++) a[n] = 1u << (n - 1);
+      for (int sq = 0; sq < 15; sq++) {                      // 2^15 bits = 4096 bytes
+        for (int n = 0; n < 32; n++) b[n] = gf2_times(a, a[n]);
+        memcpy(a, b, sizeof(a));
+      }
+      memcpy(m, a, sizeof(m));
+    }
+  } op;
+  return gf2_times(op.m, crc1) ^ crc2;
+}
+
+// the CRC values of the piece that went through buffer b have arrived (its text_ev was waited for): fold them into the member's
+static void gz_collect(mgc_session *s, uint32_t b) {
+  std::vector<mgc_session::GzCrcPiece> &pend = s->gz_pending[b];
+  if (pend.empty()) return;
+  const double t0 = mgc::now_s();
+  const size_t cap = s->gz_tab_cap[b];
+  const uint32_t *crc = reinterpret_cast<const uint32_t *>(s->gz_tab_pinned[b] + 12 * cap);
+  const uint32_t dev_err = crc[cap];
+  if (dev_err && s->gz_verdict.empty()) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "%s (in the piece that starts at compressed offset %llu)",
+             (dev_err & 2u) ? "a back-reference reaches before the start of its gzip member" : "the inflaters produced an invalid symbol",
+             (unsigned long long)s->gz_piece_off[b]);
+    s->gz_verdict = msg;
+  }
+  for (size_t i = 0; i < pend.size(); i++) {
+    s->gz_crc = pend[i].len == 4096 ? crc32_combine_4096(s->gz_crc, crc[i]) : (uint32_t)crc32_combine(s->gz_crc, crc[i], (z_off_t)pend[i].len);
+    s->gz_member_len += pend[i].len;
+    if (pend[i].end < 0) continue;
+    const mgc_session::GzEnd &e = s->gz_ends[b][(size_t)pend[i].end];
+    if (s->gz_verdict.empty() && (s->gz_crc != e.crc || (uint32_t)s->gz_member_len != e.isize)) {
+      char msg[200];
+      if (s->gz_crc != e.crc) snprintf(msg, sizeof(msg), "CRC32 mismatch (member %llu, trailer at compressed offset %llu: %08x, text %08x)",
+                                       (unsigned long long)s->gz_members, (unsigned long long)e.comp_off, e.crc, s->gz_crc);
+      else snprintf(msg, sizeof(msg), "ISIZE mismatch (member %llu, trailer at compressed offset %llu: %u, text %llu bytes)",
+                    (unsigned long long)s->gz_members, (unsigned long long)e.comp_off, e.isize, (unsigned long long)s->gz_member_len);
+      s->gz_verdict = msg;
+    }
+    s->gz_crc = 0; s->gz_member_len = 0; s->gz_members++;
+  }
+  pend.clear();
+  s->gz_ends[b].clear();
+  s->tr_gz_collect += mgc::now_s() - t0;
+}
+
+int mgc::gzip_finish(mgc_session *s) {
+  const double t0 = mgc::now_s();
+  mgc::text_drain(s);
+  s->tr_gz_wait += mgc::now_s() - t0;
+  const uint32_t older = s->text_next & 1u;
+  gz_collect(s, older);
+  gz_collect(s, older ^ 1u);
+  return s->gz_verdict.empty() ? MGC_OK : mgc::GZIP_REFUSED;
+}
+
+int mgc::gzip_submit(mgc_session *s, const char *pinned_text, size_t piece, const uint16_t *symbols, size_t n_symbols, uint32_t window_valid,
+                     const mgc::GzMemberEnd *ends, size_t n_ends, uint64_t comp_off) {
+  if (piece == 0) {
+    // Nothing for the device (an empty member, the end of the file).  A submit that queues nothing would break the count by which the
+    // pump hands slots back (see bam_submit): it waits for both pieces in flight, and the trailers are checked here.
+    if (mgc::gzip_finish(s) != MGC_OK) return mgc::GZIP_REFUSED;
+    for (size_t i = 0; i < n_ends; i++) {
+      if (s->gz_verdict.empty() && (s->gz_crc != ends[i].crc || (uint32_t)s->gz_member_len != ends[i].isize)) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "CRC32 / ISIZE mismatch (member %llu, trailer at compressed offset %llu)", (unsigned long long)s->gz_members,
+                 (unsigned long long)ends[i].comp_off);
+        s->gz_verdict = msg;
+      }
+      s->gz_crc = 0; s->gz_member_len = 0; s->gz_members++;
+    }
+    return s->gz_verdict.empty() ? MGC_OK : mgc::GZIP_REFUSED;
+  }
+  if (piece > mgc_session::TEXT_CHUNK || n_symbols > piece || window_valid > mgc::GZ_WINDOW) { set_err(&s->err, "gzip_submit: a piece out of bounds"); return MGC_EINVAL; }
+  const uint32_t b = s->text_next & 1u;
+  const double w0 = mgc::now_s();
+  if (s->text_ev_used[b]) HIP_TRY(s, hipEventSynchronize(s->text_ev[b]));       // device buffers b (and their previous sources) are free again
+  s->tr_gz_wait += mgc::now_s() - w0;
+  gz_collect(s, b);
+  if (!s->gz_verdict.empty()) return mgc::GZIP_REFUSED;
+  s->gz_piece_off[b] = comp_off;
+  HIP_TRY(s, s->ensure_preserve(stage_id(s->fill), s->fill_len + piece + 4096, s->fill_len, s->st_in));
+  // the CRC table: pieces of at most 4 KiB that never cross a member's end
+  std::vector<mgc_session::GzCrcPiece> &pend = s->gz_pending[b];
+  const size_t want_tab = piece / 4096 + 2 * n_ends + 2;
+  if (s->gz_tab_cap[b] < want_tab) {
+    if (s->gz_tab_pinned[b]) { (void)hipHostFree(s->gz_tab_pinned[b]); s->gz_tab_pinned[b] = nullptr; s->gz_tab_cap[b] = 0; }
+    const size_t cap = want_tab + want_tab / 2 + 1024;
+    HIP_TRY(s, hipHostMalloc(reinterpret_cast<void **>(&s->gz_tab_pinned[b]), cap * 16 + 16, hipHostMallocDefault));
+    s->gz_tab_cap[b] = cap;
+  }
+  const size_t cap = s->gz_tab_cap[b];
+  const int tab_buf = b ? mgc_session::B_GZ_TAB1 : mgc_session::B_GZ_TAB0, sym_buf = b ? mgc_session::B_GZ_SYM1 : mgc_session::B_GZ_SYM0;
+  HIP_TRY(s, s->ensure(tab_buf, cap * 16 + 16));
+  uint64_t *h_begin = reinterpret_cast<uint64_t *>(s->gz_tab_pinned[b]);
+  uint32_t *h_len = reinterpret_cast<uint32_t *>(s->gz_tab_pinned[b] + 8 * cap);
+  size_t n_tab = 0;
+  uint64_t at = 0;
+  for (size_t e = 0; e <= n_ends; e++) {
+    const uint64_t stop = e < n_ends ? ends[e].text_off : piece;
+    if (stop < at || stop > piece) { set_err(&s->err, "gzip_submit: member ends out of order"); return MGC_EINVAL; }
+    do {                                                                         // (a member end with no text before it: one piece of 0 bytes)
+      const uint32_t l = (uint32_t)std::min<uint64_t>(4096, stop - at);
+      if (e == n_ends && l == 0) break;
+      h_begin[n_tab] = at; h_len[n_tab] = l;
+      at += l;
+      pend.push_back({l, (e < n_ends && at == stop) ? (int32_t)s->gz_ends[b].size() : -1});
+      n_tab++;
+    } while (at < stop);
+    if (e < n_ends) s->gz_ends[b].push_back({ends[e].crc, ends[e].isize, ends[e].comp_off});
+  }
+  if (n_symbols * 2 > s->gz_sym_cap[b]) {
+    if (s->gz_sym_pinned[b]) { (void)hipHostFree(s->gz_sym_pinned[b]); s->gz_sym_pinned[b] = nullptr; s->gz_sym_cap[b] = 0; }
+    const size_t want = std::min<size_t>(2 * mgc_session::TEXT_CHUNK, n_symbols * 3 + (1u << 20));
+    HIP_TRY(s, hipHostMalloc(reinterpret_cast<void **>(&s->gz_sym_pinned[b]), want, hipHostMallocDefault));
+    s->gz_sym_cap[b] = want;
+  }
+  HIP_TRY(s, s->ensure(sym_buf, std::max<size_t>(s->gz_sym_cap[b], 256)));
+  const double c0 = mgc::now_s();
+  if (n_symbols) memcpy(s->gz_sym_pinned[b], symbols, n_symbols * 2);
+  s->tr_gz_copy += mgc::now_s() - c0;
+  uint8_t *d_in = reinterpret_cast<uint8_t *>(s->buf[b ? mgc_session::B_TEXT_IN1 : mgc_session::B_TEXT_IN0].p);
+  uint8_t *d_tab = static_cast<uint8_t *>(s->buf[tab_buf].p);
+  uint8_t *d_win = static_cast<uint8_t *>(s->buf[mgc_session::B_GZ_WIN].p);
+  HIP_TRY(s, hipMemcpyAsync(d_in, pinned_text, piece, hipMemcpyHostToDevice, s->st_up));
+  if (n_symbols) HIP_TRY(s, hipMemcpyAsync(s->buf[sym_buf].p, s->gz_sym_pinned[b], n_symbols * 2, hipMemcpyHostToDevice, s->st_up));
+  HIP_TRY(s, hipMemcpyAsync(d_tab, h_begin, n_tab * 8, hipMemcpyHostToDevice, s->st_up));
+  HIP_TRY(s, hipMemcpyAsync(d_tab + 8 * cap, h_len, n_tab * 4, hipMemcpyHostToDevice, s->st_up));
+  HIP_TRY(s, hipEventRecord(s->up_ev[b], s->st_up));
+  HIP_TRY(s, hipStreamWaitEvent(s->st_in, s->up_ev[b], 0));
+  HIP_TRY(s, mgc::launch_gzip_resolve(d_in, piece, static_cast<const uint16_t *>(s->buf[sym_buf].p), n_symbols, d_win + (size_t)s->gz_win * mgc::GZ_WINDOW,
+                                      window_valid, d_win + (size_t)(s->gz_win ^ 1) * mgc::GZ_WINDOW, gz_error_word(s), s->st_in));
+  s->gz_win ^= 1;
+  HIP_TRY(s, mgc::launch_gzip_crc32(d_in, reinterpret_cast<const uint64_t *>(d_tab), reinterpret_cast<const uint32_t *>(d_tab + 8 * cap), n_tab,
+                                    reinterpret_cast<uint32_t *>(d_tab + 12 * cap), s->st_in));
+  HIP_TRY(s, hipMemcpyAsync(s->gz_tab_pinned[b] + 12 * cap, d_tab + 12 * cap, n_tab * 4, hipMemcpyDeviceToHost, s->st_in));
+  HIP_TRY(s, hipMemcpyAsync(s->gz_tab_pinned[b] + 16 * cap, gz_error_word(s), 4, hipMemcpyDeviceToHost, s->st_in));
+  HIP_TRY(s, mgc::launch_text_parse(d_in, piece, s->text_format == MGC_TEXT_FASTQ, s->buf[mgc_session::B_TEXT_STATE].p,
+                                    s->buf[mgc_session::B_TEXT_WS].p, stage_ptr(s, s->fill), s->st_in));
+  HIP_TRY(s, hipEventRecord(s->text_ev[b], s->st_in));
+  s->text_ev_used[b] = true;
+  s->text_next++;
+  s->fill_len += piece;                                     // an upper bound, as in text_submit
+  s->len_inexact = true;
+  if (s->fill_len >= s->batch_limit) return cut_batch(s);
+  return MGC_OK;
+}
+
+int mgc::gzip_refuse(mgc_session *s, const char *what, const char *why) {
+  const std::string w = why;                                // (why may point into the session's own strings)
+  mgc::text_drain(s);
+  for (int b = 0; b < 2; b++) { s->gz_pending[b].clear(); s->gz_ends[b].clear(); }
+  const int rc = mgc::text_rollback(s);
+  if (rc == MGC_EINVAL) set_err(&s->err, "'%s': %s, after part of the file was counted (input larger than one batch)", what, w.c_str());
+  if (rc != MGC_OK) return rc;
+  set_err(&s->err, "'%s': %s", what, w.c_str());
+  return MGC_EFORMAT;
+}
+
+extern "C" int mgc_dev_gzip_resolve(uint8_t *d_text, uint64_t text_bytes, const uint16_t *d_symbols, uint64_t n_symbols, const uint8_t *d_window_in,
+                                    uint32_t window_valid, uint8_t *d_window_out, uint32_t *d_error, void *stream) {
+  if ((!d_text && text_bytes) || (!d_symbols && n_symbols) || (n_symbols && !d_error) || n_symbols > text_bytes || window_valid > mgc::GZ_WINDOW ||
+      (!d_window_in && window_valid) || (d_window_out && d_window_out == d_window_in)) {
+    set_err(nullptr, "mgc_dev_gzip_resolve: n_symbols <= text_bytes, window_valid <= 32768 (0 without a window), two different windows");
+    return MGC_EINVAL;
+  }
+  HIP_TRY((mgc_session *)nullptr, mgc::launch_gzip_resolve(d_text, text_bytes, d_symbols, n_symbols, d_window_in, window_valid, d_window_out, d_error,
+                                                           static_cast<hipStream_t>(stream)));
+  return MGC_OK;
+}
+
+extern "C" int mgc_dev_crc32_pieces(const uint8_t *d_text, const uint64_t *d_begin, const uint32_t *d_len, uint64_t n_pieces, uint32_t *d_crc, void *stream) {
+  if (n_pieces && (!d_text || !d_begin || !d_len || !d_crc)) return MGC_EINVAL;
+  HIP_TRY((mgc_session *)nullptr, mgc::launch_gzip_crc32(d_text, d_begin, d_len, n_pieces, d_crc, static_cast<hipStream_t>(stream)));
   return MGC_OK;
 }
 

@@ -382,6 +382,16 @@ hipError_t launch_text_parse(const uint8_t *d_text, uint64_t n, int fastq, void 
 // fields through the nt16 alphabet, '.' after the flagged segments.  The running length of the stream is the caller's business.
 hipError_t launch_bam_decode(const uint8_t *d_piece, uint64_t piece_bytes, const void *d_segments, uint64_t n_segments, uint64_t out_total,
                              uint8_t *d_out, hipStream_t st);
+// ---- the parallel gzip reader's second pass (mgc_gzip.hip) ----
+// One piece of a gzip stream's text in HBM (text_bytes at d_text, any alignment) whose first n_symbols bytes are still unresolved:
+// d_symbols holds them as 16-bit symbols (mgc_gzip_par.hpp), 0x8000 + o standing for byte o of the 32 KiB window before the piece
+// (d_window_in; only its last window_valid bytes belong to the piece's gzip member).  Patches d_text in place; a symbol that is
+// neither a byte nor a marker inside the valid window ORs 1 / 2 into *d_error and becomes 0.  d_window_out (another buffer, or
+// null): the window after the piece.  n_symbols == 0 and d_window_in == null (with window_valid 0) are fine.
+hipError_t launch_gzip_resolve(uint8_t *d_text, uint64_t text_bytes, const uint16_t *d_symbols, uint64_t n_symbols, const uint8_t *d_window_in,
+                               uint32_t window_valid, uint8_t *d_window_out, uint32_t *d_error, hipStream_t st);
+// d_crc[i] = CRC-32 of d_text[d_begin[i] .. + d_len[i]), d_len[i] <= 4096 (more is not read)
+hipError_t launch_gzip_crc32(const uint8_t *d_text, const uint64_t *d_begin, const uint32_t *d_len, uint64_t n_pieces, uint32_t *d_crc, hipStream_t st);
 // what: 0 begin file, 1 end file (breaker), 2 roll the current file back, 3 reset
 hipError_t launch_text_file_op(void *d_state, uint8_t *d_out, int what, hipStream_t st);
 // the stream now holds new_len bytes (bases appended by a plain copy, or the tail kept after a batch was cut off);

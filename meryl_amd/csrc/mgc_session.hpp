@@ -85,7 +85,9 @@ struct mgc_session {
          B_TEXT_STATE, B_RK, B_RC, B_R2K, B_R2C, B_MERGE_WS, B_SORT_HDRS, B_FINE, B_NARROW_WS, B_Y2, B_Y3, B_Y4, B_HWS0, B_HWS1, B_HWS2, B_HWS3,
          B_PACKED /* the count's packed base stream: 2-bit codes + invalid-base masks, written by the histogram, read by the partition */,
          B_GROUP_BATCH /* the batched grouping launches' control words and descriptor tables (mgc_count.cpp, group_batches) */,
-         B_BAM_SEG0, B_BAM_SEG1 /* the segment tables of the two BAM pieces in flight (mgc_bam_walk.hpp) */, B_NUM };
+         B_BAM_SEG0, B_BAM_SEG1 /* the segment tables of the two BAM pieces in flight (mgc_bam_walk.hpp) */,
+         B_GZ_SYM0, B_GZ_SYM1 /* the unresolved symbols of the two gzip pieces in flight (mgc_gzip.hip) */, B_GZ_TAB0, B_GZ_TAB1 /* their CRC
+         piece tables and results */, B_GZ_WIN /* two 32 KiB windows, ping-pong, and the error word */, B_NUM };
   Buf buf[B_NUM];
   size_t arena_bytes() const { size_t t = 0; for (const auto &b : buf) t += b.cap; return t; }
   double tr_alloc = 0;                   // seconds inside hipMalloc / hipFree of the arena (MGC_IO_TRACE)
@@ -161,6 +163,22 @@ struct mgc_session {
   mgc::BamSegment *bam_seg_pinned[2] = {nullptr, nullptr};   // pinned, grow-only, one per device input buffer
   size_t      bam_seg_cap[2] = {0, 0};                   // segments
   double      tr_bam_walk = 0;                           // seconds in the walker, this file (MGC_IO_TRACE)
+  // gzip (mgc_push_text_gzip_file): the open file is a text file whose pieces come with the symbols of an unresolved prefix; they are
+  // resolved on the device before the parse kernels read them, and the CRC-32 of every member is computed there over the resolved text
+  struct GzCrcPiece { uint32_t len; int32_t end; };       // one entry of a piece's CRC table; end >= 0: a member ends after it (gz_ends[b][end])
+  struct GzEnd { uint32_t crc, isize; uint64_t comp_off; };
+  int         gz_win = 0;                                 // which of the two windows holds the text before the next piece
+  char       *gz_sym_pinned[2] = {nullptr, nullptr};      // pinned, grow-only, one per device input buffer
+  size_t      gz_sym_cap[2] = {0, 0};                     // bytes
+  char       *gz_tab_pinned[2] = {nullptr, nullptr};      // {begin[cap], len[cap], crc[cap], error}: up, up, down, down
+  size_t      gz_tab_cap[2] = {0, 0};                     // entries
+  std::vector<GzCrcPiece> gz_pending[2];                  // what the results in gz_tab_pinned[b] will mean
+  std::vector<GzEnd> gz_ends[2];
+  uint32_t    gz_crc = 0;                                 // of the current member, over the pieces collected so far
+  uint64_t    gz_member_len = 0, gz_members = 0;
+  std::string gz_verdict;                                 // non-empty: the stream is refused
+  uint64_t    gz_piece_off[2] = {0, 0};                   // where in the file the piece in buffer b starts (for the verdict)
+  double      tr_gz_copy = 0, tr_gz_collect = 0, tr_gz_wait = 0;   // seconds of this file's submits in the symbol copy, in folding the CRCs, waiting for the device (MGC_IO_TRACE)
   // host-pushed bases: two pinned chunks, the upload of one overlaps the filling of the other
   char       *pin[2] = {nullptr, nullptr};
   size_t      pin_len = 0;
@@ -235,6 +253,21 @@ int bam_submit(mgc_session *s, const char *pinned_src, size_t piece);
 // closes the refused BAM file and rolls it back: MGC_EFORMAT with "'what': the walker's words" as the session's error, or
 // MGC_EINVAL when part of the file was already counted
 int bam_refuse(mgc_session *s, const char *what);
+// The open text file as a gzip stream (gzip_begin after mgc_begin_text): one piece of its text (<= TEXT_CHUNK, in pinned memory) whose
+// first n_symbols bytes are unresolved -- `symbols` holds them (mgc_gzip_par.hpp) -- window_valid bytes of its gzip member before it, and
+// the members that end inside it.  Uploads text and symbols, queues resolve -> window -> CRC and the parse kernels; returns once that is
+// queued.  GZIP_REFUSED (> 0): a CRC32 / ISIZE of an earlier piece did not match its trailer or the device met an unresolvable symbol
+// (s->gz_verdict); the file is still open (gzip_refuse closes it).
+struct GzMemberEnd;
+constexpr int GZIP_REFUSED = 1;
+int gzip_begin(mgc_session *s);
+int gzip_submit(mgc_session *s, const char *pinned_text, size_t piece, const uint16_t *symbols, size_t n_symbols, uint32_t window_valid,
+                const GzMemberEnd *ends, size_t n_ends, uint64_t comp_off);
+// waits for the pieces in flight and checks what they brought back; GZIP_REFUSED as above
+int gzip_finish(mgc_session *s);
+// closes the refused file and rolls it back: MGC_EFORMAT with "'what': why" as the session's error, or MGC_EINVAL when part of the file
+// was already counted
+int gzip_refuse(mgc_session *s, const char *what, const char *why);
 // mgc_end_bam with the name the refusal of a stream that ends inside the header or a record is reported under
 int bam_end(mgc_session *s, const char *what);
 }  // namespace mgc

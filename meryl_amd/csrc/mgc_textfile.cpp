@@ -1,11 +1,13 @@
 // mgc_textfile.cpp -- whole FASTA / FASTQ files into a session's base stream (include/meryl_gpu_count.h): plain files read
 // with pread, BGZF files inflated, by several threads STRAIGHT into a ring of pinned buffers (mgc_chunk_ring.hpp) that the
-// calling thread uploads and parses in file order; BGZF BAM files likewise, walked and decoded instead of parsed.  The session
-// is reached through mgc_begin_text / mgc_end_text / mgc_begin_bam / mgc_end_bam and text_submit / bam_submit / text_drain /
-// text_rollback / bam_refuse (mgc_session.hpp) only.
+// calling thread uploads and parses in file order; BGZF BAM files likewise, walked and decoded instead of parsed; plain gzip files
+// through the pump of mgc_gzip_par.hpp, whose pieces the device resolves (mgc_gzip.hip).  The session is reached through mgc_begin_text /
+// mgc_end_text / mgc_begin_bam / mgc_end_bam and text_submit / bam_submit / gzip_submit / text_drain / text_rollback / bam_refuse /
+// gzip_refuse (mgc_session.hpp) only.
 #include "../../include/meryl_gpu_count.h"
 #include "mgc_bgzf.hpp"
 #include "mgc_chunk_ring.hpp"
+#include "mgc_gzip_par.hpp"
 #include "mgc_session.hpp"
 
 #include <algorithm>
@@ -316,4 +318,133 @@ extern "C" int mgc_push_bam_file(mgc_session *s, const char *path, int threads) 
   if (refused) return mgc::bam_refuse(s, path);
   if (res.end == mgc::ChunkRingResult::CONSUMER_STOPPED) { (void)mgc::text_rollback(s); return res.detail; }
   return mgc::bam_end(s, path);                                 // a stream that ends inside a record is refused here, by the file's name
+}
+
+// ---- a plain gzip file (one deflate stream per member, no block index): mgc_gzip_par.hpp's workers inflate it from guessed block starts
+// STRAIGHT into the pinned upload ring, writing markers for what they cannot know; the calling thread takes the pieces in stream order
+// and queues upload -> resolve -> window -> CRC -> parse (gzip_submit).  Through the generic reader one gzread thread bounds the file.
+extern "C" int mgc_is_gzip_file(const char *path) {
+  if (!path) return 0;
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return 0;
+  unsigned char head[64];
+  const ssize_t got = pread(fd, head, sizeof(head), 0);
+  close(fd);
+  mgc::BgzfBlock b;
+  if (got < 18 || !mgc::gz_is_gzip(head, (size_t)got)) return 0;
+  return mgc::bgzf_parse_block(head, (size_t)got, &b) == mgc::BGZF_NOT_BLOCK ? 1 : 0;
+}
+
+namespace {
+// Compressed bytes per span.  A worker's output should fit one 32 MiB slot without a cut, and reads compress three- to six-fold:
+// 4 MiB of file are 12 .. 24 MiB of text.  (A file that compresses better is cut into more pieces; nothing else changes.)  Smaller
+// spans spend more of a worker's time in the finder and in markers (each piece's first 32 KiB and what is copied on from them).
+constexpr uint64_t GZIP_SPAN_DEFAULT = 4u << 20;
+uint64_t env_u64(const char *name, uint64_t dflt, uint64_t lo, uint64_t hi) {
+  const char *v = getenv(name);
+  if (!v || !*v) return dflt;
+  const uint64_t x = strtoull(v, nullptr, 10);
+  return std::min(std::max(x, lo), hi);
+}
+}  // namespace
+
+extern "C" int mgc_push_text_gzip_file(mgc_session *s, const char *path, int format, int threads, mgc_gzip_info *info) {
+  if (!s || !path) return MGC_EINVAL;
+  if (info) memset(info, 0, sizeof(*info));
+  uint64_t fsize = 0;
+  const int fd = open_regular(&s->err, "mgc_push_text_gzip_file", path, "regular file", 0, &fsize);
+  if (fd < 0) return MGC_EINVAL;
+  if (fsize < 18) { close(fd); set_err(&s->err, "'%s' is not a gzip file (%llu bytes)", path, (unsigned long long)fsize); return MGC_EFORMAT; }
+  const unsigned char *map = reinterpret_cast<const unsigned char *>(mmap(nullptr, fsize, PROT_READ, MAP_SHARED, fd, 0));
+  if (map == MAP_FAILED) { close(fd); set_err(&s->err, "mgc_push_text_gzip_file: mmap of '%s' failed: %s", path, strerror(errno)); return MGC_EINVAL; }
+  auto release = [&]() { munmap(const_cast<unsigned char *>(map), fsize); close(fd); };
+  if (!mgc::gz_is_gzip(map, fsize)) { release(); set_err(&s->err, "'%s' is not a gzip file", path); return MGC_EFORMAT; }
+  if (format != 0 && format != MGC_TEXT_FASTA && format != MGC_TEXT_FASTQ) { release(); return MGC_EINVAL; }
+
+  mgc::GzOptions opt;
+  opt.span = env_u64("MGC_GZIP_SPAN", GZIP_SPAN_DEFAULT, 4096, 1ull << 40);
+  opt.cap = env_u64("MGC_GZIP_TEXT_CAP", mgc_session::TEXT_CHUNK, 65536, mgc_session::TEXT_CHUNK);
+  const mgc::ChunkRingGeometry g = mgc::chunk_ring_geometry(threads, std::max<uint64_t>(1, fsize / opt.span), mgc_session::TEXT_RING_MAX);
+  opt.threads = g.threads; opt.n_slots = g.slots; opt.lag = 2;
+
+  bool begun = false, refused = false, bad_format = false;
+  char first = 0;
+  int rc = MGC_OK;
+  auto begin = [&](const char *text, size_t len) -> int {       // the first piece with text: it starts at a member's header, so it is exact
+    if (format == 0) {
+      first = first_text_byte(reinterpret_cast<const unsigned char *>(text), len);
+      format = format_of(first ? first : '>');
+      if (!format) { bad_format = true; return MGC_EFORMAT; }
+    }
+    int r = mgc_begin_text(s, format);
+    if (r == MGC_OK) r = mgc::gzip_begin(s);
+    begun = r == MGC_OK;
+    return r;
+  };
+  auto alloc = [s]() -> char * {
+    char *p = nullptr;
+    (void)hipSetDevice(s->device);
+    return hipHostMalloc(reinterpret_cast<void **>(&p), mgc_session::TEXT_CHUNK, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+  };
+  auto consume = [&](const mgc::GzPieceView &v) -> int {
+    if (!begun) {
+      if (v.n_symbols) return MGC_EINVAL;                       // (cannot be: nothing precedes the first text)
+      if (v.text_len == 0) {                                    // empty members in front: their trailers must say so
+        for (size_t i = 0; i < v.n_ends; i++)
+          if (v.ends[i].crc != 0 || v.ends[i].isize != 0) {
+            char msg[120];
+            snprintf(msg, sizeof(msg), "CRC32 / ISIZE mismatch (an empty member, trailer at compressed offset %llu)", (unsigned long long)v.ends[i].comp_off);
+            s->gz_verdict = msg; refused = true;
+            return mgc::GZIP_REFUSED;
+          }
+        mgc::text_drain(s);
+        return MGC_OK;
+      }
+      const int r = begin(v.text, v.text_len);                  // (text of white space only: FASTA, as for a plain file)
+      if (r != MGC_OK) return r;
+    }
+    const int r = mgc::gzip_submit(s, v.text, v.text_len, v.symbols, v.n_symbols, v.window_valid, v.ends, v.n_ends, v.comp_off);
+    if (r == mgc::GZIP_REFUSED) refused = true;
+    return r;
+  };
+  const mgc::GzResult res = mgc::gz_run(map, fsize, opt, s->text_ring, alloc, consume);
+  if (begun && !refused && res.end == mgc::GzResult::DONE && mgc::gzip_finish(s) != MGC_OK) refused = true;
+  mgc::text_drain(s);                                           // the last uploads still read from the ring
+  release();
+  if (info) {
+    info->members = res.info.members; info->chunks = res.info.chunks; info->confirmed = res.info.confirmed; info->discarded = res.info.discarded;
+    info->text_bytes = res.info.text_bytes; info->symbol_bytes = res.info.symbol_bytes; info->cuts = res.info.cuts;
+  }
+  if (getenv("MGC_IO_TRACE"))
+    fprintf(stderr, "[io] gzip file %.2f GB -> %.2f GB of text (%.2f GB of symbols) in %llu chunks (%llu confirmed, %llu discarded, %llu cuts), %d inflaters, "
+                    "ring %d: waiting for the inflaters %.3f s, upload+resolve+parse submit (incl. waits for the device) %.3f s; inflaters: finder %.3f s, "
+                    "inflate %.3f s, waiting for a candidate %.3f s, waiting for a free slot %.3f s; of the submit: symbol copy %.3f s, CRC fold %.3f s, "
+                    "waiting for the device %.3f s\n", fsize / 1e9, res.info.text_bytes / 1e9,
+            res.info.symbol_bytes / 1e9, (unsigned long long)res.info.chunks, (unsigned long long)res.info.confirmed, (unsigned long long)res.info.discarded,
+            (unsigned long long)res.info.cuts, opt.threads, opt.n_slots, res.t_wait, res.t_consume, res.t_find, res.t_inflate, res.t_confirm, res.t_slot_wait, s->tr_gz_copy, s->tr_gz_collect, s->tr_gz_wait);
+  if (res.end == mgc::GzResult::ALLOC_FAILED) {
+    set_err(&s->err, "mgc_push_text_gzip_file: pinned buffers: out of memory");
+    if (begun) (void)mgc::text_rollback(s);
+    return MGC_ENOMEM;
+  }
+  if (bad_format) { set_err(&s->err, "'%s' is neither FASTA nor FASTQ (record starts with '%c')", path, first ? first : '?'); return MGC_EFORMAT; }
+  if (res.end == mgc::GzResult::FORMAT) {
+    char why[200];
+    snprintf(why, sizeof(why), "damaged gzip stream at compressed offset %llu (%s)", (unsigned long long)res.offset, mgc::gz_err_text(res.detail));
+    if (begun) return mgc::gzip_refuse(s, path, why);
+    set_err(&s->err, "'%s': %s", path, why);
+    return MGC_EFORMAT;
+  }
+  if (refused && !begun) { set_err(&s->err, "'%s': %s", path, s->gz_verdict.c_str()); return MGC_EFORMAT; }
+  if (refused) return mgc::gzip_refuse(s, path, s->gz_verdict.c_str());
+  if (res.end == mgc::GzResult::CONSUMER_STOPPED) {             // a HIP error, or the worker thread's
+    rc = res.detail;
+    if (begun) (void)mgc::text_rollback(s);
+    return rc;
+  }
+  if (!begun) {                                                 // no text at all: an empty file of the format asked for (FASTA when unknown)
+    rc = mgc_begin_text(s, format ? format : MGC_TEXT_FASTA);
+    if (rc != MGC_OK) return rc;
+  }
+  return mgc_end_text(s);                                       // closes the file in every case (rolls it back on MGC_EFORMAT)
 }

@@ -5,7 +5,7 @@ import re, subprocess, sys, os
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = ""
 names = ("mgc_kmer.hip", "mgc_sort.hip", "mgc_scan.hip", "mgc_finish.hip", "mgc_misc.hip", "mgc_parse.hip", "mgc_merge.hip", "mgc_merge_many.hip", "mgc_decode.hip", "mgc_encode.hip", "mgc_value_hist.hip",
-         "mgc_lookup.hip", "mgc_filter.hip", "mgc_import.hip", "mgc_analyze.hip", "mgc_positions.hip", "mgc_list.hip")
+         "mgc_lookup.hip", "mgc_filter.hip", "mgc_import.hip", "mgc_analyze.hip", "mgc_positions.hip", "mgc_list.hip", "mgc_gzip.hip")
 for name in (sys.argv[2:] or names):
     src = os.path.join(root, "meryl_amd", "csrc", name)
     out += subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "-Rpass-analysis=kernel-resource-usage",
