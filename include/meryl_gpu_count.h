@@ -728,7 +728,8 @@ typedef struct mgc_profile {
   uint64_t stream_retries;         /* sub-buckets with more distinct suffixes than that kernel's table holds (counted by its retry launch) */
   double   probe_ratio;            /* distinct / instances of the probe file that chose between the plans (0: no probe ran) */
   /* what the rest of the count stage lasts (offsets of the sub-buckets in the packed result + the packing kernels of all files), on
-   * the session stream behind the count kernels: stage_ms[MGC_STAGE_RLE] - pack_ms = the wall clock of the count kernels themselves */
+   * the session stream behind the count kernels: stage_ms[MGC_STAGE_RLE] - pack_ms = the wall clock of the count kernels themselves.
+   * With early packing (early_pack_files below) that is only the part of the packing the count kernels do not hide */
   double   pack_ms;
   uint64_t hist_bytes;             /* ALGORITHMIC bytes of the histogram kernel (the bases read + the packed base stream it stores, 6 bytes per
                                     * 16 bases, where the count has one: not with MGC_PACKED_BASES=0) ... */
@@ -737,6 +738,14 @@ typedef struct mgc_profile {
   /* kernel launches of the first / the second grouping pass: pass_launches[] counts one per FILE and pass whether or not files shared a
    * launch; a batched launch over m files (mgc_device.h, GroupBatch) adds m there and 1 here */
   uint32_t pass_kernel_launches[2];
+  /* early packing (files packed on a third stream while later files are still counted; MGC_PACK_OVERLAP=0: off): files packed by
+   * the chain on that stream (not deferred; WHEN their launches ran against the count kernels a kernel trace shows, not this number),
+   * and files the device deferred to the serial path behind the last count kernel (a retry list, a result without room).  Both 0:
+   * the count took the serial path for every file.  pack_ms is only the part of the packing the count kernels did not hide: from
+   * the end of the last count kernel to the end of the last packing launch */
+  uint32_t early_pack_files, early_pack_deferred;
+  int32_t  probe_file;             /* the file that was counted first to choose the others' plan (probe_ratio); -1: no probe ran */
+  uint32_t reserved_;
 } mgc_profile;
 int mgc_set_profiling(mgc_session *s, int enable);
 int mgc_get_profile(const mgc_session *s, mgc_profile *p);

@@ -207,6 +207,10 @@ class Profile(ctypes.Structure):
         ("hist_bytes", ctypes.c_uint64),
         ("partition_bytes", ctypes.c_uint64),
         ("pass_kernel_launches", ctypes.c_uint32 * 2),
+        ("early_pack_files", ctypes.c_uint32),
+        ("early_pack_deferred", ctypes.c_uint32),
+        ("probe_file", ctypes.c_int32),
+        ("reserved_", ctypes.c_uint32),
     ]
 
 

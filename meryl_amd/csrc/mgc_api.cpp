@@ -49,6 +49,9 @@ Switches read_switches() {
   sw.pass_stagger = (uint32_t)num("MGC_PASS_STAGGER", 0);
   sw.group_batch_bytes = num("MGC_GROUP_BATCH_BYTES", sw.group_batch_bytes);
   sw.group_batch_files = (uint32_t)num("MGC_GROUP_BATCH_FILES", 0);
+  sw.pack_overlap = !off("MGC_PACK_OVERLAP");
+  { const char *e = getenv("MGC_PACK_MARGIN"); if (e && *e) sw.pack_margin = strtoll(e, nullptr, 10); }
+  sw.pack_ratio = (uint32_t)num("MGC_PACK_RATIO", 0);
   return sw;
 }
 }  // namespace mgc
@@ -718,6 +721,8 @@ extern "C" void mgc_close(mgc_session *s) {
   if (s->h_stats) (void)hipHostFree(s->h_stats);
   if (s->ev_join) (void)hipEventDestroy(s->ev_join);
   if (s->stream2) (void)hipStreamDestroy(s->stream2);
+  for (hipEvent_t e : s->pack_ev) (void)hipEventDestroy(e);
+  if (s->ev_pack_done) (void)hipEventDestroy(s->ev_pack_done);
   for (int i = 0; i < mgc_session::HUGE_EXTRA; i++) if (s->stream_h[i]) (void)hipStreamDestroy(s->stream_h[i]);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;

@@ -4,6 +4,7 @@
 #include "mgc_session.hpp"
 #include "mgc_group_batch.hpp"
 #include "mgc_group_route.hpp"
+#include "mgc_pack_plan.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -347,6 +348,15 @@ struct Count {
   int n_huge_streams = 1, huge_next = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> fin_ev; // profiling: around every file's count-kernel launch
   uint64_t fin_keys = 0, fin_in_bytes = 0; bool fin_narrow = false;
+  // early packing (mgc_pack_plan.hpp): the files are packed on pack_st, in index order, while later files are still counted
+  bool early = false;
+  std::vector<uint32_t> chain;                           // the files that hold k-mers, in index order: the packing chain
+  std::vector<int> chain_pos;                            // a file's place in it (-1: empty)
+  std::vector<char> pack_ev2;                            // the file has a second event to wait for (s->pack_ev[nb + b])
+  uint64_t *d_pstate = nullptr;                          // mgc_device.h, launch_pack_gate_scan
+  hipStream_t pack_st = nullptr;
+  uint64_t early_cap = 0;                                // k-mers the result had room for when the chain was queued
+  hipEvent_t ev_pack[2] = {nullptr, nullptr};            // profiling: around what the count kernels do not hide of the packing
 
   Count(mgc_session *s_, const mgc::CountInput &in_, uint32_t bucket_bits_)
       : s(s_), in(in_), st(s_->stream), c(s_->cfg), sw(s_->sw), prof(s_->prof), k(c.k), kw(s_->key_words), bucket_bits(bucket_bits_),
@@ -378,7 +388,9 @@ struct Count {
   int huge_setup(); int huge_sync_all(); int huge_join_all();
   int finish_file(uint32_t b); int oversized_streams(uint32_t b, bool *stream); int widen_back(uint32_t b, bool *unordered);
   int count_file(uint32_t b, bool stream); int fallback_file(uint32_t b, bool unordered);
-  int trace_slices(); int retry(); int scan_pack(); int pack_file(uint32_t b); void finish_profile();
+  int trace_slices(); int retry(); int scan_pack(); void finish_profile();
+  int pack_file(uint32_t b, hipStream_t ps, const uint64_t *d_gate = nullptr, uint64_t gate_above = 0);
+  int pack_events(); int pack_plan(); int pack_step(uint32_t b); int pack_finish(); int pack_done();
   int block_offsets(); void collect_profile();
 };
 
@@ -966,6 +978,11 @@ int Count::count_file(uint32_t b, bool stream) {
   }
   HIP_TRY(s, mgc::launch_finish_file(finish_desc(b, stream, fst, hsel)));
   if (s->profiling) (void)hipEventRecord(fin_ev.back().second, fst);
+  if ((size_t)nb + b < s->pack_ev.size()) {              // (the packing chain waits for them: pack_step)
+    HIP_TRY(s, hipEventRecord(s->pack_ev[b], fst));
+    pack_ev2[b] = stream && x.nlarge > 0 && hstream[hsel] != fst;          // ... the streaming launch of its oversized list
+    if (pack_ev2[b]) HIP_TRY(s, hipEventRecord(s->pack_ev[(size_t)nb + b], hstream[hsel]));
+  }
   return MGC_OK;
 }
 
@@ -1022,7 +1039,6 @@ int Count::retry() {
 
 // ---- E/F. offsets of every sub-bucket in the packed result; G/H. pack ----
 int Count::scan_pack() {
-  hipEvent_t ev_pack[2] = {nullptr, nullptr};
   if (s->profiling) { (void)hipEventCreate(&ev_pack[0]); (void)hipEventCreate(&ev_pack[1]); (void)hipEventRecord(ev_pack[0], st); }
   HIP_TRY(s, mgc::launch_finish_scan(d_group, plan.ng_total, s->buf[S::B_GSCAN].p, st));
   HIP_TRY(s, hipMemcpyAsync(&nd, d_group + plan.ng_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -1039,7 +1055,11 @@ int Count::scan_pack() {
     s->d_unique = s->buf[S::B_UNIQUE].p;
     s->d_counts = reinterpret_cast<uint32_t *>(s->buf[S::B_COUNTS].p);
   }
-  for (uint32_t b = 0; b < nb; b++) TRY(pack_file(b));
+  for (uint32_t b = 0; b < nb; b++) TRY(pack_file(b, st));
+  return pack_done();
+}
+
+int Count::pack_done() {
   if (s->profiling) (void)hipEventRecord(ev_pack[1], st);
   tm.end(MGC_STAGE_RLE);
   prof.stage_launches[MGC_STAGE_RLE] = 4 * nb;
@@ -1052,25 +1072,166 @@ int Count::scan_pack() {
   return MGC_OK;
 }
 
-int Count::pack_file(uint32_t b) {
+int Count::pack_file(uint32_t b, hipStream_t ps, const uint64_t *d_gate, uint64_t gate_above) {
   const FilePlan &x = plan.files[b];
   if (x.size == 0) return MGC_OK;
   void *sg = seg(b);
   if (x.kind == Group::NARROW) {
     HIP_TRY(s, mgc::launch_compact_groups_narrow(sg, x.cnt, d_substart + x.sbase, d_group + x.gbase, x.ngf(), (uint64_t)b << rem_bits, low(x),
-                                                 s->d_unique, s->d_counts, st, x.tr_a, x.tr_b, nz_list(x), x.nzcount));
+                                                 s->d_unique, s->d_counts, ps, x.tr_a, x.tr_b, nz_list(x), x.nzcount, d_gate, gate_above));
   } else if (!x.fallback && x.k96) {
     const unsigned __int128 fb = (unsigned __int128)b << rem_bits;
     HIP_TRY(s, mgc::launch_compact_groups_k96(sg, x.cnt, d_substart + x.sbase, d_group + x.gbase, x.ngf(), (uint64_t)fb, (uint64_t)(fb >> 64),
-                                              s->d_unique, s->d_counts, st, x.tr_a, x.tr_b, nz_list(x), x.nzcount));
+                                              s->d_unique, s->d_counts, ps, x.tr_a, x.tr_b, nz_list(x), x.nzcount, d_gate, gate_above));
   } else if (!x.fallback) {
-    HIP_TRY(s, mgc::launch_compact_groups(sg, kw, x.cnt, d_substart + x.sbase, d_group + x.gbase, x.ngf(), s->d_unique, s->d_counts, st,
-                                          x.tr_a, x.tr_b, nz_list(x), x.nzcount));
-  } else {
-    HIP_TRY(s, mgc::launch_rle_count(sg, x.size, kw, rle_ws, st));
-    HIP_TRY(s, mgc::launch_rle_emit(sg, x.size, kw, rle_ws, s->d_unique, s->d_counts, st, d_group + x.gbase));
+    HIP_TRY(s, mgc::launch_compact_groups(sg, kw, x.cnt, d_substart + x.sbase, d_group + x.gbase, x.ngf(), s->d_unique, s->d_counts, ps,
+                                          x.tr_a, x.tr_b, nz_list(x), x.nzcount, d_gate, gate_above));
+  } else {                                               // (never early: mgc_pack_plan.hpp, pack_file_ok)
+    HIP_TRY(s, mgc::launch_rle_count(sg, x.size, kw, rle_ws, ps));
+    HIP_TRY(s, mgc::launch_rle_emit(sg, x.size, kw, rle_ws, s->d_unique, s->d_counts, ps, d_group + x.gbase));
   }
   return MGC_OK;
+}
+
+// ---- early packing: a file is packed while the files after it are still being counted ----
+// The count kernels are bound by instruction issue, the packing kernels by memory: behind each other each leaves idle what the other
+// needs.  Nothing but a file's offset in the result makes them serial, and that is the sum of the distinct k-mers of the files before
+// it.  So the files are packed in index order on a third stream (pack_st), file i as soon as its count kernel and those of
+// the files before it have ended: a gate and the scan of its slice of d_group with the carry-in base[i] (mgc_finish.hip,
+// pack_gate_scan_kernel), then the packing launch of file i - 1 -- one step behind, because the last sub-bucket of a
+// file ends at d_group[first slot of the next file], which the next file's scan writes.  d_group ends up as the scan of all files
+// leaves it.  What can still go wrong once the chain is queued is decided on the device and is sticky (a file with sub-buckets on the
+// retry list, or a result without room: that file and every later one stay untouched); pack_finish then takes the serial path from
+// there.  Which counts take it at all, and how much room the result gets beforehand: mgc_pack_plan.hpp.
+int Count::pack_events() {                               // once per session: two events per file, behind its count launch(es)
+  if (!sw.pack_overlap) return MGC_OK;
+  pack_ev2.assign(nb, 0);
+  while (s->pack_ev.size() < 2 * (size_t)nb) {
+    hipEvent_t e = nullptr;
+    HIP_TRY(s, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    s->pack_ev.push_back(e);
+  }
+  return MGC_OK;
+}
+
+int Count::pack_plan() {                                 // the statistics of all files are back, nothing but the probe file is counted
+  if (!sw.pack_overlap || s->pack_ev.size() < 2 * (size_t)nb) return MGC_OK;
+  std::vector<mgc::PackFile> pf(nb);
+  uint32_t listed = 0;
+  for (uint32_t b = 0; b < nb; b++) {
+    const FilePlan &x = plan.files[b];
+    pf[b] = mgc::PackFile{x.size, x.maxsub, x.nlarge, mgc::finish_uses_hash(kw, low(x)), x.fallback};
+    listed += x.size && x.nlarge ? 1u : 0u;
+  }
+  const bool eligible = mgc::pack_overlap_eligible(pf, plan.cap, sw.stream_max, true);
+  if (sw.finish_trace) fprintf(stderr, "[finish] early packing: %u files have an oversized list; the count is %s\n", listed, eligible ? "eligible" : "not eligible");
+  if (!eligible) return MGC_OK;
+  // The stream: the session's input stream, which has a hardware queue to itself (created at mgc_open between the two count streams)
+  // and is idle while the caller's own thread counts (mgc_count has waited for everything queued there).  Not while the worker
+  // thread counts a batch: the caller is then pushing the next one through it.  A stream of its own, created on first need behind
+  // all the others, shares a hardware queue with a count stream -- four queues, the note at huge_setup -- and the chain's waits
+  // then hold that stream's count kernels back: measured slower than no early packing at all (profiles/pack_overlap_ab.txt).
+  // For the same reason not where huge_setup has created further streams for gigantic sub-buckets: one of them may share the
+  // chain's queue (not measured).  Decided before the arena is touched: such a count keeps the result buffers it has.
+  if (s->worker_active || !s->st_in || n_huge_streams > 1) return MGC_OK;
+  pack_st = s->st_in;
+  const bool caller = in.out_keys && in.out_counts;
+  auto arena_kmers = [&]() { return mgc::pack_buffers_kmers(s->buf[S::B_UNIQUE].cap, s->buf[S::B_COUNTS].cap, kbytes); };
+  const double ratio = probe >= 0 ? prof.probe_ratio : (double)sw.pack_ratio / 1000.0;
+  const uint64_t est = mgc::pack_estimate(ratio, N, sw.pack_margin);
+  const uint64_t want = mgc::pack_arena_want(caller, est, arena_kmers());
+  if (want && (s->ensure(S::B_UNIQUE, kbytes * want) != hipSuccess || s->ensure(S::B_COUNTS, sizeof(uint32_t) * want) != hipSuccess))
+    (void)hipGetLastError();                             // (the arena cannot grow: what is there has to do)
+  early_cap = mgc::pack_capacity(caller, in.out_cap, arena_kmers());
+  if (sw.finish_trace) fprintf(stderr, "[finish] early packing: %llu k-mers, %llu distinct expected (%s %.4f, margin %lld/1000), room for %llu%s\n",
+                               (unsigned long long)N, (unsigned long long)est, probe >= 0 ? "probe file's ratio" : (sw.pack_ratio ? "MGC_PACK_RATIO" : "no probe file: ratio"), ratio, (long long)sw.pack_margin,
+                               (unsigned long long)early_cap, caller ? " in the caller's buffers" : "");
+  if (early_cap == 0) return MGC_OK;
+  if (!s->ev_pack_done && hipEventCreateWithFlags(&s->ev_pack_done, hipEventDisableTiming) != hipSuccess) { s->ev_pack_done = nullptr; (void)hipGetLastError(); return MGC_OK; }
+  chain_pos.assign(nb, -1);
+  for (uint32_t b = 0; b < nb; b++) if (plan.files[b].size) { chain_pos[b] = (int)chain.size(); chain.push_back(b); }
+  uint64_t max_slice = 0;
+  for (size_t i = 0; i < chain.size(); i++)
+    max_slice = std::max(max_slice, (i + 1 < chain.size() ? plan.files[chain[i + 1]].gbase : plan.ng_total) - plan.files[chain[i]].gbase);
+  HIP_TRY(s, s->ensure(S::B_PACK_STATE, mgc::pack_state_bytes((uint32_t)chain.size(), max_slice)));
+  d_pstate = reinterpret_cast<uint64_t *>(s->buf[S::B_PACK_STATE].p);
+  s->d_unique = caller ? in.out_keys : s->buf[S::B_UNIQUE].p;
+  s->d_counts = caller ? in.out_counts : reinterpret_cast<uint32_t *>(s->buf[S::B_COUNTS].p);
+  HIP_TRY(s, mgc::launch_pack_state_init(d_pstate, early_cap, pack_st));
+  early = true;
+  return MGC_OK;
+}
+
+int Count::pack_step(uint32_t b) {                       // file b's count launch is queued (the probe file's ended long ago)
+  if (!early || chain_pos[b] < 0) return MGC_OK;
+  const FilePlan &x = plan.files[b];
+  const uint64_t i = (uint64_t)chain_pos[b], m = chain.size();
+  hipStream_t ps = pack_st;
+  HIP_TRY(s, hipStreamWaitEvent(ps, s->pack_ev[b], 0));
+  if (pack_ev2[b]) HIP_TRY(s, hipStreamWaitEvent(ps, s->pack_ev[(size_t)nb + b], 0));
+  const uint64_t g1 = i + 1 < m ? plan.files[chain[i + 1]].gbase : plan.ng_total;
+  HIP_TRY(s, mgc::launch_pack_gate_scan(d_group + x.gbase, g1 - x.gbase, d_pstate, (uint32_t)m, (uint32_t)i, x.stream ? d_retrycnt + b : nullptr,
+                                        i + 1 == m ? d_group + plan.ng_total : nullptr, false, ps));
+  if (i > 0) TRY(pack_file(chain[i - 1], ps, d_pstate, mgc::pack_gate_threshold(i - 1, m)));
+  if (i + 1 == m) TRY(pack_file(b, ps, d_pstate, mgc::pack_gate_threshold(i, m)));
+  return MGC_OK;
+}
+
+// The session stream is behind every count kernel here.  One copy brings the chain's state back: the first deferred file q and every
+// file's place in the result.  q == m: everything is packed.  Otherwise the serial path from q on: the retry launches, the scans of the
+// files from q on (carry-in base[q]), the result grown if it has to be, and the packing launches of the files the chain left out --
+// of ALL files if the result moved (the packing launches do not modify their source).
+int Count::pack_finish() {
+  const uint64_t m = chain.size(), none = mgc::pack_state_none();
+  if (s->profiling) { (void)hipEventCreate(&ev_pack[0]); (void)hipEventCreate(&ev_pack[1]); (void)hipEventRecord(ev_pack[0], st); }
+  HIP_TRY(s, hipEventRecord(s->ev_pack_done, pack_st));
+  HIP_TRY(s, hipStreamWaitEvent(st, s->ev_pack_done, 0));
+  std::vector<uint64_t> h(3 + m + 1, 0);
+  HIP_TRY(s, hipMemcpyAsync(h.data(), d_pstate, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(s, hipStreamSynchronize(st));
+  const uint64_t q = h[0] == none ? m : std::min<uint64_t>(h[0], m);
+  for (uint64_t i = 0; i < m; i++) prof.early_pack_files += mgc::pack_ran_early(i, q, m) ? 1u : 0u;
+  prof.early_pack_deferred = (uint32_t)(m - q);
+  if (sw.finish_trace) {
+    double lo = 2.0, hi = 0.0;                           // (the spread the margin of the estimate is chosen from: mgc_pack_plan.hpp)
+    for (uint64_t i = 0; i < q; i++) { const double r = (double)(h[3 + i + 1] - h[3 + i]) / (double)plan.files[chain[i]].size; lo = std::min(lo, r); hi = std::max(hi, r); }
+    fprintf(stderr, "[finish] early packing: %llu of %llu files scanned before the last count kernel ended (%u packed), %llu distinct in them, "
+                    "distinct / instances per file %.4f .. %.4f\n", (unsigned long long)q, (unsigned long long)m, prof.early_pack_files,
+            (unsigned long long)h[3 + q], q ? lo : 0.0, hi);
+  }
+  if (q == m) {
+    nd = h[3 + m];
+    s->n_distinct = nd;
+    return pack_done();
+  }
+  TRY(retry());
+  if (s->profiling) (void)hipEventRecord(ev_pack[0], st);  // (the retry launches belong to the count, as on the serial path)
+  for (uint64_t i = q; i < m; i++) {
+    const FilePlan &x = plan.files[chain[i]];
+    const uint64_t g1 = i + 1 < m ? plan.files[chain[i + 1]].gbase : plan.ng_total;
+    HIP_TRY(s, mgc::launch_pack_gate_scan(d_group + x.gbase, g1 - x.gbase, d_pstate, (uint32_t)m, (uint32_t)i, nullptr,
+                                          i + 1 == m ? d_group + plan.ng_total : nullptr, true, st));
+  }
+  HIP_TRY(s, hipMemcpyAsync(&nd, d_group + plan.ng_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(s, hipStreamSynchronize(st));
+  s->n_distinct = nd;
+  const void *was_keys = s->d_unique; const uint32_t *was_counts = s->d_counts;
+  bool moved = false;
+  if (in.out_keys && in.out_counts && nd <= in.out_cap) {
+    s->d_unique = in.out_keys;
+    s->d_counts = in.out_counts;
+  } else {
+    // (a buffer that grows is a new one, even where the allocator hands the old address out again)
+    moved = s->buf[S::B_UNIQUE].cap < std::max<size_t>(kbytes * nd, 256) || s->buf[S::B_COUNTS].cap < std::max<size_t>(sizeof(uint32_t) * nd, 256);
+    HIP_TRY(s, s->ensure(S::B_UNIQUE, kbytes * nd));
+    HIP_TRY(s, s->ensure(S::B_COUNTS, sizeof(uint32_t) * nd));
+    s->d_unique = s->buf[S::B_UNIQUE].p;
+    s->d_counts = reinterpret_cast<uint32_t *>(s->buf[S::B_COUNTS].p);
+  }
+  moved = moved || s->d_unique != was_keys || s->d_counts != was_counts;
+  if (moved) prof.early_pack_files = 0;
+  for (uint64_t i = moved ? 0 : mgc::pack_late_from(q, m); i < m; i++) TRY(pack_file(chain[i], st));
+  return pack_done();
 }
 
 void Count::finish_profile() {
@@ -1119,11 +1280,18 @@ int Count::count_finish() {
   hstream[0] = fork_huge ? s->stream2 : st;
   halt[0] = Y;
   hws_bytes = mgc::finish_huge_workspace_bytes(plan.max_bucket);
+  TRY(pack_events());
+  prof.probe_file = probe;
   if (probe >= 0) TRY(probe_file());
   TRY(group_all());
-  for (uint32_t b = 0; b < nb; b++) if ((int)b != probe) TRY(finish_file(b));
+  TRY(pack_plan());
+  for (uint32_t b = 0; b < nb; b++) {
+    if ((int)b != probe) TRY(finish_file(b));
+    TRY(pack_step(b));
+  }
   if (need_join) TRY(huge_join_all());
   TRY(trace_slices());
+  if (early) return pack_finish();
   TRY(retry());
   return scan_pack();
 }
@@ -1200,6 +1368,7 @@ int mgc::count_device(mgc_session *s, const CountInput &in) {
   HIP_TRY(s, hipSetDevice(s->device));
   const uint32_t bucket_bits = in.keys ? in.bucket_bits : plan_bucket_bits(s->cfg, s->sw, s->n_bases);
   memset(&s->prof, 0, sizeof(s->prof));
+  s->prof.probe_file = -1;
   Count count(s, in, bucket_bits);
   return count.run();
 }

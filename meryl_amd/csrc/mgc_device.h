@@ -50,6 +50,11 @@ struct Switches {
                                 // The default holds every file (35 GB at 10 Gbp; measured against 8 GiB and one file: profiles/group_batch_ab.txt);
                                 // where the arena cannot grow to it the count halves it, down to single files
   uint32_t group_batch_files = 0;   // MGC_GROUP_BATCH_FILES: at most that many files per batched launch (0: as many as the budget holds; tests)
+  bool     pack_overlap = true; // MGC_PACK_OVERLAP=0: every file is packed behind the last count kernel (no early packing, mgc_pack_plan.hpp)
+  int64_t  pack_margin = 64;    // MGC_PACK_MARGIN: thousandths added to the estimate of the distinct k-mers the result is sized by before the
+                                // total is known (mgc_pack_plan.hpp, PACK_MARGIN_PERMILLE; tests: negative, the estimate falls short)
+  uint32_t pack_ratio = 0;      // MGC_PACK_RATIO: thousandths; stands in for the probe file's distinct / instances ratio in that estimate where a
+                                // count has no probe file (tests: inputs too small for one; 0: no estimate without a probe)
 };
 Switches read_switches();        // (mgc_api.cpp)
 
@@ -285,15 +290,30 @@ hipError_t launch_finish_scan(uint64_t *d_group /*[ng_total+1]*/, uint64_t ng_to
 hipError_t launch_compact_groups(const void *d_keys, uint32_t key_words, const uint32_t *d_cnt_tmp, const uint64_t *d_starts,
                                  const uint64_t *d_offs, uint64_t ng, void *d_out_keys, uint32_t *d_out_counts, hipStream_t st,
                                  uint32_t tr_a = 0, uint32_t tr_b = 0 /*launch_group_wide's: d_offs goes by tr_index(sub-bucket)*/,
-                                 const uint32_t *d_nonempty_list = nullptr, uint64_t n_nonempty = 0 /*visit only these (host count)*/);
+                                 const uint32_t *d_nonempty_list = nullptr, uint64_t n_nonempty = 0 /*visit only these (host count)*/,
+                                 const uint64_t *d_gate = nullptr, uint64_t gate_above = 0 /*early packing: the launch does nothing unless
+                                 *d_gate > gate_above (launch_pack_gate_scan's state[0]); nullptr: no gate*/);
 // narrowed files: k-mer = base | sub-bucket << low_bits | suffix
 hipError_t launch_compact_groups_narrow(const void *d_keys32, const uint32_t *d_cnt_tmp, const uint64_t *d_starts, const uint64_t *d_offs,
                                         uint64_t ng, uint64_t base, uint32_t low_bits, void *d_out_keys, uint32_t *d_out_counts, hipStream_t st,
-                                        uint32_t tr_a, uint32_t tr_b, const uint32_t *d_nonempty_list = nullptr, uint64_t n_nonempty = 0);
+                                        uint32_t tr_a, uint32_t tr_b, const uint32_t *d_nonempty_list = nullptr, uint64_t n_nonempty = 0,
+                                        const uint64_t *d_gate = nullptr, uint64_t gate_above = 0);
 // K96 records (k = 33..51: the bits below the file, 12 bytes) -> whole 16-byte k-mers; base_lo / base_hi: the file's bits in their place
 hipError_t launch_compact_groups_k96(const void *d_keys96, const uint32_t *d_cnt_tmp, const uint64_t *d_starts, const uint64_t *d_offs,
                                      uint64_t ng, uint64_t base_lo, uint64_t base_hi, void *d_out_keys, uint32_t *d_out_counts, hipStream_t st,
-                                     uint32_t tr_a, uint32_t tr_b, const uint32_t *d_nonempty_list = nullptr, uint64_t n_nonempty = 0);
+                                     uint32_t tr_a, uint32_t tr_b, const uint32_t *d_nonempty_list = nullptr, uint64_t n_nonempty = 0,
+                                     const uint64_t *d_gate = nullptr, uint64_t gate_above = 0);
+// Early packing: the files of a count are packed in index order on another stream while later files are still counted.
+// d_state[pack_state_bytes(m, the longest slice) / 8] for a chain of m files: [0] the first deferred file (pack_state_none(): none), [1]
+// the k-mers the result has room for, [3 + i] the distinct k-mers before file i.  launch_pack_gate_scan, file i of m: unless the gate defers it (an earlier
+// file deferred; *d_retry_count != 0 -- nullptr: not asked; no room for its k-mers), its slice d_slice[n] of group_distinct becomes
+// the exclusive offsets the scan of ALL files would leave there, [3 + i + 1] is written and, with d_total, *d_total as well.
+// force: no gate (the serial path from the first deferred file on).
+size_t     pack_state_bytes(uint32_t n_files, uint64_t max_slice);
+uint64_t   pack_state_none();
+hipError_t launch_pack_state_init(uint64_t *d_state, uint64_t capacity, hipStream_t st);
+hipError_t launch_pack_gate_scan(uint64_t *d_slice, uint64_t n, uint64_t *d_state, uint32_t n_files, uint32_t i, const uint64_t *d_retry_count,
+                                 uint64_t *d_total, bool force, hipStream_t st);
 hipError_t launch_widen_k96(const void *d_keys96, uint64_t n, uint64_t base_lo, uint64_t base_hi, void *d_out128, hipStream_t st);
 hipError_t launch_widen_groups(const void *d_keys32, const uint64_t *d_starts, uint64_t ng, uint64_t base, uint32_t low_bits, void *d_out64,
                                hipStream_t st, uint32_t tr_a, uint32_t tr_b);      // tr_a != 0: the result is NOT in key order

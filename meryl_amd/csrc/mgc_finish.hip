@@ -2393,7 +2393,9 @@ template <typename K>
 __global__ __launch_bounds__(256)
 void compact_groups_kernel(const K *__restrict__ keys, const u32 *__restrict__ cnt_tmp, const u64 *__restrict__ starts,
                            const u64 *__restrict__ offs, u64 ng, K *__restrict__ out_keys, u32 *__restrict__ out_counts, u32 tr_a, u32 tr_b,
-                           const u32 *__restrict__ nz, u64 n_nz /* the non-empty sub-buckets only (a sparse grid: `compress`), or null */) {
+                           const u32 *__restrict__ nz, u64 n_nz /* the non-empty sub-buckets only (a sparse grid: `compress`), or null */,
+                           const u64 *__restrict__ gate, u64 gate_above /* early packing: run only if *gate > gate_above (null: run) */) {
+  if (gate && *gate <= gate_above) return;
   u64 g = (u64)blockIdx.x * 4 + wave_id();
   if (nz) { if (g >= n_nz) return; g = nz[g]; }
   else if (g >= ng) return;
@@ -2410,7 +2412,9 @@ void compact_groups_kernel(const K *__restrict__ keys, const u32 *__restrict__ c
 __global__ __launch_bounds__(256)
 void compact_groups_k96_kernel(const K96 *__restrict__ keys, const u32 *__restrict__ cnt_tmp, const u64 *__restrict__ starts,
                                const u64 *__restrict__ offs, u64 ng, u64 base_lo, u64 base_hi, K128 *__restrict__ out_keys,
-                               u32 *__restrict__ out_counts, u32 tr_a, u32 tr_b, const u32 *__restrict__ nz, u64 n_nz) {
+                               u32 *__restrict__ out_counts, u32 tr_a, u32 tr_b, const u32 *__restrict__ nz, u64 n_nz,
+                               const u64 *__restrict__ gate, u64 gate_above) {
+  if (gate && *gate <= gate_above) return;
   u64 g = (u64)blockIdx.x * 4 + wave_id();
   if (nz) { if (g >= n_nz) return; g = nz[g]; }
   else if (g >= ng) return;
@@ -2436,7 +2440,9 @@ void widen_k96_kernel(const K96 *__restrict__ in, u64 n, u64 base_lo, u64 base_h
 __global__ __launch_bounds__(256)
 void compact_groups_narrow_kernel(const u32 *__restrict__ keys32, const u32 *__restrict__ cnt_tmp, const u64 *__restrict__ starts,
                                   const u64 *__restrict__ offs, u64 ng, u64 base, u32 low_bits, u64 *__restrict__ out_keys,
-                                  u32 *__restrict__ out_counts, u32 tr_a, u32 tr_b, const u32 *__restrict__ nz, u64 n_nz) {
+                                  u32 *__restrict__ out_counts, u32 tr_a, u32 tr_b, const u32 *__restrict__ nz, u64 n_nz,
+                               const u64 *__restrict__ gate, u64 gate_above) {
+  if (gate && *gate <= gate_above) return;
   u64 g = (u64)blockIdx.x * 4 + wave_id();
   if (nz) { if (g >= n_nz) return; g = nz[g]; }
   else if (g >= ng) return;
@@ -2954,39 +2960,132 @@ hipError_t launch_finish_scan(uint64_t *d_group, uint64_t ng_total, void *d_scra
                             reinterpret_cast<u64 *>(d_group) + ng_total, st);
 }
 
+// Early packing (mgc_count.cpp, Count::pack_step): file i of the packing chain, once its count kernel has ended.  The gate, then the
+// exclusive scan of the file's slice of group_distinct with the carry-in base[i], in place; base[i + 1] behind it.
+//   state[0]      the first deferred file of the chain (PACK_NONE: none so far) -- sticky: from it on nothing is scanned or packed
+//   state[1]      k-mers the result has room for
+//   state[3 + i]  base[i]: the distinct k-mers of the files before file i
+//   behind them   the sums of the slice's 4096-entry chunks (pack_chunk_sums_kernel; the launches of a chain run one after another)
+// The gate defers the file -- its slice stays as the count kernel left it: the retry launch adds to those counts -- if an earlier one
+// was deferred, if its count kernel put sub-buckets on the retry list, or if the result has no room for it.  force: the serial path
+// after a deferral scans the files from the first deferred one on with the same kernels (no gate; base[i] is there).
+// Two launches of one 256-thread workgroup per chunk: every workgroup of the second adds up the chunk sums before its own (a slice
+// has 17 chunks at 10 Gbp, 256 at the largest file the plan makes) and decides the gate for itself, from the same numbers.  The
+// workgroups are the count kernels' size on purpose: those hold every wave slot of the device while the chain runs, and a
+// 1024-thread workgroup finds no CU with sixteen free slots before the last of them has ended (measured: DESIGN.md section 3.5).
+constexpr u64 PACK_NONE = ~0ull;
+constexpr int PG_BLOCK = 256, PG_ITEMS = 16, PG_CHUNK = PG_BLOCK * PG_ITEMS;
+__global__ __launch_bounds__(PG_BLOCK)
+void pack_chunk_sums_kernel(const u64 *__restrict__ grp, u64 n, u64 *__restrict__ chunk_tot) {
+  __shared__ u64 s_tmp[PG_BLOCK / 64 + 1];
+  const u64 c0 = (u64)blockIdx.x * PG_CHUNK;
+  u64 v = 0;
+#pragma unroll
+  for (int q = 0; q < PG_ITEMS; q++) {
+    const u64 j = c0 + (u64)q * PG_BLOCK + threadIdx.x;
+    v += j < n ? grp[j] : 0ull;
+  }
+  u64 tot;
+  (void)block_excl_scan<PG_BLOCK, u64>(v, s_tmp, &tot);
+  if (threadIdx.x == 0) chunk_tot[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(PG_BLOCK)
+void pack_gate_scan_kernel(u64 *__restrict__ grp, u64 n, u64 *state, u32 i, const u64 *__restrict__ retry_count,
+                           u64 *__restrict__ total_out, u32 force, const u64 *__restrict__ chunk_tot) {
+  __shared__ u64 s_tmp[PG_BLOCK / 64 + 1];
+  __shared__ u32 s_go;
+  const u32 tid = threadIdx.x, c = blockIdx.x, nchunks = gridDim.x;
+  if (!force) {
+    if (tid == 0) s_go = (state[0] == PACK_NONE) ? ((retry_count && *retry_count != 0) ? 1u : 2u) : 0u;
+    __syncthreads();
+    if (s_go == 0) return;                                 // an earlier file was deferred (or another workgroup of this launch said so)
+  }
+  u64 pre = 0, all = 0;
+  for (u32 j = tid; j < nchunks; j += PG_BLOCK) { const u64 t = chunk_tot[j]; all += t; pre += j < c ? t : 0ull; }
+  u64 pre_tot, all_tot;
+  (void)block_excl_scan<PG_BLOCK, u64>(pre, s_tmp, &pre_tot);
+  (void)block_excl_scan<PG_BLOCK, u64>(all, s_tmp, &all_tot);
+  const u64 base = state[3 + i];
+  if (!force && (s_go == 1 || base + all_tot > state[1])) { if (c == 0 && tid == 0) state[0] = i; return; }
+  const u64 c0 = (u64)c * PG_CHUNK;
+  u64 v[PG_ITEMS], sum = 0;
+#pragma unroll
+  for (int q = 0; q < PG_ITEMS; q++) {
+    const u64 j = c0 + (u64)tid * PG_ITEMS + q;
+    v[q] = j < n ? grp[j] : 0ull;
+    sum += v[q];
+  }
+  u64 tot;
+  u64 run = base + pre_tot + block_excl_scan<PG_BLOCK, u64>(sum, s_tmp, &tot);
+#pragma unroll
+  for (int q = 0; q < PG_ITEMS; q++) {
+    const u64 j = c0 + (u64)tid * PG_ITEMS + q;
+    if (j < n) grp[j] = run;
+    run += v[q];
+  }
+  if (c + 1 == nchunks && tid == 0) {
+    state[3 + i + 1] = base + all_tot;
+    if (total_out) *total_out = base + all_tot;            // the last file: group_distinct[ng_total], as the scan of all files leaves it
+  }
+}
+
+__global__ void pack_state_init_kernel(u64 *__restrict__ state, u64 capacity) {
+  state[0] = PACK_NONE; state[1] = capacity; state[2] = 0; state[3] = 0;
+}
+
+static uint64_t pack_chunks(uint64_t n) { return (n + PG_CHUNK - 1) / PG_CHUNK; }
+size_t pack_state_bytes(uint32_t n_files, uint64_t max_slice) { return sizeof(uint64_t) * (3 + (size_t)n_files + 1 + (size_t)pack_chunks(max_slice)); }
+uint64_t pack_state_none() { return PACK_NONE; }
+hipError_t launch_pack_state_init(uint64_t *d_state, uint64_t capacity, hipStream_t st) {
+  hipLaunchKernelGGL(pack_state_init_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<u64 *>(d_state), (u64)capacity);
+  return hipGetLastError();
+}
+hipError_t launch_pack_gate_scan(uint64_t *d_slice, uint64_t n, uint64_t *d_state, uint32_t n_files, uint32_t i, const uint64_t *d_retry_count,
+                                 uint64_t *d_total, bool force, hipStream_t st) {
+  if (n == 0 || i >= n_files) return hipErrorInvalidValue;
+  u64 *chunk_tot = reinterpret_cast<u64 *>(d_state) + 3 + (size_t)n_files + 1;
+  const dim3 grid((uint32_t)pack_chunks(n));
+  hipLaunchKernelGGL(pack_chunk_sums_kernel, grid, dim3(PG_BLOCK), 0, st, reinterpret_cast<const u64 *>(d_slice), (u64)n, chunk_tot);
+  MGC_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(pack_gate_scan_kernel, grid, dim3(PG_BLOCK), 0, st, reinterpret_cast<u64 *>(d_slice), (u64)n, reinterpret_cast<u64 *>(d_state), i,
+                     reinterpret_cast<const u64 *>(d_retry_count), reinterpret_cast<u64 *>(d_total), force ? 1u : 0u, (const u64 *)chunk_tot);
+  return hipGetLastError();
+}
+
 hipError_t launch_compact_groups(const void *d_keys, uint32_t key_words, const uint32_t *d_cnt_tmp, const uint64_t *d_starts,
                                  const uint64_t *d_offs, uint64_t ng, void *d_out_keys, uint32_t *d_out_counts, hipStream_t st,
-                                 uint32_t tr_a, uint32_t tr_b, const uint32_t *d_nz, uint64_t n_nz) {
+                                 uint32_t tr_a, uint32_t tr_b, const uint32_t *d_nz, uint64_t n_nz, const uint64_t *d_gate, uint64_t gate_above) {
   const dim3 grid((uint32_t)(((d_nz ? n_nz : ng) + 3) / 4));
   if (d_nz && n_nz == 0) return hipSuccess;
   if (key_words == 2)
     hipLaunchKernelGGL(compact_groups_kernel<K128>, grid, dim3(256), 0, st, reinterpret_cast<const K128 *>(d_keys), d_cnt_tmp,
                        reinterpret_cast<const u64 *>(d_starts), reinterpret_cast<const u64 *>(d_offs), (u64)ng,
-                       reinterpret_cast<K128 *>(d_out_keys), d_out_counts, tr_a, tr_b, d_nz, (u64)n_nz);
+                       reinterpret_cast<K128 *>(d_out_keys), d_out_counts, tr_a, tr_b, d_nz, (u64)n_nz, reinterpret_cast<const u64 *>(d_gate), (u64)gate_above);
   else
     hipLaunchKernelGGL(compact_groups_kernel<u64>, grid, dim3(256), 0, st, reinterpret_cast<const u64 *>(d_keys), d_cnt_tmp,
                        reinterpret_cast<const u64 *>(d_starts), reinterpret_cast<const u64 *>(d_offs), (u64)ng,
-                       reinterpret_cast<u64 *>(d_out_keys), d_out_counts, tr_a, tr_b, d_nz, (u64)n_nz);
+                       reinterpret_cast<u64 *>(d_out_keys), d_out_counts, tr_a, tr_b, d_nz, (u64)n_nz, reinterpret_cast<const u64 *>(d_gate), (u64)gate_above);
   return hipGetLastError();
 }
 
 hipError_t launch_compact_groups_narrow(const void *d_keys32, const uint32_t *d_cnt_tmp, const uint64_t *d_starts, const uint64_t *d_offs,
                                         uint64_t ng, uint64_t base, uint32_t low_bits, void *d_out_keys, uint32_t *d_out_counts, hipStream_t st,
-                                        uint32_t tr_a, uint32_t tr_b, const uint32_t *d_nz, uint64_t n_nz) {
+                                        uint32_t tr_a, uint32_t tr_b, const uint32_t *d_nz, uint64_t n_nz, const uint64_t *d_gate, uint64_t gate_above) {
   if (d_nz && n_nz == 0) return hipSuccess;
   hipLaunchKernelGGL(compact_groups_narrow_kernel, dim3((uint32_t)(((d_nz ? n_nz : ng) + 3) / 4)), dim3(256), 0, st, reinterpret_cast<const u32 *>(d_keys32),
                      d_cnt_tmp, reinterpret_cast<const u64 *>(d_starts), reinterpret_cast<const u64 *>(d_offs), (u64)ng, (u64)base, low_bits,
-                     reinterpret_cast<u64 *>(d_out_keys), d_out_counts, tr_a, tr_b, d_nz, (u64)n_nz);
+                     reinterpret_cast<u64 *>(d_out_keys), d_out_counts, tr_a, tr_b, d_nz, (u64)n_nz, reinterpret_cast<const u64 *>(d_gate), (u64)gate_above);
   return hipGetLastError();
 }
 
 hipError_t launch_compact_groups_k96(const void *d_keys96, const uint32_t *d_cnt_tmp, const uint64_t *d_starts, const uint64_t *d_offs,
                                      uint64_t ng, uint64_t base_lo, uint64_t base_hi, void *d_out_keys, uint32_t *d_out_counts, hipStream_t st,
-                                     uint32_t tr_a, uint32_t tr_b, const uint32_t *d_nz, uint64_t n_nz) {
+                                     uint32_t tr_a, uint32_t tr_b, const uint32_t *d_nz, uint64_t n_nz, const uint64_t *d_gate, uint64_t gate_above) {
   if (d_nz && n_nz == 0) return hipSuccess;
   hipLaunchKernelGGL(compact_groups_k96_kernel, dim3((uint32_t)(((d_nz ? n_nz : ng) + 3) / 4)), dim3(256), 0, st, reinterpret_cast<const K96 *>(d_keys96),
                      d_cnt_tmp, reinterpret_cast<const u64 *>(d_starts), reinterpret_cast<const u64 *>(d_offs), (u64)ng, (u64)base_lo, (u64)base_hi,
-                     reinterpret_cast<K128 *>(d_out_keys), d_out_counts, tr_a, tr_b, d_nz, (u64)n_nz);
+                     reinterpret_cast<K128 *>(d_out_keys), d_out_counts, tr_a, tr_b, d_nz, (u64)n_nz, reinterpret_cast<const u64 *>(d_gate), (u64)gate_above);
   return hipGetLastError();
 }
 

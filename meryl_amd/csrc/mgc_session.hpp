@@ -59,6 +59,10 @@ struct mgc_session {
   hipStream_t      stream_h[HUGE_EXTRA] = {nullptr, nullptr, nullptr};   // more streams for the streaming kernels of oversized sub-buckets (count_device)
   hipStream_t      stream2 = nullptr;    // the streaming hash-count of a file's oversized sub-buckets runs beside its persistent kernel
   hipEvent_t       ev_fork = nullptr, ev_join = nullptr;
+  // early packing (mgc_count.cpp, Count::pack_plan): the events behind every file's count launches, created once, and the one behind
+  // the packing chain's last launch.  The chain itself runs on st_in (below), which is idle while the caller's own thread counts
+  std::vector<hipEvent_t> pack_ev;
+  hipEvent_t       ev_pack_done = nullptr;
   uint64_t        *h_stats = nullptr;    // pinned: per file {largest sub-bucket, oversized sub-buckets, non-empty sub-buckets}
   size_t           h_stats_cap = 0;
   std::string      err;
@@ -87,7 +91,8 @@ struct mgc_session {
          B_GROUP_BATCH /* the batched grouping launches' control words and descriptor tables (mgc_count.cpp, group_batches) */,
          B_BAM_SEG0, B_BAM_SEG1 /* the segment tables of the two BAM pieces in flight (mgc_bam_walk.hpp) */,
          B_GZ_SYM0, B_GZ_SYM1 /* the unresolved symbols of the two gzip pieces in flight (mgc_gzip.hip) */, B_GZ_TAB0, B_GZ_TAB1 /* their CRC
-         piece tables and results */, B_GZ_WIN /* two 32 KiB windows, ping-pong, and the error word */, B_NUM };
+         piece tables and results */, B_GZ_WIN /* two 32 KiB windows, ping-pong, and the error word */,
+         B_PACK_STATE /* early packing: the gate's state and the files' places in the result (mgc_device.h, launch_pack_gate_scan) */, B_NUM };
   Buf buf[B_NUM];
   size_t arena_bytes() const { size_t t = 0; for (const auto &b : buf) t += b.cap; return t; }
   double tr_alloc = 0;                   // seconds inside hipMalloc / hipFree of the arena (MGC_IO_TRACE)
