@@ -746,6 +746,16 @@ typedef struct mgc_profile {
   uint32_t early_pack_files, early_pack_deferred;
   int32_t  probe_file;             /* the file that was counted first to choose the others' plan (probe_ratio); -1: no probe ran */
   uint32_t reserved_;
+  /* gigantic sub-buckets (above 65536 keys: cut into slices, the slices' pairs merged; the dense ones counted by 64 ranges of the suffix
+   * space), summed over the files of the count -- which path ran, counted on the device:
+   *   huge_cut, huge_slices   sub-buckets cut and the slices planned for them (MGC_HUGE_SLICES=0: both stay 0, and so does huge_dense)
+   *   huge_dense              cut sub-buckets a slice marked dense (more distinct suffixes than 1/8 of the slice's keys)
+   *   huge_repasses[m]        passes that overflowed their table and were run again over a narrower suffix range: [0] an oversized
+   *                           sub-bucket that is not cut, [1] a slice, [2] the merge of a sub-bucket's pairs, [3] a range of a dense one
+   *   huge_empty_ranges       ranges of dense sub-buckets that held no suffix (equal splitters: a heavy k-mer) */
+  uint32_t huge_cut, huge_slices, huge_dense;
+  uint32_t huge_repasses[4];
+  uint32_t huge_empty_ranges;
 } mgc_profile;
 int mgc_set_profiling(mgc_session *s, int enable);
 int mgc_get_profile(const mgc_session *s, mgc_profile *p);

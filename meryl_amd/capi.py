@@ -211,6 +211,11 @@ class Profile(ctypes.Structure):
         ("early_pack_deferred", ctypes.c_uint32),
         ("probe_file", ctypes.c_int32),
         ("reserved_", ctypes.c_uint32),
+        ("huge_cut", ctypes.c_uint32),
+        ("huge_slices", ctypes.c_uint32),
+        ("huge_dense", ctypes.c_uint32),
+        ("huge_repasses", ctypes.c_uint32 * 4),
+        ("huge_empty_ranges", ctypes.c_uint32),
     ]
 
 

@@ -502,9 +502,11 @@ int Count::buffers() {
   sort_ws_bytes = mgc::sort_workspace_bytes(plan.max_bucket) + 256;
   HIP_TRY(s, s->ensure(S::B_SORT_WS, sort_ws_bytes));
   sort_ws = s->buf[S::B_SORT_WS].p;
-  // device flags: [0] look-back timeout, [1] scratch answer of the hash probe, [2] overflow of a streamed sub-bucket
+  // device flags: [0] look-back timeout, [1] scratch answer of the hash probe, [2] overflow of a streamed sub-bucket;
+  // [FIN_HUGE_STATS_AT ...]: the path counters of the gigantic sub-buckets (mgc_device.h), zero when the count begins
   d_err = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(sort_ws) + sort_ws_bytes - 256);
-  HIP_TRY(s, hipMemsetAsync(d_err, 0, 32, st));
+  static_assert(sizeof(uint32_t) * (mgc::FIN_HUGE_STATS_AT + mgc::FIN_HUGE_STATS) <= 256, "the flag block holds the path counters");
+  HIP_TRY(s, hipMemsetAsync(d_err, 0, sizeof(uint32_t) * (mgc::FIN_HUGE_STATS_AT + mgc::FIN_HUGE_STATS), st));
   if (s->profiling) {
     pass_ev.resize((size_t)nb * ev_per_file);
     for (auto &e : pass_ev) (void)hipEventCreate(&e);
@@ -1242,6 +1244,13 @@ void Count::finish_profile() {
   }
   prof.finish_keys = fin_keys;
   prof.finish_bytes = fin_in_bytes + nd * (fin_narrow ? 8u : (uint64_t)kbytes + 4u);
+  // which way the gigantic sub-buckets went (the caller has just waited for the stream: every count kernel is done)
+  uint32_t h_huge[mgc::FIN_HUGE_STATS] = {};
+  if (d_err && hipMemcpy(h_huge, d_err + mgc::FIN_HUGE_STATS_AT, sizeof(h_huge), hipMemcpyDeviceToHost) == hipSuccess) {
+    prof.huge_cut += h_huge[0]; prof.huge_slices += h_huge[1]; prof.huge_dense += h_huge[2];
+    for (int m = 0; m < 4; m++) prof.huge_repasses[m] += h_huge[3 + m];
+    prof.huge_empty_ranges += h_huge[7];
+  }
 }
 
 // The default path: every file grouped by its top bits, then its sub-buckets sorted and counted in LDS (or streamed through the hash

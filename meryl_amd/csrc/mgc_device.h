@@ -246,8 +246,13 @@ enum class FinishKeys : uint32_t {
   WHOLE16,                      // whole 16-byte k-mers
 };
 // One file's count launch: what launch_finish_probe / launch_finish_file / launch_finish_retry share.
+// Path counters of the gigantic sub-buckets (mgc_finish.hip, HugeSliced::stats): FIN_HUGE_STATS words of the count's flag block, from
+// word FIN_HUGE_STATS_AT on -- [0] sub-buckets cut, [1] slices planned, [2] sub-buckets marked dense, [3 + MODE] passes of MODE 0 / 1 / 2 / 3
+// that overflowed their table and were run again over a narrower range, [7] empty ranges of MODE 3.  Zeroed with the flags when a
+// count begins, added to on the device, read back by the count only when it is profiled.
+constexpr uint32_t FIN_HUGE_STATS_AT = 16, FIN_HUGE_STATS = 8;
 struct FinishFile {
-  void *keys = nullptr;                       // the file's segment; distinct keys are written in place
+  void *keys = nullptr;                      // the file's segment; distinct keys are written in place
   void *alt = nullptr;                        // room for the file's keys (the streaming kernels' second buffer)
   FinishKeys layout = FinishKeys::WHOLE8;
   const uint64_t *starts = nullptr;           // [ng + 1] sub-bucket boundaries
@@ -270,8 +275,8 @@ struct FinishFile {
   // finish_huge_workspace_bytes(huge_ws_keys >= n_keys), one per stream the streaming kernels run on: with it a GIGANTIC sub-bucket --
   // above 65536 keys -- is counted in slices by many workgroups instead of one
   void *huge_ws = nullptr; size_t huge_ws_bytes = 0; uint64_t huge_ws_keys = 0;
-  uint32_t *d_error = nullptr;                // the count's look-back / chain time-out flag
-  hipStream_t st = nullptr;                   // where the persistent kernels are launched
+  uint32_t *d_error = nullptr;                // the count's look-back / chain time-out flag; d_error[FIN_HUGE_STATS_AT ...]: the path counters below
+  hipStream_t st = nullptr;                  // where the persistent kernels are launched
   hipStream_t st_huge = nullptr;              // where the streaming kernel of the oversized list is launched (st, or a stream forked from it)
   int  hash_multi = -1;                       // Switches::hash_multi
   bool hash_dbg = false;                      // Switches::hash_dbg

@@ -1667,16 +1667,20 @@ struct HugeSliced {                       // device-side plan of one file's giga
   u64 *chain;                             // [max_gig][HUGE_RANGES]: bit 63 set = the range is done, below: distinct k-mers up to and including it
   u64 *split;                             // [max_gig][HUGE_RANGES][2]: the largest suffix of a range (low, high word) -- quantiles of a sample (huge_split_kernel)
   u32 *error;                             // a chain wait that timed out (the count then ends with MGC_ETIMEOUT)
+  u32 *stats;                             // path counters of the whole count (HUGE_STAT_*), or null; read back only with profiling on
   u32 max_gig, max_slices;
 };
+// hs.stats[]: which path the gigantic sub-buckets of a count took (mgc_profile: huge_cut ... huge_empty_ranges).  One thread adds, in
+// branches that run once per sub-bucket or once per pass; nothing reads them on the device.
+constexpr u32 HUGE_STAT_CUT = 0, HUGE_STAT_SLICES = 1, HUGE_STAT_DENSE = 2, HUGE_STAT_REPASS = 3 /* + MODE */, HUGE_STAT_EMPTY = 7;
+__device__ __forceinline__ void huge_stat(const HugeSliced &hs, u32 what, u32 by = 1u) { if (hs.stats) atomicAdd(hs.stats + what, by); }
 __device__ __forceinline__ bool huge_is_cut(u64 n, u64 huge_max) { return huge_max != 0 && n > huge_max && (n + HUGE_SLICE - 1) / HUGE_SLICE <= (u64)HUGE_WMAX; }
 // a cut sub-bucket of n keys: W slices of equal length (no ragged tail: a slice's pairs have to fit half its keys)
 __device__ __forceinline__ u32 huge_slices(u64 n) { return (u32)((n + HUGE_SLICE - 1) / HUGE_SLICE); }
 __device__ __forceinline__ u64 huge_slice_len(u64 n) { const u64 W = huge_slices(n); return (n + W - 1) / W; }
 
 __global__ __launch_bounds__(256)
-void huge_plan_kernel(const u64 *__restrict__ starts, const u32 *__restrict__ list, u64 n_list, u64 huge_max, HugeSliced hs,
-                      u32 mark_dense = 0 /* 16-byte keys: every cut sub-bucket is counted by ranges (MODE 3), no slices */) {
+void huge_plan_kernel(const u64 *__restrict__ starts, const u32 *__restrict__ list, u64 n_list, u64 huge_max, HugeSliced hs) {
   const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_list) return;
   const u64 g = list[i];
@@ -1687,7 +1691,7 @@ void huge_plan_kernel(const u64 *__restrict__ starts, const u32 *__restrict__ li
   const u32 first = atomicAdd(&hs.counters[1], W);
   if (q >= hs.max_gig || first + W > hs.max_slices) return;            // (sized for the file: cannot happen; the single-workgroup form would be skipped too -- see launch)
   hs.gig_g[q] = (u32)g;
-  if (mark_dense) { hs.gig_fail[q] = 1u; return; }
+  huge_stat(hs, HUGE_STAT_CUT); huge_stat(hs, HUGE_STAT_SLICES, W);
   for (u32 j = 0; j < W; j++) { hs.slice_g[first + j] = (u32)g; hs.slice_j[first + j] = j; hs.slice_q[first + j] = q; }
 }
 
@@ -1788,7 +1792,7 @@ void hash_count_huge_body(u32 work, KT *__restrict__ keys, const u64 *__restrict
     // the range: between two quantiles of the sub-bucket's sample (huge_split_kernel); an empty one still passes the chain on
     u128 rl, rh;
     if (huge_range(hs, cq, rr, rl, rh)) { range_lo = (u64)rl; range_hi = (u64)rh; }
-    else { range_lo = 1; range_hi = 0; n64 = 0; }
+    else { range_lo = 1; range_hi = 0; n64 = 0; if (tid == 0) huge_stat(hs, HUGE_STAT_EMPTY); }
   }
   const u64 prefix = (sizeof(KT) == 8 && MODE != 1) ? ((u64)keys[starts[g]] & ~low_mask) : 0ull;   // whole keys: the sub-bucket's first key tells (read before anything is written)
   constexpr u32 smask = SLOTS - 1, sshift = 32 - __builtin_ctz((unsigned)SLOTS);
@@ -1915,6 +1919,7 @@ void hash_count_huge_body(u32 work, KT *__restrict__ keys, const u64 *__restrict
       // New upper end = the sample's quantile below which the whole stream should bring at most 0.7 CAP distinct
       // suffixes even if everything still to come is new.  Always below the sample's maximum, so the range shrinks.
       const u32 Ds = D < (u32)BLOCK ? D : (u32)BLOCK;
+      if (tid == 0) huge_stat(hs, HUGE_STAT_REPASS + MODE);
 #pragma unroll
       for (int j = 0; j < SPT; j++)
         if ((occ >> j) & 1u) { if (o < (u32)BLOCK) dk[o] = tk[(u32)j * BLOCK + tid]; o++; }
@@ -1942,7 +1947,7 @@ void hash_count_huge_body(u32 work, KT *__restrict__ keys, const u64 *__restrict
     if constexpr (MODE == 1) {
       // the slice's pairs must fit half its keys (otherwise little repeats -- a dense sub-bucket: MODE 3's): then all slices' pairs fit
       // the sub-bucket's place in alt[], packed in the order the passes of the slices come by
-      if (HUGE_DENSE_DIV * (out + D) > n64) { if (tid == 0) hs.gig_fail[cq] = 1u; return; }
+      if (HUGE_DENSE_DIV * (out + D) > n64) { if (tid == 0 && atomicExch(&hs.gig_fail[cq], 1u) == 0u) huge_stat(hs, HUGE_STAT_DENSE); return; }
       if (tid == 0) s_base = (u64)atomicAdd(&hs.gig_pairs[cq], D);
       __syncthreads();
       emit_at = s_base;
@@ -2092,7 +2097,7 @@ void hash_count128_huge_body(u32 work, KT *__restrict__ keys, const u64 *__restr
     g = hs.gig_g[cq];
     a = starts[g]; n64 = starts[g + 1] - a;
     // the range: between two quantiles of the sub-bucket's sample (huge_split_kernel); an empty one still passes the chain on
-    if (!huge_range(hs, cq, rr, range_lo, range_hi)) { range_lo = 1; range_hi = 0; n64 = 0; }
+    if (!huge_range(hs, cq, rr, range_lo, range_hi)) { range_lo = 1; range_hi = 0; n64 = 0; if (tid == 0) huge_stat(hs, HUGE_STAT_EMPTY); }
   }
   const u128 prefix = MODE == 1 ? (u128)0 : (KO::v(keys[starts[g]]) & ~low_mask);
   constexpr u32 smask = SLOTS - 1, sshift = 32 - __builtin_ctz((unsigned)SLOTS);
@@ -2207,6 +2212,7 @@ void hash_count128_huge_body(u32 work, KT *__restrict__ keys, const u64 *__restr
     u32 o = block_excl_scan<BLOCK, u32>(__popc(occ), s_tmp, &D);
     if (overflowed) {                                  // new upper end = a quantile of the table's suffixes (see above)
       const u32 Ds = D < (u32)BLOCK ? D : (u32)BLOCK;
+      if (tid == 0) huge_stat(hs, HUGE_STAT_REPASS + MODE);
 #pragma unroll
       for (int j = 0; j < SPT; j++) {
         if ((occ >> j) & 1u) {
@@ -2245,7 +2251,7 @@ void hash_count128_huge_body(u32 work, KT *__restrict__ keys, const u64 *__restr
     __syncthreads();
     u64 emit_at = out;
     if constexpr (MODE == 1) {
-      if (HUGE_DENSE_DIV * (out + D) > n64) { if (tid == 0) hs.gig_fail[cq] = 1u; return; }
+      if (HUGE_DENSE_DIV * (out + D) > n64) { if (tid == 0 && atomicExch(&hs.gig_fail[cq], 1u) == 0u) huge_stat(hs, HUGE_STAT_DENSE); return; }
       if (tid == 0) s_base = (u64)atomicAdd(&hs.gig_pairs[cq], D);
       __syncthreads();
       emit_at = s_base;
@@ -2668,6 +2674,7 @@ static HugeSliced huge_layout(void *ws, u64 ws_keys, u32 *d_error) {
   hs.chain = reinterpret_cast<u64 *>((reinterpret_cast<uintptr_t>(hs.slice_q + hs.max_slices) + 7) & ~(uintptr_t)7);
   hs.split = hs.chain + (size_t)hs.max_gig * HUGE_RANGES;
   hs.error = d_error;
+  hs.stats = d_error ? d_error + FIN_HUGE_STATS_AT : nullptr;
   return hs;
 }
 hipError_t finish_huge_trace(const void *d_ws, uint64_t ws_keys, HugeTrace *out) {
@@ -2734,10 +2741,14 @@ static hipError_t launch_huge(const FinishFile &f, u64 huge_min) {
   if (n_large == 0) return hipSuccess;
   const bool sliced = f.huge_ws && f.d_error && f.max_sub > (u64)HUGE_SLICE_MIN && n_keys && n_keys <= f.huge_ws_keys &&
                       f.huge_ws_bytes >= finish_huge_workspace_bytes(f.huge_ws_keys);
-  if (!sliced) return launch_huge_mode<T, 0>(f, f.large_list, (uint32_t)n_large, huge_min, 0, HugeSliced(), st);
+  if (!sliced) {                                         // (no plan: only the counter of MODE 0's narrowed passes goes along)
+    HugeSliced none = HugeSliced();
+    none.stats = f.d_error ? f.d_error + FIN_HUGE_STATS_AT : nullptr;
+    return launch_huge_mode<T, 0>(f, f.large_list, (uint32_t)n_large, huge_min, 0, none, st);
+  }
   const HugeSliced hs = huge_layout(f.huge_ws, f.huge_ws_keys, f.d_error);
   MGC_CHECK(hipMemsetAsync(f.huge_ws, 0, finish_huge_workspace_bytes(f.huge_ws_keys), st));
-  hipLaunchKernelGGL(huge_plan_kernel, dim3((uint32_t)((n_large + 255) / 256)), dim3(256), 0, st, fin_starts(f), f.large_list, n_large, (u64)HUGE_SLICE_MIN, hs, 0u);
+  hipLaunchKernelGGL(huge_plan_kernel, dim3((uint32_t)((n_large + 255) / 256)), dim3(256), 0, st, fin_starts(f), f.large_list, n_large, (u64)HUGE_SLICE_MIN, hs);
   MGC_CHECK(hipGetLastError());
   const uint32_t sgrid = (uint32_t)std::min<u64>(512, std::min<u64>((u64)hs.max_slices, n_keys / HUGE_SLICE + n_keys / HUGE_SLICE_MIN + 4));   // (by ticket)
   const uint32_t ggrid = (uint32_t)std::min<u64>(std::min<u64>(n_large, (u64)hs.max_gig), n_keys / HUGE_SLICE_MIN + 1);

@@ -12,8 +12,8 @@ profile().stream_files > 0: it cannot pass on another kernel."""
 import numpy as np
 import pytest
 
+import plant_helpers as ph
 import structured_helpers as sh
-import test_count_structured_keys as tsk
 
 pytestmark = pytest.mark.gpu
 
@@ -55,12 +55,12 @@ class Planter:
         self.oracle, self.k, self.min_top, self.plen = oracle_lib, k, min_top, plen
         self.low = 2 * k - 6 - min_top
         self.rng = np.random.default_rng(seed)
-        self.occ = tsk._occupied(oracle_lib, k, self.low, (1,))
+        self.occ = ph.occupied(oracle_lib, k, self.low, (1,))
         self.text, self.planted, self.used = "", [], set()
 
     def prefix(self, head="A"):
         for _ in range(1000):
-            pre, _ = tsk._pick_prefix(head, self.plen, self.min_top, self.occ, self.rng)
+            pre, _ = ph.pick_prefix(head, self.plen, self.min_top, self.occ, self.rng)
             if pre not in self.used:
                 self.used.add(pre)
                 return pre
@@ -70,15 +70,15 @@ class Planter:
         """n reads of one k-mer each over `tails` (each at least once) in a sub-bucket of their own"""
         pre = pre or self.prefix()
         assert all(len(t) == self.k - len(pre) for t in tails) and len(set(tails)) == len(tails)
-        self.text += tsk._plant(pre, list(tails), n, self.rng)
+        self.text += ph.plant(pre, list(tails), n, self.rng)
         self.planted.append((pre, n, len(tails)))
         return pre
 
     def run(self, ops):
-        text = self.text + tsk._filler(self.oracle, self.k)
-        whi, wlo, wcn, prof = tsk._count_and_compare(ops, self.oracle, text, self.k, 1)
+        text = self.text + ph.filler(self.oracle, self.k)
+        whi, wlo, wcn, prof = ph.count_and_compare(ops, self.oracle, text, self.k, 1)
         for pre, n, d in self.planted:            # the sub-buckets are what the case says: n keys, d distinct, nothing else in them
-            assert tsk._subbucket(whi, wlo, wcn, self.low, tsk._id_range(pre[:PLEN], self.min_top)) == (n, d), (pre, n, d)
+            assert ph.subbucket(whi, wlo, wcn, self.low, ph.id_range(pre[:PLEN], self.min_top)) == (n, d), (pre, n, d)
         assert prof.stream_files > 0, prof.stream_files
         return whi, wlo, wcn, prof
 
@@ -181,7 +181,7 @@ def _file_with_empty(occ, min_top, first):
         head = sh.decode(f, 3)
         a = head + ("A" if first else "G") * (PLEN - 3)
         b = a[:-1] + ("C" if first else "T")                 # A0 C1 T2 G3: the sub-bucket next to it
-        if tsk._strays(occ, tsk._id_range(a, min_top)) == 0 and tsk._strays(occ, tsk._id_range(b, min_top)) == 0:
+        if ph.strays(occ, ph.id_range(a, min_top)) == 0 and ph.strays(occ, ph.id_range(b, min_top)) == 0:
             return a
     raise AssertionError("no file whose %s two sub-buckets are free of filler k-mers" % ("first" if first else "last"))
 
@@ -193,7 +193,7 @@ def test_first_and_last_subbucket_of_a_file(ops, oracle_lib, torch_cuda, monkeyp
     p = Planter(oracle_lib, K, MIN_TOP, 7700, PLEN)
     for first, n in ((True, 1537), (False, 257)):
         pre = _file_with_empty(p.occ, MIN_TOP, first)
-        lo, hi = tsk._id_range(pre, MIN_TOP)
+        lo, hi = ph.id_range(pre, MIN_TOP)
         assert hi == lo + 1 and (lo if first else hi) % (1 << MIN_TOP) == 0
         p.plant(_tails(300 if first else 257, K - PLEN, 800 + n), n, pre)
     _, _, _, prof = p.run(ops)

@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 
 import structured_helpers as sh
+from plant_helpers import (filler as _filler, occupied as _occupied, id_range as _id_range, pick_prefix as _pick_prefix, plant as _plant,
+                           count_and_compare as _count_and_compare, subbucket as _subbucket)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,99 +33,6 @@ def torch_cuda():
 def ops(native_lib, torch_cuda):
     from meryl_amd import count
     return count
-
-
-# ---- the filler reads and what they leave free ----
-
-_FILLER, _OCCUPIED = {}, {}
-
-
-def _filler(oracle_lib, k):
-    """the stream-kernel test's reads: 4.5 Mbases at ~1x, so that the judged plan (fifteen-bit histogram, narrowed files) is on"""
-    if k not in _FILLER:
-        _FILLER[k] = oracle_lib.synth_reads(k, 4_000_000, 0, 30_000).tobytes().decode()
-    return _FILLER[k]
-
-
-def _ids(whi, wlo, low):
-    """sub-bucket numbers (file bits included) of k-mers given as 64-bit halves: kmer >> low"""
-    if low >= 64:
-        return whi >> np.uint64(low - 64)
-    return (whi << np.uint64(64 - low)) | (wlo >> np.uint64(low))
-
-
-def _occupied(oracle_lib, k, low, modes):
-    """per mode: the sorted sub-bucket numbers of the filler's distinct k-mers and the running sum of their counts"""
-    out = []
-    for mode in modes:
-        key = (k, low, mode)
-        if key not in _OCCUPIED:
-            whi, wlo, wcn, _ = oracle_lib.count_brute(_filler(oracle_lib, k), k, mode)
-            _OCCUPIED[key] = (_ids(whi, wlo, low), np.concatenate([[0], np.cumsum(wcn.astype(np.int64))]))   # (k-mers ascending: so are the numbers)
-        out.append(_OCCUPIED[key])
-    return out
-
-
-def _id_range(pre, min_top):
-    """the sub-bucket numbers [first, end) whose k-mers begin with pre"""
-    shift = (6 + min_top) - 2 * len(pre)
-    v = sh.encode(pre)
-    return (v << shift, (v + 1) << shift) if shift >= 0 else (v >> -shift, (v >> -shift) + 1)
-
-
-def _strays(occ, rng_ids):
-    """filler k-mers (instances) inside the sub-buckets [first, end), the most over the modes"""
-    worst = 0
-    for ids, csum in occ:
-        l, r = np.searchsorted(ids, np.uint64(rng_ids[0]), "left"), np.searchsorted(ids, np.uint64(rng_ids[1]), "left")
-        worst = max(worst, int(csum[r] - csum[l]))
-    return worst
-
-
-def _pick_prefix(head, n_bases, min_top, occ, rng, max_strays=0):
-    """head + random bases (n_bases in all) such that the sub-buckets of k-mers beginning with it hold at most max_strays filler
-    k-mers: a planted sub-bucket then has exactly the size -- and the table -- its case is built for.  Returns (prefix, strays)."""
-    for _ in range(100_000):
-        pre = head + "".join(sh.BASES[i] for i in rng.integers(0, 4, n_bases - len(head)))
-        n = _strays(occ, _id_range(pre, min_top))
-        if n <= max_strays:
-            return pre, n
-    raise AssertionError("no prefix %s... with at most %d filler k-mers" % (head, max_strays))
-
-
-def _plant(pre, tails, n_inst, rng):
-    """n_inst reads of one k-mer each: every tail once, the rest drawn from them, shuffled"""
-    m = len(tails)
-    assert n_inst >= m
-    picks = np.concatenate([np.arange(m), rng.integers(0, m, n_inst - m)])
-    rng.shuffle(picks)
-    return ".".join(pre + tails[int(i)] for i in picks) + "."
-
-
-def _count_and_compare(ops, oracle_lib, text, k, mode):
-    """the device count of text against count_brute, exactly; returns (oracle k-mers hi, lo, counts, profile)"""
-    from meryl_amd import capi
-    cfg = capi.configure(k, len(text), 1 << 30, mode)
-    cfg.use_simple = 0
-    with ops.Session(cfg) as s:
-        s.set_profiling(True)
-        s.push_bases(text, end_of_sequence=False)
-        s.count()
-        klo, khi, counts, _ = s.result_wide()
-        prof = s.profile()
-    whi, wlo, wcn, _ = oracle_lib.count_brute(text, k, mode)
-    print("mode %d: %d distinct k-mers on the device, %d in the oracle; stream_files %d, stream_retries %d"
-          % (mode, len(klo), len(wlo), prof.stream_files, prof.stream_retries))
-    assert len(klo) == len(wlo), "%d k-mers missing from the device result (%d against the oracle's %d)" % (len(wlo) - len(klo), len(klo), len(wlo))
-    assert np.array_equal(klo, wlo) and np.array_equal(khi, whi) and np.array_equal(counts, wcn)
-    return whi, wlo, wcn, prof
-
-
-def _subbucket(whi, wlo, wcn, low, ids):
-    """(keys, distinct k-mers) of the sub-buckets [first, end) in the oracle's result"""
-    got = _ids(whi, wlo, low)
-    sel = (got >= np.uint64(ids[0])) & (got < np.uint64(ids[1]))
-    return int(wcn[sel].sum()), int(sel.sum())
 
 
 # ---- hash_count_stream_kernel<u32> ----

@@ -1513,8 +1513,10 @@ def test_gigantic_subbuckets_are_counted_in_slices(ops, oracle_lib, torch_cuda, 
     with 20 distinct suffixes (three slices), 200 K with 3000 (several passes per slice and in the merge), 66 K of ONE k-mer, 100 K
     that are all distinct and 300 K with 80 K distinct (DENSE: the slices' pairs do not fit half their keys -- 64 workgroups count a
     range of the suffix space each, MODE 3, a chain carries the ranges' places, huge_copy_back_kernel brings the result home),
-    40 K (oversized, not cut), next to ordinary reads; narrowed files (k = 16, 21, 26), whole 8-byte k-mers (k = 28, 31), K96
-    records (k = 40, 51) and 16-byte keys (k = 64: ranges only); MGC_HUGE_SLICES=0: round 5's form.  Against the oracle."""
+    40 K (oversized, not cut), next to ordinary reads; narrowed files (k = 16, 21), whole 8-byte k-mers (k = 26, 28, 31), K96
+    records (k = 40, 51) and 16-byte keys (k = 64) -- sliced and merged like the others (hash_count128_huge_kernel MODE 1 / 2; a
+    pair is two records), their dense ones by ranges; MGC_HUGE_SLICES=0: round 5's form.  Against the oracle.  (The edges of these
+    paths, and which of them ran: test_count_huge_edges.py.)"""
     from meryl_amd import capi
     monkeypatch.setenv("MGC_FINISH_MIN_TOP", str(min_top))
     monkeypatch.setenv("MGC_HUGE_SLICES", slices)
@@ -1534,7 +1536,7 @@ def test_gigantic_subbuckets_are_counted_in_slices(ops, oracle_lib, torch_cuda, 
     if k <= 32:
         text = (cluster("AAC", 70_000, 20) + cluster("ACA", 200_000, 3000) + cluster("ATT", 66_000, 1) + cluster("AGC", 100_000, 100_000)
                 + cluster("CAT", 40_000, 700) + cluster("AAC", 90_000, 5) + cluster("GGT", 300_000, 80_000) + reads)
-    else:       # 16-byte keys / K96 records: every cut sub-bucket is counted by ranges (hash_count128_huge_kernel MODE 3)
+    else:       # 16-byte keys / K96 records (hash_count128_huge_kernel): 70 K / 20 and 66 K / 1 in slices + merge (MODE 1 / 2), the dense two by ranges (MODE 3)
         text = (cluster("AAC", 70_000, 20) + cluster("ATT", 66_000, 1) + cluster("AGC", 80_000, 80_000) + cluster("CAT", 40_000, 700)
                 + cluster("GGT", 150_000, 30_000) + reads)
     for mode in (0, 1):                                     # forward mode keeps the clusters where they were put
