@@ -15,8 +15,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmeryl_gpu_count.so")
 SOURCES = ["mgc_kmer.hip", "mgc_sort.hip", "mgc_scan.hip", "mgc_finish.hip", "mgc_misc.hip", "mgc_parse.hip",
            "mgc_encode.hip", "mgc_decode.hip", "mgc_merge.hip", "mgc_merge_many.hip", "mgc_lookup.hip", "mgc_filter.hip", "mgc_import.hip", "mgc_analyze.hip", "mgc_value_hist.hip", "mgc_positions.hip", "mgc_list.hip", "mgc_bam.hip", "mgc_gzip.hip",
-           "mgc_api.cpp", "mgc_textfile.cpp", "mgc_import.cpp", "mgc_analyze.cpp", "mgc_dbfile.cpp", "mgc_positions.cpp", "mgc_count.cpp", "mgc_stream.cpp", "mgc_eval.cpp", "mgc_runs.cpp", "mgc_node.cpp", "meryl_db.cpp", "meryl_seq.cpp"]
-HEADERS = ["mgc_device.h", "mgc_common.hpp", "mgc_compact.hpp", "mgc_bases.hpp", "mgc_stream_geom.hpp", "mdb_layout.h", "mdb_statistics.hpp", "mgc_session.hpp", "mgc_devbuf.hpp", "mgc_dbfile.hpp", "mgc_hist_list.hpp", "mgc_clock.hpp", "mgc_chunk_ring.hpp", "mgc_bgzf.hpp", "mgc_bam_walk.hpp", "mgc_gzip_par.hpp", "mgc_runs.hpp", "mgc_lookup_dev.hpp", "mgc_import_dev.hpp", "mgc_analyze_dev.hpp", "mgc_positions_dev.hpp", "mgc_fastx.hpp", "mgc_label.hpp", "mgc_selector.hpp", "mgc_value.hpp", "mgc_route.hpp", "mgc_group_route.hpp", "mgc_group_batch.hpp", "mgc_pack_plan.hpp", "mgc_list.hpp",
+           "mgc_api.cpp", "mgc_input.cpp", "mgc_textfile.cpp", "mgc_import.cpp", "mgc_analyze.cpp", "mgc_dbfile.cpp", "mgc_positions.cpp", "mgc_count.cpp", "mgc_stream.cpp", "mgc_eval.cpp", "mgc_runs.cpp", "mgc_node.cpp", "meryl_db.cpp", "meryl_seq.cpp"]
+HEADERS = ["mgc_device.h", "mgc_common.hpp", "mgc_compact.hpp", "mgc_bases.hpp", "mgc_stream_geom.hpp", "mdb_layout.h", "mdb_statistics.hpp", "mgc_session.hpp", "mgc_devbuf.hpp", "mgc_dbfile.hpp", "mgc_hist_list.hpp", "mgc_clock.hpp", "mgc_chunk_ring.hpp", "mgc_bgzf.hpp", "mgc_bam_walk.hpp", "mgc_gzip_par.hpp", "mgc_gzip_crc.hpp", "mgc_input.hpp", "mgc_runs.hpp", "mgc_lookup_dev.hpp", "mgc_import_dev.hpp", "mgc_analyze_dev.hpp", "mgc_positions_dev.hpp", "mgc_fastx.hpp", "mgc_label.hpp", "mgc_selector.hpp", "mgc_value.hpp", "mgc_route.hpp", "mgc_group_route.hpp", "mgc_group_batch.hpp", "mgc_pack_plan.hpp", "mgc_list.hpp",
            os.path.join("..", "..", "include", "meryl_gpu_count.h"),
            os.path.join("..", "..", "include", "meryl_db.h"), os.path.join("..", "..", "include", "meryl_seq.h"),
            os.path.join("..", "..", "include", "meryl_lookup.h"), os.path.join("..", "..", "include", "meryl_import.h"),

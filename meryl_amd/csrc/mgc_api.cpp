@@ -3,12 +3,13 @@
 // Host-side mirror of the reference's counting engine:
 //   mgc_configure_counting  <-> merylOperation::configureCounting  src/meryl/merylOp-count.C:300-403
 //   mgc_open/push/count/finish <-> merylOperation::countThreads     src/meryl/merylOp-countThreads.C:385-474
+// Here: configuration, the bare mgc_dev_* operators, open / close, count and the result calls.  What is pushed into a session between
+// open and count is staged by mgc_input.cpp (settle_input hands the staged stream over; count_staged_batch is what its batches run).
 // There is NO CPU fallback in here: every compute entry point launches HIP
 // kernels and fails with MGC_EHIP if the device or the code object is missing.
 #include "../../include/meryl_gpu_count.h"
 #include "mgc_device.h"
 #include "mgc_session.hpp"
-#include "mgc_gzip_par.hpp"
 #include "mgc_runs.hpp"
 #include "mgc_selector.hpp"
 #include "mgc_value.hpp"
@@ -596,6 +597,32 @@ extern "C" int mgc_dev_synth_reads_ex(uint64_t seed, uint64_t genome_len, uint64
                                         repeat_ppm, repeat_unit, repeat_families, d_out, (hipStream_t)stream), "synth_reads");
 }
 
+extern "C" int mgc_dev_bam_decode(const uint8_t *d_piece, uint64_t piece_bytes, const void *d_segments, uint64_t n_segments, uint64_t out_bytes,
+                                  uint8_t *d_out, void *stream) {
+  if ((!d_piece && piece_bytes) || (!d_segments && n_segments) || (!d_out && out_bytes)) return MGC_EINVAL;
+  if (piece_bytes > 0xffffffffull) { set_err(nullptr, "mgc_dev_bam_decode: a piece holds less than 4 GiB"); return MGC_EINVAL; }
+  HIP_TRY((mgc_session *)nullptr, mgc::launch_bam_decode(d_piece, piece_bytes, d_segments, n_segments, out_bytes, d_out, static_cast<hipStream_t>(stream)));
+  return MGC_OK;
+}
+
+extern "C" int mgc_dev_gzip_resolve(uint8_t *d_text, uint64_t text_bytes, const uint16_t *d_symbols, uint64_t n_symbols, const uint8_t *d_window_in,
+                                    uint32_t window_valid, uint8_t *d_window_out, uint32_t *d_error, void *stream) {
+  if ((!d_text && text_bytes) || (!d_symbols && n_symbols) || (n_symbols && !d_error) || n_symbols > text_bytes || window_valid > mgc::GZ_WINDOW ||
+      (!d_window_in && window_valid) || (d_window_out && d_window_out == d_window_in)) {
+    set_err(nullptr, "mgc_dev_gzip_resolve: n_symbols <= text_bytes, window_valid <= 32768 (0 without a window), two different windows");
+    return MGC_EINVAL;
+  }
+  HIP_TRY((mgc_session *)nullptr, mgc::launch_gzip_resolve(d_text, text_bytes, d_symbols, n_symbols, d_window_in, window_valid, d_window_out, d_error,
+                                                           static_cast<hipStream_t>(stream)));
+  return MGC_OK;
+}
+
+extern "C" int mgc_dev_crc32_pieces(const uint8_t *d_text, const uint64_t *d_begin, const uint32_t *d_len, uint64_t n_pieces, uint32_t *d_crc, void *stream) {
+  if (n_pieces && (!d_text || !d_begin || !d_len || !d_crc)) return MGC_EINVAL;
+  HIP_TRY((mgc_session *)nullptr, mgc::launch_gzip_crc32(d_text, d_begin, d_len, n_pieces, d_crc, static_cast<hipStream_t>(stream)));
+  return MGC_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Session
 // ---------------------------------------------------------------------------
@@ -705,17 +732,9 @@ extern "C" void mgc_close(mgc_session *s) {
   delete s->runs;
   s->runs = nullptr;
   for (int i = 0; i < 2; i++) {
-    if (s->text_pinned[i]) (void)hipHostFree(s->text_pinned[i]);
-    if (s->text_ev[i]) (void)hipEventDestroy(s->text_ev[i]);
-    if (s->up_ev[i]) (void)hipEventDestroy(s->up_ev[i]);
     if (s->pin[i]) (void)hipHostFree(s->pin[i]);
     if (s->pin_ev[i]) (void)hipEventDestroy(s->pin_ev[i]);
-    if (s->bam_seg_pinned[i]) (void)hipHostFree(s->bam_seg_pinned[i]);
-    if (s->gz_sym_pinned[i]) (void)hipHostFree(s->gz_sym_pinned[i]);
-    if (s->gz_tab_pinned[i]) (void)hipHostFree(s->gz_tab_pinned[i]);
   }
-  for (char *&p : s->text_ring) if (p) { (void)hipHostFree(p); p = nullptr; }
-  if (s->st_up) { (void)hipStreamSynchronize(s->st_up); (void)hipStreamDestroy(s->st_up); }
   if (s->st_in) (void)hipStreamDestroy(s->st_in);
   if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
   if (s->h_stats) (void)hipHostFree(s->h_stats);
@@ -725,643 +744,7 @@ extern "C" void mgc_close(mgc_session *s) {
   if (s->ev_pack_done) (void)hipEventDestroy(s->ev_pack_done);
   for (int i = 0; i < mgc_session::HUGE_EXTRA; i++) if (s->stream_h[i]) (void)hipStreamDestroy(s->stream_h[i]);
   if (s->stream) (void)hipStreamDestroy(s->stream);
-  delete s;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-//  Input staging (see mgc_session.hpp): one device-resident base stream per batch, double buffered
-// ---------------------------------------------------------------------------------------------------------------
-struct HostParseState { uint64_t out_len, file_start_len; uint32_t state, prev_nl, error, pad; };
-
-static int count_staged_batch(mgc_session *s, int which, uint64_t n);      // count stage[which][0, n) and merge it into R
-
-// The count's largest buffer (the k-mer instances, 8 / 16 B per base at most) is allocated NOW, by a helper thread, while the
-// caller reads and uploads its input: a first large hipMalloc is the slowest single thing a freshly started process does
-// (0.3 s for 100 GB on a quiet device, seconds when another process has just released that much), and until the count starts
-// nobody needs the memory.  Only when the whole input is expected to fit one pass; a wrong estimate costs a re-allocation,
-// never a wrong result.
-extern "C" int mgc_prepare(mgc_session *s, uint64_t expected_bases) {
-  if (!s) return MGC_EINVAL;
-  if (s->borrowed || s->counted || s->prep_active || expected_bases == 0) return MGC_OK;
-  HIP_TRY(s, hipSetDevice(s->device));
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return MGC_OK;
-  const uint64_t per_base = 2 + 14ull * s->key_words;
-  if (s->batch_limit && expected_bases > s->batch_limit) return MGC_OK;
-  if ((double)expected_bases * (double)per_base > 0.8 * (double)free_b) return MGC_OK;       // batches: their arena is sized by the first one
-  const size_t bytes = sizeof(uint64_t) * s->key_words * expected_bases;
-  s->prep_active = true;
-  s->prep_thread = std::thread([s, bytes] {
-    (void)hipSetDevice(s->device);
-    if (s->ensure(mgc_session::B_X, bytes) != hipSuccess) (void)hipGetLastError();           // the count will say so itself
-    // ... and the code objects of the count and of the database encoder: loaded lazily at the first launch, i.e. inside a fresh
-    // process's first count otherwise (0.36 s of count for a 0.12 s step, profiles/r04o)
-    (void)mgc::warm_kmer(); (void)mgc::warm_scan(); (void)mgc::warm_sort(); (void)mgc::warm_finish(); (void)mgc::warm_encode(); (void)mgc::warm_value_hist();
-    (void)hipGetLastError();
-  });
-  return MGC_OK;
-}
-
-extern "C" int mgc_set_batch_bases(mgc_session *s, uint64_t bases_per_batch) {
-  if (!s) return MGC_EINVAL;
-  s->batch_limit = bases_per_batch;
-  return MGC_OK;
-}
-
-static inline int stage_id(int which) { return which ? mgc_session::B_STAGE1 : mgc_session::B_STAGE0; }
-static inline uint8_t *stage_ptr(mgc_session *s, int which) { return reinterpret_cast<uint8_t *>(s->buf[stage_id(which)].p); }
-
-// first input of a session: streams, parse state, the batch size
-static int input_setup(mgc_session *s) {
-  if (s->borrowed || s->counted) { set_err(&s->err, "input after device input / count"); return MGC_ESTATE; }
-  HIP_TRY(s, hipSetDevice(s->device));
-  if (s->state_ready) return MGC_OK;
-  if (s->batch_limit == 0) {
-    // One pass holds, per base: the staged base, 0.87 k-mer instances of 8 (16) B in X, 4 B of count scratch each, the
-    // distinct k-mers with their counts (about a seventh of the instances at 30x), the ping-pong buffer of the largest
-    // file -- measured 13 B per base at k=21 (130 GB for 10 Gbp: DESIGN.md section 2), 16 (30) B with slack.  A fifth of
-    // the HBM stays free for the running result of earlier batches and its merge target.
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b) {
-      const uint64_t per_base = 2 + 14ull * s->key_words;
-      s->batch_limit = (uint64_t)((double)free_b * 0.80 / (double)per_base);
-    }
-    if (s->batch_limit < (1u << 20)) s->batch_limit = 1u << 20;
-  }
-  HIP_TRY(s, s->ensure(mgc_session::B_TEXT_STATE, mgc::text_parse_state_bytes() + 64));
-  HIP_TRY(s, s->ensure_preserve(stage_id(s->fill), 1u << 20, 0, s->st_in));
-  HIP_TRY(s, mgc::launch_text_file_op(s->buf[mgc_session::B_TEXT_STATE].p, stage_ptr(s, s->fill), 3, s->st_in));
-  s->state_ready = true;
-  return MGC_OK;
-}
-
-// the device knows the exact length of the staged stream; bring the host's copy up to date (synchronises st_in)
-static int resolve_length(mgc_session *s, HostParseState *out = nullptr) {
-  HostParseState h;
-  HIP_TRY(s, hipMemcpyAsync(&h, s->buf[mgc_session::B_TEXT_STATE].p, sizeof(h), hipMemcpyDeviceToHost, s->st_in));
-  HIP_TRY(s, hipStreamSynchronize(s->st_in));
-  s->fill_len = h.out_len;
-  s->len_inexact = false;
-  if (out) *out = h;
-  return MGC_OK;
-}
-
-static int join_worker(mgc_session *s) {
-  if (s->worker_active) {
-    const double t0 = mgc::now_s();
-    s->worker.join();
-    s->tr_join += mgc::now_s() - t0;
-    s->worker_active = false;
-    if (s->worker_rc != MGC_OK) return s->worker_rc;
-  }
-  return s->worker_rc;
-}
-
-// host-pushed bases collected in the current pinned chunk -> stage[fill] (asynchronous; the other chunk takes over)
-static int flush_pinned(mgc_session *s) {
-  if (s->pin_len == 0) return MGC_OK;
-  if (s->len_inexact) { const int rc = resolve_length(s); if (rc != MGC_OK) return rc; }
-  const int c = s->pin_cur;
-  HIP_TRY(s, s->ensure_preserve(stage_id(s->fill), s->fill_len + s->pin_len + 4096, s->fill_len, s->st_in));
-  HIP_TRY(s, hipMemcpyAsync(stage_ptr(s, s->fill) + s->fill_len, s->pin[c], s->pin_len, hipMemcpyHostToDevice, s->st_in));
-  s->fill_len += s->pin_len;
-  HIP_TRY(s, mgc::launch_text_set_len(s->buf[mgc_session::B_TEXT_STATE].p, s->fill_len, 0, s->st_in));
-  HIP_TRY(s, hipEventRecord(s->pin_ev[c], s->st_in));
-  s->pin_used[c] = true;
-  s->pin_len = 0;
-  s->pin_cur = c ^ 1;
-  if (s->pin_used[s->pin_cur]) HIP_TRY(s, hipEventSynchronize(s->pin_ev[s->pin_cur]));     // that chunk's upload has read it
-  return MGC_OK;
-}
-
-// The staged stream has reached the batch size: everything up to the last sequence boundary becomes a batch, counted by
-// the worker thread while the caller goes on filling the other staging buffer (k-mers never span a breaker, so no
-// carry is needed, and `compress` stays a per-sequence operation).
-static int cut_batch(mgc_session *s) {
-  int rc = flush_pinned(s);
-  if (rc != MGC_OK) return rc;
-  HostParseState h;
-  rc = resolve_length(s, &h);
-  if (rc != MGC_OK) return rc;
-  if (s->text_open && h.error) return MGC_OK;              // the open file is about to be refused and rolled back: not now
-  if (s->fill_len < s->batch_limit) return MGC_OK;         // the bound was pessimistic
-  if (s->fill_len < s->no_cut_below) return MGC_OK;        // no sequence boundary was found last time: look again once the stream has doubled
-  uint64_t *d_last = reinterpret_cast<uint64_t *>(reinterpret_cast<unsigned char *>(s->buf[mgc_session::B_TEXT_STATE].p) +
-                                                  ((mgc::text_parse_state_bytes() + 7) / 8) * 8);
-  uint64_t cut = 0;
-  HIP_TRY(s, mgc::launch_last_breaker(stage_ptr(s, s->fill), s->fill_len, d_last, s->st_in));
-  HIP_TRY(s, hipMemcpyAsync(&cut, d_last, sizeof(cut), hipMemcpyDeviceToHost, s->st_in));
-  HIP_TRY(s, hipStreamSynchronize(s->st_in));
-  uint64_t overlap = 0;
-  if (cut == 0) {
-    // One sequence longer than a batch (this used to return and re-scan the whole staged stream on every later
-    // push -- O(n^2) -- while staging grew without bound).  The reference spills inside a sequence too; here the batch is cut
-    // at the end of what is staged and the last k-1 bases are staged AGAIN in front of the next batch: a window that starts
-    // in them is incomplete in this batch and complete in the next, so no k-mer is lost or counted twice (the rule the
-    // node count cuts its slices by).  `compress` needs whole sequences: such a stream waits until it has doubled.
-    if (s->cfg.homopoly_compress || s->text_open || s->fill_len < 4ull * s->cfg.k) {
-      s->no_cut_below = s->fill_len * 2;
-      return MGC_OK;
-    }
-    cut = s->fill_len;
-    overlap = s->cfg.k - 1;
-  }
-  rc = join_worker(s);                                      // the previous batch is done: its staging buffer is free, R is stable
-  if (rc != MGC_OK) return rc;
-  const uint64_t tail = s->fill_len - cut + overlap;
-  cut -= overlap;                                           // the tail starts k-1 bases before the cut ...
-  const int other = s->fill ^ 1;
-  HIP_TRY(s, s->ensure_preserve(stage_id(other), tail + (1u << 20), 0, s->st_in));
-  if (tail) HIP_TRY(s, hipMemcpyAsync(stage_ptr(s, other), stage_ptr(s, s->fill) + cut, tail, hipMemcpyDeviceToDevice, s->st_in));
-  HIP_TRY(s, mgc::launch_text_set_len(s->buf[mgc_session::B_TEXT_STATE].p, tail, s->text_open ? 1 : 0, s->st_in));
-  HIP_TRY(s, hipStreamSynchronize(s->st_in));
-  if (s->text_open) s->text_cut_in_file = true;
-  const int which = s->fill;
-  s->fill = other;
-  s->fill_len = tail;
-  s->no_cut_below = 0;
-  cut += overlap;                                           // ... and the batch still ends at the cut
-  s->worker_rc = MGC_OK;
-  s->worker_active = true;
-  s->worker = std::thread([s, which, cut] { s->worker_rc = count_staged_batch(s, which, cut); });
-  return MGC_OK;
-}
-
-extern "C" int mgc_push_bases(mgc_session *s, const char *bases, size_t len, int end_of_sequence) {
-  if (!s || (!bases && len)) return MGC_EINVAL;
-  int rc = input_setup(s);
-  if (rc != MGC_OK) return rc;
-  if (s->text_open) { set_err(&s->err, "mgc_push_bases while a text file is open (mgc_end_text first)"); return MGC_ESTATE; }
-  s->input_seen = true;
-  for (int i = 0; i < 2; i++) {
-    if (!s->pin[i]) HIP_TRY(s, hipHostMalloc(reinterpret_cast<void **>(&s->pin[i]), mgc_session::PIN_CHUNK, hipHostMallocDefault));
-    if (!s->pin_ev[i]) HIP_TRY(s, hipEventCreateWithFlags(&s->pin_ev[i], hipEventDisableTiming));
-  }
-  const char breaker = '.';                                  // merylOp-countThreads.C:214-215
-  for (int part = 0; part < 2; part++) {
-    const char *src = part ? &breaker : bases;
-    size_t left = part ? (end_of_sequence ? 1 : 0) : len;
-    while (left) {
-      const size_t take = std::min(left, mgc_session::PIN_CHUNK - s->pin_len);
-      const double t0 = mgc::now_s();
-      memcpy(s->pin[s->pin_cur] + s->pin_len, src, take);
-      const double t1 = mgc::now_s();
-      s->tr_memcpy += t1 - t0;
-      s->pin_len += take; src += take; left -= take;
-      if (s->pin_len == mgc_session::PIN_CHUNK) { rc = flush_pinned(s); if (rc != MGC_OK) return rc; }
-      const double t2 = mgc::now_s();
-      s->tr_flush += t2 - t1;
-      if (s->fill_len + s->pin_len >= s->batch_limit) { rc = cut_batch(s); if (rc != MGC_OK) return rc; s->tr_cut += mgc::now_s() - t2; }
-    }
-  }
-  return MGC_OK;
-}
-
-// ---- text input, parsed on the device (include/meryl_gpu_count.h) ------------------------------
-static int text_setup(mgc_session *s) {
-  int rc = input_setup(s);
-  if (rc != MGC_OK) return rc;
-  if (!s->text_pinned[0]) {
-    HIP_TRY(s, s->ensure(mgc_session::B_TEXT_IN0, mgc_session::TEXT_CHUNK));
-    HIP_TRY(s, s->ensure(mgc_session::B_TEXT_IN1, mgc_session::TEXT_CHUNK));
-    HIP_TRY(s, s->ensure(mgc_session::B_TEXT_WS, mgc::text_parse_workspace_bytes(mgc_session::TEXT_CHUNK)));
-    if (!s->st_up) HIP_TRY(s, hipStreamCreateWithFlags(&s->st_up, hipStreamNonBlocking));
-    for (int i = 0; i < 2; i++) {
-      if (!s->text_pinned[i]) HIP_TRY(s, hipHostMalloc(reinterpret_cast<void **>(&s->text_pinned[i]), mgc_session::TEXT_CHUNK, hipHostMallocDefault));
-      if (!s->text_ev[i]) HIP_TRY(s, hipEventCreateWithFlags(&s->text_ev[i], hipEventDisableTiming));
-      if (!s->up_ev[i]) HIP_TRY(s, hipEventCreateWithFlags(&s->up_ev[i], hipEventDisableTiming));
-    }
-  }
-  return MGC_OK;
-}
-
-extern "C" int mgc_reserve_text(mgc_session *s, uint64_t text_bytes) {
-  if (!s) return MGC_EINVAL;
-  int rc = text_setup(s);
-  if (rc != MGC_OK) return rc;
-  // no more than a batch (plus what a chunk can add before the cut is noticed) is ever staged at once
-  const uint64_t want = std::min<uint64_t>(text_bytes, s->batch_limit + 2 * mgc_session::TEXT_CHUNK) + 4096;
-  HIP_TRY(s, s->ensure_preserve(stage_id(s->fill), want, s->fill_len, s->st_in));
-  return MGC_OK;
-}
-
-extern "C" int mgc_begin_text(mgc_session *s, int format) {
-  if (!s || (format != MGC_TEXT_FASTA && format != MGC_TEXT_FASTQ)) return MGC_EINVAL;
-  if (s->text_open) { set_err(&s->err, "mgc_begin_text: the previous file was not ended"); return MGC_ESTATE; }
-  int rc = text_setup(s);
-  if (rc != MGC_OK) return rc;
-  rc = flush_pinned(s);                                     // host-pushed bases come first in the stream
-  if (rc != MGC_OK) return rc;
-  HIP_TRY(s, mgc::launch_text_file_op(s->buf[mgc_session::B_TEXT_STATE].p, stage_ptr(s, s->fill), 0, s->st_in));
-  s->text_format = format;
-  s->text_open = true;
-  s->text_cut_in_file = false;
-  s->input_seen = true;
-  return MGC_OK;
-}
-
-// one piece (<= TEXT_CHUNK bytes, in pinned memory) -> device input buffer b -> parse kernels; returns once they are queued
-int mgc::text_submit(mgc_session *s, const char *pinned_src, size_t piece) {
-  const uint32_t b = s->text_next & 1u;
-  if (s->text_ev_used[b]) HIP_TRY(s, hipEventSynchronize(s->text_ev[b]));       // device buffer b (and its previous source) are free again
-  HIP_TRY(s, s->ensure_preserve(stage_id(s->fill), s->fill_len + piece + 4096, s->fill_len, s->st_in));
-  uint8_t *d_in = reinterpret_cast<uint8_t *>(s->buf[b ? mgc_session::B_TEXT_IN1 : mgc_session::B_TEXT_IN0].p);
-  // the copy runs on its own stream, so that chunk c travels while chunk c-1 is parsed (one stream did them in turn: 0.56 ms
-  // of copy + 0.4 ms of parse per 32 MiB, 0.6 s of the 20 GB file -> database run; profiles/r03m_e2e_io.txt)
-  HIP_TRY(s, hipMemcpyAsync(d_in, pinned_src, piece, hipMemcpyHostToDevice, s->st_up));
-  HIP_TRY(s, hipEventRecord(s->up_ev[b], s->st_up));
-  HIP_TRY(s, hipStreamWaitEvent(s->st_in, s->up_ev[b], 0));
-  HIP_TRY(s, mgc::launch_text_parse(d_in, piece, s->text_format == MGC_TEXT_FASTQ, s->buf[mgc_session::B_TEXT_STATE].p,
-                                    s->buf[mgc_session::B_TEXT_WS].p, stage_ptr(s, s->fill), s->st_in));
-  HIP_TRY(s, hipEventRecord(s->text_ev[b], s->st_in));
-  s->text_ev_used[b] = true;
-  s->text_next++;
-  s->fill_len += piece;                                     // an upper bound: headers, qualities and line ends are dropped
-  s->len_inexact = true;
-  if (s->fill_len >= s->batch_limit) return cut_batch(s);
-  return MGC_OK;
-}
-
-extern "C" int mgc_push_text(mgc_session *s, const char *text, size_t len) {
-  if (!s || (!text && len)) return MGC_EINVAL;
-  if (!s->text_open || s->text_format == mgc_session::TEXT_BAM) { set_err(&s->err, "mgc_push_text without mgc_begin_text"); return MGC_ESTATE; }
-  HIP_TRY(s, hipSetDevice(s->device));
-  while (len) {
-    const size_t piece = len < mgc_session::TEXT_CHUNK ? len : mgc_session::TEXT_CHUNK;
-    const uint32_t b = s->text_next & 1u;
-    if (s->text_ev_used[b]) HIP_TRY(s, hipEventSynchronize(s->text_ev[b]));     // pinned + device buffer b are free again
-    memcpy(s->text_pinned[b], text, piece);
-    const int rc = mgc::text_submit(s, s->text_pinned[b], piece);
-    if (rc != MGC_OK) return rc;
-    text += piece;
-    len -= piece;
-  }
-  return MGC_OK;
-}
-
-// the last two text uploads still read from their pinned sources: wait for them
-void mgc::text_drain(mgc_session *s) {
-  for (int b = 0; b < 2; b++) if (s->text_ev_used[b]) (void)hipEventSynchronize(s->text_ev[b]);
-}
-
-// Closes the open file and takes what it has put into the stream back out.  MGC_EINVAL, and the stream as it is, when part
-// of the file went into a batch that is already counted: that cannot be taken back.
-int mgc::text_rollback(mgc_session *s) {
-  s->text_open = false;
-  if (s->text_cut_in_file) return MGC_EINVAL;
-  HIP_TRY(s, mgc::launch_text_file_op(s->buf[mgc_session::B_TEXT_STATE].p, stage_ptr(s, s->fill), 2, s->st_in));
-  return resolve_length(s);
-}
-
-extern "C" int mgc_end_text(mgc_session *s) {
-  if (!s) return MGC_EINVAL;
-  if (!s->text_open || s->text_format == mgc_session::TEXT_BAM) { set_err(&s->err, "mgc_end_text without mgc_begin_text"); return MGC_ESTATE; }
-  HIP_TRY(s, hipSetDevice(s->device));
-  s->text_open = false;
-  HIP_TRY(s, s->ensure_preserve(stage_id(s->fill), s->fill_len + 4096, s->fill_len, s->st_in));
-  HIP_TRY(s, mgc::launch_text_file_op(s->buf[mgc_session::B_TEXT_STATE].p, stage_ptr(s, s->fill), 1, s->st_in));
-  HostParseState h;
-  int rc = resolve_length(s, &h);
-  if (rc != MGC_OK) return rc;
-  if (h.error) {
-    rc = mgc::text_rollback(s);
-    if (rc == MGC_EINVAL)
-      set_err(&s->err, "the file stops being strict four-line FASTQ after part of it was counted (input larger than one batch): "
-                       "convert it, or feed it through mgc_push_bases from the start");
-    if (rc != MGC_OK) return rc;
-    set_err(&s->err, "the file is not strict four-line FASTQ: feed it through mgc_push_bases (meryl_seq.h reader)");
-    return MGC_EFORMAT;
-  }
-  if (s->fill_len >= s->batch_limit) return cut_batch(s);
-  return MGC_OK;
-}
-
-// ---- BAM input, decoded on the device (include/meryl_gpu_count.h) ------------------------------
-// The open BAM file shares the text file's state (text_open, the cut inside a file, the rollback point in the device's parse
-// state); its lengths are exact on the host, so fill_len stays exact while it is open.
-extern "C" int mgc_begin_bam(mgc_session *s) {
-  if (!s) return MGC_EINVAL;
-  if (s->text_open) { set_err(&s->err, "mgc_begin_bam: the previous file was not ended"); return MGC_ESTATE; }
-  int rc = text_setup(s);
-  if (rc != MGC_OK) return rc;
-  rc = flush_pinned(s);                                     // host-pushed bases come first in the stream
-  if (rc != MGC_OK) return rc;
-  if (s->len_inexact) { rc = resolve_length(s); if (rc != MGC_OK) return rc; }
-  HIP_TRY(s, mgc::launch_text_file_op(s->buf[mgc_session::B_TEXT_STATE].p, stage_ptr(s, s->fill), 0, s->st_in));
-  s->bam_walker.reset();
-  s->tr_bam_walk = 0;
-  s->text_format = mgc_session::TEXT_BAM;
-  s->text_open = true;
-  s->text_cut_in_file = false;
-  s->input_seen = true;
-  return MGC_OK;
-}
-
-int mgc::bam_submit(mgc_session *s, const char *pinned_src, size_t piece) {
-  const double t0 = mgc::now_s();
-  s->bam_segs.clear();
-  uint64_t out_bytes = 0;
-  const bool ok = s->bam_walker.walk(reinterpret_cast<const unsigned char *>(pinned_src), piece, &s->bam_segs, &out_bytes);
-  s->tr_bam_walk += mgc::now_s() - t0;
-  if (!ok) return mgc::BAM_REFUSED;
-  const size_t nseg = s->bam_segs.size();
-  if (nseg == 0) {
-    // Header bytes, names, qualities, aux -- a piece that lies wholly inside a long record's tail: nothing for the device.  The
-    // whole-file reader's ring gives a slot back two pieces after its submit BECAUSE a submit waits for the piece two before it
-    // (mgc_chunk_ring.hpp); a piece that queues nothing would break that count, so it waits for both pieces in flight instead.
-    mgc::text_drain(s);
-    return MGC_OK;
-  }
-  const uint32_t b = s->text_next & 1u;
-  if (s->text_ev_used[b]) HIP_TRY(s, hipEventSynchronize(s->text_ev[b]));       // device buffers b (and their previous sources) are free again
-  HIP_TRY(s, s->ensure_preserve(stage_id(s->fill), s->fill_len + out_bytes + 4096, s->fill_len, s->st_in));
-  if (s->bam_seg_cap[b] < nseg) {                           // grow-only, with room to spare: records of one file are alike
-    if (s->bam_seg_pinned[b]) { (void)hipHostFree(s->bam_seg_pinned[b]); s->bam_seg_pinned[b] = nullptr; s->bam_seg_cap[b] = 0; }
-    const size_t want = nseg + nseg / 2 + 4096;
-    HIP_TRY(s, hipHostMalloc(reinterpret_cast<void **>(&s->bam_seg_pinned[b]), want * sizeof(mgc::BamSegment), hipHostMallocDefault));
-    s->bam_seg_cap[b] = want;
-  }
-  const int seg_buf = b ? mgc_session::B_BAM_SEG1 : mgc_session::B_BAM_SEG0;
-  HIP_TRY(s, s->ensure(seg_buf, s->bam_seg_cap[b] * sizeof(mgc::BamSegment)));
-  memcpy(s->bam_seg_pinned[b], s->bam_segs.data(), nseg * sizeof(mgc::BamSegment));
-  uint8_t *d_in = reinterpret_cast<uint8_t *>(s->buf[b ? mgc_session::B_TEXT_IN1 : mgc_session::B_TEXT_IN0].p);
-  HIP_TRY(s, hipMemcpyAsync(d_in, pinned_src, piece, hipMemcpyHostToDevice, s->st_up));
-  HIP_TRY(s, hipMemcpyAsync(s->buf[seg_buf].p, s->bam_seg_pinned[b], nseg * sizeof(mgc::BamSegment), hipMemcpyHostToDevice, s->st_up));
-  HIP_TRY(s, hipEventRecord(s->up_ev[b], s->st_up));
-  HIP_TRY(s, hipStreamWaitEvent(s->st_in, s->up_ev[b], 0));
-  HIP_TRY(s, mgc::launch_bam_decode(d_in, piece, s->buf[seg_buf].p, nseg, out_bytes, stage_ptr(s, s->fill) + s->fill_len, s->st_in));
-  s->fill_len += out_bytes;                                 // exact
-  HIP_TRY(s, mgc::launch_text_set_len(s->buf[mgc_session::B_TEXT_STATE].p, s->fill_len, 0, s->st_in));
-  HIP_TRY(s, hipEventRecord(s->text_ev[b], s->st_in));
-  s->text_ev_used[b] = true;
-  s->text_next++;
-  if (s->fill_len >= s->batch_limit) return cut_batch(s);
-  return MGC_OK;
-}
-
-int mgc::bam_refuse(mgc_session *s, const char *what) {
-  const std::string why = s->bam_walker.error();
-  const int rc = mgc::text_rollback(s);
-  if (rc == MGC_EINVAL) set_err(&s->err, "'%s': %s, after part of the file was counted (input larger than one batch)", what, why.c_str());
-  if (rc != MGC_OK) return rc;
-  set_err(&s->err, "'%s': %s", what, why.c_str());
-  return MGC_EFORMAT;
-}
-
-extern "C" int mgc_push_bam(mgc_session *s, const void *bam_bytes, size_t len) {
-  if (!s || (!bam_bytes && len)) return MGC_EINVAL;
-  if (!s->text_open || s->text_format != mgc_session::TEXT_BAM) { set_err(&s->err, "mgc_push_bam without mgc_begin_bam"); return MGC_ESTATE; }
-  HIP_TRY(s, hipSetDevice(s->device));
-  const char *src = static_cast<const char *>(bam_bytes);
-  while (len) {
-    const size_t piece = len < mgc_session::TEXT_CHUNK ? len : mgc_session::TEXT_CHUNK;
-    const uint32_t b = s->text_next & 1u;
-    if (s->text_ev_used[b]) HIP_TRY(s, hipEventSynchronize(s->text_ev[b]));     // pinned + device buffer b are free again
-    memcpy(s->text_pinned[b], src, piece);
-    const int rc = mgc::bam_submit(s, s->text_pinned[b], piece);
-    if (rc == mgc::BAM_REFUSED) return mgc::bam_refuse(s, "mgc_push_bam");
-    if (rc != MGC_OK) return rc;
-    src += piece;
-    len -= piece;
-  }
-  return MGC_OK;
-}
-
-int mgc::bam_end(mgc_session *s, const char *what) {
-  if (!s->text_open || s->text_format != mgc_session::TEXT_BAM) { set_err(&s->err, "mgc_end_bam without mgc_begin_bam"); return MGC_ESTATE; }
-  HIP_TRY(s, hipSetDevice(s->device));
-  if (!s->bam_walker.finish()) return mgc::bam_refuse(s, what);
-  s->text_open = false;
-  if (s->fill_len >= s->batch_limit) return cut_batch(s);
-  return MGC_OK;
-}
-
-extern "C" int mgc_end_bam(mgc_session *s) { return s ? mgc::bam_end(s, "mgc_end_bam") : MGC_EINVAL; }
-
-extern "C" int mgc_dev_bam_decode(const uint8_t *d_piece, uint64_t piece_bytes, const void *d_segments, uint64_t n_segments, uint64_t out_bytes,
-                                  uint8_t *d_out, void *stream) {
-  if ((!d_piece && piece_bytes) || (!d_segments && n_segments) || (!d_out && out_bytes)) return MGC_EINVAL;
-  if (piece_bytes > 0xffffffffull) { set_err(nullptr, "mgc_dev_bam_decode: a piece holds less than 4 GiB"); return MGC_EINVAL; }
-  HIP_TRY((mgc_session *)nullptr, mgc::launch_bam_decode(d_piece, piece_bytes, d_segments, n_segments, out_bytes, d_out, static_cast<hipStream_t>(stream)));
-  return MGC_OK;
-}
-
-// ---- gzip input, inflated by several host threads, resolved on the device (mgc_gzip_par.hpp, mgc_gzip.hip) ----------------------
-// The open gzip file IS an open text file (mgc_begin_text): its pieces go through the same device input buffers, upload stream and
-// parse kernels as text_submit's.  Before the parse kernels read a piece, its unresolved prefix is patched from the window the device
-// keeps of the text before it; the CRC-32 of the resolved text comes back two pieces later (or at gzip_finish) and is held against the
-// members' trailers then.
-static uint32_t *gz_error_word(mgc_session *s) { return reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(s->buf[mgc_session::B_GZ_WIN].p) + 2 * mgc::GZ_WINDOW); }
-
-int mgc::gzip_begin(mgc_session *s) {
-  HIP_TRY(s, s->ensure(mgc_session::B_GZ_WIN, 2 * mgc::GZ_WINDOW + 256));
-  HIP_TRY(s, hipMemsetAsync(s->buf[mgc_session::B_GZ_WIN].p, 0, 2 * mgc::GZ_WINDOW + 256, s->st_in));
-  s->gz_win = 0;
-  s->tr_gz_copy = s->tr_gz_collect = s->tr_gz_wait = 0;
-  s->gz_crc = 0; s->gz_member_len = 0; s->gz_members = 0;
-  s->gz_verdict.clear();
-  for (int b = 0; b < 2; b++) { s->gz_pending[b].clear(); s->gz_ends[b].clear(); }
-  return MGC_OK;
-}
-
-// crc32_combine(crc1, crc2, 4096) without zlib's work: zlib squares a 32 x 32 GF(2) matrix some fifteen times per call (tens of
-// microseconds in zlib 1.2), and a 32 MiB piece brings 8192 values.  Nearly every CRC piece is exactly 4096 bytes, so the operator
-// "append 4096 zero bytes" is built once -- the one-zero-bit operator squared fifteen times -- and applied in at most 32 steps.
-static uint32_t gf2_times(const uint32_t *mat, uint32_t vec) {
-  uint32_t sum = 0;
-  for (; vec; vec >>= 1, mat++) if (vec & 1u) sum ^= *mat;
-  return sum;
-}
-static uint32_t crc32_combine_4096(uint32_t crc1, uint32_t crc2) {
-  static const struct Op {
-    uint32_t m[32];
-    Op() {
-      uint32_t a[32], b[32];
-      a[0] = 0xedb88320u;                                    // one zero bit
-      for (int n = 1; n < 32; n++) a[n] = 1u << (n - 1);
-      for (int sq = 0; sq < 15; sq++) {                      // 2^15 bits = 4096 bytes
-        for (int n = 0; n < 32; n++) b[n] = gf2_times(a, a[n]);
-        memcpy(a, b, sizeof(a));
-      }
-      memcpy(m, a, sizeof(m));
-    }
-  } op;
-  return gf2_times(op.m, crc1) ^ crc2;
-}
-
-// the CRC values of the piece that went through buffer b have arrived (its text_ev was waited for): fold them into the member's
-static void gz_collect(mgc_session *s, uint32_t b) {
-  std::vector<mgc_session::GzCrcPiece> &pend = s->gz_pending[b];
-  if (pend.empty()) return;
-  const double t0 = mgc::now_s();
-  const size_t cap = s->gz_tab_cap[b];
-  const uint32_t *crc = reinterpret_cast<const uint32_t *>(s->gz_tab_pinned[b] + 12 * cap);
-  const uint32_t dev_err = crc[cap];
-  if (dev_err && s->gz_verdict.empty()) {
-    char msg[200];
-    snprintf(msg, sizeof(msg), "%s (in the piece that starts at compressed offset %llu)",
-             (dev_err & 2u) ? "a back-reference reaches before the start of its gzip member" : "the inflaters produced an invalid symbol",
-             (unsigned long long)s->gz_piece_off[b]);
-    s->gz_verdict = msg;
-  }
-  for (size_t i = 0; i < pend.size(); i++) {
-    s->gz_crc = pend[i].len == 4096 ? crc32_combine_4096(s->gz_crc, crc[i]) : (uint32_t)crc32_combine(s->gz_crc, crc[i], (z_off_t)pend[i].len);
-    s->gz_member_len += pend[i].len;
-    if (pend[i].end < 0) continue;
-    const mgc_session::GzEnd &e = s->gz_ends[b][(size_t)pend[i].end];
-    if (s->gz_verdict.empty() && (s->gz_crc != e.crc || (uint32_t)s->gz_member_len != e.isize)) {
-      char msg[200];
-      if (s->gz_crc != e.crc) snprintf(msg, sizeof(msg), "CRC32 mismatch (member %llu, trailer at compressed offset %llu: %08x, text %08x)",
-                                       (unsigned long long)s->gz_members, (unsigned long long)e.comp_off, e.crc, s->gz_crc);
-      else snprintf(msg, sizeof(msg), "ISIZE mismatch (member %llu, trailer at compressed offset %llu: %u, text %llu bytes)",
-                    (unsigned long long)s->gz_members, (unsigned long long)e.comp_off, e.isize, (unsigned long long)s->gz_member_len);
-      s->gz_verdict = msg;
-    }
-    s->gz_crc = 0; s->gz_member_len = 0; s->gz_members++;
-  }
-  pend.clear();
-  s->gz_ends[b].clear();
-  s->tr_gz_collect += mgc::now_s() - t0;
-}
-
-int mgc::gzip_finish(mgc_session *s) {
-  const double t0 = mgc::now_s();
-  mgc::text_drain(s);
-  s->tr_gz_wait += mgc::now_s() - t0;
-  const uint32_t older = s->text_next & 1u;
-  gz_collect(s, older);
-  gz_collect(s, older ^ 1u);
-  return s->gz_verdict.empty() ? MGC_OK : mgc::GZIP_REFUSED;
-}
-
-int mgc::gzip_submit(mgc_session *s, const char *pinned_text, size_t piece, const uint16_t *symbols, size_t n_symbols, uint32_t window_valid,
-                     const mgc::GzMemberEnd *ends, size_t n_ends, uint64_t comp_off) {
-  if (piece == 0) {
-    // Nothing for the device (an empty member, the end of the file).  A submit that queues nothing would break the count by which the
-    // pump hands slots back (see bam_submit): it waits for both pieces in flight, and the trailers are checked here.
-    if (mgc::gzip_finish(s) != MGC_OK) return mgc::GZIP_REFUSED;
-    for (size_t i = 0; i < n_ends; i++) {
-      if (s->gz_verdict.empty() && (s->gz_crc != ends[i].crc || (uint32_t)s->gz_member_len != ends[i].isize)) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "CRC32 / ISIZE mismatch (member %llu, trailer at compressed offset %llu)", (unsigned long long)s->gz_members,
-                 (unsigned long long)ends[i].comp_off);
-        s->gz_verdict = msg;
-      }
-      s->gz_crc = 0; s->gz_member_len = 0; s->gz_members++;
-    }
-    return s->gz_verdict.empty() ? MGC_OK : mgc::GZIP_REFUSED;
-  }
-  if (piece > mgc_session::TEXT_CHUNK || n_symbols > piece || window_valid > mgc::GZ_WINDOW) { set_err(&s->err, "gzip_submit: a piece out of bounds"); return MGC_EINVAL; }
-  const uint32_t b = s->text_next & 1u;
-  const double w0 = mgc::now_s();
-  if (s->text_ev_used[b]) HIP_TRY(s, hipEventSynchronize(s->text_ev[b]));       // device buffers b (and their previous sources) are free again
-  s->tr_gz_wait += mgc::now_s() - w0;
-  gz_collect(s, b);
-  if (!s->gz_verdict.empty()) return mgc::GZIP_REFUSED;
-  s->gz_piece_off[b] = comp_off;
-  HIP_TRY(s, s->ensure_preserve(stage_id(s->fill), s->fill_len + piece + 4096, s->fill_len, s->st_in));
-  // the CRC table: pieces of at most 4 KiB that never cross a member's end
-  std::vector<mgc_session::GzCrcPiece> &pend = s->gz_pending[b];
-  const size_t want_tab = piece / 4096 + 2 * n_ends + 2;
-  if (s->gz_tab_cap[b] < want_tab) {
-    if (s->gz_tab_pinned[b]) { (void)hipHostFree(s->gz_tab_pinned[b]); s->gz_tab_pinned[b] = nullptr; s->gz_tab_cap[b] = 0; }
-    const size_t cap = want_tab + want_tab / 2 + 1024;
-    HIP_TRY(s, hipHostMalloc(reinterpret_cast<void **>(&s->gz_tab_pinned[b]), cap * 16 + 16, hipHostMallocDefault));
-    s->gz_tab_cap[b] = cap;
-  }
-  const size_t cap = s->gz_tab_cap[b];
-  const int tab_buf = b ? mgc_session::B_GZ_TAB1 : mgc_session::B_GZ_TAB0, sym_buf = b ? mgc_session::B_GZ_SYM1 : mgc_session::B_GZ_SYM0;
-  HIP_TRY(s, s->ensure(tab_buf, cap * 16 + 16));
-  uint64_t *h_begin = reinterpret_cast<uint64_t *>(s->gz_tab_pinned[b]);
-  uint32_t *h_len = reinterpret_cast<uint32_t *>(s->gz_tab_pinned[b] + 8 * cap);
-  size_t n_tab = 0;
-  uint64_t at = 0;
-  for (size_t e = 0; e <= n_ends; e++) {
-    const uint64_t stop = e < n_ends ? ends[e].text_off : piece;
-    if (stop < at || stop > piece) { set_err(&s->err, "gzip_submit: member ends out of order"); return MGC_EINVAL; }
-    do {                                                                         // (a member end with no text before it: one piece of 0 bytes)
-      const uint32_t l = (uint32_t)std::min<uint64_t>(4096, stop - at);
-      if (e == n_ends && l == 0) break;
-      h_begin[n_tab] = at; h_len[n_tab] = l;
-      at += l;
-      pend.push_back({l, (e < n_ends && at == stop) ? (int32_t)s->gz_ends[b].size() : -1});
-      n_tab++;
-    } while (at < stop);
-    if (e < n_ends) s->gz_ends[b].push_back({ends[e].crc, ends[e].isize, ends[e].comp_off});
-  }
-  if (n_symbols * 2 > s->gz_sym_cap[b]) {
-    if (s->gz_sym_pinned[b]) { (void)hipHostFree(s->gz_sym_pinned[b]); s->gz_sym_pinned[b] = nullptr; s->gz_sym_cap[b] = 0; }
-    const size_t want = std::min<size_t>(2 * mgc_session::TEXT_CHUNK, n_symbols * 3 + (1u << 20));
-    HIP_TRY(s, hipHostMalloc(reinterpret_cast<void **>(&s->gz_sym_pinned[b]), want, hipHostMallocDefault));
-    s->gz_sym_cap[b] = want;
-  }
-  HIP_TRY(s, s->ensure(sym_buf, std::max<size_t>(s->gz_sym_cap[b], 256)));
-  const double c0 = mgc::now_s();
-  if (n_symbols) memcpy(s->gz_sym_pinned[b], symbols, n_symbols * 2);
-  s->tr_gz_copy += mgc::now_s() - c0;
-  uint8_t *d_in = reinterpret_cast<uint8_t *>(s->buf[b ? mgc_session::B_TEXT_IN1 : mgc_session::B_TEXT_IN0].p);
-  uint8_t *d_tab = static_cast<uint8_t *>(s->buf[tab_buf].p);
-  uint8_t *d_win = static_cast<uint8_t *>(s->buf[mgc_session::B_GZ_WIN].p);
-  HIP_TRY(s, hipMemcpyAsync(d_in, pinned_text, piece, hipMemcpyHostToDevice, s->st_up));
-  if (n_symbols) HIP_TRY(s, hipMemcpyAsync(s->buf[sym_buf].p, s->gz_sym_pinned[b], n_symbols * 2, hipMemcpyHostToDevice, s->st_up));
-  HIP_TRY(s, hipMemcpyAsync(d_tab, h_begin, n_tab * 8, hipMemcpyHostToDevice, s->st_up));
-  HIP_TRY(s, hipMemcpyAsync(d_tab + 8 * cap, h_len, n_tab * 4, hipMemcpyHostToDevice, s->st_up));
-  HIP_TRY(s, hipEventRecord(s->up_ev[b], s->st_up));
-  HIP_TRY(s, hipStreamWaitEvent(s->st_in, s->up_ev[b], 0));
-  HIP_TRY(s, mgc::launch_gzip_resolve(d_in, piece, static_cast<const uint16_t *>(s->buf[sym_buf].p), n_symbols, d_win + (size_t)s->gz_win * mgc::GZ_WINDOW,
-                                      window_valid, d_win + (size_t)(s->gz_win ^ 1) * mgc::GZ_WINDOW, gz_error_word(s), s->st_in));
-  s->gz_win ^= 1;
-  HIP_TRY(s, mgc::launch_gzip_crc32(d_in, reinterpret_cast<const uint64_t *>(d_tab), reinterpret_cast<const uint32_t *>(d_tab + 8 * cap), n_tab,
-                                    reinterpret_cast<uint32_t *>(d_tab + 12 * cap), s->st_in));
-  HIP_TRY(s, hipMemcpyAsync(s->gz_tab_pinned[b] + 12 * cap, d_tab + 12 * cap, n_tab * 4, hipMemcpyDeviceToHost, s->st_in));
-  HIP_TRY(s, hipMemcpyAsync(s->gz_tab_pinned[b] + 16 * cap, gz_error_word(s), 4, hipMemcpyDeviceToHost, s->st_in));
-  HIP_TRY(s, mgc::launch_text_parse(d_in, piece, s->text_format == MGC_TEXT_FASTQ, s->buf[mgc_session::B_TEXT_STATE].p,
-                                    s->buf[mgc_session::B_TEXT_WS].p, stage_ptr(s, s->fill), s->st_in));
-  HIP_TRY(s, hipEventRecord(s->text_ev[b], s->st_in));
-  s->text_ev_used[b] = true;
-  s->text_next++;
-  s->fill_len += piece;                                     // an upper bound, as in text_submit
-  s->len_inexact = true;
-  if (s->fill_len >= s->batch_limit) return cut_batch(s);
-  return MGC_OK;
-}
-
-int mgc::gzip_refuse(mgc_session *s, const char *what, const char *why) {
-  const std::string w = why;                                // (why may point into the session's own strings)
-  mgc::text_drain(s);
-  for (int b = 0; b < 2; b++) { s->gz_pending[b].clear(); s->gz_ends[b].clear(); }
-  const int rc = mgc::text_rollback(s);
-  if (rc == MGC_EINVAL) set_err(&s->err, "'%s': %s, after part of the file was counted (input larger than one batch)", what, w.c_str());
-  if (rc != MGC_OK) return rc;
-  set_err(&s->err, "'%s': %s", what, w.c_str());
-  return MGC_EFORMAT;
-}
-
-extern "C" int mgc_dev_gzip_resolve(uint8_t *d_text, uint64_t text_bytes, const uint16_t *d_symbols, uint64_t n_symbols, const uint8_t *d_window_in,
-                                    uint32_t window_valid, uint8_t *d_window_out, uint32_t *d_error, void *stream) {
-  if ((!d_text && text_bytes) || (!d_symbols && n_symbols) || (n_symbols && !d_error) || n_symbols > text_bytes || window_valid > mgc::GZ_WINDOW ||
-      (!d_window_in && window_valid) || (d_window_out && d_window_out == d_window_in)) {
-    set_err(nullptr, "mgc_dev_gzip_resolve: n_symbols <= text_bytes, window_valid <= 32768 (0 without a window), two different windows");
-    return MGC_EINVAL;
-  }
-  HIP_TRY((mgc_session *)nullptr, mgc::launch_gzip_resolve(d_text, text_bytes, d_symbols, n_symbols, d_window_in, window_valid, d_window_out, d_error,
-                                                           static_cast<hipStream_t>(stream)));
-  return MGC_OK;
-}
-
-extern "C" int mgc_dev_crc32_pieces(const uint8_t *d_text, const uint64_t *d_begin, const uint32_t *d_len, uint64_t n_pieces, uint32_t *d_crc, void *stream) {
-  if (n_pieces && (!d_text || !d_begin || !d_len || !d_crc)) return MGC_EINVAL;
-  HIP_TRY((mgc_session *)nullptr, mgc::launch_gzip_crc32(d_text, d_begin, d_len, n_pieces, d_crc, static_cast<hipStream_t>(stream)));
-  return MGC_OK;
-}
-
-extern "C" int mgc_push_bases_device(mgc_session *s, const uint8_t *d_bases, uint64_t n_bases) {
-  if (!s || (!d_bases && n_bases)) return MGC_EINVAL;
-  if (s->borrowed || s->input_seen || s->counted) { set_err(&s->err, "device input must be the only input"); return MGC_ESTATE; }
-  s->d_bases = d_bases;
-  s->n_bases = n_bases;
-  s->borrowed = true;
-  return MGC_OK;
+  delete s;                                                  // (the input ring frees its own: mgc_input.hpp)
 }
 
 extern "C" int mgc_set_profiling(mgc_session *s, int enable) {
@@ -1419,8 +802,8 @@ static int park_batch_result(mgc_session *s) {
 }
 
 // one batch: stage[which][0, n) -> count -> park.  Runs on the worker thread while the caller stages the next batch.
-static int count_staged_batch(mgc_session *s, int which, uint64_t n) {
-  s->d_bases = stage_ptr(s, which);
+int mgc::count_staged_batch(mgc_session *s, int which, uint64_t n) {
+  s->d_bases = mgc::stage_ptr(s, which);
   s->n_bases = n;
   int rc = mgc::count_device(s);
   if (rc != MGC_OK) return rc;
@@ -1485,20 +868,15 @@ extern "C" int mgc_count(mgc_session *s) {
   }
   if (s->counted) return MGC_OK;                             // nothing can have been pushed since: the result stands
   if (s->text_open) { set_err(&s->err, "mgc_count: a text file is still open (mgc_end_text)"); return MGC_ESTATE; }
-  int rc = MGC_OK;
-  if (!s->state_ready) { rc = input_setup(s); if (rc != MGC_OK) return rc; }     // nothing was pushed: an empty stream
-  rc = flush_pinned(s);
-  if (rc == MGC_OK) rc = resolve_length(s);
-  const int wrc = join_worker(s);
-  if (rc == MGC_OK) rc = wrc;
+  int rc = mgc::settle_input(s);
   if (rc != MGC_OK) return rc;
   if (!s->have_r) {                                          // everything fits in one pass
-    s->d_bases = stage_ptr(s, s->fill);
+    s->d_bases = mgc::stage_ptr(s, s->fill);
     s->n_bases = s->fill_len;
     rc = mgc::count_device(s);
     s->prof.n_batches = 1;
   } else {
-    if (s->fill_len) rc = count_staged_batch(s, s->fill, s->fill_len);
+    if (s->fill_len) rc = mgc::count_staged_batch(s, s->fill, s->fill_len);
     if (rc == MGC_OK) rc = finalize_from_runs(s);
   }
   if (rc == MGC_OK) s->counted = true;
@@ -1516,15 +894,10 @@ extern "C" int mgc_staged_bases(mgc_session *s, const uint8_t **d_bases, uint64_
   if (s->borrowed) { *d_bases = s->d_bases; *n_bases = s->n_bases; return MGC_OK; }
   if (s->text_open) { set_err(&s->err, "mgc_staged_bases: a text file is still open (mgc_end_text)"); return MGC_ESTATE; }
   if (s->counted || s->have_r || s->n_batches) { set_err(&s->err, "mgc_staged_bases: part of the input has already been counted"); return MGC_ESTATE; }
-  int rc = MGC_OK;
-  if (!s->state_ready) { rc = input_setup(s); if (rc != MGC_OK) return rc; }
-  rc = flush_pinned(s);
-  if (rc == MGC_OK) rc = resolve_length(s);
-  const int wrc = join_worker(s);
-  if (rc == MGC_OK) rc = wrc;
+  const int rc = mgc::settle_input(s);
   if (rc != MGC_OK) return rc;
   HIP_TRY(s, hipStreamSynchronize(s->st_in));
-  *d_bases = stage_ptr(s, s->fill);
+  *d_bases = mgc::stage_ptr(s, s->fill);
   *n_bases = s->fill_len;
   return MGC_OK;
 }

@@ -1,7 +1,7 @@
 // mgc_bam_walk.hpp -- a resumable walker over the records of an (inflated) BAM byte stream (SAMv1 4.2): it is fed the stream in
 // pieces of any size and turns the packed SEQ field of every record into SEGMENTS, the table the device decoder
 // (mgc_bam.hip) expands into the base stream: SEQ as stored, '.' after every record, no FLAG filtering.  Host-only, no HIP,
-// no zlib; the session (mgc_api.cpp), the whole-file reader (mgc_textfile.cpp) and tests/host/bam_walk_host.cpp use it.
+// no zlib; the session (mgc_input.cpp), the whole-file reader (mgc_textfile.cpp) and tests/host/bam_walk_host.cpp use it.
 //
 // What holds for the segments of a piece of n bytes:
 //   - src_off + (n_bases + 1) / 2 <= n: no segment refers to a byte outside its piece;

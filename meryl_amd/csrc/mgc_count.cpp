@@ -428,7 +428,7 @@ int Count::histogram() {
     // read of every file goes away.
     // The packed base stream (MGC_PACKED_BASES=0: off): the histogram kernel stores the 2-bit codes and invalid-base masks it has to
     // make anyway, and the partition stages its tiles from them instead of decoding the ASCII bases a second time.  Only where the
-    // arena can grow by it beside what the count itself is budgeted at (2 + 14 bytes per key word and base, mgc_api.cpp: input_setup);
+    // arena can grow by it beside what the count itself is budgeted at (2 + 14 bytes per key word and base, mgc_input.cpp: input_setup);
     // a count that cannot have it runs as before.
     if (sw.packed_bases && n_bases) {
       const size_t pb = mgc::kp_packed_bytes(n_bases);

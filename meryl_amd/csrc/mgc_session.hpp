@@ -1,5 +1,5 @@
 // mgc_session.hpp -- the session object behind include/meryl_gpu_count.h and the helpers its translation units
-// (mgc_api.cpp: input + batches; mgc_textfile.cpp: whole-file readers; mgc_count.cpp: counting; mgc_stream.cpp: delivery of the result,
+// (mgc_api.cpp: configuration, open / close, count, results; mgc_input.cpp: input staging + batches; mgc_textfile.cpp: whole-file readers; mgc_count.cpp: counting; mgc_stream.cpp: delivery of the result,
 // database streaming; mgc_eval.cpp: operations over databases) share.  The owning device buffer they use, mgc::DBuf, is mgc_devbuf.hpp's;
 // the session's arena below is a different thing (grow-only for the session's life, traced by MGC_IO_TRACE).  Internal.
 #pragma once
@@ -9,6 +9,8 @@
 #include "mgc_clock.hpp"
 #include "mgc_devbuf.hpp"
 #include "mgc_device.h"
+#include "mgc_gzip_crc.hpp"
+#include "mgc_input.hpp"
 
 #include <cstdarg>
 #include <cstdio>
@@ -149,40 +151,21 @@ struct mgc_session {
   uint64_t    fill_len = 0;
   bool        len_inexact = false;
   bool        input_seen = false;
-  // text
+  // the open file: text (mgc_begin_text; a plain gzip file is one) or BAM (mgc_begin_bam; format TEXT_BAM) -- one "open file" state for
+  // both: the cut inside a file, the rollback point in the device's parse state
   bool        text_open = false, text_cut_in_file = false;
   int         text_format = 0;
-  char       *text_pinned[2] = {nullptr, nullptr};
-  hipEvent_t  text_ev[2] = {nullptr, nullptr};
-  hipStream_t st_up = nullptr;           // text chunks are UPLOADED here while the previous chunk is parsed on st_in
-  hipEvent_t  up_ev[2] = {nullptr, nullptr};
-  bool        text_ev_used[2] = {false, false};
-  uint32_t    text_next = 0;
-  static constexpr int TEXT_RING_MAX = 64;
-  char       *text_ring[TEXT_RING_MAX] = {nullptr};      // the whole-file readers' pinned slots (mgc_textfile.cpp; allocated on first use)
-  // BAM (mgc_begin_bam ...): the open file is a text file of format TEXT_BAM -- one "open file" state for both -- whose pieces are
-  // inflated BAM bytes: walked on the host, decoded on the device (mgc_bam.hip) from a segment table that travels with the piece
   static constexpr int TEXT_BAM = 3;
+  static constexpr int TEXT_RING_MAX = mgc::InputRing::FILE_SLOTS_MAX;
+  mgc::InputRing in;                                      // the two piece slots every route's pieces go through (mgc_input.hpp)
+  // BAM: pieces are inflated BAM bytes, walked on the host, decoded on the device (mgc_bam.hip) from a segment table that travels with the piece
   mgc::BamWalker bam_walker;
   std::vector<mgc::BamSegment> bam_segs;                 // of the piece being walked
-  mgc::BamSegment *bam_seg_pinned[2] = {nullptr, nullptr};   // pinned, grow-only, one per device input buffer
-  size_t      bam_seg_cap[2] = {0, 0};                   // segments
   double      tr_bam_walk = 0;                           // seconds in the walker, this file (MGC_IO_TRACE)
-  // gzip (mgc_push_text_gzip_file): the open file is a text file whose pieces come with the symbols of an unresolved prefix; they are
-  // resolved on the device before the parse kernels read them, and the CRC-32 of every member is computed there over the resolved text
-  struct GzCrcPiece { uint32_t len; int32_t end; };       // one entry of a piece's CRC table; end >= 0: a member ends after it (gz_ends[b][end])
-  struct GzEnd { uint32_t crc, isize; uint64_t comp_off; };
+  // gzip (mgc_push_text_gzip_file): pieces come with the symbols of an unresolved prefix; they are resolved on the device before the
+  // parse kernels read them, and the CRC-32 of every member is computed there over the resolved text and held against its trailer here
   int         gz_win = 0;                                 // which of the two windows holds the text before the next piece
-  char       *gz_sym_pinned[2] = {nullptr, nullptr};      // pinned, grow-only, one per device input buffer
-  size_t      gz_sym_cap[2] = {0, 0};                     // bytes
-  char       *gz_tab_pinned[2] = {nullptr, nullptr};      // {begin[cap], len[cap], crc[cap], error}: up, up, down, down
-  size_t      gz_tab_cap[2] = {0, 0};                     // entries
-  std::vector<GzCrcPiece> gz_pending[2];                  // what the results in gz_tab_pinned[b] will mean
-  std::vector<GzEnd> gz_ends[2];
-  uint32_t    gz_crc = 0;                                 // of the current member, over the pieces collected so far
-  uint64_t    gz_member_len = 0, gz_members = 0;
-  std::string gz_verdict;                                 // non-empty: the stream is refused
-  uint64_t    gz_piece_off[2] = {0, 0};                   // where in the file the piece in buffer b starts (for the verdict)
+  mgc::GzCrcLedger gz;                                    // (mgc_gzip_crc.hpp)
   double      tr_gz_copy = 0, tr_gz_collect = 0, tr_gz_wait = 0;   // seconds of this file's submits in the symbol copy, in folding the CRCs, waiting for the device (MGC_IO_TRACE)
   // host-pushed bases: two pinned chunks, the upload of one overlaps the filling of the other
   char       *pin[2] = {nullptr, nullptr};
@@ -243,37 +226,46 @@ struct CountInput {
 // (mgc_count.cpp).  The caller marks the session counted.
 int count_device(mgc_session *s, const CountInput &in = CountInput());
 
-// What the whole-file readers (mgc_textfile.cpp) use of the open text file besides mgc_begin_text / mgc_end_text (mgc_api.cpp):
-// one piece (<= TEXT_CHUNK bytes, in pinned memory) -> device input buffer -> parse kernels; returns once they are queued
+// ---- input staging (mgc_input.cpp) --------------------------------------------------------------------------------------------
+inline int stage_id(int which) { return which ? mgc_session::B_STAGE1 : mgc_session::B_STAGE0; }
+inline uint8_t *stage_ptr(mgc_session *s, int which) { return reinterpret_cast<uint8_t *>(s->buf[stage_id(which)].p); }
+// Everything pushed so far is in stage[fill], its exact length in fill_len, and no batch is being counted: an empty stream is set up if
+// nothing was pushed, the pinned chunk of host-pushed bases is flushed, the length is read back, the worker thread is joined.
+int settle_input(mgc_session *s);
+// one batch: stage[which][0, n) -> count -> park (mgc_api.cpp; cut_batch runs it on the worker thread)
+int count_staged_batch(mgc_session *s, int which, uint64_t n);
+
+// What the whole-file readers (mgc_textfile.cpp) use of the open file besides mgc_begin_text / mgc_end_text / mgc_begin_bam.  Each
+// submit takes one piece (<= TEXT_CHUNK bytes, in pinned memory) and returns once its upload and kernels are queued.
 int text_submit(mgc_session *s, const char *pinned_src, size_t piece);
-// waits until the last two pieces submitted have been read from their pinned sources
+// Waits for both pieces in flight: after a file's last piece (the uploads still read from their pinned sources), and FOR a piece that
+// queues nothing (see mgc_input.cpp).
 void text_drain(mgc_session *s);
 // closes the open file and takes it back out of the stream; MGC_EINVAL when part of it was already counted
 int text_rollback(mgc_session *s);
-// The open BAM file (mgc_begin_bam): one piece of its inflated bytes (<= TEXT_CHUNK, in pinned memory) walked on the host,
-// uploaded with its segment table and decoded into the stream; returns once that is queued.  BAM_REFUSED (> 0): the walker
-// refuses the stream (s->bam_walker.error()); nothing of the piece was queued, the file is still open (bam_refuse closes it).
+// text_rollback and the session's error: MGC_EFORMAT with "'what': why" + format_tail, or MGC_EINVAL with "'what': why" + joint +
+// "after part of the file was counted (input larger than one batch)" when it cannot be taken back
+int refuse_file(mgc_session *s, const char *what, const std::string &why, const char *joint = ", ", const char *format_tail = "");
+// The open BAM file: the piece is walked on the host, uploaded with its segment table and decoded into the stream.  BAM_REFUSED (> 0):
+// the walker refuses the stream (s->bam_walker.error()); nothing of the piece was queued, the file is still open (bam_refuse closes it).
 constexpr int BAM_REFUSED = 1;
 int bam_submit(mgc_session *s, const char *pinned_src, size_t piece);
-// closes the refused BAM file and rolls it back: MGC_EFORMAT with "'what': the walker's words" as the session's error, or
-// MGC_EINVAL when part of the file was already counted
+// refuse_file with the walker's words
 int bam_refuse(mgc_session *s, const char *what);
-// The open text file as a gzip stream (gzip_begin after mgc_begin_text): one piece of its text (<= TEXT_CHUNK, in pinned memory) whose
-// first n_symbols bytes are unresolved -- `symbols` holds them (mgc_gzip_par.hpp) -- window_valid bytes of its gzip member before it, and
-// the members that end inside it.  Uploads text and symbols, queues resolve -> window -> CRC and the parse kernels; returns once that is
-// queued.  GZIP_REFUSED (> 0): a CRC32 / ISIZE of an earlier piece did not match its trailer or the device met an unresolvable symbol
-// (s->gz_verdict); the file is still open (gzip_refuse closes it).
-struct GzMemberEnd;
+// mgc_end_bam with the name the refusal of a stream that ends inside the header or a record is reported under
+int bam_end(mgc_session *s, const char *what);
+// The open text file as a gzip stream (gzip_begin after mgc_begin_text): a piece of its text whose first n_symbols bytes are unresolved
+// -- `symbols` holds them (mgc_gzip_par.hpp) -- window_valid bytes of its gzip member before it, and the members that end inside it.
+// Uploads text, symbols and CRC table, queues resolve -> window -> CRC and the parse kernels.  GZIP_REFUSED (> 0): a CRC32 / ISIZE of
+// an earlier piece did not match its trailer or the device met an unresolvable symbol (s->gz.verdict); the file is still open
+// (gzip_refuse closes it).
 constexpr int GZIP_REFUSED = 1;
 int gzip_begin(mgc_session *s);
 int gzip_submit(mgc_session *s, const char *pinned_text, size_t piece, const uint16_t *symbols, size_t n_symbols, uint32_t window_valid,
                 const GzMemberEnd *ends, size_t n_ends, uint64_t comp_off);
 // waits for the pieces in flight and checks what they brought back; GZIP_REFUSED as above
 int gzip_finish(mgc_session *s);
-// closes the refused file and rolls it back: MGC_EFORMAT with "'what': why" as the session's error, or MGC_EINVAL when part of the file
-// was already counted
+// refuse_file once the pieces in flight are done and forgotten
 int gzip_refuse(mgc_session *s, const char *what, const char *why);
-// mgc_end_bam with the name the refusal of a stream that ends inside the header or a record is reported under
-int bam_end(mgc_session *s, const char *what);
 }  // namespace mgc
 

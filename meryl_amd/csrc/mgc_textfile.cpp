@@ -2,8 +2,8 @@
 // with pread, BGZF files inflated, by several threads STRAIGHT into a ring of pinned buffers (mgc_chunk_ring.hpp) that the
 // calling thread uploads and parses in file order; BGZF BAM files likewise, walked and decoded instead of parsed; plain gzip files
 // through the pump of mgc_gzip_par.hpp, whose pieces the device resolves (mgc_gzip.hip).  The session is reached through mgc_begin_text /
-// mgc_end_text / mgc_begin_bam / mgc_end_bam and text_submit / bam_submit / gzip_submit / text_drain / text_rollback / bam_refuse /
-// gzip_refuse (mgc_session.hpp) only.
+// mgc_end_text / mgc_begin_bam and what mgc_session.hpp declares of mgc_input.cpp (text_submit / bam_submit / gzip_submit, text_drain,
+// text_rollback, refuse_file and its BAM / gzip forms, bam_end, the ring's pinned file slots, the gzip ledger's verdict) only.
 #include "../../include/meryl_gpu_count.h"
 #include "mgc_bgzf.hpp"
 #include "mgc_chunk_ring.hpp"
@@ -53,14 +53,10 @@ int sniff_text_format(int fd, char *first) {
 
 // The ring of a session: its pinned slots are allocated by the producers themselves, in parallel, on first use, and stay
 // with the session for the next file (mgc_close frees them).  lag 2: see run_chunk_ring.
+inline auto slot_alloc(mgc_session *s) { return [s]() { return mgc::InputRing::alloc_file_slot(s->device, mgc_session::TEXT_CHUNK); }; }
 template <class Fill, class Consume>
 mgc::ChunkRingResult run_session_ring(mgc_session *s, uint64_t n_chunks, const mgc::ChunkRingGeometry &g, Fill fill, Consume consume) {
-  auto alloc = [s]() -> char * {
-    char *p = nullptr;
-    (void)hipSetDevice(s->device);
-    return hipHostMalloc(reinterpret_cast<void **>(&p), mgc_session::TEXT_CHUNK, hipHostMallocDefault) == hipSuccess ? p : nullptr;
-  };
-  return mgc::run_chunk_ring(n_chunks, s->text_ring, g.slots, g.threads, 2, alloc, fill, consume);
+  return mgc::run_chunk_ring(n_chunks, s->in.file_slots, g.slots, g.threads, 2, slot_alloc(s), fill, consume);
 }
 }  // namespace
 
@@ -179,73 +175,97 @@ extern "C" int mgc_is_bgzf_file(const char *path) {
   return (got >= 18 && mgc::bgzf_parse_block(head, (size_t)got, &b) != mgc::BGZF_NOT_BLOCK) ? 1 : 0;
 }
 
-extern "C" int mgc_push_text_bgzf_file(mgc_session *s, const char *path, int format, int threads) {
-  if (!s || !path) return MGC_EINVAL;
+namespace {
+// A BGZF file for the chunk ring: mapped, its blocks planned into chunks of <= TEXT_CHUNK of text, one inflater per worker thread.
+struct BgzfFile {
+  int fd = -1;
+  const unsigned char *map = nullptr;
   uint64_t fsize = 0;
-  const int fd = open_regular(&s->err, "mgc_push_text_bgzf_file", path, "regular BGZF file", 28, &fsize);
-  if (fd < 0) return MGC_EINVAL;
-  const unsigned char *map = reinterpret_cast<const unsigned char *>(mmap(nullptr, fsize, PROT_READ, MAP_SHARED, fd, 0));
-  if (map == MAP_FAILED) { close(fd); set_err(&s->err, "mgc_push_text_bgzf_file: mmap of '%s' failed: %s", path, strerror(errno)); return MGC_EINVAL; }
+  mgc::BgzfPlan plan;
+  mgc::ChunkRingGeometry g;
   std::vector<z_stream> zs;                                     // one inflater per worker thread, n_z of them set up
   int n_z = 0;
-  auto release = [&]() { for (int t = 0; t < n_z; t++) inflateEnd(&zs[t]); munmap(const_cast<unsigned char *>(map), fsize); close(fd); };
-  const mgc::BgzfPlan plan = mgc::bgzf_plan_chunks(map, fsize, mgc_session::TEXT_CHUNK);
-  const std::vector<mgc::BgzfBlock> &blocks = plan.blocks;
-  if (plan.bad != mgc::BGZF_BLOCK) {
-    release();
-    if (plan.bad == mgc::BGZF_BAD_ISIZE) set_err(&s->err, "'%s': corrupt BGZF block at offset %zu (ISIZE %u)", path, (size_t)plan.bad_off, plan.bad_isize);
-    else set_err(&s->err, "'%s': not a BGZF block at offset %zu (plain gzip data, or a truncated file)", path, (size_t)plan.bad_off);
-    return MGC_EFORMAT;
+
+  // MGC_OK, or the code to return with the session's error set (`who`: the calling function's name)
+  int open(mgc_session *s, const char *who, const char *path, int threads) {
+    fd = open_regular(&s->err, who, path, "regular BGZF file", 28, &fsize);
+    if (fd < 0) return MGC_EINVAL;
+    void *m = mmap(nullptr, fsize, PROT_READ, MAP_SHARED, fd, 0);
+    if (m == MAP_FAILED) { set_err(&s->err, "%s: mmap of '%s' failed: %s", who, path, strerror(errno)); return MGC_EINVAL; }
+    map = static_cast<const unsigned char *>(m);
+    plan = mgc::bgzf_plan_chunks(map, fsize, mgc_session::TEXT_CHUNK);
+    if (plan.bad != mgc::BGZF_BLOCK) {
+      if (plan.bad == mgc::BGZF_BAD_ISIZE) set_err(&s->err, "'%s': corrupt BGZF block at offset %zu (ISIZE %u)", path, (size_t)plan.bad_off, plan.bad_isize);
+      else set_err(&s->err, "'%s': not a BGZF block at offset %zu (plain gzip data, or a truncated file)", path, (size_t)plan.bad_off);
+      return MGC_EFORMAT;
+    }
+    g = mgc::chunk_ring_geometry(threads, plan.chunks.size(), mgc_session::TEXT_RING_MAX);
+    zs.resize(g.threads);
+    while (n_z < g.threads && inflateInit2(&zs[n_z], -15) == Z_OK) n_z++;
+    if (n_z < g.threads) { set_err(&s->err, "zlib: inflateInit2 failed"); return MGC_ENOMEM; }
+    return MGC_OK;
   }
-  const uint64_t nchunks = plan.chunks.size();
-  const mgc::ChunkRingGeometry g = mgc::chunk_ring_geometry(threads, nchunks, mgc_session::TEXT_RING_MAX);
-  zs.resize(g.threads);
-  while (n_z < g.threads && inflateInit2(&zs[n_z], -15) == Z_OK) n_z++;
-  if (n_z < g.threads) { release(); set_err(&s->err, "zlib: inflateInit2 failed"); return MGC_ENOMEM; }
+  bool inflate_block(int t, size_t i, unsigned char *dst) { return mgc::bgzf_inflate_block(zs[t], map + plan.blocks[i].off, plan.blocks[i], dst); }
+  // the ring's fill: worker t inflates the blocks of chunk c into dst; -1 and the block's number when one does not inflate
+  int64_t fill(int t, uint64_t c, char *dst, int *bad_block) {
+    size_t at = 0;
+    for (size_t i = plan.chunks[c].first; i < plan.chunks[c].last; i++) {
+      if (!inflate_block(t, i, reinterpret_cast<unsigned char *>(dst) + at)) { *bad_block = (int)i; return -1; }
+      at += plan.blocks[i].isize;
+    }
+    return (int64_t)at;
+  }
+  // A block did not inflate: what the file has put into the stream is taken back (as for a file that stops being strict FASTQ), unless
+  // part of it already went into a counted batch
+  static int refuse_block(mgc_session *s, const char *path, int block) {
+    char why[80];
+    snprintf(why, sizeof(why), "BGZF block %llu failed to inflate", (unsigned long long)block);
+    return mgc::refuse_file(s, path, why, " ", " (corrupt file)");
+  }
+  BgzfFile() = default;
+  BgzfFile(const BgzfFile &) = delete;
+  BgzfFile &operator=(const BgzfFile &) = delete;
+  ~BgzfFile() {
+    for (int t = 0; t < n_z; t++) inflateEnd(&zs[t]);
+    if (map) munmap(const_cast<unsigned char *>(map), fsize);
+    if (fd >= 0) close(fd);
+  }
+};
+}  // namespace
+
+extern "C" int mgc_push_text_bgzf_file(mgc_session *s, const char *path, int format, int threads) {
+  if (!s || !path) return MGC_EINVAL;
+  BgzfFile f;
+  int rc = f.open(s, "mgc_push_text_bgzf_file", path, threads);
+  if (rc != MGC_OK) return rc;
+  const std::vector<mgc::BgzfBlock> &blocks = f.plan.blocks;
   if (format == 0) {                                            // sniff: the first byte of text that is not white space
     char c = 0;
     std::vector<unsigned char> tmp(65536);
     for (size_t i = 0; i < blocks.size() && !c; i++) {
-      if (!mgc::bgzf_inflate_block(zs[0], map + blocks[i].off, blocks[i], tmp.data())) { release(); set_err(&s->err, "'%s': BGZF block %zu failed to inflate (corrupt file)", path, i); return MGC_EFORMAT; }
+      if (!f.inflate_block(0, i, tmp.data())) { set_err(&s->err, "'%s': BGZF block %zu failed to inflate (corrupt file)", path, i); return MGC_EFORMAT; }
       c = first_text_byte(tmp.data(), blocks[i].isize);
     }
     format = format_of(c);
-    if (!format) { release(); set_err(&s->err, "'%s' is neither FASTA nor FASTQ (record starts with '%c')", path, c ? c : '?'); return MGC_EFORMAT; }
+    if (!format) { set_err(&s->err, "'%s' is neither FASTA nor FASTQ (record starts with '%c')", path, c ? c : '?'); return MGC_EFORMAT; }
   }
-  int rc = mgc_begin_text(s, format);
-  if (rc != MGC_OK) { release(); return rc; }
+  rc = mgc_begin_text(s, format);
+  if (rc != MGC_OK) return rc;
 
-  auto fill = [&](int t, uint64_t c, char *dst, int *bad_block) -> int64_t {
-    size_t at = 0;
-    for (size_t i = plan.chunks[c].first; i < plan.chunks[c].last; i++) {
-      if (!mgc::bgzf_inflate_block(zs[t], map + blocks[i].off, blocks[i], reinterpret_cast<unsigned char *>(dst) + at)) { *bad_block = (int)i; return -1; }
-      at += blocks[i].isize;
-    }
-    return (int64_t)at;
-  };
   uint64_t text_total = 0;
   auto consume = [&](uint64_t, const char *p, size_t len) {
     text_total += len;
     return len ? mgc::text_submit(s, p, len) : MGC_OK;          // (a chunk of empty blocks: the end-of-file marker)
   };
-  const mgc::ChunkRingResult res = run_session_ring(s, nchunks, g, fill, consume);
+  const uint64_t nchunks = f.plan.chunks.size();
+  const mgc::ChunkRingResult res = run_session_ring(s, nchunks, f.g, [&f](int t, uint64_t c, char *dst, int *bad) { return f.fill(t, c, dst, bad); }, consume);
   mgc::text_drain(s);                                           // the last uploads still read from the ring
-  release();
   if (getenv("MGC_IO_TRACE"))
     fprintf(stderr, "[io] BGZF file %.2f GB -> %.2f GB of text in %llu chunks (%zu blocks), %d inflaters, ring %d: waiting for the inflaters %.3f s, "
-                    "upload+parse submit (incl. waits for the device) %.3f s\n", fsize / 1e9, text_total / 1e9, (unsigned long long)nchunks, blocks.size(),
-            g.threads, g.slots, res.t_wait, res.t_consume);
+                    "upload+parse submit (incl. waits for the device) %.3f s\n", f.fsize / 1e9, text_total / 1e9, (unsigned long long)nchunks, blocks.size(),
+            f.g.threads, f.g.slots, res.t_wait, res.t_consume);
   if (res.end == mgc::ChunkRingResult::ALLOC_FAILED) { set_err(&s->err, "mgc_push_text_bgzf_file: pinned buffers: out of memory"); (void)mgc_end_text(s); return MGC_ENOMEM; }
-  if (res.end == mgc::ChunkRingResult::FILL_FAILED) {
-    // what the file has put into the stream is taken back (as for a file that stops being strict FASTQ), unless part of it already went
-    // into a counted batch
-    const unsigned long long bb = (unsigned long long)res.detail;
-    rc = mgc::text_rollback(s);
-    if (rc == MGC_EINVAL) set_err(&s->err, "'%s': BGZF block %llu failed to inflate after part of the file was counted (input larger than one batch)", path, bb);
-    if (rc != MGC_OK) return rc;
-    set_err(&s->err, "'%s': BGZF block %llu failed to inflate (corrupt file)", path, bb);
-    return MGC_EFORMAT;
-  }
+  if (res.end == mgc::ChunkRingResult::FILL_FAILED) return BgzfFile::refuse_block(s, path, res.detail);
   if (res.end == mgc::ChunkRingResult::CONSUMER_STOPPED) rc = res.detail;
   const int rc_end = mgc_end_text(s);                           // closes the file in every case (rolls it back on MGC_EFORMAT)
   return rc != MGC_OK ? rc : rc_end;
@@ -257,38 +277,12 @@ extern "C" int mgc_push_text_bgzf_file(mgc_session *s, const char *path, int for
 // every base (meryl_seq.cpp) is one host thread reading 36 bytes per record.
 extern "C" int mgc_push_bam_file(mgc_session *s, const char *path, int threads) {
   if (!s || !path) return MGC_EINVAL;
-  uint64_t fsize = 0;
-  const int fd = open_regular(&s->err, "mgc_push_bam_file", path, "regular BGZF file", 28, &fsize);
-  if (fd < 0) return MGC_EINVAL;
-  const unsigned char *map = reinterpret_cast<const unsigned char *>(mmap(nullptr, fsize, PROT_READ, MAP_SHARED, fd, 0));
-  if (map == MAP_FAILED) { close(fd); set_err(&s->err, "mgc_push_bam_file: mmap of '%s' failed: %s", path, strerror(errno)); return MGC_EINVAL; }
-  std::vector<z_stream> zs;                                     // one inflater per worker thread, n_z of them set up
-  int n_z = 0;
-  auto release = [&]() { for (int t = 0; t < n_z; t++) inflateEnd(&zs[t]); munmap(const_cast<unsigned char *>(map), fsize); close(fd); };
-  const mgc::BgzfPlan plan = mgc::bgzf_plan_chunks(map, fsize, mgc_session::TEXT_CHUNK);
-  const std::vector<mgc::BgzfBlock> &blocks = plan.blocks;
-  if (plan.bad != mgc::BGZF_BLOCK) {
-    release();
-    if (plan.bad == mgc::BGZF_BAD_ISIZE) set_err(&s->err, "'%s': corrupt BGZF block at offset %zu (ISIZE %u)", path, (size_t)plan.bad_off, plan.bad_isize);
-    else set_err(&s->err, "'%s': not a BGZF block at offset %zu (plain gzip data, or a truncated file)", path, (size_t)plan.bad_off);
-    return MGC_EFORMAT;
-  }
-  const uint64_t nchunks = plan.chunks.size();
-  const mgc::ChunkRingGeometry g = mgc::chunk_ring_geometry(threads, nchunks, mgc_session::TEXT_RING_MAX);
-  zs.resize(g.threads);
-  while (n_z < g.threads && inflateInit2(&zs[n_z], -15) == Z_OK) n_z++;
-  if (n_z < g.threads) { release(); set_err(&s->err, "zlib: inflateInit2 failed"); return MGC_ENOMEM; }
-  int rc = mgc_begin_bam(s);
-  if (rc != MGC_OK) { release(); return rc; }
+  BgzfFile f;
+  int rc = f.open(s, "mgc_push_bam_file", path, threads);
+  if (rc != MGC_OK) return rc;
+  rc = mgc_begin_bam(s);
+  if (rc != MGC_OK) return rc;
 
-  auto fill = [&](int t, uint64_t c, char *dst, int *bad_block) -> int64_t {
-    size_t at = 0;
-    for (size_t i = plan.chunks[c].first; i < plan.chunks[c].last; i++) {
-      if (!mgc::bgzf_inflate_block(zs[t], map + blocks[i].off, blocks[i], reinterpret_cast<unsigned char *>(dst) + at)) { *bad_block = (int)i; return -1; }
-      at += blocks[i].isize;
-    }
-    return (int64_t)at;
-  };
   uint64_t bam_total = 0;
   bool refused = false;
   auto consume = [&](uint64_t, const char *p, size_t len) {
@@ -298,23 +292,15 @@ extern "C" int mgc_push_bam_file(mgc_session *s, const char *path, int threads) 
     if (r == mgc::BAM_REFUSED) refused = true;
     return r;
   };
-  const mgc::ChunkRingResult res = run_session_ring(s, nchunks, g, fill, consume);
+  const uint64_t nchunks = f.plan.chunks.size();
+  const mgc::ChunkRingResult res = run_session_ring(s, nchunks, f.g, [&f](int t, uint64_t c, char *dst, int *bad) { return f.fill(t, c, dst, bad); }, consume);
   mgc::text_drain(s);                                           // the last uploads still read from the ring
-  release();
   if (getenv("MGC_IO_TRACE"))
     fprintf(stderr, "[io] BAM file %.2f GB -> %.2f GB of records in %llu chunks (%zu blocks), %d inflaters, ring %d: waiting for the inflaters %.3f s, "
-                    "walk %.3f s (%llu records), upload+decode submit (incl. the walk and waits for the device) %.3f s\n", fsize / 1e9, bam_total / 1e9,
-            (unsigned long long)nchunks, blocks.size(), g.threads, g.slots, res.t_wait, s->tr_bam_walk, (unsigned long long)s->bam_walker.records(), res.t_consume);
+                    "walk %.3f s (%llu records), upload+decode submit (incl. the walk and waits for the device) %.3f s\n", f.fsize / 1e9, bam_total / 1e9,
+            (unsigned long long)nchunks, f.plan.blocks.size(), f.g.threads, f.g.slots, res.t_wait, s->tr_bam_walk, (unsigned long long)s->bam_walker.records(), res.t_consume);
   if (res.end == mgc::ChunkRingResult::ALLOC_FAILED) { set_err(&s->err, "mgc_push_bam_file: pinned buffers: out of memory"); (void)mgc::text_rollback(s); return MGC_ENOMEM; }
-  if (res.end == mgc::ChunkRingResult::FILL_FAILED) {
-    // what the file has put into the stream is taken back, unless part of it already went into a counted batch
-    const unsigned long long bb = (unsigned long long)res.detail;
-    rc = mgc::text_rollback(s);
-    if (rc == MGC_EINVAL) set_err(&s->err, "'%s': BGZF block %llu failed to inflate after part of the file was counted (input larger than one batch)", path, bb);
-    if (rc != MGC_OK) return rc;
-    set_err(&s->err, "'%s': BGZF block %llu failed to inflate (corrupt file)", path, bb);
-    return MGC_EFORMAT;
-  }
+  if (res.end == mgc::ChunkRingResult::FILL_FAILED) return BgzfFile::refuse_block(s, path, res.detail);
   if (refused) return mgc::bam_refuse(s, path);
   if (res.end == mgc::ChunkRingResult::CONSUMER_STOPPED) { (void)mgc::text_rollback(s); return res.detail; }
   return mgc::bam_end(s, path);                                 // a stream that ends inside a record is refused here, by the file's name
@@ -381,11 +367,6 @@ extern "C" int mgc_push_text_gzip_file(mgc_session *s, const char *path, int for
     begun = r == MGC_OK;
     return r;
   };
-  auto alloc = [s]() -> char * {
-    char *p = nullptr;
-    (void)hipSetDevice(s->device);
-    return hipHostMalloc(reinterpret_cast<void **>(&p), mgc_session::TEXT_CHUNK, hipHostMallocDefault) == hipSuccess ? p : nullptr;
-  };
   auto consume = [&](const mgc::GzPieceView &v) -> int {
     if (!begun) {
       if (v.n_symbols) return MGC_EINVAL;                       // (cannot be: nothing precedes the first text)
@@ -394,7 +375,7 @@ extern "C" int mgc_push_text_gzip_file(mgc_session *s, const char *path, int for
           if (v.ends[i].crc != 0 || v.ends[i].isize != 0) {
             char msg[120];
             snprintf(msg, sizeof(msg), "CRC32 / ISIZE mismatch (an empty member, trailer at compressed offset %llu)", (unsigned long long)v.ends[i].comp_off);
-            s->gz_verdict = msg; refused = true;
+            s->gz.verdict = msg; refused = true;
             return mgc::GZIP_REFUSED;
           }
         mgc::text_drain(s);
@@ -407,7 +388,7 @@ extern "C" int mgc_push_text_gzip_file(mgc_session *s, const char *path, int for
     if (r == mgc::GZIP_REFUSED) refused = true;
     return r;
   };
-  const mgc::GzResult res = mgc::gz_run(map, fsize, opt, s->text_ring, alloc, consume);
+  const mgc::GzResult res = mgc::gz_run(map, fsize, opt, s->in.file_slots, slot_alloc(s), consume);
   if (begun && !refused && res.end == mgc::GzResult::DONE && mgc::gzip_finish(s) != MGC_OK) refused = true;
   mgc::text_drain(s);                                           // the last uploads still read from the ring
   release();
@@ -435,8 +416,8 @@ extern "C" int mgc_push_text_gzip_file(mgc_session *s, const char *path, int for
     set_err(&s->err, "'%s': %s", path, why);
     return MGC_EFORMAT;
   }
-  if (refused && !begun) { set_err(&s->err, "'%s': %s", path, s->gz_verdict.c_str()); return MGC_EFORMAT; }
-  if (refused) return mgc::gzip_refuse(s, path, s->gz_verdict.c_str());
+  if (refused && !begun) { set_err(&s->err, "'%s': %s", path, s->gz.verdict.c_str()); return MGC_EFORMAT; }
+  if (refused) return mgc::gzip_refuse(s, path, s->gz.verdict.c_str());
   if (res.end == mgc::GzResult::CONSUMER_STOPPED) {             // a HIP error, or the worker thread's
     rc = res.detail;
     if (begun) (void)mgc::text_rollback(s);
