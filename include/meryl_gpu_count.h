@@ -745,7 +745,9 @@ typedef struct mgc_profile {
    * the end of the last count kernel to the end of the last packing launch */
   uint32_t early_pack_files, early_pack_deferred;
   int32_t  probe_file;             /* the file that was counted first to choose the others' plan (probe_ratio); -1: no probe ran */
-  uint32_t reserved_;
+  uint32_t wide_digit_widths;      /* whole-key files on the high-digit-first passes (wide_msd_files), ORed over them: bit b set: a HIGH digit of b
+                                    * bits (the plan's pass_bits[1]); bit 16 + b: a LOW digit of b bits (pass_bits[0]).  `compress`: the ten-bit
+                                    * field of a dense-rank digit counts as 10 */
   /* gigantic sub-buckets (above 65536 keys: cut into slices, the slices' pairs merged; the dense ones counted by 64 ranges of the suffix
    * space), summed over the files of the count -- which path ran, counted on the device:
    *   huge_cut, huge_slices   sub-buckets cut and the slices planned for them (MGC_HUGE_SLICES=0: both stay 0, and so does huge_dense)

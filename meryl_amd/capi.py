@@ -210,7 +210,7 @@ class Profile(ctypes.Structure):
         ("early_pack_files", ctypes.c_uint32),
         ("early_pack_deferred", ctypes.c_uint32),
         ("probe_file", ctypes.c_int32),
-        ("reserved_", ctypes.c_uint32),
+        ("wide_digit_widths", ctypes.c_uint32),
         ("huge_cut", ctypes.c_uint32),
         ("huge_slices", ctypes.c_uint32),
         ("huge_dense", ctypes.c_uint32),

@@ -670,6 +670,7 @@ int Count::group_file(uint32_t b) {
       x.passes = 2;
       x.k96_passes = x.k96;
       prof.wide_msd_files++;
+      prof.wide_digit_widths |= (1u << x.sp.pass_bits[1]) | (1u << (16 + x.sp.pass_bits[0]));
       break;
     }
     x.kind = Group::SORT;
