@@ -522,9 +522,26 @@ int mgc_result_out_of_core(const mgc_session *s);
  * does not hold -- the file's output is then already rolled back and the caller feeds the file through
  * mgc_push_bases instead (include/meryl_seq.h reads multi-line FASTQ).  Text input is batched like pushed bases
  * (a batch may be cut inside a file: if such a file is refused AFTER part of it was counted, mgc_end_text returns
- * MGC_EINVAL instead of MGC_EFORMAT -- nothing can be rolled back then); it may be mixed with mgc_push_bases. */
+ * MGC_EINVAL instead of MGC_EFORMAT -- nothing can be rolled back then); it may be mixed with mgc_push_bases.
+ *
+ * SAM text (MGC_TEXT_SAM; also what `samtools view -h` makes of a CRAM): the SEQ column is extracted on the device.  A LINE START is a
+ * byte that begins the file or follows '\n'.
+ *   line start '\n'   an empty line: emits nothing.
+ *   line start '@'    a header line: emits nothing through its '\n', whatever it holds (tabs, any length).
+ *   line start '\r'   the file is REFUSED (the host reader skips such bytes before it decides a line's kind; the device does not).
+ *   anything else     an alignment line.  A byte's column is the number of '\t' before it in the line.  The bytes of column 9 that are
+ *                     not '\t' '\n' '\r' '*' are emitted as they are, nothing else of the line is (columns 10 and up -- QUAL, aux
+ *                     fields, any number of tabs -- are ignored), and the line's '\n' emits one '.'.  A '\n' with fewer than 9 tabs
+ *                     before it in the line REFUSES the file, as the host reader does ("fewer than 10 columns").
+ * A last alignment line without '\n' emits its column-9 bytes if it reaches that column, and nothing (no error) if it does not;
+ * mgc_end_text adds its usual single '.'.  No FLAG filtering, no reverse-complementing: SEQ as stored, as the BAM route and the host
+ * reader give it.  Refusal works as for FASTQ: mgc_end_text reads the device's error word, rolls the file's output back and returns
+ * MGC_EFORMAT (MGC_EINVAL after part of the file was counted); mgc_last_error names the reason.  For every accepted file the stream
+ * equals msr_load_stream's for the same bytes (SEQ + '.' per record) plus the end-of-file breaker.  SAM is never sniffed (format 0
+ * tells FASTA from FASTQ only: a leading '@' means FASTQ); it is asked for by name wherever a format is taken. */
 #define MGC_TEXT_FASTA 1
 #define MGC_TEXT_FASTQ 2
+#define MGC_TEXT_SAM   3
 int mgc_reserve_text(mgc_session *s, uint64_t text_bytes);       /* optional: expected total, avoids regrowth */
 int mgc_begin_text(mgc_session *s, int format);
 int mgc_push_text(mgc_session *s, const char *text, size_t len);
@@ -535,7 +552,7 @@ int mgc_push_text_file(mgc_session *s, const char *path, int format, int reader_
 /* A byte window [begin, end) of such a file -- begin at a record start (mgc_text_record_start), end = where the next reader
  * begins (or anything >= the file size): the ranks of a node count read disjoint windows of the input, each through its
  * own device's link.  mgc_text_record_start: the first record start at or after `offset` (FASTA: a line starting with
- * '>'; FASTQ: a line starting with '@' whose next-but-one line starts with '+'); the file size when there is none;
+ * '>'; FASTQ: a line starting with '@' whose next-but-one line starts with '+'; SAM: any line start); the file size when there is none;
  * format 0 = sniff.  Host I/O only, no device. */
 int mgc_push_text_file_range(mgc_session *s, const char *path, int format, int reader_threads, uint64_t begin, uint64_t end);
 int mgc_text_record_start(const char *path, int format, uint64_t offset, uint64_t *start);
@@ -568,6 +585,13 @@ typedef struct {
 } mgc_gzip_info;
 int mgc_push_text_gzip_file(mgc_session *s, const char *path, int format, int threads, mgc_gzip_info *info);
 int mgc_is_gzip_file(const char *path);
+
+/* The parse alone, device to device, for tests and benchmarks: one whole file of text_bytes at d_text (any alignment) -> its base
+ * stream at d_out (room for text_bytes), without mgc_end_text's final '.', on `stream`.  d_workspace: 256-byte aligned,
+ * mgc_dev_text_parse_workspace_bytes(text_bytes) bytes; afterwards its first 8 bytes hold the stream's length (uint64) and the
+ * uint32 at byte 24 is the error word (not 0: mgc_end_text would refuse the file). */
+uint64_t mgc_dev_text_parse_workspace_bytes(uint64_t text_bytes);
+int mgc_dev_text_parse(const uint8_t *d_text, uint64_t text_bytes, int format, void *d_workspace, uint8_t *d_out, void *stream);
 
 /* The device side of the above, on buffers of the caller's (any alignment; `stream`: a hipStream_t, NULL: the default stream).
  * mgc_dev_gzip_resolve: d_text[i] = d_symbols[i] < 256 ? d_symbols[i] : d_window_in[d_symbols[i] - 0x8000] for i < n_symbols

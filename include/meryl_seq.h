@@ -32,7 +32,7 @@ typedef struct msr_reader msr_reader;
 
 #define MSR_FORMAT_FASTX 0   /* FASTA / FASTQ text (msr_read_text may hand it to the device parser) */
 #define MSR_FORMAT_BAM   1
-#define MSR_FORMAT_SAM   2
+#define MSR_FORMAT_SAM   2   /* SAM text, also what `samtools view -h` makes of a CRAM (msr_read_text hands it to the device parser as MGC_TEXT_SAM) */
 
 /* name "-" reads stdin.  NULL on failure; text via msr_last_error().  A BGZF file (bgzip output, every BAM) is
  * inflated block-parallel by up to 16 threads (MERYL_BGZF_THREADS=n; 0 = zlib's single stream). */
@@ -52,7 +52,7 @@ int msr_load_stream(msr_reader *r, char *buf, uint64_t max_length, uint64_t *len
 
 /* The file's TEXT (decompressed, otherwise untouched), up to max_length bytes per call; 0 at end of input, <0 on a
  * read error.  For callers that parse on the device (mgc_push_text, include/meryl_gpu_count.h); not to be mixed with
- * msr_load_bases on the same reader. */
+ * msr_load_bases on the same reader.  FASTA / FASTQ and SAM text; a BAM reader is refused. */
 int64_t msr_read_text(msr_reader *r, char *buf, uint64_t max_length);
 
 /* MSR_FORMAT_*: told from the content (BAM magic, @HD line) or the name (.sam). */

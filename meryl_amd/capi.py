@@ -21,7 +21,7 @@ SYMBOLS = (
     "mgc_dev_partition_workspace_bytes", "mgc_dev_kmer_histogram", "mgc_dev_kmer_partition",
     "mgc_dev_sort_workspace_bytes", "mgc_dev_radix_sort", "mgc_dev_radix_group", "mgc_dev_kmer_histogram_fine",
     "mgc_dev_rle_workspace_bytes", "mgc_dev_rle_count", "mgc_dev_rle_emit", "mgc_dev_block_offsets",
-    "mgc_open", "mgc_close", "mgc_last_error", "mgc_push_bases", "mgc_push_bases_device", "mgc_staged_bases", "mgc_reserve_text", "mgc_begin_text", "mgc_push_text", "mgc_end_text", "mgc_push_text_file", "mgc_push_text_file_range", "mgc_text_record_start", "mgc_push_text_bgzf_file", "mgc_is_bgzf_file", "mgc_begin_bam", "mgc_push_bam", "mgc_end_bam", "mgc_push_bam_file", "mgc_dev_bam_decode", "mgc_push_text_gzip_file", "mgc_is_gzip_file", "mgc_dev_gzip_resolve", "mgc_dev_crc32_pieces", "mgc_count", "mgc_count_partitioned", "mgc_count_buckets", "mgc_count_buckets_into", "mgc_copy_result_device",
+    "mgc_open", "mgc_close", "mgc_last_error", "mgc_push_bases", "mgc_push_bases_device", "mgc_staged_bases", "mgc_reserve_text", "mgc_begin_text", "mgc_push_text", "mgc_end_text", "mgc_push_text_file", "mgc_push_text_file_range", "mgc_text_record_start", "mgc_push_text_bgzf_file", "mgc_is_bgzf_file", "mgc_begin_bam", "mgc_push_bam", "mgc_end_bam", "mgc_push_bam_file", "mgc_dev_bam_decode", "mgc_dev_text_parse", "mgc_dev_text_parse_workspace_bytes", "mgc_push_text_gzip_file", "mgc_is_gzip_file", "mgc_dev_gzip_resolve", "mgc_dev_crc32_pieces", "mgc_count", "mgc_count_partitioned", "mgc_count_buckets", "mgc_count_buckets_into", "mgc_copy_result_device",
     "mgc_get_result_info", "mgc_get_result_device", "mgc_copy_result", "mgc_finish", "mgc_finish_labelled",
     "mgc_set_profiling", "mgc_get_profile", "mgc_dev_synth_reads", "mgc_dev_synth_reads_ex", "mgc_version",
     "mgc_dev_merge_workspace_bytes", "mgc_dev_merge_count", "mgc_dev_merge_count_values", "mgc_dev_merge_emit",
@@ -373,6 +373,8 @@ BLOCK_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctyp
 
 
 OK, EINVAL, ENOMEM, EHIP, ESTATE, EUNSUPPORTED, ETIMEOUT, EFORMAT = 0, -1, -2, -3, -4, -5, -6, -7
+TEXT_FASTA, TEXT_FASTQ, TEXT_SAM = 1, 2, 3            # MGC_TEXT_* (mgc_begin_text and the text-file readers)
+TEXT_FORMATS = {"fasta": TEXT_FASTA, "fastq": TEXT_FASTQ, "sam": TEXT_SAM}
 
 
 class MgcError(RuntimeError):
@@ -512,6 +514,8 @@ def lib():
     sig("mgc_end_bam", i32, vp)
     sig("mgc_push_bam_file", i32, vp, ctypes.c_char_p, i32)
     sig("mgc_dev_bam_decode", i32, vp, u64, vp, u64, u64, vp, vp)
+    sig("mgc_dev_text_parse_workspace_bytes", u64, u64)
+    sig("mgc_dev_text_parse", i32, vp, u64, i32, vp, vp, vp)
     sig("mgc_push_text_gzip_file", i32, vp, ctypes.c_char_p, i32, i32, ctypes.POINTER(GzipInfo))
     sig("mgc_is_gzip_file", i32, ctypes.c_char_p)
     sig("mgc_dev_gzip_resolve", i32, vp, u64, vp, u64, vp, u32, vp, vp, vp)

@@ -492,12 +492,12 @@ class Session:
                    self._h)
 
     def push_text(self, text, fmt, pieces=None):
-        """One whole sequence file as raw text (bytes/str), parsed on the device.  fmt: "fasta" | "fastq".
+        """One whole sequence file as raw text (bytes/str), parsed on the device.  fmt: "fasta" | "fastq" | "sam".
         pieces: optional chunk size (the text is fed in pieces of that many bytes -- tests use odd sizes).
         Raises MgcError(code MGC_EFORMAT) if the device parser refuses the file (its output is rolled back)."""
         b = text.encode("ascii") if isinstance(text, str) else bytes(text)
         L = capi.lib()
-        capi.check(L.mgc_begin_text(self._h, 1 if fmt == "fasta" else 2), "mgc_begin_text", self._h)
+        capi.check(L.mgc_begin_text(self._h, capi.TEXT_FORMATS[fmt]), "mgc_begin_text", self._h)
         step = pieces or max(len(b), 1)
         for i in range(0, len(b), step):
             piece = b[i:i + step]
@@ -521,13 +521,14 @@ class Session:
         """One whole BGZF BAM file, inflated by `threads` threads (0: default) into the upload ring, decoded on the device."""
         capi.check(capi.lib().mgc_push_bam_file(self._h, os.fsencode(path), int(threads)), "mgc_push_bam_file", self._h)
 
-    def push_text_gzip_file(self, path, threads=0):
-        """One whole FASTA / FASTQ file in plain gzip (not BGZF), inflated by `threads` threads (0: default) from guessed block
-        starts into the upload ring; the device resolves what they could not know and checks every member's CRC-32.  Returns
-        mgc_gzip_info as a dict.  Raises MgcError(code MGC_EFORMAT) for a file that is not gzip, is damaged or is not strict
-        FASTA / FASTQ (its output is rolled back)."""
+    def push_text_gzip_file(self, path, threads=0, fmt=None):
+        """One whole FASTA / FASTQ / SAM file in plain gzip (not BGZF), inflated by `threads` threads (0: default) from guessed
+        block starts into the upload ring; the device resolves what they could not know and checks every member's CRC-32.  fmt:
+        None (FASTA or FASTQ, told from the first byte) | "fasta" | "fastq" | "sam".  Returns mgc_gzip_info as a dict.  Raises
+        MgcError(code MGC_EFORMAT) for a file that is not gzip, is damaged or is not strict FASTA / FASTQ / SAM (its output is
+        rolled back)."""
         info = capi.GzipInfo()
-        capi.check(capi.lib().mgc_push_text_gzip_file(self._h, os.fsencode(path), 0, int(threads), ctypes.byref(info)),
+        capi.check(capi.lib().mgc_push_text_gzip_file(self._h, os.fsencode(path), capi.TEXT_FORMATS[fmt] if fmt else 0, int(threads), ctypes.byref(info)),
                    "mgc_push_text_gzip_file", self._h)
         return {n: int(getattr(info, n)) for n, _ in capi.GzipInfo._fields_}
 

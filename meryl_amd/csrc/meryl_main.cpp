@@ -136,7 +136,7 @@ struct Globals {
 void usage(const char *prog) {
   fprintf(stderr,
           "usage: %s [k=<K>] [memory=<GB>] [threads=<T>] [gpus=<N>] [n=<kmers>] [compress] [-l <label-bits>] [-C] [-Q] [-V]\n"
-          "          count|count-forward|count-reverse [label=#<n>] <reads.fa|fq[.gz]|sam|bam> ... output <database.meryl>\n"
+          "          count|count-forward|count-reverse [label=#<n>] <reads.fa|fq[.gz]|sam[.gz]|bam|cram> ... output <database.meryl>\n"
           "       %s print <database.meryl | [operation]>\n"
           "       %s histogram|statistics <database.meryl | [operation]>\n"
           "       %s dumpIndex <database.meryl>\n"
@@ -248,9 +248,10 @@ static bool is_regular_file(const std::string &name) { struct stat st; return st
 
 // Input: the file's raw text goes to the device and is parsed there (mgc_push_text*; a plain gzip file's is inflated by several threads
 // and resolved there, mgc_push_text_gzip_file); a BGZF BAM file goes there as its
-// inflated bytes and its SEQ fields are decoded there (mgc_push_bam_file); files the device routes refuse (multi-line
-// FASTQ, a damaged BAM ...), SAM, BAM in plain gzip or on stdin and MERYL_HOST_PARSER=1 take the host state machine of
-// meryl_seq.cpp.  Returns the bytes / bases taken in (reported with -V -V).
+// inflated bytes and its SEQ fields are decoded there (mgc_push_bam_file); SAM text -- a .sam, a .sam.gz, stdin with an @HD line, a
+// CRAM through `samtools view -h` -- takes the same text routes as MGC_TEXT_SAM and its SEQ column is extracted there; files the
+// device routes refuse (multi-line FASTQ, a damaged BAM, a SAM line with fewer than 10 columns or "\r\n" blank lines ...), BAM in
+// plain gzip or on stdin and MERYL_HOST_PARSER=1 take the host state machine of meryl_seq.cpp.  Returns the bytes / bases taken in (reported with -V -V).
 int g_inflate_threads = 16;                                  // threads= of the command line: the BGZF inflaters (readers of plain text: at most 16)
 bool g_gzip_parallel = true;                                 // false under gpus=N: every rank reads its files with the host reader's one gzread thread
 uint64_t load_inputs(mgc_session *s, const std::vector<InputPiece> &pieces, int reader_threads) {
@@ -291,12 +292,15 @@ uint64_t load_inputs(mgc_session *s, const std::vector<InputPiece> &pieces, int 
       if (rc == MGC_OK && stat(name.c_str(), &fst) == 0) total_bases += (uint64_t)fst.st_size * 3;   // (a guess, as for bgzip'd text)
       continue;
     }
-    if (msr_format(r) != MSR_FORMAT_FASTX) { msr_close(r); load_on_host(name); continue; }   // SAM text, BAM in plain gzip or on stdin: decoded on the host
-    if (name != "-" && !has_compressed_suffix(name)) {
+    if (msr_format(r) == MSR_FORMAT_BAM) { msr_close(r); load_on_host(name); continue; }     // BAM in plain gzip or on stdin: decoded on the host
+    const bool sam = msr_format(r) == MSR_FORMAT_SAM;                                        // asked for by name: a leading '@' would be sniffed as FASTQ
+    const int fmt = sam ? MGC_TEXT_SAM : 0;
+    const bool cram = name.size() > 5 && name.compare(name.size() - 5, 5, ".cram") == 0;     // its SAM text comes through a pipe: the generic loop below
+    if (name != "-" && !has_compressed_suffix(name) && !cram && !(sam && !is_regular_file(name))) {
       // plain text: the library reads the file itself, several threads straight into its pinned upload buffers
       msr_close(r);
-      const int rc = whole ? mgc_push_text_file(s, name.c_str(), 0, reader_threads)
-                           : mgc_push_text_file_range(s, name.c_str(), 0, reader_threads, pc.begin, pc.end);
+      const int rc = whole ? mgc_push_text_file(s, name.c_str(), fmt, reader_threads)
+                           : mgc_push_text_file_range(s, name.c_str(), fmt, reader_threads, pc.begin, pc.end);
       if (rc == MGC_EFORMAT && whole) load_on_host(name);
       else if (rc == MGC_EFORMAT) die("ERROR: '%s' is not strict four-line FASTQ / FASTA: it cannot be read in windows by several ranks (gpus=1 reads it)", name.c_str());
       else if (rc != MGC_OK) die("ERROR: %s", mgc_last_error(s));
@@ -305,24 +309,24 @@ uint64_t load_inputs(mgc_session *s, const std::vector<InputPiece> &pieces, int 
       else total_bases += pc.end - pc.begin;
       continue;
     }
-    if (name != "-" && whole && mgc_is_bgzf_file(name.c_str()) && !getenv("MERYL_BGZF_GENERIC")) {
+    if (name != "-" && whole && !cram && mgc_is_bgzf_file(name.c_str()) && !getenv("MERYL_BGZF_GENERIC")) {
       // BGZF (bgzip'd FASTA / FASTQ): the library maps the file and inflates its blocks with several threads straight into its pinned
       // upload buffers (MERYL_BGZF_GENERIC=1: through the generic reader below, as every other compressed input)
       msr_close(r);
       const char *bt = getenv("MERYL_BGZF_THREADS");
-      const int rc = mgc_push_text_bgzf_file(s, name.c_str(), 0, bt ? atoi(bt) : std::max(reader_threads, g_inflate_threads));
+      const int rc = mgc_push_text_bgzf_file(s, name.c_str(), fmt, bt ? atoi(bt) : std::max(reader_threads, g_inflate_threads));
       if (rc == MGC_EFORMAT) load_on_host(name);
       else if (rc != MGC_OK) die("ERROR: %s", mgc_last_error(s));
       struct stat fst;
       if (stat(name.c_str(), &fst) == 0) total_bases += (uint64_t)fst.st_size * 3;             // (text bytes, as the reference guesses them for .gz)
       continue;
     }
-    if (name != "-" && whole && g_gzip_parallel && is_regular_file(name) && mgc_is_gzip_file(name.c_str()) && !getenv("MERYL_GZIP_GENERIC")) {
+    if (name != "-" && whole && g_gzip_parallel && !cram && is_regular_file(name) && mgc_is_gzip_file(name.c_str()) && !getenv("MERYL_GZIP_GENERIC")) {
       // plain gzip: the library maps the file, several threads inflate it from guessed block starts straight into its pinned upload
       // buffers, the device resolves what they could not know and checks the CRC (MERYL_GZIP_GENERIC=1: one gzread thread, below)
       msr_close(r);
       const char *gt = getenv("MERYL_GZIP_THREADS");
-      const int rc = mgc_push_text_gzip_file(s, name.c_str(), 0, gt ? atoi(gt) : std::max(reader_threads, g_inflate_threads), nullptr);
+      const int rc = mgc_push_text_gzip_file(s, name.c_str(), fmt, gt ? atoi(gt) : std::max(reader_threads, g_inflate_threads), nullptr);
       if (rc == MGC_EFORMAT) load_on_host(name);
       else if (rc != MGC_OK) die("ERROR: %s", mgc_last_error(s));
       struct stat fst;
@@ -334,6 +338,10 @@ uint64_t load_inputs(mgc_session *s, const std::vector<InputPiece> &pieces, int 
       const int64_t got = msr_read_text(r, text.data(), text.size());
       if (got < 0) die("ERROR: %s", msr_last_error());
       if (got == 0) break;
+      if (!begun && sam) {
+        if (mgc_begin_text(s, MGC_TEXT_SAM) != MGC_OK) die("ERROR: %s", mgc_last_error(s));
+        begun = true;
+      }
       if (!begun) {
         int64_t p = 0;
         while (p < got && (text[p] == '\n' || text[p] == '\r' || text[p] == ' ' || text[p] == '\t')) p++;

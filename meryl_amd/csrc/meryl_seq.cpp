@@ -342,8 +342,8 @@ extern "C" int msr_format(const msr_reader *r) { return r ? r->format : -1; }
 
 extern "C" int64_t msr_read_text(msr_reader *r, char *buf, uint64_t max_length) {
   if (!r || !buf) return -1;
-  if (r->format != MSR_FORMAT_FASTX) { seq_err("msr_read_text: '" + r->name + "' is SAM/BAM: use msr_load_bases"); return -1; }
-  if (r->st != msr_reader::AT_RECORD_START || r->in_sequence) {
+  if (r->format == MSR_FORMAT_BAM) { seq_err("msr_read_text: '" + r->name + "' is BAM: use msr_load_bases"); return -1; }
+  if (r->st != msr_reader::AT_RECORD_START || r->in_sequence || (r->format == MSR_FORMAT_SAM && (!r->line_start || r->sam_field != 0))) {
     seq_err("msr_read_text: '" + r->name + "': raw and parsed reads cannot be mixed on one reader");
     return -1;
   }

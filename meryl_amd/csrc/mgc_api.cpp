@@ -605,6 +605,19 @@ extern "C" int mgc_dev_bam_decode(const uint8_t *d_piece, uint64_t piece_bytes, 
   return MGC_OK;
 }
 
+extern "C" uint64_t mgc_dev_text_parse_workspace_bytes(uint64_t text_bytes) { return 256 + mgc::text_parse_workspace_bytes(text_bytes); }
+
+extern "C" int mgc_dev_text_parse(const uint8_t *d_text, uint64_t text_bytes, int format, void *d_workspace, uint8_t *d_out, void *stream) {
+  if ((!d_text && text_bytes) || !d_workspace || !d_out || (reinterpret_cast<uintptr_t>(d_workspace) & 255u) ||
+      (format != MGC_TEXT_FASTA && format != MGC_TEXT_FASTQ && format != MGC_TEXT_SAM)) return MGC_EINVAL;
+  static_assert(sizeof(uint64_t) * 2 + sizeof(uint32_t) * 4 <= 256, "the parse state lies in the workspace's first 256 bytes");
+  if (mgc::text_parse_state_bytes() > 256) return MGC_EINVAL;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  HIP_TRY((mgc_session *)nullptr, mgc::launch_text_file_op(d_workspace, d_out, 3, st));
+  HIP_TRY((mgc_session *)nullptr, mgc::launch_text_parse(d_text, text_bytes, format, d_workspace, static_cast<uint8_t *>(d_workspace) + 256, d_out, st));
+  return MGC_OK;
+}
+
 extern "C" int mgc_dev_gzip_resolve(uint8_t *d_text, uint64_t text_bytes, const uint16_t *d_symbols, uint64_t n_symbols, const uint8_t *d_window_in,
                                     uint32_t window_valid, uint8_t *d_window_out, uint32_t *d_error, void *stream) {
   if ((!d_text && text_bytes) || (!d_symbols && n_symbols) || (n_symbols && !d_error) || n_symbols > text_bytes || window_valid > mgc::GZ_WINDOW ||

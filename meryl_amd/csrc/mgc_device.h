@@ -396,11 +396,11 @@ size_t     hpc_workspace_bytes(uint64_t n);
 // compressed length lands in the first uint64 of the workspace
 hipError_t launch_homopoly_compress(const uint8_t *d_in, uint64_t n, uint8_t *d_out, void *d_ws, hipStream_t st);
 
-// ---- FASTA / FASTQ text -> base stream (mgc_parse.hip) ----------------------------------------
+// ---- FASTA / FASTQ / SAM text -> base stream (mgc_parse.hip) ----------------------------------
 size_t     text_parse_state_bytes();
 size_t     text_parse_workspace_bytes(uint64_t n);            // for one chunk of n text bytes
-// appends the bases of one text chunk to d_out at the running length kept in d_state
-hipError_t launch_text_parse(const uint8_t *d_text, uint64_t n, int fastq, void *d_state, void *d_ws, uint8_t *d_out, hipStream_t st);
+// appends the bases of one text chunk to d_out at the running length kept in d_state; format: MGC_TEXT_FASTA / _FASTQ / _SAM
+hipError_t launch_text_parse(const uint8_t *d_text, uint64_t n, int format, void *d_state, void *d_ws, uint8_t *d_out, hipStream_t st);
 // ---- BAM records -> base stream (mgc_bam.hip) ----
 // One piece of an inflated BAM stream (piece_bytes at d_piece) and the segments the host walker made of it (n_segments of 16
 // bytes, mgc::BamSegment of mgc_bam_walk.hpp, tiling [0, out_total)): writes out_total bytes at d_out (any alignment) -- the SEQ

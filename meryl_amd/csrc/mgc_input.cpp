@@ -5,6 +5,7 @@
 // differs.  The whole-file readers on top of it are mgc_textfile.cpp's.
 #include "../../include/meryl_gpu_count.h"
 #include "mgc_device.h"
+#include "mgc_sam_fsm.hpp"
 #include "mgc_session.hpp"
 
 #include <algorithm>
@@ -278,7 +279,7 @@ extern "C" int mgc_reserve_text(mgc_session *s, uint64_t text_bytes) {
 }
 
 extern "C" int mgc_begin_text(mgc_session *s, int format) {
-  if (!s || (format != MGC_TEXT_FASTA && format != MGC_TEXT_FASTQ)) return MGC_EINVAL;
+  if (!s || (format != MGC_TEXT_FASTA && format != MGC_TEXT_FASTQ && format != MGC_TEXT_SAM)) return MGC_EINVAL;
   if (s->text_open) { set_err(&s->err, "mgc_begin_text: the previous file was not ended"); return MGC_ESTATE; }
   int rc = text_setup(s);
   if (rc != MGC_OK) return rc;
@@ -339,7 +340,7 @@ static int queue_piece(mgc_session *s, PieceSlot &sl, const char *pinned_src, si
 }
 
 static int launch_parse(mgc_session *s, const uint8_t *d_in, size_t piece, uint8_t *d_stage, hipStream_t st) {
-  HIP_TRY(s, mgc::launch_text_parse(d_in, piece, s->text_format == MGC_TEXT_FASTQ, s->buf[mgc_session::B_TEXT_STATE].p,
+  HIP_TRY(s, mgc::launch_text_parse(d_in, piece, s->text_format, s->buf[mgc_session::B_TEXT_STATE].p,
                                     s->buf[mgc_session::B_TEXT_WS].p, d_stage, st));
   return MGC_OK;
 }
@@ -404,6 +405,16 @@ extern "C" int mgc_end_text(mgc_session *s) {
   HostParseState h;
   int rc = resolve_length(s, &h);
   if (rc != MGC_OK) return rc;
+  if (h.error && s->text_format == MGC_TEXT_SAM) {
+    const char *why = (h.error & mgc::SAM_ERR_CR_LINE_START) ? "line starts with a carriage return" : "alignment line with fewer than 10 columns";
+    rc = mgc::text_rollback(s);
+    if (rc == MGC_EINVAL)
+      set_err(&s->err, "the SAM file is refused (%s) after part of it was counted (input larger than one batch): "
+                       "convert it, or feed it through mgc_push_bases from the start", why);
+    if (rc != MGC_OK) return rc;
+    set_err(&s->err, "the SAM file is refused: %s: feed it through mgc_push_bases (meryl_seq.h reader)", why);
+    return MGC_EFORMAT;
+  }
   if (h.error) {
     rc = mgc::text_rollback(s);
     if (rc == MGC_EINVAL)

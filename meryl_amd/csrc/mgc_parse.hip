@@ -1,4 +1,4 @@
-// mgc_parse.hip -- FASTA / FASTQ text -> base stream, on the device (gfx950).
+// mgc_parse.hip -- FASTA / FASTQ / SAM text -> base stream, on the device (gfx950).
 //
 // Replaces, for text that is already in HBM, the byte-at-a-time host loader
 //   dnaSeqFile::loadBases (absent submodule) behind merylInput::loadBases, src/meryl/merylInput.C:245-271
@@ -9,13 +9,18 @@
 // appear).  FASTA: any line structure.  FASTQ: strict four-line records (the device cannot know where a
 // multi-line record ends without the sequential state machine); every '@' / '+' line start is validated and
 // a violation sets an error flag -- the caller then re-reads that file with the host parser (meryl_seq.cpp).
+// SAM: the SEQ column (the bytes after the ninth tab) of every alignment line and one '.' for the line's '\n'; '@' header lines and
+// empty lines emit nothing; a line that ends before column 9 or starts with '\r' sets the error word (mgc_sam_fsm.hpp has the
+// contract and the state functions, which a host program shares).  A line of a long read spans several tiles, so the entry state of
+// a tile (header, column 0 .. 9, past column 9) is a segmented scan: the state at the last line start plus the tabs since.
 //
 // A finite-state parse made parallel the usual way: tiles of 16 KiB; pass 1 summarises every tile as a
-// function of the (two / four) states it can be entered in, a single workgroup composes the summaries into
+// function of the (two / four / twelve) states it can be entered in, a single workgroup composes the summaries into
 // each tile's entry state and output offset, pass 2 re-parses with that knowledge and writes.  The running
 // state (output length, line type, "previous byte was a newline", error) lives in device memory, so
 // consecutive chunks of a file are parsed without any host round trip.
 #include "mgc_device.h"
+#include "mgc_sam_fsm.hpp"
 
 namespace mgc {
 
@@ -32,8 +37,9 @@ struct ParseState {             // device-resident, one per session
   u64 file_start_len;           // out_len when the current file began (mgc_text_rollback)
   u32 state;                    // FASTA: 0 = in a header (or before the first one), 1 = in sequence lines
                                 // FASTQ: type (0..3) of the line the next byte belongs to
+                                // SAM: column 0 .. 9, SAM_PAST or SAM_HEADER of the next byte (mgc_sam_fsm.hpp)
   u32 prev_nl;                  // the previous byte was '\n' (the next byte starts a line)
-  u32 error;                    // FASTQ structure violated
+  u32 error;                    // FASTQ structure violated; SAM: SAM_ERR_* bits
   u32 pad;
 };
 
@@ -46,6 +52,8 @@ struct TileSummary {            // 16 x u32
   u32 eA, eB;                   // FASTA: bytes emitted regardless of the entry state / only if entered in sequence state
   u32 last_nl;                  // the tile's last byte is '\n'
 };
+
+static_assert(sizeof(SamTileSummary) <= sizeof(TileSummary), "a SAM tile summary lies in a TileSummary's place in the workspace");
 
 struct TileInfo { u64 out_off; u32 state_in; u32 pad; };
 
@@ -83,6 +91,24 @@ __device__ __forceinline__ u32 pblock_excl_max(u32 v, u32 *s_tmp, u32 *total) {
   u32 up = __shfl_up(x, 1);
   if (p_lane() == 0) up = 0;
   return base > up ? base : up;
+}
+
+// exclusive running composition of SAM state functions (sam_fn_then; 0 = the identity)
+__device__ __forceinline__ u32 pblock_excl_fn(u32 v, u32 *s_tmp, u32 *total) {
+  constexpr int NW = PT_BLOCK / 64;
+  u32 x = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) { u32 y = __shfl_up(x, d); if ((int)p_lane() >= d) x = sam_fn_then(y, x); }
+  __syncthreads();
+  if (p_lane() == 63) s_tmp[p_wave()] = x;
+  __syncthreads();
+  u32 base = 0, tot = 0;
+#pragma unroll
+  for (int i = 0; i < NW; i++) { u32 t = s_tmp[i]; if (i < (int)p_wave()) base = sam_fn_then(base, t); tot = sam_fn_then(tot, t); }
+  *total = tot;
+  u32 up = __shfl_up(x, 1);
+  if (p_lane() == 0) up = 0;
+  return sam_fn_then(base, up);
 }
 
 // What every pass needs to know about this thread's 16 bytes.
@@ -306,13 +332,133 @@ void text_emit_kernel(const u8 *__restrict__ text, u64 n, const ParseState *__re
     if ((emit >> j) & 1u) *o++ = ((dot >> j) & 1u) ? (u8)'.' : t.b[j];
 }
 
+// ---- SAM: the three passes over mgc_sam_fsm.hpp's summaries ----------------------------------------------------------------------
+// the summary of this thread's bytes
+__device__ __forceinline__ SamSummary<SamSegPacked> sam_thread_summary(const ThreadText &t) {
+  SamSummariser<SamSegPacked> r;
+  r.begin((t.ls & 1u) != 0u);
+#pragma unroll
+  for (int j = 0; j < PT_BYTES; j++) if ((t.valid >> j) & 1u) r.feed(t.b[j]);
+  r.finish();
+  return r.S;
+}
+
+// pass 1: the tile's summary is the composition of its threads' (sam_compose), the threads adding their part at once
+__global__ __launch_bounds__(PT_BLOCK)
+void sam_summary_kernel(const u8 *__restrict__ text, u64 n, const ParseState *__restrict__ ps, SamTileSummary *__restrict__ sums) {
+  __shared__ u8  s_last[PT_BLOCK];
+  __shared__ u32 s_tmp[PT_BLOCK / 64 + 1];
+  __shared__ u32 s_acc[16];                                // 0 .. 9: seg, 10: rest, 11: flags, 12: the head's tabs
+  const u64 tile = blockIdx.x, tile_base = tile * (u64)PT_TILE;
+  if (threadIdx.x < 16) s_acc[threadIdx.x] = 0;
+  ThreadText t;
+  load_thread_text(text, n, tile_base, ps->prev_nl, s_last, t);      // contains a barrier: s_acc is cleared
+  const SamSummary<SamSegPacked> mine = sam_thread_summary(t);
+  u32 tot;
+  const u32 before = pblock_excl_fn(mine.fn, s_tmp, &tot);
+  if (mine.flags & SAM_S_NONEMPTY) {
+    if (before & SAM_FN_CONST) {                           // behind the tile's head: entered in a known state
+      u32 err = 0;
+      const u32 e = sam_emit_for_entry(mine, before & 15u, &err);
+      if (e)   atomicAdd(&s_acc[10], e);
+      if (err) atomicOr(&s_acc[11], err << SAM_S_ERR_SHIFT);
+    } else {                                               // in the head, `before` tabs into it
+#pragma unroll
+      for (u32 i = 0; i < 10u; i++) {
+        const u32 c = mine.seg.get(i);
+        if (c && before + i <= SAM_SEQ_COLUMN) atomicAdd(&s_acc[before + i], c);
+      }
+      if (mine.rest) atomicAdd(&s_acc[10], mine.rest);
+      const u32 fl = mine.flags & (SAM_S_HEAD_NL | (~0u << SAM_S_ERR_SHIFT));
+      if (fl) atomicOr(&s_acc[11], fl);
+      if (mine.fn & SAM_FN_CONST) s_acc[12] = sam_tabs_on(before, mine.tabs);     // the one thread in which the head ends
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    SamTileSummary s;
+    for (int i = 0; i < 10; i++) s.seg.c[i] = s_acc[i];
+    s.tabs = (tot & SAM_FN_CONST) ? s_acc[12] : tot;
+    s.rest = s_acc[10];
+    s.fn = tot;
+    const u64 last = (tile_base + PT_TILE <= n) ? tile_base + PT_TILE - 1 : n - 1;
+    s.flags = s_acc[11] | SAM_S_NONEMPTY | (text[last] == '\n' ? SAM_S_LAST_NL : 0u);
+    sums[tile] = s;
+  }
+}
+
+__global__ __launch_bounds__(PT_BLOCK)
+void sam_compose_kernel(const SamTileSummary *__restrict__ sums, u64 ntiles, ParseState *__restrict__ ps, TileInfo *__restrict__ info) {
+  __shared__ u32 s_tmp[PT_BLOCK / 64 + 1];
+  __shared__ u64 s_tmp64[PT_BLOCK / 64 + 1];
+  u64 out = 0;                                             // relative to ps->out_len
+  u32 state = ps->state, err = 0, last_nl = ps->prev_nl;
+  for (u64 base = 0; base < ntiles; base += PT_BLOCK) {
+    const u64 t = base + threadIdx.x;
+    const bool live = t < ntiles;
+    u32 tot;
+    const u32 before = pblock_excl_fn(live ? sums[t].fn : 0u, s_tmp, &tot);
+    const u32 st_in = sam_fn_apply(before, state);
+    const u64 emit = live ? (u64)sam_emit_for_entry(sums[t], st_in, &err) : 0ull;
+    state = sam_fn_apply(tot, state);
+    u64 tot64;
+    const u64 off = pblock_excl_sum<u64>(emit, s_tmp64, &tot64);
+    if (live) { TileInfo ti; ti.out_off = out + off; ti.state_in = st_in; ti.pad = 0; info[t] = ti; }
+    out += tot64;
+    if (base + PT_BLOCK >= ntiles) {                       // the last tile's trailing byte
+      const u64 lt = ntiles - 1 - base;
+      __syncthreads();
+      if (threadIdx.x == lt) s_tmp[0] = (sums[t].flags & SAM_S_LAST_NL) ? 1u : 0u;
+      __syncthreads();
+      last_nl = s_tmp[0];
+    }
+  }
+  // every thread saw the same totals except `err`
+  __syncthreads();
+  if (threadIdx.x == 0) s_tmp[0] = 0;
+  __syncthreads();
+  if (err) atomicOr(&s_tmp[0], err);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    TileInfo fin; fin.out_off = out; fin.state_in = state; fin.pad = last_nl | (s_tmp[0] << 1);
+    info[ntiles] = fin;
+  }
+}
+
+__global__ __launch_bounds__(PT_BLOCK)
+void sam_emit_kernel(const u8 *__restrict__ text, u64 n, const ParseState *__restrict__ ps, const TileInfo *__restrict__ info,
+                     u8 *__restrict__ out) {
+  __shared__ u8  s_last[PT_BLOCK];
+  __shared__ u32 s_tmp[PT_BLOCK / 64 + 1];
+  const u64 tile = blockIdx.x, tile_base = tile * (u64)PT_TILE;
+  const TileInfo ti = info[tile];
+  ThreadText t;
+  load_thread_text(text, n, tile_base, ps->prev_nl, s_last, t);
+  u32 tot;
+  const u32 before = pblock_excl_fn(sam_thread_summary(t).fn, s_tmp, &tot);
+  u32 st = sam_fn_apply(before, ti.state_in), emit = 0, dot = 0, err = 0;
+#pragma unroll
+  for (int j = 0; j < PT_BYTES; j++) {
+    if (!((t.valid >> j) & 1u)) continue;
+    u32 o;
+    st = sam_step(st, t.b[j], (t.ls >> j) & 1u, &o, &err);
+    if (o != SAM_OUT_NONE) emit |= 1u << j;
+    if (o == SAM_OUT_DOT)  dot |= 1u << j;
+  }
+  const u32 off = pblock_excl_sum<u32>(__popc(emit), s_tmp, &tot);
+  u8 *o = out + ps->out_len + ti.out_off + off;
+#pragma unroll
+  for (int j = 0; j < PT_BYTES; j++)
+    if ((emit >> j) & 1u) *o++ = ((dot >> j) & 1u) ? (u8)'.' : t.b[j];
+}
+
 // after pass 2 of a chunk: fold the chunk's totals into the running state
 __global__ void text_commit_kernel(ParseState *ps, const TileInfo *info, u64 ntiles) {
   const TileInfo fin = info[ntiles];
   ps->out_len += fin.out_off;
   ps->state    = fin.state_in;
   ps->prev_nl  = fin.pad & 1u;
-  ps->error   |= (fin.pad >> 1) & 1u;
+  ps->error   |= fin.pad >> 1;
 }
 
 // file boundaries: begin (format-specific entry state), end (breaker), rollback (drop the file's output)
@@ -345,14 +491,19 @@ size_t text_parse_workspace_bytes(uint64_t n) {
   return (size_t)(ntiles + 1) * (sizeof(TileSummary) + sizeof(TileInfo)) + 256;
 }
 
-hipError_t launch_text_parse(const uint8_t *d_text, uint64_t n, int fastq, void *d_state, void *d_ws, uint8_t *d_out, hipStream_t st) {
+hipError_t launch_text_parse(const uint8_t *d_text, uint64_t n, int format, void *d_state, void *d_ws, uint8_t *d_out, hipStream_t st) {
   if (n == 0) return hipSuccess;
   const uint64_t ntiles = (n + PT_TILE - 1) / PT_TILE;
   ParseState  *ps   = reinterpret_cast<ParseState *>(d_state);
   TileSummary *sums = reinterpret_cast<TileSummary *>(d_ws);
   TileInfo    *info = reinterpret_cast<TileInfo *>(reinterpret_cast<unsigned char *>(d_ws) +
                                                    (((ntiles + 1) * sizeof(TileSummary) + 255) / 256) * 256);
-  if (fastq) {
+  if (format == 3) {                                        // MGC_TEXT_SAM
+    SamTileSummary *ssums = reinterpret_cast<SamTileSummary *>(d_ws);
+    hipLaunchKernelGGL(sam_summary_kernel, dim3((uint32_t)ntiles), dim3(PT_BLOCK), 0, st, d_text, (u64)n, ps, ssums);
+    hipLaunchKernelGGL(sam_compose_kernel, dim3(1), dim3(PT_BLOCK), 0, st, ssums, (u64)ntiles, ps, info);
+    hipLaunchKernelGGL(sam_emit_kernel, dim3((uint32_t)ntiles), dim3(PT_BLOCK), 0, st, d_text, (u64)n, ps, info, d_out);
+  } else if (format == 2) {                                 // MGC_TEXT_FASTQ
     hipLaunchKernelGGL(text_summary_kernel<true>, dim3((uint32_t)ntiles), dim3(PT_BLOCK), 0, st, d_text, (u64)n, ps, sums);
     hipLaunchKernelGGL(text_compose_kernel<true>, dim3(1), dim3(PT_BLOCK), 0, st, sums, (u64)ntiles, ps, info);
     hipLaunchKernelGGL(text_emit_kernel<true>, dim3((uint32_t)ntiles), dim3(PT_BLOCK), 0, st, d_text, (u64)n, ps, info, d_out);

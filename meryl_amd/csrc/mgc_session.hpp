@@ -155,7 +155,7 @@ struct mgc_session {
   // both: the cut inside a file, the rollback point in the device's parse state
   bool        text_open = false, text_cut_in_file = false;
   int         text_format = 0;
-  static constexpr int TEXT_BAM = 3;
+  static constexpr int TEXT_BAM = -1;                      // (not one of MGC_TEXT_FASTA / _FASTQ / _SAM)
   static constexpr int TEXT_RING_MAX = mgc::InputRing::FILE_SLOTS_MAX;
   mgc::InputRing in;                                      // the two piece slots every route's pieces go through (mgc_input.hpp)
   // BAM: pieces are inflated BAM bytes, walked on the host, decoded on the device (mgc_bam.hip) from a segment table that travels with the piece

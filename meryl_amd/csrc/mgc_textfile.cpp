@@ -1,4 +1,4 @@
-// mgc_textfile.cpp -- whole FASTA / FASTQ files into a session's base stream (include/meryl_gpu_count.h): plain files read
+// mgc_textfile.cpp -- whole FASTA / FASTQ / SAM files into a session's base stream (include/meryl_gpu_count.h): plain files read
 // with pread, BGZF files inflated, by several threads STRAIGHT into a ring of pinned buffers (mgc_chunk_ring.hpp) that the
 // calling thread uploads and parses in file order; BGZF BAM files likewise, walked and decoded instead of parsed; plain gzip files
 // through the pump of mgc_gzip_par.hpp, whose pieces the device resolves (mgc_gzip.hip).  The session is reached through mgc_begin_text /
@@ -41,7 +41,8 @@ char first_text_byte(const unsigned char *p, size_t n) {
 }
 int format_of(char c) { return c == '@' ? MGC_TEXT_FASTQ : (c == '>' ? MGC_TEXT_FASTA : 0); }
 
-// format of a FASTA / FASTQ file from its first byte that is not white space; 0: neither
+// format of a FASTA / FASTQ file from its first byte that is not white space; 0: neither (SAM is never sniffed: its header lines
+// start with '@' as FASTQ records do, so it is asked for by name)
 int sniff_text_format(int fd, char *first) {
   unsigned char head[4096];
   const ssize_t got = pread(fd, head, sizeof(head), 0);
@@ -58,19 +59,20 @@ template <class Fill, class Consume>
 mgc::ChunkRingResult run_session_ring(mgc_session *s, uint64_t n_chunks, const mgc::ChunkRingGeometry &g, Fill fill, Consume consume) {
   return mgc::run_chunk_ring(n_chunks, s->in.file_slots, g.slots, g.threads, 2, slot_alloc(s), fill, consume);
 }
+bool known_format(int format) { return format == MGC_TEXT_FASTA || format == MGC_TEXT_FASTQ || format == MGC_TEXT_SAM; }
 }  // namespace
 
 // First record start at or after `offset` of a FASTA / FASTQ file -- where a reader that takes the file from the middle
 // may begin (the ranks of a node count read disjoint byte windows of the input, each through its own device's link).
 // FASTA: a line that starts with '>'.  FASTQ (four-line records): a line that starts with '@' whose next-but-one line starts
-// with '+' -- a quality line may start with '@', but then the line two below it is a sequence line, never '+'.
+// with '+' -- a quality line may start with '@', but then the line two below it is a sequence line, never '+'.  SAM: any line start.
 extern "C" int mgc_text_record_start(const char *path, int format, uint64_t offset, uint64_t *start) {
   if (!path || !start) return MGC_EINVAL;
   uint64_t size = 0;
   const int fd = open_regular(nullptr, "mgc_text_record_start", path, "regular file", 0, &size);
   if (fd < 0) return MGC_EINVAL;
   if (format == 0) format = sniff_text_format(fd, nullptr);
-  if (format != MGC_TEXT_FASTA && format != MGC_TEXT_FASTQ) { close(fd); set_err(nullptr, "'%s' is neither FASTA nor FASTQ", path); return MGC_EFORMAT; }
+  if (!known_format(format)) { close(fd); set_err(nullptr, "'%s' is neither FASTA nor FASTQ", path); return MGC_EFORMAT; }
   if (offset == 0 || offset >= size) { close(fd); *start = offset >= size ? size : 0; return MGC_OK; }
   // line starts from offset - 1 on: the byte before a line start is '\n'
   std::vector<char> buf(1u << 20);
@@ -89,6 +91,7 @@ extern "C" int mgc_text_record_start(const char *path, int format, uint64_t offs
       char c;
       if (i + 1 < got) c = buf[i + 1];
       else if (pread(fd, &c, 1, (off_t)line) != 1) break;
+      if (format == MGC_TEXT_SAM) { answer = line; found = true; continue; }
       if (format == MGC_TEXT_FASTA) { if (c == '>') { answer = line; found = true; } continue; }
       ls.push_back(line); lc.push_back(c);
       const size_t m = ls.size();
@@ -119,6 +122,7 @@ extern "C" int mgc_push_text_file_range(mgc_session *s, const char *path, int fo
     format = sniff_text_format(fd, &c);
     if (!format) { close(fd); set_err(&s->err, "'%s' is neither FASTA nor FASTQ (record starts with '%c')", path, c); return MGC_EFORMAT; }
   }
+  if (!known_format(format)) { close(fd); return MGC_EINVAL; }
   if (range_end > file_size) range_end = file_size;
   if (range_begin > range_end) range_begin = range_end;
   const uint64_t size = range_end - range_begin;            // every chunk offset below is relative to the window
@@ -145,9 +149,9 @@ extern "C" int mgc_push_text_file_range(mgc_session *s, const char *path, int fo
   close(fd);
   if (res.end == mgc::ChunkRingResult::ALLOC_FAILED) { set_err(&s->err, "mgc_push_text_file: pinned buffers: out of memory"); (void)mgc_end_text(s); return MGC_ENOMEM; }
   if (getenv("MGC_IO_TRACE"))
-    fprintf(stderr, "[io] text file %.2f GB in %llu chunks, %d readers, ring %d: waiting for readers %.3f s, upload+parse submit (incl. waits "
+    fprintf(stderr, "[io] %s file %.2f GB in %llu chunks, %d readers, ring %d: waiting for readers %.3f s, upload+parse submit (incl. waits "
                     "for the device) %.3f s; readers: %.3f s in pread (%.1f GB/s each), %.3f s waiting for a free slot\n",
-            size / 1e9, (unsigned long long)nchunks, g.threads, g.slots, res.t_wait, res.t_consume, res.t_fill,
+            format == MGC_TEXT_SAM ? "SAM" : "text", size / 1e9, (unsigned long long)nchunks, g.threads, g.slots, res.t_wait, res.t_consume, res.t_fill,
             res.t_fill > 0 ? size / 1e9 / res.t_fill : 0.0, res.t_slot_wait);
   if (res.end == mgc::ChunkRingResult::CONSUMER_STOPPED) rc = res.detail;
   if (res.end == mgc::ChunkRingResult::FILL_FAILED) {
@@ -261,8 +265,8 @@ extern "C" int mgc_push_text_bgzf_file(mgc_session *s, const char *path, int for
   const mgc::ChunkRingResult res = run_session_ring(s, nchunks, f.g, [&f](int t, uint64_t c, char *dst, int *bad) { return f.fill(t, c, dst, bad); }, consume);
   mgc::text_drain(s);                                           // the last uploads still read from the ring
   if (getenv("MGC_IO_TRACE"))
-    fprintf(stderr, "[io] BGZF file %.2f GB -> %.2f GB of text in %llu chunks (%zu blocks), %d inflaters, ring %d: waiting for the inflaters %.3f s, "
-                    "upload+parse submit (incl. waits for the device) %.3f s\n", f.fsize / 1e9, text_total / 1e9, (unsigned long long)nchunks, blocks.size(),
+    fprintf(stderr, "[io] BGZF %sfile %.2f GB -> %.2f GB of text in %llu chunks (%zu blocks), %d inflaters, ring %d: waiting for the inflaters %.3f s, "
+                    "upload+parse submit (incl. waits for the device) %.3f s\n", format == MGC_TEXT_SAM ? "SAM " : "", f.fsize / 1e9, text_total / 1e9, (unsigned long long)nchunks, blocks.size(),
             f.g.threads, f.g.slots, res.t_wait, res.t_consume);
   if (res.end == mgc::ChunkRingResult::ALLOC_FAILED) { set_err(&s->err, "mgc_push_text_bgzf_file: pinned buffers: out of memory"); (void)mgc_end_text(s); return MGC_ENOMEM; }
   if (res.end == mgc::ChunkRingResult::FILL_FAILED) return BgzfFile::refuse_block(s, path, res.detail);
@@ -345,7 +349,7 @@ extern "C" int mgc_push_text_gzip_file(mgc_session *s, const char *path, int for
   if (map == MAP_FAILED) { close(fd); set_err(&s->err, "mgc_push_text_gzip_file: mmap of '%s' failed: %s", path, strerror(errno)); return MGC_EINVAL; }
   auto release = [&]() { munmap(const_cast<unsigned char *>(map), fsize); close(fd); };
   if (!mgc::gz_is_gzip(map, fsize)) { release(); set_err(&s->err, "'%s' is not a gzip file", path); return MGC_EFORMAT; }
-  if (format != 0 && format != MGC_TEXT_FASTA && format != MGC_TEXT_FASTQ) { release(); return MGC_EINVAL; }
+  if (format != 0 && !known_format(format)) { release(); return MGC_EINVAL; }
 
   mgc::GzOptions opt;
   opt.span = env_u64("MGC_GZIP_SPAN", GZIP_SPAN_DEFAULT, 4096, 1ull << 40);
@@ -397,10 +401,10 @@ extern "C" int mgc_push_text_gzip_file(mgc_session *s, const char *path, int for
     info->text_bytes = res.info.text_bytes; info->symbol_bytes = res.info.symbol_bytes; info->cuts = res.info.cuts;
   }
   if (getenv("MGC_IO_TRACE"))
-    fprintf(stderr, "[io] gzip file %.2f GB -> %.2f GB of text (%.2f GB of symbols) in %llu chunks (%llu confirmed, %llu discarded, %llu cuts), %d inflaters, "
+    fprintf(stderr, "[io] gzip %sfile %.2f GB -> %.2f GB of text (%.2f GB of symbols) in %llu chunks (%llu confirmed, %llu discarded, %llu cuts), %d inflaters, "
                     "ring %d: waiting for the inflaters %.3f s, upload+resolve+parse submit (incl. waits for the device) %.3f s; inflaters: finder %.3f s, "
                     "inflate %.3f s, waiting for a candidate %.3f s, waiting for a free slot %.3f s; of the submit: symbol copy %.3f s, CRC fold %.3f s, "
-                    "waiting for the device %.3f s\n", fsize / 1e9, res.info.text_bytes / 1e9,
+                    "waiting for the device %.3f s\n", format == MGC_TEXT_SAM ? "SAM " : "", fsize / 1e9, res.info.text_bytes / 1e9,
             res.info.symbol_bytes / 1e9, (unsigned long long)res.info.chunks, (unsigned long long)res.info.confirmed, (unsigned long long)res.info.discarded,
             (unsigned long long)res.info.cuts, opt.threads, opt.n_slots, res.t_wait, res.t_consume, res.t_find, res.t_inflate, res.t_confirm, res.t_slot_wait, s->tr_gz_copy, s->tr_gz_collect, s->tr_gz_wait);
   if (res.end == mgc::GzResult::ALLOC_FAILED) {
