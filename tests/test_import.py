@@ -10,27 +10,16 @@ import subprocess
 import numpy as np
 import pytest
 
+from import_helpers import assert_same_dirs, codes_to_keys, pick, prefixes, rand_kmer, read_db, with_batch
+
 pytestmark = pytest.mark.gpu
 
 W_PREFIX = 10
 MODE_NAMES = ("canonical", "forward", "reverse")
-CODE = {"A": 0, "C": 1, "T": 2, "G": 3}
 LETTERS = np.frombuffer(b"ACTG", dtype=np.uint8)          # code -> letter
 
 
 # ---- the model -------------------------------------------------------------------------------------------------------
-def pick(word, k, mode):
-    """the k-mer a word stands for, as a Python int: its last k bases, packed; canonical / forward / reverse complement"""
-    w = word[-k:].upper()
-    f = 0
-    for ch in w:
-        f = (f << 2) | CODE[ch]
-    r = 0
-    for ch in reversed(w):
-        r = (r << 2) | (CODE[ch] ^ 2)
-    return f if mode == 1 else r if mode == 2 else min(f, r)
-
-
 def model_records(text, k, mode):
     """[(k-mer, value)] in input order: meryl-import.C:175-219 restated"""
     persistent = 1
@@ -58,20 +47,10 @@ def model_sums(records):
     return lo, hi, np.array([acc[x] for x in keys], dtype=np.uint32)
 
 
-def prefixes(lo, hi, k):
-    w_data = 2 * k - W_PREFIX
-    if w_data >= 64:
-        return (hi >> np.uint64(w_data - 64)) if w_data > 64 else hi.copy()
-    p = lo >> np.uint64(w_data)
-    if 2 * k > 64:
-        p = p | (hi << np.uint64(64 - w_data))
-    return p
-
-
 def host_write(path, lo, hi, cn, k):
     from meryl_amd import db
     w_data = 2 * k - W_PREFIX
-    starts = np.searchsorted(prefixes(lo, hi, k), np.arange(0, (1 << W_PREFIX) + 1, dtype=np.uint64))
+    starts = np.searchsorted(prefixes(lo, hi, k, W_PREFIX), np.arange(0, (1 << W_PREFIX) + 1, dtype=np.uint64))
     mlo = np.uint64((1 << w_data) - 1) if w_data < 64 else np.uint64(0xFFFFFFFFFFFFFFFF)
     mhi = np.uint64((1 << (w_data - 64)) - 1) if w_data > 64 else np.uint64(0)
     w = db.Writer(path, k, W_PREFIX)
@@ -79,24 +58,6 @@ def host_write(path, lo, hi, cn, k):
         s, e = int(starts[p]), int(starts[p + 1])
         w.add_block(p, lo[s:e] & mlo, cn[s:e], (hi[s:e] & mhi) if w_data > 64 else None)
     w.close()
-
-
-def assert_same_dirs(a, b):
-    fa, fb = sorted(os.listdir(a)), sorted(os.listdir(b))
-    assert fa == fb and len(fa) == 129, (len(fa), len(fb))
-    for f in fa:
-        assert open(os.path.join(a, f), "rb").read() == open(os.path.join(b, f), "rb").read(), f
-
-
-def read_db(path):
-    from meryl_amd import db
-    r = db.Reader(path)
-    try:
-        lo, hi, cn = r.read_all()
-        hv, ho = r.histogram()
-    finally:
-        r.close()
-    return lo, hi, cn, hv, ho
 
 
 def assert_db_equals(path, lo, hi, cn, k):
@@ -110,10 +71,6 @@ def assert_db_equals(path, lo, hi, cn, k):
 
 
 # ---- inputs ----------------------------------------------------------------------------------------------------------
-def rand_kmer(rng, k):
-    return "".join("ACGT"[i] for i in rng.integers(0, 4, k))
-
-
 def messy_text(rng, k, n_records=1200, pool=350, hash_until=1.0):
     """Shuffled records over a small pool (well above 30 % repeats), `#` lines (only in the first `hash_until` of the lines),
     records without a value before and after the first `#`, blank lines, CRLF, tabs and runs of spaces, lower case, words
@@ -168,31 +125,6 @@ def messy_text(rng, k, n_records=1200, pool=350, hash_until=1.0):
     return text
 
 
-def codes_to_keys(codes, mode):
-    """codes: uint8[n, k] (A0 C1 T2 G3) -> (lo, hi) uint64 of the canonical / forward / reverse k-mer"""
-    n, k = codes.shape
-
-    def pack(c):
-        lo = np.zeros(n, np.uint64)
-        hi = np.zeros(n, np.uint64)
-        for i in range(k):
-            sh = 2 * (k - 1 - i)
-            if sh >= 64:
-                hi |= c[:, i].astype(np.uint64) << np.uint64(sh - 64)
-            else:
-                lo |= c[:, i].astype(np.uint64) << np.uint64(sh)
-        return lo, hi
-
-    flo, fhi = pack(codes)
-    rlo, rhi = pack(codes[:, ::-1] ^ 2)
-    if mode == 1:
-        return flo, fhi
-    if mode == 2:
-        return rlo, rhi
-    f_small = (fhi < rhi) | ((fhi == rhi) & (flo < rlo))
-    return np.where(f_small, flo, rlo), np.where(f_small, fhi, rhi)
-
-
 def fixed_width_text(codes, values, digits):
     """`KMER<TAB>value<LF>` rows of one width, as a uint8 matrix (vectorised)"""
     n, k = codes.shape
@@ -240,20 +172,6 @@ def long_segment_input(rng, k=21):
 def clis(native_lib):
     from meryl_amd import build
     return build.build_cli(), build.build_import_cli()
-
-
-def with_batch(nbytes):
-    class _Env:
-        def __enter__(self):
-            self.old = os.environ.get("MGC_IMPORT_BATCH")
-            os.environ["MGC_IMPORT_BATCH"] = str(int(nbytes))
-
-        def __exit__(self, *a):
-            if self.old is None:
-                del os.environ["MGC_IMPORT_BATCH"]
-            else:
-                os.environ["MGC_IMPORT_BATCH"] = self.old
-    return _Env()
 
 
 # ---- 1. round trip -----------------------------------------------------------------------------------------------------

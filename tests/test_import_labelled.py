@@ -15,27 +15,17 @@ import subprocess
 import numpy as np
 import pytest
 
+import import_helpers
+from import_helpers import assert_same_dirs, pick, prefixes, rand_kmer, with_batch
+
 pytestmark = pytest.mark.gpu
 
 W_PREFIX = 6
-CODE = {"A": 0, "C": 1, "T": 2, "G": 3}
 LETTERS = np.frombuffer(b"ACTG", dtype=np.uint8)          # code -> letter
 M32 = 0xFFFFFFFF
 
 
 # ---- the model -------------------------------------------------------------------------------------------------------
-def pick(word, k, mode):
-    """the k-mer a word stands for, as a Python int: its last k bases, packed; canonical / forward / reverse complement"""
-    w = word[-k:].upper()
-    f = 0
-    for ch in w:
-        f = (f << 2) | CODE[ch]
-    r = 0
-    for ch in reversed(w):
-        r = (r << 2) | (CODE[ch] ^ 2)
-    return f if mode == 1 else r if mode == 2 else min(f, r)
-
-
 def decode_integer(word):
     """reference.rst:615-617: 123 / 123d, <hex>h, <octal>o, <binary>b; the last byte decides"""
     base = {"h": 16, "o": 8, "b": 2, "d": 10}.get(word[-1])
@@ -72,20 +62,10 @@ def model_sums(records, lw):
     return lo, hi, np.array([acc[x][0] for x in keys], dtype=np.uint32), np.array([acc[x][1] for x in keys], dtype=np.uint64)
 
 
-def prefixes(lo, hi, k):
-    w_data = 2 * k - W_PREFIX
-    if w_data >= 64:
-        return (hi >> np.uint64(w_data - 64)) if w_data > 64 else hi.copy()
-    p = lo >> np.uint64(w_data)
-    if 2 * k > 64:
-        p = p | (hi << np.uint64(64 - w_data))
-    return p
-
-
 def host_write(path, lo, hi, cn, lab, k, lw):
     from meryl_amd import db
     w_data = 2 * k - W_PREFIX
-    starts = np.searchsorted(prefixes(lo, hi, k), np.arange(0, (1 << W_PREFIX) + 1, dtype=np.uint64))
+    starts = np.searchsorted(prefixes(lo, hi, k, W_PREFIX), np.arange(0, (1 << W_PREFIX) + 1, dtype=np.uint64))
     mlo = np.uint64((1 << w_data) - 1) if w_data < 64 else np.uint64(0xFFFFFFFFFFFFFFFF)
     mhi = np.uint64((1 << (w_data - 64)) - 1) if w_data > 64 else np.uint64(0)
     w = db.Writer(path, k, W_PREFIX, label_size=lw)
@@ -95,23 +75,8 @@ def host_write(path, lo, hi, cn, lab, k, lw):
     w.close()
 
 
-def assert_same_dirs(a, b):
-    fa, fb = sorted(os.listdir(a)), sorted(os.listdir(b))
-    assert fa == fb and len(fa) == 129, (len(fa), len(fb))
-    for f in fa:
-        assert open(os.path.join(a, f), "rb").read() == open(os.path.join(b, f), "rb").read(), f
-
-
 def read_db(path):
-    from meryl_amd import db
-    r = db.Reader(path)
-    try:
-        lo, hi, cn, lab = r.read_all(labels=True)
-        hv, ho = r.histogram()
-        label_size = int(r.info.label_size)
-    finally:
-        r.close()
-    return lo, hi, cn, lab, hv, ho, label_size
+    return import_helpers.read_db(path, labels=True)
 
 
 def assert_db_equals(path, lo, hi, cn, lab, k, lw):
@@ -126,10 +91,6 @@ def assert_db_equals(path, lo, hi, cn, lab, k, lw):
 
 
 # ---- inputs ----------------------------------------------------------------------------------------------------------
-def rand_kmer(rng, k):
-    return "".join("ACGT"[i] for i in rng.integers(0, 4, k))
-
-
 def number(rng, v):
     """v in one of the forms decodeInteger reads, now and then with leading zeros"""
     u = rng.random()
@@ -232,20 +193,6 @@ def check_messy(text):
     assert "\r\n" in text and "\t" in text and "   " in text and " 00" in body
 
 
-def with_batch(nbytes):
-    class _Env:
-        def __enter__(self):
-            self.old = os.environ.get("MGC_IMPORT_BATCH")
-            os.environ["MGC_IMPORT_BATCH"] = str(int(nbytes))
-
-        def __exit__(self, *a):
-            if self.old is None:
-                del os.environ["MGC_IMPORT_BATCH"]
-            else:
-                os.environ["MGC_IMPORT_BATCH"] = self.old
-    return _Env()
-
-
 @pytest.fixture(scope="module")
 def clis(native_lib):
     from meryl_amd import build
@@ -316,17 +263,9 @@ def test_parser_alone_in_four_chunks(native_lib, k, mode):
 
 
 # ---- 3. segments across workgroups, and both wraps ---------------------------------------------------------------------
-def codes_to_keys(codes, mode=0):
+def codes_to_keys(codes):
     """codes: uint8[n, k] (A0 C1 T2 G3), k <= 32 -> uint64 of the canonical k-mer"""
-    n, k = codes.shape
-
-    def pack(c):
-        lo = np.zeros(n, np.uint64)
-        for i in range(k):
-            lo |= c[:, i].astype(np.uint64) << np.uint64(2 * (k - 1 - i))
-        return lo
-    f, r = pack(codes), pack(codes[:, ::-1] ^ 2)
-    return np.minimum(f, r)
+    return import_helpers.codes_to_keys(codes, 0)[0]
 
 
 def fixed_width_text(codes, values, vdigits, labels, ldigits):
@@ -421,6 +360,43 @@ def test_sort_triples_alone(native_lib, kw, begin_bit, end_bit):
         assert np.array_equal(rk.cpu().numpy().view(np.uint64), host_keys[order][starts])
         assert np.array_equal(rv.cpu().numpy().view(np.uint32), np.add.reduceat(vals[order], starts, dtype=np.uint32))
         assert np.array_equal(rl.cpu().numpy().view(np.uint64), np.add.reduceat(labs[order], starts) & np.uint64((1 << 17) - 1))
+
+
+@pytest.mark.parametrize("lw", [1, 64])
+@pytest.mark.parametrize("pattern", ["equal", "random"])
+@pytest.mark.parametrize("kw", [1, 2])
+@pytest.mark.parametrize("n", [1, 2047, 2048, 2049, 4097])
+def test_reduce_triples_at_tile_edges(native_lib, n, kw, pattern, lw):
+    """a reduce tile holds 2048 triples: one short of it, exactly it, one more, and two tiles and one; a segment over all of them
+    (equal) and segments of about three; np.add.at in uint32 and in uint64 modulo 2^lw"""
+    import torch
+    from meryl_amd import kmer_import
+    rng = np.random.default_rng(n * 7 + kw + lw)
+    if pattern == "equal":
+        lo, hi = np.full(n, 0x123456789ABCDEF, np.uint64), np.full(n, 0x2A if kw == 2 else 0, np.uint64)
+    else:
+        distinct = max(1, n // 3)
+        pool_lo = rng.integers(0, 1 << 64, distinct, dtype=np.uint64, endpoint=False)
+        pool_hi = rng.integers(0, 1 << 64, distinct, dtype=np.uint64, endpoint=False) if kw == 2 else np.zeros(distinct, np.uint64)
+        idx = rng.integers(0, distinct, n)
+        order = np.lexsort((pool_lo[idx], pool_hi[idx]))
+        lo, hi = pool_lo[idx][order], pool_hi[idx][order]
+    vals = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    labs = rng.integers(0, 1 << 64, n, dtype=np.uint64, endpoint=False)
+    head = np.ones(n, bool)
+    head[1:] = (lo[1:] != lo[:-1]) | (hi[1:] != hi[:-1])
+    seg = np.cumsum(head) - 1
+    want_v, want_l = np.zeros(int(seg[-1]) + 1, np.uint32), np.zeros(int(seg[-1]) + 1, np.uint64)
+    np.add.at(want_v, seg, vals)
+    np.add.at(want_l, seg, labs)                                     # uint64: wraps modulo 2^64
+    if lw < 64:
+        want_l &= np.uint64((1 << lw) - 1)
+    host_keys = lo if kw == 1 else np.stack([lo, hi], axis=1)
+    rk, rv, rl = kmer_import.reduce_triples(torch.from_numpy(np.ascontiguousarray(host_keys).view(np.int64)).cuda(),
+                                            torch.from_numpy(vals.view(np.int32)).cuda(), torch.from_numpy(labs.view(np.int64)).cuda(), lw)
+    assert rk.shape[0] == want_v.size
+    assert np.array_equal(rk.cpu().numpy().view(np.uint64), host_keys[head])
+    assert np.array_equal(rv.cpu().numpy().view(np.uint32), want_v) and np.array_equal(rl.cpu().numpy().view(np.uint64), want_l)
 
 
 # ---- 5. batches --------------------------------------------------------------------------------------------------------
